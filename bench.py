@@ -31,6 +31,10 @@ Besides the headline value the line carries
   train         BASELINE config 3 (optimizer steps over an accumulation window, every rank taking part) -- `--mode train` makes it the headline;
   cpu_baseline  the CPU oracle (a port of the reference's PyTorch CPU path, oracle/conformer_oracle.py) timed on the host
                 cores of the same box on a bounded sample of the same workload (rank 0, N=1 only).
+
+--dump-outputs DIR (e.g. `--dump-outputs bench_outputs`, which git ignores) writes what the last timed step computed (rank 0) as
+DIR/<name>.npy, so that two builds can be compared output for output: the inputs and weights are seeded, identical from run to run for
+the same arguments.
 """
 import argparse
 import json
@@ -65,6 +69,12 @@ def build_encoder(device, seed=0):
     return enc.to(device)
 
 
+def forward_inputs(batch, frames, rank, device):
+    """The forward step's input: `batch` full-length utterances of synthetic 80-d fbank, seeded by the rank."""
+    x = torch.from_numpy(np.random.RandomState(1234 + rank).standard_normal((batch, frames, 80)).astype(np.float32)).to(device)
+    return x, torch.full((batch,), frames, dtype=torch.int32, device=device)
+
+
 def cpu_baseline(enc, frames, sample_batch, iters):
     """Time the CPU oracle (port of the reference CPU path) on `sample_batch` utterances; returns frames/s."""
     from oracle import conformer_oracle as O
@@ -79,6 +89,24 @@ def cpu_baseline(enc, frames, sample_batch, iters):
             O.encoder_forward(P, cfg, x, lens)
         dt = (time.perf_counter() - t0) / iters
     return sample_batch * frames / dt, dt
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each array as out_dir/<name>.npy, float64 kept, everything else as float32; at most DUMP_LIMIT_BYTES in all."""
+    def host(v):
+        v = v.detach().cpu()
+        return (v if v.dtype == torch.float64 else v.float()).contiguous().numpy()
+
+    arrays = {k: host(v) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def build_train_job(device, rank, precision, n_micro=8):
@@ -122,9 +150,10 @@ def build_train_job(device, rank, precision, n_micro=8):
     return enc, dec, tr, mbs, frames
 
 
-def train_measure(args, dist, world, rank, device, steps, warmup, precision=None):
+def train_measure(args, dist, world, rank, device, steps, warmup, precision=None, dump_dir=None):
     """K optimizer steps (2 micro-batches each: forward, CTC loss, backward, bucketed RCCL all-reduce overlapped with backward, clip, Adam),
-    timed like the forward bench.  Returns a dict for the JSON line."""
+    timed like the forward bench.  Returns a dict for the JSON line.  dump_dir: rank 0 writes the last step's mean loss and a fixed sample of
+    the updated parameters there (dump_outputs)."""
     enc, dec, tr, mbs, frames = build_train_job(device, rank, precision)
     state = {"i": 0, "valid": 0, "padded": 0, "count": False}
 
@@ -135,7 +164,7 @@ def train_measure(args, dist, world, rank, device, steps, warmup, precision=None
             for j in (2 * i, 2 * i + 1):
                 state["valid"] += frames[j % len(mbs)][0]
                 state["padded"] += frames[j % len(mbs)][1]
-        tr.step(pair)
+        state["loss"] = tr.step(pair)
         state["i"] = i + 1
 
     def barrier():
@@ -161,6 +190,12 @@ def train_measure(args, dist, world, rank, device, steps, warmup, precision=None
         valid = torch.cat([tot, tmax])
     v, padded, elapsed = (float(t) for t in valid.tolist())
     n_param = sum(p.numel() for p in tr.params)
+    if dump_dir is not None and rank == 0:
+        flat = torch.cat([p.detach().reshape(-1).float() for p in tr.params])
+        idx = np.sort(np.random.RandomState(0).choice(flat.numel(), min(flat.numel(), 1 << 20), replace=False))
+        dump_outputs(dump_dir, {"loss": state["loss"].double().reshape(1),
+                                "params_sample": flat[torch.from_numpy(idx).to(flat.device)]})
+        del flat
     return {"metric": "CTC training input frames/sec (encoder + CTC loss + backward + gradient all-reduce + clip + Adam), whole job",
             "value": round(v / elapsed, 1), "unit": "frames/s", "ms_per_step": round(elapsed / steps * 1e3, 3), "steps": steps, "warmup": warmup,
             "frames_per_step_per_gpu": round(v / steps / world, 1), "padded_frames_per_s": round(padded / elapsed, 1),
@@ -396,7 +431,12 @@ def main():
     ap.add_argument("--ramp-ms", type=float, default=150.0, help="setup: replay the step for this long before the W warm-up steps (GPU clock ramp out of idle; 0: off)")
     ap.add_argument("--no-fp16", action="store_true", help="skip the fp16 measurement that accompanies a bf16 headline")
     ap.add_argument("--no-parity", action="store_true", help="skip the in-run parity figure (2 utterances against the CPU oracle)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes what the last timed step computed as DIR/<name>.npy (forward: encoder_out, "
+                         "encoder_mask; --mode train: loss and a fixed sample of 2^20 updated parameters, params_sample)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     world = check_world(args)                            # N > 1 outside a launcher: spawns the ranks and exits with their code
     if args.selftest_cpu:
         return selftest_cpu(args)
@@ -431,7 +471,7 @@ def main():
         raise SystemExit("bench.py: process group has %d ranks, WORLD_SIZE says %d" % (rccl_ranks, world))
 
     if args.mode == "train":
-        rec = train_measure(args, dist, world, rank, device, args.steps, args.warmup, args.precision)
+        rec = train_measure(args, dist, world, rank, device, args.steps, args.warmup, args.precision, dump_dir=args.dump_outputs)
         if rank == 0:
             line = {"metric": rec["metric"], "value": rec["value"], "unit": rec["unit"], "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                     "ms_per_step": rec["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.precision,
@@ -447,8 +487,7 @@ def main():
 
     enc = build_encoder(device)
     B, T = args.batch, args.frames
-    x = torch.from_numpy(np.random.RandomState(1234 + rank).standard_normal((B, T, 80)).astype(np.float32)).to(device)
-    lens = torch.full((B,), T, dtype=torch.int32, device=device)
+    x, lens = forward_inputs(B, T, rank, device)
 
     stream = torch.cuda.Stream(device=device)
     graph = None
@@ -467,11 +506,13 @@ def main():
                 print("[bench] graph capture unavailable (%s); launching eagerly" % (str(e).splitlines()[0],), file=sys.stderr)
                 graph = None
 
+        out = {"encoder_out": y, "encoder_mask": m}      # a replay rewrites the captured outputs in place; an eager step returns new ones
+
         def step():
             if graph is not None:
                 graph.replay()
             else:
-                enc(x, lens)
+                out["encoder_out"], out["encoder_mask"] = enc(x, lens)
 
         # setup, before the W warm-up steps: bring the GPU out of idle.  From a cold start the first ~20 replays run 10 % slower (consecutive windows of
         # 20 replays: 1.378, 1.261, 1.253, 1.252 ... ms per step, scripts/probe_clock_ramp.py), so a region of 20 steps after 5 warm-up steps would
@@ -483,6 +524,8 @@ def main():
             stream.synchronize()
 
         elapsed = timed_region(step, args.steps, args.warmup, dist, lambda: torch.cuda.synchronize(device))
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, out)
 
         # ---- instrumented pass: per-kernel HIP events on the launch stream (eager launches, same K steps) ----------
         roofline = None
