@@ -20,3 +20,4 @@ from attention import (MultiHeadSelfAttentionModule, PositionalEncoding, Relativ
                        RelativePositionalEncoding)
 from convolution import ConvolutionModule, ConvolutionSubSampling  # noqa: E402,F401
 from feedforward import PositionwiseFeedForwardModule  # noqa: E402,F401
+from rnnt import rnnt_loss  # noqa: E402,F401

@@ -160,6 +160,15 @@ class CtcGroup(ctypes.Structure):
                 ("work", c_p), ("alpha", c_p), ("lse", c_p), ("nll", c_p), ("nll_shifted", c_p), ("beta", c_p)]
 
 
+class RnntDesc(ctypes.Structure):
+    _fields_ = [("logits", c_p), ("ld", c_i64), ("logits_dtype", c_i32), ("B", c_i32), ("T", c_i32), ("U1", c_i32), ("V", c_i32), ("blank", c_i32),
+                ("targets", c_p), ("logit_lens", c_p), ("target_lens", c_p),
+                ("lse", c_p), ("lp_blank", c_p), ("lp_label", c_p), ("alpha", c_p), ("beta", c_p), ("shift", c_p),
+                ("nll", c_p), ("nll_shifted", c_p), ("ll_alpha", c_p), ("sweep", c_i32),
+                ("grad", c_p), ("ld_grad", c_i64), ("grad_dtype", c_i32), ("grad_cols", c_i32), ("gscale", ctypes.c_float),
+                ("gscale_stride", c_i32), ("gscale_dev", c_p), ("clamp", ctypes.c_float)]
+
+
 class LnBwdDesc(ctypes.Structure):
     _fields_ = [("x", c_p), ("dy", c_p), ("gamma", c_p), ("row_mask", c_p), ("dres", c_p), ("dx", c_p), ("dgamma", c_p), ("dbeta", c_p), ("ws", c_p),
                 ("dx2", c_p), ("M", c_i64), ("D", c_i32), ("dy_dtype", c_i32), ("dx2_dtype", c_i32), ("accumulate", c_i32),
@@ -254,6 +263,10 @@ def lib():
                                                 ctypes.POINTER(LayerIO), c_p, c_p, c_i32, c_p, c_p, c_p]
         L.cfm_ctc_nll.argtypes = [c_p, c_i64, c_i32, c_i32, c_i32, c_p, c_p, c_i32, c_p, c_p, c_p, c_p]
         L.cfm_joint_act.argtypes = [c_p, c_i64, c_p, c_i64, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p]
+        L.cfm_joint_act_bwd.argtypes = [c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p]
+        L.cfm_joint_act_bwd_ws.argtypes = [c_i32, c_i32, c_i32, c_i32]
+        L.cfm_rnnt_nll.argtypes = [ctypes.POINTER(RnntDesc), c_p]
+        L.cfm_rnnt_grad.argtypes = [ctypes.POINTER(RnntDesc), c_p]
         c_f = ctypes.c_float
         L.cfm_gemm_tn.argtypes = [ctypes.POINTER(GemmTnDesc), c_p]
         L.cfm_gemm_tn_group.argtypes = [ctypes.POINTER(GemmTnDesc), c_i32, c_p]
@@ -289,7 +302,7 @@ def lib():
         L.cfm_stream_advance.argtypes = [c_p, c_p, c_i32, c_i32, c_p]
         L.cfm_dwconv_causal_bn_silu.argtypes = [c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p]
         L.cfm_conv_cache_update.argtypes = [c_p, c_i32, c_p, c_i32, c_i32, c_i32, c_i32, c_p]
-        for name in ("cfm_layernorm_bwd_ws", "cfm_dwconv_bn_ws", "cfm_conv1_wgrad_ws"):
+        for name in ("cfm_layernorm_bwd_ws", "cfm_dwconv_bn_ws", "cfm_conv1_wgrad_ws", "cfm_joint_act_bwd_ws"):
             getattr(L, name).restype = c_i64
         L.cfm_prof_enable.argtypes = [c_i32]
         L.cfm_prof_enable.restype = None
@@ -299,7 +312,7 @@ def lib():
                                      ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
         for name in ("cfm_gemm", "cfm_ffn_fused", "cfm_ffn_train_forward", "cfm_ffn_train_supported", "cfm_pack_ffn_fragments", "cfm_rowchain", "cfm_rowchain_supported", "cfm_attention", "cfm_layernorm", "cfm_kv_cache_pack", "cfm_dwconv_bn_silu", "cfm_conv1_relu", "cfm_conv1_relu_mma", "cfm_conv12_relu", "cfm_conv12_supported",
                      "cfm_valid_mask", "cfm_chunk_mask", "cfm_attn_mask", "cfm_cast", "cfm_add_rows",
-                     "cfm_encoder_layer_forward", "cfm_ctc_nll", "cfm_joint_act", "cfm_prof_entry", "cfm_gemm_tn", "cfm_gemm_tn_group", "cfm_attention_bwd",
+                     "cfm_encoder_layer_forward", "cfm_ctc_nll", "cfm_joint_act", "cfm_joint_act_bwd", "cfm_rnnt_nll", "cfm_rnnt_grad", "cfm_prof_entry", "cfm_gemm_tn", "cfm_gemm_tn_group", "cfm_attention_bwd",
                      "cfm_layernorm_bwd", "cfm_glu_bwd", "cfm_dwconv_bn_train", "cfm_dwconv_bn_train_bwd", "cfm_col2im_relu_bwd", "cfm_conv1_wgrad",
                      "cfm_ctc_nll_train", "cfm_ctc_nll_train_groups", "cfm_ctc_grad", "cfm_adam_step", "cfm_adam_clip_step", "cfm_sumsq", "cfm_dropout_rows", "cfm_dropout_mask", "cfm_pack_matrices", "cfm_pack_vectors", "cfm_greedy_step", "cfm_ffn_split", "cfm_ffn_split_supported", "cfm_layernorm_bwd_fused", "cfm_dwconv_bn_train_bwd_acc",
                      "cfm_encoder_layer_train_forward", "cfm_encoder_layer_train_backward", "cfm_encoder_train_forward", "cfm_encoder_train_backward", "cfm_stream_prep", "cfm_kv_ring_write", "cfm_stream_advance", "cfm_dwconv_causal_bn_silu", "cfm_conv_cache_update"):

@@ -871,3 +871,81 @@ class CTCWindowLossFn(torch.autograd.Function):
         dW, db = cfm.gemm_tn(dlog, x2, want_colsum=True, mma_code=prec.w_code, split=prec.split)
         dx = _gemm(dlog, pk.wt, w_lo=pk.wt_lo, out_dtype=torch.float32)
         return dx, None, None, None, dW[:pk.V], db[:pk.V]
+
+
+def _rnnt_scale(gout, reduction, B):
+    """(host factor, device scale) of the upstream gradient for cfm.rnnt_grad: "none" -> one per utterance, "sum" -> one, "mean" -> 1 / B."""
+    if reduction == "none":
+        return 1.0, _f32c(gout.reshape(-1))
+    return (1.0 / B if reduction == "mean" else 1.0), _f32c(gout.reshape(1))
+
+
+def _rnnt_reduce(nll, reduction):
+    return nll if reduction == "none" else (nll.sum() if reduction == "sum" else nll.mean())
+
+
+class RNNTLossFn(torch.autograd.Function):
+    """rnnt.rnnt_loss: torchaudio.functional.rnnt_loss (model.py:107) over given logits; the gradient is a buffer of its own (the caller's logits
+    are left as they are)."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, logit_lens, target_lens, blank, clamp, reduction):
+        nll, st = cfm.rnnt_nll(logits, targets, logit_lens, target_lens, blank)
+        ctx.args = (st, clamp, reduction)
+        return _rnnt_reduce(nll, reduction)
+
+    @staticmethod
+    def backward(ctx, gout):
+        st, clamp, reduction = ctx.args
+        logits = st.logits
+        gs, gdev = _rnnt_scale(gout, reduction, logits.shape[0])
+        grad = cfm.rnnt_grad(st, torch.empty(logits.shape, dtype=logits.dtype, device=logits.device), gscale=gs, gscale_dev=gdev, clamp=clamp)
+        return grad, None, None, None, None, None, None
+
+
+class JointRNNTLossFn(torch.autograd.Function):
+    """TransducerJoint.rnnt_loss: the joint (joint.py:20-38) followed by the RNN-T loss (model.py:107), differentiable w.r.t. enc_out, pred_out and
+    the six joint parameters.  The [B,T,U+1,Vp] f32 logits exist only in here, and the gradient overwrites them in place (f32 in the accurate
+    mode; the 16-bit type of the backward GEMMs otherwise, in the first half of each row's bytes): ONE logits-sized buffer."""
+
+    @staticmethod
+    def forward(ctx, xe, xp, mod, prec, targets, enc_lens, target_lens, blank, clamp, reduction, *params):
+        pk = packing.pack_joint_train(mod, prec)
+        B, T, E = xe.shape
+        U1 = xp.shape[1]
+        xe2, xp2 = _f32c(xe.reshape(B * T, E)), _f32c(xp.reshape(B * U1, xp.shape[2]))
+        e = cfm.gemm(xe2, pk.enc.w, bias=pk.enc.b, w_lo=pk.enc.w_lo, out_dtype=torch.float32)
+        p = cfm.gemm(xp2, pk.pred.w, bias=pk.pred.b, w_lo=pk.pred.w_lo, out_dtype=torch.float32)
+        if e.shape[1] != pk.out.w.shape[1]:
+            raise ValueError("TransducerJoint.rnnt_loss: join dimensions differ (%d, ffn_out expects %d)" % (e.shape[1], pk.out.w.shape[1]))
+        act = cfm.joint_act(e, p, B, T, U1, prec.act_dtype)
+        logits = cfm.gemm(act, pk.out.w, bias=pk.out.b, w_lo=pk.out.w_lo, out_dtype=torch.float32)
+        nll, st = cfm.rnnt_nll(logits.view(B, T, U1, pk.Vp), targets, enc_lens, target_lens, blank, V=pk.V)
+        ctx.args = (pk, prec, xe2, xp2, e, p, act, logits, st, clamp, reduction, B, T, U1, xe.shape, xp.shape)
+        return _rnnt_reduce(nll, reduction)
+
+    @staticmethod
+    def backward(ctx, gout):
+        pk, prec, xe2, xp2, e, p, act, logits, st, clamp, reduction, B, T, U1, xe_shape, xp_shape = ctx.args
+        ctx.args = None
+        gs, gdev = _rnnt_scale(gout, reduction, B)
+        M, Vp = logits.shape
+        if prec.split:                                           # f32 gradient over the f32 logits, same bytes
+            cfm.rnnt_grad(st, logits.view(B, T, U1, Vp), gscale=gs, gscale_dev=gdev, clamp=clamp)
+            dlog = logits
+        else:                                                    # 16-bit gradient in the first half of each f32 row
+            half = logits.view(prec.w_dtype)                     # [M, 2 Vp]
+            cfm.rnnt_grad(st, half.view(B, T, U1, 2 * Vp), gscale=gs, gscale_dev=gdev, clamp=clamp, cols=Vp)
+            dlog = half[:, :Vp]
+        dWo, dbo = cfm.gemm_tn(dlog, act, want_colsum=True, mma_code=prec.w_code, split=prec.split)
+        dact = _gemm(dlog, pk.out.wt, w_lo=pk.out.wt_lo, out_dtype=torch.float32)
+        del logits, dlog, st
+        de, dp = cfm.joint_act_bwd(e, p, dact, B, T, U1)
+        del dact
+        dWe, dbe = cfm.gemm_tn(de, xe2, want_colsum=True, mma_code=prec.w_code, split=prec.split)
+        dWp, dbp = cfm.gemm_tn(dp, xp2, want_colsum=True, mma_code=prec.w_code, split=prec.split)
+        dxe = _gemm(de, pk.enc.wt, w_lo=pk.enc.wt_lo, out_dtype=torch.float32)
+        dxp = _gemm(dp, pk.pred.wt, w_lo=pk.pred.wt_lo, out_dtype=torch.float32)
+        V = pk.V
+        return (dxe.view(xe_shape), dxp.view(xp_shape), None, None, None, None, None, None, None, None,
+                dWe, dbe, dWp, dbp, dWo[:V], dbo[:V])

@@ -9,7 +9,7 @@ import torch
 import cfm as _c
 
 __all__ = ["stream_prep", "stream_advance", "dwconv_causal_bn_silu", "conv_cache_update", "dropout_rows", "dropout_mask", "set_deterministic", "gemm_tn", "gemm_tn_group", "layernorm_bwd", "glu_bwd", "dwconv_bn_train", "dwconv_bn_train_bwd", "col2im_relu_bwd", "conv1_wgrad", "attention_bwd",
-           "ctc_nll_train", "ctc_nll_train_groups", "ctc_grad", "ffn_split", "adam_step", "adam_clip_step", "sumsq", "scratch_stats",
+           "ctc_nll_train", "ctc_nll_train_groups", "ctc_grad", "rnnt_nll", "rnnt_grad", "joint_act_bwd", "ffn_split", "adam_step", "adam_clip_step", "sumsq", "scratch_stats",
            "gemm", "ffn_fused", "ffn_fused_supported", "rowchain", "rowchain_supported", "rowchain_pair_supported", "layernorm", "attention", "kv_cache_pack", "dwconv_bn_silu", "conv1_relu", "conv1_relu_mma_supported", "conv12_relu", "conv12_supported", "ctc_nll", "joint_act", "valid_mask", "chunk_mask",
            "attn_mask_combine", "cast", "add_rows", "scratch", "prof_enable", "prof_reset", "prof_table", "as_u8_mask"]
 
@@ -727,6 +727,99 @@ def ctc_grad(logits, V, enc_lens, labels, label_lens, state, gscale=1.0, gscale_
     _c.check(_c.lib().cfm_ctc_grad(_c.ptr(logits), logits.stride(1), B, T, V, _c.ptr(enc_lens), _c.ptr(labels), labels.size(1), _c.ptr(label_lens),
                                    _c.ptr(work), _c.ptr(alpha), _c.ptr(beta), _c.ptr(lse), _c.ptr(nllp), gscale, _c.ptr(gscale_dev), _c.ptr(out), _c.stream()), "cfm_ctc_grad")
     return out
+
+
+_RNNT_SWEEPS = {"auto": 0, "wave": 1, "lds": 2}
+
+
+class RnntState:
+    """What cfm_rnnt_grad needs after cfm_rnnt_nll: the filled cfm_rnnt_desc and the tensors its pointers refer to (kept alive here)."""
+
+    def __init__(self, desc, logits, tensors):
+        self.desc, self.logits, self.tensors = desc, logits, tensors
+
+    def __getattr__(self, name):
+        t = self.__dict__.get("tensors")
+        if t is not None and name in t:
+            return t[name]
+        raise AttributeError(name)
+
+
+def rnnt_nll(logits, targets, logit_lens, target_lens, blank, V=None, sweep=None):
+    """RNN-T negative log-likelihood per utterance from UN-normalised logits [B,T,U+1,>=V] (rows evenly spaced, unit inner stride; f32 / bf16 /
+    fp16), targets int32 [B,U], logit_lens / target_lens int32 [B] (include/cfm.h cfm_rnnt_nll).  V defaults to logits.size(3) (pass it when the
+    last axis holds pad columns).  Returns (nll f32 [B], RnntState) -- the state carries lse / lp_blank / lp_label / alpha / beta / shift /
+    nll_shifted / ll_alpha for rnnt_grad and for tests."""
+    _c.require_hip(logits, targets, logit_lens, target_lens)
+    if logits.dim() != 4 or logits.stride(3) != 1:
+        raise ValueError("cfm.rnnt_nll: logits must be [B,T,U+1,V] with unit inner stride, got %s strides %s" % (tuple(logits.shape), logits.stride()))
+    B, T, U1, W = logits.shape
+    ld = logits.stride(2)
+    if logits.stride(1) != U1 * ld or logits.stride(0) != T * U1 * ld:
+        raise ValueError("cfm.rnnt_nll: logits rows must be evenly spaced (strides %s)" % (logits.stride(),))
+    V = W if V is None else V
+    if not 1 < V <= W:
+        raise ValueError("cfm.rnnt_nll: V = %d with %d columns" % (V, W))
+    for t in (targets, logit_lens, target_lens):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise ValueError("cfm.rnnt_nll: targets and lengths must be contiguous int32")
+    if tuple(targets.shape) != (B, U1 - 1) or logit_lens.numel() != B or target_lens.numel() != B:
+        raise ValueError("cfm.rnnt_nll: targets %s / lengths do not match logits %s" % (tuple(targets.shape), tuple(logits.shape)))
+    if sweep is None:
+        sweep = os.environ.get("CFM_RNNT_SWEEP", "auto")                  # A/B switch of the recursion (same bits either way)
+    dev = logits.device
+    f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    tens = dict(lse=f(B, T, U1), lp_blank=f(B, T, U1), lp_label=f(B, T, U1), alpha=f(B, T, U1), beta=f(B, T, U1), shift=f(B, T + U1),
+                nll=f(B), nll_shifted=f(B), ll_alpha=f(B), targets=targets, logit_lens=logit_lens, target_lens=target_lens)
+    d = _c.RnntDesc()
+    d.logits, d.ld, d.logits_dtype = logits.data_ptr(), ld, _c.dt_code(logits)
+    d.B, d.T, d.U1, d.V, d.blank = B, T, U1, V, blank
+    for name in ("targets", "logit_lens", "target_lens", "lse", "lp_blank", "lp_label", "alpha", "beta", "shift", "nll", "nll_shifted", "ll_alpha"):
+        setattr(d, name, tens[name].data_ptr() if tens[name].numel() else None)
+    d.sweep = _RNNT_SWEEPS[sweep] if isinstance(sweep, str) else int(sweep)
+    _c.check(_c.lib().cfm_rnnt_nll(ctypes.byref(d), _c.stream()), "cfm_rnnt_nll")
+    return tens["nll"], RnntState(d, logits, tens)
+
+
+def rnnt_grad(state, out, gscale=1.0, gscale_dev=None, clamp=-1.0, cols=None):
+    """d nll_b / d logits (clamped to +-clamp when clamp > 0) times gscale * gscale_dev (a device scalar, or [B] per utterance) into `out`
+    [B,T,U+1,>=cols] (f32 / bf16 / fp16, rows evenly spaced; may be the logits buffer itself, include/cfm.h cfm_rnnt_grad).  Columns
+    0..cols-1 are written (default: out.size(3)); V..cols-1 and every row outside the lattice get exact zeros.  Returns out."""
+    _c.require_hip(out, gscale_dev)
+    d = state.desc
+    if out.dim() != 4 or out.stride(3) != 1 or tuple(out.shape[:3]) != (d.B, d.T, d.U1):
+        raise ValueError("cfm.rnnt_grad: out must be [B,T,U+1,cols] with unit inner stride, got %s" % (tuple(out.shape),))
+    ldg = out.stride(2)
+    if out.stride(1) != d.U1 * ldg or out.stride(0) != d.T * d.U1 * ldg:
+        raise ValueError("cfm.rnnt_grad: out rows must be evenly spaced (strides %s)" % (out.stride(),))
+    d.grad, d.ld_grad, d.grad_dtype = out.data_ptr(), ldg, _c.dt_code(out)
+    d.grad_cols = out.size(3) if cols is None else cols
+    d.gscale, d.clamp = float(gscale), float(clamp)
+    if gscale_dev is not None:
+        if gscale_dev.dtype != torch.float32 or not gscale_dev.is_contiguous() or gscale_dev.numel() not in (1, d.B):
+            raise ValueError("cfm.rnnt_grad: gscale_dev must be a contiguous float32 scalar or [B]")
+        d.gscale_dev, d.gscale_stride = gscale_dev.data_ptr(), 1 if gscale_dev.numel() == d.B and d.B > 1 else 0
+    else:
+        d.gscale_dev, d.gscale_stride = None, 0
+    _c.check(_c.lib().cfm_rnnt_grad(ctypes.byref(d), _c.stream()), "cfm_rnnt_grad")
+    d.grad, d.gscale_dev = None, None
+    return out
+
+
+def joint_act_bwd(enc, pred, dact, B, T, U):
+    """Backward of cfm_joint_act: (d_enc f32 [B*T,J], d_pred f32 [B*U,J]) from dact f32 [B*T*U, J] (include/cfm.h cfm_joint_act_bwd)."""
+    _c.require_hip(enc, pred, dact)
+    enc, pred = _rows2d(enc, "joint_act_bwd(enc)"), _rows2d(pred, "joint_act_bwd(pred)")
+    J = enc.shape[1]
+    if (enc.dtype, pred.dtype, dact.dtype) != (torch.float32,) * 3 or tuple(enc.shape) != (B * T, J) or tuple(pred.shape) != (B * U, J) \
+            or tuple(dact.shape) != (B * T * U, J) or not dact.is_contiguous():
+        raise ValueError("cfm.joint_act_bwd: enc f32 [%d,J], pred f32 [%d,J], dact contiguous f32 [%d,J] expected" % (B * T, B * U, B * T * U))
+    de = torch.empty((B * T, J), dtype=torch.float32, device=enc.device)
+    dp = torch.empty((B * U, J), dtype=torch.float32, device=enc.device)
+    ws = scratch("joint_act_bwd", _c.lib().cfm_joint_act_bwd_ws(B, T, U, J), torch.float32, enc.device)
+    _c.check(_c.lib().cfm_joint_act_bwd(enc.data_ptr(), enc.stride(0), pred.data_ptr(), pred.stride(0), dact.data_ptr(), de.data_ptr(), dp.data_ptr(),
+                                        ws.data_ptr(), B, T, U, J, _c.stream()), "cfm_joint_act_bwd")
+    return de, dp
 
 
 def adam_step(p, g, m, v, lr, betas, eps, weight_decay, step, grad_scale=None):

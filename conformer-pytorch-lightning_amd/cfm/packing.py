@@ -523,3 +523,22 @@ def pack_ctc_train(mod, prec):
         wt, wtlo = matrix_t(w, prec)
         return Packed(w=wm, w_lo=wlo, wt=wt, wt_lo=wtlo, b=b, V=V, Vp=Vp)
     return _train_cache(mod).get([mod.ctc_lo.weight, mod.ctc_lo.bias], prec, build)
+
+
+def pack_joint_train(mod, prec):
+    """TransducerJoint.rnnt_loss: the three projections and their transposes; ffn_out padded to Vp = a multiple of 8 rows (cfm_gemm_tn wants
+    N % 8 == 0; the pad rows are zero, so are the logits' pad columns, which the RNN-T kernels never read and whose gradient is exactly 0)."""
+    def build():
+        def lin(m, rows=None):
+            w, b = m.weight.detach().float(), m.bias.detach().float()
+            if rows is not None and rows != w.shape[0]:
+                w = torch.cat([w, w.new_zeros((rows - w.shape[0], w.shape[1]))])
+                b = torch.cat([b, b.new_zeros((rows - b.shape[0],))])
+            wm, wlo = matrix(w.contiguous(), prec)
+            wt, wtlo = matrix_t(w, prec)
+            return Packed(w=wm, w_lo=wlo, b=b.contiguous(), wt=wt, wt_lo=wtlo)
+        V = mod.ffn_out.weight.shape[0]
+        Vp = (V + 7) // 8 * 8
+        return Packed(enc=lin(mod.enc_ffn), pred=lin(mod.pred_ffn), out=lin(mod.ffn_out, Vp), V=V, Vp=Vp)
+    params = [mod.enc_ffn.weight, mod.enc_ffn.bias, mod.pred_ffn.weight, mod.pred_ffn.bias, mod.ffn_out.weight, mod.ffn_out.bias]
+    return _train_cache(mod).get(params, prec, build)

@@ -46,7 +46,83 @@ __global__ __launch_bounds__(256) void cfm_joint_act_kernel(const float* __restr
     }
 }
 
+// backward of a = tanh(e[b,t] + p[b,u]) (train path of TransducerJoint.rnnt_loss): dz = dA (1 - a^2) with a recomputed from the f32 projections
+// (the same tanh_fast as the forward, not the 16-bit operand), reduced to de[b,t] = sum_u dz and dp[b,u] = sum_t dz in a fixed order, no atomics:
+// workgroup (column block, block of JAB_TB frames, b); each thread owns 4 columns, walks u = 0..U-1 and, per u, its JAB_TB frames: de rows are
+// complete in registers at the end, dp leaves one partial per (frame block, u) that cfm_joint_act_bwd_sum_kernel adds in frame-block order.
+// HBM-bound: dA (f32 [B T U, J]) is read once.
+constexpr int JAB_TB = 8;
+
+__global__ __launch_bounds__(64) void cfm_joint_act_bwd_kernel(const float* __restrict__ enc, int64_t ld_e, const float* __restrict__ pred, int64_t ld_p,
+                                                               const float* __restrict__ dA, float* __restrict__ de, float* __restrict__ part, int T, int U, int J) {
+    const int c = (blockIdx.x * 64 + threadIdx.x) * 4;
+    if (c >= J) return;
+    const int tb = blockIdx.y, nTB = gridDim.y, b = blockIdx.z, t0 = tb * JAB_TB;
+    f32x4 e[JAB_TB], acc[JAB_TB];
+#pragma unroll
+    for (int k = 0; k < JAB_TB; ++k) {
+        e[k] = t0 + k < T ? *(const f32x4*)(enc + ((int64_t)b * T + t0 + k) * ld_e + c) : (f32x4){0.f, 0.f, 0.f, 0.f};
+        acc[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+    for (int u = 0; u < U; ++u) {
+        const f32x4 p = *(const f32x4*)(pred + ((int64_t)b * U + u) * ld_p + c);
+        f32x4 ap = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < JAB_TB; ++k) {
+            if (t0 + k < T) {
+                const f32x4 g = *(const f32x4*)(dA + (((int64_t)b * T + t0 + k) * U + u) * J + c);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float a = tanh_fast(e[k][r] + p[r]);
+                    const float dz = g[r] * (1.0f - a * a);
+                    acc[k][r] += dz;
+                    ap[r] += dz;
+                }
+            }
+        }
+        *(f32x4*)(part + (((int64_t)b * nTB + tb) * U + u) * J + c) = ap;
+    }
+#pragma unroll
+    for (int k = 0; k < JAB_TB; ++k)
+        if (t0 + k < T) *(f32x4*)(de + ((int64_t)b * T + t0 + k) * J + c) = acc[k];
+}
+
+// dp[b,u,:] = sum over frame blocks tb = 0, 1, .. of part[b,tb,u,:]
+__global__ __launch_bounds__(256) void cfm_joint_act_bwd_sum_kernel(const float* __restrict__ part, float* __restrict__ dp, int B, int nTB, int U, int J) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;          // one 4-column chunk of dp
+    const int cpr = J / 4;
+    if (idx >= (int64_t)B * U * cpr) return;
+    const int64_t row = idx / cpr;                                       // b*U + u
+    const int c = (int)(idx - row * cpr) * 4, b = (int)(row / U), u = (int)(row - (int64_t)b * U);
+    f32x4 s = {0.f, 0.f, 0.f, 0.f};
+    for (int tb = 0; tb < nTB; ++tb) s += *(const f32x4*)(part + (((int64_t)b * nTB + tb) * U + u) * J + c);
+    *(f32x4*)(dp + row * J + c) = s;
+}
+
 }  // namespace
+
+extern "C" int64_t cfm_joint_act_bwd_ws(int32_t B, int32_t T, int32_t U, int32_t J) {
+    return (int64_t)B * ((T + JAB_TB - 1) / JAB_TB) * U * J;
+}
+
+extern "C" int cfm_joint_act_bwd(const float* enc, int64_t ld_e, const float* pred, int64_t ld_p, const float* dact, float* d_enc, float* d_pred,
+                                 float* work, int32_t B, int32_t T, int32_t U, int32_t J, cfm_stream_t stream) {
+    CFM_CHECK_ARG(enc && pred && dact && d_enc && d_pred && work, "cfm_joint_act_bwd: null pointer");
+    CFM_CHECK_ARG(B > 0 && T > 0 && U > 0 && J > 0 && J % 8 == 0, "cfm_joint_act_bwd: bad shape B=%d T=%d U=%d J=%d (J %% 8 == 0)", B, T, U, J);
+    CFM_CHECK_ARG(ld_e >= J && ld_p >= J && ld_e % 4 == 0 && ld_p % 4 == 0, "cfm_joint_act_bwd: row strides must be >= J and multiples of 4");
+    hipStream_t s = (hipStream_t)stream;
+    const int nTB = (T + JAB_TB - 1) / JAB_TB;
+    {
+        CfmProfScope prof("joint_act_bwd", s, 0.0, (double)B * T * U * J * 4 + (double)B * nTB * U * J * 4);
+        CFM_LAUNCH(cfm_joint_act_bwd_kernel, dim3((unsigned)((J / 4 + 63) / 64), (unsigned)nTB, (unsigned)B), dim3(64), 0, s, enc, ld_e, pred, ld_p, dact,
+                   d_enc, work, T, U, J);
+        if (int rc = cfm_launch_status("cfm_joint_act_bwd")) return rc;
+    }
+    const int64_t chunks = (int64_t)B * U * (J / 4);
+    CfmProfScope prof("joint_act_bwd_sum", s, 0.0, (double)B * nTB * U * J * 4);
+    CFM_LAUNCH(cfm_joint_act_bwd_sum_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, s, (const float*)work, d_pred, B, nTB, U, J);
+    return cfm_launch_status("cfm_joint_act_bwd (sum)");
+}
 
 extern "C" int cfm_joint_act(const float* enc, int64_t ld_e, const float* pred, int64_t ld_p, void* out, int32_t out_dtype, int32_t B,
                              int32_t T, int32_t U, int32_t J, cfm_stream_t stream) {

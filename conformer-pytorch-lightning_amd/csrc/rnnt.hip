@@ -1,0 +1,409 @@
+// rnnt.hip -- RNN-T loss (Graves 2012) and its gradient with respect to the joint's logits (gfx950).
+//
+// replaces torchaudio.functional.rnnt_loss(joint_out, rnnt_text, encoder_out_lens, rnnt_text_lengths, blank, reduction) of
+// Transducer.rnnt_loss (reference src/model.py:107) with fused_log_softmax = True: logits [B, T, U+1, ld >= V] (f32 / bf16 / fp16), all
+// arithmetic f32, no float atomics (the same inputs give the same bits on every run).
+//
+// Three launches (cfm_rnnt_nll: rows + recursions; cfm_rnnt_grad: gradient):
+//   rows   one wavefront per lattice node (b, t < T_b, u <= U_b): lse = log sum_v exp(L[v]) in ONE pass over the row (online max-shifted
+//          sum, 16-byte loads for f32), lp_blank = L[blank] - lse, lp_label = L[y_{u+1}] - lse (u < U_b) -> compact f32 [B, T, U+1];
+//   alpha | beta   2 B workgroups, [0, B) forwards, [B, 2B) backwards, one anti-diagonal (d = t + u) per step with thread = u:
+//              alpha[t,u] = logaddexp(alpha[t-1,u] + lp_blank[t-1,u], alpha[t,u-1] + lp_label[t,u-1])
+//              beta[t,u]  = logaddexp(beta[t+1,u] + lp_blank[t,u], beta[t,u+1] + lp_label[t,u]),  beta[T_b-1,U_b] = lp_blank[T_b-1,U_b]
+//          A thread's own column is in a register; the neighbour's value of the previous diagonal comes through an LDS double buffer with
+//          one barrier per diagonal (U+1 <= 1024), or, as a switch (sweep = 1, U+1 <= 64), a wavefront shuffle with no barrier at all.  The lattice inputs do not
+//          depend on alpha / beta and are requested RNNT_AHEAD diagonals before they are used (as ctc.hip does).
+//          Shifted recursion (the CTC precedent): every blank of frame t is offset by o_t = max_u lp_blank[t,u] and every emission of label
+//          u+1 by q_u = max_t lp_label[t,u].  Each path to (t,u) takes exactly one blank per frame < t and one emission per label <= u, so
+//          alpha' = alpha - sum_{t'<t} o - sum_{u'<u} q exactly, and alpha' + beta' - ll' = alpha + beta - ll: the posteriors do not depend
+//          on the shift, but alpha' / beta' stay small numbers where the unshifted ones grow by ~log V per step (|alpha| ~ 2500 at config 4,
+//          one f32 ulp = 2.4e-4 in the log domain, a 1e-3 error in every posterior).  nll = -(beta'[0,0] + sum o + sum q), the sums in fp64.
+//   grad   one wavefront per row over all B T (U+1) rows:
+//              g[v] = s_b * clamp( exp(L[v] - lse + alpha + beta - ll) - [v = blank] exp(alpha + lp_blank + beta[t+1,u] - ll)
+//                                                                     - [v = y_{u+1}] exp(alpha + lp_label + beta[t,u+1] - ll) )
+//          (clamped before the upstream scale, as torchaudio does), exact zeros outside t < T_b, u <= U_b and in the columns V..grad_cols-1.
+//          The output may alias the logits: each lane writes only bytes of its row that the wavefront has already read (same element size:
+//          the same bytes; a 16-bit gradient over f32 logits: the first half of the row), so the pointers are not declared __restrict__.
+#include "cfm_common.h"
+
+namespace {
+
+constexpr int RNNT_NT = 256;                               // LDS sweep: up to 4 columns per thread
+constexpr int RNNT_MAXU1 = 1024;                           // U + 1
+constexpr int RNNT_MAXT = 8192;                            // o_t lives in LDS
+constexpr int RNNT_AHEAD = 4;
+
+__device__ __forceinline__ float wave_max_(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+// log(exp(a) + exp(b)) on v_exp_f32 / v_log_f32 (ctc.hip logaddexp_: the recursion is a serial chain of these)
+__device__ __forceinline__ float lae_(float a, float b) {
+    const float m = fmaxf(a, b);
+    if (m == -INFINITY) return -INFINITY;
+    return m + __logf(1.0f + __expf(-fabsf(a - b)));
+}
+
+template <typename TI>
+__device__ __forceinline__ float ld1(const void* p, int64_t i) {
+    if constexpr (std::is_same<TI, float>::value) return ((const float*)p)[i];
+    else return TI::to_f32(((const u16*)p)[i]);
+}
+
+template <typename TI>
+__device__ __forceinline__ f32x4 ld4(const void* p, int64_t i) {          // i % 4 == 0, row base 16 (f32) / 8 (16-bit) byte aligned
+    if constexpr (std::is_same<TI, float>::value) {
+        return *(const f32x4*)((const float*)p + i);
+    } else {
+        const u32x2 w = *(const u32x2*)((const u16*)p + i);
+        return (f32x4){TI::to_f32((u16)(w.x & 0xFFFF)), TI::to_f32((u16)(w.x >> 16)), TI::to_f32((u16)(w.y & 0xFFFF)), TI::to_f32((u16)(w.y >> 16))};
+    }
+}
+
+template <typename TO>
+__device__ __forceinline__ void st1(void* p, int64_t i, float v) {
+    if constexpr (std::is_same<TO, float>::value) ((float*)p)[i] = v;
+    else ((u16*)p)[i] = TO::from_f32(v);
+}
+
+template <typename TO>
+__device__ __forceinline__ void st4(void* p, int64_t i, const f32x4& v) {
+    if constexpr (std::is_same<TO, float>::value) {
+        *(f32x4*)((float*)p + i) = v;
+    } else {
+        *(u32x2*)((u16*)p + i) = (u32x2){pack2<TO>(v.x, v.y), pack2<TO>(v.z, v.w)};
+    }
+}
+
+__device__ __forceinline__ int label_at(const int* __restrict__ targets, int b, int U, int u, int V) {
+    const int y = targets[(int64_t)b * U + u];             // labels outside [0, V) cannot index a row: clamped (torchaudio would raise)
+    return y < 0 ? 0 : (y < V ? y : V - 1);
+}
+
+// ---- rows: grid = ceil(B T U1 / 4) workgroups of 4 wavefronts, wavefront = one node ----
+template <typename TI, bool VEC>
+__global__ __launch_bounds__(256) void cfm_rnnt_rows_kernel(cfm_rnnt_desc d) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row_id = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int T = d.T, U1 = d.U1, V = d.V;
+    if (row_id >= (int64_t)d.B * T * U1) return;
+    const int b = (int)(row_id / ((int64_t)T * U1));
+    const int rem = (int)(row_id - (int64_t)b * T * U1), t = rem / U1, u = rem - t * U1;
+    const int Tb = min(max(d.logit_lens[b], 0), T), Ub = min(max(d.target_lens[b], 0), U1 - 1);
+    if (t >= Tb || u > Ub) return;                         // never read by the recursions or the gradient pass (wavefront-uniform)
+    const void* row = (const char*)d.logits + row_id * d.ld * (std::is_same<TI, float>::value ? 4 : 2);
+    float m = -INFINITY, s = 0.f;                          // online log-sum-exp: the row is read once
+    if constexpr (VEC) {
+        for (int c = lane * 4; c < V; c += 256) {
+            if (c + 3 < V) {
+                const f32x4 v = ld4<TI>(row, c);
+                const float cm = fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w));
+                if (cm > m) {
+                    s *= __expf(m - cm);
+                    m = cm;
+                }
+                if (m > -INFINITY) s += (__expf(v.x - m) + __expf(v.y - m)) + (__expf(v.z - m) + __expf(v.w - m));
+            } else {
+                for (int k = c; k < V; ++k) {
+                    const float x = ld1<TI>(row, k);
+                    if (x > m) {
+                        s *= __expf(m - x);
+                        m = x;
+                    }
+                    if (m > -INFINITY) s += __expf(x - m);
+                }
+            }
+        }
+    } else {
+        for (int c = lane; c < V; c += 64) {
+            const float x = ld1<TI>(row, c);
+            if (x > m) {
+                s *= __expf(m - x);
+                m = x;
+            }
+            if (m > -INFINITY) s += __expf(x - m);
+        }
+    }
+    const float M = wave_max_(m);
+    const float tot = wave_sum(m == -INFINITY ? 0.f : s * __expf(m - M));
+    const float lse = M + __logf(tot);
+    if (lane == 0) {
+        d.lse[row_id] = lse;
+        d.lp_blank[row_id] = ld1<TI>(row, d.blank) - lse;
+        d.lp_label[row_id] = u < Ub ? ld1<TI>(row, label_at(d.targets, b, U1 - 1, u, V)) - lse : -INFINITY;
+    }
+}
+
+// ---- alpha | beta: one workgroup per (utterance, direction) ----
+// SHFL: NT = 64, one column per lane, the neighbour through __shfl_up / __shfl_down; otherwise NT = RNNT_NT, PER columns per thread through LDS.
+template <int NT, int PER, bool SHFL>
+__device__ __forceinline__ void rnnt_sweep(const cfm_rnnt_desc& d, const int b, const bool fwd) {
+    __shared__ float sh_o[RNNT_MAXT];
+    __shared__ float sh_q[RNNT_MAXU1];
+    __shared__ float pub[SHFL ? 1 : 2][SHFL ? 1 : RNNT_MAXU1 + 2];
+    __shared__ double red[NT];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int T = d.T, U1 = d.U1;
+    const int Tb = min(max(d.logit_lens[b], 0), T), Ub = min(max(d.target_lens[b], 0), U1 - 1);
+    if (Tb == 0) {                                         // no frame: no alignment (torchaudio rejects it); +inf, zero gradient
+        if (tid == 0) {
+            if (fwd) d.ll_alpha[b] = -INFINITY;
+            else d.nll[b] = d.nll_shifted[b] = INFINITY;
+        }
+        return;
+    }
+    const int64_t base = (int64_t)b * T * U1;
+    const float* lb = d.lp_blank + base;
+    const float* ll = d.lp_label + base;
+    // shifts: o_t over the valid columns (a wavefront per frame), q_u over the valid frames (a thread per label)
+    for (int t = wave; t < Tb; t += NT / 64) {
+        float m = -INFINITY;
+        for (int u = lane; u <= Ub; u += 64) m = fmaxf(m, lb[(int64_t)t * U1 + u]);
+        m = wave_max_(m);
+        if (lane == 0) sh_o[t] = m > -INFINITY ? m : 0.f;
+    }
+    for (int u = tid; u < Ub; u += NT) {
+        float m0 = -INFINITY, m1 = -INFINITY, m2 = -INFINITY, m3 = -INFINITY;
+        int t = 0;
+        for (; t + 3 < Tb; t += 4) {
+            m0 = fmaxf(m0, ll[(int64_t)t * U1 + u]);
+            m1 = fmaxf(m1, ll[(int64_t)(t + 1) * U1 + u]);
+            m2 = fmaxf(m2, ll[(int64_t)(t + 2) * U1 + u]);
+            m3 = fmaxf(m3, ll[(int64_t)(t + 3) * U1 + u]);
+        }
+        for (; t < Tb; ++t) m0 = fmaxf(m0, ll[(int64_t)t * U1 + u]);
+        const float m = fmaxf(fmaxf(m0, m1), fmaxf(m2, m3));
+        sh_q[u] = m > -INFINITY ? m : 0.f;
+    }
+    if constexpr (!SHFL)
+        for (int i = tid; i < RNNT_MAXU1 + 2; i += NT) pub[0][i] = pub[1][i] = -INFINITY;
+    __syncthreads();
+    float* shift = d.shift + (int64_t)b * (T + U1);
+    if (fwd) {                                             // the gradient pass reads the shifts from here
+        for (int t = tid; t < Tb; t += NT) shift[t] = sh_o[t];
+        for (int u = tid; u < Ub; u += NT) shift[T + u] = sh_q[u];
+    }
+    float* out = (fwd ? d.alpha : d.beta) + base;
+    const int D = Tb + Ub;                                 // diagonals 0 .. Tb-1+Ub
+    float self[PER], lbp[PER], pv[PER];
+    float nb[RNNT_AHEAD][PER], nl[RNNT_AHEAD][PER];
+    auto fetch = [&](int step, int i, float& vb, float& vl) {
+        const int u = tid + i * NT, dd = fwd ? step : D - 1 - step, t = dd - u;
+        const bool ok = step < D && u <= Ub && t >= 0 && t < Tb;
+        vb = ok ? lb[(int64_t)t * U1 + u] - sh_o[t] : 0.f;
+        vl = (ok && u < Ub) ? ll[(int64_t)t * U1 + u] - sh_q[u] : -INFINITY;
+    };
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+        self[i] = -INFINITY;
+        lbp[i] = 0.f;
+        pv[i] = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < RNNT_AHEAD; ++k) fetch(k, i, nb[k][i], nl[k][i]);
+    }
+    for (int s0 = 0; s0 < D; s0 += RNNT_AHEAD) {
+#pragma unroll
+        for (int k = 0; k < RNNT_AHEAD; ++k) {
+            const int step = s0 + k;
+            if (step < D) {                                // uniform
+                const int dd = fwd ? step : D - 1 - step;
+#pragma unroll
+                for (int i = 0; i < PER; ++i) {
+                    const int u = tid + i * NT, t = dd - u;
+                    float nbr;                             // the neighbour column's value of the previous diagonal
+                    if constexpr (SHFL) {
+                        nbr = fwd ? __shfl_up(pv[i], 1, 64) : __shfl_down(pv[i], 1, 64);
+                        if (fwd ? lane == 0 : lane == 63) nbr = -INFINITY;
+                    } else {
+                        nbr = fwd ? pub[(step + 1) & 1][u] : pub[(step + 1) & 1][u + 1];
+                    }
+                    float v = -INFINITY;
+                    if (u <= Ub && t >= 0 && t < Tb) {
+                        if (fwd) {
+                            const float a = (t == 0 && u == 0) ? 0.f : lae_(self[i] + lbp[i], nbr);
+                            out[(int64_t)t * U1 + u] = a;
+                            self[i] = a;
+                            lbp[i] = nb[k][i];
+                            v = a + nl[k][i];                              // -inf at u = Ub
+                            if (t == Tb - 1 && u == Ub) d.ll_alpha[b] = a + nb[k][i];
+                        } else {
+                            const float bt = (t == Tb - 1 && u == Ub) ? nb[k][i] : lae_(self[i] + nb[k][i], nbr + nl[k][i]);
+                            out[(int64_t)t * U1 + u] = bt;
+                            self[i] = bt;
+                            v = bt;
+                        }
+                    }
+                    pv[i] = v;
+                    if constexpr (!SHFL) pub[step & 1][fwd ? u + 1 : u] = v;
+                    fetch(step + RNNT_AHEAD, i, nb[k][i], nl[k][i]);
+                }
+                if constexpr (!SHFL) __syncthreads();
+            }
+        }
+    }
+    if (fwd) return;
+    double part = 0.0;                                     // sum o + sum q in fp64, a fixed order
+    for (int t = tid; t < Tb; t += NT) part += (double)sh_o[t];
+    for (int u = tid; u < Ub; u += NT) part += (double)sh_q[u];
+    red[tid] = part;
+    __syncthreads();                                       // also: beta[0,0] (thread 0's column) is final
+    if (tid == 0) {
+        double tot = 0.0;
+        for (int i = 0; i < NT; ++i) tot += red[i];
+        const float b00 = self[0];                         // thread 0 owns u = 0; its last value is beta'[0,0]
+        d.nll_shifted[b] = -b00;
+        d.nll[b] = (float)(-((double)b00 + tot));
+    }
+}
+
+template <int NT, int PER, bool SHFL>
+__global__ __launch_bounds__(NT) void cfm_rnnt_alpha_beta_kernel(cfm_rnnt_desc d) {
+    const int wg = (int)blockIdx.x;
+    if (wg < d.B) rnnt_sweep<NT, PER, SHFL>(d, wg, true);
+    else rnnt_sweep<NT, PER, SHFL>(d, wg - d.B, false);
+}
+
+// ---- gradient: one wavefront per row (b, t, u), all rows ----
+template <typename TI, typename TO, bool VEC>
+__global__ __launch_bounds__(256) void cfm_rnnt_grad_kernel(cfm_rnnt_desc d) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row_id = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int T = d.T, U1 = d.U1, V = d.V, ncols = d.grad_cols;
+    if (row_id >= (int64_t)d.B * T * U1) return;
+    const int b = (int)(row_id / ((int64_t)T * U1));
+    const int rem = (int)(row_id - (int64_t)b * T * U1), t = rem / U1, u = rem - t * U1;
+    const int Tb = min(max(d.logit_lens[b], 0), T), Ub = min(max(d.target_lens[b], 0), U1 - 1);
+    const void* row = (const char*)d.logits + row_id * d.ld * (std::is_same<TI, float>::value ? 4 : 2);
+    void* grow = (char*)d.grad + row_id * d.ld_grad * (std::is_same<TO, float>::value ? 4 : 2);
+    const float nls = d.nll_shifted[b];
+    if (t >= Tb || u > Ub || !(nls < INFINITY)) {          // outside the lattice (or no alignment): exact zeros
+        if constexpr (VEC) {
+            for (int c = lane * 4; c < ncols; c += 256) st4<TO>(grow, c, (f32x4){0.f, 0.f, 0.f, 0.f});
+        } else {
+            for (int c = lane; c < ncols; c += 64) st1<TO>(grow, c, 0.f);
+        }
+        return;
+    }
+    const int64_t node = (int64_t)b * T * U1 + (int64_t)t * U1 + u;
+    const float* shift = d.shift + (int64_t)b * (T + U1);
+    const float ll = -nls, a = d.alpha[node];
+    const float lse = d.lse[node];
+    const float c0 = lse - (a + d.beta[node] - ll);                  // exp(L[v] - c0) = softmax[v] * posterior of the node
+    const float lbs = d.lp_blank[node] - shift[t];                   // the recursion's own shifted values, bit for bit
+    const float bnext = t + 1 < Tb ? d.beta[node + U1] : (u == Ub ? 0.f : -INFINITY);
+    const float cb = __expf(a + lbs + bnext - ll);
+    float cl = 0.f;
+    int y = -1;
+    if (u < Ub) {
+        y = label_at(d.targets, b, U1 - 1, u, V);
+        cl = __expf(a + (d.lp_label[node] - shift[T + u]) + d.beta[node + 1] - ll);
+    }
+    const int blank = d.blank;
+    const float gs = d.gscale * (d.gscale_dev ? d.gscale_dev[(int64_t)b * d.gscale_stride] : 1.f);
+    const float cl_ = d.clamp;
+    auto g1 = [&](int v, float x) {
+        float g = __expf(x - c0) - (v == blank ? cb : 0.f) - (v == y ? cl : 0.f);
+        if (cl_ > 0.f) g = fminf(fmaxf(g, -cl_), cl_);
+        return gs * g;
+    };
+    if constexpr (VEC) {
+        for (int c = lane * 4; c < ncols; c += 256) {
+            f32x4 g;
+            if (c + 3 < V) {
+                const f32x4 x = ld4<TI>(row, c);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) g[e] = g1(c + e, x[e]);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) g[e] = c + e < V ? g1(c + e, ld1<TI>(row, c + e)) : 0.f;
+            }
+            st4<TO>(grow, c, g);
+        }
+    } else {
+        for (int c = lane; c < ncols; c += 64) st1<TO>(grow, c, c < V ? g1(c, ld1<TI>(row, c)) : 0.f);
+    }
+}
+
+int rnnt_check(const cfm_rnnt_desc* d, const char* what) {
+    CFM_CHECK_ARG(d && d->logits && d->logit_lens && d->target_lens && d->lse && d->lp_blank && d->lp_label && d->alpha && d->beta && d->shift &&
+                  d->nll && d->nll_shifted, "%s: null pointer", what);
+    CFM_CHECK_ARG(d->B > 0 && d->T > 0 && d->U1 > 0 && d->V > 1, "%s: bad shape B=%d T=%d U+1=%d V=%d", what, d->B, d->T, d->U1, d->V);
+    CFM_CHECK_ARG(d->U1 <= RNNT_MAXU1, "%s: U+1 = %d exceeds %d", what, d->U1, RNNT_MAXU1);
+    CFM_CHECK_ARG(d->T <= RNNT_MAXT, "%s: T = %d frames exceeds %d", what, d->T, RNNT_MAXT);
+    CFM_CHECK_ARG(d->U1 == 1 || d->targets, "%s: targets is null", what);
+    CFM_CHECK_ARG(d->blank >= 0 && d->blank < d->V, "%s: blank %d outside [0, %d)", what, d->blank, d->V);
+    CFM_CHECK_ARG(d->ld >= d->V, "%s: row stride %lld < V = %d", what, (long long)d->ld, d->V);
+    CFM_CHECK_ARG(d->logits_dtype >= CFM_F32 && d->logits_dtype <= CFM_F16, "%s: bad logits dtype", what);
+    return CFM_OK;
+}
+
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+template <typename TI>
+int launch_rows(const cfm_rnnt_desc& d, hipStream_t s, CfmProfScope& prof) {
+    const int64_t rows = (int64_t)d.B * d.T * d.U1;
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    const bool vec = d.ld % 4 == 0 && (std::is_same<TI, float>::value ? aligned16(d.logits) : ((uintptr_t)d.logits & 7) == 0);
+    if (vec) CFM_LAUNCH((cfm_rnnt_rows_kernel<TI, true>), grid, dim3(256), 0, s, d);
+    else CFM_LAUNCH((cfm_rnnt_rows_kernel<TI, false>), grid, dim3(256), 0, s, d);
+    return CFM_OK;
+}
+
+template <typename TI, typename TO>
+int launch_grad(const cfm_rnnt_desc& d, hipStream_t s, CfmProfScope& prof) {
+    const int64_t rows = (int64_t)d.B * d.T * d.U1;
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    const bool in_ok = std::is_same<TI, float>::value ? aligned16(d.logits) : ((uintptr_t)d.logits & 7) == 0;
+    const bool out_ok = std::is_same<TO, float>::value ? aligned16(d.grad) : ((uintptr_t)d.grad & 7) == 0;
+    const bool vec = d.ld % 4 == 0 && d.ld_grad % 4 == 0 && d.grad_cols % 4 == 0 && in_ok && out_ok;
+    if (vec) CFM_LAUNCH((cfm_rnnt_grad_kernel<TI, TO, true>), grid, dim3(256), 0, s, d);
+    else CFM_LAUNCH((cfm_rnnt_grad_kernel<TI, TO, false>), grid, dim3(256), 0, s, d);
+    return CFM_OK;
+}
+
+template <typename TI>
+int launch_grad_out(const cfm_rnnt_desc& d, hipStream_t s, CfmProfScope& prof) {
+    if (d.grad_dtype == CFM_F32) return launch_grad<TI, float>(d, s, prof);
+    if (d.grad_dtype == CFM_BF16) return launch_grad<TI, BF16>(d, s, prof);
+    return launch_grad<TI, F16>(d, s, prof);
+}
+
+}  // namespace
+
+extern "C" int cfm_rnnt_nll(const cfm_rnnt_desc* d, cfm_stream_t stream) {
+    if (int rc = rnnt_check(d, "cfm_rnnt_nll")) return rc;
+    CFM_CHECK_ARG(d->ll_alpha, "cfm_rnnt_nll: null pointer");
+    CFM_CHECK_ARG(d->sweep >= 0 && d->sweep <= 2 && !(d->sweep == 1 && d->U1 > 64), "cfm_rnnt_nll: sweep %d (1: wavefront shuffles, U+1 <= 64; 2: LDS)", d->sweep);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t rows = (int64_t)d->B * d->T * d->U1;
+    {
+        CfmProfScope prof("rnnt_rows", s, 0.0, (double)rows * d->V * cfm_elt_size(d->logits_dtype));
+        int rc = d->logits_dtype == CFM_F32 ? launch_rows<float>(*d, s, prof) : d->logits_dtype == CFM_BF16 ? launch_rows<BF16>(*d, s, prof) : launch_rows<F16>(*d, s, prof);
+        if (rc) return rc;
+        if (int rc2 = cfm_launch_status("cfm_rnnt_nll (rows)")) return rc2;
+    }
+    const bool shfl = d->sweep == 1;                       // auto = LDS: measured faster at config 4 (RNN-T loss)
+    CfmProfScope prof("rnnt_alpha_beta", s, 0.0, (double)rows * 4 * 6);
+    if (shfl) CFM_LAUNCH((cfm_rnnt_alpha_beta_kernel<64, 1, true>), dim3(2 * d->B), dim3(64), 0, s, *d);
+    else CFM_LAUNCH((cfm_rnnt_alpha_beta_kernel<RNNT_NT, RNNT_MAXU1 / RNNT_NT, false>), dim3(2 * d->B), dim3(RNNT_NT), 0, s, *d);
+    return cfm_launch_status("cfm_rnnt_nll (alpha | beta)");
+}
+
+extern "C" int cfm_rnnt_grad(const cfm_rnnt_desc* d, cfm_stream_t stream) {
+    if (int rc = rnnt_check(d, "cfm_rnnt_grad")) return rc;
+    CFM_CHECK_ARG(d->grad, "cfm_rnnt_grad: null gradient");
+    CFM_CHECK_ARG(d->grad_dtype >= CFM_F32 && d->grad_dtype <= CFM_F16, "cfm_rnnt_grad: bad gradient dtype");
+    CFM_CHECK_ARG(d->grad_cols >= d->V && d->ld_grad >= d->grad_cols, "cfm_rnnt_grad: grad_cols %d must be in [V, ld_grad] (V = %d, ld_grad = %lld)",
+                  d->grad_cols, d->V, (long long)d->ld_grad);
+    if (d->grad == d->logits)                              // in place: each row's gradient must fit the bytes of its own row
+        CFM_CHECK_ARG(d->ld_grad * cfm_elt_size(d->grad_dtype) == d->ld * cfm_elt_size(d->logits_dtype) &&
+                      cfm_elt_size(d->grad_dtype) <= cfm_elt_size(d->logits_dtype), "cfm_rnnt_grad: in place needs the same row bytes and a gradient no wider than the logits");
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t rows = (int64_t)d->B * d->T * d->U1;
+    CfmProfScope prof("rnnt_grad", s, 0.0, (double)rows * ((double)d->V * cfm_elt_size(d->logits_dtype) + (double)d->grad_cols * cfm_elt_size(d->grad_dtype)));
+    int rc = d->logits_dtype == CFM_F32 ? launch_grad_out<float>(*d, s, prof) : d->logits_dtype == CFM_BF16 ? launch_grad_out<BF16>(*d, s, prof) : launch_grad_out<F16>(*d, s, prof);
+    if (rc) return rc;
+    return cfm_launch_status("cfm_rnnt_grad");
+}

@@ -9,9 +9,10 @@
 Same constructor arguments, parameter names (`enc_ffn`, `pred_ffn`, `ffn_out`) and the attribute `activatoin` (sic) as the reference;
 `forward(enc_out, pred_out, pre_project=True)` accepts the 3-D tensors of model.py:102 / :250 and the 4-D singleton-axis form of
 joint.py:29-33.  `out_dtype` (default torch.float32, what the reference returns) may be set to a 16-bit type to halve the 3.3 GB the
-logits take at BASELINE config 4.  The RNN-T loss itself (torchaudio.functional.rnnt_loss, model.py:107) is outside this repository:
-torchaudio is absent here, so nothing pins it.  No backward: calling it with gradients enabled on parameters that
-require them raises.
+logits take at BASELINE config 4.  `forward` has no backward: calling it in train mode with gradients enabled on parameters that require
+them raises.  Training goes through `rnnt_loss(enc_out, pred_out, targets, enc_lens, target_lens, ...)`, the joint followed by the RNN-T loss
+(torchaudio.functional.rnnt_loss at model.py:107; rnnt.py, csrc/rnnt.hip) as one differentiable step whose logits never leave it, so the
+loss gradient overwrites them in place (cfm/autograd.py JointRNNTLossFn).
 """
 import torch
 import torch.nn as nn
@@ -60,6 +61,7 @@ class TransducerJoint(nn.Module):
         return B, N, (t if t.dtype == torch.float32 else t.float()).contiguous().view(B * N, X)
 
     def forward(self, enc_out, pred_out, pre_project=True):
+        """Logits [B, T, U, V] (joint.py:20-38), inference only; for training use `rnnt_loss`, which also runs this joint."""
         if torch.is_grad_enabled() and self.training and any(p.requires_grad for p in self.parameters()):
             raise NotImplementedError("TransducerJoint: backward is not built yet (forward only)")
         cfm.require_hip(enc_out, pred_out)
@@ -78,3 +80,31 @@ class TransducerJoint(nn.Module):
         out = cfm.gemm(a, pk.out[0], bias=pk.out[2], w_lo=pk.out[1], out_dtype=self.out_dtype)
         out = out.view(B, T, U, pk.Vp)
         return out if pk.Vp == pk.V else out[..., :pk.V]
+
+    def rnnt_loss(self, enc_out, pred_out, targets, enc_lens, target_lens, blank=0, clamp=-1, reduction="mean"):
+        """torchaudio.functional.rnnt_loss(self(enc_out, pred_out), targets, enc_lens, target_lens, blank, clamp, reduction) as one step
+        (model.py:102-113), differentiable w.r.t. enc_out [B, T, E], pred_out [B, U+1, P] and the six joint parameters; targets [B, U].
+        Semantics as rnnt.rnnt_loss; the precision mode is cfm.resolve_precision(self)."""
+        from cfm import autograd as ag
+        if reduction not in ("none", "sum", "mean"):
+            raise ValueError("TransducerJoint.rnnt_loss: reduction must be 'none', 'sum' or 'mean', got %r" % (reduction,))
+        cfm.require_hip(enc_out, pred_out, targets, enc_lens, target_lens)
+        if enc_out.dim() == 4:
+            enc_out = enc_out.squeeze(2)
+        if pred_out.dim() == 4:
+            pred_out = pred_out.squeeze(1)
+        if enc_out.dim() != 3 or pred_out.dim() != 3 or enc_out.size(0) != pred_out.size(0):
+            raise ValueError("TransducerJoint.rnnt_loss: enc_out %s / pred_out %s must be (B, T, E) / (B, U+1, P)"
+                             % (tuple(enc_out.shape), tuple(pred_out.shape)))
+        B, U1 = pred_out.size(0), pred_out.size(1)
+        if tuple(targets.shape) != (B, U1 - 1):
+            raise ValueError("TransducerJoint.rnnt_loss: targets %s, expected (%d, %d)" % (tuple(targets.shape), B, U1 - 1))
+        V = self.ffn_out.weight.shape[0]
+        b = blank + V if blank < 0 else blank
+        if not 0 <= b < V:
+            raise ValueError("TransducerJoint.rnnt_loss: blank %d outside a vocabulary of %d" % (blank, V))
+        dev = enc_out.device
+        i32 = lambda t: t.to(device=dev, dtype=torch.int32).contiguous()
+        params = [self.enc_ffn.weight, self.enc_ffn.bias, self.pred_ffn.weight, self.pred_ffn.bias, self.ffn_out.weight, self.ffn_out.bias]
+        return ag.JointRNNTLossFn.apply(enc_out, pred_out, self, cfm.resolve_precision(self), i32(targets), i32(enc_lens), i32(target_lens), b,
+                                        float(clamp), reduction, *params)

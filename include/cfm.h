@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CFM_VERSION 302 /* 0.3.2: cfm_rowchain_desc.cin_* (the conv-in chain as the input stage of the next launch). 0.3.1: row chains at D = 512, cfm_rowchain_desc.psum_out / psum_in (feed-forward split over workgroup pairs), cfm_conv12_relu at C = 512. 0.3.0: row groups in the train entry points (cfm_train_group, cfm_layer_train_io.n_groups), cfm_gemm_tn_group + deferred weight gradients, cfm_encoder_train_forward / _backward (the whole stack from one host call). 0.2.3: cfm_ffn_split, cfm_layer_scratch.psum (the feed-forward split over FF for few rows). 0.2.2: cfm_ctc_nll_train / cfm_ctc_grad take a beta buffer (both recursions in one launch); GEMM tile ids 9-11 (K groups). 0.2.1: fused front-end (cfm_conv12_relu); attention stage of the conv-in chain (cfm_rowchain_desc.att_*, cfm_layer_scratch.vt). 0.2.0: training entry points */
+#define CFM_VERSION 302 /* 0.3.2 (additive, same number): the RNN-T loss (cfm_rnnt_desc, cfm_rnnt_nll, cfm_rnnt_grad) and the transducer joint's activation backward (cfm_joint_act_bwd). 0.3.2: cfm_rowchain_desc.cin_* (the conv-in chain as the input stage of the next launch). 0.3.1: row chains at D = 512, cfm_rowchain_desc.psum_out / psum_in (feed-forward split over workgroup pairs), cfm_conv12_relu at C = 512. 0.3.0: row groups in the train entry points (cfm_train_group, cfm_layer_train_io.n_groups), cfm_gemm_tn_group + deferred weight gradients, cfm_encoder_train_forward / _backward (the whole stack from one host call). 0.2.3: cfm_ffn_split, cfm_layer_scratch.psum (the feed-forward split over FF for few rows). 0.2.2: cfm_ctc_nll_train / cfm_ctc_grad take a beta buffer (both recursions in one launch); GEMM tile ids 9-11 (K groups). 0.2.1: fused front-end (cfm_conv12_relu); attention stage of the conv-in chain (cfm_rowchain_desc.att_*, cfm_layer_scratch.vt). 0.2.0: training entry points */
 
 typedef void* cfm_stream_t;
 
@@ -564,6 +564,53 @@ int cfm_ctc_nll(const float* logits, int64_t ld, int32_t B, int32_t T, int32_t V
  */
 int cfm_joint_act(const float* enc, int64_t ld_e, const float* pred, int64_t ld_p, void* out, int32_t out_dtype, int32_t B,
                   int32_t T, int32_t U, int32_t J, cfm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * RNN-T loss (csrc/rnnt.hip):  replaces
+ *     torchaudio.functional.rnnt_loss(joint_out, rnnt_text, encoder_out_lens, rnnt_text_lengths, blank=self.blank, reduction="mean")
+ * of Transducer.rnnt_loss (reference src/model.py:107; fused_log_softmax = True), per utterance and with the gradient w.r.t. the logits.
+ *  logits       [B, T, U1, ld >= V] (logits_dtype f32 / bf16 / fp16; U1 = U + 1), arithmetic f32
+ *  targets      int32 [B, U1-1] (labels y_1..y_U; may be NULL when U1 == 1), logit_lens / target_lens int32 [B] (clamped to [0,T] / [0,U1-1])
+ *  lse, lp_blank, lp_label, alpha, beta   f32 [B, T, U1] work arrays (only t < T_b, u <= U_b are written); shift f32 [B, T + U1]
+ *  nll          f32 [B]: -log P(y | x) per utterance (+inf when T_b = 0); nll_shifted / ll_alpha f32 [B]: -beta'[0,0] and alpha'[T_b-1,U_b] +
+ *               lp_blank' of the shifted recursions (csrc/rnnt.hip) -- equal up to f32 rounding
+ * cfm_rnnt_nll  the row pass (log-sum-exp, blank and label log-probabilities per node) and both recursions (2 B workgroups); fills the arrays above.
+ *               sweep: 0 = auto (LDS), 1 = wavefront shuffles (U1 <= 64), 2 = LDS and one barrier per diagonal.  U1 <= 1024, T <= 8192.
+ * cfm_rnnt_grad after cfm_rnnt_nll with the same desc: grad [B, T, U1, ld_grad] (grad_dtype) columns 0..grad_cols-1 (V <= grad_cols <= ld_grad) =
+ *               s_b * clamp(d nll_b / d logits, +-clamp) (clamp <= 0: none), s_b = gscale * (gscale_dev ? gscale_dev[b * gscale_stride] : 1) (a
+ *               DEVICE scale: no host synchronisation); exact zeros outside t < T_b, u <= U_b and in columns V..grad_cols-1.  grad may be the
+ *               logits themselves (in place) when ld_grad * sizeof(grad) == ld * sizeof(logits) and the gradient type is no wider than the logits'.
+ */
+typedef struct {
+    const void* logits;
+    int64_t ld;
+    int32_t logits_dtype;
+    int32_t B, T, U1, V, blank;
+    const int32_t* targets;
+    const int32_t* logit_lens;
+    const int32_t* target_lens;
+    float *lse, *lp_blank, *lp_label, *alpha, *beta, *shift;
+    float *nll, *nll_shifted, *ll_alpha;
+    int32_t sweep;
+    /* cfm_rnnt_grad only: */
+    void* grad;
+    int64_t ld_grad;
+    int32_t grad_dtype, grad_cols;
+    float gscale;
+    int32_t gscale_stride; /* 0: one scalar for all utterances; 1: gscale_dev[b] (reduction "none") */
+    const float* gscale_dev;
+    float clamp;
+} cfm_rnnt_desc;
+int cfm_rnnt_nll(const cfm_rnnt_desc* d, cfm_stream_t stream);
+int cfm_rnnt_grad(const cfm_rnnt_desc* d, cfm_stream_t stream);
+
+/* Backward of the joint's activation (csrc/joint.hip), the train path of TransducerJoint.rnnt_loss (reference src/joint.py:31-37 under
+ * autograd): a = tanh(enc[b*T+t] + pred[b*U+u]) recomputed from the f32 projections (as cfm_joint_act), dz = dact (1 - a^2) with dact f32
+ * [B*T*U, J]; d_enc f32 [B*T, J] = sum_u dz, d_pred f32 [B*U, J] = sum_t dz, both in a fixed order (no atomics).  work: f32 scratch of
+ * cfm_joint_act_bwd_ws(B, T, U, J) floats.  J % 8 == 0. */
+int64_t cfm_joint_act_bwd_ws(int32_t B, int32_t T, int32_t U, int32_t J);
+int cfm_joint_act_bwd(const float* enc, int64_t ld_e, const float* pred, int64_t ld_p, const float* dact, float* d_enc, float* d_pred,
+                      float* work, int32_t B, int32_t T, int32_t U, int32_t J, cfm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Training (BASELINE config 3: encoder + CTC loss + backward).  Input gradients of the dense layers are cfm_gemm on transposed
