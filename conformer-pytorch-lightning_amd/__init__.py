@@ -20,4 +20,5 @@ from attention import (MultiHeadSelfAttentionModule, PositionalEncoding, Relativ
                        RelativePositionalEncoding)
 from convolution import ConvolutionModule, ConvolutionSubSampling  # noqa: E402,F401
 from feedforward import PositionwiseFeedForwardModule  # noqa: E402,F401
-from rnnt import rnnt_loss  # noqa: E402,F401
+from rnnt import rnnt_loss, rnnt_loss_packed  # noqa: E402,F401
+from transducer import TransducerObjective  # noqa: E402,F401

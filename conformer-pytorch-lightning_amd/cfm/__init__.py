@@ -169,6 +169,19 @@ class RnntDesc(ctypes.Structure):
                 ("gscale_stride", c_i32), ("gscale_dev", c_p), ("clamp", ctypes.c_float)]
 
 
+class Lattice(ctypes.Structure):
+    _fields_ = [("B", c_i32), ("T_max", c_i32), ("U1_max", c_i32), ("M", c_i64), ("off", c_p), ("T", c_p), ("U", c_p), ("enc_row0", c_p),
+                ("pred_row0", c_p), ("n_enc", c_i64), ("n_pred", c_i64), ("blk_off", c_p)]
+
+
+class RnntPackedDesc(ctypes.Structure):
+    _fields_ = [("lat", Lattice), ("logits", c_p), ("ld", c_i64), ("logits_dtype", c_i32), ("V", c_i32), ("blank", c_i32), ("ld_targets", c_i32),
+                ("targets", c_p), ("lse", c_p), ("lp_blank", c_p), ("lp_label", c_p), ("alpha", c_p), ("beta", c_p), ("shift", c_p),
+                ("nll", c_p), ("nll_shifted", c_p), ("ll_alpha", c_p), ("sweep", c_i32),
+                ("grad", c_p), ("ld_grad", c_i64), ("grad_dtype", c_i32), ("grad_cols", c_i32), ("gscale", ctypes.c_float),
+                ("gscale_stride", c_i32), ("gscale_dev", c_p), ("clamp", ctypes.c_float)]
+
+
 class LnBwdDesc(ctypes.Structure):
     _fields_ = [("x", c_p), ("dy", c_p), ("gamma", c_p), ("row_mask", c_p), ("dres", c_p), ("dx", c_p), ("dgamma", c_p), ("dbeta", c_p), ("ws", c_p),
                 ("dx2", c_p), ("M", c_i64), ("D", c_i32), ("dy_dtype", c_i32), ("dx2_dtype", c_i32), ("accumulate", c_i32),
@@ -267,6 +280,10 @@ def lib():
         L.cfm_joint_act_bwd_ws.argtypes = [c_i32, c_i32, c_i32, c_i32]
         L.cfm_rnnt_nll.argtypes = [ctypes.POINTER(RnntDesc), c_p]
         L.cfm_rnnt_grad.argtypes = [ctypes.POINTER(RnntDesc), c_p]
+        L.cfm_rnnt_packed_nll.argtypes = [ctypes.POINTER(RnntPackedDesc), c_p]
+        L.cfm_rnnt_packed_grad.argtypes = [ctypes.POINTER(RnntPackedDesc), c_p]
+        L.cfm_joint_act_packed.argtypes = [c_p, c_i64, c_p, c_i64, c_p, c_i32, ctypes.POINTER(Lattice), c_i32, c_p]
+        L.cfm_joint_act_packed_bwd.argtypes = [c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, ctypes.POINTER(Lattice), c_i32, c_p]
         c_f = ctypes.c_float
         L.cfm_gemm_tn.argtypes = [ctypes.POINTER(GemmTnDesc), c_p]
         L.cfm_gemm_tn_group.argtypes = [ctypes.POINTER(GemmTnDesc), c_i32, c_p]

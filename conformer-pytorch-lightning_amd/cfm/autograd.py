@@ -949,3 +949,67 @@ class JointRNNTLossFn(torch.autograd.Function):
         V = pk.V
         return (dxe.view(xe_shape), dxp.view(xp_shape), None, None, None, None, None, None, None, None,
                 dWe, dbe, dWp, dbp, dWo[:V], dbo[:V])
+
+
+class RNNTPackedLossFn(torch.autograd.Function):
+    """rnnt.rnnt_loss_packed: RNNTLossFn over the rows of a packed lattice (cfm.lattice.Lattice); the gradient is a buffer of its own."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, lat, blank, clamp, reduction):
+        nll, st = cfm.rnnt_nll_packed(logits, targets, lat, blank)
+        ctx.args = (st, clamp, reduction)
+        return _rnnt_reduce(nll, reduction)
+
+    @staticmethod
+    def backward(ctx, gout):
+        st, clamp, reduction = ctx.args
+        logits = st.logits
+        gs, gdev = _rnnt_scale(gout, reduction, st.desc.lat.B)
+        grad = cfm.rnnt_grad_packed(st, torch.empty(logits.shape, dtype=logits.dtype, device=logits.device), gscale=gs, gscale_dev=gdev, clamp=clamp)
+        return grad, None, None, None, None, None
+
+
+class JointRNNTPackedLossFn(torch.autograd.Function):
+    """TransducerJoint.rnnt_loss(packed=True) and TransducerJoint.forward_window: JointRNNTLossFn over a packed lattice.  Encoder rows xe2
+    [n_enc, E] and predictor rows xp2 [n_pred, P] are projected whole (they are small); the activation, the logits and the loss exist for the
+    M valid cells only, the logits once, with the gradient in place.  Rows outside the lattice get exact zero gradients."""
+
+    @staticmethod
+    def forward(ctx, xe2, xp2, mod, prec, lat, targets, blank, clamp, reduction, *params):
+        pk = packing.pack_joint_train(mod, prec)
+        e = cfm.gemm(_f32c(xe2), pk.enc.w, bias=pk.enc.b, w_lo=pk.enc.w_lo, out_dtype=torch.float32)
+        p = cfm.gemm(_f32c(xp2), pk.pred.w, bias=pk.pred.b, w_lo=pk.pred.w_lo, out_dtype=torch.float32)
+        if e.shape[1] != pk.out.w.shape[1]:
+            raise ValueError("TransducerJoint: join dimensions differ (%d, ffn_out expects %d)" % (e.shape[1], pk.out.w.shape[1]))
+        if lat.M == 0:
+            raise ValueError("TransducerJoint: no utterance has a frame (every encoder length is 0)")
+        act = cfm.joint_act_packed(e, p, lat, prec.act_dtype)
+        logits = cfm.gemm(act, pk.out.w, bias=pk.out.b, w_lo=pk.out.w_lo, out_dtype=torch.float32)
+        nll, st = cfm.rnnt_nll_packed(logits, targets, lat, blank, V=pk.V)
+        ctx.args = (pk, prec, _f32c(xe2), _f32c(xp2), e, p, act, logits, st, lat, clamp, reduction)
+        return _rnnt_reduce(nll, reduction)
+
+    @staticmethod
+    def backward(ctx, gout):
+        pk, prec, xe2, xp2, e, p, act, logits, st, lat, clamp, reduction = ctx.args
+        ctx.args = None
+        gs, gdev = _rnnt_scale(gout, reduction, lat.B)
+        Vp = logits.shape[1]
+        if prec.split:                                           # f32 gradient over the f32 logits, same bytes
+            cfm.rnnt_grad_packed(st, logits, gscale=gs, gscale_dev=gdev, clamp=clamp)
+            dlog = logits
+        else:                                                    # 16-bit gradient in the first half of each f32 row
+            half = logits.view(prec.w_dtype)                     # [M, 2 Vp]
+            cfm.rnnt_grad_packed(st, half, gscale=gs, gscale_dev=gdev, clamp=clamp, cols=Vp)
+            dlog = half[:, :Vp]
+        dWo, dbo = cfm.gemm_tn(dlog, act, want_colsum=True, mma_code=prec.w_code, split=prec.split)
+        dact = _gemm(dlog, pk.out.wt, w_lo=pk.out.wt_lo, out_dtype=torch.float32)
+        del logits, dlog, st
+        de, dp = cfm.joint_act_packed_bwd(e, p, dact, lat)
+        del dact
+        dWe, dbe = cfm.gemm_tn(de, xe2, want_colsum=True, mma_code=prec.w_code, split=prec.split)
+        dWp, dbp = cfm.gemm_tn(dp, xp2, want_colsum=True, mma_code=prec.w_code, split=prec.split)
+        dxe = _gemm(de, pk.enc.wt, w_lo=pk.enc.wt_lo, out_dtype=torch.float32)
+        dxp = _gemm(dp, pk.pred.wt, w_lo=pk.pred.wt_lo, out_dtype=torch.float32)
+        V = pk.V
+        return (dxe, dxp, None, None, None, None, None, None, None, dWe, dbe, dWp, dbp, dWo[:V], dbo[:V])

@@ -9,7 +9,7 @@ import torch
 import cfm as _c
 
 __all__ = ["stream_prep", "stream_advance", "dwconv_causal_bn_silu", "conv_cache_update", "dropout_rows", "dropout_mask", "set_deterministic", "gemm_tn", "gemm_tn_group", "layernorm_bwd", "glu_bwd", "dwconv_bn_train", "dwconv_bn_train_bwd", "col2im_relu_bwd", "conv1_wgrad", "attention_bwd",
-           "ctc_nll_train", "ctc_nll_train_groups", "ctc_grad", "rnnt_nll", "rnnt_grad", "joint_act_bwd", "ffn_split", "adam_step", "adam_clip_step", "sumsq", "scratch_stats",
+           "ctc_nll_train", "ctc_nll_train_groups", "ctc_grad", "rnnt_nll", "rnnt_grad", "joint_act_bwd", "rnnt_nll_packed", "rnnt_grad_packed", "joint_act_packed", "joint_act_packed_bwd", "ffn_split", "adam_step", "adam_clip_step", "sumsq", "scratch_stats",
            "gemm", "ffn_fused", "ffn_fused_supported", "rowchain", "rowchain_supported", "rowchain_pair_supported", "layernorm", "attention", "kv_cache_pack", "dwconv_bn_silu", "conv1_relu", "conv1_relu_mma_supported", "conv12_relu", "conv12_supported", "ctc_nll", "joint_act", "valid_mask", "chunk_mask",
            "attn_mask_combine", "cast", "add_rows", "scratch", "prof_enable", "prof_reset", "prof_table", "as_u8_mask"]
 
@@ -820,6 +820,94 @@ def joint_act_bwd(enc, pred, dact, B, T, U):
     _c.check(_c.lib().cfm_joint_act_bwd(enc.data_ptr(), enc.stride(0), pred.data_ptr(), pred.stride(0), dact.data_ptr(), de.data_ptr(), dp.data_ptr(),
                                         ws.data_ptr(), B, T, U, J, _c.stream()), "cfm_joint_act_bwd")
     return de, dp
+
+
+def joint_act_packed(enc, pred, lat, out_dtype):
+    """tanh(enc[enc_row0[b]+t] + pred[pred_row0[b]+u]) for the valid cells of a packed lattice (cfm.lattice.Lattice) as a row-major [M, J]
+    operand (include/cfm.h cfm_joint_act_packed).  enc f32 [n_enc, J], pred f32 [n_pred, J] with unit inner stride."""
+    _c.require_hip(enc, pred)
+    enc, pred = _rows2d(enc, "joint_act_packed(enc)"), _rows2d(pred, "joint_act_packed(pred)")
+    J, d = enc.shape[1], lat.desc
+    if enc.dtype != torch.float32 or pred.dtype != torch.float32 or tuple(enc.shape) != (d.n_enc, J) or tuple(pred.shape) != (d.n_pred, J):
+        raise ValueError("cfm.joint_act_packed: enc must be f32 [%d,J] and pred f32 [%d,J], got %s %s" % (d.n_enc, d.n_pred, tuple(enc.shape), tuple(pred.shape)))
+    out = torch.empty((lat.M, J), dtype=out_dtype, device=enc.device)
+    _c.check(_c.lib().cfm_joint_act_packed(_c.ptr(enc), enc.stride(0), _c.ptr(pred), pred.stride(0), _c.ptr(out), _c.dt_code(out), ctypes.byref(d), J,
+                                           _c.stream()), "cfm_joint_act_packed")
+    return out
+
+
+def joint_act_packed_bwd(enc, pred, dact, lat):
+    """Backward of cfm_joint_act_packed: (d_enc f32 [n_enc,J], d_pred f32 [n_pred,J]) from dact f32 [M, J]; rows outside the lattice are exact
+    zeros (include/cfm.h cfm_joint_act_packed_bwd)."""
+    _c.require_hip(enc, pred, dact)
+    enc, pred = _rows2d(enc, "joint_act_packed_bwd(enc)"), _rows2d(pred, "joint_act_packed_bwd(pred)")
+    J, d = enc.shape[1], lat.desc
+    if (enc.dtype, pred.dtype, dact.dtype) != (torch.float32,) * 3 or tuple(enc.shape) != (d.n_enc, J) or tuple(pred.shape) != (d.n_pred, J) \
+            or tuple(dact.shape) != (lat.M, J) or not dact.is_contiguous():
+        raise ValueError("cfm.joint_act_packed_bwd: enc f32 [%d,J], pred f32 [%d,J], dact contiguous f32 [%d,J] expected" % (d.n_enc, d.n_pred, lat.M))
+    de = torch.empty((d.n_enc, J), dtype=torch.float32, device=enc.device)
+    dp = torch.empty((d.n_pred, J), dtype=torch.float32, device=enc.device)
+    ws = torch.empty((max(lat.n_blk, 1), J), dtype=torch.float32, device=enc.device)
+    _c.check(_c.lib().cfm_joint_act_packed_bwd(enc.data_ptr(), enc.stride(0), pred.data_ptr(), pred.stride(0), dact.data_ptr(), de.data_ptr(),
+                                               dp.data_ptr(), ws.data_ptr(), ctypes.byref(d), J, _c.stream()), "cfm_joint_act_packed_bwd")
+    return de, dp
+
+
+def rnnt_nll_packed(logits, targets, lat, blank, V=None, sweep=None):
+    """RNN-T negative log-likelihood per utterance over a packed lattice (cfm.lattice.Lattice): UN-normalised logits [M, >=V] (unit inner stride;
+    f32 / bf16 / fp16), targets int32 [B, >= max U] contiguous (include/cfm.h cfm_rnnt_packed_nll).  Returns (nll f32 [B], RnntState) as rnnt_nll;
+    the state's lse / lp_blank / lp_label / alpha / beta are [M]."""
+    _c.require_hip(logits, targets)
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[0] != lat.M:
+        raise ValueError("cfm.rnnt_nll_packed: logits must be [M=%d, V] with unit inner stride, got %s strides %s" % (lat.M, tuple(logits.shape), logits.stride()))
+    W = logits.shape[1]
+    V = W if V is None else V
+    if not 1 < V <= W:
+        raise ValueError("cfm.rnnt_nll_packed: V = %d with %d columns" % (V, W))
+    if targets.dtype != torch.int32 or not targets.is_contiguous() or targets.dim() != 2 or targets.shape[0] != lat.B or targets.shape[1] < lat.U1_max - 1:
+        raise ValueError("cfm.rnnt_nll_packed: targets must be contiguous int32 [B=%d, >=%d], got %s" % (lat.B, lat.U1_max - 1, tuple(targets.shape)))
+    if sweep is None:
+        sweep = os.environ.get("CFM_RNNT_SWEEP", "auto")
+    dev, B, M = logits.device, lat.B, lat.M
+    f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    tens = dict(lse=f(M), lp_blank=f(M), lp_label=f(M), alpha=f(M), beta=f(M), shift=f(B, lat.T_max + lat.U1_max), nll=f(B), nll_shifted=f(B),
+                ll_alpha=f(B), targets=targets, lattice=lat)
+    d = _c.RnntPackedDesc()
+    d.lat = lat.desc
+    d.logits, d.ld, d.logits_dtype = logits.data_ptr() if M else None, logits.stride(0) if M else V, _c.dt_code(logits)
+    if not M:                                                          # no node: nothing is read, but the row-pass checks want a pointer
+        d.logits = tens["nll"].data_ptr()
+    d.V, d.blank, d.ld_targets = V, blank, targets.shape[1]
+    for name in ("targets", "lse", "lp_blank", "lp_label", "alpha", "beta", "shift", "nll", "nll_shifted", "ll_alpha"):
+        t = tens[name]
+        setattr(d, name, t.data_ptr() if t.numel() else tens["nll"].data_ptr() if name != "targets" else None)
+    d.sweep = _RNNT_SWEEPS[sweep] if isinstance(sweep, str) else int(sweep)
+    _c.check(_c.lib().cfm_rnnt_packed_nll(ctypes.byref(d), _c.stream()), "cfm_rnnt_packed_nll")
+    return tens["nll"], RnntState(d, logits, tens)
+
+
+def rnnt_grad_packed(state, out, gscale=1.0, gscale_dev=None, clamp=-1.0, cols=None):
+    """rnnt_grad over a packed lattice: out [M, >=cols] (f32 / bf16 / fp16, unit inner stride; may be the logits buffer itself, include/cfm.h
+    cfm_rnnt_packed_grad).  gscale_dev: a device scalar, or [B] per utterance.  Returns out."""
+    _c.require_hip(out, gscale_dev)
+    d = state.desc
+    M, B = d.lat.M, d.lat.B
+    if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] != M:
+        raise ValueError("cfm.rnnt_grad_packed: out must be [M=%d, cols] with unit inner stride, got %s" % (M, tuple(out.shape)))
+    if not M:
+        return out
+    d.grad, d.ld_grad, d.grad_dtype = out.data_ptr(), out.stride(0), _c.dt_code(out)
+    d.grad_cols = out.size(1) if cols is None else cols
+    d.gscale, d.clamp = float(gscale), float(clamp)
+    if gscale_dev is not None:
+        if gscale_dev.dtype != torch.float32 or not gscale_dev.is_contiguous() or gscale_dev.numel() not in (1, B):
+            raise ValueError("cfm.rnnt_grad_packed: gscale_dev must be a contiguous float32 scalar or [B]")
+        d.gscale_dev, d.gscale_stride = gscale_dev.data_ptr(), 1 if gscale_dev.numel() == B and B > 1 else 0
+    else:
+        d.gscale_dev, d.gscale_stride = None, 0
+    _c.check(_c.lib().cfm_rnnt_packed_grad(ctypes.byref(d), _c.stream()), "cfm_rnnt_packed_grad")
+    d.grad, d.gscale_dev = None, None
+    return out
 
 
 def adam_step(p, g, m, v, lr, betas, eps, weight_decay, step, grad_scale=None):

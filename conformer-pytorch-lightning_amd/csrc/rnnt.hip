@@ -24,6 +24,11 @@
 //          (clamped before the upstream scale, as torchaudio does), exact zeros outside t < T_b, u <= U_b and in the columns V..grad_cols-1.
 //          The output may alias the logits: each lane writes only bytes of its row that the wavefront has already read (same element size:
 //          the same bytes; a 16-bit gradient over f32 logits: the first half of the row), so the pointers are not declared __restrict__.
+//
+// Packed lattices (cfm_rnnt_packed_nll / _grad, include/cfm.h cfm_lattice): the same three kernels, instantiated on cfm_rnnt_packed_desc.  Only the
+// valid nodes have rows (utterance b: rows off[b] + t (U_b+1) + u), so the row and gradient passes launch over M = sum T_b (U_b+1) rows and find
+// their utterance by a binary search over off (B is a few hundred at most: <= 9 probes of an L2-resident array, next to a V-wide row).  The
+// per-node code is shared through utt_geo (where utterance b's nodes live): a node's arithmetic, and so each cost, is the same bits either way.
 #include "cfm_common.h"
 
 namespace {
@@ -77,22 +82,71 @@ __device__ __forceinline__ void st4(void* p, int64_t i, const f32x4& v) {
     }
 }
 
-__device__ __forceinline__ int label_at(const int* __restrict__ targets, int b, int U, int u, int V) {
-    const int y = targets[(int64_t)b * U + u];             // labels outside [0, V) cannot index a row: clamped (torchaudio would raise)
+__device__ __forceinline__ int label_at(const int* __restrict__ tg, int u, int V) {
+    const int y = tg[u];                                   // labels outside [0, V) cannot index a row: clamped (torchaudio would raise)
     return y < 0 ? 0 : (y < V ? y : V - 1);
 }
 
+// where utterance b's nodes live: node (t, u) at base + t * ld + u (t < Tb, u <= Ub); o_t at shift[t], q_u at shift[qoff + u]; labels at tg[u]
+struct UttGeo {
+    int64_t base;
+    int ld, Tb, Ub;
+    float* shift;
+    int qoff;
+    const int32_t* tg;
+};
+
+__host__ __device__ __forceinline__ int n_utt(const cfm_rnnt_desc& d) { return d.B; }
+__host__ __device__ __forceinline__ int n_utt(const cfm_rnnt_packed_desc& d) { return d.lat.B; }
+
+__device__ __forceinline__ UttGeo utt_geo(const cfm_rnnt_desc& d, int b) {
+    return {(int64_t)b * d.T * d.U1, d.U1, min(max(d.logit_lens[b], 0), d.T), min(max(d.target_lens[b], 0), d.U1 - 1),
+            d.shift + (int64_t)b * (d.T + d.U1), d.T, d.targets + (int64_t)b * (d.U1 - 1)};
+}
+
+__device__ __forceinline__ UttGeo utt_geo(const cfm_rnnt_packed_desc& d, int b) {
+    const int Ub = d.lat.U[b];
+    return {d.lat.off[b], Ub + 1, d.lat.T[b], Ub, d.shift + (int64_t)b * (d.lat.T_max + d.lat.U1_max), d.lat.T_max, d.targets + (int64_t)b * d.ld_targets};
+}
+
+// row r -> (b, t, u); padded: every (b, t < T, u < U1) has a row (the caller checks t < Tb, u <= Ub); packed: the last b with off[b] <= r
+__device__ __forceinline__ void locate(const cfm_rnnt_desc& d, int64_t r, int& b, int& t, int& u) {
+    b = (int)(r / ((int64_t)d.T * d.U1));
+    const int rem = (int)(r - (int64_t)b * d.T * d.U1);
+    t = rem / d.U1;
+    u = rem - t * d.U1;
+}
+
+__device__ __forceinline__ void locate(const cfm_rnnt_packed_desc& d, int64_t r, int& b, int& t, int& u) {
+    const int64_t* off = d.lat.off;
+    int lo = 0, hi = d.lat.B - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (off[mid] <= r) lo = mid;
+        else hi = mid - 1;
+    }
+    b = lo;
+    const int U1 = d.lat.U[b] + 1;
+    const int rem = (int)(r - off[b]);
+    t = rem / U1;
+    u = rem - t * U1;
+}
+
+__host__ __device__ __forceinline__ int64_t n_rows(const cfm_rnnt_desc& d) { return (int64_t)d.B * d.T * d.U1; }
+__host__ __device__ __forceinline__ int64_t n_rows(const cfm_rnnt_packed_desc& d) { return d.lat.M; }
+
 // ---- rows: grid = ceil(B T U1 / 4) workgroups of 4 wavefronts, wavefront = one node ----
-template <typename TI, bool VEC>
-__global__ __launch_bounds__(256) void cfm_rnnt_rows_kernel(cfm_rnnt_desc d) {
+template <typename D, typename TI, bool VEC>
+__global__ __launch_bounds__(256) void cfm_rnnt_rows_kernel(D d) {
     const int lane = threadIdx.x & 63;
     const int64_t row_id = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int T = d.T, U1 = d.U1, V = d.V;
-    if (row_id >= (int64_t)d.B * T * U1) return;
-    const int b = (int)(row_id / ((int64_t)T * U1));
-    const int rem = (int)(row_id - (int64_t)b * T * U1), t = rem / U1, u = rem - t * U1;
-    const int Tb = min(max(d.logit_lens[b], 0), T), Ub = min(max(d.target_lens[b], 0), U1 - 1);
-    if (t >= Tb || u > Ub) return;                         // never read by the recursions or the gradient pass (wavefront-uniform)
+    const int V = d.V;
+    if (row_id >= n_rows(d)) return;
+    int b, t, u;
+    locate(d, row_id, b, t, u);
+    const UttGeo g = utt_geo(d, b);
+    const int Ub = g.Ub;
+    if (t >= g.Tb || u > Ub) return;                       // never read by the recursions or the gradient pass (wavefront-uniform)
     const void* row = (const char*)d.logits + row_id * d.ld * (std::is_same<TI, float>::value ? 4 : 2);
     float m = -INFINITY, s = 0.f;                          // online log-sum-exp: the row is read once
     if constexpr (VEC) {
@@ -132,21 +186,21 @@ __global__ __launch_bounds__(256) void cfm_rnnt_rows_kernel(cfm_rnnt_desc d) {
     if (lane == 0) {
         d.lse[row_id] = lse;
         d.lp_blank[row_id] = ld1<TI>(row, d.blank) - lse;
-        d.lp_label[row_id] = u < Ub ? ld1<TI>(row, label_at(d.targets, b, U1 - 1, u, V)) - lse : -INFINITY;
+        d.lp_label[row_id] = u < Ub ? ld1<TI>(row, label_at(g.tg, u, V)) - lse : -INFINITY;
     }
 }
 
 // ---- alpha | beta: one workgroup per (utterance, direction) ----
 // SHFL: NT = 64, one column per lane, the neighbour through __shfl_up / __shfl_down; otherwise NT = RNNT_NT, PER columns per thread through LDS.
-template <int NT, int PER, bool SHFL>
-__device__ __forceinline__ void rnnt_sweep(const cfm_rnnt_desc& d, const int b, const bool fwd) {
+template <int NT, int PER, bool SHFL, typename Desc>
+__device__ __forceinline__ void rnnt_sweep(const Desc& d, const int b, const bool fwd) {
     __shared__ float sh_o[RNNT_MAXT];
     __shared__ float sh_q[RNNT_MAXU1];
     __shared__ float pub[SHFL ? 1 : 2][SHFL ? 1 : RNNT_MAXU1 + 2];
     __shared__ double red[NT];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int T = d.T, U1 = d.U1;
-    const int Tb = min(max(d.logit_lens[b], 0), T), Ub = min(max(d.target_lens[b], 0), U1 - 1);
+    const UttGeo g = utt_geo(d, b);
+    const int U1 = g.ld, Tb = g.Tb, Ub = g.Ub;
     if (Tb == 0) {                                         // no frame: no alignment (torchaudio rejects it); +inf, zero gradient
         if (tid == 0) {
             if (fwd) d.ll_alpha[b] = -INFINITY;
@@ -154,7 +208,7 @@ __device__ __forceinline__ void rnnt_sweep(const cfm_rnnt_desc& d, const int b, 
         }
         return;
     }
-    const int64_t base = (int64_t)b * T * U1;
+    const int64_t base = g.base;
     const float* lb = d.lp_blank + base;
     const float* ll = d.lp_label + base;
     // shifts: o_t over the valid columns (a wavefront per frame), q_u over the valid frames (a thread per label)
@@ -180,10 +234,10 @@ __device__ __forceinline__ void rnnt_sweep(const cfm_rnnt_desc& d, const int b, 
     if constexpr (!SHFL)
         for (int i = tid; i < RNNT_MAXU1 + 2; i += NT) pub[0][i] = pub[1][i] = -INFINITY;
     __syncthreads();
-    float* shift = d.shift + (int64_t)b * (T + U1);
+    float* shift = g.shift;
     if (fwd) {                                             // the gradient pass reads the shifts from here
         for (int t = tid; t < Tb; t += NT) shift[t] = sh_o[t];
-        for (int u = tid; u < Ub; u += NT) shift[T + u] = sh_q[u];
+        for (int u = tid; u < Ub; u += NT) shift[g.qoff + u] = sh_q[u];
     }
     float* out = (fwd ? d.alpha : d.beta) + base;
     const int D = Tb + Ub;                                 // diagonals 0 .. Tb-1+Ub
@@ -258,23 +312,24 @@ __device__ __forceinline__ void rnnt_sweep(const cfm_rnnt_desc& d, const int b, 
     }
 }
 
-template <int NT, int PER, bool SHFL>
-__global__ __launch_bounds__(NT) void cfm_rnnt_alpha_beta_kernel(cfm_rnnt_desc d) {
-    const int wg = (int)blockIdx.x;
-    if (wg < d.B) rnnt_sweep<NT, PER, SHFL>(d, wg, true);
-    else rnnt_sweep<NT, PER, SHFL>(d, wg - d.B, false);
+template <int NT, int PER, bool SHFL, typename D>
+__global__ __launch_bounds__(NT) void cfm_rnnt_alpha_beta_kernel(D d) {
+    const int wg = (int)blockIdx.x, B = n_utt(d);
+    if (wg < B) rnnt_sweep<NT, PER, SHFL>(d, wg, true);
+    else rnnt_sweep<NT, PER, SHFL>(d, wg - B, false);
 }
 
 // ---- gradient: one wavefront per row (b, t, u), all rows ----
-template <typename TI, typename TO, bool VEC>
-__global__ __launch_bounds__(256) void cfm_rnnt_grad_kernel(cfm_rnnt_desc d) {
+template <typename D, typename TI, typename TO, bool VEC>
+__global__ __launch_bounds__(256) void cfm_rnnt_grad_kernel(D d) {
     const int lane = threadIdx.x & 63;
     const int64_t row_id = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int T = d.T, U1 = d.U1, V = d.V, ncols = d.grad_cols;
-    if (row_id >= (int64_t)d.B * T * U1) return;
-    const int b = (int)(row_id / ((int64_t)T * U1));
-    const int rem = (int)(row_id - (int64_t)b * T * U1), t = rem / U1, u = rem - t * U1;
-    const int Tb = min(max(d.logit_lens[b], 0), T), Ub = min(max(d.target_lens[b], 0), U1 - 1);
+    const int V = d.V, ncols = d.grad_cols;
+    if (row_id >= n_rows(d)) return;
+    int b, t, u;
+    locate(d, row_id, b, t, u);
+    const UttGeo g = utt_geo(d, b);
+    const int U1 = g.ld, Tb = g.Tb, Ub = g.Ub;
     const void* row = (const char*)d.logits + row_id * d.ld * (std::is_same<TI, float>::value ? 4 : 2);
     void* grow = (char*)d.grad + row_id * d.ld_grad * (std::is_same<TO, float>::value ? 4 : 2);
     const float nls = d.nll_shifted[b];
@@ -286,8 +341,8 @@ __global__ __launch_bounds__(256) void cfm_rnnt_grad_kernel(cfm_rnnt_desc d) {
         }
         return;
     }
-    const int64_t node = (int64_t)b * T * U1 + (int64_t)t * U1 + u;
-    const float* shift = d.shift + (int64_t)b * (T + U1);
+    const int64_t node = g.base + (int64_t)t * U1 + u;
+    const float* shift = g.shift;
     const float ll = -nls, a = d.alpha[node];
     const float lse = d.lse[node];
     const float c0 = lse - (a + d.beta[node] - ll);                  // exp(L[v] - c0) = softmax[v] * posterior of the node
@@ -297,8 +352,8 @@ __global__ __launch_bounds__(256) void cfm_rnnt_grad_kernel(cfm_rnnt_desc d) {
     float cl = 0.f;
     int y = -1;
     if (u < Ub) {
-        y = label_at(d.targets, b, U1 - 1, u, V);
-        cl = __expf(a + (d.lp_label[node] - shift[T + u]) + d.beta[node + 1] - ll);
+        y = label_at(g.tg, u, V);
+        cl = __expf(a + (d.lp_label[node] - shift[g.qoff + u]) + d.beta[node + 1] - ll);
     }
     const int blank = d.blank;
     const float gs = d.gscale * (d.gscale_dev ? d.gscale_dev[(int64_t)b * d.gscale_stride] : 1.f);
@@ -341,33 +396,84 @@ int rnnt_check(const cfm_rnnt_desc* d, const char* what) {
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-template <typename TI>
-int launch_rows(const cfm_rnnt_desc& d, hipStream_t s, CfmProfScope& prof) {
-    const int64_t rows = (int64_t)d.B * d.T * d.U1;
+template <typename D, typename TI>
+int launch_rows(const D& d, hipStream_t s, CfmProfScope& prof) {
+    const int64_t rows = n_rows(d);
     const dim3 grid((unsigned)((rows + 3) / 4));
     const bool vec = d.ld % 4 == 0 && (std::is_same<TI, float>::value ? aligned16(d.logits) : ((uintptr_t)d.logits & 7) == 0);
-    if (vec) CFM_LAUNCH((cfm_rnnt_rows_kernel<TI, true>), grid, dim3(256), 0, s, d);
-    else CFM_LAUNCH((cfm_rnnt_rows_kernel<TI, false>), grid, dim3(256), 0, s, d);
+    if (vec) CFM_LAUNCH((cfm_rnnt_rows_kernel<D, TI, true>), grid, dim3(256), 0, s, d);
+    else CFM_LAUNCH((cfm_rnnt_rows_kernel<D, TI, false>), grid, dim3(256), 0, s, d);
     return CFM_OK;
 }
 
-template <typename TI, typename TO>
-int launch_grad(const cfm_rnnt_desc& d, hipStream_t s, CfmProfScope& prof) {
-    const int64_t rows = (int64_t)d.B * d.T * d.U1;
+template <typename D, typename TI, typename TO>
+int launch_grad(const D& d, hipStream_t s, CfmProfScope& prof) {
+    const int64_t rows = n_rows(d);
     const dim3 grid((unsigned)((rows + 3) / 4));
     const bool in_ok = std::is_same<TI, float>::value ? aligned16(d.logits) : ((uintptr_t)d.logits & 7) == 0;
     const bool out_ok = std::is_same<TO, float>::value ? aligned16(d.grad) : ((uintptr_t)d.grad & 7) == 0;
     const bool vec = d.ld % 4 == 0 && d.ld_grad % 4 == 0 && d.grad_cols % 4 == 0 && in_ok && out_ok;
-    if (vec) CFM_LAUNCH((cfm_rnnt_grad_kernel<TI, TO, true>), grid, dim3(256), 0, s, d);
-    else CFM_LAUNCH((cfm_rnnt_grad_kernel<TI, TO, false>), grid, dim3(256), 0, s, d);
+    if (vec) CFM_LAUNCH((cfm_rnnt_grad_kernel<D, TI, TO, true>), grid, dim3(256), 0, s, d);
+    else CFM_LAUNCH((cfm_rnnt_grad_kernel<D, TI, TO, false>), grid, dim3(256), 0, s, d);
     return CFM_OK;
 }
 
-template <typename TI>
-int launch_grad_out(const cfm_rnnt_desc& d, hipStream_t s, CfmProfScope& prof) {
-    if (d.grad_dtype == CFM_F32) return launch_grad<TI, float>(d, s, prof);
-    if (d.grad_dtype == CFM_BF16) return launch_grad<TI, BF16>(d, s, prof);
-    return launch_grad<TI, F16>(d, s, prof);
+template <typename D, typename TI>
+int launch_grad_out(const D& d, hipStream_t s, CfmProfScope& prof) {
+    if (d.grad_dtype == CFM_F32) return launch_grad<D, TI, float>(d, s, prof);
+    if (d.grad_dtype == CFM_BF16) return launch_grad<D, TI, BF16>(d, s, prof);
+    return launch_grad<D, TI, F16>(d, s, prof);
+}
+
+int rnnt_packed_check(const cfm_rnnt_packed_desc* d, const char* what) {
+    CFM_CHECK_ARG(d && d->logits && d->lat.off && d->lat.T && d->lat.U && d->lse && d->lp_blank && d->lp_label && d->alpha && d->beta && d->shift &&
+                  d->nll && d->nll_shifted, "%s: null pointer", what);
+    const cfm_lattice& L = d->lat;
+    CFM_CHECK_ARG(L.B > 0 && L.M >= 0 && L.T_max >= 0 && L.U1_max > 0 && d->V > 1, "%s: bad shape B=%d M=%lld T_max=%d U1_max=%d V=%d", what, L.B,
+                  (long long)L.M, L.T_max, L.U1_max, d->V);
+    CFM_CHECK_ARG(L.U1_max <= RNNT_MAXU1, "%s: U+1 = %d exceeds %d", what, L.U1_max, RNNT_MAXU1);
+    CFM_CHECK_ARG(L.T_max <= RNNT_MAXT, "%s: T = %d frames exceeds %d", what, L.T_max, RNNT_MAXT);
+    CFM_CHECK_ARG(L.U1_max == 1 || (d->targets && d->ld_targets >= L.U1_max - 1), "%s: targets is null or ld_targets < U1_max - 1", what);
+    CFM_CHECK_ARG(d->blank >= 0 && d->blank < d->V, "%s: blank %d outside [0, %d)", what, d->blank, d->V);
+    CFM_CHECK_ARG(d->ld >= d->V, "%s: row stride %lld < V = %d", what, (long long)d->ld, d->V);
+    CFM_CHECK_ARG(d->logits_dtype >= CFM_F32 && d->logits_dtype <= CFM_F16, "%s: bad logits dtype", what);
+    return CFM_OK;
+}
+
+template <typename D>
+int rnnt_nll_launch(const D& d, const char* what, hipStream_t s) {
+    const int64_t rows = n_rows(d);
+    if (rows > 0) {                                        // a packed lattice may have no node at all (every T_b = 0)
+        CfmProfScope prof("rnnt_rows", s, 0.0, (double)rows * d.V * cfm_elt_size(d.logits_dtype));
+        int rc = d.logits_dtype == CFM_F32 ? launch_rows<D, float>(d, s, prof) : d.logits_dtype == CFM_BF16 ? launch_rows<D, BF16>(d, s, prof)
+                                                                                                              : launch_rows<D, F16>(d, s, prof);
+        if (rc) return rc;
+        if (int rc2 = cfm_launch_status(what)) return rc2;
+    }
+    const bool shfl = d.sweep == 1;                        // auto = LDS: measured faster at config 4 (RNN-T loss)
+    CfmProfScope prof("rnnt_alpha_beta", s, 0.0, (double)rows * 4 * 6);
+    const int B = n_utt(d);
+    if (shfl) CFM_LAUNCH((cfm_rnnt_alpha_beta_kernel<64, 1, true, D>), dim3(2 * B), dim3(64), 0, s, d);
+    else CFM_LAUNCH((cfm_rnnt_alpha_beta_kernel<RNNT_NT, RNNT_MAXU1 / RNNT_NT, false, D>), dim3(2 * B), dim3(RNNT_NT), 0, s, d);
+    return cfm_launch_status(what);
+}
+
+template <typename D>
+int rnnt_grad_launch(const D& d, const char* what, hipStream_t s) {
+    CFM_CHECK_ARG(d.grad, "%s: null gradient", what);
+    CFM_CHECK_ARG(d.grad_dtype >= CFM_F32 && d.grad_dtype <= CFM_F16, "%s: bad gradient dtype", what);
+    CFM_CHECK_ARG(d.grad_cols >= d.V && d.ld_grad >= d.grad_cols, "%s: grad_cols %d must be in [V, ld_grad] (V = %d, ld_grad = %lld)", what,
+                  d.grad_cols, d.V, (long long)d.ld_grad);
+    if (d.grad == d.logits)                                // in place: each row's gradient must fit the bytes of its own row
+        CFM_CHECK_ARG(d.ld_grad * cfm_elt_size(d.grad_dtype) == d.ld * cfm_elt_size(d.logits_dtype) &&
+                      cfm_elt_size(d.grad_dtype) <= cfm_elt_size(d.logits_dtype), "%s: in place needs the same row bytes and a gradient no wider than the logits", what);
+    const int64_t rows = n_rows(d);
+    if (rows == 0) return CFM_OK;
+    CfmProfScope prof("rnnt_grad", s, 0.0, (double)rows * ((double)d.V * cfm_elt_size(d.logits_dtype) + (double)d.grad_cols * cfm_elt_size(d.grad_dtype)));
+    int rc = d.logits_dtype == CFM_F32 ? launch_grad_out<D, float>(d, s, prof) : d.logits_dtype == CFM_BF16 ? launch_grad_out<D, BF16>(d, s, prof)
+                                                                                                             : launch_grad_out<D, F16>(d, s, prof);
+    if (rc) return rc;
+    return cfm_launch_status(what);
 }
 
 }  // namespace
@@ -376,34 +482,23 @@ extern "C" int cfm_rnnt_nll(const cfm_rnnt_desc* d, cfm_stream_t stream) {
     if (int rc = rnnt_check(d, "cfm_rnnt_nll")) return rc;
     CFM_CHECK_ARG(d->ll_alpha, "cfm_rnnt_nll: null pointer");
     CFM_CHECK_ARG(d->sweep >= 0 && d->sweep <= 2 && !(d->sweep == 1 && d->U1 > 64), "cfm_rnnt_nll: sweep %d (1: wavefront shuffles, U+1 <= 64; 2: LDS)", d->sweep);
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t rows = (int64_t)d->B * d->T * d->U1;
-    {
-        CfmProfScope prof("rnnt_rows", s, 0.0, (double)rows * d->V * cfm_elt_size(d->logits_dtype));
-        int rc = d->logits_dtype == CFM_F32 ? launch_rows<float>(*d, s, prof) : d->logits_dtype == CFM_BF16 ? launch_rows<BF16>(*d, s, prof) : launch_rows<F16>(*d, s, prof);
-        if (rc) return rc;
-        if (int rc2 = cfm_launch_status("cfm_rnnt_nll (rows)")) return rc2;
-    }
-    const bool shfl = d->sweep == 1;                       // auto = LDS: measured faster at config 4 (RNN-T loss)
-    CfmProfScope prof("rnnt_alpha_beta", s, 0.0, (double)rows * 4 * 6);
-    if (shfl) CFM_LAUNCH((cfm_rnnt_alpha_beta_kernel<64, 1, true>), dim3(2 * d->B), dim3(64), 0, s, *d);
-    else CFM_LAUNCH((cfm_rnnt_alpha_beta_kernel<RNNT_NT, RNNT_MAXU1 / RNNT_NT, false>), dim3(2 * d->B), dim3(RNNT_NT), 0, s, *d);
-    return cfm_launch_status("cfm_rnnt_nll (alpha | beta)");
+    return rnnt_nll_launch(*d, "cfm_rnnt_nll", (hipStream_t)stream);
 }
 
 extern "C" int cfm_rnnt_grad(const cfm_rnnt_desc* d, cfm_stream_t stream) {
     if (int rc = rnnt_check(d, "cfm_rnnt_grad")) return rc;
-    CFM_CHECK_ARG(d->grad, "cfm_rnnt_grad: null gradient");
-    CFM_CHECK_ARG(d->grad_dtype >= CFM_F32 && d->grad_dtype <= CFM_F16, "cfm_rnnt_grad: bad gradient dtype");
-    CFM_CHECK_ARG(d->grad_cols >= d->V && d->ld_grad >= d->grad_cols, "cfm_rnnt_grad: grad_cols %d must be in [V, ld_grad] (V = %d, ld_grad = %lld)",
-                  d->grad_cols, d->V, (long long)d->ld_grad);
-    if (d->grad == d->logits)                              // in place: each row's gradient must fit the bytes of its own row
-        CFM_CHECK_ARG(d->ld_grad * cfm_elt_size(d->grad_dtype) == d->ld * cfm_elt_size(d->logits_dtype) &&
-                      cfm_elt_size(d->grad_dtype) <= cfm_elt_size(d->logits_dtype), "cfm_rnnt_grad: in place needs the same row bytes and a gradient no wider than the logits");
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t rows = (int64_t)d->B * d->T * d->U1;
-    CfmProfScope prof("rnnt_grad", s, 0.0, (double)rows * ((double)d->V * cfm_elt_size(d->logits_dtype) + (double)d->grad_cols * cfm_elt_size(d->grad_dtype)));
-    int rc = d->logits_dtype == CFM_F32 ? launch_grad_out<float>(*d, s, prof) : d->logits_dtype == CFM_BF16 ? launch_grad_out<BF16>(*d, s, prof) : launch_grad_out<F16>(*d, s, prof);
-    if (rc) return rc;
-    return cfm_launch_status("cfm_rnnt_grad");
+    return rnnt_grad_launch(*d, "cfm_rnnt_grad", (hipStream_t)stream);
+}
+
+extern "C" int cfm_rnnt_packed_nll(const cfm_rnnt_packed_desc* d, cfm_stream_t stream) {
+    if (int rc = rnnt_packed_check(d, "cfm_rnnt_packed_nll")) return rc;
+    CFM_CHECK_ARG(d->ll_alpha, "cfm_rnnt_packed_nll: null pointer");
+    CFM_CHECK_ARG(d->sweep >= 0 && d->sweep <= 2 && !(d->sweep == 1 && d->lat.U1_max > 64),
+                  "cfm_rnnt_packed_nll: sweep %d (1: wavefront shuffles, U+1 <= 64; 2: LDS)", d->sweep);
+    return rnnt_nll_launch(*d, "cfm_rnnt_packed_nll", (hipStream_t)stream);
+}
+
+extern "C" int cfm_rnnt_packed_grad(const cfm_rnnt_packed_desc* d, cfm_stream_t stream) {
+    if (int rc = rnnt_packed_check(d, "cfm_rnnt_packed_grad")) return rc;
+    return rnnt_grad_launch(*d, "cfm_rnnt_packed_grad", (hipStream_t)stream);
 }

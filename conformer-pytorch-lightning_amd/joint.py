@@ -12,8 +12,11 @@ joint.py:29-33.  `out_dtype` (default torch.float32, what the reference returns)
 logits take at BASELINE config 4.  `forward` has no backward: calling it in train mode with gradients enabled on parameters that require
 them raises.  Training goes through `rnnt_loss(enc_out, pred_out, targets, enc_lens, target_lens, ...)`, the joint followed by the RNN-T loss
 (torchaudio.functional.rnnt_loss at model.py:107; rnnt.py, csrc/rnnt.hip) as one differentiable step whose logits never leave it, so the
-loss gradient overwrites them in place (cfm/autograd.py JointRNNTLossFn).
+loss gradient overwrites them in place (cfm/autograd.py JointRNNTLossFn).  `rnnt_loss(..., packed=True)` builds the logits for the valid cells
+(b, t < enc_lens[b], u <= target_lens[b]) only (a packed lattice, cfm/lattice.py), and `forward_window(rows, groups)` runs the loss of every
+micro-batch of an accumulation window through one packed lattice over the window's encoder row matrix (cfm/autograd.py JointRNNTPackedLossFn).
 """
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -81,10 +84,22 @@ class TransducerJoint(nn.Module):
         out = out.view(B, T, U, pk.Vp)
         return out if pk.Vp == pk.V else out[..., :pk.V]
 
-    def rnnt_loss(self, enc_out, pred_out, targets, enc_lens, target_lens, blank=0, clamp=-1, reduction="mean"):
+    def _params(self):
+        return [self.enc_ffn.weight, self.enc_ffn.bias, self.pred_ffn.weight, self.pred_ffn.bias, self.ffn_out.weight, self.ffn_out.bias]
+
+    def _blank(self, blank, what):
+        V = self.ffn_out.weight.shape[0]
+        b = blank + V if blank < 0 else blank
+        if not 0 <= b < V:
+            raise ValueError("TransducerJoint.%s: blank %d outside a vocabulary of %d" % (what, blank, V))
+        return b
+
+    def rnnt_loss(self, enc_out, pred_out, targets, enc_lens, target_lens, blank=0, clamp=-1, reduction="mean", packed=False):
         """torchaudio.functional.rnnt_loss(self(enc_out, pred_out), targets, enc_lens, target_lens, blank, clamp, reduction) as one step
         (model.py:102-113), differentiable w.r.t. enc_out [B, T, E], pred_out [B, U+1, P] and the six joint parameters; targets [B, U].
-        Semantics as rnnt.rnnt_loss; the precision mode is cfm.resolve_precision(self)."""
+        Semantics as rnnt.rnnt_loss; the precision mode is cfm.resolve_precision(self).
+        packed=True: the joint, the logits and the loss cover only the valid cells (cfm/lattice.py): the same loss and gradients for less work
+        and memory on a ragged batch.  It copies the lengths to the host once per call (the packed offsets are their prefix sum)."""
         from cfm import autograd as ag
         if reduction not in ("none", "sum", "mean"):
             raise ValueError("TransducerJoint.rnnt_loss: reduction must be 'none', 'sum' or 'mean', got %r" % (reduction,))
@@ -99,12 +114,56 @@ class TransducerJoint(nn.Module):
         B, U1 = pred_out.size(0), pred_out.size(1)
         if tuple(targets.shape) != (B, U1 - 1):
             raise ValueError("TransducerJoint.rnnt_loss: targets %s, expected (%d, %d)" % (tuple(targets.shape), B, U1 - 1))
-        V = self.ffn_out.weight.shape[0]
-        b = blank + V if blank < 0 else blank
-        if not 0 <= b < V:
-            raise ValueError("TransducerJoint.rnnt_loss: blank %d outside a vocabulary of %d" % (blank, V))
+        b = self._blank(blank, "rnnt_loss")
         dev = enc_out.device
         i32 = lambda t: t.to(device=dev, dtype=torch.int32).contiguous()
-        params = [self.enc_ffn.weight, self.enc_ffn.bias, self.pred_ffn.weight, self.pred_ffn.bias, self.ffn_out.weight, self.ffn_out.bias]
+        params = self._params()
+        if packed:
+            from cfm import lattice
+            T = enc_out.size(1)
+            Tb, Ub = lattice.host_lengths(enc_lens, target_lens)
+            lat = lattice.Lattice.padded(Tb.clip(0, T), Ub.clip(0, U1 - 1), T, U1, dev)
+            return ag.JointRNNTPackedLossFn.apply(enc_out.reshape(B * T, enc_out.size(2)), pred_out.reshape(B * U1, pred_out.size(2)), self,
+                                                  cfm.resolve_precision(self), lat, i32(targets), b, float(clamp), reduction, *params)
         return ag.JointRNNTLossFn.apply(enc_out, pred_out, self, cfm.resolve_precision(self), i32(targets), i32(enc_lens), i32(target_lens), b,
                                         float(clamp), reduction, *params)
+
+    def forward_window(self, rows, groups, blank=0, clamp=-1):
+        """The RNN-T losses of an accumulation window through ONE packed lattice (train path; mirrors CTCDecoder.forward_window).  rows f32
+        [sum B_g T'_g, E]: the window's encoder outputs as one row matrix (ConformerEncoder.forward_window(..., return_rows=True)); groups:
+        [(B_g, T'_g, enc_lens_g, pred_out_g (B_g, U_g+1, P), targets_g (B_g, U_g), target_lens_g)] in row order.  Returns a 1-D tensor of the
+        micro-batches' losses, entry g equal to rnnt_loss(reduction="mean") on micro-batch g alone.  The lengths of all micro-batches are
+        copied to the host once per call (the lattice offsets are their prefix sum)."""
+        from cfm import autograd as ag
+        from cfm import lattice
+        cfm.require_hip(rows)
+        if rows.dim() != 2:
+            raise ValueError("TransducerJoint.forward_window: rows must be [sum B*T', E], got %s" % (tuple(rows.shape),))
+        b = self._blank(blank, "forward_window")
+        dev = rows.device
+        gs = [(int(B), int(T), el, po, tg, tl) for B, T, el, po, tg, tl in groups]
+        host = lattice.host_lengths(*[g[2] for g in gs], *[g[5] for g in gs])
+        Umax = max(g[3].size(1) for g in gs) - 1
+        Ts, Us, e0, p0, preds, tgts, r, q = [], [], [], [], [], [], 0, 0
+        for gi, (B, T, _, po, tg, _) in enumerate(gs):
+            U1 = po.size(1)
+            if po.dim() != 3 or po.size(0) != B or tuple(tg.shape) != (B, U1 - 1):
+                raise ValueError("TransducerJoint.forward_window: group %d: pred_out %s / targets %s do not match B = %d" % (gi, tuple(po.shape), tuple(tg.shape), B))
+            Ts.append(host[gi].clip(0, T))
+            Us.append(host[len(gs) + gi].clip(0, U1 - 1))
+            e0.append(r + np.arange(B) * T)
+            p0.append(q + np.arange(B) * U1)
+            preds.append(po.reshape(B * U1, po.size(2)))
+            tgts.append(nn.functional.pad(tg.to(device=dev, dtype=torch.int32), (0, Umax - (U1 - 1))))
+            r, q = r + B * T, q + B * U1
+        if rows.size(0) != r:
+            raise ValueError("TransducerJoint.forward_window: rows has %d rows, the groups describe %d" % (rows.size(0), r))
+        cat = lambda xs: xs[0] if len(xs) == 1 else torch.cat(xs, 0)
+        lat = lattice.Lattice(np.concatenate(Ts), np.concatenate(Us), np.concatenate(e0), np.concatenate(p0), r, q, dev)
+        nll = ag.JointRNNTPackedLossFn.apply(rows, cat(preds), self, cfm.resolve_precision(self), lat, cat(tgts).contiguous(), b, float(clamp),
+                                             "none", *self._params())
+        losses, s = [], 0
+        for B, *_ in gs:
+            losses.append(nll[s:s + B].mean())
+            s += B
+        return torch.stack(losses)

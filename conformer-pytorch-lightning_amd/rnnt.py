@@ -11,12 +11,17 @@ synchronisation); an utterance with logit_lengths[b] = 0 costs +inf with a zero 
 
 The kernels are csrc/rnnt.hip (a row pass, the alpha and beta recursions in one launch, a gradient pass; include/cfm.h cfm_rnnt_*).  There is
 no CPU path.  TransducerJoint.rnnt_loss runs the joint and this loss as one differentiable step without a second logits-sized buffer.
+
+    rnnt_loss_packed(logits, targets, logit_lengths, target_lengths, blank=-1, clamp=-1, reduction="mean")
+
+The same loss over a packed lattice (cfm/lattice.py): logits [M, V] hold only the valid nodes, utterance b's T_b (U_b+1) rows in (t, u) order
+after those of utterances 0..b-1 (M = sum_b T_b (U_b+1), T_b = logit_lengths[b], U_b = target_lengths[b]).
 """
 import torch
 
 import cfm
 
-__all__ = ["rnnt_loss"]
+__all__ = ["rnnt_loss", "rnnt_loss_packed"]
 
 
 def _i32(t, device):
@@ -44,3 +49,32 @@ def rnnt_loss(logits, targets, logit_lengths, target_lengths, blank=-1, clamp=-1
     from cfm import autograd as ag
     dev = logits.device
     return ag.RNNTLossFn.apply(x, _i32(targets, dev), _i32(logit_lengths, dev), _i32(target_lengths, dev), b, float(clamp), reduction)
+
+
+def rnnt_loss_packed(logits, targets, logit_lengths, target_lengths, blank=-1, clamp=-1, reduction="mean"):
+    """rnnt_loss over a packed lattice: logits [M, V], row sum_{b'<b} T_b' (U_b'+1) + t (U_b+1) + u = node (b, t, u); targets [B, >= max U_b];
+    the same costs and gradient rows as rnnt_loss on the same nodes (csrc/rnnt.hip, cfm_rnnt_packed_*).  Lengths are clipped to >= 0 and
+    target_lengths to targets.size(1).  The row offsets are a prefix sum of the lengths: the lengths are copied to the host ONCE per call
+    (the call's only synchronisation with the device)."""
+    from cfm import lattice
+    if reduction not in ("none", "sum", "mean"):
+        raise ValueError("rnnt_loss_packed: reduction must be 'none', 'sum' or 'mean', got %r" % (reduction,))
+    cfm.require_hip(logits, targets, logit_lengths, target_lengths)
+    if logits.dim() != 2:
+        raise ValueError("rnnt_loss_packed: logits must be [M, V], got %s" % (tuple(logits.shape),))
+    M, V = logits.shape
+    B = logit_lengths.numel()
+    if targets.dim() != 2 or targets.size(0) != B or target_lengths.numel() != B or B == 0:
+        raise ValueError("rnnt_loss_packed: targets %s / lengths %s, %s do not describe one batch" % (tuple(targets.shape), tuple(logit_lengths.shape),
+                                                                                                    tuple(target_lengths.shape)))
+    b = blank + V if blank < 0 else blank
+    if not 0 <= b < V:
+        raise ValueError("rnnt_loss_packed: blank %d outside a vocabulary of %d" % (blank, V))
+    T, U = lattice.host_lengths(logit_lengths, target_lengths)
+    T, U = T.clip(0, None), U.clip(0, targets.size(1))
+    lat = lattice.Lattice.padded(T, U, max(int(T.max()), 1), int(U.max()) + 1, logits.device)
+    if lat.M != M:
+        raise ValueError("rnnt_loss_packed: logits have %d rows, the lengths describe %d nodes" % (M, lat.M))
+    x = logits if logits.stride(1) == 1 else logits.contiguous()
+    from cfm import autograd as ag
+    return ag.RNNTPackedLossFn.apply(x, _i32(targets, logits.device), lat, b, float(clamp), reduction)

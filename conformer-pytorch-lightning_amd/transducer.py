@@ -1,0 +1,69 @@
+"""The reference's training objective -- `Transducer.forward` / `rnnt_loss` / `ctc_loss` of src/model.py:71-124 -- over this repository's modules.
+
+    loss = ctc_weight * CTC + transducer_weight * RNN-T                  (model.py:84; train.sh: 0.2 and 0.8)
+
+`TransducerObjective.forward(batch)` takes the reference's 6-tuple batch and returns its dict (model.py:89-93).  The wiring is model.py:95-124:
+the predictor reads add_blank(labels) (a blank in front, ignore_id -> blank), the RNN-T targets are where(labels == ignore_id, blank, labels),
+the CTC loss is summed.  The joint and the RNN-T loss are one step over a packed lattice (TransducerJoint.rnnt_loss(packed=True); packed=False
+selects the padded joint).
+
+`forward_window(micro_batches)` is the same objective over a whole accumulation window, one loss per micro-batch -- the
+`DataParallelTrainer(window_loss_fn=...)` form: ConformerEncoder.forward_window(return_rows=True), CTCDecoder.forward_window over the row matrix,
+the predictor ONCE for the window (label matrices padded to the window's longest with ignore_id; the LSTM is causal, so what a micro-batch's rows
+read does not change), and TransducerJoint.forward_window, whose packed lattice spans every micro-batch's valid cells.
+"""
+import torch
+import torch.nn as nn
+
+import utils
+
+
+class TransducerObjective(nn.Module):
+
+    def __init__(self, encoder, predictor, joint, ctc, blank=0, ignore_id=-1, ctc_weight=0.0, transducer_weight=1.0, packed=True):
+        super().__init__()
+        self.encoder, self.predictor, self.joint, self.ctc = encoder, predictor, joint, ctc
+        self.blank, self.ignore_id = blank, ignore_id
+        self.ctc_weight, self.transducer_weight = ctc_weight, transducer_weight
+        self.packed = packed
+
+    def _text(self, labels):
+        return torch.where(labels == self.ignore_id, self.blank, labels).to(torch.int32)
+
+    def rnnt_loss(self, encoder_out, encoder_out_lens, padded_labels, label_lengths):
+        """model.py:95-113."""
+        predictor_out = self.predictor(utils.add_blank(padded_labels, self.blank, self.ignore_id))
+        return self.joint.rnnt_loss(encoder_out, predictor_out, self._text(padded_labels), encoder_out_lens.to(torch.int32),
+                                    label_lengths.to(torch.int32), blank=self.blank, reduction="mean", packed=self.packed)
+
+    def forward(self, batch):
+        _, padded_feats, feats_length, padded_labels, label_lengths, _ = batch
+        encoder_out, encoder_mask = self.encoder(padded_feats, feats_length)
+        encoder_out_lens = encoder_mask.squeeze(1).sum(1)
+        loss_rnnt = self.rnnt_loss(encoder_out, encoder_out_lens, padded_labels, label_lengths)
+        loss_ctc = self.ctc(encoder_out, encoder_out_lens, padded_labels, label_lengths).sum()
+        loss = self.ctc_weight * loss_ctc + self.transducer_weight * loss_rnnt
+        return {"loss": loss, "loss_ctc": loss_ctc, "loss_rnnt": loss_rnnt, "encoder_out": encoder_out, "encoder_out_lens": encoder_out_lens}
+
+    def forward_window(self, micro_batches):
+        """The losses of an accumulation window's micro-batches (each the reference's 6-tuple), a 1-D tensor whose entry g equals
+        forward(micro_batches[g])["loss"] (train mode; dropout masks differ, as between any two calls)."""
+        rows, outs = self.encoder.forward_window([(mb[1], mb[2]) for mb in micro_batches], return_rows=True)
+        ctc_groups, shapes = [], []
+        for (y, mask), mb in zip(outs, micro_batches):
+            B, T = y.shape[0], y.shape[1]
+            lens = mask.squeeze(1).sum(1)
+            ctc_groups.append((B, T, lens, mb[3], mb[4]))
+            shapes.append((B, T, lens))
+        loss_ctc = self.ctc.forward_window(rows, ctc_groups)
+        labels = [mb[3] for mb in micro_batches]
+        Umax = max(lab.size(1) for lab in labels)
+        window = torch.cat([nn.functional.pad(lab, (0, Umax - lab.size(1)), value=self.ignore_id) for lab in labels], 0)
+        pred = self.predictor(utils.add_blank(window, self.blank, self.ignore_id))              # (sum B_g, Umax + 1, P)
+        groups, s = [], 0
+        for (B, T, lens), lab, mb in zip(shapes, labels, micro_batches):
+            U1 = lab.size(1) + 1
+            groups.append((B, T, lens, pred[s:s + B, :U1], self._text(lab), mb[4]))
+            s += B
+        loss_rnnt = self.joint.forward_window(rows, groups, blank=self.blank)
+        return self.ctc_weight * loss_ctc + self.transducer_weight * loss_rnnt

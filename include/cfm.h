@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CFM_VERSION 302 /* 0.3.2 (additive, same number): the RNN-T loss (cfm_rnnt_desc, cfm_rnnt_nll, cfm_rnnt_grad) and the transducer joint's activation backward (cfm_joint_act_bwd). 0.3.2: cfm_rowchain_desc.cin_* (the conv-in chain as the input stage of the next launch). 0.3.1: row chains at D = 512, cfm_rowchain_desc.psum_out / psum_in (feed-forward split over workgroup pairs), cfm_conv12_relu at C = 512. 0.3.0: row groups in the train entry points (cfm_train_group, cfm_layer_train_io.n_groups), cfm_gemm_tn_group + deferred weight gradients, cfm_encoder_train_forward / _backward (the whole stack from one host call). 0.2.3: cfm_ffn_split, cfm_layer_scratch.psum (the feed-forward split over FF for few rows). 0.2.2: cfm_ctc_nll_train / cfm_ctc_grad take a beta buffer (both recursions in one launch); GEMM tile ids 9-11 (K groups). 0.2.1: fused front-end (cfm_conv12_relu); attention stage of the conv-in chain (cfm_rowchain_desc.att_*, cfm_layer_scratch.vt). 0.2.0: training entry points */
+#define CFM_VERSION 302 /* 0.3.2 (additive, same number): packed RNN-T lattices (cfm_lattice, cfm_rnnt_packed_desc, cfm_rnnt_packed_nll / _grad, cfm_joint_act_packed / _bwd). 0.3.2 (additive, same number): the RNN-T loss (cfm_rnnt_desc, cfm_rnnt_nll, cfm_rnnt_grad) and the transducer joint's activation backward (cfm_joint_act_bwd). 0.3.2: cfm_rowchain_desc.cin_* (the conv-in chain as the input stage of the next launch). 0.3.1: row chains at D = 512, cfm_rowchain_desc.psum_out / psum_in (feed-forward split over workgroup pairs), cfm_conv12_relu at C = 512. 0.3.0: row groups in the train entry points (cfm_train_group, cfm_layer_train_io.n_groups), cfm_gemm_tn_group + deferred weight gradients, cfm_encoder_train_forward / _backward (the whole stack from one host call). 0.2.3: cfm_ffn_split, cfm_layer_scratch.psum (the feed-forward split over FF for few rows). 0.2.2: cfm_ctc_nll_train / cfm_ctc_grad take a beta buffer (both recursions in one launch); GEMM tile ids 9-11 (K groups). 0.2.1: fused front-end (cfm_conv12_relu); attention stage of the conv-in chain (cfm_rowchain_desc.att_*, cfm_layer_scratch.vt). 0.2.0: training entry points */
 
 typedef void* cfm_stream_t;
 
@@ -611,6 +611,64 @@ int cfm_rnnt_grad(const cfm_rnnt_desc* d, cfm_stream_t stream);
 int64_t cfm_joint_act_bwd_ws(int32_t B, int32_t T, int32_t U, int32_t J);
 int cfm_joint_act_bwd(const float* enc, int64_t ld_e, const float* pred, int64_t ld_p, const float* dact, float* d_enc, float* d_pred,
                       float* work, int32_t B, int32_t T, int32_t U, int32_t J, cfm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Packed ("compact") RNN-T lattices: only the valid nodes of a ragged batch get a row.  Utterance b owns the rows
+ * [off[b], off[b] + T[b] (U[b]+1)) of a [M, V] logits matrix, M = off[B]; row off[b] + t (U[b]+1) + u is node (b, t, u).  The encoder row of
+ * (b, t) is enc_row0[b] + t and the predictor row of (b, u) is pred_row0[b] + u, so one descriptor covers one padded batch (enc_row0[b] = b T')
+ * and the row matrix of an accumulation window whose micro-batches have different T' (ConformerEncoder.forward_window(return_rows=True)).
+ * Encoder rows are owned in order: rows [enc_row0[b], enc_row0[b+1]) (the last: up to n_enc) belong to b, the ones with t >= T[b] are padding
+ * (likewise the predictor rows with u > U[b]).  Every array is on the device and built by the caller from host lengths (the offsets are a
+ * prefix sum): T[b] >= 0 frames, U[b] >= 0 labels, T_max >= max T[b], U1_max >= max U[b] + 1; blk_off[b] = sum_{b' < b} ceil(T[b'] / 8) (U[b'] + 1)
+ * (the rows of cfm_joint_act_packed_bwd's per-frame-block partials, blk_off[B] of them).
+ */
+typedef struct {
+    int32_t B, T_max, U1_max;
+    int64_t M;                    /* = off[B] */
+    const int64_t* off;           /* [B + 1] */
+    const int32_t* T;             /* [B] */
+    const int32_t* U;             /* [B] */
+    const int64_t* enc_row0;      /* [B], nondecreasing */
+    const int64_t* pred_row0;     /* [B], nondecreasing */
+    int64_t n_enc, n_pred;        /* rows of the encoder / predictor matrices */
+    const int64_t* blk_off;       /* [B + 1] */
+} cfm_lattice;
+
+/* Joint activation over a packed lattice (csrc/joint.hip): replaces the broadcast of joint.py:31-37 (as cfm_joint_act) for the valid cells only:
+ * out [M, J] (out_dtype f32 / bf16 / f16) row off[b] + t (U[b]+1) + u = tanh(enc[enc_row0[b] + t] + pred[pred_row0[b] + u]).  J % 8 == 0.
+ * cfm_joint_act_packed_bwd: dz = dact (1 - a^2) over dact f32 [M, J], d_enc f32 [n_enc, J] = sum_u dz, d_pred f32 [n_pred, J] = sum_t dz, both in a
+ * fixed order (no atomics), exact zeros in the padding rows; work: f32 scratch of blk_off[B] * J floats. */
+int cfm_joint_act_packed(const float* enc, int64_t ld_e, const float* pred, int64_t ld_p, void* out, int32_t out_dtype, const cfm_lattice* lat,
+                         int32_t J, cfm_stream_t stream);
+int cfm_joint_act_packed_bwd(const float* enc, int64_t ld_e, const float* pred, int64_t ld_p, const float* dact, float* d_enc, float* d_pred,
+                             float* work, const cfm_lattice* lat, int32_t J, cfm_stream_t stream);
+
+/* RNN-T loss over a packed lattice (csrc/rnnt.hip): torchaudio.functional.rnnt_loss of Transducer.rnnt_loss (reference src/model.py:107) on the
+ * valid nodes only, what cfm_rnnt_nll / cfm_rnnt_grad compute on the same nodes of a padded [B, T, U1, ld] buffer (same per-node code: the
+ * costs are the same bits).  logits [M, ld >= V]; targets int32 row b at targets + b * ld_targets (U[b] labels; may be NULL when every U[b] is 0);
+ * lse, lp_blank, lp_label, alpha, beta f32 [M]; shift f32 [B, T_max + U1_max]; nll, nll_shifted, ll_alpha f32 [B] (+inf / -inf when T[b] = 0).
+ * The gradient fields are those of cfm_rnnt_desc: grad [M, ld_grad] (may be the logits, in place), per-utterance gscale_dev[b * gscale_stride].
+ * U1_max <= 1024, T_max <= 8192 (cfm_last_error otherwise). */
+typedef struct {
+    cfm_lattice lat;
+    const void* logits;
+    int64_t ld;
+    int32_t logits_dtype, V, blank, ld_targets;
+    const int32_t* targets;
+    float *lse, *lp_blank, *lp_label, *alpha, *beta, *shift;
+    float *nll, *nll_shifted, *ll_alpha;
+    int32_t sweep;
+    /* cfm_rnnt_packed_grad only: */
+    void* grad;
+    int64_t ld_grad;
+    int32_t grad_dtype, grad_cols;
+    float gscale;
+    int32_t gscale_stride;
+    const float* gscale_dev;
+    float clamp;
+} cfm_rnnt_packed_desc;
+int cfm_rnnt_packed_nll(const cfm_rnnt_packed_desc* d, cfm_stream_t stream);
+int cfm_rnnt_packed_grad(const cfm_rnnt_packed_desc* d, cfm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Training (BASELINE config 3: encoder + CTC loss + backward).  Input gradients of the dense layers are cfm_gemm on transposed
