@@ -107,14 +107,7 @@ _TRAIN_W_PTRS = ["ln_ffm_g", "ln_ffm_b", "ln_mha_g", "ln_mha_b", "ln_conv_g", "l
 
 
 class LayerTrainWeights(ctypes.Structure):
-    _fields_ = [(n, c_p) for n in _TRAIN_W_PTRS] + [("bn_momentum", ctypes.c_float), ("bn_eps", ctypes.c_float)] + \
-               [(n, c_p) for n in ("ffm_w1f", "ffm_w2f", "ff_w1f", "ff_w2f")]
-
-
-class FfnTrainDesc(ctypes.Structure):
-    _fields_ = [("x", c_p), ("ln_g", c_p), ("ln_b", c_p), ("w1f", c_p), ("w2f", c_p), ("b1", c_p), ("b2", c_p), ("y", c_p), ("xn_out", c_p), ("z_out", c_p),
-                ("h_out", c_p), ("M", c_i64), ("D", c_i32), ("FF", c_i32), ("w_dtype", c_i32), ("alpha", c_f), ("eps", c_f), ("p_hidden", c_f), ("p_out", c_f),
-                ("seed_hidden", ctypes.c_uint32), ("seed_out", ctypes.c_uint32)]
+    _fields_ = [(n, c_p) for n in _TRAIN_W_PTRS] + [("bn_momentum", ctypes.c_float), ("bn_eps", ctypes.c_float)]
 
 
 class TrainGroup(ctypes.Structure):
@@ -125,10 +118,9 @@ LAYER_DONE_FN = ctypes.CFUNCTYPE(None, c_i32, c_p)
 
 
 class LayerTrainIO(ctypes.Structure):
-    _fields_ = [("B", c_i32), ("T", c_i32), ("D", c_i32), ("H", c_i32), ("FF", c_i32), ("ktaps", c_i32), ("act_dtype", c_i32), ("w_dtype", c_i32),
-                ("attn_mask", c_p), ("am_sb", c_i64), ("am_sq", c_i64), ("pad_valid", c_p),
+    _fields_ = [("D", c_i32), ("H", c_i32), ("FF", c_i32), ("ktaps", c_i32), ("act_dtype", c_i32), ("w_dtype", c_i32), ("pad_valid", c_p),
                 ("p_hidden_m", ctypes.c_float), ("p_hidden", ctypes.c_float), ("p_branch", ctypes.c_float), ("p_attn", ctypes.c_float),
-                ("p_attn_out", ctypes.c_float), ("seed", ctypes.c_uint32), ("deterministic", c_i32), ("grads_accumulate", c_i32), ("side_stream", c_p),
+                ("p_attn_out", ctypes.c_float), ("seed", ctypes.c_uint32), ("deterministic", c_i32), ("grads_accumulate", c_i32),
                 ("n_groups", c_i32), ("groups", ctypes.POINTER(TrainGroup)), ("defer_wgrad", c_i32)]
 
 
@@ -243,9 +235,6 @@ def lib():
         L.cfm_gemm.argtypes = [ctypes.POINTER(GemmDesc), c_p]
         L.cfm_attention.argtypes = [ctypes.POINTER(AttnDesc), c_p]
         L.cfm_ffn_fused.argtypes = [ctypes.POINTER(FfnDesc), c_p]
-        L.cfm_ffn_train_forward.argtypes = [ctypes.POINTER(FfnTrainDesc), c_p]
-        L.cfm_ffn_train_supported.argtypes = [c_i32, c_i32]
-        L.cfm_pack_ffn_fragments.argtypes = [c_p, c_i32, c_i32, c_i32, c_i32, c_p]
         L.cfm_rowchain.argtypes = [ctypes.POINTER(RowChainDesc), c_p]
         L.cfm_rowchain_supported.argtypes = [c_i32, c_i32]
         L.cfm_rowchain_pair_supported.argtypes = [c_i32, c_i32]
@@ -305,14 +294,10 @@ def lib():
         L.cfm_adam_clip_step.argtypes = [c_p, c_p, c_p, c_p, c_i64, c_f, c_f, c_f, c_f, c_f, c_i64, c_p, c_f, c_f, c_i32, c_p, c_p]
         L.cfm_dropout_rows.argtypes = [c_p, c_i32, c_p, c_i32, c_p, c_f, c_f, ctypes.c_uint32, c_f, ctypes.c_uint32, c_i64, c_i32, c_p]
         L.cfm_dropout_mask.argtypes = [c_p, c_i64, c_f, ctypes.c_uint32, c_p]
-        L.cfm_encoder_layer_train_forward.argtypes = [ctypes.POINTER(LayerTrainWeights), ctypes.POINTER(LayerTrainIO), ctypes.POINTER(LayerTrainSaved),
-                                                      ctypes.POINTER(LayerTrainScratch), c_p, c_p, c_p]
-        L.cfm_encoder_layer_train_backward.argtypes = [ctypes.POINTER(LayerTrainWeights), ctypes.POINTER(LayerTrainIO), ctypes.POINTER(LayerTrainSaved),
-                                                       ctypes.POINTER(LayerTrainScratch), ctypes.POINTER(LayerTrainGrads), c_p, c_p, c_p, c_p]
         L.cfm_encoder_train_forward.argtypes = [c_i32, ctypes.POINTER(LayerTrainWeights), ctypes.POINTER(LayerTrainIO), ctypes.POINTER(LayerTrainSaved),
                                                 ctypes.POINTER(LayerTrainScratch), ctypes.POINTER(c_p), c_p]
         L.cfm_encoder_train_backward.argtypes = [c_i32, ctypes.POINTER(LayerTrainWeights), ctypes.POINTER(LayerTrainIO), ctypes.POINTER(LayerTrainSaved),
-                                                 ctypes.POINTER(LayerTrainScratch), c_i32, ctypes.POINTER(LayerTrainGrads), ctypes.POINTER(c_p), c_p, c_p, c_p,
+                                                 ctypes.POINTER(LayerTrainScratch), ctypes.POINTER(LayerTrainGrads), ctypes.POINTER(c_p), c_p, c_p, c_p,
                                                  LAYER_DONE_FN, c_p, ctypes.POINTER(c_p), c_p]
         L.cfm_stream_prep.argtypes = [c_p, c_i32, c_i32, c_i32, c_i32, c_p, c_i32, c_i32, c_p, c_p, c_p, c_p]
         L.cfm_kv_ring_write.argtypes = [c_p, c_p, c_i32, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p]
@@ -327,12 +312,12 @@ def lib():
         L.cfm_prof_collect.restype = ctypes.c_int
         L.cfm_prof_entry.argtypes = [c_i32, ctypes.c_char_p, c_i32, ctypes.POINTER(c_i64), ctypes.POINTER(ctypes.c_double),
                                      ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
-        for name in ("cfm_gemm", "cfm_ffn_fused", "cfm_ffn_train_forward", "cfm_ffn_train_supported", "cfm_pack_ffn_fragments", "cfm_rowchain", "cfm_rowchain_supported", "cfm_attention", "cfm_layernorm", "cfm_kv_cache_pack", "cfm_dwconv_bn_silu", "cfm_conv1_relu", "cfm_conv1_relu_mma", "cfm_conv12_relu", "cfm_conv12_supported",
+        for name in ("cfm_gemm", "cfm_ffn_fused", "cfm_rowchain", "cfm_rowchain_supported", "cfm_attention", "cfm_layernorm", "cfm_kv_cache_pack", "cfm_dwconv_bn_silu", "cfm_conv1_relu", "cfm_conv1_relu_mma", "cfm_conv12_relu", "cfm_conv12_supported",
                      "cfm_valid_mask", "cfm_chunk_mask", "cfm_attn_mask", "cfm_cast", "cfm_add_rows",
                      "cfm_encoder_layer_forward", "cfm_ctc_nll", "cfm_joint_act", "cfm_joint_act_bwd", "cfm_rnnt_nll", "cfm_rnnt_grad", "cfm_prof_entry", "cfm_gemm_tn", "cfm_gemm_tn_group", "cfm_attention_bwd",
                      "cfm_layernorm_bwd", "cfm_glu_bwd", "cfm_dwconv_bn_train", "cfm_dwconv_bn_train_bwd", "cfm_col2im_relu_bwd", "cfm_conv1_wgrad",
                      "cfm_ctc_nll_train", "cfm_ctc_nll_train_groups", "cfm_ctc_grad", "cfm_adam_step", "cfm_adam_clip_step", "cfm_sumsq", "cfm_dropout_rows", "cfm_dropout_mask", "cfm_pack_matrices", "cfm_pack_vectors", "cfm_greedy_step", "cfm_ffn_split", "cfm_ffn_split_supported", "cfm_layernorm_bwd_fused", "cfm_dwconv_bn_train_bwd_acc",
-                     "cfm_encoder_layer_train_forward", "cfm_encoder_layer_train_backward", "cfm_encoder_train_forward", "cfm_encoder_train_backward", "cfm_stream_prep", "cfm_kv_ring_write", "cfm_stream_advance", "cfm_dwconv_causal_bn_silu", "cfm_conv_cache_update"):
+                     "cfm_encoder_train_forward", "cfm_encoder_train_backward", "cfm_stream_prep", "cfm_kv_ring_write", "cfm_stream_advance", "cfm_dwconv_causal_bn_silu", "cfm_conv_cache_update"):
             getattr(L, name).restype = ctypes.c_int
         _lib = L
     return _lib

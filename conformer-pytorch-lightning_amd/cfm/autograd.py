@@ -14,7 +14,6 @@ What train mode means here (reference: encoder_layer.py:49-71, convolution.py:34
     zero gradient (the reference's is rounding noise ~1e-8) and the term is not evaluated; pos_bias_u rides in linear_q's bias.
 """
 import ctypes
-import os
 
 import torch
 
@@ -353,7 +352,11 @@ def subsampling_params(mod):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-# the block as TWO host calls (csrc/train_layer.cpp): the same launches as the op-by-op composition above, enqueued from C++
+# the blocks from ONE host call each way (csrc/train_layer.cpp cfm_encoder_train_forward / _backward): the same launches as the op-by-op
+# composition above, enqueued from C++.  EncoderStackFn runs all blocks of the encoder over an accumulation WINDOW (round 3): the
+# micro-batches of the window concatenated along the row axis (cfm.h cfm_train_group), each block's weight gradients as ONE grouped launch
+# at the end of its backward, gradients written straight into the data-parallel trainer's flat buffer.  EncoderLayerFn runs one block over
+# one micro-batch through the same entry points (one block, one row group, each weight gradient launched where it is computed).
 # ----------------------------------------------------------------------------------------------------------------------
 USE_COMPOSITE = True          # False: EncoderLayerFn runs the op-by-op composition (tests compare the two)
 
@@ -395,6 +398,9 @@ def layer_grad_layout(layer, offsets=None):
     pw1_row = lay["conv_module.pointwise_conv1.weight"][0] + idx * D
     pw1_bias = lay["conv_module.pointwise_conv1.bias"][0] + idx
     hit = dict(device=dev, layout=lay, numel=n, qkv_row=qkv_row.to(dev), qkv_bias=qkv_bias.to(dev), pw1_row=pw1_row.to(dev), pw1_bias=pw1_bias.to(dev))
+    if "self_attn.pos_bias_u" in lay:                                    # pos_bias_u as a second destination of linear_q.bias' column sums
+        u0 = lay["self_attn.pos_bias_u"][0]
+        hit["qkv_bias2"] = torch.cat([u0 + ar, torch.full((2 * D,), -1, dtype=torch.int64)]).to(dev)
     cache[key] = hit
     return hit
 
@@ -443,8 +449,6 @@ def _build_train_weights_struct(layer, pks):
     for pre, pk in (("ffm", ffm), ("ff", ff)):
         for f in ("w1", "w1_lo", "w2", "w2_lo", "w1t", "w1t_lo", "w2t", "w2t_lo", "b1", "b2"):
             setattr(w, pre + "_" + f, cfm.ptr(getattr(pk, f)))
-        for f in ("w1f", "w2f"):                            # fragment-major packs (the stack pack builds them): the one-launch feed-forward forward
-            setattr(w, pre + "_" + f, cfm.ptr(getattr(pk, f, None)))
     for f in ("qkv_w", "qkv_w_lo", "qkv_t", "qkv_t_lo", "out_w", "out_w_lo", "out_t", "out_t_lo", "qkv_b", "out_b"):
         setattr(w, f, cfm.ptr(getattr(att, f)))
     for f in ("pw1_w", "pw1_w_lo", "pw1_t", "pw1_t_lo", "pw2_w", "pw2_w_lo", "pw2_t", "pw2_t_lo", "pw1_b", "pw2_b", "dw_w", "dw_b"):
@@ -456,23 +460,6 @@ def _build_train_weights_struct(layer, pks):
     w.bn_momentum = bn.momentum if bn.momentum is not None else 1.0 / float(int(bn.num_batches_tracked) + 1)
     w.bn_eps = bn.eps
     return w
-
-
-DIRECT_GRADS = os.environ.get("CFM_DIRECT_GRADS", "0") != "0"     # flat-leaf blocks add their gradients straight into the trainer's gradient buffer: measured
-# SLOWER at config 3 (17.8 vs 17.1 ms per step: the atomics / read-add-stores then hit a cold 139 MB buffer instead of a just-zeroed slab in cache) -- opt-in
-USE_PACK_KERNEL = os.environ.get("CFM_PACK_KERNEL", "1") != "0"   # one cfm_pack_matrices launch per block and step instead of ~25 torch ops
-WGRAD_BESIDE = os.environ.get("CFM_WGRAD_BESIDE", "0") != "0"     # stack path: each block's grouped weight-gradient launch on a side stream
-OVERLAP_WGRAD = os.environ.get("CFM_OVERLAP_WGRAD", "0") != "0"   # measured at config 3: 21.3 ms per step with, 19.7 ms without
-_SIDE = {}
-
-
-def _side_stream(dev):
-    """The per-device stream the composite backward issues its weight-gradient products on (cfm.h: cfm_layer_train_io.side_stream)."""
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-    st = _SIDE.get(key)
-    if st is None:
-        st = _SIDE[key] = torch.cuda.Stream(device=dev)
-    return st
 
 
 def _composite_ok(layer, x, flat=False):
@@ -511,88 +498,150 @@ def train_f32_layout(M, D, BHT, G, L, outputs=True):
     return blocks, outs, o
 
 
-def _layer_composite_forward(ctx, x0, layer, prec, mask8, m_str, keep, pks, B, T, D):
-    dev, adt = x0.device, prec.act_dtype
-    M, FF, H = B * T, layer.hidden_dim, layer.num_heads
+_SAVED_ACT = ("xn1", "z1", "h1", "xn2", "qkv", "ctx", "xn3", "u", "glu", "s", "xn4", "z2", "h2")
+
+
+def _stack_grads(owner, layers, bases, lays, tag, u_table):
+    """ctypes array of the blocks' gradient destinations: block i's slab starts at address bases[i], laid out as lays[i] (layer_grad_layout's
+    cached dicts); cached per destination and layout.  u_table: pos_bias_u as a second destination of linear_q.bias' column sums (what the
+    grouped weight gradients need) instead of a copy after the product."""
+    key = (tag, u_table, tuple(bases), tuple(id(lay) for lay in lays))
+    hit = owner.__dict__.get("_stack_g")
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    arr = (cfm.LayerTrainGrads * len(layers))()
+    for g, base, lay in zip(arr, bases, lays):
+        g.slab = base
+        for name, field in _GRAD_FIELDS.items():
+            if name in lay["layout"]:
+                setattr(g, field, base + 4 * lay["layout"][name][0])
+        g.q_bias = base + 4 * lay["layout"]["self_attn.linear_q.bias"][0]
+        g.qkv_row_off, g.qkv_bias_off, g.pw1_row_off, g.pw1_bias_off = (lay[k].data_ptr() for k in ("qkv_row", "qkv_bias", "pw1_row", "pw1_bias"))
+        if u_table and "qkv_bias2" in lay:
+            g.qkv_bias_off2 = lay["qkv_bias2"].data_ptr()
+    owner.__dict__["_stack_g"] = (key, arr)
+    return arr
+
+
+def _param_grads(layers, slabs, lays):
+    """The blocks' slabs as one gradient per parameter, in named_parameters order (None where no gradient is wanted)."""
+    grads = []
+    for l, slab, lay in zip(layers, slabs, lays):
+        for name, p in l.named_parameters():
+            off, n = lay["layout"][name]
+            grads.append(slab[off:off + n].view(p.shape) if p.requires_grad else None)
+    return tuple(grads)
+
+
+def _train_forward(ctx, x, owner, layers, prec, groups, keep, flat, w_arr, pks, defer):
+    """The blocks' forward (cfm_encoder_train_forward) over x f32 [M,D], the rows of the micro-batches `groups` ([(B, T, mask8 | None, (m_sb, m_sq))])
+    one after the other; keep u8 [M] | None.  Keeps what _train_backward needs on ctx and returns the last block's output [M,D].
+    defer: each block's weight gradients as one grouped launch at the end of its backward (cfm.h cfm_layer_train_io.defer_wgrad)."""
+    dev, adt = x.device, prec.act_dtype
+    L, G = len(layers), len(groups)
+    l0 = layers[0]
+    D, FF, H = l0.encoder_dim, l0.hidden_dim, l0.num_heads
+    M = x.shape[0]
+    BHT = sum(B * H * T for B, T, _, _ in groups)
+    # everything the backward needs, in two allocations: act-dtype rows and f32 rows (the block outputs included)
     esz = 4 if adt == torch.float32 else 2
-    # everything the backward needs, in two allocations: act-dtype rows and f32 rows
     widths = dict(xn1=D, z1=FF, h1=FF, xn2=D, qkv=3 * D, ctx=D, xn3=D, u=2 * D, glu=D, s=D, xn4=D, z2=FF, h2=FF)
-    act = torch.empty((M * sum(widths.values()),), dtype=adt, device=dev)
-    regions, _, n_f32 = train_f32_layout(M, D, B * H * T, 1, 1, outputs=False)
+    per_act = M * sum(widths.values())
+    regions, outs, n_f32 = train_f32_layout(M, D, BHT, G, L)
+    act = torch.empty((L * per_act,), dtype=adt, device=dev)
     f32 = torch.empty((n_f32,), dtype=torch.float32, device=dev)
-    sv = cfm.LayerTrainSaved()
-    o = 0
-    for name, wd in widths.items():
-        setattr(sv, name, act.data_ptr() + o * esz)
-        o += M * wd
-    for name, (off, _n) in regions[0].items():
-        setattr(sv, name, f32.data_ptr() + off * 4)
-    sc = cfm.LayerTrainScratch()
-    sc.dwbn_ws = cfm.scratch("dwbn", cfm.lib().cfm_dwconv_bn_ws(B, T, D), torch.float32, dev).data_ptr()
+    sv = (cfm.LayerTrainSaved * L)()
+    xs = (ctypes.c_void_p * (L + 1))()
+    xs[0] = x.data_ptr()
+    pa, pf = act.data_ptr(), f32.data_ptr()
+    for l in range(L):
+        o = pa + l * per_act * esz
+        for name in _SAVED_ACT:
+            setattr(sv[l], name, o)
+            o += M * widths[name] * esz
+        for name, (off, _n) in regions[l].items():
+            setattr(sv[l], name, pf + off * 4)
+        xs[l + 1] = pf + outs[l][0] * 4
+    garr = (cfm.TrainGroup * G)()
+    row0 = 0
+    for g, (B, T, m8, m_str) in zip(garr, groups):
+        g.B, g.T, g.row0, g.attn_mask, g.am_sb, g.am_sq = B, T, row0, cfm.ptr(m8), m_str[0], m_str[1]
+        row0 += B * T
     io = cfm.LayerTrainIO()
-    io.B, io.T, io.D, io.H, io.FF, io.ktaps, io.act_dtype, io.w_dtype = B, T, D, H, FF, layer.kernel_size, prec.act_code, prec.w_code
-    io.attn_mask, io.am_sb, io.am_sq, io.pad_valid = cfm.ptr(mask8), m_str[0], m_str[1], cfm.ptr(keep)
-    p_br, p_a = layer.dropout.p, layer.self_attn.dropout.p
-    io.p_hidden_m, io.p_hidden, io.p_branch, io.p_attn = layer.feed_forward_macaron.dropout.p, layer.feed_forward.dropout.p, p_br, p_a
-    io.p_attn_out = 0.0 if layer.use_relative else p_a
+    io.D, io.H, io.FF, io.ktaps, io.act_dtype, io.w_dtype = D, H, FF, l0.kernel_size, prec.act_code, prec.w_code
+    io.pad_valid = cfm.ptr(keep)
+    p_br, p_a = l0.dropout.p, l0.self_attn.dropout.p
+    io.p_hidden_m, io.p_hidden, io.p_branch, io.p_attn = l0.feed_forward_macaron.dropout.p, l0.feed_forward.dropout.p, p_br, p_a
+    io.p_attn_out = 0.0 if l0.use_relative else p_a
     io.seed = draw_seed() if max(io.p_hidden_m, io.p_hidden, p_br, p_a) > 0 else 0
     io.deterministic = 1 if cfm.ops._deterministic[0] else 0
-    w = _train_weights_struct(layer, pks)
-    y = torch.empty((M, D), dtype=torch.float32, device=dev)
-    cfm.check(cfm.lib().cfm_encoder_layer_train_forward(ctypes.byref(w), ctypes.byref(io), ctypes.byref(sv), ctypes.byref(sc), x0.data_ptr(), y.data_ptr(),
-                                                        cfm.stream()), "cfm_encoder_layer_train_forward")
-    bn = layer.conv_module.norm
-    if bn.track_running_stats:
-        bn.num_batches_tracked += 1
-    ctx.comp = (layer, prec, mask8, keep, pks, w, io, sv, (act, f32, x0), B, T, D)
-    return y
+    io.n_groups, io.groups, io.defer_wgrad = G, garr, 1 if defer else 0
+    ws = sum(cfm.lib().cfm_dwconv_bn_ws(B, T, D) for B, T, _, _ in groups)
+    sc = cfm.LayerTrainScratch()
+    sc.dwbn_ws = cfm.scratch("dwbn", ws, torch.float32, dev).data_ptr()
+    cfm.check(cfm.lib().cfm_encoder_train_forward(L, w_arr, ctypes.byref(io), sv, ctypes.byref(sc), xs, cfm.stream()), "cfm_encoder_train_forward")
+    if l0.conv_module.norm.track_running_stats:
+        torch._foreach_add_([l.conv_module.norm.num_batches_tracked for l in layers], G)
+    # held: what the structs point to -- the backward reads the saves, the input rows, the masks of the groups and the pad mask
+    ctx.st = (owner, layers, prec, flat, defer, w_arr, pks, io, garr, sv, xs, (act, f32, x, groups, keep), M, BHT, ws)
+    return f32[outs[-1][0]:outs[-1][0] + M * D].view(M, D)
 
 
-def _layer_composite_backward(ctx, dy):
-    layer, prec, mask8, keep, pks, w, io, sv, (act, f32, x0), B, T, D = ctx.comp
-    dev, adt = x0.device, prec.act_dtype
-    M, FF, H = B * T, layer.hidden_dim, layer.num_heads
-    # the slab mirrors the trainer's flat layout of this block when the block takes part as one autograd leaf (trainer.py), else a private
-    # named_parameters-order layout; zero-filled: weight / bias gradients are accumulated into it by the split-M products
-    leaf = layer.__dict__.get("_flat_leaf") if ctx.flat else None
-    lay = layer_grad_layout(layer, layer.__dict__.get("_flat_grad_offsets") if ctx.flat else None)
-    # A block registered with a gradient SINK (trainer.py: its range of the step's flat gradient buffer + a "ready" callback) has its gradients
-    # added straight into that buffer -- no zero-filled slab, no AccumulateGrad add; needs the accumulating (atomic) LayerNorm sums
-    sink = layer.__dict__.get("_flat_grad_sink") if (ctx.flat and DIRECT_GRADS and not cfm.ops._deterministic[0]) else None
-    if sink is not None and (sink[0].numel() != leaf.numel() or sink[0].device != dev):
-        sink = None
-    io.grads_accumulate = 1 if sink is not None else 0
-    slab = sink[0] if sink is not None else torch.zeros((leaf.numel() if leaf is not None else lay["numel"],), dtype=torch.float32, device=dev)
-    g = cfm.LayerTrainGrads()
-    g.slab = slab.data_ptr()
-    for name, field in _GRAD_FIELDS.items():
-        if name in lay["layout"]:
-            setattr(g, field, slab.data_ptr() + 4 * lay["layout"][name][0])
-    g.q_bias = slab.data_ptr() + 4 * lay["layout"]["self_attn.linear_q.bias"][0]
-    g.qkv_row_off, g.qkv_bias_off, g.pw1_row_off, g.pw1_bias_off = (lay[k].data_ptr() for k in ("qkv_row", "qkv_bias", "pw1_row", "pw1_bias"))
-    esz = 4 if adt == torch.float32 else 2
+def _train_backward(ctx, dy, use_sinks):
+    """The blocks' backward (cfm_encoder_train_backward) -> (dx f32 [M,D], one slab per block | None, the blocks' gradient layouts).
+    use_sinks: write the gradients into the trainer's flat gradient buffer itself when every block is registered with a sink (trainer.py: its
+    range of the buffer + a ready hook, called from the per-block callback; needs the atomic sums) -- nothing is then returned for the leaves
+    (slabs None).  Otherwise one zero-filled slab per block, laid out as the block's flat leaf (flat) or in named_parameters order."""
+    owner, layers, prec, flat, defer, w_arr, pks, io, garr, sv, xs, held, M, BHT, ws = ctx.st
+    dev, adt = dy.device, prec.act_dtype
+    L = len(layers)
+    l0 = layers[0]
+    D, FF = l0.encoder_dim, l0.hidden_dim
+    sinks = [l.__dict__.get("_flat_grad_sink") for l in layers] if use_sinks else None
+    if sinks is not None and any(s is None or s[0].device != dev for s in sinks):
+        sinks = None
+    lays = [layer_grad_layout(l, l.__dict__.get("_flat_grad_offsets") if flat else None) for l in layers]
+    if sinks is not None:
+        slabs = None
+        g_arr = _stack_grads(owner, layers, [s[0].data_ptr() for s in sinks], lays, "sink", defer)
+        io.grads_accumulate = 1
+    else:
+        sizes = [(l.__dict__["_flat_leaf"].numel() if flat else lay["numel"]) for l, lay in zip(layers, lays)]
+        slab_all = torch.zeros((sum(sizes),), dtype=torch.float32, device=dev)
+        slabs, o = [], 0
+        for n in sizes:
+            slabs.append(slab_all[o:o + n])
+            o += n
+        g_arr = _stack_grads(owner, layers, [s.data_ptr() for s in slabs], lays, "slab", defer)
+        io.grads_accumulate = 0
     sc = cfm.LayerTrainScratch()
     sc.dxn = cfm.scratch("t_dxn", M * D, torch.float32, dev).data_ptr()
-    for name, wd in (("dz", FF), ("dyb", D), ("ds", D), ("dglu", D), ("du", 2 * D), ("dctx", D), ("dqkv", 3 * D)):
+    for name, wd in (("dz", FF), ("dz2", FF), ("dyb", D), ("dyb2", D), ("dyb3", D), ("dyb4", D), ("du", 2 * D), ("dqkv", 3 * D), ("ds", D), ("dglu", D),
+                     ("dctx", D)):
         setattr(sc, name, cfm.scratch("t_" + name, M * wd, adt, dev).data_ptr())
-    sc.delta = cfm.scratch("attn_delta", B * H * T, torch.float32, dev).data_ptr()
+    sc.delta = cfm.scratch("attn_delta", BHT, torch.float32, dev).data_ptr()
     sc.ln_ws = cfm.scratch("ln_bwd", cfm.lib().cfm_layernorm_bwd_ws(M, D), torch.float32, dev).data_ptr()
-    sc.dwbn_ws = cfm.scratch("dwbn", cfm.lib().cfm_dwconv_bn_ws(B, T, D), torch.float32, dev).data_ptr()
+    sc.dwbn_ws = cfm.scratch("dwbn", ws, torch.float32, dev).data_ptr()
     sc.dy_ws = cfm.scratch("dwbn_dy", M * D, torch.float32, dev).data_ptr()
-    if OVERLAP_WGRAD:                                       # weight-gradient products on a second stream, overlapped with the input-gradient chain
-        for name, wd in (("dz2", FF), ("dyb2", D), ("dyb3", D), ("dyb4", D)):
-            setattr(sc, name, cfm.scratch("t_" + name, M * wd, adt, dev).data_ptr())
-        io.side_stream = _side_stream(dev).cuda_stream
-    else:
-        io.side_stream = None
     dyc = _f32c(dy.reshape(M, D))
-    dx = torch.empty((M, D), dtype=torch.float32, device=dev)
-    cfm.check(cfm.lib().cfm_encoder_layer_train_backward(ctypes.byref(w), ctypes.byref(io), ctypes.byref(sv), ctypes.byref(sc), ctypes.byref(g), x0.data_ptr(),
-                                                         dyc.data_ptr(), dx.data_ptr(), cfm.stream()), "cfm_encoder_layer_train_backward")
-    if sink is not None:
-        sink[1]()                                           # the trainer's ready hook (bucket all-reduce), after the kernels are enqueued
-        return dx, None, lay
-    return dx, slab, lay
+    bufs = torch.empty((2, M, D), dtype=torch.float32, device=dev)
+    failed = []
+
+    def done(layer, _user):
+        if sinks is not None:
+            try:
+                sinks[layer][1]()                                   # the trainer's ready hook: this block's bucket may be all-reduced
+            except BaseException as e:                              # noqa: BLE001 -- ctypes would swallow it: re-raised below
+                failed.append(e)
+
+    cb = cfm.LAYER_DONE_FN(done)
+    out = ctypes.c_void_p()
+    cfm.check(cfm.lib().cfm_encoder_train_backward(L, w_arr, ctypes.byref(io), sv, ctypes.byref(sc), g_arr, xs, dyc.data_ptr(), bufs[0].data_ptr(),
+                                                   bufs[1].data_ptr(), cb, None, ctypes.byref(out), cfm.stream()), "cfm_encoder_train_backward")
+    if failed:
+        raise failed[0]
+    dx = bufs[0] if out.value == bufs[0].data_ptr() else bufs[1]
+    return dx, slabs, lays
 
 
 class EncoderLayerFn(torch.autograd.Function):
@@ -602,16 +651,18 @@ class EncoderLayerFn(torch.autograd.Function):
     def forward(ctx, x, layer, prec, mask8, m_str, keep, *params):
         B, T, D = x.shape
         rel = layer.use_relative
-        ctx.comp = None
+        ctx.comp = False
         ctx.flat = len(params) == 1 and params[0] is getattr(layer, "_flat_leaf", None)
         comp = _composite_ok(layer, x, ctx.flat)
         if ctx.flat and not comp:
             raise RuntimeError("a block registered with a flat parameter leaf (trainer.py) needs the composite train path")
         if comp:
-            pks = packing.pack_layer_train(layer, prec, rel) if USE_PACK_KERNEL else (
-                packing.pack_ffn_train(layer.feed_forward_macaron, prec), packing.pack_mhsa_train(layer.self_attn, prec, rel),
-                packing.pack_conv_module_train(layer.conv_module, prec), packing.pack_ffn_train(layer.feed_forward, prec))
-            return _layer_composite_forward(ctx, _f32c(x.reshape(B * T, D)), layer, prec, mask8, m_str, keep, pks, B, T, D).view(B, T, D)
+            # one block, one row group, no deferred weight gradients, no gradient sink: the launches of the op-by-op composition below, in order
+            ctx.comp, ctx.shape = True, x.shape
+            pks = packing.pack_layer_train(layer, prec, rel)
+            w = ctypes.pointer(_train_weights_struct(layer, pks))
+            y = _train_forward(ctx, _f32c(x.reshape(B * T, D)), layer, [layer], prec, [(B, T, mask8, m_str)], keep, ctx.flat, w, pks, False)
+            return y.view(B, T, D)
         pks = (packing.pack_ffn_train(layer.feed_forward_macaron, prec), packing.pack_mhsa_train(layer.self_attn, prec, rel),
                packing.pack_conv_module_train(layer.conv_module, prec), packing.pack_ffn_train(layer.feed_forward, prec))
         ln = lambda m: (m.weight.detach(), m.bias.detach())
@@ -633,16 +684,12 @@ class EncoderLayerFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        if ctx.comp is not None:
-            layer, B, T, D = ctx.comp[0], ctx.comp[-3], ctx.comp[-2], ctx.comp[-1]
-            dx, slab, lay = _layer_composite_backward(ctx, dy)
+        if ctx.comp:
+            dx, slabs, lays = _train_backward(ctx, dy, False)
+            head = (dx.view(ctx.shape), None, None, None, None, None)
             if ctx.flat:                                              # one gradient for the block's flat parameter leaf (trainer.py)
-                return (dx.view(B, T, D), None, None, None, None, None, slab)
-            grads = []
-            for name, p in layer.named_parameters():
-                off, n = lay["layout"][name]
-                grads.append(slab[off:off + n].view(p.shape) if p.requires_grad else None)
-            return (dx.view(B, T, D), None, None, None, None, None) + tuple(grads)
+                return head + (slabs[0],)
+            return head + _param_grads(ctx.st[1], slabs, lays)
         layer, prec, mask8, m_str, keep, pks, (s1, s2, s3, s4, x4), B, T, D, dr = ctx.args
         rel = layer.use_relative
         ln = lambda m: (m.weight.detach(), m.bias.detach())
@@ -667,14 +714,6 @@ class EncoderLayerFn(torch.autograd.Function):
         return (d.view(B, T, D), None, None, None, None, None) + tuple(_ordered(names, grads, tensors))
 
 
-# ----------------------------------------------------------------------------------------------------------------------
-# the whole block STACK over an accumulation WINDOW (round 3): one host call each way (csrc/train_layer.cpp cfm_encoder_train_forward /
-# _backward), the micro-batches of the window concatenated along the row axis (cfm.h cfm_train_group), each block's weight gradients as ONE
-# grouped launch at the end of its backward, gradients written straight into the data-parallel trainer's flat buffer.
-# ----------------------------------------------------------------------------------------------------------------------
-_SAVED_ACT = ("xn1", "z1", "h1", "xn2", "qkv", "ctx", "xn3", "u", "glu", "s", "xn4", "z2", "h2")
-
-
 def stack_supported(layers, flat):
     """The stack path needs every block on the composite train path with the same sizes and dropout rates (it shares one io struct)."""
     l0 = layers[0]
@@ -687,8 +726,7 @@ def stack_supported(layers, flat):
 
 def _stack_weights(owner, layers, prec, flat):
     """ctypes array of the blocks' weight structs (cached while the packs stay the same objects)."""
-    rel = layers[0].use_relative
-    pks = packing.pack_stack_train(owner, layers, prec, rel, flat) if USE_PACK_KERNEL else tuple(packing.pack_layer_train(l, prec, rel) for l in layers)
+    pks = packing.pack_stack_train(owner, layers, prec, layers[0].use_relative, flat)
     hit = owner.__dict__.get("_stack_w")
     ptrs = tuple(_inplace_ptrs(l) for l in layers)
     if hit is not None and len(hit[0]) == len(pks) and all(a is b for a, b in zip(hit[0], pks)) and hit[2] == ptrs:
@@ -700,162 +738,34 @@ def _stack_weights(owner, layers, prec, flat):
     return arr, pks
 
 
-def _stack_grads(owner, layers, bases, lays, tag):
-    """ctypes array of the blocks' gradient destinations: block i's slab starts at address bases[i]; cached per destination."""
-    key = (tag, tuple(bases))
-    hit = owner.__dict__.get("_stack_g")
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    arr = (cfm.LayerTrainGrads * len(layers))()
-    for g, base, lay in zip(arr, bases, lays):
-        g.slab = base
-        for name, field in _GRAD_FIELDS.items():
-            if name in lay["layout"]:
-                setattr(g, field, base + 4 * lay["layout"][name][0])
-        g.q_bias = base + 4 * lay["layout"]["self_attn.linear_q.bias"][0]
-        g.qkv_row_off, g.qkv_bias_off, g.pw1_row_off, g.pw1_bias_off = (lay[k].data_ptr() for k in ("qkv_row", "qkv_bias", "pw1_row", "pw1_bias"))
-        if "qkv_bias2" in lay:
-            g.qkv_bias_off2 = lay["qkv_bias2"].data_ptr()
-    owner.__dict__["_stack_g"] = (key, arr)
-    return arr
-
-
 class EncoderStackFn(torch.autograd.Function):
     """All conformer blocks of the encoder in train mode over one accumulation window (encoder.py:72-73 under module.train())."""
 
     @staticmethod
     def forward(ctx, x, owner, layers, prec, groups, keep, flat, *params):
         """x f32 [M,D]: the window's rows, micro-batch after micro-batch; groups: [(B, T, mask8 | None, (m_sb, m_sq))]; keep u8 [M] | None."""
-        dev, adt = x.device, prec.act_dtype
-        L, G = len(layers), len(groups)
-        l0 = layers[0]
-        D, FF, H = l0.encoder_dim, l0.hidden_dim, l0.num_heads
+        D = layers[0].encoder_dim
         M = sum(B * T for B, T, _, _ in groups)
-        BHT = sum(B * H * T for B, T, _, _ in groups)
         if tuple(x.shape) != (M, D) or x.dtype != torch.float32 or not x.is_contiguous():
             raise RuntimeError("EncoderStackFn: rows must be contiguous float32 (%d,%d), got %s %s" % (M, D, tuple(x.shape), x.dtype))
-        if G > 8:
+        if len(groups) > 8:
             raise RuntimeError("EncoderStackFn: at most 8 micro-batches per window")
         w_arr, pks = _stack_weights(owner, layers, prec, flat)
-        esz = 4 if adt == torch.float32 else 2
-        widths = dict(xn1=D, z1=FF, h1=FF, xn2=D, qkv=3 * D, ctx=D, xn3=D, u=2 * D, glu=D, s=D, xn4=D, z2=FF, h2=FF)
-        per_act = M * sum(widths.values())
-        regions, outs, n_f32 = train_f32_layout(M, D, BHT, G, L)
-        act = torch.empty((L * per_act,), dtype=adt, device=dev)
-        f32 = torch.empty((n_f32,), dtype=torch.float32, device=dev)
-        sv = (cfm.LayerTrainSaved * L)()
-        xs = (ctypes.c_void_p * (L + 1))()
-        xs[0] = x.data_ptr()
-        pa, pf = act.data_ptr(), f32.data_ptr()
-        for l in range(L):
-            o = pa + l * per_act * esz
-            for name in _SAVED_ACT:
-                setattr(sv[l], name, o)
-                o += M * widths[name] * esz
-            for name, (off, _n) in regions[l].items():
-                setattr(sv[l], name, pf + off * 4)
-            xs[l + 1] = pf + outs[l][0] * 4
-        garr = (cfm.TrainGroup * G)()
-        row0 = 0
-        for g, (B, T, m8, m_str) in zip(garr, groups):
-            g.B, g.T, g.row0, g.attn_mask, g.am_sb, g.am_sq = B, T, row0, cfm.ptr(m8), m_str[0], m_str[1]
-            row0 += B * T
-        io = cfm.LayerTrainIO()
-        io.D, io.H, io.FF, io.ktaps, io.act_dtype, io.w_dtype = D, H, FF, l0.kernel_size, prec.act_code, prec.w_code
-        io.pad_valid = cfm.ptr(keep)
-        p_br, p_a = l0.dropout.p, l0.self_attn.dropout.p
-        io.p_hidden_m, io.p_hidden, io.p_branch, io.p_attn = l0.feed_forward_macaron.dropout.p, l0.feed_forward.dropout.p, p_br, p_a
-        io.p_attn_out = 0.0 if l0.use_relative else p_a
-        io.seed = draw_seed() if max(io.p_hidden_m, io.p_hidden, p_br, p_a) > 0 else 0
-        io.deterministic = 1 if cfm.ops._deterministic[0] else 0
-        io.n_groups, io.groups, io.defer_wgrad = G, garr, 1
-        ws = sum(cfm.lib().cfm_dwconv_bn_ws(B, T, D) for B, T, _, _ in groups)
-        sc = cfm.LayerTrainScratch()
-        sc.dwbn_ws = cfm.scratch("dwbn", ws, torch.float32, dev).data_ptr()
-        cfm.check(cfm.lib().cfm_encoder_train_forward(L, w_arr, ctypes.byref(io), sv, ctypes.byref(sc), xs, cfm.stream()), "cfm_encoder_train_forward")
-        if l0.conv_module.norm.track_running_stats:
-            torch._foreach_add_([l.conv_module.norm.num_batches_tracked for l in layers], G)
-        ctx.st = (owner, layers, prec, groups, keep, flat, w_arr, pks, io, garr, sv, xs, (act, f32, x), M, BHT, ws)
-        return f32[outs[-1][0]:outs[-1][0] + M * D].view(M, D)
+        return _train_forward(ctx, x, owner, layers, prec, groups, keep, flat, w_arr, pks, True)
 
     @staticmethod
     def backward(ctx, dy):
-        owner, layers, prec, groups, keep, flat, w_arr, pks, io, garr, sv, xs, held, M, BHT, ws = ctx.st
-        dev, adt = dy.device, prec.act_dtype
-        L = len(layers)
-        l0 = layers[0]
-        D, FF = l0.encoder_dim, l0.hidden_dim
-        det = cfm.ops._deterministic[0]
+        layers, flat = ctx.st[1], ctx.st[3]
         # where the gradients go: the trainer's flat gradient buffer itself (each block registered with a sink: trainer.py) -- nothing is
-        # returned to autograd for the leaves, the trainer's ready hook is called from the per-block callback -- or one zero-filled slab per
-        # block (plain autograd / deterministic sums), returned as the leaves' / parameters' gradients
-        sinks = [l.__dict__.get("_flat_grad_sink") for l in layers] if (flat and not det) else None
-        if sinks is not None and any(s is None or s[0].device != dev for s in sinks):
-            sinks = None
-        lays = [layer_grad_layout(l, l.__dict__.get("_flat_grad_offsets") if flat else None) for l in layers]
-        for lay, l in zip(lays, layers):
-            if "qkv_bias2" not in lay and "self_attn.pos_bias_u" in lay["layout"]:
-                u0 = lay["layout"]["self_attn.pos_bias_u"][0]
-                lay["qkv_bias2"] = torch.cat([u0 + torch.arange(D, dtype=torch.int64), torch.full((2 * D,), -1, dtype=torch.int64)]).to(dev)
-        if sinks is not None:
-            slabs = None
-            g_arr = _stack_grads(owner, layers, [s[0].data_ptr() for s in sinks], lays, "sink")
-            io.grads_accumulate = 1
-        else:
-            sizes = [(l.__dict__["_flat_leaf"].numel() if flat else lay["numel"]) for l, lay in zip(layers, lays)]
-            slab_all = torch.zeros((sum(sizes),), dtype=torch.float32, device=dev)
-            slabs, o = [], 0
-            for n in sizes:
-                slabs.append(slab_all[o:o + n])
-                o += n
-            g_arr = _stack_grads(owner, layers, [s.data_ptr() for s in slabs], lays, "slab")
-            io.grads_accumulate = 0
-        # the grouped weight-gradient launch of each block on a side stream, beside the next block's chain (two scratch sets: its operands
-        # must outlive the block); measured at config 3 -- see WGRAD_BESIDE
-        beside = WGRAD_BESIDE and adt != torch.float32
-        io.side_stream = _side_stream(dev).cuda_stream if beside else None
-        n_sc = 2 if beside else 1
-        scs = (cfm.LayerTrainScratch * n_sc)()
-        for si, sc in enumerate(scs):
-            tag = "t%d_" % si
-            sc.dxn = cfm.scratch("t_dxn", M * D, torch.float32, dev).data_ptr()
-            for name, wd in (("dz", FF), ("dz2", FF), ("dyb", D), ("dyb2", D), ("dyb3", D), ("dyb4", D), ("du", 2 * D), ("dqkv", 3 * D)):
-                setattr(sc, name, cfm.scratch(tag + name, M * wd, adt, dev).data_ptr())         # operands of the deferred products: per set
-            for name, wd in (("ds", D), ("dglu", D), ("dctx", D)):
-                setattr(sc, name, cfm.scratch("t_" + name, M * wd, adt, dev).data_ptr())
-            sc.delta = cfm.scratch("attn_delta", BHT, torch.float32, dev).data_ptr()
-            sc.ln_ws = cfm.scratch("ln_bwd", cfm.lib().cfm_layernorm_bwd_ws(M, D), torch.float32, dev).data_ptr()
-            sc.dwbn_ws = cfm.scratch("dwbn", ws, torch.float32, dev).data_ptr()
-            sc.dy_ws = cfm.scratch("dwbn_dy", M * D, torch.float32, dev).data_ptr()
-        dyc = _f32c(dy.reshape(M, D))
-        bufs = torch.empty((2, M, D), dtype=torch.float32, device=dev)
-        failed = []
-
-        def done(layer, _user):
-            if sinks is not None:
-                try:
-                    sinks[layer][1]()                                   # the trainer's ready hook: this block's bucket may be all-reduced
-                except BaseException as e:                              # noqa: BLE001 -- ctypes would swallow it: re-raised below
-                    failed.append(e)
-
-        cb = cfm.LAYER_DONE_FN(done)
-        out = ctypes.c_void_p()
-        cfm.check(cfm.lib().cfm_encoder_train_backward(L, w_arr, ctypes.byref(io), sv, scs, n_sc, g_arr, xs, dyc.data_ptr(), bufs[0].data_ptr(),
-                                                       bufs[1].data_ptr(), cb, None, ctypes.byref(out), cfm.stream()), "cfm_encoder_train_backward")
-        if failed:
-            raise failed[0]
-        dx = bufs[0] if out.value == bufs[0].data_ptr() else bufs[1]
+        # returned to autograd for the leaves -- or one zero-filled slab per block (plain autograd / deterministic sums), returned as the
+        # leaves' / parameters' gradients
+        dx, slabs, lays = _train_backward(ctx, dy, flat and not cfm.ops._deterministic[0])
         head = (dx, None, None, None, None, None, None)
-        if sinks is not None:
-            return head + (None,) * L
+        if slabs is None:
+            return head + (None,) * len(layers)
         if flat:
             return head + tuple(slabs)
-        grads = []
-        for l, slab, lay in zip(layers, slabs, lays):
-            for name, p in l.named_parameters():
-                off, n = lay["layout"][name]
-                grads.append(slab[off:off + n].view(p.shape) if p.requires_grad else None)
-        return head + tuple(grads)
+        return head + _param_grads(layers, slabs, lays)
 
 
 class CTCLossFn(torch.autograd.Function):

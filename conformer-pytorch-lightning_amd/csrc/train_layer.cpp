@@ -1,4 +1,4 @@
-// train_layer.cpp -- one conformer block in TRAIN mode, forward and backward, enqueued from C++ (no host synchronisation, no allocation).
+// train_layer.cpp -- the conformer blocks in TRAIN mode, forward and backward, enqueued from C++ (no host synchronisation, no allocation).
 //
 // reference: src/encoder_layer.py:49-71 under module.train() -- four residual sub-blocks (1/2 FFN, MHSA, convolution module with BatchNorm
 // batch statistics, 1/2 FFN) + norm_final, dropout on every branch output / FFN hidden activation / attention probabilities -- and what
@@ -40,67 +40,32 @@ struct TCtx {
     int M, D, FF, H, dk, adt, wdt;
     bool split;
     cfm_stream_t st;
-    cfm_stream_t side;      // weight-gradient products go here when set (backward)
     int ng;
     Grp grp[CFM_TRAIN_MAX_GROUPS];
     cfm_train_group cg[CFM_TRAIN_MAX_GROUPS];   // the same table in the C-ABI form (the depthwise / BatchNorm entry points take it)
     bool defer;             // weight-gradient products are collected in `pend` and launched as one group at the end of the block's backward
-    cfm_stream_t wg_stream; // ... on this stream when set (the caller owns the hand-off back: cfm_encoder_train_backward)
     cfm_gemm_tn_desc pend[12];
     int npend;
 };
 
-// io -> the context's dimensions and row groups (n_groups == 0: the single micro-batch B x T of the round-2 interface)
+// io -> the context's dimensions and row groups
 int init_ctx(TCtx& c, const cfm_layer_train_weights* w, const cfm_layer_train_io* io, cfm_stream_t stream) {
     c.w = w; c.io = io; c.D = io->D; c.FF = io->FF; c.H = io->H; c.dk = io->D / io->H; c.adt = io->act_dtype; c.wdt = io->w_dtype;
-    c.split = io->act_dtype == CFM_F32; c.st = stream; c.side = nullptr; c.defer = false; c.npend = 0; c.wg_stream = nullptr;
-    if (io->n_groups > 0) {
-        CFM_CHECK_ARG(io->groups && io->n_groups <= CFM_TRAIN_MAX_GROUPS, "train layer: %d row groups (at most %d)", io->n_groups, CFM_TRAIN_MAX_GROUPS);
-        c.ng = io->n_groups;
-        int64_t rows = 0, bht = 0;
-        for (int i = 0; i < c.ng; ++i) {
-            const cfm_train_group& g = io->groups[i];
-            CFM_CHECK_ARG(g.B > 0 && g.T > 0 && g.row0 == rows, "train layer: group %d (B=%d T=%d row0=%lld) must start where group %d ends (%lld)", i, g.B, g.T,
-                          (long long)g.row0, i - 1, (long long)rows);
-            c.grp[i] = {g.B, g.T, g.row0, bht, g.attn_mask, g.am_sb, g.am_sq};
-            c.cg[i] = g;
-            rows += (int64_t)g.B * g.T;
-            bht += (int64_t)g.B * io->H * g.T;
-        }
-        CFM_CHECK_ARG(rows < (1ll << 31), "train layer: %lld rows", (long long)rows);
-        c.M = (int)rows;
-    } else {
-        c.ng = 1;
-        c.grp[0] = {io->B, io->T, 0, 0, io->attn_mask, io->am_sb, io->am_sq};
-        c.cg[0] = {};
-        c.cg[0].B = io->B; c.cg[0].T = io->T; c.cg[0].row0 = 0;
-        c.M = io->B * io->T;
+    c.split = io->act_dtype == CFM_F32; c.st = stream; c.defer = false; c.npend = 0;
+    CFM_CHECK_ARG(io->groups && io->n_groups <= CFM_TRAIN_MAX_GROUPS, "train layer: %d row groups (at most %d)", io->n_groups, CFM_TRAIN_MAX_GROUPS);
+    c.ng = io->n_groups;
+    int64_t rows = 0, bht = 0;
+    for (int i = 0; i < c.ng; ++i) {
+        const cfm_train_group& g = io->groups[i];
+        CFM_CHECK_ARG(g.B > 0 && g.T > 0 && g.row0 == rows, "train layer: group %d (B=%d T=%d row0=%lld) must start where group %d ends (%lld)", i, g.B, g.T,
+                      (long long)g.row0, i - 1, (long long)rows);
+        c.grp[i] = {g.B, g.T, g.row0, bht, g.attn_mask, g.am_sb, g.am_sq};
+        c.cg[i] = g;
+        rows += (int64_t)g.B * g.T;
+        bht += (int64_t)g.B * io->H * g.T;
     }
-    return CFM_OK;
-}
-
-// A small pool of timing-free events for the main -> side stream hand-offs (created once per process; events are recorded and waited on
-// in stream order, so one event can be reused as soon as its wait has been enqueued).
-struct EventPool {
-    hipEvent_t ev[32];
-    int n = 0, next = 0;
-    hipEvent_t get() {
-        if (n < 32) {
-            if (hipEventCreateWithFlags(&ev[n], hipEventDisableTiming) != hipSuccess) return nullptr;
-            return ev[n++];
-        }
-        hipEvent_t e = ev[next];
-        next = (next + 1) % 32;
-        return e;
-    }
-};
-thread_local EventPool g_events;
-
-// make `to` wait for everything enqueued on `from` so far
-int stream_after(cfm_stream_t from, cfm_stream_t to) {
-    hipEvent_t e = g_events.get();
-    if (!e || hipEventRecord(e, (hipStream_t)from) != hipSuccess || hipStreamWaitEvent((hipStream_t)to, e, 0) != hipSuccess)
-        return cfm_fail(CFM_ERR_LAUNCH, "train layer: stream hand-off failed");
+    CFM_CHECK_ARG(rows < (1ll << 31), "train layer: %lld rows", (long long)rows);
+    c.M = (int)rows;
     return CFM_OK;
 }
 
@@ -131,15 +96,10 @@ int gemm(const TCtx& c, const void* A, int a_dt, int64_t lda, const void* W, con
     return cfm_gemm(&d, c.st);
 }
 
-// dW (+)= alpha * A^T . B, db (+)= alpha * colsum(A), accumulated into caller memory.  With a side stream: issued there, after everything the
-// main stream has enqueued so far (its operands); the operands must then stay untouched until the streams are joined (end of the backward)
+// dW (+)= alpha * A^T . B, db (+)= alpha * colsum(A), accumulated into caller memory.  Deferred: kept in `pend` (the operands must then stay
+// untouched until flush_wgrads at the end of the block's backward)
 int wgrad(TCtx& c, const void* A, int a_dt, int64_t lda, const void* B, int b_dt, int64_t ldb, float* dW, float* db, int M, int N, int K, float alpha,
           const uint8_t* row_mask, const int64_t* row_off, const int64_t* colsum_off, const int64_t* colsum_off2 = nullptr) {
-    cfm_stream_t st = c.st;
-    if (c.side) {
-        if (int rc = stream_after(c.st, c.side)) return rc;
-        st = c.side;
-    }
     cfm_gemm_tn_desc d = {};
     d.A = A; d.B = B; d.C = dW; d.colsum = db; d.row_mask = row_mask; d.lda = lda; d.ldb = ldb; d.ldc = K; d.M = M; d.N = N; d.K = K;
     d.a_dtype = a_dt; d.b_dtype = b_dt; d.mma_dtype = c.wdt; d.split = c.split ? 1 : 0; d.accumulate = 1; d.splits = c.io->deterministic ? 1 : 0;
@@ -149,17 +109,13 @@ int wgrad(TCtx& c, const void* A, int a_dt, int64_t lda, const void* B, int b_dt
         c.pend[c.npend++] = d;
         return CFM_OK;
     }
-    return cfm_gemm_tn(&d, st);
+    return cfm_gemm_tn(&d, c.st);
 }
 
 int flush_wgrads(TCtx& c) {
     if (!c.npend) return CFM_OK;
     const int n = c.npend;
     c.npend = 0;
-    if (c.wg_stream) {                                   // after everything the block enqueued on the main stream (the operands), beside what follows
-        if (int rc = stream_after(c.st, c.wg_stream)) return rc;
-        return cfm_gemm_tn_group(c.pend, n, c.wg_stream);
-    }
     return cfm_gemm_tn_group(c.pend, n, c.st);
 }
 
@@ -171,17 +127,7 @@ int ln_fwd(const TCtx& c, const float* x, const float* g, const float* b, void* 
 
 // ---- feed-forward sub-block: x_out = x + 1/2 drop_o(W2 drop_h(silu(W1 LN(x) + b1)) + b2) -------------------------------------------------
 int ffn_fwd(const TCtx& c, const float* x, const float* lg, const float* lb, const void* w1, const void* w1l, const float* b1, const void* w2, const void* w2l,
-            const float* b2, void* xn, void* z, void* h, float* x_out, float p_h, uint32_t s_h, float p_o, uint32_t s_o, bool xn_ready = false,
-            const void* w1f = nullptr, const void* w2f = nullptr) {
-    if (w1f && w2f && !c.split && cfm_ffn_train_supported(c.D, c.FF)) {
-        // ONE launch (csrc/ffn.hip, TRAIN): LayerNorm, both products, both dropout sites, the residual -- the hidden activation goes from the
-        // first product's accumulators into the second's operand and is written out only for the backward (25 us against 5 + 19 + 17 at a
-        // window's 3 400 rows, scripts/bench_ffn_fused_rows.py)
-        cfm_ffn_train_desc d = {};
-        d.x = x; d.ln_g = lg; d.ln_b = lb; d.w1f = w1f; d.w2f = w2f; d.b1 = b1; d.b2 = b2; d.y = x_out; d.xn_out = xn; d.z_out = z; d.h_out = h;
-        d.M = c.M; d.D = c.D; d.FF = c.FF; d.w_dtype = c.wdt; d.alpha = 0.5f; d.eps = 1e-5f; d.p_hidden = p_h; d.seed_hidden = s_h; d.p_out = p_o; d.seed_out = s_o;
-        return cfm_ffn_train_forward(&d, c.st);
-    }
+            const float* b2, void* xn, void* z, void* h, float* x_out, float p_h, uint32_t s_h, float p_o, uint32_t s_o, bool xn_ready = false) {
     if (!xn_ready) CFM_TRY(ln_fwd(c, x, lg, lb, xn, c.adt, nullptr));
     CFM_TRY(gemm(c, xn, c.adt, c.D, w1, w1l, b1, h, c.adt, c.FF, c.M, c.FF, c.D, CFM_ACT_SILU, nullptr, 0.f, nullptr, 0, z, nullptr, p_h, s_h));
     return gemm(c, h, c.adt, c.FF, w2, w2l, b2, x_out, CFM_F32, c.D, c.M, c.D, c.FF, CFM_ACT_NONE, x, 0.5f, nullptr, 0, nullptr, nullptr, p_o, s_o);
@@ -255,7 +201,7 @@ int layer_forward(TCtx& c, const cfm_layer_train_saved* sv, const cfm_layer_trai
     const uint32_t sd = io->seed;
     // (1) macaron feed-forward
     CFM_TRY(ffn_fwd(c, x_in, w->ln_ffm_g, w->ln_ffm_b, w->ffm_w1, w->ffm_w1_lo, w->ffm_b1, w->ffm_w2, w->ffm_w2_lo, w->ffm_b2, sv->xn1, sv->z1, sv->h1, sv->x1,
-                    io->p_hidden_m, site_seed(sd, 1), io->p_branch, site_seed(sd, 2), xn1_ready, w->ffm_w1f, w->ffm_w2f));
+                    io->p_hidden_m, site_seed(sd, 1), io->p_branch, site_seed(sd, 2), xn1_ready));
     // (2) self-attention: q + pos_bias_u rides in the projection's bias; the batch path's positional term is softmax-invariant
     CFM_TRY(ln_fwd(c, sv->x1, w->ln_mha_g, w->ln_mha_b, sv->xn2, adt, nullptr));
     CFM_TRY(gemm(c, sv->xn2, adt, D, w->qkv_w, w->qkv_w_lo, w->qkv_b, sv->qkv, adt, 3 * D, M, 3 * D, D, CFM_ACT_NONE, nullptr, 0.f, nullptr, 0, nullptr, nullptr, 0.f, 0));
@@ -291,7 +237,7 @@ int layer_forward(TCtx& c, const cfm_layer_train_saved* sv, const cfm_layer_trai
                  io->p_branch, site_seed(sd, 6)));
     // (4) feed-forward, (5) norm_final
     CFM_TRY(ffn_fwd(c, sv->x3, w->ln_ff_g, w->ln_ff_b, w->ff_w1, w->ff_w1_lo, w->ff_b1, w->ff_w2, w->ff_w2_lo, w->ff_b2, sv->xn4, sv->z2, sv->h2, sv->x4, io->p_hidden,
-                    site_seed(sd, 7), io->p_branch, site_seed(sd, 8), false, w->ff_w1f, w->ff_w2f));
+                    site_seed(sd, 7), io->p_branch, site_seed(sd, 8)));
     if (next_w && next_sv)
         return cfm_layernorm(sv->x4, w->ln_final_g, w->ln_final_b, y_out, CFM_F32, next_w->ln_ffm_g, next_w->ln_ffm_b, next_sv->xn1, adt, nullptr, 1e-5f, M, D, stream);
     return cfm_layernorm(sv->x4, w->ln_final_g, w->ln_final_b, y_out, CFM_F32, nullptr, nullptr, nullptr, 0, nullptr, 1e-5f, M, D, stream);
@@ -304,21 +250,18 @@ int layer_backward(TCtx& c, const cfm_layer_train_saved* sv, const cfm_layer_tra
     const cfm_layer_train_weights* w = c.w;
     const cfm_layer_train_io* io = c.io;
     cfm_stream_t stream = c.st;
-    c.side = io->side_stream && io->side_stream != stream ? io->side_stream : nullptr;
-    // deferral keeps every product's operands until the block's last launch: same buffers as the side-stream variant; the grouped kernel
-    // takes 16-bit operands (the f32-accurate mode keeps its immediate, single products).  Deferral AND a side stream: the one grouped
-    // launch goes to the side stream (c.wg_stream), everything else stays on the main one
+    // deferral keeps every product's operands until the block's last launch; the grouped kernel takes 16-bit operands (the f32-accurate mode
+    // keeps its immediate, single products)
     c.defer = io->defer_wgrad && !c.split;
-    if (c.defer) { c.wg_stream = c.side; c.side = nullptr; }
-    const bool keep_ops = c.side || c.defer;
-    CFM_CHECK_ARG(!keep_ops || (t->dz2 && t->dyb2 && t->dyb3 && t->dyb4), "cfm_encoder_layer_train_backward: a side stream / deferred weight gradients need the dz2 / dyb2..4 scratch buffers");
-    CFM_CHECK_ARG(!io->grads_accumulate || !io->deterministic, "cfm_encoder_layer_train_backward: grads_accumulate needs deterministic == 0");
+    const bool keep_ops = c.defer;
+    CFM_CHECK_ARG(!keep_ops || (t->dz2 && t->dyb2 && t->dyb3 && t->dyb4), "cfm_encoder_train_backward: deferred weight gradients need the dz2 / dyb2..4 scratch buffers");
+    CFM_CHECK_ARG(!io->grads_accumulate || !io->deterministic, "cfm_encoder_train_backward: grads_accumulate needs deterministic == 0");
     const int M = c.M, D = c.D, adt = c.adt;
     const uint32_t sd = io->seed;
     float* d = dx;                                        // the residual stream's gradient, updated in place from the block's output to its input
     // Each sub-block's branch gradient (dropout mask * alpha * d, act dtype) is written by the LayerNorm backward that produces d -- when it is
     // needed at all: with dropout, or when the operands must outlive the sub-block (d is overwritten by the sub-block's own LayerNorm backward
-    // while a weight-gradient product on the side stream / at the end of the block still reads its operand; one buffer per sub-block then)
+    // while a deferred weight-gradient product at the end of the block still reads its operand; one buffer per sub-block then)
     const bool br = io->p_branch > 0.f || keep_ops;
     float pa1 = io->p_branch, pa2 = io->p_attn_out;
     uint32_t sa1 = site_seed(sd, 4), sa2 = site_seed(sd, 5);
@@ -379,8 +322,8 @@ int layer_backward(TCtx& c, const cfm_layer_train_saved* sv, const cfm_layer_tra
         const bool u_table = g->pos_bias_u && g->qkv_bias_off2;
         CFM_TRY(wgrad(c, t->dqkv, adt, 3 * D, sv->xn2, adt, D, g->slab, g->slab, M, 3 * D, D, 1.0f, nullptr, g->qkv_row_off, g->qkv_bias_off, u_table ? g->qkv_bias_off2 : nullptr));
         if (g->pos_bias_u && g->q_bias && !u_table) {
-            CFM_CHECK_ARG(!c.defer, "cfm_encoder_layer_train_backward: deferred weight gradients need grads.qkv_bias_off2 for pos_bias_u");
-            if (hipMemcpyAsync(g->pos_bias_u, g->q_bias, (size_t)D * 4, hipMemcpyDeviceToDevice, (hipStream_t)(c.side ? c.side : stream)) != hipSuccess)
+            CFM_CHECK_ARG(!c.defer, "cfm_encoder_train_backward: deferred weight gradients need grads.qkv_bias_off2 for pos_bias_u");
+            if (hipMemcpyAsync(g->pos_bias_u, g->q_bias, (size_t)D * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
                 return cfm_fail(CFM_ERR_LAUNCH, "train layer: copy of the pos_bias_u gradient failed");
         }
         CFM_TRY(gemm(c, t->dqkv, adt, 3 * D, w->qkv_t, w->qkv_t_lo, nullptr, t->dxn, CFM_F32, D, M, D, 3 * D, CFM_ACT_NONE, nullptr, 0.f, nullptr, 0, nullptr, nullptr, 0.f, 0));
@@ -389,14 +332,12 @@ int layer_backward(TCtx& c, const cfm_layer_train_saved* sv, const cfm_layer_tra
     // (1) macaron feed-forward
     CFM_TRY(ffn_bwd(c, t, n_ffm.buf, keep_ops ? t->dz2 : t->dz, d, x_in, w->ln_ffm_g, sv->xn1, sv->z1, sv->h1, w->ffm_w1t, w->ffm_w1t_lo, w->ffm_w2t,
                     w->ffm_w2t_lo, g->ffm_w1, g->ffm_b1, g->ffm_w2, g->ffm_b2, g->ln_ffm_g, g->ln_ffm_b, io->p_hidden_m, site_seed(sd, 1), n_none, leave));
-    CFM_TRY(flush_wgrads(c));                            // deferred: the block's eight weight-gradient products, one launch
-    if (c.side) return stream_after(c.side, c.st);       // join: the block's gradients are complete when the main stream gets past this point
-    return CFM_OK;                                       // (c.wg_stream: the caller joins -- cfm_encoder_layer_train_backward at once, the stack one block later)
+    return flush_wgrads(c);                              // deferred: the block's eight weight-gradient products, one launch
 }
 
 int check_io(const cfm_layer_train_io* io, const char* who) {
-    CFM_CHECK_ARG(io->D > 0 && io->H > 0 && io->D % io->H == 0 && io->FF > 0 && io->D % 16 == 0 && (io->n_groups > 0 || (io->B > 0 && io->T > 0)),
-                  "%s: bad dims B=%d T=%d D=%d H=%d FF=%d", who, io->B, io->T, io->D, io->H, io->FF);
+    CFM_CHECK_ARG(io->D > 0 && io->H > 0 && io->D % io->H == 0 && io->FF > 0 && io->D % 16 == 0 && io->n_groups >= 1,
+                  "%s: bad dims D=%d H=%d FF=%d n_groups=%d", who, io->D, io->H, io->FF, io->n_groups);
     return CFM_OK;
 }
 
@@ -404,27 +345,6 @@ int check_io(const cfm_layer_train_io* io, const char* who) {
 inline uint32_t layer_seed(uint32_t seed, int l) { return seed ? seed + 0x632BE5ABu * (uint32_t)l : 0u; }
 
 }  // namespace
-
-extern "C" int cfm_encoder_layer_train_forward(const cfm_layer_train_weights* w, const cfm_layer_train_io* io, const cfm_layer_train_saved* sv,
-                                               const cfm_layer_train_scratch* t, const float* x_in, float* y_out, cfm_stream_t stream) {
-    CFM_CHECK_ARG(w && io && sv && t && x_in && y_out, "cfm_encoder_layer_train_forward: null pointer");
-    CFM_TRY(check_io(io, "cfm_encoder_layer_train_forward"));
-    TCtx c;
-    CFM_TRY(init_ctx(c, w, io, stream));
-    return layer_forward(c, sv, t, x_in, y_out);
-}
-
-extern "C" int cfm_encoder_layer_train_backward(const cfm_layer_train_weights* w, const cfm_layer_train_io* io, const cfm_layer_train_saved* sv,
-                                                const cfm_layer_train_scratch* t, const cfm_layer_train_grads* g, const float* x_in, const float* dy,
-                                                float* dx, cfm_stream_t stream) {
-    CFM_CHECK_ARG(w && io && sv && t && g && x_in && dy && dx && dx != dy, "cfm_encoder_layer_train_backward: null pointer (dx must not alias dy)");
-    CFM_TRY(check_io(io, "cfm_encoder_layer_train_backward"));
-    TCtx c;
-    CFM_TRY(init_ctx(c, w, io, stream));
-    CFM_TRY(layer_backward(c, sv, t, g, x_in, dy, dx));
-    if (c.wg_stream) return stream_after(c.wg_stream, c.st);
-    return CFM_OK;
-}
 
 // ---- the whole stack (encoder.py:72-73 `for block in self.encoders` under module.train()) from one host call each way ------------------------
 extern "C" int cfm_encoder_train_forward(int32_t n_layers, const cfm_layer_train_weights* w, const cfm_layer_train_io* io, const cfm_layer_train_saved* sv,
@@ -437,39 +357,25 @@ extern "C" int cfm_encoder_train_forward(int32_t n_layers, const cfm_layer_train
         iol.seed = layer_seed(io->seed, l);
         TCtx c;
         CFM_TRY(init_ctx(c, &w[l], &iol, stream));
-        // norm_final of block l and norm_ff_macaron of block l+1: one launch -- unless block l+1's macaron feed-forward is the fused launch, which
-        // normalises its rows itself
-        const bool fused_next = l + 1 < n_layers && w[l + 1].ffm_w1f && w[l + 1].ffm_w2f && io->act_dtype != CFM_F32 && cfm_ffn_train_supported(io->D, io->FF);
-        const bool chain = l + 1 < n_layers && !fused_next;
+        // norm_final of block l and norm_ff_macaron of block l+1: one launch
+        const bool chain = l + 1 < n_layers;
         CFM_TRY(layer_forward(c, &sv[l], t, xs[l], xs[l + 1], l > 0, chain ? &w[l + 1] : nullptr, chain ? &sv[l + 1] : nullptr));
     }
     return CFM_OK;
 }
 
 extern "C" int cfm_encoder_train_backward(int32_t n_layers, const cfm_layer_train_weights* w, const cfm_layer_train_io* io, const cfm_layer_train_saved* sv,
-                                          const cfm_layer_train_scratch* t, int32_t n_scratch, const cfm_layer_train_grads* g, float* const* xs, const float* dy,
-                                          float* dbuf0, float* dbuf1, cfm_layer_done_fn done, void* user, float** dx_out, cfm_stream_t stream) {
+                                          const cfm_layer_train_scratch* t, const cfm_layer_train_grads* g, float* const* xs, const float* dy, float* dbuf0,
+                                          float* dbuf1, cfm_layer_done_fn done, void* user, float** dx_out, cfm_stream_t stream) {
     CFM_CHECK_ARG(n_layers > 0 && w && io && sv && t && g && xs && dy && dbuf0 && dbuf1 && dbuf0 != dbuf1 && dx_out && dy != dbuf0 && dy != dbuf1,
                   "cfm_encoder_train_backward: null or aliased pointer");
-    CFM_CHECK_ARG(n_scratch == 1 || n_scratch == 2, "cfm_encoder_train_backward: n_scratch must be 1 or 2");
     CFM_TRY(check_io(io, "cfm_encoder_train_backward"));
-    // Weight gradients beside the chain: with io->side_stream and io->defer_wgrad block l's grouped launch runs on the side stream while the main
-    // stream goes on with block l-1.  Its operands live in scratch set l & 1 (two sets: n_scratch == 2), which block l-2 reuses -- the main
-    // stream waits for block l's launch before block l-2 starts (two blocks later: never a stall in practice), and `done(l)` is reported one
-    // block late, after that wait, so that whoever reduces block l's gradients from the MAIN stream sees them complete.
-    const bool beside = io->side_stream && io->side_stream != stream && io->defer_wgrad && io->act_dtype != CFM_F32;
-    CFM_CHECK_ARG(!beside || n_scratch == 2, "cfm_encoder_train_backward: weight gradients on a side stream need two scratch sets");
-    static thread_local hipEvent_t wg_done[2] = {nullptr, nullptr};
-    if (beside)
-        for (int i = 0; i < 2; ++i)
-            if (!wg_done[i] && hipEventCreateWithFlags(&wg_done[i], hipEventDisableTiming) != hipSuccess)
-                return cfm_fail(CFM_ERR_LAUNCH, "cfm_encoder_train_backward: event creation failed");
     // consecutive blocks: block l+1's last LayerNorm backward (norm_ff_macaron) and block l's first (norm_final) act on the same rows one after the
     // other -- block l+1 leaves its own pending and block l's first launch runs both (cfm_ln_bwd_desc.chain_*); needs the atomic parameter sums
     const bool chain_ln = !io->deterministic;
     const float* cur = dy;
     float* bufs[2] = {dbuf0, dbuf1};
-    int k = 0, report = -1;                               // report: a block whose gradients are complete only after the NEXT block's first launch(es)
+    int k = 0, report = -1;                               // report: a block whose gradients are complete only after the NEXT block's first launch
     PendingLn pend = {}, left = {};
     bool have = false;
     for (int l = n_layers - 1; l >= 0; --l) {
@@ -477,28 +383,16 @@ extern "C" int cfm_encoder_train_backward(int32_t n_layers, const cfm_layer_trai
         iol.seed = layer_seed(io->seed, l);
         TCtx c;
         CFM_TRY(init_ctx(c, &w[l], &iol, stream));
-        const int set = n_scratch == 2 ? (l & 1) : 0;
-        if (beside && l + 2 < n_layers && hipStreamWaitEvent((hipStream_t)stream, wg_done[set], 0) != hipSuccess)       // block l+2's products have read this set
-            return cfm_fail(CFM_ERR_LAUNCH, "cfm_encoder_train_backward: stream wait failed");
         const bool leave = chain_ln && l > 0;
-        CFM_TRY(layer_backward(c, &sv[l], &t[set], &g[l], xs[l], cur, bufs[k], have ? &pend : nullptr, leave ? &left : nullptr));
+        CFM_TRY(layer_backward(c, &sv[l], t, &g[l], xs[l], cur, bufs[k], have ? &pend : nullptr, leave ? &left : nullptr));
         cur = bufs[k];
         k ^= 1;
         have = leave;
         pend = left;
-        if (beside && hipEventRecord(wg_done[set], (hipStream_t)io->side_stream) != hipSuccess)
-            return cfm_fail(CFM_ERR_LAUNCH, "cfm_encoder_train_backward: event record failed");
-        if (report >= 0) {                                // block l+1: its pending LayerNorm sums and (beside) its weight gradients are now enqueued / awaited
-            if (beside && hipStreamWaitEvent((hipStream_t)stream, wg_done[set ^ 1], 0) != hipSuccess) return cfm_fail(CFM_ERR_LAUNCH, "cfm_encoder_train_backward: stream wait failed");
-            if (done) done(report, user);
-            report = -1;
-        }
-        if (beside || leave) report = l;
-        else if (done) done(l, user);                     // every launch of block l's backward is enqueued: its gradients may be reduced
+        if (report >= 0 && done) done(report, user);      // block l+1: its pending LayerNorm sums are now enqueued
+        report = leave ? l : -1;
+        if (!leave && done) done(l, user);                // every launch of block l's backward is enqueued: its gradients may be reduced
     }
-    if (beside)
-        if (int rc = stream_after(io->side_stream, stream)) return rc;     // join: block 0's (and, with it, every) weight gradient
-    if (report >= 0 && done) done(report, user);
     *dx_out = (float*)cur;
     return CFM_OK;
 }

@@ -129,7 +129,7 @@ class DataParallelTrainer:
         self.kernels.weights_changed()
 
         # Autograd UNITS.  A conformer block whose backward writes all its parameter gradients into one contiguous slab (cfm/autograd.py
-        # EncoderLayerFn on the composite path) takes part as ONE leaf -- a view of the flat parameter buffer over the block's range, its
+        # EncoderStackFn, or EncoderLayerFn for a block run on its own) takes part as ONE leaf -- a view of the flat parameter buffer over the block's range, its
         # .grad the same range of the flat gradient buffer: one AccumulateGrad (one add over the slab) and one hook per block instead of
         # ~33.  Every other parameter is its own unit.
         off_of = {id(p): o for p, o in zip(self.params, offs)}
@@ -150,7 +150,8 @@ class DataParallelTrainer:
                 leaf.grad = self.flat_g[lo:hi]
                 blk.__dict__["_flat_leaf"] = leaf
                 blk.__dict__["_flat_grad_offsets"] = {n: off_of[id(p)] - lo for n, p in blk.named_parameters()}
-                # gradient sink: the block's backward adds into this range directly and then calls the ready hook itself (cfm/autograd.py)
+                # gradient sink: the stack's backward adds into this range directly and then calls the ready hook itself (cfm/autograd.py
+                # EncoderStackFn, unless the sums must be deterministic)
                 blk.__dict__["_flat_grad_sink"] = (self.flat_g[lo:hi], functools.partial(self._on_grad, leaf))
                 self.leaves.append(leaf)
                 for p in ps:

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CFM_VERSION 302 /* 0.3.2 (additive, same number): packed RNN-T lattices (cfm_lattice, cfm_rnnt_packed_desc, cfm_rnnt_packed_nll / _grad, cfm_joint_act_packed / _bwd). 0.3.2 (additive, same number): the RNN-T loss (cfm_rnnt_desc, cfm_rnnt_nll, cfm_rnnt_grad) and the transducer joint's activation backward (cfm_joint_act_bwd). 0.3.2: cfm_rowchain_desc.cin_* (the conv-in chain as the input stage of the next launch). 0.3.1: row chains at D = 512, cfm_rowchain_desc.psum_out / psum_in (feed-forward split over workgroup pairs), cfm_conv12_relu at C = 512. 0.3.0: row groups in the train entry points (cfm_train_group, cfm_layer_train_io.n_groups), cfm_gemm_tn_group + deferred weight gradients, cfm_encoder_train_forward / _backward (the whole stack from one host call). 0.2.3: cfm_ffn_split, cfm_layer_scratch.psum (the feed-forward split over FF for few rows). 0.2.2: cfm_ctc_nll_train / cfm_ctc_grad take a beta buffer (both recursions in one launch); GEMM tile ids 9-11 (K groups). 0.2.1: fused front-end (cfm_conv12_relu); attention stage of the conv-in chain (cfm_rowchain_desc.att_*, cfm_layer_scratch.vt). 0.2.0: training entry points */
+#define CFM_VERSION 303 /* 0.3.3: removed cfm_encoder_layer_train_forward / _backward (the stack entry points run a single block), cfm_ffn_train_forward / _supported, cfm_ffn_train_desc, cfm_pack_ffn_fragments, cfm_layer_train_weights.*_w1f / *_w2f, cfm_layer_train_io.B / T / attn_mask / am_sb / am_sq / side_stream and cfm_encoder_train_backward's n_scratch. 0.3.2 (additive, same number): packed RNN-T lattices (cfm_lattice, cfm_rnnt_packed_desc, cfm_rnnt_packed_nll / _grad, cfm_joint_act_packed / _bwd). 0.3.2 (additive, same number): the RNN-T loss (cfm_rnnt_desc, cfm_rnnt_nll, cfm_rnnt_grad) and the transducer joint's activation backward (cfm_joint_act_bwd). 0.3.2: cfm_rowchain_desc.cin_* (the conv-in chain as the input stage of the next launch). 0.3.1: row chains at D = 512, cfm_rowchain_desc.psum_out / psum_in (feed-forward split over workgroup pairs), cfm_conv12_relu at C = 512. 0.3.0: row groups in the train entry points (cfm_train_group, cfm_layer_train_io.n_groups), cfm_gemm_tn_group + deferred weight gradients, cfm_encoder_train_forward / _backward (the whole stack from one host call). 0.2.3: cfm_ffn_split, cfm_layer_scratch.psum (the feed-forward split over FF for few rows). 0.2.2: cfm_ctc_nll_train / cfm_ctc_grad take a beta buffer (both recursions in one launch); GEMM tile ids 9-11 (K groups). 0.2.1: fused front-end (cfm_conv12_relu); attention stage of the conv-in chain (cfm_rowchain_desc.att_*, cfm_layer_scratch.vt). 0.2.0: training entry points */
 
 typedef void* cfm_stream_t;
 
@@ -192,30 +192,6 @@ typedef struct {
 } cfm_ffn_desc;
 
 int cfm_ffn_fused(const cfm_ffn_desc* d, cfm_stream_t stream);
-
-/* The same launch in TRAIN mode (one feed-forward sub-block of encoder_layer.py:56-58 / :67-69 under module.train()):
- *     y = x + alpha * drop_o( W2 . drop_h( silu( W1 . LN(x) + b1 ) ) + b2 )
- * keeping what the backward needs: xn_out = LN(x) (16-bit [M,D], the operand of dW1), z_out = the pre-activation (16-bit [M,FF], silu'),
- * h_out = the hidden activation after its dropout (16-bit [M,FF], the operand of dW2).  Dropout masks are the counter-based ones of the
- * unfused products (element row*FF + column for the hidden, row*D + column for the output: the backward regenerates them).
- * w1f / w2f: the fragment-major packs of cfm_ffn_fused (cfm_pack_ffn_fragments builds them on the device).  D = 256, FF % 128 == 0, FF <= 2048. */
-typedef struct {
-    const float* x;
-    const float *ln_g, *ln_b;
-    const void *w1f, *w2f;
-    const float *b1, *b2;
-    float* y;
-    void *xn_out, *z_out, *h_out;
-    int64_t M;
-    int32_t D, FF, w_dtype;
-    float alpha, eps;
-    float p_hidden, p_out;
-    uint32_t seed_hidden, seed_out;
-} cfm_ffn_train_desc;
-int cfm_ffn_train_supported(int32_t D, int32_t FF);
-int cfm_ffn_train_forward(const cfm_ffn_train_desc* d, cfm_stream_t stream);
-/* w1f / w2f of n_jobs feed-forwards in one launch; job = 4 x int64 on the device: W1 f32 [FF,D], W2 f32 [D,FF], w1f, w2f (16-bit, FF*D elements each). */
-int cfm_pack_ffn_fragments(const int64_t* jobs_dev, int32_t n_jobs, int32_t D, int32_t FF, int32_t w_dtype, cfm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Row-local chain on 32-row tiles, one launch (csrc/rowchain.hip):
@@ -887,13 +863,13 @@ int cfm_pack_matrices(const int64_t* jobs_dev, int32_t n_jobs, int64_t total_til
 int cfm_pack_vectors(const float* const* a, const float* const* b, float* out, int64_t n, cfm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
- * One conformer block in TRAIN mode as two host calls (csrc/train_layer.cpp): encoder_layer.py:49-71 under module.train() and its
+ * The conformer blocks in TRAIN mode (csrc/train_layer.cpp): encoder_layer.py:49-71 under module.train() and its
  * backward, the same launches in the same order as the op-by-op composition of cfm/autograd.py.  All buffers are the caller's:
  *   weights  the train packs (forward [N,K] and transposed [K,N] 16-bit matrices, + lo planes in the f32-accurate mode; cfm/packing.py)
  *   saved    activations the backward needs, act dtype unless typed: xn1..4 [M,D], z1,z2,h1,h2 [M,FF], qkv [M,3D], ctx [M,D], u [M,2D], glu/s [M,D],
  *            f32 x1..x4 / c [M,D], lse [B,H,T], stats [4,D]
  *   scratch  backward work buffers (dxn f32 [M,D], dz [M,FF], dyb/ds/dglu/dctx [M,D], du [M,2D], dqkv [M,3D], delta f32 [B,H,T],
- *            ln_ws cfm_layernorm_bwd_ws floats, dwbn_ws cfm_dwconv_bn_ws floats, dy_ws f32 [M,D]; dz2 / dyb2..4 with a side stream);
+ *            ln_ws cfm_layernorm_bwd_ws floats, dwbn_ws cfm_dwconv_bn_ws floats, dy_ws f32 [M,D]; dz2 / dyb2..4 with io->defer_wgrad);
  *            the forward uses dwbn_ws only
  *   grads    where each parameter's gradient goes: plain pointers, and for the two fused products (q|k|v, the interleaved pointwise-conv-1
  *            pack) per-row element offsets relative to `slab` (cfm_gemm_tn_desc.row_off).  Weight / bias gradients are ACCUMULATED: the
@@ -912,16 +888,11 @@ typedef struct {
     const float *pw1_b, *pw2_b, *dw_w, *dw_b, *bn_gamma, *bn_beta;
     float *bn_running_mean, *bn_running_var;
     float bn_momentum, bn_eps;
-    /* optional: fragment-major packs of the two feed-forwards (cfm_pack_ffn_fragments).  When set (and D = 256, 16-bit mode) each feed-forward's
-     * forward is ONE launch (cfm_ffn_train_forward) instead of LayerNorm + two products. */
-    const void *ffm_w1f, *ffm_w2f, *ff_w1f, *ff_w2f;
 } cfm_layer_train_weights;
 
 
 typedef struct {
-    int32_t B, T, D, H, FF, ktaps, act_dtype, w_dtype;
-    const uint8_t* attn_mask;
-    int64_t am_sb, am_sq;
+    int32_t D, H, FF, ktaps, act_dtype, w_dtype;
     const uint8_t* pad_valid;
     float p_hidden_m, p_hidden, p_branch, p_attn, p_attn_out;
     uint32_t seed;
@@ -929,21 +900,15 @@ typedef struct {
     /* backward only: the gradient slab is a running sum (the optimizer step's flat gradient buffer itself) -- every parameter gradient is ADDED
      * to it and nothing in it is overwritten.  Needs deterministic == 0 (the LayerNorm sums are added with atomics). */
     int32_t grads_accumulate;
-    /* backward only, optional: a second HIP stream of the same device.  The weight-gradient products do not feed the chain of input
-     * gradients, so they are issued there (each after an event on its operands) and overlap with the chain on the main stream -- at
-     * training batch sizes no single kernel fills the chip; the main stream waits for the side stream before the call's work is
-     * complete from its point of view (an event wait, not a host synchronisation).  NULL: everything on `stream`. */
-    cfm_stream_t side_stream;
-    /* ROW GROUPS (optional; n_groups = 0: one micro-batch B x T with attn_mask / am_sb / am_sq above).  The micro-batches of an accumulation
-     * window concatenated along the row axis: every row matrix has M = sum B_g*T_g rows, pad_valid has M entries, lse / delta are the groups'
-     * [B_g,H,T_g] arrays one after the other, stats is [n_groups][4*D].  Row-local work (dense products, LayerNorm, their backward, the
+    /* ROW GROUPS (n_groups >= 1; one group: a single micro-batch).  The micro-batches of an accumulation window concatenated along the row
+     * axis: every row matrix has M = sum B_g*T_g rows, pad_valid has M entries, lse / delta are the groups' [B_g,H,T_g] arrays one after the other, stats is [n_groups][4*D].  Row-local work (dense products, LayerNorm, their backward, the
      * weight gradients) runs once over all rows; attention, the depthwise convolution and BatchNorm run per group, BatchNorm's running
      * statistics updated group after group -- the reference's sequence of forward passes over those micro-batches.  host array. */
     int32_t n_groups;
     const cfm_train_group* groups;
     /* backward: keep the operands of the block's eight weight-gradient products until its last launch and issue them as ONE
      * cfm_gemm_tn_group (needs the dz2 / dyb2..4 scratch buffers and, for pos_bias_u, grads.qkv_bias_off2; 16-bit modes -- ignored in the
-     * f32-accurate mode and with a side stream). */
+     * f32-accurate mode). */
     int32_t defer_wgrad;
 } cfm_layer_train_io;
 
@@ -956,7 +921,7 @@ typedef struct {
     float* dxn;
     void *dz, *dyb, *ds, *dglu, *du, *dctx, *dqkv;
     float *delta, *ln_ws, *dwbn_ws, *dy_ws;
-    void *dz2, *dyb2, *dyb3, *dyb4; /* with a side stream: the operands of overlapped weight-gradient products must outlive the sub-block that
+    void *dz2, *dyb2, *dyb3, *dyb4; /* with io->defer_wgrad: the operands of the deferred weight-gradient products must outlive the sub-block that
                                        made them: second feed-forward's dz, one branch-gradient buffer per sub-block (act dtype, [M,FF] / [M,D]) */
 } cfm_layer_train_scratch;
 
@@ -971,26 +936,19 @@ typedef struct {
     const int64_t* qkv_bias_off2; /* optional: int64 [3D], entry n < D = offset of pos_bias_u[n] relative to slab, others -1 (cfm_gemm_tn_desc.colsum_off2) */
 } cfm_layer_train_grads;
 
-int cfm_encoder_layer_train_forward(const cfm_layer_train_weights* w, const cfm_layer_train_io* io, const cfm_layer_train_saved* sv,
-                                    const cfm_layer_train_scratch* t, const float* x_in, float* y_out, cfm_stream_t stream);
-int cfm_encoder_layer_train_backward(const cfm_layer_train_weights* w, const cfm_layer_train_io* io, const cfm_layer_train_saved* sv,
-                                     const cfm_layer_train_scratch* t, const cfm_layer_train_grads* g, const float* x_in, const float* dy, float* dx,
-                                     cfm_stream_t stream);
-
 /* The whole block stack in train mode (src/encoder.py:72-73 `for block in self.encoders` under module.train()) from ONE host call each way.
  *   w, sv, g  arrays of n_layers structs; io, t shared by all blocks (layer l's dropout seed is derived from io->seed and l)
  *   xs        n_layers + 1 f32 [M,D] row matrices: xs[0] the stack's input, xs[l+1] block l's output (kept: block l+1's backward reads xs[l+1])
  * backward: dy = gradient of xs[n_layers]; dbuf0 / dbuf1 two f32 [M,D] work buffers, *dx_out is set to the one holding the gradient of xs[0].
  * `done(l, user)` (optional) is called on the host right after block l's backward launches have been enqueued, last block first -- the
  * data-parallel trainer starts that block's gradient bucket all-reduce from it (DDP's reducer hook, executor.py:137-154).
- * t is an array of n_scratch (1 or 2) scratch sets, block l uses set l & 1.  With io->defer_wgrad AND io->side_stream (two sets needed) each
- * block's grouped weight-gradient launch runs on the side stream beside the next block's chain of input gradients; `done(l)` is then
- * reported one block late, after the main stream has been made to wait for block l's launch, and the call ends with the streams joined. */
+ * With deterministic == 0 block l's last LayerNorm backward (norm_ff_macaron) runs chained in block l-1's first launch, and `done(l)` follows
+ * that launch.  One block with one row group is the plain single-block training pass. */
 typedef void (*cfm_layer_done_fn)(int32_t layer, void* user);
 int cfm_encoder_train_forward(int32_t n_layers, const cfm_layer_train_weights* w, const cfm_layer_train_io* io, const cfm_layer_train_saved* sv,
                               const cfm_layer_train_scratch* t, float* const* xs, cfm_stream_t stream);
 int cfm_encoder_train_backward(int32_t n_layers, const cfm_layer_train_weights* w, const cfm_layer_train_io* io, const cfm_layer_train_saved* sv,
-                               const cfm_layer_train_scratch* t, int32_t n_scratch, const cfm_layer_train_grads* g, float* const* xs, const float* dy,
+                               const cfm_layer_train_scratch* t, const cfm_layer_train_grads* g, float* const* xs, const float* dy,
                                float* dbuf0, float* dbuf1, cfm_layer_done_fn done, void* user, float** dx_out, cfm_stream_t stream);
 
 /* Optimizer step over flat f32 buffers (module.py:140-143 Adam; executor.py:150 gradient_clip_val):  g' = g * (*grad_scale) + wd * p;

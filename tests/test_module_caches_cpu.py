@@ -138,7 +138,6 @@ def test_stack_weight_array_follows_replaced_norm_tensors(monkeypatch):
     layers = list(enc.encoders)
     pks = tuple(fake_packs() for _ in layers)
     monkeypatch.setattr(packing, "pack_stack_train", lambda owner, ls, prec, rel, flat=False: pks)
-    monkeypatch.setattr(ag, "USE_PACK_KERNEL", True)
     prec = cfm.Precision("bf16")
     arr, _ = ag._stack_weights(enc, layers, prec, False)
     assert ag._stack_weights(enc, layers, prec, False)[0] is arr

@@ -111,7 +111,7 @@ def test_header_declares_and_library_exports_the_packed_entries(cfm):
     for n in NEW_ENTRIES:
         assert n in names, "include/cfm.h does not declare %s" % n
         assert hasattr(lib, n), "libconformer_gfx950.so does not export %s" % n
-    assert lib.cfm_version() == 302
+    assert lib.cfm_version() == 303
 
 
 def test_packed_structs_ctypes_size_matches_c(cfm, tmp_path):

@@ -143,21 +143,26 @@ def test_trainer_bf16_loss_goes_down(p_drop, window):
     assert all(np.isfinite(losses)) and losses[-1] < 0.7 * losses[0]
 
 
-def test_direct_gradient_sink_equals_accumulate_grad():
-    """Blocks registered with a gradient sink can add their gradients straight into the trainer's flat gradient buffer (cfm/autograd.py
-    DIRECT_GRADS, opt-in -- it measured slower: no zero-filled slab, no AccumulateGrad add) -- the flat gradient after 2 accumulated micro-batches equals the
-    autograd-accumulated one up to the order of f32 atomic sums, the buckets are still launched once each and in order, and the buffer is
-    clean again after the step."""
+def test_direct_gradient_sink_equals_accumulate_grad(monkeypatch):
+    """With the atomic sums (the default) the encoder stack adds its blocks' gradients straight into the trainer's flat gradient buffer through
+    their gradient sinks (cfm/autograd.py EncoderStackFn: no zero-filled slab, no AccumulateGrad add); deterministic mode turns the sinks off
+    and the blocks' slabs reach the buffer through AccumulateGrad -- the flat gradient after 2 accumulated micro-batches is the same up to the
+    order of f32 sums, and the buckets are launched once each and in order either way."""
     import cfm
     import trainer as T
     from cfm import autograd as ag
     cfm.set_precision("fp32")
+    dests = []
+    stack_grads = ag._stack_grads
+    monkeypatch.setattr(ag, "_stack_grads", lambda owner, layers, bases, lays, tag, u_table: dests.append(tag) or
+                        stack_grads(owner, layers, bases, lays, tag, u_table))
     try:
         g, meta = load_golden("train_cfg1")
         data = micro_batches(2, 900)
         grads = {}
         for direct in (True, False):
-            ag.DIRECT_GRADS = direct
+            cfm.set_deterministic(not direct)
+            dests.clear()
             enc, dec = build(meta)
             tr = T.DataParallelTrainer([enc, dec], make_loss(enc, dec), lr=1e-3, warmup_steps=2, accum_grad=2, grad_clip=4.0, bucket_mb=1.0, always_reduce=False)
             seen = {}
@@ -165,6 +170,7 @@ def test_direct_gradient_sink_equals_accumulate_grad():
             tr.finish = lambda: seen.setdefault("g", tr.flat_g.clone())        # look at the accumulated gradient instead of stepping
             torch.manual_seed(5)
             tr.step(data)
+            assert dests and set(dests) == {"sink" if direct else "slab"}, dests
             assert tr.reduce_log == list(range(len(tr.buckets)))
             grads[direct] = seen["g"]
             tr.finish = orig_finish
@@ -172,5 +178,5 @@ def test_direct_gradient_sink_equals_accumulate_grad():
         scale = float(b.abs().max())
         assert scale > 0 and float((a - b).abs().max()) < 2e-5 * scale, float((a - b).abs().max()) / scale
     finally:
-        ag.DIRECT_GRADS = False
+        cfm.set_deterministic(False)
         cfm.set_precision("bf16")
