@@ -156,7 +156,7 @@ class RnntDesc(ctypes.Structure):
     _fields_ = [("logits", c_p), ("ld", c_i64), ("logits_dtype", c_i32), ("B", c_i32), ("T", c_i32), ("U1", c_i32), ("V", c_i32), ("blank", c_i32),
                 ("targets", c_p), ("logit_lens", c_p), ("target_lens", c_p),
                 ("lse", c_p), ("lp_blank", c_p), ("lp_label", c_p), ("alpha", c_p), ("beta", c_p), ("shift", c_p),
-                ("nll", c_p), ("nll_shifted", c_p), ("ll_alpha", c_p), ("sweep", c_i32),
+                ("nll", c_p), ("nll_shifted", c_p), ("ll_alpha", c_p),
                 ("grad", c_p), ("ld_grad", c_i64), ("grad_dtype", c_i32), ("grad_cols", c_i32), ("gscale", ctypes.c_float),
                 ("gscale_stride", c_i32), ("gscale_dev", c_p), ("clamp", ctypes.c_float)]
 
@@ -169,7 +169,7 @@ class Lattice(ctypes.Structure):
 class RnntPackedDesc(ctypes.Structure):
     _fields_ = [("lat", Lattice), ("logits", c_p), ("ld", c_i64), ("logits_dtype", c_i32), ("V", c_i32), ("blank", c_i32), ("ld_targets", c_i32),
                 ("targets", c_p), ("lse", c_p), ("lp_blank", c_p), ("lp_label", c_p), ("alpha", c_p), ("beta", c_p), ("shift", c_p),
-                ("nll", c_p), ("nll_shifted", c_p), ("ll_alpha", c_p), ("sweep", c_i32),
+                ("nll", c_p), ("nll_shifted", c_p), ("ll_alpha", c_p),
                 ("grad", c_p), ("ld_grad", c_i64), ("grad_dtype", c_i32), ("grad_cols", c_i32), ("gscale", ctypes.c_float),
                 ("gscale_stride", c_i32), ("gscale_dev", c_p), ("clamp", ctypes.c_float)]
 
@@ -286,7 +286,6 @@ def lib():
         L.cfm_col2im_relu_bwd.argtypes = [c_p, c_i32, c_p, c_i32, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p]
         L.cfm_conv1_wgrad_ws.argtypes = [c_i32, c_i32, c_i32]
         L.cfm_conv1_wgrad.argtypes = [c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p]
-        L.cfm_ctc_nll_train.argtypes = [c_p, c_i64, c_i32, c_i32, c_i32, c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]
         L.cfm_ctc_nll_train_groups.argtypes = [ctypes.POINTER(CtcGroup), c_i32, c_i32, c_p]
         L.cfm_ctc_grad.argtypes = [c_p, c_i64, c_i32, c_i32, c_i32, c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p]
         L.cfm_adam_step.argtypes = [c_p, c_p, c_p, c_p, c_i64, c_f, c_f, c_f, c_f, c_f, c_i64, c_p, c_p]
@@ -316,7 +315,7 @@ def lib():
                      "cfm_valid_mask", "cfm_chunk_mask", "cfm_attn_mask", "cfm_cast", "cfm_add_rows",
                      "cfm_encoder_layer_forward", "cfm_ctc_nll", "cfm_joint_act", "cfm_joint_act_bwd", "cfm_rnnt_nll", "cfm_rnnt_grad", "cfm_prof_entry", "cfm_gemm_tn", "cfm_gemm_tn_group", "cfm_attention_bwd",
                      "cfm_layernorm_bwd", "cfm_glu_bwd", "cfm_dwconv_bn_train", "cfm_dwconv_bn_train_bwd", "cfm_col2im_relu_bwd", "cfm_conv1_wgrad",
-                     "cfm_ctc_nll_train", "cfm_ctc_nll_train_groups", "cfm_ctc_grad", "cfm_adam_step", "cfm_adam_clip_step", "cfm_sumsq", "cfm_dropout_rows", "cfm_dropout_mask", "cfm_pack_matrices", "cfm_pack_vectors", "cfm_greedy_step", "cfm_ffn_split", "cfm_ffn_split_supported", "cfm_layernorm_bwd_fused", "cfm_dwconv_bn_train_bwd_acc",
+                     "cfm_ctc_nll_train_groups", "cfm_ctc_grad", "cfm_adam_step", "cfm_adam_clip_step", "cfm_sumsq", "cfm_dropout_rows", "cfm_dropout_mask", "cfm_pack_matrices", "cfm_pack_vectors", "cfm_greedy_step", "cfm_ffn_split", "cfm_ffn_split_supported", "cfm_layernorm_bwd_fused", "cfm_dwconv_bn_train_bwd_acc",
                      "cfm_encoder_train_forward", "cfm_encoder_train_backward", "cfm_stream_prep", "cfm_kv_ring_write", "cfm_stream_advance", "cfm_dwconv_causal_bn_silu", "cfm_conv_cache_update"):
             getattr(L, name).restype = ctypes.c_int
         _lib = L

@@ -4,7 +4,7 @@ Each Function's ``forward`` runs the train-mode kernels and keeps what the backw
 every ``nn.Parameter`` it was given (so ``.grad`` accumulation, DDP reducer hooks and gradient accumulation work as with any torch
 op -- SURVEY 8b "Threading").  Nothing here computes: the arithmetic is cfm.gemm (input gradients, on transposed weight packs, with
 the activation-derivative epilogues), cfm.gemm_tn (weight / bias gradients), cfm.layernorm_bwd, cfm.attention_bwd,
-cfm.dwconv_bn_train(_bwd), cfm.glu_bwd, cfm.col2im_relu_bwd, cfm.conv1_wgrad, cfm.ctc_nll_train / cfm.ctc_grad.
+cfm.dwconv_bn_train(_bwd), cfm.glu_bwd, cfm.col2im_relu_bwd, cfm.conv1_wgrad, cfm.ctc_nll_train_groups / cfm.ctc_grad.
 
 What train mode means here (reference: encoder_layer.py:49-71, convolution.py:34-49, decoder.py:18-23 under module.train()):
   * BatchNorm1d uses BATCH statistics over all B*T' positions, padded frames included (quirk Q6), and updates its running statistics;
@@ -769,33 +769,11 @@ class EncoderStackFn(torch.autograd.Function):
 
 
 class CTCLossFn(torch.autograd.Function):
-    """sum_b nll_b / padded label length on top of ctc_lo (decoder.py:19-22)."""
-
-    @staticmethod
-    def forward(ctx, enc_out, mod, prec, enc_lens, labels, label_lens, weight, bias):
-        pk = packing.pack_ctc_train(mod, prec)
-        B, T, D = enc_out.shape
-        x2 = _f32c(enc_out.reshape(B * T, D))
-        logits = _gemm(x2, pk.w, bias=pk.b, w_lo=pk.w_lo, out_dtype=torch.float32).view(B, T, pk.Vp)
-        nll, state = cfm.ctc_nll_train(logits, pk.V, enc_lens, labels, label_lens)
-        ctx.args = (prec, pk, x2, logits, state, enc_lens, labels, label_lens, B, T, D)
-        return nll.sum() / labels.size(1)
-
-    @staticmethod
-    def backward(ctx, gout):
-        prec, pk, x2, logits, state, enc_lens, labels, label_lens, B, T, D = ctx.args
-        gdev = _f32c(gout.reshape(1))
-        dlog = cfm.ctc_grad(logits, pk.V, enc_lens, labels, label_lens, state, gscale=1.0 / labels.size(1), gscale_dev=gdev).view(B * T, pk.Vp)
-        dW, db = cfm.gemm_tn(dlog, x2, want_colsum=True, mma_code=prec.w_code, split=prec.split)
-        dx = _gemm(dlog, pk.wt, w_lo=pk.wt_lo, out_dtype=torch.float32)
-        return dx.view(B, T, D), None, None, None, None, None, dW[:pk.V], db[:pk.V]
-
-
-class CTCWindowLossFn(torch.autograd.Function):
-    """The CTC heads of an accumulation window in one projection: the window's rows are one [M, D] matrix (ConformerEncoder.forward_window), so the
-    vocabulary projection, its weight gradient and its input gradient each run ONCE over all micro-batches' rows; the recursions and the per-row
-    gradients run per micro-batch on slices of the one logits matrix (each micro-batch has its own T', label width and normaliser).
-    Returns the micro-batches' losses (sum_b nll_b / padded label length each, decoder.py:19-22) as a 1-D tensor."""
+    """The CTC heads of an accumulation window in one projection (a single batch is a window of one micro-batch): the window's rows are one [M, D]
+    matrix (ConformerEncoder.forward_window), so the vocabulary projection, its weight gradient and its input gradient each run ONCE over all
+    micro-batches' rows; the recursions and the per-row gradients run per micro-batch on slices of the one logits matrix (each micro-batch has its
+    own T', label width and normaliser).  Returns the micro-batches' losses (sum_b nll_b / padded label length each, decoder.py:19-22) as a 1-D
+    tensor."""
 
     @staticmethod
     def forward(ctx, rows, mod, prec, groups, weight, bias):
@@ -808,12 +786,14 @@ class CTCWindowLossFn(torch.autograd.Function):
             problems.append((logits[r0:r0 + B * T].view(B, T, pk.Vp), enc_lens, labels, label_lens))
             r0 += B * T
         res = cfm.ctc_nll_train_groups(problems, pk.V)         # the recursions of all micro-batches in one launch
-        losses = [nll.sum() / pr[2].size(1) for (nll, _), pr in zip(res, problems)]
+        losses = torch.empty((len(groups),), dtype=torch.float32, device=x2.device)
+        for g, ((nll, _), pr) in enumerate(zip(res, problems)):
+            torch.div(nll.sum(), pr[2].size(1), out=losses[g])
         states = [st for _, st in res]
         if r0 != x2.shape[0]:
-            raise RuntimeError("CTCWindowLossFn: the micro-batches cover %d rows, the row matrix has %d" % (r0, x2.shape[0]))
+            raise RuntimeError("CTCLossFn: the micro-batches cover %d rows, the row matrix has %d" % (r0, x2.shape[0]))
         ctx.args = (prec, pk, x2, logits, states, groups)
-        return torch.stack(losses)
+        return losses
 
     @staticmethod
     def backward(ctx, gout):
@@ -842,12 +822,16 @@ def _rnnt_reduce(nll, reduction):
 
 
 class RNNTLossFn(torch.autograd.Function):
-    """rnnt.rnnt_loss: torchaudio.functional.rnnt_loss (model.py:107) over given logits; the gradient is a buffer of its own (the caller's logits
-    are left as they are)."""
+    """rnnt.rnnt_loss / rnnt.rnnt_loss_packed: torchaudio.functional.rnnt_loss (model.py:107) over given logits, padded [B,T,U+1,V] with
+    lens = (logit_lens, target_lens), or packed [M, V] with lens = a cfm.lattice.Lattice; the gradient is a buffer of its own (the caller's
+    logits are left as they are)."""
 
     @staticmethod
-    def forward(ctx, logits, targets, logit_lens, target_lens, blank, clamp, reduction):
-        nll, st = cfm.rnnt_nll(logits, targets, logit_lens, target_lens, blank)
+    def forward(ctx, logits, targets, lens, blank, clamp, reduction):
+        if logits.dim() == 2:
+            nll, st = cfm.rnnt_nll_packed(logits, targets, lens, blank)
+        else:
+            nll, st = cfm.rnnt_nll(logits, targets, *lens, blank)
         ctx.args = (st, clamp, reduction)
         return _rnnt_reduce(nll, reduction)
 
@@ -855,114 +839,61 @@ class RNNTLossFn(torch.autograd.Function):
     def backward(ctx, gout):
         st, clamp, reduction = ctx.args
         logits = st.logits
-        gs, gdev = _rnnt_scale(gout, reduction, logits.shape[0])
+        gs, gdev = _rnnt_scale(gout, reduction, st.nll.numel())
         grad = cfm.rnnt_grad(st, torch.empty(logits.shape, dtype=logits.dtype, device=logits.device), gscale=gs, gscale_dev=gdev, clamp=clamp)
-        return grad, None, None, None, None, None, None
-
-
-class JointRNNTLossFn(torch.autograd.Function):
-    """TransducerJoint.rnnt_loss: the joint (joint.py:20-38) followed by the RNN-T loss (model.py:107), differentiable w.r.t. enc_out, pred_out and
-    the six joint parameters.  The [B,T,U+1,Vp] f32 logits exist only in here, and the gradient overwrites them in place (f32 in the accurate
-    mode; the 16-bit type of the backward GEMMs otherwise, in the first half of each row's bytes): ONE logits-sized buffer."""
-
-    @staticmethod
-    def forward(ctx, xe, xp, mod, prec, targets, enc_lens, target_lens, blank, clamp, reduction, *params):
-        pk = packing.pack_joint_train(mod, prec)
-        B, T, E = xe.shape
-        U1 = xp.shape[1]
-        xe2, xp2 = _f32c(xe.reshape(B * T, E)), _f32c(xp.reshape(B * U1, xp.shape[2]))
-        e = cfm.gemm(xe2, pk.enc.w, bias=pk.enc.b, w_lo=pk.enc.w_lo, out_dtype=torch.float32)
-        p = cfm.gemm(xp2, pk.pred.w, bias=pk.pred.b, w_lo=pk.pred.w_lo, out_dtype=torch.float32)
-        if e.shape[1] != pk.out.w.shape[1]:
-            raise ValueError("TransducerJoint.rnnt_loss: join dimensions differ (%d, ffn_out expects %d)" % (e.shape[1], pk.out.w.shape[1]))
-        act = cfm.joint_act(e, p, B, T, U1, prec.act_dtype)
-        logits = cfm.gemm(act, pk.out.w, bias=pk.out.b, w_lo=pk.out.w_lo, out_dtype=torch.float32)
-        nll, st = cfm.rnnt_nll(logits.view(B, T, U1, pk.Vp), targets, enc_lens, target_lens, blank, V=pk.V)
-        ctx.args = (pk, prec, xe2, xp2, e, p, act, logits, st, clamp, reduction, B, T, U1, xe.shape, xp.shape)
-        return _rnnt_reduce(nll, reduction)
-
-    @staticmethod
-    def backward(ctx, gout):
-        pk, prec, xe2, xp2, e, p, act, logits, st, clamp, reduction, B, T, U1, xe_shape, xp_shape = ctx.args
-        ctx.args = None
-        gs, gdev = _rnnt_scale(gout, reduction, B)
-        M, Vp = logits.shape
-        if prec.split:                                           # f32 gradient over the f32 logits, same bytes
-            cfm.rnnt_grad(st, logits.view(B, T, U1, Vp), gscale=gs, gscale_dev=gdev, clamp=clamp)
-            dlog = logits
-        else:                                                    # 16-bit gradient in the first half of each f32 row
-            half = logits.view(prec.w_dtype)                     # [M, 2 Vp]
-            cfm.rnnt_grad(st, half.view(B, T, U1, 2 * Vp), gscale=gs, gscale_dev=gdev, clamp=clamp, cols=Vp)
-            dlog = half[:, :Vp]
-        dWo, dbo = cfm.gemm_tn(dlog, act, want_colsum=True, mma_code=prec.w_code, split=prec.split)
-        dact = _gemm(dlog, pk.out.wt, w_lo=pk.out.wt_lo, out_dtype=torch.float32)
-        del logits, dlog, st
-        de, dp = cfm.joint_act_bwd(e, p, dact, B, T, U1)
-        del dact
-        dWe, dbe = cfm.gemm_tn(de, xe2, want_colsum=True, mma_code=prec.w_code, split=prec.split)
-        dWp, dbp = cfm.gemm_tn(dp, xp2, want_colsum=True, mma_code=prec.w_code, split=prec.split)
-        dxe = _gemm(de, pk.enc.wt, w_lo=pk.enc.wt_lo, out_dtype=torch.float32)
-        dxp = _gemm(dp, pk.pred.wt, w_lo=pk.pred.wt_lo, out_dtype=torch.float32)
-        V = pk.V
-        return (dxe.view(xe_shape), dxp.view(xp_shape), None, None, None, None, None, None, None, None,
-                dWe, dbe, dWp, dbp, dWo[:V], dbo[:V])
-
-
-class RNNTPackedLossFn(torch.autograd.Function):
-    """rnnt.rnnt_loss_packed: RNNTLossFn over the rows of a packed lattice (cfm.lattice.Lattice); the gradient is a buffer of its own."""
-
-    @staticmethod
-    def forward(ctx, logits, targets, lat, blank, clamp, reduction):
-        nll, st = cfm.rnnt_nll_packed(logits, targets, lat, blank)
-        ctx.args = (st, clamp, reduction)
-        return _rnnt_reduce(nll, reduction)
-
-    @staticmethod
-    def backward(ctx, gout):
-        st, clamp, reduction = ctx.args
-        logits = st.logits
-        gs, gdev = _rnnt_scale(gout, reduction, st.desc.lat.B)
-        grad = cfm.rnnt_grad_packed(st, torch.empty(logits.shape, dtype=logits.dtype, device=logits.device), gscale=gs, gscale_dev=gdev, clamp=clamp)
         return grad, None, None, None, None, None
 
 
-class JointRNNTPackedLossFn(torch.autograd.Function):
-    """TransducerJoint.rnnt_loss(packed=True) and TransducerJoint.forward_window: JointRNNTLossFn over a packed lattice.  Encoder rows xe2
-    [n_enc, E] and predictor rows xp2 [n_pred, P] are projected whole (they are small); the activation, the logits and the loss exist for the
-    M valid cells only, the logits once, with the gradient in place.  Rows outside the lattice get exact zero gradients."""
+class JointRNNTLossFn(torch.autograd.Function):
+    """TransducerJoint.rnnt_loss and TransducerJoint.forward_window: the joint (joint.py:20-38) followed by the RNN-T loss (model.py:107),
+    differentiable w.r.t. the encoder rows xe2 [n_enc, E], the predictor rows xp2 [n_pred, P] and the six joint parameters.  lat: the padded
+    shape (B, T, U+1, enc_lens, target_lens) -- rows b*T + t and b*(U+1) + u -- or a packed lattice (cfm.lattice.Lattice), whose activation, logits
+    and loss exist for its M valid cells only (rows outside it get exact zero gradients).  The f32 logits exist only in here, and the gradient
+    overwrites them in place (f32 in the accurate mode; the 16-bit type of the backward GEMMs otherwise, in the first half of each row's bytes):
+    ONE logits-sized buffer."""
 
     @staticmethod
     def forward(ctx, xe2, xp2, mod, prec, lat, targets, blank, clamp, reduction, *params):
         pk = packing.pack_joint_train(mod, prec)
-        e = cfm.gemm(_f32c(xe2), pk.enc.w, bias=pk.enc.b, w_lo=pk.enc.w_lo, out_dtype=torch.float32)
-        p = cfm.gemm(_f32c(xp2), pk.pred.w, bias=pk.pred.b, w_lo=pk.pred.w_lo, out_dtype=torch.float32)
+        xe2, xp2 = _f32c(xe2), _f32c(xp2)
+        e = cfm.gemm(xe2, pk.enc.w, bias=pk.enc.b, w_lo=pk.enc.w_lo, out_dtype=torch.float32)
+        p = cfm.gemm(xp2, pk.pred.w, bias=pk.pred.b, w_lo=pk.pred.w_lo, out_dtype=torch.float32)
         if e.shape[1] != pk.out.w.shape[1]:
             raise ValueError("TransducerJoint: join dimensions differ (%d, ffn_out expects %d)" % (e.shape[1], pk.out.w.shape[1]))
-        if lat.M == 0:
-            raise ValueError("TransducerJoint: no utterance has a frame (every encoder length is 0)")
-        act = cfm.joint_act_packed(e, p, lat, prec.act_dtype)
+        packed = not isinstance(lat, tuple)
+        if packed:
+            if lat.M == 0:
+                raise ValueError("TransducerJoint: no utterance has a frame (every encoder length is 0)")
+            act = cfm.joint_act_packed(e, p, lat, prec.act_dtype)
+        else:
+            act = cfm.joint_act(e, p, *lat[:3], prec.act_dtype)
         logits = cfm.gemm(act, pk.out.w, bias=pk.out.b, w_lo=pk.out.w_lo, out_dtype=torch.float32)
-        nll, st = cfm.rnnt_nll_packed(logits, targets, lat, blank, V=pk.V)
-        ctx.args = (pk, prec, _f32c(xe2), _f32c(xp2), e, p, act, logits, st, lat, clamp, reduction)
+        if packed:
+            nll, st = cfm.rnnt_nll_packed(logits, targets, lat, blank, V=pk.V)
+        else:
+            B, T, U1, enc_lens, target_lens = lat
+            nll, st = cfm.rnnt_nll(logits.view(B, T, U1, pk.Vp), targets, enc_lens, target_lens, blank, V=pk.V)
+        ctx.args = (pk, prec, xe2, xp2, e, p, act, logits, st, lat, clamp, reduction)
         return _rnnt_reduce(nll, reduction)
 
     @staticmethod
     def backward(ctx, gout):
         pk, prec, xe2, xp2, e, p, act, logits, st, lat, clamp, reduction = ctx.args
         ctx.args = None
-        gs, gdev = _rnnt_scale(gout, reduction, lat.B)
+        packed = not isinstance(lat, tuple)
+        gs, gdev = _rnnt_scale(gout, reduction, lat.B if packed else lat[0])
         Vp = logits.shape[1]
         if prec.split:                                           # f32 gradient over the f32 logits, same bytes
-            cfm.rnnt_grad_packed(st, logits, gscale=gs, gscale_dev=gdev, clamp=clamp)
+            cfm.rnnt_grad(st, logits.view(*st.rows, Vp), gscale=gs, gscale_dev=gdev, clamp=clamp)
             dlog = logits
         else:                                                    # 16-bit gradient in the first half of each f32 row
             half = logits.view(prec.w_dtype)                     # [M, 2 Vp]
-            cfm.rnnt_grad_packed(st, half, gscale=gs, gscale_dev=gdev, clamp=clamp, cols=Vp)
+            cfm.rnnt_grad(st, half.view(*st.rows, 2 * Vp), gscale=gs, gscale_dev=gdev, clamp=clamp, cols=Vp)
             dlog = half[:, :Vp]
         dWo, dbo = cfm.gemm_tn(dlog, act, want_colsum=True, mma_code=prec.w_code, split=prec.split)
         dact = _gemm(dlog, pk.out.wt, w_lo=pk.out.wt_lo, out_dtype=torch.float32)
         del logits, dlog, st
-        de, dp = cfm.joint_act_packed_bwd(e, p, dact, lat)
+        de, dp = cfm.joint_act_packed_bwd(e, p, dact, lat) if packed else cfm.joint_act_bwd(e, p, dact, *lat[:3])
         del dact
         dWe, dbe = cfm.gemm_tn(de, xe2, want_colsum=True, mma_code=prec.w_code, split=prec.split)
         dWp, dbp = cfm.gemm_tn(dp, xp2, want_colsum=True, mma_code=prec.w_code, split=prec.split)

@@ -2,14 +2,12 @@
 allocates its output with torch.empty on the same device, and enqueues on the current HIP stream."""
 import ctypes
 
-import os
-
 import torch
 
 import cfm as _c
 
 __all__ = ["stream_prep", "stream_advance", "dwconv_causal_bn_silu", "conv_cache_update", "dropout_rows", "dropout_mask", "set_deterministic", "gemm_tn", "gemm_tn_group", "layernorm_bwd", "glu_bwd", "dwconv_bn_train", "dwconv_bn_train_bwd", "col2im_relu_bwd", "conv1_wgrad", "attention_bwd",
-           "ctc_nll_train", "ctc_nll_train_groups", "ctc_grad", "rnnt_nll", "rnnt_grad", "joint_act_bwd", "rnnt_nll_packed", "rnnt_grad_packed", "joint_act_packed", "joint_act_packed_bwd", "ffn_split", "adam_step", "adam_clip_step", "sumsq", "scratch_stats",
+           "ctc_nll_train_groups", "ctc_grad", "rnnt_nll", "rnnt_grad", "joint_act_bwd", "rnnt_nll_packed", "joint_act_packed", "joint_act_packed_bwd", "ffn_split", "adam_step", "adam_clip_step", "sumsq", "scratch_stats",
            "gemm", "ffn_fused", "ffn_fused_supported", "rowchain", "rowchain_supported", "rowchain_pair_supported", "layernorm", "attention", "kv_cache_pack", "dwconv_bn_silu", "conv1_relu", "conv1_relu_mma_supported", "conv12_relu", "conv12_supported", "ctc_nll", "joint_act", "valid_mask", "chunk_mask",
            "attn_mask_combine", "cast", "add_rows", "scratch", "prof_enable", "prof_reset", "prof_table", "as_u8_mask"]
 
@@ -669,30 +667,10 @@ def _ctc_args(logits, enc_lens, labels, label_lens):
         raise ValueError("cfm.ctc: batch sizes differ")
 
 
-def ctc_nll_train(logits, V, enc_lens, labels, label_lens, beta_now=None):
-    """As ctc_nll, keeping what the backward needs: returns (nll [B], state) with state = (work, alpha, lse, nll_shifted, beta | None) owned by the
-    caller.  beta_now: run the backward recursion beside the forward one (one launch of 2 B workgroups) instead of inside ctc_grad."""
-    _c.require_hip(logits, enc_lens, labels, label_lens)
-    _ctc_args(logits, enc_lens, labels, label_lens)
-    if beta_now is None:
-        beta_now = os.environ.get("CFM_CTC_BETA_NOW", "1") != "0"        # A/B switch (same bits either way)
-    B, T = logits.shape[:2]
-    SM = 2 * labels.size(1) + 2
-    dev = logits.device
-    nll = torch.empty((B,), dtype=torch.float32, device=dev)
-    nllp = torch.empty((B,), dtype=torch.float32, device=dev)
-    work = torch.empty((B, T, SM), dtype=torch.float32, device=dev)
-    alpha = torch.empty((B, T, SM), dtype=torch.float32, device=dev)
-    lse = torch.empty((B, T), dtype=torch.float32, device=dev)
-    beta = torch.empty((B, T, SM), dtype=torch.float32, device=dev) if beta_now else None
-    _c.check(_c.lib().cfm_ctc_nll_train(_c.ptr(logits), logits.stride(1), B, T, V, _c.ptr(enc_lens), _c.ptr(labels), labels.size(1), _c.ptr(label_lens),
-                                        _c.ptr(work), _c.ptr(alpha), _c.ptr(lse), _c.ptr(nll), _c.ptr(nllp), _c.ptr(beta), _c.stream()), "cfm_ctc_nll_train")
-    return nll, (work, alpha, lse, nllp, beta)
-
-
 def ctc_nll_train_groups(problems, V):
-    """ctc_nll_train for several micro-batches with ONE launch for all their recursions (include/cfm.h cfm_ctc_nll_train_groups).
-    problems: [(logits [B,T,ld], enc_lens, labels, label_lens)]; returns [(nll [B], state)] as ctc_nll_train does."""
+    """As ctc_nll for the micro-batches of a training window (a single batch is a window of one), keeping what ctc_grad needs, with ONE launch for
+    all their recursions (include/cfm.h cfm_ctc_nll_train_groups).  problems: [(logits [B,T,ld], enc_lens, labels, label_lens)]; returns
+    [(nll [B], state)] with state = (work, alpha, lse, nll_shifted, beta) owned by the caller."""
     n = len(problems)
     arr = (_c.CtcGroup * n)()
     outs = []
@@ -714,11 +692,10 @@ def ctc_nll_train_groups(problems, V):
 
 
 def ctc_grad(logits, V, enc_lens, labels, label_lens, state, gscale=1.0, gscale_dev=None, out=None):
-    """d (sum_b nll_b) / d logits * gscale * (*gscale_dev), f32 [B,T,ld]; consumes state[1] (alpha is overwritten unless the state carries beta)."""
+    """d (sum_b nll_b) / d logits * gscale * (*gscale_dev), f32 [B,T,ld], from one micro-batch's state of ctc_nll_train_groups."""
     _c.require_hip(logits, enc_lens, labels, label_lens, gscale_dev, out)
     _ctc_args(logits, enc_lens, labels, label_lens)
-    work, alpha, lse, nllp = state[:4]
-    beta = state[4] if len(state) > 4 else None
+    work, alpha, lse, nllp, beta = state
     B, T = logits.shape[:2]
     if out is None:
         out = torch.empty_like(logits)
@@ -729,14 +706,16 @@ def ctc_grad(logits, V, enc_lens, labels, label_lens, state, gscale=1.0, gscale_
     return out
 
 
-_RNNT_SWEEPS = {"auto": 0, "wave": 1, "lds": 2}
-
-
 class RnntState:
-    """What cfm_rnnt_grad needs after cfm_rnnt_nll: the filled cfm_rnnt_desc and the tensors its pointers refer to (kept alive here)."""
+    """What cfm_rnnt_grad / cfm_rnnt_packed_grad need after rnnt_nll / rnnt_nll_packed: the filled descriptor, the tensors its pointers refer to
+    (kept alive here) and the leading shape of the gradient, rows = (B, T, U+1) padded or (M,) packed."""
 
-    def __init__(self, desc, logits, tensors):
-        self.desc, self.logits, self.tensors = desc, logits, tensors
+    def __init__(self, desc, logits, tensors, rows):
+        self.desc, self.logits, self.tensors, self.rows = desc, logits, tensors, rows
+
+    @property
+    def packed(self):
+        return isinstance(self.desc, _c.RnntPackedDesc)
 
     def __getattr__(self, name):
         t = self.__dict__.get("tensors")
@@ -745,7 +724,27 @@ class RnntState:
         raise AttributeError(name)
 
 
-def rnnt_nll(logits, targets, logit_lens, target_lens, blank, V=None, sweep=None):
+def _rnnt_state(d, what, logits, ld, V, blank, targets, nodes, B, shift_cols):
+    """The part of rnnt_nll / rnnt_nll_packed both layouts share: the V check, the state arrays (nodes: their per-node shape) and the descriptor
+    fields common to cfm_rnnt_desc and cfm_rnnt_packed_desc.  An empty array gets nll's address (the C checks want a pointer; nothing is read),
+    empty targets none."""
+    W = logits.shape[-1]
+    V = W if V is None else V
+    if not 1 < V <= W:
+        raise ValueError("cfm.%s: V = %d with %d columns" % (what, V, W))
+    dev = logits.device
+    f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    tens = dict(lse=f(*nodes), lp_blank=f(*nodes), lp_label=f(*nodes), alpha=f(*nodes), beta=f(*nodes), shift=f(B, shift_cols), nll=f(B),
+                nll_shifted=f(B), ll_alpha=f(B), targets=targets)
+    d.logits, d.ld, d.logits_dtype = logits.data_ptr(), ld, _c.dt_code(logits)
+    d.V, d.blank = V, blank
+    for name in ("targets", "lse", "lp_blank", "lp_label", "alpha", "beta", "shift", "nll", "nll_shifted", "ll_alpha"):
+        t = tens[name]
+        setattr(d, name, t.data_ptr() if t.numel() else None if name == "targets" else tens["nll"].data_ptr())
+    return tens
+
+
+def rnnt_nll(logits, targets, logit_lens, target_lens, blank, V=None):
     """RNN-T negative log-likelihood per utterance from UN-normalised logits [B,T,U+1,>=V] (rows evenly spaced, unit inner stride; f32 / bf16 /
     fp16), targets int32 [B,U], logit_lens / target_lens int32 [B] (include/cfm.h cfm_rnnt_nll).  V defaults to logits.size(3) (pass it when the
     last axis holds pad columns).  Returns (nll f32 [B], RnntState) -- the state carries lse / lp_blank / lp_label / alpha / beta / shift /
@@ -753,55 +752,54 @@ def rnnt_nll(logits, targets, logit_lens, target_lens, blank, V=None, sweep=None
     _c.require_hip(logits, targets, logit_lens, target_lens)
     if logits.dim() != 4 or logits.stride(3) != 1:
         raise ValueError("cfm.rnnt_nll: logits must be [B,T,U+1,V] with unit inner stride, got %s strides %s" % (tuple(logits.shape), logits.stride()))
-    B, T, U1, W = logits.shape
+    B, T, U1 = logits.shape[:3]
     ld = logits.stride(2)
     if logits.stride(1) != U1 * ld or logits.stride(0) != T * U1 * ld:
         raise ValueError("cfm.rnnt_nll: logits rows must be evenly spaced (strides %s)" % (logits.stride(),))
-    V = W if V is None else V
-    if not 1 < V <= W:
-        raise ValueError("cfm.rnnt_nll: V = %d with %d columns" % (V, W))
     for t in (targets, logit_lens, target_lens):
         if t.dtype != torch.int32 or not t.is_contiguous():
             raise ValueError("cfm.rnnt_nll: targets and lengths must be contiguous int32")
     if tuple(targets.shape) != (B, U1 - 1) or logit_lens.numel() != B or target_lens.numel() != B:
         raise ValueError("cfm.rnnt_nll: targets %s / lengths do not match logits %s" % (tuple(targets.shape), tuple(logits.shape)))
-    if sweep is None:
-        sweep = os.environ.get("CFM_RNNT_SWEEP", "auto")                  # A/B switch of the recursion (same bits either way)
-    dev = logits.device
-    f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-    tens = dict(lse=f(B, T, U1), lp_blank=f(B, T, U1), lp_label=f(B, T, U1), alpha=f(B, T, U1), beta=f(B, T, U1), shift=f(B, T + U1),
-                nll=f(B), nll_shifted=f(B), ll_alpha=f(B), targets=targets, logit_lens=logit_lens, target_lens=target_lens)
     d = _c.RnntDesc()
-    d.logits, d.ld, d.logits_dtype = logits.data_ptr(), ld, _c.dt_code(logits)
-    d.B, d.T, d.U1, d.V, d.blank = B, T, U1, V, blank
-    for name in ("targets", "logit_lens", "target_lens", "lse", "lp_blank", "lp_label", "alpha", "beta", "shift", "nll", "nll_shifted", "ll_alpha"):
-        setattr(d, name, tens[name].data_ptr() if tens[name].numel() else None)
-    d.sweep = _RNNT_SWEEPS[sweep] if isinstance(sweep, str) else int(sweep)
+    tens = _rnnt_state(d, "rnnt_nll", logits, ld, V, blank, targets, (B, T, U1), B, T + U1)
+    tens.update(logit_lens=logit_lens, target_lens=target_lens)
+    d.B, d.T, d.U1 = B, T, U1
+    d.logit_lens, d.target_lens = logit_lens.data_ptr(), target_lens.data_ptr()
     _c.check(_c.lib().cfm_rnnt_nll(ctypes.byref(d), _c.stream()), "cfm_rnnt_nll")
-    return tens["nll"], RnntState(d, logits, tens)
+    return tens["nll"], RnntState(d, logits, tens, (B, T, U1))
 
 
 def rnnt_grad(state, out, gscale=1.0, gscale_dev=None, clamp=-1.0, cols=None):
-    """d nll_b / d logits (clamped to +-clamp when clamp > 0) times gscale * gscale_dev (a device scalar, or [B] per utterance) into `out`
-    [B,T,U+1,>=cols] (f32 / bf16 / fp16, rows evenly spaced; may be the logits buffer itself, include/cfm.h cfm_rnnt_grad).  Columns
-    0..cols-1 are written (default: out.size(3)); V..cols-1 and every row outside the lattice get exact zeros.  Returns out."""
+    """d nll_b / d logits (clamped to +-clamp when clamp > 0) times gscale * gscale_dev (a device scalar, or [B] per utterance) into `out`, after
+    rnnt_nll ([B,T,U+1,>=cols], rows evenly spaced) or rnnt_nll_packed ([M, >=cols]); f32 / bf16 / fp16 with unit inner stride, and may be the
+    logits buffer itself (include/cfm.h cfm_rnnt_grad / cfm_rnnt_packed_grad).  Columns 0..cols-1 are written (default: all of out's last
+    axis); V..cols-1 and every row outside the lattice get exact zeros.  Returns out."""
     _c.require_hip(out, gscale_dev)
-    d = state.desc
-    if out.dim() != 4 or out.stride(3) != 1 or tuple(out.shape[:3]) != (d.B, d.T, d.U1):
-        raise ValueError("cfm.rnnt_grad: out must be [B,T,U+1,cols] with unit inner stride, got %s" % (tuple(out.shape),))
-    ldg = out.stride(2)
-    if out.stride(1) != d.U1 * ldg or out.stride(0) != d.T * d.U1 * ldg:
-        raise ValueError("cfm.rnnt_grad: out rows must be evenly spaced (strides %s)" % (out.stride(),))
+    d, rows = state.desc, state.rows
+    if out.dim() != len(rows) + 1 or out.stride(-1) != 1 or tuple(out.shape[:-1]) != rows:
+        raise ValueError("cfm.rnnt_grad: out must be [%s, cols] with unit inner stride, got %s" % (",".join(map(str, rows)), tuple(out.shape)))
+    if state.packed:
+        if not d.lat.M:
+            return out
+        B, ldg = d.lat.B, out.stride(0)
+    else:
+        B, ldg = d.B, out.stride(2)
+        if out.stride(1) != d.U1 * ldg or out.stride(0) != d.T * d.U1 * ldg:
+            raise ValueError("cfm.rnnt_grad: out rows must be evenly spaced (strides %s)" % (out.stride(),))
     d.grad, d.ld_grad, d.grad_dtype = out.data_ptr(), ldg, _c.dt_code(out)
-    d.grad_cols = out.size(3) if cols is None else cols
+    d.grad_cols = out.size(-1) if cols is None else cols
     d.gscale, d.clamp = float(gscale), float(clamp)
     if gscale_dev is not None:
-        if gscale_dev.dtype != torch.float32 or not gscale_dev.is_contiguous() or gscale_dev.numel() not in (1, d.B):
+        if gscale_dev.dtype != torch.float32 or not gscale_dev.is_contiguous() or gscale_dev.numel() not in (1, B):
             raise ValueError("cfm.rnnt_grad: gscale_dev must be a contiguous float32 scalar or [B]")
-        d.gscale_dev, d.gscale_stride = gscale_dev.data_ptr(), 1 if gscale_dev.numel() == d.B and d.B > 1 else 0
+        d.gscale_dev, d.gscale_stride = gscale_dev.data_ptr(), 1 if gscale_dev.numel() == B and B > 1 else 0
     else:
         d.gscale_dev, d.gscale_stride = None, 0
-    _c.check(_c.lib().cfm_rnnt_grad(ctypes.byref(d), _c.stream()), "cfm_rnnt_grad")
+    if state.packed:
+        _c.check(_c.lib().cfm_rnnt_packed_grad(ctypes.byref(d), _c.stream()), "cfm_rnnt_packed_grad")
+    else:
+        _c.check(_c.lib().cfm_rnnt_grad(ctypes.byref(d), _c.stream()), "cfm_rnnt_grad")
     d.grad, d.gscale_dev = None, None
     return out
 
@@ -853,61 +851,24 @@ def joint_act_packed_bwd(enc, pred, dact, lat):
     return de, dp
 
 
-def rnnt_nll_packed(logits, targets, lat, blank, V=None, sweep=None):
+def rnnt_nll_packed(logits, targets, lat, blank, V=None):
     """RNN-T negative log-likelihood per utterance over a packed lattice (cfm.lattice.Lattice): UN-normalised logits [M, >=V] (unit inner stride;
     f32 / bf16 / fp16), targets int32 [B, >= max U] contiguous (include/cfm.h cfm_rnnt_packed_nll).  Returns (nll f32 [B], RnntState) as rnnt_nll;
     the state's lse / lp_blank / lp_label / alpha / beta are [M]."""
     _c.require_hip(logits, targets)
     if logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[0] != lat.M:
         raise ValueError("cfm.rnnt_nll_packed: logits must be [M=%d, V] with unit inner stride, got %s strides %s" % (lat.M, tuple(logits.shape), logits.stride()))
-    W = logits.shape[1]
-    V = W if V is None else V
-    if not 1 < V <= W:
-        raise ValueError("cfm.rnnt_nll_packed: V = %d with %d columns" % (V, W))
     if targets.dtype != torch.int32 or not targets.is_contiguous() or targets.dim() != 2 or targets.shape[0] != lat.B or targets.shape[1] < lat.U1_max - 1:
         raise ValueError("cfm.rnnt_nll_packed: targets must be contiguous int32 [B=%d, >=%d], got %s" % (lat.B, lat.U1_max - 1, tuple(targets.shape)))
-    if sweep is None:
-        sweep = os.environ.get("CFM_RNNT_SWEEP", "auto")
-    dev, B, M = logits.device, lat.B, lat.M
-    f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-    tens = dict(lse=f(M), lp_blank=f(M), lp_label=f(M), alpha=f(M), beta=f(M), shift=f(B, lat.T_max + lat.U1_max), nll=f(B), nll_shifted=f(B),
-                ll_alpha=f(B), targets=targets, lattice=lat)
+    M = lat.M
     d = _c.RnntPackedDesc()
-    d.lat = lat.desc
-    d.logits, d.ld, d.logits_dtype = logits.data_ptr() if M else None, logits.stride(0) if M else V, _c.dt_code(logits)
+    tens = _rnnt_state(d, "rnnt_nll_packed", logits, logits.stride(0), V, blank, targets, (M,), lat.B, lat.T_max + lat.U1_max)
+    tens["lattice"] = lat
     if not M:                                                          # no node: nothing is read, but the row-pass checks want a pointer
-        d.logits = tens["nll"].data_ptr()
-    d.V, d.blank, d.ld_targets = V, blank, targets.shape[1]
-    for name in ("targets", "lse", "lp_blank", "lp_label", "alpha", "beta", "shift", "nll", "nll_shifted", "ll_alpha"):
-        t = tens[name]
-        setattr(d, name, t.data_ptr() if t.numel() else tens["nll"].data_ptr() if name != "targets" else None)
-    d.sweep = _RNNT_SWEEPS[sweep] if isinstance(sweep, str) else int(sweep)
+        d.logits, d.ld = tens["nll"].data_ptr(), d.V
+    d.lat, d.ld_targets = lat.desc, targets.shape[1]
     _c.check(_c.lib().cfm_rnnt_packed_nll(ctypes.byref(d), _c.stream()), "cfm_rnnt_packed_nll")
-    return tens["nll"], RnntState(d, logits, tens)
-
-
-def rnnt_grad_packed(state, out, gscale=1.0, gscale_dev=None, clamp=-1.0, cols=None):
-    """rnnt_grad over a packed lattice: out [M, >=cols] (f32 / bf16 / fp16, unit inner stride; may be the logits buffer itself, include/cfm.h
-    cfm_rnnt_packed_grad).  gscale_dev: a device scalar, or [B] per utterance.  Returns out."""
-    _c.require_hip(out, gscale_dev)
-    d = state.desc
-    M, B = d.lat.M, d.lat.B
-    if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] != M:
-        raise ValueError("cfm.rnnt_grad_packed: out must be [M=%d, cols] with unit inner stride, got %s" % (M, tuple(out.shape)))
-    if not M:
-        return out
-    d.grad, d.ld_grad, d.grad_dtype = out.data_ptr(), out.stride(0), _c.dt_code(out)
-    d.grad_cols = out.size(1) if cols is None else cols
-    d.gscale, d.clamp = float(gscale), float(clamp)
-    if gscale_dev is not None:
-        if gscale_dev.dtype != torch.float32 or not gscale_dev.is_contiguous() or gscale_dev.numel() not in (1, B):
-            raise ValueError("cfm.rnnt_grad_packed: gscale_dev must be a contiguous float32 scalar or [B]")
-        d.gscale_dev, d.gscale_stride = gscale_dev.data_ptr(), 1 if gscale_dev.numel() == B and B > 1 else 0
-    else:
-        d.gscale_dev, d.gscale_stride = None, 0
-    _c.check(_c.lib().cfm_rnnt_packed_grad(ctypes.byref(d), _c.stream()), "cfm_rnnt_packed_grad")
-    d.grad, d.gscale_dev = None, None
-    return out
+    return tens["nll"], RnntState(d, logits, tens, (M,))
 
 
 def adam_step(p, g, m, v, lr, betas, eps, weight_decay, step, grad_scale=None):

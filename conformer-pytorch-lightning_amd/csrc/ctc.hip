@@ -16,6 +16,8 @@
 // The first version did both in one workgroup per utterance with a dependent global gather in every step: 1.16 ms at B = 32,
 // T' = 249, V = 5002 (32 of 256 CUs busy, ~1 us of memory latency per frame).  fp32 throughout, as the reference computes the loss
 // on probs.to(float32).
+// Training (cfm_ctc_nll_train_groups) keeps alpha and runs the beta recursion beside it, in the same launch; cfm_ctc_grad forms the state
+// posteriors from the two.
 #include "cfm_common.h"
 
 namespace {
@@ -182,13 +184,10 @@ __device__ __forceinline__ void ctc_alpha_body(const int b, const float* __restr
 }
 
 
-// beta recursion, one workgroup per utterance, walking the frames backwards; ab[t][s] = log(alpha_t(s) beta_t(s) / y_t(z_s)) replaces
-// alpha in place (both recursions include the emission at t, as torch's CTC does, hence the division)
-// SEP: the recursion does not read alpha; it writes bml[t][s] = log(beta_t(s) / y_t(z_s)) to its own array, so that it can run BESIDE the alpha
-// recursion (one launch of 2 B workgroups, cfm_ctc_nll_train with a beta buffer) and the gradient kernel forms alpha + bml -- the same f32
-// sum the in-place form stores.
-template <bool SEP>
-__device__ __forceinline__ void ctc_beta_body(const int b, const float* __restrict__ work, float* __restrict__ ab, int T, int V, const int* __restrict__ enc_lens,
+// beta recursion, one workgroup per utterance, walking the frames backwards.  It does not read alpha: it writes bml[t][s] = log(beta_t(s) / y_t(z_s))
+// to its own array (both recursions include the emission at t, as torch's CTC does, hence the division), so that it runs BESIDE the alpha
+// recursion (one launch, cfm_ctc_nll_train_groups) and the gradient kernel forms alpha + bml.
+__device__ __forceinline__ void ctc_beta_body(const int b, const float* __restrict__ work, float* __restrict__ bml, int T, int V, const int* __restrict__ enc_lens,
                                               const int* __restrict__ labels, int Umax, const int* __restrict__ label_lens) {
     __shared__ float beta[2][CTC_MAXS + 2];
     const int tid = threadIdx.x;
@@ -197,7 +196,7 @@ __device__ __forceinline__ void ctc_beta_body(const int b, const float* __restri
     const int S = 2 * U + 1, SM = 2 * Umax + 2;
     if (len == 0) return;
     const float* lp = work + (int64_t)b * T * SM;
-    float* abp = ab + (int64_t)b * T * SM;
+    float* bp = bml + (int64_t)b * T * SM;
     bool skip[2], live[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -222,24 +221,20 @@ __device__ __forceinline__ void ctc_beta_body(const int b, const float* __restri
                 const float l = lp[(int64_t)t * SM + s];
                 const float bt = (s >= S - 2) ? l : -INFINITY;
                 beta[0][s] = bt;
-                if constexpr (SEP) abp[(int64_t)t * SM + s] = bt - l;
-                else abp[(int64_t)t * SM + s] = abp[(int64_t)t * SM + s] + (bt - l);      // grouped as the SEP form's sum
+                bp[(int64_t)t * SM + s] = bt - l;
             }
         }
         __syncthreads();
     }
-    // the frame's log-probabilities and alpha values are requested AHEAD frames before they are used (as the alpha recursion does): read in
-    // the step that needs them, every step waited out two L2 round trips (180 us per launch at config 3 against 114 us for alpha)
+    // the frame's log-probabilities are requested AHEAD frames before they are used (as the alpha recursion does)
     constexpr int AHEAD = 4;
-    float nl[AHEAD][2], na[AHEAD][2];
+    float nl[AHEAD][2];
 #pragma unroll
     for (int k = 0; k < AHEAD; ++k)
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int t = len - 2 - k, s = tid + i * CTC_NT;
-            const bool ok = live[i] && t >= 0;
-            nl[k][i] = ok ? lp[(int64_t)t * SM + s] : 0.f;
-            na[k][i] = (ok && !SEP) ? abp[(int64_t)t * SM + s] : 0.f;
+            nl[k][i] = (live[i] && t >= 0) ? lp[(int64_t)t * SM + s] : 0.f;
         }
     for (int t0 = len - 2; t0 >= 0; t0 -= AHEAD) {
 #pragma unroll
@@ -253,10 +248,9 @@ __device__ __forceinline__ void ctc_beta_body(const int b, const float* __restri
                         float a = logaddexp_(beta[cur][s], beta[cur][s + 1]);
                         if (skip[i]) a = logaddexp_(a, beta[cur][s + 2]);
                         beta[cur ^ 1][s] = a + nl[k][i];
-                        abp[(int64_t)t * SM + s] = SEP ? a : na[k][i] + a;        // (alpha +) beta - lp
+                        bp[(int64_t)t * SM + s] = a;                 // beta - lp
                         const int tn = t - AHEAD;
                         nl[k][i] = tn >= 0 ? lp[(int64_t)tn * SM + s] : 0.f;
-                        if constexpr (!SEP) na[k][i] = tn >= 0 ? abp[(int64_t)tn * SM + s] : 0.f;
                     }
                 }
                 __syncthreads();
@@ -272,23 +266,9 @@ __global__ __launch_bounds__(CTC_NT) void cfm_ctc_alpha_kernel(const float* __re
     ctc_alpha_body(blockIdx.x, work, T, V, enc_lens, labels, Umax, label_lens, nll, alpha_out, nllp_out);
 }
 
-__global__ __launch_bounds__(CTC_NT) void cfm_ctc_beta_kernel(const float* __restrict__ work, float* __restrict__ ab, int T, int V, const int* __restrict__ enc_lens,
-                                                              const int* __restrict__ labels, int Umax, const int* __restrict__ label_lens) {
-    ctc_beta_body<false>(blockIdx.x, work, ab, T, V, enc_lens, labels, Umax, label_lens);
-}
-
-// both recursions in ONE launch: workgroups [0, B) walk forwards, [B, 2B) backwards (each is a serial chain of T' steps on one CU; a training
-// micro-batch has 5..40 utterances, so the two launches ran one after the other on a nearly empty chip: 113 + 113 us at config 3)
-__global__ __launch_bounds__(CTC_NT) void cfm_ctc_alpha_beta_kernel(const float* __restrict__ work, int B, int T, int V, const int* __restrict__ enc_lens,
-                                                                    const int* __restrict__ labels, int Umax, const int* __restrict__ label_lens,
-                                                                    float* __restrict__ nll, float* __restrict__ alpha_out, float* __restrict__ nllp_out,
-                                                                    float* __restrict__ bml) {
-    if ((int)blockIdx.x < B) ctc_alpha_body(blockIdx.x, work, T, V, enc_lens, labels, Umax, label_lens, nll, alpha_out, nllp_out);
-    else ctc_beta_body<true>((int)blockIdx.x - B, work, bml, T, V, enc_lens, labels, Umax, label_lens);
-}
-
-// the same for the micro-batches of a training window (cfm_ctc_nll_train_groups): each recursion is a serial chain of T' steps on one CU and a
-// micro-batch has 5..40 utterances, so two micro-batches' launches ran one after the other on a nearly empty chip (2 x 113 us at config 3)
+// training (cfm_ctc_nll_train_groups): both recursions of every micro-batch of a window in ONE launch, per micro-batch workgroups [0, B) forwards and
+// [B, 2B) backwards.  Each recursion is a serial chain of T' steps on one CU and a micro-batch has 5..40 utterances: as separate launches they ran
+// one after the other on a nearly empty chip (113 + 113 us at config 3)
 constexpr int CTC_GROUPS_MAX = 8;
 struct CtcGroupArgs {
     const float* work[CTC_GROUPS_MAX];
@@ -312,15 +292,15 @@ __global__ __launch_bounds__(CTC_NT) void cfm_ctc_alpha_beta_group_kernel(const 
         if (i < G.n && wg >= G.first[i]) gi = i;            // uniform
     const int rel = wg - G.first[gi], B = G.B[gi];
     if (rel < B) ctc_alpha_body(rel, G.work[gi], G.T[gi], G.V, G.enc_lens[gi], G.labels[gi], G.Umax[gi], G.label_lens[gi], G.nll[gi], G.alpha[gi], G.nllp[gi]);
-    else ctc_beta_body<true>(rel - B, G.work[gi], G.beta[gi], G.T[gi], G.V, G.enc_lens[gi], G.labels[gi], G.Umax[gi], G.label_lens[gi]);
+    else ctc_beta_body(rel - B, G.work[gi], G.beta[gi], G.T[gi], G.V, G.enc_lens[gi], G.labels[gi], G.Umax[gi], G.label_lens[gi]);
 }
 
 // d nll / d logits, one wavefront per frame, persistent over frames.  Each wavefront keeps an occupancy table over the vocabulary in LDS:
-// the <= 2U+1 state posteriors exp(ab + nll) of a frame are scattered into it (several states share a class: blank, repeated labels),
+// the <= 2U+1 state posteriors exp(alpha + bml + nll) of a frame are scattered into it (several states share a class: blank, repeated labels),
 // the row is written as gs * (softmax - occupancy), and the touched entries are cleared again.
 __global__ __launch_bounds__(CTC_NT) void cfm_ctc_grad_kernel(const float* __restrict__ logits, int64_t ld, int B, int T, int V, const int* __restrict__ enc_lens,
                                                               const int* __restrict__ labels, int Umax, const int* __restrict__ label_lens,
-                                                              const float* __restrict__ ab, const float* __restrict__ bml, const float* __restrict__ lse,
+                                                              const float* __restrict__ alpha, const float* __restrict__ bml, const float* __restrict__ lse,
                                                               const float* __restrict__ nll, float gscale, const float* __restrict__ gscale_dev, float* __restrict__ dlogits) {
     extern __shared__ float occ_all[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -346,7 +326,7 @@ __global__ __launch_bounds__(CTC_NT) void cfm_ctc_grad_kernel(const float* __res
         }
         const int S = 2 * min(max(label_lens[b], 0), Umax) + 1;
         for (int s = lane; s < S; s += 64) {
-            const float abv = bml ? ab[row_id * SM + s] + bml[row_id * SM + s] : ab[row_id * SM + s];      // alpha + (beta - lp): the in-place form's own sum
+            const float abv = alpha[row_id * SM + s] + bml[row_id * SM + s];      // alpha + (beta - lp)
             atomicAdd(&occ[ext_label(labels, (int64_t)b * Umax, s, V)], __expf(abv + nl));
         }
         __threadfence_block();
@@ -371,7 +351,7 @@ __global__ __launch_bounds__(CTC_NT) void cfm_ctc_grad_kernel(const float* __res
 }  // namespace
 
 static int ctc_forward(const float* logits, int64_t ld, int32_t B, int32_t T, int32_t V, const int32_t* enc_lens, const int32_t* labels, int32_t Umax,
-                       const int32_t* label_lens, float* work, float* alpha, float* lse, float* nll, float* nllp, float* beta, cfm_stream_t stream,
+                       const int32_t* label_lens, float* work, float* alpha, float* lse, float* nll, float* nllp, cfm_stream_t stream,
                        bool rows_only = false) {
     CFM_CHECK_ARG(logits && enc_lens && labels && label_lens && work && nll, "cfm_ctc_nll: null pointer");
     CFM_CHECK_ARG(B > 0 && T > 0 && V > 1 && Umax > 0, "cfm_ctc_nll: bad shape B=%d T=%d V=%d Umax=%d", B, T, V, Umax);
@@ -386,11 +366,6 @@ static int ctc_forward(const float* logits, int64_t ld, int32_t B, int32_t T, in
         if (int rc = cfm_launch_status("cfm_ctc_nll (rows)")) return rc;
     }
     if (rows_only) return CFM_OK;
-    if (beta) {
-        CfmProfScope prof("ctc_alpha_beta", s, 0.0, (double)B * T * (2 * Umax + 1) * 16);
-        CFM_LAUNCH(cfm_ctc_alpha_beta_kernel, dim3(2 * B), dim3(CTC_NT), 0, s, (const float*)work, B, T, V, enc_lens, labels, Umax, label_lens, nll, alpha, nllp, beta);
-        return cfm_launch_status("cfm_ctc_nll (alpha | beta)");
-    }
     CfmProfScope prof("ctc_alpha", s, 0.0, (double)B * T * (2 * Umax + 1) * 4);
     CFM_LAUNCH(cfm_ctc_alpha_kernel, dim3(B), dim3(CTC_NT), 0, s, (const float*)work, T, V, enc_lens, labels, Umax, label_lens, nll, alpha, nllp);
     return cfm_launch_status("cfm_ctc_nll (alpha)");
@@ -398,13 +373,7 @@ static int ctc_forward(const float* logits, int64_t ld, int32_t B, int32_t T, in
 
 extern "C" int cfm_ctc_nll(const float* logits, int64_t ld, int32_t B, int32_t T, int32_t V, const int32_t* enc_lens,
                            const int32_t* labels, int32_t Umax, const int32_t* label_lens, float* work, float* nll, cfm_stream_t stream) {
-    return ctc_forward(logits, ld, B, T, V, enc_lens, labels, Umax, label_lens, work, nullptr, nullptr, nll, nullptr, nullptr, stream);
-}
-
-extern "C" int cfm_ctc_nll_train(const float* logits, int64_t ld, int32_t B, int32_t T, int32_t V, const int32_t* enc_lens, const int32_t* labels, int32_t Umax,
-                                 const int32_t* label_lens, float* work, float* alpha, float* lse, float* nll, float* nll_shifted, float* beta, cfm_stream_t stream) {
-    CFM_CHECK_ARG(alpha && lse && nll_shifted, "cfm_ctc_nll_train: null pointer");
-    return ctc_forward(logits, ld, B, T, V, enc_lens, labels, Umax, label_lens, work, alpha, lse, nll, nll_shifted, beta, stream);
+    return ctc_forward(logits, ld, B, T, V, enc_lens, labels, Umax, label_lens, work, nullptr, nullptr, nll, nullptr, stream);
 }
 
 extern "C" int cfm_ctc_nll_train_groups(const cfm_ctc_group* groups, int32_t n, int32_t V, cfm_stream_t stream) {
@@ -416,7 +385,7 @@ extern "C" int cfm_ctc_nll_train_groups(const cfm_ctc_group* groups, int32_t n, 
     for (int i = 0; i < n; ++i) {
         const cfm_ctc_group& g = groups[i];
         CFM_CHECK_ARG(g.alpha && g.lse && g.nll_shifted && g.beta, "cfm_ctc_nll_train_groups: null pointer");
-        if (int rc = ctc_forward(g.logits, g.ld, g.B, g.T, V, g.enc_lens, g.labels, g.Umax, g.label_lens, g.work, g.alpha, g.lse, g.nll, g.nll_shifted, g.beta, stream, true))
+        if (int rc = ctc_forward(g.logits, g.ld, g.B, g.T, V, g.enc_lens, g.labels, g.Umax, g.label_lens, g.work, g.alpha, g.lse, g.nll, g.nll_shifted, stream, true))
             return rc;
         G.work[i] = g.work; G.enc_lens[i] = g.enc_lens; G.labels[i] = g.labels; G.label_lens[i] = g.label_lens; G.nll[i] = g.nll; G.alpha[i] = g.alpha;
         G.nllp[i] = g.nll_shifted; G.beta[i] = g.beta; G.B[i] = g.B; G.T[i] = g.T; G.Umax[i] = g.Umax; G.first[i] = first;
@@ -435,21 +404,16 @@ extern "C" int cfm_ctc_nll_train_groups(const cfm_ctc_group* groups, int32_t n, 
 }
 
 extern "C" int cfm_ctc_grad(const float* logits, int64_t ld, int32_t B, int32_t T, int32_t V, const int32_t* enc_lens, const int32_t* labels, int32_t Umax,
-                            const int32_t* label_lens, const float* work, float* alpha_beta, const float* beta, const float* lse, const float* nll_shifted,
+                            const int32_t* label_lens, const float* work, const float* alpha, const float* beta, const float* lse, const float* nll_shifted,
                             float gscale, const float* gscale_dev, float* dlogits, cfm_stream_t stream) {
     const float* nll = nll_shifted;
-    CFM_CHECK_ARG(logits && enc_lens && labels && label_lens && work && alpha_beta && lse && nll && dlogits, "cfm_ctc_grad: null pointer");
+    CFM_CHECK_ARG(logits && enc_lens && labels && label_lens && work && alpha && beta && lse && nll && dlogits, "cfm_ctc_grad: null pointer");
     CFM_CHECK_ARG(B > 0 && T > 0 && V > 1 && Umax > 0 && 2 * Umax + 1 <= CTC_MAXS, "cfm_ctc_grad: bad shape B=%d T=%d V=%d Umax=%d", B, T, V, Umax);
     CFM_CHECK_ARG(ld >= V && ld % 4 == 0, "cfm_ctc_grad: row stride %lld must be >= V and a multiple of 4", (long long)ld);
     const int Vp = (V + 3) & ~3;
     const size_t lds = (size_t)(CTC_NT / 64) * Vp * 4;
     CFM_CHECK_ARG(lds <= 128 * 1024, "cfm_ctc_grad: vocabulary of %d classes exceeds the LDS occupancy tables (<= 8192)", V);
     hipStream_t s = (hipStream_t)stream;
-    if (!beta) {                                            // the backward recursion has not run beside the forward one: here, in place over alpha
-        CfmProfScope prof("ctc_beta", s, 0.0, (double)B * T * (2 * Umax + 1) * 12);
-        CFM_LAUNCH(cfm_ctc_beta_kernel, dim3(B), dim3(CTC_NT), 0, s, work, alpha_beta, T, V, enc_lens, labels, Umax, label_lens);
-        if (int rc = cfm_launch_status("cfm_ctc_grad (beta)")) return rc;
-    }
     static bool attr_set = false;                           // > 64 KB of dynamic LDS needs the attribute once per process
     if (!attr_set) {
         if (hipFuncSetAttribute((const void*)cfm_ctc_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess)
@@ -460,7 +424,7 @@ extern "C" int cfm_ctc_grad(const float* logits, int64_t ld, int32_t B, int32_t 
     int64_t nb = (rows + CTC_NT / 64 - 1) / (CTC_NT / 64);
     nb = nb > 512 ? 512 : nb;
     CfmProfScope prof("ctc_grad", s, 0.0, (double)rows * ld * 8);
-    CFM_LAUNCH(cfm_ctc_grad_kernel, dim3((unsigned)nb), dim3(CTC_NT), lds, s, logits, ld, B, T, V, enc_lens, labels, Umax, label_lens, (const float*)alpha_beta, beta, lse, nll,
+    CFM_LAUNCH(cfm_ctc_grad_kernel, dim3((unsigned)nb), dim3(CTC_NT), lds, s, logits, ld, B, T, V, enc_lens, labels, Umax, label_lens, alpha, beta, lse, nll,
                gscale, gscale_dev, dlogits);
     return cfm_launch_status("cfm_ctc_grad");
 }

@@ -11,7 +11,7 @@
 //              alpha[t,u] = logaddexp(alpha[t-1,u] + lp_blank[t-1,u], alpha[t,u-1] + lp_label[t,u-1])
 //              beta[t,u]  = logaddexp(beta[t+1,u] + lp_blank[t,u], beta[t,u+1] + lp_label[t,u]),  beta[T_b-1,U_b] = lp_blank[T_b-1,U_b]
 //          A thread's own column is in a register; the neighbour's value of the previous diagonal comes through an LDS double buffer with
-//          one barrier per diagonal (U+1 <= 1024), or, as a switch (sweep = 1, U+1 <= 64), a wavefront shuffle with no barrier at all.  The lattice inputs do not
+//          one barrier per diagonal (U+1 <= 1024).  The lattice inputs do not
 //          depend on alpha / beta and are requested RNNT_AHEAD diagonals before they are used (as ctc.hip does).
 //          Shifted recursion (the CTC precedent): every blank of frame t is offset by o_t = max_u lp_blank[t,u] and every emission of label
 //          u+1 by q_u = max_t lp_label[t,u].  Each path to (t,u) takes exactly one blank per frame < t and one emission per label <= u, so
@@ -33,7 +33,7 @@
 
 namespace {
 
-constexpr int RNNT_NT = 256;                               // LDS sweep: up to 4 columns per thread
+constexpr int RNNT_NT = 256;                               // up to 4 columns per thread
 constexpr int RNNT_MAXU1 = 1024;                           // U + 1
 constexpr int RNNT_MAXT = 8192;                            // o_t lives in LDS
 constexpr int RNNT_AHEAD = 4;
@@ -190,13 +190,12 @@ __global__ __launch_bounds__(256) void cfm_rnnt_rows_kernel(D d) {
     }
 }
 
-// ---- alpha | beta: one workgroup per (utterance, direction) ----
-// SHFL: NT = 64, one column per lane, the neighbour through __shfl_up / __shfl_down; otherwise NT = RNNT_NT, PER columns per thread through LDS.
-template <int NT, int PER, bool SHFL, typename Desc>
+// ---- alpha | beta: one workgroup per (utterance, direction), PER columns per thread, the neighbour column through LDS ----
+template <int NT, int PER, typename Desc>
 __device__ __forceinline__ void rnnt_sweep(const Desc& d, const int b, const bool fwd) {
     __shared__ float sh_o[RNNT_MAXT];
     __shared__ float sh_q[RNNT_MAXU1];
-    __shared__ float pub[SHFL ? 1 : 2][SHFL ? 1 : RNNT_MAXU1 + 2];
+    __shared__ float pub[2][RNNT_MAXU1 + 2];
     __shared__ double red[NT];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const UttGeo g = utt_geo(d, b);
@@ -231,8 +230,7 @@ __device__ __forceinline__ void rnnt_sweep(const Desc& d, const int b, const boo
         const float m = fmaxf(fmaxf(m0, m1), fmaxf(m2, m3));
         sh_q[u] = m > -INFINITY ? m : 0.f;
     }
-    if constexpr (!SHFL)
-        for (int i = tid; i < RNNT_MAXU1 + 2; i += NT) pub[0][i] = pub[1][i] = -INFINITY;
+    for (int i = tid; i < RNNT_MAXU1 + 2; i += NT) pub[0][i] = pub[1][i] = -INFINITY;
     __syncthreads();
     float* shift = g.shift;
     if (fwd) {                                             // the gradient pass reads the shifts from here
@@ -241,7 +239,7 @@ __device__ __forceinline__ void rnnt_sweep(const Desc& d, const int b, const boo
     }
     float* out = (fwd ? d.alpha : d.beta) + base;
     const int D = Tb + Ub;                                 // diagonals 0 .. Tb-1+Ub
-    float self[PER], lbp[PER], pv[PER];
+    float self[PER], lbp[PER];
     float nb[RNNT_AHEAD][PER], nl[RNNT_AHEAD][PER];
     auto fetch = [&](int step, int i, float& vb, float& vl) {
         const int u = tid + i * NT, dd = fwd ? step : D - 1 - step, t = dd - u;
@@ -253,7 +251,6 @@ __device__ __forceinline__ void rnnt_sweep(const Desc& d, const int b, const boo
     for (int i = 0; i < PER; ++i) {
         self[i] = -INFINITY;
         lbp[i] = 0.f;
-        pv[i] = -INFINITY;
 #pragma unroll
         for (int k = 0; k < RNNT_AHEAD; ++k) fetch(k, i, nb[k][i], nl[k][i]);
     }
@@ -266,13 +263,8 @@ __device__ __forceinline__ void rnnt_sweep(const Desc& d, const int b, const boo
 #pragma unroll
                 for (int i = 0; i < PER; ++i) {
                     const int u = tid + i * NT, t = dd - u;
-                    float nbr;                             // the neighbour column's value of the previous diagonal
-                    if constexpr (SHFL) {
-                        nbr = fwd ? __shfl_up(pv[i], 1, 64) : __shfl_down(pv[i], 1, 64);
-                        if (fwd ? lane == 0 : lane == 63) nbr = -INFINITY;
-                    } else {
-                        nbr = fwd ? pub[(step + 1) & 1][u] : pub[(step + 1) & 1][u + 1];
-                    }
+                    // the neighbour column's value of the previous diagonal
+                    const float nbr = fwd ? pub[(step + 1) & 1][u] : pub[(step + 1) & 1][u + 1];
                     float v = -INFINITY;
                     if (u <= Ub && t >= 0 && t < Tb) {
                         if (fwd) {
@@ -289,11 +281,10 @@ __device__ __forceinline__ void rnnt_sweep(const Desc& d, const int b, const boo
                             v = bt;
                         }
                     }
-                    pv[i] = v;
-                    if constexpr (!SHFL) pub[step & 1][fwd ? u + 1 : u] = v;
+                    pub[step & 1][fwd ? u + 1 : u] = v;
                     fetch(step + RNNT_AHEAD, i, nb[k][i], nl[k][i]);
                 }
-                if constexpr (!SHFL) __syncthreads();
+                __syncthreads();
             }
         }
     }
@@ -312,11 +303,11 @@ __device__ __forceinline__ void rnnt_sweep(const Desc& d, const int b, const boo
     }
 }
 
-template <int NT, int PER, bool SHFL, typename D>
+template <int NT, int PER, typename D>
 __global__ __launch_bounds__(NT) void cfm_rnnt_alpha_beta_kernel(D d) {
     const int wg = (int)blockIdx.x, B = n_utt(d);
-    if (wg < B) rnnt_sweep<NT, PER, SHFL>(d, wg, true);
-    else rnnt_sweep<NT, PER, SHFL>(d, wg - B, false);
+    if (wg < B) rnnt_sweep<NT, PER>(d, wg, true);
+    else rnnt_sweep<NT, PER>(d, wg - B, false);
 }
 
 // ---- gradient: one wavefront per row (b, t, u), all rows ----
@@ -450,11 +441,8 @@ int rnnt_nll_launch(const D& d, const char* what, hipStream_t s) {
         if (rc) return rc;
         if (int rc2 = cfm_launch_status(what)) return rc2;
     }
-    const bool shfl = d.sweep == 1;                        // auto = LDS: measured faster at config 4 (RNN-T loss)
     CfmProfScope prof("rnnt_alpha_beta", s, 0.0, (double)rows * 4 * 6);
-    const int B = n_utt(d);
-    if (shfl) CFM_LAUNCH((cfm_rnnt_alpha_beta_kernel<64, 1, true, D>), dim3(2 * B), dim3(64), 0, s, d);
-    else CFM_LAUNCH((cfm_rnnt_alpha_beta_kernel<RNNT_NT, RNNT_MAXU1 / RNNT_NT, false, D>), dim3(2 * B), dim3(RNNT_NT), 0, s, d);
+    CFM_LAUNCH((cfm_rnnt_alpha_beta_kernel<RNNT_NT, RNNT_MAXU1 / RNNT_NT, D>), dim3(2 * n_utt(d)), dim3(RNNT_NT), 0, s, d);
     return cfm_launch_status(what);
 }
 
@@ -481,7 +469,6 @@ int rnnt_grad_launch(const D& d, const char* what, hipStream_t s) {
 extern "C" int cfm_rnnt_nll(const cfm_rnnt_desc* d, cfm_stream_t stream) {
     if (int rc = rnnt_check(d, "cfm_rnnt_nll")) return rc;
     CFM_CHECK_ARG(d->ll_alpha, "cfm_rnnt_nll: null pointer");
-    CFM_CHECK_ARG(d->sweep >= 0 && d->sweep <= 2 && !(d->sweep == 1 && d->U1 > 64), "cfm_rnnt_nll: sweep %d (1: wavefront shuffles, U+1 <= 64; 2: LDS)", d->sweep);
     return rnnt_nll_launch(*d, "cfm_rnnt_nll", (hipStream_t)stream);
 }
 
@@ -493,8 +480,6 @@ extern "C" int cfm_rnnt_grad(const cfm_rnnt_desc* d, cfm_stream_t stream) {
 extern "C" int cfm_rnnt_packed_nll(const cfm_rnnt_packed_desc* d, cfm_stream_t stream) {
     if (int rc = rnnt_packed_check(d, "cfm_rnnt_packed_nll")) return rc;
     CFM_CHECK_ARG(d->ll_alpha, "cfm_rnnt_packed_nll: null pointer");
-    CFM_CHECK_ARG(d->sweep >= 0 && d->sweep <= 2 && !(d->sweep == 1 && d->lat.U1_max > 64),
-                  "cfm_rnnt_packed_nll: sweep %d (1: wavefront shuffles, U+1 <= 64; 2: LDS)", d->sweep);
     return rnnt_nll_launch(*d, "cfm_rnnt_packed_nll", (hipStream_t)stream);
 }
 

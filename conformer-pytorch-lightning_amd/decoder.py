@@ -6,8 +6,8 @@
 Same constructor arguments and parameter names (`ctc_lo.weight`, `ctc_lo.bias`) as the reference.  Quirk Q7 is kept: the reference
 calls F.dropout with its default training=True, i.e. it drops activations even in eval mode; with dropout > 0 this module does the same
 (and is then as random as the reference), parity is defined and tested at dropout = 0.  In train mode `forward` is differentiable
-(cfm/autograd.py CTCLossFn: the beta recursion and d loss / d logits in csrc/ctc.hip, the projection's gradients through cfm_gemm /
-cfm_gemm_tn); `nll` is loss evaluation only.
+(cfm/autograd.py CTCLossFn, the batch as a window of one micro-batch: the alpha and beta recursions and d loss / d logits in csrc/ctc.hip, the
+projection's gradients through cfm_gemm / cfm_gemm_tn); `nll` is loss evaluation only.
 """
 import torch
 import torch.nn as nn
@@ -51,14 +51,15 @@ class CTCDecoder(nn.Module):
 
     def forward(self, encoder_out, encoder_out_lens, padded_labels, label_lengths):
         if self.training:
-            # differentiable path (cfm/autograd.py CTCLossFn): projection, alpha AND beta recursions, gradients for ctc_lo and the encoder
+            # differentiable path (cfm/autograd.py CTCLossFn): the batch's [B*T', D] rows as a window of one micro-batch
             from cfm import autograd as ag
             cfm.require_hip(encoder_out)
             dev = encoder_out.device
             i32 = lambda t: t.to(device=dev, dtype=torch.int32).contiguous()
             x = nn.functional.dropout(encoder_out, self.dropout)          # training=True by default, as decoder.py:19 (quirk Q7); a torch op
-            return ag.CTCLossFn.apply(x, self, cfm.resolve_precision(self), i32(encoder_out_lens), i32(padded_labels), i32(label_lengths),
-                                      self.ctc_lo.weight, self.ctc_lo.bias)
+            B, T, D = x.shape
+            g = (B, T, i32(encoder_out_lens), i32(padded_labels), i32(label_lengths))
+            return ag.CTCLossFn.apply(x.reshape(B * T, D), self, cfm.resolve_precision(self), [g], self.ctc_lo.weight, self.ctc_lo.bias).reshape(())
         loss = self.nll(encoder_out, encoder_out_lens, padded_labels, label_lengths).sum()
         return loss / padded_labels.size(1)
 
@@ -75,4 +76,4 @@ class CTCDecoder(nn.Module):
         i32 = lambda t: t.to(device=dev, dtype=torch.int32).contiguous()
         x = nn.functional.dropout(rows, self.dropout)                    # training=True by default, as decoder.py:19 (quirk Q7)
         gs = [(int(B), int(T), i32(el), i32(lab), i32(ll)) for B, T, el, lab, ll in groups]
-        return ag.CTCWindowLossFn.apply(x, self, cfm.resolve_precision(self), gs, self.ctc_lo.weight, self.ctc_lo.bias)
+        return ag.CTCLossFn.apply(x, self, cfm.resolve_precision(self), gs, self.ctc_lo.weight, self.ctc_lo.bias)

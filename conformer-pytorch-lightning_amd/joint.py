@@ -14,7 +14,7 @@ them raises.  Training goes through `rnnt_loss(enc_out, pred_out, targets, enc_l
 (torchaudio.functional.rnnt_loss at model.py:107; rnnt.py, csrc/rnnt.hip) as one differentiable step whose logits never leave it, so the
 loss gradient overwrites them in place (cfm/autograd.py JointRNNTLossFn).  `rnnt_loss(..., packed=True)` builds the logits for the valid cells
 (b, t < enc_lens[b], u <= target_lens[b]) only (a packed lattice, cfm/lattice.py), and `forward_window(rows, groups)` runs the loss of every
-micro-batch of an accumulation window through one packed lattice over the window's encoder row matrix (cfm/autograd.py JointRNNTPackedLossFn).
+micro-batch of an accumulation window through one packed lattice over the window's encoder row matrix (the same Function).
 """
 import numpy as np
 import torch
@@ -117,16 +117,15 @@ class TransducerJoint(nn.Module):
         b = self._blank(blank, "rnnt_loss")
         dev = enc_out.device
         i32 = lambda t: t.to(device=dev, dtype=torch.int32).contiguous()
-        params = self._params()
+        T = enc_out.size(1)
         if packed:
             from cfm import lattice
-            T = enc_out.size(1)
             Tb, Ub = lattice.host_lengths(enc_lens, target_lens)
             lat = lattice.Lattice.padded(Tb.clip(0, T), Ub.clip(0, U1 - 1), T, U1, dev)
-            return ag.JointRNNTPackedLossFn.apply(enc_out.reshape(B * T, enc_out.size(2)), pred_out.reshape(B * U1, pred_out.size(2)), self,
-                                                  cfm.resolve_precision(self), lat, i32(targets), b, float(clamp), reduction, *params)
-        return ag.JointRNNTLossFn.apply(enc_out, pred_out, self, cfm.resolve_precision(self), i32(targets), i32(enc_lens), i32(target_lens), b,
-                                        float(clamp), reduction, *params)
+        else:
+            lat = (B, T, U1, i32(enc_lens), i32(target_lens))
+        return ag.JointRNNTLossFn.apply(enc_out.reshape(B * T, enc_out.size(2)), pred_out.reshape(B * U1, pred_out.size(2)), self,
+                                        cfm.resolve_precision(self), lat, i32(targets), b, float(clamp), reduction, *self._params())
 
     def forward_window(self, rows, groups, blank=0, clamp=-1):
         """The RNN-T losses of an accumulation window through ONE packed lattice (train path; mirrors CTCDecoder.forward_window).  rows f32
@@ -160,8 +159,8 @@ class TransducerJoint(nn.Module):
             raise ValueError("TransducerJoint.forward_window: rows has %d rows, the groups describe %d" % (rows.size(0), r))
         cat = lambda xs: xs[0] if len(xs) == 1 else torch.cat(xs, 0)
         lat = lattice.Lattice(np.concatenate(Ts), np.concatenate(Us), np.concatenate(e0), np.concatenate(p0), r, q, dev)
-        nll = ag.JointRNNTPackedLossFn.apply(rows, cat(preds), self, cfm.resolve_precision(self), lat, cat(tgts).contiguous(), b, float(clamp),
-                                             "none", *self._params())
+        nll = ag.JointRNNTLossFn.apply(rows, cat(preds), self, cfm.resolve_precision(self), lat, cat(tgts).contiguous(), b, float(clamp), "none",
+                                       *self._params())
         losses, s = [], 0
         for B, *_ in gs:
             losses.append(nll[s:s + B].mean())

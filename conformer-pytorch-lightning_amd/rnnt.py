@@ -48,7 +48,7 @@ def rnnt_loss(logits, targets, logit_lengths, target_lengths, blank=-1, clamp=-1
         x = x.contiguous()
     from cfm import autograd as ag
     dev = logits.device
-    return ag.RNNTLossFn.apply(x, _i32(targets, dev), _i32(logit_lengths, dev), _i32(target_lengths, dev), b, float(clamp), reduction)
+    return ag.RNNTLossFn.apply(x, _i32(targets, dev), (_i32(logit_lengths, dev), _i32(target_lengths, dev)), b, float(clamp), reduction)
 
 
 def rnnt_loss_packed(logits, targets, logit_lengths, target_lengths, blank=-1, clamp=-1, reduction="mean"):
@@ -77,4 +77,4 @@ def rnnt_loss_packed(logits, targets, logit_lengths, target_lengths, blank=-1, c
         raise ValueError("rnnt_loss_packed: logits have %d rows, the lengths describe %d nodes" % (M, lat.M))
     x = logits if logits.stride(1) == 1 else logits.contiguous()
     from cfm import autograd as ag
-    return ag.RNNTPackedLossFn.apply(x, _i32(targets, logits.device), lat, b, float(clamp), reduction)
+    return ag.RNNTLossFn.apply(x, _i32(targets, logits.device), lat, b, float(clamp), reduction)

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CFM_VERSION 303 /* 0.3.3: removed cfm_encoder_layer_train_forward / _backward (the stack entry points run a single block), cfm_ffn_train_forward / _supported, cfm_ffn_train_desc, cfm_pack_ffn_fragments, cfm_layer_train_weights.*_w1f / *_w2f, cfm_layer_train_io.B / T / attn_mask / am_sb / am_sq / side_stream and cfm_encoder_train_backward's n_scratch. 0.3.2 (additive, same number): packed RNN-T lattices (cfm_lattice, cfm_rnnt_packed_desc, cfm_rnnt_packed_nll / _grad, cfm_joint_act_packed / _bwd). 0.3.2 (additive, same number): the RNN-T loss (cfm_rnnt_desc, cfm_rnnt_nll, cfm_rnnt_grad) and the transducer joint's activation backward (cfm_joint_act_bwd). 0.3.2: cfm_rowchain_desc.cin_* (the conv-in chain as the input stage of the next launch). 0.3.1: row chains at D = 512, cfm_rowchain_desc.psum_out / psum_in (feed-forward split over workgroup pairs), cfm_conv12_relu at C = 512. 0.3.0: row groups in the train entry points (cfm_train_group, cfm_layer_train_io.n_groups), cfm_gemm_tn_group + deferred weight gradients, cfm_encoder_train_forward / _backward (the whole stack from one host call). 0.2.3: cfm_ffn_split, cfm_layer_scratch.psum (the feed-forward split over FF for few rows). 0.2.2: cfm_ctc_nll_train / cfm_ctc_grad take a beta buffer (both recursions in one launch); GEMM tile ids 9-11 (K groups). 0.2.1: fused front-end (cfm_conv12_relu); attention stage of the conv-in chain (cfm_rowchain_desc.att_*, cfm_layer_scratch.vt). 0.2.0: training entry points */
+#define CFM_VERSION 304 /* 0.3.4: removed cfm_ctc_nll_train (cfm_ctc_nll_train_groups is the training forward), cfm_ctc_grad requires beta (alpha is no longer overwritten), removed cfm_rnnt_desc.sweep / cfm_rnnt_packed_desc.sweep (the LDS recursion is the only one). 0.3.3: removed cfm_encoder_layer_train_forward / _backward (the stack entry points run a single block), cfm_ffn_train_forward / _supported, cfm_ffn_train_desc, cfm_pack_ffn_fragments, cfm_layer_train_weights.*_w1f / *_w2f, cfm_layer_train_io.B / T / attn_mask / am_sb / am_sq / side_stream and cfm_encoder_train_backward's n_scratch. 0.3.2 (additive, same number): packed RNN-T lattices (cfm_lattice, cfm_rnnt_packed_desc, cfm_rnnt_packed_nll / _grad, cfm_joint_act_packed / _bwd). 0.3.2 (additive, same number): the RNN-T loss (cfm_rnnt_desc, cfm_rnnt_nll, cfm_rnnt_grad) and the transducer joint's activation backward (cfm_joint_act_bwd). 0.3.2: cfm_rowchain_desc.cin_* (the conv-in chain as the input stage of the next launch). 0.3.1: row chains at D = 512, cfm_rowchain_desc.psum_out / psum_in (feed-forward split over workgroup pairs), cfm_conv12_relu at C = 512. 0.3.0: row groups in the train entry points (cfm_train_group, cfm_layer_train_io.n_groups), cfm_gemm_tn_group + deferred weight gradients, cfm_encoder_train_forward / _backward (the whole stack from one host call). 0.2.3: cfm_ffn_split, cfm_layer_scratch.psum (the feed-forward split over FF for few rows). 0.2.2: cfm_ctc_nll_train / cfm_ctc_grad take a beta buffer (both recursions in one launch); GEMM tile ids 9-11 (K groups). 0.2.1: fused front-end (cfm_conv12_relu); attention stage of the conv-in chain (cfm_rowchain_desc.att_*, cfm_layer_scratch.vt). 0.2.0: training entry points */
 
 typedef void* cfm_stream_t;
 
@@ -550,8 +550,8 @@ int cfm_joint_act(const float* enc, int64_t ld_e, const float* pred, int64_t ld_
  *  lse, lp_blank, lp_label, alpha, beta   f32 [B, T, U1] work arrays (only t < T_b, u <= U_b are written); shift f32 [B, T + U1]
  *  nll          f32 [B]: -log P(y | x) per utterance (+inf when T_b = 0); nll_shifted / ll_alpha f32 [B]: -beta'[0,0] and alpha'[T_b-1,U_b] +
  *               lp_blank' of the shifted recursions (csrc/rnnt.hip) -- equal up to f32 rounding
- * cfm_rnnt_nll  the row pass (log-sum-exp, blank and label log-probabilities per node) and both recursions (2 B workgroups); fills the arrays above.
- *               sweep: 0 = auto (LDS), 1 = wavefront shuffles (U1 <= 64), 2 = LDS and one barrier per diagonal.  U1 <= 1024, T <= 8192.
+ * cfm_rnnt_nll  the row pass (log-sum-exp, blank and label log-probabilities per node) and both recursions (2 B workgroups, one barrier per
+ *               diagonal); fills the arrays above.  U1 <= 1024, T <= 8192.
  * cfm_rnnt_grad after cfm_rnnt_nll with the same desc: grad [B, T, U1, ld_grad] (grad_dtype) columns 0..grad_cols-1 (V <= grad_cols <= ld_grad) =
  *               s_b * clamp(d nll_b / d logits, +-clamp) (clamp <= 0: none), s_b = gscale * (gscale_dev ? gscale_dev[b * gscale_stride] : 1) (a
  *               DEVICE scale: no host synchronisation); exact zeros outside t < T_b, u <= U_b and in columns V..grad_cols-1.  grad may be the
@@ -567,7 +567,6 @@ typedef struct {
     const int32_t* target_lens;
     float *lse, *lp_blank, *lp_label, *alpha, *beta, *shift;
     float *nll, *nll_shifted, *ll_alpha;
-    int32_t sweep;
     /* cfm_rnnt_grad only: */
     void* grad;
     int64_t ld_grad;
@@ -633,7 +632,6 @@ typedef struct {
     const int32_t* targets;
     float *lse, *lp_blank, *lp_label, *alpha, *beta, *shift;
     float *nll, *nll_shifted, *ll_alpha;
-    int32_t sweep;
     /* cfm_rnnt_packed_grad only: */
     void* grad;
     int64_t ld_grad;
@@ -816,19 +814,15 @@ typedef struct {
 int cfm_ffn_split(const cfm_ffn_split_desc* d, cfm_stream_t stream);
 int cfm_ffn_split_supported(int32_t D, int32_t FF);
 
-/* CTC backward (csrc/ctc.hip): cfm_ctc_nll_train is cfm_ctc_nll that also keeps log alpha (alpha f32 [B,T,2*Umax+2]), the per-frame
- * log-sum-exp (lse f32 [B,T]) and nll_shifted f32 [B] (-log P of the per-frame-shifted recursion: the posteriors' normaliser); cfm_ctc_grad runs the beta recursion and writes d loss / d logits [B,T,ld] = gscale[b] * (softmax - occupancy)
+/* CTC backward (csrc/ctc.hip).  cfm_ctc_nll_train_groups is cfm_ctc_nll for the micro-batches of a training window that also keeps, per micro-batch,
+ * log alpha (alpha f32 [B,T,2*Umax+2]), log(beta / y) (beta, same shape), the per-frame log-sum-exp (lse f32 [B,T]) and nll_shifted f32 [B] (-log P
+ * of the per-frame-shifted recursion: the posteriors' normaliser): the per-frame row passes per micro-batch, then BOTH recursions of ALL micro-batches
+ * in one launch (each is a serial chain on one CU; 2 * B workgroups per micro-batch).  A single batch is a window of one micro-batch.
+ * cfm_ctc_grad takes one micro-batch's arrays and writes d loss / d logits [B,T,ld] = gscale[b] * (softmax - occupancy)
  * for t < enc_lens[b] and 0 elsewhere (pad columns V..ld-1 too) -- what autograd gives for nn.CTCLoss(reduction='sum') on
  * log_softmax(logits) (decoder.py:20-21).  The scale is gscale * (gscale_dev ? *gscale_dev : 1): a host factor (1 / padded label length,
- * decoder.py:22) times an optional DEVICE scalar (the upstream gradient).  alpha_beta is cfm_ctc_nll_train's alpha, overwritten.
- * beta (f32 [B,T,2*Umax+2], may be null in both calls): given to cfm_ctc_nll_train, the backward recursion runs BESIDE the forward one in the same
- * launch (2 B workgroups) and leaves log(beta / y) there; given to cfm_ctc_grad, that array is used instead of running the recursion (alpha is then
- * left untouched).  Both forms produce the same bits.
+ * decoder.py:22) times an optional DEVICE scalar (the upstream gradient).  alpha and beta are read only.
  * An utterance with no valid alignment (nll = inf) gets a zero gradient (torch's is undefined without zero_infinity).  V <= 8192. */
-int cfm_ctc_nll_train(const float* logits, int64_t ld, int32_t B, int32_t T, int32_t V, const int32_t* enc_lens, const int32_t* labels, int32_t Umax,
-                      const int32_t* label_lens, float* work, float* alpha, float* lse, float* nll, float* nll_shifted, float* beta, cfm_stream_t stream);
-/* cfm_ctc_nll_train for the micro-batches of a training window: the per-frame row passes per micro-batch, then BOTH recursions of ALL micro-batches in
- * one launch (each is a serial chain on one CU; 2 * B workgroups per micro-batch).  Fields as cfm_ctc_nll_train's arguments; beta is required. */
 typedef struct {
     const float* logits;
     int64_t ld;
@@ -838,7 +832,7 @@ typedef struct {
 } cfm_ctc_group;
 int cfm_ctc_nll_train_groups(const cfm_ctc_group* groups, int32_t n, int32_t V, cfm_stream_t stream);
 int cfm_ctc_grad(const float* logits, int64_t ld, int32_t B, int32_t T, int32_t V, const int32_t* enc_lens, const int32_t* labels, int32_t Umax,
-                 const int32_t* label_lens, const float* work, float* alpha_beta, const float* beta, const float* lse, const float* nll_shifted,
+                 const int32_t* label_lens, const float* work, const float* alpha, const float* beta, const float* lse, const float* nll_shifted,
                  float gscale, const float* gscale_dev, float* dlogits, cfm_stream_t stream);
 
 /* Dropout as an elementwise pass:  y[m,n] = keep(seed, m*N + n) ? alpha * x[m,n] / (1-p) : 0, rows with row_mask == 0 zeroed.  The backward of

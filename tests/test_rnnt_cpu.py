@@ -108,9 +108,9 @@ def test_header_declares_and_library_exports_the_rnnt_entries(cfm):
 def test_rnnt_desc_ctypes_size_matches_c(cfm, tmp_path):
     src = tmp_path / "sz.c"
     src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "cfm.h"\nint main(){printf("%zu %zu %zu\\n", sizeof(cfm_rnnt_desc), '
-                   'offsetof(cfm_rnnt_desc, sweep), offsetof(cfm_rnnt_desc, clamp)); return 0;}\n')
+                   'offsetof(cfm_rnnt_desc, grad), offsetof(cfm_rnnt_desc, clamp)); return 0;}\n')
     exe = tmp_path / "sz"
     subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    size, off_sweep, off_clamp = map(int, subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split())
+    size, off_grad, off_clamp = map(int, subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split())
     assert size == ctypes.sizeof(cfm.RnntDesc)
-    assert off_sweep == cfm.RnntDesc.sweep.offset and off_clamp == cfm.RnntDesc.clamp.offset
+    assert off_grad == cfm.RnntDesc.grad.offset and off_clamp == cfm.RnntDesc.clamp.offset

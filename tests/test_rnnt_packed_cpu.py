@@ -111,17 +111,17 @@ def test_header_declares_and_library_exports_the_packed_entries(cfm):
     for n in NEW_ENTRIES:
         assert n in names, "include/cfm.h does not declare %s" % n
         assert hasattr(lib, n), "libconformer_gfx950.so does not export %s" % n
-    assert lib.cfm_version() == 303
+    assert lib.cfm_version() == 304
 
 
 def test_packed_structs_ctypes_size_matches_c(cfm, tmp_path):
     src = tmp_path / "sz.c"
     src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "cfm.h"\nint main(){printf("%zu %zu %zu %zu %zu %zu\\n", sizeof(cfm_lattice), '
                    'offsetof(cfm_lattice, blk_off), sizeof(cfm_rnnt_packed_desc), offsetof(cfm_rnnt_packed_desc, logits), '
-                   'offsetof(cfm_rnnt_packed_desc, sweep), offsetof(cfm_rnnt_packed_desc, clamp)); return 0;}\n')
+                   'offsetof(cfm_rnnt_packed_desc, grad), offsetof(cfm_rnnt_packed_desc, clamp)); return 0;}\n')
     exe = tmp_path / "sz"
     subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
     got = list(map(int, subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()))
     want = [ctypes.sizeof(cfm.Lattice), cfm.Lattice.blk_off.offset, ctypes.sizeof(cfm.RnntPackedDesc), cfm.RnntPackedDesc.logits.offset,
-            cfm.RnntPackedDesc.sweep.offset, cfm.RnntPackedDesc.clamp.offset]
+            cfm.RnntPackedDesc.grad.offset, cfm.RnntPackedDesc.clamp.offset]
     assert got == want

@@ -97,16 +97,16 @@ def test_in_place_16bit_over_f32_and_determinism(pkg):
         nll, st = cfm.rnnt_nll_packed(logits, targets, lat, 0)
         return nll, out_of(st)
 
-    nll1, ref = run(lambda st: cfm.rnnt_grad_packed(st, torch.empty_like(logits), gscale_dev=gdev))
-    nll2, ref2 = run(lambda st: cfm.rnnt_grad_packed(st, torch.empty_like(logits), gscale_dev=gdev))
+    nll1, ref = run(lambda st: cfm.rnnt_grad(st, torch.empty_like(logits), gscale_dev=gdev))
+    nll2, ref2 = run(lambda st: cfm.rnnt_grad(st, torch.empty_like(logits), gscale_dev=gdev))
     assert torch.equal(nll1, nll2) and torch.equal(ref, ref2)       # two calls, same bits
     keep = logits.clone()
-    _, inplace = run(lambda st: cfm.rnnt_grad_packed(st, logits, gscale_dev=gdev))
+    _, inplace = run(lambda st: cfm.rnnt_grad(st, logits, gscale_dev=gdev))
     assert inplace.data_ptr() == logits.data_ptr() and torch.equal(inplace, ref)
     logits.copy_(keep)
-    _, sep16 = run(lambda st: cfm.rnnt_grad_packed(st, torch.empty((lat.M, V), dtype=torch.bfloat16, device=DEV), gscale_dev=gdev))
+    _, sep16 = run(lambda st: cfm.rnnt_grad(st, torch.empty((lat.M, V), dtype=torch.bfloat16, device=DEV), gscale_dev=gdev))
     half = logits.view(torch.bfloat16)
-    run(lambda st: cfm.rnnt_grad_packed(st, half, gscale_dev=gdev, cols=V))
+    run(lambda st: cfm.rnnt_grad(st, half, gscale_dev=gdev, cols=V))
     assert torch.equal(half[:, :V], sep16)
     assert relerr(sep16.float(), ref) <= 1e-2
 
