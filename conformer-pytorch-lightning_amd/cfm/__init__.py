@@ -81,9 +81,6 @@ class RowChainDesc(ctypes.Structure):
                 ("tail_w", c_p), ("tail_b", c_p), ("tail_out", c_p), ("M", c_i64), ("D", c_i32), ("FF", c_i32),
                 ("tail_N", c_i32), ("tail_glu", c_i32), ("w_dtype", c_i32), ("alpha", ctypes.c_float), ("eps", ctypes.c_float),
                 ("out2_f32", c_p), ("dw_w", c_p), ("dw_b", c_p), ("dw_scale", c_p), ("dw_shift", c_p), ("dw_T", c_i32), ("dw_K", c_i32),
-                ("tail_vt", c_p), ("vt_T", c_i32), ("vt_ld", c_i32),
-                ("att_qkv", c_p), ("att_vt", c_p), ("att_p", c_p), ("att_bias_u", c_p), ("att_bias_v", c_p), ("att_mask", c_p),
-                ("att_p_sb", c_i64), ("att_m_sb", c_i64), ("att_T", c_i32), ("att_H", c_i32), ("att_vt_ld", c_i32), ("att_scale", ctypes.c_float),
                 ("s2_ln_g", c_p), ("s2_ln_b", c_p), ("s2_w1f", c_p), ("s2_w2n", c_p), ("s2_b1", c_p), ("s2_b2", c_p), ("s2_out_f32", c_p),
                 ("s2_alpha", ctypes.c_float), ("psum_out", c_p), ("psum_in", c_p), ("psum_b2", c_p), ("psum_alpha", ctypes.c_float),
                 ("cin_a", c_p), ("cin_w", c_p), ("cin_b", c_p), ("cin_res", c_p), ("cin_out", c_p), ("cin_ln_g", c_p), ("cin_ln_b", c_p), ("cin_mask", c_p),
@@ -198,7 +195,7 @@ class FfnSplitDesc(ctypes.Structure):
 
 
 class LayerScratch(ctypes.Structure):
-    _fields_ = [(n, c_p) for n in ("xn", "hid", "qkv", "pos", "ctx", "glu", "dw", "vt")] + [("vt_ld", c_i32), ("psum", c_p), ("psum_splits", c_i32)]
+    _fields_ = [(n, c_p) for n in ("xn", "hid", "qkv", "pos", "ctx", "glu", "dw")] + [("psum", c_p), ("psum_splits", c_i32)]
 
 
 class LayerIO(ctypes.Structure):

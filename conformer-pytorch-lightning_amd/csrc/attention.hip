@@ -17,8 +17,6 @@
 // conflict-free); V is staged transposed with a padded row stride (ds_read_b64, conflict-free).
 //
 // SPLIT evaluates every product as hi*hi + lo*hi + hi*lo on bf16 hi/lo planes (f32-accurate mode).
-#include <stdlib.h>
-
 #include "cfm_common.h"
 #include "attn_common.h"
 
@@ -545,10 +543,9 @@ int launch_attn2(const AttnArgs& a, hipStream_t s, const char* name) {
     const bool mfull = a.mask && a.m_sq != 0;
     const bool kvf32 = a.kv_dtype == CFM_F32;
     // 128 queries per workgroup when that still gives every CU a workgroup (config 2 / config 4: 128 (b, h) pairs x 2 tiles = 256): half the workgroups to
-    // dispatch, keys / values staged twice instead of four times per pair -- measured 1.217 -> 1.201 ms per config-2 step (A/B on one box, CFM_ATTN_Q128=0 for the
+    // dispatch, keys / values staged twice instead of four times per pair -- measured 1.217 -> 1.201 ms per config-2 step (A/B on one box against the
     // 64-query form); per query the same arithmetic in the same order: bit-identical
-    static const bool q128 = getenv("CFM_ATTN_Q128") == nullptr || atoi(getenv("CFM_ATTN_Q128")) != 0;
-    if (q128 && !mfull && !kvf32 && pmode != 2 && a.Tq > 64 && ((pairs + 7) / 8) * 8 * ((a.Tq + 127) / 128) >= 192) {
+    if (!mfull && !kvf32 && pmode != 2 && a.Tq > 64 && ((pairs + 7) / 8) * 8 * ((a.Tq + 127) / 128) >= 192) {
         const int nq8 = (a.Tq + 127) / 128;
         const dim3 grid8((unsigned)(((pairs + 7) / 8) * 8 * nq8)), block8(512);
         if (pmode == 0) CFM_LAUNCH((cfm_attn2_q128_kernel<HT, 0>), grid8, block8, 0, s, a);
@@ -631,7 +628,7 @@ static int attn_args(const cfm_attn_desc* d, AttnArgs& a, bool& fast) {
     const bool al8 = (d->q_sb % 8 == 0) && (d->q_st % 8 == 0) && (d->k_sb % 4 == 0) && (d->k_st % 8 == 0) && (d->k_sh % 8 == 0) &&
                      (d->v_sb % 4 == 0) && (d->v_st % 8 == 0) && (d->v_sh % 8 == 0) && (!pos || ((d->p_sb % 8 == 0) && (d->p_st % 8 == 0)));
     fast = !d->split && d->dk == 64 && d->q_dtype == d->mma_dtype && (!pos || d->p_dtype == d->mma_dtype) &&
-           (d->kv_dtype == d->mma_dtype || d->kv_dtype == CFM_F32) && al8 && !getenv("CFM_ATTN_V1") &&
+           (d->kv_dtype == d->mma_dtype || d->kv_dtype == CFM_F32) && al8 &&
            (int64_t)d->Tk * d->k_st < ((int64_t)1 << 31) && (int64_t)d->Tk * d->v_st < ((int64_t)1 << 31) && (int64_t)d->Tk * d->p_st < ((int64_t)1 << 31);
     return CFM_OK;
 }

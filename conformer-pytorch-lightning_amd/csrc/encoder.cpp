@@ -1,6 +1,5 @@
 // encoder.cpp -- composite: one conformer block enqueued from C++ (2 launches when consecutive blocks are chained: attention, then the conv-in chain + depthwise + final chain
-// + the next block's macaron chain in one; 3 launches with the row-local chains of rowchain.hip when the attention rides in the
-// conv-in chain, 4 otherwise, 17 on the general path; no host sync).
+// + the next block's macaron chain in one; 4 with the row-local chains of rowchain.hip otherwise, 17 on the general path; no host sync).
 //
 // Mirrors reference src/encoder_layer.py:49-71:
 //   x = x + 1/2 FFNm(LN(x)); x = x + MHSA(LN(x)); x = x + Conv(LN(x)); x = x + 1/2 FFN(LN(x)); out = LN(x)
@@ -102,16 +101,12 @@ extern "C" int cfm_encoder_layer_forward(const cfm_layer_weights* w, const cfm_l
         if (!io->after_out) return CFM_OK;
         return cfm_layernorm(x_out, io->after_g, io->after_b, io->after_out, CFM_F32, nullptr, nullptr, nullptr, 0, nullptr, eps, M, D, stream);
     };
-    // 3-launch path: the attention runs as the input stage of the conv-in chain (batch path only: no cache / ring, key-validity mask, at most
-    // one positional row per item, T <= 256, 4 heads x 64) on values the macaron chain's tail wrote transposed
-    const bool merged = chains && s->vt && s->vt_ld >= 256 && s->vt_ld % 4 == 0 && D == 256 && H == 4 && !ring && Tc == 0 && !io->new_cache &&
-                        io->T <= 256 && (!has_pos || P == 1) && (!io->attn_mask || io->am_sq == 0) && !io->macaron_done && !io->next_w;
     CFM_CHECK_ARG(!io->macaron_done || chains, "encoder layer: macaron_done needs the chain path");
     // few rows (a streaming step): both feed-forwards split over FF / 256 workgroups per 32-row tile (ffnsplit.hip) instead of inside the row
     // chains, where every tile's workgroup streams all 2 MB of a feed-forward's weights whatever the row count
     bool ring_written = false;                            // the split path's q|k|v launch also filled the K/V ring
     static const int ffsplit_rows = getenv("CFM_FFSPLIT_MAX_ROWS") ? atoi(getenv("CFM_FFSPLIT_MAX_ROWS")) : CFM_FFSPLIT_MAX_ROWS;   // experiments (scripts/bench_small_batch.py)
-    const bool ffsplit = chains && s->psum && M <= ffsplit_rows && cfm_ffn_split_supported(D, FF) && s->psum_splits >= FF / 256 && !merged &&
+    const bool ffsplit = chains && s->psum && M <= ffsplit_rows && cfm_ffn_split_supported(D, FF) && s->psum_splits >= FF / 256 &&
                          !io->macaron_done && !io->next_w && w->pw2_w && io->ktaps == 15;
     auto split_desc = [&](int mode) {
         cfm_ffn_split_desc f = {};
@@ -120,8 +115,7 @@ extern "C" int cfm_encoder_layer_forward(const cfm_layer_weights* w, const cfm_l
     };
     // D = 512 with at most one row tile per CU pair (config 4: 125 tiles): both feed-forwards split over workgroup pairs, one half of FF each
     // (rowchain.hip FSPLIT); the halves meet in the next launch's row load
-    static const int pair_rows = getenv("CFM_PAIR_MAX_ROWS") ? atoi(getenv("CFM_PAIR_MAX_ROWS")) : CFM_PAIR_MAX_ROWS;
-    const bool pair = chains && s->psum && s->psum_splits >= 3 && M <= pair_rows && cfm_rowchain_pair_supported(D, FF) && !io->macaron_done && !io->next_w;
+    const bool pair = chains && s->psum && s->psum_splits >= 3 && M <= CFM_PAIR_MAX_ROWS && cfm_rowchain_pair_supported(D, FF) && !io->macaron_done && !io->next_w;
     if (pair) {
         cfm_rowchain_desc m = {};
         m.x = x_in; m.ln_g = w->ln_ffm_g; m.ln_b = w->ln_ffm_b; m.w1f = w->ffm_w1f; m.w2n = w->ffm_w2n; m.b1 = w->ffm_b1; m.b2 = w->ffm_b2;
@@ -146,7 +140,6 @@ extern "C" int cfm_encoder_layer_forward(const cfm_layer_weights* w, const cfm_l
         CFM_TRY(cfm_ffn_split(&q, stream));
     } else if (chains && !io->macaron_done && !pair) {
         cfm_rowchain_desc m = {};
-        if (merged) { m.tail_vt = s->vt; m.vt_T = io->T; m.vt_ld = s->vt_ld; }
         m.x = x_in; m.ln_g = w->ln_ffm_g; m.ln_b = w->ln_ffm_b; m.w1f = w->ffm_w1f; m.w2n = w->ffm_w2n; m.b1 = w->ffm_b1; m.b2 = w->ffm_b2;
         m.ln2_g = w->ln_mha_g; m.ln2_b = w->ln_mha_b; m.out_f32 = x_out; m.tail_w = w->qkv_wf; m.tail_b = w->qkv_b; m.tail_out = s->qkv;
         m.M = M; m.D = D; m.FF = FF; m.tail_N = 3 * D; m.tail_glu = 0; m.w_dtype = c.w_dt; m.alpha = 0.5f; m.eps = eps;
@@ -175,21 +168,6 @@ extern "C" int cfm_encoder_layer_forward(const cfm_layer_weights* w, const cfm_l
     if (has_pos && !io->pos_proj)
         CFM_TRY(gemm(c, io->pos_embed, CFM_F32, D, w->pos_w, w->pos_w_lo, nullptr, s->pos, adt, D, io->pos_rows, D, D, CFM_ACT_NONE,
                      nullptr, 0.f, nullptr));
-    if (merged) {
-        // attention + conv-in chain in one launch: context -> out-proj + residual -> LN_conv (pad mask) -> pointwise-conv-1 + GLU
-        cfm_rowchain_desc ci = {};
-        ci.att_qkv = s->qkv; ci.att_vt = s->vt; ci.att_vt_ld = s->vt_ld; ci.att_T = io->T; ci.att_H = H; ci.att_scale = 1.0f / sqrtf((float)dk);
-        ci.att_mask = io->attn_mask; ci.att_m_sb = io->am_sb;
-        if (has_pos) {
-            const int64_t pld = io->pos_proj ? io->pos_proj_ld : D;
-            ci.att_p = io->pos_proj ? io->pos_proj : s->pos; ci.att_p_sb = io->pos_shared ? 0 : pld;
-            ci.att_bias_u = w->bias_u; ci.att_bias_v = w->bias_v;
-        }
-        ci.head_w = w->out_wf; ci.head_b = w->out_b; ci.head_res = x_out; ci.ln_g = w->ln_conv_g; ci.ln_b = w->ln_conv_b;
-        ci.ln_mask = io->pad_valid; ci.out_f32 = x_out; ci.tail_w = w->pw1_wf; ci.tail_b = w->pw1_b; ci.tail_out = s->glu;
-        ci.M = M; ci.D = D; ci.FF = FF; ci.tail_N = 2 * D; ci.tail_glu = 1; ci.w_dtype = c.w_dt; ci.alpha = 1.0f; ci.eps = eps;
-        CFM_TRY(cfm_rowchain(&ci, stream));
-    }
     const void* kq = eoff(s->qkv, D, adt);
     const void* vq = eoff(s->qkv, 2 * D, adt);
     const int64_t sb = (int64_t)io->T * 3 * D, stt = 3 * D;
@@ -219,7 +197,7 @@ extern "C" int cfm_encoder_layer_forward(const cfm_layer_weights* w, const cfm_l
     a.B = io->B; a.H = H; a.Tq = io->T; a.Tk = Tk; a.dk = dk;
     a.mma_dtype = c.w_dt; a.split = c.split ? 1 : 0;
     a.scale = 1.0f / sqrtf((float)dk);
-    if (!merged) CFM_TRY(cfm_attention(&a, stream));
+    CFM_TRY(cfm_attention(&a, stream));
     if (chains) {
         // conv-in chain: out-proj + residual -> LN_conv (pad mask) -> pointwise-conv-1 + GLU
         cfm_rowchain_desc ci = {};
@@ -229,12 +207,12 @@ extern "C" int cfm_encoder_layer_forward(const cfm_layer_weights* w, const cfm_l
         if (pair) { ci.tail_pair = 1; ci.out_f32 = s->psum + (int64_t)2 * M * D; }   // the pair's other workgroup still reads x_out: the rows go to the third slab
         // chained blocks at D = 256: the conv-in chain runs as the input stage of the next launch (depthwise + final chain + the next block's macaron chain) on
         // the tile's 32 + 14 halo rows -- no launch of its own (cfm.h cfm_rowchain_desc.cin_*)
-        const bool cin = cin_merge_flag() != 0 && !merged && !pair && !ffsplit && io->next_w && io->next_x_out && D == 256 && FF == 2048 && io->ktaps == 15 && !io->causal_conv &&
+        const bool cin = cin_merge_flag() != 0 && !pair && !ffsplit && io->next_w && io->next_x_out && D == 256 && FF == 2048 && io->ktaps == 15 && !io->causal_conv &&
                          !io->after_out;
-        if (!merged && !cin) CFM_TRY(cfm_rowchain(&ci, stream));
+        if (!cin) CFM_TRY(cfm_rowchain(&ci, stream));
         // the depthwise conv runs inside the final chain's input stage (15 taps); otherwise on its own
         const bool dw_fused = io->ktaps == 15 && !io->causal_conv && cfm_rowchain_dw_supported(D);
-        const bool pair_dw = pair && io->ktaps == 15 && !io->causal_conv && getenv("CFM_PAIR_HEAD_GEMM") == nullptr;   // depthwise stage + pointwise-conv-2, columns over the pairs
+        const bool pair_dw = pair && io->ktaps == 15 && !io->causal_conv;   // depthwise stage + pointwise-conv-2, columns over the pairs
         if (io->causal_conv) {
             CFM_TRY(cfm_dwconv_causal_bn_silu(s->glu, adt, io->conv_cache, w->dw_w, w->dw_b, w->bn_scale, w->bn_shift, s->dw, adt, io->B, io->T, D, io->ktaps, stream));
             if (io->conv_cache) CFM_TRY(cfm_conv_cache_update(s->glu, adt, io->conv_cache, io->B, io->T, D, io->ktaps, stream));
@@ -275,14 +253,12 @@ extern "C" int cfm_encoder_layer_forward(const cfm_layer_weights* w, const cfm_l
                 dh.dw_w = w->dw_w; dh.dw_b = w->dw_b; dh.dw_scale = w->bn_scale; dh.dw_shift = w->bn_shift; dh.dw_T = io->T; dh.dw_K = 15;
                 dh.out_f32 = x_out; dh.tail_pair = 1; dh.M = M; dh.D = D; dh.FF = FF; dh.w_dtype = c.w_dt; dh.alpha = 1.0f; dh.eps = eps;
                 CFM_TRY(cfm_rowchain(&dh, stream));
-                fa.x = x_out;
-            } else if (w->pw2_w && getenv("CFM_PAIR_HEAD_IN_CHAIN") == nullptr) {
-                // the 0.5 MB head would be streamed by BOTH workgroups of every pair (+18 us per launch): it runs as a plain product over all CUs instead
-                CFM_TRY(gemm(c, s->dw, adt, D, w->pw2_w, w->pw2_w_lo, w->pw2_b, x_out, CFM_F32, D, M, D, D, CFM_ACT_NONE, park, 1.0f, io->pad_valid));
-                fa.x = x_out;
             } else {
-                fa.head_a = s->dw; fa.head_w = w->pw2_wf; fa.head_b = w->pw2_b; fa.head_res = park; fa.head_mask = io->pad_valid; fa.out_f32 = x_out;
+                // causal or not 15 taps: the 0.5 MB head would be streamed by BOTH workgroups of every pair in the chain (+18 us per launch), so it
+                // runs as a plain product over all CUs
+                CFM_TRY(gemm(c, s->dw, adt, D, w->pw2_w, w->pw2_w_lo, w->pw2_b, x_out, CFM_F32, D, M, D, D, CFM_ACT_NONE, park, 1.0f, io->pad_valid));
             }
+            fa.x = x_out;
             fa.ln_g = w->ln_ff_g; fa.ln_b = w->ln_ff_b; fa.w1f = w->ff_w1f; fa.w2n = w->ff_w2n; fa.b1 = w->ff_b1; fa.b2 = w->ff_b2;
             fa.psum_out = s->psum; fa.M = M; fa.D = D; fa.FF = FF; fa.w_dtype = c.w_dt; fa.alpha = 0.5f; fa.eps = eps;
             CFM_TRY(cfm_rowchain(&fa, stream));

@@ -61,7 +61,7 @@ __global__ __launch_bounds__(256 * KG, KG == 1 ? 2 : 1) void cfm_gemm_kernel(con
     constexpr int RPB = 16 / CPR;    // LDS rows per 256-byte bank row
     constexpr int A_PLANE = BM * CPR;
     // (Reading the weight operand straight from a fragment-major pack, only A through LDS, was built and measured slower on the front-end --
-    // conv2 250 -> 280 us: 8 more 1 KB global loads per K tile and wavefront at ~64 clk of issue each.  scripts/experiments/README.md.)
+    // conv2 250 -> 280 us: 8 more 1 KB global loads per K tile and wavefront at ~64 clk of issue each.  Removed; see git history.)
     constexpr int W_PLANE = BN * CPR;
     constexpr int NPL = SPLIT ? 2 : 1;
     constexpr int BUF = (A_PLANE + W_PLANE) * NPL;

@@ -61,7 +61,7 @@ class ConformerEncoder(nn.Module):
         # config-2 width; encoder_layer.CHAIN_BLOCKS)
         import encoder_layer as _el
         e0 = self.encoders[0]
-        chain = (_el.CHAIN_BLOCKS and not _el.MERGE_ATTENTION and fuse_after and caches is None and conv is None and self.encoder_dim == 256 and
+        chain = (_el.CHAIN_BLOCKS and fuse_after and caches is None and conv is None and self.encoder_dim == 256 and
                  e0.hidden_dim == 2048 and e0.kernel_size == 15 and not getattr(e0.conv_module, "causal", False) and
                  all(b.chain_ready(prec) for b in self.encoders) and
                  not (streaming and _el.SPLIT_FFN_FEW_ROWS and _el.split_rows(x.size(0) * x.size(1), self.encoder_dim, e0.hidden_dim)))   # few rows: the split feed-forward instead

@@ -5,10 +5,11 @@ Drop-in for the reference's ``src/encoder_layer.py`` (constructor arguments, chi
 ``(out, inputs_attn_mask, new_attn_cache, new_cnn_cache)`` contract of encoder_layer.py:11-71).
 
 The whole block -- LN, 1/2 macaron FFN, LN, MHSA, LN, convolution module, LN, 1/2 FFN, final LN with every residual -- is
-ONE call into libconformer_gfx950 (``cfm_encoder_layer_forward``): 5 kernel launches (row chains; 17 on the general path) enqueued from C++ with no host
-synchronisation, the residual stream in f32, every bias / activation / GLU / mask / residual add fused into a GEMM
-epilogue, and LayerNorm writing the next GEMM's operand dtype directly.  The child modules (feedforward / attention /
-convolution) only own the parameters here; called on their own they run the same kernels op by op.
+ONE call into libconformer_gfx950 (``cfm_encoder_layer_forward``): 4 kernel launches on the row chains (2 per block when the encoder
+chains consecutive blocks; 17 on the general path) enqueued from C++ with no host synchronisation, the residual stream in f32, every
+bias / activation / GLU / mask / residual add fused into a GEMM epilogue, and LayerNorm writing the next GEMM's operand dtype
+directly.  The child modules (feedforward / attention / convolution) only own the parameters here; called on their own they run the
+same kernels op by op.
 """
 import ctypes
 
@@ -38,8 +39,6 @@ def split_rows(M, D, FF):
 
 
 CHAIN_BLOCKS = True        # the final chain of block i also runs the macaron chain of block i+1 (one launch and one residual round trip less)
-MERGE_ATTENTION = False    # attention as the input stage of the conv-in chain (3 launches per block instead of 4): built, parity-tested and
-                           # measured SLOWER at config 2 (27.7 us vs 9.7 + 13.1 us, rowchain.hip) -- opt-in
 
 
 class ConformerEncoderLayer(nn.Module):
@@ -142,9 +141,6 @@ class ConformerEncoderLayer(nn.Module):
         s.ctx = cfm.scratch("ctx", M * D, adt, dev).data_ptr()
         s.glu = cfm.scratch("glu", M * D, adt, dev).data_ptr()
         s.dw = cfm.scratch("dw", M * D, adt, dev).data_ptr()
-        if MERGE_ATTENTION and D == 256 and H == 4 and T <= 256 and adt != torch.float32:
-            # transposed values for the attention stage of the conv-in chain (cfm.h cfm_layer_scratch.vt); key columns past T are read, never written
-            s.vt, s.vt_ld = cfm.scratch("vt", B * D * 256, adt, dev, zero=True).data_ptr(), 256
         if split_ffn and SPLIT_FFN_FEW_ROWS and split_rows(M, D, FF) and adt != torch.float32 and chain_next is None and not macaron_done:
             # partial slabs of the feed-forward split over FF (cfm.h cfm_layer_scratch.psum, csrc/ffnsplit.hip): few rows, e.g. a streaming step
             s.psum, s.psum_splits = cfm.scratch("psum", (FF // 256) * M * D, torch.float32, dev).data_ptr(), FF // 256

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CFM_VERSION 304 /* 0.3.4: removed cfm_ctc_nll_train (cfm_ctc_nll_train_groups is the training forward), cfm_ctc_grad requires beta (alpha is no longer overwritten), removed cfm_rnnt_desc.sweep / cfm_rnnt_packed_desc.sweep (the LDS recursion is the only one). 0.3.3: removed cfm_encoder_layer_train_forward / _backward (the stack entry points run a single block), cfm_ffn_train_forward / _supported, cfm_ffn_train_desc, cfm_pack_ffn_fragments, cfm_layer_train_weights.*_w1f / *_w2f, cfm_layer_train_io.B / T / attn_mask / am_sb / am_sq / side_stream and cfm_encoder_train_backward's n_scratch. 0.3.2 (additive, same number): packed RNN-T lattices (cfm_lattice, cfm_rnnt_packed_desc, cfm_rnnt_packed_nll / _grad, cfm_joint_act_packed / _bwd). 0.3.2 (additive, same number): the RNN-T loss (cfm_rnnt_desc, cfm_rnnt_nll, cfm_rnnt_grad) and the transducer joint's activation backward (cfm_joint_act_bwd). 0.3.2: cfm_rowchain_desc.cin_* (the conv-in chain as the input stage of the next launch). 0.3.1: row chains at D = 512, cfm_rowchain_desc.psum_out / psum_in (feed-forward split over workgroup pairs), cfm_conv12_relu at C = 512. 0.3.0: row groups in the train entry points (cfm_train_group, cfm_layer_train_io.n_groups), cfm_gemm_tn_group + deferred weight gradients, cfm_encoder_train_forward / _backward (the whole stack from one host call). 0.2.3: cfm_ffn_split, cfm_layer_scratch.psum (the feed-forward split over FF for few rows). 0.2.2: cfm_ctc_nll_train / cfm_ctc_grad take a beta buffer (both recursions in one launch); GEMM tile ids 9-11 (K groups). 0.2.1: fused front-end (cfm_conv12_relu); attention stage of the conv-in chain (cfm_rowchain_desc.att_*, cfm_layer_scratch.vt). 0.2.0: training entry points */
+#define CFM_VERSION 305 /* 0.3.5: removed the attention input stage of the conv-in chain (cfm_rowchain_desc.att_*, cfm_layer_scratch.vt and its row stride) and the transposed-value output of the macaron chain's tail that fed it (three cfm_rowchain_desc fields); psum_out chains take no head. 0.3.4: removed cfm_ctc_nll_train (cfm_ctc_nll_train_groups is the training forward), cfm_ctc_grad requires beta (alpha is no longer overwritten), removed cfm_rnnt_desc.sweep / cfm_rnnt_packed_desc.sweep (the LDS recursion is the only one). 0.3.3: removed cfm_encoder_layer_train_forward / _backward (the stack entry points run a single block), cfm_ffn_train_forward / _supported, cfm_ffn_train_desc, cfm_pack_ffn_fragments, cfm_layer_train_weights.*_w1f / *_w2f, cfm_layer_train_io.B / T / attn_mask / am_sb / am_sq / side_stream and cfm_encoder_train_backward's n_scratch. 0.3.2 (additive, same number): packed RNN-T lattices (cfm_lattice, cfm_rnnt_packed_desc, cfm_rnnt_packed_nll / _grad, cfm_joint_act_packed / _bwd). 0.3.2 (additive, same number): the RNN-T loss (cfm_rnnt_desc, cfm_rnnt_nll, cfm_rnnt_grad) and the transducer joint's activation backward (cfm_joint_act_bwd). 0.3.2: cfm_rowchain_desc.cin_* (the conv-in chain as the input stage of the next launch). 0.3.1: row chains at D = 512, cfm_rowchain_desc.psum_out / psum_in (feed-forward split over workgroup pairs), cfm_conv12_relu at C = 512. 0.3.0: row groups in the train entry points (cfm_train_group, cfm_layer_train_io.n_groups), cfm_gemm_tn_group + deferred weight gradients, cfm_encoder_train_forward / _backward (the whole stack from one host call). 0.2.3: cfm_ffn_split, cfm_layer_scratch.psum (the feed-forward split over FF for few rows). 0.2.2: cfm_ctc_nll_train / cfm_ctc_grad take a beta buffer (both recursions in one launch); GEMM tile ids 9-11 (K groups). 0.2.1: fused front-end (cfm_conv12_relu); attention stage of the conv-in chain (cfm_rowchain_desc.att_*, cfm_layer_scratch.vt). 0.2.0: training entry points */
 
 typedef void* cfm_stream_t;
 
@@ -237,23 +237,6 @@ typedef struct {
      * utterance edges -- exactly cfm_dwconv_bn_silu (convolution.py:43-45) without its launch and its round trip. */
     const float *dw_w, *dw_b, *dw_scale, *dw_shift;
     int32_t dw_T, dw_K;
-    /* optional, macaron chain with the fused-QKV tail at D = 256 (4 heads x 64): the value columns [2D, 3D) of row (b, t) are written
-     * transposed per head, tail_vt[((b*H + h)*64 + d) * vt_ld + t] (16 bit), INSTEAD of into tail_out -- the layout the attention stage
-     * below reads as MFMA fragments.  vt_T frames per utterance (M % vt_T == 0), vt_ld >= vt_T elements per row. */
-    void* tail_vt;
-    int32_t vt_T, vt_ld;
-    /* optional attention input stage of the conv-in chain (head_a NULL, att_qkv set): the head input is the self-attention context of the
-     * tile's 32 frames, computed in the same launch (attention.py:81-96 batch path: no cache, key-validity mask, one positional row per
-     * item) -- replaces a cfm_attention launch and the [M, D] context round trip.  Tiles do not cross utterances: B * ceil(T/32)
-     * workgroups.  att_qkv [B*T, 3D] rows q | k | -, att_vt the transposed values above (key columns >= T must hold finite numbers:
-     * zero-fill the buffer once), att_p one projected positional row per item (stride att_p_sb elements, 0 = shared) or NULL for plain
-     * MHSA, att_mask key validity bytes [B, >= T] (stride att_m_sb) or NULL.  D = 256, att_H = 4, att_T <= 256. */
-    const void *att_qkv, *att_vt, *att_p;
-    const float *att_bias_u, *att_bias_v;
-    const uint8_t* att_mask;
-    int64_t att_p_sb, att_m_sb;
-    int32_t att_T, att_H, att_vt_ld;
-    float att_scale;
     /* optional SECOND feed-forward segment on the same rows, kept in registers (final chain of block i + macaron chain of block i+1):
      *     y1 = LN1(y)                       (as above; out_f32 may be NULL then: nothing else reads the block's output)
      *     z  = y1 + s2_alpha * FFN2( LN(y1; s2_ln_g, s2_ln_b) )   -> s2_out_f32
@@ -265,9 +248,8 @@ typedef struct {
     float* s2_out_f32;
     float s2_alpha;
     /* D = 512 (config 4: 3 984 rows are 125 row tiles for 256 CUs): the feed-forward of a chain split over PAIRS of workgroups, one half of FF each.
-     *   psum_out  (with w1f, no tail, no ln1 / ln2): the launch runs [head ->] LN -> this workgroup's half of the feed-forward and leaves the partial
-     *             sums psum_out[half][M][D] (f32, without b2 / alpha / residual); a head chain also writes its rows x to out_f32, which must NOT alias
-     *             head_res then (the pair's other workgroup still reads it).  2 x ceil(M/32) workgroups, halves on different XCDs.
+     *   psum_out  (with w1f, no head, no tail, no ln1 / ln2): the launch runs LN -> this workgroup's half of the feed-forward and leaves the partial
+     *             sums psum_out[half][M][D] (f32, without b2 / alpha / residual).  2 x ceil(M/32) workgroups, halves on different XCDs.
      *   psum_in   (a chain without head and feed-forward): the rows are x + psum_alpha * (psum_in[0] + psum_in[1] + psum_b2) -> out_f32, then LN -> the
      *             tail; without a tail the normalised rows go to out2_f32. */
     float* psum_out;
@@ -456,9 +438,6 @@ typedef struct {
 
 typedef struct {
     void *xn, *hid, *qkv, *pos, *ctx, *glu, *dw; /* activation-dtype scratch: [M,D],[M,FF],[M,3D],[R,D],[M,D],[M,D],[M,D] */
-    void* vt;      /* optional [B, D, vt_ld] activation-dtype, ZERO-FILLED ONCE by the caller: transposed values for the attention stage of the
-                      conv-in chain (cfm_rowchain_desc.att_*); NULL: attention runs as its own launch */
-    int32_t vt_ld; /* elements per row of vt: >= 256, multiple of 4 */
     float* psum;   /* optional f32 [psum_splits, M, D]: partial slabs of the split feed-forward (cfm_ffn_split).  Given with psum_splits >= FF/256,
                       blocks of at most CFM_FFSPLIT_MAX_ROWS rows at D = 256 run their two feed-forwards split over FF/256 workgroups per 32-row
                       tile instead of inside the row chains (few rows: a streaming step); null = never.  At D = 512 (cfm_rowchain_pair_supported) with
