@@ -8,10 +8,11 @@
 //   6     control       k = argmax over the tiles; the reference's branches as selects on the per-stream state (model.py:255-267)
 //
 // The torch-operation form of the same step (greedy.py) is ~45 small launches; the products here are "skinny": B <= 64 streams against weight
-// matrices of 0.26-2.5 M elements, i.e. one read of 7.5 M f32 weights per step, spread over the chip.  Everything stays f32 so that the argmax is
-// the reference's: the products run on the f32 MFMA (v_mfma_f32_16x16x4_f32: exact f32 multiplies, f32 accumulation) -- one wavefront
-// per 16 output columns, the weight rows as the A operand and up to four 16-stream tiles as B operands, both read as 16-byte pieces straight
-// from memory (the contraction index is walked in the order lane group g holds k = 16 q + 4 g + r, the same for both operands).
+// matrices of 0.26-2.5 M elements, i.e. one read of 7.5 M f32 weights per step, spread over the chip.  Everything stays f32, so the argmax is
+// the reference's wherever its two best logits are further apart than f32 rounding (DESIGN.md's margin rule): the products run on the f32
+// MFMA (v_mfma_f32_16x16x4_f32: exact f32 multiplies, f32 accumulation) -- one wavefront per 16 output columns, the weight rows as the A
+// operand and up to four 16-stream tiles as B operands, both read as 16-byte pieces straight from memory (the contraction index is walked
+// in the order lane group g holds k = 16 q + 4 g + r, the same for both operands).
 //   * the LSTM weight rows are packed [unit][gate] so that the lane that owns output rows 4 g .. 4 g + 3 of a tile holds the four gates
 //     (i, f, g, o) of one hidden unit of one stream: the cell update is lane-local;
 //   * streams that are finished, or whose step produced a blank, keep their state: the candidates (h', c') go to side buffers and the

@@ -18,8 +18,9 @@ streams, with the reference's branches turned into selects:
 `steps_per_replay` such steps are captured in ONE HIP graph; the host replays it and looks at a single "all finished" flag per replay -- one
 synchronisation per `steps_per_replay` steps instead of two per step, and B streams share every weight read.  `enc_ffn` is applied to all
 frames once (model.py:250 does it per step).  Everything runs in float32 torch operations on the reference's own parameters (the joint
-and the predictor are tiny here: one row per stream); the result is the reference's token sequence per stream -- tests compare with the
-oracle's restatement of the loop and with tokens produced by running the reference's predictor / joint modules.
+and the predictor are tiny here: one row per stream); the result is the reference's token sequence per stream wherever the two best logits
+of a decision are further apart than f32 rounding (DESIGN.md's margin rule) -- tests compare with the oracle's restatement of the loop, with
+tokens produced by running the reference's predictor / joint modules, and with a float64 restatement of the step (tests/greedy_ref.py).
 """
 import torch
 import torch.nn.functional as F
@@ -36,7 +37,15 @@ class BatchedGreedySearch:
         self._graph = None
         self._key = None
         self._key_f = None
+        self._key_w = None
         self._fw = None
+
+    def _weights_key(self):
+        """Identity of the current weights, as cfm.packing keys its packs: the packing epoch (bumped by updates that bypass torch's version
+        counters: trainer.py's flat Adam kernel writes through raw pointers), then address, version counter, device and dtype per parameter."""
+        from cfm import packing
+        srcs = list(self.predictor.parameters()) + list(self.joint.parameters())
+        return (packing._EPOCH[0],) + tuple((t.data_ptr(), t._version, str(t.device), t.dtype) for t in srcs)
 
     # -- fused step -----------------------------------------------------------------------------------------------------------------------
     def _fused_ok(self, B, dev):
@@ -46,11 +55,10 @@ class BatchedGreedySearch:
                 jn.pred_ffn.in_features == pr.projection.out_features)
 
     def _fused_weights(self, dev):
-        """f32 packs for cfm_greedy_step, rebuilt when a source parameter changes: [W_ih | W_hh] per layer with rows ordered [unit][gate],
-        b_ih + b_hh likewise, the vocabulary projection padded to a multiple of 16 rows (bias -inf there: never the argmax)."""
+        """f32 packs for cfm_greedy_step, rebuilt when the weights change (_weights_key): [W_ih | W_hh] per layer with rows ordered
+        [unit][gate], b_ih + b_hh likewise, the vocabulary projection padded to a multiple of 16 rows (bias -inf there: never the argmax)."""
         pr, jn = self.predictor, self.joint
-        srcs = list(pr.parameters()) + list(jn.parameters())
-        key = tuple((t.data_ptr(), t._version) for t in srcs)
+        key = (self._weights_key(), str(dev))
         if self._fw is not None and self._fw[0] == key:
             return self._fw[1]
         H = pr.hidden_size
@@ -157,6 +165,9 @@ class BatchedGreedySearch:
         if self._key != key:
             self._S, self._graph, self._key, self._key_f = self._state(B, T, dev), None, key, None
         S = self._S
+        wkey = self._weights_key()
+        if self._key_w != wkey:                                                         # a captured graph holds the parameters' addresses
+            self._graph, self._key_w = None, wkey
         S["enc_proj"].copy_(self.joint.enc_ffn(enc_out.float()))
         S["lens"].copy_(torch.as_tensor(enc_lens, device=dev).to(torch.int64).clamp(0, T))
         for k in ("t", "count", "frame_count", "hyps"):

@@ -7,7 +7,9 @@ every step (the loop around them restated in the generator: model.py does not im
   * greedy.BatchedGreedySearch -- all utterances of a case as ONE batch, control state in tensors, no per-step host decisions -- eagerly
     on the CPU here, and on the GPU with the steps captured in a HIP graph (`-m gpu`), including ragged lengths, the per-frame cap
     (n_steps 1, 3, 4) and a search continued from a carried (token, LSTM state).
-Token sequences are integers: the comparison is exact."""
+Token sequences are integers: the comparison is exact.
+Against float64 (tests/greedy_ref.py; the fused HIP step in tests/test_greedy_step_gpu.py): one step of the torch-operation form on a random
+state, and its search by the margin rule (tokens equal up to the first decision whose two best float64 logits are within 1e-4)."""
 import numpy as np
 import pytest
 import torch
@@ -131,3 +133,75 @@ def test_fused_search_40_streams_matches_torch_form():
         gs = greedy.BatchedGreedySearch(pr, jn, blank=0, n_steps=c["n_steps"], steps_per_replay=16, use_graph=True, fused=fused)
         res.append(gs.search(enc, lens)[0])
     assert res[0] == res[1] and sum(len(h) for h in res[0]) > 50 and res[0][0] == []
+
+
+# name, B, L, (E, H, P, J), V, blank, n_steps -- the torch-operation step (greedy.py _step: the CPU path, and the GPU's beyond 64 streams)
+TORCH_STEP_CASES = [("b1_l1_v16", 1, 1, (16, 16, 16, 16), 16, 0, 1), ("b17_l2_v73", 17, 2, (48, 80, 96, 64), 73, 72, 3),
+                    ("b65_l3_v31", 65, 3, (24, 40, 20, 36), 31, 0, 64), ("b33_l4_v5002", 33, 4, (64, 32, 48, 80), 5002, 5001, 2)]
+
+
+@pytest.mark.parametrize("case", TORCH_STEP_CASES, ids=[c[0] for c in TORCH_STEP_CASES])
+def test_torch_form_step_matches_float64(case):
+    """One `_step` of the torch-operation form on a random state (tests/greedy_ref.py random_state) against the float64 restatement: the
+    new LSTM state of the streams that emitted within 1e-6 (max|d| / max|ref|; measured 1.5e-7), everything else exactly."""
+    import greedy
+    import greedy_ref as R
+    name, B, L, (E, H, P, J), V, blank, n_steps = case
+    pr, jn = R.modules(V, E, H, P, J, L, 400 + B)
+    gs = greedy.BatchedGreedySearch(pr, jn, blank=blank, n_steps=n_steps, use_graph=False, fused=False)
+    S = gs._state(B, 7, torch.device("cpu"))
+    host = R.random_state(S, np.random.RandomState(2000 + B), V, n_steps)
+    with torch.no_grad():
+        gs._step(S)
+    ref = R.step64(R.params64(pr, jn), host["token"], host["h"], host["c"], R.enc_rows(S, host))
+    k, gap, _ = R.argmax_within(ref["logits"], 0.0)
+    assert float(gap.min()) > 1e-4 * float(ref["logits"].abs().max()), "the fixture has a near tie: the f32 argmax may go either way"
+    exp = R.control(host, k.numpy(), ref["h_new"].numpy(), ref["c_new"].numpy(), blank, n_steps)
+    for key in ("token", "t", "frame_count", "count", "hyps", "done"):
+        np.testing.assert_array_equal(S[key].numpy(), exp[key], err_msg=key)
+    nb = (k.numpy() != blank) & ~host["done"]
+    assert 0 < nb.sum() < B or B == 1
+    for key in ("h", "c"):
+        got = S[key].numpy()
+        np.testing.assert_array_equal(got[:, ~nb], host[key][:, ~nb], err_msg=key)
+        new = ref[key + "_new"][:, torch.from_numpy(nb)]
+        if nb.any():
+            err = float(np.abs(got[:, nb] - new.numpy()).max() / float(new.abs().max()))
+            assert err < 1e-6, (name, key, err)
+
+
+def test_float64_search_matches_reference_tokens():
+    """The margin-aware float64 loop (tests/greedy_ref.py search64, the checker of the GPU searches) reproduces the reference-module tokens
+    up to its first close decision; at least one fixture utterance has none."""
+    import greedy_ref as R
+    g, cases = _cases()
+    whole = 0
+    for c in cases:
+        pr, jn = _case_modules(c)
+        P64 = R.params64(pr, jn)
+        for u, n in enumerate(c["lens"]):
+            enc_proj = _enc(c, u)[0].double() @ P64["j.enc_ffn.weight"].t() + P64["j.enc_ffn.bias"]
+            hyps, _, first = R.search64(P64, enc_proj, n, 0, c["n_steps"], 1e-4)
+            ref = g["%s_utt%d" % (c["name"], u)].tolist()
+            assert hyps[:first] == ref[:first], (c["name"], u, first)
+            whole += first is None and hyps == ref
+    assert whole >= 6, whole
+
+
+def test_torch_form_search_on_cpu_matches_float64_loop():
+    """Eight ragged streams through the batched torch-operation form (eager, CPU) against the float64 loop by the margin rule, from a
+    carried (token, LSTM state); final state of the streams without a close decision within 1e-6 (measured 7.5e-8)."""
+    import greedy
+    import greedy_ref as R
+    g, cases = _cases()
+    c = [x for x in cases if x["name"] == "small"][0]
+    pr, jn = _case_modules(c)
+    B, T = 8, c["T"]
+    rs = np.random.RandomState(17)
+    enc = torch.from_numpy(rs.standard_normal((B, T, c["E"])).astype(np.float32))
+    lens = [T, 0, 3, 11, T, 7, 1, 20]
+    tok0 = torch.from_numpy(rs.randint(0, c["V"], B))
+    st0 = tuple(torch.from_numpy(rs.uniform(-0.5, 0.5, (c["layers"], B, c["hidden"])).astype(np.float32)) for _ in range(2))
+    res = greedy.BatchedGreedySearch(pr, jn, blank=0, n_steps=c["n_steps"], use_graph=False, fused=False).search(enc, lens, token=tok0, state=st0)
+    clean, ntok, serr = R.check_search(pr, jn, enc, lens, 0, c["n_steps"], res, 1e-4, tok0, st0)
+    assert clean >= 6 and ntok >= 20 and serr < 1e-6, (clean, ntok, serr)
