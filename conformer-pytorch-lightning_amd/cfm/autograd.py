@@ -352,14 +352,13 @@ def subsampling_params(mod):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-# the blocks from ONE host call each way (csrc/train_layer.cpp cfm_encoder_train_forward / _backward): the same launches as the op-by-op
-# composition above, enqueued from C++.  EncoderStackFn runs all blocks of the encoder over an accumulation WINDOW (round 3): the
-# micro-batches of the window concatenated along the row axis (cfm.h cfm_train_group), each block's weight gradients as ONE grouped launch
-# at the end of its backward, gradients written straight into the data-parallel trainer's flat buffer.  EncoderLayerFn runs one block over
-# one micro-batch through the same entry points (one block, one row group, each weight gradient launched where it is computed).
+# the blocks from ONE host call each way (csrc/train_layer.cpp cfm_encoder_train_forward / _backward): the launches of the sub-block
+# helpers above, enqueued from C++ (tests/train_block_ref.py composes those helpers into a block and is the specification the tests compare
+# against).  EncoderStackFn runs all blocks of the encoder over an accumulation WINDOW (round 3): the micro-batches of the window
+# concatenated along the row axis (cfm.h cfm_train_group), each block's weight gradients as ONE grouped launch at the end of its backward,
+# gradients written straight into the data-parallel trainer's flat buffer.  EncoderLayerFn runs one block over one micro-batch through the
+# same path (one block, one row group, each weight gradient launched where it is computed).
 # ----------------------------------------------------------------------------------------------------------------------
-USE_COMPOSITE = True          # False: EncoderLayerFn runs the op-by-op composition (tests compare the two)
-
 _GRAD_FIELDS = {"norm_ff_macaron.weight": "ln_ffm_g", "norm_ff_macaron.bias": "ln_ffm_b", "norm_mha.weight": "ln_mha_g", "norm_mha.bias": "ln_mha_b",
                 "norm_conv.weight": "ln_conv_g", "norm_conv.bias": "ln_conv_b", "norm_ff.weight": "ln_ff_g", "norm_ff.bias": "ln_ff_b",
                 "norm_final.weight": "ln_final_g", "norm_final.bias": "ln_final_b",
@@ -370,10 +369,15 @@ _GRAD_FIELDS = {"norm_ff_macaron.weight": "ln_ffm_g", "norm_ff_macaron.bias": "l
                 "conv_module.depthwise_conv.bias": "dw_b", "conv_module.norm.weight": "bn_g", "conv_module.norm.bias": "bn_b", "self_attn.pos_bias_u": "pos_bias_u"}
 
 
+# gradients the kernels always write (cfm_dwconv_bn_train_bwd_groups, the pointwise-conv-1 bias column sums) whose parameter a block may lack
+_DISCARDED = ("conv_module.pointwise_conv1.bias", "conv_module.depthwise_conv.bias", "conv_module.norm.weight", "conv_module.norm.bias")
+
+
 def layer_grad_layout(layer, offsets=None):
     """Where each parameter's gradient lives in the block's flat gradient slab: {name: (offset, numel)} in floats (16-byte aligned), the slab
     length, and the device row-offset maps of the two fused products.  offsets: a ready-made {name: offset} (the data-parallel trainer's
-    bucket layout) or None for a private slab in named_parameters order.  Cached on the layer per layout."""
+    bucket layout) or None for a private slab in named_parameters order.  A block without a conv-module bias or BatchNorm affine gets a
+    discard region at the end of its private slab ("discard": its offset) where those gradients go.  Cached on the layer per layout."""
     key = None if offsets is None else tuple(sorted(offsets.items()))
     cache = layer.__dict__.setdefault("_grad_layout", {})
     hit = cache.get(key)
@@ -389,6 +393,9 @@ def layer_grad_layout(layer, offsets=None):
             lay[name] = (offsets[name], p.numel())
             n = max(n, offsets[name] + p.numel())
     D = layer.encoder_dim
+    discard = None
+    if offsets is None and any(name not in lay for name in _DISCARDED):        # (check_params refuses such a block with a flat leaf)
+        discard, n = n, n + 2 * D
     ar = torch.arange(D, dtype=torch.int64)
     qo, ko, vo = (lay["self_attn.linear_%s.weight" % c][0] for c in "qkv")
     qb, kb, vb = (lay["self_attn.linear_%s.bias" % c][0] for c in "qkv")
@@ -396,8 +403,9 @@ def layer_grad_layout(layer, offsets=None):
     qkv_bias = torch.cat([qb + ar, kb + ar, vb + ar])
     idx = packing.glu_interleave_index(D, torch.device("cpu"))            # GEMM row j of the interleaved pack = reference row idx[j]
     pw1_row = lay["conv_module.pointwise_conv1.weight"][0] + idx * D
-    pw1_bias = lay["conv_module.pointwise_conv1.bias"][0] + idx
-    hit = dict(device=dev, layout=lay, numel=n, qkv_row=qkv_row.to(dev), qkv_bias=qkv_bias.to(dev), pw1_row=pw1_row.to(dev), pw1_bias=pw1_bias.to(dev))
+    pw1_bias = lay["conv_module.pointwise_conv1.bias"][0] + idx if "conv_module.pointwise_conv1.bias" in lay else discard + idx
+    hit = dict(device=dev, layout=lay, numel=n, discard=discard, qkv_row=qkv_row.to(dev), qkv_bias=qkv_bias.to(dev), pw1_row=pw1_row.to(dev),
+               pw1_bias=pw1_bias.to(dev))
     if "self_attn.pos_bias_u" in lay:                                    # pos_bias_u as a second destination of linear_q.bias' column sums
         u0 = lay["self_attn.pos_bias_u"][0]
         hit["qkv_bias2"] = torch.cat([u0 + ar, torch.full((2 * D,), -1, dtype=torch.int64)]).to(dev)
@@ -410,7 +418,7 @@ _LN_NAMES = ("norm_ff_macaron", "norm_mha", "norm_conv", "norm_ff", "norm_final"
 
 def _inplace_ptrs(layer):
     """The addresses the weight struct takes from the module itself rather than from the packs: the five LayerNorms' weight and bias and the
-    BatchNorm's running statistics.  The packs do not see them (packing.pack_layer_train keys on the other parameters), and a replaced
+    BatchNorm's running statistics.  The packs do not see them (packing.pack_stack_train keys on the other parameters), and a replaced
     Parameter or buffer (`blk.norm_ff.weight = nn.Parameter(...)`, `bn.running_mean = t`, load_state_dict(assign=True)) keeps every
     pack -- the struct must then be rebuilt.  Reads the modules' dicts directly: ~12 pointers per block, on every train step."""
     m = layer._modules
@@ -424,19 +432,6 @@ def _inplace_ptrs(layer):
         t = b.get(name)
         ptrs.append(0 if t is None else t.data_ptr())
     return tuple(ptrs)
-
-
-def _train_weights_struct(layer, pks):
-    hit = layer.__dict__.get("_train_w_struct")
-    ptrs = _inplace_ptrs(layer)
-    if hit is not None and hit[0] is pks and hit[2] == ptrs:  # the same pack objects (packing.pack_layer_train returns them until a parameter
-        bn = layer.conv_module.norm                           # changes) and the same LayerNorm / running-statistics tensors
-        if bn.momentum is None:                             # cumulative moving average: the factor follows the batch count
-            hit[1].bn_momentum = 1.0 / float(int(bn.num_batches_tracked) + 1)
-        return hit[1]
-    w = _build_train_weights_struct(layer, pks)
-    layer.__dict__["_train_w_struct"] = (pks, w, ptrs)
-    return w
 
 
 def _build_train_weights_struct(layer, pks):
@@ -460,15 +455,6 @@ def _build_train_weights_struct(layer, pks):
     w.bn_momentum = bn.momentum if bn.momentum is not None else 1.0 / float(int(bn.num_batches_tracked) + 1)
     w.bn_eps = bn.eps
     return w
-
-
-def _composite_ok(layer, x, flat=False):
-    """flat: the block's parameters are views of the trainer's flat f32 leaf (trainer.py) -- contiguous float32 by construction, so the walk over
-    the module tree (~0.1 ms of host time per call, and the training step is host-bound) is skipped."""
-    bn = layer.conv_module.norm
-    return (USE_COMPOSITE and layer.kernel_size == 15 and bn.weight is not None and bn.bias is not None and
-            layer.conv_module.pointwise_conv1.bias is not None and layer.conv_module.depthwise_conv.bias is not None and
-            (flat or all(p.dtype == torch.float32 and p.is_contiguous() for p in layer.parameters())))
 
 
 _F32_SAVED = ("x1", "x2", "x3", "x4", "c", "lse", "stats")
@@ -515,6 +501,8 @@ def _stack_grads(owner, layers, bases, lays, tag, u_table):
         for name, field in _GRAD_FIELDS.items():
             if name in lay["layout"]:
                 setattr(g, field, base + 4 * lay["layout"][name][0])
+            elif name in _DISCARDED:                                # the kernels write it all the same: never a null pointer
+                setattr(g, field, base + 4 * lay["discard"])
         g.q_bias = base + 4 * lay["layout"]["self_attn.linear_q.bias"][0]
         g.qkv_row_off, g.qkv_bias_off, g.pw1_row_off, g.pw1_bias_off = (lay[k].data_ptr() for k in ("qkv_row", "qkv_bias", "pw1_row", "pw1_bias"))
         if u_table and "qkv_bias2" in lay:
@@ -644,96 +632,68 @@ def _train_backward(ctx, dy, use_sinks):
     return dx, slabs, lays
 
 
+def check_params(layers, flat):
+    """The weight structs and packs read the blocks' parameters through raw f32 pointers.  flat: views of the trainer's flat f32 leaf (trainer.py) --
+    contiguous float32 by construction, so the walk over the module tree (~0.1 ms of host time per call; the training step is host-bound) is
+    skipped; the leaf's gradient has no room for the gradients of absent parameters (layer_grad_layout's discard region)."""
+    if flat:
+        cvs = [l.conv_module for l in layers]
+        if any(t is None for cv in cvs for t in (cv.pointwise_conv1.bias, cv.depthwise_conv.bias, cv.norm.weight, cv.norm.bias)):
+            raise RuntimeError("a block registered with a flat parameter leaf (trainer.py) needs every conv-module bias and BatchNorm affine parameter")
+        return
+    for i, l in enumerate(layers):
+        for name, p in l.named_parameters():
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise TypeError("train mode needs contiguous float32 parameters: block %d's %s is %s%s" %
+                                (i, name, p.dtype, "" if p.is_contiguous() else ", not contiguous"))
+
+
 class EncoderLayerFn(torch.autograd.Function):
-    """One conformer block in train mode (encoder_layer.py:49-71): four residual sub-blocks + norm_final, one autograd node."""
+    """One conformer block in train mode (encoder_layer.py:49-71): four residual sub-blocks + norm_final, one autograd node -- the stack path
+    over one block and one micro-batch."""
 
     @staticmethod
     def forward(ctx, x, layer, prec, mask8, m_str, keep, *params):
         B, T, D = x.shape
-        rel = layer.use_relative
-        ctx.comp = False
         ctx.flat = len(params) == 1 and params[0] is getattr(layer, "_flat_leaf", None)
-        comp = _composite_ok(layer, x, ctx.flat)
-        if ctx.flat and not comp:
-            raise RuntimeError("a block registered with a flat parameter leaf (trainer.py) needs the composite train path")
-        if comp:
-            # one block, one row group, no deferred weight gradients, no gradient sink: the launches of the op-by-op composition below, in order
-            ctx.comp, ctx.shape = True, x.shape
-            pks = packing.pack_layer_train(layer, prec, rel)
-            w = ctypes.pointer(_train_weights_struct(layer, pks))
-            y = _train_forward(ctx, _f32c(x.reshape(B * T, D)), layer, [layer], prec, [(B, T, mask8, m_str)], keep, ctx.flat, w, pks, False)
-            return y.view(B, T, D)
-        pks = (packing.pack_ffn_train(layer.feed_forward_macaron, prec), packing.pack_mhsa_train(layer.self_attn, prec, rel),
-               packing.pack_conv_module_train(layer.conv_module, prec), packing.pack_ffn_train(layer.feed_forward, prec))
-        ln = lambda m: (m.weight.detach(), m.bias.detach())
-        x0 = _f32c(x.reshape(B * T, D))
-        # dropout (encoder_layer.py:56-69 under module.train()): the shared nn.Dropout(feedforward_dropout) on each of the four branch
-        # outputs, each FFN's own dropout on its hidden activation, the attention's on its probabilities (and, plain MHSA only, on its output)
-        p_br, p_a = layer.dropout.p, layer.self_attn.dropout.p
-        p_hm, p_h = layer.feed_forward_macaron.dropout.p, layer.feed_forward.dropout.p
-        seed = draw_seed() if max(p_br, p_a, p_hm, p_h) > 0 else 0
-        dr = dict(hm=_drop(p_hm, seed, 1), om=_drop(p_br, seed, 2), a=_drop(p_a, seed, 3), oa=_drop(p_br, seed, 4),
-                  oa2=None if rel else _drop(p_a, seed, 5), oc=_drop(p_br, seed, 6), h=_drop(p_h, seed, 7), o=_drop(p_br, seed, 8))
-        x1, s1 = ffn_fwd(pks[0], x0, ln(layer.norm_ff_macaron), prec, 0.5, drop_h=dr["hm"], drop_o=dr["om"])
-        x2, s2 = mhsa_fwd(layer.self_attn, pks[1], x1, ln(layer.norm_mha), B, T, mask8, m_str, prec, rel, dr["a"], dr["oa"], dr["oa2"])
-        x3, s3 = conv_module_fwd(layer.conv_module, pks[2], x2, ln(layer.norm_conv), B, T, keep, prec, drop_o=dr["oc"])
-        x4, s4 = ffn_fwd(pks[3], x3, ln(layer.norm_ff), prec, 0.5, drop_h=dr["h"], drop_o=dr["o"])
-        y = cfm.layernorm(x4, *ln(layer.norm_final))[0]
-        ctx.args = (layer, prec, mask8, m_str, keep, pks, (s1, s2, s3, s4, x4), B, T, D, dr)
+        check_params([layer], ctx.flat)
+        ctx.shape = x.shape
+        w_arr, pks = _stack_weights(layer, [layer], prec, ctx.flat)
+        y = _train_forward(ctx, _f32c(x.reshape(B * T, D)), layer, [layer], prec, [(B, T, mask8, m_str)], keep, ctx.flat, w_arr, pks, False)
         return y.view(B, T, D)
 
     @staticmethod
     def backward(ctx, dy):
-        if ctx.comp:
-            dx, slabs, lays = _train_backward(ctx, dy, False)
-            head = (dx.view(ctx.shape), None, None, None, None, None)
-            if ctx.flat:                                              # one gradient for the block's flat parameter leaf (trainer.py)
-                return head + (slabs[0],)
-            return head + _param_grads(ctx.st[1], slabs, lays)
-        layer, prec, mask8, m_str, keep, pks, (s1, s2, s3, s4, x4), B, T, D, dr = ctx.args
-        rel = layer.use_relative
-        ln = lambda m: (m.weight.detach(), m.bias.detach())
-        grads = {}
-
-        def put(prefix, g, norm_name, lng):
-            for k, v in g.items():
-                grads[prefix + k] = v
-            grads[norm_name + ".weight"], grads[norm_name + ".bias"] = lng
-
-        d, dgf, dbf = cfm.layernorm_bwd(x4, _f32c(dy.reshape(B * T, D)), layer.norm_final.weight.detach())
-        grads["norm_final.weight"], grads["norm_final.bias"] = dgf, dbf
-        d, g, lng = ffn_bwd(pks[3], s4, d, ln(layer.norm_ff), prec, 0.5, drop_h=dr["h"], drop_o=dr["o"])
-        put("feed_forward.", g, "norm_ff", lng)
-        d, g, lng = conv_module_bwd(layer.conv_module, pks[2], s3, d, ln(layer.norm_conv), B, T, keep, prec, drop_o=dr["oc"])
-        put("conv_module.", g, "norm_conv", lng)
-        d, g, lng = mhsa_bwd(layer.self_attn, pks[1], s2, d, ln(layer.norm_mha), B, T, mask8, m_str, prec, rel, dr["a"], dr["oa"], dr["oa2"])
-        put("self_attn.", g, "norm_mha", lng)
-        d, g, lng = ffn_bwd(pks[0], s1, d, ln(layer.norm_ff_macaron), prec, 0.5, drop_h=dr["hm"], drop_o=dr["om"])
-        put("feed_forward_macaron.", g, "norm_ff_macaron", lng)
-        names, tensors = _params(layer)
-        return (d.view(B, T, D), None, None, None, None, None) + tuple(_ordered(names, grads, tensors))
+        dx, slabs, lays = _train_backward(ctx, dy, False)
+        head = (dx.view(ctx.shape), None, None, None, None, None)
+        if ctx.flat:                                              # one gradient for the block's flat parameter leaf (trainer.py)
+            return head + (slabs[0],)
+        return head + _param_grads(ctx.st[1], slabs, lays)
 
 
-def stack_supported(layers, flat):
-    """The stack path needs every block on the composite train path with the same sizes and dropout rates (it shares one io struct)."""
+def stack_supported(layers, n_groups):
+    """Whether the blocks can share one io struct over n_groups micro-batches: the same sizes and dropout rates, and -- with several micro-batches
+    -- no cumulative moving average (BatchNorm momentum=None), whose factor changes from one micro-batch to the next."""
     l0 = layers[0]
-    bn0 = l0.conv_module.norm
     key = lambda l: (l.encoder_dim, l.hidden_dim, l.num_heads, l.kernel_size, l.use_relative, l.dropout.p, l.self_attn.dropout.p,
-                     l.feed_forward_macaron.dropout.p, l.feed_forward.dropout.p)
-    return (USE_COMPOSITE and all(_composite_ok(l, None, flat) and key(l) == key(l0) and l.conv_module.norm.momentum is not None and
-                                  l.conv_module.norm.track_running_stats == bn0.track_running_stats for l in layers))
+                     l.feed_forward_macaron.dropout.p, l.feed_forward.dropout.p, l.conv_module.norm.track_running_stats)
+    return all(key(l) == key(l0) and (n_groups == 1 or l.conv_module.norm.momentum is not None) for l in layers)
 
 
 def _stack_weights(owner, layers, prec, flat):
-    """ctypes array of the blocks' weight structs (cached while the packs stay the same objects)."""
+    """ctypes array of the blocks' weight structs (cached while the packs stay the same objects and _inplace_ptrs the same addresses)."""
     pks = packing.pack_stack_train(owner, layers, prec, layers[0].use_relative, flat)
     hit = owner.__dict__.get("_stack_w")
     ptrs = tuple(_inplace_ptrs(l) for l in layers)
     if hit is not None and len(hit[0]) == len(pks) and all(a is b for a, b in zip(hit[0], pks)) and hit[2] == ptrs:
+        for w, l in zip(hit[1], layers):
+            bn = l.conv_module.norm
+            if bn.momentum is None:                             # cumulative moving average: the factor follows the batch count
+                w.bn_momentum = 1.0 / float(int(bn.num_batches_tracked) + 1)
         return hit[1], pks
     arr = (cfm.LayerTrainWeights * len(layers))()
     for i, (l, pk) in enumerate(zip(layers, pks)):
-        arr[i] = _train_weights_struct(l, pk)
+        arr[i] = _build_train_weights_struct(l, pk)
     owner.__dict__["_stack_w"] = (pks, arr, ptrs)
     return arr, pks
 

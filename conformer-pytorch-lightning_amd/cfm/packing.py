@@ -52,7 +52,7 @@ class PackCache:
 # What the train and inference paths cache on a module's __dict__ besides PackCache objects: packed weights, plans whose launch tables hold the
 # source tensors' addresses, ctypes structs of raw device pointers.  None of it may survive a copy (copy.deepcopy, pickle, torch.save): ctypes
 # pointers cannot be pickled, and a copied pointer would still address the original's memory.
-MODULE_CACHES = ("_fused", "_train_w_struct", "_pack_layer_train", "_pack_layer_srcs", "_grad_layout", "_stack_w", "_stack_g", "_pack_stack_train")
+MODULE_CACHES = ("_fused", "_grad_layout", "_stack_w", "_stack_g", "_pack_stack_train")
 
 
 def state_without_caches(state):
@@ -75,6 +75,15 @@ def matrix(w, prec):
         lo = (w32 - hi.to(torch.float32)).to(torch.bfloat16)
         return hi.contiguous(), lo.contiguous()
     return w32.to(prec.w_dtype).contiguous(), None
+
+
+def conv_module_vectors(mod):
+    """(pointwise-conv-1 bias [2D], depthwise bias [D], BatchNorm weight [D], BatchNorm bias [D]) of a ConvolutionModule, detached: an absent
+    bias reads as zeros, an absent BatchNorm affine as ones / zeros."""
+    D = mod.pointwise_conv2.weight.shape[0]
+    dev = mod.pointwise_conv2.weight.device
+    opt = lambda t, n, fill: t.detach() if t is not None else torch.full((n,), fill, device=dev)
+    return opt(mod.pointwise_conv1.bias, 2 * D, 0.0), opt(mod.depthwise_conv.bias, D, 0.0), opt(mod.norm.weight, D, 1.0), opt(mod.norm.bias, D, 0.0)
 
 
 def glu_interleave_index(D, device):
@@ -165,15 +174,12 @@ def pack_conv_module(mod, prec):
         dev = mod.pointwise_conv2.weight.device
         idx = glu_interleave_index(D, dev)
         w1 = mod.pointwise_conv1.weight.detach()[:, :, 0]
-        b1 = mod.pointwise_conv1.bias.detach() if mod.pointwise_conv1.bias is not None else torch.zeros(2 * D, device=dev)
+        b1, dwb, gamma, beta = conv_module_vectors(mod)
         pw1, pw1l = matrix(w1[idx], prec)
         pw2, pw2l = matrix(mod.pointwise_conv2.weight.detach()[:, :, 0], prec)
-        dwb = mod.depthwise_conv.bias.detach() if mod.depthwise_conv.bias is not None else torch.zeros(D, device=dev)
         # BatchNorm1d (eval): y = (x - mean) / sqrt(var + eps) * gamma + beta   ->   x * scale + shift
-        gamma = bn.weight.detach().float() if bn.weight is not None else torch.ones(D, device=dev)
-        beta = bn.bias.detach().float() if bn.bias is not None else torch.zeros(D, device=dev)
-        scale = gamma / torch.sqrt(bn.running_var.detach().float() + bn.eps)
-        shift = beta - bn.running_mean.detach().float() * scale
+        scale = gamma.float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
+        shift = beta.float() - bn.running_mean.detach().float() * scale
         pk = Packed(pw1_w=pw1, pw1_w_lo=pw1l, pw1_b=f32(b1[idx]), pw2_w=pw2, pw2_w_lo=pw2l, pw2_b=f32(mod.pointwise_conv2.bias),
                     dw_w=f32(mod.depthwise_conv.weight.detach()[:, 0, :]), dw_b=f32(dwb), bn_scale=f32(scale), bn_shift=f32(shift),
                     pw1_wf=None, pw2_wf=None)
@@ -294,39 +300,38 @@ def pack_conv_module_train(mod, prec):
 
     def build():
         D = mod.pointwise_conv2.weight.shape[0]
-        dev = mod.pointwise_conv2.weight.device
-        idx = glu_interleave_index(D, dev)
+        idx = glu_interleave_index(D, mod.pointwise_conv2.weight.device)
         w1 = mod.pointwise_conv1.weight.detach()[:, :, 0][idx]
-        b1 = (mod.pointwise_conv1.bias.detach() if mod.pointwise_conv1.bias is not None else torch.zeros(2 * D, device=dev))[idx]
         w2 = mod.pointwise_conv2.weight.detach()[:, :, 0]
+        b1, _, _, _ = conv_module_vectors(mod)
         pw1, pw1l = matrix(w1, prec)
         pw1t, pw1tl = matrix_t(w1, prec)
         pw2, pw2l = matrix(w2, prec)
         pw2t, pw2tl = matrix_t(w2, prec)
-        dwb = mod.depthwise_conv.bias.detach() if mod.depthwise_conv.bias is not None else torch.zeros(D, device=dev)
-        gamma = bn.weight.detach() if bn.weight is not None else torch.ones(D, device=dev)
-        beta = bn.bias.detach() if bn.bias is not None else torch.zeros(D, device=dev)
-        return Packed(pw1_w=pw1, pw1_w_lo=pw1l, pw1_t=pw1t, pw1_t_lo=pw1tl, pw1_b=f32(b1), pw2_w=pw2, pw2_w_lo=pw2l, pw2_t=pw2t, pw2_t_lo=pw2tl,
-                      pw2_b=f32(mod.pointwise_conv2.bias), dw_w=f32(mod.depthwise_conv.weight.detach()[:, 0, :]), dw_b=f32(dwb), gamma=f32(gamma),
-                      beta=f32(beta), idx=idx)
+        return conv_module_train_pack(mod, idx, b1[idx], (pw1, pw1l, pw1t, pw1tl), (pw2, pw2l, pw2t, pw2tl))
     return _train_cache(mod).get(srcs, prec, build)
 
 
-class _LayerPackPlan:
-    """The 8 weight matrices of one conformer block (two feed-forwards, fused q|k|v, out-projection, the GLU-interleaved pointwise-conv-1,
-    pointwise-conv-2) as ONE cfm_pack_matrices launch per optimizer step: the destination tensors and the job table are built once (the
-    parameters' addresses do not move: the optimizer writes in place), a rebuild is one kernel + the three small bias vectors."""
+def conv_module_train_pack(mod, idx, pw1_b, pw1, pw2):
+    """The training pack of a ConvolutionModule around its two packed matrices (w, w_lo, w^T, w^T_lo) and the interleaved pointwise-conv-1 bias."""
+    _, dwb, gamma, beta = conv_module_vectors(mod)
+    return Packed(pw1_w=pw1[0], pw1_w_lo=pw1[1], pw1_t=pw1[2], pw1_t_lo=pw1[3], pw1_b=f32(pw1_b), pw2_w=pw2[0], pw2_w_lo=pw2[1], pw2_t=pw2[2],
+                  pw2_t_lo=pw2[3], pw2_b=f32(mod.pointwise_conv2.bias), dw_w=f32(mod.depthwise_conv.weight.detach()[:, 0, :]), dw_b=f32(dwb),
+                  gamma=f32(gamma), beta=f32(beta), idx=idx)
 
-    def __init__(self, layer, prec, relative):
+
+class _LayerPackPlan:
+    """The matrix jobs of one conformer block's 8 weight matrices (two feed-forwards, fused q|k|v, out-projection, the GLU-interleaved
+    pointwise-conv-1, pointwise-conv-2) for cfm_pack_matrices, and their destination tensors: built once (the parameters' addresses do not
+    move: the optimizer writes in place).  _StackPackPlan launches the jobs of all blocks together."""
+
+    def __init__(self, layer, prec):
         ffm, att, cv, ff = layer.feed_forward_macaron, layer.self_attn, layer.conv_module, layer.feed_forward
         dev = ffm.w_1.weight.device
         D = cv.pointwise_conv2.weight.shape[0]
         self.idx = glu_interleave_index(D, dev)
-        self.relative = relative
-        self.srcs = [ffm.w_1.weight, ffm.w_2.weight, att.linear_q.weight, att.linear_k.weight, att.linear_v.weight, att.linear_out.weight,
-                     cv.pointwise_conv1.weight, cv.pointwise_conv2.weight, ff.w_1.weight, ff.w_2.weight]
-        self.ptrs = tuple(t.data_ptr() for t in self.srcs)
-        for t in self.srcs:
+        for t in (ffm.w_1.weight, ffm.w_2.weight, att.linear_q.weight, att.linear_k.weight, att.linear_v.weight, att.linear_out.weight,
+                  cv.pointwise_conv1.weight, cv.pointwise_conv2.weight, ff.w_1.weight, ff.w_2.weight):
             if t.dtype != torch.float32 or not t.is_contiguous():
                 raise TypeError("the training packs need contiguous float32 parameters")
         wdt = torch.bfloat16 if prec.split else prec.w_dtype
@@ -357,75 +362,30 @@ class _LayerPackPlan:
             tile0 += ((n + 63) // 64) * ((k + 63) // 64)
         self.tiles = tile0
         self.jobs = torch.tensor(jobs, dtype=torch.int64).to(dev)
-        self.prec = prec
 
-    def valid_for(self, prec):
-        return prec.name == self.prec.name and tuple(t.data_ptr() for t in self.srcs) == self.ptrs
-
-    def run(self, layer, launch=True, vectors=None):
-        """launch=False: the matrices were packed by a launch covering several blocks (_StackPackPlan); vectors = (qkv_b, pw1_b) likewise."""
-        prec = self.prec
-        if launch:
-            _c.check(_c.lib().cfm_pack_matrices(self.jobs.data_ptr(), self.jobs.shape[0], self.tiles, _c.BF16 if prec.split else prec.w_code, 1 if prec.split else 0,
-                                                _c.stream()), "cfm_pack_matrices")
-        ffm, att, cv, ff = layer.feed_forward_macaron, layer.self_attn, layer.conv_module, layer.feed_forward
+    def packs(self, layer, qkv_b, pw1_b):
+        """The block's (macaron FFN, attention, conv module, FFN) packs around the destinations of its matrix jobs; qkv_b / pw1_b: its two gathered
+        bias vectors (_StackPackPlan packs both)."""
         o = self.out
 
         def ffn(mod, pre):
             (w1, w1l, w1t, w1tl), (w2, w2l, w2t, w2tl) = o[pre + "_w1"], o[pre + "_w2"]
             return Packed(w1=w1, w1_lo=w1l, b1=f32(mod.w_1.bias), w2=w2, w2_lo=w2l, b2=f32(mod.w_2.bias), w1t=w1t, w1t_lo=w1tl, w2t=w2t, w2t_lo=w2tl)
-        if vectors is not None:
-            qkv_b = vectors[0]
-        else:
-            bq = att.linear_q.bias.detach().float()
-            if self.relative:
-                bq = bq + att.pos_bias_u.detach().float().reshape(-1)
-            qkv_b = torch.cat([bq, att.linear_k.bias.detach().float(), att.linear_v.bias.detach().float()], 0).contiguous()
         (qkv, qkvl, qkvt, qkvtl), (out, outl, outt, outtl) = o["qkv"], o["out"]
         pa = Packed(qkv_w=qkv, qkv_w_lo=qkvl, qkv_t=qkvt, qkv_t_lo=qkvtl, qkv_b=qkv_b, out_w=out, out_w_lo=outl, out_t=outt, out_t_lo=outtl,
-                    out_b=f32(att.linear_out.bias))
-        D = cv.pointwise_conv2.weight.shape[0]
-        dev = qkv.device
-        bn = cv.norm
-        if vectors is not None:
-            b1 = vectors[1]
-        else:
-            b1 = (cv.pointwise_conv1.bias.detach() if cv.pointwise_conv1.bias is not None else torch.zeros(2 * D, device=dev))[self.idx]
-        dwb = cv.depthwise_conv.bias.detach() if cv.depthwise_conv.bias is not None else torch.zeros(D, device=dev)
-        gamma = bn.weight.detach() if bn.weight is not None else torch.ones(D, device=dev)
-        beta = bn.bias.detach() if bn.bias is not None else torch.zeros(D, device=dev)
-        (pw1, pw1l, pw1t, pw1tl), (pw2, pw2l, pw2t, pw2tl) = o["pw1"], o["pw2"]
-        pc = Packed(pw1_w=pw1, pw1_w_lo=pw1l, pw1_t=pw1t, pw1_t_lo=pw1tl, pw1_b=f32(b1), pw2_w=pw2, pw2_w_lo=pw2l, pw2_t=pw2t, pw2_t_lo=pw2tl,
-                    pw2_b=f32(cv.pointwise_conv2.bias), dw_w=f32(cv.depthwise_conv.weight.detach()[:, 0, :]), dw_b=f32(dwb), gamma=f32(gamma),
-                    beta=f32(beta), idx=self.idx)
-        return ffn(ffm, "ffm"), pa, pc, ffn(ff, "ff")
-
-
-def pack_layer_train(layer, prec, relative):
-    """(macaron FFN, attention, conv module, FFN) training packs of one block, the 8 matrices through one cfm_pack_matrices launch.
-    Same values as pack_ffn_train / pack_mhsa_train / pack_conv_module_train (tests compare them)."""
-    st = layer.__dict__.get("_pack_layer_train")
-    srcs = layer.__dict__.get("_pack_layer_srcs")
-    if srcs is None:                                   # every parameter a pack depends on (LayerNorm parameters are read in place)
-        srcs = [p for n, p in layer.named_parameters() if not n.startswith("norm_")]
-        layer.__dict__["_pack_layer_srcs"] = srcs
-    key = _key(srcs, prec)
-    if st is not None and st[0] == key:
-        return st[2]
-    with torch.no_grad():
-        plan = st[1] if st is not None and st[1].valid_for(prec) else _LayerPackPlan(layer, prec, relative)
-        val = plan.run(layer)
-    layer.__dict__["_pack_layer_train"] = (key, plan, val)
-    return val
+                    out_b=f32(layer.self_attn.linear_out.bias))
+        pc = conv_module_train_pack(layer.conv_module, self.idx, pw1_b, o["pw1"], o["pw2"])
+        return ffn(layer.feed_forward_macaron, "ffm"), pa, pc, ffn(layer.feed_forward, "ff")
 
 
 class _StackPackPlan:
     """The training packs of ALL blocks of an encoder in two launches per optimizer step -- the blocks' matrix jobs in one table
     (cfm_pack_matrices), their two small gathered vectors (fused q|k|v bias + pos_bias_u, interleaved pointwise-conv-1 bias) through
-    element-pointer tables (cfm_pack_vectors) -- instead of one matrix launch and ~4 torch operations per block (12 blocks: 60 launches)."""
+    element-pointer tables (cfm_pack_vectors) -- instead of one matrix launch and ~4 torch operations per block (12 blocks: 60 launches).
+    An absent pointwise-conv-1 bias is gathered from zeros."""
 
     def __init__(self, layers, prec, relative):
-        self.plans = [_LayerPackPlan(l, prec, relative) for l in layers]
+        self.plans = [_LayerPackPlan(l, prec) for l in layers]
         dev = self.plans[0].jobs.device
         tables, off = [], 0
         for pl in self.plans:
@@ -436,21 +396,22 @@ class _StackPackPlan:
         self.jobs, self.tiles = torch.cat(tables, 0).contiguous(), off
         pa, pb, self.vec_slices, n = [], [], [], 0
         el = lambda t: t.data_ptr() + 4 * torch.arange(t.numel(), device=dev, dtype=torch.int64)
+        self.zero_bias = torch.zeros(2 * max(l.encoder_dim for l in layers), device=dev)     # what an absent pointwise-conv-1 bias reads
         for l, pl in zip(layers, self.plans):
             att, cv = l.self_attn, l.conv_module
             D = cv.pointwise_conv2.weight.shape[0]
-            for t in (att.linear_q.bias, att.linear_k.bias, att.linear_v.bias, cv.pointwise_conv1.bias) + ((att.pos_bias_u,) if relative else ()):
+            b1 = cv.pointwise_conv1.bias if cv.pointwise_conv1.bias is not None else self.zero_bias[:2 * D]
+            for t in (att.linear_q.bias, att.linear_k.bias, att.linear_v.bias, b1) + ((att.pos_bias_u,) if relative else ()):
                 if t is None or t.dtype != torch.float32 or not t.is_contiguous():
                     raise TypeError("the stack pack needs contiguous float32 bias parameters")
             zeros = torch.zeros(D, device=dev, dtype=torch.int64)
-            pa += [el(att.linear_q.bias), el(att.linear_k.bias), el(att.linear_v.bias), el(cv.pointwise_conv1.bias)[pl.idx]]
+            pa += [el(att.linear_q.bias), el(att.linear_k.bias), el(att.linear_v.bias), el(b1)[pl.idx]]
             pb += [el(att.pos_bias_u) if relative else zeros, zeros, zeros, zeros, zeros]
             self.vec_slices.append((n, n + 3 * D, n + 5 * D))
             n += 5 * D
         self.pa, self.pb = torch.cat(pa).contiguous(), torch.cat(pb).contiguous()
         self.vec = torch.empty(n, dtype=torch.float32, device=dev)
         self.prec, self.layers, self.val = prec, list(layers), None
-        self.srcs = [t for pl in self.plans for t in pl.srcs]
         self.ptrs = tuple(t.data_ptr() for l in layers for t in l.parameters())
 
     def valid_for(self, layers, prec):
@@ -464,7 +425,7 @@ class _StackPackPlan:
         _c.check(_c.lib().cfm_pack_vectors(self.pa.data_ptr(), self.pb.data_ptr(), self.vec.data_ptr(), self.vec.numel(), _c.stream()), "cfm_pack_vectors")
         if self.val is None:        # the destinations never move (valid_for checks the sources' addresses): the same Packed objects every step, so
             # whoever caches on their identity (the stack's ctypes weight structs, cfm/autograd.py) keeps its cache across optimizer steps
-            self.val = tuple(pl.run(l, launch=False, vectors=(self.vec[a:b], self.vec[b:c])) for l, pl, (a, b, c) in zip(self.layers, self.plans, self.vec_slices))
+            self.val = tuple(pl.packs(l, self.vec[a:b], self.vec[b:c]) for l, pl, (a, b, c) in zip(self.layers, self.plans, self.vec_slices))
         return self.val
 
 

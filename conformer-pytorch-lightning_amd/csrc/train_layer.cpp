@@ -2,9 +2,11 @@
 //
 // reference: src/encoder_layer.py:49-71 under module.train() -- four residual sub-blocks (1/2 FFN, MHSA, convolution module with BatchNorm
 // batch statistics, 1/2 FFN) + norm_final, dropout on every branch output / FFN hidden activation / attention probabilities -- and what
-// autograd derives from it.  The same launches, in the same order, as the op-by-op composition in cfm/autograd.py (which remains for the
-// bare modules and as the readable specification; tests run both and compare): ~17 launches forward, ~60 backward per block, issued from
-// ONE host call each instead of ~60 Python -> ctypes round trips (~18 us apiece: the step was host-bound at 40 ms with 27 ms of kernels).
+// autograd derives from it.  The same launches, in the same order, as the op-by-op composition of cfm/autograd.py's sub-block helpers (which
+// remain for the bare modules; tests/train_block_ref.py composes them into a block, the readable specification the tests compare against bit
+// for bit).  This is the only train route of a block (cfm/autograd.py EncoderStackFn, and EncoderLayerFn with one block and one row group):
+// ~17 launches forward, ~60 backward per block, issued from ONE host call each instead of ~60 Python -> ctypes round trips (~18 us apiece:
+// the step was host-bound at 40 ms with 27 ms of kernels).
 //
 // Parameter gradients are written (accumulated: the caller zero-fills) straight into a caller-provided flat buffer through per-parameter
 // pointers / row-offset maps -- in the data-parallel trainer that buffer IS the gradient bucket memory the RCCL all-reduce runs on.

@@ -167,8 +167,10 @@ class ConformerEncoder(nn.Module):
         from encoder_layer import _mask_args
         layers = list(self.encoders)
         flat = all(l.__dict__.get("_flat_leaf") is not None for l in layers)
-        if not ag.stack_supported(layers, flat):
-            # blocks the stack path does not take (other kernel sizes, parameter-free BatchNorm ...): micro-batch after micro-batch, block by block
+        ag.check_params(layers, flat)
+        if not ag.stack_supported(layers, len(batches)):
+            # blocks that cannot share one io struct (different sizes or dropout rates; BatchNorm momentum=None over several micro-batches):
+            # micro-batch after micro-batch, block by block (cfm/autograd.py EncoderLayerFn)
             outs = []
             for inputs, lengths in batches:
                 inputs, cmvn = self._cmvn_args(inputs)

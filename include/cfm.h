@@ -837,7 +837,9 @@ int cfm_pack_vectors(const float* const* a, const float* const* b, float* out, i
 
 /* ------------------------------------------------------------------------------------------------
  * The conformer blocks in TRAIN mode (csrc/train_layer.cpp): encoder_layer.py:49-71 under module.train() and its
- * backward, the same launches in the same order as the op-by-op composition of cfm/autograd.py.  All buffers are the caller's:
+ * backward, the same launches in the same order as the op-by-op composition of cfm/autograd.py's sub-block helpers (tests/train_block_ref.py).
+ * A block may lack the conv module's biases or the BatchNorm affine: the kernels write those gradients all the same, so the caller points
+ * them at a discard buffer, never at null.  All buffers are the caller's:
  *   weights  the train packs (forward [N,K] and transposed [K,N] 16-bit matrices, + lo planes in the f32-accurate mode; cfm/packing.py)
  *   saved    activations the backward needs, act dtype unless typed: xn1..4 [M,D], z1,z2,h1,h2 [M,FF], qkv [M,3D], ctx [M,D], u [M,2D], glu/s [M,D],
  *            f32 x1..x4 / c [M,D], lse [B,H,T], stats [4,D]

@@ -2,8 +2,9 @@
 
 * copy.deepcopy and pickle (torch.save) of a module holding them must succeed and give a copy WITHOUT them: the ctypes weight structs hold
   raw device pointers (unpicklable, and a copied pointer would address the original's memory), the packs belong to the original's tensors.
-* the train-mode weight struct (cfm/autograd.py _train_weights_struct) must be rebuilt when a LayerNorm parameter or a BatchNorm running
-  buffer is replaced by a new tensor, although the weight packs it is keyed on stay the same objects."""
+* the train-mode weight structs (cfm/autograd.py _stack_weights, cached in the owner's _stack_w) must be rebuilt when a LayerNorm parameter or
+  a BatchNorm running buffer is replaced by a new tensor, although the weight packs they are keyed on stay the same objects.
+* train mode refuses, up front, a block parameter the kernels cannot read through a raw f32 pointer."""
 import copy
 import io
 import pickle
@@ -46,9 +47,9 @@ def plant(obj):
     pks = tuple(packing.Packed(w=torch.zeros(4)) for _ in range(4))
     for layer in enc.encoders:
         layer._fused = (("bf16", 0), pointer_struct(), (torch.zeros(3),))
-        layer.__dict__["_train_w_struct"] = (pks, pointer_struct(), (1, 2))
-        layer.__dict__["_pack_layer_train"] = (("bf16",), object(), pks)
-        layer.__dict__["_pack_layer_srcs"] = list(layer.parameters())[:3]
+        layer.__dict__["_stack_w"] = ((pks,), (cfm.LayerTrainWeights * 1)(pointer_struct()), ())      # a block run on its own (EncoderLayerFn)
+        layer.__dict__["_stack_g"] = (("slab", (1,)), (cfm.LayerTrainGrads * 1)())
+        layer.__dict__["_pack_stack_train"] = (("walk",), object(), (pks,))
         layer.__dict__["_grad_layout"] = {None: dict(device=torch.device("cpu"), numel=4)}
     L = len(enc.encoders)
     arr = (cfm.LayerTrainWeights * L)()
@@ -99,7 +100,7 @@ def test_deepcopy_and_pickle_drop_pointer_caches(part):
     assert_clean(mod, torch.load(buf, weights_only=False))
     # the original keeps its caches: copying does not disturb the model being trained
     layer = obj.encoder.encoders[0]
-    assert layer._fused is not None and "_train_w_struct" in layer.__dict__ and "_stack_w" in obj.encoder.__dict__
+    assert layer._fused is not None and "_stack_w" in layer.__dict__ and "_stack_w" in obj.encoder.__dict__
 
 
 def fake_packs():
@@ -112,24 +113,30 @@ def fake_packs():
     return ffn(), att, cv, ffn()
 
 
-def test_train_weight_struct_follows_replaced_norm_tensors():
+def test_train_weight_struct_follows_replaced_norm_tensors(monkeypatch):
+    """One block on its own (EncoderLayerFn: the block is its own owner)."""
     import encoder_layer
     layer = encoder_layer.ConformerEncoderLayer(64, 15, 0.0, 0.0, 136, 4, True)
-    pks = fake_packs()
-    w = ag._train_weights_struct(layer, pks)
-    assert ag._train_weights_struct(layer, pks) is w                       # nothing replaced: the cached struct
-    assert w.ln_ff_g == layer.norm_ff.weight.data_ptr()
+    pks = (fake_packs(),)
+    monkeypatch.setattr(packing, "pack_stack_train", lambda owner, ls, prec, rel, flat=False: pks)
+    prec = cfm.Precision("bf16")
+    w = ag._stack_weights(layer, [layer], prec, False)[0]
+    assert ag._stack_weights(layer, [layer], prec, False)[0] is w is layer.__dict__["_stack_w"][1]     # nothing replaced: the cached array
+    assert w[0].ln_ff_g == layer.norm_ff.weight.data_ptr()
     layer.norm_ff.weight = torch.nn.Parameter(torch.full((64,), 2.0))
-    w2 = ag._train_weights_struct(layer, pks)
-    assert w2 is not w and w2.ln_ff_g == layer.norm_ff.weight.data_ptr()
+    w2 = ag._stack_weights(layer, [layer], prec, False)[0]
+    assert w2 is not w and w2[0].ln_ff_g == layer.norm_ff.weight.data_ptr()
     bn = layer.conv_module.norm
     bn.running_mean, bn.running_var = torch.ones(64), torch.full((64,), 3.0)
-    w3 = ag._train_weights_struct(layer, pks)
+    w3 = ag._stack_weights(layer, [layer], prec, False)[0]
     assert w3 is not w2
-    assert (w3.bn_running_mean, w3.bn_running_var) == (bn.running_mean.data_ptr(), bn.running_var.data_ptr())
+    assert (w3[0].bn_running_mean, w3[0].bn_running_var) == (bn.running_mean.data_ptr(), bn.running_var.data_ptr())
     with torch.no_grad():
         layer.norm_mha.bias.add_(1.0)                                        # an in-place update keeps the address: still a hit
-    assert ag._train_weights_struct(layer, pks) is w3
+    assert ag._stack_weights(layer, [layer], prec, False)[0] is w3
+    bn.momentum = None                                                       # cumulative moving average: refreshed on every hit
+    bn.num_batches_tracked.fill_(3)
+    assert ag._stack_weights(layer, [layer], prec, False)[0] is w3 and w3[0].bn_momentum == 0.25
 
 
 def test_stack_weight_array_follows_replaced_norm_tensors(monkeypatch):
@@ -147,3 +154,25 @@ def test_stack_weight_array_follows_replaced_norm_tensors(monkeypatch):
     layers[0].conv_module.norm.running_var = torch.ones(64)
     arr3, _ = ag._stack_weights(enc, layers, prec, False)
     assert arr3 is not arr2 and arr3[0].bn_running_var == layers[0].conv_module.norm.running_var.data_ptr()
+
+
+@pytest.mark.parametrize("form", ["float64", "strided"])
+def test_train_mode_refuses_non_f32_or_strided_parameters(form):
+    """The weight structs read LayerNorm parameters, and the packs the conv module's vectors, through raw f32 pointers: a float64 or
+    non-contiguous block parameter is a TypeError naming it, before anything runs."""
+    import encoder
+    import encoder_layer
+    layer = encoder_layer.ConformerEncoderLayer(64, 15, 0.0, 0.0, 136, 4, True).train()
+    if form == "float64":
+        layer.norm_mha.weight = torch.nn.Parameter(layer.norm_mha.weight.detach().double())
+        name = "norm_mha.weight"
+    else:
+        layer.conv_module.depthwise_conv.bias = torch.nn.Parameter(torch.zeros(64, 2)[:, 0])
+        name = "conv_module.depthwise_conv.bias"
+    x = torch.zeros(2, 7, 64)
+    with pytest.raises(TypeError, match=name.replace(".", r"\.")):
+        ag.EncoderLayerFn.apply(x, layer, cfm.Precision("bf16"), None, (0, 0), None, *layer.parameters())
+    enc = encoder.ConformerEncoder(cmvn=None, **CFG).train()
+    enc.encoders[1] = layer
+    with pytest.raises(TypeError, match=name.replace(".", r"\.")):
+        enc.forward_window([(torch.zeros(2, 40, 80), torch.tensor([40, 33]))])

@@ -442,38 +442,58 @@ def test_dropout_gradients_by_finite_differences(pkg, rel):
     pkg.cfm.set_precision("bf16")
 
 
+def strip_block_(layer, case):
+    """Block forms the reference's constructors never build, made by hand: no conv-module biases (pointwise-conv-2 keeps its own), a
+    BatchNorm without affine parameters, a cumulative-moving-average BatchNorm (momentum=None)."""
+    cv = layer.conv_module
+    if case == "conv_bias_free":
+        cv.pointwise_conv1.bias = None
+        cv.depthwise_conv.bias = None
+    elif case == "bn_affine_free":
+        cv.norm = torch.nn.BatchNorm1d(cv.norm.num_features, affine=False).to(cv.pointwise_conv2.weight.device)
+    elif case == "bn_momentum_none":
+        cv.norm.momentum = None
+    return layer
+
+
 @pytest.mark.parametrize("mode", ["bf16", "fp32"])
 @pytest.mark.parametrize("rel", [True, False])
 def test_composite_block_equals_op_by_op(pkg, mode, rel):
-    """The block enqueued from C++ (csrc/train_layer.cpp, two host calls) against the op-by-op composition of cfm/autograd.py (one C-ABI call
-    per kernel): the same launches in the same order, so with the weight-gradient products unsplit (no atomics) output, input gradient and
-    every parameter gradient are BIT-identical -- with dropout 0.1 active (same seed) and a ragged batch."""
-    from cfm import autograd as ag
+    """The block enqueued from C++ (cfm.autograd.EncoderLayerFn: csrc/train_layer.cpp, two host calls) against the op-by-op composition of
+    tests/train_block_ref.py (one C-ABI call per kernel): the same launches in the same order, so with the weight-gradient products unsplit (no
+    atomics) output, input gradient, every parameter gradient and the running variance are BIT-identical -- with dropout 0.1 active (same seed)
+    and a ragged batch, over two steps (the second one from the cached packs and weight structs); for the reference's block and for the
+    hand-made forms of strip_block_."""
+    import train_block_ref
     pkg.cfm.set_precision(mode)
     pkg.cfm.set_deterministic(True)
     try:
         D, H, FF, K, B, T = 144, 4, 576, 15, 3, 37
-        layer = synth.load_synth_(pkg.encoder_layer.ConformerEncoderLayer(D, K, 0.1, 0.1, FF, H, rel), 35).to(DEV).train()
         pad = pad_valid([37, 30, 19], T)
         pos_b = pkg.attention.RelativePositionalEncoding(D, 0.0).pe[0:B].to(DEV) if rel else None
         x = dev(synth.normal(45, (B, T, D)))
         G = dev(synth.normal(46, (B, T, D)))
-        res = {}
-        for comp in (True, False):
-            ag.USE_COMPOSITE = comp
-            layer.zero_grad()
-            layer.conv_module.norm.reset_running_stats()
-            xr = x.clone().requires_grad_(True)
-            torch.manual_seed(99)
-            out = layer(xr, pad, pos_b, pad)[0]
-            (out * G).sum().backward()
-            res[comp] = (out.detach().clone(), xr.grad.clone(), {k: p.grad.clone() for k, p in layer.named_parameters()},
-                         layer.conv_module.norm.running_var.clone())
-        assert torch.equal(res[True][0], res[False][0]) and torch.equal(res[True][1], res[False][1]) and torch.equal(res[True][3], res[False][3])
-        for k in res[True][2]:
-            assert torch.equal(res[True][2][k], res[False][2][k]), k
+        for case in ("reference", "conv_bias_free", "bn_affine_free", "bn_momentum_none"):
+            layer = synth.load_synth_(pkg.encoder_layer.ConformerEncoderLayer(D, K, 0.1, 0.1, FF, H, rel), 35).to(DEV).train()
+            strip_block_(layer, case)
+            res = {}
+            for comp in (True, False):
+                layer.conv_module.norm.reset_running_stats()
+                res[comp] = []
+                for step in range(2):
+                    layer.zero_grad()
+                    xr = x.clone().requires_grad_(True)
+                    torch.manual_seed(99 + step)
+                    out = layer(xr, pad, pos_b, pad)[0] if comp else train_block_ref.block_train_forward(layer, xr, pad, pad)
+                    (out * G).sum().backward()
+                    res[comp].append((out.detach().clone(), xr.grad.clone(), {k: p.grad.clone() for k, p in layer.named_parameters()},
+                                      layer.conv_module.norm.running_var.clone()))
+            for got, ref in zip(res[True], res[False]):
+                assert torch.equal(got[0], ref[0]) and torch.equal(got[1], ref[1]) and torch.equal(got[3], ref[3]), case
+                assert got[2].keys() == ref[2].keys(), case
+                for k in got[2]:
+                    assert torch.equal(got[2][k], ref[2][k]), (case, k)
     finally:
-        ag.USE_COMPOSITE = True
         pkg.cfm.set_deterministic(False)
         pkg.cfm.set_precision("bf16")
 

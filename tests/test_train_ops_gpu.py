@@ -459,9 +459,9 @@ def test_attention_dropout_forward_backward(cfm, B, T, H, dk, mode):
 
 @pytest.mark.parametrize("mode", ["bf16", "fp16", "fp32"])
 def test_pack_kernel_equals_torch_packs(mode):
-    """cfm_pack_matrices (one launch for the 8 matrices of a block: casts, transposes, the fused q|k|v concatenation, the GLU row
-    interleave, hi/lo planes in the f32-accurate mode) against the torch-op packs it replaces: bit-identical, also after an in-place
-    weight update through a raw pointer + packing.bump_epoch() (what the trainer's Adam kernel does)."""
+    """cfm_pack_matrices + cfm_pack_vectors (two launches for the 8 matrices and the two gathered bias vectors of a block: casts, transposes, the
+    fused q|k|v concatenation with pos_bias_u, the GLU row interleave, hi/lo planes in the f32-accurate mode) against the torch-op packs they
+    replace: bit-identical, also after an in-place weight update through a raw pointer + packing.bump_epoch() (what the trainer's Adam kernel does)."""
     import cfm
     import encoder_layer
     from cfm import packing
@@ -469,7 +469,7 @@ def test_pack_kernel_equals_torch_packs(mode):
     prec = cfm.Precision(mode)
     layer = encoder_layer.ConformerEncoderLayer(256, 15, 0.1, 0.1, 2048, 4, True).to("cuda")
     for rep in range(2):
-        got = packing.pack_layer_train(layer, prec, True)
+        got = packing.pack_stack_train(layer, [layer], prec, True)[0]
         ref = (packing.pack_ffn_train(layer.feed_forward_macaron, prec), packing.pack_mhsa_train(layer.self_attn, prec, True),
                packing.pack_conv_module_train(layer.conv_module, prec), packing.pack_ffn_train(layer.feed_forward, prec))
         n = 0
