@@ -43,6 +43,7 @@ struct SkinnyArgs {
     int T;
     float* pmax;             // EPI 3: per (tile, b): best value / first index of the tile's 16 classes
     int* pidx;
+    const int* n_done;       // when given (the chunk-lookahead step): every stream finished (*n_done >= B) -> the launch does nothing
 };
 
 __device__ __forceinline__ float sigmoid_acc(float x) { return 1.0f / (1.0f + expf(-x)); }
@@ -53,6 +54,7 @@ __global__ __launch_bounds__(256) void cfm_skinny_kernel(const SkinnyArgs a) {
     const int l15 = lane & 15, g = lane >> 4;
     const int tile = blockIdx.x * 4 + wave;                 // 16 output columns per wavefront
     if (tile * 16 >= a.N) return;
+    if (a.n_done && *a.n_done >= a.B) return;               // uniform: a step captured after the last stream finished costs empty launches only
     const int n0 = tile * 16;
     const int nbt = (a.B + 15) / 16;                        // <= 4 stream tiles
     f32x4 acc[4];
@@ -254,4 +256,380 @@ extern "C" int cfm_greedy_step(const cfm_greedy_desc* d, cfm_stream_t stream) {
     CfmProfScope prof("greedy_control", s, 0.0, (double)B * (d->Vp / 16) * 8);
     CFM_LAUNCH(cfm_greedy_control_kernel, dim3((unsigned)B), dim3(256), 0, s, c);
     return cfm_launch_status("cfm_greedy_step (control)");
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// Chunk lookahead (cfm_greedy_chunk_begin / cfm_greedy_chunk_step): the streaming recogniser's decoder.  The predictor output is a pure
+// function of (token, LSTM state), which change only at an emission; between two emissions the joint is therefore evaluated for ALL
+// remaining frames of a stream's chunk against the one current predictor output and the first non-blank frame is found on the device:
+// a chunk costs at most 1 + (most emissions of any stream) steps instead of frames + emissions.  One step:
+//
+//   1..L   LSTM layers, projection (the skinny launches above), pp = pred_ffn(pred); once every stream is done with the chunk (n_done == B)
+//          these launches return at once, so the steps a captured graph holds beyond the chunk's last one cost empty launches only
+//   rows   per stream b the frames f = t_b .. lens_b - 1 become rows of a COMPACT activation matrix: act[off_b + i] = tanh(encp[b, t_b + i] + pp[b]);
+//          row_off / row_cnt / n_rows describe it (finished streams contribute no row, so they cost no product)
+//   mtile  z = act . Wout^T + bout on n_rows rows, reduced to the (max, first index) per row and 16-class tile -- an M-tiled f32 MFMA
+//          product: a wavefront holds a 64-row x 32-class tile (4 x 2 MFMA tiles), every weight fragment meets four row tiles from registers
+//   ctl    one workgroup per stream: argmax per row, the first row whose class is not blank, model.py:255-267 across the lookahead
+//
+// cfm_greedy_chunk_begin applies enc_ffn to the chunk's (B chunk, D) encoder rows with the same M-tiled product (plain epilogue) and
+// resets the per-chunk control state.
+// ---------------------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+struct MTileArgs {
+    const float* W;          // [N, K] f32 row-major (N % 16 == 0, K % 16 == 0)
+    const float* bias;       // [N]
+    const float* x;          // [M, K] rows at x + m * ldx
+    int64_t ldx;
+    int M;                   // rows the launch was sized for ...
+    const int* n_rows;       // ... and, when given, the number that exist this time (device side, <= M)
+    int N, K;
+    float* out;              // EPI 0: out[m, n] (ld_out)
+    int64_t ld_out;
+    float* pmax;             // EPI 1: per (row, 16-class tile): best value / first index, [M, ntiles]
+    int* pidx;
+};
+
+// 256 threads = 4 wavefronts side by side along N; a wavefront: rows m0 .. m0 + 63 (blockIdx.y) x two 16-column tiles.  Operands are read
+// as 16-byte pieces straight from memory in cfm_skinny_kernel's contraction order (lane group g holds k = 16 q + 4 g + r), the next
+// pieces requested before the current ones are multiplied; per 16 k: 6 loads feed 32 MFMAs.
+template <int EPI>
+__global__ __launch_bounds__(256) void cfm_mtile_kernel(const MTileArgs a) {
+    int M = a.M;
+    if (a.n_rows) { const int n = *a.n_rows; M = n < M ? n : M; }
+    const int m0 = blockIdx.y * 64;
+    if (m0 >= M) return;                                    // row tiles that do not exist this step: no product
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int l15 = lane & 15, g = lane >> 4;
+    const int ntl = a.N / 16;
+    const int nt0 = (blockIdx.x * 4 + wave) * 2;
+    if (nt0 >= ntl) return;
+    const bool two = nt0 + 1 < ntl;                         // uniform
+    const int nmt = (M - m0 + 15) / 16 < 4 ? (M - m0 + 15) / 16 : 4;
+    f32x4 acc[2][4];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) acc[j][mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const float* w0 = a.W + (int64_t)(nt0 * 16 + l15) * a.K + 4 * g;
+    const float* w1 = two ? w0 + (int64_t)16 * a.K : w0;
+    const float* xr[4];
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) {
+        int m = m0 + mt * 16 + l15;
+        m = m < M ? m : M - 1;
+        xr[mt] = a.x + (int64_t)m * a.ldx + 4 * g;
+    }
+    const int nq = a.K / 16;
+    f32x4 wv0 = *(const f32x4*)w0, wv1 = *(const f32x4*)w1, xv[4];
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) xv[mt] = mt < nmt ? *(const f32x4*)xr[mt] : (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int q = 0; q < nq; ++q) {
+        const int qn = q + 1 < nq ? q + 1 : q;
+        const f32x4 nw0 = *(const f32x4*)(w0 + 16 * qn), nw1 = *(const f32x4*)(w1 + 16 * qn);
+        f32x4 nx[4];
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) nx[mt] = mt < nmt ? *(const f32x4*)(xr[mt] + 16 * qn) : (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) {
+            if (mt < nmt) {                                  // uniform
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    acc[0][mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv0[r], xv[mt][r], acc[0][mt], 0, 0, 0);
+                    acc[1][mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv1[r], xv[mt][r], acc[1][mt], 0, 0, 0);
+                }
+            }
+        }
+        wv0 = nw0; wv1 = nw1;
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) xv[mt] = nx[mt];
+    }
+    // lane (l15, g) holds output columns n0 + 4 g + r (r = 0..3) of row m0 + 16 mt + l15
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        if (j == 1 && !two) break;
+        const int n0 = (nt0 + j) * 16;
+        const f32x4 bv = *(const f32x4*)(a.bias + n0 + 4 * g);
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) {
+            if (mt >= nmt) break;
+            const int m = m0 + mt * 16 + l15;
+            const f32x4 v = acc[j][mt] + bv;
+            if constexpr (EPI == 0) {
+                if (m < M) *(f32x4*)(a.out + (int64_t)m * a.ld_out + n0 + 4 * g) = v;
+            } else {                                         // the tile's best class per row, lowest index on ties
+                float best = v.x;
+                int bi = n0 + 4 * g;
+                if (v.y > best) { best = v.y; bi = n0 + 4 * g + 1; }
+                if (v.z > best) { best = v.z; bi = n0 + 4 * g + 2; }
+                if (v.w > best) { best = v.w; bi = n0 + 4 * g + 3; }
+#pragma unroll
+                for (int o = 16; o < 64; o <<= 1) {
+                    const float ob = __shfl_xor(best, o, 64);
+                    const int oi = __shfl_xor(bi, o, 64);
+                    if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+                }
+                if (g == 0 && m < M) {
+                    a.pmax[(int64_t)m * ntl + nt0 + j] = best;
+                    a.pidx[(int64_t)m * ntl + nt0 + j] = bi;
+                }
+            }
+        }
+    }
+}
+
+template <int EPI>
+int launch_mtile(const MTileArgs& a, hipStream_t s, const char* name) {
+    const int ntl = a.N / 16;
+    CfmProfScope prof(name, s, 2.0 * a.M * (double)a.N * a.K, ((double)a.N + a.M) * a.K * 4);
+    CFM_LAUNCH((cfm_mtile_kernel<EPI>), dim3((unsigned)((ntl + 7) / 8), (unsigned)((a.M + 63) / 64)), dim3(256), 0, s, a);
+    return cfm_launch_status(name);
+}
+
+struct ChunkBeginArgs {
+    int64_t *token, *t, *frame_count;
+    const int64_t* lens;
+    float *h, *c;
+    uint8_t* done;
+    int *n_done, *steps;
+    int B, L, H, blank, carry;
+};
+
+// one workgroup per stream: frame index and per-frame count to 0 (the reference starts every basic_greedy_search call with
+// per_frame_noblk = 0); carry == 0: the predictor restarts from blank / zeros (greedy_search_streaming_eval, model.py:155-161) on the
+// streams that have frames; an idle stream (lens == 0) keeps everything
+__global__ __launch_bounds__(256) void cfm_chunk_begin_kernel(const ChunkBeginArgs a) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const bool idle = a.lens[b] <= 0;
+    if (tid == 0) {
+        a.t[b] = 0;
+        a.frame_count[b] = 0;
+        a.done[b] = idle ? 1 : 0;
+        if (!a.carry && !idle) a.token[b] = a.blank;
+        if (b == 0) {
+            int n = 0;
+            for (int i = 0; i < a.B; ++i) n += a.lens[i] <= 0 ? 1 : 0;
+            *a.n_done = n;
+            *a.steps = 0;
+        }
+    }
+    if (!a.carry && !idle) {
+        for (int i = tid; i < a.L * a.H; i += 256) {
+            const int l = i / a.H, u = i - l * a.H;
+            const int64_t o = ((int64_t)l * a.B + b) * a.H + u;
+            a.h[o] = 0.f;
+            a.c[o] = 0.f;
+        }
+    }
+}
+
+struct ChunkRowsArgs {
+    const float *encp, *pp;
+    const int64_t *t, *lens;
+    float* act;
+    int *rows, *row_off, *row_cnt, *n_rows, *steps;
+    int B, chunk, J;
+};
+
+// one workgroup per stream: its place in the compact row list (every workgroup sums the <= 64 counts itself), then its rows
+__global__ __launch_bounds__(256) void cfm_chunk_rows_kernel(const ChunkRowsArgs a) {
+    __shared__ int s_cnt[64];
+    __shared__ int s_off, s_tot;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (tid < a.B) {
+        int64_t ti = a.t[tid], li = a.lens[tid];
+        ti = ti < 0 ? 0 : ti;
+        li = li < a.chunk ? li : a.chunk;
+        s_cnt[tid] = ti < li ? (int)(li - ti) : 0;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int off = 0, tot = 0;
+        for (int i = 0; i < a.B; ++i) {
+            if (i < b) off += s_cnt[i];
+            tot += s_cnt[i];
+        }
+        s_off = off;
+        s_tot = tot;
+        a.row_off[b] = off;
+        a.row_cnt[b] = s_cnt[b];
+        if (b == 0) {
+            *a.n_rows = tot;
+            if (tot > 0) *a.steps += 1;                      // a step that began with a live stream
+        }
+    }
+    __syncthreads();
+    const int cnt = s_cnt[b], off = s_off;
+    if (cnt == 0) return;
+    int64_t tb = a.t[b];
+    const int t0 = tb < 0 ? 0 : (int)tb;
+    for (int i = tid; i < cnt; i += 256) a.rows[off + i] = b * a.chunk + t0 + i;
+    const int j4n = a.J / 4;
+    for (int i = tid; i < cnt * j4n; i += 256) {
+        const int r = i / j4n, j = (i - r * j4n) * 4;
+        const f32x4 e = *(const f32x4*)(a.encp + ((int64_t)b * a.chunk + t0 + r) * a.J + j);
+        const f32x4 p = *(const f32x4*)(a.pp + (int64_t)b * a.J + j);
+        *(f32x4*)(a.act + (int64_t)(off + r) * a.J + j) = (f32x4){tanhf(e.x + p.x), tanhf(e.y + p.y), tanhf(e.z + p.z), tanhf(e.w + p.w)};
+    }
+}
+
+struct ChunkCtlArgs {
+    const float* pmax;
+    const int* pidx;
+    const int *row_off, *row_cnt;
+    int ntiles, B, L, H, blank, n_steps;
+    int64_t *token, *t, *count, *frame_count, *hyps;
+    const int64_t* lens;
+    int64_t hyp_cap, hyp_ld;
+    float *h, *c;
+    const float *h_new, *c_new;
+    uint8_t* done;
+    int *n_done, *overflow;
+};
+
+// one workgroup per stream: the class of each of its rows (a wavefront per row, torch.argmax's lowest-index rule), then model.py:255-267
+// across the lookahead: the first row whose class is not blank emits; the blank rows before it are the frames the reference would have
+// stepped over one by one with the same predictor output
+__global__ __launch_bounds__(256) void cfm_chunk_control_kernel(const ChunkCtlArgs a) {
+    __shared__ int s_k[32];
+    __shared__ int s_nb;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int cnt = a.row_cnt[b], off = a.row_off[b];
+    if (cnt == 0) return;                                    // idle or finished: nothing about the stream changes
+    for (int r = wave; r < cnt; r += 4) {
+        float best = -INFINITY;
+        int bi = 0x7fffffff;
+        const int64_t base = (int64_t)(off + r) * a.ntiles;
+        for (int tl = lane; tl < a.ntiles; tl += 64) {
+            const float v = a.pmax[base + tl];
+            const int i = a.pidx[base + tl];
+            if (v > best || (v == best && i < bi)) { best = v; bi = i; }
+        }
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const float ob = __shfl_xor(best, o, 64);
+            const int oi = __shfl_xor(bi, o, 64);
+            if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+        }
+        if (lane == 0) s_k[r] = bi;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int first = -1;
+        for (int r = 0; r < cnt; ++r) {
+            if (s_k[r] != a.blank) { first = r; break; }
+        }
+        int64_t t = a.t[b], fc = a.frame_count[b];
+        t = t < 0 ? 0 : t;
+        const int64_t end = t + cnt;                         // = min(lens, chunk)
+        if (first < 0) {
+            t = end;
+            fc = 0;
+        } else {
+            const int k = s_k[first];
+            const int64_t n = a.count[b];
+            if (n < a.hyp_cap) a.hyps[(int64_t)b * a.hyp_ld + n] = k;
+            else *a.overflow = 1;                            // the caller sizes the buffer; never the last slot again
+            a.count[b] = n + 1;
+            a.token[b] = k;
+            fc = (first == 0 ? fc : 0) + 1;
+            t += first;
+            if (fc >= a.n_steps) { t += 1; fc = 0; }
+        }
+        a.t[b] = t;
+        a.frame_count[b] = fc;
+        if (t >= end) {
+            a.done[b] = 1;
+            atomicAdd(a.n_done, 1);
+        }
+        s_nb = first >= 0 ? 1 : 0;
+    }
+    __syncthreads();
+    if (s_nb) {
+        for (int i = tid; i < a.L * a.H; i += 256) {
+            const int l = i / a.H, u = i - l * a.H;
+            const int64_t o = ((int64_t)l * a.B + b) * a.H + u;
+            a.h[o] = a.h_new[o];
+            a.c[o] = a.c_new[o];
+        }
+    }
+}
+
+int chunk_check(const cfm_greedy_chunk_desc* d, const char* who) {
+    CFM_CHECK_ARG(d, "%s: null descriptor", who);
+    CFM_CHECK_ARG(d->B > 0 && d->B <= 64 && d->L >= 1 && d->L <= 4 && d->chunk >= 1 && d->chunk <= 32 && d->E % 16 == 0 && d->H % 16 == 0 && d->P % 16 == 0 &&
+                      d->J % 16 == 0 && d->D % 16 == 0 && d->Vp % 16 == 0 && d->E > 0 && d->H > 0 && d->P > 0 && d->J > 0 && d->D > 0 && d->Vp > 0 && d->n_steps > 0 &&
+                      d->hyp_cap >= 0 && d->hyp_ld >= d->hyp_cap,
+                  "%s: B <= 64 streams, chunk <= 32, <= 4 LSTM layers, sizes multiples of 16 (B=%d chunk=%d L=%d E=%d H=%d P=%d J=%d D=%d Vp=%d)", who, d->B,
+                  d->chunk, d->L, d->E, d->H, d->P, d->J, d->D, d->Vp);
+    CFM_CHECK_ARG(d->embed && d->proj_w && d->proj_b && d->pf_w && d->pf_b && d->out_w && d->out_b && d->ef_w && d->ef_b && d->enc_proj && d->token && d->t &&
+                      d->lens && d->count && d->frame_count && d->hyps && d->h && d->c && d->h_new && d->c_new && d->pred && d->pp && d->act && d->pmax &&
+                      d->pidx && d->rows && d->row_off && d->row_cnt && d->n_rows && d->steps && d->overflow && d->done && d->n_done,
+                  "%s: null pointer", who);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int cfm_greedy_chunk_begin(const cfm_greedy_chunk_desc* d, cfm_stream_t stream) {
+    if (int rc = chunk_check(d, "cfm_greedy_chunk_begin")) return rc;
+    CFM_CHECK_ARG(d->enc, "cfm_greedy_chunk_begin: no encoder output");
+    hipStream_t s = (hipStream_t)stream;
+    MTileArgs a = {};
+    a.W = d->ef_w; a.bias = d->ef_b; a.x = d->enc; a.ldx = d->D; a.M = d->B * d->chunk; a.N = d->J; a.K = d->D; a.out = d->enc_proj; a.ld_out = d->J;
+    if (int rc = launch_mtile<0>(a, s, "greedy_chunk_enc_ffn")) return rc;
+    ChunkBeginArgs g;
+    g.token = d->token; g.t = d->t; g.frame_count = d->frame_count; g.lens = d->lens; g.h = d->h; g.c = d->c; g.done = d->done; g.n_done = d->n_done;
+    g.steps = d->steps; g.B = d->B; g.L = d->L; g.H = d->H; g.blank = d->blank; g.carry = d->carry;
+    CfmProfScope prof("greedy_chunk_begin", s, 0.0, 0.0);
+    CFM_LAUNCH(cfm_chunk_begin_kernel, dim3((unsigned)d->B), dim3(256), 0, s, g);
+    return cfm_launch_status("cfm_greedy_chunk_begin");
+}
+
+extern "C" int cfm_greedy_chunk_step(const cfm_greedy_chunk_desc* d, cfm_stream_t stream) {
+    if (int rc = chunk_check(d, "cfm_greedy_chunk_step")) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int B = d->B, H = d->H;
+    for (int l = 0; l < d->L; ++l) {
+        CFM_CHECK_ARG(d->lstm_w[l] && d->lstm_b[l], "cfm_greedy_chunk_step: LSTM layer %d has no weights", l);
+        SkinnyArgs a = {};
+        a.W = d->lstm_w[l]; a.bias = d->lstm_b[l]; a.B = B; a.N = 4 * H; a.x2 = d->h + (int64_t)l * B * H; a.ld2 = H;
+        if (l == 0) { a.x1 = d->embed; a.x1_rows = d->token; a.ld1 = d->E; a.K1 = d->E; }
+        else { a.x1 = d->h_new + (int64_t)(l - 1) * B * H; a.ld1 = H; a.K1 = H; }
+        a.K = a.K1 + H;
+        a.c_in = d->c + (int64_t)l * B * H; a.h_out = d->h_new + (int64_t)l * B * H; a.c_out = d->c_new + (int64_t)l * B * H; a.n_done = d->n_done;
+        if (int rc = launch_skinny<1>(a, s, "greedy_lstm")) return rc;
+    }
+    {
+        SkinnyArgs a = {};
+        a.W = d->proj_w; a.bias = d->proj_b; a.B = B; a.N = d->P; a.K = a.K1 = H; a.x1 = d->h_new + (int64_t)(d->L - 1) * B * H; a.ld1 = H; a.out = d->pred; a.ld_out = d->P; a.n_done = d->n_done;
+        if (int rc = launch_skinny<0>(a, s, "greedy_proj")) return rc;
+    }
+    {
+        SkinnyArgs a = {};
+        a.W = d->pf_w; a.bias = d->pf_b; a.B = B; a.N = d->J; a.K = a.K1 = d->P; a.x1 = d->pred; a.ld1 = d->P; a.out = d->pp; a.ld_out = d->J; a.n_done = d->n_done;
+        if (int rc = launch_skinny<0>(a, s, "greedy_chunk_pred_ffn")) return rc;
+    }
+    {
+        ChunkRowsArgs r;
+        r.encp = d->enc_proj; r.pp = d->pp; r.t = d->t; r.lens = d->lens; r.act = d->act; r.rows = d->rows; r.row_off = d->row_off; r.row_cnt = d->row_cnt;
+        r.n_rows = d->n_rows; r.steps = d->steps; r.B = B; r.chunk = d->chunk; r.J = d->J;
+        CfmProfScope prof("greedy_chunk_rows", s, 0.0, (double)B * d->chunk * d->J * 8);
+        CFM_LAUNCH(cfm_chunk_rows_kernel, dim3((unsigned)B), dim3(256), 0, s, r);
+        if (int rc = cfm_launch_status("cfm_greedy_chunk_step (rows)")) return rc;
+    }
+    {
+        MTileArgs a = {};
+        a.W = d->out_w; a.bias = d->out_b; a.x = d->act; a.ldx = d->J; a.M = B * d->chunk; a.n_rows = d->n_rows; a.N = d->Vp; a.K = d->J; a.pmax = d->pmax; a.pidx = d->pidx;
+        if (int rc = launch_mtile<1>(a, s, "greedy_chunk_joint_out")) return rc;
+    }
+    ChunkCtlArgs c;
+    c.pmax = d->pmax; c.pidx = d->pidx; c.row_off = d->row_off; c.row_cnt = d->row_cnt; c.ntiles = d->Vp / 16; c.B = B; c.L = d->L; c.H = H; c.blank = d->blank;
+    c.n_steps = d->n_steps; c.token = d->token; c.t = d->t; c.count = d->count; c.frame_count = d->frame_count; c.hyps = d->hyps; c.lens = d->lens;
+    c.hyp_cap = d->hyp_cap; c.hyp_ld = d->hyp_ld; c.h = d->h; c.c = d->c; c.h_new = d->h_new; c.c_new = d->c_new; c.done = d->done; c.n_done = d->n_done;
+    c.overflow = d->overflow;
+    CfmProfScope prof("greedy_chunk_control", s, 0.0, (double)B * d->chunk * (d->Vp / 16) * 8);
+    CFM_LAUNCH(cfm_chunk_control_kernel, dim3((unsigned)B), dim3(256), 0, s, c);
+    return cfm_launch_status("cfm_greedy_chunk_step (control)");
 }

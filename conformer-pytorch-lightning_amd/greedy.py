@@ -228,3 +228,264 @@ class BatchedGreedySearch:
         counts = S["count"].tolist()
         hyps = S["hyps"].cpu()
         return [hyps[b, :counts[b]].tolist() for b in range(B)], (S["token"].clone(), (S["h"].clone(), S["c"].clone()))
+
+
+class ChunkGreedySearch:
+    """The decoder of a batched streaming recogniser: `streams` utterances decoded chunk by chunk (`chunk` encoder frames per call), all
+    state -- the predictor's input token and LSTM state, the hypothesis buffer that ACCUMULATES across chunks and its counts -- resident on
+    the device.  It is the reference's `greedy_search_streaming_app` (src/model.py:178-199; carry=True) / `greedy_search_streaming_eval`
+    (:126-165; carry=False: that path passes cache=None, pred_input_step=None for every chunk, so the predictor restarts from blank / zeros
+    each chunk -- a quirk of the reference, kept) around `basic_greedy_search`, for all streams at once.
+
+    One decoding step is a LOOKAHEAD step: the predictor output is a pure function of (token, LSTM state), which change only when a symbol
+    is emitted, so between two emissions the joint is evaluated for all remaining frames of the chunk against the one current predictor
+    output and the first frame whose argmax is not blank is found on the device.  That is the reference's sequence of decisions -- the blank
+    frames before the emission are the ones its loop steps over one by one with the same predictor output -- in at most
+    1 + (most emissions of any stream in the chunk) steps instead of frames + emissions (`steps` holds the number the last decode needed).
+
+    On an MI355X a step is cfm_greedy_chunk_step (csrc/greedy.hip: the skinny predictor launches, a compact row list of the frames still
+    to decide, the vocabulary projection as an M-tiled f32 MFMA product, one control workgroup per stream), `steps_per_replay` of them
+    captured in one HIP graph; the host reads one "streams done" counter per replay (`replays`); the steps a replay holds beyond the chunk's
+    last one are empty launches (every kernel of the step returns at once when all streams are done).  Sizes outside the kernel's limits
+    (64 streams, chunk 32, 4 LSTM layers, dimensions multiples of 16) raise.  On the CPU the same step runs as torch operations (`_step`)."""
+
+    def __init__(self, predictor, joint, streams, chunk, blank=0, n_steps=64, steps_per_replay=4, use_graph=True, carry=True, fused=None, max_tokens=None):
+        self.predictor, self.joint = predictor, joint
+        self.B, self.chunk = int(streams), int(chunk)
+        self.blank, self.n_steps, self.steps_per_replay, self.use_graph, self.carry = int(blank), int(n_steps), int(steps_per_replay), bool(use_graph), bool(carry)
+        if self.B < 1 or self.chunk < 1 or self.n_steps < 1 or self.steps_per_replay < 1:
+            raise ValueError("ChunkGreedySearch: streams, chunk, n_steps and steps_per_replay are positive")
+        self._base = BatchedGreedySearch(predictor, joint, blank=blank, n_steps=n_steps, fused=False)      # the weight key, the f32 packs, the LSTM step
+        self.dev = next(predictor.parameters()).device
+        self.fused = (self.dev.type == "cuda") if fused is None else bool(fused)
+        if self.fused and not self._fused_ok():
+            raise RuntimeError("the fused chunk-lookahead step needs a GPU, <= 64 streams, chunk <= 32, <= 4 LSTM layers and dimensions that are "
+                               "multiples of 16 (there is no fallback)")
+        self.S = self._state(max(1, int(max_tokens) if max_tokens is not None else 2 * self.chunk * self.n_steps))     # decode needs count + chunk * n_steps
+        self._host_count = [0] * self.B                                                 # exact after every decode; + chunk * n_steps bounds the next one
+        self._host_hyps = [[] for _ in range(self.B)]
+        self._graph = self._desc = self._key_w = self._ew = self._enc_keep = None
+        self.steps = self.replays = self.total_steps = self.total_replays = 0
+
+    # -- state -----------------------------------------------------------------------------------------------------------------------------
+    def _fused_ok(self):
+        pr, jn = self.predictor, self.joint
+        dims = (pr.embed_size, pr.hidden_size, pr.projection.out_features, jn.pred_ffn.out_features, jn.enc_ffn.in_features)
+        return (self.dev.type == "cuda" and self.B <= 64 and self.chunk <= 32 and pr.num_layers <= 4 and all(d % 16 == 0 for d in dims) and pr.rnn.bias and
+                jn.pred_ffn.in_features == pr.projection.out_features)
+
+    def _state(self, cap):
+        pr, jn, B, C, dev = self.predictor, self.joint, self.B, self.chunk, self.dev
+        L, H, J = pr.num_layers, pr.hidden_size, jn.enc_ffn.out_features
+        z64 = lambda *s: torch.zeros(s, dtype=torch.int64, device=dev)
+        z32 = lambda *s: torch.zeros(s, dtype=torch.int32, device=dev)
+        S = dict(ar=torch.arange(B, device=dev), frames=torch.arange(C, device=dev), enc_proj=torch.zeros((B, C, J), device=dev), t=z64(B), lens=z64(B),
+                 token=torch.full((B,), self.blank, dtype=torch.int64, device=dev), h=torch.zeros((L, B, H), device=dev), c=torch.zeros((L, B, H), device=dev),
+                 count=z64(B), frame_count=z64(B), hyps=z64(B, cap), steps=z32(1), overflow=z32(1), n_done=z32(1))
+        if self.fused:
+            Vp = (jn.ffn_out.out_features + 15) // 16 * 16
+            S.update(h_new=torch.zeros((L, B, H), device=dev), c_new=torch.zeros((L, B, H), device=dev), pred=torch.zeros((B, pr.projection.out_features), device=dev),
+                     pp=torch.zeros((B, J), device=dev), act=torch.zeros((B * C, J), device=dev), pmax=torch.zeros((B * C, Vp // 16), device=dev),
+                     pidx=z32(B * C, Vp // 16), rows=z32(B * C), row_off=z32(B), row_cnt=z32(B), n_rows=z32(1), done8=torch.zeros((B,), dtype=torch.uint8, device=dev))
+        return S
+
+    def _fused_desc(self, S, W, EW):
+        import cfm
+        pr, jn = self.predictor, self.joint
+        d = cfm.GreedyChunkDesc()
+        d.embed = W["embed"].data_ptr()
+        for l in range(pr.num_layers):
+            d.lstm_w[l], d.lstm_b[l] = W["lstm_w"][l].data_ptr(), W["lstm_b"][l].data_ptr()
+        for k in ("proj_w", "proj_b", "pf_w", "pf_b", "out_w", "out_b"):
+            setattr(d, k, W[k].data_ptr())
+        d.ef_w, d.ef_b = EW[0].data_ptr(), EW[1].data_ptr()
+        for k in ("enc_proj", "token", "t", "count", "frame_count", "hyps", "lens", "h", "c", "h_new", "c_new", "pred", "pp", "act", "pmax", "pidx", "rows", "row_off",
+                  "row_cnt", "n_rows", "steps", "overflow", "n_done"):
+            setattr(d, k, S[k].data_ptr())
+        d.done = S["done8"].data_ptr()
+        d.hyp_cap = d.hyp_ld = S["hyps"].shape[1]
+        d.B, d.chunk, d.L, d.E, d.H, d.P, d.J, d.D, d.Vp = (self.B, self.chunk, pr.num_layers, pr.embed_size, pr.hidden_size, pr.projection.out_features,
+                                                            jn.pred_ffn.out_features, jn.enc_ffn.in_features, W["Vp"])
+        d.blank, d.n_steps, d.carry = self.blank, self.n_steps, int(self.carry)
+        return d
+
+    def _prepare(self):
+        """Packs, descriptor and graph follow the weights (BatchedGreedySearch._weights_key: packing epoch, address, version, device, dtype)."""
+        wkey = self._base._weights_key()
+        if self._key_w != wkey:
+            self._graph, self._desc, self._key_w = None, None, wkey
+            if self.fused:
+                jn = self.joint
+                self._ew = (jn.enc_ffn.weight.detach().float().contiguous(), jn.enc_ffn.bias.detach().float().contiguous())
+        if self.fused and self._desc is None:
+            self._desc = self._fused_desc(self.S, self._base._fused_weights(self.dev), self._ew)
+
+    def _grow(self, need):
+        S = self.S
+        hyps = torch.zeros((self.B, max(2 * S["hyps"].shape[1], need)), dtype=torch.int64, device=self.dev)
+        hyps[:, :S["hyps"].shape[1]] = S["hyps"]
+        S["hyps"] = hyps
+        self._graph = self._desc = None                                                 # both hold the old buffer's address
+
+    # -- one lookahead step as torch operations (the CPU form; csrc/greedy.hip's cfm_greedy_chunk_step restated) ---------------------------------
+    def _step(self, S):
+        pr, jn, ar = self.predictor, self.joint, S["ar"]
+        t, lens, fc = S["t"], S["lens"], S["frame_count"]
+        live = t < lens
+        S["steps"].add_(live.any().to(torch.int32))
+        y, h1, c1 = self._base._lstm_step(pr.embed(S["token"]), S["h"], S["c"])
+        pp = jn.pred_ffn(pr.projection(y))
+        k = jn.ffn_out(torch.tanh(S["enc_proj"] + pp[:, None, :])).argmax(dim=-1)       # (B, chunk): every frame against the one predictor output
+        f = S["frames"][None, :]
+        nb = (k != self.blank) & (f >= t[:, None]) & (f < lens[:, None])
+        emit = nb.any(dim=1)
+        fstar = nb.to(torch.int64).argmax(dim=1)                                        # the first such frame
+        kk = k.gather(1, fstar[:, None])[:, 0]
+        cap = S["hyps"].shape[1]
+        room = S["count"] < cap
+        S["overflow"].add_((emit & ~room).any().to(torch.int32))
+        pos = S["count"].clamp(max=cap - 1)
+        S["hyps"][ar, pos] = torch.where(emit & room, kk, S["hyps"][ar, pos])
+        S["count"].add_(emit.to(torch.int64))
+        S["token"].copy_(torch.where(emit, kk, S["token"]))
+        S["h"].copy_(torch.where(emit[None, :, None], h1, S["h"]))
+        S["c"].copy_(torch.where(emit[None, :, None], c1, S["c"]))
+        fc1 = torch.where(fstar == t, fc, torch.zeros_like(fc)) + 1
+        capped = fc1 >= self.n_steps
+        t_emit = fstar + capped.to(torch.int64)
+        fc_emit = torch.where(capped, torch.zeros_like(fc1), fc1)
+        S["t"].copy_(torch.where(emit, t_emit, torch.where(live, lens, t)))
+        S["frame_count"].copy_(torch.where(emit, fc_emit, torch.where(live, torch.zeros_like(fc), fc)))
+
+    def _begin_eager(self, enc):
+        S = self.S
+        S["enc_proj"].copy_(self.joint.enc_ffn(enc.float()))
+        S["t"].zero_(); S["frame_count"].zero_(); S["steps"].zero_()
+        if not self.carry:
+            m = S["lens"] > 0
+            S["token"].copy_(torch.where(m, torch.full_like(S["token"], self.blank), S["token"]))
+            S["h"].mul_((~m)[None, :, None].to(S["h"].dtype)); S["c"].mul_((~m)[None, :, None].to(S["c"].dtype))
+
+    def _run_steps(self):
+        if self.fused:
+            import ctypes
+            import cfm
+            lib = cfm.lib()
+            for _ in range(self.steps_per_replay):
+                cfm.check(lib.cfm_greedy_chunk_step(ctypes.byref(self._desc), cfm.stream()), "cfm_greedy_chunk_step")
+        else:
+            for _ in range(self.steps_per_replay):
+                self._step(self.S)
+
+    _SNAP = ("t", "count", "frame_count", "hyps", "token", "h", "c", "steps", "overflow", "n_done")
+
+    def _capture(self):
+        S, dev = self.S, self.dev
+        snap = {k: S[k].clone() for k in self._SNAP + (("done8",) if self.fused else ())}
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            self._run_steps()                                                           # warm-up (allocator, lazy init) outside the capture
+        torch.cuda.current_stream(dev).wait_stream(side)
+        for k, v in snap.items():
+            S[k].copy_(v)                                                               # ... and undone
+        self._graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self._graph):
+            self._run_steps()
+        for k, v in snap.items():
+            S[k].copy_(v)
+
+    # -- public ---------------------------------------------------------------------------------------------------------------------------
+    def reset(self, streams=None):
+        """New utterances on the given streams (all by default): token <- blank, LSTM state and hypotheses emptied (Transducer.init_state)."""
+        S = self.S
+        idx = slice(None) if streams is None else torch.as_tensor(list(streams), dtype=torch.long, device=self.dev)
+        S["token"][idx] = self.blank
+        for k in ("count", "t", "frame_count", "hyps"):
+            S[k][idx] = 0
+        S["h"][:, idx] = 0
+        S["c"][:, idx] = 0
+        for b in (range(self.B) if streams is None else list(streams)):
+            self._host_count[b] = 0
+            self._host_hyps[b] = []
+
+    def hyps(self):
+        """Everything emitted per stream since its last reset."""
+        return [list(h) for h in self._host_hyps]
+
+    def state(self):
+        """(token (B,), (h, c) (L, B, H)): the predictor input and LSTM state the next chunk starts from (copies)."""
+        return self.S["token"].clone(), (self.S["h"].clone(), self.S["c"].clone())
+
+    def set_state(self, token, state):
+        """Continue from a carried (token (B,), (h, c) (L, B, H)), as `BatchedGreedySearch.search(..., token, state)` does."""
+        self.S["token"].copy_(token.reshape(self.B))
+        self.S["h"].copy_(state[0])
+        self.S["c"].copy_(state[1])
+
+    @torch.no_grad()
+    def decode(self, enc_chunk, lens=None):
+        """enc_chunk (B, chunk, E) float32 encoder output of one chunk; lens (B,): how many of its frames belong to each stream (default: all;
+        0: the stream is idle and nothing about it changes).  Returns a list of B lists: the tokens this chunk added."""
+        if self.predictor.training or self.joint.training:
+            raise RuntimeError("greedy search is an eval-mode operation (the predictor's dropout would be live)")
+        B, C, S, dev = self.B, self.chunk, self.S, self.dev
+        if tuple(enc_chunk.shape[:2]) != (B, C) or enc_chunk.device != dev:
+            raise ValueError("ChunkGreedySearch.decode wants (%d, %d, E) on %s, got %s on %s" % (B, C, dev, tuple(enc_chunk.shape), enc_chunk.device))
+        self._prepare()
+        need = max(self._host_count) + C * self.n_steps                                 # the most any stream can hold after this chunk
+        if need > S["hyps"].shape[1]:
+            self._grow(need)
+            self._prepare()
+        maybe_live = True
+        if lens is None:
+            S["lens"].fill_(C)
+        elif isinstance(lens, torch.Tensor) and lens.device == dev and dev.type == "cuda":
+            S["lens"].copy_(lens.to(torch.int64).clamp(0, C))                           # stays on the device: the host does not know who is idle
+        else:
+            host = [min(max(int(n), 0), C) for n in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
+            if len(host) != B:
+                raise ValueError("ChunkGreedySearch.decode: %d lens for %d streams" % (len(host), B))
+            maybe_live = any(host)
+            S["lens"].copy_(torch.tensor(host, dtype=torch.int64))
+        if self.fused:
+            import ctypes
+            import cfm
+            self._enc_keep = enc_chunk if (enc_chunk.dtype == torch.float32 and enc_chunk.is_contiguous()) else enc_chunk.float().contiguous()
+            self._desc.enc = self._enc_keep.data_ptr()
+            cfm.check(cfm.lib().cfm_greedy_chunk_begin(ctypes.byref(self._desc), cfm.stream()), "cfm_greedy_chunk_begin")
+            if self.use_graph and self._graph is None:
+                self._capture()
+        else:
+            self._begin_eager(enc_chunk)
+            if self.use_graph and dev.type == "cuda" and self._graph is None:
+                self._capture()
+        self.replays = 0
+        limit = (C * (self.n_steps + 1)) // self.steps_per_replay + 2                   # a lookahead step emits or finishes a stream: fewer than the single-frame bound
+        if maybe_live:
+            for _ in range(limit):
+                if self._graph is not None:
+                    self._graph.replay()
+                else:
+                    self._run_steps()
+                self.replays += 1
+                done = int(S["n_done"]) >= B if self.fused else bool((S["t"] >= S["lens"]).all())      # the one host synchronisation per replay
+                if done:
+                    break
+            else:
+                raise RuntimeError("greedy search did not finish within its step bound")
+        rep = torch.cat([S["count"], S["overflow"].to(torch.int64), S["steps"].to(torch.int64)]).tolist()
+        counts, overflow, self.steps = rep[:B], rep[B], rep[B + 1]
+        if overflow:
+            raise RuntimeError("ChunkGreedySearch: a stream emitted more symbols than the hypothesis buffer holds")
+        self.total_steps += self.steps
+        self.total_replays += self.replays
+        lo, hi = min(self._host_count), max(counts)
+        new = [[] for _ in range(B)]
+        if hi > lo:
+            rows = S["hyps"][:, lo:hi].cpu()
+            for b in range(B):
+                new[b] = rows[b, self._host_count[b] - lo:counts[b] - lo].tolist()
+                self._host_hyps[b].extend(new[b])
+        self._host_count = counts
+        return new

@@ -11,6 +11,9 @@ selects the padded joint).
 `DataParallelTrainer(window_loss_fn=...)` form: ConformerEncoder.forward_window(return_rows=True), CTCDecoder.forward_window over the row matrix,
 the predictor ONCE for the window (label matrices padded to the window's longest with ignore_id; the LSTM is causal, so what a micro-batch's rows
 read does not change), and TransducerJoint.forward_window, whose packed lattice spans every micro-batch's valid cells.
+
+`StreamingRecognizer` is the reference's streaming product -- `Transducer.greedy_search_streaming_app` (model.py:178-199) and
+`greedy_search_streaming_eval` (:126-165): feature windows in, tokens out -- for B streams at once, all state on the device.
 """
 import torch
 import torch.nn as nn
@@ -67,3 +70,49 @@ class TransducerObjective(nn.Module):
             s += B
         loss_rnnt = self.joint.forward_window(rows, groups, blank=self.blank)
         return self.ctc_weight * loss_ctc + self.transducer_weight * loss_rnnt
+
+
+class StreamingRecognizer:
+    """B independent utterances recognised chunk by chunk: `encoder.StreamingBatch` (one batched encoder step, per-stream K/V rings) feeding
+    `greedy.ChunkGreedySearch` (chunk-lookahead greedy search, csrc/greedy.hip) on the same stream -- the encoder's output buffer is the
+    decoder's input, no torch operation and no host decision in between; per step the host reads one "streams done" counter per graph
+    replay of the decoder and, at the end, the new tokens.
+
+    The reference's `greedy_search_streaming_app(chunk, cache, pred_input_step, offset, ...)` maps onto `step`: its encoder caches and
+    offset live in the StreamingBatch, its `pred_input_step` / predictor cache in the ChunkGreedySearch (carry=True).  carry=False is
+    `greedy_search_streaming_eval`, which restarts the predictor from blank / zeros on every chunk (a quirk of the reference, kept).
+
+    step(frames (B, (chunk - 1) * 4 + 7, F), lens=None) -> list of B lists: the tokens the step added.  lens[b]: how many of the chunk's
+    encoder frames belong to stream b's utterance -- fewer than `chunk` for a padded final window, 0 for a stream between utterances
+    (its decoder state does not change; its encoder position still advances: reset it before its next utterance).
+
+    LIMIT: StreamingBatch takes full windows only, so the last lens[b] frames of a padded final window see the padding through the
+    non-causal depthwise convolution, where the reference would run a shorter chunk (model.py:146).  Ragged encoder windows are not
+    supported; causal_conv=True (the opt-in extension) has no such look-ahead."""
+
+    def __init__(self, encoder, predictor, joint, streams, decoding_chunk_size, num_decoding_left_chunks, blank=0, n_steps=64, carry=True, causal_conv=False,
+                 steps_per_replay=8, graph=True):
+        import encoder as encoder_module
+        import greedy
+        if joint.enc_ffn.in_features != encoder.encoder_dim:
+            raise ValueError("StreamingRecognizer: the joint reads %d encoder features, the encoder gives %d" % (joint.enc_ffn.in_features, encoder.encoder_dim))
+        self.B, self.chunk = int(streams), int(decoding_chunk_size)
+        self.encoder_stream = encoder_module.StreamingBatch(encoder, streams, decoding_chunk_size, num_decoding_left_chunks, causal_conv=causal_conv, graph=graph)
+        self.decoder = greedy.ChunkGreedySearch(predictor, joint, streams, decoding_chunk_size, blank=blank, n_steps=n_steps, steps_per_replay=steps_per_replay,
+                                                use_graph=graph, carry=carry, fused=True)
+        self.window = self.encoder_stream.window
+        self.encoder_out = None
+
+    def step(self, frames, lens=None):
+        self.encoder_out = self.encoder_stream.step(frames)                             # (B, chunk, D), overwritten by the next step
+        return self.decoder.decode(self.encoder_out, lens)
+
+    def reset(self, streams=None):
+        """New utterances on the given streams (all by default): encoder position and left context, predictor state and hypotheses."""
+        streams = None if streams is None else list(streams)
+        self.encoder_stream.reset(streams)
+        self.decoder.reset(streams)
+
+    def hyps(self):
+        """Everything emitted per stream since its last reset."""
+        return self.decoder.hyps()

@@ -978,6 +978,39 @@ typedef struct {
 } cfm_greedy_desc;
 int cfm_greedy_step(const cfm_greedy_desc* d, cfm_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Chunk-lookahead greedy search: the decoder of a batched streaming recogniser (reference src/model.py:178-199 / :126-165 around
+ * basic_greedy_search), B <= 64 streams, chunk <= 32 encoder frames per stream and call, everything float32 (csrc/greedy.hip).
+ * The state is cfm_greedy_desc's with two differences: t is the frame index INSIDE the current chunk, lens[b] in [0, chunk] the number
+ * of the chunk's frames that belong to stream b (0: idle, nothing about the stream changes).
+ *   cfm_greedy_chunk_begin  enc_proj = enc_ffn(enc) for the chunk's B * chunk rows (ef_w [J, D], ef_b [J]); t, frame_count <- 0,
+ *                           done / n_done from lens, steps <- 0; carry == 0: token <- blank, h, c <- 0 on the streams with frames.
+ *   cfm_greedy_chunk_step   one lookahead step: the predictor on (token, h, c), the joint for the frames t_b .. lens_b - 1 of every
+ *                           unfinished stream, the first frame whose argmax is not blank emits (none: the stream is done with the
+ *                           chunk).  At most 1 + (most emissions of any stream) steps finish a chunk; n_done == B says so.
+ * Weights as in cfm_greedy_desc.  Scratch: pred [B, P], pp [B, J], act [B * chunk, J] and rows [B * chunk] (compact: only the rows
+ * evaluated this step, row_off / row_cnt [B] per stream, n_rows [1] in all; rows[i] = b * chunk + frame), pmax / pidx [B * chunk, Vp/16]
+ * per compact row.  steps [1] counts the steps that began with a live stream, overflow [1] is set when a stream had more than hyp_cap
+ * symbols to store (the symbol is counted, not stored).  hyps accumulates across chunks: count is not reset by begin. */
+typedef struct {
+    const float* embed;
+    const float* lstm_w[4];
+    const float* lstm_b[4];
+    const float *proj_w, *proj_b, *pf_w, *pf_b, *out_w, *out_b, *ef_w, *ef_b;
+    const float* enc;            /* [B, chunk, D] encoder output (begin only) */
+    float* enc_proj;             /* [B, chunk, J] */
+    int64_t *token, *t, *count, *frame_count, *hyps;
+    const int64_t* lens;
+    float *h, *c, *h_new, *c_new, *pred, *pp, *act, *pmax;
+    int32_t *pidx, *rows, *row_off, *row_cnt, *n_rows, *steps, *overflow;
+    uint8_t* done;
+    int32_t* n_done;
+    int64_t hyp_cap, hyp_ld;
+    int32_t B, chunk, L, E, H, P, J, D, Vp, blank, n_steps, carry;
+} cfm_greedy_chunk_desc;
+int cfm_greedy_chunk_begin(const cfm_greedy_chunk_desc* d, cfm_stream_t stream);
+int cfm_greedy_chunk_step(const cfm_greedy_chunk_desc* d, cfm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
