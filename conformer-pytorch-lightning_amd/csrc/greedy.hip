@@ -1,27 +1,63 @@
-// greedy.hip -- one step of the batched RNN-T greedy search (reference src/model.py:215-269, greedy.py) as SIX launches on f32 weights:
+// greedy.hip -- the device steps of the two batched RNN-T greedy searches (reference src/model.py:215-269, greedy.py) on f32 weights:
+// cfm_greedy_step decides ONE frame per stream and step, cfm_greedy_chunk_begin / cfm_greedy_chunk_step (the streaming recogniser's
+// decoder) all remaining frames of a stream's chunk.  A step of either is the same predictor stage, then its own joint and control stage:
 //
-//   1, 2  LSTM layers   gates = [x | h] . [W_ih | W_hh]^T + (b_ih + b_hh);  c' = sig(f) c + sig(i) tanh(g);  h' = sig(o) tanh(c')
-//                       (layer 0's x is the embedding row of the stream's current token: a gather, no launch of its own)
-//   3     projection    pred = h' . Wp^T + bp                                     (predictor.py:83)
-//   4     joint input   a = tanh(enc_proj[b, t_b] + pred . Wpf^T + bpf)           (joint.py:34-36; enc_ffn was applied to all frames once)
-//   5     joint output  z = a . Wout^T + bout, per 16-class tile and stream the (max, first index) pair                (joint.py:37, model.py:254)
-//   6     control       k = argmax over the tiles; the reference's branches as selects on the per-stream state (model.py:255-267)
+//   predictor (enqueue_predictor, L + 1 launches), shared
+//     LSTM layers   gates = [x | h] . [W_ih | W_hh]^T + (b_ih + b_hh);  c' = sig(f) c + sig(i) tanh(g);  h' = sig(o) tanh(c')
+//                   (layer 0's x is the embedding row of the stream's current token: a gather, no launch of its own)
+//     projection    pred = h' . Wp^T + bp                                         (predictor.py:83)
+//   cfm_greedy_step (3 launches; six in all for L = 2)
+//     joint input   a = tanh(enc_proj[b, t_b] + pred . Wpf^T + bpf)               (joint.py:34-36; enc_ffn was applied to all frames once)
+//     joint output  z = a . Wout^T + bout, per 16-class tile and stream the (max, first index) pair            (joint.py:37, model.py:254)
+//     control       k = argmax over the tiles; the reference's branches as selects on the per-stream state (model.py:255-267)
+//   cfm_greedy_chunk_step (4 launches): pred_ffn, the compact row list, the M-tiled vocabulary product, control across the lookahead --
+//     described at its section below
 //
-// The torch-operation form of the same step (greedy.py) is ~45 small launches; the products here are "skinny": B <= 64 streams against weight
-// matrices of 0.26-2.5 M elements, i.e. one read of 7.5 M f32 weights per step, spread over the chip.  Everything stays f32, so the argmax is
-// the reference's wherever its two best logits are further apart than f32 rounding (DESIGN.md's margin rule): the products run on the f32
-// MFMA (v_mfma_f32_16x16x4_f32: exact f32 multiplies, f32 accumulation) -- one wavefront per 16 output columns, the weight rows as the A
-// operand and up to four 16-stream tiles as B operands, both read as 16-byte pieces straight from memory (the contraction index is walked
-// in the order lane group g holds k = 16 q + 4 g + r, the same for both operands).
+// The torch-operation form of a single-frame step (greedy.py) is ~45 small launches; the predictor's and the single-frame joint's products
+// are "skinny": B <= 64 streams against weight matrices of 0.26-2.5 M elements, i.e. one read of 7.5 M f32 weights per step, spread over
+// the chip.  Everything stays f32, so the argmax is the reference's wherever its two best logits are further apart than f32 rounding
+// (DESIGN.md's margin rule): the products run on the f32 MFMA (v_mfma_f32_16x16x4_f32: exact f32 multiplies, f32 accumulation) -- one
+// wavefront per 16 output columns, the weight rows as the A operand and up to four 16-stream tiles as B operands, both read as 16-byte
+// pieces straight from memory (the contraction index is walked in the order lane group g holds k = 16 q + 4 g + r, the same for both
+// operands).
 //   * the LSTM weight rows are packed [unit][gate] so that the lane that owns output rows 4 g .. 4 g + 3 of a tile holds the four gates
 //     (i, f, g, o) of one hidden unit of one stream: the cell update is lane-local;
 //   * streams that are finished, or whose step produced a blank, keep their state: the candidates (h', c') go to side buffers and the
-//     control launch selects.
+//     control launch selects (commit_state);
+//   * every argmax follows torch.argmax's rule, the lowest index among equal values (take_better), from the lane to the control kernels.
 #include <math.h>
 
 #include "cfm_common.h"
 
 namespace {
+
+// (best, bi) <- (v, i) when v is larger, or equal with the lower index
+__device__ __forceinline__ void take_better(float& best, int& bi, float v, int i) {
+    if (v > best || (v == best && i < bi)) { best = v; bi = i; }
+}
+
+// The best of a 16-class tile of an MFMA product's output, per stream / row: the lane holds classes i0 .. i0 + 3 (v), the tile's other
+// twelve are in the lanes 16, 32 and 48 further on; every lane ends up with the tile's pair.
+__device__ __forceinline__ void tile_argmax(const f32x4 v, int i0, float& best, int& bi) {
+    best = v.x;
+    bi = i0;
+    if (v.y > best) { best = v.y; bi = i0 + 1; }
+    if (v.z > best) { best = v.z; bi = i0 + 2; }
+    if (v.w > best) { best = v.w; bi = i0 + 3; }
+#pragma unroll
+    for (int o = 16; o < 64; o <<= 1) take_better(best, bi, __shfl_xor(best, o, 64), __shfl_xor(bi, o, 64));
+}
+
+// the LSTM's candidate state of this step becomes stream b's state (the step emitted); a: either control kernel's arguments
+template <class Args>
+__device__ __forceinline__ void commit_state(const Args& a, int b, int tid) {
+    for (int i = tid; i < a.L * a.H; i += 256) {
+        const int l = i / a.H, u = i - l * a.H;
+        const int64_t o = ((int64_t)l * a.B + b) * a.H + u;
+        a.h[o] = a.h_new[o];
+        a.c[o] = a.c_new[o];
+    }
+}
 
 struct SkinnyArgs {
     const float* W;          // [N, K] f32 row-major (N % 16 == 0, K % 16 == 0)
@@ -113,18 +149,10 @@ __global__ __launch_bounds__(256) void cfm_skinny_kernel(const SkinnyArgs a) {
                 const f32x4 e = *(const f32x4*)(a.enc + ((int64_t)b * a.T + t) * a.N + n0 + 4 * g);
                 *(f32x4*)(a.out + (int64_t)b * a.ld_out + n0 + 4 * g) = (f32x4){tanhf(e.x + v.x), tanhf(e.y + v.y), tanhf(e.z + v.z), tanhf(e.w + v.w)};
             }
-        } else {                                            // EPI 3: the tile's best class per stream, lowest index on ties
-            float best = v.x;
-            int bi = n0 + 4 * g;
-            if (v.y > best) { best = v.y; bi = n0 + 4 * g + 1; }
-            if (v.z > best) { best = v.z; bi = n0 + 4 * g + 2; }
-            if (v.w > best) { best = v.w; bi = n0 + 4 * g + 3; }
-#pragma unroll
-            for (int o = 16; o < 64; o <<= 1) {
-                const float ob = __shfl_xor(best, o, 64);
-                const int oi = __shfl_xor(bi, o, 64);
-                if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-            }
+        } else {                                            // EPI 3: the tile's best class per stream, [tile, B]
+            float best;
+            int bi;
+            tile_argmax(v, n0 + 4 * g, best, bi);
             if (g == 0 && live) {
                 a.pmax[(int64_t)tile * a.B + b] = best;
                 a.pidx[(int64_t)tile * a.B + b] = bi;
@@ -133,6 +161,52 @@ __global__ __launch_bounds__(256) void cfm_skinny_kernel(const SkinnyArgs a) {
     }
 }
 
+template <int EPI>
+int launch_skinny(const SkinnyArgs& a, hipStream_t s, const char* name) {
+    const int tiles = a.N / 16;
+    CfmProfScope prof(name, s, 2.0 * a.B * (double)a.N * a.K, (double)a.N * a.K * 4);
+    CFM_LAUNCH((cfm_skinny_kernel<EPI>), dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, s, a);
+    return cfm_launch_status(name);
+}
+
+// what cfm_greedy_desc and cfm_greedy_chunk_desc (Desc) have in common: the limits of the skinny launches, the weights, the per-stream
+// state and the scratch both steps use; `who` is the entry point that was called
+template <class Desc>
+int check_common(const Desc* d, const char* who) {
+    CFM_CHECK_ARG(d, "%s: null descriptor", who);
+    CFM_CHECK_ARG(d->B > 0 && d->B <= 64 && d->L >= 1 && d->L <= 4 && d->E % 16 == 0 && d->H % 16 == 0 && d->P % 16 == 0 && d->J % 16 == 0 && d->Vp % 16 == 0 &&
+                      d->n_steps > 0,
+                  "%s: B <= 64 streams, <= 4 LSTM layers, sizes multiples of 16 (B=%d L=%d E=%d H=%d P=%d J=%d Vp=%d)", who, d->B, d->L, d->E, d->H, d->P, d->J, d->Vp);
+    CFM_CHECK_ARG(d->embed && d->proj_w && d->proj_b && d->pf_w && d->pf_b && d->out_w && d->out_b && d->enc_proj && d->token && d->t && d->lens && d->count &&
+                      d->frame_count && d->hyps && d->h && d->c && d->h_new && d->c_new && d->pred && d->act && d->pmax && d->pidx && d->done && d->n_done,
+                  "%s: null pointer", who);
+    return 0;
+}
+
+// The predictor stage of a step of either search: (token, h, c) -> candidates h_new / c_new [L, B, H] and pred [B, P].  n_done: null, or
+// the device counter that turns the launches into empty ones once every stream is finished (SkinnyArgs::n_done).
+template <class Desc>
+int enqueue_predictor(const Desc* d, const int* n_done, hipStream_t s, const char* who) {
+    const int B = d->B, H = d->H;
+    for (int l = 0; l < d->L; ++l) {
+        CFM_CHECK_ARG(d->lstm_w[l] && d->lstm_b[l], "%s: LSTM layer %d has no weights", who, l);
+        SkinnyArgs a = {};
+        a.W = d->lstm_w[l]; a.bias = d->lstm_b[l]; a.B = B; a.N = 4 * H; a.x2 = d->h + (int64_t)l * B * H; a.ld2 = H;
+        if (l == 0) { a.x1 = d->embed; a.x1_rows = d->token; a.ld1 = d->E; a.K1 = d->E; }
+        else { a.x1 = d->h_new + (int64_t)(l - 1) * B * H; a.ld1 = H; a.K1 = H; }
+        a.K = a.K1 + H;
+        a.c_in = d->c + (int64_t)l * B * H; a.h_out = d->h_new + (int64_t)l * B * H; a.c_out = d->c_new + (int64_t)l * B * H; a.n_done = n_done;
+        if (int rc = launch_skinny<1>(a, s, "greedy_lstm")) return rc;
+    }
+    SkinnyArgs a = {};
+    a.W = d->proj_w; a.bias = d->proj_b; a.B = B; a.N = d->P; a.K = a.K1 = H; a.x1 = d->h_new + (int64_t)(d->L - 1) * B * H; a.ld1 = H; a.out = d->pred; a.ld_out = d->P;
+    a.n_done = n_done;
+    return launch_skinny<0>(a, s, "greedy_proj");
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// Single frame (cfm_greedy_step): the joint for the one frame each stream is on, the reference's loop body as selects.
+// ---------------------------------------------------------------------------------------------------------------------------------------
 struct CtlArgs {
     const float* pmax;
     const int* pidx;
@@ -155,19 +229,13 @@ __global__ __launch_bounds__(256) void cfm_greedy_control_kernel(const CtlArgs a
     float best = -INFINITY;
     int bi = 0x7fffffff;
     for (int tl = tid; tl < a.ntiles; tl += 256) {
-        const float v = a.pmax[(int64_t)tl * a.B + b];
-        const int i = a.pidx[(int64_t)tl * a.B + b];
-        if (v > best || (v == best && i < bi)) { best = v; bi = i; }
+        take_better(best, bi, a.pmax[(int64_t)tl * a.B + b], a.pidx[(int64_t)tl * a.B + b]);
     }
     smax[tid] = best;
     sidx[tid] = bi;
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) {
-            const float v = smax[tid + s];
-            const int i = sidx[tid + s];
-            if (v > smax[tid] || (v == smax[tid] && i < sidx[tid])) { smax[tid] = v; sidx[tid] = i; }
-        }
+        if (tid < s) take_better(smax[tid], sidx[tid], smax[tid + s], sidx[tid + s]);
         __syncthreads();
     }
     const bool was_done = a.done[b] != 0;
@@ -192,52 +260,17 @@ __global__ __launch_bounds__(256) void cfm_greedy_control_kernel(const CtlArgs a
         if (dn && !was_done) atomicAdd(a.n_done, 1);
     }
     __syncthreads();
-    if (s_nb) {                                             // a non-blank: the LSTM's new state becomes the stream's state
-        for (int i = tid; i < a.L * a.H; i += 256) {
-            const int l = i / a.H, u = i - l * a.H;
-            const int64_t o = ((int64_t)l * a.B + b) * a.H + u;
-            a.h[o] = a.h_new[o];
-            a.c[o] = a.c_new[o];
-        }
-    }
-}
-
-template <int EPI>
-int launch_skinny(const SkinnyArgs& a, hipStream_t s, const char* name) {
-    const int tiles = a.N / 16;
-    CfmProfScope prof(name, s, 2.0 * a.B * (double)a.N * a.K, (double)a.N * a.K * 4);
-    CFM_LAUNCH((cfm_skinny_kernel<EPI>), dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, s, a);
-    return cfm_launch_status(name);
+    if (s_nb) commit_state(a, b, tid);                      // a non-blank: the LSTM's new state becomes the stream's state
 }
 
 }  // namespace
 
 extern "C" int cfm_greedy_step(const cfm_greedy_desc* d, cfm_stream_t stream) {
-    CFM_CHECK_ARG(d, "cfm_greedy_step: null descriptor");
-    CFM_CHECK_ARG(d->B > 0 && d->B <= 64 && d->L >= 1 && d->L <= 4 && d->E % 16 == 0 && d->H % 16 == 0 && d->P % 16 == 0 && d->J % 16 == 0 && d->Vp % 16 == 0 &&
-                      d->T > 0 && d->n_steps > 0,
-                  "cfm_greedy_step: B <= 64 streams, <= 4 LSTM layers, sizes multiples of 16 (B=%d L=%d E=%d H=%d P=%d J=%d Vp=%d)", d->B, d->L, d->E, d->H, d->P,
-                  d->J, d->Vp);
-    CFM_CHECK_ARG(d->embed && d->proj_w && d->proj_b && d->pf_w && d->pf_b && d->out_w && d->out_b && d->enc_proj && d->token && d->t && d->lens && d->count &&
-                      d->frame_count && d->hyps && d->h && d->c && d->h_new && d->c_new && d->pred && d->act && d->pmax && d->pidx && d->done && d->n_done,
-                  "cfm_greedy_step: null pointer");
+    if (int rc = check_common(d, "cfm_greedy_step")) return rc;
+    CFM_CHECK_ARG(d->T > 0, "cfm_greedy_step: T = %d frames", d->T);
     hipStream_t s = (hipStream_t)stream;
     const int B = d->B, H = d->H;
-    for (int l = 0; l < d->L; ++l) {
-        CFM_CHECK_ARG(d->lstm_w[l] && d->lstm_b[l], "cfm_greedy_step: LSTM layer %d has no weights", l);
-        SkinnyArgs a = {};
-        a.W = d->lstm_w[l]; a.bias = d->lstm_b[l]; a.B = B; a.N = 4 * H; a.x2 = d->h + (int64_t)l * B * H; a.ld2 = H;
-        if (l == 0) { a.x1 = d->embed; a.x1_rows = d->token; a.ld1 = d->E; a.K1 = d->E; }
-        else { a.x1 = d->h_new + (int64_t)(l - 1) * B * H; a.ld1 = H; a.K1 = H; }
-        a.K = a.K1 + H;
-        a.c_in = d->c + (int64_t)l * B * H; a.h_out = d->h_new + (int64_t)l * B * H; a.c_out = d->c_new + (int64_t)l * B * H;
-        if (int rc = launch_skinny<1>(a, s, "greedy_lstm")) return rc;
-    }
-    {
-        SkinnyArgs a = {};
-        a.W = d->proj_w; a.bias = d->proj_b; a.B = B; a.N = d->P; a.K = a.K1 = H; a.x1 = d->h_new + (int64_t)(d->L - 1) * B * H; a.ld1 = H; a.out = d->pred; a.ld_out = d->P;
-        if (int rc = launch_skinny<0>(a, s, "greedy_proj")) return rc;
-    }
+    if (int rc = enqueue_predictor(d, nullptr, s, "cfm_greedy_step")) return rc;
     {
         SkinnyArgs a = {};
         a.W = d->pf_w; a.bias = d->pf_b; a.B = B; a.N = d->J; a.K = a.K1 = d->P; a.x1 = d->pred; a.ld1 = d->P; a.out = d->act; a.ld_out = d->J; a.enc = d->enc_proj;
@@ -264,7 +297,7 @@ extern "C" int cfm_greedy_step(const cfm_greedy_desc* d, cfm_stream_t stream) {
 // remaining frames of a stream's chunk against the one current predictor output and the first non-blank frame is found on the device:
 // a chunk costs at most 1 + (most emissions of any stream) steps instead of frames + emissions.  One step:
 //
-//   1..L   LSTM layers, projection (the skinny launches above), pp = pred_ffn(pred); once every stream is done with the chunk (n_done == B)
+//   pred   the predictor stage (enqueue_predictor with n_done), pp = pred_ffn(pred); once every stream is done with the chunk (n_done == B)
 //          these launches return at once, so the steps a captured graph holds beyond the chunk's last one cost empty launches only
 //   rows   per stream b the frames f = t_b .. lens_b - 1 become rows of a COMPACT activation matrix: act[off_b + i] = tanh(encp[b, t_b + i] + pp[b]);
 //          row_off / row_cnt / n_rows describe it (finished streams contribute no row, so they cost no product)
@@ -358,18 +391,10 @@ __global__ __launch_bounds__(256) void cfm_mtile_kernel(const MTileArgs a) {
             const f32x4 v = acc[j][mt] + bv;
             if constexpr (EPI == 0) {
                 if (m < M) *(f32x4*)(a.out + (int64_t)m * a.ld_out + n0 + 4 * g) = v;
-            } else {                                         // the tile's best class per row, lowest index on ties
-                float best = v.x;
-                int bi = n0 + 4 * g;
-                if (v.y > best) { best = v.y; bi = n0 + 4 * g + 1; }
-                if (v.z > best) { best = v.z; bi = n0 + 4 * g + 2; }
-                if (v.w > best) { best = v.w; bi = n0 + 4 * g + 3; }
-#pragma unroll
-                for (int o = 16; o < 64; o <<= 1) {
-                    const float ob = __shfl_xor(best, o, 64);
-                    const int oi = __shfl_xor(bi, o, 64);
-                    if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-                }
+            } else {                                         // the tile's best class per row, [row, tile]
+                float best;
+                int bi;
+                tile_argmax(v, n0 + 4 * g, best, bi);
                 if (g == 0 && m < M) {
                     a.pmax[(int64_t)m * ntl + nt0 + j] = best;
                     a.pidx[(int64_t)m * ntl + nt0 + j] = bi;
@@ -501,17 +526,9 @@ __global__ __launch_bounds__(256) void cfm_chunk_control_kernel(const ChunkCtlAr
         float best = -INFINITY;
         int bi = 0x7fffffff;
         const int64_t base = (int64_t)(off + r) * a.ntiles;
-        for (int tl = lane; tl < a.ntiles; tl += 64) {
-            const float v = a.pmax[base + tl];
-            const int i = a.pidx[base + tl];
-            if (v > best || (v == best && i < bi)) { best = v; bi = i; }
-        }
+        for (int tl = lane; tl < a.ntiles; tl += 64) take_better(best, bi, a.pmax[base + tl], a.pidx[base + tl]);
 #pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const float ob = __shfl_xor(best, o, 64);
-            const int oi = __shfl_xor(bi, o, 64);
-            if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-        }
+        for (int o = 1; o < 64; o <<= 1) take_better(best, bi, __shfl_xor(best, o, 64), __shfl_xor(bi, o, 64));
         if (lane == 0) s_k[r] = bi;
     }
     __syncthreads();
@@ -546,27 +563,16 @@ __global__ __launch_bounds__(256) void cfm_chunk_control_kernel(const ChunkCtlAr
         s_nb = first >= 0 ? 1 : 0;
     }
     __syncthreads();
-    if (s_nb) {
-        for (int i = tid; i < a.L * a.H; i += 256) {
-            const int l = i / a.H, u = i - l * a.H;
-            const int64_t o = ((int64_t)l * a.B + b) * a.H + u;
-            a.h[o] = a.h_new[o];
-            a.c[o] = a.c_new[o];
-        }
-    }
+    if (s_nb) commit_state(a, b, tid);
 }
 
 int chunk_check(const cfm_greedy_chunk_desc* d, const char* who) {
-    CFM_CHECK_ARG(d, "%s: null descriptor", who);
-    CFM_CHECK_ARG(d->B > 0 && d->B <= 64 && d->L >= 1 && d->L <= 4 && d->chunk >= 1 && d->chunk <= 32 && d->E % 16 == 0 && d->H % 16 == 0 && d->P % 16 == 0 &&
-                      d->J % 16 == 0 && d->D % 16 == 0 && d->Vp % 16 == 0 && d->E > 0 && d->H > 0 && d->P > 0 && d->J > 0 && d->D > 0 && d->Vp > 0 && d->n_steps > 0 &&
-                      d->hyp_cap >= 0 && d->hyp_ld >= d->hyp_cap,
-                  "%s: B <= 64 streams, chunk <= 32, <= 4 LSTM layers, sizes multiples of 16 (B=%d chunk=%d L=%d E=%d H=%d P=%d J=%d D=%d Vp=%d)", who, d->B,
-                  d->chunk, d->L, d->E, d->H, d->P, d->J, d->D, d->Vp);
-    CFM_CHECK_ARG(d->embed && d->proj_w && d->proj_b && d->pf_w && d->pf_b && d->out_w && d->out_b && d->ef_w && d->ef_b && d->enc_proj && d->token && d->t &&
-                      d->lens && d->count && d->frame_count && d->hyps && d->h && d->c && d->h_new && d->c_new && d->pred && d->pp && d->act && d->pmax &&
-                      d->pidx && d->rows && d->row_off && d->row_cnt && d->n_rows && d->steps && d->overflow && d->done && d->n_done,
-                  "%s: null pointer", who);
+    if (int rc = check_common(d, who)) return rc;
+    CFM_CHECK_ARG(d->chunk >= 1 && d->chunk <= 32 && d->D % 16 == 0 && d->E > 0 && d->H > 0 && d->P > 0 && d->J > 0 && d->D > 0 && d->Vp > 0 && d->hyp_cap >= 0 &&
+                      d->hyp_ld >= d->hyp_cap,
+                  "%s: chunk <= 32, sizes positive, D a multiple of 16, 0 <= hyp_cap <= hyp_ld (chunk=%d E=%d H=%d P=%d J=%d D=%d Vp=%d hyp_cap=%lld hyp_ld=%lld)", who,
+                  d->chunk, d->E, d->H, d->P, d->J, d->D, d->Vp, (long long)d->hyp_cap, (long long)d->hyp_ld);
+    CFM_CHECK_ARG(d->ef_w && d->ef_b && d->pp && d->rows && d->row_off && d->row_cnt && d->n_rows && d->steps && d->overflow, "%s: null pointer", who);
     return 0;
 }
 
@@ -591,21 +597,7 @@ extern "C" int cfm_greedy_chunk_step(const cfm_greedy_chunk_desc* d, cfm_stream_
     if (int rc = chunk_check(d, "cfm_greedy_chunk_step")) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int B = d->B, H = d->H;
-    for (int l = 0; l < d->L; ++l) {
-        CFM_CHECK_ARG(d->lstm_w[l] && d->lstm_b[l], "cfm_greedy_chunk_step: LSTM layer %d has no weights", l);
-        SkinnyArgs a = {};
-        a.W = d->lstm_w[l]; a.bias = d->lstm_b[l]; a.B = B; a.N = 4 * H; a.x2 = d->h + (int64_t)l * B * H; a.ld2 = H;
-        if (l == 0) { a.x1 = d->embed; a.x1_rows = d->token; a.ld1 = d->E; a.K1 = d->E; }
-        else { a.x1 = d->h_new + (int64_t)(l - 1) * B * H; a.ld1 = H; a.K1 = H; }
-        a.K = a.K1 + H;
-        a.c_in = d->c + (int64_t)l * B * H; a.h_out = d->h_new + (int64_t)l * B * H; a.c_out = d->c_new + (int64_t)l * B * H; a.n_done = d->n_done;
-        if (int rc = launch_skinny<1>(a, s, "greedy_lstm")) return rc;
-    }
-    {
-        SkinnyArgs a = {};
-        a.W = d->proj_w; a.bias = d->proj_b; a.B = B; a.N = d->P; a.K = a.K1 = H; a.x1 = d->h_new + (int64_t)(d->L - 1) * B * H; a.ld1 = H; a.out = d->pred; a.ld_out = d->P; a.n_done = d->n_done;
-        if (int rc = launch_skinny<0>(a, s, "greedy_proj")) return rc;
-    }
+    if (int rc = enqueue_predictor(d, d->n_done, s, "cfm_greedy_chunk_step")) return rc;
     {
         SkinnyArgs a = {};
         a.W = d->pf_w; a.bias = d->pf_b; a.B = B; a.N = d->J; a.K = a.K1 = d->P; a.x1 = d->pred; a.ld1 = d->P; a.out = d->pp; a.ld_out = d->J; a.n_done = d->n_done;

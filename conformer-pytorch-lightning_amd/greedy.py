@@ -21,93 +21,83 @@ frames once (model.py:250 does it per step).  Everything runs in float32 torch o
 and the predictor are tiny here: one row per stream); the result is the reference's token sequence per stream wherever the two best logits
 of a decision are further apart than f32 rounding (DESIGN.md's margin rule) -- tests compare with the oracle's restatement of the loop, with
 tokens produced by running the reference's predictor / joint modules, and with a float64 restatement of the step (tests/greedy_ref.py).
+
+`BatchedGreedySearch` decides one frame per step, `ChunkGreedySearch` (the streaming recogniser's decoder) all remaining frames of a chunk;
+what they share -- weights key, f32 packs, limits, descriptor weights, LSTM step (`_Head`), graph capture and the replay loop -- is here once.
 """
+import ctypes
+
 import torch
 import torch.nn.functional as F
 
+import cfm
+from cfm import packing
 
-class BatchedGreedySearch:
 
-    def __init__(self, predictor, joint, blank=0, n_steps=64, steps_per_replay=32, use_graph=True, fused=None):
-        """fused: one step = six HIP launches on f32 weights (csrc/greedy.hip, include/cfm.h cfm_greedy_step) instead of ~45 torch operations;
-        default: on an MI355X when the sizes fit (B <= 64 streams, dimensions multiples of 16), the torch-operation form otherwise (and on CPU)."""
+class _Head:
+    """What both searches need of one (predictor, joint) pair: the identity of its weights, their f32 packs for csrc/greedy.hip, the limits
+    of the fused steps, the weight half of either ctypes descriptor and the LSTM step as torch operations."""
+
+    def __init__(self, predictor, joint):
         self.predictor, self.joint = predictor, joint
-        self.blank, self.n_steps, self.steps_per_replay, self.use_graph = int(blank), int(n_steps), int(steps_per_replay), bool(use_graph)
-        self.fused = fused
-        self._graph = None
-        self._key = None
-        self._key_f = None
-        self._key_w = None
-        self._fw = None
+        self._packs = None
 
-    def _weights_key(self):
+    def weights_key(self):
         """Identity of the current weights, as cfm.packing keys its packs: the packing epoch (bumped by updates that bypass torch's version
         counters: trainer.py's flat Adam kernel writes through raw pointers), then address, version counter, device and dtype per parameter."""
-        from cfm import packing
         srcs = list(self.predictor.parameters()) + list(self.joint.parameters())
         return (packing._EPOCH[0],) + tuple((t.data_ptr(), t._version, str(t.device), t.dtype) for t in srcs)
 
-    # -- fused step -----------------------------------------------------------------------------------------------------------------------
-    def _fused_ok(self, B, dev):
+    def fused_limits(self, B, dev, chunk=None):
+        """None when the fused step takes B streams on dev, else what it needs; chunk: the lookahead step's frames (it also applies enc_ffn)."""
         pr, jn = self.predictor, self.joint
-        dims = (pr.embed_size, pr.hidden_size, pr.projection.out_features, jn.pred_ffn.out_features)
-        return (dev.type == "cuda" and B <= 64 and pr.num_layers <= 4 and all(d % 16 == 0 for d in dims) and pr.rnn.bias and
-                jn.pred_ffn.in_features == pr.projection.out_features)
+        dims = (pr.embed_size, pr.hidden_size, pr.projection.out_features, jn.pred_ffn.out_features) + (() if chunk is None else (jn.enc_ffn.in_features,))
+        if (dev.type == "cuda" and B <= 64 and (chunk is None or chunk <= 32) and pr.num_layers <= 4 and all(d % 16 == 0 for d in dims) and pr.rnn.bias and
+                jn.pred_ffn.in_features == pr.projection.out_features):
+            return None
+        return ("the fused greedy step needs a GPU, <= 64 streams, %s<= 4 LSTM layers with biases and dimensions that are multiples of 16 (there is no "
+                "fallback)" % ("" if chunk is None else "chunk <= 32, "))
 
-    def _fused_weights(self, dev):
-        """f32 packs for cfm_greedy_step, rebuilt when the weights change (_weights_key): [W_ih | W_hh] per layer with rows ordered
-        [unit][gate], b_ih + b_hh likewise, the vocabulary projection padded to a multiple of 16 rows (bias -inf there: never the argmax)."""
+    def packs(self, dev, enc_ffn=False):
+        """f32 packs for csrc/greedy.hip, rebuilt when the weights change (weights_key): [W_ih | W_hh] per layer with rows ordered [unit][gate],
+        b_ih + b_hh likewise, the vocabulary projection padded to a multiple of 16 rows (bias -inf there: never the argmax).  enc_ffn: also
+        ef_w / ef_b, which only the chunk-lookahead step reads -- added on request, so that the single-frame search holds no copy of them."""
         pr, jn = self.predictor, self.joint
-        key = (self._weights_key(), str(dev))
-        if self._fw is not None and self._fw[0] == key:
-            return self._fw[1]
-        H = pr.hidden_size
-        perm = (torch.arange(H, device=dev)[:, None] + H * torch.arange(4, device=dev)[None, :]).reshape(-1)     # row u*4 + gate <- gate*H + u
-        W = {"embed": pr.embed.weight.detach().float().contiguous(), "lstm_w": [], "lstm_b": []}
-        for l in range(pr.num_layers):
-            w = torch.cat([getattr(pr.rnn, "weight_ih_l%d" % l).detach().float(), getattr(pr.rnn, "weight_hh_l%d" % l).detach().float()], 1)
-            b = getattr(pr.rnn, "bias_ih_l%d" % l).detach().float() + getattr(pr.rnn, "bias_hh_l%d" % l).detach().float()
-            W["lstm_w"].append(w[perm].contiguous())
-            W["lstm_b"].append(b[perm].contiguous())
-        V = jn.ffn_out.out_features
-        Vp = (V + 15) // 16 * 16
-        ow = torch.zeros((Vp, jn.ffn_out.in_features), device=dev)
-        ow[:V] = jn.ffn_out.weight.detach().float()
-        ob = torch.full((Vp,), float("-inf"), device=dev)
-        ob[:V] = jn.ffn_out.bias.detach().float()
-        W.update(proj_w=pr.projection.weight.detach().float().contiguous(), proj_b=pr.projection.bias.detach().float().contiguous(),
-                 pf_w=jn.pred_ffn.weight.detach().float().contiguous(), pf_b=jn.pred_ffn.bias.detach().float().contiguous(), out_w=ow, out_b=ob, Vp=Vp)
-        self._fw = (key, W)
+        f32 = lambda t: t.detach().float().contiguous()
+        key = (self.weights_key(), str(dev))
+        if self._packs is None or self._packs[0] != key:
+            H = pr.hidden_size
+            perm = (torch.arange(H, device=dev)[:, None] + H * torch.arange(4, device=dev)[None, :]).reshape(-1)     # row u*4 + gate <- gate*H + u
+            W = {"embed": f32(pr.embed.weight), "lstm_w": [], "lstm_b": []}
+            for l in range(pr.num_layers):
+                w = torch.cat([getattr(pr.rnn, "weight_ih_l%d" % l).detach().float(), getattr(pr.rnn, "weight_hh_l%d" % l).detach().float()], 1)
+                b = getattr(pr.rnn, "bias_ih_l%d" % l).detach().float() + getattr(pr.rnn, "bias_hh_l%d" % l).detach().float()
+                W["lstm_w"].append(w[perm].contiguous())
+                W["lstm_b"].append(b[perm].contiguous())
+            V = jn.ffn_out.out_features
+            Vp = (V + 15) // 16 * 16
+            ow = torch.zeros((Vp, jn.ffn_out.in_features), device=dev)
+            ow[:V] = jn.ffn_out.weight.detach().float()
+            ob = torch.full((Vp,), float("-inf"), device=dev)
+            ob[:V] = jn.ffn_out.bias.detach().float()
+            W.update(proj_w=f32(pr.projection.weight), proj_b=f32(pr.projection.bias), pf_w=f32(jn.pred_ffn.weight), pf_b=f32(jn.pred_ffn.bias), out_w=ow, out_b=ob, Vp=Vp)
+            self._packs = (key, W)
+        W = self._packs[1]
+        if enc_ffn and "ef_w" not in W:
+            W.update(ef_w=f32(jn.enc_ffn.weight), ef_b=f32(jn.enc_ffn.bias))
         return W
 
-    def _fused_desc(self, S, W, B, T):
-        import ctypes
-        import cfm
+    def fill_weights(self, d, W):
+        """The weight pointers and the dimensions that come with them, in a cfm.GreedyDesc or cfm.GreedyChunkDesc d."""
         pr, jn = self.predictor, self.joint
-        L, H = pr.num_layers, pr.hidden_size
-        dev = S["t"].device
-        for k, shape, dt in (("h_new", (L, B, H), torch.float32), ("c_new", (L, B, H), torch.float32), ("pred", (B, pr.projection.out_features), torch.float32),
-                             ("act", (B, jn.pred_ffn.out_features), torch.float32), ("pmax", (W["Vp"] // 16, B), torch.float32),
-                             ("pidx", (W["Vp"] // 16, B), torch.int32), ("done8", (B,), torch.uint8), ("n_done", (1,), torch.int32)):
-            if k not in S:
-                S[k] = torch.zeros(shape, dtype=dt, device=dev)
-        d = cfm.GreedyDesc()
-        d.embed = W["embed"].data_ptr()
-        for l in range(L):
+        for l in range(pr.num_layers):
             d.lstm_w[l], d.lstm_b[l] = W["lstm_w"][l].data_ptr(), W["lstm_b"][l].data_ptr()
-        for k in ("proj_w", "proj_b", "pf_w", "pf_b", "out_w", "out_b"):
+        for k in ("embed", "proj_w", "proj_b", "pf_w", "pf_b", "out_w", "out_b") + (("ef_w", "ef_b") if hasattr(d, "ef_w") else ()):
             setattr(d, k, W[k].data_ptr())
-        d.enc_proj = S["enc_proj"].data_ptr()
-        for k in ("token", "t", "count", "frame_count", "hyps", "lens", "h", "c", "h_new", "c_new", "pred", "act", "pmax", "pidx", "n_done"):
-            setattr(d, k, S[k].data_ptr())
-        d.done = S["done8"].data_ptr()
-        d.hyp_cap, d.hyp_ld = int(S["cap"][0]), S["hyps"].shape[1]
-        d.B, d.T, d.L, d.E, d.H, d.P, d.J, d.Vp = B, T, L, pr.embed_size, H, pr.projection.out_features, jn.pred_ffn.out_features, W["Vp"]
-        d.blank, d.n_steps = self.blank, self.n_steps
-        return d
+        d.L, d.E, d.H, d.P, d.J, d.Vp = pr.num_layers, pr.embed_size, pr.hidden_size, pr.projection.out_features, jn.pred_ffn.out_features, W["Vp"]
 
-    # -- one LSTM step on (B, E) inputs with nn.LSTM's parameters (eval mode: no inter-layer dropout); torch.nn.LSTM restated for T = 1
-    def _lstm_step(self, x, h, c):
+    def lstm_step(self, x, h, c):
+        """One LSTM step on (B, E) inputs with nn.LSTM's parameters (eval mode: no inter-layer dropout); torch.nn.LSTM restated for T = 1."""
         rnn = self.predictor.rnn
         hs, cs = [], []
         for l in range(rnn.num_layers):
@@ -121,10 +111,79 @@ class BatchedGreedySearch:
             cs.append(c1)
         return x, torch.stack(hs), torch.stack(cs)
 
+
+def capture_graph(run, S, keys, dev):
+    """run() -- the steps of one replay on the state dict S -- captured in a HIP graph, which is returned; S[k] for k in keys, what run()
+    changes, is left as it was.  The graph holds the addresses of S's tensors, the packs and the descriptor: who replaces one drops it."""
+    snap = {k: S[k].clone() for k in keys}
+    side = torch.cuda.Stream(device=dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        run()                                                                           # warm-up (allocator, lazy init) outside the capture
+    torch.cuda.current_stream(dev).wait_stream(side)
+    for k, v in snap.items():
+        S[k].copy_(v)                                                                   # ... and undone
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        run()
+    for k, v in snap.items():
+        S[k].copy_(v)                                                                   # (capture does not execute, but keep the state explicit)
+    return graph
+
+
+def replay_until_done(graph, run, done, limit):
+    """graph.replay() (no graph: run()) until done(), the one host synchronisation per replay; returns the replays it took, raises at limit."""
+    for n in range(1, limit + 1):
+        if graph is not None:
+            graph.replay()
+        else:
+            run()
+        if done():
+            return n
+    raise RuntimeError("greedy search did not finish within its step bound")
+
+
+class BatchedGreedySearch:
+
+    def __init__(self, predictor, joint, blank=0, n_steps=64, steps_per_replay=32, use_graph=True, fused=None):
+        """fused: one step = six HIP launches on f32 weights (csrc/greedy.hip, include/cfm.h cfm_greedy_step) instead of ~45 torch operations;
+        default: on an MI355X when the sizes fit (B <= 64 streams, dimensions multiples of 16), the torch-operation form otherwise (and on CPU)."""
+        self.predictor, self.joint = predictor, joint
+        self.blank, self.n_steps, self.steps_per_replay, self.use_graph = int(blank), int(n_steps), int(steps_per_replay), bool(use_graph)
+        self.fused = fused
+        self._head = _Head(predictor, joint)
+        self._S = self._graph = self._desc = self._key = self._key_w = None
+
+    # -- fused step -----------------------------------------------------------------------------------------------------------------------
+    def _fused_ok(self, B, dev):
+        return self._head.fused_limits(B, dev) is None
+
+    def _fused_weights(self, dev):
+        return self._head.packs(dev)
+
+    def _fused_desc(self, S, W, B, T):
+        pr, jn = self.predictor, self.joint
+        L, H = pr.num_layers, pr.hidden_size
+        dev = S["t"].device
+        for k, shape, dt in (("h_new", (L, B, H), torch.float32), ("c_new", (L, B, H), torch.float32), ("pred", (B, pr.projection.out_features), torch.float32),
+                             ("act", (B, jn.pred_ffn.out_features), torch.float32), ("pmax", (W["Vp"] // 16, B), torch.float32),
+                             ("pidx", (W["Vp"] // 16, B), torch.int32), ("done8", (B,), torch.uint8), ("n_done", (1,), torch.int32)):
+            if k not in S:
+                S[k] = torch.zeros(shape, dtype=dt, device=dev)
+        d = cfm.GreedyDesc()
+        self._head.fill_weights(d, W)
+        for k in ("enc_proj", "token", "t", "count", "frame_count", "hyps", "lens", "h", "c", "h_new", "c_new", "pred", "act", "pmax", "pidx", "n_done"):
+            setattr(d, k, S[k].data_ptr())
+        d.done = S["done8"].data_ptr()
+        d.hyp_cap, d.hyp_ld = int(S["cap"][0]), S["hyps"].shape[1]
+        d.B, d.T, d.blank, d.n_steps = B, T, self.blank, self.n_steps
+        return d
+
+    # -- one step as torch operations (the CPU form, and the GPU's beyond the fused step's limits) ---------------------------------------------
     def _step(self, S):
         ar = S["ar"]
         e = S["enc_proj"][ar, torch.minimum(S["t"], S["tmax"])]                       # (B, J): the frame each stream is on
-        y, h1, c1 = self._lstm_step(self.predictor.embed(S["token"]), S["h"], S["c"])
+        y, h1, c1 = self._head.lstm_step(self.predictor.embed(S["token"]), S["h"], S["c"])
         pred = self.predictor.projection(y)
         z = self.joint.ffn_out(torch.tanh(e + self.joint.pred_ffn(pred)))
         k = z.argmax(dim=-1)
@@ -142,6 +201,8 @@ class BatchedGreedySearch:
         S["frame_count"].mul_((~adv).to(torch.int64))
         S["done"].copy_(S["t"] >= S["lens"])
 
+    _SNAP = ("t", "count", "frame_count", "hyps", "token", "h", "c", "done")             # what a step changes (capture_graph)
+
     def _state(self, B, T, dev):
         L, H = self.predictor.num_layers, self.predictor.hidden_size
         J = self.joint.enc_ffn.out_features
@@ -152,22 +213,23 @@ class BatchedGreedySearch:
                     hyps=z64(B, cap + 1), cap=torch.full((B,), cap, dtype=torch.int64, device=dev), done=torch.zeros((B,), dtype=torch.bool, device=dev),
                     all_done=torch.zeros((), dtype=torch.bool, device=dev))
 
-    @torch.no_grad()
-    def search(self, enc_out, enc_lens, token=None, state=None):
-        """enc_out (B, T', E) float32 encoder output, enc_lens (B,) valid frames per stream.  token (B,) / state (h, c): the predictor's input
-        and LSTM state to start from (a continued stream, model.py:186-192); default: blank and zeros.  Returns (list of B token lists,
-        (token, (h, c)) to continue with)."""
-        if self.predictor.training or self.joint.training:
-            raise RuntimeError("greedy search is an eval-mode operation (the predictor's dropout would be live)")
-        B, T, _ = enc_out.shape
-        dev = enc_out.device
+    def _prepare(self, enc_out, enc_lens, token, state):
+        """The state to start from, in buffers for (B, T) on enc_out's device.  Descriptor and graph hold addresses: a change of the weights
+        (_Head.weights_key) drops packs, descriptor and graph, a change of the state buffers descriptor and graph."""
+        (B, T, _), dev = enc_out.shape, enc_out.device
+        wkey = self._head.weights_key()
+        if self._key_w != wkey:
+            self._graph, self._desc, self._key_w = None, None, wkey
         key = (B, T, str(dev))
         if self._key != key:
-            self._S, self._graph, self._key, self._key_f = self._state(B, T, dev), None, key, None
-        S = self._S
-        wkey = self._weights_key()
-        if self._key_w != wkey:                                                         # a captured graph holds the parameters' addresses
-            self._graph, self._key_w = None, wkey
+            self._S, self._graph, self._desc, self._key = self._state(B, T, dev), None, None, key
+        why_not = self._head.fused_limits(B, dev)
+        if self.fused and why_not:
+            raise RuntimeError(why_not)
+        S, fused = self._S, why_not is None if self.fused is None else bool(self.fused)
+        self._fused = fused
+        if fused and self._desc is None:
+            self._desc = self._fused_desc(S, self._head.packs(dev), B, T)
         S["enc_proj"].copy_(self.joint.enc_ffn(enc_out.float()))
         S["lens"].copy_(torch.as_tensor(enc_lens, device=dev).to(torch.int64).clamp(0, T))
         for k in ("t", "count", "frame_count", "hyps"):
@@ -178,53 +240,35 @@ class BatchedGreedySearch:
         else:
             S["h"].copy_(state[0]); S["c"].copy_(state[1])
         S["done"].copy_(S["t"] >= S["lens"])
-        fused = self._fused_ok(B, dev) if self.fused is None else bool(self.fused)
         if fused:
-            import ctypes
-            import cfm
-            if not self._fused_ok(B, dev):
-                raise RuntimeError("the fused greedy step needs a GPU, B <= 64 streams and dimensions that are multiples of 16")
-            W = self._fused_weights(dev)
-            if self._key_f != (key, id(W)):
-                self._desc, self._graph, self._key_f = self._fused_desc(S, W, B, T), None, (key, id(W))
             S["done8"].copy_(S["done"].to(torch.uint8))
             S["n_done"].copy_(S["done"].sum().to(torch.int32).reshape(1))
-            desc, lib = self._desc, cfm.lib()
 
-        def run_chunk():
-            if fused:
-                for _ in range(self.steps_per_replay):
-                    cfm.check(lib.cfm_greedy_step(ctypes.byref(desc), cfm.stream()), "cfm_greedy_step")
-                S["all_done"].copy_((S["n_done"] >= B).reshape(()))
-                return
+    def _run_steps(self):
+        S = self._S
+        if self._fused:
+            lib = cfm.lib()
+            for _ in range(self.steps_per_replay):
+                cfm.check(lib.cfm_greedy_step(ctypes.byref(self._desc), cfm.stream()), "cfm_greedy_step")
+            S["all_done"].copy_((S["n_done"] >= S["t"].shape[0]).reshape(()))
+        else:
             for _ in range(self.steps_per_replay):
                 self._step(S)
             S["all_done"].copy_(S["done"].all())
 
+    @torch.no_grad()
+    def search(self, enc_out, enc_lens, token=None, state=None):
+        """enc_out (B, T', E) float32 encoder output, enc_lens (B,) valid frames per stream.  token (B,) / state (h, c): the predictor's input
+        and LSTM state to start from (a continued stream, model.py:186-192); default: blank and zeros.  Returns (list of B token lists,
+        (token, (h, c)) to continue with)."""
+        if self.predictor.training or self.joint.training:
+            raise RuntimeError("greedy search is an eval-mode operation (the predictor's dropout would be live)")
+        self._prepare(enc_out, enc_lens, token, state)
+        (B, T, _), dev, S = enc_out.shape, enc_out.device, self._S
         if self.use_graph and dev.type == "cuda" and self._graph is None:
-            snap = {k: S[k].clone() for k in ("t", "count", "frame_count", "hyps", "token", "h", "c", "done") + (("done8", "n_done") if fused else ())}
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                run_chunk()                                                             # warm-up (allocator, lazy init) outside the capture
-            torch.cuda.current_stream(dev).wait_stream(side)
-            for k, v in snap.items():
-                S[k].copy_(v)                                                           # ... and undone
-            self._graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._graph):
-                run_chunk()
-            for k, v in snap.items():
-                S[k].copy_(v)                                                           # (capture does not execute, but keep the state explicit)
+            self._graph = capture_graph(self._run_steps, S, self._SNAP + (("done8", "n_done") if self._fused else ()), dev)
         limit = (T * (self.n_steps + 1)) // self.steps_per_replay + 2                   # every step emits or advances: at most T (n_steps + 1) of them
-        for _ in range(limit):
-            if self._graph is not None:
-                self._graph.replay()
-            else:
-                run_chunk()
-            if bool(S["all_done"]):                                                     # the one host synchronisation per replay
-                break
-        else:
-            raise RuntimeError("greedy search did not finish within its step bound")
+        replay_until_done(self._graph, self._run_steps, lambda: bool(S["all_done"]), limit)
         counts = S["count"].tolist()
         hyps = S["hyps"].cpu()
         return [hyps[b, :counts[b]].tolist() for b in range(B)], (S["token"].clone(), (S["h"].clone(), S["c"].clone()))
@@ -255,24 +299,20 @@ class ChunkGreedySearch:
         self.blank, self.n_steps, self.steps_per_replay, self.use_graph, self.carry = int(blank), int(n_steps), int(steps_per_replay), bool(use_graph), bool(carry)
         if self.B < 1 or self.chunk < 1 or self.n_steps < 1 or self.steps_per_replay < 1:
             raise ValueError("ChunkGreedySearch: streams, chunk, n_steps and steps_per_replay are positive")
-        self._base = BatchedGreedySearch(predictor, joint, blank=blank, n_steps=n_steps, fused=False)      # the weight key, the f32 packs, the LSTM step
+        self._head = _Head(predictor, joint)
         self.dev = next(predictor.parameters()).device
         self.fused = (self.dev.type == "cuda") if fused is None else bool(fused)
         if self.fused and not self._fused_ok():
-            raise RuntimeError("the fused chunk-lookahead step needs a GPU, <= 64 streams, chunk <= 32, <= 4 LSTM layers and dimensions that are "
-                               "multiples of 16 (there is no fallback)")
+            raise RuntimeError(self._head.fused_limits(self.B, self.dev, self.chunk))
         self.S = self._state(max(1, int(max_tokens) if max_tokens is not None else 2 * self.chunk * self.n_steps))     # decode needs count + chunk * n_steps
         self._host_count = [0] * self.B                                                 # exact after every decode; + chunk * n_steps bounds the next one
         self._host_hyps = [[] for _ in range(self.B)]
-        self._graph = self._desc = self._key_w = self._ew = self._enc_keep = None
+        self._graph = self._desc = self._key_w = self._enc_keep = None
         self.steps = self.replays = self.total_steps = self.total_replays = 0
 
     # -- state -----------------------------------------------------------------------------------------------------------------------------
     def _fused_ok(self):
-        pr, jn = self.predictor, self.joint
-        dims = (pr.embed_size, pr.hidden_size, pr.projection.out_features, jn.pred_ffn.out_features, jn.enc_ffn.in_features)
-        return (self.dev.type == "cuda" and self.B <= 64 and self.chunk <= 32 and pr.num_layers <= 4 and all(d % 16 == 0 for d in dims) and pr.rnn.bias and
-                jn.pred_ffn.in_features == pr.projection.out_features)
+        return self._head.fused_limits(self.B, self.dev, self.chunk) is None
 
     def _state(self, cap):
         pr, jn, B, C, dev = self.predictor, self.joint, self.B, self.chunk, self.dev
@@ -289,36 +329,25 @@ class ChunkGreedySearch:
                      pidx=z32(B * C, Vp // 16), rows=z32(B * C), row_off=z32(B), row_cnt=z32(B), n_rows=z32(1), done8=torch.zeros((B,), dtype=torch.uint8, device=dev))
         return S
 
-    def _fused_desc(self, S, W, EW):
-        import cfm
-        pr, jn = self.predictor, self.joint
+    def _fused_desc(self, S, W):
         d = cfm.GreedyChunkDesc()
-        d.embed = W["embed"].data_ptr()
-        for l in range(pr.num_layers):
-            d.lstm_w[l], d.lstm_b[l] = W["lstm_w"][l].data_ptr(), W["lstm_b"][l].data_ptr()
-        for k in ("proj_w", "proj_b", "pf_w", "pf_b", "out_w", "out_b"):
-            setattr(d, k, W[k].data_ptr())
-        d.ef_w, d.ef_b = EW[0].data_ptr(), EW[1].data_ptr()
+        self._head.fill_weights(d, W)
         for k in ("enc_proj", "token", "t", "count", "frame_count", "hyps", "lens", "h", "c", "h_new", "c_new", "pred", "pp", "act", "pmax", "pidx", "rows", "row_off",
                   "row_cnt", "n_rows", "steps", "overflow", "n_done"):
             setattr(d, k, S[k].data_ptr())
         d.done = S["done8"].data_ptr()
         d.hyp_cap = d.hyp_ld = S["hyps"].shape[1]
-        d.B, d.chunk, d.L, d.E, d.H, d.P, d.J, d.D, d.Vp = (self.B, self.chunk, pr.num_layers, pr.embed_size, pr.hidden_size, pr.projection.out_features,
-                                                            jn.pred_ffn.out_features, jn.enc_ffn.in_features, W["Vp"])
-        d.blank, d.n_steps, d.carry = self.blank, self.n_steps, int(self.carry)
+        d.B, d.chunk, d.D, d.blank, d.n_steps, d.carry = self.B, self.chunk, self.joint.enc_ffn.in_features, self.blank, self.n_steps, int(self.carry)
         return d
 
     def _prepare(self):
-        """Packs, descriptor and graph follow the weights (BatchedGreedySearch._weights_key: packing epoch, address, version, device, dtype)."""
-        wkey = self._base._weights_key()
+        """A change of the weights (_Head.weights_key) drops packs, descriptor and graph; whoever replaces a state buffer (_grow) drops
+        descriptor and graph."""
+        wkey = self._head.weights_key()
         if self._key_w != wkey:
             self._graph, self._desc, self._key_w = None, None, wkey
-            if self.fused:
-                jn = self.joint
-                self._ew = (jn.enc_ffn.weight.detach().float().contiguous(), jn.enc_ffn.bias.detach().float().contiguous())
         if self.fused and self._desc is None:
-            self._desc = self._fused_desc(self.S, self._base._fused_weights(self.dev), self._ew)
+            self._desc = self._fused_desc(self.S, self._head.packs(self.dev, enc_ffn=True))
 
     def _grow(self, need):
         S = self.S
@@ -333,7 +362,7 @@ class ChunkGreedySearch:
         t, lens, fc = S["t"], S["lens"], S["frame_count"]
         live = t < lens
         S["steps"].add_(live.any().to(torch.int32))
-        y, h1, c1 = self._base._lstm_step(pr.embed(S["token"]), S["h"], S["c"])
+        y, h1, c1 = self._head.lstm_step(pr.embed(S["token"]), S["h"], S["c"])
         pp = jn.pred_ffn(pr.projection(y))
         k = jn.ffn_out(torch.tanh(S["enc_proj"] + pp[:, None, :])).argmax(dim=-1)       # (B, chunk): every frame against the one predictor output
         f = S["frames"][None, :]
@@ -368,8 +397,6 @@ class ChunkGreedySearch:
 
     def _run_steps(self):
         if self.fused:
-            import ctypes
-            import cfm
             lib = cfm.lib()
             for _ in range(self.steps_per_replay):
                 cfm.check(lib.cfm_greedy_chunk_step(ctypes.byref(self._desc), cfm.stream()), "cfm_greedy_chunk_step")
@@ -377,23 +404,7 @@ class ChunkGreedySearch:
             for _ in range(self.steps_per_replay):
                 self._step(self.S)
 
-    _SNAP = ("t", "count", "frame_count", "hyps", "token", "h", "c", "steps", "overflow", "n_done")
-
-    def _capture(self):
-        S, dev = self.S, self.dev
-        snap = {k: S[k].clone() for k in self._SNAP + (("done8",) if self.fused else ())}
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            self._run_steps()                                                           # warm-up (allocator, lazy init) outside the capture
-        torch.cuda.current_stream(dev).wait_stream(side)
-        for k, v in snap.items():
-            S[k].copy_(v)                                                               # ... and undone
-        self._graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self._graph):
-            self._run_steps()
-        for k, v in snap.items():
-            S[k].copy_(v)
+    _SNAP = ("t", "count", "frame_count", "hyps", "token", "h", "c", "steps", "overflow", "n_done")             # what a step changes (capture_graph)
 
     # -- public ---------------------------------------------------------------------------------------------------------------------------
     def reset(self, streams=None):
@@ -449,31 +460,16 @@ class ChunkGreedySearch:
             maybe_live = any(host)
             S["lens"].copy_(torch.tensor(host, dtype=torch.int64))
         if self.fused:
-            import ctypes
-            import cfm
             self._enc_keep = enc_chunk if (enc_chunk.dtype == torch.float32 and enc_chunk.is_contiguous()) else enc_chunk.float().contiguous()
             self._desc.enc = self._enc_keep.data_ptr()
             cfm.check(cfm.lib().cfm_greedy_chunk_begin(ctypes.byref(self._desc), cfm.stream()), "cfm_greedy_chunk_begin")
-            if self.use_graph and self._graph is None:
-                self._capture()
         else:
             self._begin_eager(enc_chunk)
-            if self.use_graph and dev.type == "cuda" and self._graph is None:
-                self._capture()
-        self.replays = 0
+        if self.use_graph and dev.type == "cuda" and self._graph is None:
+            self._graph = capture_graph(self._run_steps, S, self._SNAP + (("done8",) if self.fused else ()), dev)
         limit = (C * (self.n_steps + 1)) // self.steps_per_replay + 2                   # a lookahead step emits or finishes a stream: fewer than the single-frame bound
-        if maybe_live:
-            for _ in range(limit):
-                if self._graph is not None:
-                    self._graph.replay()
-                else:
-                    self._run_steps()
-                self.replays += 1
-                done = int(S["n_done"]) >= B if self.fused else bool((S["t"] >= S["lens"]).all())      # the one host synchronisation per replay
-                if done:
-                    break
-            else:
-                raise RuntimeError("greedy search did not finish within its step bound")
+        done = (lambda: int(S["n_done"]) >= B) if self.fused else (lambda: bool((S["t"] >= S["lens"]).all()))
+        self.replays = replay_until_done(self._graph, self._run_steps, done, limit) if maybe_live else 0
         rep = torch.cat([S["count"], S["overflow"].to(torch.int64), S["steps"].to(torch.int64)]).tolist()
         counts, overflow, self.steps = rep[:B], rep[B], rep[B + 1]
         if overflow:

@@ -46,7 +46,8 @@ def test_ctypes_structs_match_c_sizes(cfm, tmp_path):
                "cfm_gemm_tn_desc": cfm.GemmTnDesc, "cfm_attn_bwd_desc": cfm.AttnBwdDesc, "cfm_rowchain_desc": cfm.RowChainDesc,
                "cfm_layer_train_weights": cfm.LayerTrainWeights, "cfm_layer_train_io": cfm.LayerTrainIO, "cfm_layer_train_saved": cfm.LayerTrainSaved,
                "cfm_layer_train_scratch": cfm.LayerTrainScratch, "cfm_layer_train_grads": cfm.LayerTrainGrads,
-               "cfm_ln_bwd_desc": cfm.LnBwdDesc, "cfm_train_group": cfm.TrainGroup, "cfm_ctc_group": cfm.CtcGroup, "cfm_greedy_desc": cfm.GreedyDesc, "cfm_ffn_split_desc": cfm.FfnSplitDesc}
+               "cfm_ln_bwd_desc": cfm.LnBwdDesc, "cfm_train_group": cfm.TrainGroup, "cfm_ctc_group": cfm.CtcGroup, "cfm_greedy_desc": cfm.GreedyDesc, "cfm_ffn_split_desc": cfm.FfnSplitDesc,
+               "cfm_greedy_chunk_desc": cfm.GreedyChunkDesc}
     src = tmp_path / "sz.c"
     src.write_text('#include <stdio.h>\n#include "cfm.h"\nint main(){' +
                    "".join('printf("%s %%zu\\n", sizeof(%s));' % (n, n) for n in structs) + "return 0;}\n")
@@ -55,6 +56,19 @@ def test_ctypes_structs_match_c_sizes(cfm, tmp_path):
     out = dict(line.split() for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
     for n, cls in structs.items():
         assert int(out[n]) == ctypes.sizeof(cls), (n, out[n], ctypes.sizeof(cls))
+
+
+def test_greedy_chunk_desc_field_offsets_match_c(cfm, tmp_path):
+    """The begin-only pointer, the first int32 pointer, the first int64 and the last field of the streaming decoder's descriptor."""
+    fields = ("enc", "pidx", "hyp_cap", "carry")
+    src = tmp_path / "off.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "cfm.h"\nint main(){' +
+                   "".join('printf("%%zu\\n", offsetof(cfm_greedy_chunk_desc, %s));' % f for f in fields) + "return 0;}\n")
+    exe = tmp_path / "off"
+    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    got = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
+    assert got == [getattr(cfm.GreedyChunkDesc, f).offset for f in fields], (fields, got)
+    assert cfm.GreedyChunkDesc.carry.offset + 4 == ctypes.sizeof(cfm.GreedyChunkDesc)         # nothing after it
 
 
 def test_header_is_plain_c(tmp_path):
