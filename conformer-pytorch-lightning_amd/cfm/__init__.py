@@ -196,6 +196,13 @@ class GreedyChunkDesc(ctypes.Structure):
                 [(n, c_i32) for n in ("B", "chunk", "L", "E", "H", "P", "J", "D", "Vp", "blank", "n_steps", "carry")])
 
 
+class FbankDesc(ctypes.Structure):
+    _fields_ = ([(n, c_p) for n in ("samples", "lengths", "feats_length", "carry_in", "carry_out", "fresh_in", "pos_in", "fresh_out", "pos_out", "twiddle", "window",
+                                    "mel_w", "mel_start", "mel_len", "mel_off", "out")] + [("ld", c_i64)] +
+                [(n, c_i32) for n in ("B", "n_cols", "rows", "F", "win", "shift", "padded", "mel_nnz", "samples_i16", "carry_n", "hop")] +
+                [("dither", c_f), ("seed", ctypes.c_uint32)])
+
+
 class FfnSplitDesc(ctypes.Structure):
     _fields_ = [("x", c_p), ("psum", c_p), ("psum_b2", c_p), ("psum_splits", c_i32), ("psum_alpha", c_f), ("ln1_g", c_p), ("ln1_b", c_p), ("ln2_g", c_p),
                 ("ln2_b", c_p), ("rows_out", c_p), ("rows2_out", c_p), ("ln_g", c_p), ("ln_b", c_p), ("w1", c_p), ("b1", c_p), ("N1", c_i32), ("act", c_i32),
@@ -255,6 +262,8 @@ def lib():
         L.cfm_greedy_step.argtypes = [ctypes.POINTER(GreedyDesc), c_p]
         L.cfm_greedy_chunk_begin.argtypes = [ctypes.POINTER(GreedyChunkDesc), c_p]
         L.cfm_greedy_chunk_step.argtypes = [ctypes.POINTER(GreedyChunkDesc), c_p]
+        L.cfm_fbank.argtypes = [ctypes.POINTER(FbankDesc), c_p]
+        L.cfm_fbank_stream.argtypes = [ctypes.POINTER(FbankDesc), c_p]
         L.cfm_ffn_split.argtypes = [ctypes.POINTER(FfnSplitDesc), c_p]
         L.cfm_ffn_split_supported.argtypes = [c_i32, c_i32]
         L.cfm_attention_bwd_force_general.argtypes = [c_i32]
@@ -323,7 +332,7 @@ def lib():
                      "cfm_valid_mask", "cfm_chunk_mask", "cfm_attn_mask", "cfm_cast", "cfm_add_rows",
                      "cfm_encoder_layer_forward", "cfm_ctc_nll", "cfm_joint_act", "cfm_joint_act_bwd", "cfm_rnnt_nll", "cfm_rnnt_grad", "cfm_prof_entry", "cfm_gemm_tn", "cfm_gemm_tn_group", "cfm_attention_bwd",
                      "cfm_layernorm_bwd", "cfm_glu_bwd", "cfm_dwconv_bn_train", "cfm_dwconv_bn_train_bwd", "cfm_col2im_relu_bwd", "cfm_conv1_wgrad",
-                     "cfm_ctc_nll_train_groups", "cfm_ctc_grad", "cfm_adam_step", "cfm_adam_clip_step", "cfm_sumsq", "cfm_dropout_rows", "cfm_dropout_mask", "cfm_pack_matrices", "cfm_pack_vectors", "cfm_greedy_step", "cfm_greedy_chunk_begin", "cfm_greedy_chunk_step", "cfm_ffn_split", "cfm_ffn_split_supported", "cfm_layernorm_bwd_fused", "cfm_dwconv_bn_train_bwd_acc",
+                     "cfm_ctc_nll_train_groups", "cfm_ctc_grad", "cfm_adam_step", "cfm_adam_clip_step", "cfm_sumsq", "cfm_dropout_rows", "cfm_dropout_mask", "cfm_pack_matrices", "cfm_pack_vectors", "cfm_greedy_step", "cfm_greedy_chunk_begin", "cfm_greedy_chunk_step", "cfm_fbank", "cfm_fbank_stream", "cfm_ffn_split", "cfm_ffn_split_supported", "cfm_layernorm_bwd_fused", "cfm_dwconv_bn_train_bwd_acc",
                      "cfm_encoder_train_forward", "cfm_encoder_train_backward", "cfm_stream_prep", "cfm_kv_ring_write", "cfm_stream_advance", "cfm_dwconv_causal_bn_silu", "cfm_conv_cache_update"):
             getattr(L, name).restype = ctypes.c_int
         _lib = L

@@ -6,7 +6,7 @@ import torch
 
 import cfm as _c
 
-__all__ = ["stream_prep", "stream_advance", "dwconv_causal_bn_silu", "conv_cache_update", "dropout_rows", "dropout_mask", "set_deterministic", "gemm_tn", "gemm_tn_group", "layernorm_bwd", "glu_bwd", "dwconv_bn_train", "dwconv_bn_train_bwd", "col2im_relu_bwd", "conv1_wgrad", "attention_bwd",
+__all__ = ["fbank", "fbank_stream", "stream_prep", "stream_advance", "dwconv_causal_bn_silu", "conv_cache_update", "dropout_rows", "dropout_mask", "set_deterministic", "gemm_tn", "gemm_tn_group", "layernorm_bwd", "glu_bwd", "dwconv_bn_train", "dwconv_bn_train_bwd", "col2im_relu_bwd", "conv1_wgrad", "attention_bwd",
            "ctc_nll_train_groups", "ctc_grad", "rnnt_nll", "rnnt_grad", "joint_act_bwd", "rnnt_nll_packed", "joint_act_packed", "joint_act_packed_bwd", "ffn_split", "adam_step", "adam_clip_step", "sumsq", "scratch_stats",
            "gemm", "ffn_fused", "ffn_fused_supported", "rowchain", "rowchain_supported", "rowchain_pair_supported", "layernorm", "attention", "kv_cache_pack", "dwconv_bn_silu", "conv1_relu", "conv1_relu_mma_supported", "conv12_relu", "conv12_supported", "ctc_nll", "joint_act", "valid_mask", "chunk_mask",
            "attn_mask_combine", "cast", "add_rows", "scratch", "prof_enable", "prof_reset", "prof_table", "as_u8_mask"]
@@ -968,3 +968,46 @@ def conv_cache_update(x, cache, ktaps):
     _c.require_hip(x, cache)
     B, T, D = x.shape
     _c.check(_c.lib().cfm_conv_cache_update(_c.ptr(x), _c.dt_code(x), _c.ptr(cache), B, T, D, ktaps, _c.stream()), "cfm_conv_cache_update")
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# log-mel filter bank (include/cfm.h cfm_fbank / cfm_fbank_stream, csrc/fbank.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+def _fbank_desc(samples, tables, out, win, shift, padded, dither, seed):
+    """tables: (twiddle f64, window f64, mel weights f32, start, length, offset int32) on the device (packing.fbank_tables / pack_mel_banks)."""
+    tw, wnd, mw, ms, ml, mo = tables
+    _c.require_hip(samples, out, *tables)
+    if samples.dim() != 2 or samples.stride(1) != 1 or samples.dtype not in (torch.int16, torch.float32):
+        raise ValueError("cfm.fbank: samples must be (B, N) int16 or float32 with unit inner stride, got %s %s" % (tuple(samples.shape), samples.dtype))
+    B, rows, F = out.shape
+    if out.dtype != torch.float32 or not out.is_contiguous() or B != samples.shape[0] or F != ms.numel():
+        raise ValueError("cfm.fbank: out must be contiguous f32 (B, rows, %d), got %s %s" % (ms.numel(), tuple(out.shape), out.dtype))
+    d = _c.FbankDesc()
+    d.samples, d.ld, d.n_cols, d.samples_i16 = _c.ptr(samples), samples.stride(0) if B > 1 else max(samples.stride(0), samples.shape[1]), samples.shape[1], int(samples.dtype == torch.int16)
+    d.twiddle, d.window, d.mel_w, d.mel_start, d.mel_len, d.mel_off, d.mel_nnz = _c.ptr(tw), _c.ptr(wnd), _c.ptr(mw), _c.ptr(ms), _c.ptr(ml), _c.ptr(mo), mw.numel()
+    d.out, d.B, d.rows, d.F, d.win, d.shift, d.padded = _c.ptr(out), B, rows, F, win, shift, padded
+    d.dither, d.seed = float(dither), int(seed) & 0xFFFFFFFF
+    return d
+
+
+def fbank(samples, lengths, tables, out, feats_length, win, shift, padded, dither=0.0, seed=0):
+    """Offline: samples (B, N) int16 | f32, lengths int32 [B] -> out f32 (B, rows, F) (rows past an item's frame count zero), feats_length int32 [B]."""
+    d = _fbank_desc(samples, tables, out, win, shift, padded, dither, seed)
+    _c.require_hip(lengths, feats_length)
+    if lengths.dtype != torch.int32 or feats_length.dtype != torch.int32 or lengths.numel() != d.B or feats_length.numel() != d.B:
+        raise ValueError("cfm.fbank: lengths and feats_length are int32 [B]")
+    d.lengths, d.feats_length = _c.ptr(lengths), _c.ptr(feats_length)
+    _c.check(_c.lib().cfm_fbank(ctypes.byref(d), _c.stream()), "cfm_fbank")
+
+
+def fbank_stream(samples, state_in, state_out, tables, out, win, shift, padded, hop, dither=0.0, seed=0):
+    """Streaming: state_* = (carry f32 [B, carry_n], fresh int32 [B], pos int32 [B]); in is read, out is written (the caller swaps them)."""
+    d = _fbank_desc(samples, tables, out, win, shift, padded, dither, seed)
+    (ci, fi, pi), (co, fo, po) = state_in, state_out
+    _c.require_hip(ci, fi, pi, co, fo, po)
+    for t, dt in ((ci, torch.float32), (co, torch.float32), (fi, torch.int32), (fo, torch.int32), (pi, torch.int32), (po, torch.int32)):
+        if t.dtype != dt or not t.is_contiguous() or t.shape[0] != d.B:
+            raise ValueError("cfm.fbank_stream: state is (carry f32 [B, n], fresh int32 [B], pos int32 [B]), contiguous")
+    d.carry_in, d.fresh_in, d.pos_in, d.carry_out, d.fresh_out, d.pos_out = (_c.ptr(t) for t in (ci, fi, pi, co, fo, po))
+    d.carry_n, d.hop = ci.shape[1], hop
+    _c.check(_c.lib().cfm_fbank_stream(ctypes.byref(d), _c.stream()), "cfm_fbank_stream")

@@ -498,3 +498,54 @@ def pack_joint_train(mod, prec):
         return Packed(enc=lin(mod.enc_ffn), pred=lin(mod.pred_ffn), out=lin(mod.ffn_out, Vp), V=V, Vp=Vp)
     params = [mod.enc_ffn.weight, mod.enc_ffn.bias, mod.pred_ffn.weight, mod.pred_ffn.bias, mod.ffn_out.weight, mod.ffn_out.bias]
     return _train_cache(mod).get(params, prec, build)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# log-mel filter bank tables (csrc/fbank.hip): host float64, no module, no cache -- fbank.KaldiFbank builds them once
+# ----------------------------------------------------------------------------------------------------------------------
+def mel_banks_f64(num_mel_bins, padded, sample_frequency, low_freq=20.0):
+    """torchaudio.compliance.kaldi.get_mel_banks (high_freq = Nyquist, no VTLN) in float64: (num_mel_bins, padded // 2); the Nyquist bin,
+    whose weight is 0, is left out.  mel(f) = 1127 ln(1 + f / 700); triangle b has edges mel(low) + (b, b + 1, b + 2) delta."""
+    import math
+    lo = 1127.0 * math.log(1.0 + low_freq / 700.0)
+    hi = 1127.0 * math.log(1.0 + 0.5 * sample_frequency / 700.0)
+    delta = (hi - lo) / (num_mel_bins + 1)
+    b = torch.arange(num_mel_bins, dtype=torch.float64).unsqueeze(1)
+    left, center, right = lo + b * delta, lo + (b + 1.0) * delta, lo + (b + 2.0) * delta
+    mel = (1127.0 * torch.log(1.0 + sample_frequency / padded * torch.arange(padded // 2, dtype=torch.float64) / 700.0)).unsqueeze(0)
+    return torch.clamp(torch.min((mel - left) / (center - left), (right - mel) / (right - center)), min=0.0)
+
+
+def pack_mel_banks(num_mel_bins, padded, sample_frequency, low_freq=20.0):
+    """The banks rounded to f32, sparse: per mel bin its first FFT bin, its run length and the offset of its run in one contiguous weight
+    vector -> (weights f32 [nnz], start, length, offset int32 [num_mel_bins]) on the host.  A triangle is one run of non-zero weights."""
+    dense = mel_banks_f64(num_mel_bins, padded, sample_frequency, low_freq).to(torch.float32)
+    weights, start, length, offset = [], [], [], []
+    for row in dense:
+        nz = torch.nonzero(row).flatten()
+        if nz.numel() == 0:
+            raise ValueError("pack_mel_banks: a mel bin covers no FFT bin (%d bins over %d FFT bins at %g Hz)" % (num_mel_bins, padded // 2, sample_frequency))
+        k0, k1 = int(nz[0]), int(nz[-1]) + 1
+        start.append(k0)
+        length.append(k1 - k0)
+        offset.append(sum(length[:-1]))
+        weights.append(row[k0:k1])
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32)      # noqa: E731
+    return torch.cat(weights).contiguous(), i32(start), i32(length), i32(offset)
+
+
+def unpack_mel_banks(weights, start, length, offset, n_fft_bins):
+    """Dense (num_mel_bins, n_fft_bins) f32 view of pack_mel_banks' result (tests, documentation)."""
+    dense = torch.zeros((start.numel(), n_fft_bins), dtype=torch.float32)
+    for b, (k0, n, o) in enumerate(zip(start.tolist(), length.tolist(), offset.tolist())):
+        dense[b, k0:k0 + n] = weights[o:o + n]
+    return dense
+
+
+def fbank_tables(win, padded):
+    """(twiddle f64 [padded, 2] = (cos, -sin)(2 pi k / padded), povey window f64 [win] = hann(win, periodic=False) ** 0.85), host float64."""
+    import math
+    k = torch.arange(padded, dtype=torch.float64) * (2.0 * math.pi / padded)
+    twiddle = torch.stack([torch.cos(k), -torch.sin(k)], dim=1).contiguous()
+    window = torch.hann_window(win, periodic=False, dtype=torch.float64).pow(0.85)
+    return twiddle, window

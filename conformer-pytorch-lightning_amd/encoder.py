@@ -382,7 +382,8 @@ class StreamingBatch:
       * causal_conv=True is the OPT-IN extension (not in the reference, which has no causal convolution and ignores cnn_cache):
         every block's depthwise conv becomes causal with a (K-1)-frame left context per stream.  Off = the reference's arithmetic.
 
-    step(frames (B, (chunk-1)*4+7, F)) -> (B, chunk, D) in a buffer the next step overwrites.  reset(streams) starts new utterances."""
+    step(frames (B, (chunk-1)*4+7, F)) -> (B, chunk, D) in a buffer the next step overwrites.  reset(streams) starts new utterances.
+    input_buffer() / step_resident(): the same step on windows a producer wrote into the step's own input buffer."""
 
     def __init__(self, encoder, streams, decoding_chunk_size, num_decoding_left_chunks, causal_conv=False, graph=True):
         if num_decoding_left_chunks < 0:
@@ -469,9 +470,23 @@ class StreamingBatch:
         if tuple(frames.shape[:2]) != (self.B, self.window):
             raise ValueError("StreamingBatch.step wants (%d, %d, F) frames, got %s" % (self.B, self.window, tuple(frames.shape)))
         cfm.require_hip(frames)
+        self.input_buffer(frames.shape[2]).copy_(frames)
+        return self.step_resident()
+
+    def input_buffer(self, num_features=None):
+        """The (B, window, F) f32 buffer the step reads.  A producer on the same stream (fbank.StreamingFbank) writes the windows here and calls
+        step_resident(): no feature tensor and no copy in between."""
         if self.x is None:
-            self.x = torch.empty_like(frames, dtype=torch.float32).contiguous()
-        self.x.copy_(frames)
+            if num_features is None:
+                raise ValueError("StreamingBatch.input_buffer: the feature size is not known before the first step")
+            self.x = torch.empty((self.B, self.window, int(num_features)), dtype=torch.float32, device=self.dev)
+        elif num_features is not None and int(num_features) != self.x.shape[2]:
+            raise ValueError("StreamingBatch: %d features per frame, the stream was started with %d" % (num_features, self.x.shape[2]))
+        return self.x
+
+    def step_resident(self):
+        """step() on what input_buffer() holds."""
+        self.input_buffer()
         self.steps += 1
         if max(self._host_off) + self.chunk > self.pe.size(0):
             self._grow_table(max(self._host_off) + self.chunk)

@@ -13,7 +13,7 @@ the predictor ONCE for the window (label matrices padded to the window's longest
 read does not change), and TransducerJoint.forward_window, whose packed lattice spans every micro-batch's valid cells.
 
 `StreamingRecognizer` is the reference's streaming product -- `Transducer.greedy_search_streaming_app` (model.py:178-199) and
-`greedy_search_streaming_eval` (:126-165): feature windows in, tokens out -- for B streams at once, all state on the device.
+`greedy_search_streaming_eval` (:126-165): feature windows (step) or waveform blocks (step_audio) in, tokens out -- for B streams at once, all state on the device.
 """
 import torch
 import torch.nn as nn
@@ -82,6 +82,9 @@ class StreamingRecognizer:
     offset live in the StreamingBatch, its `pred_input_step` / predictor cache in the ChunkGreedySearch (carry=True).  carry=False is
     `greedy_search_streaming_eval`, which restarts the predictor from blank / zeros on every chunk (a quirk of the reference, kept).
 
+    step_audio(samples, lens=None) is step() from the waveform: fbank.StreamingFbank writes the feature windows straight into the encoder step's
+    input buffer (fbank_args: its num_mel_bins, dither, seed, ...; the defaults are the reference's settings without dither).
+
     step(frames (B, (chunk - 1) * 4 + 7, F), lens=None) -> list of B lists: the tokens the step added.  lens[b]: how many of the chunk's
     encoder frames belong to stream b's utterance -- fewer than `chunk` for a padded final window, 0 for a stream between utterances
     (its decoder state does not change; its encoder position still advances: reset it before its next utterance).
@@ -91,7 +94,7 @@ class StreamingRecognizer:
     supported; causal_conv=True (the opt-in extension) has no such look-ahead."""
 
     def __init__(self, encoder, predictor, joint, streams, decoding_chunk_size, num_decoding_left_chunks, blank=0, n_steps=64, carry=True, causal_conv=False,
-                 steps_per_replay=8, graph=True):
+                 steps_per_replay=8, graph=True, fbank_args=None):
         import encoder as encoder_module
         import greedy
         if joint.enc_ffn.in_features != encoder.encoder_dim:
@@ -102,16 +105,30 @@ class StreamingRecognizer:
                                                 use_graph=graph, carry=carry, fused=True)
         self.window = self.encoder_stream.window
         self.encoder_out = None
+        self.audio, self.fbank_args = None, dict(fbank_args or {})      # step_audio's fbank.StreamingFbank (made on first use) and its keyword arguments
 
     def step(self, frames, lens=None):
         self.encoder_out = self.encoder_stream.step(frames)                             # (B, chunk, D), overwritten by the next step
         return self.decoder.decode(self.encoder_out, lens)
 
+    def step_audio(self, samples, lens=None):
+        """step() from the waveform (the reference's deploy.py preprocess_stream + greedy_search_streaming_app): samples (B, n) int16 | float32 on
+        the int16 scale, left-aligned -- fbank.StreamingFbank.n_next new samples per stream, n_first for a stream that was reset (and then for
+        the call: the others read their first n_next).  One fbank launch writes the feature windows into the encoder step's input buffer."""
+        if self.audio is None:
+            import fbank
+            self.audio = fbank.StreamingFbank(self.B, self.chunk, self.encoder_stream.dev, **self.fbank_args)
+        self.audio.step(samples, self.encoder_stream.input_buffer(self.audio.fbank.num_mel_bins))
+        self.encoder_out = self.encoder_stream.step_resident()
+        return self.decoder.decode(self.encoder_out, lens)
+
     def reset(self, streams=None):
-        """New utterances on the given streams (all by default): encoder position and left context, predictor state and hypotheses."""
+        """New utterances on the given streams (all by default): audio carry, encoder position and left context, predictor state and hypotheses."""
         streams = None if streams is None else list(streams)
         self.encoder_stream.reset(streams)
         self.decoder.reset(streams)
+        if self.audio is not None:
+            self.audio.reset(streams)
 
     def hyps(self):
         """Everything emitted per stream since its last reset."""

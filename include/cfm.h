@@ -1011,6 +1011,46 @@ typedef struct {
 int cfm_greedy_chunk_begin(const cfm_greedy_chunk_desc* d, cfm_stream_t stream);
 int cfm_greedy_chunk_step(const cfm_greedy_chunk_desc* d, cfm_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Kaldi-compatible log-mel filter bank, waveform in, feature rows out, one launch (csrc/fbank.hip): the reference's
+ * kaldi.fbank(waveform * (1 << 15), num_mel_bins, frame_length, frame_shift, dither, energy_floor=0, sample_frequency) of
+ * src/processor.py:175-193 (compute_fbank) and src/deploy.py:106-146 (preprocess, preprocess_stream) with torchaudio's defaults for the rest.
+ * Row r of item b is frame pos + r of its signal: samples [shift r, shift r + win) of the item's sample sequence, minus their mean,
+ * pre-emphasised (0.97), times `window`, zero-padded to `padded` (a power of two, 8 .. 512), |rfft|^2, the sparse mel product, log(max(., f32 eps)).
+ *   samples   [B, ld] int16 (samples_i16 != 0) or f32, on the int16 scale
+ *   twiddle   f64 [padded, 2] = (cos, -sin)(2 pi k / padded);  window f64 [win]  (host tables, float64: the kernel calls no sin / cos for them)
+ *   mel_w     f32 [mel_nnz <= 512] packed weights;  mel bin b = sum_i power[mel_start[b] + i] * mel_w[mel_off[b] + i], i < mel_len[b]
+ *   out       f32 [B, rows, F]
+ *   dither    > 0 adds dither * n(seed, b, pos + r, j), standard normal from cfm_hash32 through Box-Muller: a frame's noise depends on its
+ *             ABSOLUTE index, not on how the audio was cut into calls
+ * cfm_fbank (offline, deploy.py preprocess): the sequence of item b is samples[b, 0 .. lengths[b]) (clamped to n_cols), pos = 0; rows at or beyond its frame
+ *   count 1 + (n - win) / shift (0 when n < win) are written as zeros (the reference's padding() pads features with 0), feats_length [B] receives the count.
+ * cfm_fbank_stream (deploy.py preprocess_stream, for B streams): every row is computed.  A stream with fresh_in[b] != 0 reads its `n_first` = (rows - 1) shift + win
+ *   samples from samples[b] and has pos = 0; any other stream reads carry_in[b, 0 .. carry_n) followed by `n_next` = n_first - carry_n samples of samples[b],
+ *   and pos = pos_in[b].  carry_out[b] <- the last carry_n samples of that sequence, fresh_out[b] <- 0, pos_out[b] <- pos + hop.  The *_in and *_out
+ *   buffers must not alias (the caller swaps them between calls).  n_cols >= n_next; the caller, who knows which streams it reset, passes n_first
+ *   columns when one is fresh (a read at or past n_cols yields 0, never memory beyond the row). */
+typedef struct {
+    const void* samples;
+    const int32_t* lengths;      /* offline */
+    int32_t* feats_length;       /* offline, may be null */
+    const float* carry_in;       /* streaming: f32 [B, carry_n] */
+    float* carry_out;
+    const int32_t *fresh_in, *pos_in;
+    int32_t *fresh_out, *pos_out;
+    const double* twiddle;
+    const double* window;
+    const float* mel_w;
+    const int32_t *mel_start, *mel_len, *mel_off;
+    float* out;
+    int64_t ld;
+    int32_t B, n_cols, rows, F, win, shift, padded, mel_nnz, samples_i16, carry_n, hop;
+    float dither;
+    uint32_t seed;
+} cfm_fbank_desc;
+int cfm_fbank(const cfm_fbank_desc* d, cfm_stream_t stream);
+int cfm_fbank_stream(const cfm_fbank_desc* d, cfm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
