@@ -270,6 +270,9 @@ def lib():
         L.cfm_attention_bwd_force_general.restype = None
         L.cfm_set_cin_merge.argtypes = [c_i32]
         L.cfm_set_cin_merge.restype = c_i32
+        L.cfm_set_conv12_tile.argtypes = [c_i32]
+        L.cfm_set_conv12_tile.restype = c_i32
+        L.cfm_conv12_plan.argtypes = [c_i64, c_i32, c_i32, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32)]
         L.cfm_dwconv_bn_train_bwd_acc.argtypes = [c_p, c_i32, c_p, c_p, c_p, c_i32, c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p]
         L.cfm_layernorm_bwd_fused.argtypes = [ctypes.POINTER(LnBwdDesc), c_p]
         L.cfm_conv12_relu.argtypes = [c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p]

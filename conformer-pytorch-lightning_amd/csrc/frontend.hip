@@ -20,8 +20,14 @@
 //   * (measured: a third weight buffer with two K tiles in flight -- asm-issued LDS-DMA, counted waits -- does NOT help the 96-row tail tile: 48 vs
 //     45 us.  Its K step is not waiting for the DMA but paying fixed per-step costs that do not shrink with the tile: the 32 KB weight tile
 //     through the CU's vector-memory path, 8 + 6 fragment reads per wavefront, the barrier; ~1.25 us per step whatever is in flight.)
-//   * FM = 16-row fragments per wavefront along M: tiles of 32 FM rows.  The host runs whole rounds of 256-row tiles and gives the last
-//     partial round to a smaller FM so that it, too, is one workgroup per CU (the two-kernel path did the same with 128 x 128 tiles).
+//   * FM = 16-row fragments per wavefront along M: tiles of 32 FM rows.  The host (conv12_plan) prices two plans by rounds x K steps x time
+//     per step and takes the cheaper: whole rounds of 256-row tiles with the last partial round on a smaller FM so that it, too, is one
+//     workgroup per CU (the two-kernel path did the same with 128 x 128 tiles), or every row on 320-row tiles (FM = 10) in one launch --
+//     config 2's 151 392 rows are 2.31 rounds of 256-row tiles but 1.85 of 320-row tiles: two rounds, no tail launch.
+//   * FM = 10 sits at both limits of a CU: 2 x (40 KB A + 32 KB W) + the 16 KB table = 160 KB of LDS, and 160 accumulator registers of the
+//     256 a lane has at two wavefronts per SIMD.  So it reads the A fragments of a kk step in two groups of five (the second under the first
+//     group's MFMAs; the order of MFMAs per accumulator is untouched, so the bits are), loads the output bias after the K loop, and splits
+//     its last four of 20 production units into channel halves over two wavefronts each: 2.5 units per wavefront instead of 3 and 2.
 #include <string>
 #include <type_traits>
 
@@ -54,6 +60,9 @@ __global__ __launch_bounds__(512) void cfm_conv12_kernel(const Conv12Args g) {
     constexpr int FN = 4;
     constexpr int NU = 2 * FM;                               // 16-row production units of an A tile
     constexpr int U = (NU + 7) / 8;                          // units per wavefront
+    constexpr bool HALF = NU > 8 && NU % 8 == 4;             // FM = 10: the last four units go as channel halves to two wavefronts each
+    constexpr int G = FM > 8 ? 5 : FM;                       // A fragments of a kk step held at once
+    static_assert(FM % G == 0, "A-fragment groups");
     __shared__ u32x4 smem[2 * BUF + 1024];                   // two K tiles + conv1's weight fragments (u32x2 [<= 8 slabs][4][64 lanes])
     u32x2* const w1tab = (u32x2*)(smem + 2 * BUF);
 
@@ -106,7 +115,7 @@ __global__ __launch_bounds__(512) void cfm_conv12_kernel(const Conv12Args g) {
     int xbase[U], fcol[U];
 #pragma unroll
     for (int ui = 0; ui < U; ++ui) {
-        const int u = wave + 8 * ui;
+        const int u = HALF && ui == U - 1 ? 8 * ui + (wave & 3) : wave + 8 * ui;
         int m = m0 + u * 16 + l15;
         m = m < g.M ? m : g.M - 1;
         const int per_b = g.T2 * g.F2;
@@ -156,6 +165,18 @@ __global__ __launch_bounds__(512) void cfm_conv12_kernel(const Conv12Args g) {
         }
 #pragma unroll
         for (int ui = 0; ui < U; ++ui) {
+            if (HALF && ui == U - 1) {                        // unit 8 ui + (wave & 3), fragments 2 h and 2 h + 1: the same MFMAs, the same chunk
+                const int u = 8 * ui + (wave & 3), h = wave >> 2;
+                f32x4 a[2];
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    a[j] = HT::mfma(h ? wf[2 + j] : wf[j], xcur[ui], zero4);
+                    a[j].x = fmaxf(a[j].x, 0.f); a[j].y = fmaxf(a[j].y, 0.f); a[j].z = fmaxf(a[j].z, 0.f); a[j].w = fmaxf(a[j].w, 0.f);
+                }
+                const int row = u * 16 + l15;
+                As[row * 8 + ((2 * kg + h) ^ ((row >> 1) & 7))] = pack8<HT>(a[0], a[1]);
+                continue;
+            }
             const int u = wave + 8 * ui;
             if (u < NU) {                                     // wave-uniform
                 f32x4 a[4];
@@ -185,16 +206,21 @@ __global__ __launch_bounds__(512) void cfm_conv12_kernel(const Conv12Args g) {
 #pragma unroll
         for (int kk = 0; kk < BK / 32; ++kk) {
             const int c = (kk * 4 + kg) ^ sw;
-            u32x4 af[FM], wf[FN];
+            u32x4 af[G], wf[FN];
 #pragma unroll
             for (int j = 0; j < FN; ++j) wf[j] = Ws[(w_row + j * 16) * 8 + c];
 #pragma unroll
-            for (int i = 0; i < FM; ++i) af[i] = As[(a_row + i * 16) * 8 + c];
+            for (int i = 0; i < G; ++i) af[i] = As[(a_row + i * 16) * 8 + c];
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-            for (int i = 0; i < FM; ++i)
+            for (int i0 = 0; i0 < FM; i0 += G) {              // FM > 8: the next group's fragments are read under this group's MFMAs
 #pragma unroll
-                for (int j = 0; j < FN; ++j) acc[i][j] = HT::mfma(wf[j], af[i], acc[i][j]);
+                for (int i = 0; i < G; ++i) {
+#pragma unroll
+                    for (int j = 0; j < FN; ++j) acc[i0 + i][j] = HT::mfma(wf[j], af[i], acc[i0 + i][j]);
+                    if (i0 + G < FM) af[i] = As[(a_row + (i0 + G + i) * 16) * 8 + c];
+                }
+            }
             __builtin_amdgcn_s_setprio(0);
         }
     };
@@ -208,10 +234,12 @@ __global__ __launch_bounds__(512) void cfm_conv12_kernel(const Conv12Args g) {
     produce(0, 0);
     const int q4 = kg * 4;
     f32x4 bias_r[FN];
+    if constexpr (FM <= 8) {                                 // FM = 10 has no 16 registers to carry it through the K loop: it loads it after the loop
 #pragma unroll
-    for (int j = 0; j < FN; ++j) {
-        const int col = n0 + wc * 64 + j * 16 + q4;
-        bias_r[j] = col + 3 < N ? *(const f32x4*)(g.b2 + col) : zero4;
+        for (int j = 0; j < FN; ++j) {
+            const int col = n0 + wc * 64 + j * 16 + q4;
+            bias_r[j] = col + 3 < N ? *(const f32x4*)(g.b2 + col) : zero4;
+        }
     }
     __syncthreads();
     for (int tap = 0; tap < 9; ++tap) {
@@ -238,6 +266,13 @@ __global__ __launch_bounds__(512) void cfm_conv12_kernel(const Conv12Args g) {
     }
 
     // ---- epilogue: + bias, ReLU, 8-byte stores (a lane owns 4 consecutive output channels of a row)
+    if constexpr (FM > 8) {
+#pragma unroll
+        for (int j = 0; j < FN; ++j) {
+            const int col = n0 + wc * 64 + j * 16 + q4;
+            bias_r[j] = col + 3 < N ? *(const f32x4*)(g.b2 + col) : zero4;
+        }
+    }
     const int col0 = n0 + wc * 64 + q4;
 #pragma unroll
     for (int i = 0; i < FM; ++i) {
@@ -261,26 +296,62 @@ int launch(const Conv12Args& a, hipStream_t s, const char* name) {
     return cfm_launch_status(name);
 }
 
+// ---- host tile choice.  A launch costs CONV12_LAUNCH + rounds (tiles / CUs, rounded up) x steps (9 C / 64 K tiles of one 256-wide N half) x
+// (CONV12_STEP_FIXED + CONV12_STEP_PER_FM FM) us: a least-squares line through one- and two-round launches of FM = 2, 3, 4, 8, 10 on MI355X
+// (us per K step 0.83, 1.17, 1.37, 2.20, 2.64).  It prices config 2's three plans at 207 / 195 / 243 us against 209 / 193 / 241 measured.
+constexpr double CONV12_LAUNCH = 4.0, CONV12_STEP_FIXED = 0.46, CONV12_STEP_PER_FM = 0.219;
+
+struct Conv12Plan {
+    int fm_main, fm_tail;                                    // 0 = no such launch
+    int64_t rows_main;                                        // rows 0 .. rows_main - 1 on fm_main tiles, the rest on fm_tail tiles
+};
+
+double conv12_cost(int64_t rows, int fm, int cus, int C) {
+    if (rows <= 0) return 0.0;
+    const int64_t tiles = (rows + 32 * fm - 1) / (32 * fm);
+    return CONV12_LAUNCH + (double)((tiles + cus - 1) / cus) * (9.0 * C / 64.0) * (CONV12_STEP_FIXED + CONV12_STEP_PER_FM * fm);
+}
+
+Conv12Plan conv12_plan(int64_t M, int C, int cus, int force_fm) {
+    cus /= (C + 255) / 256;                                   // C = 512: two workgroups (halves of N) per row tile
+    if (cus < 1) cus = 1;
+    if (force_fm > 0) return Conv12Plan{force_fm, 0, M};
+    // the split: whole rounds of 256-row tiles, then the remainder as ONE round of the smallest tile that fits it on the chip's CUs
+    const int64_t whole = (M / (256 * (int64_t)cus)) * cus;  // 256-row tiles in whole rounds
+    const int64_t rest = M - whole * 256;
+    Conv12Plan split{whole > 0 ? 8 : 0, 0, whole * 256};
+    if (rest > 128 * (int64_t)cus) split = Conv12Plan{8, 0, M};  // more than half a round left: it goes on 256-row tiles as well
+    else if (rest > 0) split.fm_tail = rest <= 64 * (int64_t)cus ? 2 : rest <= 96 * (int64_t)cus ? 3 : 4;
+    const double c_split = conv12_cost(split.rows_main, split.fm_main, cus, C) + conv12_cost(M - split.rows_main, split.fm_tail, cus, C);
+    // every row on 320-row tiles in one launch: fewer rounds where the row count sits just under a whole number of them
+    if (conv12_cost(M, 10, cus, C) < c_split) return Conv12Plan{10, 0, M};
+    return split;
+}
+
+int g_conv12_tile = 0;                                       // cfm_set_conv12_tile: 0 = by the plan
+
 template <typename HT>
-int run(Conv12Args a, int cus, hipStream_t s, const char* nm_big, const char* nm_tail) {
-    // whole rounds of 256-row tiles, then the remainder as ONE round of the smallest tile that fits it on the chip's CUs
-    const int M = a.M;
-    cus /= (a.C + 255) / 256;                                 // C = 512: two workgroups (halves of N) per row tile
-    const int whole = (M / (256 * cus)) * cus;               // 256-row tiles in whole rounds
-    int rest = M - whole * 256;
-    if (rest > 0 && rest > 128 * cus) {                       // more than half a round left: it goes on 256-row tiles as well
-        a.m_begin = 0; a.m_end = M;
-        return launch<HT, 8>(a, s, nm_big);
+int launch_fm(int fm, const Conv12Args& a, hipStream_t s, const char* const* nm) {   // nm: profile scopes of the 256-row, tail and 320-row launches
+    switch (fm) {
+        case 2: return launch<HT, 2>(a, s, nm[1]);
+        case 3: return launch<HT, 3>(a, s, nm[1]);
+        case 4: return launch<HT, 4>(a, s, nm[1]);
+        case 8: return launch<HT, 8>(a, s, nm[0]);
+        case 10: return launch<HT, 10>(a, s, nm[2]);
     }
-    if (whole > 0) {
-        a.m_begin = 0; a.m_end = whole * 256;
-        if (int rc = launch<HT, 8>(a, s, nm_big)) return rc;
+    return cfm_fail(CFM_ERR_ARG, "cfm_conv12_relu: no such tile");
+}
+
+template <typename HT>
+int run(Conv12Args a, int cus, hipStream_t s, const char* const* nm) {
+    const Conv12Plan p = conv12_plan(a.M, a.C, cus, g_conv12_tile);
+    if (p.fm_main) {
+        a.m_begin = 0; a.m_end = (int)p.rows_main;
+        if (int rc = launch_fm<HT>(p.fm_main, a, s, nm)) return rc;
     }
-    if (rest > 0) {
-        a.m_begin = whole * 256; a.m_end = M;
-        if (rest <= 64 * cus) return launch<HT, 2>(a, s, nm_tail);
-        if (rest <= 96 * cus) return launch<HT, 3>(a, s, nm_tail);
-        return launch<HT, 4>(a, s, nm_tail);
+    if (p.fm_tail) {
+        a.m_begin = (int)p.rows_main; a.m_end = a.M;
+        return launch_fm<HT>(p.fm_tail, a, s, nm);
     }
     return CFM_OK;
 }
@@ -313,6 +384,21 @@ extern "C" int cfm_conv12_relu(const float* x, const float* w1, const float* b1,
     a.x = x; a.w1 = w1; a.b1 = b1; a.W = (const u16*)w2; a.b2 = b2; a.y = (u16*)y; a.cm_mean = cmvn_mean; a.cm_istd = cmvn_istd;
     a.T = T; a.F = F; a.C = C; a.T2 = T2; a.F2 = F2; a.M = (int)M; a.m_begin = 0; a.m_end = (int)M;
     hipStream_t s = (hipStream_t)stream;
-    if (y_dtype == CFM_BF16) return run<BF16>(a, num_cus(), s, "conv12_bf16_256", "conv12_bf16_tail");
-    return run<F16>(a, num_cus(), s, "conv12_f16_256", "conv12_f16_tail");
+    static const char* const nm_bf16[3] = {"conv12_bf16_256", "conv12_bf16_tail", "conv12_bf16_320"};
+    static const char* const nm_f16[3] = {"conv12_f16_256", "conv12_f16_tail", "conv12_f16_320"};
+    if (y_dtype == CFM_BF16) return run<BF16>(a, num_cus(), s, nm_bf16);
+    return run<F16>(a, num_cus(), s, nm_f16);
+}
+
+extern "C" int32_t cfm_set_conv12_tile(int32_t fm) {
+    const int prev = g_conv12_tile;
+    if (fm == 0 || fm == 2 || fm == 3 || fm == 4 || fm == 8 || fm == 10) g_conv12_tile = fm;
+    return prev;
+}
+
+extern "C" int cfm_conv12_plan(int64_t M, int32_t C, int32_t cus, int32_t* fm_main, int32_t* fm_tail) {
+    CFM_CHECK_ARG(M > 0 && cus > 0 && fm_main && fm_tail && C >= 64, "cfm_conv12_plan: bad argument");
+    const Conv12Plan p = conv12_plan(M, C, cus, 0);
+    *fm_main = p.fm_main; *fm_tail = p.fm_tail;
+    return CFM_OK;
 }

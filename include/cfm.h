@@ -368,6 +368,14 @@ int cfm_conv1_relu_mma(const float* x, const float* w, const float* bias, void* 
 int cfm_conv12_supported(int32_t C, int32_t y_dtype);
 int cfm_conv12_relu(const float* x, const float* w1, const float* b1, const void* w2, const float* b2, void* y, int32_t y_dtype, int32_t B,
                     int32_t T, int32_t F, int32_t C, const float* cmvn_mean, const float* cmvn_istd, cfm_stream_t stream);
+/* The row tiles of cfm_conv12_relu are 32 fm rows (fm = 2, 3, 4, 8, 10).  cfm_conv12_plan: the host's choice for M output rows, C channels
+ * and a chip of `cus` compute units, without touching a device -- rows on fm_main tiles first (whole rounds of 256-row tiles, or every row
+ * on 256- or 320-row tiles in one launch; 0 = no such launch), the remaining rows as one round of fm_tail tiles (0 = none); by a cost
+ * model of rounds x K steps x time per step of each tile (csrc/frontend.hip).  cfm_set_conv12_tile(fm): every row on tiles of 32 fm rows
+ * whatever the plan says (0 = by the plan, the default; another value leaves the setting alone); returns the previous setting.  Every
+ * tile gives the same bits; the switch is host-side and exists for tests and measurements. */
+int cfm_conv12_plan(int64_t M, int32_t C, int32_t cus, int32_t* fm_main, int32_t* fm_tail);
+int32_t cfm_set_conv12_tile(int32_t fm);
 
 /* ------------------------------------------------------------------------------------------------
  * Masks -- integer/bool, bit-exact with the reference.
