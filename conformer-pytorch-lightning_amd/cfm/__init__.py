@@ -225,6 +225,8 @@ class LayerIO(ctypes.Structure):
                 ("next_w", c_p), ("next_x_out", c_p), ("macaron_done", c_i32)]
 
 
+ROUTES = ("GENERAL", "FUSED_FFN", "CHAIN", "CHAIN_NEXT", "CHAIN_NEXT_CIN", "FFSPLIT", "PAIR")     # include/cfm.h cfm_route, by value (cfm_encoder_layer_route)
+
 _lib = None
 _lock = threading.Lock()
 
@@ -283,6 +285,9 @@ def lib():
         L.cfm_add_rows.argtypes = [c_p, c_p, c_i64, c_i32, c_i32, c_p]
         L.cfm_encoder_layer_forward.argtypes = [ctypes.POINTER(LayerWeights), ctypes.POINTER(LayerScratch),
                                                 ctypes.POINTER(LayerIO), c_p, c_p, c_i32, c_p, c_p, c_p]
+        L.cfm_encoder_layer_route.argtypes = [ctypes.POINTER(LayerWeights), ctypes.POINTER(LayerScratch), ctypes.POINTER(LayerIO), c_p, c_p]
+        L.cfm_encoder_layer_route.restype = c_i32
+        L.cfm_ffsplit_max_rows.restype = c_i32
         L.cfm_ctc_nll.argtypes = [c_p, c_i64, c_i32, c_i32, c_i32, c_p, c_p, c_i32, c_p, c_p, c_p, c_p]
         L.cfm_joint_act.argtypes = [c_p, c_i64, c_p, c_i64, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p]
         L.cfm_joint_act_bwd.argtypes = [c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p]

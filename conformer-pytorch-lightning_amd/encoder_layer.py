@@ -12,6 +12,7 @@ directly.  The child modules (feedforward / attention / convolution) only own th
 same kernels op by op.
 """
 import ctypes
+import functools
 
 import torch
 import torch.nn as nn
@@ -24,18 +25,21 @@ from feedforward import PositionwiseFeedForwardModule, _inference_only
 
 _ABSENT = torch.ones((0, 0, 0), dtype=torch.bool)
 PAIR_MAX_ROWS = 4096       # include/cfm.h CFM_PAIR_MAX_ROWS: the pair-split feed-forward of the D = 512 row chains (one workgroup per CU up to 128 row tiles)
-SPLIT_FFN_FEW_ROWS = True  # STREAMING steps of <= 1536 rows run their feed-forwards split over FF/256 workgroups per row tile (csrc/ffnsplit.hip).  Only
+SPLIT_FFN_FEW_ROWS = True  # STREAMING steps of <= cfm_ffsplit_max_rows() (1536) rows run their feed-forwards split over FF/256 workgroups per row tile (csrc/ffnsplit.hip).  Only
 # the streaming entry points ask for it (split_ffn=True): a whole-utterance forward keeps one algorithm for every batch size, so that a batch shard
 # reproduces the batch bit for bit
 
 
-import os as _os
-_SPLIT_MAX_ROWS = int(_os.environ.get("CFM_FFSPLIT_MAX_ROWS", "1536"))     # the library reads the same variable (csrc/encoder.cpp): experiments only
+@functools.lru_cache(maxsize=None)
+def _split_max_rows():
+    """The library's row limit (cfm_ffsplit_max_rows: the one reader of CFM_FFSPLIT_MAX_ROWS), asked on first use and not at import, when the library
+    may not be built yet."""
+    return cfm.lib().cfm_ffsplit_max_rows()
 
 
 def split_rows(M, D, FF):
-    """True where cfm_encoder_layer_forward takes the split feed-forward when given the slabs (cfm.h CFM_FFSPLIT_MAX_ROWS)."""
-    return M <= _SPLIT_MAX_ROWS and D == 256 and FF % 256 == 0 and FF > 0        # measured crossover (scripts/bench_small_batch.py): 996 rows -21 %, 1992 rows +4 %
+    """True where cfm_encoder_layer_forward takes CFM_ROUTE_FFSPLIT when given the slabs."""
+    return M <= _split_max_rows() and D == 256 and FF % 256 == 0 and FF > 0
 
 
 CHAIN_BLOCKS = True        # the final chain of block i also runs the macaron chain of block i+1 (one launch and one residual round trip less)

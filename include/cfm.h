@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CFM_VERSION 305 /* 0.3.5: removed the attention input stage of the conv-in chain (cfm_rowchain_desc.att_*, cfm_layer_scratch.vt and its row stride) and the transposed-value output of the macaron chain's tail that fed it (three cfm_rowchain_desc fields); psum_out chains take no head. 0.3.4: removed cfm_ctc_nll_train (cfm_ctc_nll_train_groups is the training forward), cfm_ctc_grad requires beta (alpha is no longer overwritten), removed cfm_rnnt_desc.sweep / cfm_rnnt_packed_desc.sweep (the LDS recursion is the only one). 0.3.3: removed cfm_encoder_layer_train_forward / _backward (the stack entry points run a single block), cfm_ffn_train_forward / _supported, cfm_ffn_train_desc, cfm_pack_ffn_fragments, cfm_layer_train_weights.*_w1f / *_w2f, cfm_layer_train_io.B / T / attn_mask / am_sb / am_sq / side_stream and cfm_encoder_train_backward's n_scratch. 0.3.2 (additive, same number): packed RNN-T lattices (cfm_lattice, cfm_rnnt_packed_desc, cfm_rnnt_packed_nll / _grad, cfm_joint_act_packed / _bwd). 0.3.2 (additive, same number): the RNN-T loss (cfm_rnnt_desc, cfm_rnnt_nll, cfm_rnnt_grad) and the transducer joint's activation backward (cfm_joint_act_bwd). 0.3.2: cfm_rowchain_desc.cin_* (the conv-in chain as the input stage of the next launch). 0.3.1: row chains at D = 512, cfm_rowchain_desc.psum_out / psum_in (feed-forward split over workgroup pairs), cfm_conv12_relu at C = 512. 0.3.0: row groups in the train entry points (cfm_train_group, cfm_layer_train_io.n_groups), cfm_gemm_tn_group + deferred weight gradients, cfm_encoder_train_forward / _backward (the whole stack from one host call). 0.2.3: cfm_ffn_split, cfm_layer_scratch.psum (the feed-forward split over FF for few rows). 0.2.2: cfm_ctc_nll_train / cfm_ctc_grad take a beta buffer (both recursions in one launch); GEMM tile ids 9-11 (K groups). 0.2.1: fused front-end (cfm_conv12_relu); attention stage of the conv-in chain (cfm_rowchain_desc.att_*, cfm_layer_scratch.vt). 0.2.0: training entry points */
+#define CFM_VERSION 306 /* 0.3.6 (additive): cfm_route, cfm_encoder_layer_route (the route cfm_encoder_layer_forward would take, asked on the host), cfm_ffsplit_max_rows. 0.3.5: removed the attention input stage of the conv-in chain (cfm_rowchain_desc.att_*, cfm_layer_scratch.vt and its row stride) and the transposed-value output of the macaron chain's tail that fed it (three cfm_rowchain_desc fields); psum_out chains take no head. 0.3.4: removed cfm_ctc_nll_train (cfm_ctc_nll_train_groups is the training forward), cfm_ctc_grad requires beta (alpha is no longer overwritten), removed cfm_rnnt_desc.sweep / cfm_rnnt_packed_desc.sweep (the LDS recursion is the only one). 0.3.3: removed cfm_encoder_layer_train_forward / _backward (the stack entry points run a single block), cfm_ffn_train_forward / _supported, cfm_ffn_train_desc, cfm_pack_ffn_fragments, cfm_layer_train_weights.*_w1f / *_w2f, cfm_layer_train_io.B / T / attn_mask / am_sb / am_sq / side_stream and cfm_encoder_train_backward's n_scratch. 0.3.2 (additive, same number): packed RNN-T lattices (cfm_lattice, cfm_rnnt_packed_desc, cfm_rnnt_packed_nll / _grad, cfm_joint_act_packed / _bwd). 0.3.2 (additive, same number): the RNN-T loss (cfm_rnnt_desc, cfm_rnnt_nll, cfm_rnnt_grad) and the transducer joint's activation backward (cfm_joint_act_bwd). 0.3.2: cfm_rowchain_desc.cin_* (the conv-in chain as the input stage of the next launch). 0.3.1: row chains at D = 512, cfm_rowchain_desc.psum_out / psum_in (feed-forward split over workgroup pairs), cfm_conv12_relu at C = 512. 0.3.0: row groups in the train entry points (cfm_train_group, cfm_layer_train_io.n_groups), cfm_gemm_tn_group + deferred weight gradients, cfm_encoder_train_forward / _backward (the whole stack from one host call). 0.2.3: cfm_ffn_split, cfm_layer_scratch.psum (the feed-forward split over FF for few rows). 0.2.2: cfm_ctc_nll_train / cfm_ctc_grad take a beta buffer (both recursions in one launch); GEMM tile ids 9-11 (K groups). 0.2.1: fused front-end (cfm_conv12_relu); attention stage of the conv-in chain (cfm_rowchain_desc.att_*, cfm_layer_scratch.vt). 0.2.0: training entry points */
 
 typedef void* cfm_stream_t;
 
@@ -446,11 +446,11 @@ typedef struct {
 
 typedef struct {
     void *xn, *hid, *qkv, *pos, *ctx, *glu, *dw; /* activation-dtype scratch: [M,D],[M,FF],[M,3D],[R,D],[M,D],[M,D],[M,D] */
-    float* psum;   /* optional f32 [psum_splits, M, D]: partial slabs of the split feed-forward (cfm_ffn_split).  Given with psum_splits >= FF/256,
-                      blocks of at most CFM_FFSPLIT_MAX_ROWS rows at D = 256 run their two feed-forwards split over FF/256 workgroups per 32-row
-                      tile instead of inside the row chains (few rows: a streaming step); null = never.  At D = 512 (cfm_rowchain_pair_supported) with
-                      psum_splits >= 3 and at most CFM_PAIR_MAX_ROWS rows, both feed-forwards run split over workgroup PAIRS (two slabs + the parked rows of
-                      the final chain): 125 row tiles alone leave half of the CUs idle */
+    float* psum;   /* optional f32 [psum_splits, M, D]: partial slabs of a split feed-forward; null = the block never takes CFM_ROUTE_FFSPLIT / _PAIR.
+                      CFM_ROUTE_FFSPLIT: psum_splits >= FF/256, at most cfm_ffsplit_max_rows() rows at D = 256 (cfm_ffn_split_supported) -- both feed-forwards
+                      split over FF/256 workgroups per 32-row tile instead of inside the row chains (few rows: a streaming step).  CFM_ROUTE_PAIR:
+                      psum_splits >= 3, at most CFM_PAIR_MAX_ROWS rows at D = 512 (cfm_rowchain_pair_supported) -- both feed-forwards split over workgroup
+                      PAIRS (two slabs + the parked rows of the final chain): 125 row tiles alone leave half of the CUs idle */
     int32_t psum_splits;
 } cfm_layer_scratch;
 #define CFM_PAIR_MAX_ROWS 4096    /* 128 row tiles x 2 halves = one workgroup per CU */
@@ -471,8 +471,8 @@ typedef struct {
     const float* attn_cache;  /* f32 [B,H,Tc,2dk] or NULL */
     int32_t cache_T;
     float* new_cache;         /* f32 [B,H,Tc+T,2dk] or NULL (not materialised) */
-    const float *after_g, *after_b; /* optional, chain path only: ALSO write LN(x_out; after_g, after_b) to after_out (f32 [B*T,D]) -- the
-                                       encoder's after_norm fused into the last block's final chain */
+    const float *after_g, *after_b; /* optional: ALSO write LN(x_out; after_g, after_b) to after_out (f32 [B*T,D]) -- the encoder's after_norm, fused into the
+                                       last block's final launch on CFM_ROUTE_CHAIN / _FFSPLIT, one more LayerNorm launch on the other routes; not with next_w */
     float* after_out;
     /* Batched streaming with PER-STREAM state (csrc/stream.hip; beyond the reference): when kv_ring is set, this layer's keys /
      * values live in a ring buffer f32 [B,H,ring_T,2dk] (frame f of a stream in slot f mod ring_T); the step's T new frames of stream b are
@@ -489,24 +489,45 @@ typedef struct {
     int32_t pos_shared;       /* 1: the pos_rows == Tk positional rows are the SAME for every batch item (batched streaming step: all
                                  streams at one offset).  Beyond the reference, whose forward_chunk only works at batch 1
                                  (attention.py:78-88); per item it equals that batch-1 call. */
-    /* Chaining consecutive blocks (chain path only): the final chain of this block and the macaron chain of the NEXT block are both
+    /* Chaining consecutive blocks (CFM_ROUTE_CHAIN_NEXT / _CHAIN_NEXT_CIN; needs every chain pack, else next_w is not read): the final chain of this block and the macaron chain of the NEXT block are both
      * row-local, so one launch can run them back to back on rows that stay in registers (cfm_rowchain_desc.s2_*): one launch, one f32
      * read and one f32 write of the residual stream less per block.
      *   next_w != NULL : after norm_final, run the next block's macaron feed-forward + norm_mha + fused QKV projection as well; the
      *                    next block's post-macaron residual goes to next_x_out (f32 [B*T,D]) and its q|k|v rows to s->qkv.  x_out then
      *                    does NOT receive this block's output (it is left holding the residual stream before the feed-forward).
      *   macaron_done   : this block's macaron chain already ran in the previous block's call: x_out holds its residual, s->qkv its
-     *                    projections; x_in is not read. */
+     *                    projections; x_in is not read.  A modifier of the three CFM_ROUTE_CHAIN* routes (it excludes _FFSPLIT and _PAIR); an error elsewhere. */
     const cfm_layer_weights* next_w;
     float* next_x_out;
     int32_t macaron_done;
 } cfm_layer_io;
 
+/* The launch sequence of one block.  Every argument is checked and ONE route chosen before anything is launched (csrc/encoder.cpp select_route).
+ * chains = all eight fragment-major chain packs (ffm_w1f, ffm_w2n, ff_w1f, ff_w2n, qkv_wf, out_wf, pw1_wf, pw2_wf), a 16-bit act_dtype and
+ * cfm_rowchain_supported(D, FF).  Without chains: FUSED_FFN when the *_w1f / *_w2f packs are there, D in {144, 256}, FF % 32 == 0 and FF <= 2048, else
+ * GENERAL.  With chains, the first that applies: PAIR and FFSPLIT (cfm_layer_scratch.psum; neither with macaron_done or next_w, FFSPLIT also needs pw2_w
+ * and 15 taps; D = 512 against D = 256, so they exclude each other), CHAIN_NEXT_CIN (next_w, cfm_set_cin_merge on), CHAIN_NEXT (next_w), CHAIN. */
+typedef enum {
+    CFM_ROUTE_GENERAL = 0,        /* separate GEMMs, LayerNorm and depthwise kernels: 17 launches */
+    CFM_ROUTE_FUSED_FFN = 1,      /* ... with each feed-forward as one cfm_ffn_fused launch */
+    CFM_ROUTE_CHAIN = 2,          /* the three row chains (cfm_rowchain) around the attention: 4 launches */
+    CFM_ROUTE_CHAIN_NEXT = 3,     /* ... the final chain also runs the next block's macaron chain: 3 per block */
+    CFM_ROUTE_CHAIN_NEXT_CIN = 4, /* ... and the conv-in chain as the input stage of that launch: 2 per block */
+    CFM_ROUTE_FFSPLIT = 5,        /* both feed-forwards split over FF (cfm_ffn_split) */
+    CFM_ROUTE_PAIR = 6            /* both feed-forwards split over workgroup pairs (cfm_rowchain_desc.psum_out / psum_in) */
+} cfm_route;
+
 /* x_in f32 [B*T,D] (not modified) -> x_out f32 [B*T,D] = norm_final(block(x_in)).
- * If next_g != NULL additionally writes LN(x_out; next_g,next_b) to s->xn for the following block. */
+ * xn_ready / next_g / next_b are read on CFM_ROUTE_GENERAL only: xn_ready != 0 says s->xn already holds LN_ffm(x_in); if next_g != NULL the call additionally
+ * writes LN(x_out; next_g,next_b) to s->xn for the following block. */
 int cfm_encoder_layer_forward(const cfm_layer_weights* w, const cfm_layer_scratch* s, const cfm_layer_io* io,
                               const float* x_in, float* x_out, int xn_ready, const float* next_g,
                               const float* next_b, cfm_stream_t stream);
+/* The cfm_route that call would take, or its negative cfm_status (cfm_last_error() set) -- the same checks, asked on the host: no launch, no HIP call, and no
+ * pointer dereferenced but the three structs and io->next_w, so it also runs where there is no GPU and with made-up addresses. */
+int32_t cfm_encoder_layer_route(const cfm_layer_weights* w, const cfm_layer_scratch* s, const cfm_layer_io* io, const float* x_in, const float* x_out);
+/* The row limit of CFM_ROUTE_FFSPLIT in force: CFM_FFSPLIT_MAX_ROWS, or the environment variable of that name at first use (experiments). */
+int32_t cfm_ffsplit_max_rows(void);
 
 /* ------------------------------------------------------------------------------------------------
  * CTC negative log-likelihood per utterance on top of the vocabulary projection (csrc/ctc.hip):

@@ -70,7 +70,7 @@ def test_fbank_desc_matches_c(tmp_path):
     got = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
     assert got == [ctypes.sizeof(cfm.FbankDesc)] + [getattr(cfm.FbankDesc, f).offset for f in fields]
     lib = cfm.lib()
-    assert hasattr(lib, "cfm_fbank") and hasattr(lib, "cfm_fbank_stream") and lib.cfm_version() == 305
+    assert hasattr(lib, "cfm_fbank") and hasattr(lib, "cfm_fbank_stream") and lib.cfm_version() == 306
 
 
 def test_no_cpu_path_and_window_limit():
