@@ -18,6 +18,27 @@ def _rows2d(t, name):
     return t
 
 
+def _dense(name, **tensors):
+    """Operands whose layout the C ABI cannot carry (no stride field for them): anything but a dense tensor would be read or written with
+    the wrong stride, silently -- so it is an argument error here, before any launch."""
+    for k, t in tensors.items():
+        if t is not None and not t.is_contiguous():
+            raise ValueError("cfm.%s: %s must be contiguous (the C ABI has no stride for it), got shape %s strides %s" % (name, k, tuple(t.shape), t.stride()))
+
+
+def _strides_match(name, what, t, sb, st):
+    """An operand addressed through explicit (batch, time) element strides: where the tensor itself has those axes, they must agree with
+    what the call passes -- the C ABI reads the numbers, not the tensor."""
+    if t is None:
+        return
+    if t.dim() not in (2, 3):                 # [rows, cols] or [B, T, cols]; other ranks say nothing about (batch, time)
+        bad = t.stride(-1) != 1
+    else:
+        bad = t.stride(-1) != 1 or (t.size(-2) > 1 and t.stride(-2) != st) or (t.dim() == 3 and t.size(0) > 1 and t.stride(0) != sb)
+    if bad:
+        raise ValueError("cfm.%s: %s has strides %s but the call passes (batch %d, time %d) with unit inner stride" % (name, what, t.stride(), sb, st))
+
+
 # A grow-only arena of reusable device buffers (workspace owned by the extension side of the boundary, SURVEY 8b), keyed per
 # (device, STREAM): two streams never share a scratch buffer, so forwards running concurrently on one device cannot overwrite each
 # other's xn / hid / qkv.  A buffer that has been handed out is NEVER released: when a larger one is needed the old block is retired,
@@ -53,6 +74,8 @@ def gemm(a, w, bias=None, w_lo=None, out=None, out_dtype=None, act=_c.ACT_NONE, 
     _c.require_hip(a, w, bias, w_lo, out, residual, row_mask)
     w = _rows2d(w, "gemm(w)")
     N, K = w.shape
+    if w.stride(0) != K:                         # cfm_gemm_desc has no row stride for W: a view wbuf[:, :K] would be read with stride K
+        raise ValueError("cfm.gemm: w must be dense [N,K] (cfm_gemm_desc carries no row stride for W), got shape %s strides %s" % (tuple(w.shape), w.stride()))
     d = _c.GemmDesc()
     if conv is None:
         a = _rows2d(a, "gemm(a)")
@@ -123,6 +146,10 @@ def ffn_fused(x, w1f, w2f, b1, b2, FF, act=_c.ACT_SILU, ln=None, alpha=1.0, add_
     if x.dtype != torch.float32 or not x.is_contiguous():
         raise ValueError("cfm.ffn_fused: x must be contiguous float32 [M,D]")
     M, D = x.shape
+    _dense("ffn_fused", w1f=w1f, w2f=w2f, b1=b1, b2=b2, out_f32=out_f32, **{n + "_" + s: t for n, pr in (("ln", ln), ("ln1", ln1), ("ln2", ln2)) if pr is not None
+                                                                            for s, t in zip("gb", pr)})
+    if out_f32 is not None and (out_f32.dtype != torch.float32 or tuple(out_f32.shape) != (M, D)):
+        raise ValueError("cfm.ffn_fused: out_f32 must be float32 (%d,%d)" % (M, D))
     d = _c.FfnDesc()
     d.x, d.w1f, d.w2f, d.b1, d.b2 = _c.ptr(x), _c.ptr(w1f), _c.ptr(w2f), _c.ptr(b1), _c.ptr(b2)
     for name, pair in (("ln", ln), ("ln1", ln1), ("ln2", ln2)):
@@ -159,6 +186,15 @@ def ffn_split(x, w_code, mode, psum=None, psum_b2=None, psum_alpha=1.0, ln1=None
     M, D = x.shape
     if x.dtype != torch.float32 or not x.is_contiguous():
         raise ValueError("cfm.ffn_split: x must be contiguous float32 rows")
+    _dense("ffn_split", psum_b2=psum_b2, rows_out=rows_out, rows2_out=rows2_out, w1=w1, b1=b1, w2=w2, psum_out=psum_out,
+           ring_kv=ring[0] if ring is not None else None, ring_offsets=ring[1] if ring is not None else None, **{n + "_" + sfx: t for n, pr in (("ln", ln), ("ln1", ln1), ("ln2", ln2)) if pr is not None for sfx, t in zip("gb", pr)})
+    if ring is not None and (ring[0].dtype != torch.float32 or ring[0].dim() != 4 or ring[1].dtype != torch.int32):
+        raise ValueError("cfm.ffn_split: ring is (kv float32 [B,H,ring_T,2dk], offsets int32 [B], frames per stream)")
+    for name, t in (("rows_out", rows_out), ("rows2_out", rows2_out)):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (M, D)):
+            raise ValueError("cfm.ffn_split: %s must be float32 (%d,%d)" % (name, M, D))
+    if out16 is not None and (out16.dim() != 2 or out16.stride(1) != 1 or out16.shape[0] != M):
+        raise ValueError("cfm.ffn_split: out16 must be [M, n1] with unit inner stride")
     d = _c.FfnSplitDesc()
     d.x, d.M, d.D, d.mode, d.w_dtype, d.eps = x.data_ptr(), M, D, mode, w_code, eps
     if psum is not None:
@@ -187,6 +223,15 @@ def rowchain(M, D, w_code, x=None, head=None, ln=None, ln_mask=None, ffn=None, a
     head = (a16 [M,D], w_frag, bias, residual f32 [M,D], out_mask u8 [M] | None);  ffn = (w1f, w2n, b1, b2, FF) with
     w1f = pack_frag_major(W1), w2n = pack_frag_major(W2) (natural k order, NOT ffn_fused's permuted w2f);
     tail = (w_frag, bias, N, glu, out 16-bit [M, N or N/2]);  ln/ln1/ln2 = (gain, bias)."""
+    _dense("rowchain", x=x, out_f32=out_f32, out16=out16, ln_mask=ln_mask, **{n + "_" + sfx: t for n, pr in (("ln", ln), ("ln1", ln1), ("ln2", ln2)) if pr is not None for sfx, t in zip("gb", pr)})
+    if head is not None:
+        _dense("rowchain", head_a=head[0], head_w=head[1], head_b=head[2], head_res=head[3], head_mask=head[4])
+    if tail is not None:
+        _dense("rowchain", tail_w=tail[0], tail_b=tail[1], tail_out=tail[4])
+    if ffn is not None:
+        _dense("rowchain", w1f=ffn[0], w2n=ffn[1], b1=ffn[2], b2=ffn[3])
+    if dw is not None:
+        _dense("rowchain", dw_w=dw[0], dw_b=dw[1], dw_scale=dw[2], dw_shift=dw[3])
     d = _c.RowChainDesc()
     keep = [x, out_f32, out16, ln_mask]
     d.x, d.out_f32, d.out16, d.ln_mask = _c.ptr(x), _c.ptr(out_f32), _c.ptr(out16), _c.ptr(ln_mask)
@@ -219,6 +264,7 @@ def layernorm(x, g1, b1, out1=None, out1_dtype=None, g2=None, b2=None, out2=None
     if x.dtype != torch.float32 or not x.is_contiguous():
         raise ValueError("cfm.layernorm: x must be contiguous float32 [M,D]")
     M, D = x.shape
+    _dense("layernorm", g1=g1, b1=b1, g2=g2, b2=b2, row_mask=row_mask)
     if want1 and out1 is None:
         out1 = torch.empty((M, D), dtype=out1_dtype or torch.float32, device=x.device)
     if out2 is None and out2_dtype is not None:
@@ -248,6 +294,13 @@ def attention(q, k, v, B, H, Tq, Tk, dk, q_str, k_str, v_str, out, p=None, p_str
     _c.require_hip(q, k, v, p, out, mask, bias_u, bias_v, lse)
     if lse is not None and (lse.dtype != torch.float32 or lse.numel() != B * H * Tq or not lse.is_contiguous()):
         raise ValueError("cfm.attention: lse must be contiguous float32 [B,H,Tq]")
+    for what, t, strides in (("q", q, q_str), ("k", k, k_str), ("v", v, v_str)):
+        # [rows, cols] and [B, T, cols] tensors carry the strides the call passes beside them; p and mask are taken on the numbers alone (their
+        # rank does not say which axis is batch: a [B, Tk] pad mask and a [R, D] row matrix of positions are both 2-D)
+        _strides_match("attention", what, t, strides[0], strides[1])
+    _dense("attention", out=out, bias_u=bias_u, bias_v=bias_v)       # out is [B,Tq,H*dk] row-major: cfm_attn_desc has no stride for it
+    if out.numel() != B * Tq * H * dk:
+        raise ValueError("cfm.attention: out must hold [B,Tq,H*dk] = %d elements, got %s" % (B * Tq * H * dk, tuple(out.shape)))
     d = _c.AttnDesc()
     d.q, d.k, d.v, d.p, d.out = _c.ptr(q), _c.ptr(k), _c.ptr(v), _c.ptr(p), _c.ptr(out)
     d.bias_u, d.bias_v, d.mask = _c.ptr(bias_u), _c.ptr(bias_v), _c.ptr(mask)
@@ -276,6 +329,10 @@ def kv_cache_pack(old_cache, k, v, k_str, v_str, B, H, Tn, dk):
             raise ValueError("cfm.kv_cache_pack: cache must be float32 (B,H,Tc,2dk); got %s %s" % (old_cache.dtype, tuple(old_cache.shape)))
         old_cache = old_cache.contiguous()
     _c.require_hip(old_cache, k, v)
+    _strides_match("kv_cache_pack", "k", k, k_str[0], k_str[1])
+    _strides_match("kv_cache_pack", "v", v, v_str[0], v_str[1])
+    if k.dtype != v.dtype:
+        raise ValueError("cfm.kv_cache_pack: k and v must share one dtype")
     out = torch.empty((B, H, Tc + Tn, 2 * dk), dtype=torch.float32, device=k.device)
     _c.check(_c.lib().cfm_kv_cache_pack(_c.ptr(old_cache), Tc, _c.ptr(k), _c.ptr(v), _c.dt_code(k), k_str[0], k_str[1], v_str[0],
                                         v_str[1], _c.ptr(out), B, H, Tn, dk, _c.stream()), "cfm_kv_cache_pack")
@@ -288,8 +345,11 @@ def dwconv_bn_silu(x, w, dw_bias, bn_scale, bn_shift, out=None, out_dtype=None):
     if x.dim() != 3 or not x.is_contiguous():
         raise ValueError("cfm.dwconv_bn_silu: x must be contiguous [B,T,D]")
     B, T, D = x.shape
+    _dense("dwconv_bn_silu", w=w, dw_bias=dw_bias, bn_scale=bn_scale, bn_shift=bn_shift, out=out)
     if out is None:
         out = torch.empty((B, T, D), dtype=out_dtype or x.dtype, device=x.device)
+    elif out.numel() != B * T * D:
+        raise ValueError("cfm.dwconv_bn_silu: out must hold [B,T,D]")
     _c.check(_c.lib().cfm_dwconv_bn_silu(_c.ptr(x), _c.dt_code(x), _c.ptr(w), _c.ptr(dw_bias), _c.ptr(bn_scale), _c.ptr(bn_shift),
                                          _c.ptr(out), _c.dt_code(out), B, T, D, w.shape[1], _c.stream()), "cfm_dwconv_bn_silu")
     return out
@@ -315,6 +375,9 @@ def conv1_relu(x, w9c, bias, out_dtype, cmvn=None, mma=False):
         raise ValueError("cfm.conv1_relu: x must be contiguous float32 [B,T,F]")
     B, T, F = x.shape
     C = w9c.shape[1]
+    _dense("conv1_relu", w9c=w9c, bias=bias)
+    if tuple(w9c.shape) != (9, C) or w9c.dtype != torch.float32 or bias.dtype != torch.float32 or bias.numel() != C:
+        raise ValueError("cfm.conv1_relu: w9c must be float32 [9,C] (tap-major) and bias float32 [C]")
     T1, F1 = (T - 3) // 2 + 1, (F - 3) // 2 + 1
     out = torch.empty((B, T1, F1, C), dtype=out_dtype, device=x.device)
     fn = _c.lib().cfm_conv1_relu_mma if mma else _c.lib().cfm_conv1_relu
@@ -342,6 +405,9 @@ def conv12_relu(x, w9c, b1, w2, b2, cmvn=None):
         raise ValueError("cfm.conv12_relu: x must be contiguous float32 [B,T,F]")
     B, T, F = x.shape
     C = w9c.shape[1]
+    _dense("conv12_relu", w9c=w9c, b1=b1, b2=b2)
+    if tuple(w9c.shape) != (9, C) or any(t.dtype != torch.float32 for t in (w9c, b1, b2)) or b1.numel() != C or b2.numel() != C:
+        raise ValueError("cfm.conv12_relu: w9c must be float32 [9,C] (tap-major), b1 and b2 float32 [C]")
     if w2.shape != (C, 9 * C) or not w2.is_contiguous() or w2.dtype not in (torch.bfloat16, torch.float16):
         raise ValueError("cfm.conv12_relu: w2 must be a contiguous 16-bit [C, 9C] matrix")
     T1, F1 = (T - 3) // 2 + 1, (F - 3) // 2 + 1
@@ -429,6 +495,9 @@ def add_rows(x, add, group):
     """x[r,:] += add[r // group, :] in place (f32)."""
     _c.require_hip(x, add)
     rows, D = x.shape
+    _dense("add_rows", x=x, add=add)
+    if x.dtype != torch.float32 or add.dtype != torch.float32 or add.dim() != 2 or add.shape[1] != D or add.shape[0] * group < rows:
+        raise ValueError("cfm.add_rows: x f32 [rows,D] and add f32 [>= rows/group, D] expected, got %s %s" % (tuple(x.shape), tuple(add.shape)))
     _c.check(_c.lib().cfm_add_rows(_c.ptr(x), _c.ptr(add), rows, D, group, _c.stream()), "cfm_add_rows")
     return x
 
@@ -529,10 +598,18 @@ def gemm_tn_group(products, mma_code=_c.BF16, splits=0):
         d.A, d.B, d.C, d.colsum = a.data_ptr(), b.data_ptr(), out.data_ptr(), _c.ptr(colsum)
         d.lda, d.ldb = a.stride(0), b.stride(0)
         d.M, d.N, d.K = a.shape[0], a.shape[1], b.shape[1]
-        d.ldc = pr.get("ldc", d.K)
+        if out.stride(-1) != 1 or (colsum is not None and not colsum.is_contiguous()):
+            raise ValueError("cfm.gemm_tn_group: out needs unit inner stride and colsum must be contiguous")
+        # a 2-D out carries its own row stride; a flat slab (row_off scatter) has none to carry
+        d.ldc = pr.get("ldc", out.stride(0) if out.dim() == 2 and pr.get("row_off") is None else d.K)
         d.a_dtype, d.b_dtype, d.mma_dtype = _c.dt_code(a), _c.dt_code(b), mma_code
         d.accumulate, d.splits, d.alpha = 1, (1 if _deterministic[0] else splits), float(pr.get("alpha", 1.0))
-        d.row_off, d.colsum_off, d.colsum_off2 = _c.ptr(pr.get("row_off")), _c.ptr(pr.get("colsum_off")), _c.ptr(pr.get("colsum_off2"))
+        tabs = {k: pr.get(k) for k in ("row_off", "colsum_off", "colsum_off2")}
+        _c.require_hip(*tabs.values())
+        _dense("gemm_tn_group", **tabs)
+        if any(t is not None and (t.dtype != torch.int64 or t.numel() != d.N) for t in tabs.values()):
+            raise ValueError("cfm.gemm_tn_group: row_off / colsum_off / colsum_off2 must be int64 [N]")
+        d.row_off, d.colsum_off, d.colsum_off2 = _c.ptr(tabs["row_off"]), _c.ptr(tabs["colsum_off"]), _c.ptr(tabs["colsum_off2"])
     _c.check(_c.lib().cfm_gemm_tn_group(descs, n, _c.stream()), "cfm_gemm_tn_group")
 
 
@@ -543,6 +620,9 @@ def layernorm_bwd(x, dy, gamma, row_mask=None, dres=None, dx=None, eps=1e-5):
     M, D = x.shape
     if x.dtype != torch.float32 or not x.is_contiguous() or tuple(dy.shape) != (M, D) or not dy.is_contiguous():
         raise ValueError("cfm.layernorm_bwd: x must be contiguous float32 [M,D] and dy contiguous [M,D]")
+    _dense("layernorm_bwd", gamma=gamma, row_mask=row_mask)
+    if gamma.dtype != torch.float32 or gamma.numel() != D or (row_mask is not None and (row_mask.element_size() != 1 or row_mask.numel() != M)):
+        raise ValueError("cfm.layernorm_bwd: gamma must be float32 [D] and row_mask one byte per row [M]")
     if dx is None:
         dx = torch.empty_like(x)
     for t in (dres, dx):
@@ -574,6 +654,12 @@ def dwconv_bn_train(g, w, dw_bias, gamma, beta, running_mean, running_var, momen
     if g.dim() != 3 or not g.is_contiguous():
         raise ValueError("cfm.dwconv_bn_train: g must be contiguous [B,T,D]")
     B, T, D = g.shape
+    _dense("dwconv_bn_train", w=w, dw_bias=dw_bias, gamma=gamma, beta=beta, running_mean=running_mean, running_var=running_var)
+    for n, t in (("dw_bias", dw_bias), ("gamma", gamma), ("beta", beta), ("running_mean", running_mean), ("running_var", running_var)):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != D):
+            raise ValueError("cfm.dwconv_bn_train: %s must be float32 [D]" % n)
+    if w.dtype != torch.float32 or w.shape[0] != D:
+        raise ValueError("cfm.dwconv_bn_train: w must be float32 [D,K]")
     c = torch.empty((B, T, D), dtype=torch.float32, device=g.device)
     stats = torch.empty((4, D), dtype=torch.float32, device=g.device)
     s = torch.empty((B, T, D), dtype=s_dtype, device=g.device)
@@ -590,6 +676,9 @@ def dwconv_bn_train_bwd(ds, c, stats, g, w, dg_dtype):
     B, T, D = g.shape
     if not ds.is_contiguous() or ds.numel() != B * T * D or not c.is_contiguous() or not g.is_contiguous():
         raise ValueError("cfm.dwconv_bn_train_bwd: ds, c, g must be contiguous [B,T,D]")
+    _dense("dwconv_bn_train_bwd", stats=stats, w=w)
+    if stats.dtype != torch.float32 or stats.numel() != 4 * D or w.dtype != torch.float32 or w.shape[0] != D:
+        raise ValueError("cfm.dwconv_bn_train_bwd: stats must be float32 [4,D] and w float32 [D,K]")
     dev = g.device
     dg = torch.empty((B, T, D), dtype=dg_dtype, device=dev)
     dw_w = torch.empty((D, w.shape[1]), dtype=torch.float32, device=dev)
@@ -622,6 +711,10 @@ def conv1_wgrad(dh1, x, cmvn=None):
     C = dh1.shape[3]
     mean, istd = cmvn if cmvn is not None else (None, None)
     _c.require_hip(mean, istd)
+    _dense("conv1_wgrad", mean=mean, istd=istd)
+    for t in (mean, istd):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != F):
+            raise ValueError("cfm.conv1_wgrad: cmvn statistics must be float32 [F]")
     if x.dtype != torch.float32 or not x.is_contiguous() or not dh1.is_contiguous() or tuple(dh1.shape[:3]) != (B, (T - 3) // 2 + 1, (F - 3) // 2 + 1):
         raise ValueError("cfm.conv1_wgrad: x must be contiguous float32 [B,T,F] and dh1 contiguous [B,T1,F1,C]")
     dw = torch.empty((9, C), dtype=torch.float32, device=x.device)
@@ -636,6 +729,10 @@ def attention_bwd(q, k, v, out, dout, lse, B, H, Tq, Tk, dk, q_str, k_str, v_str
                   scale=None, drop=None):
     """Backward of attention(); q/k/v and dq/dkk/dv share strides ((batch, time) in elements, head h at h*dk); see include/cfm.h."""
     _c.require_hip(q, k, v, out, dout, lse, dq, dkk, dv, mask)
+    _dense("attention_bwd", out=out, dout=dout, lse=lse)             # [B,Tq,H*dk] / [B,H,Tq] row-major: no strides in cfm_attn_bwd_desc
+    for what, t, (sb, st) in (("q", q, q_str), ("k", k, k_str), ("v", v, v_str), ("dq", dq, q_str), ("dk", dkk, k_str), ("dv", dv, v_str)):
+        # 2-D [B*T, ...] views carry the time stride, 3-D ones both; cfm_attn_bwd_desc has ONE set of strides for an operand and its gradient
+        _strides_match("attention_bwd", what, t, sb, st)
     d = _c.AttnBwdDesc()
     d.q, d.k, d.v, d.mask, d.out, d.dout, d.lse = _c.ptr(q), _c.ptr(k), _c.ptr(v), _c.ptr(mask), _c.ptr(out), _c.ptr(dout), _c.ptr(lse)
     d.grad_q, d.grad_k, d.grad_v = _c.ptr(dq), _c.ptr(dkk), _c.ptr(dv)
@@ -696,6 +793,11 @@ def ctc_grad(logits, V, enc_lens, labels, label_lens, state, gscale=1.0, gscale_
     _ctc_args(logits, enc_lens, labels, label_lens)
     work, alpha, lse, nllp, beta = state
     B, T = logits.shape[:2]
+    _c.require_hip(work, alpha, lse, nllp, beta)
+    _dense("ctc_grad", work=work, alpha=alpha, lse=lse, nll_shifted=nllp, beta=beta, gscale_dev=gscale_dev)
+    SM = 2 * labels.size(1) + 2
+    if any(t.dtype != torch.float32 for t in state) or any(t.numel() != B * T * SM for t in (work, alpha, beta)) or lse.numel() != B * T or nllp.numel() != B:
+        raise ValueError("cfm.ctc_grad: state must be the float32 (work, alpha, lse, nll_shifted, beta) of ctc_nll_train_groups for these logits")
     if out is None:
         out = torch.empty_like(logits)
     if out.dtype != torch.float32 or out.shape != logits.shape or out.stride() != logits.stride():
@@ -877,6 +979,7 @@ def adam_step(p, g, m, v, lr, betas, eps, weight_decay, step, grad_scale=None):
     for t in (p, g, m, v):
         if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous():
             raise ValueError("cfm.adam_step: p, g, m, v must be contiguous float32 buffers of one size")
+    _dense("adam_step", grad_scale=grad_scale)
     _c.check(_c.lib().cfm_adam_step(_c.ptr(p), _c.ptr(g), _c.ptr(m), _c.ptr(v), n, lr, betas[0], betas[1], eps, weight_decay, step, _c.ptr(grad_scale),
                                     _c.stream()), "cfm_adam_step")
 
@@ -889,6 +992,7 @@ def adam_clip_step(p, g, m, v, lr, betas, eps, weight_decay, step, sumsq_t, clip
     for t in (p, g, m, v):
         if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous():
             raise ValueError("cfm.adam_clip_step: p, g, m, v must be contiguous float32 buffers of one size")
+    _dense("adam_clip_step", sumsq=sumsq_t)
     norm = torch.empty((1,), dtype=torch.float32, device=p.device)
     _c.check(_c.lib().cfm_adam_clip_step(_c.ptr(p), _c.ptr(g), _c.ptr(m), _c.ptr(v), n, lr, betas[0], betas[1], eps, weight_decay, step, _c.ptr(sumsq_t),
                                          float(clip or 0.0), float(inv_world), 1 if zero_grad else 0, _c.ptr(norm), _c.stream()), "cfm_adam_clip_step")
@@ -916,6 +1020,9 @@ def dropout_rows(x, out_dtype, alpha=1.0, drop=None, drop2=None, row_mask=None):
     if not x.is_contiguous():
         raise ValueError("cfm.dropout_rows: x must be contiguous")
     M, N = x.shape
+    _dense("dropout_rows", row_mask=row_mask)
+    if row_mask is not None and (row_mask.element_size() != 1 or row_mask.numel() != M):
+        raise ValueError("cfm.dropout_rows: row_mask must be one byte per row [M]")
     y = torch.empty((M, N), dtype=out_dtype, device=x.device)
     p1, s1 = (float(drop[0]), int(drop[1]) & 0xFFFFFFFF) if drop is not None else (0.0, 0)
     p2, s2 = (float(drop2[0]), int(drop2[1]) & 0xFFFFFFFF) if drop2 is not None else (0.0, 0)
@@ -940,6 +1047,7 @@ def stream_prep(offsets, T, need, ring_T, pe, slot_mask, pos_rows, abs_rows=None
     _c.require_hip(offsets, pe, slot_mask, pos_rows, abs_rows)
     B = offsets.numel()
     D = pe.shape[-1]
+    _dense("stream_prep", offsets=offsets, slot_mask=slot_mask, pos_rows=pos_rows, abs_rows=abs_rows)
     if offsets.dtype != torch.int32 or pe.dtype != torch.float32 or not pe.is_contiguous() or slot_mask.numel() != B * ring_T or pos_rows.numel() != B * ring_T * D:
         raise ValueError("cfm.stream_prep: offsets int32 [B], pe contiguous f32 [max_len,D], slot_mask [B,ring_T], pos_rows [B,ring_T,D]")
     _c.check(_c.lib().cfm_stream_prep(_c.ptr(offsets), B, T, need, ring_T, _c.ptr(pe), pe.numel() // D, D, _c.ptr(slot_mask), _c.ptr(pos_rows), _c.ptr(abs_rows),
@@ -948,6 +1056,7 @@ def stream_prep(offsets, T, need, ring_T, pe, slot_mask, pos_rows, abs_rows=None
 
 def stream_advance(offsets, T, active=None):
     _c.require_hip(offsets, active)
+    _dense("stream_advance", offsets=offsets, active=active)
     _c.check(_c.lib().cfm_stream_advance(_c.ptr(offsets), _c.ptr(active), offsets.numel(), T, _c.stream()), "cfm_stream_advance")
 
 
@@ -956,6 +1065,7 @@ def dwconv_causal_bn_silu(x, w, dw_bias, bn_scale, bn_shift, cache=None, out_dty
     _c.require_hip(x, w, dw_bias, bn_scale, bn_shift, cache)
     B, T, D = x.shape
     K = w.shape[1]
+    _dense("dwconv_causal_bn_silu", w=w, dw_bias=dw_bias, bn_scale=bn_scale, bn_shift=bn_shift)
     if not x.is_contiguous() or (cache is not None and (cache.dtype != torch.float32 or tuple(cache.shape) != (B, K - 1, D) or not cache.is_contiguous())):
         raise ValueError("cfm.dwconv_causal_bn_silu: x contiguous [B,T,D], cache contiguous f32 [B,K-1,D]")
     y = torch.empty((B, T, D), dtype=out_dtype or x.dtype, device=x.device)
@@ -967,6 +1077,9 @@ def dwconv_causal_bn_silu(x, w, dw_bias, bn_scale, bn_shift, cache=None, out_dty
 def conv_cache_update(x, cache, ktaps):
     _c.require_hip(x, cache)
     B, T, D = x.shape
+    _dense("conv_cache_update", x=x, cache=cache)
+    if cache.dtype != torch.float32 or tuple(cache.shape) != (B, ktaps - 1, D):
+        raise ValueError("cfm.conv_cache_update: cache must be float32 [B,ktaps-1,D], got %s %s" % (cache.dtype, tuple(cache.shape)))
     _c.check(_c.lib().cfm_conv_cache_update(_c.ptr(x), _c.dt_code(x), _c.ptr(cache), B, T, D, ktaps, _c.stream()), "cfm_conv_cache_update")
 
 
@@ -977,6 +1090,7 @@ def _fbank_desc(samples, tables, out, win, shift, padded, dither, seed):
     """tables: (twiddle f64, window f64, mel weights f32, start, length, offset int32) on the device (packing.fbank_tables / pack_mel_banks)."""
     tw, wnd, mw, ms, ml, mo = tables
     _c.require_hip(samples, out, *tables)
+    _dense("fbank", twiddle=tw, window=wnd, mel_w=mw, mel_start=ms, mel_len=ml, mel_off=mo)
     if samples.dim() != 2 or samples.stride(1) != 1 or samples.dtype not in (torch.int16, torch.float32):
         raise ValueError("cfm.fbank: samples must be (B, N) int16 or float32 with unit inner stride, got %s %s" % (tuple(samples.shape), samples.dtype))
     B, rows, F = out.shape
@@ -994,6 +1108,7 @@ def fbank(samples, lengths, tables, out, feats_length, win, shift, padded, dithe
     """Offline: samples (B, N) int16 | f32, lengths int32 [B] -> out f32 (B, rows, F) (rows past an item's frame count zero), feats_length int32 [B]."""
     d = _fbank_desc(samples, tables, out, win, shift, padded, dither, seed)
     _c.require_hip(lengths, feats_length)
+    _dense("fbank", lengths=lengths, feats_length=feats_length)
     if lengths.dtype != torch.int32 or feats_length.dtype != torch.int32 or lengths.numel() != d.B or feats_length.numel() != d.B:
         raise ValueError("cfm.fbank: lengths and feats_length are int32 [B]")
     d.lengths, d.feats_length = _c.ptr(lengths), _c.ptr(feats_length)
