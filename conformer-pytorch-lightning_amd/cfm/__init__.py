@@ -36,7 +36,8 @@ class GemmDesc(ctypes.Structure):
                 ("conv_C", c_i32), ("conv_T1", c_i32), ("conv_F1", c_i32), ("conv_T2", c_i32), ("conv_F2", c_i32),
                 ("tile", c_i32), ("mask_mode", c_i32),
                 ("C_pre", c_p), ("ld_pre", c_i64), ("pre_dtype", c_i32), ("aux_dtype", c_i32), ("aux", c_p), ("ld_aux", c_i64),
-                ("drop_p", ctypes.c_float), ("drop2_p", ctypes.c_float), ("drop_seed", ctypes.c_uint32), ("drop2_seed", ctypes.c_uint32)]
+                ("drop_p", ctypes.c_float), ("drop2_p", ctypes.c_float), ("drop_seed", ctypes.c_uint32), ("drop2_seed", ctypes.c_uint32),
+                ("row_len", c_p), ("row_T", c_i32)]
 
 
 class GemmTnDesc(ctypes.Structure):
@@ -84,7 +85,7 @@ class RowChainDesc(ctypes.Structure):
                 ("s2_ln_g", c_p), ("s2_ln_b", c_p), ("s2_w1f", c_p), ("s2_w2n", c_p), ("s2_b1", c_p), ("s2_b2", c_p), ("s2_out_f32", c_p),
                 ("s2_alpha", ctypes.c_float), ("psum_out", c_p), ("psum_in", c_p), ("psum_b2", c_p), ("psum_alpha", ctypes.c_float),
                 ("cin_a", c_p), ("cin_w", c_p), ("cin_b", c_p), ("cin_res", c_p), ("cin_out", c_p), ("cin_ln_g", c_p), ("cin_ln_b", c_p), ("cin_mask", c_p),
-                ("cin_tail_w", c_p), ("cin_tail_b", c_p), ("tail_pair", c_i32)]
+                ("cin_tail_w", c_p), ("cin_tail_b", c_p), ("tail_pair", c_i32), ("glu_len", c_p), ("glu_T", c_i32)]
 
 
 _LAYER_W_FIELDS = [
@@ -222,7 +223,7 @@ class LayerIO(ctypes.Structure):
                 ("pos_proj", c_p), ("pos_proj_ld", c_i64),
                 ("attn_cache", c_p), ("cache_T", c_i32), ("new_cache", c_p), ("after_g", c_p), ("after_b", c_p), ("after_out", c_p),
                 ("kv_ring", c_p), ("stream_offset", c_p), ("ring_T", c_i32), ("causal_conv", c_i32), ("conv_cache", c_p), ("pos_shared", c_i32),
-                ("next_w", c_p), ("next_x_out", c_p), ("macaron_done", c_i32)]
+                ("next_w", c_p), ("next_x_out", c_p), ("macaron_done", c_i32), ("utt_len", c_p)]
 
 
 ROUTES = ("GENERAL", "FUSED_FFN", "CHAIN", "CHAIN_NEXT", "CHAIN_NEXT_CIN", "FFSPLIT", "PAIR")     # include/cfm.h cfm_route, by value (cfm_encoder_layer_route)

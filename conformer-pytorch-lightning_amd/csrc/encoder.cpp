@@ -67,6 +67,8 @@ int select_route(Ctx& c) {
     }
     CFM_CHECK_ARG(c.Tc == 0 || io->new_cache, "encoder layer: a KV cache input needs new_cache storage");
     CFM_CHECK_ARG(!io->after_out || (io->after_g && io->after_b), "encoder layer: after_out needs after_g / after_b");
+    CFM_CHECK_ARG(!io->utt_len || (!c.ring && !io->attn_cache && !io->causal_conv && !io->pad_valid),
+                  "encoder layer: utt_len (a ragged batch of whole utterances) excludes kv_ring, attn_cache, causal_conv and pad_valid");
     const bool chains = !c.split && w->ffm_w1f && w->ffm_w2n && w->ff_w1f && w->ff_w2n && w->qkv_wf && w->out_wf && w->pw1_wf && w->pw2_wf &&
                         cfm_rowchain_supported(c.D, c.FF);
     CFM_CHECK_ARG(!io->macaron_done || chains, "encoder layer: macaron_done needs the chain path");
@@ -98,6 +100,7 @@ int gemm(const Ctx& c, const void* A, int a_dt, int64_t lda, const void* W, cons
     d.A = A; d.W = W; d.W_lo = c.split ? Wlo : nullptr; d.bias = bias; d.residual = res; d.row_mask = row_mask; d.C = C;
     d.lda = lda; d.ldc = ldc; d.ldr = ldc; d.M = M; d.N = N; d.K = K;
     d.a_dtype = a_dt; d.w_dtype = c.w_dt; d.c_dtype = c_dt; d.act = act; d.alpha = alpha;
+    if (act == CFM_ACT_GLU && c.io->utt_len) { d.row_len = c.io->utt_len; d.row_T = c.io->T; }   // zeros past each utterance's end (cfm.h cfm_layer_io.utt_len)
     return cfm_gemm(&d, c.st);
 }
 
@@ -194,6 +197,7 @@ int conv_in_chain(const Ctx& c, float* park = nullptr) {
     ci.head_a = c.s->ctx; ci.head_w = w->out_wf; ci.head_b = w->out_b; ci.head_res = c.x_out; ci.ln_g = w->ln_conv_g; ci.ln_b = w->ln_conv_b;
     ci.ln_mask = c.io->pad_valid; ci.out_f32 = c.x_out; ci.tail_w = w->pw1_wf; ci.tail_b = w->pw1_b; ci.tail_out = c.s->glu; ci.tail_N = 2 * c.D; ci.tail_glu = 1;
     if (park) { ci.tail_pair = 1; ci.out_f32 = park; }
+    ci.glu_len = c.io->utt_len; ci.glu_T = c.io->T;
     return cfm_rowchain(&ci, c.st);
 }
 
@@ -337,6 +341,7 @@ int run_chain_next_cin(const Ctx& c) {
     next_macaron(fi, c);
     fi.cin_a = c.s->ctx; fi.cin_w = w->out_wf; fi.cin_b = w->out_b; fi.cin_res = c.x_out; fi.cin_out = c.io->next_x_out; fi.cin_ln_g = w->ln_conv_g;
     fi.cin_ln_b = w->ln_conv_b; fi.cin_mask = c.io->pad_valid; fi.cin_tail_w = w->pw1_wf; fi.cin_tail_b = w->pw1_b; fi.head_res = c.io->next_x_out;
+    fi.glu_len = c.io->utt_len; fi.glu_T = c.io->T;
     return cfm_rowchain(&fi, c.st);
 }
 

@@ -33,6 +33,8 @@ struct GemmArgs {
     const float* bias;
     const float* res;
     const uint8_t* mask;
+    const int32_t* row_len;   // ragged batches: row (b, t) of [B, row_T] with t >= row_len[b] counts as masked (cfm.h cfm_gemm_desc.row_len)
+    int row_T;
     void* C;
     void* Cpre;      // training: optional second output, acc + bias before the activation (row stride ld_pre, pre_dtype)
     const void* aux; // training: pre-activation (DSILU) / forward output (DRELU) of the layer whose input gradient this GEMM computes
@@ -267,6 +269,14 @@ __global__ __launch_bounds__(256 * KG, KG == 1 ? 2 : 1) void cfm_gemm_kernel(con
     for (int i = 0; i < FM; ++i) {
         const int row = m0 + wr * (BM / 2) + i * 16 + (lane & 15);
         keep_r[i] = (g.mask && row < g.M) ? (g.mask[row] != 0) : true;
+    }
+    if (g.row_len) {                                      // uniform: a kernel argument
+#pragma unroll
+        for (int i = 0; i < FM; ++i) {
+            const int row = m0 + wr * (BM / 2) + i * 16 + (lane & 15);
+            const unsigned rc = (unsigned)(row < g.M ? row : g.M - 1), b = rc / (unsigned)g.row_T;
+            keep_r[i] = keep_r[i] && (int)(rc - b * (unsigned)g.row_T) < g.row_len[b];
+        }
     }
     for (int kt0 = 0; kt0 < nkt; kt0 += PF) {
         body(kt0, std::integral_constant<int, 0>{});
@@ -720,7 +730,10 @@ extern "C" int cfm_gemm(const cfm_gemm_desc* d, cfm_stream_t stream) {
     CFM_CHECK_ARG(conv ? (int64_t)(d->M / (d->conv_T2 * d->conv_F2)) * d->conv_T1 * d->conv_F1 * d->conv_C < ((int64_t)1 << 31)
                        : ((int64_t)(d->M - 1) * d->lda + d->K) < ((int64_t)1 << 31),
                   "cfm_gemm: activation operand too large for 32-bit element offsets");
+    CFM_CHECK_ARG(!d->row_len || (d->row_T > 0 && d->M % d->row_T == 0 && d->mask_mode == 0 && d->act == CFM_ACT_GLU),
+                  "cfm_gemm: row_len needs row_T > 0, M %% row_T == 0, mask_mode 0 and the GLU epilogue");
     GemmArgs a;
+    a.row_len = d->row_len; a.row_T = d->row_T;
     a.A = d->A; a.W = (const u16*)d->W; a.Wlo = (const u16*)d->W_lo; a.bias = d->bias; a.res = d->residual;
     a.mask = d->row_mask; a.C = d->C; a.lda = d->lda; a.ldc = d->ldc; a.ldr = d->ldr;
     CFM_CHECK_ARG(d->drop_p >= 0.f && d->drop_p < 1.f && d->drop2_p >= 0.f && d->drop2_p < 1.f, "cfm_gemm: dropout probabilities must be in [0, 1)");

@@ -93,6 +93,10 @@ struct ChainArgs {
     const uint8_t* cin_mask;  // pad validity per row (zeroes the normalised row), or null
     const u16* cin_tw;        // pointwise-conv-1, GLU-interleaved, fragment-major [2D/16][KS][64][8]
     const float* cin_tb;
+    // ragged batches: rows are [B, glu_T] flattened; the GLU output (TGLU tail, CIN stage) of row (b, t) with t >= glu_len[b] is written as zero, so
+    // that the depthwise stage behind it reads past an utterance's end what it reads past a tensor edge.  Null: no select
+    const int32_t* glu_len;
+    int glu_T;
 };
 
 // Phase stamps for scripts/probe_chain.hip (built with -DCFM_CHAIN_STAMPS; never defined in the product build): thread 0 of each
@@ -265,6 +269,11 @@ __global__ __launch_bounds__(NT) void cfm_rowchain_kernel(const ChainArgs a) {
     const int64_t row0 = (int64_t)fs_tile * RBM;
     const int64_t Mlim = a.M;                              // rows at or past Mlim are clamped on load and never stored
     const f32x4 zero4 = (f32x4){0.f, 0.f, 0.f, 0.f};
+    // row (b, t) of the flattened [B, glu_T] rows lies inside its utterance (gr in [0, M); only called when glu_len is set)
+    auto glu_live = [&](int64_t gr) {
+        const unsigned r = (unsigned)gr, b = r / (unsigned)a.glu_T;
+        return (int)(r - b * (unsigned)a.glu_T) < a.glu_len[b];
+    };
     CFM_STAMP(0);
 
     // The tail's weight ring is declared here so that its first fill can be issued a phase or two before the tail runs
@@ -502,7 +511,8 @@ __global__ __launch_bounds__(NT) void cfm_rowchain_kernel(const ChainArgs a) {
                         const f32x4 v1 = tacc[mf][1] + tb1;
 #pragma unroll
                         for (int q = 0; q < 4; ++q) v0[q] *= sigmoidf_(v1[q]);
-                        const bool in = gr >= 0 && gr < Mlim;
+                        bool in = gr >= 0 && gr < Mlim;
+                        if (a.glu_len) in = in && glu_live(gr < 0 ? 0 : (gr < Mlim ? gr : Mlim - 1));   // (uniform branch: a kernel argument)
                         const u32x2 pk = in ? (u32x2){pack2<HT>(v0.x, v0.y), pack2<HT>(v0.z, v0.w)} : (u32x2){0u, 0u};
                         if (r < DWROWS) *(u32x2*)(halo + r * D + wave * 16 + 4 * g) = pk;
                     }
@@ -1049,7 +1059,11 @@ __global__ __launch_bounds__(NT) void cfm_rowchain_kernel(const ChainArgs a) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) v0[r] *= sigmoidf_(v1[r]);
                         const int64_t o = grow * ldo + (f >> 1) * 16 + 4 * g;
-                        *(u32x2*)((u16*)a.tail_out + o) = (u32x2){pack2<HT>(v0.x, v0.y), pack2<HT>(v0.z, v0.w)};
+                        u32x2 pk = (u32x2){pack2<HT>(v0.x, v0.y), pack2<HT>(v0.z, v0.w)};
+                        if (a.glu_len) {                      // (uniform branch: a kernel argument)
+                            if (!glu_live(grow)) pk = (u32x2){0u, 0u};
+                        }
+                        *(u32x2*)((u16*)a.tail_out + o) = pk;
                     }
                 } else {
                     if (f < t_nfrags) {
@@ -1104,7 +1118,10 @@ extern "C" int cfm_rowchain(const cfm_rowchain_desc* d, cfm_stream_t stream) {
     CFM_CHECK_ARG(!d->tail_pair || (!mid && d->D == 512 && (tail ? (d->tail_N / 16) % 2 == 0 : (head && dw && d->out_f32 && !d->ln_g)) && (!head || d->out_f32 != d->head_res)),
                   "cfm_rowchain: tail_pair needs a chain without a feed-forward at D = 512 -- with a tail, or the depthwise head alone (no LayerNorm, rows to out_f32) -- "
                   "and (with a head) out_f32 distinct from head_res");
+    CFM_CHECK_ARG(!d->glu_len || (((tail && d->tail_glu) || d->cin_a) && d->glu_T > 0 && d->M % d->glu_T == 0 && d->M < ((int64_t)1 << 31)),
+                  "cfm_rowchain: glu_len needs a GLU tail or the conv-in input stage, glu_T > 0, M %% glu_T == 0 and M < 2^31");
     ChainArgs a;
+    a.glu_len = d->glu_len; a.glu_T = d->glu_T;
     a.psum_out = d->psum_out; a.psum_in = d->psum_in; a.psum_b2 = d->psum_b2; a.psum_alpha = d->psum_alpha;
     const bool cin = d->cin_a != nullptr;
     CFM_CHECK_ARG(!cin || (seg2 && dw && d->D == 256 && d->cin_w && d->cin_b && d->cin_res && d->cin_out && d->cin_ln_g && d->cin_ln_b && d->cin_tail_w && d->cin_tail_b &&

@@ -43,9 +43,10 @@ class ConformerEncoder(nn.Module):
         self.static_chunk_size = static_chunk_size
 
     # ------------------------------------------------------------------------------------------------------------
-    def _run_blocks(self, x, attn_mask, pos_embed, pad_mask, caches, keep_from, pos_shared=False, proj=None, ring=None, conv=None, streaming=False):
+    def _run_blocks(self, x, attn_mask, pos_embed, pad_mask, caches, keep_from, pos_shared=False, proj=None, ring=None, conv=None, streaming=False, utt_len=None):
         """x (B,T',D) f32 -> after_norm(blocks(x)); returns (y, [trimmed per-layer caches] | None).
-        ring = (kv f32 [L,B,H,ring_T,2dk], offsets int32 [B]), conv = f32 [L,B,K-1,D] | None: per-stream streaming state (StreamingBatch)."""
+        ring = (kv f32 [L,B,H,ring_T,2dk], offsets int32 [B]), conv = f32 [L,B,K-1,D] | None: per-stream streaming state (StreamingBatch).
+        utt_len int32 [B]: a ragged batch of whole utterances (forward_utterances; include/cfm.h cfm_layer_io.utt_len)."""
         n = len(self.encoders)
         if proj is None:
             proj = self._project_positions(pos_embed, x)
@@ -77,7 +78,7 @@ class ConformerEncoder(nn.Module):
                                           out=bufs[i & 1], want_cache=caches is not None, pos_proj=pp, pos_shared=pos_shared,
                                           ring=None if ring is None else (ring[0][i], ring[1]), conv_cache=None if conv is None else conv[i],
                                           chain_next=(self.encoders[i + 1], bufs[(i + 1) & 1]) if chain and i + 1 < n else None,
-                                          macaron_done=chain and i > 0, split_ffn=streaming,
+                                          macaron_done=chain and i > 0, split_ffn=streaming, utt_len=utt_len,
                                           after=(self.after_norm.weight.detach(), self.after_norm.bias.detach(), y_after)
                                           if fuse_after and i + 1 == n else None)
             if new_caches is not None:
@@ -150,6 +151,33 @@ class ConformerEncoder(nn.Module):
         # depends on which side of 1536 rows the batch falls (to rounding, 1e-3 of the output), and a batch shard no longer reproduces the batch bit for bit
         y, _ = self._run_blocks(x, attn_mask, pos_embed, pad_mask, None, 0, streaming=bool(getattr(self, "split_small_batches", False)))
         return y.to(inputs.dtype), pad_mask
+
+    def forward_utterances(self, inputs, input_lengths):
+        """A ragged batch of WHOLE utterances with the DECODING path's semantics (beyond the reference, which decodes at batch 1): inputs (B,T,F),
+        input_lengths (B,) frames per item -> (outputs (B,T'max,D), out_lens int32 (B,)), out_lens[b] = ((len_b - 1)//2 - 1)//2, 0 below 7 frames
+        (where the reference's forward_chunk_by_chunk has nothing to concatenate).  Rows [0, out_lens[b]) of item b are what the reference's
+        greedy_search computes for that utterance alone -- forward_chunk(inputs[b:b+1, :len_b], 0, -1, empty, empty), model.py:202-212 --; rows at
+        and past out_lens[b] are zero.  Unlike `forward` (the training path's semantics in eval mode) every item attends over its own keys with the real
+        positional term from the shared rows pe[0:T'max], and its depthwise convolutions read zeros past its last frame, as at a tensor edge
+        (cfm_layer_io.utt_len: a select behind the GLU).  Routes as in `forward` (split_small_batches included); no cache is materialised."""
+        if self.training:
+            raise NotImplementedError("ConformerEncoder.forward_utterances: whole-utterance decoding is inference-only; call .eval()")
+        if not isinstance(self.position_encoding, RelativePositionalEncoding):
+            raise NotImplementedError("ConformerEncoder.forward_utterances needs use_relative=True: the absolute table is indexed by batch item "
+                                      "(a quirk of the reference) and would need a path of its own")
+        inputs, cmvn = self._cmvn_args(inputs)
+        cfm.require_hip(inputs, input_lengths)
+        x = self.embed.embed_frames(inputs, cmvn)
+        x, _ = self.position_encoding(x, 0)
+        Ts = x.size(1)
+        # keys j of item b with 6 + 4 j < len_b: the first out_lens[b] = (len_b - 3) // 4 of them (two stride-2 convolutions of 3 taps, no padding)
+        keys = cfm.valid_mask(input_lengths, Ts, first=6, stride=4).unsqueeze(1)
+        out_lens = torch.div(input_lengths.to(torch.int32) - 3, 4, rounding_mode="floor").clamp_(0, Ts).to(torch.int32)
+        pos_embed = self.embed.position_encoding(offset=0, size=Ts)
+        y, _ = self._run_blocks(x, keys, pos_embed, None, None, 0, pos_shared=True, streaming=bool(getattr(self, "split_small_batches", False)),
+                                utt_len=out_lens)
+        y.masked_fill_(~keys.transpose(1, 2), 0.0)
+        return y.to(inputs.dtype), out_lens
 
     def forward_window(self, batches, decoding_chunk_size=0, num_decoding_chunk_size=-1, return_rows=False):
         """Train mode: the micro-batches of ONE accumulation window (train.sh:36 accum_grad; the weights do not change between them) in a single

@@ -14,6 +14,9 @@ read does not change), and TransducerJoint.forward_window, whose packed lattice 
 
 `StreamingRecognizer` is the reference's streaming product -- `Transducer.greedy_search_streaming_app` (model.py:178-199) and
 `greedy_search_streaming_eval` (:126-165): feature windows (step) or waveform blocks (step_audio) in, tokens out -- for B streams at once, all state on the device.
+
+`OfflineRecognizer` is its whole-utterance product -- `Transducer.greedy_search` (model.py:202-212), the path of predict_step and of the /recognize/
+endpoint -- for a ragged batch of utterances at once.
 """
 import torch
 import torch.nn as nn
@@ -133,3 +136,34 @@ class StreamingRecognizer:
     def hyps(self):
         """Everything emitted per stream since its last reset."""
         return self.decoder.hyps()
+
+
+class OfflineRecognizer:
+    """Whole utterances in, tokens out, a ragged batch at a time: `ConformerEncoder.forward_utterances` feeding `greedy.BatchedGreedySearch` -- the
+    reference's `Transducer.greedy_search` (model.py:202-212: forward_chunk_by_chunk with the lengths in the chunk-size slot, i.e. one forward_chunk
+    over the whole utterance, then basic_greedy_search), which it runs at batch 1.  Item b's tokens are those of that batch-1 call on utterance b.
+
+    recognize(feats (B,T,F), lengths (B,)) -> list of B token lists; items shorter than 7 frames (no encoder frame) give [].
+    recognize_audio(samples (B,N) int16 | float32 on the int16 scale, lengths (B,) samples) -> the same from the waveform, through
+    fbank.KaldiFbank (deploy.py preprocess); `fbank`: a KaldiFbank, or None for the reference's settings without dither.
+    The lengths stay on the device; the only host read is the search's own.  encoder_out / encoder_out_lens: what the last call's search read."""
+
+    def __init__(self, encoder, predictor, joint, blank=0, n_steps=64, fbank=None, **search_kw):
+        import greedy
+        if joint.enc_ffn.in_features != encoder.encoder_dim:
+            raise ValueError("OfflineRecognizer: the joint reads %d encoder features, the encoder gives %d" % (joint.enc_ffn.in_features, encoder.encoder_dim))
+        self.encoder = encoder
+        self.search = greedy.BatchedGreedySearch(predictor, joint, blank=blank, n_steps=n_steps, **search_kw)
+        self.fbank = fbank
+        self.encoder_out = self.encoder_out_lens = None
+
+    @torch.no_grad()
+    def recognize(self, feats, lengths):
+        self.encoder_out, self.encoder_out_lens = self.encoder.forward_utterances(feats, lengths)
+        return self.search.search(self.encoder_out, self.encoder_out_lens)[0]
+
+    def recognize_audio(self, samples, lengths):
+        if self.fbank is None:
+            import fbank
+            self.fbank = fbank.KaldiFbank()
+        return self.recognize(*self.fbank(samples, lengths))

@@ -113,6 +113,11 @@ typedef struct {
      * drop2: a second, independent mask on the same element (the plain MHSA's extra dropout after linear_out, attention.py:177). */
     float drop_p, drop2_p;
     uint32_t drop_seed, drop2_seed;
+    /* ragged batches: rows are [B, row_T] flattened and row m = (b, t) with t >= row_len[b] is treated as row_mask[m] == 0 (mask_mode 0 only: the OUTPUT
+     * row is zeroed after the activation -- with CFM_ACT_GLU the depthwise convolution behind it then reads zeros past the utterance's end, as at a tensor
+     * edge).  NULL = every row is kept.  M % row_T == 0. */
+    const int32_t* row_len;
+    int32_t row_T;
 } cfm_gemm_desc;
 
 int cfm_gemm(const cfm_gemm_desc* d, cfm_stream_t stream);
@@ -269,6 +274,11 @@ typedef struct {
     const float* cin_tail_b;
     int32_t tail_pair; /* D = 512, a chain with a tail and no feed-forward: the tail's columns split over workgroup pairs (rows and LayerNorm computed by
                           both, written by the first); out_f32 must NOT alias head_res then */
+    /* ragged batches (whole utterances of different lengths in one batch): rows are [B, glu_T] flattened and the GLU output of row (b, t) with
+     * t >= glu_len[b] is written as ZERO -- a select behind the GLU, on the tail (tail_glu) and on the conv-in input stage (cin_*), so that the depthwise
+     * stage reads zeros past the utterance's end exactly as it does past a tensor edge.  NULL = no select.  Needs tail_glu or cin_a, M % glu_T == 0. */
+    const int32_t* glu_len;
+    int32_t glu_T;
 } cfm_rowchain_desc;
 
 int cfm_rowchain(const cfm_rowchain_desc* d, cfm_stream_t stream);
@@ -500,6 +510,12 @@ typedef struct {
     const cfm_layer_weights* next_w;
     float* next_x_out;
     int32_t macaron_done;
+    /* A ragged batch of WHOLE utterances (beyond the reference, which decodes them at batch 1): int32 [B], item b has utt_len[b] <= T frames and the frames
+     * behind them do not exist for the convolution module -- the GLU output of rows t >= utt_len[b] is zero, so the depthwise convolution sees what it
+     * sees at a tensor edge (masking in front of pointwise_conv1, as pad_valid does, leaves GLU(bias) there instead).  On every route.  The caller masks
+     * the keys t >= utt_len[b] through attn_mask; rows at and past utt_len[b] of x_out hold no defined result.  NULL = today's behaviour.
+     * Not with kv_ring, attn_cache, causal_conv or pad_valid. */
+    const int32_t* utt_len;
 } cfm_layer_io;
 
 /* The launch sequence of one block.  Every argument is checked and ONE route chosen before anything is launched (csrc/encoder.cpp select_route).
