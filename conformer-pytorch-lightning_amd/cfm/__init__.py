@@ -250,6 +250,7 @@ def lib():
         L.cfm_device_ok.restype = ctypes.c_int
         L.cfm_gemm.argtypes = [ctypes.POINTER(GemmDesc), c_p]
         L.cfm_attention.argtypes = [ctypes.POINTER(AttnDesc), c_p]
+        L.cfm_attention_group.argtypes = [ctypes.POINTER(AttnDesc), c_i32, c_p]
         L.cfm_ffn_fused.argtypes = [ctypes.POINTER(FfnDesc), c_p]
         L.cfm_rowchain.argtypes = [ctypes.POINTER(RowChainDesc), c_p]
         L.cfm_rowchain_supported.argtypes = [c_i32, c_i32]
@@ -303,12 +304,16 @@ def lib():
         L.cfm_gemm_tn.argtypes = [ctypes.POINTER(GemmTnDesc), c_p]
         L.cfm_gemm_tn_group.argtypes = [ctypes.POINTER(GemmTnDesc), c_i32, c_p]
         L.cfm_attention_bwd.argtypes = [ctypes.POINTER(AttnBwdDesc), c_p]
+        L.cfm_attention_bwd_group.argtypes = [ctypes.POINTER(AttnBwdDesc), c_i32, c_p]
         L.cfm_layernorm_bwd_ws.argtypes = [c_i64, c_i32]
         L.cfm_layernorm_bwd.argtypes = [c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_i64, c_i32, c_p]
         L.cfm_glu_bwd.argtypes = [c_p, c_i32, c_p, c_i32, c_p, c_i32, c_i64, c_i32, c_p]
         L.cfm_dwconv_bn_ws.argtypes = [c_i32, c_i32, c_i32]
         L.cfm_dwconv_bn_train.argtypes = [c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_i32, c_p, c_i32, c_i32, c_i32, c_i32, c_p]
         L.cfm_dwconv_bn_train_bwd.argtypes = [c_p, c_i32, c_p, c_p, c_p, c_i32, c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p]
+        L.cfm_dwconv_bn_train_groups.argtypes = [c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_i32, c_p, ctypes.POINTER(TrainGroup), c_i32, c_i32, c_i32, c_p]
+        L.cfm_dwconv_bn_train_bwd_groups.argtypes = [c_p, c_i32, c_p, c_p, c_p, c_i32, c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.POINTER(TrainGroup), c_i32, c_i32, c_i32,
+                                                     c_i32, c_p, c_p, c_p]
         L.cfm_col2im_relu_bwd.argtypes = [c_p, c_i32, c_p, c_i32, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p]
         L.cfm_conv1_wgrad_ws.argtypes = [c_i32, c_i32, c_i32]
         L.cfm_conv1_wgrad.argtypes = [c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p]
@@ -342,6 +347,7 @@ def lib():
                      "cfm_encoder_layer_forward", "cfm_ctc_nll", "cfm_joint_act", "cfm_joint_act_bwd", "cfm_rnnt_nll", "cfm_rnnt_grad", "cfm_prof_entry", "cfm_gemm_tn", "cfm_gemm_tn_group", "cfm_attention_bwd",
                      "cfm_layernorm_bwd", "cfm_glu_bwd", "cfm_dwconv_bn_train", "cfm_dwconv_bn_train_bwd", "cfm_col2im_relu_bwd", "cfm_conv1_wgrad",
                      "cfm_ctc_nll_train_groups", "cfm_ctc_grad", "cfm_adam_step", "cfm_adam_clip_step", "cfm_sumsq", "cfm_dropout_rows", "cfm_dropout_mask", "cfm_pack_matrices", "cfm_pack_vectors", "cfm_greedy_step", "cfm_greedy_chunk_begin", "cfm_greedy_chunk_step", "cfm_fbank", "cfm_fbank_stream", "cfm_ffn_split", "cfm_ffn_split_supported", "cfm_layernorm_bwd_fused", "cfm_dwconv_bn_train_bwd_acc",
+                     "cfm_attention_group", "cfm_attention_bwd_group", "cfm_dwconv_bn_train_groups", "cfm_dwconv_bn_train_bwd_groups",
                      "cfm_encoder_train_forward", "cfm_encoder_train_backward", "cfm_stream_prep", "cfm_kv_ring_write", "cfm_stream_advance", "cfm_dwconv_causal_bn_silu", "cfm_conv_cache_update"):
             getattr(L, name).restype = ctypes.c_int
         _lib = L

@@ -6,7 +6,7 @@ import torch
 
 import cfm as _c
 
-__all__ = ["fbank", "fbank_stream", "stream_prep", "stream_advance", "dwconv_causal_bn_silu", "conv_cache_update", "dropout_rows", "dropout_mask", "set_deterministic", "gemm_tn", "gemm_tn_group", "layernorm_bwd", "glu_bwd", "dwconv_bn_train", "dwconv_bn_train_bwd", "col2im_relu_bwd", "conv1_wgrad", "attention_bwd",
+__all__ = ["fbank", "fbank_stream", "stream_prep", "stream_advance", "dwconv_causal_bn_silu", "conv_cache_update", "dropout_rows", "dropout_mask", "set_deterministic", "gemm_tn", "gemm_tn_group", "layernorm_bwd", "glu_bwd", "dwconv_bn_train", "dwconv_bn_train_bwd", "dwconv_bn_train_groups", "dwconv_bn_train_bwd_groups", "col2im_relu_bwd", "conv1_wgrad", "attention_bwd", "attention_group", "attention_bwd_group",
            "ctc_nll_train_groups", "ctc_grad", "rnnt_nll", "rnnt_grad", "joint_act_bwd", "rnnt_nll_packed", "joint_act_packed", "joint_act_packed_bwd", "ffn_split", "adam_step", "adam_clip_step", "sumsq", "scratch_stats",
            "gemm", "ffn_fused", "ffn_fused_supported", "rowchain", "rowchain_supported", "rowchain_pair_supported", "layernorm", "attention", "kv_cache_pack", "dwconv_bn_silu", "conv1_relu", "conv1_relu_mma_supported", "conv12_relu", "conv12_supported", "ctc_nll", "joint_act", "valid_mask", "chunk_mask",
            "attn_mask_combine", "cast", "add_rows", "scratch", "prof_enable", "prof_reset", "prof_table", "as_u8_mask"]
@@ -287,21 +287,19 @@ def as_u8_mask(mask):
     return (mask != 0).contiguous().view(torch.uint8)
 
 
-def attention(q, k, v, B, H, Tq, Tk, dk, q_str, k_str, v_str, out, p=None, p_str=(0, 0), bias_u=None, bias_v=None, mask=None,
-              mask_str=(0, 0), mma_code=_c.BF16, split=False, scale=None, lse=None, drop=None):
-    """Fused attention; *_str are (batch stride, time stride[, head stride]) in ELEMENTS (see include/cfm.h).  lse: optional f32 [B,H,Tq]
-    output (training): the log-sum-exp of each row's scaled masked scores."""
+def _attn_fill(d, who, q, k, v, B, H, Tq, Tk, dk, q_str, k_str, v_str, out, p=None, p_str=(0, 0), bias_u=None, bias_v=None, mask=None,
+               mask_str=(0, 0), mma_code=_c.BF16, split=False, scale=None, lse=None, drop=None):
+    """Checks one attention problem and fills its cfm_attn_desc: the single and the grouped wrapper share it, so the two cannot drift."""
     _c.require_hip(q, k, v, p, out, mask, bias_u, bias_v, lse)
     if lse is not None and (lse.dtype != torch.float32 or lse.numel() != B * H * Tq or not lse.is_contiguous()):
-        raise ValueError("cfm.attention: lse must be contiguous float32 [B,H,Tq]")
+        raise ValueError("cfm.%s: lse must be contiguous float32 [B,H,Tq]" % who)
     for what, t, strides in (("q", q, q_str), ("k", k, k_str), ("v", v, v_str)):
         # [rows, cols] and [B, T, cols] tensors carry the strides the call passes beside them; p and mask are taken on the numbers alone (their
         # rank does not say which axis is batch: a [B, Tk] pad mask and a [R, D] row matrix of positions are both 2-D)
-        _strides_match("attention", what, t, strides[0], strides[1])
-    _dense("attention", out=out, bias_u=bias_u, bias_v=bias_v)       # out is [B,Tq,H*dk] row-major: cfm_attn_desc has no stride for it
+        _strides_match(who, what, t, strides[0], strides[1])
+    _dense(who, out=out, bias_u=bias_u, bias_v=bias_v)               # out is [B,Tq,H*dk] row-major: cfm_attn_desc has no stride for it
     if out.numel() != B * Tq * H * dk:
-        raise ValueError("cfm.attention: out must hold [B,Tq,H*dk] = %d elements, got %s" % (B * Tq * H * dk, tuple(out.shape)))
-    d = _c.AttnDesc()
+        raise ValueError("cfm.%s: out must hold [B,Tq,H*dk] = %d elements, got %s" % (who, B * Tq * H * dk, tuple(out.shape)))
     d.q, d.k, d.v, d.p, d.out = _c.ptr(q), _c.ptr(k), _c.ptr(v), _c.ptr(p), _c.ptr(out)
     d.bias_u, d.bias_v, d.mask = _c.ptr(bias_u), _c.ptr(bias_v), _c.ptr(mask)
     d.q_sb, d.q_st = q_str
@@ -317,8 +315,30 @@ def attention(q, k, v, B, H, Tq, Tk, dk, q_str, k_str, v_str, out, p=None, p_str
     d.lse = _c.ptr(lse)
     if drop is not None and drop[0] > 0.0:       # (p, seed): dropout on the probabilities (train mode)
         d.drop_p, d.drop_seed = float(drop[0]), int(drop[1]) & 0xFFFFFFFF
+
+
+def attention(q, k, v, B, H, Tq, Tk, dk, q_str, k_str, v_str, out, p=None, p_str=(0, 0), bias_u=None, bias_v=None, mask=None,
+              mask_str=(0, 0), mma_code=_c.BF16, split=False, scale=None, lse=None, drop=None):
+    """Fused attention; *_str are (batch stride, time stride[, head stride]) in ELEMENTS (see include/cfm.h).  lse: optional f32 [B,H,Tq]
+    output (training): the log-sum-exp of each row's scaled masked scores."""
+    d = _c.AttnDesc()
+    _attn_fill(d, "attention", q, k, v, B, H, Tq, Tk, dk, q_str, k_str, v_str, out, p=p, p_str=p_str, bias_u=bias_u, bias_v=bias_v, mask=mask,
+               mask_str=mask_str, mma_code=mma_code, split=split, scale=scale, lse=lse, drop=drop)
     _c.check(_c.lib().cfm_attention(ctypes.byref(d), _c.stream()), "cfm_attention")
     return out
+
+
+def attention_group(problems):
+    """The attention problems of a training window (include/cfm.h cfm_attention_group: one launch when every problem qualifies, else one each).
+    problems: a list of dicts, each holding the arguments of attention() by name; returns the `out` tensors in order."""
+    n = len(problems)
+    if n == 0:
+        raise ValueError("cfm.attention_group: no problems")
+    arr = (_c.AttnDesc * n)()
+    for d, kw in zip(arr, problems):
+        _attn_fill(d, "attention_group", **kw)
+    _c.check(_c.lib().cfm_attention_group(arr, n, _c.stream()), "cfm_attention_group")
+    return [kw["out"] for kw in problems]
 
 
 def kv_cache_pack(old_cache, k, v, k_str, v_str, B, H, Tn, dk):
@@ -691,6 +711,135 @@ def dwconv_bn_train_bwd(ds, c, stats, g, w, dg_dtype):
     return dg, dw_w, dw_b, dgamma, dbeta
 
 
+def _train_groups(who, groups, rows):
+    """The contiguous cfm_train_group table of a window from its (B, T) pairs; every row matrix must be dense with sum(B*T) rows."""
+    n = len(groups)
+    if not 1 <= n <= 8:
+        raise ValueError("cfm.%s: %d row groups (1 .. 8)" % (who, n))
+    arr = (_c.TrainGroup * n)()
+    row0 = 0
+    for tg, (B, T) in zip(arr, groups):
+        if B <= 0 or T <= 0:
+            raise ValueError("cfm.%s: empty group (B=%d, T=%d)" % (who, B, T))
+        tg.B, tg.T, tg.row0 = B, T, row0
+        row0 += B * T
+    if row0 != rows:
+        raise ValueError("cfm.%s: the groups hold %d rows but the row matrices %d" % (who, row0, rows))
+    return arr
+
+
+def _row_matrix(who, name, t, M, cols, dtype=None):
+    if t is None:
+        return
+    if t.dim() != 2 or tuple(t.shape) != (M, cols) or not t.is_contiguous() or (dtype is not None and t.dtype != dtype):
+        raise ValueError("cfm.%s: %s must be a contiguous %s[%d,%d] row matrix (the C ABI has no stride for it), got %s %s strides %s"
+                         % (who, name, "" if dtype is None else str(dtype) + " ", M, cols, t.dtype, tuple(t.shape), t.stride()))
+
+
+def _vec_f32(who, D, **vecs):
+    for k, t in vecs.items():
+        if t is not None and (t.dtype != torch.float32 or t.numel() != D or not t.is_contiguous()):
+            raise ValueError("cfm.%s: %s must be contiguous float32 [%d] (the C ABI has no stride for it)" % (who, k, D))
+
+
+def _dw_window_ws(groups, D, ws, who, device):
+    need = sum(_c.lib().cfm_dwconv_bn_ws(B, T, D) for B, T in groups)            # include/cfm.h: the SUM over the groups
+    if ws is None:
+        return scratch("dwbn", need, torch.float32, device)
+    if ws.dtype != torch.float32 or ws.numel() < need or not ws.is_contiguous():
+        raise ValueError("cfm.%s: ws must be contiguous float32 with at least %d elements" % (who, need))
+    return ws
+
+
+def dwconv_bn_train_groups(g, groups, w, dw_bias, gamma, beta, running_mean=None, running_var=None, momentum=0.1, eps=1e-5, s_dtype=None, c=None, stats=None, s=None, ws=None):
+    """dwconv_bn_train over the micro-batches of a window in one launch per stage (include/cfm.h cfm_dwconv_bn_train_groups): g is the window's
+    [M, D] row matrix, groups its (B, T) pairs back to back.  -> (c f32 [M,D], stats f32 [n,4,D], s [M,D]); each group has its own batch
+    statistics, the optional running statistics take the momentum updates group after group."""
+    who = "dwconv_bn_train_groups"
+    _c.require_hip(g, w, dw_bias, gamma, beta, running_mean, running_var, c, stats, s, ws)
+    if g.dim() != 2:
+        raise ValueError("cfm.%s: g must be the window's [M,D] row matrix" % who)
+    M, D = g.shape
+    n = len(groups)
+    arr = _train_groups(who, groups, M)
+    _row_matrix(who, "g", g, M, D)
+    _vec_f32(who, D, dw_bias=dw_bias, gamma=gamma, beta=beta, running_mean=running_mean, running_var=running_var)
+    if (running_mean is None) != (running_var is None):
+        raise ValueError("cfm.%s: running_mean and running_var go together" % who)
+    if w.dtype != torch.float32 or w.dim() != 2 or w.shape[0] != D or not w.is_contiguous():
+        raise ValueError("cfm.%s: w must be contiguous float32 [D,K] (the C ABI has no stride for it)" % who)
+    dev = g.device
+    c = torch.empty((M, D), dtype=torch.float32, device=dev) if c is None else c
+    s = torch.empty((M, D), dtype=s_dtype if s_dtype is not None else g.dtype, device=dev) if s is None else s
+    stats = torch.empty((n, 4, D), dtype=torch.float32, device=dev) if stats is None else stats
+    _row_matrix(who, "c", c, M, D, torch.float32)
+    _row_matrix(who, "s", s, M, D)
+    if stats.dtype != torch.float32 or stats.numel() != n * 4 * D or not stats.is_contiguous():
+        raise ValueError("cfm.%s: stats must be contiguous float32 [n_groups,4,D]" % who)
+    ws = _dw_window_ws(groups, D, ws, who, dev)
+    _c.check(_c.lib().cfm_dwconv_bn_train_groups(_c.ptr(g), _c.dt_code(g), _c.ptr(w), _c.ptr(dw_bias), _c.ptr(gamma), _c.ptr(beta), _c.ptr(running_mean),
+                                                 _c.ptr(running_var), momentum, eps, _c.ptr(c), _c.ptr(stats), _c.ptr(s), _c.dt_code(s), _c.ptr(ws), arr, n, D,
+                                                 w.shape[1], _c.stream()), "cfm_dwconv_bn_train_groups")
+    return c, stats, s
+
+
+def dwconv_bn_train_bwd_groups(ds, c, stats, g, groups, w, dg_dtype=None, accumulate=False, glu_u=None, glu_du=None, dg=None, dw_w=None, dw_b=None, dgamma=None,
+                               dbeta=None, dy_ws=None, ws=None):
+    """dwconv_bn_train_bwd over the micro-batches of a window (include/cfm.h cfm_dwconv_bn_train_bwd_groups): row matrices [M, D], stats [n,4,D].
+    -> (dg [M,D] or None, dw_w, dw_b, dgamma, dbeta): dg per group, the four parameter gradients summed over the groups -- on top of what the
+    buffers hold with accumulate (they must then be passed).  glu_u [M,2D] (with glu_du, or one is made): the GLU backward in the same launch,
+    du instead of dg; returned in place of dg."""
+    who = "dwconv_bn_train_bwd_groups"
+    _c.require_hip(ds, c, stats, g, w, glu_u, glu_du, dg, dw_w, dw_b, dgamma, dbeta, dy_ws, ws)
+    if g.dim() != 2:
+        raise ValueError("cfm.%s: g must be the window's [M,D] row matrix" % who)
+    M, D = g.shape
+    n = len(groups)
+    arr = _train_groups(who, groups, M)
+    _row_matrix(who, "g", g, M, D)
+    _row_matrix(who, "ds", ds, M, D)
+    _row_matrix(who, "c", c, M, D, torch.float32)
+    if stats.dtype != torch.float32 or stats.numel() != n * 4 * D or not stats.is_contiguous():
+        raise ValueError("cfm.%s: stats must be contiguous float32 [n_groups,4,D]" % who)
+    if w.dtype != torch.float32 or w.dim() != 2 or w.shape[0] != D or not w.is_contiguous():
+        raise ValueError("cfm.%s: w must be contiguous float32 [D,K] (the C ABI has no stride for it)" % who)
+    dev = g.device
+    K = w.shape[1]
+    if glu_du is not None and glu_u is None:
+        raise ValueError("cfm.%s: glu_du without glu_u" % who)
+    fused = glu_u is not None
+    if fused:
+        if D % 16:
+            raise ValueError("cfm.%s: the fused GLU backward needs D %% 16 == 0 (D=%d)" % (who, D))
+        if dg is not None:
+            raise ValueError("cfm.%s: dg is not written by the fused GLU backward" % who)
+        if dg_dtype is not None and dg_dtype != g.dtype:
+            raise ValueError("cfm.%s: the fused GLU backward needs g and dg of one dtype" % who)
+        glu_du = torch.empty((M, 2 * D), dtype=g.dtype, device=dev) if glu_du is None else glu_du
+        _row_matrix(who, "glu_u", glu_u, M, 2 * D, g.dtype)
+        _row_matrix(who, "glu_du", glu_du, M, 2 * D, g.dtype)
+        dg_code = _c.dt_code(g)
+    else:
+        dg = torch.empty((M, D), dtype=dg_dtype if dg_dtype is not None else g.dtype, device=dev) if dg is None else dg
+        _row_matrix(who, "dg", dg, M, D)
+        dg_code = _c.dt_code(dg)
+    given = [t is not None for t in (dw_w, dw_b, dgamma, dbeta)]
+    if accumulate and not all(given):
+        raise ValueError("cfm.%s: accumulate adds to dw_w, dw_b, dgamma, dbeta: pass all four" % who)
+    dw_w = torch.empty((D, K), dtype=torch.float32, device=dev) if dw_w is None else dw_w
+    dw_b, dgamma, dbeta = (torch.empty((D,), dtype=torch.float32, device=dev) if t is None else t for t in (dw_b, dgamma, dbeta))
+    _row_matrix(who, "dw_w", dw_w, D, K, torch.float32)
+    _vec_f32(who, D, dw_b=dw_b, dgamma=dgamma, dbeta=dbeta)
+    dy_ws = scratch("dwbn_dy", M * D, torch.float32, dev) if dy_ws is None else dy_ws
+    if dy_ws.dtype != torch.float32 or dy_ws.numel() < M * D or not dy_ws.is_contiguous():
+        raise ValueError("cfm.%s: dy_ws must be contiguous float32 with at least M*D = %d elements" % (who, M * D))
+    ws = _dw_window_ws(groups, D, ws, who, dev)
+    _c.check(_c.lib().cfm_dwconv_bn_train_bwd_groups(_c.ptr(ds), _c.dt_code(ds), _c.ptr(c), _c.ptr(stats), _c.ptr(g), _c.dt_code(g), _c.ptr(w), _c.ptr(dg), dg_code,
+                                                     _c.ptr(dw_w), _c.ptr(dw_b), _c.ptr(dgamma), _c.ptr(dbeta), _c.ptr(dy_ws), _c.ptr(ws), arr, n, D, K,
+                                                     1 if accumulate else 0, _c.ptr(glu_u), _c.ptr(glu_du), _c.stream()), "cfm_dwconv_bn_train_bwd_groups")
+    return (glu_du if fused else dg), dw_w, dw_b, dgamma, dbeta
+
+
 def col2im_relu_bwd(dcol, h1, out_dtype):
     """dcol [B*T2*F2, 9C] (K order (kt,kf,c)), h1 [B,T1,F1,C] -> dh1 = (h1 > 0) * col2im(dcol)."""
     _c.require_hip(dcol, h1)
@@ -725,18 +874,20 @@ def conv1_wgrad(dh1, x, cmvn=None):
     return dw, db
 
 
-def attention_bwd(q, k, v, out, dout, lse, B, H, Tq, Tk, dk, q_str, k_str, v_str, dq, dkk, dv, mask=None, mask_str=(0, 0), mma_code=_c.BF16, split=False,
-                  scale=None, drop=None):
-    """Backward of attention(); q/k/v and dq/dkk/dv share strides ((batch, time) in elements, head h at h*dk); see include/cfm.h."""
-    _c.require_hip(q, k, v, out, dout, lse, dq, dkk, dv, mask)
-    _dense("attention_bwd", out=out, dout=dout, lse=lse)             # [B,Tq,H*dk] / [B,H,Tq] row-major: no strides in cfm_attn_bwd_desc
+def _attn_bwd_fill(d, who, q, k, v, out, dout, lse, B, H, Tq, Tk, dk, q_str, k_str, v_str, dq, dkk, dv, delta, mask=None, mask_str=(0, 0), mma_code=_c.BF16,
+                   split=False, scale=None, drop=None):
+    """Checks one attention backward problem and fills its cfm_attn_bwd_desc (shared by the single and the grouped wrapper)."""
+    _c.require_hip(q, k, v, out, dout, lse, dq, dkk, dv, mask, delta)
+    _dense(who, out=out, dout=dout, lse=lse, delta=delta)            # [B,Tq,H*dk] / [B,H,Tq] row-major: no strides in cfm_attn_bwd_desc
     for what, t, (sb, st) in (("q", q, q_str), ("k", k, k_str), ("v", v, v_str), ("dq", dq, q_str), ("dk", dkk, k_str), ("dv", dv, v_str)):
         # 2-D [B*T, ...] views carry the time stride, 3-D ones both; cfm_attn_bwd_desc has ONE set of strides for an operand and its gradient
-        _strides_match("attention_bwd", what, t, sb, st)
-    d = _c.AttnBwdDesc()
+        _strides_match(who, what, t, sb, st)
+    if delta.dtype != torch.float32 or delta.numel() != B * H * Tq:
+        raise ValueError("cfm.%s: delta must be float32 [B,H,Tq] = %d elements, got %s %s" % (who, B * H * Tq, delta.dtype, tuple(delta.shape)))
+    if lse.dtype != torch.float32 or lse.numel() != B * H * Tq or out.numel() != B * Tq * H * dk or dout.numel() != B * Tq * H * dk:
+        raise ValueError("cfm.%s: lse must be float32 [B,H,Tq], out and dout [B,Tq,H*dk]" % who)
     d.q, d.k, d.v, d.mask, d.out, d.dout, d.lse = _c.ptr(q), _c.ptr(k), _c.ptr(v), _c.ptr(mask), _c.ptr(out), _c.ptr(dout), _c.ptr(lse)
     d.grad_q, d.grad_k, d.grad_v = _c.ptr(dq), _c.ptr(dkk), _c.ptr(dv)
-    delta = scratch("attn_delta", B * H * Tq, torch.float32, q.device)
     d.delta = _c.ptr(delta)
     d.q_sb, d.q_st = q_str
     d.k_sb, d.k_st = k_str
@@ -744,12 +895,44 @@ def attention_bwd(q, k, v, out, dout, lse, B, H, Tq, Tk, dk, q_str, k_str, v_str
     d.m_sb, d.m_sq = mask_str
     d.B, d.H, d.Tq, d.Tk, d.dk = B, H, Tq, Tk, dk
     if not (q.dtype == k.dtype == v.dtype == out.dtype == dq.dtype == dkk.dtype == dv.dtype):
-        raise ValueError("cfm.attention_bwd: q, k, v, out and the gradients must share one dtype")
+        raise ValueError("cfm.%s: q, k, v, out and the gradients must share one dtype" % who)
     d.io_dtype, d.dout_dtype, d.mma_dtype, d.split = _c.dt_code(q), _c.dt_code(dout), mma_code, 1 if split else 0
     d.scale = scale if scale is not None else float(dk) ** -0.5
     if drop is not None and drop[0] > 0.0:
         d.drop_p, d.drop_seed = float(drop[0]), int(drop[1]) & 0xFFFFFFFF
+
+
+def attention_bwd(q, k, v, out, dout, lse, B, H, Tq, Tk, dk, q_str, k_str, v_str, dq, dkk, dv, mask=None, mask_str=(0, 0), mma_code=_c.BF16, split=False,
+                  scale=None, drop=None, delta=None):
+    """Backward of attention(); q/k/v and dq/dkk/dv share strides ((batch, time) in elements, head h at h*dk); see include/cfm.h.
+    delta: optional f32 [B,H,Tq] scratch (taken from the arena when absent)."""
+    _c.require_hip(q)
+    if delta is None:
+        delta = scratch("attn_delta", B * H * Tq, torch.float32, q.device)
+    d = _c.AttnBwdDesc()
+    _attn_bwd_fill(d, "attention_bwd", q, k, v, out, dout, lse, B, H, Tq, Tk, dk, q_str, k_str, v_str, dq, dkk, dv, delta, mask=mask, mask_str=mask_str,
+                   mma_code=mma_code, split=split, scale=scale, drop=drop)
     _c.check(_c.lib().cfm_attention_bwd(ctypes.byref(d), _c.stream()), "cfm_attention_bwd")
+
+
+def attention_bwd_group(problems):
+    """The attention backward problems of a training window (include/cfm.h cfm_attention_bwd_group).  problems: a list of dicts, each holding the
+    arguments of attention_bwd() by name; a problem without `delta` gets its [B,H,Tq] slice of ONE arena buffer, at the running offset."""
+    n = len(problems)
+    if n == 0:
+        raise ValueError("cfm.attention_bwd_group: no problems")
+    need = [kw["B"] * kw["H"] * kw["Tq"] for kw in problems]
+    _c.require_hip(problems[0]["q"])
+    pool = scratch("attn_delta", sum(need), torch.float32, problems[0]["q"].device) if any(kw.get("delta") is None for kw in problems) else None
+    arr = (_c.AttnBwdDesc * n)()
+    off = 0
+    for d, kw, m in zip(arr, problems, need):
+        kw = dict(kw)
+        if kw.get("delta") is None:
+            kw["delta"] = pool[off:off + m]
+        off += m
+        _attn_bwd_fill(d, "attention_bwd_group", **kw)
+    _c.check(_c.lib().cfm_attention_bwd_group(arr, n, _c.stream()), "cfm_attention_bwd_group")
 
 
 def _ctc_args(logits, enc_lens, labels, label_lens):
