@@ -138,12 +138,6 @@ __device__ __forceinline__ void row_frags(const void* src, int dt, int64_t off, 
     }
 }
 
-__device__ __forceinline__ void store_row4(void* base, int dt, int64_t off, const f32x4& o) {
-    if (dt == CFM_F32) *(f32x4*)((float*)base + off) = o;
-    else if (dt == CFM_BF16) *(u32x2*)((u16*)base + off) = (u32x2){pack2<BF16>(o.x, o.y), pack2<BF16>(o.z, o.w)};
-    else *(u32x2*)((u16*)base + off) = (u32x2){pack2<F16>(o.x, o.y), pack2<F16>(o.z, o.w)};
-}
-
 template <typename HT, bool SPLIT>
 __global__ __launch_bounds__(256) void cfm_attn_bwd_dq_kernel(const AttnBwdArgs a) {
     constexpr int NPL = SPLIT ? 2 : 1;
@@ -202,7 +196,7 @@ __global__ __launch_bounds__(256) void cfm_attn_bwd_dq_kernel(const AttnBwdArgs 
 #pragma unroll
         for (int fd = 0; fd < 4; ++fd) {
             const int d = fd * 16 + g * 4;
-            if (d < dk) store_row4(a.dq, a.io_dt, ob + d, acc[fd]);
+            if (d < dk) store4(a.dq, a.io_dt, ob + d, acc[fd]);
         }
     }
 }
@@ -281,8 +275,8 @@ __global__ __launch_bounds__(256) void cfm_attn_bwd_dkv_kernel(const AttnBwdArgs
         for (int fd = 0; fd < 4; ++fd) {
             const int d = fd * 16 + g * 4;
             if (d < dk) {
-                store_row4(a.dkk, a.io_dt, ko + d, acc_k[fd]);
-                store_row4(a.dv, a.io_dt, vo + d, acc_v[fd]);
+                store4(a.dkk, a.io_dt, ko + d, acc_k[fd]);
+                store4(a.dv, a.io_dt, vo + d, acc_v[fd]);
             }
         }
     }
@@ -429,7 +423,7 @@ __device__ __forceinline__ void attn_bwd_dq_fast_body(const AttnBwdArgs& a, cons
     if (qi < a.Tq) {
         const int64_t ob = (int64_t)b * a.q_sb + (int64_t)qi * a.q_st + h * dk;
 #pragma unroll
-        for (int fd = 0; fd < 4; ++fd) store_row4(a.dq, a.io_dt, ob + fd * 16 + g * 4, acc[fd]);
+        for (int fd = 0; fd < 4; ++fd) store4(a.dq, a.io_dt, ob + fd * 16 + g * 4, acc[fd]);
     }
 }
 
@@ -563,8 +557,8 @@ __device__ __forceinline__ void attn_bwd_dkv_fast_body(const AttnBwdArgs& a, con
         const int64_t ko = (int64_t)b * a.k_sb + (int64_t)kj * a.k_st + h * dk, vo = (int64_t)b * a.v_sb + (int64_t)kj * a.v_st + h * dk;
 #pragma unroll
         for (int fd = 0; fd < 4; ++fd) {
-            store_row4(a.dkk, a.io_dt, ko + fd * 16 + g * 4, acc_k[fd]);
-            store_row4(a.dv, a.io_dt, vo + fd * 16 + g * 4, acc_v[fd]);
+            store4(a.dkk, a.io_dt, ko + fd * 16 + g * 4, acc_k[fd]);
+            store4(a.dv, a.io_dt, vo + fd * 16 + g * 4, acc_v[fd]);
         }
     }
 }

@@ -50,6 +50,11 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+// the same vectors where the address is only known to be dword aligned (rows of a [M, ld] matrix with ld % 4 == 2): global memory needs
+// dword alignment only, so an access through these stays ONE global_load / global_store_dwordx4 / dwordx2
+typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+typedef float f32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
+typedef unsigned int u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 typedef unsigned short u16;
@@ -147,7 +152,66 @@ static inline CfmDrop cfm_make_drop(float p, unsigned seed) {
     return d;
 }
 
-// generic scalar load/store by runtime dtype (slow paths, edges)
+// ---------------------------------------------------------------------------------------------
+// typed loads / stores: element i of an array of T as f32 and back.  T is the element type tag `float`, `BF16` or `F16`;
+// cfm_elt_t<dtype code> maps a CFM_F32 / CFM_BF16 / CFM_F16 template argument to it, cfm_dtype_of<T> maps back.
+//   ld1 / st1    one value
+//   ld4 / st4    four consecutive values in one 16-byte (f32) / 8-byte (16-bit) access: i % 4 == 0 and a base aligned to that size
+//   st2          two consecutive values (the last column pair of a row with N % 4 == 2)
+//   A4 = true    the address is only dword aligned (the *_a4 types above): still one instruction
+// load_as_f32 / store_from_f32 / load4 / store4 / store2 are the same by RUN-TIME dtype (a branch per access: edges and epilogues;
+// a loop of many loads wants the compile-time forms, see train.hip's depthwise-conv backward).
+// ---------------------------------------------------------------------------------------------
+template <int DT> struct cfm_elt;
+template <> struct cfm_elt<CFM_F32> { typedef float type; };
+template <> struct cfm_elt<CFM_BF16> { typedef BF16 type; };
+template <> struct cfm_elt<CFM_F16> { typedef F16 type; };
+template <int DT> using cfm_elt_t = typename cfm_elt<DT>::type;
+template <typename T> inline constexpr int cfm_dtype_of = T::kId;
+template <> inline constexpr int cfm_dtype_of<float> = CFM_F32;
+template <typename T> constexpr bool cfm_is_f32 = cfm_dtype_of<T> == CFM_F32;
+
+template <typename HT>
+__device__ __forceinline__ f32x4 unpack4(u32x2 r) {  // 4 consecutive 16-bit values -> f32
+    return (f32x4){HT::to_f32((u16)(r.x & 0xffffu)), HT::to_f32((u16)(r.x >> 16)), HT::to_f32((u16)(r.y & 0xffffu)), HT::to_f32((u16)(r.y >> 16))};
+}
+
+template <typename T>
+__device__ __forceinline__ float ld1(const void* p, int64_t i) {
+    if constexpr (cfm_is_f32<T>) return ((const float*)p)[i];
+    else return T::to_f32(((const u16*)p)[i]);
+}
+template <typename T>
+__device__ __forceinline__ void st1(void* p, int64_t i, float v) {
+    if constexpr (cfm_is_f32<T>) ((float*)p)[i] = v;
+    else ((u16*)p)[i] = T::from_f32(v);
+}
+template <typename T>
+__device__ __forceinline__ f32x4 ld4(const void* p, int64_t i) {
+    if constexpr (cfm_is_f32<T>) return *(const f32x4*)((const float*)p + i);
+    else return unpack4<T>(*(const u32x2*)((const u16*)p + i));
+}
+template <typename T, bool A4 = false>
+__device__ __forceinline__ void st4(void* p, int64_t i, const f32x4& v) {
+    if constexpr (cfm_is_f32<T>) {
+        if constexpr (A4) *(f32x4_a4*)((float*)p + i) = v;
+        else *(f32x4*)((float*)p + i) = v;
+    } else {
+        const u32x2 w = {pack2<T>(v.x, v.y), pack2<T>(v.z, v.w)};
+        if constexpr (A4) *(u32x2_a4*)((u16*)p + i) = w;
+        else *(u32x2*)((u16*)p + i) = w;
+    }
+}
+template <typename T, bool A4 = false>
+__device__ __forceinline__ void st2(void* p, int64_t i, const f32x2& v) {
+    if constexpr (cfm_is_f32<T>) {
+        if constexpr (A4) *(f32x2_a4*)((float*)p + i) = v;
+        else *(f32x2*)((float*)p + i) = v;
+    } else {
+        *(unsigned*)((u16*)p + i) = pack2<T>(v.x, v.y);
+    }
+}
+
 __device__ __forceinline__ float load_as_f32(const void* p, int64_t i, int dt) {
     if (dt == CFM_F32) return ((const float*)p)[i];
     u16 v = ((const u16*)p)[i];
@@ -158,6 +222,33 @@ __device__ __forceinline__ void store_from_f32(void* p, int64_t i, int dt, float
         ((float*)p)[i] = v;
     else
         ((u16*)p)[i] = dt == CFM_BF16 ? BF16::from_f32(v) : F16::from_f32(v);
+}
+__device__ __forceinline__ f32x4 load4(const void* p, int dt, int64_t i) {
+    if (dt == CFM_F32) return ld4<float>(p, i);
+    const u32x2 r = *(const u32x2*)((const u16*)p + i);  // one load for both 16-bit types
+    return dt == CFM_BF16 ? unpack4<BF16>(r) : unpack4<F16>(r);
+}
+template <bool A4 = false>
+__device__ __forceinline__ void store4(void* p, int dt, int64_t i, const f32x4& v) {
+    if (dt == CFM_F32) st4<float, A4>(p, i, v);
+    else if (dt == CFM_BF16) st4<BF16, A4>(p, i, v);
+    else st4<F16, A4>(p, i, v);
+}
+template <bool A4 = false>
+__device__ __forceinline__ void store2(void* p, int dt, int64_t i, const f32x2& v) {
+    if (dt == CFM_F32) st2<float, A4>(p, i, v);
+    else if (dt == CFM_BF16) st2<BF16, A4>(p, i, v);
+    else st2<F16, A4>(p, i, v);
+}
+
+// host: calls f with a value of the element type of a run-time dtype, so that a generic lambda can name the type:
+//   cfm_by_dtype(dt, [&](auto tag) { return launch<decltype(tag)>(...); })
+// A kernel templated on the dtype code instead takes cfm_dtype_of<decltype(tag)>.  Callers check the code first; any other code selects float.
+template <typename F>
+static inline decltype(auto) cfm_by_dtype(int dt, F&& f) {
+    if (dt == CFM_BF16) return f(BF16());
+    if (dt == CFM_F16) return f(F16());
+    return f(float());
 }
 
 // Sum over the 64 lanes of a wavefront, result in every lane (EXEC must be all ones).  Four DPP adds fold each row of 16
@@ -176,4 +267,32 @@ __device__ __forceinline__ float wave_sum(float v) {
     const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 0)), r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 16));
     const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 32)), r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48));
     return (r0 + r1) + (r2 + r3);
+}
+
+// Maximum over the 64 lanes, result in every lane: the six-step xor shuffle (the CTC / RNN-T row passes call it once per row)
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+// log(exp(a) + exp(b)) on the hardware exp2/log2 units (v_exp_f32 / v_log_f32, ~1 ulp): the CTC and RNN-T recursions are serial chains of
+// these, the library expf / log1pf sequences made CTC's 181 us at T' = 249.  1 + e is in (1, 2], where log needs no special care.
+__device__ __forceinline__ float logaddexp_(float a, float b) {
+    const float m = fmaxf(a, b);
+    if (m == -INFINITY) return -INFINITY;
+    return m + __logf(1.0f + __expf(-fabsf(a - b)));
+}
+
+// the last b with key[b] <= r (keys nondecreasing: a packed lattice's off / enc_row0 / pred_row0), -1 if none: <= 9 probes at B <= 512, all
+// lanes of a wavefront at one address
+__device__ __forceinline__ int last_le(const int64_t* __restrict__ key, int B, int64_t r) {
+    if (key[0] > r) return -1;
+    int lo = 0, hi = B - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (key[mid] <= r) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
 }

@@ -73,12 +73,7 @@ __global__ __launch_bounds__(256) void cfm_dwconv_kernel(const void* __restrict_
         a0 = siluf_((a0 + b0) * s0 + h0);
         a1 = siluf_((a1 + b1) * s1 + h1);
         const int64_t o = base + (int64_t)t * D;
-        if (y_dt == CFM_F32)
-            *(float2*)((float*)y + o) = make_float2(a0, a1);
-        else if (y_dt == CFM_BF16)
-            *(unsigned*)((u16*)y + o) = pack2<BF16>(a0, a1);
-        else
-            *(unsigned*)((u16*)y + o) = pack2<F16>(a0, a1);
+        store2(y, y_dt, o, (f32x2){a0, a1});
     }
 }
 

@@ -25,20 +25,6 @@ namespace {
 constexpr int CTC_NT = 256;
 constexpr int CTC_MAXS = 2 * CTC_NT;                       // extended states (U <= 255)
 
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
-// log(exp(a) + exp(b)) on the hardware exp2/log2 units (v_exp_f32 / v_log_f32, ~1 ulp): the recursion is a serial chain of these, the
-// library expf / log1pf sequences made it 181 us at T' = 249.  1 + e is in (1, 2], where log needs no special care.
-__device__ __forceinline__ float logaddexp_(float a, float b) {
-    const float m = fmaxf(a, b);
-    if (m == -INFINITY) return -INFINITY;
-    return m + __logf(1.0f + __expf(-fabsf(a - b)));
-}
-
 __device__ __forceinline__ int ext_label(const int* __restrict__ labels, int64_t base, int s, int V) {
     const int y = (s & 1) ? labels[base + (s >> 1)] : 0;   // labels outside [0, V) cannot index a row: clamped (the reference would raise)
     return y < 0 ? 0 : (y < V ? y : V - 1);

@@ -288,10 +288,8 @@ __global__ __launch_bounds__(256) void cfm_ffn_kernel(const FfnArgs a) {
                 for (int it = 0; it < VPL; ++it) {
                     const int c = (lane + 64 * it) * 4;
                     if (c < D) {
-                        if (a.out16_dtype == CFM_BF16)
-                            *(u32x2*)((u16*)a.out16 + grow * D + c) = (u32x2){pack2<BF16>(v[it].x, v[it].y), pack2<BF16>(v[it].z, v[it].w)};
-                        else
-                            *(u32x2*)((u16*)a.out16 + grow * D + c) = (u32x2){pack2<F16>(v[it].x, v[it].y), pack2<F16>(v[it].z, v[it].w)};
+                        if (a.out16_dtype == CFM_BF16) st4<BF16>(a.out16, grow * D + c, v[it]);
+                        else st4<F16>(a.out16, grow * D + c, v[it]);
                     }
                 }
             }

@@ -183,7 +183,7 @@ __global__ __launch_bounds__(FS_NW * 64) void cfm_ffn_split_kernel(const FfnSpli
                             const int m = row0 + row, b = m / a.ring_Tq, t = m - b * a.ring_Tq;
                             const int slot = (a.ring_off[b] + t) % a.ring_T;
                             const int hh = col / a.ring_dk, e = col - hh * a.ring_dk + (slice == 2 ? a.ring_dk : 0);
-                            const f32x4 rv = (f32x4){HT::to_f32((u16)(pk.x & 0xffffu)), HT::to_f32((u16)(pk.x >> 16)), HT::to_f32((u16)(pk.y & 0xffffu)), HT::to_f32((u16)(pk.y >> 16))};
+                            const f32x4 rv = unpack4<HT>(pk);
                             *(f32x4*)(a.ring + (((int64_t)b * a.ring_H + hh) * a.ring_T + slot) * (2 * a.ring_dk) + e) = rv;
                         }
                     }

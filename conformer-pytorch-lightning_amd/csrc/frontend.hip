@@ -35,8 +35,6 @@
 
 namespace {
 
-typedef unsigned int u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
-
 #define CFM_INL __attribute__((always_inline))
 
 struct Conv12Args {

@@ -21,11 +21,6 @@
 #include "cfm_common.h"
 #include "gemm256.h"
 
-// vector types whose address is only known to be dword aligned (rows of a [M, ldc] matrix with ldc % 4 == 2)
-typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
-typedef float f32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
-typedef unsigned int u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
-
 struct GemmArgs {
     const void* A;
     const u16* W;
@@ -312,10 +307,7 @@ __global__ __launch_bounds__(256 * KG, KG == 1 ? 2 : 1) void cfm_gemm_kernel(con
     f32x4 res_r[FM][FN];
     const bool dact = g.act == CFM_ACT_DSILU || g.act == CFM_ACT_DRELU;
     auto store_pre = [&](int row, int col, const f32x4& pv) {   // training: the pre-activation, 4 columns (N % 4 == 0 checked by the host)
-        const int64_t po = (int64_t)row * g.ld_pre + col;
-        if (g.pre_dtype == CFM_F32) *(f32x4*)((float*)g.Cpre + po) = pv;
-        else if (g.pre_dtype == CFM_BF16) *(u32x2*)((u16*)g.Cpre + po) = (u32x2){pack2<BF16>(pv[0], pv[1]), pack2<BF16>(pv[2], pv[3])};
-        else *(u32x2*)((u16*)g.Cpre + po) = (u32x2){pack2<F16>(pv[0], pv[1]), pack2<F16>(pv[2], pv[3])};
+        store4(g.Cpre, g.pre_dtype, (int64_t)row * g.ld_pre + col, pv);
     };
 #pragma unroll
     for (int i = 0; i < FM; ++i) {
@@ -328,16 +320,7 @@ __global__ __launch_bounds__(256 * KG, KG == 1 ? 2 : 1) void cfm_gemm_kernel(con
             const bool live = g.res && row < g.M && col < g.N && !(glu && (j & 1));
             res_r[i][j] = live ? *(const f32x4*)(g.res + (int64_t)row * g.ldr + ocol) : (f32x4){0.f, 0.f, 0.f, 0.f};
             if (dact && row < g.M && col + 3 < g.N) {        // backward epilogue: the activation's argument shares the residual's registers
-                const int64_t ao = (int64_t)row * g.ld_aux + col;
-                if (g.aux_dtype == CFM_F32) {
-                    res_r[i][j] = *(const f32x4*)((const float*)g.aux + ao);
-                } else {
-                    const u32x2 r2 = *(const u32x2*)((const u16*)g.aux + ao);
-                    if (g.aux_dtype == CFM_BF16)
-                        res_r[i][j] = (f32x4){BF16::to_f32((u16)(r2.x & 0xffffu)), BF16::to_f32((u16)(r2.x >> 16)), BF16::to_f32((u16)(r2.y & 0xffffu)), BF16::to_f32((u16)(r2.y >> 16))};
-                    else
-                        res_r[i][j] = (f32x4){F16::to_f32((u16)(r2.x & 0xffffu)), F16::to_f32((u16)(r2.x >> 16)), F16::to_f32((u16)(r2.y & 0xffffu)), F16::to_f32((u16)(r2.y >> 16))};
-                }
+                res_r[i][j] = load4(g.aux, g.aux_dtype, (int64_t)row * g.ld_aux + col);
             }
         }
     }
@@ -402,18 +385,10 @@ __global__ __launch_bounds__(256 * KG, KG == 1 ? 2 : 1) void cfm_gemm_kernel(con
                 // one 16-byte (f32) / 8-byte (16 bit) store per lane.  When ldc is only a multiple of 2 the address is 8- / 4-byte aligned:
                 // the under-aligned vector types keep it ONE global_store_dwordx4 / dwordx2 (global memory needs dword alignment only);
                 // splitting into pairs cost 10 % on the joint's vocabulary projection (2224 -> 2028 us at ldc 5002 vs 5004)
-                if (g.c_dtype == CFM_F32) {
-                    *(f32x4_a4*)((float*)g.C + o) = v;
-                } else if (g.c_dtype == CFM_BF16) {
-                    *(u32x2_a4*)((u16*)g.C + o) = (u32x2){pack2<BF16>(v[0], v[1]), pack2<BF16>(v[2], v[3])};
-                } else {
-                    *(u32x2_a4*)((u16*)g.C + o) = (u32x2){pack2<F16>(v[0], v[1]), pack2<F16>(v[2], v[3])};
-                }
+                store4<true>(g.C, g.c_dtype, o, v);
             } else if (col + 1 < g.N) {
                 // N % 4 == 2 (a vocabulary of 5002 columns): the last column pair of the row
-                if (g.c_dtype == CFM_F32) *(f32x2_a4*)((float*)g.C + o) = (f32x2){v[0], v[1]};
-                else if (g.c_dtype == CFM_BF16) *(unsigned*)((u16*)g.C + o) = pack2<BF16>(v[0], v[1]);
-                else *(unsigned*)((u16*)g.C + o) = pack2<F16>(v[0], v[1]);
+                store2<true>(g.C, g.c_dtype, o, (f32x2){v[0], v[1]});
             }
         }
     }
@@ -560,15 +535,8 @@ __global__ __launch_bounds__(256, 2) void cfm_gemm_pers_kernel(const GemmArgs g)
                 }
                 if (row >= g.M) continue;
                 const int64_t o = (int64_t)row * g.ldc + col;
-                if (col + 3 < g.N) {
-                    if (g.c_dtype == CFM_F32) *(f32x4_a4*)((float*)g.C + o) = v;
-                    else if (g.c_dtype == CFM_BF16) *(u32x2_a4*)((u16*)g.C + o) = (u32x2){pack2<BF16>(v[0], v[1]), pack2<BF16>(v[2], v[3])};
-                    else *(u32x2_a4*)((u16*)g.C + o) = (u32x2){pack2<F16>(v[0], v[1]), pack2<F16>(v[2], v[3])};
-                } else if (col + 1 < g.N) {
-                    if (g.c_dtype == CFM_F32) *(f32x2_a4*)((float*)g.C + o) = (f32x2){v[0], v[1]};
-                    else if (g.c_dtype == CFM_BF16) *(unsigned*)((u16*)g.C + o) = pack2<BF16>(v[0], v[1]);
-                    else *(unsigned*)((u16*)g.C + o) = pack2<F16>(v[0], v[1]);
-                }
+                if (col + 3 < g.N) store4<true>(g.C, g.c_dtype, o, v);
+                else if (col + 1 < g.N) store2<true>(g.C, g.c_dtype, o, (f32x2){v[0], v[1]});
             }
         }
     };

@@ -25,10 +25,6 @@
 
 namespace {
 
-typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
-typedef float f32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
-typedef unsigned int u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
-
 #define CFM_INL __attribute__((always_inline))
 
 template <typename HT, bool CONV>
@@ -134,9 +130,9 @@ __global__ __launch_bounds__(512) void cfm_gemm256_kernel(const Gemm256Args g) {
         }
     };
     // Epilogue: one 64-bit row pointer per fragment row and constant column offsets, one dtype branch around the whole tile.
-    auto store_tile = [&](int tm0, int tn0, auto dt_c) CFM_INL {
-        constexpr int DT = decltype(dt_c)::value;
-        constexpr int ESZ = DT == CFM_F32 ? 4 : 2;
+    auto store_tile = [&](int tm0, int tn0, auto tag) CFM_INL {
+        typedef decltype(tag) T;
+        constexpr int ESZ = cfm_is_f32<T> ? 4 : 2;
         const int col0 = tn0 + wc * 64 + q4;
 #pragma unroll
         for (int i = 0; i < FM; ++i) {
@@ -156,22 +152,15 @@ __global__ __launch_bounds__(512) void cfm_gemm256_kernel(const Gemm256Args g) {
                 if (row >= g.M) continue;
                 const int col = col0 + j * 16;
                 char* const p = rowp + j * 16 * ESZ;
-                if (col + 3 < g.N) {
-                    if constexpr (DT == CFM_F32) *(f32x4_a4*)p = v;
-                    else if constexpr (DT == CFM_BF16) *(u32x2_a4*)p = (u32x2){pack2<BF16>(v[0], v[1]), pack2<BF16>(v[2], v[3])};
-                    else *(u32x2_a4*)p = (u32x2){pack2<F16>(v[0], v[1]), pack2<F16>(v[2], v[3])};
-                } else if (col + 1 < g.N) {
-                    if constexpr (DT == CFM_F32) *(f32x2_a4*)p = (f32x2){v[0], v[1]};
-                    else if constexpr (DT == CFM_BF16) *(unsigned*)p = pack2<BF16>(v[0], v[1]);
-                    else *(unsigned*)p = pack2<F16>(v[0], v[1]);
-                }
+                if (col + 3 < g.N) st4<T, true>(p, 0, v);
+                else if (col + 1 < g.N) st2<T, true>(p, 0, (f32x2){v[0], v[1]});
             }
         }
     };
     auto epilogue = [&](int tm0, int tn0) CFM_INL {
-        if (g.c_dtype == CFM_F32) store_tile(tm0, tn0, std::integral_constant<int, CFM_F32>{});
-        else if (g.c_dtype == CFM_BF16) store_tile(tm0, tn0, std::integral_constant<int, CFM_BF16>{});
-        else store_tile(tm0, tn0, std::integral_constant<int, CFM_F16>{});
+        if (g.c_dtype == CFM_F32) store_tile(tm0, tn0, float());
+        else if (g.c_dtype == CFM_BF16) store_tile(tm0, tn0, BF16());
+        else store_tile(tm0, tn0, F16());
     };
 
     const int nkt = g.K / BK;

@@ -105,18 +105,6 @@ __global__ __launch_bounds__(256) void cfm_joint_act_bwd_sum_kernel(const float*
 
 // ---- packed lattices (include/cfm.h cfm_lattice): only the valid cells (b, t < T_b, u <= U_b) have rows ----
 
-// the last b with key[b] <= r (keys nondecreasing), -1 if none: <= 9 probes at B <= 512, all lanes of a wavefront at one address
-__device__ __forceinline__ int last_le(const int64_t* __restrict__ key, int B, int64_t r) {
-    if (key[0] > r) return -1;
-    int lo = 0, hi = B - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (key[mid] <= r) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
 // forward: one wavefront per run of JPK_RUN consecutive packed rows; the run's first row is found by a binary search over off, the rest by
 // stepping (b, t, u), so the encoder chunk (shared by U_b+1 consecutive rows) is loaded once per frame of the run.  8 columns per lane.
 constexpr int JPK_RUN = 16;
@@ -270,9 +258,9 @@ extern "C" int cfm_joint_act(const float* enc, int64_t ld_e, const float* pred, 
     const int64_t want = (chunks + 255) / 256;
     const unsigned grid = (unsigned)(want < 256 * 16 ? want : 256 * 16);      // grid-stride beyond 16 workgroups per CU
     CfmProfScope prof("joint_act", s, 0.0, (double)rows * J * cfm_elt_size(out_dtype));
-    if (out_dtype == CFM_F32) CFM_LAUNCH(cfm_joint_act_kernel<float>, dim3(grid), dim3(256), 0, s, enc, ld_e, pred, ld_p, out, T, U, J, chunks);
-    else if (out_dtype == CFM_BF16) CFM_LAUNCH(cfm_joint_act_kernel<BF16>, dim3(grid), dim3(256), 0, s, enc, ld_e, pred, ld_p, out, T, U, J, chunks);
-    else CFM_LAUNCH(cfm_joint_act_kernel<F16>, dim3(grid), dim3(256), 0, s, enc, ld_e, pred, ld_p, out, T, U, J, chunks);
+    cfm_by_dtype(out_dtype, [&](auto ot) {
+        CFM_LAUNCH(cfm_joint_act_kernel<decltype(ot)>, dim3(grid), dim3(256), 0, s, enc, ld_e, pred, ld_p, out, T, U, J, chunks);
+    });
     return cfm_launch_status("cfm_joint_act");
 }
 
@@ -294,9 +282,9 @@ extern "C" int cfm_joint_act_packed(const float* enc, int64_t ld_e, const float*
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)((lat->M + 4 * JPK_RUN - 1) / (4 * JPK_RUN)));
     CfmProfScope prof("joint_act_packed", s, 0.0, (double)lat->M * J * cfm_elt_size(out_dtype));
-    if (out_dtype == CFM_F32) CFM_LAUNCH(cfm_joint_act_packed_kernel<float>, grid, dim3(256), 0, s, enc, ld_e, pred, ld_p, out, *lat, J);
-    else if (out_dtype == CFM_BF16) CFM_LAUNCH(cfm_joint_act_packed_kernel<BF16>, grid, dim3(256), 0, s, enc, ld_e, pred, ld_p, out, *lat, J);
-    else CFM_LAUNCH(cfm_joint_act_packed_kernel<F16>, grid, dim3(256), 0, s, enc, ld_e, pred, ld_p, out, *lat, J);
+    cfm_by_dtype(out_dtype, [&](auto ot) {
+        CFM_LAUNCH(cfm_joint_act_packed_kernel<decltype(ot)>, grid, dim3(256), 0, s, enc, ld_e, pred, ld_p, out, *lat, J);
+    });
     return cfm_launch_status("cfm_joint_act_packed");
 }
 

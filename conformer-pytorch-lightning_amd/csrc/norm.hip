@@ -8,16 +8,6 @@
 
 namespace {
 
-__device__ __forceinline__ void store4(void* base, int dt, int64_t off, const f32x4& v) {
-    if (dt == CFM_F32) {
-        *(f32x4*)((float*)base + off) = v;
-    } else if (dt == CFM_BF16) {
-        *(u32x2*)((u16*)base + off) = (u32x2){pack2<BF16>(v.x, v.y), pack2<BF16>(v.z, v.w)};
-    } else {
-        *(u32x2*)((u16*)base + off) = (u32x2){pack2<F16>(v.x, v.y), pack2<F16>(v.z, v.w)};
-    }
-}
-
 template <int ITERS>
 __device__ __forceinline__ void norm_inplace(f32x4 (&v)[ITERS], int lane, int D, const float* g, const float* b, float eps) {
     float s = 0.f;

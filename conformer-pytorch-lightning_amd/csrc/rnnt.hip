@@ -38,50 +38,6 @@ constexpr int RNNT_MAXU1 = 1024;                           // U + 1
 constexpr int RNNT_MAXT = 8192;                            // o_t lives in LDS
 constexpr int RNNT_AHEAD = 4;
 
-__device__ __forceinline__ float wave_max_(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
-// log(exp(a) + exp(b)) on v_exp_f32 / v_log_f32 (ctc.hip logaddexp_: the recursion is a serial chain of these)
-__device__ __forceinline__ float lae_(float a, float b) {
-    const float m = fmaxf(a, b);
-    if (m == -INFINITY) return -INFINITY;
-    return m + __logf(1.0f + __expf(-fabsf(a - b)));
-}
-
-template <typename TI>
-__device__ __forceinline__ float ld1(const void* p, int64_t i) {
-    if constexpr (std::is_same<TI, float>::value) return ((const float*)p)[i];
-    else return TI::to_f32(((const u16*)p)[i]);
-}
-
-template <typename TI>
-__device__ __forceinline__ f32x4 ld4(const void* p, int64_t i) {          // i % 4 == 0, row base 16 (f32) / 8 (16-bit) byte aligned
-    if constexpr (std::is_same<TI, float>::value) {
-        return *(const f32x4*)((const float*)p + i);
-    } else {
-        const u32x2 w = *(const u32x2*)((const u16*)p + i);
-        return (f32x4){TI::to_f32((u16)(w.x & 0xFFFF)), TI::to_f32((u16)(w.x >> 16)), TI::to_f32((u16)(w.y & 0xFFFF)), TI::to_f32((u16)(w.y >> 16))};
-    }
-}
-
-template <typename TO>
-__device__ __forceinline__ void st1(void* p, int64_t i, float v) {
-    if constexpr (std::is_same<TO, float>::value) ((float*)p)[i] = v;
-    else ((u16*)p)[i] = TO::from_f32(v);
-}
-
-template <typename TO>
-__device__ __forceinline__ void st4(void* p, int64_t i, const f32x4& v) {
-    if constexpr (std::is_same<TO, float>::value) {
-        *(f32x4*)((float*)p + i) = v;
-    } else {
-        *(u32x2*)((u16*)p + i) = (u32x2){pack2<TO>(v.x, v.y), pack2<TO>(v.z, v.w)};
-    }
-}
-
 __device__ __forceinline__ int label_at(const int* __restrict__ tg, int u, int V) {
     const int y = tg[u];                                   // labels outside [0, V) cannot index a row: clamped (torchaudio would raise)
     return y < 0 ? 0 : (y < V ? y : V - 1);
@@ -118,16 +74,9 @@ __device__ __forceinline__ void locate(const cfm_rnnt_desc& d, int64_t r, int& b
 }
 
 __device__ __forceinline__ void locate(const cfm_rnnt_packed_desc& d, int64_t r, int& b, int& t, int& u) {
-    const int64_t* off = d.lat.off;
-    int lo = 0, hi = d.lat.B - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= r) lo = mid;
-        else hi = mid - 1;
-    }
-    b = lo;
+    b = last_le(d.lat.off, d.lat.B, r);                    // r >= 0 = off[0]: never -1
     const int U1 = d.lat.U[b] + 1;
-    const int rem = (int)(r - off[b]);
+    const int rem = (int)(r - d.lat.off[b]);
     t = rem / U1;
     u = rem - t * U1;
 }
@@ -147,7 +96,7 @@ __global__ __launch_bounds__(256) void cfm_rnnt_rows_kernel(D d) {
     const UttGeo g = utt_geo(d, b);
     const int Ub = g.Ub;
     if (t >= g.Tb || u > Ub) return;                       // never read by the recursions or the gradient pass (wavefront-uniform)
-    const void* row = (const char*)d.logits + row_id * d.ld * (std::is_same<TI, float>::value ? 4 : 2);
+    const void* row = (const char*)d.logits + row_id * d.ld * (cfm_is_f32<TI> ? 4 : 2);
     float m = -INFINITY, s = 0.f;                          // online log-sum-exp: the row is read once
     if constexpr (VEC) {
         for (int c = lane * 4; c < V; c += 256) {
@@ -180,7 +129,7 @@ __global__ __launch_bounds__(256) void cfm_rnnt_rows_kernel(D d) {
             if (m > -INFINITY) s += __expf(x - m);
         }
     }
-    const float M = wave_max_(m);
+    const float M = wave_max(m);
     const float tot = wave_sum(m == -INFINITY ? 0.f : s * __expf(m - M));
     const float lse = M + __logf(tot);
     if (lane == 0) {
@@ -214,7 +163,7 @@ __device__ __forceinline__ void rnnt_sweep(const Desc& d, const int b, const boo
     for (int t = wave; t < Tb; t += NT / 64) {
         float m = -INFINITY;
         for (int u = lane; u <= Ub; u += 64) m = fmaxf(m, lb[(int64_t)t * U1 + u]);
-        m = wave_max_(m);
+        m = wave_max(m);
         if (lane == 0) sh_o[t] = m > -INFINITY ? m : 0.f;
     }
     for (int u = tid; u < Ub; u += NT) {
@@ -268,14 +217,14 @@ __device__ __forceinline__ void rnnt_sweep(const Desc& d, const int b, const boo
                     float v = -INFINITY;
                     if (u <= Ub && t >= 0 && t < Tb) {
                         if (fwd) {
-                            const float a = (t == 0 && u == 0) ? 0.f : lae_(self[i] + lbp[i], nbr);
+                            const float a = (t == 0 && u == 0) ? 0.f : logaddexp_(self[i] + lbp[i], nbr);
                             out[(int64_t)t * U1 + u] = a;
                             self[i] = a;
                             lbp[i] = nb[k][i];
                             v = a + nl[k][i];                              // -inf at u = Ub
                             if (t == Tb - 1 && u == Ub) d.ll_alpha[b] = a + nb[k][i];
                         } else {
-                            const float bt = (t == Tb - 1 && u == Ub) ? nb[k][i] : lae_(self[i] + nb[k][i], nbr + nl[k][i]);
+                            const float bt = (t == Tb - 1 && u == Ub) ? nb[k][i] : logaddexp_(self[i] + nb[k][i], nbr + nl[k][i]);
                             out[(int64_t)t * U1 + u] = bt;
                             self[i] = bt;
                             v = bt;
@@ -321,8 +270,8 @@ __global__ __launch_bounds__(256) void cfm_rnnt_grad_kernel(D d) {
     locate(d, row_id, b, t, u);
     const UttGeo g = utt_geo(d, b);
     const int U1 = g.ld, Tb = g.Tb, Ub = g.Ub;
-    const void* row = (const char*)d.logits + row_id * d.ld * (std::is_same<TI, float>::value ? 4 : 2);
-    void* grow = (char*)d.grad + row_id * d.ld_grad * (std::is_same<TO, float>::value ? 4 : 2);
+    const void* row = (const char*)d.logits + row_id * d.ld * (cfm_is_f32<TI> ? 4 : 2);
+    void* grow = (char*)d.grad + row_id * d.ld_grad * (cfm_is_f32<TO> ? 4 : 2);
     const float nls = d.nll_shifted[b];
     if (t >= Tb || u > Ub || !(nls < INFINITY)) {          // outside the lattice (or no alignment): exact zeros
         if constexpr (VEC) {
@@ -391,7 +340,7 @@ template <typename D, typename TI>
 int launch_rows(const D& d, hipStream_t s, CfmProfScope& prof) {
     const int64_t rows = n_rows(d);
     const dim3 grid((unsigned)((rows + 3) / 4));
-    const bool vec = d.ld % 4 == 0 && (std::is_same<TI, float>::value ? aligned16(d.logits) : ((uintptr_t)d.logits & 7) == 0);
+    const bool vec = d.ld % 4 == 0 && (cfm_is_f32<TI> ? aligned16(d.logits) : ((uintptr_t)d.logits & 7) == 0);
     if (vec) CFM_LAUNCH((cfm_rnnt_rows_kernel<D, TI, true>), grid, dim3(256), 0, s, d);
     else CFM_LAUNCH((cfm_rnnt_rows_kernel<D, TI, false>), grid, dim3(256), 0, s, d);
     return CFM_OK;
@@ -401,8 +350,8 @@ template <typename D, typename TI, typename TO>
 int launch_grad(const D& d, hipStream_t s, CfmProfScope& prof) {
     const int64_t rows = n_rows(d);
     const dim3 grid((unsigned)((rows + 3) / 4));
-    const bool in_ok = std::is_same<TI, float>::value ? aligned16(d.logits) : ((uintptr_t)d.logits & 7) == 0;
-    const bool out_ok = std::is_same<TO, float>::value ? aligned16(d.grad) : ((uintptr_t)d.grad & 7) == 0;
+    const bool in_ok = cfm_is_f32<TI> ? aligned16(d.logits) : ((uintptr_t)d.logits & 7) == 0;
+    const bool out_ok = cfm_is_f32<TO> ? aligned16(d.grad) : ((uintptr_t)d.grad & 7) == 0;
     const bool vec = d.ld % 4 == 0 && d.ld_grad % 4 == 0 && d.grad_cols % 4 == 0 && in_ok && out_ok;
     if (vec) CFM_LAUNCH((cfm_rnnt_grad_kernel<D, TI, TO, true>), grid, dim3(256), 0, s, d);
     else CFM_LAUNCH((cfm_rnnt_grad_kernel<D, TI, TO, false>), grid, dim3(256), 0, s, d);
@@ -411,9 +360,7 @@ int launch_grad(const D& d, hipStream_t s, CfmProfScope& prof) {
 
 template <typename D, typename TI>
 int launch_grad_out(const D& d, hipStream_t s, CfmProfScope& prof) {
-    if (d.grad_dtype == CFM_F32) return launch_grad<D, TI, float>(d, s, prof);
-    if (d.grad_dtype == CFM_BF16) return launch_grad<D, TI, BF16>(d, s, prof);
-    return launch_grad<D, TI, F16>(d, s, prof);
+    return cfm_by_dtype(d.grad_dtype, [&](auto to) { return launch_grad<D, TI, decltype(to)>(d, s, prof); });
 }
 
 int rnnt_packed_check(const cfm_rnnt_packed_desc* d, const char* what) {
@@ -436,8 +383,7 @@ int rnnt_nll_launch(const D& d, const char* what, hipStream_t s) {
     const int64_t rows = n_rows(d);
     if (rows > 0) {                                        // a packed lattice may have no node at all (every T_b = 0)
         CfmProfScope prof("rnnt_rows", s, 0.0, (double)rows * d.V * cfm_elt_size(d.logits_dtype));
-        int rc = d.logits_dtype == CFM_F32 ? launch_rows<D, float>(d, s, prof) : d.logits_dtype == CFM_BF16 ? launch_rows<D, BF16>(d, s, prof)
-                                                                                                              : launch_rows<D, F16>(d, s, prof);
+        int rc = cfm_by_dtype(d.logits_dtype, [&](auto ti) { return launch_rows<D, decltype(ti)>(d, s, prof); });
         if (rc) return rc;
         if (int rc2 = cfm_launch_status(what)) return rc2;
     }
@@ -458,8 +404,7 @@ int rnnt_grad_launch(const D& d, const char* what, hipStream_t s) {
     const int64_t rows = n_rows(d);
     if (rows == 0) return CFM_OK;
     CfmProfScope prof("rnnt_grad", s, 0.0, (double)rows * ((double)d.V * cfm_elt_size(d.logits_dtype) + (double)d.grad_cols * cfm_elt_size(d.grad_dtype)));
-    int rc = d.logits_dtype == CFM_F32 ? launch_grad_out<D, float>(d, s, prof) : d.logits_dtype == CFM_BF16 ? launch_grad_out<D, BF16>(d, s, prof)
-                                                                                                             : launch_grad_out<D, F16>(d, s, prof);
+    int rc = cfm_by_dtype(d.logits_dtype, [&](auto ti) { return launch_grad_out<D, decltype(ti)>(d, s, prof); });
     if (rc) return rc;
     return cfm_launch_status(what);
 }

@@ -17,21 +17,6 @@
 
 namespace {
 
-// ------------------------------------------------------------------------------------------------------------------------------
-// loads / stores by dtype, 4 consecutive elements
-// ------------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ f32x4 load4(const void* base, int dt, int64_t off) {
-    if (dt == CFM_F32) return *(const f32x4*)((const float*)base + off);
-    const u32x2 r = *(const u32x2*)((const u16*)base + off);
-    if (dt == CFM_BF16)
-        return (f32x4){BF16::to_f32((u16)(r.x & 0xffffu)), BF16::to_f32((u16)(r.x >> 16)), BF16::to_f32((u16)(r.y & 0xffffu)), BF16::to_f32((u16)(r.y >> 16))};
-    return (f32x4){F16::to_f32((u16)(r.x & 0xffffu)), F16::to_f32((u16)(r.x >> 16)), F16::to_f32((u16)(r.y & 0xffffu)), F16::to_f32((u16)(r.y >> 16))};
-}
-__device__ __forceinline__ void store4(void* base, int dt, int64_t off, const f32x4& v) {
-    if (dt == CFM_F32) *(f32x4*)((float*)base + off) = v;
-    else if (dt == CFM_BF16) *(u32x2*)((u16*)base + off) = (u32x2){pack2<BF16>(v.x, v.y), pack2<BF16>(v.z, v.w)};
-    else *(u32x2*)((u16*)base + off) = (u32x2){pack2<F16>(v.x, v.y), pack2<F16>(v.z, v.w)};
-}
 __device__ __forceinline__ float dsilu_(float z) {
     const float s = sigmoidf_(z);
     return s * (1.f + z * (1.f - s));
@@ -82,19 +67,6 @@ constexpr int LNB_ROWS = 2 * LNB_WAVES;   // 8 wavefronts halve the workgroups t
 
 // The element types of g / dg are TEMPLATE arguments: with a run-time dtype every one of the 30 window loads sits behind a branch, the compiler
 // waits at each join and the loads of a thread go out one memory latency after the other (28 us per launch at a config-3 micro-batch).
-template <int GDT>
-__device__ __forceinline__ float ld_t(const void* p, int64_t i) {
-    if constexpr (GDT == CFM_F32) return ((const float*)p)[i];
-    else if constexpr (GDT == CFM_BF16) return BF16::to_f32(((const u16*)p)[i]);
-    else return F16::to_f32(((const u16*)p)[i]);
-}
-template <int GDT>
-__device__ __forceinline__ void st_t(void* p, int64_t i, float v) {
-    if constexpr (GDT == CFM_F32) ((float*)p)[i] = v;
-    else if constexpr (GDT == CFM_BF16) ((u16*)p)[i] = BF16::from_f32(v);
-    else ((u16*)p)[i] = F16::from_f32(v);
-}
-
 // Optional second output (LnBwd2): the NEXT consumer of dx in a conformer block's backward is a residual branch whose gradient enters its
 // GEMMs as dropout-mask * alpha * dx in the activation dtype (cfm_dropout_rows); written here it saves that launch and its read of dx.
 struct LnBwd2 {
@@ -104,16 +76,6 @@ struct LnBwd2 {
     CfmDrop d1, d2;
     const uint8_t* mask;   // rows with mask == 0 are written as zeros (the consumer's row mask applied here)
 };
-
-template <int DT>
-__device__ __forceinline__ f32x4 ld4_t(const void* p, int64_t i) {
-    if constexpr (DT == CFM_F32) return *(const f32x4*)((const float*)p + i);
-    else {
-        const u32x2 r = *(const u32x2*)((const u16*)p + i);
-        if constexpr (DT == CFM_BF16) return (f32x4){BF16::to_f32((u16)(r.x & 0xffffu)), BF16::to_f32((u16)(r.x >> 16)), BF16::to_f32((u16)(r.y & 0xffffu)), BF16::to_f32((u16)(r.y >> 16))};
-        else return (f32x4){F16::to_f32((u16)(r.x & 0xffffu)), F16::to_f32((u16)(r.x >> 16)), F16::to_f32((u16)(r.y & 0xffffu)), F16::to_f32((u16)(r.y >> 16))};
-    }
-}
 
 // CHAIN: a SECOND LayerNorm backward on the same rows, in registers -- consecutive conformer blocks end / begin with one (block l+1's
 // norm_ff_macaron reads block l's norm_final output, encoder_layer.py:57,70), so the backward runs dLN_ffm then dLN_final on every row:
@@ -163,7 +125,7 @@ __global__ __launch_bounds__(64 * LNB_WAVES) void cfm_layernorm_bwd_kernel(const
             const int c = (lane + 64 * it) * 4;
             const int cc = c < D ? c : 0;
             xa[rr][it] = *(const f32x4*)(x + row_c * D + cc);
-            da[rr][it] = ld4_t<DYDT>(dy, row_c * D + cc);
+            da[rr][it] = ld4<cfm_elt_t<DYDT>>(dy, row_c * D + cc);
             ra[rr][it] = dres ? *(const f32x4*)(dres + row_c * D + cc) : z4f;
             if constexpr (CHAIN) xb[rr][it] = *(const f32x4*)(ch.x + row_c * D + cc);
         }
@@ -376,7 +338,7 @@ __global__ __launch_bounds__(256) void cfm_dwconv_stats_kernel(const void* __res
         for (int i = 0; i < DWW; ++i) {
             const int t = t0 - (DWK - 1) / 2 + i;
             const bool in = t >= 0 && t < T;
-            const float gv = ld_t<GDT>(g, ub + (int64_t)(in ? t : 0) * D + c);      // unconditional load, selected afterwards
+            const float gv = ld1<cfm_elt_t<GDT>>(g, ub + (int64_t)(in ? t : 0) * D + c);      // unconditional load, selected afterwards
             win[i] = in ? gv : 0.f;
         }
 #pragma unroll
@@ -510,7 +472,7 @@ __global__ __launch_bounds__(256) void cfm_bn_silu_bwd_kernel(const void* __rest
         for (int r = 0; r < BNB_ROWS; ++r) {                 // all loads first (rows past the group: clamped address, zeroed value)
             const int64_t row = r0 + r < M ? r0 + r : M - 1;
             cv[r] = c[row * D + ch];
-            dv[r] = ld_t<SDT>(ds, row * D + ch);
+            dv[r] = ld1<cfm_elt_t<SDT>>(ds, row * D + ch);
         }
 #pragma unroll
         for (int r = 0; r < BNB_ROWS; ++r) {
@@ -533,9 +495,9 @@ __global__ __launch_bounds__(256) void cfm_bn_silu_bwd_kernel(const void* __rest
 // the pointwise-conv-1 GEMM's C_pre layout); dg itself is then not stored.
 template <int ODT>
 __device__ __forceinline__ float round_as(float v) {
-    if constexpr (ODT == CFM_F32) return v;
-    else if constexpr (ODT == CFM_BF16) return BF16::to_f32((u16)(pack2<BF16>(v, 0.f) & 0xffffu));
-    else return F16::to_f32((u16)(pack2<F16>(v, 0.f) & 0xffffu));
+    typedef cfm_elt_t<ODT> T;
+    if constexpr (cfm_is_f32<T>) return v;
+    else return T::to_f32(T::from_f32(v));
 }
 
 template <int GDT, int ODT, bool GLU>
@@ -562,7 +524,7 @@ __global__ __launch_bounds__(256) void cfm_dwconv_bwd_kernel(const float* __rest
             const int64_t o = ub + (int64_t)(in ? t : 0) * D + ch;
             const float chat = (c[o] - mean) * rstd;
             dcw[i] = in ? sc * (dy[o] - k1 - chat * k2) : 0.f;
-            const float gv = ld_t<GDT>(g, o);
+            const float gv = ld1<cfm_elt_t<GDT>>(g, o);
             gw[i] = in ? gv : 0.f;
         }
 #pragma unroll
@@ -576,12 +538,12 @@ __global__ __launch_bounds__(256) void cfm_dwconv_bwd_kernel(const float* __rest
                 for (int k = 0; k < DWK; ++k) a = fmaf(wk[k], dcw[j + DWK - 1 - k], a);
                 if constexpr (GLU) {
                     const int64_t ua = (ub / D + t) * 2 * D + (ch >> 4) * 32 + (ch & 15);
-                    const float dv = round_as<ODT>(a), av = ld_t<ODT>(u, ua), gt = ld_t<ODT>(u, ua + 16);
+                    const float dv = round_as<ODT>(a), av = ld1<cfm_elt_t<ODT>>(u, ua), gt = ld1<cfm_elt_t<ODT>>(u, ua + 16);
                     const float sg = sigmoidf_(gt);
-                    st_t<ODT>(du, ua, dv * sg);
-                    st_t<ODT>(du, ua + 16, dv * av * sg * (1.f - sg));
+                    st1<cfm_elt_t<ODT>>(du, ua, dv * sg);
+                    st1<cfm_elt_t<ODT>>(du, ua + 16, dv * av * sg * (1.f - sg));
                 } else {
-                    st_t<ODT>(dg_out, ub + (int64_t)t * D + ch, a);
+                    st1<cfm_elt_t<ODT>>(dg_out, ub + (int64_t)t * D + ch, a);
                 }
             }
         }
@@ -722,8 +684,8 @@ __global__ __launch_bounds__(256) void cfm_conv1_wgrad_kernel(const void* __rest
             for (int j = 0; j < 8; ++j) {
                 const int f1 = fb + j < F1 ? fb + j : F1 - 1;
                 const int64_t o = (((int64_t)b * T1 + t1) * F1 + f1) * C;
-                d0[j] = ld_t<DDT>(dh1, o + c0);
-                d1[j] = two ? ld_t<DDT>(dh1, o + c1) : 0.f;
+                d0[j] = ld1<cfm_elt_t<DDT>>(dh1, o + c0);
+                d1[j] = two ? ld1<cfm_elt_t<DDT>>(dh1, o + c1) : 0.f;
             }
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -949,16 +911,12 @@ static int layernorm_bwd_impl(const float* x, const void* dy, int32_t dy_dtype, 
         if (chain) CFM_LAUNCH((cfm_layernorm_bwd_kernel<IT, DT, true>), grid, block, 0, s, x, dy, dy_dtype, gamma, row_mask, dres, dx, ws, eps, M, D, ag, ab, o2, ch); \
         else CFM_LAUNCH((cfm_layernorm_bwd_kernel<IT, DT, false>), grid, block, 0, s, x, dy, dy_dtype, gamma, row_mask, dres, dx, ws, eps, M, D, ag, ab, o2, ch);  \
     } while (0)
-#define CFM_LNB_DT(IT)                                        \
-    do {                                                      \
-        if (dy_dtype == CFM_F32) CFM_LNB(IT, CFM_F32);        \
-        else if (dy_dtype == CFM_BF16) CFM_LNB(IT, CFM_BF16); \
-        else CFM_LNB(IT, CFM_F16);                            \
-    } while (0)
-        if (D <= 256) CFM_LNB_DT(1);
-        else if (D <= 512) CFM_LNB_DT(2);
-        else CFM_LNB_DT(4);
-#undef CFM_LNB_DT
+        cfm_by_dtype(dy_dtype, [&](auto tag) {
+            constexpr int DT = cfm_dtype_of<decltype(tag)>;
+            if (D <= 256) CFM_LNB(1, DT);
+            else if (D <= 512) CFM_LNB(2, DT);
+            else CFM_LNB(4, DT);
+        });
 #undef CFM_LNB
         if (int rc = cfm_launch_status("cfm_layernorm_bwd")) return rc;
     }
@@ -1044,9 +1002,9 @@ extern "C" int cfm_dwconv_bn_train_groups(const void* g, int32_t g_dtype, const 
     {
         CfmProfScope prof("dwconv_stats", s, 2.0 * M * D * DWK, (double)M * D * (cfm_elt_size(g_dtype) + 4.0));
         const dim3 grid((unsigned)blks);
-        if (g_dtype == CFM_BF16) CFM_LAUNCH((cfm_dwconv_stats_kernel<CFM_BF16>), grid, dim3(256), 0, s, g, w, dw_bias, c_out, ws, G, D);
-        else if (g_dtype == CFM_F16) CFM_LAUNCH((cfm_dwconv_stats_kernel<CFM_F16>), grid, dim3(256), 0, s, g, w, dw_bias, c_out, ws, G, D);
-        else CFM_LAUNCH((cfm_dwconv_stats_kernel<CFM_F32>), grid, dim3(256), 0, s, g, w, dw_bias, c_out, ws, G, D);
+        cfm_by_dtype(g_dtype, [&](auto tag) {
+            CFM_LAUNCH((cfm_dwconv_stats_kernel<cfm_dtype_of<decltype(tag)>>), grid, dim3(256), 0, s, g, w, dw_bias, c_out, ws, G, D);
+        });
         if (int rc = cfm_launch_status("cfm_dwconv_bn_train (conv)")) return rc;
     }
     {
@@ -1090,9 +1048,9 @@ extern "C" int cfm_dwconv_bn_train_bwd_groups(const void* ds, int32_t ds_dtype, 
     float* coef = ws + (int64_t)bnbs * 2 * D;                               // [n_groups][2][D] behind the BatchNorm partials
     {
         CfmProfScope prof("bn_silu_bwd", s, 0.0, (double)M * D * (8.0 + cfm_elt_size(ds_dtype)));
-        if (ds_dtype == CFM_BF16) CFM_LAUNCH((cfm_bn_silu_bwd_kernel<CFM_BF16>), dim3((unsigned)bnbs), dim3(256), 0, s, ds, c, stats, dy_ws, ws, G, D);
-        else if (ds_dtype == CFM_F16) CFM_LAUNCH((cfm_bn_silu_bwd_kernel<CFM_F16>), dim3((unsigned)bnbs), dim3(256), 0, s, ds, c, stats, dy_ws, ws, G, D);
-        else CFM_LAUNCH((cfm_bn_silu_bwd_kernel<CFM_F32>), dim3((unsigned)bnbs), dim3(256), 0, s, ds, c, stats, dy_ws, ws, G, D);
+        cfm_by_dtype(ds_dtype, [&](auto tag) {
+            CFM_LAUNCH((cfm_bn_silu_bwd_kernel<cfm_dtype_of<decltype(tag)>>), dim3((unsigned)bnbs), dim3(256), 0, s, ds, c, stats, dy_ws, ws, G, D);
+        });
         if (int rc = cfm_launch_status("cfm_dwconv_bn_train_bwd (silu/bn sums)")) return rc;
     }
     {
@@ -1163,9 +1121,9 @@ extern "C" int cfm_conv1_wgrad(const void* dh1, int32_t dh1_dtype, const float* 
         CfmProfScope prof("conv1_wgrad", s, 20.0 * B * T1 * F1 * C, (double)B * T1 * F1 * C * cfm_elt_size(dh1_dtype));
         const dim3 grid((unsigned)nbt, (unsigned)B);
         const size_t lds = (size_t)3 * F * 4;
-        if (dh1_dtype == CFM_BF16) CFM_LAUNCH((cfm_conv1_wgrad_kernel<CFM_BF16>), grid, dim3(256), lds, s, dh1, x, cmvn_mean, cmvn_istd, ws, T, F, T1, F1, C);
-        else if (dh1_dtype == CFM_F16) CFM_LAUNCH((cfm_conv1_wgrad_kernel<CFM_F16>), grid, dim3(256), lds, s, dh1, x, cmvn_mean, cmvn_istd, ws, T, F, T1, F1, C);
-        else CFM_LAUNCH((cfm_conv1_wgrad_kernel<CFM_F32>), grid, dim3(256), lds, s, dh1, x, cmvn_mean, cmvn_istd, ws, T, F, T1, F1, C);
+        cfm_by_dtype(dh1_dtype, [&](auto tag) {
+            CFM_LAUNCH((cfm_conv1_wgrad_kernel<cfm_dtype_of<decltype(tag)>>), grid, dim3(256), lds, s, dh1, x, cmvn_mean, cmvn_istd, ws, T, F, T1, F1, C);
+        });
         if (int rc = cfm_launch_status("cfm_conv1_wgrad")) return rc;
     }
     return reduce_partials(ws, B * nbt, 10 * C, 9 * C, 1.0f, dw, db, s, "cfm_conv1_wgrad (reduce)");     // dw [9][C] tap-major (the packed layout), db [C]
