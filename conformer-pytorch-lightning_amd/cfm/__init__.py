@@ -180,6 +180,13 @@ class LnBwdDesc(ctypes.Structure):
                 ("chain_x", c_p), ("chain_gamma", c_p), ("chain_dgamma", c_p), ("chain_dbeta", c_p)]
 
 
+class LstmDesc(ctypes.Structure):
+    _fields_ = [("B", c_i32), ("U", c_i32), ("in_", c_i32), ("H", c_i32), ("layers", c_i32), ("drop_p", c_f), ("seed", ctypes.c_uint32), ("x", c_p),
+                ("w_ih", c_p * 4), ("w_hh", c_p * 4), ("b_ih", c_p * 4), ("b_hh", c_p * 4), ("h0", c_p), ("c0", c_p), ("y", c_p), ("hn", c_p), ("cn", c_p),
+                ("save", c_p * 4), ("dy", c_p), ("dhn", c_p), ("dcn", c_p), ("dx", c_p), ("dw_ih", c_p * 4), ("dw_hh", c_p * 4), ("db_ih", c_p * 4),
+                ("db_hh", c_p * 4), ("dh0", c_p), ("dc0", c_p), ("dg", c_p), ("dyl", c_p)]
+
+
 class GreedyDesc(ctypes.Structure):
     _fields_ = [("embed", c_p), ("lstm_w", c_p * 4), ("lstm_b", c_p * 4), ("proj_w", c_p), ("proj_b", c_p), ("pf_w", c_p), ("pf_b", c_p), ("out_w", c_p),
                 ("out_b", c_p), ("enc_proj", c_p), ("token", c_p), ("t", c_p), ("count", c_p), ("frame_count", c_p), ("hyps", c_p), ("lens", c_p),
@@ -267,6 +274,11 @@ def lib():
         L.cfm_greedy_chunk_begin.argtypes = [ctypes.POINTER(GreedyChunkDesc), c_p]
         L.cfm_greedy_chunk_step.argtypes = [ctypes.POINTER(GreedyChunkDesc), c_p]
         L.cfm_fbank.argtypes = [ctypes.POINTER(FbankDesc), c_p]
+        L.cfm_lstm_forward.argtypes = [ctypes.POINTER(LstmDesc), c_p]
+        L.cfm_lstm_backward.argtypes = [ctypes.POINTER(LstmDesc), c_p]
+        L.cfm_lstm_forward.restype = L.cfm_lstm_backward.restype = ctypes.c_int
+        L.cfm_lstm_save_floats.argtypes = [c_i32, c_i32, c_i32]
+        L.cfm_lstm_save_floats.restype = c_i64
         L.cfm_fbank_stream.argtypes = [ctypes.POINTER(FbankDesc), c_p]
         L.cfm_ffn_split.argtypes = [ctypes.POINTER(FfnSplitDesc), c_p]
         L.cfm_ffn_split_supported.argtypes = [c_i32, c_i32]

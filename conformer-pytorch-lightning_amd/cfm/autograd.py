@@ -861,3 +861,31 @@ class JointRNNTLossFn(torch.autograd.Function):
         dxp = _gemm(dp, pk.pred.wt, w_lo=pk.pred.wt_lo, out_dtype=torch.float32)
         V = pk.V
         return (dxe, dxp, None, None, None, None, None, None, None, dWe, dbe, dWp, dbp, dWo[:V], dbo[:V])
+
+
+class LSTMSeqFn(torch.autograd.Function):
+    """nn.LSTM(batch_first=True) over whole sequences on cfm.lstm_forward / cfm.lstm_backward: the RNN-T predictor's teacher-forced pass
+    (predictor.RNNPredictor(fused=True)).  params: weight_ih, weight_hh, bias_ih, bias_hh per layer in nn.LSTM's order (biases present iff
+    has_bias); h0 / c0 [layers, B, H] or None.  p: dropout between layers (train mode; one seed per call from draw_seed unless `seed` is given) --
+    the backward regenerates the mask.  Returns (y, hn, cn).  What is kept for the backward: ONE f32 block per layer."""
+
+    @staticmethod
+    def forward(ctx, x, h0, c0, H, has_bias, p, seed, *params):
+        per = 4 if has_bias else 2
+        weights = [tuple(_f32c(t.detach()) for t in params[i:i + per]) + ((None, None) if not has_bias else ()) for i in range(0, len(params), per)]
+        drop = None
+        if p and p > 0.0 and len(weights) > 1:
+            drop = (float(p), (draw_seed() if seed is None else int(seed)) & 0xFFFFFFFF)
+        x = _f32c(x.detach())
+        y, hn, cn, saves = cfm.lstm_forward(x, weights, H, None if h0 is None else h0.detach(), None if c0 is None else c0.detach(), drop=drop)
+        ctx.args = (x, weights, H, drop, saves, has_bias, h0 is not None, c0 is not None)
+        return y, hn, cn
+
+    @staticmethod
+    def backward(ctx, dy, dhn, dcn):
+        x, weights, H, drop, saves, has_bias, has_h0, has_c0 = ctx.args
+        if dy is None:
+            dy = torch.zeros(x.shape[0], x.shape[1], H, dtype=torch.float32, device=x.device)
+        dx, grads, dh0, dc0 = cfm.lstm_backward(x, weights, H, saves, _f32c(dy), None if dhn is None else _f32c(dhn), None if dcn is None else _f32c(dcn), drop=drop)
+        flat = [g for gw in grads for g in (gw if has_bias else gw[:2])]
+        return (dx, dh0 if has_h0 else None, dc0 if has_c0 else None, None, None, None, None, *flat)

@@ -6,7 +6,7 @@ import torch
 
 import cfm as _c
 
-__all__ = ["fbank", "fbank_stream", "stream_prep", "stream_advance", "dwconv_causal_bn_silu", "conv_cache_update", "dropout_rows", "dropout_mask", "set_deterministic", "gemm_tn", "gemm_tn_group", "layernorm_bwd", "glu_bwd", "dwconv_bn_train", "dwconv_bn_train_bwd", "dwconv_bn_train_groups", "dwconv_bn_train_bwd_groups", "col2im_relu_bwd", "conv1_wgrad", "attention_bwd", "attention_group", "attention_bwd_group",
+__all__ = ["lstm_forward", "lstm_backward", "fbank", "fbank_stream", "stream_prep", "stream_advance", "dwconv_causal_bn_silu", "conv_cache_update", "dropout_rows", "dropout_mask", "set_deterministic", "gemm_tn", "gemm_tn_group", "layernorm_bwd", "glu_bwd", "dwconv_bn_train", "dwconv_bn_train_bwd", "dwconv_bn_train_groups", "dwconv_bn_train_bwd_groups", "col2im_relu_bwd", "conv1_wgrad", "attention_bwd", "attention_group", "attention_bwd_group",
            "ctc_nll_train_groups", "ctc_grad", "rnnt_nll", "rnnt_grad", "joint_act_bwd", "rnnt_nll_packed", "joint_act_packed", "joint_act_packed_bwd", "ffn_split", "adam_step", "adam_clip_step", "sumsq", "scratch_stats",
            "gemm", "ffn_fused", "ffn_fused_supported", "rowchain", "rowchain_supported", "rowchain_pair_supported", "layernorm", "attention", "kv_cache_pack", "dwconv_bn_silu", "conv1_relu", "conv1_relu_mma_supported", "conv12_relu", "conv12_supported", "ctc_nll", "joint_act", "valid_mask", "chunk_mask",
            "attn_mask_combine", "cast", "add_rows", "scratch", "prof_enable", "prof_reset", "prof_table", "as_u8_mask"]
@@ -1309,3 +1309,99 @@ def fbank_stream(samples, state_in, state_out, tables, out, win, shift, padded, 
     d.carry_in, d.fresh_in, d.pos_in, d.carry_out, d.fresh_out, d.pos_out = (_c.ptr(t) for t in (ci, fi, pi, co, fo, po))
     d.carry_n, d.hop = ci.shape[1], hop
     _c.check(_c.lib().cfm_fbank_stream(ctypes.byref(d), _c.stream()), "cfm_fbank_stream")
+
+
+def _lstm_desc(who, x, weights, H, drop):
+    """The shape checks and the fields the forward and the backward share.  weights: per layer (w_ih, w_hh, b_ih | None, b_hh | None)."""
+    L = len(weights)
+    if x.dim() != 3 or x.dtype != torch.float32:
+        raise ValueError("cfm.%s: x must be float32 [B, U, in], got %s %s" % (who, tuple(x.shape), x.dtype))
+    _dense(who, x=x)
+    B, U, I = x.shape
+    if not 1 <= L <= 4 or H % 64 or I % 64 or not 64 <= H <= 512 or not 64 <= I <= 512 or B < 1 or U < 1:
+        raise ValueError("cfm.%s: 1-4 layers, hidden and input size multiples of 64 up to 512, B >= 1, U >= 1 (layers=%d in=%d H=%d B=%d U=%d): "
+                         "there is no other LSTM kernel" % (who, L, I, H, B, U))
+    d = _c.LstmDesc()
+    d.B, d.U, d.in_, d.H, d.layers = B, U, I, H, L
+    if drop is not None and drop[0] > 0.0 and L > 1:
+        d.drop_p, d.seed = float(drop[0]), int(drop[1]) & 0xFFFFFFFF
+    d.x = _c.ptr(x)
+    for l, (w_ih, w_hh, b_ih, b_hh) in enumerate(weights):
+        _c.require_hip(w_ih, w_hh, b_ih, b_hh)
+        _dense(who, w_ih=w_ih, w_hh=w_hh, b_ih=b_ih, b_hh=b_hh)
+        if tuple(w_ih.shape) != (4 * H, I if l == 0 else H) or tuple(w_hh.shape) != (4 * H, H) or any(t.dtype != torch.float32 for t in (w_ih, w_hh)) or \
+                any(b is not None and (b.dtype != torch.float32 or b.numel() != 4 * H) for b in (b_ih, b_hh)):
+            raise ValueError("cfm.%s: layer %d: expected float32 weight_ih [4H, in], weight_hh [4H, H], biases [4H]" % (who, l))
+        d.w_ih[l], d.w_hh[l], d.b_ih[l], d.b_hh[l] = _c.ptr(w_ih), _c.ptr(w_hh), _c.ptr(b_ih), _c.ptr(b_hh)
+    return d, B, U, I, L
+
+
+def _lstm_state(who, name, t, L, B, H):
+    if t is None:
+        return None
+    _c.require_hip(t)
+    if tuple(t.shape) != (L, B, H) or t.dtype != torch.float32:
+        raise ValueError("cfm.%s: %s must be float32 [layers, B, H] = (%d, %d, %d), got %s %s" % (who, name, L, B, H, tuple(t.shape), t.dtype))
+    return t.contiguous()
+
+
+def lstm_forward(x, weights, H, h0=None, c0=None, drop=None, out=None):
+    """nn.LSTM(batch_first=True) over whole sequences (include/cfm.h cfm_lstm_forward): x [B, U, in] f32 -> (y [B, U, H], hn, cn [layers, B, H],
+    saves: one f32 block per layer for lstm_backward).  drop = (p, seed): dropout between layers.  out: (y, hn, cn, saves) to write into."""
+    _c.require_hip(x, h0, c0)
+    d, B, U, I, L = _lstm_desc("lstm_forward", x, weights, H, drop)
+    h0, c0 = _lstm_state("lstm_forward", "h0", h0, L, B, H), _lstm_state("lstm_forward", "c0", c0, L, B, H)
+    n = int(_c.lib().cfm_lstm_save_floats(B, U, H))
+    if out is None:
+        y = torch.empty((B, U, H), dtype=torch.float32, device=x.device)
+        hn, cn = torch.empty((L, B, H), dtype=torch.float32, device=x.device), torch.empty((L, B, H), dtype=torch.float32, device=x.device)
+        saves = [torch.empty(n, dtype=torch.float32, device=x.device) for _ in range(L)]
+    else:
+        y, hn, cn, saves = out
+        if tuple(y.shape) != (B, U, H) or tuple(hn.shape) != (L, B, H) or tuple(cn.shape) != (L, B, H) or len(saves) != L or any(s.numel() != n for s in saves):
+            raise ValueError("cfm.lstm_forward: out does not match (y [B,U,H], hn, cn [layers,B,H], %d save blocks of %d floats)" % (L, n))
+        _dense("lstm_forward", y=y, hn=hn, cn=cn, **{"save%d" % i: s for i, s in enumerate(saves)})
+    d.h0, d.c0, d.y, d.hn, d.cn = _c.ptr(h0), _c.ptr(c0), _c.ptr(y), _c.ptr(hn), _c.ptr(cn)
+    for l in range(L):
+        d.save[l] = _c.ptr(saves[l])
+    _c.check(_c.lib().cfm_lstm_forward(ctypes.byref(d), _c.stream()), "cfm_lstm_forward")
+    return y, hn, cn, saves
+
+
+def lstm_backward(x, weights, H, saves, dy, dhn=None, dcn=None, drop=None, out=None, work=None):
+    """Gradients of lstm_forward (include/cfm.h cfm_lstm_backward) from dy [B, U, H] and optional dhn / dcn [layers, B, H]; drop as in the forward (the mask is
+    regenerated).  Returns (dx [B, U, in], [(dw_ih, dw_hh, db_ih | None, db_hh | None) per layer], dh0, dc0).  out: the same structure to write
+    into; work: (dg [U*B, 4H], dyl [U*B, H] | None)."""
+    _c.require_hip(x, dy, dhn, dcn, *saves)
+    d, B, U, I, L = _lstm_desc("lstm_backward", x, weights, H, drop)
+    if tuple(dy.shape) != (B, U, H) or dy.dtype != torch.float32:
+        raise ValueError("cfm.lstm_backward: dy must be float32 [B, U, H] = (%d, %d, %d), got %s %s" % (B, U, H, tuple(dy.shape), dy.dtype))
+    dy = dy.contiguous()
+    dhn, dcn = _lstm_state("lstm_backward", "dhn", dhn, L, B, H), _lstm_state("lstm_backward", "dcn", dcn, L, B, H)
+    n = int(_c.lib().cfm_lstm_save_floats(B, U, H))
+    if len(saves) != L or any(s.numel() != n or s.dtype != torch.float32 or not s.is_contiguous() for s in saves):
+        raise ValueError("cfm.lstm_backward: saves must be the forward's %d blocks of %d floats" % (L, n))
+    dev = x.device
+    if out is None:
+        def e(*shape):
+            return torch.empty(shape, dtype=torch.float32, device=dev)
+        grads = [(e(*w[0].shape), e(*w[1].shape), None if w[2] is None else e(4 * H), None if w[3] is None else e(4 * H)) for w in weights]
+        out = (e(B, U, I), grads, e(L, B, H), e(L, B, H))
+    dx, grads, dh0, dc0 = out
+    if tuple(dx.shape) != (B, U, I) or tuple(dh0.shape) != (L, B, H) or tuple(dc0.shape) != (L, B, H) or len(grads) != L:
+        raise ValueError("cfm.lstm_backward: out does not match (dx [B,U,in], per-layer gradients, dh0, dc0 [layers,B,H])")
+    _dense("lstm_backward", dx=dx, dh0=dh0, dc0=dc0)
+    for l, (gw, w) in enumerate(zip(grads, weights)):
+        for g_, w_ in zip(gw, w):
+            if (g_ is None) != (w_ is None) or (g_ is not None and (g_.shape != w_.shape or g_.dtype != torch.float32 or not g_.is_contiguous())):
+                raise ValueError("cfm.lstm_backward: layer %d: a gradient does not match its parameter" % l)
+        d.dw_ih[l], d.dw_hh[l], d.db_ih[l], d.db_hh[l] = (_c.ptr(g_) for g_ in gw)
+        d.save[l] = _c.ptr(saves[l])
+    if work is None:
+        work = (torch.empty((U * B, 4 * H), dtype=torch.float32, device=dev), torch.empty((U * B, H), dtype=torch.float32, device=dev) if L > 1 else None)
+    dg, dyl = work
+    if tuple(dg.shape) != (U * B, 4 * H) or not dg.is_contiguous() or (L > 1 and (dyl is None or tuple(dyl.shape) != (U * B, H) or not dyl.is_contiguous())):
+        raise ValueError("cfm.lstm_backward: work must be (dg [U*B, 4H], dyl [U*B, H])")
+    d.dy, d.dhn, d.dcn, d.dx, d.dh0, d.dc0, d.dg, d.dyl = _c.ptr(dy), _c.ptr(dhn), _c.ptr(dcn), _c.ptr(dx), _c.ptr(dh0), _c.ptr(dc0), _c.ptr(dg), _c.ptr(dyl)
+    _c.check(_c.lib().cfm_lstm_backward(ctypes.byref(d), _c.stream()), "cfm_lstm_backward")
+    return dx, grads, dh0, dc0

@@ -1096,6 +1096,41 @@ typedef struct {
 int cfm_fbank(const cfm_fbank_desc* d, cfm_stream_t stream);
 int cfm_fbank_stream(const cfm_fbank_desc* d, cfm_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * LSTM over whole sequences, forward and backward (csrc/lstm.hip): torch.nn.LSTM(batch_first=True) of the RNN-T predictor's teacher-forced
+ * pass (reference src/predictor.py:66-67) -- gate order i, f, g, o, weight_ih_l{k} [4H, in_k], weight_hh_l{k} [4H, H], bias_* [4H] (NULL: no
+ * bias), in_0 = in, in_k = H.  Everything is f32; every product runs on the f32 MFMA.
+ *   x [B, U, in] dense, h0 / c0 [layers, B, H] (NULL: zeros)  ->  y [B, U, H], hn / cn [layers, B, H]
+ *   save[k]   one block of cfm_lstm_save_floats(B, U, H) floats per layer, written by the forward, read by the backward (the layer's
+ *             outputs and cells with the initial state in front, and the gates after their activations)
+ *   dropout   between layers (not after the last): element e of layer k - 1's time-major [U*B, H] output is kept iff
+ *             hash(seed + 0x9E3779B1 * k, e) >= drop_p * 2^32 and scaled by 1 / (1 - drop_p); the backward regenerates the mask from
+ *             (drop_p, seed).  drop_p = 0: off (eval mode).
+ *   backward  dy [B, U, H] dense, dhn / dcn [layers, B, H] (NULL: zeros)  ->  dx [B, U, in], dw_ih / dw_hh / db_ih / db_hh (overwritten; db_*
+ *             may be NULL), dh0 / dc0 [layers, B, H];  work buffers dg [U*B, 4H] and, for layers > 1, dyl [U*B, H]
+ * H and in: multiples of 64 up to 512; B >= 1, U >= 1, B*U*4H < 2^31; 1..CFM_LSTM_MAX_LAYERS layers; every pointer 16-byte aligned.
+ * A workgroup owns 16 sequences for all U steps and never waits on another one.  All sums run in a fixed order: bitwise reproducible. */
+#define CFM_LSTM_MAX_LAYERS 4
+typedef struct {
+    int32_t B, U, in, H, layers;
+    float drop_p;
+    uint32_t seed;
+    const float* x;
+    const float *w_ih[CFM_LSTM_MAX_LAYERS], *w_hh[CFM_LSTM_MAX_LAYERS], *b_ih[CFM_LSTM_MAX_LAYERS], *b_hh[CFM_LSTM_MAX_LAYERS];
+    const float *h0, *c0;
+    float *y, *hn, *cn;
+    float* save[CFM_LSTM_MAX_LAYERS];
+    /* backward only */
+    const float *dy, *dhn, *dcn;
+    float* dx;
+    float *dw_ih[CFM_LSTM_MAX_LAYERS], *dw_hh[CFM_LSTM_MAX_LAYERS], *db_ih[CFM_LSTM_MAX_LAYERS], *db_hh[CFM_LSTM_MAX_LAYERS];
+    float *dh0, *dc0;
+    float *dg, *dyl;
+} cfm_lstm_desc;
+int64_t cfm_lstm_save_floats(int32_t B, int32_t U, int32_t H);
+int cfm_lstm_forward(const cfm_lstm_desc* d, cfm_stream_t stream);
+int cfm_lstm_backward(const cfm_lstm_desc* d, cfm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
