@@ -215,7 +215,7 @@ class FfnSplitDesc(ctypes.Structure):
     _fields_ = [("x", c_p), ("psum", c_p), ("psum_b2", c_p), ("psum_splits", c_i32), ("psum_alpha", c_f), ("ln1_g", c_p), ("ln1_b", c_p), ("ln2_g", c_p),
                 ("ln2_b", c_p), ("rows_out", c_p), ("rows2_out", c_p), ("ln_g", c_p), ("ln_b", c_p), ("w1", c_p), ("b1", c_p), ("N1", c_i32), ("act", c_i32),
                 ("w2", c_p), ("psum_out", c_p), ("out16", c_p), ("ldo", c_i64), ("M", c_i32), ("D", c_i32), ("mode", c_i32), ("w_dtype", c_i32), ("eps", c_f),
-                ("kv_ring", c_p), ("ring_offsets", c_p), ("ring_T", c_i32), ("ring_H", c_i32), ("ring_Tq", c_i32)]
+                ("kv_ring", c_p), ("ring_offsets", c_p), ("ring_T", c_i32), ("ring_H", c_i32), ("ring_Tq", c_i32), ("ring_len", c_p)]
 
 
 class LayerScratch(ctypes.Structure):
@@ -230,7 +230,7 @@ class LayerIO(ctypes.Structure):
                 ("pos_proj", c_p), ("pos_proj_ld", c_i64),
                 ("attn_cache", c_p), ("cache_T", c_i32), ("new_cache", c_p), ("after_g", c_p), ("after_b", c_p), ("after_out", c_p),
                 ("kv_ring", c_p), ("stream_offset", c_p), ("ring_T", c_i32), ("causal_conv", c_i32), ("conv_cache", c_p), ("pos_shared", c_i32),
-                ("next_w", c_p), ("next_x_out", c_p), ("macaron_done", c_i32), ("utt_len", c_p)]
+                ("next_w", c_p), ("next_x_out", c_p), ("macaron_done", c_i32), ("utt_len", c_p), ("stream_len", c_p)]
 
 
 ROUTES = ("GENERAL", "FUSED_FFN", "CHAIN", "CHAIN_NEXT", "CHAIN_NEXT_CIN", "FFSPLIT", "PAIR")     # include/cfm.h cfm_route, by value (cfm_encoder_layer_route)
@@ -346,6 +346,10 @@ def lib():
         L.cfm_stream_advance.argtypes = [c_p, c_p, c_i32, c_i32, c_p]
         L.cfm_dwconv_causal_bn_silu.argtypes = [c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p]
         L.cfm_conv_cache_update.argtypes = [c_p, c_i32, c_p, c_i32, c_i32, c_i32, c_i32, c_p]
+        L.cfm_stream_prep_len.argtypes = [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p, c_i32, c_i32, c_p, c_p, c_p, c_p]
+        L.cfm_kv_ring_write_len.argtypes = [c_p, c_p, c_i32, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p]
+        L.cfm_stream_advance_len.argtypes = [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p]
+        L.cfm_conv_cache_update_len.argtypes = [c_p, c_i32, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p]
         for name in ("cfm_layernorm_bwd_ws", "cfm_dwconv_bn_ws", "cfm_conv1_wgrad_ws", "cfm_joint_act_bwd_ws"):
             getattr(L, name).restype = c_i64
         L.cfm_prof_enable.argtypes = [c_i32]
@@ -360,7 +364,8 @@ def lib():
                      "cfm_layernorm_bwd", "cfm_glu_bwd", "cfm_dwconv_bn_train", "cfm_dwconv_bn_train_bwd", "cfm_col2im_relu_bwd", "cfm_conv1_wgrad",
                      "cfm_ctc_nll_train_groups", "cfm_ctc_grad", "cfm_adam_step", "cfm_adam_clip_step", "cfm_sumsq", "cfm_dropout_rows", "cfm_dropout_mask", "cfm_pack_matrices", "cfm_pack_vectors", "cfm_greedy_step", "cfm_greedy_chunk_begin", "cfm_greedy_chunk_step", "cfm_fbank", "cfm_fbank_stream", "cfm_ffn_split", "cfm_ffn_split_supported", "cfm_layernorm_bwd_fused", "cfm_dwconv_bn_train_bwd_acc",
                      "cfm_attention_group", "cfm_attention_bwd_group", "cfm_dwconv_bn_train_groups", "cfm_dwconv_bn_train_bwd_groups",
-                     "cfm_encoder_train_forward", "cfm_encoder_train_backward", "cfm_stream_prep", "cfm_kv_ring_write", "cfm_stream_advance", "cfm_dwconv_causal_bn_silu", "cfm_conv_cache_update"):
+                     "cfm_encoder_train_forward", "cfm_encoder_train_backward", "cfm_stream_prep", "cfm_kv_ring_write", "cfm_stream_advance", "cfm_dwconv_causal_bn_silu", "cfm_conv_cache_update",
+                     "cfm_stream_prep_len", "cfm_kv_ring_write_len", "cfm_stream_advance_len", "cfm_conv_cache_update_len"):
             getattr(L, name).restype = ctypes.c_int
         _lib = L
     return _lib

@@ -210,9 +210,12 @@ def ffn_split(x, w_code, mode, psum=None, psum_b2=None, psum_alpha=1.0, ln1=None
     if out16 is not None:
         d.out16, d.ldo = out16.data_ptr(), out16.stride(0)
     if ring is not None:                                  # (kv f32 [B,H,ring_T,2dk], offsets int32 [B], frames per stream): mode 1 as the q|k|v projection
-        kv, offs, tq = ring
+        kv, offs, tq = ring[:3]                           # an optional fourth entry: int32 [B], only rows t < lens[b] go into the ring (cfm.h ring_len)
         _c.require_hip(kv, offs)
         d.kv_ring, d.ring_offsets, d.ring_T, d.ring_H, d.ring_Tq = kv.data_ptr(), offs.data_ptr(), kv.shape[2], kv.shape[1], tq
+        if len(ring) > 3 and ring[3] is not None:
+            _stream_lens("ffn_split", offs.numel(), ring_len=ring[3])
+            d.ring_len = ring[3].data_ptr()
     _c.check(_c.lib().cfm_ffn_split(ctypes.byref(d), _c.stream()), "cfm_ffn_split")
 
 
@@ -1225,21 +1228,52 @@ def dropout_mask(n, p, seed, device):
 # ----------------------------------------------------------------------------------------------------------------------
 # per-stream streaming state (include/cfm.h, csrc/stream.hip)
 # ----------------------------------------------------------------------------------------------------------------------
-def stream_prep(offsets, T, need, ring_T, pe, slot_mask, pos_rows, abs_rows=None):
-    """offsets int32 [B] -> slot_mask u8 [B,ring_T], pos_rows f32 [B,ring_T,D] (= pe[frame held by the slot]), abs_rows f32 [B,D] = pe[offset]."""
+def _stream_lens(op, B, **named):
+    for name, t in named.items():
+        if t.dtype != torch.int32 or t.numel() != B:
+            raise ValueError("cfm.%s: %s must be int32 [B = %d], got %s %s" % (op, name, B, t.dtype, tuple(t.shape)))
+    _c.require_hip(*named.values())
+    _dense(op, **named)
+
+
+def stream_prep(offsets, T, need, ring_T, pe, slot_mask, pos_rows, abs_rows=None, frame_lens=None, out_lens=None):
+    """offsets int32 [B] -> slot_mask u8 [B,ring_T], pos_rows f32 [B,ring_T,D] (= pe[frame held by the slot]), abs_rows f32 [B,D] = pe[offset].
+    frame_lens int32 [B] (with out_lens int32 [B]): per-stream window lengths in feature frames; out_lens receives the encoder frames c_b of each
+    stream and the mask / rows cover the cached frames and those c_b (include/cfm.h cfm_stream_prep_len)."""
     _c.require_hip(offsets, pe, slot_mask, pos_rows, abs_rows)
     B = offsets.numel()
     D = pe.shape[-1]
     _dense("stream_prep", offsets=offsets, slot_mask=slot_mask, pos_rows=pos_rows, abs_rows=abs_rows)
     if offsets.dtype != torch.int32 or pe.dtype != torch.float32 or not pe.is_contiguous() or slot_mask.numel() != B * ring_T or pos_rows.numel() != B * ring_T * D:
         raise ValueError("cfm.stream_prep: offsets int32 [B], pe contiguous f32 [max_len,D], slot_mask [B,ring_T], pos_rows [B,ring_T,D]")
+    if (frame_lens is None) != (out_lens is None):
+        raise ValueError("cfm.stream_prep: frame_lens and out_lens come together")
+    if frame_lens is not None:
+        _stream_lens("stream_prep", B, frame_lens=frame_lens, out_lens=out_lens)
+        _c.check(_c.lib().cfm_stream_prep_len(_c.ptr(offsets), _c.ptr(frame_lens), _c.ptr(out_lens), B, T, need, ring_T, _c.ptr(pe), pe.numel() // D, D,
+                                              _c.ptr(slot_mask), _c.ptr(pos_rows), _c.ptr(abs_rows), _c.stream()), "cfm_stream_prep_len")
+        return
     _c.check(_c.lib().cfm_stream_prep(_c.ptr(offsets), B, T, need, ring_T, _c.ptr(pe), pe.numel() // D, D, _c.ptr(slot_mask), _c.ptr(pos_rows), _c.ptr(abs_rows),
                                       _c.stream()), "cfm_stream_prep")
 
 
-def stream_advance(offsets, T, active=None):
+def stream_advance(offsets, T, active=None, lens=None, y=None):
+    """offsets[b] += T (active streams), or -- lens int32 [B] -- += lens[b], with rows t >= lens[b] of y f32 [B,T,D] (optional) set to zero."""
     _c.require_hip(offsets, active)
     _dense("stream_advance", offsets=offsets, active=active)
+    if lens is not None:
+        B = offsets.numel()
+        _stream_lens("stream_advance", B, lens=lens)
+        D = 0
+        if y is not None:
+            _c.require_hip(y)
+            if y.dtype != torch.float32 or not y.is_contiguous() or y.dim() != 3 or tuple(y.shape[:2]) != (B, T) or active is not None:
+                raise ValueError("cfm.stream_advance: y must be contiguous float32 [B,T,D] (and active is not combined with lens)")
+            D = y.shape[2]
+        _c.check(_c.lib().cfm_stream_advance_len(_c.ptr(offsets), _c.ptr(lens), _c.ptr(y), B, T, D, _c.stream()), "cfm_stream_advance_len")
+        return
+    if y is not None:
+        raise ValueError("cfm.stream_advance: y comes with lens")
     _c.check(_c.lib().cfm_stream_advance(_c.ptr(offsets), _c.ptr(active), offsets.numel(), T, _c.stream()), "cfm_stream_advance")
 
 
@@ -1257,12 +1291,17 @@ def dwconv_causal_bn_silu(x, w, dw_bias, bn_scale, bn_shift, cache=None, out_dty
     return y
 
 
-def conv_cache_update(x, cache, ktaps):
+def conv_cache_update(x, cache, ktaps, lens=None):
+    """cache <- the last ktaps-1 frames of [cache | x], or -- lens int32 [B] -- of [cache | x[:lens[b]]] per stream (unchanged at lens[b] = 0)."""
     _c.require_hip(x, cache)
     B, T, D = x.shape
     _dense("conv_cache_update", x=x, cache=cache)
     if cache.dtype != torch.float32 or tuple(cache.shape) != (B, ktaps - 1, D):
         raise ValueError("cfm.conv_cache_update: cache must be float32 [B,ktaps-1,D], got %s %s" % (cache.dtype, tuple(cache.shape)))
+    if lens is not None:
+        _stream_lens("conv_cache_update", B, lens=lens)
+        _c.check(_c.lib().cfm_conv_cache_update_len(_c.ptr(x), _c.dt_code(x), _c.ptr(cache), _c.ptr(lens), B, T, D, ktaps, _c.stream()), "cfm_conv_cache_update_len")
+        return
     _c.check(_c.lib().cfm_conv_cache_update(_c.ptr(x), _c.dt_code(x), _c.ptr(cache), B, T, D, ktaps, _c.stream()), "cfm_conv_cache_update")
 
 

@@ -24,6 +24,7 @@ struct Ctx {   // the call's arguments, then what select_route derives from them
     const cfm_layer_weights* w; const cfm_layer_scratch* s; const cfm_layer_io* io; const float* x_in; float* x_out; cfm_stream_t st;
     int M, D, FF, H, dk, adt, w_dt, Tc, Tk, P;
     bool split, has_pos, ring;
+    const int32_t* len;   // rows per item behind which the GLU output is zero: io->utt_len (whole utterances) or io->stream_len (streaming windows), else null
 };
 
 int& cin_merge_flag() {
@@ -69,6 +70,9 @@ int select_route(Ctx& c) {
     CFM_CHECK_ARG(!io->after_out || (io->after_g && io->after_b), "encoder layer: after_out needs after_g / after_b");
     CFM_CHECK_ARG(!io->utt_len || (!c.ring && !io->attn_cache && !io->causal_conv && !io->pad_valid),
                   "encoder layer: utt_len (a ragged batch of whole utterances) excludes kv_ring, attn_cache, causal_conv and pad_valid");
+    CFM_CHECK_ARG(!io->stream_len || (c.ring && !io->utt_len && !io->pad_valid),
+                  "encoder layer: stream_len (per-stream window lengths) needs kv_ring and excludes utt_len, attn_cache and pad_valid");
+    c.len = io->utt_len ? io->utt_len : io->stream_len;
     const bool chains = !c.split && w->ffm_w1f && w->ffm_w2n && w->ff_w1f && w->ff_w2n && w->qkv_wf && w->out_wf && w->pw1_wf && w->pw2_wf &&
                         cfm_rowchain_supported(c.D, c.FF);
     CFM_CHECK_ARG(!io->macaron_done || chains, "encoder layer: macaron_done needs the chain path");
@@ -100,7 +104,7 @@ int gemm(const Ctx& c, const void* A, int a_dt, int64_t lda, const void* W, cons
     d.A = A; d.W = W; d.W_lo = c.split ? Wlo : nullptr; d.bias = bias; d.residual = res; d.row_mask = row_mask; d.C = C;
     d.lda = lda; d.ldc = ldc; d.ldr = ldc; d.M = M; d.N = N; d.K = K;
     d.a_dtype = a_dt; d.w_dtype = c.w_dt; d.c_dtype = c_dt; d.act = act; d.alpha = alpha;
-    if (act == CFM_ACT_GLU && c.io->utt_len) { d.row_len = c.io->utt_len; d.row_T = c.io->T; }   // zeros past each utterance's end (cfm.h cfm_layer_io.utt_len)
+    if (act == CFM_ACT_GLU && c.len) { d.row_len = c.len; d.row_T = c.io->T; }   // zeros past each item's end (cfm.h cfm_layer_io.utt_len / stream_len)
     return cfm_gemm(&d, c.st);
 }
 
@@ -125,8 +129,12 @@ int attention(const Ctx& c, bool ring_written = false) {
     const int64_t sb = (int64_t)io->T * 3 * D, stt = 3 * D;
     if (io->new_cache)
         CFM_TRY(cfm_kv_cache_pack(io->attn_cache, c.Tc, kq, vq, adt, sb, stt, sb, stt, io->new_cache, io->B, H, io->T, dk, c.st));
-    if (c.ring && !ring_written)
-        CFM_TRY(cfm_kv_ring_write(kq, vq, adt, sb, stt, sb, stt, io->kv_ring, io->stream_offset, io->B, H, io->T, dk, io->ring_T, c.st));
+    if (c.ring && !ring_written) {
+        if (io->stream_len)
+            CFM_TRY(cfm_kv_ring_write_len(kq, vq, adt, sb, stt, sb, stt, io->kv_ring, io->stream_offset, io->stream_len, io->B, H, io->T, dk, io->ring_T, c.st));
+        else
+            CFM_TRY(cfm_kv_ring_write(kq, vq, adt, sb, stt, sb, stt, io->kv_ring, io->stream_offset, io->B, H, io->T, dk, io->ring_T, c.st));
+    }
     cfm_attn_desc a = {};
     a.q = s->qkv; a.q_sb = sb; a.q_st = stt; a.q_dtype = adt;
     if (c.ring || c.Tc > 0) {   // keys/values in f32: every slot of the ring (the slot mask picks this step's context), or [cache | new] as packed into new_cache
@@ -156,7 +164,9 @@ int depthwise(const Ctx& c) {
     if (!io->causal_conv)
         return cfm_dwconv_bn_silu(s->glu, c.adt, w->dw_w, w->dw_b, w->bn_scale, w->bn_shift, s->dw, c.adt, io->B, io->T, c.D, io->ktaps, c.st);
     CFM_TRY(cfm_dwconv_causal_bn_silu(s->glu, c.adt, io->conv_cache, w->dw_w, w->dw_b, w->bn_scale, w->bn_shift, s->dw, c.adt, io->B, io->T, c.D, io->ktaps, c.st));
-    return io->conv_cache ? cfm_conv_cache_update(s->glu, c.adt, io->conv_cache, io->B, io->T, c.D, io->ktaps, c.st) : CFM_OK;
+    if (!io->conv_cache) return CFM_OK;
+    if (io->stream_len) return cfm_conv_cache_update_len(s->glu, c.adt, io->conv_cache, io->stream_len, io->B, io->T, c.D, io->ktaps, c.st);
+    return cfm_conv_cache_update(s->glu, c.adt, io->conv_cache, io->B, io->T, c.D, io->ktaps, c.st);
 }
 
 // ---- row-chain descriptors (cfm.h cfm_rowchain_desc) -------------------------------------------------------------------------------------------------
@@ -197,7 +207,7 @@ int conv_in_chain(const Ctx& c, float* park = nullptr) {
     ci.head_a = c.s->ctx; ci.head_w = w->out_wf; ci.head_b = w->out_b; ci.head_res = c.x_out; ci.ln_g = w->ln_conv_g; ci.ln_b = w->ln_conv_b;
     ci.ln_mask = c.io->pad_valid; ci.out_f32 = c.x_out; ci.tail_w = w->pw1_wf; ci.tail_b = w->pw1_b; ci.tail_out = c.s->glu; ci.tail_N = 2 * c.D; ci.tail_glu = 1;
     if (park) { ci.tail_pair = 1; ci.out_f32 = park; }
-    ci.glu_len = c.io->utt_len; ci.glu_T = c.io->T;
+    ci.glu_len = c.len; ci.glu_T = c.io->T;
     return cfm_rowchain(&ci, c.st);
 }
 
@@ -341,7 +351,7 @@ int run_chain_next_cin(const Ctx& c) {
     next_macaron(fi, c);
     fi.cin_a = c.s->ctx; fi.cin_w = w->out_wf; fi.cin_b = w->out_b; fi.cin_res = c.x_out; fi.cin_out = c.io->next_x_out; fi.cin_ln_g = w->ln_conv_g;
     fi.cin_ln_b = w->ln_conv_b; fi.cin_mask = c.io->pad_valid; fi.cin_tail_w = w->pw1_wf; fi.cin_tail_b = w->pw1_b; fi.head_res = c.io->next_x_out;
-    fi.glu_len = c.io->utt_len; fi.glu_T = c.io->T;
+    fi.glu_len = c.len; fi.glu_T = c.io->T;
     return cfm_rowchain(&fi, c.st);
 }
 
@@ -353,7 +363,7 @@ int run_ffsplit(const Ctx& c) {
     CFM_TRY(split_ffn(c, true, c.x_in));
     cfm_ffn_split_desc q = split_reduce(c, 1, c.x_in, w->ffm_b2);   // ... then LN_mha and the fused q|k|v projection
     q.ln_g = w->ln_mha_g; q.ln_b = w->ln_mha_b; q.w1 = w->qkv_wf; q.b1 = w->qkv_b; q.N1 = 3 * c.D; q.act = CFM_ACT_NONE; q.out16 = c.s->qkv; q.ldo = 3 * c.D;
-    if (ring_written) { q.kv_ring = io->kv_ring; q.ring_offsets = io->stream_offset; q.ring_T = io->ring_T; q.ring_H = c.H; q.ring_Tq = io->T; }
+    if (ring_written) { q.kv_ring = io->kv_ring; q.ring_offsets = io->stream_offset; q.ring_T = io->ring_T; q.ring_H = c.H; q.ring_Tq = io->T; q.ring_len = io->stream_len; }
     CFM_TRY(cfm_ffn_split(&q, c.st));
     CFM_TRY(attention(c, ring_written));
     CFM_TRY(conv_in_chain(c));

@@ -53,6 +53,7 @@ struct FfnSplitArgs {
     float* ring;
     const int* ring_off;
     int ring_T, ring_H, ring_dk, ring_Tq;
+    const int* ring_len;       // null, or per stream: only rows t < ring_len[b] go into the ring (cfm.h cfm_ffn_split_desc.ring_len)
 };
 
 __device__ __forceinline__ int fs_swz(int row, int chunk) { return row * 32 + (chunk ^ (row & 15)); }   // 16-byte chunk index in a [32][256] 16-bit tile
@@ -184,7 +185,9 @@ __global__ __launch_bounds__(FS_NW * 64) void cfm_ffn_split_kernel(const FfnSpli
                             const int slot = (a.ring_off[b] + t) % a.ring_T;
                             const int hh = col / a.ring_dk, e = col - hh * a.ring_dk + (slice == 2 ? a.ring_dk : 0);
                             const f32x4 rv = unpack4<HT>(pk);
-                            *(f32x4*)(a.ring + (((int64_t)b * a.ring_H + hh) * a.ring_T + slot) * (2 * a.ring_dk) + e) = rv;
+                            // ring_len: a kernel argument, so the test is uniform; the row test behind it predicates the store per lane
+                            if (!a.ring_len || t < a.ring_len[b])
+                                *(f32x4*)(a.ring + (((int64_t)b * a.ring_H + hh) * a.ring_T + slot) * (2 * a.ring_dk) + e) = rv;
                         }
                     }
                 } else {
@@ -265,6 +268,7 @@ extern "C" int cfm_ffn_split(const cfm_ffn_split_desc* d, cfm_stream_t stream) {
                               d->M % d->ring_Tq == 0 && d->ring_T >= d->ring_Tq,
                               "cfm_ffn_split: the K/V ring needs the fused q|k|v projection (N1 = 3 D), offsets, H | D with dk %% 4 == 0, M %% T == 0 and ring_T >= T");
                 a.ring = d->kv_ring; a.ring_off = d->ring_offsets; a.ring_T = d->ring_T; a.ring_H = d->ring_H; a.ring_dk = FS_D / d->ring_H; a.ring_Tq = d->ring_Tq;
+                a.ring_len = d->ring_len;
             }
         } else {
             CFM_CHECK_ARG(d->w2 && d->psum_out && d->psum_out != d->psum, "cfm_ffn_split: the feed-forward needs w2 and its own partial slabs");

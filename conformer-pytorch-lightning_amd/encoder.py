@@ -43,10 +43,11 @@ class ConformerEncoder(nn.Module):
         self.static_chunk_size = static_chunk_size
 
     # ------------------------------------------------------------------------------------------------------------
-    def _run_blocks(self, x, attn_mask, pos_embed, pad_mask, caches, keep_from, pos_shared=False, proj=None, ring=None, conv=None, streaming=False, utt_len=None):
+    def _run_blocks(self, x, attn_mask, pos_embed, pad_mask, caches, keep_from, pos_shared=False, proj=None, ring=None, conv=None, streaming=False, utt_len=None, stream_len=None):
         """x (B,T',D) f32 -> after_norm(blocks(x)); returns (y, [trimmed per-layer caches] | None).
         ring = (kv f32 [L,B,H,ring_T,2dk], offsets int32 [B]), conv = f32 [L,B,K-1,D] | None: per-stream streaming state (StreamingBatch).
-        utt_len int32 [B]: a ragged batch of whole utterances (forward_utterances; include/cfm.h cfm_layer_io.utt_len)."""
+        utt_len int32 [B]: a ragged batch of whole utterances (forward_utterances; include/cfm.h cfm_layer_io.utt_len).
+        stream_len int32 [B]: with ring, the encoder frames of each stream's window (StreamingBatch with frame_lens; cfm_layer_io.stream_len)."""
         n = len(self.encoders)
         if proj is None:
             proj = self._project_positions(pos_embed, x)
@@ -78,7 +79,7 @@ class ConformerEncoder(nn.Module):
                                           out=bufs[i & 1], want_cache=caches is not None, pos_proj=pp, pos_shared=pos_shared,
                                           ring=None if ring is None else (ring[0][i], ring[1]), conv_cache=None if conv is None else conv[i],
                                           chain_next=(self.encoders[i + 1], bufs[(i + 1) & 1]) if chain and i + 1 < n else None,
-                                          macaron_done=chain and i > 0, split_ffn=streaming, utt_len=utt_len,
+                                          macaron_done=chain and i > 0, split_ffn=streaming, utt_len=utt_len, stream_len=stream_len,
                                           after=(self.after_norm.weight.detach(), self.after_norm.bias.detach(), y_after)
                                           if fuse_after and i + 1 == n else None)
             if new_caches is not None:
@@ -411,7 +412,20 @@ class StreamingBatch:
         every block's depthwise conv becomes causal with a (K-1)-frame left context per stream.  Off = the reference's arithmetic.
 
     step(frames (B, (chunk-1)*4+7, F)) -> (B, chunk, D) in a buffer the next step overwrites.  reset(streams) starts new utterances.
-    input_buffer() / step_resident(): the same step on windows a producer wrote into the step's own input buffer."""
+    input_buffer() / step_resident(): the same step on windows a producer wrote into the step's own input buffer.
+
+    step(frames, frame_lens) / step_resident(frame_lens): PER-STREAM window lengths -- a list or a tensor of B entries, stream b's window holds
+    n_b valid feature frames, left-aligned, 0 <= n_b <= window (what lies behind them is ignored, whatever it holds).  This is the reference's short
+    final chunk (its streaming loop ends an utterance on a window of 7 .. window-1 frames), at any step and per stream:
+      * stream b has c_b = ((n_b - 1) // 2 - 1) // 2 encoder frames (0 for n_b < 7), computed on the device; `out_lens` (int32 [B], device) holds
+        the last step's c_b;
+      * rows [0, c_b) of item b equal the reference's batch-1 forward_chunk on window[b:b+1, :n_b] with stream b's cache and offset; rows >= c_b are
+        exactly zero;
+      * the stream's state advances by c_b frames: only they enter the mask, the K/V ring, the causal conv cache and the offset;
+      * c_b = 0 leaves every piece of the stream's state untouched: an idle step (n_b = 0) is invisible and needs no reset;
+      * the lengths live in a persistent device buffer that the captured graph reads, so ONE graph serves all lengths; the first step with lengths
+        captures the length-aware form (once), which every later step -- with or without lengths -- replays.  Without lengths ever given, the step,
+        its launches and its bits are what they were."""
 
     def __init__(self, encoder, streams, decoding_chunk_size, num_decoding_left_chunks, causal_conv=False, graph=True):
         if num_decoding_left_chunks < 0:
@@ -436,7 +450,7 @@ class StreamingBatch:
         self.causal = bool(causal_conv)
         self.conv = torch.zeros((L, self.B, K - 1, D), dtype=torch.float32, device=dev) if self.causal else None
         self.pe = encoder.position_encoding.pe.reshape(-1, D).to(device=dev, dtype=torch.float32).contiguous()
-        # host mirror of an UPPER BOUND of `offsets` (every step advances every stream by `chunk`; reset() zeroes): lets step() see, without a
+        # host mirror of an UPPER BOUND of `offsets` (every step advances every stream by at most `chunk` -- by c_b <= chunk with frame_lens; reset() zeroes): lets step() see, without a
         # device sync, that a stream is about to read past the sinusoid table -- the reference's pe[offset:offset+size] comes back short there
         # and fails (attention.py:25-29; max_len = 5000 encoder frames = 200 s of audio); a long-lived stream here gets the table EXTENDED
         # with the same formula instead of wrong rows (cfm_stream_prep used to clamp to the last row, silently)
@@ -444,6 +458,9 @@ class StreamingBatch:
         self.x = None
         self.use_graph, self.graph, self.y, self._sig = bool(graph), None, None, None
         self.steps = 0
+        # per-stream window lengths: None until a step is given frame_lens, from then on the step is the length-aware one (whole windows = `window`)
+        self.frame_lens = None
+        self.out_lens = None
 
     def reset(self, streams=None):
         """start new utterances on the given streams (all by default): position 0, empty left context."""
@@ -481,25 +498,64 @@ class StreamingBatch:
         try:
             inputs, cmvn = enc._cmvn_args(self.x)
             x = enc.embed.embed_frames(inputs, cmvn)
-            cfm.stream_prep(self.offsets, self.chunk, self.need, self.ring_T, self.pe, self.slot_mask, self.pos_rows, self.abs_rows)
+            cfm.stream_prep(self.offsets, self.chunk, self.need, self.ring_T, self.pe, self.slot_mask, self.pos_rows, self.abs_rows,
+                            frame_lens=self.frame_lens, out_lens=self.out_lens)
             if self.relative:
                 x, _ = enc.position_encoding(x, 0)
             else:
                 x, _ = enc.position_encoding(x, 0, rows=self.abs_rows)
             proj = enc._project_positions(self.pos_rows, x)
-            y, _ = enc._run_blocks(x, self.slot_mask.view(torch.bool), self.pos_rows, None, None, 0, proj=proj, ring=(self.kv, self.offsets), conv=self.conv, streaming=True)
-            cfm.stream_advance(self.offsets, self.chunk)
+            y, _ = enc._run_blocks(x, self.slot_mask.view(torch.bool), self.pos_rows, None, None, 0, proj=proj, ring=(self.kv, self.offsets), conv=self.conv, streaming=True,
+                                   stream_len=self.out_lens)
+            if self.out_lens is None:
+                cfm.stream_advance(self.offsets, self.chunk)
+            else:
+                cfm.stream_advance(self.offsets, self.chunk, lens=self.out_lens, y=y)     # ... and zeroes the rows past each stream's c_b
         finally:
             for blk in enc.encoders:
                 blk.conv_module.causal = False
         return y
 
-    def step(self, frames):
+    def step(self, frames, frame_lens=None):
         if tuple(frames.shape[:2]) != (self.B, self.window):
             raise ValueError("StreamingBatch.step wants (%d, %d, F) frames, got %s" % (self.B, self.window, tuple(frames.shape)))
         cfm.require_hip(frames)
+        self._check_lens(frame_lens)                                      # before the input buffer is touched
         self.input_buffer(frames.shape[2]).copy_(frames)
-        return self.step_resident()
+        return self.step_resident(frame_lens)
+
+    def _check_lens(self, frame_lens):
+        if frame_lens is None:
+            return
+        if isinstance(frame_lens, torch.Tensor):
+            if frame_lens.dim() != 1 or frame_lens.numel() != self.B or frame_lens.dtype not in (torch.int32, torch.int64):
+                raise ValueError("StreamingBatch: frame_lens must hold %d integers, got %s %s" % (self.B, frame_lens.dtype, tuple(frame_lens.shape)))
+            if frame_lens.device.type != "cuda":
+                frame_lens = frame_lens.tolist()
+            else:
+                return                                                    # on the device: not read on the host; out-of-range values are clamped
+        frame_lens = list(frame_lens)
+        if len(frame_lens) != self.B:
+            raise ValueError("StreamingBatch: %d frame_lens for %d streams" % (len(frame_lens), self.B))
+        for b, n in enumerate(frame_lens):
+            if int(n) != n or not 0 <= n <= self.window:
+                raise ValueError("StreamingBatch: frame_lens[%d] = %r, a window holds 0 .. %d frames" % (b, n, self.window))
+
+    def _set_lens(self, frame_lens):
+        """Copy this step's lengths into the persistent device buffer the (captured) step reads; the first call switches to the length-aware step."""
+        if self.frame_lens is None:
+            if frame_lens is None:
+                return
+            self.frame_lens = torch.full((self.B,), self.window, dtype=torch.int32, device=self.dev)
+            self.out_lens = torch.zeros((self.B,), dtype=torch.int32, device=self.dev)
+            self.graph = None                                             # captured without lengths: re-capture, once
+        if frame_lens is None:
+            self.frame_lens.fill_(self.window)
+        elif isinstance(frame_lens, torch.Tensor) and frame_lens.device.type == "cuda":
+            self.frame_lens.copy_(frame_lens.clamp(0, self.window))
+        else:
+            vals = frame_lens.tolist() if isinstance(frame_lens, torch.Tensor) else [int(n) for n in frame_lens]
+            self.frame_lens.copy_(torch.tensor(vals, dtype=torch.int32), non_blocking=False)
 
     def input_buffer(self, num_features=None):
         """The (B, window, F) f32 buffer the step reads.  A producer on the same stream (fbank.StreamingFbank) writes the windows here and calls
@@ -512,9 +568,11 @@ class StreamingBatch:
             raise ValueError("StreamingBatch: %d features per frame, the stream was started with %d" % (num_features, self.x.shape[2]))
         return self.x
 
-    def step_resident(self):
+    def step_resident(self, frame_lens=None):
         """step() on what input_buffer() holds."""
         self.input_buffer()
+        self._check_lens(frame_lens)
+        self._set_lens(frame_lens)
         self.steps += 1
         if max(self._host_off) + self.chunk > self.pe.size(0):
             self._grow_table(max(self._host_off) + self.chunk)
@@ -530,11 +588,17 @@ class StreamingBatch:
                 stream.wait_stream(torch.cuda.current_stream(self.dev))
                 with torch.cuda.stream(stream):
                     saved = self.offsets.clone(), None if self.conv is None else self.conv.clone()
+                    lens = None if self.frame_lens is None else (self.frame_lens.clone(), self.out_lens.clone())
+                    if lens is not None:
+                        self.frame_lens.zero_()                           # the length-aware warm-up runs every stream idle: it touches no state at all
                     self._step_impl()                                     # warm-up ON the capture stream (its own scratch arena) ...
                     stream.synchronize()
                     self.offsets.copy_(saved[0])                          # ... with the state it advanced put back (ring slots rewritten: same data)
                     if self.conv is not None:
                         self.conv.copy_(saved[1])
+                    if lens is not None:
+                        self.frame_lens.copy_(lens[0])
+                        self.out_lens.copy_(lens[1])                      # this step's c_b, which the warm-up overwrote with zeros
                     graph = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(graph, stream=stream):
                         self.y = self._step_impl()

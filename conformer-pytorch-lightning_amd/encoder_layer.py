@@ -90,7 +90,7 @@ class ConformerEncoderLayer(nn.Module):
 
     def fused_forward(self, x, attn_mask, pos_embed, pad_mask, attn_cache, xn_ready=False, next_norm=None, out=None,
                       want_cache=True, pos_proj=None, pos_shared=False, after=None, ring=None, conv_cache=None, chain_next=None,
-                      macaron_done=False, split_ffn=False, utt_len=None):
+                      macaron_done=False, split_ffn=False, utt_len=None, stream_len=None):
         """x (B,T,D) float32 on an MI355X -> (norm_final(block(x)), new_attn_cache | None).  ``x`` is not modified.
         ring = (kv_ring f32 [B,H,ring_T,2dk], offsets int32 [B]): per-stream streaming state (include/cfm.h cfm_layer_io.kv_ring);
         attn_mask is then the (B,1,ring_T) slot mask and pos_embed the B*ring_T positional rows.  conv_cache f32 [B,K-1,D]: the
@@ -98,7 +98,8 @@ class ConformerEncoderLayer(nn.Module):
         chain_next = (next block, its output buffer): this block's last launch also runs the NEXT block's macaron chain (cfm.h
         cfm_layer_io.next_w); the next block is then called with macaron_done=True and the same output buffer, and THIS call's
         returned tensor does not hold the block output.  Only ConformerEncoder._run_blocks uses it.
-        utt_len int32 [B]: a ragged batch of whole utterances, item b has utt_len[b] frames (cfm.h cfm_layer_io.utt_len); the caller masks the keys."""
+        utt_len int32 [B]: a ragged batch of whole utterances, item b has utt_len[b] frames (cfm.h cfm_layer_io.utt_len); the caller masks the keys.
+        stream_len int32 [B] (with ring): stream b's window has stream_len[b] encoder frames (cfm.h cfm_layer_io.stream_len)."""
         _inference_only(self, "ConformerEncoderLayer.fused_forward")
         cfm.require_hip(x)
         if x.dtype != torch.float32 or not x.is_contiguous():
@@ -193,6 +194,11 @@ class ConformerEncoderLayer(nn.Module):
                 raise RuntimeError("utt_len must be a contiguous int32 tensor of B entries")
             cfm.require_hip(utt_len)
             io.utt_len = utt_len.data_ptr()
+        if stream_len is not None:
+            if stream_len.dtype != torch.int32 or stream_len.numel() != B or not stream_len.is_contiguous():
+                raise RuntimeError("stream_len must be a contiguous int32 tensor of B entries")
+            cfm.require_hip(stream_len)
+            io.stream_len = stream_len.data_ptr()
         ng = nb = None
         if next_norm is not None:
             ng, nb = next_norm.weight.data_ptr(), next_norm.bias.data_ptr()

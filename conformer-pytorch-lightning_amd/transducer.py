@@ -88,13 +88,16 @@ class StreamingRecognizer:
     step_audio(samples, lens=None) is step() from the waveform: fbank.StreamingFbank writes the feature windows straight into the encoder step's
     input buffer (fbank_args: its num_mel_bins, dither, seed, ...; the defaults are the reference's settings without dither).
 
-    step(frames (B, (chunk - 1) * 4 + 7, F), lens=None) -> list of B lists: the tokens the step added.  lens[b]: how many of the chunk's
-    encoder frames belong to stream b's utterance -- fewer than `chunk` for a padded final window, 0 for a stream between utterances
-    (its decoder state does not change; its encoder position still advances: reset it before its next utterance).
+    step(frames (B, (chunk - 1) * 4 + 7, F), lens=None, frame_lens=None) -> list of B lists: the tokens the step added.
 
-    LIMIT: StreamingBatch takes full windows only, so the last lens[b] frames of a padded final window see the padding through the
-    non-causal depthwise convolution, where the reference would run a shorter chunk (model.py:146).  Ragged encoder windows are not
-    supported; causal_conv=True (the opt-in extension) has no such look-ahead."""
+    frame_lens[b] (list or tensor, B entries): the valid FEATURE frames of stream b's window, left-aligned, 0 .. window -- the reference's short final
+    chunk (`end = min(cur + decoding_window, num_frames)`, model.py:145-147), legal at any step.  The encoder step is then length-aware end to end
+    (encoder.StreamingBatch): stream b gets c_b = ((n_b - 1) // 2 - 1) // 2 encoder frames (0 below 7 feature frames), exactly the reference's batch-1
+    forward_chunk on the shorter window, its state advances by c_b, and the decoder reads those c_b frames (`encoder_stream.out_lens`, on the device).
+    frame_lens[b] = 0 is an idle stream: nothing of its encoder or decoder state changes, so it needs no reset before it continues.
+
+    lens[b] (without frame_lens): how many of the chunk's encoder frames the DECODER reads for stream b; the encoder still runs and advances the whole
+    window.  Giving both raises: frame_lens already fixes the decoder's lengths."""
 
     def __init__(self, encoder, predictor, joint, streams, decoding_chunk_size, num_decoding_left_chunks, blank=0, n_steps=64, carry=True, causal_conv=False,
                  steps_per_replay=8, graph=True, fbank_args=None):
@@ -110,14 +113,18 @@ class StreamingRecognizer:
         self.encoder_out = None
         self.audio, self.fbank_args = None, dict(fbank_args or {})      # step_audio's fbank.StreamingFbank (made on first use) and its keyword arguments
 
-    def step(self, frames, lens=None):
-        self.encoder_out = self.encoder_stream.step(frames)                             # (B, chunk, D), overwritten by the next step
-        return self.decoder.decode(self.encoder_out, lens)
+    def step(self, frames, lens=None, frame_lens=None):
+        if lens is not None and frame_lens is not None:
+            raise ValueError("StreamingRecognizer.step: give lens (encoder frames the decoder reads) or frame_lens (feature frames of each window), not both")
+        self.encoder_out = self.encoder_stream.step(frames, frame_lens)                 # (B, chunk, D), overwritten by the next step
+        return self.decoder.decode(self.encoder_out, self.encoder_stream.out_lens if frame_lens is not None else lens)
 
     def step_audio(self, samples, lens=None):
         """step() from the waveform (the reference's deploy.py preprocess_stream + greedy_search_streaming_app): samples (B, n) int16 | float32 on
         the int16 scale, left-aligned -- fbank.StreamingFbank.n_next new samples per stream, n_first for a stream that was reset (and then for
-        the call: the others read their first n_next).  One fbank launch writes the feature windows into the encoder step's input buffer."""
+        the call: the others read their first n_next).  One fbank launch writes the feature windows into the encoder step's input buffer.
+        Whole blocks only: a ragged audio tail would need fbank.StreamingFbank to emit fewer rows per stream, which it does not do; a caller with
+        the features at hand passes the short final window to step(frames, frame_lens=...)."""
         if self.audio is None:
             import fbank
             self.audio = fbank.StreamingFbank(self.B, self.chunk, self.encoder_stream.dev, **self.fbank_args)

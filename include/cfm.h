@@ -410,6 +410,13 @@ int cfm_attn_mask(const uint8_t* valid, const uint8_t* chunk, uint8_t* out, int3
  *                      absolute encoding's row, attention.py:119-120)
  *  cfm_kv_ring_write   K / V rows of the T new frames (addressed like cfm_attn_desc k / v, head h at h*dk) -> ring slots (offset+t) mod ring_T
  *  cfm_stream_advance  offset[b] += T for streams with active[b] != 0 (active NULL: all)
+ *  cfm_stream_prep_len / cfm_kv_ring_write_len / cfm_stream_advance_len / cfm_conv_cache_update_len: the same with per-stream lengths.  Stream b's
+ *                      window holds frame_lens[b] valid FEATURE frames (left-aligned, 0 .. window), hence out_lens[b] = c_b = ((n-1)/2-1)/2 encoder
+ *                      frames (0 for n < 7; capped at T), which cfm_stream_prep_len writes: the newest frame is offset + c_b - 1, the mask covers the
+ *                      min(offset, need) cached frames and the c_b new ones (c_b = 0: the cached frames only; none at offset 0).  The other three take
+ *                      lens = out_lens: ring slots are written for rows t < lens[b] only, the conv cache becomes the last ktaps-1 frames of
+ *                      [cache | x[:lens[b]]], offset[b] += lens[b] and rows t >= lens[b] of y f32 [B,T,D] (optional) are set to zero.  lens[b] = 0
+ *                      changes nothing of stream b.
  *  cfm_dwconv_causal_bn_silu  y = SiLU(BN_eval(causal depthwise conv over [cache | x])), cache f32 [B,ktaps-1,D] or NULL (zeros)
  *  cfm_conv_cache_update      cache <- last ktaps-1 frames of [cache | x], in place
  */
@@ -421,6 +428,13 @@ int cfm_stream_advance(int32_t* offsets, const uint8_t* active, int32_t B, int32
 int cfm_dwconv_causal_bn_silu(const void* x, int32_t x_dtype, const float* cache, const float* w, const float* dw_bias, const float* bn_scale,
                               const float* bn_shift, void* y, int32_t y_dtype, int32_t B, int32_t T, int32_t D, int32_t ktaps, cfm_stream_t stream);
 int cfm_conv_cache_update(const void* x, int32_t x_dtype, float* cache, int32_t B, int32_t T, int32_t D, int32_t ktaps, cfm_stream_t stream);
+int cfm_stream_prep_len(const int32_t* offsets, const int32_t* frame_lens, int32_t* out_lens, int32_t B, int32_t T, int32_t need, int32_t ring_T,
+                        const float* pe, int32_t max_len, int32_t D, uint8_t* slot_mask, float* pos_rows, float* abs_rows, cfm_stream_t stream);
+int cfm_kv_ring_write_len(const void* k, const void* v, int32_t kv_dtype, int64_t k_sb, int64_t k_st, int64_t v_sb, int64_t v_st, float* ring,
+                          const int32_t* offsets, const int32_t* lens, int32_t B, int32_t H, int32_t T, int32_t dk, int32_t ring_T, cfm_stream_t stream);
+int cfm_stream_advance_len(int32_t* offsets, const int32_t* lens, float* y, int32_t B, int32_t T, int32_t D, cfm_stream_t stream);
+int cfm_conv_cache_update_len(const void* x, int32_t x_dtype, float* cache, const int32_t* lens, int32_t B, int32_t T, int32_t D, int32_t ktaps,
+                              cfm_stream_t stream);
 
 /* element-wise dtype conversion:  dst = cast(src) */
 int cfm_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, cfm_stream_t stream);
@@ -516,6 +530,14 @@ typedef struct {
      * the keys t >= utt_len[b] through attn_mask; rows at and past utt_len[b] of x_out hold no defined result.  NULL = today's behaviour.
      * Not with kv_ring, attn_cache, causal_conv or pad_valid. */
     const int32_t* utt_len;
+    /* The batched streaming step with PER-STREAM window lengths (needs kv_ring): int32 [B], only the first stream_len[b] <= T rows of stream b are frames
+     * of its utterance (a short final chunk, or 0 for an idle stream).  What utt_len does for whole utterances -- the same select behind the GLU, on every
+     * route, so the symmetric depthwise convolution of a valid row sees zeros past the stream's end, as the reference's batch-1 forward_chunk on the
+     * shorter window does -- plus the streaming state: only rows t < stream_len[b] are written to the K/V ring (cfm_kv_ring_write_len, or
+     * cfm_ffn_split_desc.ring_len on CFM_ROUTE_FFSPLIT) and enter conv_cache (cfm_conv_cache_update_len); stream_len[b] = 0 leaves both untouched.
+     * attn_mask is the slot mask of cfm_stream_prep_len.  Rows at and past stream_len[b] of x_out hold no defined result (non-finite values included)
+     * and reach no valid row.  NULL = every stream has T rows, as before.  Not with utt_len, attn_cache or pad_valid. */
+    const int32_t* stream_len;
 } cfm_layer_io;
 
 /* The launch sequence of one block.  Every argument is checked and ONE route chosen before anything is launched (csrc/encoder.cpp select_route).
@@ -834,6 +856,9 @@ typedef struct {
     float* kv_ring;
     const int32_t* ring_offsets;
     int32_t ring_T, ring_H, ring_Tq;
+    /* optional int32 [B] with kv_ring: only rows t < ring_len[b] of stream b are frames of the stream and go into the ring; later rows touch no slot.
+     * out16 still receives every row.  NULL = all ring_Tq rows, as before */
+    const int32_t* ring_len;
 } cfm_ffn_split_desc;
 int cfm_ffn_split(const cfm_ffn_split_desc* d, cfm_stream_t stream);
 int cfm_ffn_split_supported(int32_t D, int32_t FF);
