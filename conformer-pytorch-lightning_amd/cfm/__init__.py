@@ -341,15 +341,11 @@ def lib():
         L.cfm_encoder_train_backward.argtypes = [c_i32, ctypes.POINTER(LayerTrainWeights), ctypes.POINTER(LayerTrainIO), ctypes.POINTER(LayerTrainSaved),
                                                  ctypes.POINTER(LayerTrainScratch), ctypes.POINTER(LayerTrainGrads), ctypes.POINTER(c_p), c_p, c_p, c_p,
                                                  LAYER_DONE_FN, c_p, ctypes.POINTER(c_p), c_p]
-        L.cfm_stream_prep.argtypes = [c_p, c_i32, c_i32, c_i32, c_i32, c_p, c_i32, c_i32, c_p, c_p, c_p, c_p]
-        L.cfm_kv_ring_write.argtypes = [c_p, c_p, c_i32, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p]
-        L.cfm_stream_advance.argtypes = [c_p, c_p, c_i32, c_i32, c_p]
+        L.cfm_stream_prep.argtypes = [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p, c_i32, c_i32, c_p, c_p, c_p, c_p]
+        L.cfm_kv_ring_write.argtypes = [c_p, c_p, c_i32, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p]
+        L.cfm_stream_advance.argtypes = [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p]
         L.cfm_dwconv_causal_bn_silu.argtypes = [c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p]
-        L.cfm_conv_cache_update.argtypes = [c_p, c_i32, c_p, c_i32, c_i32, c_i32, c_i32, c_p]
-        L.cfm_stream_prep_len.argtypes = [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p, c_i32, c_i32, c_p, c_p, c_p, c_p]
-        L.cfm_kv_ring_write_len.argtypes = [c_p, c_p, c_i32, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p]
-        L.cfm_stream_advance_len.argtypes = [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p]
-        L.cfm_conv_cache_update_len.argtypes = [c_p, c_i32, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p]
+        L.cfm_conv_cache_update.argtypes = [c_p, c_i32, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p]
         for name in ("cfm_layernorm_bwd_ws", "cfm_dwconv_bn_ws", "cfm_conv1_wgrad_ws", "cfm_joint_act_bwd_ws"):
             getattr(L, name).restype = c_i64
         L.cfm_prof_enable.argtypes = [c_i32]
@@ -364,8 +360,7 @@ def lib():
                      "cfm_layernorm_bwd", "cfm_glu_bwd", "cfm_dwconv_bn_train", "cfm_dwconv_bn_train_bwd", "cfm_col2im_relu_bwd", "cfm_conv1_wgrad",
                      "cfm_ctc_nll_train_groups", "cfm_ctc_grad", "cfm_adam_step", "cfm_adam_clip_step", "cfm_sumsq", "cfm_dropout_rows", "cfm_dropout_mask", "cfm_pack_matrices", "cfm_pack_vectors", "cfm_greedy_step", "cfm_greedy_chunk_begin", "cfm_greedy_chunk_step", "cfm_fbank", "cfm_fbank_stream", "cfm_ffn_split", "cfm_ffn_split_supported", "cfm_layernorm_bwd_fused", "cfm_dwconv_bn_train_bwd_acc",
                      "cfm_attention_group", "cfm_attention_bwd_group", "cfm_dwconv_bn_train_groups", "cfm_dwconv_bn_train_bwd_groups",
-                     "cfm_encoder_train_forward", "cfm_encoder_train_backward", "cfm_stream_prep", "cfm_kv_ring_write", "cfm_stream_advance", "cfm_dwconv_causal_bn_silu", "cfm_conv_cache_update",
-                     "cfm_stream_prep_len", "cfm_kv_ring_write_len", "cfm_stream_advance_len", "cfm_conv_cache_update_len"):
+                     "cfm_encoder_train_forward", "cfm_encoder_train_backward", "cfm_stream_prep", "cfm_kv_ring_write", "cfm_stream_advance", "cfm_dwconv_causal_bn_silu", "cfm_conv_cache_update"):
             getattr(L, name).restype = ctypes.c_int
         _lib = L
     return _lib

@@ -1239,7 +1239,7 @@ def _stream_lens(op, B, **named):
 def stream_prep(offsets, T, need, ring_T, pe, slot_mask, pos_rows, abs_rows=None, frame_lens=None, out_lens=None):
     """offsets int32 [B] -> slot_mask u8 [B,ring_T], pos_rows f32 [B,ring_T,D] (= pe[frame held by the slot]), abs_rows f32 [B,D] = pe[offset].
     frame_lens int32 [B] (with out_lens int32 [B]): per-stream window lengths in feature frames; out_lens receives the encoder frames c_b of each
-    stream and the mask / rows cover the cached frames and those c_b (include/cfm.h cfm_stream_prep_len)."""
+    stream and the mask / rows cover the cached frames and those c_b (include/cfm.h cfm_stream_prep)."""
     _c.require_hip(offsets, pe, slot_mask, pos_rows, abs_rows)
     B = offsets.numel()
     D = pe.shape[-1]
@@ -1250,31 +1250,28 @@ def stream_prep(offsets, T, need, ring_T, pe, slot_mask, pos_rows, abs_rows=None
         raise ValueError("cfm.stream_prep: frame_lens and out_lens come together")
     if frame_lens is not None:
         _stream_lens("stream_prep", B, frame_lens=frame_lens, out_lens=out_lens)
-        _c.check(_c.lib().cfm_stream_prep_len(_c.ptr(offsets), _c.ptr(frame_lens), _c.ptr(out_lens), B, T, need, ring_T, _c.ptr(pe), pe.numel() // D, D,
-                                              _c.ptr(slot_mask), _c.ptr(pos_rows), _c.ptr(abs_rows), _c.stream()), "cfm_stream_prep_len")
-        return
-    _c.check(_c.lib().cfm_stream_prep(_c.ptr(offsets), B, T, need, ring_T, _c.ptr(pe), pe.numel() // D, D, _c.ptr(slot_mask), _c.ptr(pos_rows), _c.ptr(abs_rows),
-                                      _c.stream()), "cfm_stream_prep")
+    _c.check(_c.lib().cfm_stream_prep(_c.ptr(offsets), _c.ptr(frame_lens), _c.ptr(out_lens), B, T, need, ring_T, _c.ptr(pe), pe.numel() // D, D,
+                                      _c.ptr(slot_mask), _c.ptr(pos_rows), _c.ptr(abs_rows), _c.stream()), "cfm_stream_prep")
 
 
 def stream_advance(offsets, T, active=None, lens=None, y=None):
     """offsets[b] += T (active streams), or -- lens int32 [B] -- += lens[b], with rows t >= lens[b] of y f32 [B,T,D] (optional) set to zero."""
     _c.require_hip(offsets, active)
     _dense("stream_advance", offsets=offsets, active=active)
+    B = offsets.numel()
+    D = 0
     if lens is not None:
-        B = offsets.numel()
         _stream_lens("stream_advance", B, lens=lens)
-        D = 0
-        if y is not None:
-            _c.require_hip(y)
-            if y.dtype != torch.float32 or not y.is_contiguous() or y.dim() != 3 or tuple(y.shape[:2]) != (B, T) or active is not None:
-                raise ValueError("cfm.stream_advance: y must be contiguous float32 [B,T,D] (and active is not combined with lens)")
-            D = y.shape[2]
-        _c.check(_c.lib().cfm_stream_advance_len(_c.ptr(offsets), _c.ptr(lens), _c.ptr(y), B, T, D, _c.stream()), "cfm_stream_advance_len")
-        return
+        if active is not None:
+            raise ValueError("cfm.stream_advance: active is not combined with lens")
     if y is not None:
-        raise ValueError("cfm.stream_advance: y comes with lens")
-    _c.check(_c.lib().cfm_stream_advance(_c.ptr(offsets), _c.ptr(active), offsets.numel(), T, _c.stream()), "cfm_stream_advance")
+        if lens is None:
+            raise ValueError("cfm.stream_advance: y comes with lens")
+        _c.require_hip(y)
+        if y.dtype != torch.float32 or not y.is_contiguous() or y.dim() != 3 or tuple(y.shape[:2]) != (B, T):
+            raise ValueError("cfm.stream_advance: y must be contiguous float32 [B,T,D]")
+        D = y.shape[2]
+    _c.check(_c.lib().cfm_stream_advance(_c.ptr(offsets), _c.ptr(active), _c.ptr(lens), _c.ptr(y), B, T, D, _c.stream()), "cfm_stream_advance")
 
 
 def dwconv_causal_bn_silu(x, w, dw_bias, bn_scale, bn_shift, cache=None, out_dtype=None):
@@ -1300,9 +1297,7 @@ def conv_cache_update(x, cache, ktaps, lens=None):
         raise ValueError("cfm.conv_cache_update: cache must be float32 [B,ktaps-1,D], got %s %s" % (cache.dtype, tuple(cache.shape)))
     if lens is not None:
         _stream_lens("conv_cache_update", B, lens=lens)
-        _c.check(_c.lib().cfm_conv_cache_update_len(_c.ptr(x), _c.dt_code(x), _c.ptr(cache), _c.ptr(lens), B, T, D, ktaps, _c.stream()), "cfm_conv_cache_update_len")
-        return
-    _c.check(_c.lib().cfm_conv_cache_update(_c.ptr(x), _c.dt_code(x), _c.ptr(cache), B, T, D, ktaps, _c.stream()), "cfm_conv_cache_update")
+    _c.check(_c.lib().cfm_conv_cache_update(_c.ptr(x), _c.dt_code(x), _c.ptr(cache), _c.ptr(lens), B, T, D, ktaps, _c.stream()), "cfm_conv_cache_update")
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -129,12 +129,8 @@ int attention(const Ctx& c, bool ring_written = false) {
     const int64_t sb = (int64_t)io->T * 3 * D, stt = 3 * D;
     if (io->new_cache)
         CFM_TRY(cfm_kv_cache_pack(io->attn_cache, c.Tc, kq, vq, adt, sb, stt, sb, stt, io->new_cache, io->B, H, io->T, dk, c.st));
-    if (c.ring && !ring_written) {
-        if (io->stream_len)
-            CFM_TRY(cfm_kv_ring_write_len(kq, vq, adt, sb, stt, sb, stt, io->kv_ring, io->stream_offset, io->stream_len, io->B, H, io->T, dk, io->ring_T, c.st));
-        else
-            CFM_TRY(cfm_kv_ring_write(kq, vq, adt, sb, stt, sb, stt, io->kv_ring, io->stream_offset, io->B, H, io->T, dk, io->ring_T, c.st));
-    }
+    if (c.ring && !ring_written)
+        CFM_TRY(cfm_kv_ring_write(kq, vq, adt, sb, stt, sb, stt, io->kv_ring, io->stream_offset, io->stream_len, io->B, H, io->T, dk, io->ring_T, c.st));
     cfm_attn_desc a = {};
     a.q = s->qkv; a.q_sb = sb; a.q_st = stt; a.q_dtype = adt;
     if (c.ring || c.Tc > 0) {   // keys/values in f32: every slot of the ring (the slot mask picks this step's context), or [cache | new] as packed into new_cache
@@ -165,8 +161,7 @@ int depthwise(const Ctx& c) {
         return cfm_dwconv_bn_silu(s->glu, c.adt, w->dw_w, w->dw_b, w->bn_scale, w->bn_shift, s->dw, c.adt, io->B, io->T, c.D, io->ktaps, c.st);
     CFM_TRY(cfm_dwconv_causal_bn_silu(s->glu, c.adt, io->conv_cache, w->dw_w, w->dw_b, w->bn_scale, w->bn_shift, s->dw, c.adt, io->B, io->T, c.D, io->ktaps, c.st));
     if (!io->conv_cache) return CFM_OK;
-    if (io->stream_len) return cfm_conv_cache_update_len(s->glu, c.adt, io->conv_cache, io->stream_len, io->B, io->T, c.D, io->ktaps, c.st);
-    return cfm_conv_cache_update(s->glu, c.adt, io->conv_cache, io->B, io->T, c.D, io->ktaps, c.st);
+    return cfm_conv_cache_update(s->glu, c.adt, io->conv_cache, io->stream_len, io->B, io->T, c.D, io->ktaps, c.st);
 }
 
 // ---- row-chain descriptors (cfm.h cfm_rowchain_desc) -------------------------------------------------------------------------------------------------

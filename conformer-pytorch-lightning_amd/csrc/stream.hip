@@ -12,9 +12,10 @@
 //   cfm_stream_prep     offsets -> slot mask [B, ring_T], positional rows pe[frame in slot] [B, ring_T, D], optional absolute rows [B, D]
 //   cfm_kv_ring_write   this step's K / V rows (from the fused QKV projection) -> their slots of the ring
 //   cfm_stream_advance  offset[b] += chunk for active streams
-//   cfm_*_len           the same four steps with PER-STREAM lengths: stream b's window holds frame_lens[b] valid feature frames, hence
-//                       c_b = ((n - 1) / 2 - 1) / 2 encoder frames (0 below 7: the two un-padded stride-2 convolutions of the front-end); only
-//                       those enter the mask, the ring, the conv cache and the offset, and c_b = 0 touches no state at all
+//   frame_lens / lens   optional in those three and in cfm_conv_cache_update (NULL: whole windows) -- PER-STREAM lengths: stream b's window holds
+//                       frame_lens[b] valid feature frames, hence c_b = ((n - 1) / 2 - 1) / 2 encoder frames (0 below 7: the two un-padded stride-2
+//                       convolutions of the front-end); only those enter the mask, the ring, the conv cache and the offset, and c_b = 0 touches no
+//                       state at all
 //   cfm_dwconv_causal_bn_silu / cfm_conv_cache_update   the OPT-IN causal depthwise convolution with a (ktaps-1)-frame left context per
 //                       stream (the reference has no causal mode and ignores its cnn_cache, convolution.py:34-39: off = parity)
 #include "cfm_common.h"
@@ -28,29 +29,44 @@ __device__ __forceinline__ int slot_frame(int last, int s, int ring_T) {
     return last - r;
 }
 
-__global__ void cfm_stream_prep_kernel(const int* __restrict__ offsets, int B, int T, int need, int ring_T, const float* __restrict__ pe, int max_len,
-                                       int D, uint8_t* __restrict__ slot_mask, float* __restrict__ pos_rows, float* __restrict__ abs_rows) {
+// encoder frames of a window of n feature frames (convolution.py: two 3-tap stride-2 convolutions without padding), at most T
+__device__ __forceinline__ int stream_out_len(int n, int T) {
+    const int c = n < 7 ? 0 : ((n - 1) / 2 - 1) / 2;
+    return c < T ? c : T;
+}
+
+// The newest frame of stream b is off + c_b - 1, c_b = T or -- frame_lens set -- stream_out_len(frame_lens[b]), which out_lens[b] receives: the mask covers
+// the min(off, need) cached frames and the c_b new ones.  c_b = 0: the newest frame is off - 1, so the mask is the cached frames alone, and at off = 0 no
+// slot at all (slot_frame then returns a negative frame)
+__global__ void cfm_stream_prep_kernel(const int* __restrict__ offsets, const int* __restrict__ frame_lens, int* __restrict__ out_lens, int B, int T, int need,
+                                       int ring_T, const float* __restrict__ pe, int max_len, int D, uint8_t* __restrict__ slot_mask,
+                                       float* __restrict__ pos_rows, float* __restrict__ abs_rows) {
     const int b = blockIdx.y, s = blockIdx.x;
     const int off = offsets[b];
+    const int c = frame_lens ? stream_out_len(frame_lens[b], T) : T;
     const int cached = off < need ? off : need;
+    if (frame_lens && s == 0 && threadIdx.x == 0) out_lens[b] = c;
     if (s < ring_T) {
-        const int f = slot_frame(off + T - 1, s, ring_T);
+        const int f = slot_frame(off + c - 1, s, ring_T);
         const bool valid = f >= off - cached && f >= 0;
         if (threadIdx.x == 0) slot_mask[(int64_t)b * ring_T + s] = valid ? 1 : 0;
         // f < max_len is the caller's job (encoder.StreamingBatch extends the table before a stream reaches its end); the clamp only keeps a
         // misuse of the C entry point inside the allocation
         const int row = valid ? (f < max_len ? f : max_len - 1) : 0;
-        for (int c = threadIdx.x * 4; c < D; c += blockDim.x * 4)
-            *(f32x4*)(pos_rows + ((int64_t)b * ring_T + s) * D + c) = *(const f32x4*)(pe + (int64_t)row * D + c);
+        for (int i = threadIdx.x * 4; i < D; i += blockDim.x * 4)
+            *(f32x4*)(pos_rows + ((int64_t)b * ring_T + s) * D + i) = *(const f32x4*)(pe + (int64_t)row * D + i);
     } else if (abs_rows) {                                  // one extra block per stream: the absolute-encoding row pe[offset] (attention.py:119-120)
         const int row = off < max_len ? off : max_len - 1;
-        for (int c = threadIdx.x * 4; c < D; c += blockDim.x * 4) *(f32x4*)(abs_rows + (int64_t)b * D + c) = *(const f32x4*)(pe + (int64_t)row * D + c);
+        for (int i = threadIdx.x * 4; i < D; i += blockDim.x * 4) *(f32x4*)(abs_rows + (int64_t)b * D + i) = *(const f32x4*)(pe + (int64_t)row * D + i);
     }
 }
 
-// ring[b, h, (offset[b] + t) mod ring_T, 0:dk] = K_t, [dk:2dk] = V_t for the T new frames
+// ring[b, h, (offset[b] + t) mod ring_T, 0:dk] = K_t, [dk:2dk] = V_t for the T new frames, or -- lens set -- for rows t < lens[b] only.  Later rows touch
+// no slot: they are no frames of the stream and may hold anything, non-finite values included, while a masked slot has to stay finite (the attention
+// multiplies its values with a probability of zero)
 __global__ void cfm_kv_ring_write_kernel(const void* __restrict__ k, const void* __restrict__ v, int dt, int64_t k_sb, int64_t k_st, int64_t v_sb, int64_t v_st,
-                                         float* __restrict__ ring, const int* __restrict__ offsets, int B, int H, int T, int dk, int ring_T) {
+                                         float* __restrict__ ring, const int* __restrict__ offsets, const int* __restrict__ lens, int B, int H, int T, int dk,
+                                         int ring_T) {
     const int64_t n = (int64_t)B * T * H * 2 * dk;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int e = (int)(i % (2 * dk));
@@ -59,6 +75,7 @@ __global__ void cfm_kv_ring_write_kernel(const void* __restrict__ k, const void*
         r /= H;
         const int t = (int)(r % T);
         const int b = (int)(r / T);
+        if (lens && t >= lens[b]) continue;
         const int slot = (offsets[b] + t) % ring_T;
         const float val = e < dk ? load_as_f32(k, (int64_t)b * k_sb + (int64_t)t * k_st + h * dk + e, dt)
                                  : load_as_f32(v, (int64_t)b * v_sb + (int64_t)t * v_st + h * dk + (e - dk), dt);
@@ -66,9 +83,19 @@ __global__ void cfm_kv_ring_write_kernel(const void* __restrict__ k, const void*
     }
 }
 
-__global__ void cfm_stream_advance_kernel(int* offsets, const uint8_t* __restrict__ active, int B, int T) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < B && (!active || active[b])) offsets[b] += T;
+// offsets[b] += c_b, one workgroup per stream: c_b = T for an active stream and 0 for an inactive one (active NULL: all active), or -- lens set --
+// lens[b] clamped to 0 .. T.  Rows t >= c_b of y [B, T, D] (optional, with lens) become zero -- a store, not a product: those rows may hold anything
+__global__ void cfm_stream_advance_kernel(int* offsets, const uint8_t* __restrict__ active, const int* __restrict__ lens, float* __restrict__ y, int T, int D) {
+    const int b = blockIdx.x;
+    int c = T;
+    if (lens) c = lens[b] < 0 ? 0 : (lens[b] < T ? lens[b] : T);
+    else if (active && !active[b]) c = 0;
+    if (y) {
+        float* const rows = y + ((int64_t)b * T + c) * D;
+        const int n = (T - c) * D;
+        for (int i = threadIdx.x * 4; i < n; i += blockDim.x * 4) *(f32x4*)(rows + i) = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+    if (threadIdx.x == 0 && c > 0) offsets[b] += c;
 }
 
 // y[b,t,d] = silu( (sum_k w[d,k] xx[b, t+k, d] + bias[d]) * scale[d] + shift[d] ),  xx = [cache (K-1 frames) | x (T frames)]
@@ -92,96 +119,17 @@ __global__ void cfm_dwconv_causal_kernel(const void* __restrict__ x, int x_dt, c
     }
 }
 
-// cache <- the last K-1 frames of [cache | x], in place: a thread owns one (stream, channel) column and walks its rows upwards, so a row
-// is overwritten only after every later read of it (new row j reads old row j + T > j)
-__global__ void cfm_conv_cache_update_kernel(const void* __restrict__ x, int x_dt, float* __restrict__ cache, int B, int T, int D, int K) {
+// cache <- the last K-1 frames of [cache | x[:T_b]], in place; T_b = T, or -- lens set -- min(lens[b], T).  New row j is row j + T_b of [cache | x[:T_b]]:
+// old cache row j + T_b while j + T_b < K-1, else x row j + T_b - (K-1) < T_b.  A thread owns one (stream, channel) column and walks j upwards, and for
+// T_b > 0 the cache row it reads, j + T_b, lies above every row written so far (<= j); T_b = 0 would read and write row j itself -- the column is left alone
+__global__ void cfm_conv_cache_update_kernel(const void* __restrict__ x, int x_dt, float* __restrict__ cache, const int* __restrict__ lens, int B, int T, int D,
+                                             int K) {
     const int C = K - 1;
     const int64_t n = (int64_t)B * D;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int d = (int)(i % D);
         const int b = (int)(i / D);
-        for (int j = 0; j < C; ++j) {
-            const int tt = j + T - C;                       // position in x of new cache row j
-            cache[((int64_t)b * C + j) * D + d] = tt >= 0 ? load_as_f32(x, ((int64_t)b * T + tt) * D + d, x_dt) : cache[((int64_t)b * C + (C + tt)) * D + d];
-        }
-    }
-}
-
-// encoder frames of a window of n feature frames (convolution.py: two 3-tap stride-2 convolutions without padding), at most T
-__device__ __forceinline__ int stream_out_len(int n, int T) {
-    const int c = n < 7 ? 0 : ((n - 1) / 2 - 1) / 2;
-    return c < T ? c : T;
-}
-
-// cfm_stream_prep_kernel with the newest frame at off + c_b - 1: the mask covers the min(off, need) cached frames and the c_b new ones.  c_b = 0: the
-// newest frame is off - 1, so the mask is the cached frames alone, and at off = 0 no slot at all (slot_frame then returns a negative frame)
-__global__ void cfm_stream_prep_len_kernel(const int* __restrict__ offsets, const int* __restrict__ frame_lens, int* __restrict__ out_lens, int B, int T, int need,
-                                           int ring_T, const float* __restrict__ pe, int max_len, int D, uint8_t* __restrict__ slot_mask,
-                                           float* __restrict__ pos_rows, float* __restrict__ abs_rows) {
-    const int b = blockIdx.y, s = blockIdx.x;
-    const int off = offsets[b];
-    const int c = stream_out_len(frame_lens[b], T);
-    const int cached = off < need ? off : need;
-    if (s == 0 && threadIdx.x == 0) out_lens[b] = c;
-    if (s < ring_T) {
-        const int f = slot_frame(off + c - 1, s, ring_T);
-        const bool valid = f >= off - cached && f >= 0;
-        if (threadIdx.x == 0) slot_mask[(int64_t)b * ring_T + s] = valid ? 1 : 0;
-        const int row = valid ? (f < max_len ? f : max_len - 1) : 0;
-        for (int cc = threadIdx.x * 4; cc < D; cc += blockDim.x * 4)
-            *(f32x4*)(pos_rows + ((int64_t)b * ring_T + s) * D + cc) = *(const f32x4*)(pe + (int64_t)row * D + cc);
-    } else if (abs_rows) {
-        const int row = off < max_len ? off : max_len - 1;
-        for (int cc = threadIdx.x * 4; cc < D; cc += blockDim.x * 4) *(f32x4*)(abs_rows + (int64_t)b * D + cc) = *(const f32x4*)(pe + (int64_t)row * D + cc);
-    }
-}
-
-// cfm_kv_ring_write_kernel for rows t < lens[b] only.  Later rows touch no slot: they are no frames of the stream and may hold anything, non-finite
-// values included, while a masked slot has to stay finite (the attention multiplies its values with a probability of zero)
-__global__ void cfm_kv_ring_write_len_kernel(const void* __restrict__ k, const void* __restrict__ v, int dt, int64_t k_sb, int64_t k_st, int64_t v_sb, int64_t v_st,
-                                             float* __restrict__ ring, const int* __restrict__ offsets, const int* __restrict__ lens, int B, int H, int T, int dk,
-                                             int ring_T) {
-    const int64_t n = (int64_t)B * T * H * 2 * dk;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int e = (int)(i % (2 * dk));
-        int64_t r = i / (2 * dk);
-        const int h = (int)(r % H);
-        r /= H;
-        const int t = (int)(r % T);
-        const int b = (int)(r / T);
-        if (t >= lens[b]) continue;
-        const int slot = (offsets[b] + t) % ring_T;
-        const float val = e < dk ? load_as_f32(k, (int64_t)b * k_sb + (int64_t)t * k_st + h * dk + e, dt)
-                                 : load_as_f32(v, (int64_t)b * v_sb + (int64_t)t * v_st + h * dk + (e - dk), dt);
-        ring[(((int64_t)b * H + h) * ring_T + slot) * (2 * dk) + e] = val;
-    }
-}
-
-// offsets[b] += lens[b]; rows t >= lens[b] of y [B, T, D] (optional) become zero -- a store, not a product: those rows may hold anything
-__global__ void cfm_stream_advance_len_kernel(int* offsets, const int* __restrict__ lens, float* __restrict__ y, int T, int D) {
-    const int b = blockIdx.x;
-    int c = lens[b];
-    c = c < 0 ? 0 : (c < T ? c : T);
-    if (y) {
-        float* const rows = y + ((int64_t)b * T + c) * D;
-        const int n = (T - c) * D;
-        for (int i = threadIdx.x * 4; i < n; i += blockDim.x * 4) *(f32x4*)(rows + i) = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-    if (threadIdx.x == 0) offsets[b] += c;
-}
-
-// cache <- the last K-1 frames of [cache | x[:T_b]], T_b = lens[b] <= T, in place.  New row j is row j + T_b of [cache | x[:T_b]]: old cache row
-// j + T_b while j + T_b < K-1, else x row j + T_b - (K-1) < T_b.  A thread owns one (stream, channel) column and walks j upwards, and for T_b > 0 the
-// cache row it reads, j + T_b, lies above every row written so far (<= j); T_b = 0 would read and write row j itself -- the column is left alone
-__global__ void cfm_conv_cache_update_len_kernel(const void* __restrict__ x, int x_dt, float* __restrict__ cache, const int* __restrict__ lens, int B, int T, int D,
-                                                 int K) {
-    const int C = K - 1;
-    const int64_t n = (int64_t)B * D;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int d = (int)(i % D);
-        const int b = (int)(i / D);
-        int Tb = lens[b];
-        Tb = Tb < T ? Tb : T;
+        const int Tb = lens && lens[b] < T ? lens[b] : T;
         if (Tb <= 0) continue;
         for (int j = 0; j < C; ++j) {
             const int tt = j + Tb - C;                      // position in x of new cache row j
@@ -197,34 +145,39 @@ inline int blocks_for(int64_t n) {
 
 }  // namespace
 
-extern "C" int cfm_stream_prep(const int32_t* offsets, int32_t B, int32_t T, int32_t need, int32_t ring_T, const float* pe, int32_t max_len, int32_t D,
-                               uint8_t* slot_mask, float* pos_rows, float* abs_rows, cfm_stream_t stream) {
+extern "C" int cfm_stream_prep(const int32_t* offsets, const int32_t* frame_lens, int32_t* out_lens, int32_t B, int32_t T, int32_t need, int32_t ring_T,
+                               const float* pe, int32_t max_len, int32_t D, uint8_t* slot_mask, float* pos_rows, float* abs_rows, cfm_stream_t stream) {
     CFM_CHECK_ARG(offsets && pe && slot_mask && pos_rows, "cfm_stream_prep: null pointer");
+    CFM_CHECK_ARG(!frame_lens == !out_lens, "cfm_stream_prep: frame_lens and out_lens come together");
     CFM_CHECK_ARG(B > 0 && B <= 65535 && T > 0 && need >= 0 && ring_T >= need + T && D > 0 && D % 4 == 0 && max_len > 0,
                   "cfm_stream_prep: bad shape B=%d T=%d need=%d ring_T=%d D=%d (ring_T >= need + T)", B, T, need, ring_T, D);
     hipStream_t s = (hipStream_t)stream;
     CfmProfScope prof("stream_prep", s, 0.0, (double)B * ring_T * D * 8);
-    CFM_LAUNCH(cfm_stream_prep_kernel, dim3((unsigned)(ring_T + (abs_rows ? 1 : 0)), (unsigned)B), dim3(64), 0, s, offsets, B, T, need, ring_T, pe, max_len, D,
-               slot_mask, pos_rows, abs_rows);
+    CFM_LAUNCH(cfm_stream_prep_kernel, dim3((unsigned)(ring_T + (abs_rows ? 1 : 0)), (unsigned)B), dim3(64), 0, s, offsets, frame_lens, out_lens, B, T, need, ring_T,
+               pe, max_len, D, slot_mask, pos_rows, abs_rows);
     return cfm_launch_status("cfm_stream_prep");
 }
 
 extern "C" int cfm_kv_ring_write(const void* k, const void* v, int32_t kv_dtype, int64_t k_sb, int64_t k_st, int64_t v_sb, int64_t v_st, float* ring,
-                                 const int32_t* offsets, int32_t B, int32_t H, int32_t T, int32_t dk, int32_t ring_T, cfm_stream_t stream) {
+                                 const int32_t* offsets, const int32_t* lens, int32_t B, int32_t H, int32_t T, int32_t dk, int32_t ring_T, cfm_stream_t stream) {
     CFM_CHECK_ARG(k && v && ring && offsets, "cfm_kv_ring_write: null pointer");
     CFM_CHECK_ARG(B > 0 && H > 0 && T > 0 && dk > 0 && ring_T >= T, "cfm_kv_ring_write: bad shape");
     hipStream_t s = (hipStream_t)stream;
     const int64_t n = (int64_t)B * T * H * 2 * dk;
-    CfmProfScope prof("kv_ring_write", s, 0.0, (double)n * (4 + cfm_elt_size(kv_dtype)));
-    CFM_LAUNCH(cfm_kv_ring_write_kernel, dim3((unsigned)blocks_for(n)), dim3(256), 0, s, k, v, kv_dtype, k_sb, k_st, v_sb, v_st, ring, offsets, B, H, T, dk, ring_T);
+    // the one scope that keeps its length-aware name: tests/test_stream_ragged_gpu.py tells the two ring write sites of a ragged step apart by it
+    CfmProfScope prof(lens ? "kv_ring_write_len" : "kv_ring_write", s, 0.0, (double)n * (4 + cfm_elt_size(kv_dtype)));
+    CFM_LAUNCH(cfm_kv_ring_write_kernel, dim3((unsigned)blocks_for(n)), dim3(256), 0, s, k, v, kv_dtype, k_sb, k_st, v_sb, v_st, ring, offsets, lens, B, H, T, dk,
+               ring_T);
     return cfm_launch_status("cfm_kv_ring_write");
 }
 
-extern "C" int cfm_stream_advance(int32_t* offsets, const uint8_t* active, int32_t B, int32_t T, cfm_stream_t stream) {
+extern "C" int cfm_stream_advance(int32_t* offsets, const uint8_t* active, const int32_t* lens, float* y, int32_t B, int32_t T, int32_t D, cfm_stream_t stream) {
     CFM_CHECK_ARG(offsets && B > 0 && T > 0, "cfm_stream_advance: bad arguments");
+    CFM_CHECK_ARG(!lens || !active, "cfm_stream_advance: active is not combined with lens");
+    CFM_CHECK_ARG(!y || (lens && D > 0 && D % 4 == 0), "cfm_stream_advance: y needs lens and D > 0, a multiple of 4");
     hipStream_t s = (hipStream_t)stream;
     CfmProfScope prof("stream_advance", s, 0.0, (double)B * 8);
-    CFM_LAUNCH(cfm_stream_advance_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, offsets, active, B, T);
+    CFM_LAUNCH(cfm_stream_advance_kernel, dim3((unsigned)B), dim3(64), 0, s, offsets, active, lens, y, T, D);
     return cfm_launch_status("cfm_stream_advance");
 }
 
@@ -239,54 +192,12 @@ extern "C" int cfm_dwconv_causal_bn_silu(const void* x, int32_t x_dtype, const f
     return cfm_launch_status("cfm_dwconv_causal_bn_silu");
 }
 
-extern "C" int cfm_conv_cache_update(const void* x, int32_t x_dtype, float* cache, int32_t B, int32_t T, int32_t D, int32_t ktaps, cfm_stream_t stream) {
+extern "C" int cfm_conv_cache_update(const void* x, int32_t x_dtype, float* cache, const int32_t* lens, int32_t B, int32_t T, int32_t D, int32_t ktaps,
+                                     cfm_stream_t stream) {
     CFM_CHECK_ARG(x && cache, "cfm_conv_cache_update: null pointer");
     CFM_CHECK_ARG(B > 0 && T > 0 && D > 0 && ktaps > 1, "cfm_conv_cache_update: bad shape");
     hipStream_t s = (hipStream_t)stream;
     CfmProfScope prof("conv_cache_update", s, 0.0, (double)B * (ktaps - 1) * D * 8);
-    CFM_LAUNCH(cfm_conv_cache_update_kernel, dim3((unsigned)blocks_for((int64_t)B * D)), dim3(256), 0, s, x, x_dtype, cache, B, T, D, ktaps);
+    CFM_LAUNCH(cfm_conv_cache_update_kernel, dim3((unsigned)blocks_for((int64_t)B * D)), dim3(256), 0, s, x, x_dtype, cache, lens, B, T, D, ktaps);
     return cfm_launch_status("cfm_conv_cache_update");
-}
-
-extern "C" int cfm_stream_prep_len(const int32_t* offsets, const int32_t* frame_lens, int32_t* out_lens, int32_t B, int32_t T, int32_t need, int32_t ring_T,
-                                   const float* pe, int32_t max_len, int32_t D, uint8_t* slot_mask, float* pos_rows, float* abs_rows, cfm_stream_t stream) {
-    CFM_CHECK_ARG(offsets && frame_lens && out_lens && pe && slot_mask && pos_rows, "cfm_stream_prep_len: null pointer");
-    CFM_CHECK_ARG(B > 0 && B <= 65535 && T > 0 && need >= 0 && ring_T >= need + T && D > 0 && D % 4 == 0 && max_len > 0,
-                  "cfm_stream_prep_len: bad shape B=%d T=%d need=%d ring_T=%d D=%d (ring_T >= need + T)", B, T, need, ring_T, D);
-    hipStream_t s = (hipStream_t)stream;
-    CfmProfScope prof("stream_prep_len", s, 0.0, (double)B * ring_T * D * 8);
-    CFM_LAUNCH(cfm_stream_prep_len_kernel, dim3((unsigned)(ring_T + (abs_rows ? 1 : 0)), (unsigned)B), dim3(64), 0, s, offsets, frame_lens, out_lens, B, T, need, ring_T,
-               pe, max_len, D, slot_mask, pos_rows, abs_rows);
-    return cfm_launch_status("cfm_stream_prep_len");
-}
-
-extern "C" int cfm_kv_ring_write_len(const void* k, const void* v, int32_t kv_dtype, int64_t k_sb, int64_t k_st, int64_t v_sb, int64_t v_st, float* ring,
-                                     const int32_t* offsets, const int32_t* lens, int32_t B, int32_t H, int32_t T, int32_t dk, int32_t ring_T, cfm_stream_t stream) {
-    CFM_CHECK_ARG(k && v && ring && offsets && lens, "cfm_kv_ring_write_len: null pointer");
-    CFM_CHECK_ARG(B > 0 && H > 0 && T > 0 && dk > 0 && ring_T >= T, "cfm_kv_ring_write_len: bad shape");
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t n = (int64_t)B * T * H * 2 * dk;
-    CfmProfScope prof("kv_ring_write_len", s, 0.0, (double)n * (4 + cfm_elt_size(kv_dtype)));
-    CFM_LAUNCH(cfm_kv_ring_write_len_kernel, dim3((unsigned)blocks_for(n)), dim3(256), 0, s, k, v, kv_dtype, k_sb, k_st, v_sb, v_st, ring, offsets, lens, B, H, T, dk,
-               ring_T);
-    return cfm_launch_status("cfm_kv_ring_write_len");
-}
-
-extern "C" int cfm_stream_advance_len(int32_t* offsets, const int32_t* lens, float* y, int32_t B, int32_t T, int32_t D, cfm_stream_t stream) {
-    CFM_CHECK_ARG(offsets && lens && B > 0 && T > 0, "cfm_stream_advance_len: bad arguments");
-    CFM_CHECK_ARG(!y || (D > 0 && D % 4 == 0), "cfm_stream_advance_len: y needs D > 0, a multiple of 4");
-    hipStream_t s = (hipStream_t)stream;
-    CfmProfScope prof("stream_advance_len", s, 0.0, (double)B * 8);
-    CFM_LAUNCH(cfm_stream_advance_len_kernel, dim3((unsigned)B), dim3(64), 0, s, offsets, lens, y, T, D);
-    return cfm_launch_status("cfm_stream_advance_len");
-}
-
-extern "C" int cfm_conv_cache_update_len(const void* x, int32_t x_dtype, float* cache, const int32_t* lens, int32_t B, int32_t T, int32_t D, int32_t ktaps,
-                                         cfm_stream_t stream) {
-    CFM_CHECK_ARG(x && cache && lens, "cfm_conv_cache_update_len: null pointer");
-    CFM_CHECK_ARG(B > 0 && T > 0 && D > 0 && ktaps > 1, "cfm_conv_cache_update_len: bad shape");
-    hipStream_t s = (hipStream_t)stream;
-    CfmProfScope prof("conv_cache_update_len", s, 0.0, (double)B * (ktaps - 1) * D * 8);
-    CFM_LAUNCH(cfm_conv_cache_update_len_kernel, dim3((unsigned)blocks_for((int64_t)B * D)), dim3(256), 0, s, x, x_dtype, cache, lens, B, T, D, ktaps);
-    return cfm_launch_status("cfm_conv_cache_update_len");
 }

@@ -405,36 +405,29 @@ int cfm_attn_mask(const uint8_t* valid, const uint8_t* chunk, uint8_t* out, int3
  * Per-stream state of the batched streaming step (csrc/stream.hip) -- beyond the reference, whose forward_chunk serves one stream at a
  * time (encoder.py:78-123) and rebuilds its cache with cat + slice (:117).  offsets int32 [B] on the device: encoder frames each stream has
  * consumed.  need = chunk * left_chunks cached frames, ring_T >= need + T slots.
- *  cfm_stream_prep     slot_mask u8 [B,ring_T] = slot holds a frame of [offset-min(offset,need), offset+T); pos_rows f32 [B,ring_T,D] = pe[that
+ *  cfm_stream_prep     slot_mask u8 [B,ring_T] = slot holds a frame of [offset-min(offset,need), offset+c_b); pos_rows f32 [B,ring_T,D] = pe[that
  *                      frame] (pe f32 [max_len,D], the sinusoid table of attention.py:12-16); abs_rows f32 [B,D] = pe[offset] (optional: the
- *                      absolute encoding's row, attention.py:119-120)
- *  cfm_kv_ring_write   K / V rows of the T new frames (addressed like cfm_attn_desc k / v, head h at h*dk) -> ring slots (offset+t) mod ring_T
- *  cfm_stream_advance  offset[b] += T for streams with active[b] != 0 (active NULL: all)
- *  cfm_stream_prep_len / cfm_kv_ring_write_len / cfm_stream_advance_len / cfm_conv_cache_update_len: the same with per-stream lengths.  Stream b's
- *                      window holds frame_lens[b] valid FEATURE frames (left-aligned, 0 .. window), hence out_lens[b] = c_b = ((n-1)/2-1)/2 encoder
- *                      frames (0 for n < 7; capped at T), which cfm_stream_prep_len writes: the newest frame is offset + c_b - 1, the mask covers the
- *                      min(offset, need) cached frames and the c_b new ones (c_b = 0: the cached frames only; none at offset 0).  The other three take
- *                      lens = out_lens: ring slots are written for rows t < lens[b] only, the conv cache becomes the last ktaps-1 frames of
- *                      [cache | x[:lens[b]]], offset[b] += lens[b] and rows t >= lens[b] of y f32 [B,T,D] (optional) are set to zero.  lens[b] = 0
- *                      changes nothing of stream b.
+ *                      absolute encoding's row, attention.py:119-120).  frame_lens NULL (then out_lens NULL too): whole windows, c_b = T.  Else
+ *                      per-stream lengths: stream b's window holds frame_lens[b] valid FEATURE frames (left-aligned, 0 .. window), hence
+ *                      out_lens[b] = c_b = ((n-1)/2-1)/2 encoder frames (0 for n < 7; capped at T), which it writes: the newest frame is
+ *                      offset + c_b - 1, the mask covers the min(offset, need) cached frames and the c_b new ones (c_b = 0: the cached frames only;
+ *                      none at offset 0).  The other three take lens = out_lens, and lens[b] = 0 changes nothing of stream b.
+ *  cfm_kv_ring_write   K / V rows of the T new frames (addressed like cfm_attn_desc k / v, head h at h*dk) -> ring slots (offset+t) mod ring_T.
+ *                      lens NULL: whole windows; else rows t < lens[b] only.
+ *  cfm_stream_advance  lens NULL: offset[b] += T for streams with active[b] != 0 (active NULL: all).  Else offset[b] += lens[b] (clamped to 0 .. T; not
+ *                      with active) and rows t >= lens[b] of y f32 [B,T,D] (optional, needs lens and D % 4 == 0) are set to zero.
  *  cfm_dwconv_causal_bn_silu  y = SiLU(BN_eval(causal depthwise conv over [cache | x])), cache f32 [B,ktaps-1,D] or NULL (zeros)
- *  cfm_conv_cache_update      cache <- last ktaps-1 frames of [cache | x], in place
+ *  cfm_conv_cache_update      cache <- last ktaps-1 frames of [cache | x], in place.  lens NULL: whole windows; else of [cache | x[:lens[b]]] per stream
  */
-int cfm_stream_prep(const int32_t* offsets, int32_t B, int32_t T, int32_t need, int32_t ring_T, const float* pe, int32_t max_len, int32_t D,
-                    uint8_t* slot_mask, float* pos_rows, float* abs_rows, cfm_stream_t stream);
+int cfm_stream_prep(const int32_t* offsets, const int32_t* frame_lens, int32_t* out_lens, int32_t B, int32_t T, int32_t need, int32_t ring_T,
+                    const float* pe, int32_t max_len, int32_t D, uint8_t* slot_mask, float* pos_rows, float* abs_rows, cfm_stream_t stream);
 int cfm_kv_ring_write(const void* k, const void* v, int32_t kv_dtype, int64_t k_sb, int64_t k_st, int64_t v_sb, int64_t v_st, float* ring,
-                      const int32_t* offsets, int32_t B, int32_t H, int32_t T, int32_t dk, int32_t ring_T, cfm_stream_t stream);
-int cfm_stream_advance(int32_t* offsets, const uint8_t* active, int32_t B, int32_t T, cfm_stream_t stream);
+                      const int32_t* offsets, const int32_t* lens, int32_t B, int32_t H, int32_t T, int32_t dk, int32_t ring_T, cfm_stream_t stream);
+int cfm_stream_advance(int32_t* offsets, const uint8_t* active, const int32_t* lens, float* y, int32_t B, int32_t T, int32_t D, cfm_stream_t stream);
 int cfm_dwconv_causal_bn_silu(const void* x, int32_t x_dtype, const float* cache, const float* w, const float* dw_bias, const float* bn_scale,
                               const float* bn_shift, void* y, int32_t y_dtype, int32_t B, int32_t T, int32_t D, int32_t ktaps, cfm_stream_t stream);
-int cfm_conv_cache_update(const void* x, int32_t x_dtype, float* cache, int32_t B, int32_t T, int32_t D, int32_t ktaps, cfm_stream_t stream);
-int cfm_stream_prep_len(const int32_t* offsets, const int32_t* frame_lens, int32_t* out_lens, int32_t B, int32_t T, int32_t need, int32_t ring_T,
-                        const float* pe, int32_t max_len, int32_t D, uint8_t* slot_mask, float* pos_rows, float* abs_rows, cfm_stream_t stream);
-int cfm_kv_ring_write_len(const void* k, const void* v, int32_t kv_dtype, int64_t k_sb, int64_t k_st, int64_t v_sb, int64_t v_st, float* ring,
-                          const int32_t* offsets, const int32_t* lens, int32_t B, int32_t H, int32_t T, int32_t dk, int32_t ring_T, cfm_stream_t stream);
-int cfm_stream_advance_len(int32_t* offsets, const int32_t* lens, float* y, int32_t B, int32_t T, int32_t D, cfm_stream_t stream);
-int cfm_conv_cache_update_len(const void* x, int32_t x_dtype, float* cache, const int32_t* lens, int32_t B, int32_t T, int32_t D, int32_t ktaps,
-                              cfm_stream_t stream);
+int cfm_conv_cache_update(const void* x, int32_t x_dtype, float* cache, const int32_t* lens, int32_t B, int32_t T, int32_t D, int32_t ktaps,
+                          cfm_stream_t stream);
 
 /* element-wise dtype conversion:  dst = cast(src) */
 int cfm_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, cfm_stream_t stream);
@@ -533,9 +526,9 @@ typedef struct {
     /* The batched streaming step with PER-STREAM window lengths (needs kv_ring): int32 [B], only the first stream_len[b] <= T rows of stream b are frames
      * of its utterance (a short final chunk, or 0 for an idle stream).  What utt_len does for whole utterances -- the same select behind the GLU, on every
      * route, so the symmetric depthwise convolution of a valid row sees zeros past the stream's end, as the reference's batch-1 forward_chunk on the
-     * shorter window does -- plus the streaming state: only rows t < stream_len[b] are written to the K/V ring (cfm_kv_ring_write_len, or
-     * cfm_ffn_split_desc.ring_len on CFM_ROUTE_FFSPLIT) and enter conv_cache (cfm_conv_cache_update_len); stream_len[b] = 0 leaves both untouched.
-     * attn_mask is the slot mask of cfm_stream_prep_len.  Rows at and past stream_len[b] of x_out hold no defined result (non-finite values included)
+     * shorter window does -- plus the streaming state: only rows t < stream_len[b] are written to the K/V ring (cfm_kv_ring_write with lens, or
+     * cfm_ffn_split_desc.ring_len on CFM_ROUTE_FFSPLIT) and enter conv_cache (cfm_conv_cache_update with lens); stream_len[b] = 0 leaves both untouched.
+     * attn_mask is the slot mask of cfm_stream_prep with frame_lens.  Rows at and past stream_len[b] of x_out hold no defined result (non-finite values included)
      * and reach no valid row.  NULL = every stream has T rows, as before.  Not with utt_len, attn_cache or pad_valid. */
     const int32_t* stream_len;
 } cfm_layer_io;

@@ -644,7 +644,7 @@ def test_kv_ring_write(cfm, H, dk):
     qv, ring = G.inp(qkv, ld=ld, name="qkv"), G.io(ring0, name="ring")
     ov = G.inp(torch.tensor(offsets, dtype=torch.int32), name="offsets")
     cfm.check(cfm.lib().cfm_kv_ring_write(qv[..., D:].data_ptr(), qv[..., 2 * D:].data_ptr(), cfm.BF16, T * ld, ld, T * ld, ld, ring.data_ptr(), ov.data_ptr(),
-                                          B, H, T, dk, ring_T, cfm.stream()), "cfm_kv_ring_write")
+                                          None, B, H, T, dk, ring_T, cfm.stream()), "cfm_kv_ring_write")
     want = ring0.clone()
     for b, off in enumerate(offsets):
         for t in range(T):

@@ -681,7 +681,7 @@ def test_ffn_split_modes(cfm, M, wdt):
         q3 = qkv2.view(Bs, Tq, 3 * D)
         kq, vq = q3[:, :, D:2 * D], q3[:, :, 2 * D:]
         cfm.check(cfm.lib().cfm_kv_ring_write(kq.data_ptr(), vq.data_ptr(), code, Tq * 3 * D, 3 * D, Tq * 3 * D, 3 * D, kv_ref.data_ptr(), offs.data_ptr(),
-                                              Bs, H, Tq, dk, ring_T, cfm.stream()), "cfm_kv_ring_write")
+                                              None, Bs, H, Tq, dk, ring_T, cfm.stream()), "cfm_kv_ring_write")
         assert torch.equal(qkv2, qkv) and torch.equal(kv, kv_ref)
     # reproducible
     again = torch.empty_like(slabs)
