@@ -208,7 +208,8 @@ class FbankDesc(ctypes.Structure):
     _fields_ = ([(n, c_p) for n in ("samples", "lengths", "feats_length", "carry_in", "carry_out", "fresh_in", "pos_in", "fresh_out", "pos_out", "twiddle", "window",
                                     "mel_w", "mel_start", "mel_len", "mel_off", "out")] + [("ld", c_i64)] +
                 [(n, c_i32) for n in ("B", "n_cols", "rows", "F", "win", "shift", "padded", "mel_nnz", "samples_i16", "carry_n", "hop")] +
-                [("dither", c_f), ("seed", ctypes.c_uint32)])
+                [("dither", c_f), ("seed", ctypes.c_uint32)] +
+                [(n, c_p) for n in ("n_new", "final", "carry_len_in", "carry_len_out", "frame_lens")] + [("carry_cap", c_i32)])
 
 
 class FfnSplitDesc(ctypes.Structure):

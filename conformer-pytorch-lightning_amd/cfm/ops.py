@@ -6,7 +6,7 @@ import torch
 
 import cfm as _c
 
-__all__ = ["lstm_forward", "lstm_backward", "fbank", "fbank_stream", "stream_prep", "stream_advance", "dwconv_causal_bn_silu", "conv_cache_update", "dropout_rows", "dropout_mask", "set_deterministic", "gemm_tn", "gemm_tn_group", "layernorm_bwd", "glu_bwd", "dwconv_bn_train", "dwconv_bn_train_bwd", "dwconv_bn_train_groups", "dwconv_bn_train_bwd_groups", "col2im_relu_bwd", "conv1_wgrad", "attention_bwd", "attention_group", "attention_bwd_group",
+__all__ = ["lstm_forward", "lstm_backward", "fbank", "fbank_stream", "fbank_stream_ragged", "stream_prep", "stream_advance", "dwconv_causal_bn_silu", "conv_cache_update", "dropout_rows", "dropout_mask", "set_deterministic", "gemm_tn", "gemm_tn_group", "layernorm_bwd", "glu_bwd", "dwconv_bn_train", "dwconv_bn_train_bwd", "dwconv_bn_train_groups", "dwconv_bn_train_bwd_groups", "col2im_relu_bwd", "conv1_wgrad", "attention_bwd", "attention_group", "attention_bwd_group",
            "ctc_nll_train_groups", "ctc_grad", "rnnt_nll", "rnnt_grad", "joint_act_bwd", "rnnt_nll_packed", "joint_act_packed", "joint_act_packed_bwd", "ffn_split", "adam_step", "adam_clip_step", "sumsq", "scratch_stats",
            "gemm", "ffn_fused", "ffn_fused_supported", "rowchain", "rowchain_supported", "rowchain_pair_supported", "layernorm", "attention", "kv_cache_pack", "dwconv_bn_silu", "conv1_relu", "conv1_relu_mma_supported", "conv12_relu", "conv12_supported", "ctc_nll", "joint_act", "valid_mask", "chunk_mask",
            "attn_mask_combine", "cast", "add_rows", "scratch", "prof_enable", "prof_reset", "prof_table", "as_u8_mask"]
@@ -1342,6 +1342,30 @@ def fbank_stream(samples, state_in, state_out, tables, out, win, shift, padded, 
             raise ValueError("cfm.fbank_stream: state is (carry f32 [B, n], fresh int32 [B], pos int32 [B]), contiguous")
     d.carry_in, d.fresh_in, d.pos_in, d.carry_out, d.fresh_out, d.pos_out = (_c.ptr(t) for t in (ci, fi, pi, co, fo, po))
     d.carry_n, d.hop = ci.shape[1], hop
+    _c.check(_c.lib().cfm_fbank_stream(ctypes.byref(d), _c.stream()), "cfm_fbank_stream")
+
+
+def fbank_stream_ragged(samples, n_new, final, state_in, state_out, frame_lens, tables, out, win, shift, padded, hop, dither=0.0, seed=0):
+    """Streaming with audio packets of any size (cfm_fbank_stream with n_new set): samples (B, n >= 0), n_new / final int32 [B] on the device (new samples
+    per stream, utterance finished); state_* = (carry f32 [B, cap], fresh int32 [B], pos int32 [B], carry_len int32 [B]), in is read, out is written;
+    frame_lens int32 [B] receives the rows each stream's window holds (the rest of `out` is written as zeros)."""
+    d = _fbank_desc(samples, tables, out, win, shift, padded, dither, seed)
+    if len(state_in) != 4 or len(state_out) != 4:
+        raise ValueError("cfm.fbank_stream_ragged: state is (carry, fresh, pos, carry_len)")
+    (ci, fi, pi, li), (co, fo, po, lo) = state_in, state_out
+    _c.require_hip(ci, fi, pi, li, co, fo, po, lo, n_new, final, frame_lens)
+    for name, t, dt in (("carry", ci, torch.float32), ("carry", co, torch.float32), ("fresh", fi, torch.int32), ("fresh", fo, torch.int32), ("pos", pi, torch.int32),
+                        ("pos", po, torch.int32), ("carry_len", li, torch.int32), ("carry_len", lo, torch.int32), ("n_new", n_new, torch.int32),
+                        ("final", final, torch.int32), ("frame_lens", frame_lens, torch.int32)):
+        if t.dtype != dt or not t.is_contiguous() or t.dim() != (2 if name == "carry" else 1) or t.shape[0] != d.B:
+            raise ValueError("cfm.fbank_stream_ragged: %s must be contiguous %s [%d%s], got %s %s" % (name, dt, d.B, ", cap" if name == "carry" else "", t.dtype, tuple(t.shape)))
+    n_first = (d.rows - 1) * shift + win
+    if ci.shape != co.shape or ci.shape[1] < n_first - 1:
+        raise ValueError("cfm.fbank_stream_ragged: the carry buffers are two f32 [%d, >= %d], got %s and %s" % (d.B, n_first - 1, tuple(ci.shape), tuple(co.shape)))
+    if len({t.data_ptr() for t in (ci, co)}) != 2 or len({t.data_ptr() for t in (fi, fo, pi, po, li, lo, n_new, final, frame_lens)}) != 9:
+        raise ValueError("cfm.fbank_stream_ragged: state in and out (and the length buffers) must not alias")
+    d.carry_in, d.fresh_in, d.pos_in, d.carry_len_in, d.carry_out, d.fresh_out, d.pos_out, d.carry_len_out = (_c.ptr(t) for t in (ci, fi, pi, li, co, fo, po, lo))
+    d.n_new, d.final, d.frame_lens, d.carry_cap, d.hop = _c.ptr(n_new), _c.ptr(final), _c.ptr(frame_lens), ci.shape[1], hop
     _c.check(_c.lib().cfm_fbank_stream(ctypes.byref(d), _c.stream()), "cfm_fbank_stream")
 
 

@@ -53,6 +53,9 @@ struct Src {                     // the sample sequence of one item: [0, cn) fro
     }
 };
 
+// kRagged: the streaming mode for audio packets of any size (cfm_fbank_desc.n_new set), its own instantiation: the offline and the whole-block
+// streaming mode are the kRagged = false one, whose code does not know the third mode exists.
+template <bool kRagged>
 __global__ __launch_bounds__(kWaves * 64) void cfm_fbank_kernel(cfm_fbank_desc d, int streaming, int frame_blocks) {
     __shared__ d2 tw[kMaxPad];
     __shared__ double wnd[kMaxPad];
@@ -67,7 +70,16 @@ __global__ __launch_bounds__(kWaves * 64) void cfm_fbank_kernel(cfm_fbank_desc d
     s.ncols = d.n_cols;
     s.blk = (const char*)d.samples + (int64_t)b * d.ld * (d.samples_i16 ? 2 : 4);
     int pos = 0, m;
-    if (streaming) {
+    if constexpr (kRagged) {                               // a carry of carry_len_in[b] <= carry_cap samples, n_new[b] new ones, 0 .. rows frames
+        const bool fresh = d.fresh_in[b] != 0;
+        s.cn = fresh ? 0 : min(max(d.carry_len_in[b], 0), d.carry_cap);
+        s.carry = d.carry_in + (int64_t)b * d.carry_cap;
+        s.ncols = min(max(d.n_new[b], 0), d.n_cols);       // a read at or past the stream's own count yields 0
+        s.len = s.cn + s.ncols;
+        pos = fresh ? 0 : d.pos_in[b];
+        m = d.rows;                                        // a whole window, the short last one of a finished utterance, or nothing (buffering)
+        if (s.len < (d.rows - 1) * d.shift + win) m = d.final[b] == 0 || s.len < win ? 0 : 1 + (s.len - win) / d.shift;
+    } else if (streaming) {
         const bool fresh = d.fresh_in[b] != 0;
         s.cn = fresh ? 0 : d.carry_n;
         s.carry = d.carry_in + (int64_t)b * d.carry_n;
@@ -82,7 +94,21 @@ __global__ __launch_bounds__(kWaves * 64) void cfm_fbank_kernel(cfm_fbank_desc d
     }
 
     if ((int)blockIdx.x == frame_blocks) {                 // the item's bookkeeping block
-        if (streaming) {
+        if constexpr (kRagged) {
+            // the sequence loses a hop at its head after a whole window, 4 c frames after a short one of c encoder frames (cfm_stream_prep's count)
+            const int adv = m == d.rows ? d.hop : m < 7 ? 0 : 4 * (((m - 1) / 2 - 1) / 2), used = adv * d.shift;
+            const int keep = min(s.len - used, d.carry_cap);                          // the host mirror refuses a packet that would overfill the carry
+            for (int v = tid; v < keep; v += kWaves * 64) {                           // used + v < s.len: in the carry or the stream's own new samples; B * carry_cap < 2^31 (checked at the launch)
+                const int i = used + v - s.cn;
+                d.carry_out[b * d.carry_cap + v] = i < 0 ? s.carry[used + v] : s.i16 ? (float)((const int16_t*)s.blk)[i] : ((const float*)s.blk)[i];
+            }
+            if (tid == 0) {
+                d.carry_len_out[b] = keep;
+                d.fresh_out[b] = 0;
+                d.pos_out[b] = pos + adv;
+                d.frame_lens[b] = m;
+            }
+        } else if (streaming) {
             for (int v = tid; v < d.carry_n; v += kWaves * 64) d.carry_out[(int64_t)b * d.carry_n + v] = s.at(s.len - d.carry_n + v);
             if (tid == 0) {
                 d.fresh_out[b] = 0;
@@ -201,16 +227,24 @@ __global__ __launch_bounds__(kWaves * 64) void cfm_fbank_kernel(cfm_fbank_desc d
 }
 
 int fbank_launch(const cfm_fbank_desc* d, int streaming, cfm_stream_t stream, const char* who) {
-    CFM_CHECK_ARG(d && d->samples && d->twiddle && d->window && d->mel_w && d->mel_start && d->mel_len && d->mel_off && d->out, "%s: null pointer", who);
+    CFM_CHECK_ARG(d && (d->samples || (streaming && d->n_new && d->n_cols == 0)) && d->twiddle && d->window && d->mel_w && d->mel_start && d->mel_len && d->mel_off && d->out, "%s: null pointer", who);
     CFM_CHECK_ARG(d->B > 0 && d->B <= 65535 && d->rows > 0 && d->F > 0, "%s: B %d rows %d F %d", who, d->B, d->rows, d->F);
     CFM_CHECK_ARG(d->padded >= 8 && d->padded <= kMaxPad && (d->padded & (d->padded - 1)) == 0 && d->win >= 2 && d->win <= d->padded && d->shift >= 1,
                   "%s: window %d padded to %d, shift %d: the padded window must be a power of two in [8, %d]", who, d->win, d->padded, d->shift, kMaxPad);
     CFM_CHECK_ARG(d->mel_nnz > 0 && d->mel_nnz <= kMaxNnz, "%s: %d packed mel weights (at most %d)", who, d->mel_nnz, kMaxNnz);
     CFM_CHECK_ARG((int64_t)(d->rows - 1) * d->shift + d->win < (1ll << 30), "%s: rows %d: sample index out of range", who, d->rows);
+    const int64_t n_first = (int64_t)(d->rows - 1) * d->shift + d->win;
     if (streaming) {
-        const int64_t n_first = (int64_t)(d->rows - 1) * d->shift + d->win;
         CFM_CHECK_ARG(d->carry_in && d->carry_out && d->fresh_in && d->fresh_out && d->pos_in && d->pos_out, "%s: null state pointer", who);
         CFM_CHECK_ARG(d->carry_in != d->carry_out && d->fresh_in != d->fresh_out && d->pos_in != d->pos_out, "%s: state in and out alias", who);
+    }
+    if (streaming && d->n_new) {                           // audio packets of any size
+        CFM_CHECK_ARG(d->final && d->carry_len_in && d->carry_len_out && d->frame_lens && d->carry_len_in != d->carry_len_out, "%s: ragged packets: null or aliased length state", who);
+        CFM_CHECK_ARG(d->hop > 0 && (int64_t)d->hop * d->shift < n_first && d->carry_cap >= n_first - 1 && d->carry_cap < (1 << 30),
+                      "%s: ragged packets: hop %d, a carry of %d samples for a %lld-sample window", who, d->hop, d->carry_cap, (long long)n_first);
+        CFM_CHECK_ARG(d->n_cols >= 0 && d->n_cols < (1 << 30) && d->ld >= d->n_cols, "%s: %d columns (ld %lld)", who, d->n_cols, (long long)d->ld);
+        CFM_CHECK_ARG((int64_t)d->B * d->carry_cap < (1ll << 31), "%s: ragged packets: %d streams x a carry of %d samples: the carry is indexed in 32 bits", who, d->B, d->carry_cap);
+    } else if (streaming) {
         CFM_CHECK_ARG(d->carry_n >= 0 && d->carry_n < n_first && d->hop > 0, "%s: carry %d of a %lld-sample window, hop %d", who, d->carry_n, (long long)n_first, d->hop);
         CFM_CHECK_ARG(d->n_cols >= n_first - d->carry_n && d->ld >= d->n_cols, "%s: %d columns (ld %lld), a stream reads %lld new samples (%lld after a reset)", who, d->n_cols,
                       (long long)d->ld, (long long)(n_first - d->carry_n), (long long)n_first);
@@ -222,7 +256,10 @@ int fbank_launch(const cfm_fbank_desc* d, int streaming, cfm_stream_t stream, co
     const double frames = (double)d->B * d->rows;
     CfmProfScope prof(streaming ? "fbank_stream" : "fbank", s, frames * (5.0 * d->padded * 8 + 2.0 * d->mel_nnz),
                       (double)d->B * ((double)d->rows * d->shift * (d->samples_i16 ? 2 : 4) + (double)d->rows * d->F * 4));
-    CFM_LAUNCH(cfm_fbank_kernel, dim3((unsigned)frame_blocks + 1, (unsigned)d->B), dim3(kWaves * 64), 0, s, *d, streaming, frame_blocks);
+    if (streaming && d->n_new)
+        CFM_LAUNCH(cfm_fbank_kernel<true>, dim3((unsigned)frame_blocks + 1, (unsigned)d->B), dim3(kWaves * 64), 0, s, *d, streaming, frame_blocks);
+    else
+        CFM_LAUNCH(cfm_fbank_kernel<false>, dim3((unsigned)frame_blocks + 1, (unsigned)d->B), dim3(kWaves * 64), 0, s, *d, streaming, frame_blocks);
     return cfm_launch_status(who);
 }
 

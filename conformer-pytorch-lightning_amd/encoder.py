@@ -568,15 +568,19 @@ class StreamingBatch:
             raise ValueError("StreamingBatch: %d features per frame, the stream was started with %d" % (num_features, self.x.shape[2]))
         return self.x
 
-    def step_resident(self, frame_lens=None):
-        """step() on what input_buffer() holds."""
+    def step_resident(self, frame_lens=None, host_lens=None):
+        """step() on what input_buffer() holds.  host_lens: what the host knows of a DEVICE frame_lens (B window lengths, a producer's host mirror):
+        the offset bound then advances by each stream's own c_b instead of `chunk`, so that idle steps do not bring the table growth forward."""
         self.input_buffer()
         self._check_lens(frame_lens)
+        self._check_lens(host_lens)
         self._set_lens(frame_lens)
         self.steps += 1
-        if max(self._host_off) + self.chunk > self.pe.size(0):
-            self._grow_table(max(self._host_off) + self.chunk)
-        self._host_off = [o + self.chunk for o in self._host_off]
+        adv = [self.chunk] * self.B if host_lens is None else [((int(n) - 1) // 2 - 1) // 2 if n >= 7 else 0 for n in host_lens]
+        need = max(o + a for o, a in zip(self._host_off, adv))
+        if need > self.pe.size(0):
+            self._grow_table(need)
+        self._host_off = [o + a for o, a in zip(self._host_off, adv)]
         with torch.no_grad():
             if not self.use_graph:
                 return self._step_impl()

@@ -57,13 +57,102 @@ class KaldiFbank:
     __call__ = forward
 
 
+class PacketSchedule:
+    """Host mirror of the streams' audio bookkeeping when packets may have any size (StreamingFbank.step with sample_lens; csrc/fbank.hip does the
+    same integer arithmetic on the device, so nothing is read back).  Per stream: `carry` samples waiting, `pos` the absolute feature frame that is
+    row 0 of its next window, `final` whether its last packet said the utterance is over.  The windows it emits are the reference's
+    greedy_search_streaming_eval loop over the stream's whole utterance (model.py:133-147), however the audio was cut:
+
+      L = carry + new samples;  frames(L) = 1 + (L - win) // shift, 0 below win
+      L >= n_first            a whole window of `window` frames; n_next samples and 4 * chunk frames go
+      L <  n_first, final     the short last window of m = frames(L) frames; c = ((m - 1) // 2 - 1) // 2 encoder frames (0 below 7 frames:
+                              no window at all), 4 * c frames go -- at most 6 are left, less than a window's context: the reference's loop bound
+      L <  n_first otherwise  the stream buffers
+
+    A stream accepts n_first + n_next - 1 - carry samples per call, so that its carry stays below n_first."""
+
+    def __init__(self, streams, decoding_chunk_size, win, shift):
+        self.B, self.chunk, self.win, self.shift = int(streams), int(decoding_chunk_size), int(win), int(shift)
+        self.window, self.hop = (self.chunk - 1) * 4 + 7, 4 * self.chunk
+        self.n_first = (self.window - 1) * self.shift + self.win
+        self.n_next = self.hop * self.shift
+        self.carry, self.pos, self.final = [0] * self.B, [0] * self.B, [False] * self.B
+
+    def frames(self, n):
+        return 1 + (n - self.win) // self.shift if n >= self.win else 0
+
+    def reset(self, streams=None):
+        for b in (range(self.B) if streams is None else streams):
+            self.carry[b], self.pos[b], self.final[b] = 0, 0, False
+
+    def accepts(self):
+        """Samples each stream can take in the next call."""
+        return [self.n_first + self.n_next - 1 - c for c in self.carry]
+
+    def pending(self):
+        """Streams whose carry still holds a window to run: call again with no new samples (and the same `final`) until this is empty."""
+        return [b for b in range(self.B) if self.carry[b] >= self.n_first or (self.final[b] and self.frames(self.carry[b]) >= 7)]
+
+    def check(self, sample_lens, final, columns=None):
+        """(sample_lens, final) as lists of B ints / bools, or ValueError: host values only, and no stream may be overfilled."""
+        vals = []
+        for name, v, default in (("sample_lens", sample_lens, columns), ("final", final, False)):
+            if v is None:
+                v = [default] * self.B
+            if isinstance(v, torch.Tensor):
+                if v.device.type != "cpu":
+                    raise ValueError("StreamingFbank: %s are host values (a list or a CPU tensor), the host mirrors the streams' bookkeeping; got a tensor on %s" % (name, v.device))
+                if v.dim() != 1 or v.dtype.is_floating_point or v.dtype.is_complex:
+                    raise ValueError("StreamingFbank: %s must hold %d integers, got %s %s" % (name, self.B, v.dtype, tuple(v.shape)))
+                v = v.tolist()
+            v = list(v)
+            if len(v) != self.B:
+                raise ValueError("StreamingFbank: %d %s for %d streams" % (len(v), name, self.B))
+            vals.append(v)
+        lens, final = vals
+        for b, n in enumerate(lens):
+            if n is None or int(n) != n or n < 0 or (columns is not None and n > columns):
+                raise ValueError("StreamingFbank: sample_lens[%d] = %r: a count of new samples, 0 .. %s" % (b, n, "the block's %d columns" % columns if columns is not None else "accepts()"))
+            room = self.n_first + self.n_next - 1 - self.carry[b]
+            if n > room:
+                raise ValueError("StreamingFbank: stream %d is handed %d samples and accepts %d (it holds %d; a call runs one window, %d new samples, per stream)"
+                                 % (b, n, room, self.carry[b], self.n_next))
+        return [int(n) for n in lens], [bool(f) for f in final]
+
+    def advance(self, sample_lens, final):
+        """One call: -> per stream (first frame, frames) of the window it runs, frames = 0 where it runs none.  The arguments went through check()."""
+        windows = []
+        for b in range(self.B):
+            L = self.carry[b] + sample_lens[b]
+            self.final[b] = final[b]
+            if L >= self.n_first:
+                m, used, adv = self.window, self.n_next, self.hop
+            elif final[b]:
+                m = self.frames(L)
+                adv = 4 * (((m - 1) // 2 - 1) // 2) if m >= 7 else 0
+                used = adv * self.shift
+            else:
+                m = used = adv = 0
+            windows.append((self.pos[b], m))
+            self.carry[b], self.pos[b] = L - used, self.pos[b] + adv
+        return windows
+
+
 class StreamingFbank:
     """B streams, `window` = (chunk - 1) * 4 + 7 feature rows per step, of which the first window - 4 * chunk repeat the previous step's last.
     A step consumes n_next = 4 * chunk * shift new samples per stream; the last carry_n = (window - 4 * chunk - 1) * shift + win samples of
     what a stream has read are kept on the device, so a frame that starts in them and ends in the new block is read through one index map.
     A stream that was reset has no carry and reads n_first = (window - 1) * shift + win samples.
 
-    step(samples (B, >= n_first if any stream is fresh else >= n_next), out (B, window, F) f32) -- blocks left-aligned; reset(streams)."""
+    step(samples (B, >= n_first if any stream is fresh else >= n_next), out (B, window, F) f32) -- blocks left-aligned; reset(streams).
+
+    step(samples (B, n), out, sample_lens, final=None): audio packets of ANY size -- stream b brings sample_lens[b] >= 0 new samples, left-aligned (what
+    lies behind them in its row is never read), and final[b] says its utterance ends with them.  Host values (lists or CPU tensors of B entries).  The
+    stream's window then holds frame_lens[b] frames (device int32 [B], written by the kernel; rows past them are zero): a whole window once n_first
+    samples are there, the utterance's short last window when it is final, else none -- PacketSchedule, the host mirror, has the rules.  It gives
+    accepts() (samples each stream can take now; more is a ValueError) and pending() (streams with a window still to run: call again with
+    sample_lens 0 and the same final) without reading the device.  The first such call widens the carry to n_first samples per stream, with a length
+    each; from then on a call without sample_lens brings samples.shape[1] samples for every stream.  Until then nothing changes."""
 
     def __init__(self, streams, decoding_chunk_size, device, num_mel_bins=80, frame_length=25, frame_shift=10, dither=0.0, sample_frequency=16000, seed=0):
         self.fbank = KaldiFbank(num_mel_bins, frame_length, frame_shift, dither, sample_frequency, seed)
@@ -81,20 +170,75 @@ class StreamingFbank:
                     torch.zeros((self.B,), dtype=torch.int32, device=self.device))
         self._state, self._next = state(), state()          # read by the next step / written by it: swapped after every step
         self._fresh = [True] * self.B                        # host mirror of the device flag
+        self._pos = [0] * self.B                             # ... and of pos, for the switch to packets of any size
+        self.schedule = None                                 # PacketSchedule once a step was given sample_lens; the state is then (carry [B, n_first], fresh, pos, carry_len)
+        self.frame_lens = None                               # int32 [B] on the device: the frames of each stream's last window
 
     def reset(self, streams=None):
         """New utterances on the given streams (all by default): their next block starts at sample 0 of frame 0."""
         fresh = self._state[1]
         if streams is None:
             fresh.fill_(1)
-            self._fresh = [True] * self.B
+            streams = range(self.B)
         else:
             streams = list(streams)
             fresh[torch.as_tensor(streams, dtype=torch.long, device=self.device)] = 1
-            for b in streams:
-                self._fresh[b] = True
+        for b in streams:
+            self._fresh[b], self._pos[b] = True, 0
+        if self.schedule is not None:
+            self.schedule.reset(streams)
 
-    def step(self, samples, out):
+    def accepts(self):
+        """Samples each stream can take in the next step(..., sample_lens)."""
+        return self._schedule().accepts()
+
+    def pending(self):
+        """Streams whose carry still holds a window to run (PacketSchedule.pending)."""
+        return [] if self.schedule is None else self.schedule.pending()
+
+    def _schedule(self):
+        """The host mirror; before the first step with sample_lens, what it will start from: whole blocks leave carry_n samples behind."""
+        if self.schedule is not None:
+            return self.schedule
+        sch = PacketSchedule(self.B, self.chunk, self.fbank.win, self.fbank.shift)
+        sch.carry = [0 if f else self.carry_n for f in self._fresh]
+        sch.pos = list(self._pos)
+        return sch
+
+    def _widen(self):
+        """The first step with sample_lens: the carry of carry_n samples becomes the head of one of n_first, with a length per stream."""
+        self.schedule = self._schedule()
+        def wide(state):
+            carry, fresh, pos = state
+            w = torch.zeros((self.B, self.n_first), dtype=torch.float32, device=self.device)
+            w[:, :self.carry_n] = carry
+            return (w, fresh, pos, torch.full((self.B,), self.carry_n, dtype=torch.int32, device=self.device))
+        self._state, self._next = wide(self._state), wide(self._next)
+        self.frame_lens = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
+        self._packet = torch.zeros((2, self.B), dtype=torch.int32, device=self.device)      # this step's (sample_lens, final)
+
+    def _step_packets(self, samples, out, sample_lens, final):
+        cfm.require_hip(samples, out)
+        if samples.dim() != 2 or samples.shape[0] != self.B:
+            raise ValueError("StreamingFbank.step wants (%d, n) samples, got %s" % (self.B, tuple(samples.shape)))
+        if tuple(out.shape) != (self.B, self.window, self.fbank.num_mel_bins):
+            raise ValueError("StreamingFbank.step writes (%d, %d, %d) feature windows, got a buffer of %s" % (self.B, self.window, self.fbank.num_mel_bins, tuple(out.shape)))
+        lens, final = self._schedule().check(sample_lens, final, samples.shape[1])            # raises before anything changes
+        if self.schedule is None:
+            self._widen()
+        self.windows = self.schedule.advance(lens, final)                                    # per stream (first frame, frames) of this step's window
+        self._packet.copy_(torch.tensor([lens, [int(f) for f in final]], dtype=torch.int32))
+        fb = self.fbank
+        cfm.fbank_stream_ragged(samples, self._packet[0], self._packet[1], self._state, self._next, self.frame_lens, fb.tables(samples.device), out,
+                                fb.win, fb.shift, fb.padded, self.hop, fb.dither, fb.seed)
+        self._state, self._next = self._next, self._state
+        self._fresh = [False] * self.B
+        self._pos = list(self.schedule.pos)
+        return out
+
+    def step(self, samples, out, sample_lens=None, final=None):
+        if sample_lens is not None or final is not None or self.schedule is not None:
+            return self._step_packets(samples, out, sample_lens, final)
         cfm.require_hip(samples, out)
         need = self.n_first if any(self._fresh) else self.n_next
         if samples.dim() != 2 or samples.shape[0] != self.B or samples.shape[1] < need:
@@ -106,5 +250,6 @@ class StreamingFbank:
         fb = self.fbank
         cfm.fbank_stream(samples, self._state, self._next, fb.tables(samples.device), out, fb.win, fb.shift, fb.padded, self.hop, fb.dither, fb.seed)
         self._state, self._next = self._next, self._state
+        self._pos = [(0 if f else p) + self.hop for f, p in zip(self._fresh, self._pos)]
         self._fresh = [False] * self.B
         return out

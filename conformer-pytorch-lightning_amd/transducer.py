@@ -85,8 +85,9 @@ class StreamingRecognizer:
     offset live in the StreamingBatch, its `pred_input_step` / predictor cache in the ChunkGreedySearch (carry=True).  carry=False is
     `greedy_search_streaming_eval`, which restarts the predictor from blank / zeros on every chunk (a quirk of the reference, kept).
 
-    step_audio(samples, lens=None) is step() from the waveform: fbank.StreamingFbank writes the feature windows straight into the encoder step's
-    input buffer (fbank_args: its num_mel_bins, dither, seed, ...; the defaults are the reference's settings without dither).
+    step_audio(samples, lens=None, sample_lens=None, final=None) is step() from the waveform: fbank.StreamingFbank writes the feature windows straight
+    into the encoder step's input buffer (fbank_args: its num_mel_bins, dither, seed, ...; the defaults are the reference's settings without dither);
+    with sample_lens / final the audio comes in packets of any size and an utterance ends where it ends.
 
     step(frames (B, (chunk - 1) * 4 + 7, F), lens=None, frame_lens=None) -> list of B lists: the tokens the step added.
 
@@ -119,18 +120,42 @@ class StreamingRecognizer:
         self.encoder_out = self.encoder_stream.step(frames, frame_lens)                 # (B, chunk, D), overwritten by the next step
         return self.decoder.decode(self.encoder_out, self.encoder_stream.out_lens if frame_lens is not None else lens)
 
-    def step_audio(self, samples, lens=None):
+    def step_audio(self, samples, lens=None, sample_lens=None, final=None):
         """step() from the waveform (the reference's deploy.py preprocess_stream + greedy_search_streaming_app): samples (B, n) int16 | float32 on
-        the int16 scale, left-aligned -- fbank.StreamingFbank.n_next new samples per stream, n_first for a stream that was reset (and then for
-        the call: the others read their first n_next).  One fbank launch writes the feature windows into the encoder step's input buffer.
-        Whole blocks only: a ragged audio tail would need fbank.StreamingFbank to emit fewer rows per stream, which it does not do; a caller with
-        the features at hand passes the short final window to step(frames, frame_lens=...)."""
+        the int16 scale, left-aligned.  One fbank launch writes the feature windows into the encoder step's input buffer.
+
+        Whole blocks (no sample_lens, no final): fbank.StreamingFbank.n_next new samples per stream, n_first for a stream that was reset (and then
+        for the call: the others read their first n_next); lens[b] as in step().
+
+        Packets of any size: sample_lens[b] >= 0 new samples of stream b (host values: a list or a CPU tensor), final[b] true when its utterance ends
+        with them.  A stream runs a whole window once it holds n_first samples, the utterance's short last window when it is final, and idles (no
+        state of it changes) otherwise: the windows are those of the reference's greedy_search_streaming_eval loop over the whole utterance
+        (model.py:133-147), so features, encoder rows and tokens do not depend on how the audio was cut.  The window lengths go from the fbank kernel
+        to the encoder step and the decoder on the device.  A call takes at most audio.accepts()[b] samples of stream b (n_first + n_next - 1 less what it
+        holds; more raises ValueError); after the first such call, a call without sample_lens brings samples.shape[1] samples for every stream, and
+        lens raises (the window lengths fix what the decoder reads).  The serving loop:
+
+            new = rec.step_audio(block, sample_lens=n, final=last)    # packets as they arrive; last[b] with the last packet of stream b
+            while rec.pending():                                     # windows still held back by the one-window-per-call rule
+                new = rec.step_audio(block[:, :0], sample_lens=[0] * B, final=last)
+            rec.reset(ended)                                         # streams whose utterance is over and no longer pending"""
+        ragged = sample_lens is not None or final is not None
+        if lens is not None and (ragged or (self.audio is not None and self.audio.schedule is not None)):
+            raise ValueError("StreamingRecognizer.step_audio: give lens (encoder frames the decoder reads, whole blocks only) or sample_lens / final "
+                             "(packets of any size: the window lengths fix what the decoder reads), not both")
         if self.audio is None:
             import fbank
             self.audio = fbank.StreamingFbank(self.B, self.chunk, self.encoder_stream.dev, **self.fbank_args)
-        self.audio.step(samples, self.encoder_stream.input_buffer(self.audio.fbank.num_mel_bins))
-        self.encoder_out = self.encoder_stream.step_resident()
-        return self.decoder.decode(self.encoder_out, lens)
+        self.audio.step(samples, self.encoder_stream.input_buffer(self.audio.fbank.num_mel_bins), sample_lens, final)
+        if self.audio.schedule is None:
+            self.encoder_out = self.encoder_stream.step_resident()
+            return self.decoder.decode(self.encoder_out, lens)
+        self.encoder_out = self.encoder_stream.step_resident(self.audio.frame_lens, host_lens=[m for _, m in self.audio.windows])
+        return self.decoder.decode(self.encoder_out, self.encoder_stream.out_lens)
+
+    def pending(self):
+        """Streams that still hold a window to run (fbank.StreamingFbank.pending): call step_audio with sample_lens 0 until it is empty."""
+        return [] if self.audio is None else self.audio.pending()
 
     def reset(self, streams=None):
         """New utterances on the given streams (all by default): audio carry, encoder position and left context, predictor state and hypotheses."""

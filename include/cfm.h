@@ -1092,7 +1092,17 @@ int cfm_greedy_chunk_step(const cfm_greedy_chunk_desc* d, cfm_stream_t stream);
  *   samples from samples[b] and has pos = 0; any other stream reads carry_in[b, 0 .. carry_n) followed by `n_next` = n_first - carry_n samples of samples[b],
  *   and pos = pos_in[b].  carry_out[b] <- the last carry_n samples of that sequence, fresh_out[b] <- 0, pos_out[b] <- pos + hop.  The *_in and *_out
  *   buffers must not alias (the caller swaps them between calls).  n_cols >= n_next; the caller, who knows which streams it reset, passes n_first
- *   columns when one is fresh (a read at or past n_cols yields 0, never memory beyond the row). */
+ *   columns when one is fresh (a read at or past n_cols yields 0, never memory beyond the row).
+ * cfm_fbank_stream with n_new != null (audio packets of any size; the fields behind `seed`, which the other two modes leave null / 0 and never read):
+ *   the carry is f32 [B, carry_cap] of which carry_len_in[b] samples count (0 for a fresh stream), the sequence of stream b is those followed by
+ *   samples[b, 0 .. n_new[b]) (clamped to n_cols; a read at or past n_new[b] yields 0), L samples in all, and with n_first as above:
+ *     L >= n_first                 a whole window: m = rows, the sequence loses hop * shift samples at its head, pos + hop
+ *     L <  n_first, final[b] != 0  the utterance's short last window: m = 1 + (L - win) / shift (0 when L < win) rows, rows >= m written as zeros;
+ *                                  c = ((m - 1) / 2 - 1) / 2 (0 for m < 7, cfm_stream_prep's encoder-frame count), 4 c shift samples lost, pos + 4 c
+ *     L <  n_first otherwise       buffering: m = 0, nothing lost, every row zero
+ *   carry_out[b] <- what is left of the sequence (at most carry_cap samples: the caller admits L <= n_first + hop * shift - 1, so that n_first - 1
+ *   remain at the most; carry_cap >= n_first - 1), carry_len_out[b] <- its length, pos_out, fresh_out <- 0, frame_lens[b] <- m: the device buffer of
+ *   window lengths that the length-aware encoder step reads.  carry_n is not read; n_cols may be 0 (samples may then be null). */
 typedef struct {
     const void* samples;
     const int32_t* lengths;      /* offline */
@@ -1110,6 +1120,10 @@ typedef struct {
     int32_t B, n_cols, rows, F, win, shift, padded, mel_nnz, samples_i16, carry_n, hop;
     float dither;
     uint32_t seed;
+    const int32_t *n_new, *final;    /* ragged packets (cfm_fbank_stream with n_new != null): int32 [B] each */
+    const int32_t* carry_len_in;     /* int32 [B] */
+    int32_t *carry_len_out, *frame_lens;
+    int32_t carry_cap;               /* the carry buffers are f32 [B, carry_cap] */
 } cfm_fbank_desc;
 int cfm_fbank(const cfm_fbank_desc* d, cfm_stream_t stream);
 int cfm_fbank_stream(const cfm_fbank_desc* d, cfm_stream_t stream);
