@@ -204,6 +204,16 @@ class GreedyChunkDesc(ctypes.Structure):
                 [(n, c_i32) for n in ("B", "chunk", "L", "E", "H", "P", "J", "D", "Vp", "blank", "n_steps", "carry")])
 
 
+class CtcGreedyDesc(ctypes.Structure):
+    _fields_ = ([("idx", c_p), ("logp", c_p), ("ld_k", c_i64)] + [(n, c_p) for n in ("lens", "prev", "frame_base", "hyps", "count", "frames", "token_logp", "overflow")] +
+                [("hyp_cap", c_i64), ("hyp_ld", c_i64)] + [(n, c_i32) for n in ("B", "T", "V", "blank")])
+
+
+class CtcBeamDesc(ctypes.Structure):
+    _fields_ = ([(n, c_p) for n in ("idx", "logp", "lens", "nodes")] + [("n_nodes", c_i64)] + [(n, c_p) for n in ("nbest_tokens", "nbest_len", "nbest_score")] +
+                [(n, c_i32) for n in ("B", "T", "V", "k", "beam", "blank")])
+
+
 class FbankDesc(ctypes.Structure):
     _fields_ = ([(n, c_p) for n in ("samples", "lengths", "feats_length", "carry_in", "carry_out", "fresh_in", "pos_in", "fresh_out", "pos_out", "twiddle", "window",
                                     "mel_w", "mel_start", "mel_len", "mel_off", "out")] + [("ld", c_i64)] +
@@ -275,6 +285,12 @@ def lib():
         L.cfm_greedy_chunk_begin.argtypes = [ctypes.POINTER(GreedyChunkDesc), c_p]
         L.cfm_greedy_chunk_step.argtypes = [ctypes.POINTER(GreedyChunkDesc), c_p]
         L.cfm_fbank.argtypes = [ctypes.POINTER(FbankDesc), c_p]
+        L.cfm_ctc_topk.argtypes = [c_p, c_i64, c_i32, c_i32, c_i32, c_p, c_i32, c_p, c_p, c_p, c_p]
+        L.cfm_ctc_greedy.argtypes = [ctypes.POINTER(CtcGreedyDesc), c_p]
+        L.cfm_ctc_prefix_beam.argtypes = [ctypes.POINTER(CtcBeamDesc), c_p]
+        L.cfm_ctc_topk.restype = L.cfm_ctc_greedy.restype = L.cfm_ctc_prefix_beam.restype = ctypes.c_int
+        L.cfm_ctc_beam_nodes.argtypes = [c_i32, c_i32, c_i32]
+        L.cfm_ctc_beam_nodes.restype = c_i64
         L.cfm_lstm_forward.argtypes = [ctypes.POINTER(LstmDesc), c_p]
         L.cfm_lstm_backward.argtypes = [ctypes.POINTER(LstmDesc), c_p]
         L.cfm_lstm_forward.restype = L.cfm_lstm_backward.restype = ctypes.c_int

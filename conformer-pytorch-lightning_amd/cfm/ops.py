@@ -8,7 +8,7 @@ import cfm as _c
 
 __all__ = ["lstm_forward", "lstm_backward", "fbank", "fbank_stream", "fbank_stream_ragged", "stream_prep", "stream_advance", "dwconv_causal_bn_silu", "conv_cache_update", "dropout_rows", "dropout_mask", "set_deterministic", "gemm_tn", "gemm_tn_group", "layernorm_bwd", "glu_bwd", "dwconv_bn_train", "dwconv_bn_train_bwd", "dwconv_bn_train_groups", "dwconv_bn_train_bwd_groups", "col2im_relu_bwd", "conv1_wgrad", "attention_bwd", "attention_group", "attention_bwd_group",
            "ctc_nll_train_groups", "ctc_grad", "rnnt_nll", "rnnt_grad", "joint_act_bwd", "rnnt_nll_packed", "joint_act_packed", "joint_act_packed_bwd", "ffn_split", "adam_step", "adam_clip_step", "sumsq", "scratch_stats",
-           "gemm", "ffn_fused", "ffn_fused_supported", "rowchain", "rowchain_supported", "rowchain_pair_supported", "layernorm", "attention", "kv_cache_pack", "dwconv_bn_silu", "conv1_relu", "conv1_relu_mma_supported", "conv12_relu", "conv12_supported", "ctc_nll", "joint_act", "valid_mask", "chunk_mask",
+           "gemm", "ffn_fused", "ffn_fused_supported", "rowchain", "rowchain_supported", "rowchain_pair_supported", "layernorm", "attention", "kv_cache_pack", "dwconv_bn_silu", "conv1_relu", "conv1_relu_mma_supported", "conv12_relu", "conv12_supported", "ctc_nll", "ctc_topk", "ctc_greedy", "ctc_greedy_state", "ctc_prefix_beam", "joint_act", "valid_mask", "chunk_mask",
            "attn_mask_combine", "cast", "add_rows", "scratch", "prof_enable", "prof_reset", "prof_table", "as_u8_mask"]
 
 
@@ -458,6 +458,108 @@ def ctc_nll(logits, V, enc_lens, labels, label_lens):
     _c.check(_c.lib().cfm_ctc_nll(_c.ptr(logits), logits.stride(1), B, T, V, _c.ptr(enc_lens), _c.ptr(labels), labels.size(1), _c.ptr(label_lens),
                                   _c.ptr(work), _c.ptr(out), _c.stream()), "cfm_ctc_nll")
     return out
+
+
+def ctc_topk(logits, V, lens, k, out=None):
+    """Per valid frame of f32 logits [B,T,ld>=V] the k <= 16 largest log-probabilities (log-softmax applied on the fly) with their classes, in
+    descending order, the lower class first among equal values, and the frame's log-sum-exp.  lens int32 [B].  Returns (idx int32 [B,T,k],
+    logp f32 [B,T,k], lse f32 [B,T]); rows of frames at or beyond lens[b] are not written (out: such a triple to write into; fresh ones are
+    zero-filled).  include/cfm.h cfm_ctc_topk."""
+    _c.require_hip(logits, lens)
+    if logits.dim() != 3 or logits.dtype != torch.float32 or logits.stride(2) != 1 or logits.stride(0) != logits.size(1) * logits.stride(1):
+        raise ValueError("cfm.ctc_topk: logits must be float32 [B,T,>=V] with contiguous rows")
+    B, T = logits.shape[:2]
+    if lens.dtype != torch.int32 or not lens.is_contiguous() or lens.numel() != B:
+        raise ValueError("cfm.ctc_topk: lens must be contiguous int32 [B]")
+    k = int(k)
+    if out is None:
+        out = (torch.zeros((B, T, max(k, 0)), dtype=torch.int32, device=logits.device), torch.zeros((B, T, max(k, 0)), dtype=torch.float32, device=logits.device),
+               torch.zeros((B, T), dtype=torch.float32, device=logits.device))
+    idx, logp, lse = out
+    _c.require_hip(idx, logp, lse)
+    _dense("ctc_topk", idx=idx, logp=logp, lse=lse)
+    if (idx.dtype, logp.dtype, lse.dtype) != (torch.int32, torch.float32, torch.float32) or idx.numel() != B * T * k or logp.numel() != B * T * k or lse.numel() != B * T:
+        raise ValueError("cfm.ctc_topk: out must be (int32 [B,T,k], float32 [B,T,k], float32 [B,T])")
+    _c.check(_c.lib().cfm_ctc_topk(_c.ptr(logits), logits.stride(1), B, T, V, _c.ptr(lens), k, _c.ptr(idx), _c.ptr(logp), _c.ptr(lse), _c.stream()), "cfm_ctc_topk")
+    return idx, logp, lse
+
+
+def ctc_greedy_state(B, cap, device):
+    """The per-stream state of ctc_greedy for B streams and room for cap symbols each: prev int32 [B] (-1), frame_base int32 [B], count int64 [B],
+    hyps int64 / frames int32 / token_logp f32 [B, cap], overflow int32 [1]."""
+    z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)
+    return dict(prev=torch.full((B,), -1, dtype=torch.int32, device=device), frame_base=z((B,), torch.int32), count=z((B,), torch.int64),
+                hyps=z((B, cap), torch.int64), frames=z((B, cap), torch.int32), token_logp=z((B, cap), torch.float32), overflow=z((1,), torch.int32))
+
+
+def ctc_greedy(idx, logp, lens, V, blank=0, state=None, hyp_cap=None):
+    """Best-path CTC decoding of ctc_topk's output (any k; the first column is read): per stream the classes of frames 0 .. lens[b] - 1 with
+    repeats collapsed and blanks dropped are APPENDED to state (ctc_greedy_state; a fresh one with room for T symbols when None), which carries
+    the last frame's class from call to call.  Returns state; the caller reads count / hyps / frames / token_logp / overflow from it.
+    include/cfm.h cfm_ctc_greedy."""
+    _c.require_hip(idx, logp, lens)
+    if idx.dim() != 3 or idx.shape != logp.shape or idx.dtype != torch.int32 or logp.dtype != torch.float32:
+        raise ValueError("cfm.ctc_greedy: idx int32 and logp float32 [B,T,k] of ctc_topk")
+    _dense("ctc_greedy", idx=idx, logp=logp, lens=lens)
+    B, T, k = idx.shape
+    if lens.dtype != torch.int32 or lens.numel() != B:
+        raise ValueError("cfm.ctc_greedy: lens must be contiguous int32 [B]")
+    S = ctc_greedy_state(B, T, idx.device) if state is None else state
+    _c.require_hip(*[v for v in S.values() if v is not None])
+    _dense("ctc_greedy", **S)
+    for name, dt, shape in (("prev", torch.int32, (B,)), ("count", torch.int64, (B,)), ("hyps", torch.int64, None), ("frames", torch.int32, tuple(S["hyps"].shape)),
+                            ("token_logp", torch.float32, tuple(S["hyps"].shape)), ("overflow", torch.int32, (1,))):
+        if S[name].dtype != dt or (shape is not None and tuple(S[name].shape) != shape):
+            raise ValueError("cfm.ctc_greedy: state[%r] must be %s %s" % (name, dt, shape))
+    if S["hyps"].dim() != 2 or S["hyps"].size(0) != B:
+        raise ValueError("cfm.ctc_greedy: state['hyps'] must be int64 [B, cap]")
+    fb = S.get("frame_base")
+    if fb is not None and (fb.dtype != torch.int32 or tuple(fb.shape) != (B,)):
+        raise ValueError("cfm.ctc_greedy: state['frame_base'] must be int32 [B]")
+    d = _c.CtcGreedyDesc()
+    d.idx, d.logp, d.ld_k, d.lens = _c.ptr(idx), _c.ptr(logp), k, _c.ptr(lens)
+    d.prev, d.frame_base, d.hyps, d.count, d.frames, d.token_logp, d.overflow = (_c.ptr(S["prev"]), _c.ptr(fb), _c.ptr(S["hyps"]), _c.ptr(S["count"]), _c.ptr(S["frames"]),
+                                                                                 _c.ptr(S["token_logp"]), _c.ptr(S["overflow"]))
+    d.hyp_ld = S["hyps"].size(1)
+    d.hyp_cap = d.hyp_ld if hyp_cap is None else int(hyp_cap)
+    d.B, d.T, d.V, d.blank = B, T, int(V), int(blank)
+    _c.check(_c.lib().cfm_ctc_greedy(ctypes.byref(d), _c.stream()), "cfm_ctc_greedy")
+    return S
+
+
+def ctc_prefix_beam(idx, logp, lens, V, beam=None, blank=0, out=None, nodes=None):
+    """CTC prefix beam search over ctc_topk's output: idx int32 / logp f32 [B,T,k], lens int32 [B]; beam <= 16 prefixes are kept (default: k) and a
+    frame offers its first min(k, beam) classes.  Returns
+    (nbest_tokens int64 [B,beam,T], nbest_len int32 [B,beam], nbest_score f32 [B,beam]), best first; entry n holds nbest_len[b,n] tokens, entries
+    beyond the live prefixes have length 0 and score -inf.  out: such a triple to write into; nodes: the int32 [B*beam*(T+1), 2] trie scratch.
+    include/cfm.h cfm_ctc_prefix_beam."""
+    _c.require_hip(idx, logp, lens)
+    if idx.dim() != 3 or idx.shape != logp.shape or idx.dtype != torch.int32 or logp.dtype != torch.float32:
+        raise ValueError("cfm.ctc_prefix_beam: idx int32 and logp float32 [B,T,beam] of ctc_topk")
+    _dense("ctc_prefix_beam", idx=idx, logp=logp, lens=lens)
+    B, T, k = idx.shape
+    beam = k if beam is None else int(beam)
+    if lens.dtype != torch.int32 or lens.numel() != B:
+        raise ValueError("cfm.ctc_prefix_beam: lens must be contiguous int32 [B]")
+    dev = idx.device
+    if out is None:
+        nb = max(beam, 0)
+        out = (torch.zeros((B, nb, T), dtype=torch.int64, device=dev), torch.zeros((B, nb), dtype=torch.int32, device=dev),
+               torch.zeros((B, nb), dtype=torch.float32, device=dev))
+    tokens, nlen, score = out
+    if nodes is None:
+        nodes = scratch("ctc_beam_nodes", 2 * B * max(beam, 1) * (T + 1), torch.int32, dev)
+    _c.require_hip(tokens, nlen, score, nodes)
+    _dense("ctc_prefix_beam", nbest_tokens=tokens, nbest_len=nlen, nbest_score=score, nodes=nodes)
+    if ((tokens.dtype, nlen.dtype, score.dtype, nodes.dtype) != (torch.int64, torch.int32, torch.float32, torch.int32) or tokens.numel() != B * beam * T or
+            nlen.numel() != B * beam or score.numel() != B * beam):
+        raise ValueError("cfm.ctc_prefix_beam: out must be (int64 [B,beam,T], int32 [B,beam], float32 [B,beam]), nodes int32")
+    d = _c.CtcBeamDesc()
+    d.idx, d.logp, d.lens, d.nodes, d.n_nodes = _c.ptr(idx), _c.ptr(logp), _c.ptr(lens), _c.ptr(nodes), nodes.numel() // 2
+    d.nbest_tokens, d.nbest_len, d.nbest_score = _c.ptr(tokens), _c.ptr(nlen), _c.ptr(score)
+    d.B, d.T, d.V, d.k, d.beam, d.blank = B, T, int(V), k, beam, int(blank)
+    _c.check(_c.lib().cfm_ctc_prefix_beam(ctypes.byref(d), _c.stream()), "cfm_ctc_prefix_beam")
+    return tokens, nlen, score
 
 
 def joint_act(enc, pred, B, T, U, out_dtype):

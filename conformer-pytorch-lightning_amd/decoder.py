@@ -8,6 +8,10 @@ calls F.dropout with its default training=True, i.e. it drops activations even i
 (and is then as random as the reference), parity is defined and tested at dropout = 0.  In train mode `forward` is differentiable
 (cfm/autograd.py CTCLossFn, the batch as a window of one micro-batch: the alpha and beta recursions and d loss / d logits in csrc/ctc.hip, the
 projection's gradients through cfm_gemm / cfm_gemm_tn); `nll` is loss evaluation only.
+
+Decoding (eval mode only, csrc/ctc_decode.hip; the reference has none): `greedy_search` (best path), `prefix_beam_search` (n-best lists with
+scores) and `CTCGreedyStream` (best path chunk by chunk, all state on the device).  They read the same logits as `nll` but apply NO dropout:
+Q7 is a quirk of the reference's loss, a decoder that drops activations would only be a worse decoder.
 """
 import torch
 import torch.nn as nn
@@ -36,15 +40,20 @@ class CTCDecoder(nn.Module):
             return packing.Packed(w=wm, w_lo=wlo, b=b, V=V, Vp=Vp)
         return self._pack.get([self.ctc_lo.weight, self.ctc_lo.bias], prec, build)
 
+    @staticmethod
+    def _logits(x, pk):
+        """f32 logits [B, T, Vp] of x [B, T, D] (columns V..Vp are padding that no consumer reads)."""
+        B, T, D = x.shape
+        x2 = (x if x.dtype == torch.float32 else x.float()).contiguous().view(B * T, D)
+        return cfm.gemm(x2, pk.w, bias=pk.b, w_lo=pk.w_lo, out_dtype=torch.float32).view(B, T, pk.Vp)
+
     def nll(self, encoder_out, encoder_out_lens, padded_labels, label_lengths):
         """Per-utterance CTC negative log-likelihood, f32 [B] (loss evaluation: not differentiable -- use forward in train mode)."""
         cfm.require_hip(encoder_out)
         prec = cfm.resolve_precision(self)
         pk = self._weights(prec)
         x = nn.functional.dropout(encoder_out, self.dropout)      # training=True by default, as decoder.py:19 (quirk Q7)
-        B, T, D = x.shape
-        x2 = (x if x.dtype == torch.float32 else x.float()).contiguous().view(B * T, D)
-        logits = cfm.gemm(x2, pk.w, bias=pk.b, w_lo=pk.w_lo, out_dtype=torch.float32).view(B, T, pk.Vp)
+        logits = self._logits(x, pk)
         dev = x.device
         i32 = lambda t: t.to(device=dev, dtype=torch.int32).contiguous()
         return cfm.ctc_nll(logits, pk.V, i32(encoder_out_lens), i32(padded_labels), i32(label_lengths))
@@ -77,3 +86,115 @@ class CTCDecoder(nn.Module):
         x = nn.functional.dropout(rows, self.dropout)                    # training=True by default, as decoder.py:19 (quirk Q7)
         gs = [(int(B), int(T), i32(el), i32(lab), i32(ll)) for B, T, el, lab, ll in groups]
         return ag.CTCLossFn.apply(x, self, cfm.resolve_precision(self), gs, self.ctc_lo.weight, self.ctc_lo.bias)
+
+    # -- decoding (inference only) ------------------------------------------------------------------------------------------------------------
+    def _topk(self, encoder_out, encoder_out_lens, k, who):
+        """(idx, logp, lse, lens int32 on the device, V) of cfm.ctc_topk on the head's logits: no dropout (see the module docstring)."""
+        if self.training:
+            raise RuntimeError("CTCDecoder.%s is an eval-mode operation (inference only); in train mode call forward" % who)
+        cfm.require_hip(encoder_out)
+        if encoder_out.dim() != 3:
+            raise ValueError("CTCDecoder.%s: encoder_out must be [B, T, D], got %s" % (who, tuple(encoder_out.shape)))
+        pk = self._weights(cfm.resolve_precision(self))
+        lens = torch.as_tensor(encoder_out_lens).to(device=encoder_out.device, dtype=torch.int32).contiguous()
+        return cfm.ctc_topk(self._logits(encoder_out, pk), pk.V, lens, k) + (lens, pk.V)
+
+    @torch.no_grad()
+    def greedy_search(self, encoder_out, encoder_out_lens, blank=0, return_details=False):
+        """Best path: per frame the most probable class, repeats collapsed, blanks dropped (cfm_ctc_topk with k = 1, cfm_ctc_greedy).
+        encoder_out [B, T, D], encoder_out_lens (B,).  Returns a list of B token lists; return_details=True: (that list, details) with
+        details = {"frames": int32 [B, T], "logp": f32 [B, T], "count": int64 [B]} on the device -- per emitted token its frame and its
+        log-probability, count[b] of them valid per row."""
+        idx, logp, _, lens, V = self._topk(encoder_out, encoder_out_lens, 1, "greedy_search")
+        S = cfm.ctc_greedy(idx, logp, lens, V, blank=blank)
+        counts = S["count"].tolist()
+        hyps = S["hyps"].cpu()
+        out = [hyps[b, :counts[b]].tolist() for b in range(len(counts))]
+        return (out, {"frames": S["frames"], "logp": S["token_logp"], "count": S["count"]}) if return_details else out
+
+    @torch.no_grad()
+    def prefix_beam_search(self, encoder_out, encoder_out_lens, beam=10, blank=0):
+        """CTC prefix beam search (cfm_ctc_topk with k = min(beam, V), beam <= 16, cfm_ctc_prefix_beam; include/cfm.h states the algorithm and its ranking
+        rule).  Returns per utterance a list of (tokens, score) pairs, best first; score = log of the summed probability of the alignments of
+        the token string that the search kept."""
+        beam = int(beam)
+        idx, logp, _, lens, V = self._topk(encoder_out, encoder_out_lens, max(1, min(beam, self.ctc_lo.out_features)), "prefix_beam_search")
+        tokens, nlen, score = cfm.ctc_prefix_beam(idx, logp, lens, V, beam=beam, blank=blank)
+        tokens, nlen, score = tokens.cpu(), nlen.tolist(), score.tolist()
+        return [[(tokens[b, n, :nlen[b][n]].tolist(), score[b][n]) for n in range(len(nlen[b])) if score[b][n] > float("-inf")] for b in range(len(nlen))]
+
+
+class CTCGreedyStream:
+    """Best-path CTC decoding of `streams` utterances chunk by chunk -- `CTCDecoder.greedy_search` as a streaming step, with the contract of
+    greedy.ChunkGreedySearch's decode / hyps / reset.  All state lives on the device: per stream the last frame's class (`prev`: a repeat that
+    straddles two chunks collapses), the frames seen so far, the hypothesis buffer, its frames and log-probabilities, and the counts.  A decode
+    is three launches (projection, cfm_ctc_topk, cfm_ctc_greedy) and one host read of the counts; a chunk of C frames adds at most C symbols
+    per stream, so the buffer is grown BEFORE a chunk that could overflow it (as ChunkGreedySearch._grow) and the kernel's overflow flag stays
+    an error."""
+
+    def __init__(self, ctc, streams, blank=0, max_tokens=None):
+        self.ctc, self.B, self.blank = ctc, int(streams), int(blank)
+        if self.B < 1:
+            raise ValueError("CTCGreedyStream: streams is positive")
+        self.dev = ctc.ctc_lo.weight.device
+        self.S = cfm.ctc_greedy_state(self.B, max(1, int(max_tokens) if max_tokens is not None else 256), self.dev) if self.dev.type == "cuda" else None
+        self._host_count = [0] * self.B
+        self._host_hyps = [[] for _ in range(self.B)]
+
+    def _grow(self, need):
+        S = self.S
+        old = S["hyps"].shape[1]
+        for k in ("hyps", "frames", "token_logp"):
+            t = torch.zeros((self.B, max(2 * old, need)), dtype=S[k].dtype, device=self.dev)
+            t[:, :old] = S[k]
+            S[k] = t
+
+    def reset(self, streams=None):
+        """New utterances on the given streams (all by default): no previous class, frame 0, hypotheses emptied."""
+        if self.S is None:
+            raise RuntimeError("cfm: CTCGreedyStream on %s -- this framework runs on MI355X (HIP) only; there is no CPU path" % self.dev)
+        idx = slice(None) if streams is None else torch.as_tensor(list(streams), dtype=torch.long, device=self.dev)
+        self.S["prev"][idx] = -1
+        for k in ("frame_base", "count", "hyps", "frames", "token_logp"):
+            self.S[k][idx] = 0
+        for b in (range(self.B) if streams is None else list(streams)):
+            self._host_count[b] = 0
+            self._host_hyps[b] = []
+
+    def hyps(self):
+        """Everything emitted per stream since its last reset."""
+        return [list(h) for h in self._host_hyps]
+
+    @torch.no_grad()
+    def decode(self, enc_chunk, lens=None):
+        """enc_chunk (B, C, D) encoder output of one chunk (any C); lens (B,): how many of its frames belong to each stream (default: all; 0: the
+        stream is idle and nothing about it changes).  Returns a list of B lists: the tokens this chunk added."""
+        if self.ctc.training:
+            raise RuntimeError("CTCGreedyStream.decode is an eval-mode operation (inference only)")
+        cfm.require_hip(enc_chunk)
+        B = self.B
+        if enc_chunk.dim() != 3 or enc_chunk.shape[0] != B or enc_chunk.device != self.dev:
+            raise ValueError("CTCGreedyStream.decode wants (%d, C, D) on %s, got %s on %s" % (B, self.dev, tuple(enc_chunk.shape), enc_chunk.device))
+        C = enc_chunk.shape[1]
+        if lens is None:
+            lens = torch.full((B,), C, dtype=torch.int32, device=self.dev)
+        elif not isinstance(lens, torch.Tensor) and len(lens) != B:
+            raise ValueError("CTCGreedyStream.decode: %d lens for %d streams" % (len(lens), B))
+        need = max(self._host_count) + C
+        if need > self.S["hyps"].shape[1]:
+            self._grow(need)
+        idx, logp, _, lens, V = self.ctc._topk(enc_chunk, lens, 1, "greedy_search")
+        cfm.ctc_greedy(idx, logp, lens, V, blank=self.blank, state=self.S)
+        rep = torch.cat([self.S["count"], self.S["overflow"].to(torch.int64)]).tolist()
+        counts, overflow = rep[:B], rep[B]
+        if overflow:
+            raise RuntimeError("CTCGreedyStream: a stream emitted more symbols than the hypothesis buffer holds")
+        lo, hi = min(self._host_count), max(counts)
+        new = [[] for _ in range(B)]
+        if hi > lo:
+            rows = self.S["hyps"][:, lo:hi].cpu()
+            for b in range(B):
+                new[b] = rows[b, self._host_count[b] - lo:counts[b] - lo].tolist()
+                self._host_hyps[b].extend(new[b])
+        self._host_count = counts
+        return new

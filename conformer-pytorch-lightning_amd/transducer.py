@@ -75,6 +75,19 @@ class TransducerObjective(nn.Module):
         return self.ctc_weight * loss_ctc + self.transducer_weight * loss_rnnt
 
 
+def _check_ctc(ctc, encoder, who):
+    if ctc is not None and ctc.ctc_lo.in_features != encoder.encoder_dim:
+        raise ValueError("%s: the CTC head reads %d encoder features, the encoder gives %d" % (who, ctc.ctc_lo.in_features, encoder.encoder_dim))
+    return ctc
+
+
+def _ctc_stream(ctc, encoder, streams, blank, who):
+    if _check_ctc(ctc, encoder, who) is None:
+        return None
+    import decoder
+    return decoder.CTCGreedyStream(ctc, streams, blank=blank)
+
+
 class StreamingRecognizer:
     """B independent utterances recognised chunk by chunk: `encoder.StreamingBatch` (one batched encoder step, per-stream K/V rings) feeding
     `greedy.ChunkGreedySearch` (chunk-lookahead greedy search, csrc/greedy.hip) on the same stream -- the encoder's output buffer is the
@@ -101,11 +114,12 @@ class StreamingRecognizer:
     window.  Giving both raises: frame_lens already fixes the decoder's lengths."""
 
     def __init__(self, encoder, predictor, joint, streams, decoding_chunk_size, num_decoding_left_chunks, blank=0, n_steps=64, carry=True, causal_conv=False,
-                 steps_per_replay=8, graph=True, fbank_args=None):
+                 steps_per_replay=8, graph=True, fbank_args=None, ctc=None):
         import encoder as encoder_module
         import greedy
         if joint.enc_ffn.in_features != encoder.encoder_dim:
             raise ValueError("StreamingRecognizer: the joint reads %d encoder features, the encoder gives %d" % (joint.enc_ffn.in_features, encoder.encoder_dim))
+        self.ctc_decoder = _ctc_stream(ctc, encoder, streams, blank, "StreamingRecognizer")
         self.B, self.chunk = int(streams), int(decoding_chunk_size)
         self.encoder_stream = encoder_module.StreamingBatch(encoder, streams, decoding_chunk_size, num_decoding_left_chunks, causal_conv=causal_conv, graph=graph)
         self.decoder = greedy.ChunkGreedySearch(predictor, joint, streams, decoding_chunk_size, blank=blank, n_steps=n_steps, steps_per_replay=steps_per_replay,
@@ -118,7 +132,13 @@ class StreamingRecognizer:
         if lens is not None and frame_lens is not None:
             raise ValueError("StreamingRecognizer.step: give lens (encoder frames the decoder reads) or frame_lens (feature frames of each window), not both")
         self.encoder_out = self.encoder_stream.step(frames, frame_lens)                 # (B, chunk, D), overwritten by the next step
-        return self.decoder.decode(self.encoder_out, self.encoder_stream.out_lens if frame_lens is not None else lens)
+        return self._decode(self.encoder_stream.out_lens if frame_lens is not None else lens)
+
+    def _decode(self, lens):
+        """The step's encoder chunk and per-stream lengths to the RNN-T decoder and, when there is a CTC head, to its best-path decoder too."""
+        if self.ctc_decoder is not None:
+            self.ctc_decoder.decode(self.encoder_out, lens)
+        return self.decoder.decode(self.encoder_out, lens)
 
     def step_audio(self, samples, lens=None, sample_lens=None, final=None):
         """step() from the waveform (the reference's deploy.py preprocess_stream + greedy_search_streaming_app): samples (B, n) int16 | float32 on
@@ -149,9 +169,9 @@ class StreamingRecognizer:
         self.audio.step(samples, self.encoder_stream.input_buffer(self.audio.fbank.num_mel_bins), sample_lens, final)
         if self.audio.schedule is None:
             self.encoder_out = self.encoder_stream.step_resident()
-            return self.decoder.decode(self.encoder_out, lens)
+            return self._decode(lens)
         self.encoder_out = self.encoder_stream.step_resident(self.audio.frame_lens, host_lens=[m for _, m in self.audio.windows])
-        return self.decoder.decode(self.encoder_out, self.encoder_stream.out_lens)
+        return self._decode(self.encoder_stream.out_lens)
 
     def pending(self):
         """Streams that still hold a window to run (fbank.StreamingFbank.pending): call step_audio with sample_lens 0 until it is empty."""
@@ -162,12 +182,20 @@ class StreamingRecognizer:
         streams = None if streams is None else list(streams)
         self.encoder_stream.reset(streams)
         self.decoder.reset(streams)
+        if self.ctc_decoder is not None:
+            self.ctc_decoder.reset(streams)
         if self.audio is not None:
             self.audio.reset(streams)
 
     def hyps(self):
         """Everything emitted per stream since its last reset."""
         return self.decoder.hyps()
+
+    def ctc_hyps(self):
+        """The CTC head's best-path hypotheses per stream since its last reset (the recogniser was built with ctc=...)."""
+        if self.ctc_decoder is None:
+            raise RuntimeError("StreamingRecognizer.ctc_hyps: the recogniser was built without a CTC head (ctc=None)")
+        return self.ctc_decoder.hyps()
 
 
 class OfflineRecognizer:
@@ -178,12 +206,14 @@ class OfflineRecognizer:
     recognize(feats (B,T,F), lengths (B,)) -> list of B token lists; items shorter than 7 frames (no encoder frame) give [].
     recognize_audio(samples (B,N) int16 | float32 on the int16 scale, lengths (B,) samples) -> the same from the waveform, through
     fbank.KaldiFbank (deploy.py preprocess); `fbank`: a KaldiFbank, or None for the reference's settings without dither.
-    The lengths stay on the device; the only host read is the search's own.  encoder_out / encoder_out_lens: what the last call's search read."""
+    The lengths stay on the device; the only host read is the search's own.  encoder_out / encoder_out_lens: what the last call's search read.
+    ctc: a decoder.CTCDecoder on the same encoder; recognize_ctc / recognize_ctc_audio then decode its output instead (the hybrid model's cheap first pass)."""
 
-    def __init__(self, encoder, predictor, joint, blank=0, n_steps=64, fbank=None, **search_kw):
+    def __init__(self, encoder, predictor, joint, blank=0, n_steps=64, fbank=None, ctc=None, **search_kw):
         import greedy
         if joint.enc_ffn.in_features != encoder.encoder_dim:
             raise ValueError("OfflineRecognizer: the joint reads %d encoder features, the encoder gives %d" % (joint.enc_ffn.in_features, encoder.encoder_dim))
+        self.ctc, self.blank = _check_ctc(ctc, encoder, "OfflineRecognizer"), blank
         self.encoder = encoder
         self.search = greedy.BatchedGreedySearch(predictor, joint, blank=blank, n_steps=n_steps, **search_kw)
         self.fbank = fbank
@@ -199,3 +229,21 @@ class OfflineRecognizer:
             import fbank
             self.fbank = fbank.KaldiFbank()
         return self.recognize(*self.fbank(samples, lengths))
+
+    @torch.no_grad()
+    def recognize_ctc(self, feats, lengths, beam=None):
+        """The CTC head's hypotheses of the same ragged batch: forward_utterances once, then decoder.CTCDecoder.greedy_search (beam=None: a list
+        of B token lists) or prefix_beam_search(beam) (per utterance a list of (tokens, score), best first).  An utterance with no encoder
+        frame gives [] (beam: the empty hypothesis alone, [([], 0.0)])."""
+        if self.ctc is None:
+            raise RuntimeError("OfflineRecognizer.recognize_ctc: the recogniser was built without a CTC head (ctc=None)")
+        self.encoder_out, self.encoder_out_lens = self.encoder.forward_utterances(feats, lengths)
+        if beam is None:
+            return self.ctc.greedy_search(self.encoder_out, self.encoder_out_lens, blank=self.blank)
+        return self.ctc.prefix_beam_search(self.encoder_out, self.encoder_out_lens, beam=beam, blank=self.blank)
+
+    def recognize_ctc_audio(self, samples, lengths, beam=None):
+        if self.fbank is None:
+            import fbank
+            self.fbank = fbank.KaldiFbank()
+        return self.recognize_ctc(*self.fbank(samples, lengths), beam=beam)

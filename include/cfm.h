@@ -1163,6 +1163,68 @@ int64_t cfm_lstm_save_floats(int32_t B, int32_t U, int32_t H);
 int cfm_lstm_forward(const cfm_lstm_desc* d, cfm_stream_t stream);
 int cfm_lstm_backward(const cfm_lstm_desc* d, cfm_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * CTC decoding on top of the vocabulary projection (csrc/ctc_decode.hip).  logits f32 [B,T,ld>=V] as for cfm_ctc_nll (ld % 4 == 0, columns
+ * V..ld never read); lens int32 [B]: the valid frames of each utterance / stream (clamped to [0, T]).  The reference has no CTC decoder;
+ * the algorithms are the standard ones, restated in float64 in tests/ctc_decode_ref.py.
+ *
+ * cfm_ctc_topk: per valid frame lse = log sum_c exp(logits[c]) (max-shifted, f32) and the k largest log-probabilities logits[c] - lse with
+ *   their classes, 1 <= k <= min(16, V), in descending order, the lower class first among equal values (torch.argmax's rule for k = 1,
+ *   torch.sort(stable=True, descending=True) otherwise).  idx int32 [B*T, k], logp f32 [B*T, k], lse f32 [B*T]; the rows of frames at or
+ *   beyond lens[b] are not touched. */
+int cfm_ctc_topk(const float* logits, int64_t ld, int32_t B, int32_t T, int32_t V, const int32_t* lens, int32_t k, int32_t* idx, float* logp,
+                 float* lse, cfm_stream_t stream);
+
+/* cfm_ctc_greedy: best-path decoding -- the per-frame argmax, repeats collapsed, blanks dropped -- as a streaming step.  idx / logp: the
+ *   first column of cfm_ctc_topk's output (row stride ld_k >= 1, so any k serves).  Frame t < lens[b] of stream b emits its class when it
+ *   differs from the class of the frame before it and from blank; the frame before frame 0 is prev[b] (int32 [B], -1 at an utterance's start,
+ *   left holding the last frame's class: a repeat across two calls collapses).  An emission is appended at hyps[b, count[b]] (int64
+ *   [B, hyp_ld], count int64 [B]) together with frames[b, .] = frame_base[b] + t (int32; frame_base int32 [B] may be null: 0, else it is
+ *   advanced by lens[b]) and token_logp[b, .] = the class's log-probability (f32), both of hyps' shape.  A stream that already holds hyp_cap
+ *   symbols sets overflow[0] = 1; the symbol is counted, not stored.  lens[b] == 0 changes nothing for stream b.  blank in [0, V). */
+typedef struct {
+    const int32_t* idx;
+    const float* logp;
+    int64_t ld_k;
+    const int32_t* lens;
+    int32_t* prev;
+    int32_t* frame_base;
+    int64_t *hyps, *count;
+    int32_t* frames;
+    float* token_logp;
+    int32_t* overflow;
+    int64_t hyp_cap, hyp_ld;
+    int32_t B, T, V, blank;
+} cfm_ctc_greedy_desc;
+int cfm_ctc_greedy(const cfm_ctc_greedy_desc* d, cfm_stream_t stream);
+
+/* cfm_ctc_prefix_beam: CTC prefix beam search, 1 <= beam <= 16 prefixes kept.  idx / logp [B, T, k]: cfm_ctc_topk's output, 1 <= k <= min(16, V), of
+ *   which a frame offers its first min(k, beam) classes (k = beam unless the vocabulary has fewer classes than the beam has places).  Every
+ *   prefix of the beam carries pb / pnb, the f32 log-probabilities of its alignments that end in blank / in its last token (-inf:
+ *   impossible); the empty prefix starts at (0, -inf).  A frame's class (c, p) adds logaddexp(pb, pnb) + p to pb of the prefix itself
+ *   (c blank) or to pnb of the prefix extended by c, except that c equal to the prefix's last token adds pnb + p to the prefix's own pnb and
+ *   only pb + p to the extension.  Candidates that are the same TOKEN STRING are merged (a prefix that left the beam and returned under a new
+ *   trie node meets its surviving extension again): the kernel compares (length, last token, 64-bit incremental hash of the string), see
+ *   csrc/ctc_decode.hip for the collision bound.  The `beam` best candidates by logaddexp(pb, pnb) are kept; a score of -inf is no candidate.
+ *   The order is total: higher score; then the candidate that continues the better-ranked parent; then the prefix itself before its
+ *   extensions; then the lower class (a merged candidate ranks with the better of its two sources).
+ *   nodes: scratch, int32 pairs (parent, token), n_nodes >= cfm_ctc_beam_nodes(B, T, beam) = B * beam * (T + 1) pairs.
+ *   nbest_tokens int64 [B, beam, T] (entry n holds nbest_len[b, n] tokens, the rest is not touched), nbest_len int32 [B, beam], nbest_score
+ *   f32 [B, beam], best first; entries beyond the live prefixes have length 0 and score -inf.  lens[b] == 0: one empty hypothesis, score 0. */
+typedef struct {
+    const int32_t* idx;
+    const float* logp;
+    const int32_t* lens;
+    int32_t* nodes;
+    int64_t n_nodes;
+    int64_t* nbest_tokens;
+    int32_t* nbest_len;
+    float* nbest_score;
+    int32_t B, T, V, k, beam, blank;
+} cfm_ctc_beam_desc;
+int64_t cfm_ctc_beam_nodes(int32_t B, int32_t T, int32_t beam);
+int cfm_ctc_prefix_beam(const cfm_ctc_beam_desc* d, cfm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
