@@ -1274,14 +1274,15 @@ def adam_step(p, g, m, v, lr, betas, eps, weight_decay, step, grad_scale=None):
 
 def adam_clip_step(p, g, m, v, lr, betas, eps, weight_decay, step, sumsq_t, clip, inv_world, zero_grad=True):
     """adam_step with the clip coefficient computed on the device from `sumsq_t` (cfm.sumsq of g), the 1/world averaging and the zeroing of g in
-    the same launch (include/cfm.h cfm_adam_clip_step).  Returns the averaged gradient's norm as a 1-element device tensor."""
+    the same launch (include/cfm.h cfm_adam_clip_step).  Returns the averaged gradient's norm as a 1-element device tensor, or None when
+    sumsq_t is None (clip off: the kernel has nothing to take a norm from)."""
     _c.require_hip(p, g, m, v, sumsq_t)
     n = p.numel()
     for t in (p, g, m, v):
         if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous():
             raise ValueError("cfm.adam_clip_step: p, g, m, v must be contiguous float32 buffers of one size")
     _dense("adam_clip_step", sumsq=sumsq_t)
-    norm = torch.empty((1,), dtype=torch.float32, device=p.device)
+    norm = None if sumsq_t is None else torch.empty((1,), dtype=torch.float32, device=p.device)
     _c.check(_c.lib().cfm_adam_clip_step(_c.ptr(p), _c.ptr(g), _c.ptr(m), _c.ptr(v), n, lr, betas[0], betas[1], eps, weight_decay, step, _c.ptr(sumsq_t),
                                          float(clip or 0.0), float(inv_world), 1 if zero_grad else 0, _c.ptr(norm), _c.stream()), "cfm_adam_clip_step")
     return norm

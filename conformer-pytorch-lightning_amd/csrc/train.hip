@@ -751,7 +751,10 @@ __global__ void cfm_adam_clip_kernel(float* __restrict__ p, float* __restrict__ 
     float gs = inv_world;
     if (sumsq) {
         const float norm = sqrtf(*sumsq) * inv_world;
-        if (clip > 0.f) gs = fminf(clip / (norm + 1e-6f), 1.0f) * inv_world;
+        if (clip > 0.f) {
+            const float c = clip / (norm + 1e-6f);
+            gs = (c > 1.0f ? 1.0f : c) * inv_world;         // not fminf: a NaN norm must give a NaN scale (torch's clamp(max=1), clip_grad_norm_), not an unclipped step
+        }
         if (norm_out && blockIdx.x == 0 && threadIdx.x == 0) *norm_out = norm;
     }
     const int64_t n4 = n / 4;
@@ -1165,13 +1168,21 @@ extern "C" int cfm_dropout_mask(uint8_t* out, int64_t n, float p, uint32_t seed,
     return cfm_launch_status("cfm_dropout_mask");
 }
 
+// Bias corrections 1 - beta1^step and sqrt(1 - beta2^step), in double on the host and rounded once: in float, 1.f - powf(0.999f, 2.f) keeps
+// 15 of its 24 bits (the power lies next to 1 and is rounded there), an error of 1.5e-5 in sqrt(bc2) and so in every element's update.
+static void adam_bias_corrections(float beta1, float beta2, int64_t step, float* bc1, float* bc2_sqrt) {
+    *bc1 = (float)(1.0 - pow((double)beta1, (double)step));
+    *bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
+}
+
 extern "C" int cfm_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
                              int64_t step, const float* grad_scale, cfm_stream_t stream) {
     CFM_CHECK_ARG(p && g && m && v && n > 0 && step > 0, "cfm_adam_step: bad arguments");
     hipStream_t s = (hipStream_t)stream;
-    const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
+    float bc1, bc2_sqrt;
+    adam_bias_corrections(beta1, beta2, step, &bc1, &bc2_sqrt);
     CfmProfScope prof("adam_step", s, 0.0, (double)n * 28);
-    CFM_LAUNCH(cfm_adam_kernel, dim3((unsigned)grid_for(n / 4 + 1, 256, 8192)), dim3(256), 0, s, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, sqrtf(bc2),
+    CFM_LAUNCH(cfm_adam_kernel, dim3((unsigned)grid_for(n / 4 + 1, 256, 8192)), dim3(256), 0, s, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt,
                grad_scale);
     return cfm_launch_status("cfm_adam_step");
 }
@@ -1180,9 +1191,10 @@ extern "C" int cfm_adam_clip_step(float* p, float* g, float* m, float* v, int64_
                                   int64_t step, const float* sumsq, float clip, float inv_world, int32_t zero_grad, float* norm_out, cfm_stream_t stream) {
     CFM_CHECK_ARG(p && g && m && v && n > 0 && step > 0 && inv_world > 0.f && (clip <= 0.f || sumsq), "cfm_adam_clip_step: bad arguments");
     hipStream_t s = (hipStream_t)stream;
-    const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
+    float bc1, bc2_sqrt;
+    adam_bias_corrections(beta1, beta2, step, &bc1, &bc2_sqrt);
     CfmProfScope prof("adam_clip_step", s, 0.0, (double)n * 32);
-    CFM_LAUNCH(cfm_adam_clip_kernel, dim3((unsigned)grid_for(n / 4 + 1, 256, 8192)), dim3(256), 0, s, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, sqrtf(bc2),
+    CFM_LAUNCH(cfm_adam_clip_kernel, dim3((unsigned)grid_for(n / 4 + 1, 256, 8192)), dim3(256), 0, s, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt,
                sumsq, clip, inv_world, zero_grad, norm_out);
     return cfm_launch_status("cfm_adam_clip_step");
 }

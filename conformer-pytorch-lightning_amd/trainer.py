@@ -52,7 +52,7 @@ class HipStepKernels:
         cfm.adam_step(p, g, m, v, lr, betas, eps, weight_decay, step, grad_scale=grad_scale)
 
     def adam_clip_step(self, p, g, m, v, lr, betas, eps, weight_decay, step, clip, inv_world):
-        """sum of squares, then ONE launch: clip coefficient from it, 1/world averaging, Adam, gradient buffer zeroed.  Returns the norm."""
+        """sum of squares, then ONE launch: clip coefficient from it, 1/world averaging, Adam, gradient buffer zeroed.  Returns the norm (None with the clip off: no sum of squares is taken)."""
         import cfm
         return cfm.adam_clip_step(p, g, m, v, lr, betas, eps, weight_decay, step, cfm.sumsq(g) if clip else None, clip, inv_world, zero_grad=True)
 

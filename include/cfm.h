@@ -998,7 +998,9 @@ int cfm_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float
 int cfm_sumsq(const float* x, int64_t n, float* partials, int32_t n_partials, float* out, cfm_stream_t stream);
 /* cfm_adam_step with the step's scalar glue inside (executor.py:150 gradient_clip_val + Lightning DDP's gradient averaging): the gradient
  * scale is min(1, clip / (sqrt(*sumsq) * inv_world + 1e-6)) * inv_world (clip <= 0: inv_world), computed on the device from cfm_sumsq's result;
- * *norm_out (optional) receives the averaged gradient's norm; zero_grad != 0 zeroes g as it is read (the next step's accumulation buffer). */
+ * *norm_out (optional) receives the averaged gradient's norm when sumsq is given (sumsq NULL, allowed with clip <= 0: it is not written);
+ * zero_grad != 0 zeroes g as it is read (the next step's accumulation buffer).  A NaN *sumsq under clip > 0 gives a NaN scale, so p, m, v
+ * all become NaN (torch's clip_grad_norm_ + Adam); an infinite one gives the scale 0. */
 int cfm_adam_clip_step(float* p, float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
                        int64_t step, const float* sumsq, float clip, float inv_world, int32_t zero_grad, float* norm_out, cfm_stream_t stream);
 
