@@ -68,10 +68,11 @@ def scratch_stats():
 
 
 def gemm(a, w, bias=None, w_lo=None, out=None, out_dtype=None, act=_c.ACT_NONE, residual=None, alpha=1.0, row_mask=None,
-         mask_mode=0, conv=None, tile=0, n_out=None, pre_out=None, aux=None, drop=None, drop2=None):
+         mask_mode=0, conv=None, tile=0, n_out=None, pre_out=None, aux=None, drop=None, drop2=None, row_len=None, row_T=0):
     """out = epilogue(a[M,K] . w[N,K]^T); see include/cfm.h cfm_gemm.  conv=(C,T1,F1,T2,F2,M) selects the implicit
-    3x3/stride-2 convolution over a channels-last image `a` of shape [B,T1,F1,C]."""
-    _c.require_hip(a, w, bias, w_lo, out, residual, row_mask)
+    3x3/stride-2 convolution over a channels-last image `a` of shape [B,T1,F1,C].  row_len (int32 [M/row_T], device) with row_T: the
+    ragged-batch select behind the GLU (cfm_gemm_desc.row_len)."""
+    _c.require_hip(a, w, bias, w_lo, out, residual, row_mask, row_len)
     w = _rows2d(w, "gemm(w)")
     N, K = w.shape
     if w.stride(0) != K:                         # cfm_gemm_desc has no row stride for W: a view wbuf[:, :K] would be read with stride K
@@ -124,6 +125,14 @@ def gemm(a, w, bias=None, w_lo=None, out=None, out_dtype=None, act=_c.ACT_NONE, 
         d.drop_p, d.drop_seed = float(drop[0]), int(drop[1]) & 0xFFFFFFFF
         if drop2 is not None and drop2[0] > 0.0:
             d.drop2_p, d.drop2_seed = float(drop2[0]), int(drop2[1]) & 0xFFFFFFFF
+    if row_len is not None:                      # M % row_T, mask_mode and the GLU requirement are the ABI's own checks
+        _dense("gemm", row_len=row_len)
+        if row_len.dtype != torch.int32:
+            raise ValueError("cfm.gemm: row_len must be int32, got %s" % row_len.dtype)
+        if row_T > 0 and M % row_T == 0 and row_len.numel() < M // row_T:      # every other misuse is the ABI's own argument error
+            raise ValueError("cfm.gemm: row_len has %d entries, %d rows of %d need %d" % (row_len.numel(), M, row_T, M // row_T))
+        d.row_len = _c.ptr(row_len)
+    d.row_T = int(row_T)
     d.A, d.W, d.W_lo, d.bias, d.residual, d.row_mask, d.C = _c.ptr(a), _c.ptr(w), _c.ptr(w_lo), _c.ptr(bias), _c.ptr(residual), _c.ptr(row_mask), _c.ptr(out)
     d.ldc = out.stride(0)
     d.M, d.N, d.K = M, N, K

@@ -121,6 +121,9 @@ __device__ __forceinline__ void split8(const f32x4& a, const f32x4& b, u32x4& hi
 // v_exp_f32 + v_rcp_f32 (1 ulp): the IEEE divide sequence costs ~10 VALU ops per element in a GEMM epilogue
 __device__ __forceinline__ float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 __device__ __forceinline__ float siluf_(float x) { return x * sigmoidf_(x); }
+// ReLU of the GEMM epilogues: fmaxf alone returns its other argument for a NaN, which turns an overflowed activation into a clean zero
+// (torch.relu keeps the NaN).  Every other value, -0.0 included, keeps the bits fmaxf gives.
+__device__ __forceinline__ float reluf_(float x) { return x != x ? x : fmaxf(x, 0.f); }
 
 // ---------------------------------------------------------------------------------------------
 // dropout: a counter-based generator -- keep(seed, element index) is a pure function, so the backward regenerates the forward's

@@ -354,7 +354,7 @@ __global__ __launch_bounds__(256 * KG, KG == 1 ? 2 : 1) void cfm_gemm_kernel(con
                 for (int r = 0; r < 4; ++r) v[r] = siluf_(v[r]);
             } else if (g.act == CFM_ACT_RELU) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
+                for (int r = 0; r < 4; ++r) v[r] = reluf_(v[r]);
             } else if (g.act == CFM_ACT_DSILU) {               // d silu(z)/dz = s (1 + z (1 - s)), s = sigmoid(z)
                 if (g.drop.thresh) {                           // the gradient arrives at dropout(silu(z)): same mask as the forward's hidden
 #pragma unroll
@@ -531,7 +531,7 @@ __global__ __launch_bounds__(256, 2) void cfm_gemm_pers_kernel(const GemmArgs g)
                     for (int r = 0; r < 4; ++r) v[r] = siluf_(v[r]);
                 } else if (g.act == CFM_ACT_RELU) {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
+                    for (int r = 0; r < 4; ++r) v[r] = reluf_(v[r]);
                 }
                 if (row >= g.M) continue;
                 const int64_t o = (int64_t)row * g.ldc + col;

@@ -147,7 +147,7 @@ __global__ __launch_bounds__(512) void cfm_gemm256_kernel(const Gemm256Args g) {
                     for (int r = 0; r < 4; ++r) v[r] = siluf_(v[r]);
                 } else if (g.act == CFM_ACT_RELU) {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
+                    for (int r = 0; r < 4; ++r) v[r] = reluf_(v[r]);
                 }
                 if (row >= g.M) continue;
                 const int col = col0 + j * 16;
