@@ -24,7 +24,9 @@ _TORCH_DT = {F32: torch.float32, BF16: torch.bfloat16, F16: torch.float16}
 c_p = ctypes.c_void_p
 c_i64 = ctypes.c_int64
 c_i32 = ctypes.c_int32
+c_int = ctypes.c_int
 c_f = ctypes.c_float
+P = ctypes.POINTER
 
 
 class GemmDesc(ctypes.Structure):
@@ -181,6 +183,7 @@ class LnBwdDesc(ctypes.Structure):
 
 
 class LstmDesc(ctypes.Structure):
+    _c_fields_ = {"in_": "in"}              # Python field -> C member, where `in` cannot be spelled
     _fields_ = [("B", c_i32), ("U", c_i32), ("in_", c_i32), ("H", c_i32), ("layers", c_i32), ("drop_p", c_f), ("seed", ctypes.c_uint32), ("x", c_p),
                 ("w_ih", c_p * 4), ("w_hh", c_p * 4), ("b_ih", c_p * 4), ("b_hh", c_p * 4), ("h0", c_p), ("c0", c_p), ("y", c_p), ("hn", c_p), ("cn", c_p),
                 ("save", c_p * 4), ("dy", c_p), ("dhn", c_p), ("dcn", c_p), ("dx", c_p), ("dw_ih", c_p * 4), ("dw_hh", c_p * 4), ("db_ih", c_p * 4),
@@ -246,6 +249,110 @@ class LayerIO(ctypes.Structure):
 
 ROUTES = ("GENERAL", "FUSED_FFN", "CHAIN", "CHAIN_NEXT", "CHAIN_NEXT_CIN", "FFSPLIT", "PAIR")     # include/cfm.h cfm_route, by value (cfm_encoder_layer_route)
 
+# The whole binding: every mirror above gets the header's name for it as `_c_name_`, and PROTOTYPES is (name, restype, *argtypes) for every function
+# include/cfm.h declares, in the header's order; lib() applies it.  tests/abi_check.py has the compiler check each field and each prototype against the header.
+for _c_name, _cls in dict(
+        cfm_gemm_desc=GemmDesc, cfm_gemm_tn_desc=GemmTnDesc, cfm_attn_bwd_desc=AttnBwdDesc, cfm_attn_desc=AttnDesc, cfm_ffn_desc=FfnDesc, cfm_rowchain_desc=RowChainDesc,
+        cfm_layer_train_weights=LayerTrainWeights, cfm_train_group=TrainGroup, cfm_layer_train_io=LayerTrainIO, cfm_layer_train_saved=LayerTrainSaved,
+        cfm_layer_train_scratch=LayerTrainScratch, cfm_layer_train_grads=LayerTrainGrads, cfm_layer_weights=LayerWeights, cfm_ctc_group=CtcGroup,
+        cfm_rnnt_desc=RnntDesc, cfm_lattice=Lattice, cfm_rnnt_packed_desc=RnntPackedDesc, cfm_ln_bwd_desc=LnBwdDesc, cfm_lstm_desc=LstmDesc, cfm_greedy_desc=GreedyDesc,
+        cfm_greedy_chunk_desc=GreedyChunkDesc, cfm_ctc_greedy_desc=CtcGreedyDesc, cfm_ctc_beam_desc=CtcBeamDesc, cfm_fbank_desc=FbankDesc,
+        cfm_ffn_split_desc=FfnSplitDesc, cfm_layer_scratch=LayerScratch, cfm_layer_io=LayerIO).items():
+    _cls._c_name_ = _c_name
+PROTOTYPES = (
+    ("cfm_version", c_int),
+    ("cfm_last_error", ctypes.c_char_p),
+    ("cfm_device_ok", c_int),
+    ("cfm_gemm", c_int, P(GemmDesc), c_p),
+    ("cfm_gemm_tn", c_int, P(GemmTnDesc), c_p),
+    ("cfm_gemm_tn_group", c_int, P(GemmTnDesc), c_i32, c_p),
+    ("cfm_ffn_fused", c_int, P(FfnDesc), c_p),
+    ("cfm_rowchain", c_int, P(RowChainDesc), c_p),
+    ("cfm_rowchain_supported", c_int, c_i32, c_i32),
+    ("cfm_rowchain_dw_supported", c_int, c_i32),
+    ("cfm_rowchain_pair_supported", c_int, c_i32, c_i32),
+    ("cfm_layernorm", c_int, c_p, c_p, c_p, c_p, c_i32, c_p, c_p, c_p, c_i32, c_p, c_f, c_i64, c_i32, c_p),
+    ("cfm_attention", c_int, P(AttnDesc), c_p),
+    ("cfm_attention_group", c_int, P(AttnDesc), c_i32, c_p),
+    ("cfm_kv_cache_pack", c_int, c_p, c_i32, c_p, c_p, c_i32, c_i64, c_i64, c_i64, c_i64, c_p, c_i32, c_i32, c_i32, c_i32, c_p),
+    ("cfm_dwconv_bn_silu", c_int, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p),
+    ("cfm_conv1_relu", c_int, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p),
+    ("cfm_conv1_relu_mma", c_int, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p),
+    ("cfm_conv12_supported", c_int, c_i32, c_i32),
+    ("cfm_conv12_relu", c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p),
+    ("cfm_conv12_plan", c_int, c_i64, c_i32, c_i32, P(c_i32), P(c_i32)),
+    ("cfm_set_conv12_tile", c_i32, c_i32),
+    ("cfm_valid_mask", c_int, c_p, c_i32, c_p, c_i32, c_i32, c_i32, c_i32, c_p),
+    ("cfm_chunk_mask", c_int, c_p, c_i32, c_i32, c_i32, c_p),
+    ("cfm_attn_mask", c_int, c_p, c_p, c_p, c_i32, c_i32, c_p),
+    ("cfm_stream_prep", c_int, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p, c_i32, c_i32, c_p, c_p, c_p, c_p),
+    ("cfm_kv_ring_write", c_int, c_p, c_p, c_i32, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p),
+    ("cfm_stream_advance", c_int, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p),
+    ("cfm_dwconv_causal_bn_silu", c_int, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p),
+    ("cfm_conv_cache_update", c_int, c_p, c_i32, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p),
+    ("cfm_cast", c_int, c_p, c_i32, c_p, c_i32, c_i64, c_p),
+    ("cfm_add_rows", c_int, c_p, c_p, c_i64, c_i32, c_i32, c_p),
+    ("cfm_encoder_layer_forward", c_int, P(LayerWeights), P(LayerScratch), P(LayerIO), c_p, c_p, c_i32, c_p, c_p, c_p),
+    ("cfm_encoder_layer_route", c_i32, P(LayerWeights), P(LayerScratch), P(LayerIO), c_p, c_p),
+    ("cfm_ffsplit_max_rows", c_i32),
+    ("cfm_ctc_nll", c_int, c_p, c_i64, c_i32, c_i32, c_i32, c_p, c_p, c_i32, c_p, c_p, c_p, c_p),
+    ("cfm_joint_act", c_int, c_p, c_i64, c_p, c_i64, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p),
+    ("cfm_rnnt_nll", c_int, P(RnntDesc), c_p),
+    ("cfm_rnnt_grad", c_int, P(RnntDesc), c_p),
+    ("cfm_joint_act_bwd_ws", c_i64, c_i32, c_i32, c_i32, c_i32),
+    ("cfm_joint_act_bwd", c_int, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p),
+    ("cfm_joint_act_packed", c_int, c_p, c_i64, c_p, c_i64, c_p, c_i32, P(Lattice), c_i32, c_p),
+    ("cfm_joint_act_packed_bwd", c_int, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, P(Lattice), c_i32, c_p),
+    ("cfm_rnnt_packed_nll", c_int, P(RnntPackedDesc), c_p),
+    ("cfm_rnnt_packed_grad", c_int, P(RnntPackedDesc), c_p),
+    ("cfm_layernorm_bwd_ws", c_i64, c_i64, c_i32),
+    ("cfm_layernorm_bwd_fused", c_int, P(LnBwdDesc), c_p),
+    ("cfm_layernorm_bwd", c_int, c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_i64, c_i32, c_p),
+    ("cfm_glu_bwd", c_int, c_p, c_i32, c_p, c_i32, c_p, c_i32, c_i64, c_i32, c_p),
+    ("cfm_dwconv_bn_ws", c_i64, c_i32, c_i32, c_i32),
+    ("cfm_dwconv_bn_train", c_int, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_i32, c_p, c_i32, c_i32, c_i32, c_i32, c_p),
+    ("cfm_dwconv_bn_train_bwd", c_int, c_p, c_i32, c_p, c_p, c_p, c_i32, c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p),
+    ("cfm_dwconv_bn_train_bwd_acc", c_int, c_p, c_i32, c_p, c_p, c_p, c_i32, c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p),
+    ("cfm_dwconv_bn_train_groups", c_int, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_i32, c_p, P(TrainGroup), c_i32, c_i32, c_i32, c_p),
+    ("cfm_dwconv_bn_train_bwd_groups", c_int, c_p, c_i32, c_p, c_p, c_p, c_i32, c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, P(TrainGroup), c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p),
+    ("cfm_col2im_relu_bwd", c_int, c_p, c_i32, c_p, c_i32, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p),
+    ("cfm_conv1_wgrad_ws", c_i64, c_i32, c_i32, c_i32),
+    ("cfm_conv1_wgrad", c_int, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p),
+    ("cfm_attention_bwd", c_int, P(AttnBwdDesc), c_p),
+    ("cfm_attention_bwd_group", c_int, P(AttnBwdDesc), c_i32, c_p),
+    ("cfm_attention_bwd_force_general", None, c_i32),
+    ("cfm_set_cin_merge", c_i32, c_i32),
+    ("cfm_ffn_split", c_int, P(FfnSplitDesc), c_p),
+    ("cfm_ffn_split_supported", c_int, c_i32, c_i32),
+    ("cfm_ctc_nll_train_groups", c_int, P(CtcGroup), c_i32, c_i32, c_p),
+    ("cfm_ctc_grad", c_int, c_p, c_i64, c_i32, c_i32, c_i32, c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p),
+    ("cfm_dropout_rows", c_int, c_p, c_i32, c_p, c_i32, c_p, c_f, c_f, ctypes.c_uint32, c_f, ctypes.c_uint32, c_i64, c_i32, c_p),
+    ("cfm_dropout_mask", c_int, c_p, c_i64, c_f, ctypes.c_uint32, c_p),
+    ("cfm_pack_matrices", c_int, c_p, c_i32, c_i64, c_i32, c_i32, c_p),
+    ("cfm_pack_vectors", c_int, c_p, c_p, c_p, c_i64, c_p),
+    ("cfm_encoder_train_forward", c_int, c_i32, P(LayerTrainWeights), P(LayerTrainIO), P(LayerTrainSaved), P(LayerTrainScratch), P(c_p), c_p),
+    ("cfm_encoder_train_backward", c_int, c_i32, P(LayerTrainWeights), P(LayerTrainIO), P(LayerTrainSaved), P(LayerTrainScratch), P(LayerTrainGrads), P(c_p), c_p, c_p, c_p, LAYER_DONE_FN, c_p, P(c_p), c_p),
+    ("cfm_adam_step", c_int, c_p, c_p, c_p, c_p, c_i64, c_f, c_f, c_f, c_f, c_f, c_i64, c_p, c_p),
+    ("cfm_sumsq", c_int, c_p, c_i64, c_p, c_i32, c_p, c_p),
+    ("cfm_adam_clip_step", c_int, c_p, c_p, c_p, c_p, c_i64, c_f, c_f, c_f, c_f, c_f, c_i64, c_p, c_f, c_f, c_i32, c_p, c_p),
+    ("cfm_prof_enable", None, c_i32),
+    ("cfm_prof_reset", None),
+    ("cfm_prof_collect", c_int),
+    ("cfm_prof_entry", c_int, c_i32, ctypes.c_char_p, c_i32, P(c_i64), P(ctypes.c_double), P(ctypes.c_double), P(ctypes.c_double)),
+    ("cfm_greedy_step", c_int, P(GreedyDesc), c_p),
+    ("cfm_greedy_chunk_begin", c_int, P(GreedyChunkDesc), c_p),
+    ("cfm_greedy_chunk_step", c_int, P(GreedyChunkDesc), c_p),
+    ("cfm_fbank", c_int, P(FbankDesc), c_p),
+    ("cfm_fbank_stream", c_int, P(FbankDesc), c_p),
+    ("cfm_lstm_save_floats", c_i64, c_i32, c_i32, c_i32),
+    ("cfm_lstm_forward", c_int, P(LstmDesc), c_p),
+    ("cfm_lstm_backward", c_int, P(LstmDesc), c_p),
+    ("cfm_ctc_topk", c_int, c_p, c_i64, c_i32, c_i32, c_i32, c_p, c_i32, c_p, c_p, c_p, c_p),
+    ("cfm_ctc_greedy", c_int, P(CtcGreedyDesc), c_p),
+    ("cfm_ctc_beam_nodes", c_i64, c_i32, c_i32, c_i32),
+    ("cfm_ctc_prefix_beam", c_int, P(CtcBeamDesc), c_p),
+)
+
 _lib = None
 _lock = threading.Lock()
 
@@ -263,122 +370,9 @@ def lib():
                 "libconformer_gfx950.so not found at %s -- build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "or `make -C conformer-pytorch-lightning_amd/csrc`. There is no CPU fallback." % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
-        L.cfm_version.restype = ctypes.c_int
-        L.cfm_last_error.restype = ctypes.c_char_p
-        L.cfm_device_ok.restype = ctypes.c_int
-        L.cfm_gemm.argtypes = [ctypes.POINTER(GemmDesc), c_p]
-        L.cfm_attention.argtypes = [ctypes.POINTER(AttnDesc), c_p]
-        L.cfm_attention_group.argtypes = [ctypes.POINTER(AttnDesc), c_i32, c_p]
-        L.cfm_ffn_fused.argtypes = [ctypes.POINTER(FfnDesc), c_p]
-        L.cfm_rowchain.argtypes = [ctypes.POINTER(RowChainDesc), c_p]
-        L.cfm_rowchain_supported.argtypes = [c_i32, c_i32]
-        L.cfm_rowchain_pair_supported.argtypes = [c_i32, c_i32]
-        L.cfm_layernorm.argtypes = [c_p, c_p, c_p, c_p, c_i32, c_p, c_p, c_p, c_i32, c_p, ctypes.c_float, c_i64, c_i32, c_p]
-        L.cfm_kv_cache_pack.argtypes = [c_p, c_i32, c_p, c_p, c_i32, c_i64, c_i64, c_i64, c_i64, c_p, c_i32, c_i32, c_i32, c_i32, c_p]
-        L.cfm_dwconv_bn_silu.argtypes = [c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p]
-        L.cfm_conv1_relu.argtypes = [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p]
-        L.cfm_conv1_relu_mma.argtypes = [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p]
-        L.cfm_conv12_supported.argtypes = [c_i32, c_i32]
-        L.cfm_pack_matrices.argtypes = [c_p, c_i32, c_i64, c_i32, c_i32, c_p]
-        L.cfm_pack_vectors.argtypes = [c_p, c_p, c_p, c_i64, c_p]
-        L.cfm_greedy_step.argtypes = [ctypes.POINTER(GreedyDesc), c_p]
-        L.cfm_greedy_chunk_begin.argtypes = [ctypes.POINTER(GreedyChunkDesc), c_p]
-        L.cfm_greedy_chunk_step.argtypes = [ctypes.POINTER(GreedyChunkDesc), c_p]
-        L.cfm_fbank.argtypes = [ctypes.POINTER(FbankDesc), c_p]
-        L.cfm_ctc_topk.argtypes = [c_p, c_i64, c_i32, c_i32, c_i32, c_p, c_i32, c_p, c_p, c_p, c_p]
-        L.cfm_ctc_greedy.argtypes = [ctypes.POINTER(CtcGreedyDesc), c_p]
-        L.cfm_ctc_prefix_beam.argtypes = [ctypes.POINTER(CtcBeamDesc), c_p]
-        L.cfm_ctc_topk.restype = L.cfm_ctc_greedy.restype = L.cfm_ctc_prefix_beam.restype = ctypes.c_int
-        L.cfm_ctc_beam_nodes.argtypes = [c_i32, c_i32, c_i32]
-        L.cfm_ctc_beam_nodes.restype = c_i64
-        L.cfm_lstm_forward.argtypes = [ctypes.POINTER(LstmDesc), c_p]
-        L.cfm_lstm_backward.argtypes = [ctypes.POINTER(LstmDesc), c_p]
-        L.cfm_lstm_forward.restype = L.cfm_lstm_backward.restype = ctypes.c_int
-        L.cfm_lstm_save_floats.argtypes = [c_i32, c_i32, c_i32]
-        L.cfm_lstm_save_floats.restype = c_i64
-        L.cfm_fbank_stream.argtypes = [ctypes.POINTER(FbankDesc), c_p]
-        L.cfm_ffn_split.argtypes = [ctypes.POINTER(FfnSplitDesc), c_p]
-        L.cfm_ffn_split_supported.argtypes = [c_i32, c_i32]
-        L.cfm_attention_bwd_force_general.argtypes = [c_i32]
-        L.cfm_attention_bwd_force_general.restype = None
-        L.cfm_set_cin_merge.argtypes = [c_i32]
-        L.cfm_set_cin_merge.restype = c_i32
-        L.cfm_set_conv12_tile.argtypes = [c_i32]
-        L.cfm_set_conv12_tile.restype = c_i32
-        L.cfm_conv12_plan.argtypes = [c_i64, c_i32, c_i32, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32)]
-        L.cfm_dwconv_bn_train_bwd_acc.argtypes = [c_p, c_i32, c_p, c_p, c_p, c_i32, c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p]
-        L.cfm_layernorm_bwd_fused.argtypes = [ctypes.POINTER(LnBwdDesc), c_p]
-        L.cfm_conv12_relu.argtypes = [c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p]
-        L.cfm_valid_mask.argtypes = [c_p, c_i32, c_p, c_i32, c_i32, c_i32, c_i32, c_p]
-        L.cfm_chunk_mask.argtypes = [c_p, c_i32, c_i32, c_i32, c_p]
-        L.cfm_attn_mask.argtypes = [c_p, c_p, c_p, c_i32, c_i32, c_p]
-        L.cfm_cast.argtypes = [c_p, c_i32, c_p, c_i32, c_i64, c_p]
-        L.cfm_add_rows.argtypes = [c_p, c_p, c_i64, c_i32, c_i32, c_p]
-        L.cfm_encoder_layer_forward.argtypes = [ctypes.POINTER(LayerWeights), ctypes.POINTER(LayerScratch),
-                                                ctypes.POINTER(LayerIO), c_p, c_p, c_i32, c_p, c_p, c_p]
-        L.cfm_encoder_layer_route.argtypes = [ctypes.POINTER(LayerWeights), ctypes.POINTER(LayerScratch), ctypes.POINTER(LayerIO), c_p, c_p]
-        L.cfm_encoder_layer_route.restype = c_i32
-        L.cfm_ffsplit_max_rows.restype = c_i32
-        L.cfm_ctc_nll.argtypes = [c_p, c_i64, c_i32, c_i32, c_i32, c_p, c_p, c_i32, c_p, c_p, c_p, c_p]
-        L.cfm_joint_act.argtypes = [c_p, c_i64, c_p, c_i64, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p]
-        L.cfm_joint_act_bwd.argtypes = [c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p]
-        L.cfm_joint_act_bwd_ws.argtypes = [c_i32, c_i32, c_i32, c_i32]
-        L.cfm_rnnt_nll.argtypes = [ctypes.POINTER(RnntDesc), c_p]
-        L.cfm_rnnt_grad.argtypes = [ctypes.POINTER(RnntDesc), c_p]
-        L.cfm_rnnt_packed_nll.argtypes = [ctypes.POINTER(RnntPackedDesc), c_p]
-        L.cfm_rnnt_packed_grad.argtypes = [ctypes.POINTER(RnntPackedDesc), c_p]
-        L.cfm_joint_act_packed.argtypes = [c_p, c_i64, c_p, c_i64, c_p, c_i32, ctypes.POINTER(Lattice), c_i32, c_p]
-        L.cfm_joint_act_packed_bwd.argtypes = [c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, ctypes.POINTER(Lattice), c_i32, c_p]
-        c_f = ctypes.c_float
-        L.cfm_gemm_tn.argtypes = [ctypes.POINTER(GemmTnDesc), c_p]
-        L.cfm_gemm_tn_group.argtypes = [ctypes.POINTER(GemmTnDesc), c_i32, c_p]
-        L.cfm_attention_bwd.argtypes = [ctypes.POINTER(AttnBwdDesc), c_p]
-        L.cfm_attention_bwd_group.argtypes = [ctypes.POINTER(AttnBwdDesc), c_i32, c_p]
-        L.cfm_layernorm_bwd_ws.argtypes = [c_i64, c_i32]
-        L.cfm_layernorm_bwd.argtypes = [c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_i64, c_i32, c_p]
-        L.cfm_glu_bwd.argtypes = [c_p, c_i32, c_p, c_i32, c_p, c_i32, c_i64, c_i32, c_p]
-        L.cfm_dwconv_bn_ws.argtypes = [c_i32, c_i32, c_i32]
-        L.cfm_dwconv_bn_train.argtypes = [c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_i32, c_p, c_i32, c_i32, c_i32, c_i32, c_p]
-        L.cfm_dwconv_bn_train_bwd.argtypes = [c_p, c_i32, c_p, c_p, c_p, c_i32, c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p]
-        L.cfm_dwconv_bn_train_groups.argtypes = [c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_i32, c_p, ctypes.POINTER(TrainGroup), c_i32, c_i32, c_i32, c_p]
-        L.cfm_dwconv_bn_train_bwd_groups.argtypes = [c_p, c_i32, c_p, c_p, c_p, c_i32, c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.POINTER(TrainGroup), c_i32, c_i32, c_i32,
-                                                     c_i32, c_p, c_p, c_p]
-        L.cfm_col2im_relu_bwd.argtypes = [c_p, c_i32, c_p, c_i32, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p]
-        L.cfm_conv1_wgrad_ws.argtypes = [c_i32, c_i32, c_i32]
-        L.cfm_conv1_wgrad.argtypes = [c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p]
-        L.cfm_ctc_nll_train_groups.argtypes = [ctypes.POINTER(CtcGroup), c_i32, c_i32, c_p]
-        L.cfm_ctc_grad.argtypes = [c_p, c_i64, c_i32, c_i32, c_i32, c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p]
-        L.cfm_adam_step.argtypes = [c_p, c_p, c_p, c_p, c_i64, c_f, c_f, c_f, c_f, c_f, c_i64, c_p, c_p]
-        L.cfm_sumsq.argtypes = [c_p, c_i64, c_p, c_i32, c_p, c_p]
-        L.cfm_adam_clip_step.argtypes = [c_p, c_p, c_p, c_p, c_i64, c_f, c_f, c_f, c_f, c_f, c_i64, c_p, c_f, c_f, c_i32, c_p, c_p]
-        L.cfm_dropout_rows.argtypes = [c_p, c_i32, c_p, c_i32, c_p, c_f, c_f, ctypes.c_uint32, c_f, ctypes.c_uint32, c_i64, c_i32, c_p]
-        L.cfm_dropout_mask.argtypes = [c_p, c_i64, c_f, ctypes.c_uint32, c_p]
-        L.cfm_encoder_train_forward.argtypes = [c_i32, ctypes.POINTER(LayerTrainWeights), ctypes.POINTER(LayerTrainIO), ctypes.POINTER(LayerTrainSaved),
-                                                ctypes.POINTER(LayerTrainScratch), ctypes.POINTER(c_p), c_p]
-        L.cfm_encoder_train_backward.argtypes = [c_i32, ctypes.POINTER(LayerTrainWeights), ctypes.POINTER(LayerTrainIO), ctypes.POINTER(LayerTrainSaved),
-                                                 ctypes.POINTER(LayerTrainScratch), ctypes.POINTER(LayerTrainGrads), ctypes.POINTER(c_p), c_p, c_p, c_p,
-                                                 LAYER_DONE_FN, c_p, ctypes.POINTER(c_p), c_p]
-        L.cfm_stream_prep.argtypes = [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p, c_i32, c_i32, c_p, c_p, c_p, c_p]
-        L.cfm_kv_ring_write.argtypes = [c_p, c_p, c_i32, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p]
-        L.cfm_stream_advance.argtypes = [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p]
-        L.cfm_dwconv_causal_bn_silu.argtypes = [c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p]
-        L.cfm_conv_cache_update.argtypes = [c_p, c_i32, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p]
-        for name in ("cfm_layernorm_bwd_ws", "cfm_dwconv_bn_ws", "cfm_conv1_wgrad_ws", "cfm_joint_act_bwd_ws"):
-            getattr(L, name).restype = c_i64
-        L.cfm_prof_enable.argtypes = [c_i32]
-        L.cfm_prof_enable.restype = None
-        L.cfm_prof_reset.restype = None
-        L.cfm_prof_collect.restype = ctypes.c_int
-        L.cfm_prof_entry.argtypes = [c_i32, ctypes.c_char_p, c_i32, ctypes.POINTER(c_i64), ctypes.POINTER(ctypes.c_double),
-                                     ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
-        for name in ("cfm_gemm", "cfm_ffn_fused", "cfm_rowchain", "cfm_rowchain_supported", "cfm_attention", "cfm_layernorm", "cfm_kv_cache_pack", "cfm_dwconv_bn_silu", "cfm_conv1_relu", "cfm_conv1_relu_mma", "cfm_conv12_relu", "cfm_conv12_supported",
-                     "cfm_valid_mask", "cfm_chunk_mask", "cfm_attn_mask", "cfm_cast", "cfm_add_rows",
-                     "cfm_encoder_layer_forward", "cfm_ctc_nll", "cfm_joint_act", "cfm_joint_act_bwd", "cfm_rnnt_nll", "cfm_rnnt_grad", "cfm_prof_entry", "cfm_gemm_tn", "cfm_gemm_tn_group", "cfm_attention_bwd",
-                     "cfm_layernorm_bwd", "cfm_glu_bwd", "cfm_dwconv_bn_train", "cfm_dwconv_bn_train_bwd", "cfm_col2im_relu_bwd", "cfm_conv1_wgrad",
-                     "cfm_ctc_nll_train_groups", "cfm_ctc_grad", "cfm_adam_step", "cfm_adam_clip_step", "cfm_sumsq", "cfm_dropout_rows", "cfm_dropout_mask", "cfm_pack_matrices", "cfm_pack_vectors", "cfm_greedy_step", "cfm_greedy_chunk_begin", "cfm_greedy_chunk_step", "cfm_fbank", "cfm_fbank_stream", "cfm_ffn_split", "cfm_ffn_split_supported", "cfm_layernorm_bwd_fused", "cfm_dwconv_bn_train_bwd_acc",
-                     "cfm_attention_group", "cfm_attention_bwd_group", "cfm_dwconv_bn_train_groups", "cfm_dwconv_bn_train_bwd_groups",
-                     "cfm_encoder_train_forward", "cfm_encoder_train_backward", "cfm_stream_prep", "cfm_kv_ring_write", "cfm_stream_advance", "cfm_dwconv_causal_bn_silu", "cfm_conv_cache_update"):
-            getattr(L, name).restype = ctypes.c_int
+        for name, restype, *argtypes in PROTOTYPES:
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = L
     return _lib
 
@@ -413,6 +407,11 @@ def ptr(t):
 
 def stream():
     return torch.cuda.current_stream().cuda_stream
+
+
+def call(name, *args):
+    """Launch the status-returning entry point `name`(*args, current stream); a non-zero status raises with cfm_last_error()."""
+    check(getattr(lib(), name)(*args, stream()), name)
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -567,7 +567,7 @@ def _train_forward(ctx, x, owner, layers, prec, groups, keep, flat, w_arr, pks, 
     ws = sum(cfm.lib().cfm_dwconv_bn_ws(B, T, D) for B, T, _, _ in groups)
     sc = cfm.LayerTrainScratch()
     sc.dwbn_ws = cfm.scratch("dwbn", ws, torch.float32, dev).data_ptr()
-    cfm.check(cfm.lib().cfm_encoder_train_forward(L, w_arr, ctypes.byref(io), sv, ctypes.byref(sc), xs, cfm.stream()), "cfm_encoder_train_forward")
+    cfm.call("cfm_encoder_train_forward", L, w_arr, ctypes.byref(io), sv, ctypes.byref(sc), xs)
     if l0.conv_module.norm.track_running_stats:
         torch._foreach_add_([l.conv_module.norm.num_batches_tracked for l in layers], G)
     # held: what the structs point to -- the backward reads the saves, the input rows, the masks of the groups and the pad mask
@@ -624,8 +624,8 @@ def _train_backward(ctx, dy, use_sinks):
 
     cb = cfm.LAYER_DONE_FN(done)
     out = ctypes.c_void_p()
-    cfm.check(cfm.lib().cfm_encoder_train_backward(L, w_arr, ctypes.byref(io), sv, ctypes.byref(sc), g_arr, xs, dyc.data_ptr(), bufs[0].data_ptr(),
-                                                   bufs[1].data_ptr(), cb, None, ctypes.byref(out), cfm.stream()), "cfm_encoder_train_backward")
+    cfm.call("cfm_encoder_train_backward", L, w_arr, ctypes.byref(io), sv, ctypes.byref(sc), g_arr, xs, dyc.data_ptr(), bufs[0].data_ptr(),
+             bufs[1].data_ptr(), cb, None, ctypes.byref(out))
     if failed:
         raise failed[0]
     dx = bufs[0] if out.value == bufs[0].data_ptr() else bufs[1]

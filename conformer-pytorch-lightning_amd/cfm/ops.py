@@ -138,7 +138,7 @@ def gemm(a, w, bias=None, w_lo=None, out=None, out_dtype=None, act=_c.ACT_NONE, 
     d.M, d.N, d.K = M, N, K
     d.a_dtype, d.w_dtype, d.c_dtype = _c.dt_code(a), _c.dt_code(w), _c.dt_code(out)
     d.act, d.alpha, d.tile, d.mask_mode = act, alpha, tile, mask_mode
-    _c.check(_c.lib().cfm_gemm(ctypes.byref(d), _c.stream()), "cfm_gemm")
+    _c.call("cfm_gemm", ctypes.byref(d))
     return out
 
 
@@ -173,7 +173,7 @@ def ffn_fused(x, w1f, w2f, b1, b2, FF, act=_c.ACT_SILU, ln=None, alpha=1.0, add_
     d.w_dtype = _c.dt_code(w1f)
     d.out16_dtype = _c.dt_code(out16) if out16 is not None else 0
     d.act, d.add_x, d.alpha, d.eps = act, 1 if add_x else 0, alpha, eps
-    _c.check(_c.lib().cfm_ffn_fused(ctypes.byref(d), _c.stream()), "cfm_ffn_fused")
+    _c.call("cfm_ffn_fused", ctypes.byref(d))
     return out_f32, out16
 
 
@@ -225,7 +225,7 @@ def ffn_split(x, w_code, mode, psum=None, psum_b2=None, psum_alpha=1.0, ln1=None
         if len(ring) > 3 and ring[3] is not None:
             _stream_lens("ffn_split", offs.numel(), ring_len=ring[3])
             d.ring_len = ring[3].data_ptr()
-    _c.check(_c.lib().cfm_ffn_split(ctypes.byref(d), _c.stream()), "cfm_ffn_split")
+    _c.call("cfm_ffn_split", ctypes.byref(d))
 
 
 def rowchain(M, D, w_code, x=None, head=None, ln=None, ln_mask=None, ffn=None, alpha=1.0, ln1=None, ln2=None, out_f32=None, out16=None,
@@ -265,7 +265,7 @@ def rowchain(M, D, w_code, x=None, head=None, ln=None, ln_mask=None, ffn=None, a
         d.dw_w, d.dw_b, d.dw_scale, d.dw_shift, d.dw_T, d.dw_K = _c.ptr(dw[0]), _c.ptr(dw[1]), _c.ptr(dw[2]), _c.ptr(dw[3]), dw[4], dw[0].shape[1]
     _c.require_hip(x, out_f32, out16)
     d.M, d.D, d.w_dtype, d.alpha, d.eps = M, D, w_code, alpha, eps
-    _c.check(_c.lib().cfm_rowchain(ctypes.byref(d), _c.stream()), "cfm_rowchain")
+    _c.call("cfm_rowchain", ctypes.byref(d))
 
 
 def layernorm(x, g1, b1, out1=None, out1_dtype=None, g2=None, b2=None, out2=None, out2_dtype=None, row_mask=None, eps=1e-5,
@@ -284,9 +284,9 @@ def layernorm(x, g1, b1, out1=None, out1_dtype=None, g2=None, b2=None, out2=None
     for o in (out1, out2):
         if o is not None and (tuple(o.shape) != (M, D) or not o.is_contiguous()):
             raise ValueError("cfm.layernorm: outputs must be contiguous [M,D]")
-    _c.check(_c.lib().cfm_layernorm(_c.ptr(x), _c.ptr(g1), _c.ptr(b1), _c.ptr(out1), _c.dt_code(out1) if out1 is not None else 0,
-                                    _c.ptr(g2), _c.ptr(b2), _c.ptr(out2), _c.dt_code(out2) if out2 is not None else 0,
-                                    _c.ptr(row_mask), eps, M, D, _c.stream()), "cfm_layernorm")
+    _c.call("cfm_layernorm", _c.ptr(x), _c.ptr(g1), _c.ptr(b1), _c.ptr(out1), _c.dt_code(out1) if out1 is not None else 0,
+            _c.ptr(g2), _c.ptr(b2), _c.ptr(out2), _c.dt_code(out2) if out2 is not None else 0,
+            _c.ptr(row_mask), eps, M, D)
     return out1, out2
 
 
@@ -336,7 +336,7 @@ def attention(q, k, v, B, H, Tq, Tk, dk, q_str, k_str, v_str, out, p=None, p_str
     d = _c.AttnDesc()
     _attn_fill(d, "attention", q, k, v, B, H, Tq, Tk, dk, q_str, k_str, v_str, out, p=p, p_str=p_str, bias_u=bias_u, bias_v=bias_v, mask=mask,
                mask_str=mask_str, mma_code=mma_code, split=split, scale=scale, lse=lse, drop=drop)
-    _c.check(_c.lib().cfm_attention(ctypes.byref(d), _c.stream()), "cfm_attention")
+    _c.call("cfm_attention", ctypes.byref(d))
     return out
 
 
@@ -349,7 +349,7 @@ def attention_group(problems):
     arr = (_c.AttnDesc * n)()
     for d, kw in zip(arr, problems):
         _attn_fill(d, "attention_group", **kw)
-    _c.check(_c.lib().cfm_attention_group(arr, n, _c.stream()), "cfm_attention_group")
+    _c.call("cfm_attention_group", arr, n)
     return [kw["out"] for kw in problems]
 
 
@@ -366,8 +366,8 @@ def kv_cache_pack(old_cache, k, v, k_str, v_str, B, H, Tn, dk):
     if k.dtype != v.dtype:
         raise ValueError("cfm.kv_cache_pack: k and v must share one dtype")
     out = torch.empty((B, H, Tc + Tn, 2 * dk), dtype=torch.float32, device=k.device)
-    _c.check(_c.lib().cfm_kv_cache_pack(_c.ptr(old_cache), Tc, _c.ptr(k), _c.ptr(v), _c.dt_code(k), k_str[0], k_str[1], v_str[0],
-                                        v_str[1], _c.ptr(out), B, H, Tn, dk, _c.stream()), "cfm_kv_cache_pack")
+    _c.call("cfm_kv_cache_pack", _c.ptr(old_cache), Tc, _c.ptr(k), _c.ptr(v), _c.dt_code(k), k_str[0], k_str[1], v_str[0],
+            v_str[1], _c.ptr(out), B, H, Tn, dk)
     return out
 
 
@@ -382,8 +382,8 @@ def dwconv_bn_silu(x, w, dw_bias, bn_scale, bn_shift, out=None, out_dtype=None):
         out = torch.empty((B, T, D), dtype=out_dtype or x.dtype, device=x.device)
     elif out.numel() != B * T * D:
         raise ValueError("cfm.dwconv_bn_silu: out must hold [B,T,D]")
-    _c.check(_c.lib().cfm_dwconv_bn_silu(_c.ptr(x), _c.dt_code(x), _c.ptr(w), _c.ptr(dw_bias), _c.ptr(bn_scale), _c.ptr(bn_shift),
-                                         _c.ptr(out), _c.dt_code(out), B, T, D, w.shape[1], _c.stream()), "cfm_dwconv_bn_silu")
+    _c.call("cfm_dwconv_bn_silu", _c.ptr(x), _c.dt_code(x), _c.ptr(w), _c.ptr(dw_bias), _c.ptr(bn_scale), _c.ptr(bn_shift),
+            _c.ptr(out), _c.dt_code(out), B, T, D, w.shape[1])
     return out
 
 
@@ -412,9 +412,8 @@ def conv1_relu(x, w9c, bias, out_dtype, cmvn=None, mma=False):
         raise ValueError("cfm.conv1_relu: w9c must be float32 [9,C] (tap-major) and bias float32 [C]")
     T1, F1 = (T - 3) // 2 + 1, (F - 3) // 2 + 1
     out = torch.empty((B, T1, F1, C), dtype=out_dtype, device=x.device)
-    fn = _c.lib().cfm_conv1_relu_mma if mma else _c.lib().cfm_conv1_relu
-    _c.check(fn(_c.ptr(x), _c.ptr(w9c), _c.ptr(bias), _c.ptr(out), _c.dt_code(out), B, T, F, C, _c.ptr(mean), _c.ptr(istd), _c.stream()),
-             "cfm_conv1_relu_mma" if mma else "cfm_conv1_relu")
+    _c.call("cfm_conv1_relu_mma" if mma else "cfm_conv1_relu",
+            _c.ptr(x), _c.ptr(w9c), _c.ptr(bias), _c.ptr(out), _c.dt_code(out), B, T, F, C, _c.ptr(mean), _c.ptr(istd))
     return out
 
 
@@ -445,8 +444,8 @@ def conv12_relu(x, w9c, b1, w2, b2, cmvn=None):
     T1, F1 = (T - 3) // 2 + 1, (F - 3) // 2 + 1
     T2, F2 = (T1 - 3) // 2 + 1, (F1 - 3) // 2 + 1
     out = torch.empty((B * T2 * F2, C), dtype=w2.dtype, device=x.device)
-    _c.check(_c.lib().cfm_conv12_relu(_c.ptr(x), _c.ptr(w9c), _c.ptr(b1), _c.ptr(w2), _c.ptr(b2), _c.ptr(out), _c.dt_code(out), B, T, F, C,
-                                      _c.ptr(mean), _c.ptr(istd), _c.stream()), "cfm_conv12_relu")
+    _c.call("cfm_conv12_relu", _c.ptr(x), _c.ptr(w9c), _c.ptr(b1), _c.ptr(w2), _c.ptr(b2), _c.ptr(out), _c.dt_code(out), B, T, F, C,
+            _c.ptr(mean), _c.ptr(istd))
     return out
 
 
@@ -464,8 +463,8 @@ def ctc_nll(logits, V, enc_lens, labels, label_lens):
         raise ValueError("cfm.ctc_nll: batch sizes differ")
     out = torch.empty((B,), dtype=torch.float32, device=logits.device)
     work = scratch("ctc_lp", B * T * (2 * labels.size(1) + 2), torch.float32, logits.device)
-    _c.check(_c.lib().cfm_ctc_nll(_c.ptr(logits), logits.stride(1), B, T, V, _c.ptr(enc_lens), _c.ptr(labels), labels.size(1), _c.ptr(label_lens),
-                                  _c.ptr(work), _c.ptr(out), _c.stream()), "cfm_ctc_nll")
+    _c.call("cfm_ctc_nll", _c.ptr(logits), logits.stride(1), B, T, V, _c.ptr(enc_lens), _c.ptr(labels), labels.size(1), _c.ptr(label_lens),
+            _c.ptr(work), _c.ptr(out))
     return out
 
 
@@ -489,7 +488,7 @@ def ctc_topk(logits, V, lens, k, out=None):
     _dense("ctc_topk", idx=idx, logp=logp, lse=lse)
     if (idx.dtype, logp.dtype, lse.dtype) != (torch.int32, torch.float32, torch.float32) or idx.numel() != B * T * k or logp.numel() != B * T * k or lse.numel() != B * T:
         raise ValueError("cfm.ctc_topk: out must be (int32 [B,T,k], float32 [B,T,k], float32 [B,T])")
-    _c.check(_c.lib().cfm_ctc_topk(_c.ptr(logits), logits.stride(1), B, T, V, _c.ptr(lens), k, _c.ptr(idx), _c.ptr(logp), _c.ptr(lse), _c.stream()), "cfm_ctc_topk")
+    _c.call("cfm_ctc_topk", _c.ptr(logits), logits.stride(1), B, T, V, _c.ptr(lens), k, _c.ptr(idx), _c.ptr(logp), _c.ptr(lse))
     return idx, logp, lse
 
 
@@ -532,7 +531,7 @@ def ctc_greedy(idx, logp, lens, V, blank=0, state=None, hyp_cap=None):
     d.hyp_ld = S["hyps"].size(1)
     d.hyp_cap = d.hyp_ld if hyp_cap is None else int(hyp_cap)
     d.B, d.T, d.V, d.blank = B, T, int(V), int(blank)
-    _c.check(_c.lib().cfm_ctc_greedy(ctypes.byref(d), _c.stream()), "cfm_ctc_greedy")
+    _c.call("cfm_ctc_greedy", ctypes.byref(d))
     return S
 
 
@@ -567,7 +566,7 @@ def ctc_prefix_beam(idx, logp, lens, V, beam=None, blank=0, out=None, nodes=None
     d.idx, d.logp, d.lens, d.nodes, d.n_nodes = _c.ptr(idx), _c.ptr(logp), _c.ptr(lens), _c.ptr(nodes), nodes.numel() // 2
     d.nbest_tokens, d.nbest_len, d.nbest_score = _c.ptr(tokens), _c.ptr(nlen), _c.ptr(score)
     d.B, d.T, d.V, d.k, d.beam, d.blank = B, T, int(V), k, beam, int(blank)
-    _c.check(_c.lib().cfm_ctc_prefix_beam(ctypes.byref(d), _c.stream()), "cfm_ctc_prefix_beam")
+    _c.call("cfm_ctc_prefix_beam", ctypes.byref(d))
     return tokens, nlen, score
 
 
@@ -580,8 +579,7 @@ def joint_act(enc, pred, B, T, U, out_dtype):
     if enc.dtype != torch.float32 or pred.dtype != torch.float32 or tuple(enc.shape) != (B * T, J) or tuple(pred.shape) != (B * U, J):
         raise ValueError("cfm.joint_act: enc must be f32 [%d,J] and pred f32 [%d,J], got %s %s" % (B * T, B * U, tuple(enc.shape), tuple(pred.shape)))
     out = torch.empty((B * T * U, J), dtype=out_dtype, device=enc.device)
-    _c.check(_c.lib().cfm_joint_act(_c.ptr(enc), enc.stride(0), _c.ptr(pred), pred.stride(0), _c.ptr(out), _c.dt_code(out), B, T, U, J,
-                                    _c.stream()), "cfm_joint_act")
+    _c.call("cfm_joint_act", _c.ptr(enc), enc.stride(0), _c.ptr(pred), pred.stride(0), _c.ptr(out), _c.dt_code(out), B, T, U, J)
     return out
 
 
@@ -593,15 +591,14 @@ def valid_mask(lengths, T, first=0, stride=1):
     lengths = lengths.contiguous()
     B = lengths.numel()
     out = torch.empty((B, T), dtype=torch.uint8, device=lengths.device)
-    _c.check(_c.lib().cfm_valid_mask(_c.ptr(lengths), 1 if lengths.dtype == torch.int64 else 0, _c.ptr(out), B, T, first, stride,
-                                     _c.stream()), "cfm_valid_mask")
+    _c.call("cfm_valid_mask", _c.ptr(lengths), 1 if lengths.dtype == torch.int64 else 0, _c.ptr(out), B, T, first, stride)
     return out.view(torch.bool)
 
 
 def chunk_mask(size, chunk, left, device):
     out = torch.empty((size, size), dtype=torch.uint8, device=device)
     _c.require_hip(out)
-    _c.check(_c.lib().cfm_chunk_mask(_c.ptr(out), size, chunk, left, _c.stream()), "cfm_chunk_mask")
+    _c.call("cfm_chunk_mask", _c.ptr(out), size, chunk, left)
     return out.view(torch.bool)
 
 
@@ -612,7 +609,7 @@ def attn_mask_combine(valid, chunk):
     _c.require_hip(v, c)
     B, T = v.shape
     out = torch.empty((B, T, T), dtype=torch.uint8, device=v.device)
-    _c.check(_c.lib().cfm_attn_mask(_c.ptr(v), _c.ptr(c), _c.ptr(out), B, T, _c.stream()), "cfm_attn_mask")
+    _c.call("cfm_attn_mask", _c.ptr(v), _c.ptr(c), _c.ptr(out), B, T)
     return out.view(torch.bool)
 
 
@@ -621,7 +618,7 @@ def cast(src, dtype):
     src = src.contiguous()
     out = torch.empty(src.shape, dtype=dtype, device=src.device)
     if src.numel():
-        _c.check(_c.lib().cfm_cast(_c.ptr(src), _c.dt_code(src), _c.ptr(out), _c.dt_code(out), src.numel(), _c.stream()), "cfm_cast")
+        _c.call("cfm_cast", _c.ptr(src), _c.dt_code(src), _c.ptr(out), _c.dt_code(out), src.numel())
     return out
 
 
@@ -632,7 +629,7 @@ def add_rows(x, add, group):
     _dense("add_rows", x=x, add=add)
     if x.dtype != torch.float32 or add.dtype != torch.float32 or add.dim() != 2 or add.shape[1] != D or add.shape[0] * group < rows:
         raise ValueError("cfm.add_rows: x f32 [rows,D] and add f32 [>= rows/group, D] expected, got %s %s" % (tuple(x.shape), tuple(add.shape)))
-    _c.check(_c.lib().cfm_add_rows(_c.ptr(x), _c.ptr(add), rows, D, group, _c.stream()), "cfm_add_rows")
+    _c.call("cfm_add_rows", _c.ptr(x), _c.ptr(add), rows, D, group)
     return x
 
 
@@ -713,7 +710,7 @@ def gemm_tn(a, b, out=None, want_colsum=False, row_mask=None, alpha=1.0, conv=No
     d.M, d.N, d.K = M, N, K
     d.a_dtype, d.b_dtype, d.mma_dtype = _c.dt_code(a), _c.dt_code(b), mma_code
     d.split, d.accumulate, d.splits, d.alpha = 1 if split else 0, 1 if accumulate else 0, (1 if _deterministic[0] else splits), alpha
-    _c.check(_c.lib().cfm_gemm_tn(ctypes.byref(d), _c.stream()), "cfm_gemm_tn")
+    _c.call("cfm_gemm_tn", ctypes.byref(d))
     return out, colsum
 
 
@@ -744,7 +741,7 @@ def gemm_tn_group(products, mma_code=_c.BF16, splits=0):
         if any(t is not None and (t.dtype != torch.int64 or t.numel() != d.N) for t in tabs.values()):
             raise ValueError("cfm.gemm_tn_group: row_off / colsum_off / colsum_off2 must be int64 [N]")
         d.row_off, d.colsum_off, d.colsum_off2 = _c.ptr(tabs["row_off"]), _c.ptr(tabs["colsum_off"]), _c.ptr(tabs["colsum_off2"])
-    _c.check(_c.lib().cfm_gemm_tn_group(descs, n, _c.stream()), "cfm_gemm_tn_group")
+    _c.call("cfm_gemm_tn_group", descs, n)
 
 
 def layernorm_bwd(x, dy, gamma, row_mask=None, dres=None, dx=None, eps=1e-5):
@@ -765,8 +762,8 @@ def layernorm_bwd(x, dy, gamma, row_mask=None, dres=None, dx=None, eps=1e-5):
     dg = torch.empty((D,), dtype=torch.float32, device=x.device)
     db = torch.empty((D,), dtype=torch.float32, device=x.device)
     ws = scratch("ln_bwd", _c.lib().cfm_layernorm_bwd_ws(M, D), torch.float32, x.device)
-    _c.check(_c.lib().cfm_layernorm_bwd(_c.ptr(x), _c.ptr(dy), _c.dt_code(dy), _c.ptr(gamma), _c.ptr(row_mask), _c.ptr(dres), _c.ptr(dx), _c.ptr(dg),
-                                        _c.ptr(db), _c.ptr(ws), eps, M, D, _c.stream()), "cfm_layernorm_bwd")
+    _c.call("cfm_layernorm_bwd", _c.ptr(x), _c.ptr(dy), _c.dt_code(dy), _c.ptr(gamma), _c.ptr(row_mask), _c.ptr(dres), _c.ptr(dx), _c.ptr(dg),
+            _c.ptr(db), _c.ptr(ws), eps, M, D)
     return dx, dg, db
 
 
@@ -778,7 +775,7 @@ def glu_bwd(u, dg, out_dtype):
     if not u.is_contiguous() or not dg.is_contiguous() or tuple(dg.shape) != (M, D):
         raise ValueError("cfm.glu_bwd: u must be contiguous [M,2D] and dg contiguous [M,D]")
     du = torch.empty((M, D2), dtype=out_dtype, device=u.device)
-    _c.check(_c.lib().cfm_glu_bwd(_c.ptr(u), _c.dt_code(u), _c.ptr(dg), _c.dt_code(dg), _c.ptr(du), _c.dt_code(du), M, D, _c.stream()), "cfm_glu_bwd")
+    _c.call("cfm_glu_bwd", _c.ptr(u), _c.dt_code(u), _c.ptr(dg), _c.dt_code(dg), _c.ptr(du), _c.dt_code(du), M, D)
     return du
 
 
@@ -798,9 +795,8 @@ def dwconv_bn_train(g, w, dw_bias, gamma, beta, running_mean, running_var, momen
     stats = torch.empty((4, D), dtype=torch.float32, device=g.device)
     s = torch.empty((B, T, D), dtype=s_dtype, device=g.device)
     ws = scratch("dwbn", _c.lib().cfm_dwconv_bn_ws(B, T, D), torch.float32, g.device)
-    _c.check(_c.lib().cfm_dwconv_bn_train(_c.ptr(g), _c.dt_code(g), _c.ptr(w), _c.ptr(dw_bias), _c.ptr(gamma), _c.ptr(beta), _c.ptr(running_mean),
-                                          _c.ptr(running_var), momentum, eps, _c.ptr(c), _c.ptr(stats), _c.ptr(s), _c.dt_code(s), _c.ptr(ws), B, T, D,
-                                          w.shape[1], _c.stream()), "cfm_dwconv_bn_train")
+    _c.call("cfm_dwconv_bn_train", _c.ptr(g), _c.dt_code(g), _c.ptr(w), _c.ptr(dw_bias), _c.ptr(gamma), _c.ptr(beta), _c.ptr(running_mean),
+            _c.ptr(running_var), momentum, eps, _c.ptr(c), _c.ptr(stats), _c.ptr(s), _c.dt_code(s), _c.ptr(ws), B, T, D, w.shape[1])
     return c, stats, s
 
 
@@ -819,9 +815,8 @@ def dwconv_bn_train_bwd(ds, c, stats, g, w, dg_dtype):
     dw_b, dgamma, dbeta = (torch.empty((D,), dtype=torch.float32, device=dev) for _ in range(3))
     dy = scratch("dwbn_dy", B * T * D, torch.float32, dev)
     ws = scratch("dwbn", _c.lib().cfm_dwconv_bn_ws(B, T, D), torch.float32, dev)
-    _c.check(_c.lib().cfm_dwconv_bn_train_bwd(_c.ptr(ds), _c.dt_code(ds), _c.ptr(c), _c.ptr(stats), _c.ptr(g), _c.dt_code(g), _c.ptr(w), _c.ptr(dg),
-                                              _c.dt_code(dg), _c.ptr(dw_w), _c.ptr(dw_b), _c.ptr(dgamma), _c.ptr(dbeta), _c.ptr(dy), _c.ptr(ws), B, T, D,
-                                              w.shape[1], _c.stream()), "cfm_dwconv_bn_train_bwd")
+    _c.call("cfm_dwconv_bn_train_bwd", _c.ptr(ds), _c.dt_code(ds), _c.ptr(c), _c.ptr(stats), _c.ptr(g), _c.dt_code(g), _c.ptr(w), _c.ptr(dg),
+            _c.dt_code(dg), _c.ptr(dw_w), _c.ptr(dw_b), _c.ptr(dgamma), _c.ptr(dbeta), _c.ptr(dy), _c.ptr(ws), B, T, D, w.shape[1])
     return dg, dw_w, dw_b, dgamma, dbeta
 
 
@@ -891,9 +886,8 @@ def dwconv_bn_train_groups(g, groups, w, dw_bias, gamma, beta, running_mean=None
     if stats.dtype != torch.float32 or stats.numel() != n * 4 * D or not stats.is_contiguous():
         raise ValueError("cfm.%s: stats must be contiguous float32 [n_groups,4,D]" % who)
     ws = _dw_window_ws(groups, D, ws, who, dev)
-    _c.check(_c.lib().cfm_dwconv_bn_train_groups(_c.ptr(g), _c.dt_code(g), _c.ptr(w), _c.ptr(dw_bias), _c.ptr(gamma), _c.ptr(beta), _c.ptr(running_mean),
-                                                 _c.ptr(running_var), momentum, eps, _c.ptr(c), _c.ptr(stats), _c.ptr(s), _c.dt_code(s), _c.ptr(ws), arr, n, D,
-                                                 w.shape[1], _c.stream()), "cfm_dwconv_bn_train_groups")
+    _c.call("cfm_dwconv_bn_train_groups", _c.ptr(g), _c.dt_code(g), _c.ptr(w), _c.ptr(dw_bias), _c.ptr(gamma), _c.ptr(beta), _c.ptr(running_mean),
+            _c.ptr(running_var), momentum, eps, _c.ptr(c), _c.ptr(stats), _c.ptr(s), _c.dt_code(s), _c.ptr(ws), arr, n, D, w.shape[1])
     return c, stats, s
 
 
@@ -948,9 +942,9 @@ def dwconv_bn_train_bwd_groups(ds, c, stats, g, groups, w, dg_dtype=None, accumu
     if dy_ws.dtype != torch.float32 or dy_ws.numel() < M * D or not dy_ws.is_contiguous():
         raise ValueError("cfm.%s: dy_ws must be contiguous float32 with at least M*D = %d elements" % (who, M * D))
     ws = _dw_window_ws(groups, D, ws, who, dev)
-    _c.check(_c.lib().cfm_dwconv_bn_train_bwd_groups(_c.ptr(ds), _c.dt_code(ds), _c.ptr(c), _c.ptr(stats), _c.ptr(g), _c.dt_code(g), _c.ptr(w), _c.ptr(dg), dg_code,
-                                                     _c.ptr(dw_w), _c.ptr(dw_b), _c.ptr(dgamma), _c.ptr(dbeta), _c.ptr(dy_ws), _c.ptr(ws), arr, n, D, K,
-                                                     1 if accumulate else 0, _c.ptr(glu_u), _c.ptr(glu_du), _c.stream()), "cfm_dwconv_bn_train_bwd_groups")
+    _c.call("cfm_dwconv_bn_train_bwd_groups", _c.ptr(ds), _c.dt_code(ds), _c.ptr(c), _c.ptr(stats), _c.ptr(g), _c.dt_code(g), _c.ptr(w), _c.ptr(dg), dg_code,
+            _c.ptr(dw_w), _c.ptr(dw_b), _c.ptr(dgamma), _c.ptr(dbeta), _c.ptr(dy_ws), _c.ptr(ws), arr, n, D, K,
+            1 if accumulate else 0, _c.ptr(glu_u), _c.ptr(glu_du))
     return (glu_du if fused else dg), dw_w, dw_b, dgamma, dbeta
 
 
@@ -962,8 +956,7 @@ def col2im_relu_bwd(dcol, h1, out_dtype):
     if not dcol.is_contiguous() or tuple(dcol.shape) != (B * T2 * F2, 9 * C) or not h1.is_contiguous():
         raise ValueError("cfm.col2im_relu_bwd: dcol must be contiguous [B*T2*F2, 9C] and h1 contiguous [B,T1,F1,C]")
     dh1 = torch.empty((B, T1, F1, C), dtype=out_dtype, device=h1.device)
-    _c.check(_c.lib().cfm_col2im_relu_bwd(_c.ptr(dcol), _c.dt_code(dcol), _c.ptr(h1), _c.dt_code(h1), _c.ptr(dh1), _c.dt_code(dh1), B, T1, F1, C,
-                                          _c.stream()), "cfm_col2im_relu_bwd")
+    _c.call("cfm_col2im_relu_bwd", _c.ptr(dcol), _c.dt_code(dcol), _c.ptr(h1), _c.dt_code(h1), _c.ptr(dh1), _c.dt_code(dh1), B, T1, F1, C)
     return dh1
 
 
@@ -983,8 +976,7 @@ def conv1_wgrad(dh1, x, cmvn=None):
     dw = torch.empty((9, C), dtype=torch.float32, device=x.device)
     db = torch.empty((C,), dtype=torch.float32, device=x.device)
     ws = scratch("conv1_wgrad", _c.lib().cfm_conv1_wgrad_ws(B, T, C), torch.float32, x.device)
-    _c.check(_c.lib().cfm_conv1_wgrad(_c.ptr(dh1), _c.dt_code(dh1), _c.ptr(x), _c.ptr(mean), _c.ptr(istd), _c.ptr(dw), _c.ptr(db), _c.ptr(ws), B, T, F, C,
-                                      _c.stream()), "cfm_conv1_wgrad")
+    _c.call("cfm_conv1_wgrad", _c.ptr(dh1), _c.dt_code(dh1), _c.ptr(x), _c.ptr(mean), _c.ptr(istd), _c.ptr(dw), _c.ptr(db), _c.ptr(ws), B, T, F, C)
     return dw, db
 
 
@@ -1026,7 +1018,7 @@ def attention_bwd(q, k, v, out, dout, lse, B, H, Tq, Tk, dk, q_str, k_str, v_str
     d = _c.AttnBwdDesc()
     _attn_bwd_fill(d, "attention_bwd", q, k, v, out, dout, lse, B, H, Tq, Tk, dk, q_str, k_str, v_str, dq, dkk, dv, delta, mask=mask, mask_str=mask_str,
                    mma_code=mma_code, split=split, scale=scale, drop=drop)
-    _c.check(_c.lib().cfm_attention_bwd(ctypes.byref(d), _c.stream()), "cfm_attention_bwd")
+    _c.call("cfm_attention_bwd", ctypes.byref(d))
 
 
 def attention_bwd_group(problems):
@@ -1046,7 +1038,7 @@ def attention_bwd_group(problems):
             kw["delta"] = pool[off:off + m]
         off += m
         _attn_bwd_fill(d, "attention_bwd_group", **kw)
-    _c.check(_c.lib().cfm_attention_bwd_group(arr, n, _c.stream()), "cfm_attention_bwd_group")
+    _c.call("cfm_attention_bwd_group", arr, n)
 
 
 def _ctc_args(logits, enc_lens, labels, label_lens):
@@ -1080,7 +1072,7 @@ def ctc_nll_train_groups(problems, V):
         g.enc_lens, g.labels, g.label_lens = enc_lens.data_ptr(), labels.data_ptr(), label_lens.data_ptr()
         g.work, g.alpha, g.lse, g.nll, g.nll_shifted, g.beta = work.data_ptr(), alpha.data_ptr(), lse.data_ptr(), nll.data_ptr(), nllp.data_ptr(), beta.data_ptr()
         outs.append((nll, (work, alpha, lse, nllp, beta)))
-    _c.check(_c.lib().cfm_ctc_nll_train_groups(arr, n, V, _c.stream()), "cfm_ctc_nll_train_groups")
+    _c.call("cfm_ctc_nll_train_groups", arr, n, V)
     return outs
 
 
@@ -1099,8 +1091,8 @@ def ctc_grad(logits, V, enc_lens, labels, label_lens, state, gscale=1.0, gscale_
         out = torch.empty_like(logits)
     if out.dtype != torch.float32 or out.shape != logits.shape or out.stride() != logits.stride():
         raise ValueError("cfm.ctc_grad: out must match logits")
-    _c.check(_c.lib().cfm_ctc_grad(_c.ptr(logits), logits.stride(1), B, T, V, _c.ptr(enc_lens), _c.ptr(labels), labels.size(1), _c.ptr(label_lens),
-                                   _c.ptr(work), _c.ptr(alpha), _c.ptr(beta), _c.ptr(lse), _c.ptr(nllp), gscale, _c.ptr(gscale_dev), _c.ptr(out), _c.stream()), "cfm_ctc_grad")
+    _c.call("cfm_ctc_grad", _c.ptr(logits), logits.stride(1), B, T, V, _c.ptr(enc_lens), _c.ptr(labels), labels.size(1), _c.ptr(label_lens),
+            _c.ptr(work), _c.ptr(alpha), _c.ptr(beta), _c.ptr(lse), _c.ptr(nllp), gscale, _c.ptr(gscale_dev), _c.ptr(out))
     return out
 
 
@@ -1164,7 +1156,7 @@ def rnnt_nll(logits, targets, logit_lens, target_lens, blank, V=None):
     tens.update(logit_lens=logit_lens, target_lens=target_lens)
     d.B, d.T, d.U1 = B, T, U1
     d.logit_lens, d.target_lens = logit_lens.data_ptr(), target_lens.data_ptr()
-    _c.check(_c.lib().cfm_rnnt_nll(ctypes.byref(d), _c.stream()), "cfm_rnnt_nll")
+    _c.call("cfm_rnnt_nll", ctypes.byref(d))
     return tens["nll"], RnntState(d, logits, tens, (B, T, U1))
 
 
@@ -1195,9 +1187,9 @@ def rnnt_grad(state, out, gscale=1.0, gscale_dev=None, clamp=-1.0, cols=None):
     else:
         d.gscale_dev, d.gscale_stride = None, 0
     if state.packed:
-        _c.check(_c.lib().cfm_rnnt_packed_grad(ctypes.byref(d), _c.stream()), "cfm_rnnt_packed_grad")
+        _c.call("cfm_rnnt_packed_grad", ctypes.byref(d))
     else:
-        _c.check(_c.lib().cfm_rnnt_grad(ctypes.byref(d), _c.stream()), "cfm_rnnt_grad")
+        _c.call("cfm_rnnt_grad", ctypes.byref(d))
     d.grad, d.gscale_dev = None, None
     return out
 
@@ -1213,8 +1205,8 @@ def joint_act_bwd(enc, pred, dact, B, T, U):
     de = torch.empty((B * T, J), dtype=torch.float32, device=enc.device)
     dp = torch.empty((B * U, J), dtype=torch.float32, device=enc.device)
     ws = scratch("joint_act_bwd", _c.lib().cfm_joint_act_bwd_ws(B, T, U, J), torch.float32, enc.device)
-    _c.check(_c.lib().cfm_joint_act_bwd(enc.data_ptr(), enc.stride(0), pred.data_ptr(), pred.stride(0), dact.data_ptr(), de.data_ptr(), dp.data_ptr(),
-                                        ws.data_ptr(), B, T, U, J, _c.stream()), "cfm_joint_act_bwd")
+    _c.call("cfm_joint_act_bwd", enc.data_ptr(), enc.stride(0), pred.data_ptr(), pred.stride(0), dact.data_ptr(), de.data_ptr(), dp.data_ptr(),
+            ws.data_ptr(), B, T, U, J)
     return de, dp
 
 
@@ -1227,8 +1219,7 @@ def joint_act_packed(enc, pred, lat, out_dtype):
     if enc.dtype != torch.float32 or pred.dtype != torch.float32 or tuple(enc.shape) != (d.n_enc, J) or tuple(pred.shape) != (d.n_pred, J):
         raise ValueError("cfm.joint_act_packed: enc must be f32 [%d,J] and pred f32 [%d,J], got %s %s" % (d.n_enc, d.n_pred, tuple(enc.shape), tuple(pred.shape)))
     out = torch.empty((lat.M, J), dtype=out_dtype, device=enc.device)
-    _c.check(_c.lib().cfm_joint_act_packed(_c.ptr(enc), enc.stride(0), _c.ptr(pred), pred.stride(0), _c.ptr(out), _c.dt_code(out), ctypes.byref(d), J,
-                                           _c.stream()), "cfm_joint_act_packed")
+    _c.call("cfm_joint_act_packed", _c.ptr(enc), enc.stride(0), _c.ptr(pred), pred.stride(0), _c.ptr(out), _c.dt_code(out), ctypes.byref(d), J)
     return out
 
 
@@ -1244,8 +1235,8 @@ def joint_act_packed_bwd(enc, pred, dact, lat):
     de = torch.empty((d.n_enc, J), dtype=torch.float32, device=enc.device)
     dp = torch.empty((d.n_pred, J), dtype=torch.float32, device=enc.device)
     ws = torch.empty((max(lat.n_blk, 1), J), dtype=torch.float32, device=enc.device)
-    _c.check(_c.lib().cfm_joint_act_packed_bwd(enc.data_ptr(), enc.stride(0), pred.data_ptr(), pred.stride(0), dact.data_ptr(), de.data_ptr(),
-                                               dp.data_ptr(), ws.data_ptr(), ctypes.byref(d), J, _c.stream()), "cfm_joint_act_packed_bwd")
+    _c.call("cfm_joint_act_packed_bwd", enc.data_ptr(), enc.stride(0), pred.data_ptr(), pred.stride(0), dact.data_ptr(), de.data_ptr(),
+            dp.data_ptr(), ws.data_ptr(), ctypes.byref(d), J)
     return de, dp
 
 
@@ -1265,7 +1256,7 @@ def rnnt_nll_packed(logits, targets, lat, blank, V=None):
     if not M:                                                          # no node: nothing is read, but the row-pass checks want a pointer
         d.logits, d.ld = tens["nll"].data_ptr(), d.V
     d.lat, d.ld_targets = lat.desc, targets.shape[1]
-    _c.check(_c.lib().cfm_rnnt_packed_nll(ctypes.byref(d), _c.stream()), "cfm_rnnt_packed_nll")
+    _c.call("cfm_rnnt_packed_nll", ctypes.byref(d))
     return tens["nll"], RnntState(d, logits, tens, (M,))
 
 
@@ -1277,8 +1268,7 @@ def adam_step(p, g, m, v, lr, betas, eps, weight_decay, step, grad_scale=None):
         if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous():
             raise ValueError("cfm.adam_step: p, g, m, v must be contiguous float32 buffers of one size")
     _dense("adam_step", grad_scale=grad_scale)
-    _c.check(_c.lib().cfm_adam_step(_c.ptr(p), _c.ptr(g), _c.ptr(m), _c.ptr(v), n, lr, betas[0], betas[1], eps, weight_decay, step, _c.ptr(grad_scale),
-                                    _c.stream()), "cfm_adam_step")
+    _c.call("cfm_adam_step", _c.ptr(p), _c.ptr(g), _c.ptr(m), _c.ptr(v), n, lr, betas[0], betas[1], eps, weight_decay, step, _c.ptr(grad_scale))
 
 
 def adam_clip_step(p, g, m, v, lr, betas, eps, weight_decay, step, sumsq_t, clip, inv_world, zero_grad=True):
@@ -1292,8 +1282,8 @@ def adam_clip_step(p, g, m, v, lr, betas, eps, weight_decay, step, sumsq_t, clip
             raise ValueError("cfm.adam_clip_step: p, g, m, v must be contiguous float32 buffers of one size")
     _dense("adam_clip_step", sumsq=sumsq_t)
     norm = None if sumsq_t is None else torch.empty((1,), dtype=torch.float32, device=p.device)
-    _c.check(_c.lib().cfm_adam_clip_step(_c.ptr(p), _c.ptr(g), _c.ptr(m), _c.ptr(v), n, lr, betas[0], betas[1], eps, weight_decay, step, _c.ptr(sumsq_t),
-                                         float(clip or 0.0), float(inv_world), 1 if zero_grad else 0, _c.ptr(norm), _c.stream()), "cfm_adam_clip_step")
+    _c.call("cfm_adam_clip_step", _c.ptr(p), _c.ptr(g), _c.ptr(m), _c.ptr(v), n, lr, betas[0], betas[1], eps, weight_decay, step, _c.ptr(sumsq_t),
+            float(clip or 0.0), float(inv_world), 1 if zero_grad else 0, _c.ptr(norm))
     return norm
 
 
@@ -1306,7 +1296,7 @@ def sumsq(x):
     nb = max(1, min(1024, (n + 4095) // 4096))
     part = scratch("sumsq", nb, torch.float32, x.device)
     out = torch.empty((1,), dtype=torch.float32, device=x.device)
-    _c.check(_c.lib().cfm_sumsq(_c.ptr(x), n, _c.ptr(part), nb, _c.ptr(out), _c.stream()), "cfm_sumsq")
+    _c.call("cfm_sumsq", _c.ptr(x), n, _c.ptr(part), nb, _c.ptr(out))
     return out
 
 
@@ -1324,8 +1314,7 @@ def dropout_rows(x, out_dtype, alpha=1.0, drop=None, drop2=None, row_mask=None):
     y = torch.empty((M, N), dtype=out_dtype, device=x.device)
     p1, s1 = (float(drop[0]), int(drop[1]) & 0xFFFFFFFF) if drop is not None else (0.0, 0)
     p2, s2 = (float(drop2[0]), int(drop2[1]) & 0xFFFFFFFF) if drop2 is not None else (0.0, 0)
-    _c.check(_c.lib().cfm_dropout_rows(_c.ptr(x), _c.dt_code(x), _c.ptr(y), _c.dt_code(y), _c.ptr(row_mask), alpha, p1, s1, p2, s2, M, N, _c.stream()),
-             "cfm_dropout_rows")
+    _c.call("cfm_dropout_rows", _c.ptr(x), _c.dt_code(x), _c.ptr(y), _c.dt_code(y), _c.ptr(row_mask), alpha, p1, s1, p2, s2, M, N)
     return y
 
 
@@ -1333,7 +1322,7 @@ def dropout_mask(n, p, seed, device):
     """the 0/1 keep mask the kernels regenerate for (p, seed) over element indices 0..n-1 (bool tensor; for tests)."""
     out = torch.empty((n,), dtype=torch.uint8, device=device)
     _c.require_hip(out)
-    _c.check(_c.lib().cfm_dropout_mask(_c.ptr(out), n, float(p), int(seed) & 0xFFFFFFFF, _c.stream()), "cfm_dropout_mask")
+    _c.call("cfm_dropout_mask", _c.ptr(out), n, float(p), int(seed) & 0xFFFFFFFF)
     return out.view(torch.bool)
 
 
@@ -1362,8 +1351,8 @@ def stream_prep(offsets, T, need, ring_T, pe, slot_mask, pos_rows, abs_rows=None
         raise ValueError("cfm.stream_prep: frame_lens and out_lens come together")
     if frame_lens is not None:
         _stream_lens("stream_prep", B, frame_lens=frame_lens, out_lens=out_lens)
-    _c.check(_c.lib().cfm_stream_prep(_c.ptr(offsets), _c.ptr(frame_lens), _c.ptr(out_lens), B, T, need, ring_T, _c.ptr(pe), pe.numel() // D, D,
-                                      _c.ptr(slot_mask), _c.ptr(pos_rows), _c.ptr(abs_rows), _c.stream()), "cfm_stream_prep")
+    _c.call("cfm_stream_prep", _c.ptr(offsets), _c.ptr(frame_lens), _c.ptr(out_lens), B, T, need, ring_T, _c.ptr(pe), pe.numel() // D, D,
+            _c.ptr(slot_mask), _c.ptr(pos_rows), _c.ptr(abs_rows))
 
 
 def stream_advance(offsets, T, active=None, lens=None, y=None):
@@ -1383,7 +1372,7 @@ def stream_advance(offsets, T, active=None, lens=None, y=None):
         if y.dtype != torch.float32 or not y.is_contiguous() or y.dim() != 3 or tuple(y.shape[:2]) != (B, T):
             raise ValueError("cfm.stream_advance: y must be contiguous float32 [B,T,D]")
         D = y.shape[2]
-    _c.check(_c.lib().cfm_stream_advance(_c.ptr(offsets), _c.ptr(active), _c.ptr(lens), _c.ptr(y), B, T, D, _c.stream()), "cfm_stream_advance")
+    _c.call("cfm_stream_advance", _c.ptr(offsets), _c.ptr(active), _c.ptr(lens), _c.ptr(y), B, T, D)
 
 
 def dwconv_causal_bn_silu(x, w, dw_bias, bn_scale, bn_shift, cache=None, out_dtype=None):
@@ -1395,8 +1384,8 @@ def dwconv_causal_bn_silu(x, w, dw_bias, bn_scale, bn_shift, cache=None, out_dty
     if not x.is_contiguous() or (cache is not None and (cache.dtype != torch.float32 or tuple(cache.shape) != (B, K - 1, D) or not cache.is_contiguous())):
         raise ValueError("cfm.dwconv_causal_bn_silu: x contiguous [B,T,D], cache contiguous f32 [B,K-1,D]")
     y = torch.empty((B, T, D), dtype=out_dtype or x.dtype, device=x.device)
-    _c.check(_c.lib().cfm_dwconv_causal_bn_silu(_c.ptr(x), _c.dt_code(x), _c.ptr(cache), _c.ptr(w), _c.ptr(dw_bias), _c.ptr(bn_scale), _c.ptr(bn_shift), _c.ptr(y),
-                                                _c.dt_code(y), B, T, D, K, _c.stream()), "cfm_dwconv_causal_bn_silu")
+    _c.call("cfm_dwconv_causal_bn_silu", _c.ptr(x), _c.dt_code(x), _c.ptr(cache), _c.ptr(w), _c.ptr(dw_bias), _c.ptr(bn_scale), _c.ptr(bn_shift), _c.ptr(y),
+            _c.dt_code(y), B, T, D, K)
     return y
 
 
@@ -1409,7 +1398,7 @@ def conv_cache_update(x, cache, ktaps, lens=None):
         raise ValueError("cfm.conv_cache_update: cache must be float32 [B,ktaps-1,D], got %s %s" % (cache.dtype, tuple(cache.shape)))
     if lens is not None:
         _stream_lens("conv_cache_update", B, lens=lens)
-    _c.check(_c.lib().cfm_conv_cache_update(_c.ptr(x), _c.dt_code(x), _c.ptr(cache), _c.ptr(lens), B, T, D, ktaps, _c.stream()), "cfm_conv_cache_update")
+    _c.call("cfm_conv_cache_update", _c.ptr(x), _c.dt_code(x), _c.ptr(cache), _c.ptr(lens), B, T, D, ktaps)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -1441,7 +1430,7 @@ def fbank(samples, lengths, tables, out, feats_length, win, shift, padded, dithe
     if lengths.dtype != torch.int32 or feats_length.dtype != torch.int32 or lengths.numel() != d.B or feats_length.numel() != d.B:
         raise ValueError("cfm.fbank: lengths and feats_length are int32 [B]")
     d.lengths, d.feats_length = _c.ptr(lengths), _c.ptr(feats_length)
-    _c.check(_c.lib().cfm_fbank(ctypes.byref(d), _c.stream()), "cfm_fbank")
+    _c.call("cfm_fbank", ctypes.byref(d))
 
 
 def fbank_stream(samples, state_in, state_out, tables, out, win, shift, padded, hop, dither=0.0, seed=0):
@@ -1454,7 +1443,7 @@ def fbank_stream(samples, state_in, state_out, tables, out, win, shift, padded, 
             raise ValueError("cfm.fbank_stream: state is (carry f32 [B, n], fresh int32 [B], pos int32 [B]), contiguous")
     d.carry_in, d.fresh_in, d.pos_in, d.carry_out, d.fresh_out, d.pos_out = (_c.ptr(t) for t in (ci, fi, pi, co, fo, po))
     d.carry_n, d.hop = ci.shape[1], hop
-    _c.check(_c.lib().cfm_fbank_stream(ctypes.byref(d), _c.stream()), "cfm_fbank_stream")
+    _c.call("cfm_fbank_stream", ctypes.byref(d))
 
 
 def fbank_stream_ragged(samples, n_new, final, state_in, state_out, frame_lens, tables, out, win, shift, padded, hop, dither=0.0, seed=0):
@@ -1478,7 +1467,7 @@ def fbank_stream_ragged(samples, n_new, final, state_in, state_out, frame_lens, 
         raise ValueError("cfm.fbank_stream_ragged: state in and out (and the length buffers) must not alias")
     d.carry_in, d.fresh_in, d.pos_in, d.carry_len_in, d.carry_out, d.fresh_out, d.pos_out, d.carry_len_out = (_c.ptr(t) for t in (ci, fi, pi, li, co, fo, po, lo))
     d.n_new, d.final, d.frame_lens, d.carry_cap, d.hop = _c.ptr(n_new), _c.ptr(final), _c.ptr(frame_lens), ci.shape[1], hop
-    _c.check(_c.lib().cfm_fbank_stream(ctypes.byref(d), _c.stream()), "cfm_fbank_stream")
+    _c.call("cfm_fbank_stream", ctypes.byref(d))
 
 
 def _lstm_desc(who, x, weights, H, drop):
@@ -1534,7 +1523,7 @@ def lstm_forward(x, weights, H, h0=None, c0=None, drop=None, out=None):
     d.h0, d.c0, d.y, d.hn, d.cn = _c.ptr(h0), _c.ptr(c0), _c.ptr(y), _c.ptr(hn), _c.ptr(cn)
     for l in range(L):
         d.save[l] = _c.ptr(saves[l])
-    _c.check(_c.lib().cfm_lstm_forward(ctypes.byref(d), _c.stream()), "cfm_lstm_forward")
+    _c.call("cfm_lstm_forward", ctypes.byref(d))
     return y, hn, cn, saves
 
 
@@ -1573,5 +1562,5 @@ def lstm_backward(x, weights, H, saves, dy, dhn=None, dcn=None, drop=None, out=N
     if tuple(dg.shape) != (U * B, 4 * H) or not dg.is_contiguous() or (L > 1 and (dyl is None or tuple(dyl.shape) != (U * B, H) or not dyl.is_contiguous())):
         raise ValueError("cfm.lstm_backward: work must be (dg [U*B, 4H], dyl [U*B, H])")
     d.dy, d.dhn, d.dcn, d.dx, d.dh0, d.dc0, d.dg, d.dyl = _c.ptr(dy), _c.ptr(dhn), _c.ptr(dcn), _c.ptr(dx), _c.ptr(dh0), _c.ptr(dc0), _c.ptr(dg), _c.ptr(dyl)
-    _c.check(_c.lib().cfm_lstm_backward(ctypes.byref(d), _c.stream()), "cfm_lstm_backward")
+    _c.call("cfm_lstm_backward", ctypes.byref(d))
     return dx, grads, dh0, dc0

@@ -420,9 +420,8 @@ class _StackPackPlan:
 
     def run(self):
         prec = self.prec
-        _c.check(_c.lib().cfm_pack_matrices(self.jobs.data_ptr(), self.jobs.shape[0], self.tiles, _c.BF16 if prec.split else prec.w_code, 1 if prec.split else 0,
-                                            _c.stream()), "cfm_pack_matrices")
-        _c.check(_c.lib().cfm_pack_vectors(self.pa.data_ptr(), self.pb.data_ptr(), self.vec.data_ptr(), self.vec.numel(), _c.stream()), "cfm_pack_vectors")
+        _c.call("cfm_pack_matrices", self.jobs.data_ptr(), self.jobs.shape[0], self.tiles, _c.BF16 if prec.split else prec.w_code, 1 if prec.split else 0)
+        _c.call("cfm_pack_vectors", self.pa.data_ptr(), self.pb.data_ptr(), self.vec.data_ptr(), self.vec.numel())
         if self.val is None:        # the destinations never move (valid_for checks the sources' addresses): the same Packed objects every step, so
             # whoever caches on their identity (the stack's ctypes weight structs, cfm/autograd.py) keeps its cache across optimizer steps
             self.val = tuple(pl.packs(l, self.vec[a:b], self.vec[b:c]) for l, pl, (a, b, c) in zip(self.layers, self.plans, self.vec_slices))

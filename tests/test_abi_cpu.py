@@ -1,5 +1,5 @@
-"""CPU (no GPU): the C-ABI shared library loads, exports every symbol include/cfm.h declares, the ctypes mirrors of its
-structs have the C sizes, and the host-side logic (weight packing index maps, module construction, loud failures) is right.
+"""CPU (no GPU): the C-ABI shared library loads, exports every symbol include/cfm.h declares, the ctypes binding agrees with
+the header in every struct field and every prototype (tests/abi_check.py), and the host-side logic (weight packing index maps, module construction, loud failures) is right.
 No compute entry point is called."""
 import ctypes
 import json
@@ -11,9 +11,9 @@ import numpy as np
 import pytest
 import torch
 
+import abi_check
+from abi_check import declared_functions
 from conftest import ROOT, load_golden
-
-HDR = os.path.join(ROOT, "include", "cfm.h")
 
 
 @pytest.fixture(scope="module")
@@ -23,11 +23,6 @@ def cfm():
         import __graft_entry__ as g
         g.build()
     return c
-
-
-def declared_functions():
-    text = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(cfm_[a-z0-9_]+)\s*\(", text)))
 
 
 def test_library_exports_every_declared_symbol_at_abi_306(cfm):
@@ -40,35 +35,31 @@ def test_library_exports_every_declared_symbol_at_abi_306(cfm):
     assert isinstance(lib.cfm_last_error(), bytes)
 
 
-def test_ctypes_structs_match_c_sizes(cfm, tmp_path):
-    structs = {"cfm_gemm_desc": cfm.GemmDesc, "cfm_attn_desc": cfm.AttnDesc, "cfm_ffn_desc": cfm.FfnDesc,
-               "cfm_layer_weights": cfm.LayerWeights, "cfm_layer_scratch": cfm.LayerScratch, "cfm_layer_io": cfm.LayerIO,
-               "cfm_gemm_tn_desc": cfm.GemmTnDesc, "cfm_attn_bwd_desc": cfm.AttnBwdDesc, "cfm_rowchain_desc": cfm.RowChainDesc,
-               "cfm_layer_train_weights": cfm.LayerTrainWeights, "cfm_layer_train_io": cfm.LayerTrainIO, "cfm_layer_train_saved": cfm.LayerTrainSaved,
-               "cfm_layer_train_scratch": cfm.LayerTrainScratch, "cfm_layer_train_grads": cfm.LayerTrainGrads,
-               "cfm_ln_bwd_desc": cfm.LnBwdDesc, "cfm_train_group": cfm.TrainGroup, "cfm_ctc_group": cfm.CtcGroup, "cfm_greedy_desc": cfm.GreedyDesc, "cfm_ffn_split_desc": cfm.FfnSplitDesc,
-               "cfm_greedy_chunk_desc": cfm.GreedyChunkDesc}
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include "cfm.h"\nint main(){' +
-                   "".join('printf("%s %%zu\\n", sizeof(%s));' % (n, n) for n in structs) + "return 0;}\n")
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    out = dict(line.split() for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    for n, cls in structs.items():
-        assert int(out[n]) == ctypes.sizeof(cls), (n, out[n], ctypes.sizeof(cls))
+def test_every_struct_mirror_matches_c_field_by_field(tmp_path):
+    """sizeof of every struct include/cfm.h defines, and offsetof and sizeof of every member, against the ctypes mirror: no library needed."""
+    import cfm
+    mirrors = abi_check.mirrors(cfm)
+    assert sorted(mirrors) == abi_check.declared_structs()                 # a mirror for each `typedef struct { ... } cfm_x;`, and nothing else
+    n_fields, bad = abi_check.struct_mismatches(cfm, tmp_path)
+    print("%d structs, %d fields compared with include/cfm.h" % (len(mirrors), n_fields))
+    assert not bad, "ctypes mirrors that differ from include/cfm.h:\n" + "\n".join(bad)
 
 
-def test_greedy_chunk_desc_field_offsets_match_c(cfm, tmp_path):
-    """The begin-only pointer, the first int32 pointer, the first int64 and the last field of the streaming decoder's descriptor."""
-    fields = ("enc", "pidx", "hyp_cap", "carry")
-    src = tmp_path / "off.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "cfm.h"\nint main(){' +
-                   "".join('printf("%%zu\\n", offsetof(cfm_greedy_chunk_desc, %s));' % f for f in fields) + "return 0;}\n")
-    exe = tmp_path / "off"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert got == [getattr(cfm.GreedyChunkDesc, f).offset for f in fields], (fields, got)
-    assert cfm.GreedyChunkDesc.carry.offset + 4 == ctypes.sizeof(cfm.GreedyChunkDesc)         # nothing after it
+def test_greedy_chunk_desc_field_offsets_match_c():
+    import cfm
+    assert cfm.GreedyChunkDesc.carry.offset + 4 == ctypes.sizeof(cfm.GreedyChunkDesc)         # nothing after the last field
+
+
+def test_every_prototype_matches_the_header(tmp_path):
+    """cfm.PROTOTYPES against decltype(&cfm_x) of every function include/cfm.h declares: return type, argument count, each argument's class."""
+    import cfm
+    names = [entry[0] for entry in cfm.PROTOTYPES]
+    only = sorted(set(names) ^ set(declared_functions()))
+    assert not only and len(names) == len(set(names)), "in only one of include/cfm.h and cfm.PROTOTYPES, or twice in the table: %s" % only
+    want, got = abi_check.c_signatures(names, tmp_path), abi_check.table_signatures(cfm)
+    print("%d prototypes compared with include/cfm.h" % len(names))
+    bad = ["%s: header %s, cfm.PROTOTYPES %s" % (n, want[n], got[n]) for n in names if want[n] != got[n] or "?" in want[n] + got[n]]
+    assert not bad, "prototypes (return:arguments) that differ from include/cfm.h, or hold a type the check does not know (?):\n" + "\n".join(bad)
 
 
 def test_header_is_plain_c(tmp_path):

@@ -1,16 +1,13 @@
 """CPU (no GPU): the log-mel front-end's host side -- the torch restatement of kaldi.fbank the GPU tests measure against (tests/fbank_ref.py),
-the packed sparse mel table, the descriptor's ctypes mirror and the loud failures.  No compute entry point is called."""
-import ctypes
+the packed sparse mel table, the front-end's entry points in the built library and the loud failures.  No compute entry point is called."""
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import fbank_ref as R
-from conftest import ROOT, load_golden
+from conftest import load_golden
 
 
 def fixture_pcm(zero_stretch=True):
@@ -59,16 +56,8 @@ def test_packed_mel_table_equals_the_dense_banks():
             assert int(length.min()) == 1 and int(length.max()) == 16 and int((dense[:, 0] > 0).sum()) == 0
 
 
-def test_fbank_desc_matches_c(tmp_path):
+def test_fbank_desc_matches_c():
     import cfm
-    fields = ("samples", "out", "ld", "B", "hop", "dither", "seed")
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "cfm.h"\nint main(){printf("%zu\\n", sizeof(cfm_fbank_desc));' +
-                   "".join('printf("%%zu\\n", offsetof(cfm_fbank_desc, %s));' % f for f in fields) + "return 0;}\n")
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert got == [ctypes.sizeof(cfm.FbankDesc)] + [getattr(cfm.FbankDesc, f).offset for f in fields]
     lib = cfm.lib()
     assert hasattr(lib, "cfm_fbank") and hasattr(lib, "cfm_fbank_stream") and lib.cfm_version() == 306
 

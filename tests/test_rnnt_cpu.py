@@ -1,10 +1,8 @@
 """CPU (no GPU): the float64 RNN-T reference against brute-force enumeration of alignments, the loud failures of rnnt.rnnt_loss /
-TransducerJoint.rnnt_loss off the GPU, and the C ABI of the RNN-T entry points (declared, exported, struct sizes)."""
-import ctypes
+TransducerJoint.rnnt_loss off the GPU, and the C ABI of the RNN-T entry points (declared, exported)."""
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -103,14 +101,3 @@ def test_header_declares_and_library_exports_the_rnnt_entries(cfm):
         assert n in names, "include/cfm.h does not declare %s" % n
         assert hasattr(lib, n), "libconformer_gfx950.so does not export %s" % n
     assert lib.cfm_joint_act_bwd_ws(2, 9, 4, 16) == 2 * 2 * 4 * 16          # two frame blocks of 8
-
-
-def test_rnnt_desc_ctypes_size_matches_c(cfm, tmp_path):
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "cfm.h"\nint main(){printf("%zu %zu %zu\\n", sizeof(cfm_rnnt_desc), '
-                   'offsetof(cfm_rnnt_desc, grad), offsetof(cfm_rnnt_desc, clamp)); return 0;}\n')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    size, off_grad, off_clamp = map(int, subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split())
-    assert size == ctypes.sizeof(cfm.RnntDesc)
-    assert off_grad == cfm.RnntDesc.grad.offset and off_clamp == cfm.RnntDesc.clamp.offset
