@@ -307,12 +307,8 @@ PROTOTYPES = (
     ("cfm_rnnt_packed_grad", c_int, P(RnntPackedDesc), c_p),
     ("cfm_layernorm_bwd_ws", c_i64, c_i64, c_i32),
     ("cfm_layernorm_bwd_fused", c_int, P(LnBwdDesc), c_p),
-    ("cfm_layernorm_bwd", c_int, c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_i64, c_i32, c_p),
     ("cfm_glu_bwd", c_int, c_p, c_i32, c_p, c_i32, c_p, c_i32, c_i64, c_i32, c_p),
     ("cfm_dwconv_bn_ws", c_i64, c_i32, c_i32, c_i32),
-    ("cfm_dwconv_bn_train", c_int, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_i32, c_p, c_i32, c_i32, c_i32, c_i32, c_p),
-    ("cfm_dwconv_bn_train_bwd", c_int, c_p, c_i32, c_p, c_p, c_p, c_i32, c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p),
-    ("cfm_dwconv_bn_train_bwd_acc", c_int, c_p, c_i32, c_p, c_p, c_p, c_i32, c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p),
     ("cfm_dwconv_bn_train_groups", c_int, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_i32, c_p, P(TrainGroup), c_i32, c_i32, c_i32, c_p),
     ("cfm_dwconv_bn_train_bwd_groups", c_int, c_p, c_i32, c_p, c_p, c_p, c_i32, c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, P(TrainGroup), c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p),
     ("cfm_col2im_relu_bwd", c_int, c_p, c_i32, c_p, c_i32, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p),

@@ -762,8 +762,11 @@ def layernorm_bwd(x, dy, gamma, row_mask=None, dres=None, dx=None, eps=1e-5):
     dg = torch.empty((D,), dtype=torch.float32, device=x.device)
     db = torch.empty((D,), dtype=torch.float32, device=x.device)
     ws = scratch("ln_bwd", _c.lib().cfm_layernorm_bwd_ws(M, D), torch.float32, x.device)
-    _c.call("cfm_layernorm_bwd", _c.ptr(x), _c.ptr(dy), _c.dt_code(dy), _c.ptr(gamma), _c.ptr(row_mask), _c.ptr(dres), _c.ptr(dx), _c.ptr(dg),
-            _c.ptr(db), _c.ptr(ws), eps, M, D)
+    d = _c.LnBwdDesc()                      # the plain descriptor: accumulate = 0, no dx2, no chained norm
+    d.x, d.dy, d.gamma, d.row_mask, d.dres = _c.ptr(x), _c.ptr(dy), _c.ptr(gamma), _c.ptr(row_mask), _c.ptr(dres)
+    d.dx, d.dgamma, d.dbeta, d.ws = _c.ptr(dx), _c.ptr(dg), _c.ptr(db), _c.ptr(ws)
+    d.M, d.D, d.dy_dtype, d.eps = M, D, _c.dt_code(dy), eps
+    _c.call("cfm_layernorm_bwd_fused", ctypes.byref(d))
     return dx, dg, db
 
 
@@ -777,47 +780,6 @@ def glu_bwd(u, dg, out_dtype):
     du = torch.empty((M, D2), dtype=out_dtype, device=u.device)
     _c.call("cfm_glu_bwd", _c.ptr(u), _c.dt_code(u), _c.ptr(dg), _c.dt_code(dg), _c.ptr(du), _c.dt_code(du), M, D)
     return du
-
-
-def dwconv_bn_train(g, w, dw_bias, gamma, beta, running_mean, running_var, momentum, eps, s_dtype):
-    """g [B,T,D] -> (c f32 [B,T,D], stats f32 [4,D], s = SiLU(BatchNorm_train(c)) in s_dtype); running statistics updated in place."""
-    _c.require_hip(g, w, dw_bias, gamma, beta, running_mean, running_var)
-    if g.dim() != 3 or not g.is_contiguous():
-        raise ValueError("cfm.dwconv_bn_train: g must be contiguous [B,T,D]")
-    B, T, D = g.shape
-    _dense("dwconv_bn_train", w=w, dw_bias=dw_bias, gamma=gamma, beta=beta, running_mean=running_mean, running_var=running_var)
-    for n, t in (("dw_bias", dw_bias), ("gamma", gamma), ("beta", beta), ("running_mean", running_mean), ("running_var", running_var)):
-        if t is not None and (t.dtype != torch.float32 or t.numel() != D):
-            raise ValueError("cfm.dwconv_bn_train: %s must be float32 [D]" % n)
-    if w.dtype != torch.float32 or w.shape[0] != D:
-        raise ValueError("cfm.dwconv_bn_train: w must be float32 [D,K]")
-    c = torch.empty((B, T, D), dtype=torch.float32, device=g.device)
-    stats = torch.empty((4, D), dtype=torch.float32, device=g.device)
-    s = torch.empty((B, T, D), dtype=s_dtype, device=g.device)
-    ws = scratch("dwbn", _c.lib().cfm_dwconv_bn_ws(B, T, D), torch.float32, g.device)
-    _c.call("cfm_dwconv_bn_train", _c.ptr(g), _c.dt_code(g), _c.ptr(w), _c.ptr(dw_bias), _c.ptr(gamma), _c.ptr(beta), _c.ptr(running_mean),
-            _c.ptr(running_var), momentum, eps, _c.ptr(c), _c.ptr(stats), _c.ptr(s), _c.dt_code(s), _c.ptr(ws), B, T, D, w.shape[1])
-    return c, stats, s
-
-
-def dwconv_bn_train_bwd(ds, c, stats, g, w, dg_dtype):
-    """-> (dg [B,T,D], d taps [D,K], d conv bias [D], d BatchNorm gain [D], d BatchNorm bias [D])."""
-    _c.require_hip(ds, c, stats, g, w)
-    B, T, D = g.shape
-    if not ds.is_contiguous() or ds.numel() != B * T * D or not c.is_contiguous() or not g.is_contiguous():
-        raise ValueError("cfm.dwconv_bn_train_bwd: ds, c, g must be contiguous [B,T,D]")
-    _dense("dwconv_bn_train_bwd", stats=stats, w=w)
-    if stats.dtype != torch.float32 or stats.numel() != 4 * D or w.dtype != torch.float32 or w.shape[0] != D:
-        raise ValueError("cfm.dwconv_bn_train_bwd: stats must be float32 [4,D] and w float32 [D,K]")
-    dev = g.device
-    dg = torch.empty((B, T, D), dtype=dg_dtype, device=dev)
-    dw_w = torch.empty((D, w.shape[1]), dtype=torch.float32, device=dev)
-    dw_b, dgamma, dbeta = (torch.empty((D,), dtype=torch.float32, device=dev) for _ in range(3))
-    dy = scratch("dwbn_dy", B * T * D, torch.float32, dev)
-    ws = scratch("dwbn", _c.lib().cfm_dwconv_bn_ws(B, T, D), torch.float32, dev)
-    _c.call("cfm_dwconv_bn_train_bwd", _c.ptr(ds), _c.dt_code(ds), _c.ptr(c), _c.ptr(stats), _c.ptr(g), _c.dt_code(g), _c.ptr(w), _c.ptr(dg),
-            _c.dt_code(dg), _c.ptr(dw_w), _c.ptr(dw_b), _c.ptr(dgamma), _c.ptr(dbeta), _c.ptr(dy), _c.ptr(ws), B, T, D, w.shape[1])
-    return dg, dw_w, dw_b, dgamma, dbeta
 
 
 def _train_groups(who, groups, rows):
@@ -884,7 +846,7 @@ def dwconv_bn_train_groups(g, groups, w, dw_bias, gamma, beta, running_mean=None
     _row_matrix(who, "c", c, M, D, torch.float32)
     _row_matrix(who, "s", s, M, D)
     if stats.dtype != torch.float32 or stats.numel() != n * 4 * D or not stats.is_contiguous():
-        raise ValueError("cfm.%s: stats must be contiguous float32 [n_groups,4,D]" % who)
+        raise ValueError("cfm.%s: stats must be contiguous float32 [n_groups,4,D] (the C ABI has no stride for it)" % who)
     ws = _dw_window_ws(groups, D, ws, who, dev)
     _c.call("cfm_dwconv_bn_train_groups", _c.ptr(g), _c.dt_code(g), _c.ptr(w), _c.ptr(dw_bias), _c.ptr(gamma), _c.ptr(beta), _c.ptr(running_mean),
             _c.ptr(running_var), momentum, eps, _c.ptr(c), _c.ptr(stats), _c.ptr(s), _c.dt_code(s), _c.ptr(ws), arr, n, D, w.shape[1])
@@ -908,7 +870,7 @@ def dwconv_bn_train_bwd_groups(ds, c, stats, g, groups, w, dg_dtype=None, accumu
     _row_matrix(who, "ds", ds, M, D)
     _row_matrix(who, "c", c, M, D, torch.float32)
     if stats.dtype != torch.float32 or stats.numel() != n * 4 * D or not stats.is_contiguous():
-        raise ValueError("cfm.%s: stats must be contiguous float32 [n_groups,4,D]" % who)
+        raise ValueError("cfm.%s: stats must be contiguous float32 [n_groups,4,D] (the C ABI has no stride for it)" % who)
     if w.dtype != torch.float32 or w.dim() != 2 or w.shape[0] != D or not w.is_contiguous():
         raise ValueError("cfm.%s: w must be contiguous float32 [D,K] (the C ABI has no stride for it)" % who)
     dev = g.device
@@ -946,6 +908,35 @@ def dwconv_bn_train_bwd_groups(ds, c, stats, g, groups, w, dg_dtype=None, accumu
             _c.ptr(dw_w), _c.ptr(dw_b), _c.ptr(dgamma), _c.ptr(dbeta), _c.ptr(dy_ws), _c.ptr(ws), arr, n, D, K,
             1 if accumulate else 0, _c.ptr(glu_u), _c.ptr(glu_du))
     return (glu_du if fused else dg), dw_w, dw_b, dgamma, dbeta
+
+
+def _dense_as(t, *shape):
+    """t seen as `shape` where it is dense and holds that many elements; any other tensor as it is, for the callee's checks to refuse."""
+    n = 1
+    for k in shape:
+        n *= k
+    return t.view(shape) if t.is_contiguous() and t.numel() == n else t
+
+
+def dwconv_bn_train(g, w, dw_bias, gamma, beta, running_mean, running_var, momentum, eps, s_dtype):
+    """g [B,T,D] -> (c f32 [B,T,D], stats f32 [4,D], s = SiLU(BatchNorm_train(c)) in s_dtype); running statistics updated in place.
+    dwconv_bn_train_groups on a window of this one batch."""
+    if g.dim() != 3:
+        raise ValueError("cfm.dwconv_bn_train: g must be [B,T,D]")
+    B, T, D = g.shape
+    c, stats, s = dwconv_bn_train_groups(_dense_as(g, B * T, D), [(B, T)], w, dw_bias, gamma, beta, running_mean, running_var, momentum, eps, s_dtype)
+    return c.view(B, T, D), stats.view(4, D), s.view(B, T, D)
+
+
+def dwconv_bn_train_bwd(ds, c, stats, g, w, dg_dtype):
+    """-> (dg [B,T,D], d taps [D,K], d conv bias [D], d BatchNorm gain [D], d BatchNorm bias [D]).  dwconv_bn_train_bwd_groups on a window of this
+    one batch: g [B,T,D]; ds, c [B,T,D] or [B*T,D]; stats [4,D] as dwconv_bn_train returned it."""
+    if g.dim() != 3:
+        raise ValueError("cfm.dwconv_bn_train_bwd: g must be [B,T,D]")
+    B, T, D = g.shape
+    M = B * T
+    dg, *grads = dwconv_bn_train_bwd_groups(_dense_as(ds, M, D), _dense_as(c, M, D), _dense_as(stats, 1, 4, D), _dense_as(g, M, D), [(B, T)], w, dg_dtype)
+    return (dg.view(B, T, D), *grads)
 
 
 def col2im_relu_bwd(dcol, h1, out_dtype):

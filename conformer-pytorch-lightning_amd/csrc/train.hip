@@ -1,10 +1,10 @@
 // train.hip -- the HBM-bound half of the backward pass (config 3: encoder + CTC loss + backward).
 //
-//   cfm_layernorm_bwd        d LayerNorm (+ the residual branch's gradient) and its gain / bias gradients  (encoder_layer.py:56-70)
+//   cfm_layernorm_bwd_fused  d LayerNorm (+ the residual branch's gradient) and its gain / bias gradients  (encoder_layer.py:56-70)
 //   cfm_glu_bwd              d GLU over the interleaved pointwise-conv-1 output                            (convolution.py:42)
-//   cfm_dwconv_bn_train      depthwise conv -> BatchNorm1d with BATCH statistics (all B*T rows, padded ones included: quirk Q6)
-//                            -> SiLU, running statistics updated as torch does                              (convolution.py:43-45)
-//   cfm_dwconv_bn_train_bwd  its backward: d SiLU, d BatchNorm (batch statistics), d depthwise conv (input, taps, bias)
+//   cfm_dwconv_bn_train_groups      depthwise conv -> BatchNorm1d with BATCH statistics (all B*T rows of a micro-batch, padded ones included:
+//                                   quirk Q6) -> SiLU, running statistics updated as torch does             (convolution.py:43-45)
+//   cfm_dwconv_bn_train_bwd_groups  its backward: d SiLU, d BatchNorm (batch statistics), d depthwise conv (input, taps, bias)
 //   cfm_col2im_relu_bwd      scatter-free transpose of the 3x3 stride-2 im2col (a <= 4-term gather per element) * ReLU'
 //   cfm_conv1_wgrad          tap / bias gradients of the first convolution                                  (convolution.py:60-61)
 //   cfm_adam_step            fused clip-scale + Adam update over a flat parameter buffer                    (module.py:140-143, train.sh:35)
@@ -927,20 +927,12 @@ static int layernorm_bwd_impl(const float* x, const void* dy, int32_t dy_dtype, 
     return reduce_partials(ws, nblk, 2 * D, D, 1.0f, dgamma, dbeta, s, "cfm_layernorm_bwd (reduce)");
 }
 
-extern "C" int cfm_layernorm_bwd(const float* x, const void* dy, int32_t dy_dtype, const float* gamma, const uint8_t* row_mask, const float* dres,
-                                 float* dx, float* dgamma, float* dbeta, float* ws, float eps, int64_t M, int32_t D, cfm_stream_t stream) {
-    CFM_CHECK_ARG(x && dy && gamma && dx && dgamma && dbeta && ws, "cfm_layernorm_bwd: null pointer");
-    CFM_CHECK_ARG(M > 0 && D > 0 && D % 4 == 0 && D <= 1024, "cfm_layernorm_bwd: need D %% 4 == 0 and D <= 1024 (M=%lld D=%d)", (long long)M, D);
-    CFM_CHECK_ARG(dy_dtype >= CFM_F32 && dy_dtype <= CFM_F16, "cfm_layernorm_bwd: bad dy dtype");
-    LnBwd2 none = {};
-    return layernorm_bwd_impl(x, dy, dy_dtype, gamma, row_mask, dres, dx, dgamma, dbeta, ws, false, none, eps, M, D, (hipStream_t)stream);
-}
-
 extern "C" int cfm_layernorm_bwd_fused(const cfm_ln_bwd_desc* d, cfm_stream_t stream) {
     CFM_CHECK_ARG(d && d->x && d->dy && d->gamma && d->dx && d->dgamma && d->dbeta && (d->accumulate || d->ws), "cfm_layernorm_bwd_fused: null pointer");
     CFM_CHECK_ARG(d->M > 0 && d->D > 0 && d->D % 4 == 0 && d->D <= 1024, "cfm_layernorm_bwd_fused: need D %% 4 == 0 and D <= 1024");
     CFM_CHECK_ARG(d->dy_dtype >= CFM_F32 && d->dy_dtype <= CFM_F16 && (!d->dx2 || (d->dx2_dtype >= CFM_F32 && d->dx2_dtype <= CFM_F16)), "cfm_layernorm_bwd_fused: bad dtype");
-    CFM_CHECK_ARG(d->p1 >= 0.f && d->p1 < 1.f && d->p2 >= 0.f && d->p2 < 1.f && d->M * d->D < ((int64_t)1 << 32), "cfm_layernorm_bwd_fused: p in [0,1), fewer than 2^32 elements");
+    const bool drops = d->dx2 && (d->p1 > 0.f || d->p2 > 0.f);              // the dropout counter of dx2 is the element index in 32 bits
+    CFM_CHECK_ARG(d->p1 >= 0.f && d->p1 < 1.f && d->p2 >= 0.f && d->p2 < 1.f && (!drops || d->M * d->D < ((int64_t)1 << 32)), "cfm_layernorm_bwd_fused: p in [0,1), fewer than 2^32 elements");
     LnBwd2 o2 = {};
     if (d->dx2) { o2.y = d->dx2; o2.dt = d->dx2_dtype; o2.alpha = d->alpha2; o2.d1 = cfm_make_drop(d->p1, d->seed1); o2.d2 = cfm_make_drop(d->p2, d->seed2); o2.mask = d->dx2_row_mask; }
     LnChain ch = {};
@@ -1021,21 +1013,6 @@ extern "C" int cfm_dwconv_bn_train_groups(const void* g, int32_t g_dtype, const 
     return cfm_launch_status("cfm_dwconv_bn_train (apply)");
 }
 
-extern "C" int cfm_dwconv_bn_train(const void* g, int32_t g_dtype, const float* w, const float* dw_bias, const float* gamma, const float* beta,
-                                   float* running_mean, float* running_var, float momentum, float eps, float* c_out, float* stats, void* s_out,
-                                   int32_t s_dtype, float* ws, int32_t B, int32_t T, int32_t D, int32_t ktaps, cfm_stream_t stream) {
-    cfm_train_group one = {};
-    one.B = B; one.T = T; one.row0 = 0;
-    return cfm_dwconv_bn_train_groups(g, g_dtype, w, dw_bias, gamma, beta, running_mean, running_var, momentum, eps, c_out, stats, s_out, s_dtype, ws, &one, 1, D,
-                                      ktaps, stream);
-}
-
-extern "C" int cfm_dwconv_bn_train_bwd(const void* ds, int32_t ds_dtype, const float* c, const float* stats, const void* g, int32_t g_dtype, const float* w,
-                                       void* dg_out, int32_t dg_dtype, float* dw_w, float* dw_b, float* dgamma, float* dbeta, float* dy_ws, float* ws,
-                                       int32_t B, int32_t T, int32_t D, int32_t ktaps, cfm_stream_t stream) {
-    return cfm_dwconv_bn_train_bwd_acc(ds, ds_dtype, c, stats, g, g_dtype, w, dg_out, dg_dtype, dw_w, dw_b, dgamma, dbeta, dy_ws, ws, B, T, D, ktaps, 0, stream);
-}
-
 extern "C" int cfm_dwconv_bn_train_bwd_groups(const void* ds, int32_t ds_dtype, const float* c, const float* stats, const void* g, int32_t g_dtype, const float* w,
                                               void* dg_out, int32_t dg_dtype, float* dw_w, float* dw_b, float* dgamma, float* dbeta, float* dy_ws, float* ws,
                                               const cfm_train_group* groups, int32_t n_groups, int32_t D, int32_t ktaps, int32_t accumulate, const void* glu_u,
@@ -1085,15 +1062,6 @@ extern "C" int cfm_dwconv_bn_train_bwd_groups(const void* ds, int32_t ds_dtype, 
     CfmProfScope prof("dwconv_bwd_finalize", s, 0.0, (double)blks * 16 * D * 4);
     CFM_LAUNCH(cfm_dwconv_bwd_finalize_kernel, dim3((unsigned)((16 * D + 63) / 64)), dim3(64 * RP_Q), 0, s, (const float*)part, blks, D, dw_w, dw_b, accumulate);
     return cfm_launch_status("cfm_dwconv_bn_train_bwd (reduce)");
-}
-
-extern "C" int cfm_dwconv_bn_train_bwd_acc(const void* ds, int32_t ds_dtype, const float* c, const float* stats, const void* g, int32_t g_dtype, const float* w,
-                                           void* dg_out, int32_t dg_dtype, float* dw_w, float* dw_b, float* dgamma, float* dbeta, float* dy_ws, float* ws,
-                                           int32_t B, int32_t T, int32_t D, int32_t ktaps, int32_t accumulate, cfm_stream_t stream) {
-    cfm_train_group one = {};
-    one.B = B; one.T = T; one.row0 = 0;
-    return cfm_dwconv_bn_train_bwd_groups(ds, ds_dtype, c, stats, g, g_dtype, w, dg_out, dg_dtype, dw_w, dw_b, dgamma, dbeta, dy_ws, ws, &one, 1, D, ktaps, accumulate,
-                                          nullptr, nullptr, stream);
 }
 
 extern "C" int cfm_col2im_relu_bwd(const void* dcol, int32_t dcol_dtype, const void* h1, int32_t h1_dtype, void* dh1, int32_t dh1_dtype, int32_t B, int32_t T1,

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CFM_VERSION 306 /* 0.3.6 (additive): cfm_route, cfm_encoder_layer_route (the route cfm_encoder_layer_forward would take, asked on the host), cfm_ffsplit_max_rows. 0.3.5: removed the attention input stage of the conv-in chain (cfm_rowchain_desc.att_*, cfm_layer_scratch.vt and its row stride) and the transposed-value output of the macaron chain's tail that fed it (three cfm_rowchain_desc fields); psum_out chains take no head. 0.3.4: removed cfm_ctc_nll_train (cfm_ctc_nll_train_groups is the training forward), cfm_ctc_grad requires beta (alpha is no longer overwritten), removed cfm_rnnt_desc.sweep / cfm_rnnt_packed_desc.sweep (the LDS recursion is the only one). 0.3.3: removed cfm_encoder_layer_train_forward / _backward (the stack entry points run a single block), cfm_ffn_train_forward / _supported, cfm_ffn_train_desc, cfm_pack_ffn_fragments, cfm_layer_train_weights.*_w1f / *_w2f, cfm_layer_train_io.B / T / attn_mask / am_sb / am_sq / side_stream and cfm_encoder_train_backward's n_scratch. 0.3.2 (additive, same number): packed RNN-T lattices (cfm_lattice, cfm_rnnt_packed_desc, cfm_rnnt_packed_nll / _grad, cfm_joint_act_packed / _bwd). 0.3.2 (additive, same number): the RNN-T loss (cfm_rnnt_desc, cfm_rnnt_nll, cfm_rnnt_grad) and the transducer joint's activation backward (cfm_joint_act_bwd). 0.3.2: cfm_rowchain_desc.cin_* (the conv-in chain as the input stage of the next launch). 0.3.1: row chains at D = 512, cfm_rowchain_desc.psum_out / psum_in (feed-forward split over workgroup pairs), cfm_conv12_relu at C = 512. 0.3.0: row groups in the train entry points (cfm_train_group, cfm_layer_train_io.n_groups), cfm_gemm_tn_group + deferred weight gradients, cfm_encoder_train_forward / _backward (the whole stack from one host call). 0.2.3: cfm_ffn_split, cfm_layer_scratch.psum (the feed-forward split over FF for few rows). 0.2.2: cfm_ctc_nll_train / cfm_ctc_grad take a beta buffer (both recursions in one launch); GEMM tile ids 9-11 (K groups). 0.2.1: fused front-end (cfm_conv12_relu); attention stage of the conv-in chain (cfm_rowchain_desc.att_*, cfm_layer_scratch.vt). 0.2.0: training entry points */
+#define CFM_VERSION 307 /* 0.3.7: removed cfm_dwconv_bn_train (cfm_dwconv_bn_train_groups with one group), cfm_dwconv_bn_train_bwd and cfm_dwconv_bn_train_bwd_acc (cfm_dwconv_bn_train_bwd_groups with one group; its accumulate argument) and cfm_layernorm_bwd (cfm_layernorm_bwd_fused with the descriptor's optional fields zero). 0.3.6 (additive): cfm_route, cfm_encoder_layer_route (the route cfm_encoder_layer_forward would take, asked on the host), cfm_ffsplit_max_rows. 0.3.5: removed the attention input stage of the conv-in chain (cfm_rowchain_desc.att_*, cfm_layer_scratch.vt and its row stride) and the transposed-value output of the macaron chain's tail that fed it (three cfm_rowchain_desc fields); psum_out chains take no head. 0.3.4: removed cfm_ctc_nll_train (cfm_ctc_nll_train_groups is the training forward), cfm_ctc_grad requires beta (alpha is no longer overwritten), removed cfm_rnnt_desc.sweep / cfm_rnnt_packed_desc.sweep (the LDS recursion is the only one). 0.3.3: removed cfm_encoder_layer_train_forward / _backward (the stack entry points run a single block), cfm_ffn_train_forward / _supported, cfm_ffn_train_desc, cfm_pack_ffn_fragments, cfm_layer_train_weights.*_w1f / *_w2f, cfm_layer_train_io.B / T / attn_mask / am_sb / am_sq / side_stream and cfm_encoder_train_backward's n_scratch. 0.3.2 (additive, same number): packed RNN-T lattices (cfm_lattice, cfm_rnnt_packed_desc, cfm_rnnt_packed_nll / _grad, cfm_joint_act_packed / _bwd). 0.3.2 (additive, same number): the RNN-T loss (cfm_rnnt_desc, cfm_rnnt_nll, cfm_rnnt_grad) and the transducer joint's activation backward (cfm_joint_act_bwd). 0.3.2: cfm_rowchain_desc.cin_* (the conv-in chain as the input stage of the next launch). 0.3.1: row chains at D = 512, cfm_rowchain_desc.psum_out / psum_in (feed-forward split over workgroup pairs), cfm_conv12_relu at C = 512. 0.3.0: row groups in the train entry points (cfm_train_group, cfm_layer_train_io.n_groups), cfm_gemm_tn_group + deferred weight gradients, cfm_encoder_train_forward / _backward (the whole stack from one host call). 0.2.3: cfm_ffn_split, cfm_layer_scratch.psum (the feed-forward split over FF for few rows). 0.2.2: cfm_ctc_nll_train / cfm_ctc_grad take a beta buffer (both recursions in one launch); GEMM tile ids 9-11 (K groups). 0.2.1: fused front-end (cfm_conv12_relu); attention stage of the conv-in chain (cfm_rowchain_desc.att_*, cfm_layer_scratch.vt). 0.2.0: training entry points */
 
 typedef void* cfm_stream_t;
 
@@ -689,17 +689,20 @@ int cfm_rnnt_packed_grad(const cfm_rnnt_packed_desc* d, cfm_stream_t stream);
  * Every reduction over rows is two-stage through a caller-provided f32 workspace (size from the matching *_ws function, in floats)
  * and bitwise reproducible.
  *
- * cfm_layernorm_bwd     x f32 [M,D] (the norm's INPUT; statistics are recomputed), dy [M,D] (dy_dtype), gamma [D];
- *                       dx = (dres ? dres : 0) + dLN(dy)   (dx may alias dres: the residual stream's gradient is updated in place);
- *                       rows with row_mask == 0 have dy = 0 (the masked norm_conv of convolution.py:36-37);  dgamma, dbeta f32 [D].
- *                       backward of nn.LayerNorm at encoder_layer.py:57,60,64,68,70 and encoder.py:74.   D % 4 == 0, D <= 1024.
+ * cfm_layernorm_bwd_fused: backward of nn.LayerNorm at encoder_layer.py:57,60,64,68,70 and encoder.py:74.   D % 4 == 0, D <= 1024.
+ *   x f32 [M,D] (the norm's INPUT; statistics are recomputed), dy [M,D] (dy_dtype), gamma [D];
+ *   dx = (dres ? dres : 0) + dLN(dy)   (dx may alias dres: the residual stream's gradient is updated in place);
+ *   rows with row_mask == 0 have dy = 0 (the masked norm_conv of convolution.py:36-37);  dgamma, dbeta f32 [D].
+ * Every other field of the descriptor is optional and zero in the plain backward; they fold in what a conformer block's backward does right
+ * before and after it:
+ *   accumulate != 0 : dgamma / dbeta are ADDED to with f32 atomics in the same launch (no workspace pass, ws may be NULL; the caller zero-fills
+ *                     them or carries a running sum; summation order varies from run to run) -- 0: two-stage through ws
+ *                     (cfm_layernorm_bwd_ws(M, D) floats), overwritten, reproducible;
+ *   dx2 != NULL     : also writes dropout(alpha2 * dx) in dx2_dtype -- the next residual branch's gradient as a GEMM operand, exactly
+ *                     cfm_dropout_rows(dx, .., alpha2, p1, seed1, p2, seed2) without its launch.  With p1 > 0 or p2 > 0 the dropout counter
+ *                     limits the call to M * D < 2^32 elements.
  */
 int64_t cfm_layernorm_bwd_ws(int64_t M, int32_t D);
-/* The same backward with two launches folded in (what a conformer block's backward does right before and after it):
- *   accumulate != 0 : dgamma / dbeta are ADDED to with f32 atomics in the same launch (no workspace pass; the caller zero-fills them or
- *                     carries a running sum; summation order varies from run to run) -- 0: two-stage through ws, overwritten, reproducible;
- *   dx2 != NULL     : also writes dropout(alpha2 * dx) in dx2_dtype -- the next residual branch's gradient as a GEMM operand, exactly
- *                     cfm_dropout_rows(dx, .., alpha2, p1, seed1, p2, seed2) without its launch. */
 typedef struct {
     const float* x;
     const void* dy;
@@ -720,8 +723,6 @@ typedef struct {
     float *chain_dgamma, *chain_dbeta;
 } cfm_ln_bwd_desc;
 int cfm_layernorm_bwd_fused(const cfm_ln_bwd_desc* d, cfm_stream_t stream);
-int cfm_layernorm_bwd(const float* x, const void* dy, int32_t dy_dtype, const float* gamma, const uint8_t* row_mask, const float* dres,
-                      float* dx, float* dgamma, float* dbeta, float* ws, float eps, int64_t M, int32_t D, cfm_stream_t stream);
 
 /* GLU backward (convolution.py:42) on the column-interleaved layout the pointwise-conv-1 GEMM writes through cfm_gemm_desc.C_pre:
  * u [M,2D] (blocks of 16 value columns followed by their 16 gate columns), dg [M,D] -> du [M,2D] same layout.  D % 16 == 0. */
@@ -738,32 +739,23 @@ typedef struct {
     int64_t am_sb, am_sq;
 } cfm_train_group;
 
-/* Depthwise conv (15 taps) -> BatchNorm1d in TRAINING mode -> SiLU  (convolution.py:43-45 under module.train()):
- *   c = dw(g) + bias            -> c_out f32 [B,T,D]  (kept for the backward)
- *   batch mean / biased variance over ALL B*T rows of each channel, padded frames included
- *   stats f32 [4][D] = mean, rstd, scale = gamma*rstd, shift = beta - mean*scale;   s_out = SiLU(c*scale + shift)  (s_dtype)
- *   running_mean / running_var (optional) are updated in place with `momentum` and the UNBIASED variance, as torch does.
- * cfm_dwconv_bn_train_bwd: ds = d loss / d s_out -> dg_out = d loss / d g, and the gradients of the taps dw_w [D,15], the conv bias
- * dw_b [D], the BatchNorm gain / bias dgamma, dbeta [D].  dy_ws: f32 [B*T,D] scratch.  ws: cfm_dwconv_bn_ws(B,T,D) floats (both). */
+/* Depthwise conv (15 taps) -> BatchNorm1d in TRAINING mode -> SiLU  (convolution.py:43-45 under module.train()), over the micro-batches of a
+ * training window (cfm_train_group; csrc/train_layer.cpp; a single batch is a window of one group with row0 = 0).  g / c_out / s_out are the window's
+ * [M, D] row matrices, M = the sum of B*T over the groups; every stage is ONE launch for all groups, each group with its own batch statistics:
+ *   c = dw(g) + bias            -> c_out f32 [M,D]  (kept for the backward); the taps see zeros before frame 0 and after frame T-1 of each utterance
+ *   batch mean / biased variance of each channel over ALL B*T rows of the group, padded frames included
+ *   stats f32 [n_groups][4][D] = mean, rstd, scale = gamma*rstd, shift = beta - mean*scale;   s_out = SiLU(c*scale + shift)  (s_dtype)
+ *   running_mean / running_var (optional, both or neither) are updated in place with `momentum` and the UNBIASED variance, as torch does, group
+ *   after group in the order of the table.
+ * cfm_dwconv_bn_train_bwd_groups: ds [M,D] = d loss / d s_out, with c and stats as the forward left them -> dg_out [M,D] = d loss / d g, and the
+ * gradients of the taps dw_w [D,15], the conv bias dw_b [D], the BatchNorm gain / bias dgamma, dbeta [D], each summed over the groups.
+ *   accumulate != 0: the four parameter gradients are added to what the buffers hold (one writer per element: reproducible) instead of
+ *   overwritten -- a gradient buffer shared by the micro-batches of an optimizer step.
+ *   glu_u / glu_du (both or neither; dtype = g_dtype = dg_dtype): the GLU backward of convolution.py:42 in the depthwise launch -- u [M,2D] the
+ *   pre-GLU columns (cfm_gemm_desc.C_pre layout), du [M,2D] their gradient; dg_out is then not written (may be NULL).  Same values as
+ *   cfm_glu_bwd on the rounded dg.
+ * dy_ws: f32 [M,D] scratch.  ws (both directions): the sum of cfm_dwconv_bn_ws(B,T,D) floats over the groups.  D % 4 == 0, D <= 512. */
 int64_t cfm_dwconv_bn_ws(int32_t B, int32_t T, int32_t D);
-int cfm_dwconv_bn_train(const void* g, int32_t g_dtype, const float* w, const float* dw_bias, const float* gamma, const float* beta,
-                        float* running_mean, float* running_var, float momentum, float eps, float* c_out, float* stats, void* s_out,
-                        int32_t s_dtype, float* ws, int32_t B, int32_t T, int32_t D, int32_t ktaps, cfm_stream_t stream);
-int cfm_dwconv_bn_train_bwd(const void* ds, int32_t ds_dtype, const float* c, const float* stats, const void* g, int32_t g_dtype, const float* w,
-                            void* dg_out, int32_t dg_dtype, float* dw_w, float* dw_b, float* dgamma, float* dbeta, float* dy_ws, float* ws,
-                            int32_t B, int32_t T, int32_t D, int32_t ktaps, cfm_stream_t stream);
-/* accumulate != 0: the four parameter gradients (dw_w, dw_b, dgamma, dbeta) are added to what the buffers hold (one writer per element:
- * reproducible) instead of overwritten -- a gradient buffer shared by the micro-batches of an optimizer step. */
-int cfm_dwconv_bn_train_bwd_acc(const void* ds, int32_t ds_dtype, const float* c, const float* stats, const void* g, int32_t g_dtype, const float* w,
-                                void* dg_out, int32_t dg_dtype, float* dw_w, float* dw_b, float* dgamma, float* dbeta, float* dy_ws, float* ws,
-                                int32_t B, int32_t T, int32_t D, int32_t ktaps, int32_t accumulate, cfm_stream_t stream);
-
-/* Front-end backward (convolution.py:60-63).  cfm_col2im_relu_bwd: dcol [B*T2*F2, 9*C] = dh2 . W2 (cfm_gemm on the transposed conv2 pack,
- * K order (kt,kf,c)) -> dh1 [B,T1,F1,C] = ReLU'(h1) * (transposed im2col of dcol).  cfm_conv1_wgrad: dh1 and the fbank input x [B,T,F]
- * (global CMVN folded as in cfm_conv1_relu) -> dw [9,C] tap-major, db [C]. */
-/* The same two entry points over the micro-batches of a training window (cfm_train_group; csrc/train_layer.cpp): g / c / s / ds / dg / dy_ws are the
- * window's [M, D] row matrices, stats is [n_groups][4*D]; every stage is ONE launch for all micro-batches, each with its own batch statistics,
- * the running statistics updated micro-batch after micro-batch.  ws: the sum of cfm_dwconv_bn_ws over the groups. */
 int cfm_dwconv_bn_train_groups(const void* g, int32_t g_dtype, const float* w, const float* dw_bias, const float* gamma, const float* beta,
                                float* running_mean, float* running_var, float momentum, float eps, float* c_out, float* stats, void* s_out,
                                int32_t s_dtype, float* ws, const cfm_train_group* groups, int32_t n_groups, int32_t D, int32_t ktaps, cfm_stream_t stream);
@@ -771,9 +763,10 @@ int cfm_dwconv_bn_train_bwd_groups(const void* ds, int32_t ds_dtype, const float
                                    void* dg_out, int32_t dg_dtype, float* dw_w, float* dw_b, float* dgamma, float* dbeta, float* dy_ws, float* ws,
                                    const cfm_train_group* groups, int32_t n_groups, int32_t D, int32_t ktaps, int32_t accumulate, const void* glu_u,
                                    void* glu_du, cfm_stream_t stream);
-/* glu_u / glu_du (both or neither; dtype = g_dtype = dg_dtype): the GLU backward of convolution.py:42 in the depthwise launch -- u [M,2D] the
- * pre-GLU columns (cfm_gemm_desc.C_pre layout), du [M,2D] their gradient; dg_out is then not written (may be NULL).  Same values as
- * cfm_glu_bwd on the rounded dg. */
+
+/* Front-end backward (convolution.py:60-63).  cfm_col2im_relu_bwd: dcol [B*T2*F2, 9*C] = dh2 . W2 (cfm_gemm on the transposed conv2 pack,
+ * K order (kt,kf,c)) -> dh1 [B,T1,F1,C] = ReLU'(h1) * (transposed im2col of dcol).  cfm_conv1_wgrad: dh1 and the fbank input x [B,T,F]
+ * (global CMVN folded as in cfm_conv1_relu) -> dw [9,C] tap-major, db [C]. */
 int cfm_col2im_relu_bwd(const void* dcol, int32_t dcol_dtype, const void* h1, int32_t h1_dtype, void* dh1, int32_t dh1_dtype, int32_t B, int32_t T1,
                         int32_t F1, int32_t C, cfm_stream_t stream);
 int64_t cfm_conv1_wgrad_ws(int32_t B, int32_t T, int32_t C);

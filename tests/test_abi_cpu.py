@@ -25,13 +25,13 @@ def cfm():
     return c
 
 
-def test_library_exports_every_declared_symbol_at_abi_306(cfm):
+def test_library_exports_every_declared_symbol_at_abi_307(cfm):
     lib = cfm.lib()
     names = declared_functions()
     assert len(names) >= 20 and "cfm_gemm" in names and "cfm_ffn_fused" in names and "cfm_encoder_layer_forward" in names
     for n in names:
         assert hasattr(lib, n), "libconformer_gfx950.so does not export %s" % n
-    assert lib.cfm_version() == 306
+    assert lib.cfm_version() == 307
     assert isinstance(lib.cfm_last_error(), bytes)
 
 
@@ -64,7 +64,7 @@ def test_every_prototype_matches_the_header(tmp_path):
 
 def test_header_is_plain_c(tmp_path):
     src = tmp_path / "c.c"
-    src.write_text('#include "cfm.h"\nint main(void){return CFM_VERSION == 306 ? 0 : 1;}\n')
+    src.write_text('#include "cfm.h"\nint main(void){return CFM_VERSION == 307 ? 0 : 1;}\n')
     subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(tmp_path / "c")], check=True)
 
 

@@ -382,8 +382,11 @@ def test_layernorm_bwd(cfm, M, D, dyt):
         drv = G.io(dres, name="dres = dx") if in_place else G.inp(dres, name="dres")
         dx = drv if in_place else G.out((M, D), F32, name="dx")
         dg, db, ws = G.out((D,), F32, name="dgamma"), G.out((D,), F32, name="dbeta"), G.ws(L.cfm_layernorm_bwd_ws(M, D), name="ws")
-        cfm.check(L.cfm_layernorm_bwd(xv.data_ptr(), dyv.data_ptr(), cfm.dt_code(dy), gv.data_ptr(), mv.data_ptr(), drv.data_ptr(), dx.data_ptr(), dg.data_ptr(),
-                                      db.data_ptr(), ws.data_ptr(), 1e-5, M, D, cfm.stream()), "cfm_layernorm_bwd")
+        d = cfm.LnBwdDesc()                 # the plain (non-accumulating, no-dx2) descriptor: every other field zero
+        d.x, d.dy, d.gamma, d.row_mask, d.dres = xv.data_ptr(), dyv.data_ptr(), gv.data_ptr(), mv.data_ptr(), drv.data_ptr()
+        d.dx, d.dgamma, d.dbeta, d.ws = dx.data_ptr(), dg.data_ptr(), db.data_ptr(), ws.data_ptr()
+        d.M, d.D, d.dy_dtype, d.eps = M, D, cfm.dt_code(dy), 1e-5
+        cfm.check(L.cfm_layernorm_bwd_fused(ctypes.byref(d), cfm.stream()), "cfm_layernorm_bwd_fused")
         close(dx, xr.grad + dres.double(), 2e-5, "dx")
         close(dg, gr.grad, 2e-5, "dgamma")
         close(db, br.grad, 2e-5, "dbeta")
@@ -393,9 +396,9 @@ def test_layernorm_bwd(cfm, M, D, dyt):
 @pytest.mark.parametrize("M,D", LN_SHAPES)
 @pytest.mark.parametrize("variant", ["overwrite", "accumulate", "chain"])
 def test_layernorm_bwd_fused(cfm, M, D, variant):
-    """cfm_layernorm_bwd_fused with EVERY pointer of its descriptor placed, against what tests/test_train_ops_gpu.py compares it with: cfm_layernorm_bwd for dx and
+    """cfm_layernorm_bwd_fused with EVERY pointer of its descriptor placed, against what tests/test_train_ops_gpu.py compares it with: the plain (non-accumulating, no-dx2) descriptor for dx and
     the parameter sums (identical through the workspace; 1e-5 on top of a running sum with atomics), cfm_dropout_rows on dx for the 16-bit second output.
-    chain: dx = dLN(dres + dLN(dy; x, gamma); chain_x, chain_gamma) against the two cfm_layernorm_bwd calls it folds, at that op's own 2e-5."""
+    chain: dx = dLN(dres + dLN(dy; x, gamma); chain_x, chain_gamma) against the two plain calls it folds, at that op's own 2e-5."""
     acc, chain = int(variant != "overwrite"), variant == "chain"
     x, dy, dres, gamma = rnd((M, D), 17), rnd((M, D), 18), rnd((M, D), 21), 1 + rnd((D,), 19, 0.1)
     mask = u8(torch.rand(M, generator=torch.Generator().manual_seed(22)) > 0.3).cuda()
@@ -940,10 +943,13 @@ def test_dwconv_bn_train_fwd_bwd(cfm, B, T, D, dt):
     G = Guards()
     gv, wv, bv, gav, bev = G.inp(g, name="g"), G.inp(w, name="w"), G.inp(bias, name="dw_bias"), G.inp(gamma, name="gamma"), G.inp(beta, name="beta")
     rm, rv = G.io(rm0, name="running_mean"), G.io(rv0, name="running_var")
-    c, stats, s = G.out((B, T, D), F32, name="c"), G.out((4, D), F32, name="stats"), G.out((B, T, D), dt, name="s")
+    c, stats, s = G.out((B, T, D), F32, name="c"), G.out((1, 4, D), F32, name="stats"), G.out((B, T, D), dt, name="s")
     ws = G.ws(L.cfm_dwconv_bn_ws(B, T, D), name="ws")
-    cfm.check(L.cfm_dwconv_bn_train(gv.data_ptr(), cfm.dt_code(dt), wv.data_ptr(), bv.data_ptr(), gav.data_ptr(), bev.data_ptr(), rm.data_ptr(), rv.data_ptr(), 0.1, 1e-5,
-                                    c.data_ptr(), stats.data_ptr(), s.data_ptr(), cfm.dt_code(dt), ws.data_ptr(), B, T, D, K, cfm.stream()), "cfm_dwconv_bn_train")
+    one = (cfm.TrainGroup * 1)()
+    one[0].B, one[0].T, one[0].row0 = B, T, 0
+    cfm.check(L.cfm_dwconv_bn_train_groups(gv.data_ptr(), cfm.dt_code(dt), wv.data_ptr(), bv.data_ptr(), gav.data_ptr(), bev.data_ptr(), rm.data_ptr(), rv.data_ptr(), 0.1,
+                                           1e-5, c.data_ptr(), stats.data_ptr(), s.data_ptr(), cfm.dt_code(dt), ws.data_ptr(), one, 1, D, K, cfm.stream()),
+              "cfm_dwconv_bn_train_groups")
     close(c, cr.transpose(1, 2), 1e-5, "c")
     close(s, sr, 1e-5 if dt == F32 else 1e-2, "s")
     close(rm, rmr, 1e-5, "running_mean")
@@ -952,7 +958,7 @@ def test_dwconv_bn_train_fwd_bwd(cfm, B, T, D, dt):
     mean, var = cr.detach().mean((0, 2)), cr.detach().var((0, 2), unbiased=False)
     rstd = (var + 1e-5).rsqrt()
     for i, (name, ref) in enumerate((("mean", mean), ("rstd", rstd), ("scale", gamma.double() * rstd), ("shift", beta.double() - mean * gamma.double() * rstd))):
-        close(stats[i], ref, 1e-5, "stats: " + name)             # the f32 bound this op's test uses for c and the running statistics
+        close(stats[0, i], ref, 1e-5, "stats: " + name)             # the f32 bound this op's test uses for c and the running statistics
     G.check()
     ds = rnd((B, T, D), 30).to(dt)
     sr.backward(ds.double())
@@ -965,11 +971,8 @@ def test_dwconv_bn_train_fwd_bwd(cfm, B, T, D, dt):
                [G2.out(p.shape, F32, name=n) for p, n in zip(prior, ("dw_w", "dw_b", "dgamma", "dbeta"))]
         dy_ws, ws2 = G2.ws(B * T * D, name="dy_ws"), G2.ws(L.cfm_dwconv_bn_ws(B, T, D), name="ws")
         args = [dsv.data_ptr(), cfm.dt_code(dt), cv.data_ptr(), stv.data_ptr(), gv2.data_ptr(), cfm.dt_code(dt), wv2.data_ptr(), dg.data_ptr(), cfm.dt_code(dt)] + \
-               [o.data_ptr() for o in outs] + [dy_ws.data_ptr(), ws2.data_ptr(), B, T, D, K]
-        if acc:
-            cfm.check(L.cfm_dwconv_bn_train_bwd_acc(*args, 1, cfm.stream()), "cfm_dwconv_bn_train_bwd_acc")
-        else:
-            cfm.check(L.cfm_dwconv_bn_train_bwd(*args, cfm.stream()), "cfm_dwconv_bn_train_bwd")
+               [o.data_ptr() for o in outs] + [dy_ws.data_ptr(), ws2.data_ptr(), one, 1, D, K]
+        cfm.check(L.cfm_dwconv_bn_train_bwd_groups(*args, acc, None, None, cfm.stream()), "cfm_dwconv_bn_train_bwd_groups")
         base = [p.double() if acc else torch.zeros_like(p, dtype=torch.float64) for p in prior]
         close(dg, gr.grad, 1e-4 if dt == F32 else 1e-2, "dg")
         close(outs[0].double() - base[0], wr.grad, 1e-4, "dw_w")

@@ -59,7 +59,7 @@ def test_packed_mel_table_equals_the_dense_banks():
 def test_fbank_desc_matches_c():
     import cfm
     lib = cfm.lib()
-    assert hasattr(lib, "cfm_fbank") and hasattr(lib, "cfm_fbank_stream") and lib.cfm_version() == 306
+    assert hasattr(lib, "cfm_fbank") and hasattr(lib, "cfm_fbank_stream") and lib.cfm_version() == 307
 
 
 def test_no_cpu_path_and_window_limit():

@@ -103,10 +103,10 @@ def _declared():
     return set(re.findall(r"\b(cfm_[a-z0-9_]+)\s*\(", text))
 
 
-def test_header_declares_and_library_exports_the_packed_entries_at_abi_306(cfm):
+def test_header_declares_and_library_exports_the_packed_entries_at_abi_307(cfm):
     names = _declared()
     lib = cfm.lib()
     for n in NEW_ENTRIES:
         assert n in names, "include/cfm.h does not declare %s" % n
         assert hasattr(lib, n), "libconformer_gfx950.so does not export %s" % n
-    assert lib.cfm_version() == 306
+    assert lib.cfm_version() == 307

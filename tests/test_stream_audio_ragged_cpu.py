@@ -101,7 +101,7 @@ def test_fbank_desc_ragged_fields_match_c():
     import cfm
     fields = ("seed", "n_new", "final", "carry_len_in", "carry_len_out", "frame_lens", "carry_cap")
     assert [n for n, _ in cfm.FbankDesc._fields_][-6:] == list(fields[1:])           # appended: every earlier field keeps its offset
-    assert cfm.lib().cfm_version() == 306 and callable(cfm.fbank_stream_ragged)
+    assert cfm.lib().cfm_version() == 307 and callable(cfm.fbank_stream_ragged)
 
 
 def test_loud_failures():

@@ -491,7 +491,7 @@ def test_pack_kernel_equals_torch_packs(mode):
 
 @pytest.mark.parametrize("accumulate", [0, 1])
 def test_layernorm_bwd_fused_equals_separate_launches(accumulate):
-    """cfm_layernorm_bwd_fused: dx identical to cfm_layernorm_bwd; the second output identical to cfm_dropout_rows on dx (two dropouts, bf16);
+    """cfm_layernorm_bwd_fused: dx identical to the plain (non-accumulating, no-dx2) descriptor; the second output identical to cfm_dropout_rows on dx (two dropouts, bf16);
     parameter gradients identical through the workspace (accumulate = 0) and added on top of what is there by atomics (accumulate = 1: order of
     the f32 sums differs, 1e-5)."""
     import ctypes

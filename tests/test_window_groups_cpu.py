@@ -1,4 +1,4 @@
-"""CPU (no GPU): the grouped window entry points (cfm_dwconv_bn_train(_bwd)_groups, cfm_attention(_bwd)_group, cfm_ctc_nll_train_groups) refuse what
+"""CPU (no GPU): the grouped window entry points (cfm_dwconv_bn_train_groups, cfm_dwconv_bn_train_bwd_groups, cfm_attention(_bwd)_group, cfm_ctc_nll_train_groups) refuse what
 they cannot run BEFORE their first launch, with a message that names the cause.  All device pointers are made-up addresses (as in
 tests/test_layer_route_cpu.py): a check that came late would show as a launch error instead of the argument error."""
 import os

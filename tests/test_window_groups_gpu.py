@@ -1,4 +1,4 @@
-"""GPU: the grouped window kernels op by op -- cfm_attention_group, cfm_attention_bwd_group, cfm_dwconv_bn_train(_bwd)_groups and
+"""GPU: the grouped window kernels op by op -- cfm_attention_group, cfm_attention_bwd_group, cfm_dwconv_bn_train_groups, cfm_dwconv_bn_train_bwd_groups and
 cfm_ctc_nll_train_groups with more than one problem -- at the smallest shapes that reach their edges.
 
 Every case places every pointer operand with tests/extent.py (inputs between NaN bands, outputs pre-filled with NaN, workspaces at exactly the
