@@ -377,12 +377,13 @@ def layer_grad_layout(layer, offsets=None):
     """Where each parameter's gradient lives in the block's flat gradient slab: {name: (offset, numel)} in floats (16-byte aligned), the slab
     length, and the device row-offset maps of the two fused products.  offsets: a ready-made {name: offset} (the data-parallel trainer's
     bucket layout) or None for a private slab in named_parameters order.  A block without a conv-module bias or BatchNorm affine gets a
-    discard region at the end of its private slab ("discard": its offset) where those gradients go.  Cached on the layer per layout."""
+    discard region at the end of its private slab ("discard": its offset) where those gradients go.  Cached on the layer per layout, in a
+    slot keyed on the parameters' device."""
     key = None if offsets is None else tuple(sorted(offsets.items()))
-    cache = layer.__dict__.setdefault("_grad_layout", {})
-    hit = cache.get(key)
     dev = next(layer.parameters()).device
-    if hit is not None and hit["device"] == dev:
+    cache = packing.slot(layer, "_grad_layout").get(dev, dict)
+    hit = cache.get(key)
+    if hit is not None:
         return hit
     lay, n = {}, 0
     for name, p in layer.named_parameters():
@@ -404,7 +405,7 @@ def layer_grad_layout(layer, offsets=None):
     idx = packing.glu_interleave_index(D, torch.device("cpu"))            # GEMM row j of the interleaved pack = reference row idx[j]
     pw1_row = lay["conv_module.pointwise_conv1.weight"][0] + idx * D
     pw1_bias = lay["conv_module.pointwise_conv1.bias"][0] + idx if "conv_module.pointwise_conv1.bias" in lay else discard + idx
-    hit = dict(device=dev, layout=lay, numel=n, discard=discard, qkv_row=qkv_row.to(dev), qkv_bias=qkv_bias.to(dev), pw1_row=pw1_row.to(dev),
+    hit = dict(layout=lay, numel=n, discard=discard, qkv_row=qkv_row.to(dev), qkv_bias=qkv_bias.to(dev), pw1_row=pw1_row.to(dev),
                pw1_bias=pw1_bias.to(dev))
     if "self_attn.pos_bias_u" in lay:                                    # pos_bias_u as a second destination of linear_q.bias' column sums
         u0 = lay["self_attn.pos_bias_u"][0]
@@ -492,10 +493,11 @@ def _stack_grads(owner, layers, bases, lays, tag, u_table):
     cached dicts); cached per destination and layout.  u_table: pos_bias_u as a second destination of linear_q.bias' column sums (what the
     grouped weight gradients need) instead of a copy after the product."""
     key = (tag, u_table, tuple(bases), tuple(id(lay) for lay in lays))
-    hit = owner.__dict__.get("_stack_g")
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    arr = (cfm.LayerTrainGrads * len(layers))()
+    return packing.slot(owner, "_stack_g").get(key, lambda: _build_stack_grads(bases, lays, u_table))[0]
+
+
+def _build_stack_grads(bases, lays, u_table):
+    arr = (cfm.LayerTrainGrads * len(lays))()
     for g, base, lay in zip(arr, bases, lays):
         g.slab = base
         for name, field in _GRAD_FIELDS.items():
@@ -507,8 +509,7 @@ def _stack_grads(owner, layers, bases, lays, tag, u_table):
         g.qkv_row_off, g.qkv_bias_off, g.pw1_row_off, g.pw1_bias_off = (lay[k].data_ptr() for k in ("qkv_row", "qkv_bias", "pw1_row", "pw1_bias"))
         if u_table and "qkv_bias2" in lay:
             g.qkv_bias_off2 = lay["qkv_bias2"].data_ptr()
-    owner.__dict__["_stack_g"] = (key, arr)
-    return arr
+    return arr, lays                                                # the layouts stay alive with the array keyed on their identity
 
 
 def _param_grads(layers, slabs, lays):
@@ -681,20 +682,20 @@ def stack_supported(layers, n_groups):
 
 
 def _stack_weights(owner, layers, prec, flat):
-    """ctypes array of the blocks' weight structs (cached while the packs stay the same objects and _inplace_ptrs the same addresses)."""
+    """ctypes array of the blocks' weight structs (cached while the packs stay the same objects and _inplace_ptrs the same addresses; the
+    slot keeps the packs alive beside the array)."""
     pks = packing.pack_stack_train(owner, layers, prec, layers[0].use_relative, flat)
-    hit = owner.__dict__.get("_stack_w")
-    ptrs = tuple(_inplace_ptrs(l) for l in layers)
-    if hit is not None and len(hit[0]) == len(pks) and all(a is b for a, b in zip(hit[0], pks)) and hit[2] == ptrs:
-        for w, l in zip(hit[1], layers):
-            bn = l.conv_module.norm
-            if bn.momentum is None:                             # cumulative moving average: the factor follows the batch count
-                w.bn_momentum = 1.0 / float(int(bn.num_batches_tracked) + 1)
-        return hit[1], pks
-    arr = (cfm.LayerTrainWeights * len(layers))()
-    for i, (l, pk) in enumerate(zip(layers, pks)):
-        arr[i] = _build_train_weights_struct(l, pk)
-    owner.__dict__["_stack_w"] = (pks, arr, ptrs)
+
+    def build():
+        arr = (cfm.LayerTrainWeights * len(layers))()
+        for i, (l, pk) in enumerate(zip(layers, pks)):
+            arr[i] = _build_train_weights_struct(l, pk)
+        return arr, pks
+    arr = packing.slot(owner, "_stack_w").get((tuple(id(pk) for pk in pks), tuple(_inplace_ptrs(l) for l in layers)), build)[0]
+    for w, l in zip(arr, layers):
+        bn = l.conv_module.norm
+        if bn.momentum is None:                                 # cumulative moving average: the factor follows the batch count
+            w.bn_momentum = 1.0 / float(int(bn.num_batches_tracked) + 1)
     return arr, pks
 
 

@@ -3,8 +3,9 @@
 The nn.Modules keep the reference's parameter names / shapes / dtypes (so state_dicts, optimizers and DDP see what they
 expect); the kernels want: 16-bit (or hi/lo bf16 split) [N,K] matrices, a fused QKV matrix, the pointwise-conv-1
 rows interleaved for the in-register GLU, BatchNorm folded to scale/shift, conv kernels reordered to the implicit-GEMM K
-order.  A pack is rebuilt only when a source tensor's version counter / storage / device changes or the precision mode
-changes (in-place optimizer steps bump ``_version``).
+order.  Everything derived from weights -- packs, launch plans, ctypes structs of raw device pointers -- sits in a Slot on its module and
+is rebuilt when weights_key changes: the pack epoch, the precision mode, or a source tensor's address, version counter (in-place
+optimizer steps bump it), device or dtype.
 """
 import torch
 
@@ -20,8 +21,30 @@ def bump_epoch():
     _EPOCH[0] += 1
 
 
-def _key(tensors, prec):
-    return (prec.name, _EPOCH[0]) + tuple((t.data_ptr(), t._version, str(t.device), t.dtype) for t in tensors if t is not None)
+def weights_key(tensors, *extra):
+    """THE answer to "have these weights changed?": (pack epoch,) + extra (a precision name, a tag) + (address, version counter, device,
+    dtype) per tensor; None entries are skipped.  In-place updates move the version counter, `p.data = ...` / a replaced Parameter / .to()
+    the address, device or dtype, raw-pointer writes (bump_epoch) the epoch.  The only reader of the epoch and of the version counters
+    besides its cheap variant graph_watch."""
+    return (_EPOCH[0],) + extra + tuple((t.data_ptr(), t._version, str(t.device), t.dtype) for t in tensors if t is not None)
+
+
+def graph_watch(owner):
+    """What a captured graph's owner (owner.enc: its encoder) compares before every replay: changes whenever a parameter / buffer of
+    owner.enc is updated in place or every pack is invalidated -- the graph holds raw pointers to the PACKED weights of the capture and
+    must be re-captured then.  The cheap variant of weights_key: it runs before every replayed step, so it is one attribute read per tensor
+    (~50 us for the 12-block encoder) over a tensor list built ONCE per owner, with the addresses summed at that moment (.to() /
+    load_state_dict keep storage), where the full key would allocate a 300-tuple per streaming step.
+    Its one known limit: a Parameter OBJECT replaced under a captured graph (`blk.norm_ff.weight = nn.Parameter(...)`) is not in the list
+    and is not seen until the graph is dropped for another reason."""
+    s = slot(owner, "_watch")
+    if s.value is None:
+        s.value = list(owner.enc.parameters()) + list(owner.enc.buffers())
+        s.key = sum(t.data_ptr() for t in s.value)
+    v = 0
+    for t in s.value:
+        v += t._version
+    return _EPOCH[0], v, s.key, str(_c.resolve_precision(owner.enc))
 
 
 class Packed:
@@ -31,36 +54,41 @@ class Packed:
         self.__dict__.update(kw)
 
 
-class PackCache:
+class Slot:
+    """One cached value and the key it was built for -- the one way derived state is kept on a module (or on any object with a __dict__).
+    A copy (copy.deepcopy, pickle, torch.save) starts EMPTY: ctypes pointers cannot be pickled, a copied pointer would still address the
+    original's memory, and the packs belong to the original's tensors."""
+
     def __init__(self):
-        self._key = None
-        self._val = None
+        self.key = self.value = None
 
     def __reduce__(self):
-        # copy.deepcopy / pickle / torch.save of a module: the copy starts with an empty cache (the packs belong to the original's tensors)
-        return (PackCache, ())
+        return (type(self), ())
+
+    def clear(self):
+        self.key = self.value = None
+
+    def get(self, key, build):
+        if key != self.key:
+            with torch.no_grad():
+                self.value = build()
+            self.key = key
+        return self.value
+
+
+class PackCache(Slot):
+    """The slot of a module's weight pack (constructed in the module's __init__), keyed on its source tensors and the precision mode."""
 
     def get(self, tensors, prec, build):
-        k = _key(tensors, prec)
-        if k != self._key:
-            with torch.no_grad():
-                self._val = build()
-            self._key = k
-        return self._val
+        return Slot.get(self, weights_key(tensors, prec.name), build)
 
 
-# What the train and inference paths cache on a module's __dict__ besides PackCache objects: packed weights, plans whose launch tables hold the
-# source tensors' addresses, ctypes structs of raw device pointers.  None of it may survive a copy (copy.deepcopy, pickle, torch.save): ctypes
-# pointers cannot be pickled, and a copied pointer would still address the original's memory.
-MODULE_CACHES = ("_fused", "_grad_layout", "_stack_w", "_stack_g", "_pack_stack_train")
-
-
-def state_without_caches(state):
-    """A module's __getstate__ dict without MODULE_CACHES (a new dict; `_fused`, an attribute set in __init__, becomes None)."""
-    out = {k: v for k, v in state.items() if k not in MODULE_CACHES}
-    if "_fused" in state:
-        out["_fused"] = None
-    return out
+def slot(mod, name, cls=Slot):
+    """The slot mod.__dict__[name], created empty on first use."""
+    try:
+        return mod.__dict__[name]
+    except KeyError:
+        return mod.__dict__.setdefault(name, cls())
 
 
 def f32(t):
@@ -254,12 +282,8 @@ def matrix_t(w, prec):
     return matrix(w.detach().t(), prec)
 
 
-def _train_cache(mod):
-    pc = mod.__dict__.get("_pack_train")
-    if pc is None:
-        pc = PackCache()
-        mod.__dict__["_pack_train"] = pc
-    return pc
+def _train_slot(mod):
+    return slot(mod, "_pack_train", PackCache)
 
 
 def pack_ffn_train(mod, prec):
@@ -269,7 +293,7 @@ def pack_ffn_train(mod, prec):
         w1t, w1tl = matrix_t(mod.w_1.weight, prec)
         w2t, w2tl = matrix_t(mod.w_2.weight, prec)
         return Packed(w1=w1, w1_lo=w1l, b1=f32(mod.w_1.bias), w2=w2, w2_lo=w2l, b2=f32(mod.w_2.bias), w1t=w1t, w1t_lo=w1tl, w2t=w2t, w2t_lo=w2tl)
-    return _train_cache(mod).get([mod.w_1.weight, mod.w_1.bias, mod.w_2.weight, mod.w_2.bias], prec, build)
+    return _train_slot(mod).get([mod.w_1.weight, mod.w_1.bias, mod.w_2.weight, mod.w_2.bias], prec, build)
 
 
 def pack_mhsa_train(mod, prec, relative):
@@ -290,7 +314,7 @@ def pack_mhsa_train(mod, prec, relative):
         qkv_b = torch.cat([bq, mod.linear_k.bias.detach().float(), mod.linear_v.bias.detach().float()], 0).contiguous()
         return Packed(qkv_w=qkv, qkv_w_lo=qkvl, qkv_t=qkvt, qkv_t_lo=qkvtl, qkv_b=qkv_b, out_w=out, out_w_lo=outl, out_t=outt, out_t_lo=outtl,
                       out_b=f32(mod.linear_out.bias))
-    return _train_cache(mod).get(srcs, prec, build)
+    return _train_slot(mod).get(srcs, prec, build)
 
 
 def pack_conv_module_train(mod, prec):
@@ -309,7 +333,7 @@ def pack_conv_module_train(mod, prec):
         pw2, pw2l = matrix(w2, prec)
         pw2t, pw2tl = matrix_t(w2, prec)
         return conv_module_train_pack(mod, idx, b1[idx], (pw1, pw1l, pw1t, pw1tl), (pw2, pw2l, pw2t, pw2tl))
-    return _train_cache(mod).get(srcs, prec, build)
+    return _train_slot(mod).get(srcs, prec, build)
 
 
 def conv_module_train_pack(mod, idx, pw1_b, pw1, pw2):
@@ -431,21 +455,24 @@ class _StackPackPlan:
 def pack_stack_train(owner, layers, prec, relative, flat=False):
     """((macaron FFN, attention, conv module, FFN) training packs) per block for the whole stack, two launches when anything changed.
     flat: every parameter lives in the data-parallel trainer's flat buffer and changes only through its step (which bumps the pack epoch) --
-    the per-tensor version walk (~300 tensors) is skipped."""
-    st = owner.__dict__.get("_pack_stack_train")
-    if flat and st is not None and st[0][:3] == ("flat", prec.name, _EPOCH[0]) and st[1].valid_for(layers, prec):
-        return st[2]
+    the per-tensor version walk (~300 tensors) is skipped: the key is the epoch, and the plan's valid_for (blocks and addresses) stands in
+    for the rest.  The slot holds (plan, packs); the plan outlives a key miss while it is valid_for, and so do its Packed objects."""
+    s = slot(owner, "_pack_stack_train")
     if flat:
-        key = ("flat", prec.name, _EPOCH[0])
+        key = (_EPOCH[0], "flat", prec.name)                 # weights_key of no tensors, spelled out: this is the per-step path
+        if key == s.key:
+            plan, val = s.value
+            if plan.valid_for(layers, prec):
+                return val
+            s.clear()                                        # same epoch, other blocks or addresses: neither plan nor packs survive
     else:
-        key = ("walk",) + _key([p for l in layers for n, p in l.named_parameters() if not n.startswith("norm_")], prec)
-        if st is not None and st[0] == key:
-            return st[2]
-    with torch.no_grad():
-        plan = st[1] if st is not None and st[1].valid_for(layers, prec) else _StackPackPlan(layers, prec, relative)
-        val = plan.run()
-    owner.__dict__["_pack_stack_train"] = (key, plan, val)
-    return val
+        key = weights_key([p for l in layers for n, p in l.named_parameters() if not n.startswith("norm_")], "walk", prec.name)
+    plan = s.value[0] if s.value is not None else None
+
+    def build():
+        p = plan if plan is not None and plan.valid_for(layers, prec) else _StackPackPlan(layers, prec, relative)
+        return p, p.run()
+    return s.get(key, build)[1]
 
 
 def pack_subsampling_train(mod, prec):
@@ -463,7 +490,7 @@ def pack_subsampling_train(mod, prec):
         wlt, wltl = matrix_t(wlf, prec)
         return Packed(w1=f32(c1.weight.detach().reshape(C, 9).t()), b1=f32(c1.bias), w2=w2, w2_lo=w2l, w2t=w2t, w2t_lo=w2tl, b2=f32(c2.bias),
                       wl=wl, wl_lo=wll, wlt=wlt, wlt_lo=wltl, bl=f32(lin.bias), C=C, Fp=Fp)
-    return _train_cache(mod).get([c1.weight, c1.bias, c2.weight, c2.bias, lin.weight, lin.bias], prec, build)
+    return _train_slot(mod).get([c1.weight, c1.bias, c2.weight, c2.bias, lin.weight, lin.bias], prec, build)
 
 
 def pack_ctc_train(mod, prec):
@@ -477,7 +504,7 @@ def pack_ctc_train(mod, prec):
         wm, wlo = matrix(w, prec)
         wt, wtlo = matrix_t(w, prec)
         return Packed(w=wm, w_lo=wlo, wt=wt, wt_lo=wtlo, b=b, V=V, Vp=Vp)
-    return _train_cache(mod).get([mod.ctc_lo.weight, mod.ctc_lo.bias], prec, build)
+    return _train_slot(mod).get([mod.ctc_lo.weight, mod.ctc_lo.bias], prec, build)
 
 
 def pack_joint_train(mod, prec):
@@ -496,7 +523,7 @@ def pack_joint_train(mod, prec):
         Vp = (V + 7) // 8 * 8
         return Packed(enc=lin(mod.enc_ffn), pred=lin(mod.pred_ffn), out=lin(mod.ffn_out, Vp), V=V, Vp=Vp)
     params = [mod.enc_ffn.weight, mod.enc_ffn.bias, mod.pred_ffn.weight, mod.pred_ffn.bias, mod.ffn_out.weight, mod.ffn_out.bias]
-    return _train_cache(mod).get(params, prec, build)
+    return _train_slot(mod).get(params, prec, build)
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -15,6 +15,7 @@ import torch
 import torch.nn as nn
 
 import cfm
+from cfm import packing
 from attention import PositionalEncoding, RelativePositionalEncoding
 from convolution import ConvolutionSubSampling
 from encoder_layer import ConformerEncoderLayer
@@ -110,19 +111,12 @@ class ConformerEncoder(nn.Module):
         i*D .. (i+1)*D).  The per-block projections are 8 us launches of a 32-row GEMM in the batch path otherwise."""
         if not isinstance(self.position_encoding, RelativePositionalEncoding) or pos_embed is None:
             return None
-        from cfm import packing
         prec = cfm.resolve_precision(self)
         ws = [blk.self_attn.linear_pos.weight for blk in self.encoders]
-        if not hasattr(self, "_pos_pack"):
-            self._pos_pack = packing.PackCache()
-        pk = self._pos_pack.get(ws, prec, lambda: packing.Packed(w=packing.matrix(torch.cat([w.detach() for w in ws], 0), prec)))
+        pk = packing.slot(self, "_pos_pack", packing.PackCache).get(ws, prec, lambda: packing.Packed(w=packing.matrix(torch.cat([w.detach() for w in ws], 0), prec)))
         pe = pos_embed.reshape(-1, self.encoder_dim)
         pe = (pe if pe.dtype == torch.float32 else pe.float()).contiguous()
         return cfm.gemm(pe, pk.w[0], w_lo=pk.w[1], out_dtype=prec.act_dtype)
-
-    def __getstate__(self):                # copy.deepcopy / pickle: the copy starts without the stack's packs or raw-pointer structs
-        from cfm import packing
-        return packing.state_without_caches(super().__getstate__())
 
     def set_precision(self, name):
         """Pin this encoder (every drop-in module under it) to a precision mode, independent of the process default
@@ -302,22 +296,6 @@ class ConformerEncoder(nn.Module):
         return out, torch.ones((out.size(0), 1, out.size(1)))
 
 
-def _weights_signature(owner):
-    """Changes whenever a parameter / buffer of owner.enc is updated in place or repacked: a captured graph holds raw pointers to the PACKED
-    weights of that moment and must be re-captured then.  Runs before every replayed step, so it is kept to one attribute read per tensor
-    (~50 us for the 12-layer encoder; data pointers are checked when the tensor list is (re)built: .to() / load_state_dict keep storage)."""
-    from cfm import packing
-    ts = owner.__dict__.get("_sig_tensors")
-    if ts is None:
-        ts = list(owner.enc.parameters()) + list(owner.enc.buffers())
-        owner.__dict__["_sig_tensors"] = ts
-        owner.__dict__["_sig_ptrs"] = sum(t.data_ptr() for t in ts)
-    v = 0
-    for t in ts:
-        v += t._version
-    return packing._EPOCH[0], v, owner.__dict__["_sig_ptrs"], str(cfm.resolve_precision(owner.enc))
-
-
 class StreamingSession:
     """B streams advanced in lockstep, chunk by chunk, with ONE captured HIP graph per steady-state step.
 
@@ -340,9 +318,6 @@ class StreamingSession:
         self.graph = None
         self.relative = isinstance(encoder.position_encoding, RelativePositionalEncoding)
 
-    def _weights_signature(self):
-        return _weights_signature(self)
-
     def _abs_rows(self, batch, dev):
         pe = self.enc.position_encoding._table_like(torch.empty(0, device=dev, dtype=torch.float32))
         return pe[self.offset: self.offset + batch]
@@ -353,7 +328,7 @@ class StreamingSession:
             raise ValueError("StreamingSession.step wants windows of %d frames" % self.window)
         dev = frames.device
         empty = torch.zeros((0, 0, 0, 0), device=dev)
-        if self.graph is not None and self._weights_signature() != self._sig:
+        if self.graph is not None and packing.graph_watch(self) != self._sig:
             self.cache, self.graph = self.kv.clone(), None            # weights changed under the captured graph: back to eager, re-capture
         if self.graph is None:
             cache = self.cache if self.cache is not None else empty
@@ -379,7 +354,7 @@ class StreamingSession:
         # absolute encoding (use_relative=False): the table rows added to the chunk live in a static buffer too -- sliced at `offset`
         # inside the captured region they would be frozen at the capture step's offset
         self.abs = None if self.relative else self._abs_rows(frames.size(0), dev).clone()
-        self._sig = self._weights_signature()
+        self._sig = packing.graph_watch(self)
         stream = torch.cuda.Stream(device=dev)
         stream.wait_stream(torch.cuda.current_stream(dev))
         with torch.no_grad(), torch.cuda.stream(stream):
@@ -477,9 +452,6 @@ class StreamingBatch:
             self.offsets[idx] = 0
             if self.conv is not None:
                 self.conv[:, idx] = 0
-
-    def _signature(self):
-        return _weights_signature(self)
 
     def _grow_table(self, rows_needed):
         """Append sinusoid rows [len, new_len) -- the reference's formula (attention.py:12-16 / :109-115 incl. the absolute table's fp16
@@ -584,7 +556,7 @@ class StreamingBatch:
         with torch.no_grad():
             if not self.use_graph:
                 return self._step_impl()
-            if self.graph is not None and self._signature() != self._sig:
+            if self.graph is not None and packing.graph_watch(self) != self._sig:
                 self.graph = None                                         # weights changed under the captured graph
             if self.graph is None:
                 y = self._step_impl()                                     # this step runs eagerly (it also sizes the arena and packs the weights)
@@ -607,7 +579,7 @@ class StreamingBatch:
                     with torch.cuda.graph(graph, stream=stream):
                         self.y = self._step_impl()
                 torch.cuda.current_stream(self.dev).wait_stream(stream)
-                self.graph, self._sig = graph, self._signature()
+                self.graph, self._sig = graph, packing.graph_watch(self)
                 return y
             self.graph.replay()
             return self.y

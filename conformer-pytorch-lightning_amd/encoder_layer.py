@@ -63,24 +63,15 @@ class ConformerEncoderLayer(nn.Module):
         self.use_relative = bool(use_relative)
         self.encoder_dim, self.hidden_dim, self.num_heads, self.kernel_size = encoder_dim, hidden_dim, num_heads, kernel_size
         self.return_cache = True           # the reference always materialises cat(k,v) (attention.py:76)
-        self._fused = None                 # (key, LayerWeights, keepalive)
-
-    def __getstate__(self):                # copy.deepcopy / pickle: the copy starts without packs or raw-pointer structs
-        return packing.state_without_caches(super().__getstate__())
-
-    def _apply(self, fn, *a, **kw):        # .to() / .cuda() / .half(): drop every packed copy
-        self._fused = None
-        return super()._apply(fn, *a, **kw)
 
     def _weights(self, prec):
         # the tensor list is rebuilt on every call: replacing a Parameter OBJECT (layer.norm_ff.weight = nn.Parameter(...), pruning /
-        # reparametrisation, swapping a submodule) must change the key too; walking ~60 tensors is cheap next to a 5-launch block
-        plist = list(self.parameters()) + list(self.buffers())
-        key = (prec.name, packing._EPOCH[0]) + tuple((t.data_ptr(), t._version) for t in plist)   # in-place updates bump _version; `p.data = ...` moves the pointer
-        if self._fused is None or self._fused[0] != key:
-            struct, keep = packing.layer_weight_struct(self, prec)
-            self._fused = (key, struct, keep)
-        return self._fused[1]
+        # reparametrisation, swapping a submodule) must change the key too; walking ~40 tensors is cheap next to a 5-launch block (read off
+        # the modules' own dicts: parameters() + buffers() walk the tree twice and build every dotted name, 2.4x the time; weights_key
+        # skips the absent entries).  The slot holds (LayerWeights, keepalive); .to() / .cuda() / .half() change address, device or dtype
+        plist = [t for m in self.modules() for d in (m._parameters, m._buffers) for t in d.values()]
+        key = packing.weights_key(plist, prec.name)
+        return packing.slot(self, "_fused").get(key, lambda: packing.layer_weight_struct(self, prec))[0]
 
     def chain_ready(self, prec):
         """True when this block's weight struct carries every fragment-major pack of the row-chain path (cfm_encoder_layer_forward then

@@ -40,13 +40,11 @@ class _Head:
 
     def __init__(self, predictor, joint):
         self.predictor, self.joint = predictor, joint
-        self._packs = None
+        self._packs = packing.Slot()
 
     def weights_key(self):
-        """Identity of the current weights, as cfm.packing keys its packs: the packing epoch (bumped by updates that bypass torch's version
-        counters: trainer.py's flat Adam kernel writes through raw pointers), then address, version counter, device and dtype per parameter."""
-        srcs = list(self.predictor.parameters()) + list(self.joint.parameters())
-        return (packing._EPOCH[0],) + tuple((t.data_ptr(), t._version, str(t.device), t.dtype) for t in srcs)
+        """Identity of the current weights: packing.weights_key over the predictor's and the joint's parameters."""
+        return packing.weights_key(list(self.predictor.parameters()) + list(self.joint.parameters()))
 
     def fused_limits(self, B, dev, chunk=None):
         """None when the fused step takes B streams on dev, else what it needs; chunk: the lookahead step's frames (it also applies enc_ffn)."""
@@ -64,8 +62,8 @@ class _Head:
         ef_w / ef_b, which only the chunk-lookahead step reads -- added on request, so that the single-frame search holds no copy of them."""
         pr, jn = self.predictor, self.joint
         f32 = lambda t: t.detach().float().contiguous()
-        key = (self.weights_key(), str(dev))
-        if self._packs is None or self._packs[0] != key:
+
+        def build():
             H = pr.hidden_size
             perm = (torch.arange(H, device=dev)[:, None] + H * torch.arange(4, device=dev)[None, :]).reshape(-1)     # row u*4 + gate <- gate*H + u
             W = {"embed": f32(pr.embed.weight), "lstm_w": [], "lstm_b": []}
@@ -81,8 +79,8 @@ class _Head:
             ob = torch.full((Vp,), float("-inf"), device=dev)
             ob[:V] = jn.ffn_out.bias.detach().float()
             W.update(proj_w=f32(pr.projection.weight), proj_b=f32(pr.projection.bias), pf_w=f32(jn.pred_ffn.weight), pf_b=f32(jn.pred_ffn.bias), out_w=ow, out_b=ob, Vp=Vp)
-            self._packs = (key, W)
-        W = self._packs[1]
+            return W
+        W = self._packs.get((self.weights_key(), str(dev)), build)
         if enc_ffn and "ef_w" not in W:
             W.update(ef_w=f32(jn.enc_ffn.weight), ef_b=f32(jn.enc_ffn.bias))
         return W

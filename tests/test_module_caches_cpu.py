@@ -41,40 +41,50 @@ def pointer_struct():
     return w
 
 
+# every name the package caches under on a module: each holds a packing.Slot, planted through packing.slot as the code itself fetches it
+CACHE_NAMES = ("_fused", "_stack_w", "_stack_g", "_pack_stack_train", "_grad_layout", "_pos_pack", "_pack_train", "_pack")
+KEY = ("bf16", 0)
+
+
+def fill(mod, name, value, cls=packing.Slot):
+    packing.Slot.get(packing.slot(mod, name, cls), KEY, lambda: value)
+
+
 def plant(obj):
-    """What an eval forward and a train step leave behind, with pointer-bearing ctypes structs where the real ones sit."""
+    """What an eval forward and a train step leave behind, with pointer-bearing ctypes structs where the real ones sit: a slot type that
+    did not empty itself on a copy would make deepcopy / pickle raise on them."""
     enc = obj.encoder
     pks = tuple(packing.Packed(w=torch.zeros(4)) for _ in range(4))
-    for layer in enc.encoders:
-        layer._fused = (("bf16", 0), pointer_struct(), (torch.zeros(3),))
-        layer.__dict__["_stack_w"] = ((pks,), (cfm.LayerTrainWeights * 1)(pointer_struct()), ())      # a block run on its own (EncoderLayerFn)
-        layer.__dict__["_stack_g"] = (("slab", (1,)), (cfm.LayerTrainGrads * 1)())
-        layer.__dict__["_pack_stack_train"] = (("walk",), object(), (pks,))
-        layer.__dict__["_grad_layout"] = {None: dict(device=torch.device("cpu"), numel=4)}
     L = len(enc.encoders)
-    arr = (cfm.LayerTrainWeights * L)()
-    arr[0] = pointer_struct()
-    enc.__dict__["_stack_w"] = ((pks,) * L, arr, ())
-    enc.__dict__["_stack_g"] = (("slab", (1,)), (cfm.LayerTrainGrads * L)())
-    enc.__dict__["_pack_stack_train"] = (("walk",), object(), ((pks,) * L))
-    for m in obj.modules():                                  # every PackCache (eval packs, training packs) holding a struct
+    for owner, n in [(layer, 1) for layer in enc.encoders] + [(enc, L)]:      # a block run on its own (EncoderLayerFn) is its own owner
+        fill(owner, "_stack_w", ((cfm.LayerTrainWeights * n)(pointer_struct()), (pks,) * n))
+        fill(owner, "_stack_g", ((cfm.LayerTrainGrads * n)(), [dict(numel=4)] * n))
+        fill(owner, "_pack_stack_train", (object(), (pks,) * n, pointer_struct()))
+    for layer in enc.encoders:
+        fill(layer, "_fused", (pointer_struct(), (torch.zeros(3),)))
+        fill(layer, "_grad_layout", {None: dict(numel=4, table=pointer_struct())})
+    for m in obj.modules():                                  # every slot the modules construct (eval packs), and a training pack beside each
         for v in list(m.__dict__.values()):
-            if isinstance(v, packing.PackCache):
-                v._key, v._val = ("bf16", 0), pointer_struct()
+            if isinstance(v, packing.Slot):
+                packing.Slot.get(v, KEY, pointer_struct)
         if hasattr(m, "weight") and isinstance(getattr(m, "weight"), torch.Tensor):
-            pc = packing._train_cache(m)
-            pc._key, pc._val = ("bf16", 0), pointer_struct()
-    enc._pos_pack = packing.PackCache()
-    enc._pos_pack._key, enc._pos_pack._val = ("bf16", 0), pointer_struct()
+            fill(m, "_pack_train", pointer_struct(), packing.PackCache)
+    fill(enc, "_pos_pack", pointer_struct(), packing.PackCache)
+
+
+def slots_of(root):
+    return [(type(m).__name__, k, v) for m in root.modules() for k, v in m.__dict__.items() if isinstance(v, packing.Slot)]
 
 
 def assert_clean(orig, cp):
     for m in cp.modules():
-        for k in packing.MODULE_CACHES:
-            assert m.__dict__.get(k) is None, (type(m).__name__, k)
-        for k, v in m.__dict__.items():
-            if isinstance(v, packing.PackCache):
-                assert v._key is None and v._val is None, (type(m).__name__, k)
+        for k in CACHE_NAMES:
+            v = m.__dict__.get(k)
+            assert v is None or (isinstance(v, packing.Slot) and v.key is None and v.value is None), (type(m).__name__, k)
+    for owner, k, v in slots_of(cp):
+        assert v.key is None and v.value is None, (owner, k)
+    assert {k for _, k, _ in slots_of(orig)} <= set(CACHE_NAMES)
+    assert all(v.key == KEY and v.value is not None for _, _, v in slots_of(orig))     # the original keeps what was planted
     so, sc = orig.state_dict(), cp.state_dict()
     assert so.keys() == sc.keys()
     for k in so:
@@ -91,7 +101,8 @@ def test_planted_structs_are_what_blocks_pickling():
 def test_deepcopy_and_pickle_drop_pointer_caches(part):
     obj = build_objective()
     plant(obj)
-    mod = {"objective": obj, "encoder": obj.encoder, "ctc": obj.ctc, "layer": obj.encoder.encoders[1]}[part]
+    assert {k for _, k, _ in slots_of(obj)} == set(CACHE_NAMES)             # plant() reaches every kind of slot the code has
+    mod ={"objective": obj, "encoder": obj.encoder, "ctc": obj.ctc, "layer": obj.encoder.encoders[1]}[part]
     cp = copy.deepcopy(mod)
     assert_clean(mod, cp)
     buf = io.BytesIO()
@@ -100,7 +111,7 @@ def test_deepcopy_and_pickle_drop_pointer_caches(part):
     assert_clean(mod, torch.load(buf, weights_only=False))
     # the original keeps its caches: copying does not disturb the model being trained
     layer = obj.encoder.encoders[0]
-    assert layer._fused is not None and "_stack_w" in layer.__dict__ and "_stack_w" in obj.encoder.__dict__
+    assert all(packing.slot(m, k).value is not None for m, k in ((layer, "_fused"), (layer, "_stack_w"), (obj.encoder, "_stack_w")))
 
 
 def fake_packs():
@@ -121,7 +132,7 @@ def test_train_weight_struct_follows_replaced_norm_tensors(monkeypatch):
     monkeypatch.setattr(packing, "pack_stack_train", lambda owner, ls, prec, rel, flat=False: pks)
     prec = cfm.Precision("bf16")
     w = ag._stack_weights(layer, [layer], prec, False)[0]
-    assert ag._stack_weights(layer, [layer], prec, False)[0] is w is layer.__dict__["_stack_w"][1]     # nothing replaced: the cached array
+    assert ag._stack_weights(layer, [layer], prec, False)[0] is w is packing.slot(layer, "_stack_w").value[0]     # nothing replaced: the cached array
     assert w[0].ln_ff_g == layer.norm_ff.weight.data_ptr()
     layer.norm_ff.weight = torch.nn.Parameter(torch.full((64,), 2.0))
     w2 = ag._stack_weights(layer, [layer], prec, False)[0]
