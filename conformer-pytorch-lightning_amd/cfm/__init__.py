@@ -217,6 +217,15 @@ class CtcBeamDesc(ctypes.Structure):
                 [(n, c_i32) for n in ("B", "T", "V", "k", "beam", "blank")])
 
 
+class RnntBeamDesc(ctypes.Structure):
+    _fields_ = ([("embed", c_p), ("lstm_w", c_p * 4), ("lstm_b", c_p * 4)] +
+                [(n, c_p) for n in ("proj_w", "proj_b", "pf_w", "pf_b", "out_w", "out_b", "enc_proj", "lens", "token", "t", "hash", "fc", "len", "node", "parent", "ext",
+                                    "live", "score", "h", "c", "h_new", "c_new", "pred", "act", "logits", "topk_idx", "topk_logp", "lse", "nodes")] +
+                [("n_nodes", c_i64)] +
+                [(n, c_p) for n in ("fin_score", "fin_node", "fin_len", "n_fin", "step", "done", "n_done", "nbest_tokens", "nbest_len", "nbest_score")] +
+                [(n, c_i32) for n in ("B", "T", "L", "E", "H", "P", "J", "V", "Vp", "beam", "blank", "max_symbols", "max_len", "len_by_frames", "parity")])
+
+
 class FbankDesc(ctypes.Structure):
     _fields_ = ([(n, c_p) for n in ("samples", "lengths", "feats_length", "carry_in", "carry_out", "fresh_in", "pos_in", "fresh_out", "pos_out", "twiddle", "window",
                                     "mel_w", "mel_start", "mel_len", "mel_off", "out")] + [("ld", c_i64)] +
@@ -256,7 +265,7 @@ for _c_name, _cls in dict(
         cfm_layer_train_weights=LayerTrainWeights, cfm_train_group=TrainGroup, cfm_layer_train_io=LayerTrainIO, cfm_layer_train_saved=LayerTrainSaved,
         cfm_layer_train_scratch=LayerTrainScratch, cfm_layer_train_grads=LayerTrainGrads, cfm_layer_weights=LayerWeights, cfm_ctc_group=CtcGroup,
         cfm_rnnt_desc=RnntDesc, cfm_lattice=Lattice, cfm_rnnt_packed_desc=RnntPackedDesc, cfm_ln_bwd_desc=LnBwdDesc, cfm_lstm_desc=LstmDesc, cfm_greedy_desc=GreedyDesc,
-        cfm_greedy_chunk_desc=GreedyChunkDesc, cfm_ctc_greedy_desc=CtcGreedyDesc, cfm_ctc_beam_desc=CtcBeamDesc, cfm_fbank_desc=FbankDesc,
+        cfm_greedy_chunk_desc=GreedyChunkDesc, cfm_ctc_greedy_desc=CtcGreedyDesc, cfm_ctc_beam_desc=CtcBeamDesc, cfm_rnnt_beam_desc=RnntBeamDesc, cfm_fbank_desc=FbankDesc,
         cfm_ffn_split_desc=FfnSplitDesc, cfm_layer_scratch=LayerScratch, cfm_layer_io=LayerIO).items():
     _cls._c_name_ = _c_name
 PROTOTYPES = (
@@ -347,6 +356,9 @@ PROTOTYPES = (
     ("cfm_ctc_greedy", c_int, P(CtcGreedyDesc), c_p),
     ("cfm_ctc_beam_nodes", c_i64, c_i32, c_i32, c_i32),
     ("cfm_ctc_prefix_beam", c_int, P(CtcBeamDesc), c_p),
+    ("cfm_rnnt_beam_nodes", c_i64, c_i32, c_i32, c_i32, c_i32),
+    ("cfm_rnnt_beam_begin", c_int, P(RnntBeamDesc), c_p),
+    ("cfm_rnnt_beam_step", c_int, P(RnntBeamDesc), c_p),
 )
 
 _lib = None

@@ -12,6 +12,8 @@
 //     control       k = argmax over the tiles; the reference's branches as selects on the per-stream state (model.py:255-267)
 //   cfm_greedy_chunk_step (4 launches): pred_ffn, the compact row list, the M-tiled vocabulary product, control across the lookahead --
 //     described at its section below
+//   cfm_rnnt_beam_step (5 launches): the RNN-T beam search, hypotheses as rows of the same predictor and joint launches -- described at its
+//     section at the end of the file
 //
 // The torch-operation form of a single-frame step (greedy.py) is ~45 small launches; the predictor's and the single-frame joint's products
 // are "skinny": B <= 64 streams against weight matrices of 0.26-2.5 M elements, i.e. one read of 7.5 M f32 weights per step, spread over
@@ -77,9 +79,11 @@ struct SkinnyArgs {
     const float* enc;        // EPI 2: enc_proj [B, T, N];  a[b, n] = tanh(enc[b, min(t[b], T-1), n] + acc + bias)
     const int64_t* t_idx;
     int T;
+    int enc_div;             //        enc's item of row b is b / enc_div (0: b itself) -- the beam search's rows, `beam` per utterance
     float* pmax;             // EPI 3: per (tile, b): best value / first index of the tile's 16 classes
     int* pidx;
     const int* n_done;       // when given (the chunk-lookahead step): every stream finished (*n_done >= B) -> the launch does nothing
+    int done_at;             // ... *n_done >= done_at instead, when not 0 (the beam search counts utterances, B is its rows)
 };
 
 __device__ __forceinline__ float sigmoid_acc(float x) { return 1.0f / (1.0f + expf(-x)); }
@@ -90,7 +94,7 @@ __global__ __launch_bounds__(256) void cfm_skinny_kernel(const SkinnyArgs a) {
     const int l15 = lane & 15, g = lane >> 4;
     const int tile = blockIdx.x * 4 + wave;                 // 16 output columns per wavefront
     if (tile * 16 >= a.N) return;
-    if (a.n_done && *a.n_done >= a.B) return;               // uniform: a step captured after the last stream finished costs empty launches only
+    if (a.n_done && *a.n_done >= (a.done_at ? a.done_at : a.B)) return;   // uniform: a step captured after the last stream finished costs empty launches only
     const int n0 = tile * 16;
     const int nbt = (a.B + 15) / 16;                        // <= 4 stream tiles
     f32x4 acc[4];
@@ -146,7 +150,8 @@ __global__ __launch_bounds__(256) void cfm_skinny_kernel(const SkinnyArgs a) {
             if (live) {
                 int64_t t = a.t_idx[b];
                 t = t < a.T ? t : a.T - 1;
-                const f32x4 e = *(const f32x4*)(a.enc + ((int64_t)b * a.T + t) * a.N + n0 + 4 * g);
+                const int eb = a.enc_div ? b / a.enc_div : b;
+                const f32x4 e = *(const f32x4*)(a.enc + ((int64_t)eb * a.T + t) * a.N + n0 + 4 * g);
                 *(f32x4*)(a.out + (int64_t)b * a.ld_out + n0 + 4 * g) = (f32x4){tanhf(e.x + v.x), tanhf(e.y + v.y), tanhf(e.z + v.z), tanhf(e.w + v.w)};
             }
         } else {                                            // EPI 3: the tile's best class per stream, [tile, B]
@@ -186,7 +191,7 @@ int check_common(const Desc* d, const char* who) {
 // The predictor stage of a step of either search: (token, h, c) -> candidates h_new / c_new [L, B, H] and pred [B, P].  n_done: null, or
 // the device counter that turns the launches into empty ones once every stream is finished (SkinnyArgs::n_done).
 template <class Desc>
-int enqueue_predictor(const Desc* d, const int* n_done, hipStream_t s, const char* who) {
+int enqueue_predictor(const Desc* d, const int* n_done, hipStream_t s, const char* who, int done_at = 0) {
     const int B = d->B, H = d->H;
     for (int l = 0; l < d->L; ++l) {
         CFM_CHECK_ARG(d->lstm_w[l] && d->lstm_b[l], "%s: LSTM layer %d has no weights", who, l);
@@ -195,12 +200,12 @@ int enqueue_predictor(const Desc* d, const int* n_done, hipStream_t s, const cha
         if (l == 0) { a.x1 = d->embed; a.x1_rows = d->token; a.ld1 = d->E; a.K1 = d->E; }
         else { a.x1 = d->h_new + (int64_t)(l - 1) * B * H; a.ld1 = H; a.K1 = H; }
         a.K = a.K1 + H;
-        a.c_in = d->c + (int64_t)l * B * H; a.h_out = d->h_new + (int64_t)l * B * H; a.c_out = d->c_new + (int64_t)l * B * H; a.n_done = n_done;
+        a.c_in = d->c + (int64_t)l * B * H; a.h_out = d->h_new + (int64_t)l * B * H; a.c_out = d->c_new + (int64_t)l * B * H; a.n_done = n_done; a.done_at = done_at;
         if (int rc = launch_skinny<1>(a, s, "greedy_lstm")) return rc;
     }
     SkinnyArgs a = {};
     a.W = d->proj_w; a.bias = d->proj_b; a.B = B; a.N = d->P; a.K = a.K1 = H; a.x1 = d->h_new + (int64_t)(d->L - 1) * B * H; a.ld1 = H; a.out = d->pred; a.ld_out = d->P;
-    a.n_done = n_done;
+    a.n_done = n_done; a.done_at = done_at;
     return launch_skinny<0>(a, s, "greedy_proj");
 }
 
@@ -624,4 +629,376 @@ extern "C" int cfm_greedy_chunk_step(const cfm_greedy_chunk_desc* d, cfm_stream_
     CfmProfScope prof("greedy_chunk_control", s, 0.0, (double)B * d->chunk * (d->Vp / 16) * 8);
     CFM_LAUNCH(cfm_chunk_control_kernel, dim3((unsigned)B), dim3(256), 0, s, c);
     return cfm_launch_status("cfm_greedy_chunk_step (control)");
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// RNN-T beam search (cfm_rnnt_beam_begin / cfm_rnnt_beam_step): n-best lists from the transducer head; the algorithm is stated once, in
+// float64, in tests/rnnt_beam_ref.py.  The hypotheses are ROWS of the skinny products: utterance b's `beam` slots are rows b * beam + j,
+// R = B * beam <= 64 in all; the live hypotheses of an utterance sit in its first slots in rank order, the other slots are dead (live = 0):
+// they run through the products on stale, valid inputs and are never candidates.  All live hypotheses of an utterance have the same
+// alignment length t + len, so one step advances every utterance by one lattice diagonal.  One step, L + 5 launches (7 for L = 2; the
+// greedy step has 6):
+//
+//   pred    the predictor stage over R rows (enqueue_predictor; the token gather is per row)
+//   act     tanh(enc_proj[row / beam, t_row] + pred_ffn(pred))                       (cfm_skinny_kernel<2> with enc_div = beam)
+//   logits  z = act . Wout^T + bout, [R, Vp]; the pad columns V..Vp carry bias -inf  (cfm_skinny_kernel<0>)
+//   topk    cfm_ctc_topk over the R rows as R one-frame items, `live` as their lengths (a dead row costs nothing), the V real classes,
+//           k = beam + 1: lse and the k best log-probabilities, the lower class first among equal values.  One of them may be the blank, so
+//           the other `beam` are the row's best non-blank classes; the blank's own log-probability is logits[blank] - lse
+//   ctl     one workgroup per utterance, thread (j, e) = candidate e of parent slot j: e = 0 the blank (t + 1, fc = 0, the unchanged
+//           predictor input), e = 1 .. beam the extension by the parent's e-th best non-blank class (not offered at fc == max_symbols or
+//           len == max_len).  An extension whose string is the string of a live slot q -- (length, last token, 64-bit hash) equal, as in
+//           cfm_ctc_prefix_beam_kernel -- is folded into q's blank candidate with logaddexp and leaves (at equal alignment length no other
+//           two candidates can be the same string, and at most one extension meets a given q: its parent is q's string less the last token).
+//           Every candidate counts those that rank before it (score; then parent slot, blank before extension, class: c_key; a merged
+//           candidate has the smaller key of its sources); rank < beam is kept.  Thread 0 then walks the <= beam kept candidates in rank
+//           order: those with t == n enter the finished set F (global memory between the steps, best first, at most beam), the others get
+//           the next free live slot unless F is full and their score is below F's worst.  The candidates write their slots' scalars and
+//           trie nodes; all threads copy the slots' LSTM states.  An utterance whose live set is empty writes its n-best list and counts in
+//           n_done; from then on its workgroup returns at once, and when n_done == B so do the launches before it.
+//
+// State reorder: a new slot takes (h, c) from its parent slot -- the candidates (h_new, c_new) of this step when it extended, the
+// parent's own state when it took the blank -- and the slots of an utterance read each other's state, so it cannot be done in place: h and c
+// are two buffers [2, L, R, H], a step reads [parity] and its control launch writes [parity ^ 1].  parity is the caller's (it alternates
+// 0, 1, 0, ... from cfm_rnnt_beam_begin on; the steps after the last live one change nothing, so a captured graph of an even number of
+// steps keeps it).  No launch of its own: the control workgroup copies at most beam * L * H * 2 floats.
+//
+// Identity by hash: unequal strings of equal length and last token collide with probability 2^-64 per comparison; a step makes at most
+// beam^3 <= 3375 comparisons per utterance, so ~2e-16 per step -- 1e-11 for 64 rows over 1 000 steps, far below what f32 rounding of the
+// scores does to the comparison anyway.
+//
+// Trie: a kept extension of step s in live slot i becomes node 1 + s * beam + i of its utterance ((parent, token) pairs, node 0 the empty
+// string); s < T + max_len + 1, so beam (T + max_len + 1) + 1 nodes per utterance (cfm_rnnt_beam_nodes).
+// ---------------------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int RB_W = 16;                                    // candidate slots per parent: the blank and up to 15 extensions
+
+__device__ __forceinline__ uint64_t beam_hash(uint64_t h, int c) {       // ctc_decode.hip's prefix_hash: splitmix64's finaliser per token
+    uint64_t z = h + 0x9E3779B97F4A7C15ull * (uint64_t)(unsigned)(c + 1);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+__device__ __forceinline__ float logaddexp_acc(float a, float b) {       // full-precision expf / log1pf: the scores are compared with float64
+    const float m = fmaxf(a, b);
+    if (m == -INFINITY) return -INFINITY;
+    return m + log1pf(expf(-fabsf(a - b)));
+}
+
+struct BeamArgs {
+    const int64_t* lens;
+    int64_t *token, *t, *hash;
+    int *fc, *len, *node, *parent, *ext, *live;
+    float* score;
+    float *h, *c;                // [2, L, R, H]
+    const float *h_new, *c_new;  // [L, R, H]
+    const float* logits;         // [R, Vp]
+    const int* topk_idx;         // [R, k]
+    const float *topk_logp, *lse;
+    int* nodes;
+    float* fin_score;
+    int *fin_node, *fin_len, *n_fin, *step;
+    uint8_t* done;
+    int* n_done;
+    int64_t* nbest_tokens;
+    int* nbest_len;
+    float* nbest_score;
+    int B, T, L, H, Vp, beam, blank, max_symbols, max_len, len_by_frames, parity;
+};
+
+__device__ __forceinline__ int64_t beam_nodes_per_utt(int T, int max_len, int beam) { return (int64_t)beam * ((int64_t)T + max_len + 1) + 1; }
+
+// one workgroup per utterance: the empty hypothesis in slot 0, zero LSTM state in both buffers, no finished entry; n == 0: the result
+__global__ __launch_bounds__(256) void cfm_rnnt_beam_begin_kernel(const BeamArgs a) {
+    const int b = blockIdx.x, tid = threadIdx.x, K = a.beam, R = a.B * K;
+    const bool idle = a.lens[b] <= 0;
+    if (tid < K) {
+        const int r = b * K + tid;
+        a.token[r] = a.blank; a.t[r] = 0; a.hash[r] = 0;
+        a.fc[r] = 0; a.len[r] = 0; a.node[r] = 0; a.parent[r] = r; a.ext[r] = 0;
+        a.live[r] = (tid == 0 && !idle) ? 1 : 0;
+        a.score[r] = tid == 0 ? 0.f : -INFINITY;
+        a.fin_score[r] = -INFINITY; a.fin_node[r] = 0; a.fin_len[r] = 0;
+        a.nbest_len[r] = 0;
+        a.nbest_score[r] = (tid == 0 && idle) ? 0.f : -INFINITY;
+    }
+    if (tid == 0) {
+        a.n_fin[b] = 0;
+        a.step[b] = 0;
+        a.done[b] = idle ? 1 : 0;
+        int* nodes = a.nodes + beam_nodes_per_utt(a.T, a.max_len, K) * 2 * b;
+        nodes[0] = -1; nodes[1] = -1;
+        if (b == 0) {
+            int n = 0;
+            for (int i = 0; i < a.B; ++i) n += a.lens[i] <= 0 ? 1 : 0;
+            *a.n_done = n;
+        }
+    }
+    const int KH = K * a.H;
+    for (int i = tid; i < 2 * a.L * KH; i += 256) {
+        const int pl = i / KH, x = i - pl * KH;             // (buffer, layer), (slot, unit)
+        const int64_t o = ((int64_t)pl * R + (int64_t)b * K) * a.H + x;
+        a.h[o] = 0.f;
+        a.c[o] = 0.f;
+    }
+}
+
+__global__ __launch_bounds__(256) void cfm_rnnt_beam_control_kernel(const BeamArgs a) {
+    __shared__ float c_score[256];
+    __shared__ unsigned c_key[256];
+    __shared__ int slot_of[256];                            // the new live slot of a candidate, -1: none
+    __shared__ float m_score[RB_W];                         // the extension folded into slot q's blank candidate
+    __shared__ unsigned m_key[RB_W];
+    __shared__ int kept[RB_W], k_fin[RB_W], k_node[RB_W], k_len[RB_W];   // by rank: candidate, finished?, the string's node and length
+    __shared__ float k_score[RB_W];
+    __shared__ float f_score[RB_W];                         // F, best first
+    __shared__ int f_node[RB_W], f_len[RB_W];
+    __shared__ int new_par[RB_W], new_ext[RB_W];            // by new slot
+    __shared__ int s_nkept, s_nlive, s_nfin;
+    const int b = blockIdx.x, tid = threadIdx.x, K = a.beam, R = a.B * K, kk = K + 1;
+    if (a.done[b]) return;                                  // uniform
+    int64_t n64 = a.lens[b];
+    const int n = n64 < a.T ? (int)n64 : a.T;
+    const int max_len = a.len_by_frames && n < a.max_len ? n : a.max_len;   // the most tokens of a hypothesis of this utterance
+    const int stp = a.step[b];
+    const bool overrun = stp >= a.T + a.max_len + 1;        // cannot happen (a step adds one to t + len); would run past the node buffer
+    const int j = tid >> 4, e = tid & 15;
+    const int row = b * K + (j < K ? j : 0);
+    const bool par_live = j < K && e <= K && !overrun && a.live[row] != 0;
+    int64_t pt = 0;
+    int pfc = 0, plen = 0, pnode = 0, ptok = 0, cls = -1, merge_into = -1;
+    uint64_t phash = 0, xh = 0;
+    float sc = -INFINITY;
+    unsigned key = 0xffffffffu;
+    if (par_live) {
+        pt = a.t[row]; pfc = a.fc[row]; plen = a.len[row]; pnode = a.node[row]; ptok = (int)a.token[row]; phash = (uint64_t)a.hash[row];
+        const float pscore = a.score[row];
+        if (e == 0) {
+            sc = pscore + (a.logits[(int64_t)row * a.Vp + a.blank] - a.lse[row]);
+            key = (unsigned)(2 * j) << 20;
+        } else if (pfc < a.max_symbols && plen < max_len) {
+            const int* ix = a.topk_idx + (int64_t)row * kk;
+            int pb = kk;                                    // where the blank stands among the k best, k: not among them
+            for (int q = kk - 1; q >= 0; --q) pb = ix[q] == a.blank ? q : pb;
+            const int pos = (e - 1) < pb ? e - 1 : e;       // the e-th best non-blank class; pos <= beam < k
+            cls = ix[pos];
+            sc = pscore + a.topk_logp[(int64_t)row * kk + pos];
+            key = ((unsigned)(2 * j + 1) << 20) | (unsigned)cls;
+            xh = beam_hash(phash, cls);
+            for (int q = 0; q < K; ++q) {
+                const int rq = b * K + q;
+                if (a.live[rq] != 0 && a.len[rq] == plen + 1 && (int)a.token[rq] == cls && (uint64_t)a.hash[rq] == xh) merge_into = q;
+            }
+        }
+    }
+    if (tid < RB_W) { m_score[tid] = -INFINITY; m_key[tid] = 0xffffffffu; }
+    if (tid == 0) s_nkept = 0;
+    __syncthreads();
+    if (merge_into >= 0) {                                  // at most one extension per slot
+        m_score[merge_into] = sc;
+        m_key[merge_into] = key;
+        sc = -INFINITY;
+        key = 0xffffffffu;
+    }
+    __syncthreads();
+    if (par_live && e == 0) {
+        sc = logaddexp_acc(sc, m_score[j]);
+        key = min(key, m_key[j]);
+    }
+    c_score[tid] = sc;
+    c_key[tid] = key;
+    slot_of[tid] = -1;
+    __syncthreads();
+    if (key != 0xffffffffu) {
+        int rank = 0;
+        for (int q = 0; q < K; ++q) {
+            for (int x = 0; x <= K; ++x) {
+                const float s = c_score[q * RB_W + x];
+                const unsigned kq = c_key[q * RB_W + x];
+                rank += (kq != 0xffffffffu && (s > sc || (s == sc && kq < key))) ? 1 : 0;
+            }
+        }
+        if (rank < K) {
+            kept[rank] = tid;
+            k_score[rank] = sc;
+            k_fin[rank] = (e == 0 && pt + 1 >= n) ? 1 : 0;
+            k_node[rank] = pnode;
+            k_len[rank] = plen;
+            atomicAdd(&s_nkept, 1);
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {                                         // <= beam kept candidates in rank order: F, the prune, the new live slots
+        int nf = a.n_fin[b], nl = 0;
+        int order[RB_W];
+        for (int i = 0; i < nf; ++i) { f_score[i] = a.fin_score[b * K + i]; f_node[i] = a.fin_node[b * K + i]; f_len[i] = a.fin_len[b * K + i]; }
+        const int nk = s_nkept < K ? s_nkept : K;
+        for (int r = 0; r < nk; ++r) {
+            if (!k_fin[r]) { order[nl++] = r; continue; }
+            int p = nf;
+            while (p > 0 && f_score[p - 1] < k_score[r]) --p;       // behind the entries of the same score
+            if (p >= K) continue;
+            for (int i = (nf < K ? nf : K - 1); i > p; --i) { f_score[i] = f_score[i - 1]; f_node[i] = f_node[i - 1]; f_len[i] = f_len[i - 1]; }
+            f_score[p] = k_score[r]; f_node[p] = k_node[r]; f_len[p] = k_len[r];
+            nf = nf < K ? nf + 1 : K;
+        }
+        int nlive = 0;
+        for (int i = 0; i < nl; ++i) {
+            if (nf == K && k_score[order[i]] < f_score[K - 1]) continue;   // scores only fall: it cannot enter F any more
+            slot_of[kept[order[i]]] = nlive++;
+        }
+        for (int i = 0; i < nf; ++i) { a.fin_score[b * K + i] = f_score[i]; a.fin_node[b * K + i] = f_node[i]; a.fin_len[b * K + i] = f_len[i]; }
+        a.n_fin[b] = nf;
+        a.step[b] = stp + 1;
+        s_nlive = nlive;
+        s_nfin = nf;
+    }
+    __syncthreads();
+    const int slot = slot_of[tid], nl = s_nlive;
+    if (slot >= 0) {
+        const int nr = b * K + slot;
+        if (e == 0) {
+            a.t[nr] = pt + 1; a.fc[nr] = 0; a.len[nr] = plen; a.hash[nr] = (int64_t)phash; a.token[nr] = ptok; a.node[nr] = pnode;
+        } else {
+            int* nodes = a.nodes + beam_nodes_per_utt(a.T, a.max_len, K) * 2 * b;
+            const int id = 1 + stp * K + slot;
+            nodes[2 * id] = pnode;
+            nodes[2 * id + 1] = cls;
+            a.t[nr] = pt; a.fc[nr] = pfc + 1; a.len[nr] = plen + 1; a.hash[nr] = (int64_t)xh; a.token[nr] = cls; a.node[nr] = id;
+        }
+        a.score[nr] = sc;
+        a.parent[nr] = row;
+        a.ext[nr] = e != 0 ? 1 : 0;
+        a.live[nr] = 1;
+        new_par[slot] = j;
+        new_ext[slot] = e != 0 ? 1 : 0;
+    }
+    if (tid < K && tid >= nl) a.live[b * K + tid] = 0;
+    __syncthreads();
+    // the new slots' LSTM states, into the other buffer
+    const int LH = a.L * a.H;
+    const int64_t buf = (int64_t)a.L * R * a.H;
+    const float *h_in = a.h + a.parity * buf, *c_in = a.c + a.parity * buf;
+    float *h_out = a.h + (a.parity ^ 1) * buf, *c_out = a.c + (a.parity ^ 1) * buf;
+    for (int i = tid; i < nl * LH; i += 256) {
+        const int sl = i / LH, x = i - sl * LH, l = x / a.H, u = x - l * a.H;
+        const int64_t src = ((int64_t)l * R + b * K + new_par[sl]) * a.H + u, dst = ((int64_t)l * R + b * K + sl) * a.H + u;
+        h_out[dst] = new_ext[sl] ? a.h_new[src] : h_in[src];
+        c_out[dst] = new_ext[sl] ? a.c_new[src] : c_in[src];
+    }
+    if (nl > 0) return;                                     // uniform
+    // the live set is empty: the utterance is done, F is its n-best list (the strings by walking the parent links back)
+    if (tid < K) {
+        const int64_t o = (int64_t)b * K + tid;
+        if (tid < s_nfin) {
+            const int* nodes = a.nodes + beam_nodes_per_utt(a.T, a.max_len, K) * 2 * b;
+            const int len = f_len[tid];
+            a.nbest_len[o] = len;
+            a.nbest_score[o] = f_score[tid];
+            int node = f_node[tid];
+            for (int pos = len - 1; pos >= 0; --pos) {
+                a.nbest_tokens[o * a.max_len + pos] = nodes[2 * node + 1];
+                node = nodes[2 * node];
+            }
+        } else {
+            a.nbest_len[o] = 0;
+            a.nbest_score[o] = -INFINITY;
+        }
+    }
+    if (tid == 0) {
+        a.done[b] = 1;
+        atomicAdd(a.n_done, 1);
+    }
+}
+
+// what enqueue_predictor reads of a descriptor, over the R rows
+struct BeamRows {
+    const float* embed;
+    const float* const* lstm_w;
+    const float* const* lstm_b;
+    const float *proj_w, *proj_b;
+    const int64_t* token;
+    const float *h, *c;
+    float *h_new, *c_new, *pred;
+    int B, L, E, H, P;
+};
+
+int beam_check(const cfm_rnnt_beam_desc* d, const char* who) {
+    CFM_CHECK_ARG(d, "%s: null descriptor", who);
+    CFM_CHECK_ARG(d->beam >= 1 && d->beam <= 15 && d->B > 0 && (int64_t)d->B * d->beam <= 64, "%s: 1 <= beam <= 15 and B * beam <= 64 rows (B=%d beam=%d)", who, d->B,
+                  d->beam);
+    CFM_CHECK_ARG(d->T > 0 && d->L >= 1 && d->L <= 4 && d->E > 0 && d->H > 0 && d->P > 0 && d->J > 0 && d->E % 16 == 0 && d->H % 16 == 0 && d->P % 16 == 0 &&
+                      d->J % 16 == 0 && d->Vp % 16 == 0 && d->V > 0 && d->V <= d->Vp && d->V <= (1 << 20),
+                  "%s: T > 0, <= 4 LSTM layers, sizes multiples of 16, V <= Vp, V <= 2^20 (T=%d L=%d E=%d H=%d P=%d J=%d V=%d Vp=%d)", who, d->T, d->L, d->E, d->H, d->P,
+                  d->J, d->V, d->Vp);
+    CFM_CHECK_ARG(d->beam + 1 <= d->V && d->blank >= 0 && d->blank < d->V, "%s: beam + 1 <= V classes, blank in [0, V) (beam=%d V=%d blank=%d)", who, d->beam, d->V,
+                  d->blank);
+    CFM_CHECK_ARG(d->max_symbols >= 1 && d->max_len >= 0 && d->parity >= 0 && d->parity <= 1, "%s: max_symbols >= 1, max_len >= 0, parity 0 or 1 (%d, %d, %d)", who,
+                  d->max_symbols, d->max_len, d->parity);
+    CFM_CHECK_ARG((int64_t)d->beam * ((int64_t)d->T + d->max_len + 1) < (1ll << 30), "%s: beam * (T + max_len + 1) nodes per utterance exceed 2^30", who);
+    CFM_CHECK_ARG(d->n_nodes >= cfm_rnnt_beam_nodes(d->B, d->T, d->max_len, d->beam), "%s: node buffer of %lld nodes, %lld needed", who, (long long)d->n_nodes,
+                  (long long)cfm_rnnt_beam_nodes(d->B, d->T, d->max_len, d->beam));
+    CFM_CHECK_ARG(d->embed && d->proj_w && d->proj_b && d->pf_w && d->pf_b && d->out_w && d->out_b && d->enc_proj && d->lens && d->token && d->t && d->hash && d->fc &&
+                      d->len && d->node && d->parent && d->ext && d->live && d->score && d->h && d->c && d->h_new && d->c_new && d->pred && d->act && d->logits &&
+                      d->topk_idx && d->topk_logp && d->lse && d->nodes && d->fin_score && d->fin_node && d->fin_len && d->n_fin && d->step && d->done && d->n_done &&
+                      d->nbest_tokens && d->nbest_len && d->nbest_score,
+                  "%s: null pointer", who);
+    return 0;
+}
+
+BeamArgs beam_args(const cfm_rnnt_beam_desc* d) {
+    BeamArgs a;
+    a.lens = d->lens; a.token = d->token; a.t = d->t; a.hash = d->hash; a.fc = d->fc; a.len = d->len; a.node = d->node; a.parent = d->parent; a.ext = d->ext;
+    a.live = d->live; a.score = d->score; a.h = d->h; a.c = d->c; a.h_new = d->h_new; a.c_new = d->c_new; a.logits = d->logits; a.topk_idx = d->topk_idx;
+    a.topk_logp = d->topk_logp; a.lse = d->lse; a.nodes = d->nodes; a.fin_score = d->fin_score; a.fin_node = d->fin_node; a.fin_len = d->fin_len; a.n_fin = d->n_fin;
+    a.step = d->step; a.done = d->done; a.n_done = d->n_done; a.nbest_tokens = d->nbest_tokens; a.nbest_len = d->nbest_len; a.nbest_score = d->nbest_score;
+    a.B = d->B; a.T = d->T; a.L = d->L; a.H = d->H; a.Vp = d->Vp; a.beam = d->beam; a.blank = d->blank; a.max_symbols = d->max_symbols; a.max_len = d->max_len; a.len_by_frames = d->len_by_frames;
+    a.parity = d->parity;
+    return a;
+}
+
+}  // namespace
+
+extern "C" int64_t cfm_rnnt_beam_nodes(int32_t B, int32_t T, int32_t max_len, int32_t beam) {
+    return (int64_t)B * ((int64_t)beam * ((int64_t)T + max_len + 1) + 1);
+}
+
+extern "C" int cfm_rnnt_beam_begin(const cfm_rnnt_beam_desc* d, cfm_stream_t stream) {
+    if (int rc = beam_check(d, "cfm_rnnt_beam_begin")) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const BeamArgs a = beam_args(d);
+    CfmProfScope prof("rnnt_beam_begin", s, 0.0, 0.0);
+    CFM_LAUNCH(cfm_rnnt_beam_begin_kernel, dim3((unsigned)d->B), dim3(256), 0, s, a);
+    return cfm_launch_status("cfm_rnnt_beam_begin");
+}
+
+extern "C" int cfm_rnnt_beam_step(const cfm_rnnt_beam_desc* d, cfm_stream_t stream) {
+    if (int rc = beam_check(d, "cfm_rnnt_beam_step")) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int R = d->B * d->beam, k = d->beam + 1;
+    const int64_t buf = (int64_t)d->L * R * d->H;
+    BeamRows rows;
+    rows.embed = d->embed; rows.lstm_w = d->lstm_w; rows.lstm_b = d->lstm_b; rows.proj_w = d->proj_w; rows.proj_b = d->proj_b; rows.token = d->token;
+    rows.h = d->h + d->parity * buf; rows.c = d->c + d->parity * buf; rows.h_new = d->h_new; rows.c_new = d->c_new; rows.pred = d->pred;
+    rows.B = R; rows.L = d->L; rows.E = d->E; rows.H = d->H; rows.P = d->P;
+    if (int rc = enqueue_predictor(&rows, d->n_done, s, "cfm_rnnt_beam_step", d->B)) return rc;
+    {
+        SkinnyArgs a = {};
+        a.W = d->pf_w; a.bias = d->pf_b; a.B = R; a.N = d->J; a.K = a.K1 = d->P; a.x1 = d->pred; a.ld1 = d->P; a.out = d->act; a.ld_out = d->J; a.enc = d->enc_proj;
+        a.t_idx = d->t; a.T = d->T; a.enc_div = d->beam; a.n_done = d->n_done; a.done_at = d->B;
+        if (int rc = launch_skinny<2>(a, s, "rnnt_beam_joint_in")) return rc;
+    }
+    {
+        SkinnyArgs a = {};
+        a.W = d->out_w; a.bias = d->out_b; a.B = R; a.N = d->Vp; a.K = a.K1 = d->J; a.x1 = d->act; a.ld1 = d->J; a.out = d->logits; a.ld_out = d->Vp;
+        a.n_done = d->n_done; a.done_at = d->B;
+        if (int rc = launch_skinny<0>(a, s, "rnnt_beam_joint_out")) return rc;
+    }
+    if (int rc = cfm_ctc_topk(d->logits, d->Vp, R, 1, d->V, d->live, k, d->topk_idx, d->topk_logp, d->lse, stream)) return rc;
+    const BeamArgs c = beam_args(d);
+    CfmProfScope prof("rnnt_beam_control", s, 0.0, (double)R * (k * 8 + 64));
+    CFM_LAUNCH(cfm_rnnt_beam_control_kernel, dim3((unsigned)d->B), dim3(256), 0, s, c);
+    return cfm_launch_status("cfm_rnnt_beam_step (control)");
 }

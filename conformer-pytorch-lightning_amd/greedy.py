@@ -24,6 +24,7 @@ tokens produced by running the reference's predictor / joint modules, and with a
 
 `BatchedGreedySearch` decides one frame per step, `ChunkGreedySearch` (the streaming recogniser's decoder) all remaining frames of a chunk;
 what they share -- weights key, f32 packs, limits, descriptor weights, LSTM step (`_Head`), graph capture and the replay loop -- is here once.
+`BeamSearch` is the RNN-T beam search on the same packs, capture and replay loop: n-best lists with scores, device only.
 """
 import ctypes
 
@@ -483,3 +484,105 @@ class ChunkGreedySearch:
                 self._host_hyps[b].extend(new[b])
         self._host_count = counts
         return new
+
+
+class BeamSearch:
+    """RNN-T beam search on the device: per utterance the `beam` best finished hypotheses with their scores (log of the summed probability
+    of the alignments found, no length normalisation).  The search is alignment-length synchronous and is specified in float64 in
+    tests/rnnt_beam_ref.py; include/cfm.h (cfm_rnnt_beam_step) restates it.  max_symbols: the most symbols emitted on one frame (the role
+    n_steps plays in the greedy searches); max_len: the most tokens of a hypothesis (default: the utterance's frames).
+
+    The B * beam <= 64 hypotheses are the rows of the fused step (csrc/greedy.hip: the greedy step's predictor and joint launches, the
+    log-softmax top-k of the CTC decoder, one ranking / merging workgroup per utterance); `steps_per_replay` steps (made even: the LSTM state
+    alternates between two buffers by step parity) are captured in one HIP graph and the host reads one "utterances done" counter per replay.
+    Device only: there is no torch-operation form; CPU tensors and sizes outside the kernels' limits raise."""
+
+    def __init__(self, predictor, joint, beam, blank=0, max_symbols=64, max_len=None, steps_per_replay=16, use_graph=True):
+        self.predictor, self.joint = predictor, joint
+        self.beam, self.blank, self.max_symbols = int(beam), int(blank), int(max_symbols)
+        self.max_len = None if max_len is None else int(max_len)
+        self.steps_per_replay, self.use_graph = int(steps_per_replay) + (int(steps_per_replay) & 1), bool(use_graph)
+        if not 1 <= self.beam <= 15:
+            raise ValueError("BeamSearch: beam = %d outside 1..15 (the top-k launch returns 16 classes, one of which may be the blank)" % self.beam)
+        if self.max_symbols < 1 or self.steps_per_replay < 1 or (self.max_len is not None and self.max_len < 0):
+            raise ValueError("BeamSearch: max_symbols and steps_per_replay are positive, max_len is not negative")
+        if not 0 <= self.blank < joint.ffn_out.out_features or self.beam + 1 > joint.ffn_out.out_features:
+            raise ValueError("BeamSearch: blank inside the vocabulary, beam + 1 <= its size")
+        self._head = _Head(predictor, joint)
+        self._S = self._graph = self._descs = self._key = self._key_w = None
+        self.steps = self.replays = 0
+
+    def _state(self, B, T, dev):
+        pr, jn, K = self.predictor, self.joint, self.beam
+        L, H, R = pr.num_layers, pr.hidden_size, B * K
+        Vp = (jn.ffn_out.out_features + 15) // 16 * 16
+        max_len = T if self.max_len is None else self.max_len
+        n_nodes = int(cfm.lib().cfm_rnnt_beam_nodes(B, T, max_len, K))
+        z = lambda dt, *s: torch.zeros(s, dtype=dt, device=dev)
+        f32, i32, i64 = torch.float32, torch.int32, torch.int64
+        return dict(enc_proj=z(f32, B, T, jn.enc_ffn.out_features), lens=z(i64, B), token=z(i64, R), t=z(i64, R), hash=z(i64, R), fc=z(i32, R), len=z(i32, R),
+                    node=z(i32, R), parent=z(i32, R), ext=z(i32, R), live=z(i32, R), score=z(f32, R), h=z(f32, 2, L, R, H), c=z(f32, 2, L, R, H),
+                    h_new=z(f32, L, R, H), c_new=z(f32, L, R, H), pred=z(f32, R, pr.projection.out_features), act=z(f32, R, jn.pred_ffn.out_features),
+                    logits=z(f32, R, Vp), topk_idx=z(i32, R, K + 1), topk_logp=z(f32, R, K + 1), lse=z(f32, R), nodes=z(i32, n_nodes, 2), fin_score=z(f32, B, K),
+                    fin_node=z(i32, B, K), fin_len=z(i32, B, K), n_fin=z(i32, B), step=z(i32, B), done=z(torch.uint8, B), n_done=z(i32, 1),
+                    nbest_tokens=z(i64, B, K, max_len), nbest_len=z(i32, B, K), nbest_score=z(f32, B, K), all_done=z(torch.bool))
+
+    # what a step changes (capture_graph); the scratch a step writes before it reads it is not among them
+    _SNAP = ("token", "t", "hash", "fc", "len", "node", "parent", "ext", "live", "score", "h", "c", "nodes", "fin_score", "fin_node", "fin_len", "n_fin", "step", "done",
+             "n_done", "nbest_tokens", "nbest_len", "nbest_score")
+
+    def _make_descs(self, S, W, B, T):
+        """The descriptor of the steps of either parity: the h / c buffer a step reads alternates."""
+        out = []
+        for parity in (0, 1):
+            d = cfm.RnntBeamDesc()
+            self._head.fill_weights(d, W)
+            for k in cfm.RnntBeamDesc._fields_:
+                if k[0] in S:
+                    setattr(d, k[0], S[k[0]].data_ptr())
+            d.n_nodes = S["nodes"].shape[0]
+            d.B, d.T, d.V, d.beam, d.blank, d.max_symbols = B, T, self.joint.ffn_out.out_features, self.beam, self.blank, self.max_symbols
+            d.max_len, d.len_by_frames, d.parity = S["nbest_tokens"].shape[2], int(self.max_len is None), parity
+            out.append(d)
+        return out
+
+    def _run_steps(self):
+        lib, S = cfm.lib(), self._S
+        for i in range(self.steps_per_replay):
+            cfm.check(lib.cfm_rnnt_beam_step(ctypes.byref(self._descs[i & 1]), cfm.stream()), "cfm_rnnt_beam_step")
+        S["all_done"].copy_((S["n_done"] >= S["lens"].shape[0]).reshape(()))
+
+    @torch.no_grad()
+    def search(self, enc_out, enc_lens):
+        """enc_out (B, T', E) float32 encoder output on the device, enc_lens (B,) valid frames per utterance.  Returns per utterance a list
+        of (tokens, score), best first, at most `beam`; an utterance without frames gives [([], 0.0)]."""
+        if self.predictor.training or self.joint.training:
+            raise RuntimeError("beam search is an eval-mode operation (the predictor's dropout would be live)")
+        (B, T, _), dev, K = enc_out.shape, enc_out.device, self.beam
+        if dev.type != "cuda":
+            raise RuntimeError("BeamSearch runs on the device only: enc_out is on %s (there is no fallback)" % dev)
+        if B * K > 64 or B < 1 or T < 1:
+            raise RuntimeError("BeamSearch: B * beam = %d * %d rows, the fused step takes 1..64 (and T' >= 1)" % (B, K))
+        why_not = self._head.fused_limits(B * K, dev)
+        if why_not:
+            raise RuntimeError(why_not)
+        wkey = self._head.weights_key()
+        if self._key_w != wkey:                                                         # new weights: packs (by their own key), descriptors and graph
+            self._graph, self._descs, self._key_w = None, None, wkey
+        key = (B, T, K, str(dev))
+        if self._key != key:                                                            # new buffers: descriptors and graph hold their addresses
+            self._S, self._graph, self._descs, self._key = self._state(B, T, dev), None, None, key
+        S = self._S
+        if self._descs is None:
+            self._descs = self._make_descs(S, self._head.packs(dev), B, T)
+        S["enc_proj"].copy_(self.joint.enc_ffn(enc_out.float()))
+        S["lens"].copy_(torch.as_tensor(enc_lens, device=dev).to(torch.int64).clamp(0, T))
+        cfm.check(cfm.lib().cfm_rnnt_beam_begin(ctypes.byref(self._descs[0]), cfm.stream()), "cfm_rnnt_beam_begin")
+        if self.use_graph and self._graph is None:
+            self._graph = capture_graph(self._run_steps, S, self._SNAP, dev)
+        max_len = S["nbest_tokens"].shape[2]
+        limit = (T + max_len + 1) // self.steps_per_replay + 2                           # a step adds one to every live t + len: at most T + max_len + 1 of them
+        self.replays = replay_until_done(self._graph, self._run_steps, lambda: bool(S["all_done"]), limit)
+        lens, scores, toks = S["nbest_len"].tolist(), S["nbest_score"].tolist(), S["nbest_tokens"].cpu()
+        self.steps = int(S["step"].max())
+        return [[(toks[b, j, :lens[b][j]].tolist(), scores[b][j]) for j in range(K) if scores[b][j] != float("-inf")] for b in range(B)]

@@ -217,18 +217,28 @@ class OfflineRecognizer:
         self.encoder = encoder
         self.search = greedy.BatchedGreedySearch(predictor, joint, blank=blank, n_steps=n_steps, **search_kw)
         self.fbank = fbank
-        self.encoder_out = self.encoder_out_lens = None
+        self.encoder_out = self.encoder_out_lens = self._beam = None
 
     @torch.no_grad()
-    def recognize(self, feats, lengths):
+    def recognize(self, feats, lengths, beam=None):
+        """beam=None: the greedy search, a list of B token lists.  beam = 1..15: greedy.BeamSearch over groups of at most 64 // beam utterances,
+        per utterance a list of (tokens, score), best first; an utterance with no encoder frame gives [([], 0.0)]."""
         self.encoder_out, self.encoder_out_lens = self.encoder.forward_utterances(feats, lengths)
-        return self.search.search(self.encoder_out, self.encoder_out_lens)[0]
+        if beam is None:
+            return self.search.search(self.encoder_out, self.encoder_out_lens)[0]
+        import greedy
+        if self._beam is None or self._beam.beam != int(beam):
+            self._beam = greedy.BeamSearch(self.search.predictor, self.search.joint, beam, blank=self.blank, max_symbols=self.search.n_steps)
+        group, out = 64 // self._beam.beam, []
+        for b0 in range(0, self.encoder_out.shape[0], group):
+            out.extend(self._beam.search(self.encoder_out[b0:b0 + group], self.encoder_out_lens[b0:b0 + group]))
+        return out
 
-    def recognize_audio(self, samples, lengths):
+    def recognize_audio(self, samples, lengths, beam=None):
         if self.fbank is None:
             import fbank
             self.fbank = fbank.KaldiFbank()
-        return self.recognize(*self.fbank(samples, lengths))
+        return self.recognize(*self.fbank(samples, lengths), beam=beam)
 
     @torch.no_grad()
     def recognize_ctc(self, feats, lengths, beam=None):

@@ -1220,6 +1220,65 @@ typedef struct {
 int64_t cfm_ctc_beam_nodes(int32_t B, int32_t T, int32_t beam);
 int cfm_ctc_prefix_beam(const cfm_ctc_beam_desc* d, cfm_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * RNN-T beam search on the transducer head: n-best lists with scores, B utterances at once, 1 <= beam <= 15 hypotheses each, everything
+ * float32 (csrc/greedy.hip).  The search is alignment-length synchronous and is stated once, in float64, in tests/rnnt_beam_ref.py (the
+ * reference project has no beam search): a hypothesis is (string, frame t, symbols fc emitted on that frame, score = log of the summed
+ * probability of the alignments found, the predictor input (token, h, c) as cfm_greedy_desc keeps it).  One step, per live hypothesis:
+ * logp = log_softmax over the V real classes of the joint at (t, predictor output); it offers its blank (t + 1, fc = 0, predictor input
+ * unchanged) and, unless fc == max_symbols or its length == max_len, its `beam` best non-blank classes (the lower class first among equal
+ * values); candidates that are the same TOKEN STRING are merged with logaddexp (compared by length, last token and a 64-bit incremental
+ * hash, collision bound in csrc/greedy.hip; only a blank candidate and an extension can meet, the blank candidate's t and state stay);
+ * the `beam` best are kept -- higher score, then the better-ranked parent, then the blank before the extensions, then the lower class, a
+ * merged candidate with the better of its sources; kept candidates with t == lens[b] are finished and enter the finished set (the `beam`
+ * best by score); with that set full, live hypotheses whose score is below its worst are dropped.  An utterance is done when no
+ * hypothesis is live, after at most lens[b] + max_len + 1 steps.
+ *   cfm_rnnt_beam_begin  the empty hypothesis (score 0, token = blank, zero LSTM state) per utterance; lens[b] <= 0: done at once, the
+ *                        empty hypothesis with score 0 is its result.  n_done [1] counts the utterances that are done.
+ *   cfm_rnnt_beam_step   one step for every utterance that is not done (L + 5 launches); when n_done == B every launch returns at once.
+ *                        The step that empties an utterance's live set writes its result.
+ * Rows: hypothesis slot j of utterance b is row b * beam + j, R = B * beam <= 64 rows in all; an utterance's live hypotheses are its
+ * first slots in rank order (live [R] int32 1 / 0).  Weights as in cfm_greedy_desc (out_w [Vp, J], rows >= V zero, out_b there -inf),
+ * enc_proj [B, T, J], lens int64 [B] (clamped to T).  beam + 1 <= V <= 2^20.
+ *   per row [R]: token / t / hash int64, fc / len / node / parent / ext / live int32, score f32; parent and ext say which row of the
+ *     previous step the slot continues and whether it extended it.
+ *   h / c f32 [2, L, R, H]: a step reads buffer `parity` and writes the new slots' states to the other one, so the caller alternates
+ *     parity 0, 1, 0, ... from begin on (steps after the last live one change nothing).  h_new / c_new [L, R, H].
+ *   scratch: pred [R, P], act [R, J], logits [R, Vp], topk_idx int32 / topk_logp f32 [R, beam + 1], lse [R]; nodes int32 pairs
+ *     (parent, token), n_nodes >= cfm_rnnt_beam_nodes(B, T, max_len, beam) = B * (beam * (T + max_len + 1) + 1) pairs; the finished
+ *     set fin_score f32 / fin_node / fin_len int32 [B, beam], n_fin [B]; step int32 [B] the steps an utterance took; done uint8 [B].
+ *   result: nbest_tokens int64 [B, beam, max_len] (entry n holds nbest_len[b, n] tokens, the rest is not touched), nbest_len int32
+ *     [B, beam], nbest_score f32 [B, beam], best first; entries beyond the finished ones have length 0 and score -inf.  No length
+ *     normalisation.
+ *   len_by_frames != 0: a hypothesis of utterance b holds at most min(max_len, lens[b]) tokens (the search's default: max_len = T). */
+typedef struct {
+    const float* embed;
+    const float* lstm_w[4];
+    const float* lstm_b[4];
+    const float *proj_w, *proj_b, *pf_w, *pf_b, *out_w, *out_b;
+    const float* enc_proj;
+    const int64_t* lens;
+    int64_t *token, *t, *hash;
+    int32_t *fc, *len, *node, *parent, *ext, *live;
+    float* score;
+    float *h, *c, *h_new, *c_new, *pred, *act, *logits;
+    int32_t* topk_idx;
+    float *topk_logp, *lse;
+    int32_t* nodes;
+    int64_t n_nodes;
+    float* fin_score;
+    int32_t *fin_node, *fin_len, *n_fin, *step;
+    uint8_t* done;
+    int32_t* n_done;
+    int64_t* nbest_tokens;
+    int32_t* nbest_len;
+    float* nbest_score;
+    int32_t B, T, L, E, H, P, J, V, Vp, beam, blank, max_symbols, max_len, len_by_frames, parity;
+} cfm_rnnt_beam_desc;
+int64_t cfm_rnnt_beam_nodes(int32_t B, int32_t T, int32_t max_len, int32_t beam);
+int cfm_rnnt_beam_begin(const cfm_rnnt_beam_desc* d, cfm_stream_t stream);
+int cfm_rnnt_beam_step(const cfm_rnnt_beam_desc* d, cfm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
