@@ -8,7 +8,7 @@ import cfm as _c
 
 __all__ = ["lstm_forward", "lstm_backward", "fbank", "fbank_stream", "fbank_stream_ragged", "stream_prep", "stream_advance", "dwconv_causal_bn_silu", "conv_cache_update", "dropout_rows", "dropout_mask", "set_deterministic", "gemm_tn", "gemm_tn_group", "layernorm_bwd", "glu_bwd", "dwconv_bn_train", "dwconv_bn_train_bwd", "dwconv_bn_train_groups", "dwconv_bn_train_bwd_groups", "col2im_relu_bwd", "conv1_wgrad", "attention_bwd", "attention_group", "attention_bwd_group",
            "ctc_nll_train_groups", "ctc_grad", "rnnt_nll", "rnnt_grad", "joint_act_bwd", "rnnt_nll_packed", "joint_act_packed", "joint_act_packed_bwd", "ffn_split", "adam_step", "adam_clip_step", "sumsq", "scratch_stats",
-           "gemm", "ffn_fused", "ffn_fused_supported", "rowchain", "rowchain_supported", "rowchain_pair_supported", "layernorm", "attention", "kv_cache_pack", "dwconv_bn_silu", "conv1_relu", "conv1_relu_mma_supported", "conv12_relu", "conv12_supported", "ctc_nll", "ctc_topk", "ctc_greedy", "ctc_greedy_state", "ctc_prefix_beam", "joint_act", "valid_mask", "chunk_mask",
+           "gemm", "ffn_fused", "ffn_fused_supported", "rowchain", "rowchain_supported", "rowchain_pair_supported", "layernorm", "attention", "kv_cache_pack", "dwconv_bn_silu", "conv1_relu", "conv1_relu_mma_supported", "conv12_relu", "conv12_supported", "ctc_nll", "ctc_topk", "ctc_greedy", "ctc_greedy_state", "ctc_prefix_beam", "ctc_align", "joint_act", "valid_mask", "chunk_mask",
            "attn_mask_combine", "cast", "add_rows", "scratch", "prof_enable", "prof_reset", "prof_table", "as_u8_mask"]
 
 
@@ -568,6 +568,44 @@ def ctc_prefix_beam(idx, logp, lens, V, beam=None, blank=0, out=None, nodes=None
     d.B, d.T, d.V, d.k, d.beam, d.blank = B, T, int(V), k, beam, int(blank)
     _c.call("cfm_ctc_prefix_beam", ctypes.byref(d))
     return tokens, nlen, score
+
+
+def ctc_align(logits, V, enc_lens, labels, label_lens, out=None):
+    """CTC forced alignment: the best single alignment of each utterance's frames to its labels (blank 0, as the loss), from UN-normalised f32
+    logits [B,T,ld>=V].  enc_lens / label_lens int32 [B], labels int32 [B,Umax], Umax <= 255.  Returns (path int32 [B,T], score f32 [B],
+    start int32 [B,Umax], end int32 [B,Umax], token_logp f32 [B,Umax]) on the device: path[b,t] the state 0..2U of frame t (-1 at and beyond
+    enc_lens[b]), score the path's log-probability, per label its first / last frame and the sum of its frames' log-probabilities (-1, -1, -inf
+    beyond label_lens[b]); an utterance that has no alignment gives score -inf and that fill everywhere.  out: such a tuple to write into.
+    include/cfm.h cfm_ctc_align states the recursion and its tie rule."""
+    _c.require_hip(logits, enc_lens, labels, label_lens)
+    if logits.dim() != 3 or logits.dtype != torch.float32 or logits.stride(2) != 1 or logits.stride(0) != logits.size(1) * logits.stride(1):
+        raise ValueError("cfm.ctc_align: logits must be float32 [B,T,>=V] with contiguous rows")
+    B, T = logits.shape[:2]
+    for t in (enc_lens, labels, label_lens):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise ValueError("cfm.ctc_align: lengths and labels must be contiguous int32")
+    if labels.dim() != 2 or labels.size(0) != B or enc_lens.numel() != B or label_lens.numel() != B:
+        raise ValueError("cfm.ctc_align: batch sizes differ")
+    Umax, dev = labels.size(1), logits.device
+    if out is None:
+        out = (torch.empty((B, T), dtype=torch.int32, device=dev), torch.empty((B,), dtype=torch.float32, device=dev), torch.empty((B, Umax), dtype=torch.int32, device=dev),
+               torch.empty((B, Umax), dtype=torch.int32, device=dev), torch.empty((B, Umax), dtype=torch.float32, device=dev))
+    path, score, start, end, token_logp = out
+    _c.require_hip(path, score, start, end, token_logp)
+    _dense("ctc_align", path=path, score=score, start=start, end=end, token_logp=token_logp)
+    if ((path.dtype, score.dtype, start.dtype, end.dtype, token_logp.dtype) != (torch.int32, torch.float32, torch.int32, torch.int32, torch.float32) or
+            path.numel() != B * T or score.numel() != B or start.numel() != B * Umax or end.numel() != B * Umax or token_logp.numel() != B * Umax):
+        raise ValueError("cfm.ctc_align: out must be (int32 [B,T], float32 [B], int32 [B,Umax], int32 [B,Umax], float32 [B,Umax])")
+    nbytes = int(_c.lib().cfm_ctc_align_scratch_bytes(B, T, max(Umax, 0)))
+    work = scratch("ctc_lp", B * T * (2 * Umax + 2), torch.float32, dev)
+    moves = scratch("ctc_align_moves", nbytes, torch.uint8, dev)
+    d = _c.CtcAlignDesc()
+    d.logits, d.ld, d.enc_lens, d.labels, d.label_lens = _c.ptr(logits), logits.stride(1), _c.ptr(enc_lens), _c.ptr(labels), _c.ptr(label_lens)
+    d.work, d.scratch, d.scratch_bytes = _c.ptr(work), _c.ptr(moves), nbytes
+    d.path, d.score, d.start, d.end, d.token_logp = _c.ptr(path), _c.ptr(score), _c.ptr(start), _c.ptr(end), _c.ptr(token_logp)
+    d.B, d.T, d.V, d.Umax = B, T, int(V), Umax
+    _c.call("cfm_ctc_align", ctypes.byref(d))
+    return path, score, start, end, token_logp
 
 
 def joint_act(enc, pred, B, T, U, out_dtype):

@@ -252,6 +252,160 @@ __global__ __launch_bounds__(CTC_NT) void cfm_ctc_alpha_kernel(const float* __re
     ctc_alpha_body(blockIdx.x, work, T, V, enc_lens, labels, Umax, label_lens, nll, alpha_out, nllp_out);
 }
 
+// Forced alignment (cfm_ctc_align): the max-plus twin of the alpha recursion on the same shifted lp' rows (subtracting a per-frame constant moves
+// no argmax; sum_t o_t is added back to the score in fp64), same ownership of states, same LDS double buffer with the two -inf guard cells, one
+// barrier per frame, same AHEAD prefetch.  logaddexp becomes a compare-select that also yields the move 0 / 1 / 2 (stay, s-1, s-2): candidates in
+// that order, a later one replaces an earlier one only if strictly greater.  The moves go to global scratch, one byte per (b, t, s), row stride
+// ctc_bp_ld(Umax) bytes (T is not bounded, so they cannot stay in LDS).  The trace-back runs in the same launch: the workgroup copies the move rows of
+// VIT_TB frames into LDS (they are contiguous: dword loads by all 256 threads), thread 0 walks the block backwards in LDS -- one dependent LDS read
+// per frame instead of one dependent global load -- and the block's path entries are stored by the workgroup.  VIT_TB = 64: 64 rows of <= 512 bytes
+// are 32 KiB, 41 KiB with the rest, so three workgroups still fit a CU's 160 KiB and the 2 * len / 64 extra barriers vanish beside the len of the
+// recursion.  Last, parallel over the frames, the first and last frame of every label state, and parallel over u the label's log-probability,
+// summed in f32 from lp' + o_t in frame order.
+constexpr int VIT_TB = 64;                                 // frames per trace-back block
+__host__ __device__ __forceinline__ int ctc_bp_ld(int Umax) { return (2 * Umax + 1 + 3) & ~3; }
+
+__global__ __launch_bounds__(CTC_NT) void cfm_ctc_viterbi_kernel(const float* __restrict__ work, int T, int V, const int* __restrict__ enc_lens,
+                                                                 const int* __restrict__ labels, int Umax, const int* __restrict__ label_lens,
+                                                                 uint8_t* __restrict__ bp, int* __restrict__ path, float* __restrict__ score,
+                                                                 int* __restrict__ start, int* __restrict__ end, float* __restrict__ token_logp) {
+    __shared__ float delta[2][CTC_MAXS + 2];
+    __shared__ double osum[CTC_NT];
+    __shared__ uint32_t stage[VIT_TB * CTC_MAXS / 4];
+    __shared__ int pth[VIT_TB];
+    __shared__ int first[CTC_NT], last[CTC_NT];
+    __shared__ int fin;                                    // the final state, -1: no alignment
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int len = min(max(enc_lens[b], 0), T);
+    const int U = min(max(label_lens[b], 0), Umax);
+    const int S = 2 * U + 1, SM = 2 * Umax + 2, BL = ctc_bp_ld(Umax);
+    const float* lp = work + (int64_t)b * T * SM;
+    uint8_t* mv = bp + (int64_t)b * T * BL;
+    int* pb = path + (int64_t)b * T;
+    bool skip[2], live[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int s = tid + i * CTC_NT;
+        live[i] = s < S;
+        skip[i] = false;
+        if (live[i] && s >= 2 && (s & 1)) {
+            const int z = ext_label(labels, (int64_t)b * Umax, s, V);
+            skip[i] = z != 0 && z != ext_label(labels, (int64_t)b * Umax, s - 2, V);
+        }
+    }
+    if (tid < 2) delta[0][tid] = delta[1][tid] = -INFINITY;
+    if (len > 0) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int s = tid + i * CTC_NT;
+            if (live[i]) {
+                delta[0][s + 2] = s < 2 ? lp[s] : -INFINITY;
+                mv[s] = 0;                                 // frame 0 has no move; the row is staged with the others
+            }
+        }
+    }
+    constexpr int AHEAD = 4;
+    float nxt[AHEAD][2];
+#pragma unroll
+    for (int k = 0; k < AHEAD; ++k)
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int t = 1 + k, s = tid + i * CTC_NT;
+            nxt[k][i] = (live[i] && t < len) ? lp[(int64_t)t * SM + s] : 0.f;
+        }
+    __syncthreads();
+    int cur = 0;
+    for (int t0 = 1; t0 < len; t0 += AHEAD) {
+#pragma unroll
+        for (int k = 0; k < AHEAD; ++k) {
+            const int t = t0 + k;
+            if (t < len) {                                 // uniform
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    const int s = tid + i * CTC_NT;
+                    if (live[i]) {
+                        float best = delta[cur][s + 2];
+                        int m = 0;
+                        const float d1 = delta[cur][s + 1];
+                        if (d1 > best) { best = d1; m = 1; }
+                        if (skip[i]) {
+                            const float d2 = delta[cur][s];
+                            if (d2 > best) { best = d2; m = 2; }
+                        }
+                        delta[cur ^ 1][s + 2] = best + nxt[k][i];
+                        mv[(int64_t)t * BL + s] = (uint8_t)m;
+                        const int tn = t + AHEAD;
+                        nxt[k][i] = tn < len ? lp[(int64_t)tn * SM + s] : 0.f;
+                    }
+                }
+                __syncthreads();
+                cur ^= 1;
+            }
+        }
+    }
+    double part = 0.0;                                      // sum_t o_t, fp64
+    for (int t = tid; t < len; t += CTC_NT) part += (double)lp[(int64_t)t * SM + SM - 1];
+    osum[tid] = part;
+    first[tid] = T;
+    last[tid] = -1;
+    __syncthreads();
+    if (tid == 0) {
+        if (len == 0) {                                    // no frames: only the empty label sequence aligns
+            score[b] = U == 0 ? 0.f : -INFINITY;
+            fin = -1;
+        } else {
+            double tot = 0.0;
+            for (int i = 0; i < CTC_NT; ++i) tot += osum[i];
+            int f = S >= 2 ? S - 2 : 0;                    // the last label, unless ending in the blank after it is strictly better
+            if (S >= 2 && delta[cur][S + 1] > delta[cur][S]) f = S - 1;
+            const float a = delta[cur][f + 2];
+            score[b] = a > -INFINITY ? (float)((double)a + tot) : -INFINITY;
+            fin = a > -INFINITY ? f : -1;
+        }
+    }
+    __syncthreads();
+    const int f = fin;
+    const int plen = f >= 0 ? len : 0;                     // path entries that hold a state; the rest is -1
+    for (int t = plen + tid; t < T; t += CTC_NT) pb[t] = -1;
+    // trace-back, a block of VIT_TB frames at a time, last block first
+    int s_cur = f;
+    for (int hi = plen; hi > 0; hi -= VIT_TB) {
+        const int lo = max(hi - VIT_TB, 0), nw = (hi - lo) * BL / 4;
+        const uint32_t* src = (const uint32_t*)(mv + (int64_t)lo * BL);
+        for (int i = tid; i < nw; i += CTC_NT) stage[i] = src[i];
+        __syncthreads();
+        if (tid == 0) {
+            const uint8_t* rows = (const uint8_t*)stage;
+            for (int t = hi - 1; t >= lo; --t) {
+                pth[t - lo] = s_cur;
+                s_cur = max(s_cur - (int)rows[(t - lo) * BL + s_cur], 0);      // frame 0's row holds 0
+            }
+        }
+        __syncthreads();
+        for (int t = lo + tid; t < hi; t += CTC_NT) {
+            const int s = pth[t - lo];
+            pb[t] = s;
+            if (s & 1) {                                   // a label state: the run's ends within this block are candidates for its first / last frame
+                if (t == lo || pth[t - lo - 1] != s) atomicMin(&first[s >> 1], t);
+                if (t + 1 == hi || pth[t - lo + 1] != s) atomicMax(&last[s >> 1], t);
+            }
+        }
+        __syncthreads();
+    }
+    // per label: start / end frame and the sum of its frames' log-probabilities
+    for (int u = tid; u < Umax; u += CTC_NT) {
+        const int64_t o = (int64_t)b * Umax + u;
+        if (u < U && f >= 0) {
+            const int t0 = first[u], t1 = last[u];
+            float acc = 0.f;
+            for (int t = t0; t <= t1; ++t) acc += lp[(int64_t)t * SM + 2 * u + 1] + lp[(int64_t)t * SM + SM - 1];
+            start[o] = t0; end[o] = t1; token_logp[o] = acc;
+        } else {
+            start[o] = -1; end[o] = -1; token_logp[o] = -INFINITY;
+        }
+    }
+}
+
 // training (cfm_ctc_nll_train_groups): both recursions of every micro-batch of a window in ONE launch, per micro-batch workgroups [0, B) forwards and
 // [B, 2B) backwards.  Each recursion is a serial chain of T' steps on one CU and a micro-batch has 5..40 utterances: as separate launches they ran
 // one after the other on a nearly empty chip (113 + 113 us at config 3)
@@ -360,6 +514,32 @@ static int ctc_forward(const float* logits, int64_t ld, int32_t B, int32_t T, in
 extern "C" int cfm_ctc_nll(const float* logits, int64_t ld, int32_t B, int32_t T, int32_t V, const int32_t* enc_lens,
                            const int32_t* labels, int32_t Umax, const int32_t* label_lens, float* work, float* nll, cfm_stream_t stream) {
     return ctc_forward(logits, ld, B, T, V, enc_lens, labels, Umax, label_lens, work, nullptr, nullptr, nll, nullptr, stream);
+}
+
+extern "C" int64_t cfm_ctc_align_scratch_bytes(int32_t B, int32_t T, int32_t Umax) { return (int64_t)B * T * ctc_bp_ld(Umax); }
+
+extern "C" int cfm_ctc_align(const cfm_ctc_align_desc* d, cfm_stream_t stream) {
+    CFM_CHECK_ARG(d, "cfm_ctc_align: null descriptor");
+    CFM_CHECK_ARG(d->logits && d->enc_lens && d->labels && d->label_lens && d->work && d->scratch && d->path && d->score && d->start && d->end && d->token_logp,
+                  "cfm_ctc_align: null pointer");
+    CFM_CHECK_ARG(d->B > 0 && d->T > 0 && d->V > 1 && d->Umax > 0, "cfm_ctc_align: bad shape B=%d T=%d V=%d Umax=%d", d->B, d->T, d->V, d->Umax);
+    CFM_CHECK_ARG(2 * d->Umax + 1 <= CTC_MAXS, "cfm_ctc_align: Umax=%d labels exceeds %d", d->Umax, (CTC_MAXS - 1) / 2);
+    CFM_CHECK_ARG(d->ld >= d->V && d->ld % 4 == 0, "cfm_ctc_align: row stride %lld must be >= V and a multiple of 4", (long long)d->ld);
+    CFM_CHECK_ARG(d->scratch_bytes >= cfm_ctc_align_scratch_bytes(d->B, d->T, d->Umax), "cfm_ctc_align: scratch of %lld bytes, cfm_ctc_align_scratch_bytes = %lld needed",
+                  (long long)d->scratch_bytes, (long long)cfm_ctc_align_scratch_bytes(d->B, d->T, d->Umax));
+    CFM_CHECK_ARG(((uintptr_t)d->scratch & 3) == 0, "cfm_ctc_align: scratch must be 4-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    {
+        const int64_t rows = (int64_t)d->B * d->T;
+        CfmProfScope prof("ctc_rows", s, 0.0, (double)rows * d->V * 4);
+        CFM_LAUNCH(cfm_ctc_rows_kernel, dim3((unsigned)((rows + CTC_NT / 64 - 1) / (CTC_NT / 64))), dim3(CTC_NT), 0, s, d->logits, d->ld, d->B, d->T, d->V, d->enc_lens,
+                   d->labels, d->Umax, d->label_lens, d->work, (float*)nullptr);
+        if (int rc = cfm_launch_status("cfm_ctc_align (rows)")) return rc;
+    }
+    CfmProfScope prof("ctc_viterbi", s, 0.0, (double)d->B * d->T * ((2 * d->Umax + 1) * 4 + 2 * ctc_bp_ld(d->Umax) + 4));
+    CFM_LAUNCH(cfm_ctc_viterbi_kernel, dim3(d->B), dim3(CTC_NT), 0, s, (const float*)d->work, d->T, d->V, d->enc_lens, d->labels, d->Umax, d->label_lens,
+               (uint8_t*)d->scratch, d->path, d->score, d->start, d->end, d->token_logp);
+    return cfm_launch_status("cfm_ctc_align (viterbi)");
 }
 
 extern "C" int cfm_ctc_nll_train_groups(const cfm_ctc_group* groups, int32_t n, int32_t V, cfm_stream_t stream) {

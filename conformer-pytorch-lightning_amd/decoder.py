@@ -12,6 +12,10 @@ projection's gradients through cfm_gemm / cfm_gemm_tn); `nll` is loss evaluation
 Decoding (eval mode only, csrc/ctc_decode.hip; the reference has none): `greedy_search` (best path), `prefix_beam_search` (n-best lists with
 scores) and `CTCGreedyStream` (best path chunk by chunk, all state on the device).  They read the same logits as `nll` but apply NO dropout:
 Q7 is a quirk of the reference's loss, a decoder that drops activations would only be a worse decoder.
+
+Forced alignment (eval mode only, cfm_ctc_align in csrc/ctc.hip; the reference has none): `forced_align` gives, for a known transcript, each
+token's first and last encoder frame and its log-probability along the best single alignment, and that alignment's score.  Blank is 0 as in the
+loss, and there is no dropout, for the same reason as in decoding.
 """
 import torch
 import torch.nn as nn
@@ -122,6 +126,48 @@ class CTCDecoder(nn.Module):
         tokens, nlen, score = cfm.ctc_prefix_beam(idx, logp, lens, V, beam=beam, blank=blank)
         tokens, nlen, score = tokens.cpu(), nlen.tolist(), score.tolist()
         return [[(tokens[b, n, :nlen[b][n]].tolist(), score[b][n]) for n in range(len(nlen[b])) if score[b][n] > float("-inf")] for b in range(len(nlen))]
+
+    @torch.no_grad()
+    def forced_align(self, encoder_out, encoder_out_lens, padded_labels, label_lengths, return_path=False):
+        """Forced alignment: which frames carry which token of a KNOWN transcript (cfm_ctc_align: the best single alignment, blank 0 as in the loss;
+        include/cfm.h states the recursion and its tie rule).  encoder_out [B, T, D], encoder_out_lens (B,), padded_labels [B, Umax] (padding beyond
+        label_lengths[b] is ignored), label_lengths (B,).  Returns a list of B entries: None for an utterance that has no alignment (fewer frames than
+        labels plus adjacent repeats), else {"score": the path's log-probability, "tokens": [(token, start_frame, end_frame, logp), ...]} with
+        inclusive encoder frames and logp the sum of the token's frames' log-probabilities; return_path=True adds "path", the int32 [len] state
+        indices 0..2U (odd 2u+1: label u, even: blank) on the host.  One host transfer per call."""
+        if self.training:
+            raise RuntimeError("CTCDecoder.forced_align is an eval-mode operation (inference only); in train mode call forward")
+        cfm.require_hip(encoder_out)
+        if encoder_out.dim() != 3:
+            raise ValueError("CTCDecoder.forced_align: encoder_out must be [B, T, D], got %s" % (tuple(encoder_out.shape),))
+        B, T = encoder_out.shape[:2]
+        dev = encoder_out.device
+        i32 = lambda t: torch.as_tensor(t).to(device=dev, dtype=torch.int32).contiguous()
+        lens, labels, llens = i32(encoder_out_lens), i32(padded_labels), i32(label_lengths)
+        if labels.dim() != 2 or labels.shape[0] != B or lens.shape != (B,) or llens.shape != (B,):
+            raise ValueError("CTCDecoder.forced_align: %d utterances, but lengths %s, labels %s, label lengths %s" %
+                             (B, tuple(lens.shape), tuple(labels.shape), tuple(llens.shape)))
+        pk = self._weights(cfm.resolve_precision(self))
+        Umax = labels.shape[1]
+        if Umax == 0:                                          # cfm_ctc_align wants a label column; an empty transcript aligns all-blank
+            labels = torch.zeros((B, 1), dtype=torch.int32, device=dev)
+        path, score, start, end, token_logp = cfm.ctc_align(self._logits(encoder_out, pk), pk.V, lens, labels, llens)
+        # one transfer: everything as float64 columns (frames, states and lengths are far below 2^53)
+        host = torch.cat([t.to(torch.float64).reshape(B, -1) for t in (score, lens.clamp(0, T), llens.clamp(0, Umax), labels, start, end, token_logp, path)], 1).cpu()
+        W = labels.shape[1]
+        out = []
+        for b in range(B):
+            row = host[b]
+            sc, n, U = float(row[0]), int(row[1]), int(row[2])
+            if sc == float("-inf"):
+                out.append(None)
+                continue
+            lab, st, en, lp = (row[3 + k * W:3 + k * W + U].tolist() for k in range(4))
+            entry = {"score": sc, "tokens": [(int(lab[u]), int(st[u]), int(en[u]), lp[u]) for u in range(U)]}
+            if return_path:
+                entry["path"] = row[3 + 4 * W:3 + 4 * W + n].to(torch.int32)
+            out.append(entry)
+        return out
 
 
 class CTCGreedyStream:

@@ -207,7 +207,8 @@ class OfflineRecognizer:
     recognize_audio(samples (B,N) int16 | float32 on the int16 scale, lengths (B,) samples) -> the same from the waveform, through
     fbank.KaldiFbank (deploy.py preprocess); `fbank`: a KaldiFbank, or None for the reference's settings without dither.
     The lengths stay on the device; the only host read is the search's own.  encoder_out / encoder_out_lens: what the last call's search read.
-    ctc: a decoder.CTCDecoder on the same encoder; recognize_ctc / recognize_ctc_audio then decode its output instead (the hybrid model's cheap first pass)."""
+    ctc: a decoder.CTCDecoder on the same encoder; recognize_ctc / recognize_ctc_audio then decode its output instead (the hybrid model's cheap first pass),
+    and align / align_audio give a known transcript's token spans in encoder frames (frame_seconds converts a frame to its start time)."""
 
     def __init__(self, encoder, predictor, joint, blank=0, n_steps=64, fbank=None, ctc=None, **search_kw):
         import greedy
@@ -257,3 +258,27 @@ class OfflineRecognizer:
             import fbank
             self.fbank = fbank.KaldiFbank()
         return self.recognize_ctc(*self.fbank(samples, lengths), beam=beam)
+
+    @torch.no_grad()
+    def align(self, feats, lengths, labels, label_lengths, return_path=False):
+        """Forced alignment of known transcripts with the CTC head: forward_utterances once, as recognize_ctc, then
+        decoder.CTCDecoder.forced_align.  labels [B, Umax], label_lengths (B,).  Per utterance None (no alignment exists, e.g. no encoder frame
+        for a non-empty transcript) or {"score", "tokens": [(token, start_frame, end_frame, logp)]} with inclusive ENCODER frames;
+        frame_seconds converts them."""
+        if self.ctc is None:
+            raise RuntimeError("OfflineRecognizer.align: the recogniser was built without a CTC head (ctc=None)")
+        self.encoder_out, self.encoder_out_lens = self.encoder.forward_utterances(feats, lengths)
+        return self.ctc.forced_align(self.encoder_out, self.encoder_out_lens, labels, label_lengths, return_path=return_path)
+
+    def align_audio(self, samples, lengths, labels, label_lengths, return_path=False):
+        if self.fbank is None:
+            import fbank
+            self.fbank = fbank.KaldiFbank()
+        return self.align(*self.fbank(samples, lengths), labels, label_lengths, return_path=return_path)
+
+    def frame_seconds(self, frame):
+        """Start time in seconds of encoder frame `frame`: the front-end's two stride-2, width-3 convolutions make encoder frame i start at feature
+        frame 4 i, and feature frame j starts at sample j * shift of the recogniser's fbank (the reference's 10 ms at 16 kHz when
+        none was given).  A token aligned to frames [start, end] spans frame_seconds(start) .. frame_seconds(end + 1)."""
+        shift, rate = (self.fbank.shift, self.fbank.sample_frequency) if self.fbank is not None else (160, 16000.0)
+        return 4 * frame * shift / rate

@@ -1220,6 +1220,44 @@ typedef struct {
 int64_t cfm_ctc_beam_nodes(int32_t B, int32_t T, int32_t beam);
 int cfm_ctc_prefix_beam(const cfm_ctc_beam_desc* d, cfm_stream_t stream);
 
+/* cfm_ctc_align: CTC forced alignment (csrc/ctc.hip) -- the best single alignment of each utterance's frames to ITS labels, the max-plus
+ *   (Viterbi) twin of cfm_ctc_nll's alpha recursion.  The reference has nothing of the kind; the algorithm is stated in float64 in
+ *   tests/ctc_align_ref.py.  logits / ld / enc_lens / labels / label_lens / work exactly as for cfm_ctc_nll; blank is 0 as in the loss (an
+ *   alignment against a head uses the blank the head was trained with); labels outside [0, V) are clamped as the loss clamps them; Umax <= 255.
+ *   With lp[t, c] = log_softmax(logits[t, :V])[c], len = enc_lens[b] clamped to [0, T], U = label_lens[b] clamped to [0, Umax] and the extended
+ *   sequence z = (0, y1, 0, ..., yU, 0) of S = 2U + 1 states:
+ *       delta_0[s] = lp[0, z_s] for s < 2, -inf otherwise
+ *       delta_t[s] = lp[t, z_s] + max(delta_{t-1}[s], delta_{t-1}[s-1], delta_{t-1}[s-2])    the s-2 term only where z_s != 0 and z_s != z_{s-2}
+ *   Ties: the candidates are taken in the order stay, s-1, s-2 and a later one replaces an earlier one only if it is STRICTLY greater.  The
+ *   path ends in state S-2 (the last label) unless delta_{len-1}[S-1] is strictly greater; with U = 0 it ends in state 0.  From there the
+ *   recorded moves are followed back to frame 0.  The recursion runs in f32 on lp[t, .] - max_s lp[t, z_s] (no argmax moves); the per-frame
+ *   maxima are added back to the score in fp64.
+ *   score f32 [B]: the path's log-probability; -inf when no alignment exists (len < U + the number of adjacent equal labels, or len == 0 < U),
+ *     0 for len == 0 and U == 0.
+ *   path int32 [B, T]: the state index s_t for t < len, -1 for t >= len and in every frame of an utterance without an alignment.
+ *   start / end int32 [B, Umax]: the first and last frame (inclusive) whose state is 2u + 1; token_logp f32 [B, Umax]: the sum over those
+ *     frames of lp[t, y_u] (f32, in frame order).  Entries u >= U, and all of an utterance without an alignment, are -1, -1 and -inf.
+ *   work: f32 scratch [B, T, 2*Umax + 2] as for cfm_ctc_nll; scratch: the recorded moves, scratch_bytes >= cfm_ctc_align_scratch_bytes(B, T, Umax)
+ *     = B * T * ((2*Umax + 1) rounded up to a multiple of 4) bytes (one byte per frame and state), 4-byte aligned.
+ *   Two launches, no host synchronisation. */
+typedef struct {
+    const float* logits;
+    int64_t ld;
+    const int32_t* enc_lens;
+    const int32_t* labels;
+    const int32_t* label_lens;
+    float* work;
+    void* scratch;
+    int64_t scratch_bytes;
+    int32_t* path;
+    float* score;
+    int32_t *start, *end;
+    float* token_logp;
+    int32_t B, T, V, Umax;
+} cfm_ctc_align_desc;
+int64_t cfm_ctc_align_scratch_bytes(int32_t B, int32_t T, int32_t Umax);
+int cfm_ctc_align(const cfm_ctc_align_desc* d, cfm_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * RNN-T beam search on the transducer head: n-best lists with scores, B utterances at once, 1 <= beam <= 15 hypotheses each, everything
  * float32 (csrc/greedy.hip).  The search is alignment-length synchronous and is stated once, in float64, in tests/rnnt_beam_ref.py (the
