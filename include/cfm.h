@@ -204,7 +204,7 @@ int cfm_ffn_fused(const cfm_ffn_desc* d, cfm_stream_t stream);
  *     xn = LN(x; ln_g, ln_b), rows with ln_mask == 0 zeroed
  *     y  = w1f ? x + alpha * FFN(xn) : x                                         (FFN as in cfm_ffn_fused, SiLU)
  *     y1 = ln1_g ? LN(y) : y -> out_f32        (head without FFN: out_f32 receives x, the new residual stream)
- *     y2 = ln2_g ? LN(y1) : xn -> out16 (optional) and the tail's input
+ *     y2 = ln2_g ? LN(y1) : xn -> the tail's input; behind a feed-forward with ln2_g also -> out16 (optional; not written otherwise)
  *     t  = tail_w ? y2 . Wt^T + tail_b, tail_glu: value*sigmoid(gate) on 16-column fragment pairs -> tail_out (16 bit)
  * The three chains of a conformer block (encoder_layer.py:56-70):
  *     macaron : x, LN_ffm, FFN_m, ln2 = LN_mha, tail = fused QKV                       (no head)
@@ -212,7 +212,7 @@ int cfm_ffn_fused(const cfm_ffn_desc* d, cfm_stream_t stream);
  *     final   : head = pointwise-conv-2 (+ pad mask) + residual, LN_ff, FFN, ln1 = LN_final
  * All matrices are 16-bit FRAGMENT-MAJOR: w[((nfrag*KS + kk)*64 + lane)*8 + j] = W[nfrag*16 + (lane&15)][kk*32 + 8*(lane>>4) + j]
  * for every matrix here, W2 included (the feed-forward keeps its hidden activation as a 32 x FF tile in LDS between the two
- * products, so W2 is read in natural k order).  Instances: D in {144, 256} with the FF / tail sizes of those configs.
+ * products, so W2 is read in natural k order).  Instances: D in {144, 256, 512} with the FF / tail sizes of those configs.
  */
 typedef struct {
     const float* x;
@@ -264,7 +264,7 @@ typedef struct {
     /* The conv-in chain of the SAME block as the input stage of the depthwise stage (with dw_w and the second segment, D = 256): out-projection of the
      * attention context cin_a [M,D] (16 bit) + residual cin_res -> cin_out (this tile's rows; == head_res, != cin_res), LN(cin_ln_*; rows with cin_mask == 0
      * zeroed), pointwise-conv-1 + GLU (cin_tail_w: GLU-interleaved, fragment-major) -- computed per tile for its 32 + 14 halo rows, the GLU rows go
-     * straight to the depthwise stage (head_a is not read).  One launch per block less than conv-in chain + this chain. */
+     * straight to the depthwise stage (head_a is not read, but stays non-NULL: it is what names the head).  One launch per block less than conv-in chain + this chain. */
     const void *cin_a, *cin_w;
     const float *cin_b, *cin_res;
     float* cin_out;
