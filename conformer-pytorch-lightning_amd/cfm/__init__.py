@@ -231,6 +231,13 @@ class RnntBeamDesc(ctypes.Structure):
                 [(n, c_i32) for n in ("B", "T", "L", "E", "H", "P", "J", "V", "Vp", "beam", "blank", "max_symbols", "max_len", "len_by_frames", "parity")])
 
 
+class RnntBeamStreamDesc(ctypes.Structure):
+    _fields_ = ([("beam", RnntBeamDesc)] +
+                [(n, c_p) for n in ("enc", "ef_w", "ef_b", "chunk_proj", "avail", "final", "paused", "feed_final", "overflow", "best_tokens", "best_len", "stable_len",
+                                    "best_score")] +
+                [(n, c_i32) for n in ("chunk", "D")])
+
+
 class FbankDesc(ctypes.Structure):
     _fields_ = ([(n, c_p) for n in ("samples", "lengths", "feats_length", "carry_in", "carry_out", "fresh_in", "pos_in", "fresh_out", "pos_out", "twiddle", "window",
                                     "mel_w", "mel_start", "mel_len", "mel_off", "out")] + [("ld", c_i64)] +
@@ -270,7 +277,7 @@ for _c_name, _cls in dict(
         cfm_layer_train_weights=LayerTrainWeights, cfm_train_group=TrainGroup, cfm_layer_train_io=LayerTrainIO, cfm_layer_train_saved=LayerTrainSaved,
         cfm_layer_train_scratch=LayerTrainScratch, cfm_layer_train_grads=LayerTrainGrads, cfm_layer_weights=LayerWeights, cfm_ctc_group=CtcGroup,
         cfm_rnnt_desc=RnntDesc, cfm_lattice=Lattice, cfm_rnnt_packed_desc=RnntPackedDesc, cfm_ln_bwd_desc=LnBwdDesc, cfm_lstm_desc=LstmDesc, cfm_greedy_desc=GreedyDesc,
-        cfm_greedy_chunk_desc=GreedyChunkDesc, cfm_ctc_greedy_desc=CtcGreedyDesc, cfm_ctc_beam_desc=CtcBeamDesc, cfm_ctc_align_desc=CtcAlignDesc, cfm_rnnt_beam_desc=RnntBeamDesc, cfm_fbank_desc=FbankDesc,
+        cfm_greedy_chunk_desc=GreedyChunkDesc, cfm_ctc_greedy_desc=CtcGreedyDesc, cfm_ctc_beam_desc=CtcBeamDesc, cfm_ctc_align_desc=CtcAlignDesc, cfm_rnnt_beam_desc=RnntBeamDesc, cfm_rnnt_beam_stream_desc=RnntBeamStreamDesc, cfm_fbank_desc=FbankDesc,
         cfm_ffn_split_desc=FfnSplitDesc, cfm_layer_scratch=LayerScratch, cfm_layer_io=LayerIO).items():
     _cls._c_name_ = _c_name
 PROTOTYPES = (
@@ -366,6 +373,10 @@ PROTOTYPES = (
     ("cfm_rnnt_beam_nodes", c_i64, c_i32, c_i32, c_i32, c_i32),
     ("cfm_rnnt_beam_begin", c_int, P(RnntBeamDesc), c_p),
     ("cfm_rnnt_beam_step", c_int, P(RnntBeamDesc), c_p),
+    ("cfm_rnnt_beam_stream_reset", c_int, P(RnntBeamStreamDesc), c_p, c_p),
+    ("cfm_rnnt_beam_stream_feed", c_int, P(RnntBeamStreamDesc), c_p),
+    ("cfm_rnnt_beam_stream_step", c_int, P(RnntBeamStreamDesc), c_p),
+    ("cfm_rnnt_beam_stream_report", c_int, P(RnntBeamStreamDesc), c_p),
 )
 
 _lib = None

@@ -13,7 +13,8 @@
 //   cfm_greedy_chunk_step (4 launches): pred_ffn, the compact row list, the M-tiled vocabulary product, control across the lookahead --
 //     described at its section below
 //   cfm_rnnt_beam_step (5 launches): the RNN-T beam search, hypotheses as rows of the same predictor and joint launches -- described at its
-//     section at the end of the file
+//     section near the end of the file
+//   cfm_rnnt_beam_stream_reset / _feed / _step / _report: that search with the beam carried across encoder chunks -- the last section
 //
 // The torch-operation form of a single-frame step (greedy.py) is ~45 small launches; the predictor's and the single-frame joint's products
 // are "skinny": B <= 64 streams against weight matrices of 0.26-2.5 M elements, i.e. one read of 7.5 M f32 weights per step, spread over
@@ -710,10 +711,15 @@ struct BeamArgs {
 
 __device__ __forceinline__ int64_t beam_nodes_per_utt(int T, int max_len, int beam) { return (int64_t)beam * ((int64_t)T + max_len + 1) + 1; }
 
-// one workgroup per utterance: the empty hypothesis in slot 0, zero LSTM state in both buffers, no finished entry; n == 0: the result
-__global__ __launch_bounds__(256) void cfm_rnnt_beam_begin_kernel(const BeamArgs a) {
-    const int b = blockIdx.x, tid = threadIdx.x, K = a.beam, R = a.B * K;
-    const bool idle = a.lens[b] <= 0;
+// what the streaming entry points (cfm_rnnt_beam_stream_*, at the end of the file) add per stream
+struct BeamStreamArgs : BeamArgs {
+    int* avail;                  // [B] encoder frames fed so far
+    uint8_t *final, *paused;     // [B] the utterance has ended (n = avail); the stream waits for frames
+};
+
+// utterance b's empty hypothesis in slot 0, zero LSTM state in both buffers, no finished entry; idle (no frames): that is the result
+__device__ __forceinline__ void beam_empty_hyp(const BeamArgs& a, int b, int tid, bool idle) {
+    const int K = a.beam, R = a.B * K;
     if (tid < K) {
         const int r = b * K + tid;
         a.token[r] = a.blank; a.t[r] = 0; a.hash[r] = 0;
@@ -730,11 +736,6 @@ __global__ __launch_bounds__(256) void cfm_rnnt_beam_begin_kernel(const BeamArgs
         a.done[b] = idle ? 1 : 0;
         int* nodes = a.nodes + beam_nodes_per_utt(a.T, a.max_len, K) * 2 * b;
         nodes[0] = -1; nodes[1] = -1;
-        if (b == 0) {
-            int n = 0;
-            for (int i = 0; i < a.B; ++i) n += a.lens[i] <= 0 ? 1 : 0;
-            *a.n_done = n;
-        }
     }
     const int KH = K * a.H;
     for (int i = tid; i < 2 * a.L * KH; i += 256) {
@@ -745,7 +746,22 @@ __global__ __launch_bounds__(256) void cfm_rnnt_beam_begin_kernel(const BeamArgs
     }
 }
 
-__global__ __launch_bounds__(256) void cfm_rnnt_beam_control_kernel(const BeamArgs a) {
+// one workgroup per utterance: the empty hypothesis in slot 0, zero LSTM state in both buffers, no finished entry; n == 0: the result
+__global__ __launch_bounds__(256) void cfm_rnnt_beam_begin_kernel(const BeamArgs a) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    beam_empty_hyp(a, b, tid, a.lens[b] <= 0);
+    if (tid == 0 && b == 0) {
+        int n = 0;
+        for (int i = 0; i < a.B; ++i) n += a.lens[i] <= 0 ? 1 : 0;
+        *a.n_done = n;
+    }
+}
+
+// STREAM (cfm_rnnt_beam_stream_step): n is known only once `final` is set -- until then nothing finishes; a paused stream carries its
+// live slots' LSTM state to the other buffer and changes nothing else; the step that leaves a live hypothesis within one frame of
+// `avail` pauses the stream and counts it in n_done (which there counts the streams that are done OR paused)
+template <bool STREAM>
+__global__ __launch_bounds__(256) void cfm_rnnt_beam_control_kernel(const std::conditional_t<STREAM, BeamStreamArgs, BeamArgs> a) {
     __shared__ float c_score[256];
     __shared__ unsigned c_key[256];
     __shared__ int slot_of[256];                            // the new live slot of a candidate, -1: none
@@ -756,11 +772,35 @@ __global__ __launch_bounds__(256) void cfm_rnnt_beam_control_kernel(const BeamAr
     __shared__ float f_score[RB_W];                         // F, best first
     __shared__ int f_node[RB_W], f_len[RB_W];
     __shared__ int new_par[RB_W], new_ext[RB_W];            // by new slot
+    __shared__ int new_t[RB_W];                             // STREAM: the new slots' frames
     __shared__ int s_nkept, s_nlive, s_nfin;
     const int b = blockIdx.x, tid = threadIdx.x, K = a.beam, R = a.B * K, kk = K + 1;
     if (a.done[b]) return;                                  // uniform
-    int64_t n64 = a.lens[b];
-    const int n = n64 < a.T ? (int)n64 : a.T;
+    const int LH = a.L * a.H;
+    const int64_t buf = (int64_t)a.L * R * a.H;
+    const float *h_in = a.h + a.parity * buf, *c_in = a.c + a.parity * buf;
+    float *h_out = a.h + (a.parity ^ 1) * buf, *c_out = a.c + (a.parity ^ 1) * buf;
+    int n, avail = 0;
+    bool fin = true;
+    if constexpr (STREAM) {
+        if (a.paused[b]) {                                  // uniform.  The reorder below with new_par = identity, new_ext = 0: the next step
+            int nl = 0;                                      // reads the other buffer, and so does the step that resumes the stream
+            for (int q = 0; q < K; ++q) nl += a.live[b * K + q] != 0 ? 1 : 0;
+            for (int i = tid; i < nl * LH; i += 256) {
+                const int sl = i / LH, x = i - sl * LH, l = x / a.H, u = x - l * a.H;
+                const int64_t o = ((int64_t)l * R + b * K + sl) * a.H + u;
+                h_out[o] = h_in[o];
+                c_out[o] = c_in[o];
+            }
+            return;
+        }
+        avail = a.avail[b];
+        fin = a.final[b] != 0;
+        n = fin ? (avail < a.T ? avail : a.T) : 0x7fffffff;  // not final: no candidate finishes (the pause rule keeps every t < avail)
+    } else {
+        int64_t n64 = a.lens[b];
+        n = n64 < a.T ? (int)n64 : a.T;
+    }
     const int max_len = a.len_by_frames && n < a.max_len ? n : a.max_len;   // the most tokens of a hypothesis of this utterance
     const int stp = a.step[b];
     const bool overrun = stp >= a.T + a.max_len + 1;        // cannot happen (a step adds one to t + len); would run past the node buffer
@@ -874,21 +914,30 @@ __global__ __launch_bounds__(256) void cfm_rnnt_beam_control_kernel(const BeamAr
         a.live[nr] = 1;
         new_par[slot] = j;
         new_ext[slot] = e != 0 ? 1 : 0;
+        if constexpr (STREAM) new_t[slot] = (int)pt + (e == 0 ? 1 : 0);
     }
     if (tid < K && tid >= nl) a.live[b * K + tid] = 0;
     __syncthreads();
     // the new slots' LSTM states, into the other buffer
-    const int LH = a.L * a.H;
-    const int64_t buf = (int64_t)a.L * R * a.H;
-    const float *h_in = a.h + a.parity * buf, *c_in = a.c + a.parity * buf;
-    float *h_out = a.h + (a.parity ^ 1) * buf, *c_out = a.c + (a.parity ^ 1) * buf;
     for (int i = tid; i < nl * LH; i += 256) {
         const int sl = i / LH, x = i - sl * LH, l = x / a.H, u = x - l * a.H;
         const int64_t src = ((int64_t)l * R + b * K + new_par[sl]) * a.H + u, dst = ((int64_t)l * R + b * K + sl) * a.H + u;
         h_out[dst] = new_ext[sl] ? a.h_new[src] : h_in[src];
         c_out[dst] = new_ext[sl] ? a.c_new[src] : c_in[src];
     }
-    if (nl > 0) return;                                     // uniform
+    if (nl > 0) {                                           // uniform
+        if constexpr (STREAM) {
+            if (tid == 0 && !fin) {                          // the next step is permitted only with every live t <= avail - 2
+                int mt = 0;
+                for (int q = 0; q < nl; ++q) mt = new_t[q] > mt ? new_t[q] : mt;
+                if (mt > avail - 2) {
+                    a.paused[b] = 1;
+                    atomicAdd(a.n_done, 1);
+                }
+            }
+        }
+        return;
+    }
     // the live set is empty: the utterance is done, F is its n-best list (the strings by walking the parent links back)
     if (tid < K) {
         const int64_t o = (int64_t)b * K + tid;
@@ -974,8 +1023,11 @@ extern "C" int cfm_rnnt_beam_begin(const cfm_rnnt_beam_desc* d, cfm_stream_t str
     return cfm_launch_status("cfm_rnnt_beam_begin");
 }
 
-extern "C" int cfm_rnnt_beam_step(const cfm_rnnt_beam_desc* d, cfm_stream_t stream) {
-    if (int rc = beam_check(d, "cfm_rnnt_beam_step")) return rc;
+namespace {
+
+// the launches of one step on the rows of d; the control kernel's arguments are the caller's (offline or streaming)
+template <bool STREAM, class Args>
+int beam_step_launches(const cfm_rnnt_beam_desc* d, const Args& c, cfm_stream_t stream, const char* who) {
     hipStream_t s = (hipStream_t)stream;
     const int R = d->B * d->beam, k = d->beam + 1;
     const int64_t buf = (int64_t)d->L * R * d->H;
@@ -983,7 +1035,7 @@ extern "C" int cfm_rnnt_beam_step(const cfm_rnnt_beam_desc* d, cfm_stream_t stre
     rows.embed = d->embed; rows.lstm_w = d->lstm_w; rows.lstm_b = d->lstm_b; rows.proj_w = d->proj_w; rows.proj_b = d->proj_b; rows.token = d->token;
     rows.h = d->h + d->parity * buf; rows.c = d->c + d->parity * buf; rows.h_new = d->h_new; rows.c_new = d->c_new; rows.pred = d->pred;
     rows.B = R; rows.L = d->L; rows.E = d->E; rows.H = d->H; rows.P = d->P;
-    if (int rc = enqueue_predictor(&rows, d->n_done, s, "cfm_rnnt_beam_step", d->B)) return rc;
+    if (int rc = enqueue_predictor(&rows, d->n_done, s, who, d->B)) return rc;
     {
         SkinnyArgs a = {};
         a.W = d->pf_w; a.bias = d->pf_b; a.B = R; a.N = d->J; a.K = a.K1 = d->P; a.x1 = d->pred; a.ld1 = d->P; a.out = d->act; a.ld_out = d->J; a.enc = d->enc_proj;
@@ -997,8 +1049,234 @@ extern "C" int cfm_rnnt_beam_step(const cfm_rnnt_beam_desc* d, cfm_stream_t stre
         if (int rc = launch_skinny<0>(a, s, "rnnt_beam_joint_out")) return rc;
     }
     if (int rc = cfm_ctc_topk(d->logits, d->Vp, R, 1, d->V, d->live, k, d->topk_idx, d->topk_logp, d->lse, stream)) return rc;
-    const BeamArgs c = beam_args(d);
-    CfmProfScope prof("rnnt_beam_control", s, 0.0, (double)R * (k * 8 + 64));
-    CFM_LAUNCH(cfm_rnnt_beam_control_kernel, dim3((unsigned)d->B), dim3(256), 0, s, c);
-    return cfm_launch_status("cfm_rnnt_beam_step (control)");
+    CfmProfScope prof(STREAM ? "rnnt_beam_stream_control" : "rnnt_beam_control", s, 0.0, (double)R * (k * 8 + 64));
+    CFM_LAUNCH((cfm_rnnt_beam_control_kernel<STREAM>), dim3((unsigned)d->B), dim3(256), 0, s, c);
+    return cfm_launch_status(who);
+}
+
+}  // namespace
+
+extern "C" int cfm_rnnt_beam_step(const cfm_rnnt_beam_desc* d, cfm_stream_t stream) {
+    if (int rc = beam_check(d, "cfm_rnnt_beam_step")) return rc;
+    return beam_step_launches<false>(d, beam_args(d), stream, "cfm_rnnt_beam_step");
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// Streaming RNN-T beam search (cfm_rnnt_beam_stream_reset / _feed / _step / _report): the search above on frames that arrive in pieces;
+// the algorithm is stated in tests/rnnt_beam_ref_stream.py.  enc_proj [B, max_frames, J] fills as frames arrive (avail[b] rows are valid);
+// a stream whose utterance has not ended (`final` not set) steps only while every live hypothesis has t <= avail - 2, else it is PAUSED:
+// after a permitted step every t <= avail - 1 < n for whatever n the utterance turns out to have, so no candidate that should have
+// finished is missed and no live hypothesis waits at t == n -- the steps taken, the live sets and the result are the offline search's.
+// n_done counts the streams that are done or paused ("idle"): when it reaches B the launches before the control kernel return at once.
+//
+// State parity: a paused stream resumes, and must find (h, c) in the buffer the resuming step reads.  Its control workgroup copies its
+// live slots' state from buffer `parity` to the other one on every step (the reorder with the identity for parents); a decode runs
+// whole replays of an even number of steps from parity 0, so whichever step paused the stream, buffer 0 holds its state at the next
+// decode.  The predictor launches are the offline ones.
+//
+// Reads at the frontier: paused and dead rows still run through rnnt_beam_joint_in on stale, valid inputs.  cfm_skinny_kernel<2> reads
+// enc_proj[row / beam, min(t, T - 1)] with T = max_frames, inside [B, max_frames, J] whatever t holds; a row that is read for a result is
+// live in a stream that steps, hence t <= avail - 1: rows >= avail (not yet written) reach only rows whose outputs the control kernel
+// does not read.
+// ---------------------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+struct StreamFeedArgs {
+    const float* chunk_proj;     // [B, chunk, J]
+    float* enc_proj;             // [B, T, J]
+    const int64_t* lens;         // [B] frames of this chunk
+    const uint8_t* feed_final;   // [B] or null
+    const int64_t* t;
+    int* live;
+    int* avail;
+    uint8_t *final, *paused, *done;
+    int *n_idle, *overflow, *nbest_len;
+    float* nbest_score;
+    int B, T, J, chunk, beam;
+};
+
+// one workgroup per stream: lens[b] projected rows appended at row avail[b] (a ragged destination), avail advanced, final latched, the
+// pause rule evaluated again.  avail + lens > max_frames: the overflow flag, nothing about the stream changes.  A done stream ignores feeds.
+__global__ __launch_bounds__(256) void cfm_rnnt_beam_stream_feed_kernel(const StreamFeedArgs a) {
+    const int b = blockIdx.x, tid = threadIdx.x, K = a.beam;
+    if (a.done[b]) return;                                  // uniform
+    int64_t n64 = a.lens[b];
+    const int n = n64 < 0 ? 0 : (n64 < a.chunk ? (int)n64 : a.chunk);
+    const int av = a.avail[b];
+    if (av < 0 || av > a.T || n > a.T - av) {               // uniform
+        if (tid == 0) *a.overflow = 1;
+        return;
+    }
+    const int j4n = a.J / 4;
+    for (int i = tid; i < n * j4n; i += 256) {
+        const int r = i / j4n, j = (i - r * j4n) * 4;
+        *(f32x4*)(a.enc_proj + ((int64_t)b * a.T + av + r) * a.J + j) = *(const f32x4*)(a.chunk_proj + ((int64_t)b * a.chunk + r) * a.J + j);
+    }
+    if (tid == 0) {
+        const int av2 = av + n;
+        const bool fin = a.final[b] != 0 || (a.feed_final && a.feed_final[b] != 0);
+        const int was_idle = a.paused[b] != 0 ? 1 : 0;
+        int idle;
+        a.avail[b] = av2;
+        a.final[b] = fin ? 1 : 0;
+        if (fin && av2 == 0) {                               // an utterance without frames: the empty hypothesis with score 0 is its result
+            a.live[b * K] = 0;
+            a.nbest_len[b * K] = 0;
+            a.nbest_score[b * K] = 0.f;
+            a.done[b] = 1;
+            a.paused[b] = 0;
+            idle = 1;
+        } else {
+            int64_t mt = 0;
+            for (int q = 0; q < K; ++q) {
+                if (a.live[b * K + q] != 0) mt = a.t[b * K + q] > mt ? a.t[b * K + q] : mt;
+            }
+            idle = (!fin && mt > (int64_t)av2 - 2) ? 1 : 0;
+            a.paused[b] = (uint8_t)idle;
+        }
+        if (idle != was_idle) atomicAdd(a.n_idle, idle - was_idle);
+    }
+}
+
+struct StreamResetArgs {
+    BeamArgs a;
+    const uint8_t* mask;         // [B] or null (every stream)
+    int* avail;
+    uint8_t *final, *paused;
+    int *best_len, *stable_len;
+    float* best_score;
+};
+
+// cfm_rnnt_beam_begin_kernel's work for the masked streams: the empty hypothesis, no frames, not final, not done -- and paused, since
+// nothing can step without frames
+__global__ __launch_bounds__(256) void cfm_rnnt_beam_stream_reset_kernel(const StreamResetArgs r) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (b == 0 && tid == 0) {                               // the idle count: a masked stream is idle after this launch, the others are not written by it
+        int n = 0;
+        for (int i = 0; i < r.a.B; ++i) n += (!r.mask || r.mask[i] || r.a.done[i] != 0 || r.paused[i] != 0) ? 1 : 0;
+        *r.a.n_done = n;
+    }
+    if (r.mask && !r.mask[b]) return;                       // uniform
+    beam_empty_hyp(r.a, b, tid, false);
+    if (tid == 0) {
+        r.avail[b] = 0;
+        r.final[b] = 0;
+        r.paused[b] = 1;
+        r.best_len[b] = 0;
+        r.stable_len[b] = 0;
+        r.best_score[b] = 0.f;
+    }
+}
+
+struct StreamReportArgs {
+    const int *live, *len, *node, *nodes;
+    const float* score;
+    const uint8_t* done;
+    int64_t* best_tokens;        // [B, max_len]
+    int *best_len, *stable_len;
+    float* best_score;
+    int B, T, max_len, beam;
+};
+
+// one workgroup (its first wavefront) per stream that is not done: the best live hypothesis (slot 0: the live slots are in rank order)
+// and the length of the longest common prefix, BY TOKENS, of the live hypotheses' strings: lane j walks slot j's string up the trie, first
+// to the shallowest live length, then all in lockstep comparing tokens until the node ids coincide (equal nodes have equal ancestors).
+// The common prefix only grows and is a prefix of every later best hypothesis, so best_tokens below the previous stable length are
+// already there: the backtrace stops at it.
+__global__ __launch_bounds__(64) void cfm_rnnt_beam_stream_report_kernel(const StreamReportArgs a) {
+    const int b = blockIdx.x, lane = threadIdx.x, K = a.beam;
+    if (a.done[b]) return;                                  // uniform: the n-best list is the result
+    const int* nodes = a.nodes + beam_nodes_per_utt(a.T, a.max_len, K) * 2 * b;
+    const bool lv = lane < K && a.live[b * K + lane] != 0;
+    if (!__any(lv)) return;                                 // cannot happen: a stream that is not done has a live hypothesis
+    const int len0 = a.len[b * K], node0 = a.node[b * K];  // slot 0 is live
+    int len = lv ? a.len[b * K + lane] : len0, node = lv ? a.node[b * K + lane] : node0;   // the other lanes mirror slot 0
+    int lmin = len;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int x = __shfl_xor(lmin, o, 64); lmin = x < lmin ? x : lmin; }
+    for (int d = len; d > lmin; --d) node = nodes[2 * node];
+    int stable = lmin;
+    for (int d = lmin; d >= 1; --d) {
+        if (__all(node == __shfl(node, 0, 64))) break;      // uniform
+        const int tok = nodes[2 * node + 1];
+        if (__any(tok != __shfl(tok, 0, 64))) stable = d - 1;
+        node = nodes[2 * node];
+    }
+    if (lane == 0) {
+        int prev = a.stable_len[b];
+        prev = prev < 0 ? 0 : (prev < len0 ? prev : len0);
+        int nd = node0;
+        for (int pos = len0 - 1; pos >= prev; --pos) {
+            a.best_tokens[(int64_t)b * a.max_len + pos] = nodes[2 * nd + 1];
+            nd = nodes[2 * nd];
+        }
+        a.best_len[b] = len0;
+        a.best_score[b] = a.score[b * K];
+        a.stable_len[b] = stable;
+    }
+}
+
+int stream_check(const cfm_rnnt_beam_stream_desc* d, const char* who) {
+    CFM_CHECK_ARG(d, "%s: null descriptor", who);
+    if (int rc = beam_check(&d->beam, who)) return rc;
+    CFM_CHECK_ARG(d->beam.len_by_frames == 0, "%s: max_len is explicit in streaming (len_by_frames = %d)", who, d->beam.len_by_frames);
+    CFM_CHECK_ARG(d->chunk >= 1 && d->D > 0 && d->D % 16 == 0, "%s: chunk >= 1, D a positive multiple of 16 (chunk=%d D=%d)", who, d->chunk, d->D);
+    CFM_CHECK_ARG(d->ef_w && d->ef_b && d->chunk_proj && d->avail && d->final && d->paused && d->overflow && d->best_tokens && d->best_len && d->best_score &&
+                      d->stable_len,
+                  "%s: null pointer", who);
+    return 0;
+}
+
+BeamStreamArgs stream_args(const cfm_rnnt_beam_stream_desc* d) {
+    BeamStreamArgs a;
+    static_cast<BeamArgs&>(a) = beam_args(&d->beam);
+    a.avail = d->avail; a.final = d->final; a.paused = d->paused;
+    return a;
+}
+
+}  // namespace
+
+extern "C" int cfm_rnnt_beam_stream_reset(const cfm_rnnt_beam_stream_desc* d, const uint8_t* mask, cfm_stream_t stream) {
+    if (int rc = stream_check(d, "cfm_rnnt_beam_stream_reset")) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    StreamResetArgs r;
+    r.a = beam_args(&d->beam); r.mask = mask; r.avail = d->avail; r.final = d->final; r.paused = d->paused; r.best_len = d->best_len; r.stable_len = d->stable_len;
+    r.best_score = d->best_score;
+    CfmProfScope prof("rnnt_beam_stream_reset", s, 0.0, 0.0);
+    CFM_LAUNCH(cfm_rnnt_beam_stream_reset_kernel, dim3((unsigned)d->beam.B), dim3(256), 0, s, r);
+    return cfm_launch_status("cfm_rnnt_beam_stream_reset");
+}
+
+extern "C" int cfm_rnnt_beam_stream_feed(const cfm_rnnt_beam_stream_desc* d, cfm_stream_t stream) {
+    if (int rc = stream_check(d, "cfm_rnnt_beam_stream_feed")) return rc;
+    CFM_CHECK_ARG(d->enc, "cfm_rnnt_beam_stream_feed: no encoder output");
+    hipStream_t s = (hipStream_t)stream;
+    const cfm_rnnt_beam_desc* o = &d->beam;
+    MTileArgs m = {};
+    m.W = d->ef_w; m.bias = d->ef_b; m.x = d->enc; m.ldx = d->D; m.M = o->B * d->chunk; m.N = o->J; m.K = d->D; m.out = d->chunk_proj; m.ld_out = o->J;
+    if (int rc = launch_mtile<0>(m, s, "rnnt_beam_stream_enc_ffn")) return rc;
+    StreamFeedArgs f;
+    f.chunk_proj = d->chunk_proj; f.enc_proj = const_cast<float*>(o->enc_proj); f.lens = o->lens; f.feed_final = d->feed_final; f.t = o->t; f.live = o->live;
+    f.avail = d->avail; f.final = d->final; f.paused = d->paused; f.done = o->done; f.n_idle = o->n_done; f.overflow = d->overflow; f.nbest_len = o->nbest_len;
+    f.nbest_score = o->nbest_score; f.B = o->B; f.T = o->T; f.J = o->J; f.chunk = d->chunk; f.beam = o->beam;
+    CfmProfScope prof("rnnt_beam_stream_feed", s, 0.0, (double)o->B * d->chunk * o->J * 8);
+    CFM_LAUNCH(cfm_rnnt_beam_stream_feed_kernel, dim3((unsigned)o->B), dim3(256), 0, s, f);
+    return cfm_launch_status("cfm_rnnt_beam_stream_feed");
+}
+
+extern "C" int cfm_rnnt_beam_stream_step(const cfm_rnnt_beam_stream_desc* d, cfm_stream_t stream) {
+    if (int rc = stream_check(d, "cfm_rnnt_beam_stream_step")) return rc;
+    return beam_step_launches<true>(&d->beam, stream_args(d), stream, "cfm_rnnt_beam_stream_step");
+}
+
+extern "C" int cfm_rnnt_beam_stream_report(const cfm_rnnt_beam_stream_desc* d, cfm_stream_t stream) {
+    if (int rc = stream_check(d, "cfm_rnnt_beam_stream_report")) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const cfm_rnnt_beam_desc* o = &d->beam;
+    StreamReportArgs a;
+    a.live = o->live; a.len = o->len; a.node = o->node; a.nodes = o->nodes; a.score = o->score; a.done = o->done; a.best_tokens = d->best_tokens;
+    a.best_len = d->best_len; a.stable_len = d->stable_len; a.best_score = d->best_score; a.B = o->B; a.T = o->T; a.max_len = o->max_len; a.beam = o->beam;
+    CfmProfScope prof("rnnt_beam_stream_report", s, 0.0, 0.0);
+    CFM_LAUNCH(cfm_rnnt_beam_stream_report_kernel, dim3((unsigned)o->B), dim3(64), 0, s, a);
+    return cfm_launch_status("cfm_rnnt_beam_stream_report");
 }

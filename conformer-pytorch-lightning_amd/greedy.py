@@ -24,7 +24,8 @@ tokens produced by running the reference's predictor / joint modules, and with a
 
 `BatchedGreedySearch` decides one frame per step, `ChunkGreedySearch` (the streaming recogniser's decoder) all remaining frames of a chunk;
 what they share -- weights key, f32 packs, limits, descriptor weights, LSTM step (`_Head`), graph capture and the replay loop -- is here once.
-`BeamSearch` is the RNN-T beam search on the same packs, capture and replay loop: n-best lists with scores, device only.
+`BeamSearch` is the RNN-T beam search on the same packs, capture and replay loop: n-best lists with scores, device only;
+`StreamingBeamSearch` carries its beam across encoder chunks, as `ChunkGreedySearch` carries the greedy hypothesis.
 """
 import ctypes
 
@@ -486,6 +487,21 @@ class ChunkGreedySearch:
         return new
 
 
+def _beam_state(pr, jn, K, B, T, max_len, dev):
+    """The device buffers of cfm.RnntBeamDesc for B utterances of at most T frames, K hypotheses each (both beam searches)."""
+    L, H, R = pr.num_layers, pr.hidden_size, B * K
+    Vp = (jn.ffn_out.out_features + 15) // 16 * 16
+    n_nodes = int(cfm.lib().cfm_rnnt_beam_nodes(B, T, max_len, K))
+    z = lambda dt, *s: torch.zeros(s, dtype=dt, device=dev)
+    f32, i32, i64 = torch.float32, torch.int32, torch.int64
+    return dict(enc_proj=z(f32, B, T, jn.enc_ffn.out_features), lens=z(i64, B), token=z(i64, R), t=z(i64, R), hash=z(i64, R), fc=z(i32, R), len=z(i32, R),
+                node=z(i32, R), parent=z(i32, R), ext=z(i32, R), live=z(i32, R), score=z(f32, R), h=z(f32, 2, L, R, H), c=z(f32, 2, L, R, H),
+                h_new=z(f32, L, R, H), c_new=z(f32, L, R, H), pred=z(f32, R, pr.projection.out_features), act=z(f32, R, jn.pred_ffn.out_features),
+                logits=z(f32, R, Vp), topk_idx=z(i32, R, K + 1), topk_logp=z(f32, R, K + 1), lse=z(f32, R), nodes=z(i32, n_nodes, 2), fin_score=z(f32, B, K),
+                fin_node=z(i32, B, K), fin_len=z(i32, B, K), n_fin=z(i32, B), step=z(i32, B), done=z(torch.uint8, B), n_done=z(i32, 1),
+                nbest_tokens=z(i64, B, K, max_len), nbest_len=z(i32, B, K), nbest_score=z(f32, B, K), all_done=z(torch.bool))
+
+
 class BeamSearch:
     """RNN-T beam search on the device: per utterance the `beam` best finished hypotheses with their scores (log of the summed probability
     of the alignments found, no length normalisation).  The search is alignment-length synchronous and is specified in float64 in
@@ -513,19 +529,7 @@ class BeamSearch:
         self.steps = self.replays = 0
 
     def _state(self, B, T, dev):
-        pr, jn, K = self.predictor, self.joint, self.beam
-        L, H, R = pr.num_layers, pr.hidden_size, B * K
-        Vp = (jn.ffn_out.out_features + 15) // 16 * 16
-        max_len = T if self.max_len is None else self.max_len
-        n_nodes = int(cfm.lib().cfm_rnnt_beam_nodes(B, T, max_len, K))
-        z = lambda dt, *s: torch.zeros(s, dtype=dt, device=dev)
-        f32, i32, i64 = torch.float32, torch.int32, torch.int64
-        return dict(enc_proj=z(f32, B, T, jn.enc_ffn.out_features), lens=z(i64, B), token=z(i64, R), t=z(i64, R), hash=z(i64, R), fc=z(i32, R), len=z(i32, R),
-                    node=z(i32, R), parent=z(i32, R), ext=z(i32, R), live=z(i32, R), score=z(f32, R), h=z(f32, 2, L, R, H), c=z(f32, 2, L, R, H),
-                    h_new=z(f32, L, R, H), c_new=z(f32, L, R, H), pred=z(f32, R, pr.projection.out_features), act=z(f32, R, jn.pred_ffn.out_features),
-                    logits=z(f32, R, Vp), topk_idx=z(i32, R, K + 1), topk_logp=z(f32, R, K + 1), lse=z(f32, R), nodes=z(i32, n_nodes, 2), fin_score=z(f32, B, K),
-                    fin_node=z(i32, B, K), fin_len=z(i32, B, K), n_fin=z(i32, B), step=z(i32, B), done=z(torch.uint8, B), n_done=z(i32, 1),
-                    nbest_tokens=z(i64, B, K, max_len), nbest_len=z(i32, B, K), nbest_score=z(f32, B, K), all_done=z(torch.bool))
+        return _beam_state(self.predictor, self.joint, self.beam, B, T, T if self.max_len is None else self.max_len, dev)
 
     # what a step changes (capture_graph); the scratch a step writes before it reads it is not among them
     _SNAP = ("token", "t", "hash", "fc", "len", "node", "parent", "ext", "live", "score", "h", "c", "nodes", "fin_score", "fin_node", "fin_len", "n_fin", "step", "done",
@@ -586,3 +590,167 @@ class BeamSearch:
         lens, scores, toks = S["nbest_len"].tolist(), S["nbest_score"].tolist(), S["nbest_tokens"].cpu()
         self.steps = int(S["step"].max())
         return [[(toks[b, j, :lens[b][j]].tolist(), scores[b][j]) for j in range(K) if scores[b][j] != float("-inf")] for b in range(B)]
+
+
+class StreamingBeamSearch:
+    """The RNN-T beam search of `BeamSearch` with the beam carried across encoder chunks: `streams` utterances decoded chunk by chunk, every
+    hypothesis, the trie and the projected frames fed so far ((streams, max_frames, J): no ring, a live hypothesis may sit many frames behind
+    the newest) resident on the device.  Specified in float64 in tests/rnnt_beam_ref_stream.py; include/cfm.h (cfm_rnnt_beam_stream_*)
+    restates it.
+
+    A stream whose utterance has not ended steps only while every live hypothesis is at least two frames behind the frames it holds, and
+    PAUSES otherwise; `final` lifts the rule and the stream runs to its n-best list.  Holding one frame back makes the decisions those of the
+    offline search on the whole utterance however the frames were cut: tokens and order are BeamSearch's (max_len given explicitly there too)
+    wherever float32 tells the candidates apart.  The beam trails the encoder by one frame.
+
+    decode(enc_chunk, lens, final) returns per stream dict(stable=tokens, best=(tokens, score), nbest=None | [(tokens, score)] best first):
+    `best` is the top-ranked live hypothesis, `stable` the longest common prefix of all live hypotheses -- it only grows and is a prefix of
+    every entry of the final n-best list: what a UI may print without retracting it --, `nbest` the result once the stream is final and done
+    (`best` is then its first entry).  A done stream ignores feeds until `reset`.
+
+    Limits: streams * beam <= 64, 1 <= beam <= 15, max_frames encoder frames per utterance (more raises), max_len tokens per hypothesis
+    (default: max_frames).  `steps_per_replay` is made even (the LSTM state alternates between two buffers by step parity, and a paused
+    stream must find its state at parity 0 of the next decode).  Device only: there is no torch-operation form."""
+
+    def __init__(self, predictor, joint, streams, beam, chunk, max_frames, max_len=None, blank=0, max_symbols=64, steps_per_replay=8, use_graph=True):
+        self.predictor, self.joint = predictor, joint
+        self.B, self.beam, self.chunk, self.max_frames = int(streams), int(beam), int(chunk), int(max_frames)
+        self.max_len = self.max_frames if max_len is None else int(max_len)
+        self.blank, self.max_symbols = int(blank), int(max_symbols)
+        self.steps_per_replay, self.use_graph = int(steps_per_replay) + (int(steps_per_replay) & 1), bool(use_graph)
+        if not 1 <= self.beam <= 15 or self.B < 1 or self.B * self.beam > 64:
+            raise ValueError("StreamingBeamSearch: 1 <= beam <= 15 and streams * beam <= 64 rows (streams=%d beam=%d)" % (self.B, self.beam))
+        if self.chunk < 1 or self.max_frames < 1 or self.max_len < 0 or self.max_symbols < 1 or self.steps_per_replay < 1:
+            raise ValueError("StreamingBeamSearch: chunk, max_frames, max_symbols and steps_per_replay are positive, max_len is not negative")
+        if not 0 <= self.blank < joint.ffn_out.out_features or self.beam + 1 > joint.ffn_out.out_features:
+            raise ValueError("StreamingBeamSearch: blank inside the vocabulary, beam + 1 <= its size")
+        self._head = _Head(predictor, joint)
+        self.dev = next(predictor.parameters()).device
+        if self.dev.type != "cuda":
+            raise RuntimeError("StreamingBeamSearch runs on the device only: the predictor is on %s (there is no fallback)" % self.dev)
+        why_not = self._head.fused_limits(self.B * self.beam, self.dev)
+        if why_not is None and joint.enc_ffn.in_features % 16:
+            why_not = "the streaming beam search needs an encoder dimension that is a multiple of 16 (there is no fallback)"
+        if why_not:
+            raise RuntimeError(why_not)
+        self.S = self._state()
+        self._graph = self._descs = self._key_w = self._enc_keep = None
+        self.steps = self.replays = self.total_steps = self.total_replays = 0
+        self._stable = [[] for _ in range(self.B)]
+        self._nbest = [None] * self.B
+        self._step_host, self._avail_host = [0] * self.B, [0] * self.B
+        self.reset()
+
+    def _state(self):
+        B, K, C, dev = self.B, self.beam, self.chunk, self.dev
+        S = _beam_state(self.predictor, self.joint, K, B, self.max_frames, self.max_len, dev)
+        z = lambda dt, *s: torch.zeros(s, dtype=dt, device=dev)
+        S.update(chunk_proj=z(torch.float32, B * C, self.joint.enc_ffn.out_features), avail=z(torch.int32, B), final=z(torch.uint8, B), paused=z(torch.uint8, B),
+                 feed_final=z(torch.uint8, B), overflow=z(torch.int32, 1), best_tokens=z(torch.int64, B, max(self.max_len, 1)), best_len=z(torch.int32, B),
+                 stable_len=z(torch.int32, B), best_score=z(torch.float32, B), mask=z(torch.uint8, B))
+        return S
+
+    # what a step changes (capture_graph): BeamSearch's, and the pause flags
+    _SNAP = ("token", "t", "hash", "fc", "len", "node", "parent", "ext", "live", "score", "h", "c", "nodes", "fin_score", "fin_node", "fin_len", "n_fin", "step", "done",
+             "n_done", "nbest_tokens", "nbest_len", "nbest_score", "paused")
+
+    def _make_descs(self, W):
+        out, S = [], self.S
+        for parity in (0, 1):
+            d = cfm.RnntBeamStreamDesc()
+            self._head.fill_weights(d.beam, W)
+            for k in cfm.RnntBeamDesc._fields_:
+                if k[0] in S:
+                    setattr(d.beam, k[0], S[k[0]].data_ptr())
+            d.beam.n_nodes = S["nodes"].shape[0]
+            d.beam.B, d.beam.T, d.beam.V, d.beam.beam, d.beam.blank = self.B, self.max_frames, self.joint.ffn_out.out_features, self.beam, self.blank
+            d.beam.max_symbols, d.beam.max_len, d.beam.len_by_frames, d.beam.parity = self.max_symbols, self.max_len, 0, parity
+            for k in ("chunk_proj", "avail", "final", "paused", "feed_final", "overflow", "best_tokens", "best_len", "stable_len", "best_score"):
+                setattr(d, k, S[k].data_ptr())
+            d.ef_w, d.ef_b = W["ef_w"].data_ptr(), W["ef_b"].data_ptr()
+            d.chunk, d.D = self.chunk, self.joint.enc_ffn.in_features
+            out.append(d)
+        return out
+
+    def _prepare(self):
+        """A change of the weights (_Head.weights_key) drops packs (by their own key), descriptors and graph; the state buffers stay."""
+        wkey = self._head.weights_key()
+        if self._key_w != wkey:
+            self._graph, self._descs, self._key_w = None, None, wkey
+        if self._descs is None:
+            self._descs = self._make_descs(self._head.packs(self.dev, enc_ffn=True))
+
+    def _run_steps(self):
+        lib, S = cfm.lib(), self.S
+        for i in range(self.steps_per_replay):
+            cfm.check(lib.cfm_rnnt_beam_stream_step(ctypes.byref(self._descs[i & 1]), cfm.stream()), "cfm_rnnt_beam_stream_step")
+        S["all_done"].copy_((S["n_done"] >= self.B).reshape(()))
+
+    def reset(self, streams=None):
+        """New utterances on the given streams (all by default): the empty hypothesis, no frames, not final."""
+        self._prepare()
+        idx = list(range(self.B)) if streams is None else [int(b) for b in streams]
+        mask = [0] * self.B
+        for b in idx:
+            mask[b] = 1
+            self._stable[b], self._nbest[b], self._step_host[b], self._avail_host[b] = [], None, 0, 0
+        self.S["mask"].copy_(torch.tensor(mask, dtype=torch.uint8))
+        cfm.check(cfm.lib().cfm_rnnt_beam_stream_reset(ctypes.byref(self._descs[0]), self.S["mask"].data_ptr(), cfm.stream()), "cfm_rnnt_beam_stream_reset")
+
+    @torch.no_grad()
+    def decode(self, enc_chunk, lens=None, final=None):
+        """enc_chunk (B, chunk, E) float32 encoder output of one chunk on the device; lens (B,): how many of its frames belong to each stream
+        (default: all; 0: nothing arrives); final (B,) truthy where the utterance ends with this feed (it may come with 0 frames)."""
+        if self.predictor.training or self.joint.training:
+            raise RuntimeError("beam search is an eval-mode operation (the predictor's dropout would be live)")
+        B, C, K, S, dev = self.B, self.chunk, self.beam, self.S, self.dev
+        if tuple(enc_chunk.shape[:2]) != (B, C) or enc_chunk.device != dev:
+            raise ValueError("StreamingBeamSearch.decode wants (%d, %d, E) on %s, got %s on %s" % (B, C, dev, tuple(enc_chunk.shape), enc_chunk.device))
+        self._prepare()
+        for name, v, dt, hi in (("lens", lens, torch.int64, C), ("feed_final", final, torch.uint8, 1)):
+            if v is None:
+                S[name].fill_(C if name == "lens" else 0)
+            else:
+                v = torch.as_tensor(v)
+                if v.numel() != B:
+                    raise ValueError("StreamingBeamSearch.decode: %d %s for %d streams" % (v.numel(), "lens" if name == "lens" else "final flags", B))
+                S[name].copy_(v.reshape(B).to(torch.int64).clamp(0, hi).to(dt))
+        self._enc_keep = enc_chunk if (enc_chunk.dtype == torch.float32 and enc_chunk.is_contiguous()) else enc_chunk.float().contiguous()
+        for d in self._descs:
+            d.enc = self._enc_keep.data_ptr()
+        lib = cfm.lib()
+        cfm.check(lib.cfm_rnnt_beam_stream_feed(ctypes.byref(self._descs[0]), cfm.stream()), "cfm_rnnt_beam_stream_feed")
+        if self.use_graph and self._graph is None:
+            self._graph = capture_graph(self._run_steps, S, self._SNAP, dev)
+        # a step adds one to every live t + len, which is the steps the stream has taken: at most avail + max_len + 1 of them in all
+        most = max(min(a + C, self.max_frames) + self.max_len + 1 - s for a, s in zip(self._avail_host, self._step_host))
+        S["all_done"].copy_((S["n_done"] >= B).reshape(()))
+        self.replays = 0 if bool(S["all_done"]) else replay_until_done(self._graph, self._run_steps, lambda: bool(S["all_done"]), most // self.steps_per_replay + 2)
+        cfm.check(lib.cfm_rnnt_beam_stream_report(ctypes.byref(self._descs[0]), cfm.stream()), "cfm_rnnt_beam_stream_report")
+        ints = torch.cat([S["avail"], S["step"], S["best_len"], S["stable_len"], S["done"].to(torch.int32), S["overflow"]]).tolist()
+        avail, step, best_len, stable_len, done = (ints[i * B:(i + 1) * B] for i in range(5))
+        overflow = ints[5 * B]
+        if overflow:
+            S["overflow"].zero_()
+            raise RuntimeError("StreamingBeamSearch: a stream was fed more than max_frames = %d encoder frames (nothing of it changed)" % self.max_frames)
+        self.steps = max(s - s0 for s, s0 in zip(step, self._step_host))
+        self.total_steps += self.steps
+        self.total_replays += self.replays
+        self._step_host, self._avail_host = step, avail
+        top = max([n for n, dn in zip(best_len, done) if not dn] + [0])
+        best_tokens = S["best_tokens"][:, :top].cpu() if top else None
+        best_score = S["best_score"].tolist()
+        fresh = [b for b in range(B) if done[b] and self._nbest[b] is None]
+        if fresh:
+            n_len, n_score, n_tok = S["nbest_len"].tolist(), S["nbest_score"].tolist(), S["nbest_tokens"].cpu()
+            for b in fresh:
+                self._nbest[b] = [(n_tok[b, j, :n_len[b][j]].tolist(), n_score[b][j]) for j in range(K) if n_score[b][j] != float("-inf")]
+        out = []
+        for b in range(B):
+            if done[b]:
+                out.append(dict(stable=list(self._stable[b]), best=(list(self._nbest[b][0][0]), self._nbest[b][0][1]), nbest=[(list(t), s) for t, s in self._nbest[b]]))
+                continue
+            row = best_tokens[b, :best_len[b]].tolist() if best_len[b] else []
+            self._stable[b].extend(row[len(self._stable[b]):stable_len[b]])
+            out.append(dict(stable=list(self._stable[b]), best=(row, best_score[b]), nbest=None))
+        return out

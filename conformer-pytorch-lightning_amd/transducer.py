@@ -111,10 +111,16 @@ class StreamingRecognizer:
     frame_lens[b] = 0 is an idle stream: nothing of its encoder or decoder state changes, so it needs no reset before it continues.
 
     lens[b] (without frame_lens): how many of the chunk's encoder frames the DECODER reads for stream b; the encoder still runs and advances the whole
-    window.  Giving both raises: frame_lens already fixes the decoder's lengths."""
+    window.  Giving both raises: frame_lens already fixes the decoder's lengths.
+
+    beam = 1..15 (default None: the greedy decoder above, unchanged): the decoder is `greedy.StreamingBeamSearch`, a beam carried across the chunks
+    (streams * beam <= 64; max_frames encoder frames per utterance, max_len tokens per hypothesis; n_steps is its max_symbols).  step / step_audio then
+    return the decoder's records (stable, best, nbest); step takes final[b], true where stream b's utterance ends with this step, and step_audio passes
+    its own final through -- to the step that runs the utterance's last window.  hyps() is stable + the rest of best per stream, stable_hyps() the part
+    that can no longer change, nbest() the n-best list of the streams that are final and done (None for the others)."""
 
     def __init__(self, encoder, predictor, joint, streams, decoding_chunk_size, num_decoding_left_chunks, blank=0, n_steps=64, carry=True, causal_conv=False,
-                 steps_per_replay=8, graph=True, fbank_args=None, ctc=None):
+                 steps_per_replay=8, graph=True, fbank_args=None, ctc=None, beam=None, max_frames=None, max_len=None):
         import encoder as encoder_module
         import greedy
         if joint.enc_ffn.in_features != encoder.encoder_dim:
@@ -122,23 +128,40 @@ class StreamingRecognizer:
         self.ctc_decoder = _ctc_stream(ctc, encoder, streams, blank, "StreamingRecognizer")
         self.B, self.chunk = int(streams), int(decoding_chunk_size)
         self.encoder_stream = encoder_module.StreamingBatch(encoder, streams, decoding_chunk_size, num_decoding_left_chunks, causal_conv=causal_conv, graph=graph)
-        self.decoder = greedy.ChunkGreedySearch(predictor, joint, streams, decoding_chunk_size, blank=blank, n_steps=n_steps, steps_per_replay=steps_per_replay,
-                                                use_graph=graph, carry=carry, fused=True)
+        self.beam = None if beam is None else int(beam)
+        if self.beam is None:
+            if max_frames is not None or max_len is not None:
+                raise ValueError("StreamingRecognizer: max_frames and max_len belong to the beam search (beam=k)")
+            self.decoder = greedy.ChunkGreedySearch(predictor, joint, streams, decoding_chunk_size, blank=blank, n_steps=n_steps, steps_per_replay=steps_per_replay,
+                                                    use_graph=graph, carry=carry, fused=True)
+        else:
+            if not carry:
+                raise ValueError("StreamingRecognizer: beam search carries the predictor across chunks (carry=False is the greedy decoder's)")
+            if max_frames is None:
+                raise ValueError("StreamingRecognizer: beam=k needs max_frames, the most encoder frames of an utterance")
+            self.decoder = greedy.StreamingBeamSearch(predictor, joint, streams, self.beam, decoding_chunk_size, max_frames, max_len=max_len, blank=blank,
+                                                      max_symbols=n_steps, steps_per_replay=steps_per_replay, use_graph=graph)
+            self._last = [dict(stable=[], best=([], 0.0), nbest=None) for _ in range(int(streams))]
         self.window = self.encoder_stream.window
         self.encoder_out = None
         self.audio, self.fbank_args = None, dict(fbank_args or {})      # step_audio's fbank.StreamingFbank (made on first use) and its keyword arguments
 
-    def step(self, frames, lens=None, frame_lens=None):
+    def step(self, frames, lens=None, frame_lens=None, final=None):
         if lens is not None and frame_lens is not None:
             raise ValueError("StreamingRecognizer.step: give lens (encoder frames the decoder reads) or frame_lens (feature frames of each window), not both")
+        if final is not None and self.beam is None:
+            raise ValueError("StreamingRecognizer.step: final belongs to the beam search (beam=k); the greedy decoder has nothing held back")
         self.encoder_out = self.encoder_stream.step(frames, frame_lens)                 # (B, chunk, D), overwritten by the next step
-        return self._decode(self.encoder_stream.out_lens if frame_lens is not None else lens)
+        return self._decode(self.encoder_stream.out_lens if frame_lens is not None else lens, final)
 
-    def _decode(self, lens):
+    def _decode(self, lens, final=None):
         """The step's encoder chunk and per-stream lengths to the RNN-T decoder and, when there is a CTC head, to its best-path decoder too."""
         if self.ctc_decoder is not None:
             self.ctc_decoder.decode(self.encoder_out, lens)
-        return self.decoder.decode(self.encoder_out, lens)
+        if self.beam is None:
+            return self.decoder.decode(self.encoder_out, lens)
+        self._last = self.decoder.decode(self.encoder_out, lens, final)
+        return self._last
 
     def step_audio(self, samples, lens=None, sample_lens=None, final=None):
         """step() from the waveform (the reference's deploy.py preprocess_stream + greedy_search_streaming_app): samples (B, n) int16 | float32 on
@@ -171,7 +194,10 @@ class StreamingRecognizer:
             self.encoder_out = self.encoder_stream.step_resident()
             return self._decode(lens)
         self.encoder_out = self.encoder_stream.step_resident(self.audio.frame_lens, host_lens=[m for _, m in self.audio.windows])
-        return self._decode(self.encoder_stream.out_lens)
+        if self.beam is None:
+            return self._decode(self.encoder_stream.out_lens)
+        held = set(self.audio.pending())                                                # an utterance ends with the step that runs its last window
+        return self._decode(self.encoder_stream.out_lens, [bool(f) and b not in held for b, f in enumerate(self.audio.schedule.final)])
 
     def pending(self):
         """Streams that still hold a window to run (fbank.StreamingFbank.pending): call step_audio with sample_lens 0 until it is empty."""
@@ -182,14 +208,32 @@ class StreamingRecognizer:
         streams = None if streams is None else list(streams)
         self.encoder_stream.reset(streams)
         self.decoder.reset(streams)
+        if self.beam is not None:
+            for b in (range(self.B) if streams is None else streams):
+                self._last[b] = dict(stable=[], best=([], 0.0), nbest=None)
         if self.ctc_decoder is not None:
             self.ctc_decoder.reset(streams)
         if self.audio is not None:
             self.audio.reset(streams)
 
     def hyps(self):
-        """Everything emitted per stream since its last reset."""
-        return self.decoder.hyps()
+        """Everything emitted per stream since its last reset; beam=k: the stable prefix and the rest of the best live hypothesis (which may still
+        change), the best entry of the n-best list once the stream is done."""
+        if self.beam is None:
+            return self.decoder.hyps()
+        return [list(r["stable"]) + list(r["best"][0][len(r["stable"]):]) for r in self._last]
+
+    def stable_hyps(self):
+        """beam=k: per stream the common prefix of all live hypotheses -- it only grows, and every entry of the final n-best list begins with it."""
+        if self.beam is None:
+            raise RuntimeError("StreamingRecognizer.stable_hyps: the recogniser was built without a beam (beam=None): hyps() never changes what it has returned")
+        return [list(r["stable"]) for r in self._last]
+
+    def nbest(self):
+        """beam=k: per stream [(tokens, score)] best first once its utterance is final and decoded, None until then."""
+        if self.beam is None:
+            raise RuntimeError("StreamingRecognizer.nbest: the recogniser was built without a beam (beam=None)")
+        return [None if r["nbest"] is None else [(list(t), sc) for t, sc in r["nbest"]] for r in self._last]
 
     def ctc_hyps(self):
         """The CTC head's best-path hypotheses per stream since its last reset (the recogniser was built with ctc=...)."""

@@ -1317,6 +1317,56 @@ int64_t cfm_rnnt_beam_nodes(int32_t B, int32_t T, int32_t max_len, int32_t beam)
 int cfm_rnnt_beam_begin(const cfm_rnnt_beam_desc* d, cfm_stream_t stream);
 int cfm_rnnt_beam_step(const cfm_rnnt_beam_desc* d, cfm_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Streaming RNN-T beam search: the search above with a beam carried across encoder chunks (csrc/greedy.hip; the algorithm is stated in
+ * float64 in tests/rnnt_beam_ref_stream.py).  Per stream, avail[b] encoder frames have been fed and final[b] says whether the utterance
+ * has ended (n = avail).  Before each step: final set -- the offline step with n = avail; final not set -- the stream steps only if every
+ * live hypothesis has t <= avail - 2, else it is PAUSED and the step changes nothing about it.  After a permitted step every t <= avail - 1
+ * < n for any n the utterance can still have (a final that arrives with no new frame included), so for every split of an utterance into
+ * feeds the steps taken, the live sets and the n-best list are those of cfm_rnnt_beam_step on the whole utterance; the beam trails the
+ * encoder by one frame.
+ *   `beam` is the offline descriptor with these readings: T = max_frames, enc_proj [B, max_frames, J] is filled as frames arrive (no
+ *     ring: a live hypothesis may sit many frames behind avail), lens int64 [B] holds the frames of the chunk being FED (clamped to
+ *     0..chunk), n_done [1] counts the streams that are done OR paused ("idle": when it reaches B the launches before the control kernel
+ *     return at once; the host reads it once per replay), len_by_frames = 0 (max_len is explicit: n is not known), n_nodes >=
+ *     cfm_rnnt_beam_nodes(B, max_frames, max_len, beam).  Limits as offline: B * beam <= 64, 1 <= beam <= 15.
+ *   avail int32 [B], final / paused uint8 [B]; feed_final uint8 [B] or null: the streams whose utterance ends with this feed; overflow
+ *     int32 [1]: a feed with avail + lens > max_frames sets it and leaves the stream as it was (the host raises).
+ *   enc f32 [B, chunk, D] the chunk's encoder output, ef_w [J, D] / ef_b [J] the joint's enc_ffn, chunk_proj f32 [B * chunk, J] scratch.
+ *   report: best_tokens int64 [B, max_len], best_len int32 [B], best_score f32 [B] the top-ranked live hypothesis; stable_len int32 [B]
+ *     the length of the longest common prefix BY TOKENS of all live hypotheses' strings: it only grows and is a prefix of every entry of the
+ *     final n-best list.  Entries of best_tokens below the previous stable_len are not rewritten (they cannot change).
+ *   cfm_rnnt_beam_stream_reset   cfm_rnnt_beam_begin's work for the streams with mask[b] != 0 (mask null: all): the empty hypothesis,
+ *                                zero state in both buffers, avail = 0, not final, not done, paused; the others are not touched.
+ *   cfm_rnnt_beam_stream_feed    enc_ffn of the chunk (one M-tiled product), then one launch that appends lens[b] projected rows at row
+ *                                avail[b] of each stream, advances avail, latches final and evaluates the pause rule again.  final with
+ *                                avail == 0: done, the result is the empty hypothesis with score 0.  A done stream ignores feeds.
+ *   cfm_rnnt_beam_stream_step    the offline step's launches with the streaming instance of the control kernel (L + 5 launches).  h / c
+ *                                alternate by the caller's parity as offline; a paused stream's control workgroup copies its live slots'
+ *                                state to the other buffer each step, so the step that resumes it finds it whichever parity it has --
+ *                                PROVIDED the caller runs an even number of steps between feeds, starting at parity 0.
+ *   cfm_rnnt_beam_stream_report  one launch: best / stable of every stream that is not done (a done stream's result is nbest_*).
+ * Reads at the frontier: paused and dead rows still pass through the joint on stale inputs; the joint-input launch reads
+ * enc_proj[b, min(t, max_frames - 1)], inside the buffer for any t, and a row whose output is used is live in a stepping stream, so
+ * t <= avail - 1: rows >= avail, which nobody has written, never reach a result. */
+typedef struct {
+    cfm_rnnt_beam_desc beam;
+    const float *enc, *ef_w, *ef_b;
+    float* chunk_proj;
+    int32_t* avail;
+    uint8_t *final, *paused;
+    const uint8_t* feed_final;
+    int32_t* overflow;
+    int64_t* best_tokens;
+    int32_t *best_len, *stable_len;
+    float* best_score;
+    int32_t chunk, D;
+} cfm_rnnt_beam_stream_desc;
+int cfm_rnnt_beam_stream_reset(const cfm_rnnt_beam_stream_desc* d, const uint8_t* mask, cfm_stream_t stream);
+int cfm_rnnt_beam_stream_feed(const cfm_rnnt_beam_stream_desc* d, cfm_stream_t stream);
+int cfm_rnnt_beam_stream_step(const cfm_rnnt_beam_stream_desc* d, cfm_stream_t stream);
+int cfm_rnnt_beam_stream_report(const cfm_rnnt_beam_stream_desc* d, cfm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
