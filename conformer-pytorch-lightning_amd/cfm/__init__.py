@@ -246,6 +246,12 @@ class FbankDesc(ctypes.Structure):
                 [(n, c_p) for n in ("n_new", "final", "carry_len_in", "carry_len_out", "frame_lens")] + [("carry_cap", c_i32)])
 
 
+class ResampleDesc(ctypes.Structure):
+    _fields_ = ([(n, c_p) for n in ("samples", "lengths", "taps", "tap_first", "tap_off", "out", "out_lens")] + [("ld", c_i64), ("ld_out", c_i64)] +
+                [(n, c_i32) for n in ("B", "n_cols", "cap", "samples_i16", "o", "n", "width", "n_live")] +
+                [(n, c_p) for n in ("n_new", "final", "tail_in", "tail_out", "counts_in", "counts_out")] + [("tail_cap", c_i32)])
+
+
 class FfnSplitDesc(ctypes.Structure):
     _fields_ = [("x", c_p), ("psum", c_p), ("psum_b2", c_p), ("psum_splits", c_i32), ("psum_alpha", c_f), ("ln1_g", c_p), ("ln1_b", c_p), ("ln2_g", c_p),
                 ("ln2_b", c_p), ("rows_out", c_p), ("rows2_out", c_p), ("ln_g", c_p), ("ln_b", c_p), ("w1", c_p), ("b1", c_p), ("N1", c_i32), ("act", c_i32),
@@ -277,7 +283,7 @@ for _c_name, _cls in dict(
         cfm_layer_train_weights=LayerTrainWeights, cfm_train_group=TrainGroup, cfm_layer_train_io=LayerTrainIO, cfm_layer_train_saved=LayerTrainSaved,
         cfm_layer_train_scratch=LayerTrainScratch, cfm_layer_train_grads=LayerTrainGrads, cfm_layer_weights=LayerWeights, cfm_ctc_group=CtcGroup,
         cfm_rnnt_desc=RnntDesc, cfm_lattice=Lattice, cfm_rnnt_packed_desc=RnntPackedDesc, cfm_ln_bwd_desc=LnBwdDesc, cfm_lstm_desc=LstmDesc, cfm_greedy_desc=GreedyDesc,
-        cfm_greedy_chunk_desc=GreedyChunkDesc, cfm_ctc_greedy_desc=CtcGreedyDesc, cfm_ctc_beam_desc=CtcBeamDesc, cfm_ctc_align_desc=CtcAlignDesc, cfm_rnnt_beam_desc=RnntBeamDesc, cfm_rnnt_beam_stream_desc=RnntBeamStreamDesc, cfm_fbank_desc=FbankDesc,
+        cfm_greedy_chunk_desc=GreedyChunkDesc, cfm_ctc_greedy_desc=CtcGreedyDesc, cfm_ctc_beam_desc=CtcBeamDesc, cfm_ctc_align_desc=CtcAlignDesc, cfm_rnnt_beam_desc=RnntBeamDesc, cfm_rnnt_beam_stream_desc=RnntBeamStreamDesc, cfm_fbank_desc=FbankDesc, cfm_resample_desc=ResampleDesc,
         cfm_ffn_split_desc=FfnSplitDesc, cfm_layer_scratch=LayerScratch, cfm_layer_io=LayerIO).items():
     _cls._c_name_ = _c_name
 PROTOTYPES = (
@@ -377,6 +383,9 @@ PROTOTYPES = (
     ("cfm_rnnt_beam_stream_feed", c_int, P(RnntBeamStreamDesc), c_p),
     ("cfm_rnnt_beam_stream_step", c_int, P(RnntBeamStreamDesc), c_p),
     ("cfm_rnnt_beam_stream_report", c_int, P(RnntBeamStreamDesc), c_p),
+    ("cfm_resample", c_int, P(ResampleDesc), c_p),
+    ("cfm_resample_stream", c_int, P(ResampleDesc), c_p),
+    ("cfm_resample_tile_blocks", c_i32, c_i32, c_i32, c_i32),
 )
 
 _lib = None

@@ -6,7 +6,7 @@ import torch
 
 import cfm as _c
 
-__all__ = ["lstm_forward", "lstm_backward", "fbank", "fbank_stream", "fbank_stream_ragged", "stream_prep", "stream_advance", "dwconv_causal_bn_silu", "conv_cache_update", "dropout_rows", "dropout_mask", "set_deterministic", "gemm_tn", "gemm_tn_group", "layernorm_bwd", "glu_bwd", "dwconv_bn_train", "dwconv_bn_train_bwd", "dwconv_bn_train_groups", "dwconv_bn_train_bwd_groups", "col2im_relu_bwd", "conv1_wgrad", "attention_bwd", "attention_group", "attention_bwd_group",
+__all__ = ["lstm_forward", "lstm_backward", "fbank", "fbank_stream", "fbank_stream_ragged", "resample", "resample_stream", "stream_prep", "stream_advance", "dwconv_causal_bn_silu", "conv_cache_update", "dropout_rows", "dropout_mask", "set_deterministic", "gemm_tn", "gemm_tn_group", "layernorm_bwd", "glu_bwd", "dwconv_bn_train", "dwconv_bn_train_bwd", "dwconv_bn_train_groups", "dwconv_bn_train_bwd_groups", "col2im_relu_bwd", "conv1_wgrad", "attention_bwd", "attention_group", "attention_bwd_group",
            "ctc_nll_train_groups", "ctc_grad", "rnnt_nll", "rnnt_grad", "joint_act_bwd", "rnnt_nll_packed", "joint_act_packed", "joint_act_packed_bwd", "ffn_split", "adam_step", "adam_clip_step", "sumsq", "scratch_stats",
            "gemm", "ffn_fused", "ffn_fused_supported", "rowchain", "rowchain_supported", "rowchain_pair_supported", "layernorm", "attention", "kv_cache_pack", "dwconv_bn_silu", "conv1_relu", "conv1_relu_mma_supported", "conv12_relu", "conv12_supported", "ctc_nll", "ctc_topk", "ctc_greedy", "ctc_greedy_state", "ctc_prefix_beam", "ctc_align", "joint_act", "valid_mask", "chunk_mask",
            "attn_mask_combine", "cast", "add_rows", "scratch", "prof_enable", "prof_reset", "prof_table", "as_u8_mask"]
@@ -1497,6 +1497,62 @@ def fbank_stream_ragged(samples, n_new, final, state_in, state_out, frame_lens, 
     d.carry_in, d.fresh_in, d.pos_in, d.carry_len_in, d.carry_out, d.fresh_out, d.pos_out, d.carry_len_out = (_c.ptr(t) for t in (ci, fi, pi, li, co, fo, po, lo))
     d.n_new, d.final, d.frame_lens, d.carry_cap, d.hop = _c.ptr(n_new), _c.ptr(final), _c.ptr(frame_lens), ci.shape[1], hop
     _c.call("cfm_fbank_stream", ctypes.byref(d))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# sample-rate conversion (include/cfm.h cfm_resample / cfm_resample_stream, csrc/resample.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+def _resample_desc(who, samples, tables, geometry, out, out_lens):
+    """tables: (taps f32, first int32 [n], offset int32 [n + 1]) on the device (packing.resample_tables); geometry: (o, n, width)."""
+    taps, first, off = tables
+    o, n, width = geometry
+    _c.require_hip(samples, out, out_lens, *tables)
+    _dense(who, taps=taps, tap_first=first, tap_off=off, out_lens=out_lens)
+    if samples.dim() != 2 or (samples.shape[1] > 0 and samples.stride(1) != 1) or samples.dtype not in (torch.int16, torch.float32):
+        raise ValueError("cfm.%s: samples must be (B, N) int16 or float32 with unit inner stride, got %s %s" % (who, tuple(samples.shape), samples.dtype))
+    B, N = samples.shape
+    if out.dim() != 2 or out.dtype != torch.float32 or out.shape[0] != B or (out.shape[1] > 0 and out.stride(1) != 1):
+        raise ValueError("cfm.%s: out must be f32 (%d, cap) with unit inner stride, got %s %s" % (who, B, tuple(out.shape), out.dtype))
+    if taps.dtype != torch.float32 or first.dtype != torch.int32 or off.dtype != torch.int32 or first.numel() != n or off.numel() != n + 1:
+        raise ValueError("cfm.%s: tables are (taps f32, first int32 [%d], offset int32 [%d])" % (who, n, n + 1))
+    if out_lens.dtype != torch.int32 or out_lens.numel() != B:
+        raise ValueError("cfm.%s: out_lens is int32 [%d]" % (who, B))
+    ld = lambda t: t.stride(0) if B > 1 and t.shape[1] > 0 else max(t.stride(0), t.shape[1])      # noqa: E731
+    d = _c.ResampleDesc()
+    d.samples, d.ld, d.n_cols, d.samples_i16 = _c.ptr(samples) if N else None, ld(samples), N, int(samples.dtype == torch.int16)
+    d.taps, d.tap_first, d.tap_off, d.n_live = _c.ptr(taps), _c.ptr(first), _c.ptr(off), taps.numel()
+    d.out, d.ld_out, d.cap, d.out_lens = _c.ptr(out) if out.shape[1] else None, ld(out), out.shape[1], _c.ptr(out_lens)
+    d.B, d.o, d.n, d.width = B, o, n, width
+    return d
+
+
+def resample(samples, lengths, tables, geometry, out, out_lens):
+    """Offline: samples (B, N) int16 | f32, lengths int32 [B] -> out f32 (B, cap) (columns at or beyond an item's ceil(n len / o) samples zero), out_lens int32 [B]."""
+    d = _resample_desc("resample", samples, tables, geometry, out, out_lens)
+    _c.require_hip(lengths)
+    _dense("resample", lengths=lengths)
+    if lengths.dtype != torch.int32 or lengths.numel() != d.B:
+        raise ValueError("cfm.resample: lengths is int32 [%d]" % d.B)
+    d.lengths = _c.ptr(lengths)
+    _c.call("cfm_resample", ctypes.byref(d))
+
+
+def resample_stream(samples, n_new, final, state_in, state_out, tables, geometry, out, out_lens):
+    """Streaming: samples (B, n >= 0), n_new / final int32 [B] on the device; state_* = (tail f32 [B, tail_cap], counts int64 [B, 2] = (samples seen, blocks
+    emitted)), in is read, out is written (the caller swaps them).  out f32 (B, cap >= 0) receives each stream's new samples left-aligned, out_lens their count."""
+    d = _resample_desc("resample_stream", samples, tables, geometry, out, out_lens)
+    (ti, ci), (to, co) = state_in, state_out
+    _c.require_hip(n_new, final, ti, ci, to, co)
+    for name, t, dt, shape in (("tail", ti, torch.float32, None), ("tail", to, torch.float32, None), ("counts", ci, torch.int64, (d.B, 2)), ("counts", co, torch.int64, (d.B, 2)),
+                               ("n_new", n_new, torch.int32, (d.B,)), ("final", final, torch.int32, (d.B,))):
+        if t.dtype != dt or not t.is_contiguous() or (tuple(t.shape) != shape if shape else t.dim() != 2 or t.shape[0] != d.B):
+            raise ValueError("cfm.resample_stream: %s must be contiguous %s %s, got %s %s" % (name, dt, shape or "[%d, tail_cap]" % d.B, t.dtype, tuple(t.shape)))
+    if ti.shape != to.shape or ti.shape[1] < 2 * d.width + d.o:
+        raise ValueError("cfm.resample_stream: the tail buffers are two f32 [%d, >= %d], got %s and %s" % (d.B, 2 * d.width + d.o, tuple(ti.shape), tuple(to.shape)))
+    if len({t.data_ptr() for t in (ti, to)}) != 2 or len({t.data_ptr() for t in (ci, co)}) != 2:
+        raise ValueError("cfm.resample_stream: state in and out must not alias")
+    d.n_new, d.final, d.tail_in, d.tail_out, d.counts_in, d.counts_out, d.tail_cap = _c.ptr(n_new), _c.ptr(final), _c.ptr(ti), _c.ptr(to), _c.ptr(ci), _c.ptr(co), ti.shape[1]
+    _c.call("cfm_resample_stream", ctypes.byref(d))
 
 
 def _lstm_desc(who, x, weights, H, drop):

@@ -575,3 +575,71 @@ def fbank_tables(win, padded):
     twiddle = torch.stack([torch.cos(k), -torch.sin(k)], dim=1).contiguous()
     window = torch.hann_window(win, periodic=False, dtype=torch.float64).pow(0.85)
     return twiddle, window
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# sample-rate conversion tables (csrc/resample.hip): host float64, no module, no cache -- resample.Resampler builds them once
+# ----------------------------------------------------------------------------------------------------------------------
+RESAMPLE_MAX_PHASES = 1024               # reduced new rate n: one int32 first-tap and one offset per phase in LDS
+RESAMPLE_MAX_TABLE_BYTES = 64 * 1024     # the compact f32 tap table, whole in LDS
+RESAMPLE_LIVE = 2.0 ** -60               # |h| below this is a clamped end of the window (cos^2 ~ 4e-33): dropped
+
+
+def resample_geometry(orig_freq, new_freq):
+    """(o, n, base, width): the rates over their gcd, the cutoff min(o, n) * 0.99 and ceil(6 o / base) taps on either side."""
+    import math
+    if int(orig_freq) != orig_freq or int(new_freq) != new_freq or orig_freq < 1 or new_freq < 1:
+        raise ValueError("resample: whole sample rates >= 1 Hz, got %r -> %r" % (orig_freq, new_freq))
+    g = math.gcd(int(orig_freq), int(new_freq))
+    o, n = int(orig_freq) // g, int(new_freq) // g
+    base = min(o, n) * 0.99
+    return o, n, base, int(math.ceil(6 * o / base))
+
+
+def resample_kernel_f64(orig_freq, new_freq):
+    """torchaudio's _get_sinc_resample_kernel (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99) in float64: h [n, 2 width + o],
+    h[j][k] = sinc(t) cos^2(pi t / 12) base / o at t = clamp((-j / n + (k - width) / o) base, -6, 6)."""
+    import math
+    o, n, base, width = resample_geometry(orig_freq, new_freq)
+    i = torch.arange(-width, width + o, dtype=torch.float64).unsqueeze(0) / o
+    j = torch.arange(0, -n, -1, dtype=torch.float64).unsqueeze(1) / n
+    t = ((j + i) * base).clamp_(-6.0, 6.0)
+    window = torch.cos(t * (math.pi / 12.0)) ** 2
+    t = t * math.pi
+    return torch.where(t == 0, torch.ones_like(t), torch.sin(t) / torch.where(t == 0, torch.ones_like(t), t)) * window * (base / o)
+
+
+def resample_tables(orig_freq, new_freq):
+    """The polyphase bank, compact: per phase its one run of live taps (|h| >= 2^-60) rounded to f32, end to end in one vector ->
+    (taps f32 [total], first int32 [n]: the run's first tap k = i + width, offset int32 [n + 1]: where it starts in `taps`) on the host.
+    ValueError beyond RESAMPLE_MAX_PHASES phases or RESAMPLE_MAX_TABLE_BYTES of taps: the kernel keeps the whole bank in LDS."""
+    o, n, _, width = resample_geometry(orig_freq, new_freq)
+    if n > RESAMPLE_MAX_PHASES:
+        raise ValueError("resample_tables: %d -> %d Hz has %d phases (the new rate over the gcd); the kernel takes at most RESAMPLE_MAX_PHASES = %d"
+                         % (orig_freq, new_freq, n, RESAMPLE_MAX_PHASES))
+    if n * 4 > RESAMPLE_MAX_TABLE_BYTES or (2 * width + o) * 4 > 16 * RESAMPLE_MAX_TABLE_BYTES:    # before the dense bank is even built
+        raise ValueError("resample_tables: %d -> %d Hz needs %d taps per phase; the compact table may hold RESAMPLE_MAX_TABLE_BYTES = %d bytes"
+                         % (orig_freq, new_freq, 2 * width + o, RESAMPLE_MAX_TABLE_BYTES))
+    h = resample_kernel_f64(orig_freq, new_freq)
+    taps, first, offset = [], [], [0]
+    for j in range(n):
+        live = torch.nonzero(h[j].abs() >= RESAMPLE_LIVE).flatten()
+        k0, k1 = int(live[0]), int(live[-1]) + 1
+        if k1 - k0 != live.numel():
+            raise ValueError("resample_tables: phase %d of %d -> %d Hz has a gap in its live taps" % (j, orig_freq, new_freq))
+        first.append(k0)
+        offset.append(offset[-1] + k1 - k0)
+        taps.append(h[j, k0:k1].to(torch.float32))
+    if offset[-1] * 4 > RESAMPLE_MAX_TABLE_BYTES:
+        raise ValueError("resample_tables: %d -> %d Hz needs %d live taps, %d bytes; the compact table may hold RESAMPLE_MAX_TABLE_BYTES = %d bytes (and at most "
+                         "RESAMPLE_MAX_PHASES = %d phases)" % (orig_freq, new_freq, offset[-1], offset[-1] * 4, RESAMPLE_MAX_TABLE_BYTES, RESAMPLE_MAX_PHASES))
+    return torch.cat(taps).contiguous(), torch.tensor(first, dtype=torch.int32), torch.tensor(offset, dtype=torch.int32)
+
+
+def unpack_resample_tables(taps, first, offset, n_taps):
+    """Dense (n, n_taps) f32 view of resample_tables' result (tests, documentation)."""
+    dense = torch.zeros((first.numel(), n_taps), dtype=torch.float32)
+    for j, k0 in enumerate(first.tolist()):
+        a, b = int(offset[j]), int(offset[j + 1])
+        dense[j, k0:k0 + b - a] = taps[a:b]
+    return dense

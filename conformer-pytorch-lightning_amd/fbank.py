@@ -9,7 +9,10 @@ no energy column).  One launch of csrc/fbank.hip per call; tables (twiddles, win
 `KaldiFbank` is preprocess: a padded batch of waveforms in, the (padded_feats, feats_length) pair ConformerEncoder.forward takes out.
 `StreamingFbank` is preprocess_stream for B streams with the state on the device: blocks of new samples in, the overlapping feature
 windows encoder.StreamingBatch reads out.  Dither noise is a pure function of (seed, item or stream, absolute frame, sample in frame):
-a frame gets the same draw however the audio was cut into calls, so the streaming features equal the offline ones bit for bit."""
+a frame gets the same draw however the audio was cut into calls, so the streaming features equal the offline ones bit for bit.
+
+The one line of preprocess / preprocess_stream in front of the fbank call, torchaudio's Resample(orig_freq=sample_rate, new_freq=16000)
+(deploy.py:108-110, :129-131), is resample.py (Resampler, StreamingResampler), on the device too."""
 import torch
 
 import cfm

@@ -100,7 +100,9 @@ class StreamingRecognizer:
 
     step_audio(samples, lens=None, sample_lens=None, final=None) is step() from the waveform: fbank.StreamingFbank writes the feature windows straight
     into the encoder step's input buffer (fbank_args: its num_mel_bins, dither, seed, ...; the defaults are the reference's settings without dither);
-    with sample_lens / final the audio comes in packets of any size and an utterance ends where it ends.
+    with sample_lens / final the audio comes in packets of any size and an utterance ends where it ends.  sample_rate (Hz): audio at another rate than
+    the fbank's (browser and telephone audio at 48, 44.1, 8 kHz) goes through a resample.StreamingResampler first, state on the device; step_audio then
+    takes packets only, at most accepts()[b] source samples of stream b per call.
 
     step(frames (B, (chunk - 1) * 4 + 7, F), lens=None, frame_lens=None) -> list of B lists: the tokens the step added.
 
@@ -120,7 +122,7 @@ class StreamingRecognizer:
     that can no longer change, nbest() the n-best list of the streams that are final and done (None for the others)."""
 
     def __init__(self, encoder, predictor, joint, streams, decoding_chunk_size, num_decoding_left_chunks, blank=0, n_steps=64, carry=True, causal_conv=False,
-                 steps_per_replay=8, graph=True, fbank_args=None, ctc=None, beam=None, max_frames=None, max_len=None):
+                 steps_per_replay=8, graph=True, fbank_args=None, ctc=None, beam=None, max_frames=None, max_len=None, sample_rate=None):
         import encoder as encoder_module
         import greedy
         if joint.enc_ffn.in_features != encoder.encoder_dim:
@@ -145,6 +147,13 @@ class StreamingRecognizer:
         self.window = self.encoder_stream.window
         self.encoder_out = None
         self.audio, self.fbank_args = None, dict(fbank_args or {})      # step_audio's fbank.StreamingFbank (made on first use) and its keyword arguments
+        self.resampler = None                                           # resample.StreamingResampler when sample_rate is not the fbank's rate
+        rate = self.fbank_args.get("sample_frequency", 16000)
+        if sample_rate is not None and sample_rate != rate:
+            import resample
+            if int(rate) != rate:
+                raise ValueError("StreamingRecognizer: cannot resample to the fbank's %g Hz, not a whole rate" % rate)
+            self.resampler = resample.StreamingResampler(self.B, sample_rate, int(rate), self.encoder_stream.dev)
 
     def step(self, frames, lens=None, frame_lens=None, final=None):
         if lens is not None and frame_lens is not None:
@@ -186,9 +195,21 @@ class StreamingRecognizer:
         if lens is not None and (ragged or (self.audio is not None and self.audio.schedule is not None)):
             raise ValueError("StreamingRecognizer.step_audio: give lens (encoder frames the decoder reads, whole blocks only) or sample_lens / final "
                              "(packets of any size: the window lengths fix what the decoder reads), not both")
+        if self.resampler is not None and not ragged:
+            raise ValueError("StreamingRecognizer.step_audio: audio at %d Hz is resampled to %d Hz, and a resampled block is not a whole number of fbank blocks: "
+                             "give packets (sample_lens / final), at most accepts() samples per stream" % (self.resampler.orig_freq, self.resampler.new_freq))
         if self.audio is None:
             import fbank
             self.audio = fbank.StreamingFbank(self.B, self.chunk, self.encoder_stream.dev, **self.fbank_args)
+        if self.resampler is not None:                                                  # packets at the source rate -> packets at the fbank's rate
+            if samples.dim() != 2 or samples.shape[0] != self.B:
+                raise ValueError("StreamingRecognizer.step_audio wants (%d, n) samples, got %s" % (self.B, tuple(samples.shape)))
+            sample_lens, final = self.resampler.check(sample_lens, final, samples.shape[1])
+            for b, (n, room) in enumerate(zip(sample_lens, self.accepts())):            # raises before anything changes
+                if n > room:
+                    raise ValueError("StreamingRecognizer.step_audio: stream %d is handed %d samples at %d Hz and accepts %d (what its filter bank can take after "
+                                     "resampling, a final flush included)" % (b, n, self.resampler.orig_freq, room))
+            samples, _, sample_lens = self.resampler.step(samples, sample_lens, final)  # the flushed tail and the end of the utterance arrive together
         self.audio.step(samples, self.encoder_stream.input_buffer(self.audio.fbank.num_mel_bins), sample_lens, final)
         if self.audio.schedule is None:
             self.encoder_out = self.encoder_stream.step_resident()
@@ -198,6 +219,19 @@ class StreamingRecognizer:
             return self._decode(self.encoder_stream.out_lens)
         held = set(self.audio.pending())                                                # an utterance ends with the step that runs its last window
         return self._decode(self.encoder_stream.out_lens, [bool(f) and b not in held for b, f in enumerate(self.audio.schedule.final)])
+
+    def accepts(self):
+        """Samples, at the rate the audio arrives at, that each stream can take in the next step_audio(..., sample_lens).  With a resampler: the most
+        source samples s whose output, were the packet final, still fits the filter bank -- ceil(n (held + s) / o) <= audio.accepts()[b], where `held`
+        are the stream's source samples no emitted block has consumed (at most flush_max output samples' worth)."""
+        if self.audio is None:
+            import fbank
+            self.audio = fbank.StreamingFbank(self.B, self.chunk, self.encoder_stream.dev, **self.fbank_args)
+        room = self.audio.accepts()
+        if self.resampler is None:
+            return room
+        rs = self.resampler
+        return [max(0, a * rs.o // rs.n - h) for a, h in zip(room, rs.schedule.held())]
 
     def pending(self):
         """Streams that still hold a window to run (fbank.StreamingFbank.pending): call step_audio with sample_lens 0 until it is empty."""
@@ -215,6 +249,8 @@ class StreamingRecognizer:
             self.ctc_decoder.reset(streams)
         if self.audio is not None:
             self.audio.reset(streams)
+        if self.resampler is not None:
+            self.resampler.reset(streams)
 
     def hyps(self):
         """Everything emitted per stream since its last reset; beam=k: the stable prefix and the rest of the best live hypothesis (which may still
@@ -248,8 +284,9 @@ class OfflineRecognizer:
     over the whole utterance, then basic_greedy_search), which it runs at batch 1.  Item b's tokens are those of that batch-1 call on utterance b.
 
     recognize(feats (B,T,F), lengths (B,)) -> list of B token lists; items shorter than 7 frames (no encoder frame) give [].
-    recognize_audio(samples (B,N) int16 | float32 on the int16 scale, lengths (B,) samples) -> the same from the waveform, through
-    fbank.KaldiFbank (deploy.py preprocess); `fbank`: a KaldiFbank, or None for the reference's settings without dither.
+    recognize_audio(samples (B,N) int16 | float32 on the int16 scale, lengths (B,) samples, sample_rate=None) -> the same from the waveform, through
+    fbank.KaldiFbank (deploy.py preprocess); `fbank`: a KaldiFbank, or None for the reference's settings without dither.  sample_rate (Hz; also on
+    recognize_ctc_audio and align_audio): audio at another rate than the fbank's goes through resample.Resampler first, on the device.
     The lengths stay on the device; the only host read is the search's own.  encoder_out / encoder_out_lens: what the last call's search read.
     ctc: a decoder.CTCDecoder on the same encoder; recognize_ctc / recognize_ctc_audio then decode its output instead (the hybrid model's cheap first pass),
     and align / align_audio give a known transcript's token spans in encoder frames (frame_seconds converts a frame to its start time)."""
@@ -263,6 +300,7 @@ class OfflineRecognizer:
         self.search = greedy.BatchedGreedySearch(predictor, joint, blank=blank, n_steps=n_steps, **search_kw)
         self.fbank = fbank
         self.encoder_out = self.encoder_out_lens = self._beam = None
+        self._resamplers = {}                                # sample_rate -> resample.Resampler, made on first use
 
     @torch.no_grad()
     def recognize(self, feats, lengths, beam=None):
@@ -279,11 +317,24 @@ class OfflineRecognizer:
             out.extend(self._beam.search(self.encoder_out[b0:b0 + group], self.encoder_out_lens[b0:b0 + group]))
         return out
 
-    def recognize_audio(self, samples, lengths, beam=None):
+    def _features(self, samples, lengths, sample_rate=None):
+        """The waveform batch through the fbank; sample_rate (Hz; None: the fbank's own) other than the fbank's sample_frequency goes through a cached
+        resample.Resampler first (deploy.py preprocess :108-110), whose device-side output lengths the fbank reads."""
         if self.fbank is None:
             import fbank
             self.fbank = fbank.KaldiFbank()
-        return self.recognize(*self.fbank(samples, lengths), beam=beam)
+        if sample_rate is not None and sample_rate != self.fbank.sample_frequency:
+            rs = self._resamplers.get(sample_rate)
+            if rs is None:
+                import resample
+                if int(self.fbank.sample_frequency) != self.fbank.sample_frequency:
+                    raise ValueError("OfflineRecognizer: cannot resample to the fbank's %g Hz, not a whole rate" % self.fbank.sample_frequency)
+                rs = self._resamplers[sample_rate] = resample.Resampler(sample_rate, int(self.fbank.sample_frequency))
+            samples, lengths = rs(samples, lengths)
+        return self.fbank(samples, lengths)
+
+    def recognize_audio(self, samples, lengths, beam=None, sample_rate=None):
+        return self.recognize(*self._features(samples, lengths, sample_rate), beam=beam)
 
     @torch.no_grad()
     def recognize_ctc(self, feats, lengths, beam=None):
@@ -297,11 +348,8 @@ class OfflineRecognizer:
             return self.ctc.greedy_search(self.encoder_out, self.encoder_out_lens, blank=self.blank)
         return self.ctc.prefix_beam_search(self.encoder_out, self.encoder_out_lens, beam=beam, blank=self.blank)
 
-    def recognize_ctc_audio(self, samples, lengths, beam=None):
-        if self.fbank is None:
-            import fbank
-            self.fbank = fbank.KaldiFbank()
-        return self.recognize_ctc(*self.fbank(samples, lengths), beam=beam)
+    def recognize_ctc_audio(self, samples, lengths, beam=None, sample_rate=None):
+        return self.recognize_ctc(*self._features(samples, lengths, sample_rate), beam=beam)
 
     @torch.no_grad()
     def align(self, feats, lengths, labels, label_lengths, return_path=False):
@@ -314,11 +362,8 @@ class OfflineRecognizer:
         self.encoder_out, self.encoder_out_lens = self.encoder.forward_utterances(feats, lengths)
         return self.ctc.forced_align(self.encoder_out, self.encoder_out_lens, labels, label_lengths, return_path=return_path)
 
-    def align_audio(self, samples, lengths, labels, label_lengths, return_path=False):
-        if self.fbank is None:
-            import fbank
-            self.fbank = fbank.KaldiFbank()
-        return self.align(*self.fbank(samples, lengths), labels, label_lengths, return_path=return_path)
+    def align_audio(self, samples, lengths, labels, label_lengths, return_path=False, sample_rate=None):
+        return self.align(*self._features(samples, lengths, sample_rate), labels, label_lengths, return_path=return_path)
 
     def frame_seconds(self, frame):
         """Start time in seconds of encoder frame `frame`: the front-end's two stride-2, width-3 convolutions make encoder frame i start at feature

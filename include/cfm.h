@@ -1367,6 +1367,55 @@ int cfm_rnnt_beam_stream_feed(const cfm_rnnt_beam_stream_desc* d, cfm_stream_t s
 int cfm_rnnt_beam_stream_step(const cfm_rnnt_beam_stream_desc* d, cfm_stream_t stream);
 int cfm_rnnt_beam_stream_report(const cfm_rnnt_beam_stream_desc* d, cfm_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Sample-rate conversion, waveform in, waveform out, one launch (csrc/resample.hip): torchaudio.transforms.Resample(orig_freq, new_freq) with its
+ * defaults (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99), the first line of the reference's preprocess / preprocess_stream
+ * (src/deploy.py:108-110, :129-131) and processor.resample (src/processor.py:49-59).
+ *
+ * FORMULA.  g = gcd(orig, new), o = orig / g, n = new / g, base = min(o, n) * 0.99, width = ceil(6 o / base).  For phase j < n and tap
+ *   k = i + width, i = -width .. width + o - 1 (n_taps = 2 width + o per phase):  t = clamp((-j / n + i / o) base, -6, 6),
+ *   h[j][k] = (t == 0 ? 1 : sin(pi t) / (pi t)) cos^2(pi t / 12) base / o.   y[q n + j] = sum_k h[j][k] seq[q o + k].
+ * PADDING.  seq is the input with `width` zeros in front of it and zeros behind it (torchaudio pads width on the left, width + o on the right);
+ *   the zeros are operands like any other (0.0f in LDS).
+ * OUTPUT LENGTH.  ceil(n L / o) samples for an input of L samples.
+ * TABLE.  taps f32 [tap_off[n]]: phase j's one run of live taps (|h| >= 2^-60, computed in float64 on the host; the others are the clamped ends
+ *   of the window) is taps[tap_off[j] .. tap_off[j + 1]), its first tap is k = tap_first[j]; tap_first int32 [n], tap_off int32 [n + 1].
+ *   n <= 1024 and tap_off[n] <= 16384 (64 KiB): the bank and a tile's input span stay in LDS.
+ * SUMMATION ORDER (part of the contract).  An output sample is ONE f32 fmaf chain over its live taps in ascending tap order, starting from +0.0f:
+ *   acc = fmaf(taps[.], seq[.], acc).  It therefore has the same bits whichever tile, call or mode computed it.
+ *   samples   [B, ld] int16 (samples_i16 != 0; exact in f32) or f32;   out f32 [B, ld_out], `cap` columns of each row are written
+ *
+ * cfm_resample (offline): the input of item b is samples[b, 0 .. lengths[b]) (clamped to n_cols); out_lens[b] <- ceil(n len / o) (clamped to cap), the
+ *   columns at or beyond it are written as zeros.
+ * cfm_resample_stream (B streams, packets of any size): stream b brings n_new[b] >= 0 samples (clamped to n_cols; what lies behind them in its row is
+ *   never read) and final[b] != 0 when its utterance ends with them.  State per stream: counts int64 [B, 2] = (input samples seen c, output blocks
+ *   emitted Q) and tail f32 [B, tail_cap]: the input from sample Q o - width on, c - Q o + width samples (the part before sample 0 is the left padding
+ *   and reads as zero whatever the buffer holds: clearing counts resets a stream).  EMISSION RULE: a call emits every whole block q >= Q with
+ *   (q + 1) o + width <= c -- all of its taps' samples have arrived -- as n samples each, left-aligned in out[b]; a final call emits everything up to
+ *   ceil(n c / o) and leaves the stream reset (counts 0, 0).  out_lens[b] <- the samples emitted, the columns behind them are zeros.  A stream with
+ *   n_new = 0 that is not final changes nothing.  tail_cap >= 2 width + o (a stream holds back fewer than width + o input samples); *_in and *_out
+ *   must not alias (the caller swaps them); cap = 0 is legal (out may then be null), n_cols = 0 too (samples may then be null). */
+typedef struct {
+    const void* samples;
+    const int32_t* lengths;          /* offline */
+    const float* taps;
+    const int32_t *tap_first, *tap_off;
+    float* out;
+    int32_t* out_lens;
+    int64_t ld, ld_out;
+    int32_t B, n_cols, cap, samples_i16, o, n, width, n_live; /* n_live = tap_off[n], the length of `taps` */
+    const int32_t *n_new, *final;    /* streaming: int32 [B] each */
+    const float* tail_in;            /* f32 [B, tail_cap] */
+    float* tail_out;
+    const int64_t* counts_in;        /* int64 [B, 2] */
+    int64_t* counts_out;
+    int32_t tail_cap;
+} cfm_resample_desc;
+int cfm_resample(const cfm_resample_desc* d, cfm_stream_t stream);
+int cfm_resample_stream(const cfm_resample_desc* d, cfm_stream_t stream);
+/* Input blocks (o samples in, n out) per workgroup tile for this reduced rate pair; 0 when the pair does not fit in LDS. */
+int32_t cfm_resample_tile_blocks(int32_t o, int32_t n, int32_t width);
+
 #ifdef __cplusplus
 }
 #endif
