@@ -222,6 +222,11 @@ class CtcAlignDesc(ctypes.Structure):
                 [(n, c_p) for n in ("path", "score", "start", "end", "token_logp")] + [(n, c_i32) for n in ("B", "T", "V", "Umax")])
 
 
+class EditDistanceDesc(ctypes.Structure):
+    _fields_ = ([(n, c_p) for n in ("hyp", "hyp_lens", "ref", "ref_lens", "ref_index", "dist", "counts", "ops", "ops_len", "scratch")] + [("scratch_bytes", c_i64)] +
+                [(n, c_i32) for n in ("P", "R", "Hmax", "Umax")])
+
+
 class RnntBeamDesc(ctypes.Structure):
     _fields_ = ([("embed", c_p), ("lstm_w", c_p * 4), ("lstm_b", c_p * 4)] +
                 [(n, c_p) for n in ("proj_w", "proj_b", "pf_w", "pf_b", "out_w", "out_b", "enc_proj", "lens", "token", "t", "hash", "fc", "len", "node", "parent", "ext",
@@ -283,7 +288,7 @@ for _c_name, _cls in dict(
         cfm_layer_train_weights=LayerTrainWeights, cfm_train_group=TrainGroup, cfm_layer_train_io=LayerTrainIO, cfm_layer_train_saved=LayerTrainSaved,
         cfm_layer_train_scratch=LayerTrainScratch, cfm_layer_train_grads=LayerTrainGrads, cfm_layer_weights=LayerWeights, cfm_ctc_group=CtcGroup,
         cfm_rnnt_desc=RnntDesc, cfm_lattice=Lattice, cfm_rnnt_packed_desc=RnntPackedDesc, cfm_ln_bwd_desc=LnBwdDesc, cfm_lstm_desc=LstmDesc, cfm_greedy_desc=GreedyDesc,
-        cfm_greedy_chunk_desc=GreedyChunkDesc, cfm_ctc_greedy_desc=CtcGreedyDesc, cfm_ctc_beam_desc=CtcBeamDesc, cfm_ctc_align_desc=CtcAlignDesc, cfm_rnnt_beam_desc=RnntBeamDesc, cfm_rnnt_beam_stream_desc=RnntBeamStreamDesc, cfm_fbank_desc=FbankDesc, cfm_resample_desc=ResampleDesc,
+        cfm_greedy_chunk_desc=GreedyChunkDesc, cfm_ctc_greedy_desc=CtcGreedyDesc, cfm_ctc_beam_desc=CtcBeamDesc, cfm_ctc_align_desc=CtcAlignDesc, cfm_edit_distance_desc=EditDistanceDesc, cfm_rnnt_beam_desc=RnntBeamDesc, cfm_rnnt_beam_stream_desc=RnntBeamStreamDesc, cfm_fbank_desc=FbankDesc, cfm_resample_desc=ResampleDesc,
         cfm_ffn_split_desc=FfnSplitDesc, cfm_layer_scratch=LayerScratch, cfm_layer_io=LayerIO).items():
     _cls._c_name_ = _c_name
 PROTOTYPES = (
@@ -376,6 +381,8 @@ PROTOTYPES = (
     ("cfm_ctc_prefix_beam", c_int, P(CtcBeamDesc), c_p),
     ("cfm_ctc_align_scratch_bytes", c_i64, c_i32, c_i32, c_i32),
     ("cfm_ctc_align", c_int, P(CtcAlignDesc), c_p),
+    ("cfm_edit_distance_scratch_bytes", c_i64, c_i32, c_i32, c_i32),
+    ("cfm_edit_distance", c_int, P(EditDistanceDesc), c_p),
     ("cfm_rnnt_beam_nodes", c_i64, c_i32, c_i32, c_i32, c_i32),
     ("cfm_rnnt_beam_begin", c_int, P(RnntBeamDesc), c_p),
     ("cfm_rnnt_beam_step", c_int, P(RnntBeamDesc), c_p),

@@ -8,7 +8,7 @@ import cfm as _c
 
 __all__ = ["lstm_forward", "lstm_backward", "fbank", "fbank_stream", "fbank_stream_ragged", "resample", "resample_stream", "stream_prep", "stream_advance", "dwconv_causal_bn_silu", "conv_cache_update", "dropout_rows", "dropout_mask", "set_deterministic", "gemm_tn", "gemm_tn_group", "layernorm_bwd", "glu_bwd", "dwconv_bn_train", "dwconv_bn_train_bwd", "dwconv_bn_train_groups", "dwconv_bn_train_bwd_groups", "col2im_relu_bwd", "conv1_wgrad", "attention_bwd", "attention_group", "attention_bwd_group",
            "ctc_nll_train_groups", "ctc_grad", "rnnt_nll", "rnnt_grad", "joint_act_bwd", "rnnt_nll_packed", "joint_act_packed", "joint_act_packed_bwd", "ffn_split", "adam_step", "adam_clip_step", "sumsq", "scratch_stats",
-           "gemm", "ffn_fused", "ffn_fused_supported", "rowchain", "rowchain_supported", "rowchain_pair_supported", "layernorm", "attention", "kv_cache_pack", "dwconv_bn_silu", "conv1_relu", "conv1_relu_mma_supported", "conv12_relu", "conv12_supported", "ctc_nll", "ctc_topk", "ctc_greedy", "ctc_greedy_state", "ctc_prefix_beam", "ctc_align", "joint_act", "valid_mask", "chunk_mask",
+           "gemm", "ffn_fused", "ffn_fused_supported", "rowchain", "rowchain_supported", "rowchain_pair_supported", "layernorm", "attention", "kv_cache_pack", "dwconv_bn_silu", "conv1_relu", "conv1_relu_mma_supported", "conv12_relu", "conv12_supported", "ctc_nll", "ctc_topk", "ctc_greedy", "ctc_greedy_state", "ctc_prefix_beam", "ctc_align", "edit_distance", "joint_act", "valid_mask", "chunk_mask",
            "attn_mask_combine", "cast", "add_rows", "scratch", "prof_enable", "prof_reset", "prof_table", "as_u8_mask"]
 
 
@@ -606,6 +606,48 @@ def ctc_align(logits, V, enc_lens, labels, label_lens, out=None):
     d.B, d.T, d.V, d.Umax = B, T, int(V), Umax
     _c.call("cfm_ctc_align", ctypes.byref(d))
     return path, score, start, end, token_logp
+
+
+def edit_distance(hyp, hyp_lens, ref, ref_lens, ref_index=None, counts=True, ops=False, out=None):
+    """Levenshtein distance of P hypothesis-reference pairs in one launch (include/cfm.h cfm_edit_distance states the recurrence and the tie rule of
+    the alignment).  hyp int32 [P,Hmax] with hyp_lens int32 [P], ref int32 [R,Umax] with ref_lens int32 [R], Hmax, Umax <= 1024; pair p is scored
+    against reference ref_index[p] (int32 [P], values in [0, R): the caller's to guarantee), ref_index=None: P == R and reference p.  Returns
+    (dist int32 [P], counts int32 [P,4] = (S, D, I, hits) | None, ops uint8 [P,Hmax+Umax] | None, ops_len int32 [P] | None) on the device; ops
+    (1 hit, 2 substitution, 3 deletion, 4 insertion, 0 beyond ops_len) imply counts.  out: such a tuple to write into (None where not wanted).
+    Nothing is read back to the host."""
+    _c.require_hip(hyp, hyp_lens, ref, ref_lens, ref_index)
+    for t in (hyp, hyp_lens, ref, ref_lens) + (() if ref_index is None else (ref_index,)):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise ValueError("cfm.edit_distance: tokens, lengths and ref_index must be contiguous int32")
+    if hyp.dim() != 2 or ref.dim() != 2:
+        raise ValueError("cfm.edit_distance: hyp must be [P,Hmax] and ref [R,Umax]")
+    (P, Hmax), (R, Umax), dev = hyp.shape, ref.shape, hyp.device
+    if hyp_lens.numel() != P or ref_lens.numel() != R or (ref_index is None and P != R) or (ref_index is not None and ref_index.numel() != P):
+        raise ValueError("cfm.edit_distance: batch sizes differ")
+    if P < 1 or R < 1:
+        raise ValueError("cfm.edit_distance: no pair to score")
+    if Hmax > 1024 or Umax > 1024:
+        raise ValueError("cfm.edit_distance: Hmax=%d Umax=%d exceeds 1024 tokens" % (Hmax, Umax))
+    counts = bool(counts or ops)
+    if out is None:
+        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+        out = (i32(P), i32(P, 4) if counts else None, torch.empty((P, Hmax + Umax), dtype=torch.uint8, device=dev) if ops else None, i32(P) if ops else None)
+    dist, cnt, op, op_len = out
+    _c.require_hip(dist, cnt, op, op_len)
+    _dense("edit_distance", dist=dist, counts=cnt, ops=op, ops_len=op_len)
+    if ((cnt is not None) != counts or (op is not None) != bool(ops) or (op_len is not None) != bool(ops) or dist.dtype != torch.int32 or dist.numel() != P or
+            (counts and (cnt.dtype != torch.int32 or cnt.numel() != 4 * P)) or
+            (ops and (op.dtype != torch.uint8 or op.numel() != P * (Hmax + Umax) or op_len.dtype != torch.int32 or op_len.numel() != P))):
+        raise ValueError("cfm.edit_distance: out must be (int32 [P], int32 [P,4] | None, uint8 [P,Hmax+Umax] | None, int32 [P] | None) as counts / ops ask")
+    nbytes = int(_c.lib().cfm_edit_distance_scratch_bytes(P, Hmax, Umax)) if counts else 0
+    moves = scratch("edit_distance_moves", nbytes, torch.uint8, dev) if nbytes else None
+    d = _c.EditDistanceDesc()
+    d.hyp, d.hyp_lens, d.ref, d.ref_lens, d.ref_index = _c.ptr(hyp), _c.ptr(hyp_lens), _c.ptr(ref), _c.ptr(ref_lens), _c.ptr(ref_index)
+    d.dist, d.counts, d.ops, d.ops_len = _c.ptr(dist), _c.ptr(cnt), _c.ptr(op), _c.ptr(op_len)
+    d.scratch, d.scratch_bytes = _c.ptr(moves), nbytes
+    d.P, d.R, d.Hmax, d.Umax = P, R, Hmax, Umax
+    _c.call("cfm_edit_distance", ctypes.byref(d))
+    return dist, cnt, op, op_len
 
 
 def joint_act(enc, pred, B, T, U, out_dtype):

@@ -289,7 +289,8 @@ class OfflineRecognizer:
     recognize_ctc_audio and align_audio): audio at another rate than the fbank's goes through resample.Resampler first, on the device.
     The lengths stay on the device; the only host read is the search's own.  encoder_out / encoder_out_lens: what the last call's search read.
     ctc: a decoder.CTCDecoder on the same encoder; recognize_ctc / recognize_ctc_audio then decode its output instead (the hybrid model's cheap first pass),
-    and align / align_audio give a known transcript's token spans in encoder frames (frame_seconds converts a frame to its start time)."""
+    and align / align_audio give a known transcript's token spans in encoder frames (frame_seconds converts a frame to its start time).
+    score / score_audio recognise and then score the hypotheses against known transcripts on the device (metrics.py, cfm.edit_distance)."""
 
     def __init__(self, encoder, predictor, joint, blank=0, n_steps=64, fbank=None, ctc=None, **search_kw):
         import greedy
@@ -364,6 +365,31 @@ class OfflineRecognizer:
 
     def align_audio(self, samples, lengths, labels, label_lengths, return_path=False, sample_rate=None):
         return self.align(*self._features(samples, lengths, sample_rate), labels, label_lengths, return_path=return_path)
+
+    @torch.no_grad()
+    def score(self, feats, lengths, labels, label_lengths, beam=None, head="rnnt"):
+        """Recognise, then score against known transcripts (metrics.py over cfm.edit_distance): head="rnnt" is recognize, head="ctc" recognize_ctc.
+        labels [B, Umax] with label_lengths (B,), padding ignored, as for align.  Returns {"hyps": what the recogniser returned, "dist" int32 [B]
+        and "counts" int32 [B, 4] = (S, D, I, hits) of each utterance's best hypothesis, on the device, "error_rate": (S + D + I) / reference
+        tokens of the batch}; with beam also "oracle": metrics.nbest_errors' per-utterance entries, and "oracle_error_rate"."""
+        import metrics
+        if head not in ("rnnt", "ctc"):
+            raise ValueError("OfflineRecognizer.score: head must be \"rnnt\" or \"ctc\", got %r" % (head,))
+        hyps = (self.recognize if head == "rnnt" else self.recognize_ctc)(feats, lengths, beam=beam)
+        dev = self.encoder_out.device
+        refs = metrics._packed((torch.as_tensor(labels), label_lengths), dev, "OfflineRecognizer.score")
+        if refs[0].shape[0] != len(hyps):
+            raise ValueError("OfflineRecognizer.score: %d utterances, but labels %s" % (len(hyps), tuple(refs[0].shape)))
+        best = hyps if beam is None else [n[0][0] for n in hyps]
+        dist, counts = metrics.edit_distance(best, refs, device=dev)
+        out = {"hyps": hyps, "dist": dist, "counts": counts, "error_rate": metrics.ErrorRate(dev).add_counts(counts, refs[1].clamp(0, refs[0].shape[1])).compute()}
+        if beam is not None:
+            out["oracle"] = metrics.nbest_errors(hyps, refs, dev)
+            out["oracle_error_rate"] = metrics.oracle_error_rate(hyps, refs, dev, errors=out["oracle"])
+        return out
+
+    def score_audio(self, samples, lengths, labels, label_lengths, beam=None, head="rnnt", sample_rate=None):
+        return self.score(*self._features(samples, lengths, sample_rate), labels, label_lengths, beam=beam, head=head)
 
     def frame_seconds(self, frame):
         """Start time in seconds of encoder frame `frame`: the front-end's two stride-2, width-3 convolutions make encoder frame i start at feature

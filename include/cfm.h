@@ -1258,6 +1258,38 @@ typedef struct {
 int64_t cfm_ctc_align_scratch_bytes(int32_t B, int32_t T, int32_t Umax);
 int cfm_ctc_align(const cfm_ctc_align_desc* d, cfm_stream_t stream);
 
+/* cfm_edit_distance: Levenshtein distance of P hypothesis-reference pairs in one launch, with one fixed optimal alignment each
+ *   (csrc/edit_distance.hip) -- the device counterpart of the reference's torchmetrics.WordErrorRate; stated in pure Python in
+ *   tests/edit_distance_ref.py.  Tokens are int32 and are compared for equality only (any value, negative included).  Pair p is hypothesis
+ *   row p, h[0:H] with H = hyp_lens[p] clamped to [0, Hmax], against reference row ref_index[p] (clamped to [0, R); ref_index null: row p,
+ *   and P == R), r[0:U] with U = ref_lens[.] clamped to [0, Umax]; columns at and past the lengths are never read.  Hmax, Umax <= 1024.
+ *       D[i][0] = i, D[0][j] = j, D[i][j] = min(D[i-1][j-1] + (r[i-1] != h[j-1]), D[i-1][j] + 1, D[i][j-1] + 1);     dist[p] = D[U][H]
+ *   The alignment is the backtrace from (U, H) to (0, 0) that takes the FIRST rule that applies: (1) i > 0, j > 0 and
+ *   D[i][j] == D[i-1][j-1] + (r[i-1] != h[j-1]): diagonal, a hit when the tokens are equal, a substitution otherwise; (2) i > 0 and
+ *   D[i][j] == D[i-1][j] + 1: a deletion (a reference token without a hypothesis token); (3) an insertion.
+ *   counts int32 [P, 4] = (S, D, I, hits); ops uint8 [P, Hmax + Umax]: the ops in forward order, 1 hit, 2 substitution, 3 deletion,
+ *     4 insertion, 0 from ops_len[p] to the row's end; ops_len int32 [P].  counts may be null together with ops and ops_len (distance
+ *     only: no scratch is touched); ops and ops_len may be null on their own, and are null or not together.
+ *   scratch: the recorded moves, 2 bits per cell, needed only with counts: scratch_bytes >= cfm_edit_distance_scratch_bytes(P, Hmax, Umax)
+ *     = P * Umax * 64 * (1, 2 or 4 bytes for Hmax <= 256, <= 512, <= 1024), 0 when Hmax or Umax is 0; 4-byte aligned.
+ *   One launch, one wavefront per pair, no host synchronisation; integer arithmetic, so the result is exact. */
+typedef struct {
+    const int32_t* hyp;
+    const int32_t* hyp_lens;
+    const int32_t* ref;
+    const int32_t* ref_lens;
+    const int32_t* ref_index;
+    int32_t* dist;
+    int32_t* counts;
+    uint8_t* ops;
+    int32_t* ops_len;
+    void* scratch;
+    int64_t scratch_bytes;
+    int32_t P, R, Hmax, Umax;
+} cfm_edit_distance_desc;
+int64_t cfm_edit_distance_scratch_bytes(int32_t P, int32_t Hmax, int32_t Umax);
+int cfm_edit_distance(const cfm_edit_distance_desc* d, cfm_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * RNN-T beam search on the transducer head: n-best lists with scores, B utterances at once, 1 <= beam <= 15 hypotheses each, everything
  * float32 (csrc/greedy.hip).  The search is alignment-length synchronous and is stated once, in float64, in tests/rnnt_beam_ref.py (the
