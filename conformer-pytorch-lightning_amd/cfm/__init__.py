@@ -257,6 +257,23 @@ class ResampleDesc(ctypes.Structure):
                 [(n, c_p) for n in ("n_new", "final", "tail_in", "tail_out", "counts_in", "counts_out")] + [("tail_cap", c_i32)])
 
 
+RESAMPLE_MAX_BANKS, SPEC_MAX_MASKS = 8, 32
+
+
+class ResampleBank(ctypes.Structure):
+    _fields_ = [(n, c_i32) for n in ("o", "n", "width", "n_live", "taps_at", "first_at", "off_at", "tile_blocks")]
+
+
+class ResampleGroupDesc(ctypes.Structure):
+    _fields_ = ([(n, c_p) for n in ("samples", "lengths", "bank", "taps", "tap_first", "tap_off", "out", "out_lens")] + [("ld", c_i64), ("ld_out", c_i64)] +
+                [(n, c_i32) for n in ("B", "n_cols", "cap", "samples_i16", "G", "n_taps", "n_first", "n_off")] + [("banks", ResampleBank * RESAMPLE_MAX_BANKS)])
+
+
+class SpecAugmentDesc(ctypes.Structure):
+    _fields_ = ([(n, c_p) for n in ("feats", "lengths", "ids", "masks")] + [("item_stride", c_i64), ("row_stride", c_i64)] +
+                [(n, c_i32) for n in ("B", "T_max", "F", "num_t_mask", "num_f_mask", "max_t", "max_f")] + [("seed", ctypes.c_uint32)])
+
+
 class FfnSplitDesc(ctypes.Structure):
     _fields_ = [("x", c_p), ("psum", c_p), ("psum_b2", c_p), ("psum_splits", c_i32), ("psum_alpha", c_f), ("ln1_g", c_p), ("ln1_b", c_p), ("ln2_g", c_p),
                 ("ln2_b", c_p), ("rows_out", c_p), ("rows2_out", c_p), ("ln_g", c_p), ("ln_b", c_p), ("w1", c_p), ("b1", c_p), ("N1", c_i32), ("act", c_i32),
@@ -289,6 +306,7 @@ for _c_name, _cls in dict(
         cfm_layer_train_scratch=LayerTrainScratch, cfm_layer_train_grads=LayerTrainGrads, cfm_layer_weights=LayerWeights, cfm_ctc_group=CtcGroup,
         cfm_rnnt_desc=RnntDesc, cfm_lattice=Lattice, cfm_rnnt_packed_desc=RnntPackedDesc, cfm_ln_bwd_desc=LnBwdDesc, cfm_lstm_desc=LstmDesc, cfm_greedy_desc=GreedyDesc,
         cfm_greedy_chunk_desc=GreedyChunkDesc, cfm_ctc_greedy_desc=CtcGreedyDesc, cfm_ctc_beam_desc=CtcBeamDesc, cfm_ctc_align_desc=CtcAlignDesc, cfm_edit_distance_desc=EditDistanceDesc, cfm_rnnt_beam_desc=RnntBeamDesc, cfm_rnnt_beam_stream_desc=RnntBeamStreamDesc, cfm_fbank_desc=FbankDesc, cfm_resample_desc=ResampleDesc,
+        cfm_resample_bank=ResampleBank, cfm_resample_group_desc=ResampleGroupDesc, cfm_spec_augment_desc=SpecAugmentDesc,
         cfm_ffn_split_desc=FfnSplitDesc, cfm_layer_scratch=LayerScratch, cfm_layer_io=LayerIO).items():
     _cls._c_name_ = _c_name
 PROTOTYPES = (
@@ -393,6 +411,8 @@ PROTOTYPES = (
     ("cfm_resample", c_int, P(ResampleDesc), c_p),
     ("cfm_resample_stream", c_int, P(ResampleDesc), c_p),
     ("cfm_resample_tile_blocks", c_i32, c_i32, c_i32, c_i32),
+    ("cfm_resample_group", c_int, P(ResampleGroupDesc), c_p),
+    ("cfm_spec_augment", c_int, P(SpecAugmentDesc), c_p),
 )
 
 _lib = None

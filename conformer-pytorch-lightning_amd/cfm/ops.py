@@ -6,7 +6,7 @@ import torch
 
 import cfm as _c
 
-__all__ = ["lstm_forward", "lstm_backward", "fbank", "fbank_stream", "fbank_stream_ragged", "resample", "resample_stream", "stream_prep", "stream_advance", "dwconv_causal_bn_silu", "conv_cache_update", "dropout_rows", "dropout_mask", "set_deterministic", "gemm_tn", "gemm_tn_group", "layernorm_bwd", "glu_bwd", "dwconv_bn_train", "dwconv_bn_train_bwd", "dwconv_bn_train_groups", "dwconv_bn_train_bwd_groups", "col2im_relu_bwd", "conv1_wgrad", "attention_bwd", "attention_group", "attention_bwd_group",
+__all__ = ["lstm_forward", "lstm_backward", "fbank", "fbank_stream", "fbank_stream_ragged", "resample", "resample_stream", "resample_group", "spec_augment", "stream_prep", "stream_advance", "dwconv_causal_bn_silu", "conv_cache_update", "dropout_rows", "dropout_mask", "set_deterministic", "gemm_tn", "gemm_tn_group", "layernorm_bwd", "glu_bwd", "dwconv_bn_train", "dwconv_bn_train_bwd", "dwconv_bn_train_groups", "dwconv_bn_train_bwd_groups", "col2im_relu_bwd", "conv1_wgrad", "attention_bwd", "attention_group", "attention_bwd_group",
            "ctc_nll_train_groups", "ctc_grad", "rnnt_nll", "rnnt_grad", "joint_act_bwd", "rnnt_nll_packed", "joint_act_packed", "joint_act_packed_bwd", "ffn_split", "adam_step", "adam_clip_step", "sumsq", "scratch_stats",
            "gemm", "ffn_fused", "ffn_fused_supported", "rowchain", "rowchain_supported", "rowchain_pair_supported", "layernorm", "attention", "kv_cache_pack", "dwconv_bn_silu", "conv1_relu", "conv1_relu_mma_supported", "conv12_relu", "conv12_supported", "ctc_nll", "ctc_topk", "ctc_greedy", "ctc_greedy_state", "ctc_prefix_beam", "ctc_align", "edit_distance", "joint_act", "valid_mask", "chunk_mask",
            "attn_mask_combine", "cast", "add_rows", "scratch", "prof_enable", "prof_reset", "prof_table", "as_u8_mask"]
@@ -1595,6 +1595,64 @@ def resample_stream(samples, n_new, final, state_in, state_out, tables, geometry
         raise ValueError("cfm.resample_stream: state in and out must not alias")
     d.n_new, d.final, d.tail_in, d.tail_out, d.counts_in, d.counts_out, d.tail_cap = _c.ptr(n_new), _c.ptr(final), _c.ptr(ti), _c.ptr(to), _c.ptr(ci), _c.ptr(co), ti.shape[1]
     _c.call("cfm_resample_stream", ctypes.byref(d))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# training augmentation (include/cfm.h cfm_resample_group, csrc/resample.hip; cfm_spec_augment, csrc/augment.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+def resample_group(samples, lengths, bank, tables, banks, out, out_lens):
+    """One rate pair per item: samples (B, N) int16 | f32, lengths / bank int32 [B] on the device (bank[b] indexes `banks`), tables = the G banks'
+    concatenated (taps f32, first int32, offset int32) on the device or None when every bank is the identity, banks = the host geometry rows
+    (o, n, width, n_live, taps_at, first_at, off_at, tile_blocks) (packing.resample_group_tables) -> out f32 (B, cap), out_lens int32 [B]."""
+    taps, first, off = tables if tables is not None else (None, None, None)
+    _c.require_hip(samples, lengths, bank, out, out_lens, taps, first, off)
+    _dense("resample_group", lengths=lengths, bank=bank, taps=taps, tap_first=first, tap_off=off, out_lens=out_lens)
+    if samples.dim() != 2 or (samples.shape[1] > 0 and samples.stride(1) != 1) or samples.dtype not in (torch.int16, torch.float32):
+        raise ValueError("cfm.resample_group: samples must be (B, N) int16 or float32 with unit inner stride, got %s %s" % (tuple(samples.shape), samples.dtype))
+    B, N = samples.shape
+    if out.dim() != 2 or out.dtype != torch.float32 or out.shape[0] != B or (out.shape[1] > 0 and out.stride(1) != 1):
+        raise ValueError("cfm.resample_group: out must be f32 (%d, cap) with unit inner stride, got %s %s" % (B, tuple(out.shape), out.dtype))
+    for name, t in (("lengths", lengths), ("bank", bank), ("out_lens", out_lens)):
+        if t.dtype != torch.int32 or t.numel() != B:
+            raise ValueError("cfm.resample_group: %s is int32 [%d], got %s %s" % (name, B, t.dtype, tuple(t.shape)))
+    if not 1 <= len(banks) <= _c.RESAMPLE_MAX_BANKS:
+        raise ValueError("cfm.resample_group: %d banks, 1 .. %d" % (len(banks), _c.RESAMPLE_MAX_BANKS))
+    if tables is not None and (taps.dtype != torch.float32 or first.dtype != torch.int32 or off.dtype != torch.int32):
+        raise ValueError("cfm.resample_group: tables are (taps f32, first int32, offset int32)")
+    if tables is None and any(row[0] != row[1] for row in banks):
+        raise ValueError("cfm.resample_group: a bank that converts needs the tables")
+    ld = lambda t: t.stride(0) if B > 1 and t.shape[1] > 0 else max(t.stride(0), t.shape[1])      # noqa: E731
+    d = _c.ResampleGroupDesc()
+    d.samples, d.ld, d.n_cols, d.samples_i16 = _c.ptr(samples) if N else None, ld(samples), N, int(samples.dtype == torch.int16)
+    d.lengths, d.bank, d.G = _c.ptr(lengths), _c.ptr(bank), len(banks)
+    if tables is not None:
+        d.taps, d.tap_first, d.tap_off, d.n_taps, d.n_first, d.n_off = _c.ptr(taps), _c.ptr(first), _c.ptr(off), taps.numel(), first.numel(), off.numel()
+    d.out, d.ld_out, d.cap, d.out_lens, d.B = _c.ptr(out) if out.shape[1] else None, ld(out), out.shape[1], _c.ptr(out_lens), B
+    for g, row in enumerate(banks):
+        d.banks[g] = _c.ResampleBank(*(int(v) for v in row))
+    _c.call("cfm_resample_group", ctypes.byref(d))
+
+
+def spec_augment(feats, lengths, ids, seed, num_t_mask, num_f_mask, max_t, max_f, masks=None):
+    """SpecAugment in place: feats f32 (B, T_max, F) with unit inner stride (any row and item stride), lengths int32 [B], ids int32 [B] read as uint32 or
+    None (ids[b] = b), masks int32 (B, num_t_mask + num_f_mask, 2) or None receives (start, end).  include/cfm.h cfm_spec_augment states the draws."""
+    _c.require_hip(feats, lengths, ids, masks)
+    _dense("spec_augment", lengths=lengths, ids=ids, masks=masks)
+    if feats.dim() != 3 or feats.dtype != torch.float32 or (feats.shape[2] > 1 and feats.stride(2) != 1):
+        raise ValueError("cfm.spec_augment: feats must be f32 (B, T_max, F) with unit inner stride, got %s %s strides %s" % (tuple(feats.shape), feats.dtype, feats.stride()))
+    B, T, F = feats.shape
+    nm = int(num_t_mask) + int(num_f_mask)
+    if lengths.dtype != torch.int32 or lengths.numel() != B or (ids is not None and (ids.dtype != torch.int32 or ids.numel() != B)):
+        raise ValueError("cfm.spec_augment: lengths and ids are int32 [%d]" % B)
+    if masks is not None and (masks.dtype != torch.int32 or tuple(masks.shape) != (B, nm, 2)):
+        raise ValueError("cfm.spec_augment: masks is int32 (%d, %d, 2), got %s %s" % (B, nm, masks.dtype, tuple(masks.shape)))
+    d = _c.SpecAugmentDesc()
+    d.feats, d.lengths, d.ids, d.masks = _c.ptr(feats) if T and F else None, _c.ptr(lengths), _c.ptr(ids), _c.ptr(masks)
+    d.row_stride = feats.stride(1) if T > 1 else max(feats.stride(1), F)
+    d.item_stride = feats.stride(0) if B > 1 and T > 0 else max(feats.stride(0), T * d.row_stride)
+    d.B, d.T_max, d.F, d.num_t_mask, d.num_f_mask, d.max_t, d.max_f, d.seed = B, T, F, int(num_t_mask), int(num_f_mask), int(max_t), int(max_f), int(seed) & 0xFFFFFFFF
+    _c.call("cfm_spec_augment", ctypes.byref(d))
+    return feats
 
 
 def _lstm_desc(who, x, weights, H, drop):

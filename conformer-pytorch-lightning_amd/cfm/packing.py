@@ -636,6 +636,47 @@ def resample_tables(orig_freq, new_freq):
     return torch.cat(taps).contiguous(), torch.tensor(first, dtype=torch.int32), torch.tensor(offset, dtype=torch.int32)
 
 
+RESAMPLE_MAX_BANKS = 8                   # cfm_resample_group: rate pairs in one launch (CFM_RESAMPLE_MAX_BANKS)
+
+
+def speed_rates(speed, sample_rate=16000):
+    """The rate pair torchaudio.functional.speed resamples between for this factor: (int(speed * sample_rate), sample_rate)."""
+    if not speed > 0:
+        raise ValueError("speed perturbation: a factor > 0, got %r" % (speed,))
+    return int(speed * int(sample_rate)), int(sample_rate)
+
+
+def resample_group_tables(pairs, tile_blocks):
+    """The banks of cfm_resample_group for the rate pairs [(orig, new), ...]: resample_tables of each pair that converts, end to end ->
+    ((taps f32, first int32, offset int32) on the host, or None when no pair converts,
+     one row (o, n, width, n_live, taps_at, first_at, off_at, tile_blocks) per pair).  A pair with equal rates is the identity bank (o = n = 1, no table).
+    tile_blocks(o, n, width) is cfm_resample_tile_blocks; ValueError when it returns 0 (the bank and a tile's input span exceed the kernel's LDS), beyond
+    RESAMPLE_MAX_BANKS pairs, and whatever resample_tables raises."""
+    pairs = list(pairs)
+    if not 1 <= len(pairs) <= RESAMPLE_MAX_BANKS:
+        raise ValueError("resample_group_tables: %d rate pairs; one launch takes 1 .. RESAMPLE_MAX_BANKS = %d" % (len(pairs), RESAMPLE_MAX_BANKS))
+    taps, first, offset, rows = [], [], [], []
+    n_taps = n_first = n_off = 0
+    for orig, new in pairs:
+        o, n, _, width = resample_geometry(orig, new)
+        if o == n:
+            rows.append((o, n, width, 0, 0, 0, 0, 0))
+            continue
+        t, f, off = resample_tables(orig, new)
+        tb = int(tile_blocks(o, n, width))
+        if tb <= 0:
+            raise ValueError("resample_group_tables: %d -> %d Hz reads %d samples per output block of %d with %d taps on either side: the bank "
+                             "(RESAMPLE_MAX_TABLE_BYTES = %d) and one tile's input span do not fit the kernel's LDS" % (orig, new, o, n, width, RESAMPLE_MAX_TABLE_BYTES))
+        rows.append((o, n, width, t.numel(), n_taps, n_first, n_off, tb))
+        taps.append(t)
+        first.append(f)
+        offset.append(off)
+        n_taps, n_first, n_off = n_taps + t.numel(), n_first + f.numel(), n_off + off.numel()
+    if not taps:
+        return None, rows
+    return (torch.cat(taps).contiguous(), torch.cat(first).contiguous(), torch.cat(offset).contiguous()), rows
+
+
 def unpack_resample_tables(taps, first, offset, n_taps):
     """Dense (n, n_taps) f32 view of resample_tables' result (tests, documentation)."""
     dense = torch.zeros((first.numel(), n_taps), dtype=torch.float32)

@@ -148,7 +148,122 @@ int resample_launch(const cfm_resample_desc* d, int streaming, cfm_stream_t stre
     return cfm_launch_status(who);
 }
 
+// ---------------------------------------------------------------------------------------------
+// cfm_resample_group: the offline kernel with one rate pair per item -- speed perturbation of a batch that mixes speeds in one launch.  Item b uses
+// bank g = bank[b]; its workgroups load that bank alone into LDS and walk the item in that bank's tiles, so a sample is the same fmaf chain over the
+// same LDS operands as in cfm_resample_kernel at that pair.  The grid is sized from the bank with the most tiles; a workgroup past its own item's
+// tiles leaves at once.  An identity bank (o == n) copies (int16 -> f32 is exact) in tiles of kTileOut samples and needs no table.
+// ---------------------------------------------------------------------------------------------
+int group_tile_out(const cfm_resample_bank& k) {              // output samples per tile of this bank; 0: does not fit
+    return k.o == k.n ? kTileOut : tile_blocks(k.o, k.n, k.width) * k.n;
+}
+
+__global__ __launch_bounds__(kThreads) void cfm_resample_group_kernel(cfm_resample_group_desc d, int tiles) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int g = min(max(d.bank[b], 0), d.G - 1);
+    cfm_resample_bank k = d.banks[0];
+#pragma unroll
+    for (int i = 1; i < CFM_RESAMPLE_MAX_BANKS; ++i)          // a select per bank: the table stays in scalar registers
+        if (i == g) k = d.banks[i];
+    const int o = k.o, n = k.n, w = k.width;
+    const bool same = o == n;
+
+    Seq s;
+    s.i16 = d.samples_i16;
+    s.blk = (const char*)d.samples + (int64_t)b * d.ld * (d.samples_i16 ? 2 : 4);
+    s.head = s.zeros = same ? 0 : w;
+    s.tail = nullptr;
+    s.nn = min(max(d.lengths[b], 0), d.n_cols);
+    int64_t emit = same ? s.nn : ((int64_t)s.nn * n + o - 1) / o;
+    if (emit > d.cap) emit = d.cap;
+
+    if ((int)blockIdx.x == tiles) {                          // the row's bookkeeping block
+        if (tid == 0) d.out_lens[b] = (int)emit;
+        return;
+    }
+    const int tb = same ? 0 : k.tile_blocks;
+    const int tile_out = same ? kTileOut : tb * n;
+    const int64_t col0 = (int64_t)blockIdx.x * tile_out;     // the tile's first output sample
+    if (col0 >= d.cap) return;                               // this bank has fewer tiles than the grid (block-uniform)
+    const int cols = tile_out < d.cap - col0 ? tile_out : (int)(d.cap - col0);
+    float* out = d.out + (int64_t)b * d.ld_out + col0;
+    if (col0 >= emit) {                                      // nothing but padding here (block-uniform: no barrier is skipped by a part)
+        for (int p = tid; p < cols; p += kThreads) out[p] = 0.f;
+        return;
+    }
+    if (same) {
+        for (int p = tid; p < cols; p += kThreads) out[p] = s.at(col0 + p);      // zeros at and past the item's samples
+        return;
+    }
+
+    const int K = 2 * w + o, span = tb * o + K;
+    float* taps = lds;                                       // [n_live]
+    int* first = (int*)(lds + k.n_live);                     // [n]
+    int* off = first + n;                                    // [n + 1]
+    float* x = (float*)(off + n + 1);                        // [span]
+    for (int i = tid; i < k.n_live; i += kThreads) taps[i] = d.taps[k.taps_at + i];
+    for (int i = tid; i < n; i += kThreads) first[i] = d.tap_first[k.first_at + i];
+    for (int i = tid; i <= n; i += kThreads) off[i] = d.tap_off[k.off_at + i];
+    const int64_t v0 = (int64_t)blockIdx.x * tb * o;
+    for (int i = tid; i < span; i += kThreads) x[i] = s.at(v0 + i);
+    __syncthreads();
+
+    const int live = emit - col0 < cols ? (int)(emit - col0) : cols;
+    for (int p = tid; p < cols; p += kThreads) {
+        float acc = 0.f;
+        if (p < live) {
+            const int q = p / n, j = p - q * n;
+            const int a = off[j], len = off[j + 1] - a;
+            const float* xs = x + q * o + first[j];          // first[j] + len <= K: inside the span
+            for (int i = 0; i < len; ++i) acc = fmaf(taps[a + i], xs[i], acc);
+        }
+        out[p] = acc;
+    }
+}
+
 }  // namespace
+
+extern "C" int cfm_resample_group(const cfm_resample_group_desc* d, cfm_stream_t stream) {
+    const char* who = "cfm_resample_group";
+    CFM_CHECK_ARG(d && d->lengths && d->bank && d->out_lens, "%s: null pointer", who);
+    CFM_CHECK_ARG(d->B > 0 && d->B <= 65535 && d->cap >= 0 && d->cap < (1 << 30) && (d->out || d->cap == 0) && d->ld_out >= d->cap, "%s: B %d, %d output columns (ld %lld)", who,
+                  d->B, d->cap, (long long)d->ld_out);
+    CFM_CHECK_ARG(d->n_cols >= 0 && d->n_cols < (1 << 30) && (d->samples || d->n_cols == 0) && d->ld >= d->n_cols, "%s: %d columns (ld %lld)", who, d->n_cols, (long long)d->ld);
+    CFM_CHECK_ARG(d->G >= 1 && d->G <= CFM_RESAMPLE_MAX_BANKS, "%s: %d banks, 1 .. %d", who, d->G, CFM_RESAMPLE_MAX_BANKS);
+    size_t lds = 0;
+    int tiles = 0, kmax = 1;                                 // kmax: the longest window, for the profile's operation count
+    for (int g = 0; g < d->G; ++g) {
+        const cfm_resample_bank& k = d->banks[g];
+        CFM_CHECK_ARG(k.o >= 1 && k.n >= 1 && k.n <= kMaxPhases, "%s: bank %d: %d -> %d (reduced rates): at most %d phases", who, g, k.o, k.n, kMaxPhases);
+        const int tile_out = group_tile_out(k);
+        if (k.o != k.n) {
+            CFM_CHECK_ARG(d->taps && d->tap_first && d->tap_off, "%s: null table", who);
+            CFM_CHECK_ARG(k.width >= 1 && k.n_live >= k.n && k.n_live <= kMaxLive, "%s: bank %d: width %d, %d live taps for %d phases: at most %d taps", who, g, k.width, k.n_live,
+                          k.n, kMaxLive);
+            CFM_CHECK_ARG(tile_out > 0 && k.tile_blocks == tile_out / k.n, "%s: bank %d: %d -> %d, width %d: tile_blocks %d, cfm_resample_tile_blocks gives %d (0: the bank and one tile's "
+                          "input span exceed %d bytes of LDS)", who, g, k.o, k.n, k.width, k.tile_blocks, tile_out / k.n, kMaxLds);
+            CFM_CHECK_ARG(k.taps_at >= 0 && k.first_at >= 0 && k.off_at >= 0 && (int64_t)k.taps_at + k.n_live <= d->n_taps && (int64_t)k.first_at + k.n <= d->n_first &&
+                              (int64_t)k.off_at + k.n + 1 <= d->n_off,
+                          "%s: bank %d lies outside the tables (%d taps, %d first, %d offsets)", who, g, d->n_taps, d->n_first, d->n_off);
+            const size_t need = 4 * ((size_t)k.n_live + 2 * k.n + 1 + (size_t)k.tile_blocks * k.o + 2 * k.width + k.o);
+            if (need > lds) lds = need;
+            if (2 * k.width + k.o > kmax) kmax = 2 * k.width + k.o;
+        }
+        const int t = (int)((d->cap + tile_out - 1) / tile_out);
+        if (t > tiles) tiles = t;
+    }
+    static bool attr_set = false;                           // > 64 KB of dynamic LDS needs the attribute once per process
+    if (!attr_set) {
+        if (hipFuncSetAttribute((const void*)cfm_resample_group_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds) != hipSuccess)
+            return cfm_fail(CFM_ERR_LAUNCH, "%s: cannot raise the dynamic LDS limit", who);
+        attr_set = true;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    CfmProfScope prof("resample_group", s, 2.0 * d->B * d->cap * kmax, (double)d->B * ((double)d->cap * (d->samples_i16 ? 2 : 4) + (double)d->cap * 4));
+    CFM_LAUNCH(cfm_resample_group_kernel, dim3((unsigned)tiles + 1, (unsigned)d->B), dim3(kThreads), lds, s, *d, tiles);
+    return cfm_launch_status(who);
+}
 
 extern "C" int cfm_resample(const cfm_resample_desc* d, cfm_stream_t stream) { return resample_launch(d, 0, stream, "cfm_resample"); }
 extern "C" int cfm_resample_stream(const cfm_resample_desc* d, cfm_stream_t stream) { return resample_launch(d, 1, stream, "cfm_resample_stream"); }

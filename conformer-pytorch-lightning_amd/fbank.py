@@ -46,15 +46,17 @@ class KaldiFbank:
             t = self._dev[device] = tuple(x.to(device) for x in self._host)
         return t
 
-    def forward(self, waveforms, lengths):
+    def forward(self, waveforms, lengths, seed=None):
         """waveforms (B, N) int16 | float32 on the int16 scale, lengths (B,) samples per item ->
-        (feats (B, max_frames, num_mel_bins) f32 with zero rows past each item's frames, feats_length int32 (B,))."""
+        (feats (B, max_frames, num_mel_bins) f32 with zero rows past each item's frames, feats_length int32 (B,)).
+        seed: this call's dither seed instead of the object's (training draws new noise every step: augment.TrainFrontend)."""
         cfm.require_hip(waveforms, lengths)
         B, N = waveforms.shape
         rows = max(self.num_frames(N), 1)
         feats = torch.empty((B, rows, self.num_mel_bins), dtype=torch.float32, device=waveforms.device)
         feats_length = torch.empty((B,), dtype=torch.int32, device=waveforms.device)
-        cfm.fbank(waveforms, lengths.to(torch.int32), self.tables(waveforms.device), feats, feats_length, self.win, self.shift, self.padded, self.dither, self.seed)
+        cfm.fbank(waveforms, lengths.to(torch.int32), self.tables(waveforms.device), feats, feats_length, self.win, self.shift, self.padded, self.dither,
+                  self.seed if seed is None else seed)
         return feats[:, :self.num_frames(N)], feats_length
 
     __call__ = forward

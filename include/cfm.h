@@ -1448,6 +1448,66 @@ int cfm_resample_stream(const cfm_resample_desc* d, cfm_stream_t stream);
 /* Input blocks (o samples in, n out) per workgroup tile for this reduced rate pair; 0 when the pair does not fit in LDS. */
 int32_t cfm_resample_tile_blocks(int32_t o, int32_t n, int32_t width);
 
+/* ------------------------------------------------------------------------------------------------
+ * Training augmentation on the device: the two stages of the reference's recipe that sit between the waveform and the encoder
+ * (exp/data_config.json speed_perturb / spec_aug; src/dataset.py:135-138 and :160-167).
+ *
+ * cfm_resample_group (csrc/resample.hip): cfm_resample with ONE RATE PAIR PER ITEM, one launch over a batch that mixes up to
+ *   CFM_RESAMPLE_MAX_BANKS pairs.  Speed perturbation by a factor s at rate R is torchaudio.functional.speed: resample from int(s R) to R
+ *   with the filter above -- at 16 kHz, 0.9 is o = 9, n = 10 and 1.1 is o = 11, n = 10.  (The reference calls sox's `speed` + `rate`,
+ *   another filter; the definition here is the specification.)
+ *   bank int32 [B] selects the item's bank (clamped to [0, G)); banks[g] is its geometry: the reduced pair o, n, `width`, n_live, where
+ *   its part of each concatenated table starts (taps[taps_at ..+ n_live), tap_first[first_at ..+ n), tap_off[off_at ..+ n + 1), offsets
+ *   relative to taps_at), and tile_blocks = cfm_resample_tile_blocks(o, n, width) > 0.  n_taps, n_first, n_off are the tables' lengths.
+ *   A bank with o == n is the IDENTITY: the item is copied (int16 -> f32 exactly), its other fields are not read, and the tables may be
+ *   null when every bank is one.
+ *   Contract: out_lens[b] <- ceil(n_b len_b / o_b) (len clamped to n_cols, the result to cap); every column of out [B, cap] is written
+ *   exactly once, those at or beyond out_lens[b] as +0.0f; nothing is read at or past an item's own len_b samples.  An output sample is
+ *   cfm_resample's f32 fmaf chain (SUMMATION ORDER above): item b equals cfm_resample on that item alone at that pair bit for bit. */
+#define CFM_RESAMPLE_MAX_BANKS 8
+typedef struct {
+    int32_t o, n, width, n_live, taps_at, first_at, off_at, tile_blocks;
+} cfm_resample_bank;
+typedef struct {
+    const void* samples;             /* [B, ld] int16 (samples_i16 != 0) or f32 */
+    const int32_t *lengths, *bank;   /* int32 [B] each */
+    const float* taps;
+    const int32_t *tap_first, *tap_off;
+    float* out;                      /* f32 [B, ld_out] */
+    int32_t* out_lens;
+    int64_t ld, ld_out;
+    int32_t B, n_cols, cap, samples_i16, G, n_taps, n_first, n_off;
+    cfm_resample_bank banks[CFM_RESAMPLE_MAX_BANKS];
+} cfm_resample_group_desc;
+int cfm_resample_group(const cfm_resample_group_desc* d, cfm_stream_t stream);
+
+/* cfm_spec_augment (csrc/augment.hip): SpecAugment in place, processor.spec_aug (src/processor.py:151-172) for a ragged batch in one
+ *   launch.  feats f32 [B, T_max, F], element (b, t, f) at feats[b item_stride + t row_stride + f]; T = lengths[b] clamped to
+ *   [0, T_max]; ids uint32 [B] name the items (null: ids[b] = b).  num_t_mask + num_f_mask <= CFM_SPEC_MAX_MASKS; max_t, max_f >= 1.
+ *   DRAWS (part of the contract).  r(b, k) = cfm_hash32(cfm_hash32(seed, ids[b]), k) with
+ *       cfm_hash32(s, i): h = (i * 0x9E3779B1) ^ s;  h ^= h >> 16;  h *= 0x85EBCA6B;  h ^= h >> 13;  h *= 0xC2B2AE35;  h ^= h >> 16   (uint32)
+ *     and U[0, N - 1] drawn from r is (uint64(r) * N) >> 32 (multiply-high: a value's probability is off 1 / N by at most 2^-32, a
+ *     relative bias of at most N / 2^32).  Mask m = 0 .. num_t_mask + num_f_mask - 1, the time masks first, uses k = 2 m for its start
+ *     and k = 2 m + 1 for its length:
+ *       time mask i   (m = i):               start = U[0, T - 1], len = 1 + U[0, max_t - 1], end = min(T, start + len): rows [start, end) <- 0.0f
+ *       freq mask i   (m = num_t_mask + i):  start = U[0, F - 1], len = 1 + U[0, max_f - 1], end = min(F, start + len): columns [start, end)
+ *                                            of rows [0, T) <- 0.0f
+ *     T == 0 (or F == 0): the item has no masks (the reference would raise); its rows of `masks` are (0, 0).
+ *   A step of training enters through the seed: seed + 0x9E3779B1 * step mod 2^32, the dropout sites' convention.
+ *   The kernel only STORES +0.0f to masked elements: it never loads from feats and touches neither rows at or past T nor unmasked
+ *   elements, so its traffic is the masked area.  masks int32 [B, num_t_mask + num_f_mask, 2] = (start, end), optional. */
+#define CFM_SPEC_MAX_MASKS 32
+typedef struct {
+    float* feats;
+    const int32_t* lengths;
+    const uint32_t* ids;
+    int32_t* masks;
+    int64_t item_stride, row_stride;
+    int32_t B, T_max, F, num_t_mask, num_f_mask, max_t, max_f;
+    uint32_t seed;
+} cfm_spec_augment_desc;
+int cfm_spec_augment(const cfm_spec_augment_desc* d, cfm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
