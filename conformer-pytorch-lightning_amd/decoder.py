@@ -21,6 +21,7 @@ import torch
 import torch.nn as nn
 
 import cfm
+import token_log
 from cfm import packing
 
 
@@ -174,9 +175,8 @@ class CTCGreedyStream:
     """Best-path CTC decoding of `streams` utterances chunk by chunk -- `CTCDecoder.greedy_search` as a streaming step, with the contract of
     greedy.ChunkGreedySearch's decode / hyps / reset.  All state lives on the device: per stream the last frame's class (`prev`: a repeat that
     straddles two chunks collapses), the frames seen so far, the hypothesis buffer, its frames and log-probabilities, and the counts.  A decode
-    is three launches (projection, cfm_ctc_topk, cfm_ctc_greedy) and one host read of the counts; a chunk of C frames adds at most C symbols
-    per stream, so the buffer is grown BEFORE a chunk that could overflow it (as ChunkGreedySearch._grow) and the kernel's overflow flag stays
-    an error."""
+    is three launches (projection, cfm_ctc_topk, cfm_ctc_greedy) and one host read of the counts; a chunk of C frames adds at most C symbols per
+    stream, so the buffers are grown BEFORE a chunk that could overflow them (token_log, as ChunkGreedySearch) and the overflow flag stays an error."""
 
     def __init__(self, ctc, streams, blank=0, max_tokens=None):
         self.ctc, self.B, self.blank = ctc, int(streams), int(blank)
@@ -184,16 +184,7 @@ class CTCGreedyStream:
             raise ValueError("CTCGreedyStream: streams is positive")
         self.dev = ctc.ctc_lo.weight.device
         self.S = cfm.ctc_greedy_state(self.B, max(1, int(max_tokens) if max_tokens is not None else 256), self.dev) if self.dev.type == "cuda" else None
-        self._host_count = [0] * self.B
-        self._host_hyps = [[] for _ in range(self.B)]
-
-    def _grow(self, need):
-        S = self.S
-        old = S["hyps"].shape[1]
-        for k in ("hyps", "frames", "token_logp"):
-            t = torch.zeros((self.B, max(2 * old, need)), dtype=S[k].dtype, device=self.dev)
-            t[:, :old] = S[k]
-            S[k] = t
+        self._log = token_log.TokenLog(self.B)
 
     def reset(self, streams=None):
         """New utterances on the given streams (all by default): no previous class, frame 0, hypotheses emptied."""
@@ -203,13 +194,11 @@ class CTCGreedyStream:
         self.S["prev"][idx] = -1
         for k in ("frame_base", "count", "hyps", "frames", "token_logp"):
             self.S[k][idx] = 0
-        for b in (range(self.B) if streams is None else list(streams)):
-            self._host_count[b] = 0
-            self._host_hyps[b] = []
+        self._log.reset(streams)
 
     def hyps(self):
         """Everything emitted per stream since its last reset."""
-        return [list(h) for h in self._host_hyps]
+        return self._log.hyps()
 
     @torch.no_grad()
     def decode(self, enc_chunk, lens=None):
@@ -226,21 +215,11 @@ class CTCGreedyStream:
             lens = torch.full((B,), C, dtype=torch.int32, device=self.dev)
         elif not isinstance(lens, torch.Tensor) and len(lens) != B:
             raise ValueError("CTCGreedyStream.decode: %d lens for %d streams" % (len(lens), B))
-        need = max(self._host_count) + C
-        if need > self.S["hyps"].shape[1]:
-            self._grow(need)
+        token_log.grow(self.S, ("hyps", "frames", "token_logp"), self._log.most() + C)
         idx, logp, _, lens, V = self.ctc._topk(enc_chunk, lens, 1, "greedy_search")
         cfm.ctc_greedy(idx, logp, lens, V, blank=self.blank, state=self.S)
         rep = torch.cat([self.S["count"], self.S["overflow"].to(torch.int64)]).tolist()
         counts, overflow = rep[:B], rep[B]
         if overflow:
             raise RuntimeError("CTCGreedyStream: a stream emitted more symbols than the hypothesis buffer holds")
-        lo, hi = min(self._host_count), max(counts)
-        new = [[] for _ in range(B)]
-        if hi > lo:
-            rows = self.S["hyps"][:, lo:hi].cpu()
-            for b in range(B):
-                new[b] = rows[b, self._host_count[b] - lo:counts[b] - lo].tolist()
-                self._host_hyps[b].extend(new[b])
-        self._host_count = counts
-        return new
+        return self._log.take(self.S["hyps"], counts)

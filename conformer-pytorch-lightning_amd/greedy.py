@@ -23,9 +23,9 @@ of a decision are further apart than f32 rounding (DESIGN.md's margin rule) -- t
 tokens produced by running the reference's predictor / joint modules, and with a float64 restatement of the step (tests/greedy_ref.py).
 
 `BatchedGreedySearch` decides one frame per step, `ChunkGreedySearch` (the streaming recogniser's decoder) all remaining frames of a chunk;
-what they share -- weights key, f32 packs, limits, descriptor weights, LSTM step (`_Head`), graph capture and the replay loop -- is here once.
-`BeamSearch` is the RNN-T beam search on the same packs, capture and replay loop: n-best lists with scores, device only;
-`StreamingBeamSearch` carries its beam across encoder chunks, as `ChunkGreedySearch` carries the greedy hypothesis.
+`BeamSearch` is the RNN-T beam search on the same packs (n-best lists with scores, device only), `StreamingBeamSearch` carries its beam across
+chunks as `ChunkGreedySearch` carries the greedy hypothesis.  Shared, once: `_Head` (weights key, f32 packs, padded vocabulary, limits, LSTM step),
+the base `_Search` (eval guard, "weights or buffers changed -> drop descriptor(s) and graph", capture then replay), the beam helpers, token_log.py.
 """
 import ctypes
 
@@ -33,6 +33,7 @@ import torch
 import torch.nn.functional as F
 
 import cfm
+import token_log
 from cfm import packing
 
 
@@ -47,6 +48,9 @@ class _Head:
     def weights_key(self):
         """Identity of the current weights: packing.weights_key over the predictor's and the joint's parameters."""
         return packing.weights_key(list(self.predictor.parameters()) + list(self.joint.parameters()))
+
+    def padded_vocab(self):
+        return (self.joint.ffn_out.out_features + 15) // 16 * 16                        # whole 16-class tiles: the out_w / out_b packs' rows, every per-class buffer's width
 
     def fused_limits(self, B, dev, chunk=None):
         """None when the fused step takes B streams on dev, else what it needs; chunk: the lookahead step's frames (it also applies enc_ffn)."""
@@ -74,8 +78,7 @@ class _Head:
                 b = getattr(pr.rnn, "bias_ih_l%d" % l).detach().float() + getattr(pr.rnn, "bias_hh_l%d" % l).detach().float()
                 W["lstm_w"].append(w[perm].contiguous())
                 W["lstm_b"].append(b[perm].contiguous())
-            V = jn.ffn_out.out_features
-            Vp = (V + 15) // 16 * 16
+            V, Vp = jn.ffn_out.out_features, self.padded_vocab()
             ow = torch.zeros((Vp, jn.ffn_out.in_features), device=dev)
             ow[:V] = jn.ffn_out.weight.detach().float()
             ob = torch.full((Vp,), float("-inf"), device=dev)
@@ -143,18 +146,51 @@ def replay_until_done(graph, run, done, limit):
     raise RuntimeError("greedy search did not finish within its step bound")
 
 
-class BatchedGreedySearch:
+class _Search:
+    """The host bookkeeping of the four searches.  Descriptor(s) and graph hold addresses of packs and state buffers: whoever replaces either
+    calls _drop().  A subclass has _run_steps() (the steps of one replay) and keeps its descriptor in _desc, or one per step parity in _descs."""
+
+    def __init__(self, predictor, joint, blank, steps_per_replay, use_graph, even_steps=False):
+        self.predictor, self.joint, self._head = predictor, joint, _Head(predictor, joint)
+        self.blank, self.use_graph, self._key_w, self._enc_keep = int(blank), bool(use_graph), None, None
+        self.steps_per_replay = int(steps_per_replay) + (int(steps_per_replay) & 1 if even_steps else 0)       # even: the beam searches' step parity
+        self._drop()
+
+    def _require_eval(self, who):
+        if self.predictor.training or self.joint.training:
+            raise RuntimeError("%s is an eval-mode operation (the predictor's dropout would be live)" % who)
+
+    def _drop(self):
+        self._graph = self._desc = self._descs = None
+
+    def _sync_weights(self):
+        """New weights (_Head.weights_key): descriptor(s) and graph go; the packs are rebuilt by their own key."""
+        wkey = self._head.weights_key()
+        if self._key_w != wkey:
+            self._key_w = wkey
+            self._drop()
+
+    def _replay(self, S, snap, done, limit):
+        """_run_steps captured in a graph when one is wanted and missing (snap: what the steps change in S), then replay_until_done."""
+        if self.use_graph and self._graph is None and S["token"].is_cuda:
+            self._graph = capture_graph(self._run_steps, S, snap, S["token"].device)
+        return replay_until_done(self._graph, self._run_steps, done, limit)
+
+    def _f32_chunk(self, enc_chunk):
+        """enc_chunk as contiguous float32 -- itself when it is --, kept alive while a descriptor holds its address."""
+        self._enc_keep = enc_chunk if (enc_chunk.dtype == torch.float32 and enc_chunk.is_contiguous()) else enc_chunk.float().contiguous()
+        return self._enc_keep
+
+
+class BatchedGreedySearch(_Search):
 
     def __init__(self, predictor, joint, blank=0, n_steps=64, steps_per_replay=32, use_graph=True, fused=None):
         """fused: one step = six HIP launches on f32 weights (csrc/greedy.hip, include/cfm.h cfm_greedy_step) instead of ~45 torch operations;
         default: on an MI355X when the sizes fit (B <= 64 streams, dimensions multiples of 16), the torch-operation form otherwise (and on CPU)."""
-        self.predictor, self.joint = predictor, joint
-        self.blank, self.n_steps, self.steps_per_replay, self.use_graph = int(blank), int(n_steps), int(steps_per_replay), bool(use_graph)
-        self.fused = fused
-        self._head = _Head(predictor, joint)
-        self._S = self._graph = self._desc = self._key = self._key_w = None
+        super().__init__(predictor, joint, blank, steps_per_replay, use_graph)
+        self.n_steps, self.fused, self._S, self._key = int(n_steps), fused, None, None
 
-    # -- fused step -----------------------------------------------------------------------------------------------------------------------
+    # -- fused step (_fused_ok / _fused_weights: what tests/test_greedy_step_gpu.py builds a step from) -----------------------------------------
     def _fused_ok(self, B, dev):
         return self._head.fused_limits(B, dev) is None
 
@@ -214,15 +250,13 @@ class BatchedGreedySearch:
                     all_done=torch.zeros((), dtype=torch.bool, device=dev))
 
     def _prepare(self, enc_out, enc_lens, token, state):
-        """The state to start from, in buffers for (B, T) on enc_out's device.  Descriptor and graph hold addresses: a change of the weights
-        (_Head.weights_key) drops packs, descriptor and graph, a change of the state buffers descriptor and graph."""
+        """The state to start from, in buffers for (B, T) on enc_out's device; new weights or new buffers drop descriptor and graph."""
         (B, T, _), dev = enc_out.shape, enc_out.device
-        wkey = self._head.weights_key()
-        if self._key_w != wkey:
-            self._graph, self._desc, self._key_w = None, None, wkey
+        self._sync_weights()
         key = (B, T, str(dev))
         if self._key != key:
-            self._S, self._graph, self._desc, self._key = self._state(B, T, dev), None, None, key
+            self._S, self._key = self._state(B, T, dev), key
+            self._drop()
         why_not = self._head.fused_limits(B, dev)
         if self.fused and why_not:
             raise RuntimeError(why_not)
@@ -261,20 +295,17 @@ class BatchedGreedySearch:
         """enc_out (B, T', E) float32 encoder output, enc_lens (B,) valid frames per stream.  token (B,) / state (h, c): the predictor's input
         and LSTM state to start from (a continued stream, model.py:186-192); default: blank and zeros.  Returns (list of B token lists,
         (token, (h, c)) to continue with)."""
-        if self.predictor.training or self.joint.training:
-            raise RuntimeError("greedy search is an eval-mode operation (the predictor's dropout would be live)")
+        self._require_eval("greedy search")
         self._prepare(enc_out, enc_lens, token, state)
-        (B, T, _), dev, S = enc_out.shape, enc_out.device, self._S
-        if self.use_graph and dev.type == "cuda" and self._graph is None:
-            self._graph = capture_graph(self._run_steps, S, self._SNAP + (("done8", "n_done") if self._fused else ()), dev)
+        (B, T, _), S = enc_out.shape, self._S
         limit = (T * (self.n_steps + 1)) // self.steps_per_replay + 2                   # every step emits or advances: at most T (n_steps + 1) of them
-        replay_until_done(self._graph, self._run_steps, lambda: bool(S["all_done"]), limit)
+        self._replay(S, self._SNAP + (("done8", "n_done") if self._fused else ()), lambda: bool(S["all_done"]), limit)
         counts = S["count"].tolist()
         hyps = S["hyps"].cpu()
         return [hyps[b, :counts[b]].tolist() for b in range(B)], (S["token"].clone(), (S["h"].clone(), S["c"].clone()))
 
 
-class ChunkGreedySearch:
+class ChunkGreedySearch(_Search):
     """The decoder of a batched streaming recogniser: `streams` utterances decoded chunk by chunk (`chunk` encoder frames per call), all
     state -- the predictor's input token and LSTM state, the hypothesis buffer that ACCUMULATES across chunks and its counts -- resident on
     the device.  It is the reference's `greedy_search_streaming_app` (src/model.py:178-199; carry=True) / `greedy_search_streaming_eval`
@@ -294,26 +325,19 @@ class ChunkGreedySearch:
     (64 streams, chunk 32, 4 LSTM layers, dimensions multiples of 16) raise.  On the CPU the same step runs as torch operations (`_step`)."""
 
     def __init__(self, predictor, joint, streams, chunk, blank=0, n_steps=64, steps_per_replay=4, use_graph=True, carry=True, fused=None, max_tokens=None):
-        self.predictor, self.joint = predictor, joint
-        self.B, self.chunk = int(streams), int(chunk)
-        self.blank, self.n_steps, self.steps_per_replay, self.use_graph, self.carry = int(blank), int(n_steps), int(steps_per_replay), bool(use_graph), bool(carry)
+        super().__init__(predictor, joint, blank, steps_per_replay, use_graph)
+        self.B, self.chunk, self.n_steps, self.carry = int(streams), int(chunk), int(n_steps), bool(carry)
         if self.B < 1 or self.chunk < 1 or self.n_steps < 1 or self.steps_per_replay < 1:
             raise ValueError("ChunkGreedySearch: streams, chunk, n_steps and steps_per_replay are positive")
-        self._head = _Head(predictor, joint)
         self.dev = next(predictor.parameters()).device
         self.fused = (self.dev.type == "cuda") if fused is None else bool(fused)
-        if self.fused and not self._fused_ok():
+        if self.fused and self._head.fused_limits(self.B, self.dev, self.chunk):
             raise RuntimeError(self._head.fused_limits(self.B, self.dev, self.chunk))
         self.S = self._state(max(1, int(max_tokens) if max_tokens is not None else 2 * self.chunk * self.n_steps))     # decode needs count + chunk * n_steps
-        self._host_count = [0] * self.B                                                 # exact after every decode; + chunk * n_steps bounds the next one
-        self._host_hyps = [[] for _ in range(self.B)]
-        self._graph = self._desc = self._key_w = self._enc_keep = None
+        self._log = token_log.TokenLog(self.B)
         self.steps = self.replays = self.total_steps = self.total_replays = 0
 
     # -- state -----------------------------------------------------------------------------------------------------------------------------
-    def _fused_ok(self):
-        return self._head.fused_limits(self.B, self.dev, self.chunk) is None
-
     def _state(self, cap):
         pr, jn, B, C, dev = self.predictor, self.joint, self.B, self.chunk, self.dev
         L, H, J = pr.num_layers, pr.hidden_size, jn.enc_ffn.out_features
@@ -323,7 +347,7 @@ class ChunkGreedySearch:
                  token=torch.full((B,), self.blank, dtype=torch.int64, device=dev), h=torch.zeros((L, B, H), device=dev), c=torch.zeros((L, B, H), device=dev),
                  count=z64(B), frame_count=z64(B), hyps=z64(B, cap), steps=z32(1), overflow=z32(1), n_done=z32(1))
         if self.fused:
-            Vp = (jn.ffn_out.out_features + 15) // 16 * 16
+            Vp = self._head.padded_vocab()
             S.update(h_new=torch.zeros((L, B, H), device=dev), c_new=torch.zeros((L, B, H), device=dev), pred=torch.zeros((B, pr.projection.out_features), device=dev),
                      pp=torch.zeros((B, J), device=dev), act=torch.zeros((B * C, J), device=dev), pmax=torch.zeros((B * C, Vp // 16), device=dev),
                      pidx=z32(B * C, Vp // 16), rows=z32(B * C), row_off=z32(B), row_cnt=z32(B), n_rows=z32(1), done8=torch.zeros((B,), dtype=torch.uint8, device=dev))
@@ -341,20 +365,14 @@ class ChunkGreedySearch:
         return d
 
     def _prepare(self):
-        """A change of the weights (_Head.weights_key) drops packs, descriptor and graph; whoever replaces a state buffer (_grow) drops
-        descriptor and graph."""
-        wkey = self._head.weights_key()
-        if self._key_w != wkey:
-            self._graph, self._desc, self._key_w = None, None, wkey
+        """The descriptor for the current weights and buffers (_sync_weights; _grow drops it too)."""
+        self._sync_weights()
         if self.fused and self._desc is None:
             self._desc = self._fused_desc(self.S, self._head.packs(self.dev, enc_ffn=True))
 
     def _grow(self, need):
-        S = self.S
-        hyps = torch.zeros((self.B, max(2 * S["hyps"].shape[1], need)), dtype=torch.int64, device=self.dev)
-        hyps[:, :S["hyps"].shape[1]] = S["hyps"]
-        S["hyps"] = hyps
-        self._graph = self._desc = None                                                 # both hold the old buffer's address
+        if token_log.grow(self.S, ("hyps",), need):
+            self._drop()                                                                # descriptor and graph hold the old buffer's address
 
     # -- one lookahead step as torch operations (the CPU form; csrc/greedy.hip's cfm_greedy_chunk_step restated) ---------------------------------
     def _step(self, S):
@@ -416,13 +434,11 @@ class ChunkGreedySearch:
             S[k][idx] = 0
         S["h"][:, idx] = 0
         S["c"][:, idx] = 0
-        for b in (range(self.B) if streams is None else list(streams)):
-            self._host_count[b] = 0
-            self._host_hyps[b] = []
+        self._log.reset(streams)
 
     def hyps(self):
         """Everything emitted per stream since its last reset."""
-        return [list(h) for h in self._host_hyps]
+        return self._log.hyps()
 
     def state(self):
         """(token (B,), (h, c) (L, B, H)): the predictor input and LSTM state the next chunk starts from (copies)."""
@@ -438,16 +454,12 @@ class ChunkGreedySearch:
     def decode(self, enc_chunk, lens=None):
         """enc_chunk (B, chunk, E) float32 encoder output of one chunk; lens (B,): how many of its frames belong to each stream (default: all;
         0: the stream is idle and nothing about it changes).  Returns a list of B lists: the tokens this chunk added."""
-        if self.predictor.training or self.joint.training:
-            raise RuntimeError("greedy search is an eval-mode operation (the predictor's dropout would be live)")
+        self._require_eval("greedy search")
         B, C, S, dev = self.B, self.chunk, self.S, self.dev
         if tuple(enc_chunk.shape[:2]) != (B, C) or enc_chunk.device != dev:
             raise ValueError("ChunkGreedySearch.decode wants (%d, %d, E) on %s, got %s on %s" % (B, C, dev, tuple(enc_chunk.shape), enc_chunk.device))
+        self._grow(self._log.most() + C * self.n_steps)                                 # the most any stream can hold after this chunk
         self._prepare()
-        need = max(self._host_count) + C * self.n_steps                                 # the most any stream can hold after this chunk
-        if need > S["hyps"].shape[1]:
-            self._grow(need)
-            self._prepare()
         maybe_live = True
         if lens is None:
             S["lens"].fill_(C)
@@ -460,37 +472,26 @@ class ChunkGreedySearch:
             maybe_live = any(host)
             S["lens"].copy_(torch.tensor(host, dtype=torch.int64))
         if self.fused:
-            self._enc_keep = enc_chunk if (enc_chunk.dtype == torch.float32 and enc_chunk.is_contiguous()) else enc_chunk.float().contiguous()
-            self._desc.enc = self._enc_keep.data_ptr()
+            self._desc.enc = self._f32_chunk(enc_chunk).data_ptr()
             cfm.check(cfm.lib().cfm_greedy_chunk_begin(ctypes.byref(self._desc), cfm.stream()), "cfm_greedy_chunk_begin")
         else:
             self._begin_eager(enc_chunk)
-        if self.use_graph and dev.type == "cuda" and self._graph is None:
-            self._graph = capture_graph(self._run_steps, S, self._SNAP + (("done8",) if self.fused else ()), dev)
         limit = (C * (self.n_steps + 1)) // self.steps_per_replay + 2                   # a lookahead step emits or finishes a stream: fewer than the single-frame bound
         done = (lambda: int(S["n_done"]) >= B) if self.fused else (lambda: bool((S["t"] >= S["lens"]).all()))
-        self.replays = replay_until_done(self._graph, self._run_steps, done, limit) if maybe_live else 0
+        self.replays = self._replay(S, self._SNAP + (("done8",) if self.fused else ()), done, limit) if maybe_live else 0
         rep = torch.cat([S["count"], S["overflow"].to(torch.int64), S["steps"].to(torch.int64)]).tolist()
         counts, overflow, self.steps = rep[:B], rep[B], rep[B + 1]
         if overflow:
             raise RuntimeError("ChunkGreedySearch: a stream emitted more symbols than the hypothesis buffer holds")
         self.total_steps += self.steps
         self.total_replays += self.replays
-        lo, hi = min(self._host_count), max(counts)
-        new = [[] for _ in range(B)]
-        if hi > lo:
-            rows = S["hyps"][:, lo:hi].cpu()
-            for b in range(B):
-                new[b] = rows[b, self._host_count[b] - lo:counts[b] - lo].tolist()
-                self._host_hyps[b].extend(new[b])
-        self._host_count = counts
-        return new
+        return self._log.take(S["hyps"], counts)
 
 
-def _beam_state(pr, jn, K, B, T, max_len, dev):
+def _beam_state(head, K, B, T, max_len, dev):
     """The device buffers of cfm.RnntBeamDesc for B utterances of at most T frames, K hypotheses each (both beam searches)."""
-    L, H, R = pr.num_layers, pr.hidden_size, B * K
-    Vp = (jn.ffn_out.out_features + 15) // 16 * 16
+    pr, jn = head.predictor, head.joint
+    L, H, R, Vp = pr.num_layers, pr.hidden_size, B * K, head.padded_vocab()
     n_nodes = int(cfm.lib().cfm_rnnt_beam_nodes(B, T, max_len, K))
     z = lambda dt, *s: torch.zeros(s, dtype=dt, device=dev)
     f32, i32, i64 = torch.float32, torch.int32, torch.int64
@@ -502,7 +503,29 @@ def _beam_state(pr, jn, K, B, T, max_len, dev):
                 nbest_tokens=z(i64, B, K, max_len), nbest_len=z(i32, B, K), nbest_score=z(f32, B, K), all_done=z(torch.bool))
 
 
-class BeamSearch:
+# what a beam step changes (capture_graph); the scratch a step writes before it reads it is not among them
+_BEAM_SNAP = ("token", "t", "hash", "fc", "len", "node", "parent", "ext", "live", "score", "h", "c", "nodes", "fin_score", "fin_node", "fin_len", "n_fin", "step", "done",
+              "n_done", "nbest_tokens", "nbest_len", "nbest_score")
+
+
+def _fill_beam_desc(d, search, S, W, B, T, len_by_frames, parity):
+    """The cfm.RnntBeamDesc d filled for the steps of one parity (the h / c buffer a step reads alternates); S's tensors go by field name."""
+    search._head.fill_weights(d, W)
+    for k, _ in cfm.RnntBeamDesc._fields_:
+        if k in S:
+            setattr(d, k, S[k].data_ptr())
+    d.B, d.T, d.V, d.beam, d.blank, d.max_symbols = B, T, search.joint.ffn_out.out_features, search.beam, search.blank, search.max_symbols
+    d.n_nodes, d.max_len, d.len_by_frames, d.parity = S["nodes"].shape[0], S["nbest_tokens"].shape[2], len_by_frames, parity
+    return d
+
+
+def _nbest_lists(nbest_tokens, nbest_len, nbest_score, rows):
+    """The device's n-best buffers read back: per utterance in rows its [(tokens, score)], best first, the unused (-inf) entries left out."""
+    lens, scores, toks = nbest_len.tolist(), nbest_score.tolist(), nbest_tokens.cpu()
+    return [[(toks[b, j, :lens[b][j]].tolist(), scores[b][j]) for j in range(len(scores[b])) if scores[b][j] != float("-inf")] for b in rows]
+
+
+class BeamSearch(_Search):
     """RNN-T beam search on the device: per utterance the `beam` best finished hypotheses with their scores (log of the summed probability
     of the alignments found, no length normalisation).  The search is alignment-length synchronous and is specified in float64 in
     tests/rnnt_beam_ref.py; include/cfm.h (cfm_rnnt_beam_step) restates it.  max_symbols: the most symbols emitted on one frame (the role
@@ -514,41 +537,23 @@ class BeamSearch:
     Device only: there is no torch-operation form; CPU tensors and sizes outside the kernels' limits raise."""
 
     def __init__(self, predictor, joint, beam, blank=0, max_symbols=64, max_len=None, steps_per_replay=16, use_graph=True):
-        self.predictor, self.joint = predictor, joint
-        self.beam, self.blank, self.max_symbols = int(beam), int(blank), int(max_symbols)
-        self.max_len = None if max_len is None else int(max_len)
-        self.steps_per_replay, self.use_graph = int(steps_per_replay) + (int(steps_per_replay) & 1), bool(use_graph)
+        super().__init__(predictor, joint, blank, steps_per_replay, use_graph, even_steps=True)
+        self.beam, self.max_symbols, self.max_len = int(beam), int(max_symbols), None if max_len is None else int(max_len)
         if not 1 <= self.beam <= 15:
             raise ValueError("BeamSearch: beam = %d outside 1..15 (the top-k launch returns 16 classes, one of which may be the blank)" % self.beam)
         if self.max_symbols < 1 or self.steps_per_replay < 1 or (self.max_len is not None and self.max_len < 0):
             raise ValueError("BeamSearch: max_symbols and steps_per_replay are positive, max_len is not negative")
         if not 0 <= self.blank < joint.ffn_out.out_features or self.beam + 1 > joint.ffn_out.out_features:
             raise ValueError("BeamSearch: blank inside the vocabulary, beam + 1 <= its size")
-        self._head = _Head(predictor, joint)
-        self._S = self._graph = self._descs = self._key = self._key_w = None
+        self._S = self._key = None
         self.steps = self.replays = 0
 
     def _state(self, B, T, dev):
-        return _beam_state(self.predictor, self.joint, self.beam, B, T, T if self.max_len is None else self.max_len, dev)
-
-    # what a step changes (capture_graph); the scratch a step writes before it reads it is not among them
-    _SNAP = ("token", "t", "hash", "fc", "len", "node", "parent", "ext", "live", "score", "h", "c", "nodes", "fin_score", "fin_node", "fin_len", "n_fin", "step", "done",
-             "n_done", "nbest_tokens", "nbest_len", "nbest_score")
+        return _beam_state(self._head, self.beam, B, T, T if self.max_len is None else self.max_len, dev)
 
     def _make_descs(self, S, W, B, T):
-        """The descriptor of the steps of either parity: the h / c buffer a step reads alternates."""
-        out = []
-        for parity in (0, 1):
-            d = cfm.RnntBeamDesc()
-            self._head.fill_weights(d, W)
-            for k in cfm.RnntBeamDesc._fields_:
-                if k[0] in S:
-                    setattr(d, k[0], S[k[0]].data_ptr())
-            d.n_nodes = S["nodes"].shape[0]
-            d.B, d.T, d.V, d.beam, d.blank, d.max_symbols = B, T, self.joint.ffn_out.out_features, self.beam, self.blank, self.max_symbols
-            d.max_len, d.len_by_frames, d.parity = S["nbest_tokens"].shape[2], int(self.max_len is None), parity
-            out.append(d)
-        return out
+        """The descriptor of the steps of either parity."""
+        return [_fill_beam_desc(cfm.RnntBeamDesc(), self, S, W, B, T, int(self.max_len is None), parity) for parity in (0, 1)]
 
     def _run_steps(self):
         lib, S = cfm.lib(), self._S
@@ -560,8 +565,7 @@ class BeamSearch:
     def search(self, enc_out, enc_lens):
         """enc_out (B, T', E) float32 encoder output on the device, enc_lens (B,) valid frames per utterance.  Returns per utterance a list
         of (tokens, score), best first, at most `beam`; an utterance without frames gives [([], 0.0)]."""
-        if self.predictor.training or self.joint.training:
-            raise RuntimeError("beam search is an eval-mode operation (the predictor's dropout would be live)")
+        self._require_eval("beam search")
         (B, T, _), dev, K = enc_out.shape, enc_out.device, self.beam
         if dev.type != "cuda":
             raise RuntimeError("BeamSearch runs on the device only: enc_out is on %s (there is no fallback)" % dev)
@@ -570,29 +574,25 @@ class BeamSearch:
         why_not = self._head.fused_limits(B * K, dev)
         if why_not:
             raise RuntimeError(why_not)
-        wkey = self._head.weights_key()
-        if self._key_w != wkey:                                                         # new weights: packs (by their own key), descriptors and graph
-            self._graph, self._descs, self._key_w = None, None, wkey
+        self._sync_weights()
         key = (B, T, K, str(dev))
         if self._key != key:                                                            # new buffers: descriptors and graph hold their addresses
-            self._S, self._graph, self._descs, self._key = self._state(B, T, dev), None, None, key
+            self._S, self._key = self._state(B, T, dev), key
+            self._drop()
         S = self._S
         if self._descs is None:
             self._descs = self._make_descs(S, self._head.packs(dev), B, T)
         S["enc_proj"].copy_(self.joint.enc_ffn(enc_out.float()))
         S["lens"].copy_(torch.as_tensor(enc_lens, device=dev).to(torch.int64).clamp(0, T))
         cfm.check(cfm.lib().cfm_rnnt_beam_begin(ctypes.byref(self._descs[0]), cfm.stream()), "cfm_rnnt_beam_begin")
-        if self.use_graph and self._graph is None:
-            self._graph = capture_graph(self._run_steps, S, self._SNAP, dev)
-        max_len = S["nbest_tokens"].shape[2]
-        limit = (T + max_len + 1) // self.steps_per_replay + 2                           # a step adds one to every live t + len: at most T + max_len + 1 of them
-        self.replays = replay_until_done(self._graph, self._run_steps, lambda: bool(S["all_done"]), limit)
-        lens, scores, toks = S["nbest_len"].tolist(), S["nbest_score"].tolist(), S["nbest_tokens"].cpu()
+        limit = (T + S["nbest_tokens"].shape[2] + 1) // self.steps_per_replay + 2         # a step adds one to every live t + len: at most T + max_len + 1 of them
+        self.replays = self._replay(S, _BEAM_SNAP, lambda: bool(S["all_done"]), limit)
+        out = _nbest_lists(S["nbest_tokens"], S["nbest_len"], S["nbest_score"], range(B))
         self.steps = int(S["step"].max())
-        return [[(toks[b, j, :lens[b][j]].tolist(), scores[b][j]) for j in range(K) if scores[b][j] != float("-inf")] for b in range(B)]
+        return out
 
 
-class StreamingBeamSearch:
+class StreamingBeamSearch(_Search):
     """The RNN-T beam search of `BeamSearch` with the beam carried across encoder chunks: `streams` utterances decoded chunk by chunk, every
     hypothesis, the trie and the projected frames fed so far ((streams, max_frames, J): no ring, a live hypothesis may sit many frames behind
     the newest) resident on the device.  Specified in float64 in tests/rnnt_beam_ref_stream.py; include/cfm.h (cfm_rnnt_beam_stream_*)
@@ -613,18 +613,15 @@ class StreamingBeamSearch:
     stream must find its state at parity 0 of the next decode).  Device only: there is no torch-operation form."""
 
     def __init__(self, predictor, joint, streams, beam, chunk, max_frames, max_len=None, blank=0, max_symbols=64, steps_per_replay=8, use_graph=True):
-        self.predictor, self.joint = predictor, joint
-        self.B, self.beam, self.chunk, self.max_frames = int(streams), int(beam), int(chunk), int(max_frames)
+        super().__init__(predictor, joint, blank, steps_per_replay, use_graph, even_steps=True)
+        self.B, self.beam, self.chunk, self.max_frames, self.max_symbols = int(streams), int(beam), int(chunk), int(max_frames), int(max_symbols)
         self.max_len = self.max_frames if max_len is None else int(max_len)
-        self.blank, self.max_symbols = int(blank), int(max_symbols)
-        self.steps_per_replay, self.use_graph = int(steps_per_replay) + (int(steps_per_replay) & 1), bool(use_graph)
         if not 1 <= self.beam <= 15 or self.B < 1 or self.B * self.beam > 64:
             raise ValueError("StreamingBeamSearch: 1 <= beam <= 15 and streams * beam <= 64 rows (streams=%d beam=%d)" % (self.B, self.beam))
         if self.chunk < 1 or self.max_frames < 1 or self.max_len < 0 or self.max_symbols < 1 or self.steps_per_replay < 1:
             raise ValueError("StreamingBeamSearch: chunk, max_frames, max_symbols and steps_per_replay are positive, max_len is not negative")
         if not 0 <= self.blank < joint.ffn_out.out_features or self.beam + 1 > joint.ffn_out.out_features:
             raise ValueError("StreamingBeamSearch: blank inside the vocabulary, beam + 1 <= its size")
-        self._head = _Head(predictor, joint)
         self.dev = next(predictor.parameters()).device
         if self.dev.type != "cuda":
             raise RuntimeError("StreamingBeamSearch runs on the device only: the predictor is on %s (there is no fallback)" % self.dev)
@@ -634,7 +631,6 @@ class StreamingBeamSearch:
         if why_not:
             raise RuntimeError(why_not)
         self.S = self._state()
-        self._graph = self._descs = self._key_w = self._enc_keep = None
         self.steps = self.replays = self.total_steps = self.total_replays = 0
         self._stable = [[] for _ in range(self.B)]
         self._nbest = [None] * self.B
@@ -643,40 +639,26 @@ class StreamingBeamSearch:
 
     def _state(self):
         B, K, C, dev = self.B, self.beam, self.chunk, self.dev
-        S = _beam_state(self.predictor, self.joint, K, B, self.max_frames, self.max_len, dev)
+        S = _beam_state(self._head, K, B, self.max_frames, self.max_len, dev)
         z = lambda dt, *s: torch.zeros(s, dtype=dt, device=dev)
         S.update(chunk_proj=z(torch.float32, B * C, self.joint.enc_ffn.out_features), avail=z(torch.int32, B), final=z(torch.uint8, B), paused=z(torch.uint8, B),
                  feed_final=z(torch.uint8, B), overflow=z(torch.int32, 1), best_tokens=z(torch.int64, B, max(self.max_len, 1)), best_len=z(torch.int32, B),
                  stable_len=z(torch.int32, B), best_score=z(torch.float32, B), mask=z(torch.uint8, B))
         return S
 
-    # what a step changes (capture_graph): BeamSearch's, and the pause flags
-    _SNAP = ("token", "t", "hash", "fc", "len", "node", "parent", "ext", "live", "score", "h", "c", "nodes", "fin_score", "fin_node", "fin_len", "n_fin", "step", "done",
-             "n_done", "nbest_tokens", "nbest_len", "nbest_score", "paused")
-
     def _make_descs(self, W):
-        out, S = [], self.S
-        for parity in (0, 1):
-            d = cfm.RnntBeamStreamDesc()
-            self._head.fill_weights(d.beam, W)
-            for k in cfm.RnntBeamDesc._fields_:
-                if k[0] in S:
-                    setattr(d.beam, k[0], S[k[0]].data_ptr())
-            d.beam.n_nodes = S["nodes"].shape[0]
-            d.beam.B, d.beam.T, d.beam.V, d.beam.beam, d.beam.blank = self.B, self.max_frames, self.joint.ffn_out.out_features, self.beam, self.blank
-            d.beam.max_symbols, d.beam.max_len, d.beam.len_by_frames, d.beam.parity = self.max_symbols, self.max_len, 0, parity
+        out, S = [cfm.RnntBeamStreamDesc(), cfm.RnntBeamStreamDesc()], self.S
+        for parity, d in enumerate(out):
+            _fill_beam_desc(d.beam, self, S, W, self.B, self.max_frames, 0, parity)
             for k in ("chunk_proj", "avail", "final", "paused", "feed_final", "overflow", "best_tokens", "best_len", "stable_len", "best_score"):
                 setattr(d, k, S[k].data_ptr())
             d.ef_w, d.ef_b = W["ef_w"].data_ptr(), W["ef_b"].data_ptr()
             d.chunk, d.D = self.chunk, self.joint.enc_ffn.in_features
-            out.append(d)
         return out
 
     def _prepare(self):
-        """A change of the weights (_Head.weights_key) drops packs (by their own key), descriptors and graph; the state buffers stay."""
-        wkey = self._head.weights_key()
-        if self._key_w != wkey:
-            self._graph, self._descs, self._key_w = None, None, wkey
+        """The descriptors for the current weights (_sync_weights); the state buffers stay."""
+        self._sync_weights()
         if self._descs is None:
             self._descs = self._make_descs(self._head.packs(self.dev, enc_ffn=True))
 
@@ -701,9 +683,8 @@ class StreamingBeamSearch:
     def decode(self, enc_chunk, lens=None, final=None):
         """enc_chunk (B, chunk, E) float32 encoder output of one chunk on the device; lens (B,): how many of its frames belong to each stream
         (default: all; 0: nothing arrives); final (B,) truthy where the utterance ends with this feed (it may come with 0 frames)."""
-        if self.predictor.training or self.joint.training:
-            raise RuntimeError("beam search is an eval-mode operation (the predictor's dropout would be live)")
-        B, C, K, S, dev = self.B, self.chunk, self.beam, self.S, self.dev
+        self._require_eval("beam search")
+        B, C, S, dev = self.B, self.chunk, self.S, self.dev
         if tuple(enc_chunk.shape[:2]) != (B, C) or enc_chunk.device != dev:
             raise ValueError("StreamingBeamSearch.decode wants (%d, %d, E) on %s, got %s on %s" % (B, C, dev, tuple(enc_chunk.shape), enc_chunk.device))
         self._prepare()
@@ -715,17 +696,13 @@ class StreamingBeamSearch:
                 if v.numel() != B:
                     raise ValueError("StreamingBeamSearch.decode: %d %s for %d streams" % (v.numel(), "lens" if name == "lens" else "final flags", B))
                 S[name].copy_(v.reshape(B).to(torch.int64).clamp(0, hi).to(dt))
-        self._enc_keep = enc_chunk if (enc_chunk.dtype == torch.float32 and enc_chunk.is_contiguous()) else enc_chunk.float().contiguous()
-        for d in self._descs:
-            d.enc = self._enc_keep.data_ptr()
+        self._descs[0].enc = self._descs[1].enc = self._f32_chunk(enc_chunk).data_ptr()
         lib = cfm.lib()
         cfm.check(lib.cfm_rnnt_beam_stream_feed(ctypes.byref(self._descs[0]), cfm.stream()), "cfm_rnnt_beam_stream_feed")
-        if self.use_graph and self._graph is None:
-            self._graph = capture_graph(self._run_steps, S, self._SNAP, dev)
         # a step adds one to every live t + len, which is the steps the stream has taken: at most avail + max_len + 1 of them in all
         most = max(min(a + C, self.max_frames) + self.max_len + 1 - s for a, s in zip(self._avail_host, self._step_host))
         S["all_done"].copy_((S["n_done"] >= B).reshape(()))
-        self.replays = 0 if bool(S["all_done"]) else replay_until_done(self._graph, self._run_steps, lambda: bool(S["all_done"]), most // self.steps_per_replay + 2)
+        self.replays = 0 if bool(S["all_done"]) else self._replay(S, _BEAM_SNAP + ("paused",), lambda: bool(S["all_done"]), most // self.steps_per_replay + 2)
         cfm.check(lib.cfm_rnnt_beam_stream_report(ctypes.byref(self._descs[0]), cfm.stream()), "cfm_rnnt_beam_stream_report")
         ints = torch.cat([S["avail"], S["step"], S["best_len"], S["stable_len"], S["done"].to(torch.int32), S["overflow"]]).tolist()
         avail, step, best_len, stable_len, done = (ints[i * B:(i + 1) * B] for i in range(5))
@@ -742,9 +719,8 @@ class StreamingBeamSearch:
         best_score = S["best_score"].tolist()
         fresh = [b for b in range(B) if done[b] and self._nbest[b] is None]
         if fresh:
-            n_len, n_score, n_tok = S["nbest_len"].tolist(), S["nbest_score"].tolist(), S["nbest_tokens"].cpu()
-            for b in fresh:
-                self._nbest[b] = [(n_tok[b, j, :n_len[b][j]].tolist(), n_score[b][j]) for j in range(K) if n_score[b][j] != float("-inf")]
+            for b, nbest in zip(fresh, _nbest_lists(S["nbest_tokens"], S["nbest_len"], S["nbest_score"], fresh)):
+                self._nbest[b] = nbest
         out = []
         for b in range(B):
             if done[b]:

@@ -231,3 +231,21 @@ def test_wrong_sizes_raise():
             greedy.BeamSearch(pr, jn, 2).search(enc[:2], [4, 4])
     finally:
         pr.eval()
+
+
+def test_weight_change_under_the_captured_graph():
+    """Unchanged weights reuse descriptors and graph; a weight assigned through .data drops both, and the next search is a fresh searcher's.
+    V = 17: the padded vocabulary (32) differs from it."""
+    import greedy
+    pr, jn = R.modules(17, 16, 16, 16, 16, 1, 31)
+    pr, jn = pr.to(DEV), jn.to(DEV)
+    enc = torch.from_numpy(np.random.RandomState(5).standard_normal((2, 3, 16)).astype(np.float32)).to(DEV)
+    bs = greedy.BeamSearch(pr, jn, 2)
+    before = bs.search(enc, [3, 2])
+    graph, descs, key = bs._graph, bs._descs, bs._key_w
+    assert graph is not None and bs._head.padded_vocab() == 32 and bs._descs[0].Vp == 32 and bs._descs[0].V == 17
+    assert bs.search(enc, [3, 2]) == before and bs._graph is graph and bs._descs is descs and bs._key_w == key
+    jn.ffn_out.bias.data = jn.ffn_out.bias.data + torch.linspace(-1.0, 1.0, 17, device=DEV)
+    after = bs.search(enc, [3, 2])
+    assert bs._graph is not None and bs._graph is not graph and bs._descs is not descs and bs._key_w != key
+    assert after == greedy.BeamSearch(pr, jn, 2).search(enc, [3, 2]) and after != before

@@ -391,3 +391,22 @@ def test_streaming_recognizer_with_a_beam():
             plain.nbest()
     finally:
         cfm.set_precision(before)
+
+
+def test_weight_change_under_the_captured_graph():
+    """A weight assigned through .data drops descriptors and graph; the next utterance is captured again and is a fresh searcher's.
+    V = 17: the padded vocabulary (32) differs from it."""
+    import greedy
+    pr, jn = R.modules(17, 16, 16, 16, 16, 1, 33)
+    pr, jn = pr.to(DEV), jn.to(DEV)
+    enc, lens = torch.from_numpy(np.random.RandomState(6).standard_normal((2, 4, 16)).astype(np.float32)), [4, 3]
+    make = lambda: greedy.StreamingBeamSearch(pr, jn, 2, 2, 2, 4)                        # streams, beam, chunk, max_frames
+    sb = make()
+    before = _nbest(_feed_all(sb, enc, lens, 2))
+    graph, descs, key = sb._graph, sb._descs, sb._key_w
+    assert graph is not None and sb._head.padded_vocab() == 32 and sb._descs[0].beam.Vp == 32
+    jn.ffn_out.bias.data = jn.ffn_out.bias.data + torch.linspace(-1.0, 1.0, 17, device=DEV)
+    sb.reset()
+    after = _nbest(_feed_all(sb, enc, lens, 2))
+    assert sb._graph is not None and sb._graph is not graph and sb._descs is not descs and sb._key_w != key
+    assert after == _nbest(_feed_all(make(), enc, lens, 2)) and after != before
