@@ -18,6 +18,7 @@ import cfm
 from cfm import packing
 from attention import PositionalEncoding, RelativePositionalEncoding
 from convolution import ConvolutionSubSampling
+import encoder_layer
 from encoder_layer import ConformerEncoderLayer
 from utils import make_attn_mask, make_pad_mask
 
@@ -44,52 +45,45 @@ class ConformerEncoder(nn.Module):
         self.static_chunk_size = static_chunk_size
 
     # ------------------------------------------------------------------------------------------------------------
-    def _run_blocks(self, x, attn_mask, pos_embed, pad_mask, caches, keep_from, pos_shared=False, proj=None, ring=None, conv=None, streaming=False, utt_len=None, stream_len=None):
+    def _run_blocks(self, x, attn_mask, pos_embed, pad_mask, caches, keep_from, pos_shared=False, proj=None, ring=None, conv=None, streaming=False, utt_len=None,
+                    stream_len=None, causal=None):
         """x (B,T',D) f32 -> after_norm(blocks(x)); returns (y, [trimmed per-layer caches] | None).
+        caches: None, empty, (L,H,Tc,2dk) or batched (L,B,H,Tc,2dk); not None = the new caches are returned, rows from keep_from on.
         ring = (kv f32 [L,B,H,ring_T,2dk], offsets int32 [B]), conv = f32 [L,B,K-1,D] | None: per-stream streaming state (StreamingBatch).
-        utt_len int32 [B]: a ragged batch of whole utterances (forward_utterances; include/cfm.h cfm_layer_io.utt_len).
-        stream_len int32 [B]: with ring, the encoder frames of each stream's window (StreamingBatch with frame_lens; cfm_layer_io.stream_len)."""
-        n = len(self.encoders)
+        utt_len, stream_len, causal and streaming (= split_ffn) are encoder_layer.BlockCall's; the routes are picked beside it."""
+        n, D, e0 = len(self.encoders), self.encoder_dim, self.encoders[0]
         if proj is None:
             proj = self._project_positions(pos_embed, x)
-        bufs = [torch.empty_like(x), torch.empty_like(x)]
-        new_caches = [] if caches is not None else None
-        cur, ready = x, False
         prec = cfm.resolve_precision(self)
+        ws = [blk._weights(prec) for blk in self.encoders]
         # after_norm rides in the last block's final chain when that block runs on the row chains (one launch less)
-        fuse_after = (cfm.rowchain_supported(self.encoder_dim, self.encoders[0].hidden_dim, prec) and
-                      self.after_norm.weight.dtype == torch.float32 and self.after_norm.eps == 1e-5)
-        y_after = torch.empty_like(x) if fuse_after else None
-        # consecutive blocks chained: block i's last launch runs block i+1's macaron chain too (batch path on the row chains at the
-        # config-2 width; encoder_layer.CHAIN_BLOCKS)
-        import encoder_layer as _el
-        e0 = self.encoders[0]
-        chain = (_el.CHAIN_BLOCKS and fuse_after and caches is None and conv is None and self.encoder_dim == 256 and
-                 e0.hidden_dim == 2048 and e0.kernel_size == 15 and not getattr(e0.conv_module, "causal", False) and
-                 all(b.chain_ready(prec) for b in self.encoders) and
-                 not (streaming and _el.SPLIT_FFN_FEW_ROWS and _el.split_rows(x.size(0) * x.size(1), self.encoder_dim, e0.hidden_dim)))   # few rows: the split feed-forward instead
-        for i, block in enumerate(self.encoders):
-            nxt = self.encoders[i + 1].norm_ff_macaron if i + 1 < n else None
-            cache_i = None
-            if caches is not None and caches.dim() == 5 and caches.size(0) > 0:
-                cache_i = caches[i]                                   # batched streaming: (L,B,H,Tc,2dk)
-            elif caches is not None and caches.dim() == 4 and caches.size(0) > 0:
-                cache_i = caches[i:i + 1]
-            pp = None if proj is None else (proj[:, i * self.encoder_dim:], proj.stride(0))
-            out, nc = block.fused_forward(cur, attn_mask, pos_embed, pad_mask, cache_i, xn_ready=ready, next_norm=nxt,
-                                          out=bufs[i & 1], want_cache=caches is not None, pos_proj=pp, pos_shared=pos_shared,
-                                          ring=None if ring is None else (ring[0][i], ring[1]), conv_cache=None if conv is None else conv[i],
-                                          chain_next=(self.encoders[i + 1], bufs[(i + 1) & 1]) if chain and i + 1 < n else None,
-                                          macaron_done=chain and i > 0, split_ffn=streaming, utt_len=utt_len, stream_len=stream_len,
-                                          after=(self.after_norm.weight.detach(), self.after_norm.bias.detach(), y_after)
-                                          if fuse_after and i + 1 == n else None)
+        fuse_after = (cfm.rowchain_supported(D, e0.hidden_dim, prec) and self.after_norm.weight.dtype == torch.float32 and self.after_norm.eps == 1e-5)
+        after_w = self.after_norm.weight.detach(), self.after_norm.bias.detach()
+        chain = encoder_layer.chain_blocks(ws, x.size(0) * x.size(1), D, e0.hidden_dim, e0.kernel_size,
+                                           getattr(e0.conv_module, "causal", False) if causal is None else causal,
+                                           caches is not None or conv is not None, fuse_after, streaming)
+        have = caches is not None and caches.dim() in (4, 5) and caches.size(0) > 0
+        call = encoder_layer.BlockCall(x, prec, attn_mask, pos_embed if e0.use_relative else None, pad_mask, [blk.hidden_dim for blk in self.encoders],
+                                       cache_T=caches.size(-2) if have else 0, pos_shared=pos_shared, ring=None if ring is None else (ring[1], ring[0].size(3)),
+                                       utt_len=utt_len, stream_len=stream_len, causal=causal, split_ffn=streaming, chained=chain)
+        bufs = [torch.empty_like(call.x), torch.empty_like(call.x)]
+        y_after = torch.empty_like(call.x) if fuse_after else None
+        new_caches = [] if caches is not None else None
+        cur = call.x
+        for i, (block, w) in enumerate(zip(self.encoders, ws)):
+            last, out = i + 1 == n, bufs[i & 1]
+            nc = call.run(block, w, cur, out, xn_ready=i > 0, next_norm=None if last else self.encoders[i + 1].norm_ff_macaron,
+                          cache=None if not have else caches[i] if caches.dim() == 5 else caches[i:i + 1], want_cache=caches is not None,
+                          pos_proj=None if proj is None else (proj[:, i * D:], proj.stride(0)),
+                          kv_ring=None if ring is None else ring[0][i], conv_cache=None if conv is None else conv[i],
+                          next_w=None if last or not chain else ws[i + 1], next_out=bufs[(i + 1) & 1], macaron_done=chain and i > 0,
+                          after=after_w + (y_after,) if fuse_after and last else None)
             if new_caches is not None:
                 new_caches.append(nc[:, :, keep_from:, :])
-            cur, ready = out, nxt is not None
+            cur = out
         if fuse_after:
             return y_after, new_caches
-        y, _ = cfm.layernorm(cur.view(-1, cur.size(-1)), self.after_norm.weight.detach(), self.after_norm.bias.detach(),
-                             eps=self.after_norm.eps)
+        y, _ = cfm.layernorm(cur.view(-1, D), *after_w, eps=self.after_norm.eps)
         return y.view_as(cur), new_caches
 
     def _cmvn_args(self, inputs):
@@ -465,27 +459,21 @@ class StreamingBatch:
 
     def _step_impl(self):
         enc = self.enc
-        for blk in enc.encoders:
-            blk.conv_module.causal = self.causal
-        try:
-            inputs, cmvn = enc._cmvn_args(self.x)
-            x = enc.embed.embed_frames(inputs, cmvn)
-            cfm.stream_prep(self.offsets, self.chunk, self.need, self.ring_T, self.pe, self.slot_mask, self.pos_rows, self.abs_rows,
-                            frame_lens=self.frame_lens, out_lens=self.out_lens)
-            if self.relative:
-                x, _ = enc.position_encoding(x, 0)
-            else:
-                x, _ = enc.position_encoding(x, 0, rows=self.abs_rows)
-            proj = enc._project_positions(self.pos_rows, x)
-            y, _ = enc._run_blocks(x, self.slot_mask.view(torch.bool), self.pos_rows, None, None, 0, proj=proj, ring=(self.kv, self.offsets), conv=self.conv, streaming=True,
-                                   stream_len=self.out_lens)
-            if self.out_lens is None:
-                cfm.stream_advance(self.offsets, self.chunk)
-            else:
-                cfm.stream_advance(self.offsets, self.chunk, lens=self.out_lens, y=y)     # ... and zeroes the rows past each stream's c_b
-        finally:
-            for blk in enc.encoders:
-                blk.conv_module.causal = False
+        inputs, cmvn = enc._cmvn_args(self.x)
+        x = enc.embed.embed_frames(inputs, cmvn)
+        cfm.stream_prep(self.offsets, self.chunk, self.need, self.ring_T, self.pe, self.slot_mask, self.pos_rows, self.abs_rows,
+                        frame_lens=self.frame_lens, out_lens=self.out_lens)
+        if self.relative:
+            x, _ = enc.position_encoding(x, 0)
+        else:
+            x, _ = enc.position_encoding(x, 0, rows=self.abs_rows)
+        proj = enc._project_positions(self.pos_rows, x)
+        y, _ = enc._run_blocks(x, self.slot_mask.view(torch.bool), self.pos_rows, None, None, 0, proj=proj, ring=(self.kv, self.offsets), conv=self.conv, streaming=True,
+                               stream_len=self.out_lens, causal=self.causal)
+        if self.out_lens is None:
+            cfm.stream_advance(self.offsets, self.chunk)
+        else:
+            cfm.stream_advance(self.offsets, self.chunk, lens=self.out_lens, y=y)     # ... and zeroes the rows past each stream's c_b
         return y
 
     def step(self, frames, frame_lens=None):

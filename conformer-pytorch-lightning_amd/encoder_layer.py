@@ -43,6 +43,126 @@ def split_rows(M, D, FF):
 
 
 CHAIN_BLOCKS = True        # the final chain of block i also runs the macaron chain of block i+1 (one launch and one residual round trip less)
+CHAIN_PACKS = ("ffm_w1f", "ffm_w2n", "ff_w1f", "ff_w2n", "qkv_wf", "out_wf", "pw1_wf", "pw2_wf")   # the fragment-major packs of the row-chain path
+
+
+def chain_blocks(ws, M, D, FF, ktaps, causal, stateful, after_fused, split_ffn):
+    """True when the blocks of a call are chained: block i's last launch runs block i+1's macaron chain too (cfm.h cfm_layer_io.next_w).
+    The batch path on the row chains at the config-2 width: every weight struct of `ws` carries the row-chain packs, after_norm rides in the
+    last block's final chain (after_fused), no attention or conv cache is returned (stateful), the convolution is not causal, and the call
+    does not take the split feed-forward below."""
+    return bool(CHAIN_BLOCKS and after_fused and not stateful and not causal and (D, FF, ktaps) == (256, 2048, 15) and
+                all(getattr(w, f) for w in ws for f in CHAIN_PACKS) and
+                not (split_ffn and SPLIT_FFN_FEW_ROWS and split_rows(M, D, FF)))
+
+
+def psum_splits(M, D, FF, prec, split_ffn, chained):
+    """How many partial slabs [M, D] f32 a block's feed-forwards get (cfm.h cfm_layer_scratch.psum_splits); 0 = none.  A chained block gets
+    none: its macaron chain ran in the previous block's last launch."""
+    if chained:
+        return 0
+    if split_ffn and SPLIT_FFN_FEW_ROWS and split_rows(M, D, FF) and prec.act_dtype != torch.float32:
+        return FF // 256           # few rows, e.g. a streaming step: the feed-forward split over FF (csrc/ffnsplit.hip)
+    if M <= PAIR_MAX_ROWS and cfm.rowchain_pair_supported(D, FF, prec):
+        return 3                   # D = 512, at most 128 row tiles: split over workgroup pairs -- two partial slabs + the parked rows of the final chain
+    return 0
+
+
+class BlockCall:
+    """What the blocks of ONE encoder call share, derived once: shape, precision, the masks and positional rows as the library wants them, the
+    streaming offsets and lengths, the scratch buffers (one lookup per tag; `hid` and `psum` sized for the largest hidden_dim, since a tag names
+    one arena block) and one LayerIO / LayerScratch with those fields filled.  `run` is one block: it ASSIGNS every per-block field on every call
+    (None / 0 where the block has none), so nothing set for block i reaches block i+1; the structs are not copied.
+
+    x (B,T,D) on an MI355X; attn_mask broadcastable to (B,T,cache_T+T), or the (B,1,ring_T) slot mask with ring = (offsets int32 [B], ring_T);
+    pos_embed: the positional rows (None: absolute positions); pad_mask (B,1,T) | None.
+    utt_len int32 [B]: a ragged batch of whole utterances, item b has utt_len[b] frames (cfm.h cfm_layer_io.utt_len); the caller masks the keys.
+    stream_len int32 [B] (with ring): stream b's window has stream_len[b] encoder frames (cfm.h cfm_layer_io.stream_len).
+    causal: the opt-in causal convolution for every block; None = each block's own conv_module.causal.
+    split_ffn: a streaming entry point asks for the split feed-forward; chained: chain_blocks() of this call."""
+
+    def __init__(self, x, prec, attn_mask, pos_embed, pad_mask, hidden_dims, cache_T=0, pos_shared=False, ring=None, utt_len=None,
+                 stream_len=None, causal=None, split_ffn=False, chained=False):
+        cfm.require_hip(x)
+        if x.dtype != torch.float32 or not x.is_contiguous():
+            x = x.float().contiguous()
+        B, T, D = x.shape
+        M, dev, adt = B * T, x.device, prec.act_dtype
+        self.x, self.causal, self.cache_T, self.Tk = x, causal, cache_T, cache_T + T if ring is None else ring[1]
+        pos, R = None, 0
+        if pos_embed is not None:
+            pos = pos_embed.reshape(-1, D)
+            pos = (pos if pos.dtype == torch.float32 else pos.float()).contiguous()
+            R = pos.size(0)
+        m8, (m_sb, m_sq) = _mask_args(attn_mask, B, T, self.Tk)
+        keep = None
+        if pad_mask is not None and pad_mask.dim() >= 3 and pad_mask.size(2) > 0:
+            keep = cfm.as_u8_mask(pad_mask).reshape(-1)
+            if keep.numel() != M:
+                raise RuntimeError("pad mask %s does not match inputs %s" % (tuple(pad_mask.shape), tuple(x.shape)))
+        for name, t in (("utt_len", utt_len), ("stream_len", stream_len), ("ring offsets", ring[0] if ring is not None else None)):
+            if t is not None and (t.dtype != torch.int32 or t.numel() != B or not t.is_contiguous()):
+                raise RuntimeError("%s must be a contiguous int32 tensor of B entries" % name)
+        cfm.require_hip(pos, m8, keep, utt_len, stream_len, ring[0] if ring is not None else None)
+        self._keep = (pos, m8, keep)                   # conversions may have copied: the structs hold their addresses
+        s = self.scratch = cfm.LayerScratch()
+        for tag, numel in (("xn", M * D), ("hid", M * max(hidden_dims)), ("qkv", M * 3 * D), ("pos", max(R, 1) * D), ("ctx", M * D), ("glu", M * D), ("dw", M * D)):
+            setattr(s, tag, cfm.scratch(tag, numel, adt, dev).data_ptr())
+        self.splits = {ff: psum_splits(M, D, ff, prec, split_ffn, chained) for ff in set(hidden_dims)}
+        self.psum = cfm.scratch("psum", max(self.splits.values()) * M * D, torch.float32, dev).data_ptr() if any(self.splits.values()) else None
+        io = self.io = cfm.LayerIO()
+        io.B, io.T, io.D, io.act_dtype, io.w_dtype = B, T, D, prec.act_code, prec.w_code
+        io.attn_mask, io.am_sb, io.am_sq, io.pad_valid = cfm.ptr(m8), m_sb, m_sq, cfm.ptr(keep)
+        io.pos_embed, io.pos_rows, io.pos_shared, io.cache_T = cfm.ptr(pos), R, 1 if pos_shared else 0, cache_T
+        if ring is not None:
+            io.stream_offset, io.ring_T = ring[0].data_ptr(), ring[1]
+        io.utt_len, io.stream_len = cfm.ptr(utt_len), cfm.ptr(stream_len)
+        self.stream = cfm.stream()
+
+    def run(self, block, w, x_in, out, xn_ready=False, next_norm=None, cache=None, want_cache=False, pos_proj=None, kv_ring=None, conv_cache=None,
+            next_w=None, next_out=None, macaron_done=False, after=None):
+        """One block: x_in (B,T,D) f32 -> out = norm_final(block(x_in)), returns the new attention cache or None.  `w`: the block's cached weight struct.
+        cache f32 (B,H,cache_T,2dk) | None; kv_ring f32 [B,H,ring_T,2dk]: the block's streaming ring (cfm.h cfm_layer_io.kv_ring); conv_cache f32
+        [B,K-1,D]: the causal convolution's left context; pos_proj = (view [R, D] of the driver's all-blocks projection, row stride);
+        after = (gain, bias, f32 output [B,T,D]): the encoder's after_norm in the final chain.
+        next_w, next_out: this block's last launch also runs the NEXT block's macaron chain into next_out (cfm.h cfm_layer_io.next_w); the next
+        block is then run with macaron_done=True on that buffer, and `out` does not hold this block's output."""
+        _inference_only(block, "ConformerEncoderLayer")
+        io, s = self.io, self.scratch
+        B, T, D = self.x.shape
+        H, K, Tk = block.num_heads, block.kernel_size, self.Tk
+        io.H, io.FF, io.ktaps = H, block.hidden_dim, K
+        s.psum_splits = self.splits[block.hidden_dim]
+        s.psum = self.psum if s.psum_splits else None
+        if cache is not None:
+            cache = cache.to(device=self.x.device, dtype=torch.float32).contiguous()
+            if tuple(cache.shape) != (B, H, self.cache_T, 2 * (D // H)):
+                raise RuntimeError("attn_cache of shape %s, expected (%d,%d,%d,%d)" % (tuple(cache.shape), B, H, self.cache_T, 2 * (D // H)))
+        if kv_ring is not None and (kv_ring.dtype != torch.float32 or tuple(kv_ring.shape) != (B, H, Tk, 2 * (D // H)) or not kv_ring.is_contiguous()):
+            raise RuntimeError("ring: kv must be contiguous float32 (B,H,ring_T,2dk)")
+        causal = getattr(block.conv_module, "causal", False) if self.causal is None else self.causal
+        if conv_cache is not None:
+            if not causal:
+                raise RuntimeError("a conv cache needs the opt-in causal convolution (causal=True, or conv_module.causal = True)")
+            if conv_cache.dtype != torch.float32 or tuple(conv_cache.shape) != (B, K - 1, D) or not conv_cache.is_contiguous():
+                raise RuntimeError("conv_cache must be contiguous float32 (B, kernel_size-1, D)")
+        if next_w is not None and (next_out.data_ptr() == out.data_ptr() or next_out.shape != out.shape or next_out.dtype != torch.float32):
+            raise RuntimeError("chaining: the next block's output buffer must be a distinct float32 tensor of the same shape")
+        cfm.require_hip(kv_ring, conv_cache)
+        new_cache = None
+        if kv_ring is None and (cache is not None or want_cache):
+            new_cache = torch.empty((B, H, Tk, 2 * (D // H)), dtype=torch.float32, device=self.x.device)
+        io.attn_cache, io.new_cache, io.kv_ring = cfm.ptr(cache), cfm.ptr(new_cache), cfm.ptr(kv_ring)
+        io.causal_conv, io.conv_cache = 1 if causal else 0, cfm.ptr(conv_cache)
+        io.pos_proj, io.pos_proj_ld = (pos_proj[0].data_ptr(), pos_proj[1]) if pos_proj is not None else (None, 0)
+        io.after_g, io.after_b, io.after_out = [t.data_ptr() for t in after] if after is not None else (None, None, None)
+        io.next_w = ctypes.cast(ctypes.pointer(next_w), ctypes.c_void_p) if next_w is not None else None
+        io.next_x_out = cfm.ptr(next_out) if next_w is not None else None
+        io.macaron_done = 1 if macaron_done else 0
+        ng, nb = (next_norm.weight.data_ptr(), next_norm.bias.data_ptr()) if next_norm is not None else (None, None)
+        cfm.check(cfm.lib().cfm_encoder_layer_forward(ctypes.byref(w), ctypes.byref(s), ctypes.byref(io), x_in.data_ptr(), out.data_ptr(),
+                                                      1 if xn_ready else 0, ng, nb, self.stream), "cfm_encoder_layer_forward")
+        return new_cache
 
 
 class ConformerEncoderLayer(nn.Module):
@@ -73,131 +193,6 @@ class ConformerEncoderLayer(nn.Module):
         key = packing.weights_key(plist, prec.name)
         return packing.slot(self, "_fused").get(key, lambda: packing.layer_weight_struct(self, prec))[0]
 
-    def chain_ready(self, prec):
-        """True when this block's weight struct carries every fragment-major pack of the row-chain path (cfm_encoder_layer_forward then
-        takes that path, a precondition for chaining consecutive blocks)."""
-        w = self._weights(prec)
-        return all(getattr(w, f) for f in ("ffm_w1f", "ffm_w2n", "ff_w1f", "ff_w2n", "qkv_wf", "out_wf", "pw1_wf", "pw2_wf"))
-
-    def fused_forward(self, x, attn_mask, pos_embed, pad_mask, attn_cache, xn_ready=False, next_norm=None, out=None,
-                      want_cache=True, pos_proj=None, pos_shared=False, after=None, ring=None, conv_cache=None, chain_next=None,
-                      macaron_done=False, split_ffn=False, utt_len=None, stream_len=None):
-        """x (B,T,D) float32 on an MI355X -> (norm_final(block(x)), new_attn_cache | None).  ``x`` is not modified.
-        ring = (kv_ring f32 [B,H,ring_T,2dk], offsets int32 [B]): per-stream streaming state (include/cfm.h cfm_layer_io.kv_ring);
-        attn_mask is then the (B,1,ring_T) slot mask and pos_embed the B*ring_T positional rows.  conv_cache f32 [B,K-1,D]: the
-        opt-in causal convolution's left context (only with conv_module.causal).
-        chain_next = (next block, its output buffer): this block's last launch also runs the NEXT block's macaron chain (cfm.h
-        cfm_layer_io.next_w); the next block is then called with macaron_done=True and the same output buffer, and THIS call's
-        returned tensor does not hold the block output.  Only ConformerEncoder._run_blocks uses it.
-        utt_len int32 [B]: a ragged batch of whole utterances, item b has utt_len[b] frames (cfm.h cfm_layer_io.utt_len); the caller masks the keys.
-        stream_len int32 [B] (with ring): stream b's window has stream_len[b] encoder frames (cfm.h cfm_layer_io.stream_len)."""
-        _inference_only(self, "ConformerEncoderLayer.fused_forward")
-        cfm.require_hip(x)
-        if x.dtype != torch.float32 or not x.is_contiguous():
-            x = x.float().contiguous()
-        prec = cfm.resolve_precision(self)
-        w = self._weights(prec)
-        B, T, D = x.shape
-        H, FF = self.num_heads, self.hidden_dim
-        dk = D // H
-        dev = x.device
-        M = B * T
-
-        if ring is not None:
-            attn_cache, want_cache = None, False
-        have_cache = attn_cache is not None and attn_cache.dim() == 4 and attn_cache.size(0) > 0
-        cache = attn_cache.to(device=dev, dtype=torch.float32).contiguous() if have_cache else None
-        Tc = cache.size(2) if have_cache else 0
-        Tk = Tc + T if ring is None else ring[0].size(2)
-        if have_cache and tuple(cache.shape) != (B, H, Tc, 2 * dk):
-            raise RuntimeError("attn_cache of shape %s, expected (%d,%d,Tc,%d)" % (tuple(cache.shape), B, H, 2 * dk))
-        new_cache = torch.empty((B, H, Tk, 2 * dk), dtype=torch.float32, device=dev) if (have_cache or want_cache) else None
-
-        pos = None
-        R = 0
-        if self.use_relative:
-            pos = pos_embed.reshape(-1, D)
-            pos = (pos if pos.dtype == torch.float32 else pos.float()).contiguous()
-            cfm.require_hip(pos)
-            R = pos.size(0)
-
-        m8, (m_sb, m_sq) = _mask_args(attn_mask, B, T, Tk)
-        keep = None
-        if pad_mask is not None and pad_mask.dim() >= 3 and pad_mask.size(2) > 0:
-            keep = cfm.as_u8_mask(pad_mask).reshape(-1)
-            if keep.numel() != M:
-                raise RuntimeError("pad mask %s does not match inputs %s" % (tuple(pad_mask.shape), tuple(x.shape)))
-        cfm.require_hip(m8, keep)
-
-        adt = prec.act_dtype
-        s = cfm.LayerScratch()
-        s.xn = cfm.scratch("xn", M * D, adt, dev).data_ptr()
-        s.hid = cfm.scratch("hid", M * FF, adt, dev).data_ptr()
-        s.qkv = cfm.scratch("qkv", M * 3 * D, adt, dev).data_ptr()
-        s.pos = cfm.scratch("pos", max(R, 1) * D, adt, dev).data_ptr()
-        s.ctx = cfm.scratch("ctx", M * D, adt, dev).data_ptr()
-        s.glu = cfm.scratch("glu", M * D, adt, dev).data_ptr()
-        s.dw = cfm.scratch("dw", M * D, adt, dev).data_ptr()
-        if split_ffn and SPLIT_FFN_FEW_ROWS and split_rows(M, D, FF) and adt != torch.float32 and chain_next is None and not macaron_done:
-            # partial slabs of the feed-forward split over FF (cfm.h cfm_layer_scratch.psum, csrc/ffnsplit.hip): few rows, e.g. a streaming step
-            s.psum, s.psum_splits = cfm.scratch("psum", (FF // 256) * M * D, torch.float32, dev).data_ptr(), FF // 256
-        elif M <= PAIR_MAX_ROWS and cfm.rowchain_pair_supported(D, FF, prec) and chain_next is None and not macaron_done:
-            # D = 512, at most 128 row tiles: feed-forwards split over workgroup pairs -- two partial slabs + the parked rows of the final chain
-            s.psum, s.psum_splits = cfm.scratch("psum", 3 * M * D, torch.float32, dev).data_ptr(), 3
-        io = cfm.LayerIO()
-        io.B, io.T, io.D, io.H, io.FF, io.ktaps = B, T, D, H, FF, self.kernel_size
-        io.act_dtype, io.w_dtype = prec.act_code, prec.w_code
-        io.attn_mask, io.am_sb, io.am_sq = cfm.ptr(m8), m_sb, m_sq
-        io.pad_valid = cfm.ptr(keep)
-        io.pos_embed, io.pos_rows = cfm.ptr(pos), R
-        if pos_proj is not None:                       # (tensor view [R, D] of the driver's all-blocks projection, row stride)
-            io.pos_proj, io.pos_proj_ld = pos_proj[0].data_ptr(), pos_proj[1]
-        io.attn_cache, io.cache_T = cfm.ptr(cache), Tc
-        io.pos_shared = 1 if pos_shared else 0
-        if after is not None:                          # (gain, bias, f32 output [B,T,D]): the encoder's after_norm in the final chain
-            io.after_g, io.after_b, io.after_out = after[0].data_ptr(), after[1].data_ptr(), after[2].data_ptr()
-        io.new_cache = cfm.ptr(new_cache)
-        if ring is not None:
-            kv, offs = ring
-            if kv.dtype != torch.float32 or tuple(kv.shape) != (B, H, Tk, 2 * dk) or not kv.is_contiguous() or offs.dtype != torch.int32 or offs.numel() != B:
-                raise RuntimeError("ring: kv must be contiguous float32 (B,H,ring_T,2dk) and offsets int32 (B,)")
-            cfm.require_hip(kv, offs)
-            io.kv_ring, io.stream_offset, io.ring_T = kv.data_ptr(), offs.data_ptr(), Tk
-        if getattr(self.conv_module, "causal", False):
-            io.causal_conv = 1
-            if conv_cache is not None:
-                if conv_cache.dtype != torch.float32 or tuple(conv_cache.shape) != (B, self.kernel_size - 1, D) or not conv_cache.is_contiguous():
-                    raise RuntimeError("conv_cache must be contiguous float32 (B, kernel_size-1, D)")
-                cfm.require_hip(conv_cache)
-                io.conv_cache = conv_cache.data_ptr()
-        elif conv_cache is not None:
-            raise RuntimeError("a conv cache needs the opt-in causal convolution (conv_module.causal = True)")
-        if out is None:
-            out = torch.empty_like(x)
-        if chain_next is not None:
-            nxt_w = chain_next[0]._weights(prec)
-            if chain_next[1].data_ptr() == out.data_ptr() or chain_next[1].shape != out.shape or chain_next[1].dtype != torch.float32:
-                raise RuntimeError("chain_next: the next block's output buffer must be a distinct float32 tensor of the same shape")
-            io.next_w, io.next_x_out = ctypes.cast(ctypes.pointer(nxt_w), ctypes.c_void_p), chain_next[1].data_ptr()
-        io.macaron_done = 1 if macaron_done else 0
-        if utt_len is not None:
-            if utt_len.dtype != torch.int32 or utt_len.numel() != B or not utt_len.is_contiguous():
-                raise RuntimeError("utt_len must be a contiguous int32 tensor of B entries")
-            cfm.require_hip(utt_len)
-            io.utt_len = utt_len.data_ptr()
-        if stream_len is not None:
-            if stream_len.dtype != torch.int32 or stream_len.numel() != B or not stream_len.is_contiguous():
-                raise RuntimeError("stream_len must be a contiguous int32 tensor of B entries")
-            cfm.require_hip(stream_len)
-            io.stream_len = stream_len.data_ptr()
-        ng = nb = None
-        if next_norm is not None:
-            ng, nb = next_norm.weight.data_ptr(), next_norm.bias.data_ptr()
-        cfm.check(cfm.lib().cfm_encoder_layer_forward(ctypes.byref(w), ctypes.byref(s), ctypes.byref(io), x.data_ptr(),
-                                                      out.data_ptr(), 1 if xn_ready else 0, ng, nb, cfm.stream()),
-                  "cfm_encoder_layer_forward")
-        return out, new_cache
-
     def train_forward(self, inputs, inputs_attn_mask, inputs_pad_mask):
         """module.train(): the block as ONE autograd node (cfm/autograd.py EncoderLayerFn) -- BatchNorm batch statistics, every
         parameter's gradient returned from its backward.  encoder_layer.py:49-71 with the shared nn.Dropout(feedforward_dropout)."""
@@ -221,8 +216,12 @@ class ConformerEncoderLayer(nn.Module):
             out = self.train_forward(inputs, inputs_attn_mask, inputs_pad_mask)
             return (out, inputs_attn_mask, torch.zeros((0, 0, 0, 0), dtype=torch.float32, device=inputs.device),
                     torch.zeros((0, 0, 0), dtype=inputs.dtype, device=inputs.device))
-        out, new_attn_cache = self.fused_forward(inputs, inputs_attn_mask, pos_embed, inputs_pad_mask, attn_cache,
-                                                 want_cache=self.return_cache)
+        have_cache = attn_cache is not None and attn_cache.dim() == 4 and attn_cache.size(0) > 0
+        prec = cfm.resolve_precision(self)
+        call = BlockCall(inputs, prec, inputs_attn_mask, pos_embed if self.use_relative else None, inputs_pad_mask, [self.hidden_dim],
+                         cache_T=attn_cache.size(2) if have_cache else 0)
+        out = torch.empty_like(call.x)
+        new_attn_cache = call.run(self, self._weights(prec), call.x, out, cache=attn_cache if have_cache else None, want_cache=self.return_cache)
         if new_attn_cache is None:
             new_attn_cache = torch.zeros((0, 0, 0, 0), dtype=torch.float32, device=inputs.device)
         new_cnn_cache = torch.zeros((0, 0, 0), dtype=inputs.dtype, device=inputs.device)    # convolution.py:39

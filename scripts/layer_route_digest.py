@@ -84,6 +84,61 @@ def chunks(name):
     digest(name, y, m, y1, c1, y2, c2)
 
 
+def ragged_utterances(name, split=False):
+    """forward_utterances: the per-item lengths reach the blocks (cfm_layer_io.utt_len)."""
+    cfm.set_precision("bf16")
+    enc = build(CFG, 11)
+    enc.split_small_batches = split
+    x = torch.from_numpy(synth.fbank(12, 3, 210)).to(DEV)
+    with torch.no_grad():
+        y, out_lens = enc.forward_utterances(x, torch.tensor([210, 131, 9], dtype=torch.int32, device=DEV))
+    digest(name, y, out_lens)
+
+
+def streaming_batch_ragged(name, graph, steps, cfg=CFG):
+    """StreamingBatch with per-stream window lengths (cfm_layer_io.stream_len): every step has a full window, a short one, 7 frames and an idle stream."""
+    cfm.set_precision("bf16")
+    enc = build(cfg, 31)
+    streams, chunk, left = 4, 4, 2
+    sb = encoder.StreamingBatch(enc, streams, chunk, left, graph=graph)
+    window, hop = (chunk - 1) * 4 + 7, 4 * chunk
+    x = torch.from_numpy(synth.fbank(32, streams, window + (steps - 1) * hop)).to(DEV)
+    lens = [window, 11, 7, 0]
+    outs = []
+    for i in range(steps):
+        outs.append(sb.step(x[:, i * hop: i * hop + window].contiguous(), lens[i % 4:] + lens[:i % 4]).clone())
+        outs.append(sb.out_lens.clone())
+    digest(name, *outs, sb.kv, sb.offsets)
+
+
+def chunks_batched(name):
+    """forward_chunk at B = 2 with a growing (L,B,H,Tc,2dk) cache."""
+    cfm.set_precision("bf16")
+    enc = build(CFG, 41)
+    x = torch.from_numpy(synth.fbank(43, 2, 35)).to(DEV)
+    empty = torch.zeros((0, 0, 0, 0), device=DEV)
+    with torch.no_grad():
+        y1, c1, _ = enc.forward_chunk(x[:, :19].contiguous(), 0, -1, empty, empty)
+        y2, c2, _ = enc.forward_chunk(x[:, 16:35].contiguous(), y1.size(1), -1, c1, empty)
+    assert c1.dim() == 5 and c2.size(3) == c1.size(3) + y2.size(1)
+    digest(name, y1, c1, y2, c2)
+
+
+def one_block(name):
+    """ConformerEncoderLayer.forward in eval mode, the way the reference's encoder calls it: without and with a (1,H,Tc,2dk) cache."""
+    cfm.set_precision("bf16")
+    enc = build(CFG, 51)
+    blk, T, Tc = enc.encoders[1], 13, 8
+    x = torch.randn((1, T, 256), generator=torch.Generator().manual_seed(52)).to(DEV)
+    with torch.no_grad():
+        y1, _, c1, _ = blk(x, torch.ones((1, T, T), dtype=torch.bool, device=DEV), enc.embed.position_encoding(offset=0, size=T).to(DEV))
+        cache = c1[:, :, T - Tc:, :].contiguous()
+        y2, _, c2, _ = blk(x, torch.ones((1, T, Tc + T), dtype=torch.bool, device=DEV), enc.embed.position_encoding(offset=T - Tc, size=Tc + T).to(DEV),
+                           attn_cache=cache)
+    assert tuple(c2.shape) == (1, 4, Tc + T, 128)
+    digest(name, y1, c1, y2, c2)
+
+
 def with_setting(obj, attr, value, fn):
     keep = getattr(obj, attr)
     setattr(obj, attr, value)
@@ -116,6 +171,13 @@ def main():
     with_setting(encoder_layer, "SPLIT_FFN_FEW_ROWS", False, lambda: streaming_batch("k-streaming-batch-split-ffn-off"))
     streaming_batch("k-streaming-batch-causal-conv", causal=True)
     chunks("l-forward-chunk")
+    ragged_utterances("m-forward-utterances")
+    ragged_utterances("m-forward-utterances-split-small-batches", split=True)
+    streaming_batch_ragged("n-streaming-batch-frame-lens", graph=False, steps=3)
+    streaming_batch_ragged("n-streaming-batch-frame-lens-graph", graph=True, steps=5)
+    streaming_batch_ragged("n-streaming-batch-frame-lens-absolute-positions", graph=False, steps=3, cfg=CFG | dict(use_relative=False))
+    chunks_batched("o-forward-chunk-batched")
+    one_block("p-one-block-forward")
 
 
 if __name__ == "__main__":

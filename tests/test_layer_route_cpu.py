@@ -154,6 +154,68 @@ def test_null_structs_are_argument_errors(cfm):
     assert cfm.lib().cfm_encoder_layer_route(ctypes.byref(w), ctypes.byref(s), ctypes.byref(io), PTR, None) == ERR_ARG
 
 
+def decide(cfm, D=256, FF=2048, K=15, causal=False, stateful=False, M=100, streaming=False, without=(), mode="bf16", blocks=3):
+    """(blocks chained, partial slabs per block) as ConformerEncoder._run_blocks and encoder_layer.BlockCall ask for them: after_norm is float32 with the
+    default eps, so it rides in the last block's final chain wherever the row chains run."""
+    import encoder_layer
+    prec = cfm.Precision(mode)
+    ws = [weights(cfm, without) for _ in range(blocks)]
+    chain = encoder_layer.chain_blocks(ws, M, D, FF, K, causal, stateful, cfm.rowchain_supported(D, FF, prec), streaming)
+    return chain, encoder_layer.psum_splits(M, D, FF, prec, streaming, chain)
+
+
+# the cases of ROUTE_TABLE as the Python layer meets them -> (chain, psum splits); streaming = a streaming entry point (split_ffn), stateful = attention or conv caches
+DECISION_TABLE = [
+    ("d256", dict(), (True, 0)),
+    ("d256_streaming_many_rows", dict(M=2048, streaming=True), (True, 0)),
+    ("psum_at_threshold", dict(M=1536, streaming=True), (False, 8)),
+    ("psum_past_threshold", dict(M=1537, streaming=True), (True, 0)),
+    ("psum_7_taps", dict(M=64, K=7, streaming=True), (False, 8)),           # the library then leaves the slabs unused (ROUTE_TABLE: CHAIN)
+    ("few_rows_not_streaming", dict(M=64), (True, 0)),
+    ("caches", dict(stateful=True), (False, 0)),
+    ("caches_streaming", dict(M=64, stateful=True, streaming=True), (False, 8)),
+    ("causal", dict(causal=True), (False, 0)),
+    ("causal_streaming", dict(M=64, causal=True, streaming=True), (False, 8)),
+    ("ff_1024", dict(FF=1024, M=64, streaming=True), (False, 4)),
+    ("d512_pair", dict(D=512, M=4096), (False, 3)),
+    ("d512_pair_streaming", dict(D=512, M=64, streaming=True), (False, 3)),
+    ("d512_past_pair_rows", dict(D=512, M=4097), (False, 0)),
+    ("fused_ffn_d256", dict(without=NOT_FUSED_FFN_PACKS), (False, 0)),
+    ("fused_ffn_d256_streaming", dict(without=NOT_FUSED_FFN_PACKS, M=64, streaming=True), (False, 8)),
+    ("fused_ffn_d144", dict(without=NOT_FUSED_FFN_PACKS, D=144, FF=576), (False, 0)),
+    ("f32_all_packs", dict(mode="fp32", M=64, streaming=True), (False, 0)),
+    ("d144", dict(D=144, FF=576, M=64, streaming=True), (False, 0)),
+]
+
+
+@pytest.mark.parametrize("name,kw,want", DECISION_TABLE, ids=[r[0] for r in DECISION_TABLE])
+def test_chain_and_psum_decisions(cfm, name, kw, want):
+    assert decide(cfm, **kw) == want
+
+
+def test_every_chain_pack_of_every_block_is_needed_to_chain(cfm):
+    import encoder_layer
+    assert encoder_layer.CHAIN_PACKS == CHAIN_PACKS
+    for pack in CHAIN_PACKS:
+        ws = [weights(cfm), weights(cfm, without=(pack,)), weights(cfm)]
+        assert not encoder_layer.chain_blocks(ws, 100, 256, 2048, 15, False, False, True, False), pack
+    assert not encoder_layer.chain_blocks([weights(cfm)], 100, 256, 2048, 15, False, False, False, False)      # after_norm not in the final chain
+
+
+def test_route_switches_are_read_at_call_time(cfm, monkeypatch):
+    import encoder_layer
+    monkeypatch.setattr(encoder_layer, "CHAIN_BLOCKS", False)
+    assert decide(cfm) == (False, 0) and decide(cfm, M=64, streaming=True) == (False, 8)
+    monkeypatch.setattr(encoder_layer, "CHAIN_BLOCKS", True)
+    monkeypatch.setattr(encoder_layer, "SPLIT_FFN_FEW_ROWS", False)
+    assert decide(cfm, M=64, streaming=True) == (True, 0) and decide(cfm, M=64, streaming=True, stateful=True) == (False, 0)
+    monkeypatch.setattr(encoder_layer, "PAIR_MAX_ROWS", 0)
+    assert decide(cfm, D=512) == (False, 0)
+    monkeypatch.setattr(encoder_layer, "split_rows", lambda M, D, FF: False)
+    monkeypatch.setattr(encoder_layer, "SPLIT_FFN_FEW_ROWS", True)
+    assert decide(cfm, M=64, streaming=True) == (True, 0)
+
+
 def test_one_reader_of_the_split_threshold(cfm):
     import encoder_layer
     assert "CFM_FFSPLIT_MAX_ROWS" not in os.environ           # the library reads it once, at first use
