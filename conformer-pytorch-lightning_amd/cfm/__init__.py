@@ -274,6 +274,21 @@ class SpecAugmentDesc(ctypes.Structure):
                 [(n, c_i32) for n in ("B", "T_max", "F", "num_t_mask", "num_f_mask", "max_t", "max_f")] + [("seed", ctypes.c_uint32)])
 
 
+class RescorePrepDesc(ctypes.Structure):
+    _fields_ = ([(n, c_p) for n in ("tokens", "nlen", "score", "embed", "embed_r", "pe", "x0", "x0_r", "targets", "targets_r", "mask")] +
+                [(n, c_i32) for n in ("B", "N", "Lmax", "D", "V", "sos", "eos")])
+
+
+class TokenLogprobDesc(ctypes.Structure):
+    _fields_ = ([(n, c_p) for n in ("X", "W", "bias", "logits", "target", "logp", "lse")] + [("ldx", c_i64), ("ld", c_i64)] +
+                [(n, c_i32) for n in ("M", "D", "V", "x_dtype", "w_dtype")])
+
+
+class RescoreCombineDesc(ctypes.Structure):
+    _fields_ = ([(n, c_p) for n in ("logp", "logp_r", "nlen", "score", "final_score", "left", "right", "order")] + [(n, c_i32) for n in ("B", "N", "Lc")] +
+                [("first_pass_weight", c_f), ("reverse_weight", c_f)])
+
+
 class FfnSplitDesc(ctypes.Structure):
     _fields_ = [("x", c_p), ("psum", c_p), ("psum_b2", c_p), ("psum_splits", c_i32), ("psum_alpha", c_f), ("ln1_g", c_p), ("ln1_b", c_p), ("ln2_g", c_p),
                 ("ln2_b", c_p), ("rows_out", c_p), ("rows2_out", c_p), ("ln_g", c_p), ("ln_b", c_p), ("w1", c_p), ("b1", c_p), ("N1", c_i32), ("act", c_i32),
@@ -307,6 +322,7 @@ for _c_name, _cls in dict(
         cfm_rnnt_desc=RnntDesc, cfm_lattice=Lattice, cfm_rnnt_packed_desc=RnntPackedDesc, cfm_ln_bwd_desc=LnBwdDesc, cfm_lstm_desc=LstmDesc, cfm_greedy_desc=GreedyDesc,
         cfm_greedy_chunk_desc=GreedyChunkDesc, cfm_ctc_greedy_desc=CtcGreedyDesc, cfm_ctc_beam_desc=CtcBeamDesc, cfm_ctc_align_desc=CtcAlignDesc, cfm_edit_distance_desc=EditDistanceDesc, cfm_rnnt_beam_desc=RnntBeamDesc, cfm_rnnt_beam_stream_desc=RnntBeamStreamDesc, cfm_fbank_desc=FbankDesc, cfm_resample_desc=ResampleDesc,
         cfm_resample_bank=ResampleBank, cfm_resample_group_desc=ResampleGroupDesc, cfm_spec_augment_desc=SpecAugmentDesc,
+        cfm_rescore_prep_desc=RescorePrepDesc, cfm_token_logprob_desc=TokenLogprobDesc, cfm_rescore_combine_desc=RescoreCombineDesc,
         cfm_ffn_split_desc=FfnSplitDesc, cfm_layer_scratch=LayerScratch, cfm_layer_io=LayerIO).items():
     _cls._c_name_ = _c_name
 PROTOTYPES = (
@@ -413,6 +429,9 @@ PROTOTYPES = (
     ("cfm_resample_tile_blocks", c_i32, c_i32, c_i32, c_i32),
     ("cfm_resample_group", c_int, P(ResampleGroupDesc), c_p),
     ("cfm_spec_augment", c_int, P(SpecAugmentDesc), c_p),
+    ("cfm_rescore_prep", c_int, P(RescorePrepDesc), c_p),
+    ("cfm_token_logprob", c_int, P(TokenLogprobDesc), c_p),
+    ("cfm_rescore_combine", c_int, P(RescoreCombineDesc), c_p),
 )
 
 _lib = None

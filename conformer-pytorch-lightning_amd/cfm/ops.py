@@ -6,7 +6,7 @@ import torch
 
 import cfm as _c
 
-__all__ = ["lstm_forward", "lstm_backward", "fbank", "fbank_stream", "fbank_stream_ragged", "resample", "resample_stream", "resample_group", "spec_augment", "stream_prep", "stream_advance", "dwconv_causal_bn_silu", "conv_cache_update", "dropout_rows", "dropout_mask", "set_deterministic", "gemm_tn", "gemm_tn_group", "layernorm_bwd", "glu_bwd", "dwconv_bn_train", "dwconv_bn_train_bwd", "dwconv_bn_train_groups", "dwconv_bn_train_bwd_groups", "col2im_relu_bwd", "conv1_wgrad", "attention_bwd", "attention_group", "attention_bwd_group",
+__all__ = ["rescore_prep", "token_logprob", "rescore_combine", "lstm_forward", "lstm_backward", "fbank", "fbank_stream", "fbank_stream_ragged", "resample", "resample_stream", "resample_group", "spec_augment", "stream_prep", "stream_advance", "dwconv_causal_bn_silu", "conv_cache_update", "dropout_rows", "dropout_mask", "set_deterministic", "gemm_tn", "gemm_tn_group", "layernorm_bwd", "glu_bwd", "dwconv_bn_train", "dwconv_bn_train_bwd", "dwconv_bn_train_groups", "dwconv_bn_train_bwd_groups", "col2im_relu_bwd", "conv1_wgrad", "attention_bwd", "attention_group", "attention_bwd_group",
            "ctc_nll_train_groups", "ctc_grad", "rnnt_nll", "rnnt_grad", "joint_act_bwd", "rnnt_nll_packed", "joint_act_packed", "joint_act_packed_bwd", "ffn_split", "adam_step", "adam_clip_step", "sumsq", "scratch_stats",
            "gemm", "ffn_fused", "ffn_fused_supported", "rowchain", "rowchain_supported", "rowchain_pair_supported", "layernorm", "attention", "kv_cache_pack", "dwconv_bn_silu", "conv1_relu", "conv1_relu_mma_supported", "conv12_relu", "conv12_supported", "ctc_nll", "ctc_topk", "ctc_greedy", "ctc_greedy_state", "ctc_prefix_beam", "ctc_align", "edit_distance", "joint_act", "valid_mask", "chunk_mask",
            "attn_mask_combine", "cast", "add_rows", "scratch", "prof_enable", "prof_reset", "prof_table", "as_u8_mask"]
@@ -1749,3 +1749,92 @@ def lstm_backward(x, weights, H, saves, dy, dhn=None, dcn=None, drop=None, out=N
     d.dy, d.dhn, d.dcn, d.dx, d.dh0, d.dc0, d.dg, d.dyl = _c.ptr(dy), _c.ptr(dhn), _c.ptr(dcn), _c.ptr(dx), _c.ptr(dh0), _c.ptr(dc0), _c.ptr(dg), _c.ptr(dyl)
     _c.call("cfm_lstm_backward", ctypes.byref(d))
     return dx, grads, dh0, dc0
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# attention rescoring of n-best lists (csrc/rescore.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+def rescore_prep(tokens, nlen, score, embed, pe, sos, eos, embed_r=None):
+    """Decoder inputs from the device n-best buffers in one launch (include/cfm.h cfm_rescore_prep).  tokens int32 [B,N,Lmax], nlen int32 [B,N],
+    score f32 [B,N]; embed (and embed_r: the right decoder's table, for the reversed hypotheses) f32 [V,D], pe f32 [>= Lmax + 1, D].
+    Returns (x0 f32 [P*Lc, D], targets int32 [P, Lc], mask uint8 [P, Lc, Lc], x0_r | None, targets_r | None), P = B*N, Lc = Lmax + 1."""
+    _c.require_hip(tokens, nlen, score, embed, pe, embed_r)
+    _dense("rescore_prep", tokens=tokens, nlen=nlen, score=score, embed=embed, pe=pe, embed_r=embed_r)
+    if tokens.dim() != 3 or tokens.dtype != torch.int32 or nlen.dtype != torch.int32 or score.dtype != torch.float32:
+        raise ValueError("cfm.rescore_prep: tokens int32 [B,N,Lmax], nlen int32 [B,N], score float32 [B,N]")
+    B, N, Lmax = tokens.shape
+    if tuple(nlen.shape) != (B, N) or tuple(score.shape) != (B, N):
+        raise ValueError("cfm.rescore_prep: nlen %s and score %s must be [B,N] = (%d,%d)" % (tuple(nlen.shape), tuple(score.shape), B, N))
+    if embed.dim() != 2 or embed.dtype != torch.float32 or pe.dtype != torch.float32 or pe.dim() != 2 or pe.shape[1] != embed.shape[1]:
+        raise ValueError("cfm.rescore_prep: embed float32 [V,D] and pe float32 [rows,D]")
+    V, D = embed.shape
+    Lc = Lmax + 1
+    if pe.shape[0] < Lc:
+        raise ValueError("cfm.rescore_prep: %d positions but the position table has %d rows" % (Lc, pe.shape[0]))
+    if embed_r is not None and (embed_r.shape != embed.shape or embed_r.dtype != torch.float32):
+        raise ValueError("cfm.rescore_prep: embed_r must match embed")
+    dev, P = tokens.device, B * N
+    x0 = torch.empty((P * Lc, D), dtype=torch.float32, device=dev)
+    targets = torch.empty((P, Lc), dtype=torch.int32, device=dev)
+    mask = torch.empty((P, Lc, Lc), dtype=torch.uint8, device=dev)
+    x0_r = torch.empty_like(x0) if embed_r is not None else None
+    targets_r = torch.empty_like(targets) if embed_r is not None else None
+    d = _c.RescorePrepDesc()
+    d.tokens, d.nlen, d.score, d.embed, d.embed_r, d.pe = _c.ptr(tokens) if Lmax else None, _c.ptr(nlen), _c.ptr(score), _c.ptr(embed), _c.ptr(embed_r), _c.ptr(pe)
+    d.x0, d.x0_r, d.targets, d.targets_r, d.mask = _c.ptr(x0), _c.ptr(x0_r), _c.ptr(targets), _c.ptr(targets_r), _c.ptr(mask)
+    d.B, d.N, d.Lmax, d.D, d.V, d.sos, d.eos = B, N, Lmax, D, V, int(sos), int(eos)
+    _c.call("cfm_rescore_prep", ctypes.byref(d))
+    return x0, targets, mask, x0_r, targets_r
+
+
+def token_logprob(x, w, bias, target, V, logits=None, want_lse=False, out=None):
+    """logp[m] = log_softmax(x[m] . w^T + bias)[target[m]] over the first V classes, the logits never written (include/cfm.h cfm_token_logprob);
+    0 where target < 0.  x [M,D] f32 or w's dtype (unit inner stride), w [Vp,D] bf16 / fp16 dense, bias f32 [Vp], target int32 [M].
+    logits f32 [M, >= V] (unit inner stride): the reduction and the gather alone over stored logits (x, w, bias may be None).
+    Returns logp f32 [M], or (logp, lse) with want_lse."""
+    _c.require_hip(x, w, bias, target, logits, out)
+    _dense("token_logprob", w=w, bias=bias, target=target, out=out)
+    if target.dtype != torch.int32 or target.dim() != 1:
+        raise ValueError("cfm.token_logprob: target must be int32 [M]")
+    M = target.numel()
+    d = _c.TokenLogprobDesc()
+    if logits is not None:
+        logits = _rows2d(logits, "token_logprob(logits)")
+        if logits.dtype != torch.float32 or logits.shape[0] != M or logits.shape[1] < V:
+            raise ValueError("cfm.token_logprob: logits must be float32 [M = %d, >= V = %d], got %s %s" % (M, V, tuple(logits.shape), logits.dtype))
+        d.logits, d.ld = _c.ptr(logits), logits.stride(0) if M > 1 else logits.shape[1]
+    else:
+        x = _rows2d(x, "token_logprob(x)")
+        if w.dim() != 2 or x.shape[1] != w.shape[1] or x.shape[0] != M or w.shape[0] < V or bias.dtype != torch.float32 or bias.numel() < V:
+            raise ValueError("cfm.token_logprob: x %s, w %s, bias %s, %d targets, V = %d do not fit" % (tuple(x.shape), tuple(w.shape), tuple(bias.shape), M, V))
+        d.X, d.W, d.bias, d.ldx = _c.ptr(x), _c.ptr(w), _c.ptr(bias), x.stride(0) if M > 1 else max(x.stride(0), x.shape[1])
+        d.D, d.x_dtype, d.w_dtype = x.shape[1], _c.dt_code(x), _c.dt_code(w)
+    logp = out if out is not None else torch.empty((M,), dtype=torch.float32, device=target.device)
+    if logp.dtype != torch.float32 or logp.numel() != M:
+        raise ValueError("cfm.token_logprob: out must be float32 [M]")
+    lse = torch.empty((M,), dtype=torch.float32, device=target.device) if want_lse else None
+    d.target, d.logp, d.lse, d.M, d.V = _c.ptr(target), _c.ptr(logp), _c.ptr(lse), M, int(V)
+    _c.call("cfm_token_logprob", ctypes.byref(d))
+    return (logp, lse) if want_lse else logp
+
+
+def rescore_combine(logp, nlen, score, first_pass_weight, reverse_weight=0.0, logp_r=None):
+    """Per-hypothesis sums of the token log-probabilities, the weighted scores and each utterance's ranking in one launch (include/cfm.h
+    cfm_rescore_combine).  logp (and logp_r) f32 [B*N*Lc], nlen int32 [B,N], score f32 [B,N].  Returns (final, left, right f32 [B,N],
+    order int32 [B,N]: the hypothesis index of each rank) on the device."""
+    _c.require_hip(logp, nlen, score, logp_r)
+    _dense("rescore_combine", logp=logp, nlen=nlen, score=score, logp_r=logp_r)
+    if nlen.dim() != 2 or nlen.dtype != torch.int32 or score.dtype != torch.float32 or score.shape != nlen.shape or logp.dtype != torch.float32:
+        raise ValueError("cfm.rescore_combine: nlen int32 [B,N], score float32 [B,N], logp float32")
+    B, N = nlen.shape
+    if logp.numel() % (B * N) or logp.numel() == 0 or (logp_r is not None and (logp_r.numel() != logp.numel() or logp_r.dtype != torch.float32)):
+        raise ValueError("cfm.rescore_combine: logp holds %d values, not a multiple of B*N = %d (logp_r must match it)" % (logp.numel(), B * N))
+    dev = logp.device
+    final, left, right = (torch.empty((B, N), dtype=torch.float32, device=dev) for _ in range(3))
+    order = torch.empty((B, N), dtype=torch.int32, device=dev)
+    d = _c.RescoreCombineDesc()
+    d.logp, d.logp_r, d.nlen, d.score = _c.ptr(logp), _c.ptr(logp_r), _c.ptr(nlen), _c.ptr(score)
+    d.final_score, d.left, d.right, d.order = _c.ptr(final), _c.ptr(left), _c.ptr(right), _c.ptr(order)
+    d.B, d.N, d.Lc, d.first_pass_weight, d.reverse_weight = B, N, logp.numel() // (B * N), float(first_pass_weight), float(reverse_weight)
+    _c.call("cfm_rescore_combine", ctypes.byref(d))
+    return final, left, right, order

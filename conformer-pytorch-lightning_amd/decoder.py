@@ -223,3 +223,217 @@ class CTCGreedyStream:
         if overflow:
             raise RuntimeError("CTCGreedyStream: a stream emitted more symbols than the hypothesis buffer holds")
         return self._log.take(self.S["hyps"], counts)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------------------
+# Attention decoder (eval mode only) and the rescoring of n-best lists
+# ------------------------------------------------------------------------------------------------------------------------------------------------
+class TransformerDecoder(nn.Module):
+    """Drop-in for the reference's class of the same name (src/decoder.py:26-73): constructor arguments, submodule and parameter names, the
+    forward signature and its three return values.  The reference's own decoder cannot run (decoder_layer.py:51 adds a tuple to a tensor), so the
+    arithmetic is the pre-norm transformer decoder stated in float64 in tests/attention_decoder_ref.py; eval mode only.
+
+    One deliberate difference from what the reference's lines would do: `embed` stays nn.Sequential(nn.Embedding, PositionalEncoding) -- the
+    state_dict keys are the reference's -- but it is NOT called.  PositionalEncoding.forward keeps the reference's quirk of slicing its table by
+    the BATCH size (attention.py:119), and a decoder built on that would score the same hypothesis differently depending on its batch slot.  The
+    decoder indexes the f32 sinusoid table (attention._sinusoid_table) by POSITION itself and scales the embedding by sqrt(D):
+    x_i = E[token_i] * sqrt(D) + pe[i]."""
+
+    def __init__(self, vocab_size, decoder_dim, num_heads, hidden_dim, num_layers, dropout, positional_dropout, self_attention_dropout,
+                 src_attention_dropout):
+        super().__init__()
+        from attention import PositionalEncoding
+        from decoder_layer import TransformerDecoderLayer
+        self.embed = nn.Sequential(nn.Embedding(vocab_size, decoder_dim), PositionalEncoding(decoder_dim, positional_dropout))
+        self.after_norm = nn.LayerNorm(decoder_dim, eps=1e-5)
+        self.output_layer = nn.Linear(decoder_dim, vocab_size)
+        self.decoders = nn.ModuleList([TransformerDecoderLayer(decoder_dim, num_heads, hidden_dim, dropout, self_attention_dropout, src_attention_dropout)
+                                       for _ in range(num_layers)])
+        self._pack = packing.PackCache()
+        self._pe = None                                        # f32 [max_len, D] on the parameters' device: a plain attribute, not in the state_dict
+
+    def position_table(self, rows):
+        from attention import _sinusoid_table
+        dev = self.output_layer.weight.device
+        if self._pe is None or self._pe.device != dev or self._pe.shape[0] < rows:
+            self._pe = _sinusoid_table(max(int(rows), 5000), self.output_layer.in_features)[:, 0].contiguous().to(dev)
+        return self._pe
+
+    def _output_pack(self, prec):
+        def build():
+            V, D = self.output_layer.weight.shape
+            Vp = (V + 3) // 4 * 4                              # cfm_gemm wants N % 4 == 0; cfm_token_logprob never reads rows V..Vp
+            w = torch.zeros((Vp, D), dtype=torch.float32, device=self.output_layer.weight.device)
+            w[:V] = self.output_layer.weight.detach()
+            b = torch.zeros((Vp,), dtype=torch.float32, device=w.device)
+            b[:V] = self.output_layer.bias.detach()
+            wm, wlo = packing.matrix(w, prec)
+            return packing.Packed(w=wm, w_lo=wlo, b=b, V=V, Vp=Vp)
+        return self._pack.get([self.output_layer.weight, self.output_layer.bias], prec, build)
+
+    def rows_forward(self, x, self_shape, self_mask, memory_rows, src_shape, memory_mask, prec):
+        """The layers and after_norm on the f32 row matrix x [R, D] (overwritten): the normalised rows in the activation type, ready for the output
+        projection.  The shapes and masks are decoder_layer.layer_rows'."""
+        from decoder_layer import _no_training, layer_rows
+        _no_training(self)
+        for layer in self.decoders:
+            layer_rows(layer, x, self_shape, self_mask, memory_rows, src_shape, memory_mask, prec)
+        return cfm.layernorm(x, self.after_norm.weight, self.after_norm.bias, out1_dtype=prec.act_dtype)[0]
+
+    @torch.no_grad()
+    def forward(self, memory, memory_mask, targets, target_lengths, r_targets=None, reverse_weight=None):
+        """memory [B, T, D], memory_mask bool [B, 1, T], targets long [B, L] (sos + labels), target_lengths (B,).  Returns (logits [B, L, V] -- the
+        unfused cfm.gemm, because the caller wants logits --, torch.tensor(0.0), targets_mask.sum(dim=1)) as decoder.py:62-73."""
+        import math
+        from decoder_layer import _no_training
+        from utils import make_pad_mask, make_subsequent_mask
+        _no_training(self)
+        cfm.require_hip(memory, targets)
+        prec = cfm.resolve_precision(self)
+        B, L = targets.shape
+        T, D = memory.shape[1], memory.shape[2]
+        dev = memory.device
+        lens = torch.as_tensor(target_lengths).to(device=dev, dtype=torch.int32)
+        targets_mask = ~make_pad_mask(lens, L).unsqueeze(1)
+        targets_mask = targets_mask & make_subsequent_mask(L, dev).unsqueeze(0)                       # [B, L, L]
+        E = self.embed[0].weight.detach()
+        x = (E[targets.long()].double() * math.sqrt(D) + self.position_table(L)[:L].double()).float().reshape(B * L, D).contiguous()
+        mem = memory.detach().to(torch.float32).reshape(B * T, D).contiguous()
+        xn = self.rows_forward(x, (B, L), cfm.as_u8_mask(targets_mask), mem, (B, L, T), cfm.as_u8_mask(memory_mask.expand(B, 1, T)), prec)
+        pk = self._output_pack(prec)
+        logits = cfm.gemm(xn, pk.w, bias=pk.b, w_lo=pk.w_lo, out_dtype=torch.float32)[:, :pk.V].reshape(B, L, pk.V)
+        return logits, torch.tensor(0.0), targets_mask.sum(dim=1)
+
+
+class BiTransformerDecoder(nn.Module):
+    """Drop-in for src/decoder.py:76-121: left_decoder and right_decoder (the keys decoder.left_decoder.* / decoder.right_decoder.* of the loadable
+    checkpoints), forward as decoder.py:110-121."""
+
+    def __init__(self, vocab_size, decoder_dim, num_heads, hidden_dim, num_layers, r_num_layers, dropout, pos_enc_dropout, self_attention_dropout,
+                 src_attention_dropout):
+        super().__init__()
+        self.left_decoder = TransformerDecoder(vocab_size, decoder_dim, num_heads, hidden_dim, num_layers, dropout, pos_enc_dropout,
+                                               self_attention_dropout, src_attention_dropout)
+        self.right_decoder = TransformerDecoder(vocab_size, decoder_dim, num_heads, hidden_dim, r_num_layers, dropout, pos_enc_dropout,
+                                                self_attention_dropout, src_attention_dropout)
+
+    def forward(self, memory, memory_mask, targets, target_lengths, r_targets, reverse_weight):
+        left_outputs, right_outputs, output_lengths = self.left_decoder(memory, memory_mask, targets, target_lengths)
+        if reverse_weight > 0.0:
+            right_outputs, _, output_lengths = self.right_decoder(memory, memory_mask, r_targets, target_lengths)
+        return left_outputs, right_outputs, output_lengths
+
+
+class AttentionRescorer:
+    """Second pass over n-best lists: every hypothesis is scored by the attention decoder against its utterance's encoder output and the lists are
+    re-ranked (the definition: tests/attention_decoder_ref.py; the kernels: csrc/rescore.hip).
+
+        final = (1 - reverse_weight) * s_left + reverse_weight * s_right + first_pass_weight * first_pass_score
+
+    with s(y) = sum_i log_softmax(logits_i)[target_i] over (y_1..y_L, eos); the right decoder scores the reversed hypothesis and runs only when
+    reverse_weight > 0 (it needs a BiTransformerDecoder).  No length normalisation.  `sos` / `eos` default to vocab_size - 1, as in model.py.
+
+    A pass per group of utterances: cfm_rescore_prep (inputs, targets and masks from the device n-best buffers), per layer self-attention over
+    P = B*N rows of Lc = Lmax + 1 positions and cross-attention as B utterances of N*Lc queries (the memory's keys and values projected once per
+    utterance and layer), after_norm, cfm_token_logprob (fused=True: the output projection and the log-softmax gather without the logits;
+    fused=False, and always in the fp32 precision mode: cfm_gemm, then the kernel's logits form), cfm_rescore_combine.  One host read at the end.
+    Utterances are grouped so that a group has at most MAX_ROWS = 65536 decoder rows (B * N * Lc)."""
+
+    MAX_ROWS = 65536
+    DEFAULT_FUSED = True
+
+    def __init__(self, decoder, first_pass_weight=0.5, reverse_weight=0.0, sos=None, eos=None, fused=None):
+        if isinstance(decoder, BiTransformerDecoder):
+            self.left, self.right = decoder.left_decoder, decoder.right_decoder
+        elif isinstance(decoder, TransformerDecoder):
+            self.left, self.right = decoder, None
+        else:
+            raise TypeError("AttentionRescorer: decoder is a TransformerDecoder or a BiTransformerDecoder, got %s" % type(decoder).__name__)
+        self.decoder = decoder
+        self.first_pass_weight, self.reverse_weight = float(first_pass_weight), float(reverse_weight)
+        if not 0.0 <= self.reverse_weight <= 1.0:
+            raise ValueError("AttentionRescorer: reverse_weight in [0, 1], got %r" % (reverse_weight,))
+        if self.reverse_weight > 0.0 and self.right is None:
+            raise ValueError("AttentionRescorer: reverse_weight > 0 needs a BiTransformerDecoder (a right decoder)")
+        V = self.left.output_layer.out_features
+        self.sos = V - 1 if sos is None else int(sos)
+        self.eos = V - 1 if eos is None else int(eos)
+        self.fused = self.DEFAULT_FUSED if fused is None else bool(fused)
+
+    def _logp(self, dec, x0, targets, mask, mem, mem_mask, B, N, Lc, T, prec):
+        xn = dec.rows_forward(x0, (B * N, Lc), mask, mem, (B, N * Lc, T), mem_mask, prec)
+        pk = dec._output_pack(prec)
+        D = xn.shape[1]
+        if self.fused and not prec.split and D % 8 == 0 and D <= 512:
+            return cfm.token_logprob(xn, pk.w, pk.b, targets.view(-1), pk.V)
+        logits = cfm.gemm(xn, pk.w, bias=pk.b, w_lo=pk.w_lo, out_dtype=torch.float32)
+        return cfm.token_logprob(None, None, None, targets.view(-1), pk.V, logits=logits)
+
+    def scores(self, encoder_out, encoder_out_lens, tokens, nlen, score):
+        """The device half: (final, left, right f32 [B, N], order int32 [B, N]) of the device n-best buffers tokens int32 [B, N, Lmax], nlen int32
+        [B, N] (-1: unused), score f32 [B, N]; no host synchronisation."""
+        if self.decoder.training:
+            raise NotImplementedError("AttentionRescorer: eval mode only -- the attention decoder has no backward (cross-attention); call .eval()")
+        cfm.require_hip(encoder_out, tokens, nlen, score)
+        prec = cfm.resolve_precision(self.decoder)
+        B, N, Lmax = tokens.shape
+        if encoder_out.dim() != 3 or encoder_out.shape[0] != B:
+            raise ValueError("AttentionRescorer: encoder_out %s for %d n-best lists" % (tuple(encoder_out.shape), B))
+        if not 1 <= N <= 16 or Lmax + 1 > 1024:
+            raise ValueError("AttentionRescorer: N = %d hypotheses of up to %d tokens; 1 <= N <= 16 and at most 1023 tokens" % (N, Lmax))
+        Lc, T, D = Lmax + 1, encoder_out.shape[1], encoder_out.shape[2]
+        dev = encoder_out.device
+        lens = torch.as_tensor(encoder_out_lens).to(device=dev, dtype=torch.int32)
+        mem_mask = cfm.as_u8_mask(cfm.valid_mask(lens, T)).view(B, 1, T)
+        mem = encoder_out.detach().to(torch.float32).reshape(B * T, D).contiguous()
+        pe = self.left.position_table(Lc)
+        two = self.reverse_weight > 0.0
+        group = max(1, self.MAX_ROWS // (N * Lc))
+        outs = []
+        with torch.no_grad():
+            for b0 in range(0, B, group):
+                b1 = min(B, b0 + group)
+                tk, nl, sc = tokens[b0:b1].contiguous(), nlen[b0:b1].contiguous(), score[b0:b1].contiguous()
+                x0, tg, mask, x0r, tgr = cfm.rescore_prep(tk, nl, sc, self.left.embed[0].weight.detach(), pe, self.sos, self.eos,
+                                                          embed_r=self.right.embed[0].weight.detach() if two else None)
+                args = (mem[b0 * T:b1 * T], mem_mask[b0:b1], b1 - b0, N, Lc, T, prec)
+                lp = self._logp(self.left, x0, tg, mask, *args)
+                lpr = self._logp(self.right, x0r, tgr, mask, *args) if two else None
+                outs.append(cfm.rescore_combine(lp, nl, sc, self.first_pass_weight, self.reverse_weight, logp_r=lpr))
+        return outs[0] if len(outs) == 1 else tuple(torch.cat([o[k] for o in outs], 0) for k in range(4))
+
+    def rescore(self, encoder_out, encoder_out_lens, nbest, return_details=False):
+        """nbest: the list of per-utterance lists of (tokens, score) that CTCDecoder.prefix_beam_search and greedy.BeamSearch return, or their device
+        triple (tokens int32 [B, N, Lmax], nlen int32 [B, N], score f32 [B, N]).  Returns per utterance the same hypotheses re-ranked, best first,
+        as (tokens, final); return_details=True: (tokens, final, {"left", "right", "first_pass"})."""
+        dev = encoder_out.device
+        if isinstance(nbest, (tuple, list)) and len(nbest) == 3 and all(isinstance(t, torch.Tensor) for t in nbest):
+            tokens, nlen, score = (t.to(dev) for t in nbest)
+            tokens, nlen, score = tokens.to(torch.int32).contiguous(), nlen.to(torch.int32).contiguous(), score.to(torch.float32).contiguous()
+        else:
+            B = len(nbest)
+            N = max([len(u) for u in nbest] + [1])
+            Lmax = max([len(t) for u in nbest for t, _ in u] + [1])
+            host = torch.zeros((B, N, Lmax + 2), dtype=torch.float64)           # one upload: tokens | length | score
+            host[:, :, Lmax], host[:, :, Lmax + 1] = -1.0, float("-inf")
+            for b, u in enumerate(nbest):
+                for n, (t, s) in enumerate(u):
+                    host[b, n, :len(t)] = torch.tensor(t, dtype=torch.float64)
+                    host[b, n, Lmax], host[b, n, Lmax + 1] = len(t), s
+            d = host.to(dev)
+            tokens, nlen, score = d[:, :, :Lmax].to(torch.int32).contiguous(), d[:, :, Lmax].to(torch.int32).contiguous(), d[:, :, Lmax + 1].to(torch.float32).contiguous()
+        B, N, Lmax = tokens.shape
+        final, left, right, order = self.scores(encoder_out, encoder_out_lens, tokens, nlen, score)
+        host = torch.cat([t.to(torch.float64).reshape(B, N, -1) for t in (final, left, right, order, nlen, score, tokens)], 2).cpu()      # the one host read
+        out = []
+        for b in range(B):
+            rows = []
+            for r in range(N):
+                n = int(host[b, r, 3])
+                f, l, rt, _, ln, sc = host[b, n, :6].tolist()
+                if ln < 0 or sc == float("-inf"):
+                    continue
+                tk = [int(v) for v in host[b, n, 6:6 + int(ln)].tolist()]
+                rows.append((tk, f, {"left": l, "right": rt, "first_pass": sc}) if return_details else (tk, f))
+            out.append(rows)
+        return out

@@ -290,9 +290,14 @@ class OfflineRecognizer:
     The lengths stay on the device; the only host read is the search's own.  encoder_out / encoder_out_lens: what the last call's search read.
     ctc: a decoder.CTCDecoder on the same encoder; recognize_ctc / recognize_ctc_audio then decode its output instead (the hybrid model's cheap first pass),
     and align / align_audio give a known transcript's token spans in encoder frames (frame_seconds converts a frame to its start time).
-    score / score_audio recognise and then score the hypotheses against known transcripts on the device (metrics.py, cfm.edit_distance)."""
+    score / score_audio recognise and then score the hypotheses against known transcripts on the device (metrics.py, cfm.edit_distance).
+    attention: a decoder.TransformerDecoder / BiTransformerDecoder (or a ready decoder.AttentionRescorer) on the same encoder; recognize(beam=k,
+    rescore=True), recognize_ctc(beam=k, rescore=True) and their _audio forms then re-rank each n-best list by the attention decoder
+    (first_pass_weight, reverse_weight: AttentionRescorer's) and return (tokens, final score) pairs, best first.  attention=None changes nothing and
+    adds no launch."""
 
-    def __init__(self, encoder, predictor, joint, blank=0, n_steps=64, fbank=None, ctc=None, **search_kw):
+    def __init__(self, encoder, predictor, joint, blank=0, n_steps=64, fbank=None, ctc=None, attention=None, first_pass_weight=0.5, reverse_weight=0.0,
+                 **search_kw):
         import greedy
         if joint.enc_ffn.in_features != encoder.encoder_dim:
             raise ValueError("OfflineRecognizer: the joint reads %d encoder features, the encoder gives %d" % (joint.enc_ffn.in_features, encoder.encoder_dim))
@@ -302,11 +307,27 @@ class OfflineRecognizer:
         self.fbank = fbank
         self.encoder_out = self.encoder_out_lens = self._beam = None
         self._resamplers = {}                                # sample_rate -> resample.Resampler, made on first use
+        self.rescorer = None
+        if attention is not None:
+            import decoder
+            self.rescorer = attention if isinstance(attention, decoder.AttentionRescorer) else decoder.AttentionRescorer(
+                attention, first_pass_weight=first_pass_weight, reverse_weight=reverse_weight)
+            if self.rescorer.left.output_layer.in_features != encoder.encoder_dim:
+                raise ValueError("OfflineRecognizer: the attention decoder reads %d features, the encoder gives %d" %
+                                 (self.rescorer.left.output_layer.in_features, encoder.encoder_dim))
+
+    def _check_rescore(self, rescore, beam, who):
+        if rescore and beam is None:
+            raise ValueError("OfflineRecognizer.%s: rescore=True re-ranks an n-best list; pass beam=k" % who)
+        if rescore and self.rescorer is None:
+            raise RuntimeError("OfflineRecognizer.%s: rescore=True, but the recogniser was built without an attention decoder (attention=None)" % who)
 
     @torch.no_grad()
-    def recognize(self, feats, lengths, beam=None):
+    def recognize(self, feats, lengths, beam=None, rescore=False):
         """beam=None: the greedy search, a list of B token lists.  beam = 1..15: greedy.BeamSearch over groups of at most 64 // beam utterances,
-        per utterance a list of (tokens, score), best first; an utterance with no encoder frame gives [([], 0.0)]."""
+        per utterance a list of (tokens, score), best first; an utterance with no encoder frame gives [([], 0.0)].  rescore=True (with beam): the
+        lists re-ranked by the attention decoder, (tokens, final score)."""
+        self._check_rescore(rescore, beam, "recognize")
         self.encoder_out, self.encoder_out_lens = self.encoder.forward_utterances(feats, lengths)
         if beam is None:
             return self.search.search(self.encoder_out, self.encoder_out_lens)[0]
@@ -316,7 +337,7 @@ class OfflineRecognizer:
         group, out = 64 // self._beam.beam, []
         for b0 in range(0, self.encoder_out.shape[0], group):
             out.extend(self._beam.search(self.encoder_out[b0:b0 + group], self.encoder_out_lens[b0:b0 + group]))
-        return out
+        return self.rescorer.rescore(self.encoder_out, self.encoder_out_lens, out) if rescore else out
 
     def _features(self, samples, lengths, sample_rate=None):
         """The waveform batch through the fbank; sample_rate (Hz; None: the fbank's own) other than the fbank's sample_frequency goes through a cached
@@ -334,23 +355,27 @@ class OfflineRecognizer:
             samples, lengths = rs(samples, lengths)
         return self.fbank(samples, lengths)
 
-    def recognize_audio(self, samples, lengths, beam=None, sample_rate=None):
-        return self.recognize(*self._features(samples, lengths, sample_rate), beam=beam)
+    def recognize_audio(self, samples, lengths, beam=None, sample_rate=None, rescore=False):
+        self._check_rescore(rescore, beam, "recognize_audio")
+        return self.recognize(*self._features(samples, lengths, sample_rate), beam=beam, rescore=rescore)
 
     @torch.no_grad()
-    def recognize_ctc(self, feats, lengths, beam=None):
+    def recognize_ctc(self, feats, lengths, beam=None, rescore=False):
         """The CTC head's hypotheses of the same ragged batch: forward_utterances once, then decoder.CTCDecoder.greedy_search (beam=None: a list
         of B token lists) or prefix_beam_search(beam) (per utterance a list of (tokens, score), best first).  An utterance with no encoder
-        frame gives [] (beam: the empty hypothesis alone, [([], 0.0)])."""
+        frame gives [] (beam: the empty hypothesis alone, [([], 0.0)]).  rescore=True (with beam): re-ranked by the attention decoder."""
         if self.ctc is None:
             raise RuntimeError("OfflineRecognizer.recognize_ctc: the recogniser was built without a CTC head (ctc=None)")
+        self._check_rescore(rescore, beam, "recognize_ctc")
         self.encoder_out, self.encoder_out_lens = self.encoder.forward_utterances(feats, lengths)
         if beam is None:
             return self.ctc.greedy_search(self.encoder_out, self.encoder_out_lens, blank=self.blank)
-        return self.ctc.prefix_beam_search(self.encoder_out, self.encoder_out_lens, beam=beam, blank=self.blank)
+        nbest = self.ctc.prefix_beam_search(self.encoder_out, self.encoder_out_lens, beam=beam, blank=self.blank)
+        return self.rescorer.rescore(self.encoder_out, self.encoder_out_lens, nbest) if rescore else nbest
 
-    def recognize_ctc_audio(self, samples, lengths, beam=None, sample_rate=None):
-        return self.recognize_ctc(*self._features(samples, lengths, sample_rate), beam=beam)
+    def recognize_ctc_audio(self, samples, lengths, beam=None, sample_rate=None, rescore=False):
+        self._check_rescore(rescore, beam, "recognize_ctc_audio")
+        return self.recognize_ctc(*self._features(samples, lengths, sample_rate), beam=beam, rescore=rescore)
 
     @torch.no_grad()
     def align(self, feats, lengths, labels, label_lengths, return_path=False):

@@ -1508,6 +1508,82 @@ typedef struct {
 } cfm_spec_augment_desc;
 int cfm_spec_augment(const cfm_spec_augment_desc* d, cfm_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Attention rescoring of n-best lists (csrc/rescore.hip; the definition is tests/attention_decoder_ref.py in float64, the host side
+ * decoder.AttentionRescorer).  P = B * N hypotheses, Lc = Lmax + 1 decoder positions each.
+ *
+ * cfm_rescore_prep: everything a decoder pass needs from the device n-best buffers of the beam searches, one launch, no host synchronisation.
+ *   tokens int32 [B, N, Lmax], nlen int32 [B, N], score f32 [B, N] (the first-pass scores); 1 <= N <= 16, 1 <= Lc <= 1024.  Hypothesis p is
+ *   UNUSED when nlen[p] < 0 or score[p] = -inf; otherwise L = min(nlen[p], Lmax), Lcp = L + 1, in = (sos, y_1..y_L), tg = (y_1..y_L, eos).
+ *     x0 [P * Lc, D] f32        row (p, i) = embed[in_i] * sqrt(D) + pe[i] for i < Lcp (evaluated in double, rounded once), else 0
+ *     targets int32 [P, Lc]     tg_i for i < Lcp, else -1
+ *     mask uint8 [P, Lc, Lc]    mask[p][i][j] = (j <= i and j < Lcp): causal and valid; no query row of a used hypothesis is empty
+ *   x0_r / targets_r (null, or both with embed_r): the same for the reversed hypothesis, in = (sos, y_L..y_1), tg = (y_L..y_1, eos), through
+ *   the right decoder's embedding table embed_r; the mask is shared.  An unused hypothesis is dead throughout: x0 rows 0, targets -1, mask 0.
+ *   embed, embed_r f32 [V, D] dense, pe f32 [>= Lc, D] dense (attention._sinusoid_table, indexed by POSITION).  Tokens are clamped into
+ *   [0, V) for the gather (the caller's to guarantee).  Plain vector stores only. */
+typedef struct {
+    const int32_t* tokens;
+    const int32_t* nlen;
+    const float* score;
+    const float* embed;
+    const float* embed_r;
+    const float* pe;
+    float* x0;
+    float* x0_r;
+    int32_t* targets;
+    int32_t* targets_r;
+    uint8_t* mask;
+    int32_t B, N, Lmax, D, V, sos, eos;
+} cfm_rescore_prep_desc;
+int cfm_rescore_prep(const cfm_rescore_prep_desc* d, cfm_stream_t stream);
+
+/* cfm_token_logprob: the log-probability of ONE class per row of an output projection, without the logits:
+ *     logp[m] = (x_m . w_t + b_t) - logsumexp_{c < V} (x_m . w_c + b_c),  t = target[m];     lse[m] (optional) = that logsumexp
+ *   X [M, D] f32 or W's type, rows ldx elements apart (f32 is rounded to W's type first, as cfm_gemm does); W [Vp, D] bf16 / fp16 dense,
+ *   bias f32 [Vp], Vp >= V: rows and bias entries V..Vp are never read.  D % 8 == 0, D <= 512; X and W 16-byte aligned, ldx a multiple of 4
+ *   (f32) or 8 (16-bit).  The product is 16x16x32 MFMA with f32 accumulation, computed transposed (W . X^T: the vocabulary runs along a
+ *   lane's accumulator registers, a lane owns one row); the logsumexp is online in f32 -- a running maximum and a running sum per row,
+ *   folded per tile of 32 classes, lanes and wavefronts combined once at the end in a fixed order.  No atomics: the same input gives the
+ *   same bits.  A row with target < 0 gives logp = 0 and lse = 0; a tile of 64 rows that holds no other row leaves without reading W;
+ *   target >= V gives NaN.
+ *   logits != NULL (f32 [M, >= V], rows ld elements apart): the product is skipped (X, W, bias are not read; D is ignored) and only the
+ *   reduction and the gather run, one wavefront per row -- the second half of the unfused form (cfm_gemm, then this), which the fp32
+ *   precision mode uses (cfm_gemm owns the three-product formula). */
+typedef struct {
+    const void* X;
+    const void* W;
+    const float* bias;
+    const float* logits;
+    const int32_t* target;
+    float* logp;
+    float* lse;
+    int64_t ldx, ld;
+    int32_t M, D, V, x_dtype, w_dtype;
+} cfm_token_logprob_desc;
+int cfm_token_logprob(const cfm_token_logprob_desc* d, cfm_stream_t stream);
+
+/* cfm_rescore_combine: per hypothesis the sum of its Lc token log-probabilities in position order (f32, one add per position), the weighted
+ * scores and the ranking of each utterance's N entries, one launch:
+ *     left[p] = sum_i logp[p][i]; right[p] likewise over logp_r (0 when logp_r is null: reverse_weight must then be 0)
+ *     att = left when reverse_weight = 0, else (1 - reverse_weight) * left + reverse_weight * right;   final = att + first_pass_weight * score
+ *   (each product and sum rounded on its own).  An unused hypothesis (nlen < 0 or score = -inf) has final = -inf.  order int32 [B, N]:
+ *   entry r is the index of the hypothesis of rank r -- higher final first, on an exact tie (unused entries among themselves included) the
+ *   lower index, i.e. the better first-pass rank; a NaN final ranks as -inf.  1 <= N <= 16. */
+typedef struct {
+    const float* logp;
+    const float* logp_r;
+    const int32_t* nlen;
+    const float* score;
+    float* final_score;
+    float* left;
+    float* right;
+    int32_t* order;
+    int32_t B, N, Lc;
+    float first_pass_weight, reverse_weight;
+} cfm_rescore_combine_desc;
+int cfm_rescore_combine(const cfm_rescore_combine_desc* d, cfm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
