@@ -26,6 +26,48 @@ def _dense(name, **tensors):
             raise ValueError("cfm.%s: %s must be contiguous (the C ABI has no stride for it), got shape %s strides %s" % (name, k, tuple(t.shape), t.stride()))
 
 
+_F32, _I32, _I64 = torch.float32, torch.int32, torch.int64
+
+
+def _layout(op, _hint="", **specs):
+    """What a group of dense arguments must be, said once: name=(tensor, dtype, extent).  dtype: a torch.dtype, a tuple of them, or None (any).
+    extent: an int (that many elements whatever the shape: a [B,1] lengths tensor is an int32 [B]), a shape tuple (that rank and those sizes, None
+    for an axis of any size) or None (any).  name=None is an optional argument that was not given (_opt); a tensor that is None is a required one
+    that is missing.  Always contiguous, as _dense: the C ABI has no stride for these operands.  A pure function of tensor metadata (no device,
+    no library); _hint is appended to the message (what the group is, or the phrase a caller knows the failure by)."""
+    for name, spec in specs.items():
+        if spec is None:
+            continue
+        t, dtype, extent = spec
+        dtypes = dtype if isinstance(dtype, tuple) else (dtype,)
+        if extent is None:
+            fits, size = t is not None, ""
+        elif isinstance(extent, int):
+            fits, size = t is not None and t.numel() == extent, " of %d elements" % extent
+        else:
+            fits = t is not None and t.dim() == len(extent) and all(w is None or w == g for w, g in zip(extent, t.shape))
+            size = " [%s]" % ", ".join("*" if w is None else str(w) for w in extent)
+        if not fits or not t.is_contiguous() or (dtype is not None and t.dtype not in dtypes):
+            raise ValueError("cfm.%s: %s must be contiguous%s%s (the C ABI has no stride for it), got %s%s" % (
+                op, name, "" if dtype is None else " " + " or ".join(str(d)[6:] for d in dtypes), size,
+                "None" if t is None else "%s %s strides %s" % (str(t.dtype)[6:], tuple(t.shape), t.stride()), _hint and ": " + _hint))
+
+
+def _want(op, _hint="", **specs):
+    """_layout behind the device check: a tensor that is not on the GPU is cfm.require_hip's RuntimeError before any layout complaint."""
+    _c.require_hip(*[s[0] for s in specs.values() if s is not None])
+    _layout(op, _hint, **specs)
+
+
+def _opt(t, *spec):
+    return None if t is None else (t,) + spec
+
+
+def _i32(n, **tensors):
+    """int32 [n]: lengths, offsets, flags per stream or per utterance -- by element count (n an int) or as the exact shape (n a tuple)."""
+    return {k: (t, _I32, n) for k, t in tensors.items()}
+
+
 def _strides_match(name, what, t, sb, st):
     """An operand addressed through explicit (batch, time) element strides: where the tensor itself has those axes, they must agree with
     what the call passes -- the C ABI reads the numbers, not the tensor."""
@@ -223,7 +265,7 @@ def ffn_split(x, w_code, mode, psum=None, psum_b2=None, psum_alpha=1.0, ln1=None
         _c.require_hip(kv, offs)
         d.kv_ring, d.ring_offsets, d.ring_T, d.ring_H, d.ring_Tq = kv.data_ptr(), offs.data_ptr(), kv.shape[2], kv.shape[1], tq
         if len(ring) > 3 and ring[3] is not None:
-            _stream_lens("ffn_split", offs.numel(), ring_len=ring[3])
+            _want("ffn_split", ring_len=(ring[3], _I32, offs.numel()))
             d.ring_len = ring[3].data_ptr()
     _c.call("cfm_ffn_split", ctypes.byref(d))
 
@@ -356,7 +398,7 @@ def attention_group(problems):
 def kv_cache_pack(old_cache, k, v, k_str, v_str, B, H, Tn, dk):
     """-> f32 (B,H,Tc+Tn,2dk): rows < Tc copied from old_cache, the rest taken from k / v."""
     Tc = old_cache.size(2) if old_cache is not None else 0
-    if old_cache is not None:
+    if old_cache is not None:                            # by hand: a strided cache is copied, not refused, which _layout does not state
         if old_cache.dtype != torch.float32 or tuple(old_cache.shape) != (B, H, Tc, 2 * dk):
             raise ValueError("cfm.kv_cache_pack: cache must be float32 (B,H,Tc,2dk); got %s %s" % (old_cache.dtype, tuple(old_cache.shape)))
         old_cache = old_cache.contiguous()
@@ -449,18 +491,25 @@ def conv12_relu(x, w9c, b1, w2, b2, cmvn=None):
     return out
 
 
+def _ctc_logits(op, logits):
+    """-> (B, T) of f32 logits [B,T,ld] whose rows are evenly spaced (cfm.h passes one row stride)."""
+    if logits.dim() != 3 or logits.dtype != torch.float32 or logits.stride(2) != 1 or logits.stride(0) != logits.size(1) * logits.stride(1):
+        raise ValueError("cfm.%s: logits must be float32 [B,T,>=V] with contiguous rows, got %s %s strides %s" % (op, logits.dtype, tuple(logits.shape), logits.stride()))
+    return logits.shape[:2]
+
+
+def _ctc_args(op, logits, enc_lens, labels, label_lens):
+    """The operands every CTC loss / alignment entry takes: logits, enc_lens / label_lens int32 [B], labels int32 [B,Umax].  -> (B, T)."""
+    _c.require_hip(logits, enc_lens, labels, label_lens)
+    B, T = _ctc_logits(op, logits)
+    _layout(op, "logits has B = %d; where a count is off, the batch sizes differ" % B, labels=(labels, _I32, (B, None)), **_i32(B, enc_lens=enc_lens, label_lens=label_lens))
+    return B, T
+
+
 def ctc_nll(logits, V, enc_lens, labels, label_lens):
     """Per-utterance CTC negative log-likelihood from UN-normalised f32 logits [B,T,ld>=V] (log-softmax applied on the fly); blank 0.
     enc_lens / label_lens int32 [B], labels int32 [B,Umax].  Returns f32 [B] (include/cfm.h cfm_ctc_nll)."""
-    _c.require_hip(logits, enc_lens, labels, label_lens)
-    if logits.dim() != 3 or logits.dtype != torch.float32 or logits.stride(2) != 1 or logits.stride(0) != logits.size(1) * logits.stride(1):
-        raise ValueError("cfm.ctc_nll: logits must be float32 [B,T,>=V] with contiguous rows")
-    B, T = logits.shape[:2]
-    for t in (enc_lens, labels, label_lens):
-        if t.dtype != torch.int32 or not t.is_contiguous():
-            raise ValueError("cfm.ctc_nll: lengths and labels must be contiguous int32")
-    if labels.dim() != 2 or labels.size(0) != B or enc_lens.numel() != B or label_lens.numel() != B:
-        raise ValueError("cfm.ctc_nll: batch sizes differ")
+    B, T = _ctc_args("ctc_nll", logits, enc_lens, labels, label_lens)
     out = torch.empty((B,), dtype=torch.float32, device=logits.device)
     work = scratch("ctc_lp", B * T * (2 * labels.size(1) + 2), torch.float32, logits.device)
     _c.call("cfm_ctc_nll", _c.ptr(logits), logits.stride(1), B, T, V, _c.ptr(enc_lens), _c.ptr(labels), labels.size(1), _c.ptr(label_lens),
@@ -474,20 +523,14 @@ def ctc_topk(logits, V, lens, k, out=None):
     logp f32 [B,T,k], lse f32 [B,T]); rows of frames at or beyond lens[b] are not written (out: such a triple to write into; fresh ones are
     zero-filled).  include/cfm.h cfm_ctc_topk."""
     _c.require_hip(logits, lens)
-    if logits.dim() != 3 or logits.dtype != torch.float32 or logits.stride(2) != 1 or logits.stride(0) != logits.size(1) * logits.stride(1):
-        raise ValueError("cfm.ctc_topk: logits must be float32 [B,T,>=V] with contiguous rows")
-    B, T = logits.shape[:2]
-    if lens.dtype != torch.int32 or not lens.is_contiguous() or lens.numel() != B:
-        raise ValueError("cfm.ctc_topk: lens must be contiguous int32 [B]")
+    B, T = _ctc_logits("ctc_topk", logits)
+    _layout("ctc_topk", **_i32(B, lens=lens))
     k = int(k)
     if out is None:
         out = (torch.zeros((B, T, max(k, 0)), dtype=torch.int32, device=logits.device), torch.zeros((B, T, max(k, 0)), dtype=torch.float32, device=logits.device),
                torch.zeros((B, T), dtype=torch.float32, device=logits.device))
     idx, logp, lse = out
-    _c.require_hip(idx, logp, lse)
-    _dense("ctc_topk", idx=idx, logp=logp, lse=lse)
-    if (idx.dtype, logp.dtype, lse.dtype) != (torch.int32, torch.float32, torch.float32) or idx.numel() != B * T * k or logp.numel() != B * T * k or lse.numel() != B * T:
-        raise ValueError("cfm.ctc_topk: out must be (int32 [B,T,k], float32 [B,T,k], float32 [B,T])")
+    _want("ctc_topk", "out must be (idx int32 [B,T,k], logp float32 [B,T,k], lse float32 [B,T])", idx=(idx, _I32, B * T * k), logp=(logp, _F32, B * T * k), lse=(lse, _F32, B * T))
     _c.call("cfm_ctc_topk", _c.ptr(logits), logits.stride(1), B, T, V, _c.ptr(lens), k, _c.ptr(idx), _c.ptr(logp), _c.ptr(lse))
     return idx, logp, lse
 
@@ -500,30 +543,25 @@ def ctc_greedy_state(B, cap, device):
                 hyps=z((B, cap), torch.int64), frames=z((B, cap), torch.int32), token_logp=z((B, cap), torch.float32), overflow=z((1,), torch.int32))
 
 
+def _topk_args(op, idx, logp, lens):
+    """ctc_topk's output as the decoders read it: idx int32 and logp f32 [B,T,k], lens int32 [B].  -> (B, T, k)."""
+    _want(op, "idx int32 and logp float32 are the [B,T,k] of ctc_topk", idx=(idx, _I32, (None, None, None)), logp=(logp, _F32, tuple(idx.shape)),
+          lens=(lens, _I32, idx.shape[:1].numel()))
+    return idx.shape
+
+
 def ctc_greedy(idx, logp, lens, V, blank=0, state=None, hyp_cap=None):
     """Best-path CTC decoding of ctc_topk's output (any k; the first column is read): per stream the classes of frames 0 .. lens[b] - 1 with
     repeats collapsed and blanks dropped are APPENDED to state (ctc_greedy_state; a fresh one with room for T symbols when None), which carries
     the last frame's class from call to call.  Returns state; the caller reads count / hyps / frames / token_logp / overflow from it.
     include/cfm.h cfm_ctc_greedy."""
-    _c.require_hip(idx, logp, lens)
-    if idx.dim() != 3 or idx.shape != logp.shape or idx.dtype != torch.int32 or logp.dtype != torch.float32:
-        raise ValueError("cfm.ctc_greedy: idx int32 and logp float32 [B,T,k] of ctc_topk")
-    _dense("ctc_greedy", idx=idx, logp=logp, lens=lens)
-    B, T, k = idx.shape
-    if lens.dtype != torch.int32 or lens.numel() != B:
-        raise ValueError("cfm.ctc_greedy: lens must be contiguous int32 [B]")
+    B, T, k = _topk_args("ctc_greedy", idx, logp, lens)
     S = ctc_greedy_state(B, T, idx.device) if state is None else state
-    _c.require_hip(*[v for v in S.values() if v is not None])
-    _dense("ctc_greedy", **S)
-    for name, dt, shape in (("prev", torch.int32, (B,)), ("count", torch.int64, (B,)), ("hyps", torch.int64, None), ("frames", torch.int32, tuple(S["hyps"].shape)),
-                            ("token_logp", torch.float32, tuple(S["hyps"].shape)), ("overflow", torch.int32, (1,))):
-        if S[name].dtype != dt or (shape is not None and tuple(S[name].shape) != shape):
-            raise ValueError("cfm.ctc_greedy: state[%r] must be %s %s" % (name, dt, shape))
-    if S["hyps"].dim() != 2 or S["hyps"].size(0) != B:
-        raise ValueError("cfm.ctc_greedy: state['hyps'] must be int64 [B, cap]")
-    fb = S.get("frame_base")
-    if fb is not None and (fb.dtype != torch.int32 or tuple(fb.shape) != (B,)):
-        raise ValueError("cfm.ctc_greedy: state['frame_base'] must be int32 [B]")
+    fb, cap = S.get("frame_base"), tuple(S["hyps"].shape)
+    spec = {name: _opt(t, None, None) for name, t in S.items()}               # whatever else the state holds is at least dense
+    spec.update(prev=(S["prev"], _I32, (B,)), count=(S["count"], _I64, (B,)), hyps=(S["hyps"], _I64, (B, None)), frames=(S["frames"], _I32, cap),
+                token_logp=(S["token_logp"], _F32, cap), overflow=(S["overflow"], _I32, (1,)), frame_base=_opt(fb, _I32, (B,)))
+    _want("ctc_greedy", "an entry of state (ctc_greedy_state)", **spec)
     d = _c.CtcGreedyDesc()
     d.idx, d.logp, d.ld_k, d.lens = _c.ptr(idx), _c.ptr(logp), k, _c.ptr(lens)
     d.prev, d.frame_base, d.hyps, d.count, d.frames, d.token_logp, d.overflow = (_c.ptr(S["prev"]), _c.ptr(fb), _c.ptr(S["hyps"]), _c.ptr(S["count"]), _c.ptr(S["frames"]),
@@ -541,14 +579,8 @@ def ctc_prefix_beam(idx, logp, lens, V, beam=None, blank=0, out=None, nodes=None
     (nbest_tokens int64 [B,beam,T], nbest_len int32 [B,beam], nbest_score f32 [B,beam]), best first; entry n holds nbest_len[b,n] tokens, entries
     beyond the live prefixes have length 0 and score -inf.  out: such a triple to write into; nodes: the int32 [B*beam*(T+1), 2] trie scratch.
     include/cfm.h cfm_ctc_prefix_beam."""
-    _c.require_hip(idx, logp, lens)
-    if idx.dim() != 3 or idx.shape != logp.shape or idx.dtype != torch.int32 or logp.dtype != torch.float32:
-        raise ValueError("cfm.ctc_prefix_beam: idx int32 and logp float32 [B,T,beam] of ctc_topk")
-    _dense("ctc_prefix_beam", idx=idx, logp=logp, lens=lens)
-    B, T, k = idx.shape
+    B, T, k = _topk_args("ctc_prefix_beam", idx, logp, lens)
     beam = k if beam is None else int(beam)
-    if lens.dtype != torch.int32 or lens.numel() != B:
-        raise ValueError("cfm.ctc_prefix_beam: lens must be contiguous int32 [B]")
     dev = idx.device
     if out is None:
         nb = max(beam, 0)
@@ -557,11 +589,8 @@ def ctc_prefix_beam(idx, logp, lens, V, beam=None, blank=0, out=None, nodes=None
     tokens, nlen, score = out
     if nodes is None:
         nodes = scratch("ctc_beam_nodes", 2 * B * max(beam, 1) * (T + 1), torch.int32, dev)
-    _c.require_hip(tokens, nlen, score, nodes)
-    _dense("ctc_prefix_beam", nbest_tokens=tokens, nbest_len=nlen, nbest_score=score, nodes=nodes)
-    if ((tokens.dtype, nlen.dtype, score.dtype, nodes.dtype) != (torch.int64, torch.int32, torch.float32, torch.int32) or tokens.numel() != B * beam * T or
-            nlen.numel() != B * beam or score.numel() != B * beam):
-        raise ValueError("cfm.ctc_prefix_beam: out must be (int64 [B,beam,T], int32 [B,beam], float32 [B,beam]), nodes int32")
+    _want("ctc_prefix_beam", "out must be (nbest_tokens int64 [B,beam,T], nbest_len int32 [B,beam], nbest_score float32 [B,beam]), nodes int32",
+          nbest_tokens=(tokens, _I64, B * beam * T), nbest_len=(nlen, _I32, B * beam), nbest_score=(score, _F32, B * beam), nodes=(nodes, _I32, None))
     d = _c.CtcBeamDesc()
     d.idx, d.logp, d.lens, d.nodes, d.n_nodes = _c.ptr(idx), _c.ptr(logp), _c.ptr(lens), _c.ptr(nodes), nodes.numel() // 2
     d.nbest_tokens, d.nbest_len, d.nbest_score = _c.ptr(tokens), _c.ptr(nlen), _c.ptr(score)
@@ -577,25 +606,14 @@ def ctc_align(logits, V, enc_lens, labels, label_lens, out=None):
     enc_lens[b]), score the path's log-probability, per label its first / last frame and the sum of its frames' log-probabilities (-1, -1, -inf
     beyond label_lens[b]); an utterance that has no alignment gives score -inf and that fill everywhere.  out: such a tuple to write into.
     include/cfm.h cfm_ctc_align states the recursion and its tie rule."""
-    _c.require_hip(logits, enc_lens, labels, label_lens)
-    if logits.dim() != 3 or logits.dtype != torch.float32 or logits.stride(2) != 1 or logits.stride(0) != logits.size(1) * logits.stride(1):
-        raise ValueError("cfm.ctc_align: logits must be float32 [B,T,>=V] with contiguous rows")
-    B, T = logits.shape[:2]
-    for t in (enc_lens, labels, label_lens):
-        if t.dtype != torch.int32 or not t.is_contiguous():
-            raise ValueError("cfm.ctc_align: lengths and labels must be contiguous int32")
-    if labels.dim() != 2 or labels.size(0) != B or enc_lens.numel() != B or label_lens.numel() != B:
-        raise ValueError("cfm.ctc_align: batch sizes differ")
+    B, T = _ctc_args("ctc_align", logits, enc_lens, labels, label_lens)
     Umax, dev = labels.size(1), logits.device
     if out is None:
         out = (torch.empty((B, T), dtype=torch.int32, device=dev), torch.empty((B,), dtype=torch.float32, device=dev), torch.empty((B, Umax), dtype=torch.int32, device=dev),
                torch.empty((B, Umax), dtype=torch.int32, device=dev), torch.empty((B, Umax), dtype=torch.float32, device=dev))
     path, score, start, end, token_logp = out
-    _c.require_hip(path, score, start, end, token_logp)
-    _dense("ctc_align", path=path, score=score, start=start, end=end, token_logp=token_logp)
-    if ((path.dtype, score.dtype, start.dtype, end.dtype, token_logp.dtype) != (torch.int32, torch.float32, torch.int32, torch.int32, torch.float32) or
-            path.numel() != B * T or score.numel() != B or start.numel() != B * Umax or end.numel() != B * Umax or token_logp.numel() != B * Umax):
-        raise ValueError("cfm.ctc_align: out must be (int32 [B,T], float32 [B], int32 [B,Umax], int32 [B,Umax], float32 [B,Umax])")
+    _want("ctc_align", "out must be (path int32 [B,T], score float32 [B], start int32 [B,Umax], end int32 [B,Umax], token_logp float32 [B,Umax])",
+          path=(path, _I32, B * T), score=(score, _F32, B), start=(start, _I32, B * Umax), end=(end, _I32, B * Umax), token_logp=(token_logp, _F32, B * Umax))
     nbytes = int(_c.lib().cfm_ctc_align_scratch_bytes(B, T, max(Umax, 0)))
     work = scratch("ctc_lp", B * T * (2 * Umax + 2), torch.float32, dev)
     moves = scratch("ctc_align_moves", nbytes, torch.uint8, dev)
@@ -616,14 +634,12 @@ def edit_distance(hyp, hyp_lens, ref, ref_lens, ref_index=None, counts=True, ops
     (1 hit, 2 substitution, 3 deletion, 4 insertion, 0 beyond ops_len) imply counts.  out: such a tuple to write into (None where not wanted).
     Nothing is read back to the host."""
     _c.require_hip(hyp, hyp_lens, ref, ref_lens, ref_index)
-    for t in (hyp, hyp_lens, ref, ref_lens) + (() if ref_index is None else (ref_index,)):
-        if t.dtype != torch.int32 or not t.is_contiguous():
-            raise ValueError("cfm.edit_distance: tokens, lengths and ref_index must be contiguous int32")
-    if hyp.dim() != 2 or ref.dim() != 2:
-        raise ValueError("cfm.edit_distance: hyp must be [P,Hmax] and ref [R,Umax]")
+    _layout("edit_distance", "hyp is [P,Hmax] and ref [R,Umax]", hyp=(hyp, _I32, (None, None)), ref=(ref, _I32, (None, None)))
     (P, Hmax), (R, Umax), dev = hyp.shape, ref.shape, hyp.device
-    if hyp_lens.numel() != P or ref_lens.numel() != R or (ref_index is None and P != R) or (ref_index is not None and ref_index.numel() != P):
-        raise ValueError("cfm.edit_distance: batch sizes differ")
+    _layout("edit_distance", "P = %d hypotheses, R = %d references; where a count is off, the batch sizes differ" % (P, R),
+            ref_index=_opt(ref_index, _I32, P), **_i32(P, hyp_lens=hyp_lens), **_i32(R, ref_lens=ref_lens))
+    if ref_index is None and P != R:
+        raise ValueError("cfm.edit_distance: batch sizes differ: %d hypotheses for %d references and no ref_index" % (P, R))
     if P < 1 or R < 1:
         raise ValueError("cfm.edit_distance: no pair to score")
     if Hmax > 1024 or Umax > 1024:
@@ -633,12 +649,10 @@ def edit_distance(hyp, hyp_lens, ref, ref_lens, ref_index=None, counts=True, ops
         i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
         out = (i32(P), i32(P, 4) if counts else None, torch.empty((P, Hmax + Umax), dtype=torch.uint8, device=dev) if ops else None, i32(P) if ops else None)
     dist, cnt, op, op_len = out
-    _c.require_hip(dist, cnt, op, op_len)
-    _dense("edit_distance", dist=dist, counts=cnt, ops=op, ops_len=op_len)
-    if ((cnt is not None) != counts or (op is not None) != bool(ops) or (op_len is not None) != bool(ops) or dist.dtype != torch.int32 or dist.numel() != P or
-            (counts and (cnt.dtype != torch.int32 or cnt.numel() != 4 * P)) or
-            (ops and (op.dtype != torch.uint8 or op.numel() != P * (Hmax + Umax) or op_len.dtype != torch.int32 or op_len.numel() != P))):
-        raise ValueError("cfm.edit_distance: out must be (int32 [P], int32 [P,4] | None, uint8 [P,Hmax+Umax] | None, int32 [P] | None) as counts / ops ask")
+    what = "out must be (dist int32 [P], counts int32 [P,4] | None, ops uint8 [P,Hmax+Umax] | None, ops_len int32 [P] | None) as counts / ops ask"
+    _want("edit_distance", what, dist=(dist, _I32, P), counts=_opt(cnt, _I32, 4 * P), ops=_opt(op, torch.uint8, P * (Hmax + Umax)), ops_len=_opt(op_len, _I32, P))
+    if (cnt is not None) != counts or (op is not None) != bool(ops) or (op_len is not None) != bool(ops):
+        raise ValueError("cfm.edit_distance: " + what)
     nbytes = int(_c.lib().cfm_edit_distance_scratch_bytes(P, Hmax, Umax)) if counts else 0
     moves = scratch("edit_distance_moves", nbytes, torch.uint8, dev) if nbytes else None
     d = _c.EditDistanceDesc()
@@ -764,8 +778,7 @@ def gemm_tn(a, b, out=None, want_colsum=False, row_mask=None, alpha=1.0, conv=No
         d.ldb = b.stride(0)
     else:
         C, T1, F1, T2, F2 = conv
-        if not b.is_contiguous() or b.numel() != (M // (T2 * F2)) * T1 * F1 * C:
-            raise ValueError("cfm.gemm_tn(conv): image must be contiguous channels-last [B,T1,F1,C]")
+        _layout("gemm_tn(conv)", "the channels-last image [B,T1,F1,C]", b=(b, None, (M // (T2 * F2)) * T1 * F1 * C))
         K = 9 * C
         d.conv_C, d.conv_T1, d.conv_F1, d.conv_T2, d.conv_F2 = C, T1, F1, T2, F2
     if out is None:
@@ -781,10 +794,7 @@ def gemm_tn(a, b, out=None, want_colsum=False, row_mask=None, alpha=1.0, conv=No
         raise ValueError("cfm.gemm_tn: out must be float32 (%d,%d)" % (N, K))
     if want_colsum and colsum is None:
         colsum = torch.empty((N,), dtype=torch.float32, device=a.device)
-    if colsum is not None and (colsum.dtype != torch.float32 or colsum.numel() != N or not colsum.is_contiguous()):
-        raise ValueError("cfm.gemm_tn: colsum must be contiguous float32 [N]")
-    if row_mask is not None and (row_mask.dtype != torch.uint8 or row_mask.numel() != M or not row_mask.is_contiguous()):
-        raise ValueError("cfm.gemm_tn: row_mask must be contiguous uint8 [M]")
+    _layout("gemm_tn", colsum=_opt(colsum, _F32, N), row_mask=_opt(row_mask, torch.uint8, M))
     d.A, d.B, d.C, d.colsum, d.row_mask = _c.ptr(a), _c.ptr(b), _c.ptr(out), _c.ptr(colsum), _c.ptr(row_mask)
     d.lda, d.ldc = a.stride(0), out.stride(0)
     d.M, d.N, d.K = M, N, K
@@ -804,22 +814,18 @@ def gemm_tn_group(products, mma_code=_c.BF16, splits=0):
         a, b, out = _rows2d(pr["a"], "gemm_tn_group(a)"), _rows2d(pr["b"], "gemm_tn_group(b)"), pr["out"]
         colsum = pr.get("colsum")
         _c.require_hip(a, b, out, colsum)
-        if a.shape[0] != b.shape[0] or out.dtype != torch.float32 or (colsum is not None and colsum.dtype != torch.float32):
-            raise ValueError("cfm.gemm_tn_group: a %s, b %s, out %s" % (tuple(a.shape), tuple(b.shape), out.dtype))
+        if a.shape[0] != b.shape[0] or out.dtype != torch.float32 or out.stride(-1) != 1:
+            raise ValueError("cfm.gemm_tn_group: a %s and b %s with one row count and a float32 out with unit inner stride, got out %s strides %s"
+                             % (tuple(a.shape), tuple(b.shape), out.dtype, out.stride()))
         d.A, d.B, d.C, d.colsum = a.data_ptr(), b.data_ptr(), out.data_ptr(), _c.ptr(colsum)
         d.lda, d.ldb = a.stride(0), b.stride(0)
         d.M, d.N, d.K = a.shape[0], a.shape[1], b.shape[1]
-        if out.stride(-1) != 1 or (colsum is not None and not colsum.is_contiguous()):
-            raise ValueError("cfm.gemm_tn_group: out needs unit inner stride and colsum must be contiguous")
         # a 2-D out carries its own row stride; a flat slab (row_off scatter) has none to carry
         d.ldc = pr.get("ldc", out.stride(0) if out.dim() == 2 and pr.get("row_off") is None else d.K)
         d.a_dtype, d.b_dtype, d.mma_dtype = _c.dt_code(a), _c.dt_code(b), mma_code
         d.accumulate, d.splits, d.alpha = 1, (1 if _deterministic[0] else splits), float(pr.get("alpha", 1.0))
         tabs = {k: pr.get(k) for k in ("row_off", "colsum_off", "colsum_off2")}
-        _c.require_hip(*tabs.values())
-        _dense("gemm_tn_group", **tabs)
-        if any(t is not None and (t.dtype != torch.int64 or t.numel() != d.N) for t in tabs.values()):
-            raise ValueError("cfm.gemm_tn_group: row_off / colsum_off / colsum_off2 must be int64 [N]")
+        _want("gemm_tn_group", colsum=_opt(colsum, _F32, None), **{k: _opt(t, _I64, d.N) for k, t in tabs.items()})
         d.row_off, d.colsum_off, d.colsum_off2 = _c.ptr(tabs["row_off"]), _c.ptr(tabs["colsum_off"]), _c.ptr(tabs["colsum_off2"])
     _c.call("cfm_gemm_tn_group", descs, n)
 
@@ -827,18 +833,13 @@ def gemm_tn_group(products, mma_code=_c.BF16, splits=0):
 def layernorm_bwd(x, dy, gamma, row_mask=None, dres=None, dx=None, eps=1e-5):
     """-> (dx, dgamma, dbeta): dx = (dres or 0) + dLayerNorm(dy) w.r.t. the norm's input x (f32 [M,D]); dx may be dres itself."""
     _c.require_hip(x, dy, gamma, row_mask, dres, dx)
-    x = _rows2d(x, "layernorm_bwd(x)")
+    _layout("layernorm_bwd", x=(_rows2d(x, "layernorm_bwd(x)"), _F32, None))
     M, D = x.shape
-    if x.dtype != torch.float32 or not x.is_contiguous() or tuple(dy.shape) != (M, D) or not dy.is_contiguous():
-        raise ValueError("cfm.layernorm_bwd: x must be contiguous float32 [M,D] and dy contiguous [M,D]")
-    _dense("layernorm_bwd", gamma=gamma, row_mask=row_mask)
-    if gamma.dtype != torch.float32 or gamma.numel() != D or (row_mask is not None and (row_mask.element_size() != 1 or row_mask.numel() != M)):
-        raise ValueError("cfm.layernorm_bwd: gamma must be float32 [D] and row_mask one byte per row [M]")
+    _layout("layernorm_bwd", dy=(dy, None, (M, D)), gamma=(gamma, _F32, D), row_mask=_opt(row_mask, None, M), dres=_opt(dres, _F32, (M, D)), dx=_opt(dx, _F32, (M, D)))
+    if row_mask is not None and row_mask.element_size() != 1:
+        raise ValueError("cfm.layernorm_bwd: row_mask is one byte per row, got %s" % row_mask.dtype)
     if dx is None:
         dx = torch.empty_like(x)
-    for t in (dres, dx):
-        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (M, D) or not t.is_contiguous()):
-            raise ValueError("cfm.layernorm_bwd: dres / dx must be contiguous float32 [M,D]")
     dg = torch.empty((D,), dtype=torch.float32, device=x.device)
     db = torch.empty((D,), dtype=torch.float32, device=x.device)
     ws = scratch("ln_bwd", _c.lib().cfm_layernorm_bwd_ws(M, D), torch.float32, x.device)
@@ -855,8 +856,7 @@ def glu_bwd(u, dg, out_dtype):
     _c.require_hip(u, dg)
     M, D2 = u.shape
     D = D2 // 2
-    if not u.is_contiguous() or not dg.is_contiguous() or tuple(dg.shape) != (M, D):
-        raise ValueError("cfm.glu_bwd: u must be contiguous [M,2D] and dg contiguous [M,D]")
+    _layout("glu_bwd", u=(u, None, (M, D2)), dg=(dg, None, (M, D)))
     du = torch.empty((M, D2), dtype=out_dtype, device=u.device)
     _c.call("cfm_glu_bwd", _c.ptr(u), _c.dt_code(u), _c.ptr(dg), _c.dt_code(dg), _c.ptr(du), _c.dt_code(du), M, D)
     return du
@@ -879,18 +879,8 @@ def _train_groups(who, groups, rows):
     return arr
 
 
-def _row_matrix(who, name, t, M, cols, dtype=None):
-    if t is None:
-        return
-    if t.dim() != 2 or tuple(t.shape) != (M, cols) or not t.is_contiguous() or (dtype is not None and t.dtype != dtype):
-        raise ValueError("cfm.%s: %s must be a contiguous %s[%d,%d] row matrix (the C ABI has no stride for it), got %s %s strides %s"
-                         % (who, name, "" if dtype is None else str(dtype) + " ", M, cols, t.dtype, tuple(t.shape), t.stride()))
-
-
-def _vec_f32(who, D, **vecs):
-    for k, t in vecs.items():
-        if t is not None and (t.dtype != torch.float32 or t.numel() != D or not t.is_contiguous()):
-            raise ValueError("cfm.%s: %s must be contiguous float32 [%d] (the C ABI has no stride for it)" % (who, k, D))
+def _vec_f32(D, **vecs):
+    return {k: _opt(t, _F32, D) for k, t in vecs.items()}
 
 
 def _dw_window_ws(groups, D, ws, who, device):
@@ -913,20 +903,15 @@ def dwconv_bn_train_groups(g, groups, w, dw_bias, gamma, beta, running_mean=None
     M, D = g.shape
     n = len(groups)
     arr = _train_groups(who, groups, M)
-    _row_matrix(who, "g", g, M, D)
-    _vec_f32(who, D, dw_bias=dw_bias, gamma=gamma, beta=beta, running_mean=running_mean, running_var=running_var)
+    _layout(who, g=(g, None, (M, D)), **_vec_f32(D, dw_bias=dw_bias, gamma=gamma, beta=beta, running_mean=running_mean, running_var=running_var))
     if (running_mean is None) != (running_var is None):
         raise ValueError("cfm.%s: running_mean and running_var go together" % who)
-    if w.dtype != torch.float32 or w.dim() != 2 or w.shape[0] != D or not w.is_contiguous():
-        raise ValueError("cfm.%s: w must be contiguous float32 [D,K] (the C ABI has no stride for it)" % who)
+    _layout(who, w=(w, _F32, (D, None)))
     dev = g.device
     c = torch.empty((M, D), dtype=torch.float32, device=dev) if c is None else c
     s = torch.empty((M, D), dtype=s_dtype if s_dtype is not None else g.dtype, device=dev) if s is None else s
     stats = torch.empty((n, 4, D), dtype=torch.float32, device=dev) if stats is None else stats
-    _row_matrix(who, "c", c, M, D, torch.float32)
-    _row_matrix(who, "s", s, M, D)
-    if stats.dtype != torch.float32 or stats.numel() != n * 4 * D or not stats.is_contiguous():
-        raise ValueError("cfm.%s: stats must be contiguous float32 [n_groups,4,D] (the C ABI has no stride for it)" % who)
+    _layout(who, c=(c, _F32, (M, D)), s=(s, None, (M, D)), stats=(stats, _F32, n * 4 * D))
     ws = _dw_window_ws(groups, D, ws, who, dev)
     _c.call("cfm_dwconv_bn_train_groups", _c.ptr(g), _c.dt_code(g), _c.ptr(w), _c.ptr(dw_bias), _c.ptr(gamma), _c.ptr(beta), _c.ptr(running_mean),
             _c.ptr(running_var), momentum, eps, _c.ptr(c), _c.ptr(stats), _c.ptr(s), _c.dt_code(s), _c.ptr(ws), arr, n, D, w.shape[1])
@@ -946,13 +931,7 @@ def dwconv_bn_train_bwd_groups(ds, c, stats, g, groups, w, dg_dtype=None, accumu
     M, D = g.shape
     n = len(groups)
     arr = _train_groups(who, groups, M)
-    _row_matrix(who, "g", g, M, D)
-    _row_matrix(who, "ds", ds, M, D)
-    _row_matrix(who, "c", c, M, D, torch.float32)
-    if stats.dtype != torch.float32 or stats.numel() != n * 4 * D or not stats.is_contiguous():
-        raise ValueError("cfm.%s: stats must be contiguous float32 [n_groups,4,D] (the C ABI has no stride for it)" % who)
-    if w.dtype != torch.float32 or w.dim() != 2 or w.shape[0] != D or not w.is_contiguous():
-        raise ValueError("cfm.%s: w must be contiguous float32 [D,K] (the C ABI has no stride for it)" % who)
+    _layout(who, g=(g, None, (M, D)), ds=_opt(ds, None, (M, D)), c=_opt(c, _F32, (M, D)), stats=(stats, _F32, n * 4 * D), w=(w, _F32, (D, None)))
     dev = g.device
     K = w.shape[1]
     if glu_du is not None and glu_u is None:
@@ -966,20 +945,18 @@ def dwconv_bn_train_bwd_groups(ds, c, stats, g, groups, w, dg_dtype=None, accumu
         if dg_dtype is not None and dg_dtype != g.dtype:
             raise ValueError("cfm.%s: the fused GLU backward needs g and dg of one dtype" % who)
         glu_du = torch.empty((M, 2 * D), dtype=g.dtype, device=dev) if glu_du is None else glu_du
-        _row_matrix(who, "glu_u", glu_u, M, 2 * D, g.dtype)
-        _row_matrix(who, "glu_du", glu_du, M, 2 * D, g.dtype)
+        _layout(who, glu_u=(glu_u, g.dtype, (M, 2 * D)), glu_du=(glu_du, g.dtype, (M, 2 * D)))
         dg_code = _c.dt_code(g)
     else:
         dg = torch.empty((M, D), dtype=dg_dtype if dg_dtype is not None else g.dtype, device=dev) if dg is None else dg
-        _row_matrix(who, "dg", dg, M, D)
+        _layout(who, dg=(dg, None, (M, D)))
         dg_code = _c.dt_code(dg)
     given = [t is not None for t in (dw_w, dw_b, dgamma, dbeta)]
     if accumulate and not all(given):
         raise ValueError("cfm.%s: accumulate adds to dw_w, dw_b, dgamma, dbeta: pass all four" % who)
     dw_w = torch.empty((D, K), dtype=torch.float32, device=dev) if dw_w is None else dw_w
     dw_b, dgamma, dbeta = (torch.empty((D,), dtype=torch.float32, device=dev) if t is None else t for t in (dw_b, dgamma, dbeta))
-    _row_matrix(who, "dw_w", dw_w, D, K, torch.float32)
-    _vec_f32(who, D, dw_b=dw_b, dgamma=dgamma, dbeta=dbeta)
+    _layout(who, dw_w=(dw_w, _F32, (D, K)), **_vec_f32(D, dw_b=dw_b, dgamma=dgamma, dbeta=dbeta))
     dy_ws = scratch("dwbn_dy", M * D, torch.float32, dev) if dy_ws is None else dy_ws
     if dy_ws.dtype != torch.float32 or dy_ws.numel() < M * D or not dy_ws.is_contiguous():
         raise ValueError("cfm.%s: dy_ws must be contiguous float32 with at least M*D = %d elements" % (who, M * D))
@@ -1024,8 +1001,7 @@ def col2im_relu_bwd(dcol, h1, out_dtype):
     _c.require_hip(dcol, h1)
     B, T1, F1, C = h1.shape
     T2, F2 = (T1 - 3) // 2 + 1, (F1 - 3) // 2 + 1
-    if not dcol.is_contiguous() or tuple(dcol.shape) != (B * T2 * F2, 9 * C) or not h1.is_contiguous():
-        raise ValueError("cfm.col2im_relu_bwd: dcol must be contiguous [B*T2*F2, 9C] and h1 contiguous [B,T1,F1,C]")
+    _layout("col2im_relu_bwd", dcol=(dcol, None, (B * T2 * F2, 9 * C)), h1=(h1, None, (B, T1, F1, C)))
     dh1 = torch.empty((B, T1, F1, C), dtype=out_dtype, device=h1.device)
     _c.call("cfm_col2im_relu_bwd", _c.ptr(dcol), _c.dt_code(dcol), _c.ptr(h1), _c.dt_code(h1), _c.ptr(dh1), _c.dt_code(dh1), B, T1, F1, C)
     return dh1
@@ -1037,13 +1013,10 @@ def conv1_wgrad(dh1, x, cmvn=None):
     B, T, F = x.shape
     C = dh1.shape[3]
     mean, istd = cmvn if cmvn is not None else (None, None)
-    _c.require_hip(mean, istd)
-    _dense("conv1_wgrad", mean=mean, istd=istd)
-    for t in (mean, istd):
-        if t is not None and (t.dtype != torch.float32 or t.numel() != F):
-            raise ValueError("cfm.conv1_wgrad: cmvn statistics must be float32 [F]")
-    if x.dtype != torch.float32 or not x.is_contiguous() or not dh1.is_contiguous() or tuple(dh1.shape[:3]) != (B, (T - 3) // 2 + 1, (F - 3) // 2 + 1):
-        raise ValueError("cfm.conv1_wgrad: x must be contiguous float32 [B,T,F] and dh1 contiguous [B,T1,F1,C]")
+    _want("conv1_wgrad", "the cmvn statistics", mean=_opt(mean, _F32, F), istd=_opt(istd, _F32, F))
+    _layout("conv1_wgrad", x=(x, _F32, (B, T, F)), dh1=(dh1, None, None))
+    if tuple(dh1.shape[:3]) != (B, (T - 3) // 2 + 1, (F - 3) // 2 + 1):           # a prefix test: not an extent _layout states
+        raise ValueError("cfm.conv1_wgrad: dh1 must be [B,T1,F1,C] = (%d, %d, %d, C), got %s" % (B, (T - 3) // 2 + 1, (F - 3) // 2 + 1, tuple(dh1.shape)))
     dw = torch.empty((9, C), dtype=torch.float32, device=x.device)
     db = torch.empty((C,), dtype=torch.float32, device=x.device)
     ws = scratch("conv1_wgrad", _c.lib().cfm_conv1_wgrad_ws(B, T, C), torch.float32, x.device)
@@ -1112,17 +1085,6 @@ def attention_bwd_group(problems):
     _c.call("cfm_attention_bwd_group", arr, n)
 
 
-def _ctc_args(logits, enc_lens, labels, label_lens):
-    if logits.dim() != 3 or logits.dtype != torch.float32 or logits.stride(2) != 1 or logits.stride(0) != logits.size(1) * logits.stride(1):
-        raise ValueError("cfm.ctc: logits must be float32 [B,T,>=V] with contiguous rows")
-    for t in (enc_lens, labels, label_lens):
-        if t.dtype != torch.int32 or not t.is_contiguous():
-            raise ValueError("cfm.ctc: lengths and labels must be contiguous int32")
-    B = logits.shape[0]
-    if labels.dim() != 2 or labels.size(0) != B or enc_lens.numel() != B or label_lens.numel() != B:
-        raise ValueError("cfm.ctc: batch sizes differ")
-
-
 def ctc_nll_train_groups(problems, V):
     """As ctc_nll for the micro-batches of a training window (a single batch is a window of one), keeping what ctc_grad needs, with ONE launch for
     all their recursions (include/cfm.h cfm_ctc_nll_train_groups).  problems: [(logits [B,T,ld], enc_lens, labels, label_lens)]; returns
@@ -1131,9 +1093,7 @@ def ctc_nll_train_groups(problems, V):
     arr = (_c.CtcGroup * n)()
     outs = []
     for g, (logits, enc_lens, labels, label_lens) in zip(arr, problems):
-        _c.require_hip(logits, enc_lens, labels, label_lens)
-        _ctc_args(logits, enc_lens, labels, label_lens)
-        B, T = logits.shape[:2]
+        B, T = _ctc_args("ctc_nll_train_groups", logits, enc_lens, labels, label_lens)
         SM = 2 * labels.size(1) + 2
         dev = logits.device
         nll, nllp = torch.empty((B,), dtype=torch.float32, device=dev), torch.empty((B,), dtype=torch.float32, device=dev)
@@ -1149,15 +1109,12 @@ def ctc_nll_train_groups(problems, V):
 
 def ctc_grad(logits, V, enc_lens, labels, label_lens, state, gscale=1.0, gscale_dev=None, out=None):
     """d (sum_b nll_b) / d logits * gscale * (*gscale_dev), f32 [B,T,ld], from one micro-batch's state of ctc_nll_train_groups."""
-    _c.require_hip(logits, enc_lens, labels, label_lens, gscale_dev, out)
-    _ctc_args(logits, enc_lens, labels, label_lens)
+    _c.require_hip(gscale_dev, out)
+    B, T = _ctc_args("ctc_grad", logits, enc_lens, labels, label_lens)
     work, alpha, lse, nllp, beta = state
-    B, T = logits.shape[:2]
-    _c.require_hip(work, alpha, lse, nllp, beta)
-    _dense("ctc_grad", work=work, alpha=alpha, lse=lse, nll_shifted=nllp, beta=beta, gscale_dev=gscale_dev)
-    SM = 2 * labels.size(1) + 2
-    if any(t.dtype != torch.float32 for t in state) or any(t.numel() != B * T * SM for t in (work, alpha, beta)) or lse.numel() != B * T or nllp.numel() != B:
-        raise ValueError("cfm.ctc_grad: state must be the float32 (work, alpha, lse, nll_shifted, beta) of ctc_nll_train_groups for these logits")
+    n = B * T * (2 * labels.size(1) + 2)
+    _want("ctc_grad", "state must be the float32 (work, alpha, lse, nll_shifted, beta) of ctc_nll_train_groups for these logits",
+          work=(work, _F32, n), alpha=(alpha, _F32, n), lse=(lse, _F32, B * T), nll_shifted=(nllp, _F32, B), beta=(beta, _F32, n), gscale_dev=_opt(gscale_dev, None, None))
     if out is None:
         out = torch.empty_like(logits)
     if out.dtype != torch.float32 or out.shape != logits.shape or out.stride() != logits.stride():
@@ -1217,11 +1174,7 @@ def rnnt_nll(logits, targets, logit_lens, target_lens, blank, V=None):
     ld = logits.stride(2)
     if logits.stride(1) != U1 * ld or logits.stride(0) != T * U1 * ld:
         raise ValueError("cfm.rnnt_nll: logits rows must be evenly spaced (strides %s)" % (logits.stride(),))
-    for t in (targets, logit_lens, target_lens):
-        if t.dtype != torch.int32 or not t.is_contiguous():
-            raise ValueError("cfm.rnnt_nll: targets and lengths must be contiguous int32")
-    if tuple(targets.shape) != (B, U1 - 1) or logit_lens.numel() != B or target_lens.numel() != B:
-        raise ValueError("cfm.rnnt_nll: targets %s / lengths do not match logits %s" % (tuple(targets.shape), tuple(logits.shape)))
+    _layout("rnnt_nll", "to match logits %s" % (tuple(logits.shape),), targets=(targets, _I32, (B, U1 - 1)), **_i32(B, logit_lens=logit_lens, target_lens=target_lens))
     d = _c.RnntDesc()
     tens = _rnnt_state(d, "rnnt_nll", logits, ld, V, blank, targets, (B, T, U1), B, T + U1)
     tens.update(logit_lens=logit_lens, target_lens=target_lens)
@@ -1270,9 +1223,9 @@ def joint_act_bwd(enc, pred, dact, B, T, U):
     _c.require_hip(enc, pred, dact)
     enc, pred = _rows2d(enc, "joint_act_bwd(enc)"), _rows2d(pred, "joint_act_bwd(pred)")
     J = enc.shape[1]
-    if (enc.dtype, pred.dtype, dact.dtype) != (torch.float32,) * 3 or tuple(enc.shape) != (B * T, J) or tuple(pred.shape) != (B * U, J) \
-            or tuple(dact.shape) != (B * T * U, J) or not dact.is_contiguous():
-        raise ValueError("cfm.joint_act_bwd: enc f32 [%d,J], pred f32 [%d,J], dact contiguous f32 [%d,J] expected" % (B * T, B * U, B * T * U))
+    if enc.dtype != torch.float32 or pred.dtype != torch.float32 or tuple(enc.shape) != (B * T, J) or tuple(pred.shape) != (B * U, J):
+        raise ValueError("cfm.joint_act_bwd: enc must be f32 [%d,J] and pred f32 [%d,J], got %s %s" % (B * T, B * U, tuple(enc.shape), tuple(pred.shape)))
+    _layout("joint_act_bwd", dact=(dact, _F32, (B * T * U, J)))
     de = torch.empty((B * T, J), dtype=torch.float32, device=enc.device)
     dp = torch.empty((B * U, J), dtype=torch.float32, device=enc.device)
     ws = scratch("joint_act_bwd", _c.lib().cfm_joint_act_bwd_ws(B, T, U, J), torch.float32, enc.device)
@@ -1300,9 +1253,9 @@ def joint_act_packed_bwd(enc, pred, dact, lat):
     _c.require_hip(enc, pred, dact)
     enc, pred = _rows2d(enc, "joint_act_packed_bwd(enc)"), _rows2d(pred, "joint_act_packed_bwd(pred)")
     J, d = enc.shape[1], lat.desc
-    if (enc.dtype, pred.dtype, dact.dtype) != (torch.float32,) * 3 or tuple(enc.shape) != (d.n_enc, J) or tuple(pred.shape) != (d.n_pred, J) \
-            or tuple(dact.shape) != (lat.M, J) or not dact.is_contiguous():
-        raise ValueError("cfm.joint_act_packed_bwd: enc f32 [%d,J], pred f32 [%d,J], dact contiguous f32 [%d,J] expected" % (d.n_enc, d.n_pred, lat.M))
+    if enc.dtype != torch.float32 or pred.dtype != torch.float32 or tuple(enc.shape) != (d.n_enc, J) or tuple(pred.shape) != (d.n_pred, J):
+        raise ValueError("cfm.joint_act_packed_bwd: enc must be f32 [%d,J] and pred f32 [%d,J], got %s %s" % (d.n_enc, d.n_pred, tuple(enc.shape), tuple(pred.shape)))
+    _layout("joint_act_packed_bwd", dact=(dact, _F32, (lat.M, J)))
     de = torch.empty((d.n_enc, J), dtype=torch.float32, device=enc.device)
     dp = torch.empty((d.n_pred, J), dtype=torch.float32, device=enc.device)
     ws = torch.empty((max(lat.n_blk, 1), J), dtype=torch.float32, device=enc.device)
@@ -1318,8 +1271,9 @@ def rnnt_nll_packed(logits, targets, lat, blank, V=None):
     _c.require_hip(logits, targets)
     if logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[0] != lat.M:
         raise ValueError("cfm.rnnt_nll_packed: logits must be [M=%d, V] with unit inner stride, got %s strides %s" % (lat.M, tuple(logits.shape), logits.stride()))
-    if targets.dtype != torch.int32 or not targets.is_contiguous() or targets.dim() != 2 or targets.shape[0] != lat.B or targets.shape[1] < lat.U1_max - 1:
-        raise ValueError("cfm.rnnt_nll_packed: targets must be contiguous int32 [B=%d, >=%d], got %s" % (lat.B, lat.U1_max - 1, tuple(targets.shape)))
+    _layout("rnnt_nll_packed", targets=(targets, _I32, (lat.B, None)))
+    if targets.shape[1] < lat.U1_max - 1:
+        raise ValueError("cfm.rnnt_nll_packed: targets must be int32 [B=%d, >=%d], got %s" % (lat.B, lat.U1_max - 1, tuple(targets.shape)))
     M = lat.M
     d = _c.RnntPackedDesc()
     tens = _rnnt_state(d, "rnnt_nll_packed", logits, logits.stride(0), V, blank, targets, (M,), lat.B, lat.T_max + lat.U1_max)
@@ -1333,12 +1287,8 @@ def rnnt_nll_packed(logits, targets, lat, blank, V=None):
 
 def adam_step(p, g, m, v, lr, betas, eps, weight_decay, step, grad_scale=None):
     """In-place Adam over flat float32 buffers (torch.optim.Adam's update rule); grad_scale: optional device scalar multiplied into g."""
-    _c.require_hip(p, g, m, v, grad_scale)
     n = p.numel()
-    for t in (p, g, m, v):
-        if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous():
-            raise ValueError("cfm.adam_step: p, g, m, v must be contiguous float32 buffers of one size")
-    _dense("adam_step", grad_scale=grad_scale)
+    _want("adam_step", "p, g, m, v are float32 buffers of one size", p=(p, _F32, n), g=(g, _F32, n), m=(m, _F32, n), v=(v, _F32, n), grad_scale=_opt(grad_scale, None, None))
     _c.call("cfm_adam_step", _c.ptr(p), _c.ptr(g), _c.ptr(m), _c.ptr(v), n, lr, betas[0], betas[1], eps, weight_decay, step, _c.ptr(grad_scale))
 
 
@@ -1346,12 +1296,8 @@ def adam_clip_step(p, g, m, v, lr, betas, eps, weight_decay, step, sumsq_t, clip
     """adam_step with the clip coefficient computed on the device from `sumsq_t` (cfm.sumsq of g), the 1/world averaging and the zeroing of g in
     the same launch (include/cfm.h cfm_adam_clip_step).  Returns the averaged gradient's norm as a 1-element device tensor, or None when
     sumsq_t is None (clip off: the kernel has nothing to take a norm from)."""
-    _c.require_hip(p, g, m, v, sumsq_t)
     n = p.numel()
-    for t in (p, g, m, v):
-        if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous():
-            raise ValueError("cfm.adam_clip_step: p, g, m, v must be contiguous float32 buffers of one size")
-    _dense("adam_clip_step", sumsq=sumsq_t)
+    _want("adam_clip_step", "p, g, m, v are float32 buffers of one size", p=(p, _F32, n), g=(g, _F32, n), m=(m, _F32, n), v=(v, _F32, n), sumsq=_opt(sumsq_t, None, None))
     norm = None if sumsq_t is None else torch.empty((1,), dtype=torch.float32, device=p.device)
     _c.call("cfm_adam_clip_step", _c.ptr(p), _c.ptr(g), _c.ptr(m), _c.ptr(v), n, lr, betas[0], betas[1], eps, weight_decay, step, _c.ptr(sumsq_t),
             float(clip or 0.0), float(inv_world), 1 if zero_grad else 0, _c.ptr(norm))
@@ -1360,9 +1306,7 @@ def adam_clip_step(p, g, m, v, lr, betas, eps, weight_decay, step, sumsq_t, clip
 
 def sumsq(x):
     """sum(x^2) of a flat float32 buffer as a 1-element device tensor (no host sync)."""
-    _c.require_hip(x)
-    if x.dtype != torch.float32 or not x.is_contiguous():
-        raise ValueError("cfm.sumsq: x must be a contiguous float32 buffer")
+    _want("sumsq", x=(x, _F32, None))
     n = x.numel()
     nb = max(1, min(1024, (n + 4095) // 4096))
     part = scratch("sumsq", nb, torch.float32, x.device)
@@ -1375,13 +1319,10 @@ def dropout_rows(x, out_dtype, alpha=1.0, drop=None, drop2=None, row_mask=None):
     """y = alpha * x * keep(seed, element) / (1 - p), rows with row_mask == 0 zeroed: the gradient of a residual branch
     x + alpha * dropout(f) as a GEMM operand (include/cfm.h cfm_dropout_rows).  drop / drop2 = (p, seed) or None."""
     _c.require_hip(x, row_mask)
-    x = _rows2d(x, "dropout_rows(x)")
-    if not x.is_contiguous():
-        raise ValueError("cfm.dropout_rows: x must be contiguous")
-    M, N = x.shape
-    _dense("dropout_rows", row_mask=row_mask)
-    if row_mask is not None and (row_mask.element_size() != 1 or row_mask.numel() != M):
-        raise ValueError("cfm.dropout_rows: row_mask must be one byte per row [M]")
+    M, N = _rows2d(x, "dropout_rows(x)").shape
+    _layout("dropout_rows", x=(x, None, None), row_mask=_opt(row_mask, None, M))
+    if row_mask is not None and row_mask.element_size() != 1:
+        raise ValueError("cfm.dropout_rows: row_mask is one byte per row, got %s" % row_mask.dtype)
     y = torch.empty((M, N), dtype=out_dtype, device=x.device)
     p1, s1 = (float(drop[0]), int(drop[1]) & 0xFFFFFFFF) if drop is not None else (0.0, 0)
     p2, s2 = (float(drop2[0]), int(drop2[1]) & 0xFFFFFFFF) if drop2 is not None else (0.0, 0)
@@ -1400,60 +1341,39 @@ def dropout_mask(n, p, seed, device):
 # ----------------------------------------------------------------------------------------------------------------------
 # per-stream streaming state (include/cfm.h, csrc/stream.hip)
 # ----------------------------------------------------------------------------------------------------------------------
-def _stream_lens(op, B, **named):
-    for name, t in named.items():
-        if t.dtype != torch.int32 or t.numel() != B:
-            raise ValueError("cfm.%s: %s must be int32 [B = %d], got %s %s" % (op, name, B, t.dtype, tuple(t.shape)))
-    _c.require_hip(*named.values())
-    _dense(op, **named)
-
-
 def stream_prep(offsets, T, need, ring_T, pe, slot_mask, pos_rows, abs_rows=None, frame_lens=None, out_lens=None):
     """offsets int32 [B] -> slot_mask u8 [B,ring_T], pos_rows f32 [B,ring_T,D] (= pe[frame held by the slot]), abs_rows f32 [B,D] = pe[offset].
     frame_lens int32 [B] (with out_lens int32 [B]): per-stream window lengths in feature frames; out_lens receives the encoder frames c_b of each
     stream and the mask / rows cover the cached frames and those c_b (include/cfm.h cfm_stream_prep)."""
-    _c.require_hip(offsets, pe, slot_mask, pos_rows, abs_rows)
     B = offsets.numel()
     D = pe.shape[-1]
-    _dense("stream_prep", offsets=offsets, slot_mask=slot_mask, pos_rows=pos_rows, abs_rows=abs_rows)
-    if offsets.dtype != torch.int32 or pe.dtype != torch.float32 or not pe.is_contiguous() or slot_mask.numel() != B * ring_T or pos_rows.numel() != B * ring_T * D:
-        raise ValueError("cfm.stream_prep: offsets int32 [B], pe contiguous f32 [max_len,D], slot_mask [B,ring_T], pos_rows [B,ring_T,D]")
+    _want("stream_prep", "offsets int32 [B], pe f32 [max_len,D], slot_mask [B,ring_T], pos_rows [B,ring_T,D]", offsets=(offsets, _I32, None), pe=(pe, _F32, None),
+          slot_mask=(slot_mask, None, B * ring_T), pos_rows=(pos_rows, None, B * ring_T * D), abs_rows=_opt(abs_rows, None, None),
+          frame_lens=_opt(frame_lens, _I32, B), out_lens=_opt(out_lens, _I32, B))
     if (frame_lens is None) != (out_lens is None):
         raise ValueError("cfm.stream_prep: frame_lens and out_lens come together")
-    if frame_lens is not None:
-        _stream_lens("stream_prep", B, frame_lens=frame_lens, out_lens=out_lens)
     _c.call("cfm_stream_prep", _c.ptr(offsets), _c.ptr(frame_lens), _c.ptr(out_lens), B, T, need, ring_T, _c.ptr(pe), pe.numel() // D, D,
             _c.ptr(slot_mask), _c.ptr(pos_rows), _c.ptr(abs_rows))
 
 
 def stream_advance(offsets, T, active=None, lens=None, y=None):
     """offsets[b] += T (active streams), or -- lens int32 [B] -- += lens[b], with rows t >= lens[b] of y f32 [B,T,D] (optional) set to zero."""
-    _c.require_hip(offsets, active)
-    _dense("stream_advance", offsets=offsets, active=active)
     B = offsets.numel()
-    D = 0
-    if lens is not None:
-        _stream_lens("stream_advance", B, lens=lens)
-        if active is not None:
-            raise ValueError("cfm.stream_advance: active is not combined with lens")
-    if y is not None:
-        if lens is None:
-            raise ValueError("cfm.stream_advance: y comes with lens")
-        _c.require_hip(y)
-        if y.dtype != torch.float32 or not y.is_contiguous() or y.dim() != 3 or tuple(y.shape[:2]) != (B, T):
-            raise ValueError("cfm.stream_advance: y must be contiguous float32 [B,T,D]")
-        D = y.shape[2]
+    _want("stream_advance", offsets=(offsets, None, None), active=_opt(active, None, None), lens=_opt(lens, _I32, B), y=_opt(y, _F32, (B, T, None)))
+    if lens is not None and active is not None:
+        raise ValueError("cfm.stream_advance: active is not combined with lens")
+    if y is not None and lens is None:
+        raise ValueError("cfm.stream_advance: y comes with lens")
+    D = y.shape[2] if y is not None else 0
     _c.call("cfm_stream_advance", _c.ptr(offsets), _c.ptr(active), _c.ptr(lens), _c.ptr(y), B, T, D)
 
 
 def dwconv_causal_bn_silu(x, w, dw_bias, bn_scale, bn_shift, cache=None, out_dtype=None):
     """OPT-IN causal depthwise conv + folded BatchNorm + SiLU over [cache | x]; x [B,T,D], cache f32 [B,K-1,D] or None (zeros)."""
-    _c.require_hip(x, w, dw_bias, bn_scale, bn_shift, cache)
     B, T, D = x.shape
     K = w.shape[1]
-    _dense("dwconv_causal_bn_silu", w=w, dw_bias=dw_bias, bn_scale=bn_scale, bn_shift=bn_shift)
-    if not x.is_contiguous() or (cache is not None and (cache.dtype != torch.float32 or tuple(cache.shape) != (B, K - 1, D) or not cache.is_contiguous())):
-        raise ValueError("cfm.dwconv_causal_bn_silu: x contiguous [B,T,D], cache contiguous f32 [B,K-1,D]")
+    _want("dwconv_causal_bn_silu", x=(x, None, (B, T, D)), w=(w, None, None), dw_bias=_opt(dw_bias, None, None), bn_scale=_opt(bn_scale, None, None), bn_shift=_opt(bn_shift, None, None),
+          cache=_opt(cache, _F32, (B, K - 1, D)))
     y = torch.empty((B, T, D), dtype=out_dtype or x.dtype, device=x.device)
     _c.call("cfm_dwconv_causal_bn_silu", _c.ptr(x), _c.dt_code(x), _c.ptr(cache), _c.ptr(w), _c.ptr(dw_bias), _c.ptr(bn_scale), _c.ptr(bn_shift), _c.ptr(y),
             _c.dt_code(y), B, T, D, K)
@@ -1462,13 +1382,8 @@ def dwconv_causal_bn_silu(x, w, dw_bias, bn_scale, bn_shift, cache=None, out_dty
 
 def conv_cache_update(x, cache, ktaps, lens=None):
     """cache <- the last ktaps-1 frames of [cache | x], or -- lens int32 [B] -- of [cache | x[:lens[b]]] per stream (unchanged at lens[b] = 0)."""
-    _c.require_hip(x, cache)
     B, T, D = x.shape
-    _dense("conv_cache_update", x=x, cache=cache)
-    if cache.dtype != torch.float32 or tuple(cache.shape) != (B, ktaps - 1, D):
-        raise ValueError("cfm.conv_cache_update: cache must be float32 [B,ktaps-1,D], got %s %s" % (cache.dtype, tuple(cache.shape)))
-    if lens is not None:
-        _stream_lens("conv_cache_update", B, lens=lens)
+    _want("conv_cache_update", x=(x, None, (B, T, D)), cache=(cache, _F32, (B, ktaps - 1, D)), lens=_opt(lens, _I32, B))
     _c.call("cfm_conv_cache_update", _c.ptr(x), _c.dt_code(x), _c.ptr(cache), _c.ptr(lens), B, T, D, ktaps)
 
 
@@ -1479,12 +1394,11 @@ def _fbank_desc(samples, tables, out, win, shift, padded, dither, seed):
     """tables: (twiddle f64, window f64, mel weights f32, start, length, offset int32) on the device (packing.fbank_tables / pack_mel_banks)."""
     tw, wnd, mw, ms, ml, mo = tables
     _c.require_hip(samples, out, *tables)
-    _dense("fbank", twiddle=tw, window=wnd, mel_w=mw, mel_start=ms, mel_len=ml, mel_off=mo)
     if samples.dim() != 2 or samples.stride(1) != 1 or samples.dtype not in (torch.int16, torch.float32):
         raise ValueError("cfm.fbank: samples must be (B, N) int16 or float32 with unit inner stride, got %s %s" % (tuple(samples.shape), samples.dtype))
+    _layout("fbank", twiddle=(tw, None, None), window=(wnd, None, None), mel_w=(mw, None, None), mel_start=(ms, None, None), mel_len=(ml, None, None), mel_off=(mo, None, None),
+            out=(out, _F32, (samples.shape[0], None, ms.numel())))
     B, rows, F = out.shape
-    if out.dtype != torch.float32 or not out.is_contiguous() or B != samples.shape[0] or F != ms.numel():
-        raise ValueError("cfm.fbank: out must be contiguous f32 (B, rows, %d), got %s %s" % (ms.numel(), tuple(out.shape), out.dtype))
     d = _c.FbankDesc()
     d.samples, d.ld, d.n_cols, d.samples_i16 = _c.ptr(samples), samples.stride(0) if B > 1 else max(samples.stride(0), samples.shape[1]), samples.shape[1], int(samples.dtype == torch.int16)
     d.twiddle, d.window, d.mel_w, d.mel_start, d.mel_len, d.mel_off, d.mel_nnz = _c.ptr(tw), _c.ptr(wnd), _c.ptr(mw), _c.ptr(ms), _c.ptr(ml), _c.ptr(mo), mw.numel()
@@ -1496,10 +1410,7 @@ def _fbank_desc(samples, tables, out, win, shift, padded, dither, seed):
 def fbank(samples, lengths, tables, out, feats_length, win, shift, padded, dither=0.0, seed=0):
     """Offline: samples (B, N) int16 | f32, lengths int32 [B] -> out f32 (B, rows, F) (rows past an item's frame count zero), feats_length int32 [B]."""
     d = _fbank_desc(samples, tables, out, win, shift, padded, dither, seed)
-    _c.require_hip(lengths, feats_length)
-    _dense("fbank", lengths=lengths, feats_length=feats_length)
-    if lengths.dtype != torch.int32 or feats_length.dtype != torch.int32 or lengths.numel() != d.B or feats_length.numel() != d.B:
-        raise ValueError("cfm.fbank: lengths and feats_length are int32 [B]")
+    _want("fbank", **_i32(d.B, lengths=lengths, feats_length=feats_length))
     d.lengths, d.feats_length = _c.ptr(lengths), _c.ptr(feats_length)
     _c.call("cfm_fbank", ctypes.byref(d))
 
@@ -1508,10 +1419,10 @@ def fbank_stream(samples, state_in, state_out, tables, out, win, shift, padded, 
     """Streaming: state_* = (carry f32 [B, carry_n], fresh int32 [B], pos int32 [B]); in is read, out is written (the caller swaps them)."""
     d = _fbank_desc(samples, tables, out, win, shift, padded, dither, seed)
     (ci, fi, pi), (co, fo, po) = state_in, state_out
-    _c.require_hip(ci, fi, pi, co, fo, po)
-    for t, dt in ((ci, torch.float32), (co, torch.float32), (fi, torch.int32), (fo, torch.int32), (pi, torch.int32), (po, torch.int32)):
-        if t.dtype != dt or not t.is_contiguous() or t.shape[0] != d.B:
-            raise ValueError("cfm.fbank_stream: state is (carry f32 [B, n], fresh int32 [B], pos int32 [B]), contiguous")
+    what = "state is (carry f32 [B, n], fresh int32 [B], pos int32 [B])"
+    _want("fbank_stream", what, carry_in=(ci, _F32, None), carry_out=(co, _F32, None), fresh_in=(fi, _I32, None), fresh_out=(fo, _I32, None), pos_in=(pi, _I32, None), pos_out=(po, _I32, None))
+    if any(t.shape[0] != d.B for t in (ci, co, fi, fo, pi, po)):                # the leading axis alone, as ever: not an extent _layout states
+        raise ValueError("cfm.fbank_stream: %s for B = %d streams" % (what, d.B))
     d.carry_in, d.fresh_in, d.pos_in, d.carry_out, d.fresh_out, d.pos_out = (_c.ptr(t) for t in (ci, fi, pi, co, fo, po))
     d.carry_n, d.hop = ci.shape[1], hop
     _c.call("cfm_fbank_stream", ctypes.byref(d))
@@ -1525,12 +1436,8 @@ def fbank_stream_ragged(samples, n_new, final, state_in, state_out, frame_lens, 
     if len(state_in) != 4 or len(state_out) != 4:
         raise ValueError("cfm.fbank_stream_ragged: state is (carry, fresh, pos, carry_len)")
     (ci, fi, pi, li), (co, fo, po, lo) = state_in, state_out
-    _c.require_hip(ci, fi, pi, li, co, fo, po, lo, n_new, final, frame_lens)
-    for name, t, dt in (("carry", ci, torch.float32), ("carry", co, torch.float32), ("fresh", fi, torch.int32), ("fresh", fo, torch.int32), ("pos", pi, torch.int32),
-                        ("pos", po, torch.int32), ("carry_len", li, torch.int32), ("carry_len", lo, torch.int32), ("n_new", n_new, torch.int32),
-                        ("final", final, torch.int32), ("frame_lens", frame_lens, torch.int32)):
-        if t.dtype != dt or not t.is_contiguous() or t.dim() != (2 if name == "carry" else 1) or t.shape[0] != d.B:
-            raise ValueError("cfm.fbank_stream_ragged: %s must be contiguous %s [%d%s], got %s %s" % (name, dt, d.B, ", cap" if name == "carry" else "", t.dtype, tuple(t.shape)))
+    _want("fbank_stream_ragged", carry_in=(ci, _F32, (d.B, None)), carry_out=(co, _F32, (d.B, None)),
+          **_i32((d.B,), fresh_in=fi, fresh_out=fo, pos_in=pi, pos_out=po, carry_len_in=li, carry_len_out=lo, n_new=n_new, final=final, frame_lens=frame_lens))
     n_first = (d.rows - 1) * shift + win
     if ci.shape != co.shape or ci.shape[1] < n_first - 1:
         raise ValueError("cfm.fbank_stream_ragged: the carry buffers are two f32 [%d, >= %d], got %s and %s" % (d.B, n_first - 1, tuple(ci.shape), tuple(co.shape)))
@@ -1544,37 +1451,37 @@ def fbank_stream_ragged(samples, n_new, final, state_in, state_out, frame_lens, 
 # ----------------------------------------------------------------------------------------------------------------------
 # sample-rate conversion (include/cfm.h cfm_resample / cfm_resample_stream, csrc/resample.hip)
 # ----------------------------------------------------------------------------------------------------------------------
-def _resample_desc(who, samples, tables, geometry, out, out_lens):
-    """tables: (taps f32, first int32 [n], offset int32 [n + 1]) on the device (packing.resample_tables); geometry: (o, n, width)."""
-    taps, first, off = tables
-    o, n, width = geometry
-    _c.require_hip(samples, out, out_lens, *tables)
-    _dense(who, taps=taps, tap_first=first, tap_off=off, out_lens=out_lens)
+def _resample_io(who, d, samples, out, out_lens):
+    """The fields cfm_resample_desc and cfm_resample_group_desc share: samples (B, N) and out (B, cap), each with its own row stride, out_lens int32 [B]."""
     if samples.dim() != 2 or (samples.shape[1] > 0 and samples.stride(1) != 1) or samples.dtype not in (torch.int16, torch.float32):
         raise ValueError("cfm.%s: samples must be (B, N) int16 or float32 with unit inner stride, got %s %s" % (who, tuple(samples.shape), samples.dtype))
     B, N = samples.shape
     if out.dim() != 2 or out.dtype != torch.float32 or out.shape[0] != B or (out.shape[1] > 0 and out.stride(1) != 1):
         raise ValueError("cfm.%s: out must be f32 (%d, cap) with unit inner stride, got %s %s" % (who, B, tuple(out.shape), out.dtype))
-    if taps.dtype != torch.float32 or first.dtype != torch.int32 or off.dtype != torch.int32 or first.numel() != n or off.numel() != n + 1:
-        raise ValueError("cfm.%s: tables are (taps f32, first int32 [%d], offset int32 [%d])" % (who, n, n + 1))
-    if out_lens.dtype != torch.int32 or out_lens.numel() != B:
-        raise ValueError("cfm.%s: out_lens is int32 [%d]" % (who, B))
+    _layout(who, **_i32(B, out_lens=out_lens))
     ld = lambda t: t.stride(0) if B > 1 and t.shape[1] > 0 else max(t.stride(0), t.shape[1])      # noqa: E731
-    d = _c.ResampleDesc()
     d.samples, d.ld, d.n_cols, d.samples_i16 = _c.ptr(samples) if N else None, ld(samples), N, int(samples.dtype == torch.int16)
+    d.out, d.ld_out, d.cap, d.out_lens, d.B = _c.ptr(out) if out.shape[1] else None, ld(out), out.shape[1], _c.ptr(out_lens), B
+    return B
+
+
+def _resample_desc(who, samples, tables, geometry, out, out_lens):
+    """tables: (taps f32, first int32 [n], offset int32 [n + 1]) on the device (packing.resample_tables); geometry: (o, n, width)."""
+    taps, first, off = tables
+    o, n, width = geometry
+    _c.require_hip(samples, out, out_lens, *tables)
+    d = _c.ResampleDesc()
+    _resample_io(who, d, samples, out, out_lens)
+    _layout(who, "tables are (taps f32, first int32 [n], offset int32 [n + 1])", taps=(taps, _F32, None), tap_first=(first, _I32, n), tap_off=(off, _I32, n + 1))
     d.taps, d.tap_first, d.tap_off, d.n_live = _c.ptr(taps), _c.ptr(first), _c.ptr(off), taps.numel()
-    d.out, d.ld_out, d.cap, d.out_lens = _c.ptr(out) if out.shape[1] else None, ld(out), out.shape[1], _c.ptr(out_lens)
-    d.B, d.o, d.n, d.width = B, o, n, width
+    d.o, d.n, d.width = o, n, width
     return d
 
 
 def resample(samples, lengths, tables, geometry, out, out_lens):
     """Offline: samples (B, N) int16 | f32, lengths int32 [B] -> out f32 (B, cap) (columns at or beyond an item's ceil(n len / o) samples zero), out_lens int32 [B]."""
     d = _resample_desc("resample", samples, tables, geometry, out, out_lens)
-    _c.require_hip(lengths)
-    _dense("resample", lengths=lengths)
-    if lengths.dtype != torch.int32 or lengths.numel() != d.B:
-        raise ValueError("cfm.resample: lengths is int32 [%d]" % d.B)
+    _want("resample", **_i32(d.B, lengths=lengths))
     d.lengths = _c.ptr(lengths)
     _c.call("cfm_resample", ctypes.byref(d))
 
@@ -1584,11 +1491,8 @@ def resample_stream(samples, n_new, final, state_in, state_out, tables, geometry
     emitted)), in is read, out is written (the caller swaps them).  out f32 (B, cap >= 0) receives each stream's new samples left-aligned, out_lens their count."""
     d = _resample_desc("resample_stream", samples, tables, geometry, out, out_lens)
     (ti, ci), (to, co) = state_in, state_out
-    _c.require_hip(n_new, final, ti, ci, to, co)
-    for name, t, dt, shape in (("tail", ti, torch.float32, None), ("tail", to, torch.float32, None), ("counts", ci, torch.int64, (d.B, 2)), ("counts", co, torch.int64, (d.B, 2)),
-                               ("n_new", n_new, torch.int32, (d.B,)), ("final", final, torch.int32, (d.B,))):
-        if t.dtype != dt or not t.is_contiguous() or (tuple(t.shape) != shape if shape else t.dim() != 2 or t.shape[0] != d.B):
-            raise ValueError("cfm.resample_stream: %s must be contiguous %s %s, got %s %s" % (name, dt, shape or "[%d, tail_cap]" % d.B, t.dtype, tuple(t.shape)))
+    _want("resample_stream", tail_in=(ti, _F32, (d.B, None)), tail_out=(to, _F32, (d.B, None)), counts_in=(ci, _I64, (d.B, 2)), counts_out=(co, _I64, (d.B, 2)),
+          **_i32((d.B,), n_new=n_new, final=final))
     if ti.shape != to.shape or ti.shape[1] < 2 * d.width + d.o:
         raise ValueError("cfm.resample_stream: the tail buffers are two f32 [%d, >= %d], got %s and %s" % (d.B, 2 * d.width + d.o, tuple(ti.shape), tuple(to.shape)))
     if len({t.data_ptr() for t in (ti, to)}) != 2 or len({t.data_ptr() for t in (ci, co)}) != 2:
@@ -1606,28 +1510,17 @@ def resample_group(samples, lengths, bank, tables, banks, out, out_lens):
     (o, n, width, n_live, taps_at, first_at, off_at, tile_blocks) (packing.resample_group_tables) -> out f32 (B, cap), out_lens int32 [B]."""
     taps, first, off = tables if tables is not None else (None, None, None)
     _c.require_hip(samples, lengths, bank, out, out_lens, taps, first, off)
-    _dense("resample_group", lengths=lengths, bank=bank, taps=taps, tap_first=first, tap_off=off, out_lens=out_lens)
-    if samples.dim() != 2 or (samples.shape[1] > 0 and samples.stride(1) != 1) or samples.dtype not in (torch.int16, torch.float32):
-        raise ValueError("cfm.resample_group: samples must be (B, N) int16 or float32 with unit inner stride, got %s %s" % (tuple(samples.shape), samples.dtype))
-    B, N = samples.shape
-    if out.dim() != 2 or out.dtype != torch.float32 or out.shape[0] != B or (out.shape[1] > 0 and out.stride(1) != 1):
-        raise ValueError("cfm.resample_group: out must be f32 (%d, cap) with unit inner stride, got %s %s" % (B, tuple(out.shape), out.dtype))
-    for name, t in (("lengths", lengths), ("bank", bank), ("out_lens", out_lens)):
-        if t.dtype != torch.int32 or t.numel() != B:
-            raise ValueError("cfm.resample_group: %s is int32 [%d], got %s %s" % (name, B, t.dtype, tuple(t.shape)))
+    d = _c.ResampleGroupDesc()
+    B = _resample_io("resample_group", d, samples, out, out_lens)
+    _layout("resample_group", **_i32(B, lengths=lengths, bank=bank))
     if not 1 <= len(banks) <= _c.RESAMPLE_MAX_BANKS:
         raise ValueError("cfm.resample_group: %d banks, 1 .. %d" % (len(banks), _c.RESAMPLE_MAX_BANKS))
-    if tables is not None and (taps.dtype != torch.float32 or first.dtype != torch.int32 or off.dtype != torch.int32):
-        raise ValueError("cfm.resample_group: tables are (taps f32, first int32, offset int32)")
-    if tables is None and any(row[0] != row[1] for row in banks):
-        raise ValueError("cfm.resample_group: a bank that converts needs the tables")
-    ld = lambda t: t.stride(0) if B > 1 and t.shape[1] > 0 else max(t.stride(0), t.shape[1])      # noqa: E731
-    d = _c.ResampleGroupDesc()
-    d.samples, d.ld, d.n_cols, d.samples_i16 = _c.ptr(samples) if N else None, ld(samples), N, int(samples.dtype == torch.int16)
-    d.lengths, d.bank, d.G = _c.ptr(lengths), _c.ptr(bank), len(banks)
     if tables is not None:
+        _layout("resample_group", "tables are (taps f32, first int32, offset int32)", taps=(taps, _F32, None), tap_first=(first, _I32, None), tap_off=(off, _I32, None))
         d.taps, d.tap_first, d.tap_off, d.n_taps, d.n_first, d.n_off = _c.ptr(taps), _c.ptr(first), _c.ptr(off), taps.numel(), first.numel(), off.numel()
-    d.out, d.ld_out, d.cap, d.out_lens, d.B = _c.ptr(out) if out.shape[1] else None, ld(out), out.shape[1], _c.ptr(out_lens), B
+    elif any(row[0] != row[1] for row in banks):
+        raise ValueError("cfm.resample_group: a bank that converts needs the tables")
+    d.lengths, d.bank, d.G = _c.ptr(lengths), _c.ptr(bank), len(banks)
     for g, row in enumerate(banks):
         d.banks[g] = _c.ResampleBank(*(int(v) for v in row))
     _c.call("cfm_resample_group", ctypes.byref(d))
@@ -1637,15 +1530,11 @@ def spec_augment(feats, lengths, ids, seed, num_t_mask, num_f_mask, max_t, max_f
     """SpecAugment in place: feats f32 (B, T_max, F) with unit inner stride (any row and item stride), lengths int32 [B], ids int32 [B] read as uint32 or
     None (ids[b] = b), masks int32 (B, num_t_mask + num_f_mask, 2) or None receives (start, end).  include/cfm.h cfm_spec_augment states the draws."""
     _c.require_hip(feats, lengths, ids, masks)
-    _dense("spec_augment", lengths=lengths, ids=ids, masks=masks)
     if feats.dim() != 3 or feats.dtype != torch.float32 or (feats.shape[2] > 1 and feats.stride(2) != 1):
         raise ValueError("cfm.spec_augment: feats must be f32 (B, T_max, F) with unit inner stride, got %s %s strides %s" % (tuple(feats.shape), feats.dtype, feats.stride()))
     B, T, F = feats.shape
     nm = int(num_t_mask) + int(num_f_mask)
-    if lengths.dtype != torch.int32 or lengths.numel() != B or (ids is not None and (ids.dtype != torch.int32 or ids.numel() != B)):
-        raise ValueError("cfm.spec_augment: lengths and ids are int32 [%d]" % B)
-    if masks is not None and (masks.dtype != torch.int32 or tuple(masks.shape) != (B, nm, 2)):
-        raise ValueError("cfm.spec_augment: masks is int32 (%d, %d, 2), got %s %s" % (B, nm, masks.dtype, tuple(masks.shape)))
+    _layout("spec_augment", lengths=(lengths, _I32, B), ids=_opt(ids, _I32, B), masks=_opt(masks, _I32, (B, nm, 2)))
     d = _c.SpecAugmentDesc()
     d.feats, d.lengths, d.ids, d.masks = _c.ptr(feats) if T and F else None, _c.ptr(lengths), _c.ptr(ids), _c.ptr(masks)
     d.row_stride = feats.stride(1) if T > 1 else max(feats.stride(1), F)
@@ -1658,9 +1547,7 @@ def spec_augment(feats, lengths, ids, seed, num_t_mask, num_f_mask, max_t, max_f
 def _lstm_desc(who, x, weights, H, drop):
     """The shape checks and the fields the forward and the backward share.  weights: per layer (w_ih, w_hh, b_ih | None, b_hh | None)."""
     L = len(weights)
-    if x.dim() != 3 or x.dtype != torch.float32:
-        raise ValueError("cfm.%s: x must be float32 [B, U, in], got %s %s" % (who, tuple(x.shape), x.dtype))
-    _dense(who, x=x)
+    _layout(who, "x is [B, U, in]", x=(x, _F32, (None, None, None)))
     B, U, I = x.shape
     if not 1 <= L <= 4 or H % 64 or I % 64 or not 64 <= H <= 512 or not 64 <= I <= 512 or B < 1 or U < 1:
         raise ValueError("cfm.%s: 1-4 layers, hidden and input size multiples of 64 up to 512, B >= 1, U >= 1 (layers=%d in=%d H=%d B=%d U=%d): "
@@ -1671,11 +1558,8 @@ def _lstm_desc(who, x, weights, H, drop):
         d.drop_p, d.seed = float(drop[0]), int(drop[1]) & 0xFFFFFFFF
     d.x = _c.ptr(x)
     for l, (w_ih, w_hh, b_ih, b_hh) in enumerate(weights):
-        _c.require_hip(w_ih, w_hh, b_ih, b_hh)
-        _dense(who, w_ih=w_ih, w_hh=w_hh, b_ih=b_ih, b_hh=b_hh)
-        if tuple(w_ih.shape) != (4 * H, I if l == 0 else H) or tuple(w_hh.shape) != (4 * H, H) or any(t.dtype != torch.float32 for t in (w_ih, w_hh)) or \
-                any(b is not None and (b.dtype != torch.float32 or b.numel() != 4 * H) for b in (b_ih, b_hh)):
-            raise ValueError("cfm.%s: layer %d: expected float32 weight_ih [4H, in], weight_hh [4H, H], biases [4H]" % (who, l))
+        _want(who, "layer %d of float32 weight_ih [4H, in], weight_hh [4H, H], biases [4H]" % l, w_ih=(w_ih, _F32, (4 * H, I if l == 0 else H)), w_hh=(w_hh, _F32, (4 * H, H)),
+              b_ih=_opt(b_ih, _F32, 4 * H), b_hh=_opt(b_hh, _F32, 4 * H))
         d.w_ih[l], d.w_hh[l], d.b_ih[l], d.b_hh[l] = _c.ptr(w_ih), _c.ptr(w_hh), _c.ptr(b_ih), _c.ptr(b_hh)
     return d, B, U, I, L
 
@@ -1684,7 +1568,7 @@ def _lstm_state(who, name, t, L, B, H):
     if t is None:
         return None
     _c.require_hip(t)
-    if tuple(t.shape) != (L, B, H) or t.dtype != torch.float32:
+    if tuple(t.shape) != (L, B, H) or t.dtype != torch.float32:           # by hand: a strided state is copied, not refused, which _layout does not state
         raise ValueError("cfm.%s: %s must be float32 [layers, B, H] = (%d, %d, %d), got %s %s" % (who, name, L, B, H, tuple(t.shape), t.dtype))
     return t.contiguous()
 
@@ -1702,9 +1586,10 @@ def lstm_forward(x, weights, H, h0=None, c0=None, drop=None, out=None):
         saves = [torch.empty(n, dtype=torch.float32, device=x.device) for _ in range(L)]
     else:
         y, hn, cn, saves = out
-        if tuple(y.shape) != (B, U, H) or tuple(hn.shape) != (L, B, H) or tuple(cn.shape) != (L, B, H) or len(saves) != L or any(s.numel() != n for s in saves):
-            raise ValueError("cfm.lstm_forward: out does not match (y [B,U,H], hn, cn [layers,B,H], %d save blocks of %d floats)" % (L, n))
-        _dense("lstm_forward", y=y, hn=hn, cn=cn, **{"save%d" % i: s for i, s in enumerate(saves)})
+        what = "out is (y [B,U,H], hn, cn [layers,B,H], %d save blocks of %d floats)" % (L, n)
+        if len(saves) != L:
+            raise ValueError("cfm.lstm_forward: %s, got %d blocks" % (what, len(saves)))
+        _layout("lstm_forward", what, y=(y, None, (B, U, H)), hn=(hn, None, (L, B, H)), cn=(cn, None, (L, B, H)), **{"save%d" % i: (s, None, n) for i, s in enumerate(saves)})
     d.h0, d.c0, d.y, d.hn, d.cn = _c.ptr(h0), _c.ptr(c0), _c.ptr(y), _c.ptr(hn), _c.ptr(cn)
     for l in range(L):
         d.save[l] = _c.ptr(saves[l])
@@ -1718,13 +1603,14 @@ def lstm_backward(x, weights, H, saves, dy, dhn=None, dcn=None, drop=None, out=N
     into; work: (dg [U*B, 4H], dyl [U*B, H] | None)."""
     _c.require_hip(x, dy, dhn, dcn, *saves)
     d, B, U, I, L = _lstm_desc("lstm_backward", x, weights, H, drop)
-    if tuple(dy.shape) != (B, U, H) or dy.dtype != torch.float32:
+    if tuple(dy.shape) != (B, U, H) or dy.dtype != torch.float32:         # by hand, as _lstm_state: a strided dy is copied
         raise ValueError("cfm.lstm_backward: dy must be float32 [B, U, H] = (%d, %d, %d), got %s %s" % (B, U, H, tuple(dy.shape), dy.dtype))
     dy = dy.contiguous()
     dhn, dcn = _lstm_state("lstm_backward", "dhn", dhn, L, B, H), _lstm_state("lstm_backward", "dcn", dcn, L, B, H)
     n = int(_c.lib().cfm_lstm_save_floats(B, U, H))
-    if len(saves) != L or any(s.numel() != n or s.dtype != torch.float32 or not s.is_contiguous() for s in saves):
-        raise ValueError("cfm.lstm_backward: saves must be the forward's %d blocks of %d floats" % (L, n))
+    if len(saves) != L:
+        raise ValueError("cfm.lstm_backward: saves must be the forward's %d blocks of %d floats, got %d blocks" % (L, n, len(saves)))
+    _layout("lstm_backward", "saves are the forward's %d blocks of %d floats" % (L, n), **{"save%d" % i: (s, _F32, n) for i, s in enumerate(saves)})
     dev = x.device
     if out is None:
         def e(*shape):
@@ -1732,20 +1618,21 @@ def lstm_backward(x, weights, H, saves, dy, dhn=None, dcn=None, drop=None, out=N
         grads = [(e(*w[0].shape), e(*w[1].shape), None if w[2] is None else e(4 * H), None if w[3] is None else e(4 * H)) for w in weights]
         out = (e(B, U, I), grads, e(L, B, H), e(L, B, H))
     dx, grads, dh0, dc0 = out
-    if tuple(dx.shape) != (B, U, I) or tuple(dh0.shape) != (L, B, H) or tuple(dc0.shape) != (L, B, H) or len(grads) != L:
-        raise ValueError("cfm.lstm_backward: out does not match (dx [B,U,in], per-layer gradients, dh0, dc0 [layers,B,H])")
-    _dense("lstm_backward", dx=dx, dh0=dh0, dc0=dc0)
+    what = "out is (dx [B,U,in], per-layer gradients, dh0, dc0 [layers,B,H])"
+    if len(grads) != L:
+        raise ValueError("cfm.lstm_backward: %s, got gradients for %d layers" % (what, len(grads)))
+    _layout("lstm_backward", what, dx=(dx, None, (B, U, I)), dh0=(dh0, None, (L, B, H)), dc0=(dc0, None, (L, B, H)))
     for l, (gw, w) in enumerate(zip(grads, weights)):
-        for g_, w_ in zip(gw, w):
-            if (g_ is None) != (w_ is None) or (g_ is not None and (g_.shape != w_.shape or g_.dtype != torch.float32 or not g_.is_contiguous())):
-                raise ValueError("cfm.lstm_backward: layer %d: a gradient does not match its parameter" % l)
+        if any(g_ is not None and w_ is None for g_, w_ in zip(gw, w)):
+            raise ValueError("cfm.lstm_backward: layer %d: a gradient for a bias the layer does not have" % l)
+        _layout("lstm_backward", "layer %d: a gradient matches its parameter" % l,
+                **{k: (g_, _F32, tuple(w_.shape)) for k, g_, w_ in zip(("dw_ih", "dw_hh", "db_ih", "db_hh"), gw, w) if w_ is not None})
         d.dw_ih[l], d.dw_hh[l], d.db_ih[l], d.db_hh[l] = (_c.ptr(g_) for g_ in gw)
         d.save[l] = _c.ptr(saves[l])
     if work is None:
         work = (torch.empty((U * B, 4 * H), dtype=torch.float32, device=dev), torch.empty((U * B, H), dtype=torch.float32, device=dev) if L > 1 else None)
     dg, dyl = work
-    if tuple(dg.shape) != (U * B, 4 * H) or not dg.is_contiguous() or (L > 1 and (dyl is None or tuple(dyl.shape) != (U * B, H) or not dyl.is_contiguous())):
-        raise ValueError("cfm.lstm_backward: work must be (dg [U*B, 4H], dyl [U*B, H])")
+    _layout("lstm_backward", "work is (dg [U*B, 4H], dyl [U*B, H])", dg=(dg, None, (U * B, 4 * H)), dyl=(dyl, None, (U * B, H)) if L > 1 else None)
     d.dy, d.dhn, d.dcn, d.dx, d.dh0, d.dc0, d.dg, d.dyl = _c.ptr(dy), _c.ptr(dhn), _c.ptr(dcn), _c.ptr(dx), _c.ptr(dh0), _c.ptr(dc0), _c.ptr(dg), _c.ptr(dyl)
     _c.call("cfm_lstm_backward", ctypes.byref(d))
     return dx, grads, dh0, dc0
@@ -1759,20 +1646,12 @@ def rescore_prep(tokens, nlen, score, embed, pe, sos, eos, embed_r=None):
     score f32 [B,N]; embed (and embed_r: the right decoder's table, for the reversed hypotheses) f32 [V,D], pe f32 [>= Lmax + 1, D].
     Returns (x0 f32 [P*Lc, D], targets int32 [P, Lc], mask uint8 [P, Lc, Lc], x0_r | None, targets_r | None), P = B*N, Lc = Lmax + 1."""
     _c.require_hip(tokens, nlen, score, embed, pe, embed_r)
-    _dense("rescore_prep", tokens=tokens, nlen=nlen, score=score, embed=embed, pe=pe, embed_r=embed_r)
-    if tokens.dim() != 3 or tokens.dtype != torch.int32 or nlen.dtype != torch.int32 or score.dtype != torch.float32:
-        raise ValueError("cfm.rescore_prep: tokens int32 [B,N,Lmax], nlen int32 [B,N], score float32 [B,N]")
-    B, N, Lmax = tokens.shape
-    if tuple(nlen.shape) != (B, N) or tuple(score.shape) != (B, N):
-        raise ValueError("cfm.rescore_prep: nlen %s and score %s must be [B,N] = (%d,%d)" % (tuple(nlen.shape), tuple(score.shape), B, N))
-    if embed.dim() != 2 or embed.dtype != torch.float32 or pe.dtype != torch.float32 or pe.dim() != 2 or pe.shape[1] != embed.shape[1]:
-        raise ValueError("cfm.rescore_prep: embed float32 [V,D] and pe float32 [rows,D]")
-    V, D = embed.shape
+    _layout("rescore_prep", "tokens is [B,N,Lmax] and embed [V,D]", tokens=(tokens, _I32, (None, None, None)), embed=(embed, _F32, (None, None)))
+    (B, N, Lmax), (V, D) = tokens.shape, embed.shape
+    _layout("rescore_prep", "[B,N] and D as tokens and embed have them", nlen=(nlen, _I32, (B, N)), score=(score, _F32, (B, N)), pe=(pe, _F32, (None, D)), embed_r=_opt(embed_r, _F32, (V, D)))
     Lc = Lmax + 1
     if pe.shape[0] < Lc:
         raise ValueError("cfm.rescore_prep: %d positions but the position table has %d rows" % (Lc, pe.shape[0]))
-    if embed_r is not None and (embed_r.shape != embed.shape or embed_r.dtype != torch.float32):
-        raise ValueError("cfm.rescore_prep: embed_r must match embed")
     dev, P = tokens.device, B * N
     x0 = torch.empty((P * Lc, D), dtype=torch.float32, device=dev)
     targets = torch.empty((P, Lc), dtype=torch.int32, device=dev)
@@ -1793,9 +1672,7 @@ def token_logprob(x, w, bias, target, V, logits=None, want_lse=False, out=None):
     logits f32 [M, >= V] (unit inner stride): the reduction and the gather alone over stored logits (x, w, bias may be None).
     Returns logp f32 [M], or (logp, lse) with want_lse."""
     _c.require_hip(x, w, bias, target, logits, out)
-    _dense("token_logprob", w=w, bias=bias, target=target, out=out)
-    if target.dtype != torch.int32 or target.dim() != 1:
-        raise ValueError("cfm.token_logprob: target must be int32 [M]")
+    _layout("token_logprob", w=_opt(w, None, None), bias=_opt(bias, None, None), target=(target, _I32, (None,)), out=_opt(out, _F32, target.numel()))
     M = target.numel()
     d = _c.TokenLogprobDesc()
     if logits is not None:
@@ -1810,8 +1687,6 @@ def token_logprob(x, w, bias, target, V, logits=None, want_lse=False, out=None):
         d.X, d.W, d.bias, d.ldx = _c.ptr(x), _c.ptr(w), _c.ptr(bias), x.stride(0) if M > 1 else max(x.stride(0), x.shape[1])
         d.D, d.x_dtype, d.w_dtype = x.shape[1], _c.dt_code(x), _c.dt_code(w)
     logp = out if out is not None else torch.empty((M,), dtype=torch.float32, device=target.device)
-    if logp.dtype != torch.float32 or logp.numel() != M:
-        raise ValueError("cfm.token_logprob: out must be float32 [M]")
     lse = torch.empty((M,), dtype=torch.float32, device=target.device) if want_lse else None
     d.target, d.logp, d.lse, d.M, d.V = _c.ptr(target), _c.ptr(logp), _c.ptr(lse), M, int(V)
     _c.call("cfm_token_logprob", ctypes.byref(d))
@@ -1822,13 +1697,11 @@ def rescore_combine(logp, nlen, score, first_pass_weight, reverse_weight=0.0, lo
     """Per-hypothesis sums of the token log-probabilities, the weighted scores and each utterance's ranking in one launch (include/cfm.h
     cfm_rescore_combine).  logp (and logp_r) f32 [B*N*Lc], nlen int32 [B,N], score f32 [B,N].  Returns (final, left, right f32 [B,N],
     order int32 [B,N]: the hypothesis index of each rank) on the device."""
-    _c.require_hip(logp, nlen, score, logp_r)
-    _dense("rescore_combine", logp=logp, nlen=nlen, score=score, logp_r=logp_r)
-    if nlen.dim() != 2 or nlen.dtype != torch.int32 or score.dtype != torch.float32 or score.shape != nlen.shape or logp.dtype != torch.float32:
-        raise ValueError("cfm.rescore_combine: nlen int32 [B,N], score float32 [B,N], logp float32")
+    _want("rescore_combine", "nlen and score are [B,N], logp_r holds as many values as logp", nlen=(nlen, _I32, (None, None)), score=(score, _F32, tuple(nlen.shape)),
+          logp=(logp, _F32, None), logp_r=_opt(logp_r, _F32, logp.numel()))
     B, N = nlen.shape
-    if logp.numel() % (B * N) or logp.numel() == 0 or (logp_r is not None and (logp_r.numel() != logp.numel() or logp_r.dtype != torch.float32)):
-        raise ValueError("cfm.rescore_combine: logp holds %d values, not a multiple of B*N = %d (logp_r must match it)" % (logp.numel(), B * N))
+    if logp.numel() % (B * N) or logp.numel() == 0:
+        raise ValueError("cfm.rescore_combine: logp holds %d values, not a positive multiple of B*N = %d" % (logp.numel(), B * N))
     dev = logp.device
     final, left, right = (torch.empty((B, N), dtype=torch.float32, device=dev) for _ in range(3))
     order = torch.empty((B, N), dtype=torch.int32, device=dev)

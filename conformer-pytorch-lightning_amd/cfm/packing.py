@@ -577,6 +577,32 @@ def fbank_tables(win, padded):
     return twiddle, window
 
 
+def host_packets(owner, B, sample_lens, final, columns, upto=None):
+    """The (sample_lens, final) of one streaming audio step as lists of B ints / bools, or ValueError: host values only (a list or a CPU tensor of
+    integers; the host mirrors the streams' bookkeeping from them), B of each, every count in 0 .. columns (no upper bound with columns None;
+    `upto` then names the bound in the message).  sample_lens None: `columns` for every stream; final None: all False.  fbank.PacketSchedule and
+    resample.StreamingResampler share it."""
+    vals = []
+    for name, v, default in (("sample_lens", sample_lens, columns), ("final", final, False)):
+        if v is None:
+            v = [default] * B
+        if isinstance(v, torch.Tensor):
+            if v.device.type != "cpu":
+                raise ValueError("%s: %s are host values (a list or a CPU tensor), the host mirrors the streams' bookkeeping; got a tensor on %s" % (owner, name, v.device))
+            if v.dim() != 1 or v.dtype.is_floating_point or v.dtype.is_complex:
+                raise ValueError("%s: %s must hold %d integers, got %s %s" % (owner, name, B, v.dtype, tuple(v.shape)))
+            v = v.tolist()
+        v = list(v)
+        if len(v) != B:
+            raise ValueError("%s: %d %s for %d streams" % (owner, len(v), name, B))
+        vals.append(v)
+    lens, final = vals
+    for b, n in enumerate(lens):
+        if n is None or int(n) != n or n < 0 or (columns is not None and n > columns):
+            raise ValueError("%s: sample_lens[%d] = %r: a count of new samples, 0 .. %s" % (owner, b, n, upto or "the block's %d columns" % columns))
+    return [int(n) for n in lens], [bool(f) for f in final]
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # sample-rate conversion tables (csrc/resample.hip): host float64, no module, no cache -- resample.Resampler builds them once
 # ----------------------------------------------------------------------------------------------------------------------

@@ -100,29 +100,12 @@ class PacketSchedule:
 
     def check(self, sample_lens, final, columns=None):
         """(sample_lens, final) as lists of B ints / bools, or ValueError: host values only, and no stream may be overfilled."""
-        vals = []
-        for name, v, default in (("sample_lens", sample_lens, columns), ("final", final, False)):
-            if v is None:
-                v = [default] * self.B
-            if isinstance(v, torch.Tensor):
-                if v.device.type != "cpu":
-                    raise ValueError("StreamingFbank: %s are host values (a list or a CPU tensor), the host mirrors the streams' bookkeeping; got a tensor on %s" % (name, v.device))
-                if v.dim() != 1 or v.dtype.is_floating_point or v.dtype.is_complex:
-                    raise ValueError("StreamingFbank: %s must hold %d integers, got %s %s" % (name, self.B, v.dtype, tuple(v.shape)))
-                v = v.tolist()
-            v = list(v)
-            if len(v) != self.B:
-                raise ValueError("StreamingFbank: %d %s for %d streams" % (len(v), name, self.B))
-            vals.append(v)
-        lens, final = vals
-        for b, n in enumerate(lens):
-            if n is None or int(n) != n or n < 0 or (columns is not None and n > columns):
-                raise ValueError("StreamingFbank: sample_lens[%d] = %r: a count of new samples, 0 .. %s" % (b, n, "the block's %d columns" % columns if columns is not None else "accepts()"))
-            room = self.n_first + self.n_next - 1 - self.carry[b]
+        lens, final = packing.host_packets("StreamingFbank", self.B, sample_lens, final, columns, upto=None if columns is not None else "accepts()")
+        for b, (n, room) in enumerate(zip(lens, self.accepts())):
             if n > room:
                 raise ValueError("StreamingFbank: stream %d is handed %d samples and accepts %d (it holds %d; a call runs one window, %d new samples, per stream)"
                                  % (b, n, room, self.carry[b], self.n_next))
-        return [int(n) for n in lens], [bool(f) for f in final]
+        return lens, final
 
     def advance(self, sample_lens, final):
         """One call: -> per stream (first frame, frames) of the window it runs, frames = 0 where it runs none.  The arguments went through check()."""

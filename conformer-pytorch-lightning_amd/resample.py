@@ -136,23 +136,7 @@ class StreamingResampler:
 
     def check(self, sample_lens, final, columns):
         """(sample_lens, final) as lists of B ints / bools, or ValueError: host values only."""
-        vals = []
-        for name, v, default in (("sample_lens", sample_lens, columns), ("final", final, False)):
-            if v is None:
-                v = [default] * self.B
-            if isinstance(v, torch.Tensor):
-                if v.device.type != "cpu":
-                    raise ValueError("StreamingResampler: %s are host values (a list or a CPU tensor), the host mirrors the streams' bookkeeping; got a tensor on %s" % (name, v.device))
-                v = v.tolist()
-            v = list(v)
-            if len(v) != self.B:
-                raise ValueError("StreamingResampler: %d %s for %d streams" % (len(v), name, self.B))
-            vals.append(v)
-        lens, final = vals
-        for b, n in enumerate(lens):
-            if n is None or int(n) != n or n < 0 or n > columns:
-                raise ValueError("StreamingResampler: sample_lens[%d] = %r: a count of new samples, 0 .. the block's %d columns" % (b, n, columns))
-        return [int(n) for n in lens], [bool(f) for f in final]
+        return packing.host_packets("StreamingResampler", self.B, sample_lens, final, columns)
 
     def produces(self, sample_lens, final=None):
         return self.schedule.produces(sample_lens, final if final is not None else [False] * self.B)
