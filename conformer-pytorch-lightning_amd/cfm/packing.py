@@ -47,6 +47,37 @@ def graph_watch(owner):
     return _EPOCH[0], v, s.key, str(_c.resolve_precision(owner.enc))
 
 
+def capture_step(run, dev, state, idle=None):
+    """run() -- one step of a streaming stage on device buffers -- captured in a HIP graph: returns (graph, what the captured run() returned).
+    state: the tensors run() changes (None entries are skipped); they hold their bits from before the call when it returns.  idle: called
+    before the warm-up, after the state is saved -- puts the step in a form whose warm-up changes nothing outside `state`.
+    One protocol for every captured step: a side stream waits on the current one; on it the state is cloned, idle() and the warm-up run() are
+    run, the stream is synchronised, the state is put back, run() is captured ON THAT STREAM and the state is put back again; the current stream
+    then waits on the side stream.  Warm-up and capture share a stream because the scratch arena is per (device, stream): a warm-up elsewhere
+    would size another stream's arena and leave the capture to allocate.  The graph holds the addresses of everything run() touches: whoever
+    replaces one of them drops the graph."""
+    state = [t for t in state if t is not None]
+    stream = torch.cuda.Stream(device=dev)
+    stream.wait_stream(torch.cuda.current_stream(dev))
+    with torch.no_grad(), torch.cuda.stream(stream):
+        saved = [t.clone() for t in state]
+
+        def restore():
+            for t, s in zip(state, saved):
+                t.copy_(s)
+        if idle is not None:
+            idle()
+        run()                                                           # warm-up: sizes this stream's arena, allocator, lazy init
+        stream.synchronize()
+        restore()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=stream):
+            out = run()
+        restore()                                                       # (capture does not execute, but keep the state explicit)
+    torch.cuda.current_stream(dev).wait_stream(stream)
+    return graph, out
+
+
 class Packed:
     """Attribute bag of packed tensors (keeps them alive while raw pointers are in flight)."""
 
@@ -601,6 +632,48 @@ def host_packets(owner, B, sample_lens, final, columns, upto=None):
         if n is None or int(n) != n or n < 0 or (columns is not None and n > columns):
             raise ValueError("%s: sample_lens[%d] = %r: a count of new samples, 0 .. %s" % (owner, b, n, upto or "the block's %d columns" % columns))
     return [int(n) for n in lens], [bool(f) for f in final]
+
+
+def stream_lens(owner, name, B, value, bound, buf, default=None, strict=False):
+    """One per-stream count of a streaming step (frames of a window, frames of a chunk, a final flag) read into the persistent device buffer
+    `buf` ([B], any integer dtype) that the step reads; buf None: checked only, nothing written.  Returns the B counts as a list of ints when
+    the host knows them, None when `value` is a device tensor (it stays on the device: no synchronisation).
+      * value None: `default` (`bound` when None) for every stream.
+      * host values (a list / iterable or a CPU tensor) and a device tensor alike: another count than B -> ValueError.
+      * strict=False (the decoders): a host value is truncated to an int and clamped to 0 .. bound; a tensor may have any shape of B elements.
+      * strict=True (StreamingBatch: the host mirrors the streams' offsets from these): a host value that is not a whole number in 0 .. bound
+        -> ValueError; a tensor is 1-d int32 / int64, else ValueError.
+      * a device tensor is never read on the host: its values are clamped to 0 .. bound on the device, in either mode."""
+    if value is None:
+        fill = bound if default is None else default
+        if buf is not None:
+            buf.fill_(fill)
+        return [fill] * B
+    if isinstance(value, torch.Tensor):
+        if value.numel() != B or (strict and (value.dim() != 1 or value.dtype not in (torch.int32, torch.int64))):
+            raise ValueError("%s: %s must hold %d integers, got %s %s" % (owner, name, B, value.dtype, tuple(value.shape)))
+        if value.device.type != "cpu":
+            if buf is not None:
+                buf.copy_((value if value.dtype in (torch.int32, torch.int64) else value.to(torch.int64)).reshape(B).clamp(0, bound))
+            return None
+        host = value.reshape(B).tolist()
+    else:
+        host = list(value)
+    if len(host) != B:
+        raise ValueError("%s: %d %s for %d streams" % (owner, len(host), name, B))
+    if strict:
+        for b, n in enumerate(host):
+            if int(n) != n or not 0 <= n <= bound:
+                raise ValueError("%s: %s[%d] = %r, outside 0 .. %d" % (owner, name, b, n, bound))
+    host = [min(max(int(n), 0), bound) for n in host]
+    if buf is not None:
+        buf.copy_(torch.tensor(host, dtype=buf.dtype))
+    return host
+
+
+def stream_index(streams, dev):
+    """What a reset indexes per-stream state with: every stream (streams None) or the given ones, as a long tensor on dev."""
+    return slice(None) if streams is None else torch.as_tensor(list(streams), dtype=torch.long, device=dev)
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -184,13 +184,15 @@ class CTCGreedyStream:
             raise ValueError("CTCGreedyStream: streams is positive")
         self.dev = ctc.ctc_lo.weight.device
         self.S = cfm.ctc_greedy_state(self.B, max(1, int(max_tokens) if max_tokens is not None else 256), self.dev) if self.dev.type == "cuda" else None
+        self._lens = torch.zeros((self.B,), dtype=torch.int32, device=self.dev)         # this chunk's frames per stream, as the kernels read them
         self._log = token_log.TokenLog(self.B)
 
     def reset(self, streams=None):
         """New utterances on the given streams (all by default): no previous class, frame 0, hypotheses emptied."""
         if self.S is None:
             raise RuntimeError("cfm: CTCGreedyStream on %s -- this framework runs on MI355X (HIP) only; there is no CPU path" % self.dev)
-        idx = slice(None) if streams is None else torch.as_tensor(list(streams), dtype=torch.long, device=self.dev)
+        streams = None if streams is None else list(streams)
+        idx = packing.stream_index(streams, self.dev)
         self.S["prev"][idx] = -1
         for k in ("frame_base", "count", "hyps", "frames", "token_logp"):
             self.S[k][idx] = 0
@@ -211,12 +213,9 @@ class CTCGreedyStream:
         if enc_chunk.dim() != 3 or enc_chunk.shape[0] != B or enc_chunk.device != self.dev:
             raise ValueError("CTCGreedyStream.decode wants (%d, C, D) on %s, got %s on %s" % (B, self.dev, tuple(enc_chunk.shape), enc_chunk.device))
         C = enc_chunk.shape[1]
-        if lens is None:
-            lens = torch.full((B,), C, dtype=torch.int32, device=self.dev)
-        elif not isinstance(lens, torch.Tensor) and len(lens) != B:
-            raise ValueError("CTCGreedyStream.decode: %d lens for %d streams" % (len(lens), B))
+        packing.stream_lens("CTCGreedyStream.decode", "lens", B, lens, C, self._lens)   # clamped to 0 .. C here as the kernels clamp them
         token_log.grow(self.S, ("hyps", "frames", "token_logp"), self._log.most() + C)
-        idx, logp, _, lens, V = self.ctc._topk(enc_chunk, lens, 1, "greedy_search")
+        idx, logp, _, lens, V = self.ctc._topk(enc_chunk, self._lens, 1, "greedy_search")
         cfm.ctc_greedy(idx, logp, lens, V, blank=self.blank, state=self.S)
         rep = torch.cat([self.S["count"], self.S["overflow"].to(torch.int64)]).tolist()
         counts, overflow = rep[:B], rep[B]

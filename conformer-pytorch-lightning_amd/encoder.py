@@ -290,6 +290,13 @@ class ConformerEncoder(nn.Module):
         return out, torch.ones((out.size(0), 1, out.size(1)))
 
 
+def _weights_moved(owner):
+    """Whether owner.enc's weights (packing.graph_watch) differ from those of the last call, which it records in owner._sig: asked before every
+    replay -- a captured graph holds raw pointers to the packed weights of its capture and is dropped then -- and called after every capture."""
+    sig, owner._sig = owner._sig, packing.graph_watch(owner)
+    return sig != owner._sig
+
+
 class StreamingSession:
     """B streams advanced in lockstep, chunk by chunk, with ONE captured HIP graph per steady-state step.
 
@@ -309,7 +316,7 @@ class StreamingSession:
         self.hop = 4 * decoding_chunk_size
         self.offset = 0
         self.cache = None
-        self.graph = None
+        self.graph = self._sig = None
         self.relative = isinstance(encoder.position_encoding, RelativePositionalEncoding)
 
     def _abs_rows(self, batch, dev):
@@ -322,7 +329,7 @@ class StreamingSession:
             raise ValueError("StreamingSession.step wants windows of %d frames" % self.window)
         dev = frames.device
         empty = torch.zeros((0, 0, 0, 0), device=dev)
-        if self.graph is not None and packing.graph_watch(self) != self._sig:
+        if self.graph is not None and _weights_moved(self):
             self.cache, self.graph = self.kv.clone(), None            # weights changed under the captured graph: back to eager, re-capture
         if self.graph is None:
             cache = self.cache if self.cache is not None else empty
@@ -343,26 +350,18 @@ class StreamingSession:
         enc, dev = self.enc, frames.device
         empty = torch.zeros((0, 0, 0, 0), device=dev)
         self.x = frames.clone()
-        self.kv = self.cache.clone()
-        self.pos = enc.embed.position_encoding(offset=self.offset - self.need, size=self.need + self.chunk).clone()
+        self.kv = self.cache                                       # the eager step's own result becomes the static cache (no second copy is kept)
+        self.pos =enc.embed.position_encoding(offset=self.offset - self.need, size=self.need + self.chunk).clone()
         # absolute encoding (use_relative=False): the table rows added to the chunk live in a static buffer too -- sliced at `offset`
         # inside the captured region they would be frozen at the capture step's offset
         self.abs = None if self.relative else self._abs_rows(frames.size(0), dev).clone()
-        self._sig = packing.graph_watch(self)
-        stream = torch.cuda.Stream(device=dev)
-        stream.wait_stream(torch.cuda.current_stream(dev))
-        with torch.no_grad(), torch.cuda.stream(stream):
-            enc.forward_chunk(self.x, self.offset, self.need, self.kv, empty, pos_rows=self.pos, abs_rows=self.abs)      # sizes the scratch arena
-            stream.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, stream=stream):
-                y, new_kv, _ = enc.forward_chunk(self.x, self.offset, self.need, self.kv, empty, pos_rows=self.pos, abs_rows=self.abs)
-                self.kv.copy_(new_kv)
-            self.y = y
-        torch.cuda.current_stream(dev).wait_stream(stream)
-        self.kv.copy_(self.cache)                                  # the capture pass and its warm-up advanced the static cache: restore
-        self.graph = graph
 
+        def run():
+            y, new_kv, _ = enc.forward_chunk(self.x, self.offset, self.need, self.kv, empty, pos_rows=self.pos, abs_rows=self.abs)
+            self.kv.copy_(new_kv)
+            return y
+        self.graph, self.y = packing.capture_step(run, dev, [self.kv])       # warm-up and capture advanced the static cache: it is put back
+        _weights_moved(self)
 
 
 class StreamingBatch:
@@ -433,19 +432,13 @@ class StreamingBatch:
 
     def reset(self, streams=None):
         """start new utterances on the given streams (all by default): position 0, empty left context."""
-        if streams is None:
-            self.offsets.zero_()
-            self._host_off = [0] * self.B
-            if self.conv is not None:
-                self.conv.zero_()
-        else:
-            streams = list(streams)
-            idx = torch.as_tensor(streams, dtype=torch.long, device=self.dev)
-            for b in streams:
-                self._host_off[b] = 0
-            self.offsets[idx] = 0
-            if self.conv is not None:
-                self.conv[:, idx] = 0
+        streams = None if streams is None else list(streams)
+        idx = packing.stream_index(streams, self.dev)
+        for b in range(self.B) if streams is None else streams:
+            self._host_off[b] = 0
+        self.offsets[idx] = 0
+        if self.conv is not None:
+            self.conv[:, idx] = 0
 
     def _grow_table(self, rows_needed):
         """Append sinusoid rows [len, new_len) -- the reference's formula (attention.py:12-16 / :109-115 incl. the absolute table's fp16
@@ -480,26 +473,13 @@ class StreamingBatch:
         if tuple(frames.shape[:2]) != (self.B, self.window):
             raise ValueError("StreamingBatch.step wants (%d, %d, F) frames, got %s" % (self.B, self.window, tuple(frames.shape)))
         cfm.require_hip(frames)
-        self._check_lens(frame_lens)                                      # before the input buffer is touched
+        self._read_lens(frame_lens)                                      # before the input buffer is touched
         self.input_buffer(frames.shape[2]).copy_(frames)
         return self.step_resident(frame_lens)
 
-    def _check_lens(self, frame_lens):
-        if frame_lens is None:
-            return
-        if isinstance(frame_lens, torch.Tensor):
-            if frame_lens.dim() != 1 or frame_lens.numel() != self.B or frame_lens.dtype not in (torch.int32, torch.int64):
-                raise ValueError("StreamingBatch: frame_lens must hold %d integers, got %s %s" % (self.B, frame_lens.dtype, tuple(frame_lens.shape)))
-            if frame_lens.device.type != "cuda":
-                frame_lens = frame_lens.tolist()
-            else:
-                return                                                    # on the device: not read on the host; out-of-range values are clamped
-        frame_lens = list(frame_lens)
-        if len(frame_lens) != self.B:
-            raise ValueError("StreamingBatch: %d frame_lens for %d streams" % (len(frame_lens), self.B))
-        for b, n in enumerate(frame_lens):
-            if int(n) != n or not 0 <= n <= self.window:
-                raise ValueError("StreamingBatch: frame_lens[%d] = %r, a window holds 0 .. %d frames" % (b, n, self.window))
+    def _read_lens(self, frame_lens, name="frame_lens", buf=None):
+        """packing.stream_lens with a window's rules (strict: a bad host value raises); buf None: checked only.  -> the host's list | None."""
+        return packing.stream_lens("StreamingBatch", name, self.B, frame_lens, self.window, buf, strict=True)
 
     def _set_lens(self, frame_lens):
         """Copy this step's lengths into the persistent device buffer the (captured) step reads; the first call switches to the length-aware step."""
@@ -509,13 +489,7 @@ class StreamingBatch:
             self.frame_lens = torch.full((self.B,), self.window, dtype=torch.int32, device=self.dev)
             self.out_lens = torch.zeros((self.B,), dtype=torch.int32, device=self.dev)
             self.graph = None                                             # captured without lengths: re-capture, once
-        if frame_lens is None:
-            self.frame_lens.fill_(self.window)
-        elif isinstance(frame_lens, torch.Tensor) and frame_lens.device.type == "cuda":
-            self.frame_lens.copy_(frame_lens.clamp(0, self.window))
-        else:
-            vals = frame_lens.tolist() if isinstance(frame_lens, torch.Tensor) else [int(n) for n in frame_lens]
-            self.frame_lens.copy_(torch.tensor(vals, dtype=torch.int32), non_blocking=False)
+        self._read_lens(frame_lens, buf=self.frame_lens)
 
     def input_buffer(self, num_features=None):
         """The (B, window, F) f32 buffer the step reads.  A producer on the same stream (fbank.StreamingFbank) writes the windows here and calls
@@ -532,11 +506,11 @@ class StreamingBatch:
         """step() on what input_buffer() holds.  host_lens: what the host knows of a DEVICE frame_lens (B window lengths, a producer's host mirror):
         the offset bound then advances by each stream's own c_b instead of `chunk`, so that idle steps do not bring the table growth forward."""
         self.input_buffer()
-        self._check_lens(frame_lens)
-        self._check_lens(host_lens)
+        self._read_lens(frame_lens)                                       # both checked before anything is touched
+        host_lens = None if host_lens is None else self._read_lens(host_lens, "host_lens")
         self._set_lens(frame_lens)
         self.steps += 1
-        adv = [self.chunk] * self.B if host_lens is None else [((int(n) - 1) // 2 - 1) // 2 if n >= 7 else 0 for n in host_lens]
+        adv = [self.chunk] * self.B if host_lens is None else [((n - 1) // 2 - 1) // 2 if n >= 7 else 0 for n in host_lens]
         need = max(o + a for o, a in zip(self._host_off, adv))
         if need > self.pe.size(0):
             self._grow_table(need)
@@ -544,30 +518,15 @@ class StreamingBatch:
         with torch.no_grad():
             if not self.use_graph:
                 return self._step_impl()
-            if self.graph is not None and packing.graph_watch(self) != self._sig:
+            if self.graph is not None and _weights_moved(self):
                 self.graph = None                                         # weights changed under the captured graph
             if self.graph is None:
-                y = self._step_impl()                                     # this step runs eagerly (it also sizes the arena and packs the weights)
-                stream = torch.cuda.Stream(device=self.dev)
-                stream.wait_stream(torch.cuda.current_stream(self.dev))
-                with torch.cuda.stream(stream):
-                    saved = self.offsets.clone(), None if self.conv is None else self.conv.clone()
-                    lens = None if self.frame_lens is None else (self.frame_lens.clone(), self.out_lens.clone())
-                    if lens is not None:
-                        self.frame_lens.zero_()                           # the length-aware warm-up runs every stream idle: it touches no state at all
-                    self._step_impl()                                     # warm-up ON the capture stream (its own scratch arena) ...
-                    stream.synchronize()
-                    self.offsets.copy_(saved[0])                          # ... with the state it advanced put back (ring slots rewritten: same data)
-                    if self.conv is not None:
-                        self.conv.copy_(saved[1])
-                    if lens is not None:
-                        self.frame_lens.copy_(lens[0])
-                        self.out_lens.copy_(lens[1])                      # this step's c_b, which the warm-up overwrote with zeros
-                    graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(graph, stream=stream):
-                        self.y = self._step_impl()
-                torch.cuda.current_stream(self.dev).wait_stream(stream)
-                self.graph, self._sig = graph, packing.graph_watch(self)
+                y = self._step_impl()                                     # this step runs eagerly (it also packs the weights)
+                # the warm-up's advance is put back (ring slots rewritten: same data), and out_lens -- this step's c_b -- with it; the length-aware
+                # warm-up runs every stream idle (frame_lens zeroed): it touches no state at all
+                self.graph, self.y = packing.capture_step(self._step_impl, self.dev, [self.offsets, self.conv, self.frame_lens, self.out_lens],
+                                                          idle=None if self.frame_lens is None else self.frame_lens.zero_)
+                _weights_moved(self)
                 return y
             self.graph.replay()
             return self.y

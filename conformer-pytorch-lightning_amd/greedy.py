@@ -115,25 +115,6 @@ class _Head:
         return x, torch.stack(hs), torch.stack(cs)
 
 
-def capture_graph(run, S, keys, dev):
-    """run() -- the steps of one replay on the state dict S -- captured in a HIP graph, which is returned; S[k] for k in keys, what run()
-    changes, is left as it was.  The graph holds the addresses of S's tensors, the packs and the descriptor: who replaces one drops it."""
-    snap = {k: S[k].clone() for k in keys}
-    side = torch.cuda.Stream(device=dev)
-    side.wait_stream(torch.cuda.current_stream(dev))
-    with torch.cuda.stream(side):
-        run()                                                                           # warm-up (allocator, lazy init) outside the capture
-    torch.cuda.current_stream(dev).wait_stream(side)
-    for k, v in snap.items():
-        S[k].copy_(v)                                                                   # ... and undone
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        run()
-    for k, v in snap.items():
-        S[k].copy_(v)                                                                   # (capture does not execute, but keep the state explicit)
-    return graph
-
-
 def replay_until_done(graph, run, done, limit):
     """graph.replay() (no graph: run()) until done(), the one host synchronisation per replay; returns the replays it took, raises at limit."""
     for n in range(1, limit + 1):
@@ -171,9 +152,10 @@ class _Search:
             self._drop()
 
     def _replay(self, S, snap, done, limit):
-        """_run_steps captured in a graph when one is wanted and missing (snap: what the steps change in S), then replay_until_done."""
+        """_run_steps captured in a graph (packing.capture_step) when one is wanted and missing (snap: what the steps change in S; the graph holds
+        the addresses of S's tensors, the packs and the descriptor), then replay_until_done."""
         if self.use_graph and self._graph is None and S["token"].is_cuda:
-            self._graph = capture_graph(self._run_steps, S, snap, S["token"].device)
+            self._graph, _ = packing.capture_step(self._run_steps, S["token"].device, [S[k] for k in snap])
         return replay_until_done(self._graph, self._run_steps, done, limit)
 
     def _f32_chunk(self, enc_chunk):
@@ -237,7 +219,7 @@ class BatchedGreedySearch(_Search):
         S["frame_count"].mul_((~adv).to(torch.int64))
         S["done"].copy_(S["t"] >= S["lens"])
 
-    _SNAP = ("t", "count", "frame_count", "hyps", "token", "h", "c", "done")             # what a step changes (capture_graph)
+    _SNAP = ("t", "count", "frame_count", "hyps", "token", "h", "c", "done")             # what a step changes (packing.capture_step)
 
     def _state(self, B, T, dev):
         L, H = self.predictor.num_layers, self.predictor.hidden_size
@@ -422,13 +404,14 @@ class ChunkGreedySearch(_Search):
             for _ in range(self.steps_per_replay):
                 self._step(self.S)
 
-    _SNAP = ("t", "count", "frame_count", "hyps", "token", "h", "c", "steps", "overflow", "n_done")             # what a step changes (capture_graph)
+    _SNAP = ("t", "count", "frame_count", "hyps", "token", "h", "c", "steps", "overflow", "n_done")             # what a step changes (packing.capture_step)
 
     # -- public ---------------------------------------------------------------------------------------------------------------------------
     def reset(self, streams=None):
         """New utterances on the given streams (all by default): token <- blank, LSTM state and hypotheses emptied (Transducer.init_state)."""
         S = self.S
-        idx = slice(None) if streams is None else torch.as_tensor(list(streams), dtype=torch.long, device=self.dev)
+        streams = None if streams is None else list(streams)
+        idx = packing.stream_index(streams, self.dev)
         S["token"][idx] = self.blank
         for k in ("count", "t", "frame_count", "hyps"):
             S[k][idx] = 0
@@ -460,17 +443,8 @@ class ChunkGreedySearch(_Search):
             raise ValueError("ChunkGreedySearch.decode wants (%d, %d, E) on %s, got %s on %s" % (B, C, dev, tuple(enc_chunk.shape), enc_chunk.device))
         self._grow(self._log.most() + C * self.n_steps)                                 # the most any stream can hold after this chunk
         self._prepare()
-        maybe_live = True
-        if lens is None:
-            S["lens"].fill_(C)
-        elif isinstance(lens, torch.Tensor) and lens.device == dev and dev.type == "cuda":
-            S["lens"].copy_(lens.to(torch.int64).clamp(0, C))                           # stays on the device: the host does not know who is idle
-        else:
-            host = [min(max(int(n), 0), C) for n in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
-            if len(host) != B:
-                raise ValueError("ChunkGreedySearch.decode: %d lens for %d streams" % (len(host), B))
-            maybe_live = any(host)
-            S["lens"].copy_(torch.tensor(host, dtype=torch.int64))
+        host = packing.stream_lens("ChunkGreedySearch.decode", "lens", B, lens, C, S["lens"])
+        maybe_live = host is None or any(host)                                          # lens on the device: the host does not know who is idle
         if self.fused:
             self._desc.enc = self._f32_chunk(enc_chunk).data_ptr()
             cfm.check(cfm.lib().cfm_greedy_chunk_begin(ctypes.byref(self._desc), cfm.stream()), "cfm_greedy_chunk_begin")
@@ -503,7 +477,7 @@ def _beam_state(head, K, B, T, max_len, dev):
                 nbest_tokens=z(i64, B, K, max_len), nbest_len=z(i32, B, K), nbest_score=z(f32, B, K), all_done=z(torch.bool))
 
 
-# what a beam step changes (capture_graph); the scratch a step writes before it reads it is not among them
+# what a beam step changes (packing.capture_step); the scratch a step writes before it reads it is not among them
 _BEAM_SNAP = ("token", "t", "hash", "fc", "len", "node", "parent", "ext", "live", "score", "h", "c", "nodes", "fin_score", "fin_node", "fin_len", "n_fin", "step", "done",
               "n_done", "nbest_tokens", "nbest_len", "nbest_score")
 
@@ -688,14 +662,8 @@ class StreamingBeamSearch(_Search):
         if tuple(enc_chunk.shape[:2]) != (B, C) or enc_chunk.device != dev:
             raise ValueError("StreamingBeamSearch.decode wants (%d, %d, E) on %s, got %s on %s" % (B, C, dev, tuple(enc_chunk.shape), enc_chunk.device))
         self._prepare()
-        for name, v, dt, hi in (("lens", lens, torch.int64, C), ("feed_final", final, torch.uint8, 1)):
-            if v is None:
-                S[name].fill_(C if name == "lens" else 0)
-            else:
-                v = torch.as_tensor(v)
-                if v.numel() != B:
-                    raise ValueError("StreamingBeamSearch.decode: %d %s for %d streams" % (v.numel(), "lens" if name == "lens" else "final flags", B))
-                S[name].copy_(v.reshape(B).to(torch.int64).clamp(0, hi).to(dt))
+        packing.stream_lens("StreamingBeamSearch.decode", "lens", B, lens, C, S["lens"])
+        packing.stream_lens("StreamingBeamSearch.decode", "final flags", B, final, 1, S["feed_final"], default=0)
         self._descs[0].enc = self._descs[1].enc = self._f32_chunk(enc_chunk).data_ptr()
         lib = cfm.lib()
         cfm.check(lib.cfm_rnnt_beam_stream_feed(ctypes.byref(self._descs[0]), cfm.stream()), "cfm_rnnt_beam_stream_feed")
