@@ -284,6 +284,16 @@ class TokenLogprobDesc(ctypes.Structure):
                 [(n, c_i32) for n in ("M", "D", "V", "x_dtype", "w_dtype")])
 
 
+class LsmLossDesc(ctypes.Structure):
+    _fields_ = ([(n, c_p) for n in ("X", "W", "bias", "logits", "target", "loss", "lse")] + [("ldx", c_i64), ("ld", c_i64)] +
+                [(n, c_i32) for n in ("M", "D", "V", "x_dtype", "w_dtype")] + [("smoothing", c_f)])
+
+
+class LsmGradDesc(ctypes.Structure):
+    _fields_ = ([(n, c_p) for n in ("X", "W", "bias", "logits", "target", "lse", "g", "dz")] + [("ldx", c_i64), ("ld", c_i64), ("ldz", c_i64)] +
+                [(n, c_i32) for n in ("M", "D", "V", "Vk", "x_dtype", "w_dtype", "dz_dtype")] + [("smoothing", c_f)])
+
+
 class RescoreCombineDesc(ctypes.Structure):
     _fields_ = ([(n, c_p) for n in ("logp", "logp_r", "nlen", "score", "final_score", "left", "right", "order")] + [(n, c_i32) for n in ("B", "N", "Lc")] +
                 [("first_pass_weight", c_f), ("reverse_weight", c_f)])
@@ -322,7 +332,7 @@ for _c_name, _cls in dict(
         cfm_rnnt_desc=RnntDesc, cfm_lattice=Lattice, cfm_rnnt_packed_desc=RnntPackedDesc, cfm_ln_bwd_desc=LnBwdDesc, cfm_lstm_desc=LstmDesc, cfm_greedy_desc=GreedyDesc,
         cfm_greedy_chunk_desc=GreedyChunkDesc, cfm_ctc_greedy_desc=CtcGreedyDesc, cfm_ctc_beam_desc=CtcBeamDesc, cfm_ctc_align_desc=CtcAlignDesc, cfm_edit_distance_desc=EditDistanceDesc, cfm_rnnt_beam_desc=RnntBeamDesc, cfm_rnnt_beam_stream_desc=RnntBeamStreamDesc, cfm_fbank_desc=FbankDesc, cfm_resample_desc=ResampleDesc,
         cfm_resample_bank=ResampleBank, cfm_resample_group_desc=ResampleGroupDesc, cfm_spec_augment_desc=SpecAugmentDesc,
-        cfm_rescore_prep_desc=RescorePrepDesc, cfm_token_logprob_desc=TokenLogprobDesc, cfm_rescore_combine_desc=RescoreCombineDesc,
+        cfm_rescore_prep_desc=RescorePrepDesc, cfm_token_logprob_desc=TokenLogprobDesc, cfm_rescore_combine_desc=RescoreCombineDesc, cfm_lsm_loss_desc=LsmLossDesc, cfm_lsm_grad_desc=LsmGradDesc,
         cfm_ffn_split_desc=FfnSplitDesc, cfm_layer_scratch=LayerScratch, cfm_layer_io=LayerIO).items():
     _cls._c_name_ = _c_name
 PROTOTYPES = (
@@ -432,6 +442,9 @@ PROTOTYPES = (
     ("cfm_rescore_prep", c_int, P(RescorePrepDesc), c_p),
     ("cfm_token_logprob", c_int, P(TokenLogprobDesc), c_p),
     ("cfm_rescore_combine", c_int, P(RescoreCombineDesc), c_p),
+    ("cfm_lsm_loss", c_int, P(LsmLossDesc), c_p),
+    ("cfm_lsm_grad", c_int, P(LsmGradDesc), c_p),
+    ("cfm_lsm_reduce", c_int, c_p, c_p, c_i32, c_i32, c_p, c_p),
 )
 
 _lib = None

@@ -68,8 +68,6 @@ def ffn_bwd(pk, saved, dy, ln, prec, alpha, act=cfm.ACT_SILU, drop_h=None, drop_
     dyb = dy
     if drop_o is not None:                                          # the branch gradient through the output dropout, as a GEMM operand
         dyb, alpha = cfm.dropout_rows(dy, prec.act_dtype, alpha=alpha, drop=drop_o), 1.0
-    if drop_h is not None and dact != cfm.ACT_DSILU:
-        raise NotImplementedError("hidden dropout with a ReLU feed-forward in train mode")
     dW2, db2 = cfm.gemm_tn(dyb, h, want_colsum=True, alpha=alpha, mma_code=mma, split=sp)
     dz = _gemm(dyb, pk.w2t, w_lo=pk.w2t_lo, act=dact, aux=z, alpha=alpha, out_dtype=prec.act_dtype, drop=drop_h)
     dW1, db1 = cfm.gemm_tn(dz, xn, want_colsum=True, mma_code=mma, split=sp)
@@ -131,6 +129,48 @@ def mhsa_bwd(mod, pk, saved, dy, ln, B, T, mask8, m_str, prec, relative, drop_a=
         grads["linear_pos.weight"] = torch.zeros_like(mod.linear_pos.weight)
     if ln is None:
         return dxn, grads, None
+    dx, dg, db = cfm.layernorm_bwd(x, dxn, ln[0], dres=dy, dx=dy)
+    return dx, grads, (dg, db)
+
+
+def src_attn_fwd(mod, pk, x, mem, ln, B, Tq, Tk, mask8, prec, drop_a=None, drop_o=None):
+    """The decoder layer's cross-attention sub-block (decoder_layer.layer_rows): x f32 [B*Tq, D] -> (x + drop_o(SrcAttn(LN(x), mem, mem)), saved).
+    mem [B*Tk, D] in the activation type; mask8 uint8 [B, 1, Tk], the key-validity mask; pk = packing.pack_src_attn_train."""
+    adt = prec.act_dtype
+    M, D = x.shape
+    H, dk = mod.num_heads, mod.d_k
+    xn = cfm.layernorm(x, ln[0], ln[1], out1_dtype=adt)[0]
+    q = _gemm(xn, pk.q_w, bias=pk.q_b, w_lo=pk.q_w_lo, out_dtype=adt)
+    kv = _gemm(mem, pk.kv_w, bias=pk.kv_b, w_lo=pk.kv_w_lo, out_dtype=adt)                   # k | v in one product
+    ctx = torch.empty((M, D), dtype=adt, device=x.device)
+    lse = torch.empty((B, H, Tq), dtype=torch.float32, device=x.device)
+    cfm.attention(q, kv, kv[:, D:], B, H, Tq, Tk, dk, (Tq * D, D), (Tk * 2 * D, 2 * D, dk), (Tk * 2 * D, 2 * D, dk), ctx, mask=mask8, mask_str=(Tk, 0),
+                  mma_code=prec.w_code, split=prec.split, lse=lse, drop=drop_a)
+    y = _gemm(ctx, pk.out_w, bias=pk.out_b, w_lo=pk.out_w_lo, residual=x, alpha=1.0, drop=drop_o)
+    return y, (x, xn, mem, q, kv, ctx, lse)
+
+
+def src_attn_bwd(mod, pk, saved, dy, ln, B, Tq, Tk, mask8, prec, dmem, drop_a=None, drop_o=None):
+    """dy f32 [B*Tq, D] -> (dx, grads, (dgamma, dbeta)); dx = dy + dLN(..) in place over dy.  dmem f32 [B*Tk, D] takes dkv . Wkv on top of what
+    it holds (the memory's gradient, accumulated over the layers in f32)."""
+    x, xn, mem, q, kv, ctx, lse = saved
+    D = x.shape[1]
+    H, dk = mod.num_heads, mod.d_k
+    mma, sp = prec.w_code, prec.split
+    dyb = dy if drop_o is None else cfm.dropout_rows(dy, prec.act_dtype, drop=drop_o)
+    dWo, dbo = cfm.gemm_tn(dyb, ctx, want_colsum=True, mma_code=mma, split=sp)
+    dctx = _gemm(dyb, pk.out_t, w_lo=pk.out_t_lo, out_dtype=prec.act_dtype)
+    dq, dkv = torch.empty_like(q), torch.empty_like(kv)
+    cfm.attention_bwd(q, kv, kv[:, D:], ctx, dctx, lse, B, H, Tq, Tk, dk, (Tq * D, D), (Tk * 2 * D, 2 * D), (Tk * 2 * D, 2 * D), dq, dkv, dkv[:, D:],
+                      mask=mask8, mask_str=(Tk, 0), mma_code=mma, split=sp, drop=drop_a)
+    dWq, dbq = cfm.gemm_tn(dq, xn, want_colsum=True, mma_code=mma, split=sp)
+    dWkv, dbkv = cfm.gemm_tn(dkv, mem, want_colsum=True, mma_code=mma, split=sp)
+    _gemm(dkv, pk.kv_t, w_lo=pk.kv_t_lo, residual=dmem, alpha=1.0, out=dmem)
+    dxn = _gemm(dq, pk.q_t, w_lo=pk.q_t_lo, out_dtype=torch.float32)
+    # linear_k.bias adds q . b_k to every score of a row: constant along the softmax, so its gradient is exactly zero (the column sums of dk are
+    # rounding noise), as pos_bias_v's in the encoder's batch path
+    grads = {"linear_q.weight": dWq, "linear_q.bias": dbq, "linear_k.weight": dWkv[:D], "linear_k.bias": torch.zeros_like(dbkv[:D]), "linear_v.weight": dWkv[D:],
+             "linear_v.bias": dbkv[D:], "linear_out.weight": dWo, "linear_out.bias": dbo}
     dx, dg, db = cfm.layernorm_bwd(x, dxn, ln[0], dres=dy, dx=dy)
     return dx, grads, (dg, db)
 
@@ -769,6 +809,162 @@ class CTCLossFn(torch.autograd.Function):
         dW, db = cfm.gemm_tn(dlog, x2, want_colsum=True, mma_code=prec.w_code, split=prec.split)
         dx = _gemm(dlog, pk.wt, w_lo=pk.wt_lo, out_dtype=torch.float32)
         return dx, None, None, None, dW[:pk.V], db[:pk.V]
+
+
+def _lsm_row_scale(gout, target, red):
+    """g[m] of cfm.lsm_grad: the upstream gradient over the denominator (red = cfm.lsm_reduce's pair), 0 on ignored rows; no host read."""
+    return (target >= 0).to(torch.float32) * (gout.reshape(()).to(torch.float32) / red[1])
+
+
+class LsmLossFn(torch.autograd.Function):
+    """The label-smoothing loss of an output projection over rows [M, D] (label_smoothing_loss.py:52-80 behind a Linear): sum_m loss_m / denom,
+    denom = batch, or with batch = 0 the number of targets >= 0 (normalize_length), counted on the device; no valid target gives 0.
+    fused=False (the default): cfm_gemm to f32 logits, kept for the backward, and the kernels' logits form.  fused=True (16-bit modes with
+    D % 8 == 0 and D <= 512; otherwise ignored): cfm_lsm_loss / cfm_lsm_grad on cfm_token_logprob's product loop, the logits never stored --
+    the path for a vocabulary whose logits should not be held.  Measured at the recipe's shape (992 rows, D = 256, V = 5002, bf16, MI355X):
+    the fused forward is 3.5x SLOWER than the unfused pair (its 16 workgroups leave most of the device idle; scripts/bench_lsm.py),
+    so it is not the default.  The projection's gradients are the existing products, as in CTCLossFn."""
+
+    @staticmethod
+    def forward(ctx, rows, target, linear, prec, smoothing, batch, fused, weight, bias):
+        pk = packing.pack_vocab_train(linear, prec)
+        D = rows.shape[1]
+        fused = bool(fused) and not prec.split and D % 8 == 0 and D <= 512
+        x = rows if rows.dtype == prec.act_dtype else cfm.cast(rows, prec.act_dtype)
+        x = x if x.is_contiguous() else x.contiguous()
+        target = target.reshape(-1).to(torch.int32).contiguous()
+        logits = None if fused else _gemm(x, pk.w, bias=pk.b, w_lo=pk.w_lo, out_dtype=torch.float32)
+        loss, lse = cfm.lsm_loss(x, pk.w, pk.b, target, pk.V, smoothing) if fused else cfm.lsm_loss(None, None, None, target, pk.V, smoothing, logits=logits)
+        red = cfm.lsm_reduce(loss, target, batch)
+        ctx.args = (prec, pk, x, logits, target, lse, red, smoothing)
+        return red[0].clone()
+
+    @staticmethod
+    def backward(ctx, gout):
+        prec, pk, x, logits, target, lse, red, smoothing = ctx.args
+        g = _lsm_row_scale(gout, target, red)
+        if logits is None:
+            dz = cfm.lsm_grad(x, pk.w, pk.b, target, pk.V, smoothing, lse, g)
+        else:
+            dz = cfm.lsm_grad(None, None, None, target, pk.V, smoothing, lse, g, logits=logits, out_dtype=prec.act_dtype)
+        dW, db = cfm.gemm_tn(dz, x, want_colsum=True, mma_code=prec.w_code, split=prec.split)
+        dx = _gemm(dz, pk.wt, w_lo=pk.wt_lo, out_dtype=torch.float32)
+        return dx, None, None, None, None, None, None, dW[:pk.V], db[:pk.V]
+
+
+def _p(module):
+    return float(module.p) if module.training else 0.0
+
+
+class DecoderLossFn(torch.autograd.Function):
+    """A whole decoder.TransformerDecoder and its label-smoothing loss in one node: embedding E[tok] * sqrt(D) + pe[position], positional dropout,
+    per layer mhsa_fwd (relative=False, the [B, Lc, Lc] causal-and-length mask), src_attn_fwd, ffn_fwd(ACT_RELU); after_norm; the loss as LsmLossFn
+    computes it.  memory [B, T, D] is differentiable (its gradient is the sum of the layers' dkv . Wkv, f32).  Dropout site k is
+    (p, seed + 0x9E3779B1 * k): 0 positional; per layer l at 1 + 6 l: self-attention probabilities, self-attention output, source-attention
+    probabilities, source-attention output, feed-forward hidden, feed-forward output.  C-entry calls per layer: 12 forward, 19 backward, and one
+    cfm_dropout_rows per active branch-output dropout in the backward."""
+
+    @staticmethod
+    def forward(ctx, memory, dec, ys_in, ys_out, self_mask8, mem_mask8, prec, smoothing, batch, seed, fused, *params):
+        import math
+        B, Lc = ys_in.shape
+        T, D = memory.shape[1], memory.shape[2]
+        adt = prec.act_dtype
+        mem = _f32c(memory.detach().reshape(B * T, D))
+        mem = mem if adt == torch.float32 else cfm.cast(mem, adt)
+        E = dec.embed[0].weight.detach()
+        x = (E[ys_in.long()].double() * math.sqrt(D) + dec.position_table(Lc)[:Lc].double()).float().reshape(B * Lc, D).contiguous()
+        d_pos = _drop(_p(dec.embed[1].dropout), seed, 0)
+        if d_pos is not None:
+            x = cfm.dropout_rows(x, torch.float32, drop=d_pos)
+        saved, drops = [], []
+        for l, layer in enumerate(dec.decoders):
+            sa, ca, ff = layer.self_attn, layer.src_attn, layer.feed_forward
+            po, k = _p(layer.dropout), 1 + 6 * l
+            dr = (_drop(_p(sa.dropout), seed, k), _drop(po, seed, k + 1), _drop(_p(ca.dropout), seed, k + 2), _drop(po, seed, k + 3),
+                  _drop(_p(ff.dropout), seed, k + 4), _drop(po, seed, k + 5))
+            x, s1 = mhsa_fwd(sa, packing.pack_mhsa_train(sa, prec, False), x, (layer.norm1.weight, layer.norm1.bias), B, Lc, self_mask8, (Lc * Lc, Lc), prec,
+                             False, drop_a=dr[0], drop_o=dr[1])
+            x, s2 = src_attn_fwd(ca, packing.pack_src_attn_train(ca, prec), x, mem, (layer.norm2.weight, layer.norm2.bias), B, Lc, T, mem_mask8, prec,
+                                 drop_a=dr[2], drop_o=dr[3])
+            x, s3 = ffn_fwd(packing.pack_ffn_train(ff, prec), x, (layer.norm3.weight, layer.norm3.bias), prec, 1.0, act=cfm.ACT_RELU, drop_h=dr[4], drop_o=dr[5])
+            saved.append((s1, s2, s3))
+            drops.append(dr)
+        xn = cfm.layernorm(x, dec.after_norm.weight, dec.after_norm.bias, out1_dtype=adt)[0]
+        pk = packing.pack_vocab_train(dec.output_layer, prec)
+        fused = bool(fused) and not prec.split and D % 8 == 0 and D <= 512
+        target = ys_out.reshape(-1).to(torch.int32).contiguous()
+        logits = None if fused else _gemm(xn, pk.w, bias=pk.b, w_lo=pk.w_lo, out_dtype=torch.float32)
+        loss, lse = cfm.lsm_loss(xn, pk.w, pk.b, target, pk.V, smoothing) if fused else cfm.lsm_loss(None, None, None, target, pk.V, smoothing, logits=logits)
+        red = cfm.lsm_reduce(loss, target, batch)
+        ctx.args = (dec, prec, pk, x, xn, logits, target, lse, red, smoothing, saved, drops, d_pos, ys_in, self_mask8, mem_mask8, mem, (B, Lc, T, D),
+                    memory.dtype, [id(p) for p in params])
+        return red[0].clone()
+
+    @staticmethod
+    def backward(ctx, gout):
+        import math
+        dec, prec, pk, x, xn, logits, target, lse, red, smoothing, saved, drops, d_pos, ys_in, self_mask8, mem_mask8, mem, shape, mdt, pids = ctx.args
+        B, Lc, T, D = shape
+        g = _lsm_row_scale(gout, target, red)
+        if logits is None:
+            dz = cfm.lsm_grad(xn, pk.w, pk.b, target, pk.V, smoothing, lse, g)
+        else:
+            dz = cfm.lsm_grad(None, None, None, target, pk.V, smoothing, lse, g, logits=logits, out_dtype=prec.act_dtype)
+        grads = {}
+        dW, db = cfm.gemm_tn(dz, xn, want_colsum=True, mma_code=prec.w_code, split=prec.split)
+        grads[id(dec.output_layer.weight)], grads[id(dec.output_layer.bias)] = dW[:pk.V], db[:pk.V]
+        dxn = _gemm(dz, pk.wt, w_lo=pk.wt_lo, out_dtype=torch.float32)
+        dx, dg, dbn = cfm.layernorm_bwd(x, dxn, dec.after_norm.weight)
+        grads[id(dec.after_norm.weight)], grads[id(dec.after_norm.bias)] = dg, dbn
+        dmem = torch.zeros((B * T, D), dtype=torch.float32, device=dx.device)
+
+        def put(mod, gs):
+            for name, p in mod.named_parameters():
+                if name in gs:
+                    grads[id(p)] = gs[name]
+
+        for l in range(len(dec.decoders) - 1, -1, -1):
+            layer, (s1, s2, s3), dr = dec.decoders[l], saved[l], drops[l]
+            sa, ca, ff = layer.self_attn, layer.src_attn, layer.feed_forward
+            dx, gs, (dg, dbn) = ffn_bwd(packing.pack_ffn_train(ff, prec), s3, dx, (layer.norm3.weight, layer.norm3.bias), prec, 1.0, act=cfm.ACT_RELU,
+                                        drop_h=dr[4], drop_o=dr[5])
+            put(ff, gs)
+            grads[id(layer.norm3.weight)], grads[id(layer.norm3.bias)] = dg, dbn
+            dx, gs, (dg, dbn) = src_attn_bwd(ca, packing.pack_src_attn_train(ca, prec), s2, dx, (layer.norm2.weight, layer.norm2.bias), B, Lc, T, mem_mask8,
+                                             prec, dmem, drop_a=dr[2], drop_o=dr[3])
+            put(ca, gs)
+            grads[id(layer.norm2.weight)], grads[id(layer.norm2.bias)] = dg, dbn
+            dx, gs, (dg, dbn) = mhsa_bwd(sa, packing.pack_mhsa_train(sa, prec, False), s1, dx, (layer.norm1.weight, layer.norm1.bias), B, Lc, self_mask8,
+                                         (Lc * Lc, Lc), prec, False, drop_a=dr[0], drop_o=dr[1])
+            put(sa, gs)
+            grads[id(layer.norm1.weight)], grads[id(layer.norm1.bias)] = dg, dbn
+        if d_pos is not None:
+            dx = cfm.dropout_rows(dx, torch.float32, drop=d_pos)
+        E = dec.embed[0].weight
+        dE = torch.zeros(E.shape, dtype=torch.float32, device=dx.device)
+        dE.index_add_(0, ys_in.reshape(-1).long(), dx * math.sqrt(D))
+        grads[id(E)] = dE
+        return (dmem.view(B, T, D).to(mdt),) + (None,) * 10 + tuple(grads.get(i) for i in pids)
+
+
+class LsmLogitsLossFn(torch.autograd.Function):
+    """label_smoothing_loss.LabelSmoothingLoss.forward over logits the caller holds: the kernels' logits form, f32."""
+
+    @staticmethod
+    def forward(ctx, logits, target, V, smoothing, batch):
+        z = _f32c(logits.reshape(-1, logits.shape[-1]))
+        target = target.reshape(-1).to(torch.int32).contiguous()
+        loss, lse = cfm.lsm_loss(None, None, None, target, V, smoothing, logits=z)
+        red = cfm.lsm_reduce(loss, target, batch)
+        ctx.args = (z, target, lse, red, V, smoothing, logits.shape, logits.dtype)
+        return red[0].clone()
+
+    @staticmethod
+    def backward(ctx, gout):
+        z, target, lse, red, V, smoothing, shape, dtype = ctx.args
+        dz = cfm.lsm_grad(None, None, None, target, V, smoothing, lse, _lsm_row_scale(gout, target, red), logits=z)
+        return dz[:, :V].to(dtype).reshape(shape), None, None, None, None
 
 
 def _rnnt_scale(gout, reduction, B):

@@ -6,7 +6,7 @@ import torch
 
 import cfm as _c
 
-__all__ = ["rescore_prep", "token_logprob", "rescore_combine", "lstm_forward", "lstm_backward", "fbank", "fbank_stream", "fbank_stream_ragged", "resample", "resample_stream", "resample_group", "spec_augment", "stream_prep", "stream_advance", "dwconv_causal_bn_silu", "conv_cache_update", "dropout_rows", "dropout_mask", "set_deterministic", "gemm_tn", "gemm_tn_group", "layernorm_bwd", "glu_bwd", "dwconv_bn_train", "dwconv_bn_train_bwd", "dwconv_bn_train_groups", "dwconv_bn_train_bwd_groups", "col2im_relu_bwd", "conv1_wgrad", "attention_bwd", "attention_group", "attention_bwd_group",
+__all__ = ["rescore_prep", "token_logprob", "rescore_combine", "lsm_loss", "lsm_grad", "lsm_reduce", "lstm_forward", "lstm_backward", "fbank", "fbank_stream", "fbank_stream_ragged", "resample", "resample_stream", "resample_group", "spec_augment", "stream_prep", "stream_advance", "dwconv_causal_bn_silu", "conv_cache_update", "dropout_rows", "dropout_mask", "set_deterministic", "gemm_tn", "gemm_tn_group", "layernorm_bwd", "glu_bwd", "dwconv_bn_train", "dwconv_bn_train_bwd", "dwconv_bn_train_groups", "dwconv_bn_train_bwd_groups", "col2im_relu_bwd", "conv1_wgrad", "attention_bwd", "attention_group", "attention_bwd_group",
            "ctc_nll_train_groups", "ctc_grad", "rnnt_nll", "rnnt_grad", "joint_act_bwd", "rnnt_nll_packed", "joint_act_packed", "joint_act_packed_bwd", "ffn_split", "adam_step", "adam_clip_step", "sumsq", "scratch_stats",
            "gemm", "ffn_fused", "ffn_fused_supported", "rowchain", "rowchain_supported", "rowchain_pair_supported", "layernorm", "attention", "kv_cache_pack", "dwconv_bn_silu", "conv1_relu", "conv1_relu_mma_supported", "conv12_relu", "conv12_supported", "ctc_nll", "ctc_topk", "ctc_greedy", "ctc_greedy_state", "ctc_prefix_beam", "ctc_align", "edit_distance", "joint_act", "valid_mask", "chunk_mask",
            "attn_mask_combine", "cast", "add_rows", "scratch", "prof_enable", "prof_reset", "prof_table", "as_u8_mask"]
@@ -1711,3 +1711,68 @@ def rescore_combine(logp, nlen, score, first_pass_weight, reverse_weight=0.0, lo
     d.B, d.N, d.Lc, d.first_pass_weight, d.reverse_weight = B, N, logp.numel() // (B * N), float(first_pass_weight), float(reverse_weight)
     _c.call("cfm_rescore_combine", ctypes.byref(d))
     return final, left, right, order
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# label-smoothing loss of the attention decoder (csrc/lsm.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+def _lsm_operands(op, d, x, w, bias, target, V, logits):
+    """The operands that cfm_lsm_loss and cfm_lsm_grad share with cfm_token_logprob, into descriptor d; returns M."""
+    _c.require_hip(x, w, bias, target, logits)
+    _layout(op, w=_opt(w, None, None), bias=_opt(bias, None, None), target=(target, _I32, (None,)))
+    M = target.numel()
+    if logits is not None:
+        logits = _rows2d(logits, op + "(logits)")
+        if logits.dtype != torch.float32 or logits.shape[0] != M or logits.shape[1] < V:
+            raise ValueError("cfm.%s: logits must be float32 [M = %d, >= V = %d], got %s %s" % (op, M, V, tuple(logits.shape), logits.dtype))
+        d.logits, d.ld = _c.ptr(logits), logits.stride(0) if M > 1 else logits.shape[1]
+    else:
+        x = _rows2d(x, op + "(x)")
+        if w.dim() != 2 or x.shape[1] != w.shape[1] or x.shape[0] != M or w.shape[0] < V or bias.dtype != torch.float32 or bias.numel() < V:
+            raise ValueError("cfm.%s: x %s, w %s, bias %s, %d targets, V = %d do not fit" % (op, tuple(x.shape), tuple(w.shape), tuple(bias.shape), M, V))
+        d.X, d.W, d.bias, d.ldx = _c.ptr(x), _c.ptr(w), _c.ptr(bias), x.stride(0) if M > 1 else max(x.stride(0), x.shape[1])
+        d.D, d.x_dtype, d.w_dtype = x.shape[1], _c.dt_code(x), _c.dt_code(w)
+    d.target, d.M, d.V = _c.ptr(target), M, int(V)
+    return M
+
+
+def lsm_loss(x, w, bias, target, V, smoothing, logits=None):
+    """Per-row label-smoothing loss over the first V classes of x . w^T + bias, the logits never written (include/cfm.h cfm_lsm_loss): 0 where
+    target < 0.  Operands as cfm.token_logprob; logits f32 [M, >= V]: over stored logits (x, w, bias may be None).
+    Returns (loss f32 [M], lse f32 [M])."""
+    d = _c.LsmLossDesc()
+    M = _lsm_operands("lsm_loss", d, x, w, bias, target, V, logits)
+    loss = torch.empty((M,), dtype=torch.float32, device=target.device)
+    lse = torch.empty((M,), dtype=torch.float32, device=target.device)
+    d.loss, d.lse, d.smoothing = _c.ptr(loss), _c.ptr(lse), float(smoothing)
+    _c.call("cfm_lsm_loss", ctypes.byref(d))
+    return loss, lse
+
+
+def lsm_grad(x, w, bias, target, V, smoothing, lse, g, logits=None, out=None, out_dtype=None):
+    """dz[m, c] = g[m] * (softmax(z_m)[c] - q_c) as [M, Vk], columns V..Vk zero, Vk = V rounded up to 8 (what cfm.gemm wants of a K extent),
+    the logits recomputed and never stored (include/cfm.h cfm_lsm_grad).  lse, g f32 [M].  The fused form writes w's dtype; the logits form
+    out_dtype (default float32).  out: a [M, >= Vk] tensor with unit inner stride to write into (its first Vk columns)."""
+    d = _c.LsmGradDesc()
+    M = _lsm_operands("lsm_grad", d, x, w, bias, target, V, logits)
+    _want("lsm_grad", "one per row", lse=(lse, _F32, M), g=(g, _F32, M))
+    Vk = (int(V) + 7) // 8 * 8
+    dt = out.dtype if out is not None else (w.dtype if logits is None else (out_dtype or torch.float32))
+    if out is None:
+        out = torch.empty((M, Vk), dtype=dt, device=target.device)
+    _c.require_hip(out)
+    if _rows2d(out, "lsm_grad(out)").shape[0] != M or out.shape[1] < Vk:
+        raise ValueError("cfm.lsm_grad: out %s for M = %d rows of Vk = %d columns" % (tuple(out.shape), M, Vk))
+    d.lse, d.g, d.dz, d.ldz = _c.ptr(lse), _c.ptr(g), _c.ptr(out), out.stride(0) if M > 1 else max(out.stride(0), out.shape[1])
+    d.Vk, d.dz_dtype, d.smoothing = Vk, _c.dt_code(out), float(smoothing)
+    _c.call("cfm_lsm_grad", ctypes.byref(d))
+    return out[:, :Vk]
+
+
+def lsm_reduce(loss, target, batch=0):
+    """(sum(loss) / denom, denom) as f32 [2] on the device, in a fixed order (include/cfm.h cfm_lsm_reduce): denom = batch, or with batch = 0
+    the number of targets >= 0 (at least 1)."""
+    _want("lsm_reduce", "one target per row", loss=(loss, _F32, None), target=(target, _I32, loss.numel()))
+    out = torch.empty((2,), dtype=torch.float32, device=loss.device)
+    _c.call("cfm_lsm_reduce", _c.ptr(loss), _c.ptr(target), loss.numel(), int(batch), _c.ptr(out))
+    return out

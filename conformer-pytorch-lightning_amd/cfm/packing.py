@@ -538,6 +538,41 @@ def pack_ctc_train(mod, prec):
     return _train_slot(mod).get([mod.ctc_lo.weight, mod.ctc_lo.bias], prec, build)
 
 
+def pack_src_attn_train(mod, prec):
+    """Cross-attention in train mode: q from the decoder rows, k | v in one product over the memory rows; each matrix and its transpose."""
+    srcs = [mod.linear_q.weight, mod.linear_q.bias, mod.linear_k.weight, mod.linear_k.bias, mod.linear_v.weight, mod.linear_v.bias,
+            mod.linear_out.weight, mod.linear_out.bias]
+
+    def build():
+        wkv = torch.cat([mod.linear_k.weight.detach(), mod.linear_v.weight.detach()], 0)
+        q, ql = matrix(mod.linear_q.weight, prec)
+        qt, qtl = matrix_t(mod.linear_q.weight, prec)
+        kv, kvl = matrix(wkv, prec)
+        kvt, kvtl = matrix_t(wkv, prec)
+        out, outl = matrix(mod.linear_out.weight, prec)
+        outt, outtl = matrix_t(mod.linear_out.weight, prec)
+        return Packed(q_w=q, q_w_lo=ql, q_t=qt, q_t_lo=qtl, q_b=f32(mod.linear_q.bias), kv_w=kv, kv_w_lo=kvl, kv_t=kvt, kv_t_lo=kvtl,
+                      kv_b=torch.cat([mod.linear_k.bias.detach().float(), mod.linear_v.bias.detach().float()], 0).contiguous(),
+                      out_w=out, out_w_lo=outl, out_t=outt, out_t_lo=outtl, out_b=f32(mod.linear_out.bias))
+    return slot(mod, "_pack_src_train", PackCache).get(srcs, prec, build)
+
+
+def pack_vocab_train(linear, prec):
+    """An output projection under the label-smoothing loss: the weight padded to Vk = a multiple of 8 rows (cfm_gemm wants K % 8 == 0 of the
+    transposed pack, cfm_gemm_tn N % 8 == 0; the pad rows are zero and cfm_lsm_loss / cfm_lsm_grad never read them) and its transpose."""
+    def build():
+        V, D = linear.weight.shape
+        Vk = (V + 7) // 8 * 8
+        w = torch.zeros((Vk, D), dtype=torch.float32, device=linear.weight.device)
+        w[:V] = linear.weight.detach()
+        b = torch.zeros((Vk,), dtype=torch.float32, device=w.device)
+        b[:V] = linear.bias.detach()
+        wm, wlo = matrix(w, prec)
+        wt, wtlo = matrix_t(w, prec)
+        return Packed(w=wm, w_lo=wlo, wt=wt, wt_lo=wtlo, b=b, V=V, Vk=Vk)
+    return _train_slot(linear).get([linear.weight, linear.bias], prec, build)
+
+
 def pack_joint_train(mod, prec):
     """TransducerJoint.rnnt_loss: the three projections and their transposes; ffn_out padded to Vp = a multiple of 8 rows (cfm_gemm_tn wants
     N % 8 == 0; the pad rows are zero, so are the logits' pad columns, which the RNN-T kernels never read and whose gradient is exactly 0)."""

@@ -366,10 +366,14 @@ __global__ __launch_bounds__(256 * KG, KG == 1 ? 2 : 1) void cfm_gemm_kernel(con
                     v[r] *= g.alpha * sg * (1.f + z * (1.f - sg));
                 }
             } else if (g.act == CFM_ACT_DRELU) {
+                if (g.drop.thresh) {                           // the gradient arrives at dropout(relu(z)): same mask as the forward's hidden
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[r] = cfm_drop(g.drop, (unsigned)row * (unsigned)g.N + (unsigned)(col + r), v[r]);
+                }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = res_r[i][j][r] > 0.f ? g.alpha * v[r] : 0.f;
             }
-            if (g.drop.thresh && g.act != CFM_ACT_DSILU) {
+            if (g.drop.thresh && !dact) {
                 const unsigned nout = glu ? (unsigned)g.N >> 1 : (unsigned)g.N;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {

@@ -8,12 +8,10 @@
 //                         hypothesis row) is lane & 15, so a lane folds its 8 values of a tile into ITS row's running (max, sum) in registers.  The 4
 //                         lanes of a row, then the 8 wavefronts, are combined once at the end, in a fixed order.  The second form (logits given) is
 //                         one wavefront per row over stored logits.
+//                         The product loop lives in vocab_tile.h: the label-smoothing loss (lsm.hip) runs on the same one.
 //   cfm_rescore_combine   one wavefront per utterance, lane n sums hypothesis n's rows in position order and ranks itself among the N.
 #include "cfm_common.h"
-
-#define TL_ROWS 64
-#define TL_WAVES 8
-#define TL_MAXD 512
+#include "vocab_tile.h"
 
 // ------------------------------------------------------------------------------------------------------------------------------------- prep
 __global__ __launch_bounds__(64) void cfm_rescore_prep_kernel(cfm_rescore_prep_desc d, double sqrt_d) {
@@ -65,17 +63,6 @@ extern "C" int cfm_rescore_prep(const cfm_rescore_prep_desc* d, cfm_stream_t str
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------- token logprob
-// One (max, sum) pair takes another in: the sum stays relative to the larger maximum.  Symmetric in its arguments (a float add commutes), so
-// two lanes that exchange their pairs end with the same bits.  An empty pair is (-inf, 0).
-__device__ __forceinline__ void tl_merge(float& mx, float& sm, float m2, float s2) {
-    const float mn = fmaxf(mx, m2);
-    if (mn > -INFINITY) sm = sm * __expf(mx - mn) + s2 * __expf(m2 - mn);
-    mx = mn;
-}
-
-// LDS image of the row tile: row r at r * (Dp * 2) bytes, its 16-byte chunk c (8 values) at chunk slot c ^ (r & swz)
-__device__ __forceinline__ int tl_off(int r, int c, int row_bytes, int swz) { return r * row_bytes + ((c ^ (r & swz)) << 4); }
-
 template <typename HT, typename XT>
 __global__ __launch_bounds__(TL_WAVES * 64) void cfm_token_logprob_kernel(cfm_token_logprob_desc d) {
     extern __shared__ __attribute__((aligned(16))) unsigned char tl_smem[];
@@ -91,21 +78,7 @@ __global__ __launch_bounds__(TL_WAVES * 64) void cfm_token_logprob_kernel(cfm_to
         }
         return;
     }
-    const int ksteps = (D + 31) >> 5, nchunk = ksteps * 4, row_bytes = nchunk * 16, swz = (nchunk & 7) ? 3 : 7;
-    for (int idx = tid; idx < TL_ROWS * nchunk; idx += TL_WAVES * 64) {
-        const int r = idx / nchunk, c = idx - r * nchunk, k = c * 8;
-        u32x4 v = {0u, 0u, 0u, 0u};
-        if (row0 + r < M && k < D) {                           // D % 8 == 0: a chunk lies wholly inside a row or wholly in the zero padding
-            if constexpr (cfm_is_f32<XT>) {
-                const float* src = (const float*)d.X + (int64_t)(row0 + r) * d.ldx + k;
-                v = pack8<HT>(*(const f32x4*)src, *(const f32x4*)(src + 4));
-            } else {
-                v = *(const u32x4*)((const u16*)d.X + (int64_t)(row0 + r) * d.ldx + k);
-            }
-        }
-        *(u32x4*)(tl_smem + tl_off(r, c, row_bytes, swz)) = v;
-    }
-    __syncthreads();
+    tl_stage_rows<HT, XT>(tl_smem, d.X, d.ldx, row0, M, D, tid);
 
     const int g = lane >> 4, l15 = lane & 15;
     float mx[4], sm[4], tv[4];
@@ -116,68 +89,10 @@ __global__ __launch_bounds__(TL_WAVES * 64) void cfm_token_logprob_kernel(cfm_to
         tg[s] = r < M ? d.target[r] : -1;
         mx[s] = -INFINITY, sm[s] = 0.f, tv[s] = 0.f;
     }
-    const u16* W = (const u16*)d.W;
-    const int ntile = (V + 31) >> 5;
-    for (int ct = wave; ct < ntile; ct += TL_WAVES) {
-        const int c0 = ct * 32;
-        // A operand: lane holds W[class c0 + 16 t + l15][k = 32 ks + 8 g ..+8]; classes at and past V read row V - 1 and are masked below
-        const u16* w0 = W + (int64_t)min(c0 + l15, V - 1) * D + g * 8;
-        const u16* w1 = W + (int64_t)min(c0 + 16 + l15, V - 1) * D + g * 8;
-        f32x4 acc[2][4];
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int s = 0; s < 4; ++s) acc[t][s] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        for (int ks = 0; ks < ksteps; ++ks) {
-            u32x4 a0 = {0u, 0u, 0u, 0u}, a1 = {0u, 0u, 0u, 0u};
-            if (ks * 32 + g * 8 < D) {
-                a0 = *(const u32x4*)(w0 + ks * 32);
-                a1 = *(const u32x4*)(w1 + ks * 32);
-            }
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const u32x4 b = *(const u32x4*)(tl_smem + tl_off(s * 16 + l15, ks * 4 + g, row_bytes, swz));
-                acc[0][s] = HT::mfma(a0, b, acc[0][s]);
-                acc[1][s] = HT::mfma(a1, b, acc[1][s]);
-            }
-        }
-        // this lane's 8 classes of the tile: c0 + 16 t + 4 g + e
-        float bv[8];                                           // -inf at and past V: the sum with the (finite) product masks the class
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int c = c0 + t * 16 + g * 4 + e;
-                bv[t * 4 + e] = c < V ? d.bias[c] : -INFINITY;
-            }
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            float v[8];
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[t * 4 + e] = acc[t][s][e] + bv[t * 4 + e];
-            float tm = v[0];
-#pragma unroll
-            for (int q = 1; q < 8; ++q) tm = fmaxf(tm, v[q]);
-            const float mn = fmaxf(mx[s], tm);
-            if (mn > -INFINITY) {
-                float add = 0.f;
-#pragma unroll
-                for (int q = 0; q < 8; ++q) add += __expf(v[q] - mn);
-                sm[s] = sm[s] * __expf(mx[s] - mn) + add;
-                mx[s] = mn;
-            }
-            const int dt = tg[s] - c0;
-            if (dt >= 0 && dt < 32 && ((dt >> 2) & 3) == g) {  // exactly one lane of the row's four, in exactly one tile, holds the target's logit
-                const int q = (dt >> 4) * 4 + (dt & 3);
-                float pick = v[0];
-#pragma unroll
-                for (int qq = 1; qq < 8; ++qq) pick = q == qq ? v[qq] : pick;
-                tv[s] = pick;
-            }
-        }
-    }
+    tl_tiles<HT>(tl_smem, (const u16*)d.W, d.bias, D, V, wave, TL_WAVES, (V + 31) >> 5, lane, [&](int c0, int s, const float (&v)[8]) {
+        tl_fold_lse(mx[s], sm[s], v);
+        tl_pick_target(tv[s], tg[s], c0, g, v);
+    });
     // the four lanes of a row (g = 0..3): xor 16, then xor 32
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
@@ -259,9 +174,7 @@ extern "C" int cfm_token_logprob(const cfm_token_logprob_desc* d, cfm_stream_t s
     const int xa = d->x_dtype == CFM_F32 ? 4 : 8;
     CFM_CHECK_ARG(d->ldx >= d->D && d->ldx % xa == 0 && ((uintptr_t)d->X & 15) == 0 && ((uintptr_t)d->W & 15) == 0,
                   "cfm_token_logprob: X and W must be 16-byte aligned, ldx=%lld a multiple of %d and >= D", (long long)d->ldx, xa);
-    const int ksteps = (d->D + 31) / 32;
-    const size_t image = (size_t)TL_ROWS * ksteps * 64, parts = (size_t)TL_WAVES * 3 * TL_ROWS * sizeof(float);
-    const size_t lds = image > parts ? image : parts;
+    const size_t lds = tl_lds_bytes(d->D, 3);
     const dim3 grid((unsigned)((d->M + TL_ROWS - 1) / TL_ROWS)), block(TL_WAVES * 64);
     CfmProfScope prof("token_logprob", s, 2.0 * d->M * d->V * d->D, (double)d->M * d->D * cfm_elt_size(d->x_dtype) + (double)grid.x * d->V * d->D * 2);
     if (d->w_dtype == CFM_BF16) {

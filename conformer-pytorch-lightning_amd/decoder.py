@@ -323,6 +323,66 @@ class BiTransformerDecoder(nn.Module):
         return left_outputs, right_outputs, output_lengths
 
 
+class AttentionLoss(nn.Module):
+    """The attention head's training loss (the reference's commented-out loss_attn, model.py:85): label-smoothed cross entropy of the left decoder
+    on (sos + y, y + eos) and, when reverse_weight > 0, of the right decoder on the reversed labels:
+
+        loss_att = (1 - reverse_weight) * loss_left + reverse_weight * loss_right
+
+    forward(encoder_out [B, T, D], encoder_mask bool [B, 1, T], padded_labels [B, U] (ignore_id: padding), label_lengths [B]) returns
+    (loss_att, loss_left, loss_right).  Train mode: one cfm.autograd.DecoderLossFn per decoder -- gradients for every decoder parameter and for
+    encoder_out.  Eval mode: the same value, nothing saved, no gradient.  The loss is divided by the batch size, or with normalize_length by the
+    number of target tokens.  The eval-only entry points of the decoders (forward, AttentionRescorer) are unchanged."""
+
+    def __init__(self, decoder, lsm_weight=0.0, reverse_weight=0.0, sos=None, eos=None, ignore_id=-1, normalize_length=False, fused=False):
+        super().__init__()
+        if isinstance(decoder, BiTransformerDecoder):
+            left, right = decoder.left_decoder, decoder.right_decoder
+        elif isinstance(decoder, TransformerDecoder):
+            left, right = decoder, None
+        else:
+            raise TypeError("AttentionLoss: decoder is a TransformerDecoder or a BiTransformerDecoder, got %s" % type(decoder).__name__)
+        self.decoder = decoder
+        self.lsm_weight, self.reverse_weight = float(lsm_weight), float(reverse_weight)
+        if not 0.0 <= self.reverse_weight <= 1.0 or not 0.0 <= self.lsm_weight < 1.0:
+            raise ValueError("AttentionLoss: reverse_weight in [0, 1] and lsm_weight in [0, 1), got %r and %r" % (reverse_weight, lsm_weight))
+        if self.reverse_weight > 0.0 and right is None:
+            raise ValueError("AttentionLoss: reverse_weight > 0 needs a BiTransformerDecoder (a right decoder)")
+        V = left.output_layer.out_features
+        self.sos = V - 1 if sos is None else int(sos)
+        self.eos = V - 1 if eos is None else int(eos)
+        self.ignore_id, self.normalize_length, self.fused = int(ignore_id), bool(normalize_length), bool(fused)
+
+    def _one(self, dec, encoder_out, mem_mask8, labels, prec):
+        from cfm import autograd as ag
+        from utils import add_sos_eos, make_subsequent_mask
+        ys_in, ys_out = add_sos_eos(labels, self.sos, self.eos, self.ignore_id)
+        B, Lc = ys_in.shape
+        valid = ys_out != self.ignore_id                                                      # position i is a real one: i < L + 1
+        self_mask = valid.unsqueeze(1) & make_subsequent_mask(Lc, ys_in.device).unsqueeze(0)   # [B, Lc, Lc]: j <= i and j < L + 1
+        tgt = torch.where(valid, ys_out, torch.full_like(ys_out, -1)).to(torch.int32)
+        args = (dec, ys_in.to(torch.int32), tgt, cfm.as_u8_mask(self_mask), mem_mask8, prec, self.lsm_weight, 0 if self.normalize_length else B)
+        if dec.training:
+            return ag.DecoderLossFn.apply(encoder_out, *args, ag.draw_seed(), self.fused, *dec.parameters())
+        with torch.no_grad():
+            return ag.DecoderLossFn.apply(encoder_out.detach(), *args, 0, self.fused)
+
+    def forward(self, encoder_out, encoder_mask, padded_labels, label_lengths):
+        from utils import reverse_sequence
+        cfm.require_hip(encoder_out, encoder_mask, padded_labels)                             # no CPU path
+        prec = cfm.resolve_precision(self.decoder)
+        B, T = encoder_out.shape[0], encoder_out.shape[1]
+        mem_mask8 = cfm.as_u8_mask(encoder_mask.expand(B, 1, T))
+        left = self.decoder.left_decoder if isinstance(self.decoder, BiTransformerDecoder) else self.decoder
+        labels = padded_labels.long()
+        loss_left = self._one(left, encoder_out, mem_mask8, labels, prec)
+        loss_right = torch.zeros((), dtype=torch.float32, device=encoder_out.device)
+        if self.reverse_weight > 0.0:
+            r = reverse_sequence(labels, label_lengths, self.ignore_id).long()
+            loss_right = self._one(self.decoder.right_decoder, encoder_out, mem_mask8, r, prec)
+        return (1.0 - self.reverse_weight) * loss_left + self.reverse_weight * loss_right, loss_left, loss_right
+
+
 class AttentionRescorer:
     """Second pass over n-best lists: every hypothesis is scored by the attention decoder against its utterance's encoder output and the lists are
     re-ranked (the definition: tests/attention_decoder_ref.py; the kernels: csrc/rescore.hip).

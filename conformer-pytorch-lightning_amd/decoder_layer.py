@@ -10,7 +10,8 @@ as cfm kernels on row matrices: cfm.layernorm, the fused q|k|v projection, cfm.a
 product with the residual in the GEMM epilogue (the stream x stays float32).  `layer_rows` is the one implementation; it takes the self-attention
 and the cross-attention batch shapes separately, because a rescoring pass runs self-attention over P = B*N hypotheses of Lc positions and
 cross-attention as B utterances of N*Lc queries -- so the memory's keys and values are projected once per utterance and layer, not once per
-hypothesis.  Train mode raises: cross-attention has no backward (attention._attend_train refuses key is not query)."""
+hypothesis.  These entry points are eval-only and raise in train mode; the decoder is trained through decoder.AttentionLoss
+(cfm.autograd.DecoderLossFn), which runs the same layer with its backward."""
 import torch
 import torch.nn as nn
 

@@ -26,12 +26,20 @@ import utils
 
 class TransducerObjective(nn.Module):
 
-    def __init__(self, encoder, predictor, joint, ctc, blank=0, ignore_id=-1, ctc_weight=0.0, transducer_weight=1.0, packed=True):
+    def __init__(self, encoder, predictor, joint, ctc, blank=0, ignore_id=-1, ctc_weight=0.0, transducer_weight=1.0, packed=True, attention=None,
+                 attention_weight=0.0, lsm_weight=0.0, reverse_weight=0.0):
+        """attention: a decoder.TransformerDecoder / BiTransformerDecoder; the objective then adds attention_weight * loss_attn
+        (decoder.AttentionLoss with lsm_weight and reverse_weight, model.py:85).  Without it nothing changes."""
         super().__init__()
         self.encoder, self.predictor, self.joint, self.ctc = encoder, predictor, joint, ctc
         self.blank, self.ignore_id = blank, ignore_id
         self.ctc_weight, self.transducer_weight = ctc_weight, transducer_weight
         self.packed = packed
+        self.attention_weight = float(attention_weight)
+        self.attention_loss = None
+        if attention is not None:
+            import decoder
+            self.attention_loss = decoder.AttentionLoss(attention, lsm_weight=lsm_weight, reverse_weight=reverse_weight, ignore_id=ignore_id)
 
     def _text(self, labels):
         return torch.where(labels == self.ignore_id, self.blank, labels).to(torch.int32)
@@ -49,7 +57,11 @@ class TransducerObjective(nn.Module):
         loss_rnnt = self.rnnt_loss(encoder_out, encoder_out_lens, padded_labels, label_lengths)
         loss_ctc = self.ctc(encoder_out, encoder_out_lens, padded_labels, label_lengths).sum()
         loss = self.ctc_weight * loss_ctc + self.transducer_weight * loss_rnnt
-        return {"loss": loss, "loss_ctc": loss_ctc, "loss_rnnt": loss_rnnt, "encoder_out": encoder_out, "encoder_out_lens": encoder_out_lens}
+        out = {"loss": loss, "loss_ctc": loss_ctc, "loss_rnnt": loss_rnnt, "encoder_out": encoder_out, "encoder_out_lens": encoder_out_lens}
+        if self.attention_loss is not None:
+            out["loss_attn"] = self.attention_loss(encoder_out, encoder_mask, padded_labels, label_lengths)[0]
+            out["loss"] = loss + self.attention_weight * out["loss_attn"]
+        return out
 
     def forward_window(self, micro_batches):
         """The losses of an accumulation window's micro-batches (each the reference's 6-tuple), a 1-D tensor whose entry g equals
@@ -72,7 +84,11 @@ class TransducerObjective(nn.Module):
             groups.append((B, T, lens, pred[s:s + B, :U1], self._text(lab), mb[4]))
             s += B
         loss_rnnt = self.joint.forward_window(rows, groups, blank=self.blank)
-        return self.ctc_weight * loss_ctc + self.transducer_weight * loss_rnnt
+        loss = self.ctc_weight * loss_ctc + self.transducer_weight * loss_rnnt
+        if self.attention_loss is not None:                   # one decoder pass per micro-batch, on its slice of the encoder rows
+            attn = [self.attention_loss(y, mask, mb[3], mb[4])[0] for (y, mask), mb in zip(outs, micro_batches)]
+            loss = loss + self.attention_weight * torch.stack(attn)
+        return loss
 
 
 def _check_ctc(ctc, encoder, who):

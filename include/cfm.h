@@ -109,7 +109,7 @@ typedef struct {
     int64_t ld_aux;
     /* dropout on the OUTPUT element (m,n), after the activation and before row_mask / residual (train mode): kept with probability 1-p and
      * scaled by 1/(1-p); the mask is a pure function of (seed, m*N_out + n) (csrc/cfm_common.h cfm_hash32), so the backward passes the same
-     * (p, seed) instead of reading a stored mask.  CFM_ACT_DSILU applies it to acc (the gradient arriving at the dropped activation).
+     * (p, seed) instead of reading a stored mask.  CFM_ACT_DSILU / CFM_ACT_DRELU apply it to acc (the gradient arriving at the dropped activation).
      * drop2: a second, independent mask on the same element (the plain MHSA's extra dropout after linear_out, attention.py:177). */
     float drop_p, drop2_p;
     uint32_t drop_seed, drop2_seed;
@@ -1583,6 +1583,60 @@ typedef struct {
     float first_pass_weight, reverse_weight;
 } cfm_rescore_combine_desc;
 int cfm_rescore_combine(const cfm_rescore_combine_desc* d, cfm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Label-smoothing loss of the attention decoder (csrc/lsm.hip; the reference's label_smoothing_loss.py:52-80; the definition in float64 is
+ * tests/attention_loss_ref.py).  Per row m with target t = target[m] >= 0 over V classes, smoothing s, e = s / (V - 1): the target
+ * distribution is q_c = 1 - s at c = t and e elsewhere, and the row's loss is the divergence sum_c q_c (log q_c - logp_c), 0 log 0 = 0.
+ * With z the logits, lse their logsumexp and S = sum_{c < V} z_c this is
+ *     loss[m] = C(s, V) - (1 - s - e) (z_t - lse) - e (S - V lse),     C = (1 - s) log(1 - s) + s log e   (evaluated in double on the host)
+ * A row with target < 0 is ignored: loss = 0, lse = 0, dz = 0.  target >= V gives NaN.  0 <= s < 1; s > 0 needs V >= 2.
+ *
+ * cfm_lsm_loss: the forward.  X, W, bias, D, V, ldx, the dtypes and every limit are cfm_token_logprob's (D % 8 == 0, D <= 512, rows and
+ *   bias entries V..Vp never read), and so are the product, the online logsumexp and the target gather: the two kernels include ONE product
+ *   loop (csrc/vocab_tile.h).  A running f32 sum of the logits rides along; all combined in a fixed order, no atomics, the same input gives
+ *   the same bits.  Writes loss f32 [M] and lse f32 [M] (both required: the backward reads lse).
+ *   logits != NULL (f32 [M, >= V], rows ld apart): the product is skipped, one wavefront per row (the fp32 precision mode, and callers that
+ *   hold logits). */
+typedef struct {
+    const void* X;
+    const void* W;
+    const float* bias;
+    const float* logits;
+    const int32_t* target;
+    float* loss;
+    float* lse;
+    int64_t ldx, ld;
+    int32_t M, D, V, x_dtype, w_dtype;
+    float smoothing;
+} cfm_lsm_loss_desc;
+int cfm_lsm_loss(const cfm_lsm_loss_desc* d, cfm_stream_t stream);
+
+/* cfm_lsm_grad: the backward.  dz[m][c] = g[m] (exp(z_c - lse[m]) - q_c) for c < V and exactly 0 for V <= c < Vk, as [M, Vk] with rows ldz
+ *   apart: the operand of the projection's gradient products (dX = cfm_gemm(dz, W^T pack) with K = Vk; dW, db = cfm_gemm_tn(dz, X)).
+ *   lse f32 [M] is the forward's; g f32 [M] the per-row scale (the upstream gradient over the denominator; ignored rows write 0 whatever g
+ *   holds).  Vk >= V, Vk % 4 == 0, ldz >= Vk, ldz % 4 == 0, dz 16-byte aligned.  The logits are recomputed tile by tile on the forward's
+ *   product loop and never stored; dz is of W's type.  Nothing past column Vk of a row, or past row M, is written.  Plain vector stores only.
+ *   logits != NULL: elementwise over stored f32 logits; dz_dtype is f32, bf16 or fp16. */
+typedef struct {
+    const void* X;
+    const void* W;
+    const float* bias;
+    const float* logits;
+    const int32_t* target;
+    const float* lse;
+    const float* g;
+    void* dz;
+    int64_t ldx, ld, ldz;
+    int32_t M, D, V, Vk, x_dtype, w_dtype, dz_dtype;
+    float smoothing;
+} cfm_lsm_grad_desc;
+int cfm_lsm_grad(const cfm_lsm_grad_desc* d, cfm_stream_t stream);
+
+/* cfm_lsm_reduce: out[0] = sum_m loss[m] / denom and out[1] = denom, one workgroup, a fixed order, no host read.  denom = batch when
+ *   batch > 0 (the reference's default), else the number of targets >= 0 (normalize_length), at least 1: a call without one valid target
+ *   gives 0 where the reference gives 0 / 0 -- the one deliberate difference. */
+int cfm_lsm_reduce(const float* loss, const int32_t* target, int32_t M, int32_t batch, float* out, cfm_stream_t stream);
 
 #ifdef __cplusplus
 }
