@@ -174,6 +174,17 @@ class RnntPackedDesc(ctypes.Structure):
                 ("gscale_stride", c_i32), ("gscale_dev", c_p), ("clamp", ctypes.c_float)]
 
 
+_ALIGN_OUT = [("frame", c_p), ("token_logp", c_p), ("score", c_p), ("scratch", c_p), ("scratch_bytes", c_i64)]
+
+
+class RnntAlignDesc(ctypes.Structure):
+    _fields_ = [("r", RnntDesc)] + _ALIGN_OUT
+
+
+class RnntPackedAlignDesc(ctypes.Structure):
+    _fields_ = [("r", RnntPackedDesc)] + _ALIGN_OUT
+
+
 class LnBwdDesc(ctypes.Structure):
     _fields_ = [("x", c_p), ("dy", c_p), ("gamma", c_p), ("row_mask", c_p), ("dres", c_p), ("dx", c_p), ("dgamma", c_p), ("dbeta", c_p), ("ws", c_p),
                 ("dx2", c_p), ("M", c_i64), ("D", c_i32), ("dy_dtype", c_i32), ("dx2_dtype", c_i32), ("accumulate", c_i32),
@@ -329,7 +340,7 @@ for _c_name, _cls in dict(
         cfm_gemm_desc=GemmDesc, cfm_gemm_tn_desc=GemmTnDesc, cfm_attn_bwd_desc=AttnBwdDesc, cfm_attn_desc=AttnDesc, cfm_ffn_desc=FfnDesc, cfm_rowchain_desc=RowChainDesc,
         cfm_layer_train_weights=LayerTrainWeights, cfm_train_group=TrainGroup, cfm_layer_train_io=LayerTrainIO, cfm_layer_train_saved=LayerTrainSaved,
         cfm_layer_train_scratch=LayerTrainScratch, cfm_layer_train_grads=LayerTrainGrads, cfm_layer_weights=LayerWeights, cfm_ctc_group=CtcGroup,
-        cfm_rnnt_desc=RnntDesc, cfm_lattice=Lattice, cfm_rnnt_packed_desc=RnntPackedDesc, cfm_ln_bwd_desc=LnBwdDesc, cfm_lstm_desc=LstmDesc, cfm_greedy_desc=GreedyDesc,
+        cfm_rnnt_desc=RnntDesc, cfm_lattice=Lattice, cfm_rnnt_packed_desc=RnntPackedDesc, cfm_rnnt_align_desc=RnntAlignDesc, cfm_rnnt_packed_align_desc=RnntPackedAlignDesc, cfm_ln_bwd_desc=LnBwdDesc, cfm_lstm_desc=LstmDesc, cfm_greedy_desc=GreedyDesc,
         cfm_greedy_chunk_desc=GreedyChunkDesc, cfm_ctc_greedy_desc=CtcGreedyDesc, cfm_ctc_beam_desc=CtcBeamDesc, cfm_ctc_align_desc=CtcAlignDesc, cfm_edit_distance_desc=EditDistanceDesc, cfm_rnnt_beam_desc=RnntBeamDesc, cfm_rnnt_beam_stream_desc=RnntBeamStreamDesc, cfm_fbank_desc=FbankDesc, cfm_resample_desc=ResampleDesc,
         cfm_resample_bank=ResampleBank, cfm_resample_group_desc=ResampleGroupDesc, cfm_spec_augment_desc=SpecAugmentDesc,
         cfm_rescore_prep_desc=RescorePrepDesc, cfm_token_logprob_desc=TokenLogprobDesc, cfm_rescore_combine_desc=RescoreCombineDesc, cfm_lsm_loss_desc=LsmLossDesc, cfm_lsm_grad_desc=LsmGradDesc,
@@ -381,6 +392,9 @@ PROTOTYPES = (
     ("cfm_joint_act_packed_bwd", c_int, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, P(Lattice), c_i32, c_p),
     ("cfm_rnnt_packed_nll", c_int, P(RnntPackedDesc), c_p),
     ("cfm_rnnt_packed_grad", c_int, P(RnntPackedDesc), c_p),
+    ("cfm_rnnt_align_scratch_bytes", c_i64, c_i64),
+    ("cfm_rnnt_align", c_int, P(RnntAlignDesc), c_p),
+    ("cfm_rnnt_packed_align", c_int, P(RnntPackedAlignDesc), c_p),
     ("cfm_layernorm_bwd_ws", c_i64, c_i64, c_i32),
     ("cfm_layernorm_bwd_fused", c_int, P(LnBwdDesc), c_p),
     ("cfm_glu_bwd", c_int, c_p, c_i32, c_p, c_i32, c_p, c_i32, c_i64, c_i32, c_p),

@@ -7,7 +7,7 @@ import torch
 import cfm as _c
 
 __all__ = ["rescore_prep", "token_logprob", "rescore_combine", "lsm_loss", "lsm_grad", "lsm_reduce", "lstm_forward", "lstm_backward", "fbank", "fbank_stream", "fbank_stream_ragged", "resample", "resample_stream", "resample_group", "spec_augment", "stream_prep", "stream_advance", "dwconv_causal_bn_silu", "conv_cache_update", "dropout_rows", "dropout_mask", "set_deterministic", "gemm_tn", "gemm_tn_group", "layernorm_bwd", "glu_bwd", "dwconv_bn_train", "dwconv_bn_train_bwd", "dwconv_bn_train_groups", "dwconv_bn_train_bwd_groups", "col2im_relu_bwd", "conv1_wgrad", "attention_bwd", "attention_group", "attention_bwd_group",
-           "ctc_nll_train_groups", "ctc_grad", "rnnt_nll", "rnnt_grad", "joint_act_bwd", "rnnt_nll_packed", "joint_act_packed", "joint_act_packed_bwd", "ffn_split", "adam_step", "adam_clip_step", "sumsq", "scratch_stats",
+           "ctc_nll_train_groups", "ctc_grad", "rnnt_nll", "rnnt_grad", "joint_act_bwd", "rnnt_nll_packed", "rnnt_align", "rnnt_align_packed", "joint_act_packed", "joint_act_packed_bwd", "ffn_split", "adam_step", "adam_clip_step", "sumsq", "scratch_stats",
            "gemm", "ffn_fused", "ffn_fused_supported", "rowchain", "rowchain_supported", "rowchain_pair_supported", "layernorm", "attention", "kv_cache_pack", "dwconv_bn_silu", "conv1_relu", "conv1_relu_mma_supported", "conv12_relu", "conv12_supported", "ctc_nll", "ctc_topk", "ctc_greedy", "ctc_greedy_state", "ctc_prefix_beam", "ctc_align", "edit_distance", "joint_act", "valid_mask", "chunk_mask",
            "attn_mask_combine", "cast", "add_rows", "scratch", "prof_enable", "prof_reset", "prof_table", "as_u8_mask"]
 
@@ -1142,14 +1142,43 @@ class RnntState:
         raise AttributeError(name)
 
 
-def _rnnt_state(d, what, logits, ld, V, blank, targets, nodes, B, shift_cols):
-    """The part of rnnt_nll / rnnt_nll_packed both layouts share: the V check, the state arrays (nodes: their per-node shape) and the descriptor
-    fields common to cfm_rnnt_desc and cfm_rnnt_packed_desc.  An empty array gets nll's address (the C checks want a pointer; nothing is read),
-    empty targets none."""
+def _rnnt_vocab(what, logits, V):
     W = logits.shape[-1]
     V = W if V is None else V
     if not 1 < V <= W:
         raise ValueError("cfm.%s: V = %d with %d columns" % (what, V, W))
+    return V
+
+
+def _rnnt_padded_args(what, logits, targets, logit_lens, target_lens):
+    """The operands of the padded RNN-T entries: logits [B,T,U+1,>=V] with evenly spaced rows, targets int32 [B,U], lengths int32 [B].
+    -> (B, T, U1, row stride)."""
+    _c.require_hip(logits, targets, logit_lens, target_lens)
+    if logits.dim() != 4 or logits.stride(3) != 1:
+        raise ValueError("cfm.%s: logits must be [B,T,U+1,V] with unit inner stride, got %s strides %s" % (what, tuple(logits.shape), logits.stride()))
+    B, T, U1 = logits.shape[:3]
+    ld = logits.stride(2)
+    if logits.stride(1) != U1 * ld or logits.stride(0) != T * U1 * ld:
+        raise ValueError("cfm.%s: logits rows must be evenly spaced (strides %s)" % (what, logits.stride(),))
+    _layout(what, "to match logits %s" % (tuple(logits.shape),), targets=(targets, _I32, (B, U1 - 1)), **_i32(B, logit_lens=logit_lens, target_lens=target_lens))
+    return B, T, U1, ld
+
+
+def _rnnt_packed_args(what, logits, targets, lat):
+    """The operands of the packed RNN-T entries: logits [M, >=V], targets int32 [B, >= max U] contiguous."""
+    _c.require_hip(logits, targets)
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[0] != lat.M:
+        raise ValueError("cfm.%s: logits must be [M=%d, V] with unit inner stride, got %s strides %s" % (what, lat.M, tuple(logits.shape), logits.stride()))
+    _layout(what, targets=(targets, _I32, (lat.B, None)))
+    if targets.shape[1] < lat.U1_max - 1:
+        raise ValueError("cfm.%s: targets must be int32 [B=%d, >=%d], got %s" % (what, lat.B, lat.U1_max - 1, tuple(targets.shape)))
+
+
+def _rnnt_state(d, what, logits, ld, V, blank, targets, nodes, B, shift_cols):
+    """The part of rnnt_nll / rnnt_nll_packed both layouts share: the V check, the state arrays (nodes: their per-node shape) and the descriptor
+    fields common to cfm_rnnt_desc and cfm_rnnt_packed_desc.  An empty array gets nll's address (the C checks want a pointer; nothing is read),
+    empty targets none."""
+    V = _rnnt_vocab(what, logits, V)
     dev = logits.device
     f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
     tens = dict(lse=f(*nodes), lp_blank=f(*nodes), lp_label=f(*nodes), alpha=f(*nodes), beta=f(*nodes), shift=f(B, shift_cols), nll=f(B),
@@ -1167,14 +1196,7 @@ def rnnt_nll(logits, targets, logit_lens, target_lens, blank, V=None):
     fp16), targets int32 [B,U], logit_lens / target_lens int32 [B] (include/cfm.h cfm_rnnt_nll).  V defaults to logits.size(3) (pass it when the
     last axis holds pad columns).  Returns (nll f32 [B], RnntState) -- the state carries lse / lp_blank / lp_label / alpha / beta / shift /
     nll_shifted / ll_alpha for rnnt_grad and for tests."""
-    _c.require_hip(logits, targets, logit_lens, target_lens)
-    if logits.dim() != 4 or logits.stride(3) != 1:
-        raise ValueError("cfm.rnnt_nll: logits must be [B,T,U+1,V] with unit inner stride, got %s strides %s" % (tuple(logits.shape), logits.stride()))
-    B, T, U1 = logits.shape[:3]
-    ld = logits.stride(2)
-    if logits.stride(1) != U1 * ld or logits.stride(0) != T * U1 * ld:
-        raise ValueError("cfm.rnnt_nll: logits rows must be evenly spaced (strides %s)" % (logits.stride(),))
-    _layout("rnnt_nll", "to match logits %s" % (tuple(logits.shape),), targets=(targets, _I32, (B, U1 - 1)), **_i32(B, logit_lens=logit_lens, target_lens=target_lens))
+    B, T, U1, ld = _rnnt_padded_args("rnnt_nll", logits, targets, logit_lens, target_lens)
     d = _c.RnntDesc()
     tens = _rnnt_state(d, "rnnt_nll", logits, ld, V, blank, targets, (B, T, U1), B, T + U1)
     tens.update(logit_lens=logit_lens, target_lens=target_lens)
@@ -1268,12 +1290,7 @@ def rnnt_nll_packed(logits, targets, lat, blank, V=None):
     """RNN-T negative log-likelihood per utterance over a packed lattice (cfm.lattice.Lattice): UN-normalised logits [M, >=V] (unit inner stride;
     f32 / bf16 / fp16), targets int32 [B, >= max U] contiguous (include/cfm.h cfm_rnnt_packed_nll).  Returns (nll f32 [B], RnntState) as rnnt_nll;
     the state's lse / lp_blank / lp_label / alpha / beta are [M]."""
-    _c.require_hip(logits, targets)
-    if logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[0] != lat.M:
-        raise ValueError("cfm.rnnt_nll_packed: logits must be [M=%d, V] with unit inner stride, got %s strides %s" % (lat.M, tuple(logits.shape), logits.stride()))
-    _layout("rnnt_nll_packed", targets=(targets, _I32, (lat.B, None)))
-    if targets.shape[1] < lat.U1_max - 1:
-        raise ValueError("cfm.rnnt_nll_packed: targets must be int32 [B=%d, >=%d], got %s" % (lat.B, lat.U1_max - 1, tuple(targets.shape)))
+    _rnnt_packed_args("rnnt_nll_packed", logits, targets, lat)
     M = lat.M
     d = _c.RnntPackedDesc()
     tens = _rnnt_state(d, "rnnt_nll_packed", logits, logits.stride(0), V, blank, targets, (M,), lat.B, lat.T_max + lat.U1_max)
@@ -1283,6 +1300,57 @@ def rnnt_nll_packed(logits, targets, lat, blank, V=None):
     d.lat, d.ld_targets = lat.desc, targets.shape[1]
     _c.call("cfm_rnnt_packed_nll", ctypes.byref(d))
     return tens["nll"], RnntState(d, logits, tens, (M,))
+
+
+def _rnnt_align(ad, what, logits, ld, V, blank, targets, nodes, B, Umax, out):
+    """What rnnt_align / rnnt_align_packed share: the V check, the outputs (checked when the caller owns them), the work arrays from the arena
+    (lse, lp_blank, lp_label [nodes], the recorded moves) and the descriptor fields both layouts have."""
+    r, dev = ad.r, logits.device
+    r.V, r.blank = _rnnt_vocab(what, logits, V), blank
+    if out is None:
+        out = (torch.empty((B, Umax), dtype=_I32, device=dev), torch.empty((B, Umax), dtype=_F32, device=dev), torch.empty((B,), dtype=_F32, device=dev))
+    frame, token_logp, score = out
+    _want(what, "out must be (frame int32 [B,Umax], token_logp float32 [B,Umax], score float32 [B]) with B = %d, Umax = %d" % (B, Umax),
+          frame=(frame, _I32, (B, Umax)), token_logp=(token_logp, _F32, (B, Umax)), score=(score, _F32, (B,)))
+    nbytes = int(_c.lib().cfm_rnnt_align_scratch_bytes(nodes))
+    work = scratch("rnnt_align_work", 3 * nodes, _F32, dev)
+    moves = scratch("rnnt_align_moves", nbytes, torch.uint8, dev)
+    r.logits, r.ld, r.logits_dtype = logits.data_ptr(), ld, _c.dt_code(logits)
+    r.targets = targets.data_ptr() if targets.numel() else None
+    r.lse, r.lp_blank, r.lp_label = (work.data_ptr() + 4 * k * nodes for k in range(3))
+    ad.frame, ad.token_logp, ad.score = _c.ptr(frame) or None, _c.ptr(token_logp) or None, _c.ptr(score)
+    ad.scratch, ad.scratch_bytes = _c.ptr(moves) or None, nbytes
+    return frame, token_logp, score
+
+
+def rnnt_align(logits, targets, logit_lens, target_lens, blank, V=None, out=None):
+    """RNN-T forced alignment: the best single alignment of each utterance's frames to its labels over the transducer lattice, from UN-normalised
+    logits [B,T,U+1,>=V] (as rnnt_nll takes them: rows evenly spaced, unit inner stride, f32 / bf16 / fp16), targets int32 [B,U], logit_lens /
+    target_lens int32 [B].  Returns (frame int32 [B,U], token_logp f32 [B,U], score f32 [B]) on the device: frame[b,u] the frame at which label u
+    is emitted (nondecreasing in u), token_logp its log-probability there, score the path's log-probability; -1 / -inf beyond target_lens[b], and
+    score -inf with that fill everywhere for an utterance without a frame.  out: such a tuple to write into.  include/cfm.h cfm_rnnt_align states
+    the recursion and its tie rule."""
+    B, T, U1, ld = _rnnt_padded_args("rnnt_align", logits, targets, logit_lens, target_lens)
+    ad = _c.RnntAlignDesc()
+    res = _rnnt_align(ad, "rnnt_align", logits, ld, V, blank, targets, B * T * U1, B, U1 - 1, out)
+    ad.r.B, ad.r.T, ad.r.U1 = B, T, U1
+    ad.r.logit_lens, ad.r.target_lens = logit_lens.data_ptr(), target_lens.data_ptr()
+    _c.call("cfm_rnnt_align", ctypes.byref(ad))
+    return res
+
+
+def rnnt_align_packed(logits, targets, lat, blank, V=None, out=None):
+    """rnnt_align over a packed lattice (cfm.lattice.Lattice): logits [M, >=V] hold the valid nodes only, targets int32 [B, >= max U] contiguous
+    (include/cfm.h cfm_rnnt_packed_align).  Returns (frame int32 [B,U1_max-1], token_logp f32 [B,U1_max-1], score f32 [B]) -- the same bits as
+    rnnt_align on the same nodes."""
+    _rnnt_packed_args("rnnt_align_packed", logits, targets, lat)
+    ad = _c.RnntPackedAlignDesc()
+    res = _rnnt_align(ad, "rnnt_align_packed", logits, logits.stride(0), V, blank, targets, lat.M, lat.B, lat.U1_max - 1, out)
+    if not lat.M:                                                      # no node: nothing is read, but the row-pass checks want a pointer
+        ad.r.logits, ad.r.ld = res[2].data_ptr(), ad.r.V
+    ad.r.lat, ad.r.ld_targets = lat.desc, targets.shape[1]
+    _c.call("cfm_rnnt_packed_align", ctypes.byref(ad))
+    return res
 
 
 def adam_step(p, g, m, v, lr, betas, eps, weight_decay, step, grad_scale=None):

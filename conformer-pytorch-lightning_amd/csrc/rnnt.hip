@@ -139,27 +139,10 @@ __global__ __launch_bounds__(256) void cfm_rnnt_rows_kernel(D d) {
     }
 }
 
-// ---- alpha | beta: one workgroup per (utterance, direction), PER columns per thread, the neighbour column through LDS ----
-template <int NT, int PER, typename Desc>
-__device__ __forceinline__ void rnnt_sweep(const Desc& d, const int b, const bool fwd) {
-    __shared__ float sh_o[RNNT_MAXT];
-    __shared__ float sh_q[RNNT_MAXU1];
-    __shared__ float pub[2][RNNT_MAXU1 + 2];
-    __shared__ double red[NT];
+// the shifts of one utterance into LDS (no barrier): o_t over the valid columns (a wavefront per frame), q_u over the valid frames (a thread per label)
+template <int NT>
+__device__ __forceinline__ void rnnt_shifts(const float* lb, const float* ll, const int U1, const int Tb, const int Ub, float* sh_o, float* sh_q) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const UttGeo g = utt_geo(d, b);
-    const int U1 = g.ld, Tb = g.Tb, Ub = g.Ub;
-    if (Tb == 0) {                                         // no frame: no alignment (torchaudio rejects it); +inf, zero gradient
-        if (tid == 0) {
-            if (fwd) d.ll_alpha[b] = -INFINITY;
-            else d.nll[b] = d.nll_shifted[b] = INFINITY;
-        }
-        return;
-    }
-    const int64_t base = g.base;
-    const float* lb = d.lp_blank + base;
-    const float* ll = d.lp_label + base;
-    // shifts: o_t over the valid columns (a wavefront per frame), q_u over the valid frames (a thread per label)
     for (int t = wave; t < Tb; t += NT / 64) {
         float m = -INFINITY;
         for (int u = lane; u <= Ub; u += 64) m = fmaxf(m, lb[(int64_t)t * U1 + u]);
@@ -179,6 +162,29 @@ __device__ __forceinline__ void rnnt_sweep(const Desc& d, const int b, const boo
         const float m = fmaxf(fmaxf(m0, m1), fmaxf(m2, m3));
         sh_q[u] = m > -INFINITY ? m : 0.f;
     }
+}
+
+// ---- alpha | beta: one workgroup per (utterance, direction), PER columns per thread, the neighbour column through LDS ----
+template <int NT, int PER, typename Desc>
+__device__ __forceinline__ void rnnt_sweep(const Desc& d, const int b, const bool fwd) {
+    __shared__ float sh_o[RNNT_MAXT];
+    __shared__ float sh_q[RNNT_MAXU1];
+    __shared__ float pub[2][RNNT_MAXU1 + 2];
+    __shared__ double red[NT];
+    const int tid = threadIdx.x;
+    const UttGeo g = utt_geo(d, b);
+    const int U1 = g.ld, Tb = g.Tb, Ub = g.Ub;
+    if (Tb == 0) {                                         // no frame: no alignment (torchaudio rejects it); +inf, zero gradient
+        if (tid == 0) {
+            if (fwd) d.ll_alpha[b] = -INFINITY;
+            else d.nll[b] = d.nll_shifted[b] = INFINITY;
+        }
+        return;
+    }
+    const int64_t base = g.base;
+    const float* lb = d.lp_blank + base;
+    const float* ll = d.lp_label + base;
+    rnnt_shifts<NT>(lb, ll, U1, Tb, Ub, sh_o, sh_q);
     for (int i = tid; i < RNNT_MAXU1 + 2; i += NT) pub[0][i] = pub[1][i] = -INFINITY;
     __syncthreads();
     float* shift = g.shift;
@@ -259,6 +265,106 @@ __global__ __launch_bounds__(NT) void cfm_rnnt_alpha_beta_kernel(D d) {
     else rnnt_sweep<NT, PER>(d, wg - B, false);
 }
 
+// ---- forced alignment: the max-plus (Viterbi) twin of the forward sweep, one workgroup per utterance ----
+// delta'[t,u] = max(delta'[t-1,u] + lp_blank'[t-1,u], delta'[t,u-1] + lp_label'[t,u-1]) on the shifted values of the loss (every path to (t,u)
+// takes the same offsets, so no decision moves); the blank move first, the label move only where it is STRICTLY greater (at t = 0 it is the only
+// move).  Recorded per node: ent[t,u] = the last frame t' <= t at which column u was entered by a label move -- a column thread's running
+// register, stored as int16 (T <= 8192).  The trace-back is then one dependent load per LABEL, not per move: from (Tb-1, Ub),
+// frame[u-1] = t = ent[t,u], down to u = 1.  By construction 0 <= ent[t,u] <= t, so the walk cannot leave the lattice.
+__host__ __device__ __forceinline__ int align_ld(const cfm_rnnt_desc& d) { return d.U1 - 1; }
+__host__ __device__ __forceinline__ int align_ld(const cfm_rnnt_packed_desc& d) { return d.lat.U1_max - 1; }
+
+template <int NT, int PER, typename AD>
+__global__ __launch_bounds__(NT) void cfm_rnnt_viterbi_kernel(AD ad) {
+    __shared__ float sh_o[RNNT_MAXT];
+    __shared__ float sh_q[RNNT_MAXU1];
+    __shared__ float pub[2][RNNT_MAXU1 + 2];
+    __shared__ double red[NT];
+    __shared__ float sh_end;
+    const auto& d = ad.r;
+    const int tid = threadIdx.x, b = (int)blockIdx.x;
+    const UttGeo g = utt_geo(d, b);
+    const int U1 = g.ld, Tb = g.Tb, Ub = g.Ub, W = align_ld(d);
+    int32_t* frame = ad.frame + (int64_t)b * W;
+    float* tlp = ad.token_logp + (int64_t)b * W;
+    for (int u = (Tb > 0 ? Ub : 0) + tid; u < W; u += NT) {     // beyond the labels; everything when there is no alignment
+        frame[u] = -1;
+        tlp[u] = -INFINITY;
+    }
+    if (Tb == 0) {                                         // the final blank needs a frame
+        if (tid == 0) ad.score[b] = -INFINITY;
+        return;
+    }
+    const int64_t base = g.base;
+    const float* lb = d.lp_blank + base;
+    const float* ll = d.lp_label + base;
+    int16_t* ent = (int16_t*)ad.scratch + base;
+    rnnt_shifts<NT>(lb, ll, U1, Tb, Ub, sh_o, sh_q);
+    for (int i = tid; i < RNNT_MAXU1 + 2; i += NT) pub[0][i] = pub[1][i] = -INFINITY;
+    __syncthreads();
+    const int D = Tb + Ub;                                 // diagonals 0 .. Tb-1+Ub
+    float self[PER], lbp[PER];
+    int entered[PER];
+    float nb[RNNT_AHEAD][PER], nl[RNNT_AHEAD][PER];
+    auto fetch = [&](int step, int i, float& vb, float& vl) {
+        const int u = tid + i * NT, t = step - u;
+        const bool ok = step < D && u <= Ub && t >= 0 && t < Tb;
+        vb = ok ? lb[(int64_t)t * U1 + u] - sh_o[t] : 0.f;
+        vl = (ok && u < Ub) ? ll[(int64_t)t * U1 + u] - sh_q[u] : -INFINITY;
+    };
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+        self[i] = -INFINITY;
+        lbp[i] = 0.f;
+        entered[i] = 0;
+#pragma unroll
+        for (int k = 0; k < RNNT_AHEAD; ++k) fetch(k, i, nb[k][i], nl[k][i]);
+    }
+    for (int s0 = 0; s0 < D; s0 += RNNT_AHEAD) {
+#pragma unroll
+        for (int k = 0; k < RNNT_AHEAD; ++k) {
+            const int step = s0 + k;
+            if (step < D) {                                // uniform
+#pragma unroll
+                for (int i = 0; i < PER; ++i) {
+                    const int u = tid + i * NT, t = step - u;
+                    const float nbr = pub[(step + 1) & 1][u];                  // delta'[t,u-1] + lp_label'[t,u-1]; -inf at u = 0
+                    float v = -INFINITY;
+                    if (u <= Ub && t >= 0 && t < Tb) {
+                        const float cb = self[i] + lbp[i];
+                        const bool label = t == 0 ? u > 0 : nbr > cb;
+                        const float a = (t == 0 && u == 0) ? 0.f : (label ? nbr : cb);
+                        if (label) entered[i] = t;
+                        ent[(int64_t)t * U1 + u] = (int16_t)entered[i];
+                        self[i] = a;
+                        lbp[i] = nb[k][i];
+                        v = a + nl[k][i];                                      // -inf at u = Ub
+                        if (t == Tb - 1 && u == Ub) sh_end = a + nb[k][i];
+                    }
+                    pub[step & 1][u + 1] = v;
+                    fetch(step + RNNT_AHEAD, i, nb[k][i], nl[k][i]);
+                }
+                __syncthreads();
+            }
+        }
+    }
+    double part = 0.0;                                     // sum o + sum q in fp64, a fixed order (as the loss)
+    for (int t = tid; t < Tb; t += NT) part += (double)sh_o[t];
+    for (int u = tid; u < Ub; u += NT) part += (double)sh_q[u];
+    red[tid] = part;
+    __syncthreads();                                       // the loop's last barrier already ordered sh_end and every ent store
+    if (tid != 0) return;
+    double tot = 0.0;
+    for (int i = 0; i < NT; ++i) tot += red[i];
+    ad.score[b] = (float)((double)sh_end + tot);
+    int t = Tb - 1;
+    for (int u = Ub; u > 0; --u) {                         // Ub dependent loads
+        t = ent[(int64_t)t * U1 + u];
+        frame[u - 1] = t;
+        tlp[u - 1] = ll[(int64_t)t * U1 + u - 1];
+    }
+}
+
 // ---- gradient: one wavefront per row (b, t, u), all rows ----
 template <typename D, typename TI, typename TO, bool VEC>
 __global__ __launch_bounds__(256) void cfm_rnnt_grad_kernel(D d) {
@@ -321,9 +427,10 @@ __global__ __launch_bounds__(256) void cfm_rnnt_grad_kernel(D d) {
     }
 }
 
-int rnnt_check(const cfm_rnnt_desc* d, const char* what) {
-    CFM_CHECK_ARG(d && d->logits && d->logit_lens && d->target_lens && d->lse && d->lp_blank && d->lp_label && d->alpha && d->beta && d->shift &&
-                  d->nll && d->nll_shifted, "%s: null pointer", what);
+// loss: the entries that run the alpha / beta recursions; the alignment reads neither those arrays nor the costs
+int rnnt_check(const cfm_rnnt_desc* d, const char* what, const bool loss = true) {
+    CFM_CHECK_ARG(d && d->logits && d->logit_lens && d->target_lens && d->lse && d->lp_blank && d->lp_label &&
+                  (!loss || (d->alpha && d->beta && d->shift && d->nll && d->nll_shifted)), "%s: null pointer", what);
     CFM_CHECK_ARG(d->B > 0 && d->T > 0 && d->U1 > 0 && d->V > 1, "%s: bad shape B=%d T=%d U+1=%d V=%d", what, d->B, d->T, d->U1, d->V);
     CFM_CHECK_ARG(d->U1 <= RNNT_MAXU1, "%s: U+1 = %d exceeds %d", what, d->U1, RNNT_MAXU1);
     CFM_CHECK_ARG(d->T <= RNNT_MAXT, "%s: T = %d frames exceeds %d", what, d->T, RNNT_MAXT);
@@ -363,9 +470,9 @@ int launch_grad_out(const D& d, hipStream_t s, CfmProfScope& prof) {
     return cfm_by_dtype(d.grad_dtype, [&](auto to) { return launch_grad<D, TI, decltype(to)>(d, s, prof); });
 }
 
-int rnnt_packed_check(const cfm_rnnt_packed_desc* d, const char* what) {
-    CFM_CHECK_ARG(d && d->logits && d->lat.off && d->lat.T && d->lat.U && d->lse && d->lp_blank && d->lp_label && d->alpha && d->beta && d->shift &&
-                  d->nll && d->nll_shifted, "%s: null pointer", what);
+int rnnt_packed_check(const cfm_rnnt_packed_desc* d, const char* what, const bool loss = true) {
+    CFM_CHECK_ARG(d && d->logits && d->lat.off && d->lat.T && d->lat.U && d->lse && d->lp_blank && d->lp_label &&
+                  (!loss || (d->alpha && d->beta && d->shift && d->nll && d->nll_shifted)), "%s: null pointer", what);
     const cfm_lattice& L = d->lat;
     CFM_CHECK_ARG(L.B > 0 && L.M >= 0 && L.T_max >= 0 && L.U1_max > 0 && d->V > 1, "%s: bad shape B=%d M=%lld T_max=%d U1_max=%d V=%d", what, L.B,
                   (long long)L.M, L.T_max, L.U1_max, d->V);
@@ -379,14 +486,19 @@ int rnnt_packed_check(const cfm_rnnt_packed_desc* d, const char* what) {
 }
 
 template <typename D>
+int rnnt_rows_launch(const D& d, const char* what, hipStream_t s) {
+    const int64_t rows = n_rows(d);
+    if (rows == 0) return CFM_OK;                          // a packed lattice may have no node at all (every T_b = 0)
+    CfmProfScope prof("rnnt_rows", s, 0.0, (double)rows * d.V * cfm_elt_size(d.logits_dtype));
+    int rc = cfm_by_dtype(d.logits_dtype, [&](auto ti) { return launch_rows<D, decltype(ti)>(d, s, prof); });
+    if (rc) return rc;
+    return cfm_launch_status(what);
+}
+
+template <typename D>
 int rnnt_nll_launch(const D& d, const char* what, hipStream_t s) {
     const int64_t rows = n_rows(d);
-    if (rows > 0) {                                        // a packed lattice may have no node at all (every T_b = 0)
-        CfmProfScope prof("rnnt_rows", s, 0.0, (double)rows * d.V * cfm_elt_size(d.logits_dtype));
-        int rc = cfm_by_dtype(d.logits_dtype, [&](auto ti) { return launch_rows<D, decltype(ti)>(d, s, prof); });
-        if (rc) return rc;
-        if (int rc2 = cfm_launch_status(what)) return rc2;
-    }
+    if (int rc = rnnt_rows_launch(d, what, s)) return rc;
     CfmProfScope prof("rnnt_alpha_beta", s, 0.0, (double)rows * 4 * 6);
     CFM_LAUNCH((cfm_rnnt_alpha_beta_kernel<RNNT_NT, RNNT_MAXU1 / RNNT_NT, D>), dim3(2 * n_utt(d)), dim3(RNNT_NT), 0, s, d);
     return cfm_launch_status(what);
@@ -409,7 +521,33 @@ int rnnt_grad_launch(const D& d, const char* what, hipStream_t s) {
     return cfm_launch_status(what);
 }
 
+// the alignment's own arguments, after the embedded descriptor passed its check; then the row pass as the loss runs it and the Viterbi launch
+template <typename AD>
+int rnnt_align_launch(const AD& ad, const char* what, hipStream_t s) {
+    const int64_t rows = n_rows(ad.r);
+    CFM_CHECK_ARG(ad.score && (align_ld(ad.r) == 0 || (ad.frame && ad.token_logp)) && (rows == 0 || ad.scratch), "%s: null pointer", what);
+    CFM_CHECK_ARG(ad.scratch_bytes >= cfm_rnnt_align_scratch_bytes(rows), "%s: scratch of %lld bytes, cfm_rnnt_align_scratch_bytes = %lld needed", what,
+                  (long long)ad.scratch_bytes, (long long)cfm_rnnt_align_scratch_bytes(rows));
+    CFM_CHECK_ARG(((uintptr_t)ad.scratch & 1) == 0, "%s: scratch must be 2-byte aligned", what);
+    if (int rc = rnnt_rows_launch(ad.r, what, s)) return rc;
+    CfmProfScope prof("rnnt_viterbi", s, 0.0, (double)rows * (4 * 2 + 2));
+    CFM_LAUNCH((cfm_rnnt_viterbi_kernel<RNNT_NT, RNNT_MAXU1 / RNNT_NT, AD>), dim3(n_utt(ad.r)), dim3(RNNT_NT), 0, s, ad);
+    return cfm_launch_status(what);
+}
+
 }  // namespace
+
+extern "C" int64_t cfm_rnnt_align_scratch_bytes(int64_t nodes) { return nodes <= 0 ? 0 : (2 * nodes + 3) / 4 * 4; }
+
+extern "C" int cfm_rnnt_align(const cfm_rnnt_align_desc* d, cfm_stream_t stream) {
+    if (int rc = rnnt_check(d ? &d->r : nullptr, "cfm_rnnt_align", false)) return rc;
+    return rnnt_align_launch(*d, "cfm_rnnt_align", (hipStream_t)stream);
+}
+
+extern "C" int cfm_rnnt_packed_align(const cfm_rnnt_packed_align_desc* d, cfm_stream_t stream) {
+    if (int rc = rnnt_packed_check(d ? &d->r : nullptr, "cfm_rnnt_packed_align", false)) return rc;
+    return rnnt_align_launch(*d, "cfm_rnnt_packed_align", (hipStream_t)stream);
+}
 
 extern "C" int cfm_rnnt_nll(const cfm_rnnt_desc* d, cfm_stream_t stream) {
     if (int rc = rnnt_check(d, "cfm_rnnt_nll")) return rc;

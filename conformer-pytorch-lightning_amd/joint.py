@@ -15,6 +15,8 @@ them raises.  Training goes through `rnnt_loss(enc_out, pred_out, targets, enc_l
 loss gradient overwrites them in place (cfm/autograd.py JointRNNTLossFn).  `rnnt_loss(..., packed=True)` builds the logits for the valid cells
 (b, t < enc_lens[b], u <= target_lens[b]) only (a packed lattice, cfm/lattice.py), and `forward_window(rows, groups)` runs the loss of every
 micro-batch of an accumulation window through one packed lattice over the window's encoder row matrix (the same Function).
+`forced_align(enc_out, pred_out, targets, enc_lens, target_lens)` (eval mode) runs the same packed joint and then cfm_rnnt_packed_align: the
+best single alignment of known labels on this head, per token its emission frame and log-probability.
 """
 import numpy as np
 import torch
@@ -166,3 +168,56 @@ class TransducerJoint(nn.Module):
             losses.append(nll[s:s + B].mean())
             s += B
         return torch.stack(losses)
+
+    @torch.no_grad()
+    def forced_align(self, enc_out, pred_out, targets, enc_lens, target_lens, blank=0):
+        """Forced alignment of KNOWN labels on the transducer head: the joint over the valid cells only (a packed lattice, as
+        rnnt_loss(packed=True)), then cfm_rnnt_packed_align -- the best single path through the lattice (include/cfm.h states the recursion and its
+        tie rule).  enc_out [B, T, E], pred_out [B, U+1, P] (the predictor over [blank] + labels), targets [B, U], enc_lens / target_lens (B,).
+        Returns a list of B entries: None for an utterance without a frame, else {"score": the path's log-probability, "tokens": [(token, frame,
+        logp), ...]} with the encoder frame at which each token is emitted and its log-probability there.  The results come back in one host
+        transfer; lengths given as DEVICE tensors cost one more before the joint (the lattice offsets are their prefix sum, as for
+        rnnt_loss(packed=True)), lengths given as lists or CPU tensors none."""
+        from cfm import lattice
+        if self.training:
+            raise RuntimeError("TransducerJoint.forced_align is an eval-mode operation (inference only); in train mode call rnnt_loss")
+        cfm.require_hip(enc_out, pred_out)
+        if enc_out.dim() != 3 or pred_out.dim() != 3 or enc_out.size(0) != pred_out.size(0):
+            raise ValueError("TransducerJoint.forced_align: enc_out %s / pred_out %s must be (B, T, E) / (B, U+1, P)" % (tuple(enc_out.shape), tuple(pred_out.shape)))
+        B, T, U1 = enc_out.size(0), enc_out.size(1), pred_out.size(1)
+        dev = enc_out.device
+        targets = torch.as_tensor(targets).to(device=dev, dtype=torch.int32).contiguous()
+        enc_lens, target_lens = torch.as_tensor(enc_lens), torch.as_tensor(target_lens)
+        if tuple(targets.shape) != (B, U1 - 1) or enc_lens.shape != (B,) or target_lens.shape != (B,):
+            raise ValueError("TransducerJoint.forced_align: %d utterances with U = %d, but targets %s, lengths %s, %s" %
+                             (B, U1 - 1, tuple(targets.shape), tuple(enc_lens.shape), tuple(target_lens.shape)))
+        b = self._blank(blank, "forced_align")
+        prec = cfm.resolve_precision(self)
+        pk = self._weights(prec)
+        on_dev = [t for t in (enc_lens, target_lens) if t.is_cuda]                      # only these cost a transfer (one for both)
+        host = iter(lattice.host_lengths(*on_dev)) if on_dev else None
+        Tb, Ub = (next(host) if t.is_cuda else t.to(torch.int64).numpy() for t in (enc_lens, target_lens))
+        Tb, Ub = Tb.clip(0, T), Ub.clip(0, U1 - 1)
+        lat = lattice.Lattice.padded(Tb, Ub, T, U1, dev)
+        _, _, e = self._rows(enc_out, 2, "enc_out")
+        _, _, p = self._rows(pred_out, 1, "pred_out")
+        e = cfm.gemm(e, pk.enc[0], bias=pk.enc[2], w_lo=pk.enc[1], out_dtype=torch.float32)
+        p = cfm.gemm(p, pk.pred[0], bias=pk.pred[2], w_lo=pk.pred[1], out_dtype=torch.float32)
+        if lat.M:
+            a = cfm.joint_act_packed(e, p, lat, prec.act_dtype)
+            logits = cfm.gemm(a, pk.out[0], bias=pk.out[2], w_lo=pk.out[1], out_dtype=self.out_dtype)
+        else:
+            logits = torch.empty((0, pk.Vp), dtype=self.out_dtype, device=dev)
+        frame, token_logp, score = cfm.rnnt_align_packed(logits, targets, lat, b, V=pk.V)
+        W = lat.U1_max - 1
+        # one transfer: everything as float64 columns (frames and labels are far below 2^53)
+        res = torch.cat([score.double()[:, None], frame.double(), token_logp.double(), targets.double()], 1).cpu()
+        out = []
+        for i in range(B):
+            U = int(Ub[i])
+            if Tb[i] == 0:
+                out.append(None)
+                continue
+            fr, lp, lab = (res[i, 1 + k * W:1 + k * W + U].tolist() for k in range(3))
+            out.append({"score": float(res[i, 0]), "tokens": [(int(lab[u]), int(fr[u]), lp[u]) for u in range(U)]})
+        return out

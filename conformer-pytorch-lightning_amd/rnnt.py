@@ -16,12 +16,17 @@ no CPU path.  TransducerJoint.rnnt_loss runs the joint and this loss as one diff
 
 The same loss over a packed lattice (cfm/lattice.py): logits [M, V] hold only the valid nodes, utterance b's T_b (U_b+1) rows in (t, u) order
 after those of utterances 0..b-1 (M = sum_b T_b (U_b+1), T_b = logit_lengths[b], U_b = target_lengths[b]).
+
+    rnnt_align(logits, targets, logit_lengths, target_lengths, blank=-1)
+
+Forced alignment on the same lattice: the best single path instead of the sum over all of them (cfm_rnnt_align, the max-plus twin of the loss's
+alpha recursion; include/cfm.h states it).  Same argument conventions and dtypes as rnnt_loss; no gradient.
 """
 import torch
 
 import cfm
 
-__all__ = ["rnnt_loss", "rnnt_loss_packed"]
+__all__ = ["rnnt_loss", "rnnt_loss_packed", "rnnt_align"]
 
 
 def _i32(t, device):
@@ -78,3 +83,27 @@ def rnnt_loss_packed(logits, targets, logit_lengths, target_lengths, blank=-1, c
     x = logits if logits.stride(1) == 1 else logits.contiguous()
     from cfm import autograd as ag
     return ag.RNNTLossFn.apply(x, _i32(targets, logits.device), lat, b, float(clamp), reduction)
+
+
+@torch.no_grad()
+def rnnt_align(logits, targets, logit_lengths, target_lengths, blank=-1):
+    """The best single alignment of each utterance's labels to its frames over the transducer lattice.  Arguments as rnnt_loss.  Returns
+    (frame int32 [B, U], token_logp f32 [B, U], score f32 [B]) on the device: frame[b, u] is the frame at which label u is emitted (nondecreasing
+    in u; several labels may share a frame), token_logp[b, u] its log-probability at that node, score[b] the log-probability of the whole path
+    (at most -rnnt_loss(..., reduction="none")[b]).  Entries at and beyond target_lengths[b] are -1 / -inf; an utterance with logit_lengths[b] = 0
+    has no alignment: score -inf and that fill everywhere.  Ties take the blank move (later frames)."""
+    cfm.require_hip(logits, targets, logit_lengths, target_lengths)
+    if logits.dim() != 4:
+        raise ValueError("rnnt_align: logits must be [B, T, U+1, V], got %s" % (tuple(logits.shape),))
+    B, T, U1, V = logits.shape
+    if targets.dim() != 2 or tuple(targets.shape) != (B, U1 - 1) or logit_lengths.numel() != B or target_lengths.numel() != B:
+        raise ValueError("rnnt_align: targets %s / lengths %s, %s do not match logits %s" % (tuple(targets.shape), tuple(logit_lengths.shape),
+                                                                                          tuple(target_lengths.shape), tuple(logits.shape)))
+    b = blank + V if blank < 0 else blank
+    if not 0 <= b < V:
+        raise ValueError("rnnt_align: blank %d outside a vocabulary of %d" % (blank, V))
+    x = logits.detach()
+    if x.stride(3) != 1 or x.stride(1) != U1 * x.stride(2) or x.stride(0) != T * U1 * x.stride(2):
+        x = x.contiguous()
+    dev = logits.device
+    return cfm.rnnt_align(x, _i32(targets, dev), _i32(logit_lengths, dev), _i32(target_lengths, dev), b)

@@ -306,6 +306,8 @@ class OfflineRecognizer:
     The lengths stay on the device; the only host read is the search's own.  encoder_out / encoder_out_lens: what the last call's search read.
     ctc: a decoder.CTCDecoder on the same encoder; recognize_ctc / recognize_ctc_audio then decode its output instead (the hybrid model's cheap first pass),
     and align / align_audio give a known transcript's token spans in encoder frames (frame_seconds converts a frame to its start time).
+    align(..., head="rnnt") aligns on the transducer head instead (TransducerJoint.forced_align; no CTC head needed): per token the frame that emits
+    it.  recognize(..., timestamps=True) aligns each utterance's 1-best against itself on that head: {"tokens", "frames", "logp", "score"}.
     score / score_audio recognise and then score the hypotheses against known transcripts on the device (metrics.py, cfm.edit_distance).
     attention: a decoder.TransformerDecoder / BiTransformerDecoder (or a ready decoder.AttentionRescorer) on the same encoder; recognize(beam=k,
     rescore=True), recognize_ctc(beam=k, rescore=True) and their _audio forms then re-rank each n-best list by the attention decoder
@@ -338,22 +340,57 @@ class OfflineRecognizer:
         if rescore and self.rescorer is None:
             raise RuntimeError("OfflineRecognizer.%s: rescore=True, but the recogniser was built without an attention decoder (attention=None)" % who)
 
+    def _align_rnnt(self, labels, label_lengths, who):
+        """TransducerJoint.forced_align of the labels on self.encoder_out: the predictor in eval mode over [blank] + labels, as TransducerObjective
+        prepares them (padding beyond label_lengths[b] reads as blank; the LSTM is causal, so it changes no valid row)."""
+        pr, jn = self.search.predictor, self.search.joint
+        if pr.training or jn.training:
+            raise RuntimeError("OfflineRecognizer.%s: alignment on the RNN-T head is an eval-mode operation" % who)
+        dev, B = self.encoder_out.device, self.encoder_out.shape[0]
+        labels, llens = torch.as_tensor(labels).to(dev), torch.as_tensor(label_lengths)
+        if labels.dim() != 2 or labels.shape[0] != B or llens.shape != (B,):
+            raise ValueError("OfflineRecognizer.%s: %d utterances, but labels %s, label lengths %s" % (who, B, tuple(labels.shape), tuple(llens.shape)))
+        valid = torch.arange(labels.shape[1], device=llens.device)[None, :] < llens[:, None]       # built where the lengths are: no transfer back
+        text = torch.where(valid.to(dev), labels, self.blank)
+        pred_out = pr(utils.add_blank(text, self.blank, -1))
+        return jn.forced_align(self.encoder_out, pred_out, text.to(torch.int32), self.encoder_out_lens, llens, blank=self.blank)
+
+    def _timestamps(self, hyps):
+        """The hypotheses aligned against themselves on the RNN-T head: per utterance {"tokens", "frames", "logp", "score"}."""
+        lens = [len(h) for h in hyps]
+        labels = torch.full((len(hyps), max(lens, default=0)), self.blank, dtype=torch.int64)
+        for b, h in enumerate(hyps):
+            labels[b, :len(h)] = torch.tensor(h, dtype=torch.int64)
+        out = []
+        for e in self._align_rnnt(labels, lens, "recognize"):
+            tokens = [] if e is None else e["tokens"]           # None: no encoder frame, so no token either
+            out.append({"tokens": [t[0] for t in tokens], "frames": [t[1] for t in tokens], "logp": [t[2] for t in tokens],
+                        "score": float("-inf") if e is None else e["score"]})
+        return out
+
     @torch.no_grad()
-    def recognize(self, feats, lengths, beam=None, rescore=False):
+    def recognize(self, feats, lengths, beam=None, rescore=False, timestamps=False):
         """beam=None: the greedy search, a list of B token lists.  beam = 1..15: greedy.BeamSearch over groups of at most 64 // beam utterances,
         per utterance a list of (tokens, score), best first; an utterance with no encoder frame gives [([], 0.0)].  rescore=True (with beam): the
-        lists re-ranked by the attention decoder, (tokens, final score)."""
+        lists re-ranked by the attention decoder, (tokens, final score).
+        timestamps=True: each utterance's best hypothesis is aligned against itself on the RNN-T head (the Viterbi path of its own tokens, never
+        worse than the path the search took).  beam=None: a list of {"tokens", "frames": the encoder frame that emits each token (frame_seconds
+        converts it), "logp": the token's log-probability there, "score": the path's}; an utterance with no encoder frame has empty lists and
+        score -inf.  With beam: (the n-best lists as without timestamps, that list for the best entries)."""
         self._check_rescore(rescore, beam, "recognize")
         self.encoder_out, self.encoder_out_lens = self.encoder.forward_utterances(feats, lengths)
         if beam is None:
-            return self.search.search(self.encoder_out, self.encoder_out_lens)[0]
+            hyps = self.search.search(self.encoder_out, self.encoder_out_lens)[0]
+            return self._timestamps(hyps) if timestamps else hyps
         import greedy
         if self._beam is None or self._beam.beam != int(beam):
             self._beam = greedy.BeamSearch(self.search.predictor, self.search.joint, beam, blank=self.blank, max_symbols=self.search.n_steps)
         group, out = 64 // self._beam.beam, []
         for b0 in range(0, self.encoder_out.shape[0], group):
             out.extend(self._beam.search(self.encoder_out[b0:b0 + group], self.encoder_out_lens[b0:b0 + group]))
-        return self.rescorer.rescore(self.encoder_out, self.encoder_out_lens, out) if rescore else out
+        if rescore:
+            out = self.rescorer.rescore(self.encoder_out, self.encoder_out_lens, out)
+        return (out, self._timestamps([list(n[0][0]) for n in out])) if timestamps else out
 
     def _features(self, samples, lengths, sample_rate=None):
         """The waveform batch through the fbank; sample_rate (Hz; None: the fbank's own) other than the fbank's sample_frequency goes through a cached
@@ -371,9 +408,9 @@ class OfflineRecognizer:
             samples, lengths = rs(samples, lengths)
         return self.fbank(samples, lengths)
 
-    def recognize_audio(self, samples, lengths, beam=None, sample_rate=None, rescore=False):
+    def recognize_audio(self, samples, lengths, beam=None, sample_rate=None, rescore=False, timestamps=False):
         self._check_rescore(rescore, beam, "recognize_audio")
-        return self.recognize(*self._features(samples, lengths, sample_rate), beam=beam, rescore=rescore)
+        return self.recognize(*self._features(samples, lengths, sample_rate), beam=beam, rescore=rescore, timestamps=timestamps)
 
     @torch.no_grad()
     def recognize_ctc(self, feats, lengths, beam=None, rescore=False):
@@ -394,18 +431,28 @@ class OfflineRecognizer:
         return self.recognize_ctc(*self._features(samples, lengths, sample_rate), beam=beam, rescore=rescore)
 
     @torch.no_grad()
-    def align(self, feats, lengths, labels, label_lengths, return_path=False):
+    def align(self, feats, lengths, labels, label_lengths, return_path=False, head="ctc"):
         """Forced alignment of known transcripts with the CTC head: forward_utterances once, as recognize_ctc, then
         decoder.CTCDecoder.forced_align.  labels [B, Umax], label_lengths (B,).  Per utterance None (no alignment exists, e.g. no encoder frame
         for a non-empty transcript) or {"score", "tokens": [(token, start_frame, end_frame, logp)]} with inclusive ENCODER frames;
-        frame_seconds converts them."""
+        frame_seconds converts them.
+        head="rnnt": on the transducer head instead, the one recognize reads (TransducerJoint.forced_align; works without a CTC head): per
+        utterance None (no encoder frame) or {"score", "tokens": [(token, frame, logp)]}, frame the encoder frame that emits the token.  There
+        is no state path: return_path raises."""
+        if head not in ("ctc", "rnnt"):
+            raise ValueError("OfflineRecognizer.align: head must be \"ctc\" or \"rnnt\", got %r" % (head,))
+        if head == "rnnt":
+            if return_path:
+                raise ValueError("OfflineRecognizer.align: return_path belongs to the CTC head (head=\"rnnt\" has frames, not a state path)")
+            self.encoder_out, self.encoder_out_lens = self.encoder.forward_utterances(feats, lengths)
+            return self._align_rnnt(labels, label_lengths, "align")
         if self.ctc is None:
             raise RuntimeError("OfflineRecognizer.align: the recogniser was built without a CTC head (ctc=None)")
         self.encoder_out, self.encoder_out_lens = self.encoder.forward_utterances(feats, lengths)
         return self.ctc.forced_align(self.encoder_out, self.encoder_out_lens, labels, label_lengths, return_path=return_path)
 
-    def align_audio(self, samples, lengths, labels, label_lengths, return_path=False, sample_rate=None):
-        return self.align(*self._features(samples, lengths, sample_rate), labels, label_lengths, return_path=return_path)
+    def align_audio(self, samples, lengths, labels, label_lengths, return_path=False, sample_rate=None, head="ctc"):
+        return self.align(*self._features(samples, lengths, sample_rate), labels, label_lengths, return_path=return_path, head=head)
 
     @torch.no_grad()
     def score(self, feats, lengths, labels, label_lengths, beam=None, head="rnnt"):

@@ -683,6 +683,50 @@ typedef struct {
 int cfm_rnnt_packed_nll(const cfm_rnnt_packed_desc* d, cfm_stream_t stream);
 int cfm_rnnt_packed_grad(const cfm_rnnt_packed_desc* d, cfm_stream_t stream);
 
+/* cfm_rnnt_align / cfm_rnnt_packed_align: RNN-T forced alignment (csrc/rnnt.hip) -- the best single alignment of each utterance's frames to ITS
+ *   labels over the transducer lattice, the max-plus (Viterbi) twin of cfm_rnnt_nll's alpha recursion (as cfm_ctc_align is of cfm_ctc_nll's).  The
+ *   reference has nothing of the kind; the algorithm is stated in float64 in tests/rnnt_align_ref.py.  `r` is the loss's descriptor, read exactly
+ *   as cfm_rnnt_nll / cfm_rnnt_packed_nll read it (logits, lengths and their clamping, labels clamped into [0, V), blank); r.lse, r.lp_blank
+ *   and r.lp_label are required work arrays of the loss's sizes and are filled as the loss fills them; r.shift, r.alpha, r.beta, r.nll,
+ *   r.nll_shifted, r.ll_alpha and the gradient fields are not used and may be NULL (the shifts live in LDS; nothing reads them afterwards).
+ *   With lb[t,u] = log_softmax(logits[t,u,:V])[blank], ll[t,u] = log_softmax(logits[t,u,:V])[y_{u+1}], Tb = logit_lens[b] clamped to [0, T] and
+ *   Ub = target_lens[b] clamped to [0, U1-1] (packed: lat.T[b], lat.U[b]):
+ *       delta[0,0] = 0
+ *       delta[t,u] = max(delta[t-1,u] + lb[t-1,u]   (the blank move, only where t > 0),
+ *                        delta[t,u-1] + ll[t,u-1])  (the label move, only where u > 0)
+ *       score      = delta[Tb-1,Ub] + lb[Tb-1,Ub]
+ *   Ties: the blank move is taken first; the label move replaces it only if it is STRICTLY greater.  From (Tb-1, Ub) the recorded moves are
+ *   followed back to (0, 0).  The recursion runs in f32 on the loss's shifted values (lb[t,u] - max_u lb[t,.], ll[t,u] - max_t ll[.,u]: every
+ *   path to a node takes the same offsets, so no decision moves); the offsets are added back to the score in fp64.
+ *   score f32 [B]: the path's log-probability; -inf when Tb == 0 (the final blank needs a frame; the loss is +inf there).
+ *   frame int32 [B, Umax]: frame[u] is the t of the label move (t,u) -> (t,u+1) that emits label u (0-based); nondecreasing in u, several
+ *     labels may share a frame.  token_logp f32 [B, Umax]: ll[frame[u], u].  Entries u >= Ub, and all of an utterance with Tb == 0, are -1 and
+ *     -inf.  Umax = U1 - 1 (padded) or lat.U1_max - 1 (packed).
+ *   scratch: the recorded moves, scratch_bytes >= cfm_rnnt_align_scratch_bytes(nodes), nodes = B * T * U1 (padded) or lat.M (packed): two
+ *     bytes per node (per node the last frame at which its column was entered by a label move, so the trace-back is Ub dependent loads),
+ *     rounded up to a multiple of 4; 2-byte aligned (int16 entries).
+ *   Two launches (the loss's row pass, then one workgroup per utterance), no host synchronisation, no float atomics: the same inputs give the
+ *   same bits on every run, and padded and packed give the same bits on the same nodes.  U1 <= 1024, T <= 8192 (cfm_last_error otherwise). */
+typedef struct {
+    cfm_rnnt_desc r;
+    int32_t* frame;
+    float* token_logp;
+    float* score;
+    void* scratch;
+    int64_t scratch_bytes;
+} cfm_rnnt_align_desc;
+typedef struct {
+    cfm_rnnt_packed_desc r;
+    int32_t* frame;
+    float* token_logp;
+    float* score;
+    void* scratch;
+    int64_t scratch_bytes;
+} cfm_rnnt_packed_align_desc;
+int64_t cfm_rnnt_align_scratch_bytes(int64_t nodes);
+int cfm_rnnt_align(const cfm_rnnt_align_desc* d, cfm_stream_t stream);
+int cfm_rnnt_packed_align(const cfm_rnnt_packed_align_desc* d, cfm_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Training (BASELINE config 3: encoder + CTC loss + backward).  Input gradients of the dense layers are cfm_gemm on transposed
  * weight packs (with the CFM_ACT_DSILU / CFM_ACT_DRELU epilogues), weight / bias gradients are cfm_gemm_tn; the rest is below.
