@@ -283,8 +283,9 @@ __global__ __launch_bounds__(256) void cfm_attn_bwd_dkv_kernel(const AttnBwdArgs
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------
-// Fast forms for what a bf16 / fp16 training step actually runs: d_k = 64, 16-bit q / k / v / dO rows (16-byte aligned), no mask or a
-// key-validity mask (B, 1, Tk).  Same products, same element-wise arithmetic, same MFMA order as the general kernels above --
+// Fast forms for what a bf16 / fp16 training step actually runs: d_k = 64, 16-bit q / k / v / dO rows (16-byte aligned); no mask, a
+// key-validity mask (B, 1, Tk) or -- the MFULL instances below -- a (B, Tq, Tk) mask with row stride m_sq.  Same products, same
+// element-wise arithmetic, same MFMA order as the general kernels above --
 // bit-identical results (tests) -- but
 //   * tiles are staged as they lie in memory (16-byte pieces into the swizzled row-major image, no f32 round trip) and the TRANSPOSED
 //     operands of the second products are read straight out of that image with ds_read_b64_tr_b16: no transposed copy is written
@@ -675,13 +676,13 @@ int launch_bwd_group(AttnBwdGroupArgs& G, hipStream_t s, const char* n_dq, const
 }
 
 template <typename HT, bool SPLIT>
-int launch_bwd(const AttnBwdArgs& a, hipStream_t s, const char* n_dq, const char* n_dkv) {
+int launch_bwd(const AttnBwdArgs& a, hipStream_t s, const char* n_dq, const char* n_dkv, const char* n_dq_fast, const char* n_dkv_fast) {
     const double fl = 2.0 * a.B * a.H * (double)a.Tq * a.Tk * a.dk;
     const double by = (double)a.B * a.H * (a.Tq + a.Tk) * a.dk * cfm_elt_size(a.io_dt) * 3;
     bool fast = false;
     if constexpr (!SPLIT) fast = bwd_fast_ok<HT>(a);
     {
-        CfmProfScope prof("attn_bwd_delta", s, 0.0, 2.0 * a.B * a.Tq * a.H * a.dk * cfm_elt_size(a.io_dt));
+        CfmProfScope prof(fast ? "attn_bwd_delta_fast" : "attn_bwd_delta", s, 0.0, 2.0 * a.B * a.Tq * a.H * a.dk * cfm_elt_size(a.io_dt));
         const int64_t n = (int64_t)a.B * a.H * a.Tq;
         if constexpr (!SPLIT) {
             if (fast) CFM_LAUNCH((cfm_attn_delta_fast_kernel<HT>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
@@ -692,7 +693,7 @@ int launch_bwd(const AttnBwdArgs& a, hipStream_t s, const char* n_dq, const char
         if (int rc = cfm_launch_status("cfm_attention_bwd (delta)")) return rc;
     }
     {
-        CfmProfScope prof(n_dq, s, 3.0 * fl, by);
+        CfmProfScope prof(fast ? n_dq_fast : n_dq, s, 3.0 * fl, by);     // the fast launches under names of their own, the prefixes kept
         const dim3 grid((unsigned)((a.Tq + QT - 1) / QT), (unsigned)a.H, (unsigned)a.B);
         if constexpr (!SPLIT) {
             if (fast && a.mask && a.m_sq != 0) CFM_LAUNCH((cfm_attn_bwd_dq_fast_kernel<HT, true>), grid, dim3(256), 0, s, a);
@@ -703,7 +704,7 @@ int launch_bwd(const AttnBwdArgs& a, hipStream_t s, const char* n_dq, const char
         }
         if (int rc = cfm_launch_status("cfm_attention_bwd (dq)")) return rc;
     }
-    CfmProfScope prof(n_dkv, s, 4.0 * fl, by);
+    CfmProfScope prof(fast ? n_dkv_fast : n_dkv, s, 4.0 * fl, by);
     const dim3 grid((unsigned)((a.Tk + KT - 1) / KT), (unsigned)a.H, (unsigned)a.B);
     if constexpr (!SPLIT) {
         if (fast && a.mask && a.m_sq != 0) CFM_LAUNCH((cfm_attn_bwd_dkv_fast_kernel<HT, true>), grid, dim3(256), 0, s, a);
@@ -740,13 +741,13 @@ extern "C" int cfm_attention_bwd(const cfm_attn_bwd_desc* d, cfm_stream_t stream
     AttnBwdArgs a;
     if (int rc = attn_bwd_args(d, a)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (d->split) return launch_bwd<BF16, true>(a, s, "attn_bwd_dq_bf16x3", "attn_bwd_dkv_bf16x3");
-    if (d->mma_dtype == CFM_BF16) return launch_bwd<BF16, false>(a, s, "attn_bwd_dq_bf16", "attn_bwd_dkv_bf16");
-    return launch_bwd<F16, false>(a, s, "attn_bwd_dq_f16", "attn_bwd_dkv_f16");
+    if (d->split) return launch_bwd<BF16, true>(a, s, "attn_bwd_dq_bf16x3", "attn_bwd_dkv_bf16x3", "", "");
+    if (d->mma_dtype == CFM_BF16) return launch_bwd<BF16, false>(a, s, "attn_bwd_dq_bf16", "attn_bwd_dkv_bf16", "attn_bwd_dq_fast_bf16", "attn_bwd_dkv_fast_bf16");
+    return launch_bwd<F16, false>(a, s, "attn_bwd_dq_f16", "attn_bwd_dkv_f16", "attn_bwd_dq_fast_f16", "attn_bwd_dkv_fast_f16");
 }
 
 // n attention backward problems (the micro-batches of a training window) in three launches instead of 3 n when every one takes the d_k = 64 /
-// 16-bit fast kernels (no (B,Tq,Tk) mask); otherwise problem after problem.  Same results either way.
+// 16-bit fast kernels and all share one mask kind ((B,Tq,Tk) or not); otherwise problem after problem.  Same results either way.
 extern "C" int cfm_attention_bwd_group(const cfm_attn_bwd_desc* descs, int32_t n, cfm_stream_t stream) {
     CFM_CHECK_ARG(descs && n > 0, "cfm_attention_bwd_group: no problems");
     hipStream_t s = (hipStream_t)stream;

@@ -843,9 +843,9 @@ typedef struct {
 int cfm_attention_bwd(const cfm_attn_bwd_desc* d, cfm_stream_t stream);
 /* n backward problems in three launches (delta, dq, dkv over all of them) when every one takes the d_k = 64 / 16-bit kernels; else one by one. */
 int cfm_attention_bwd_group(const cfm_attn_bwd_desc* descs, int32_t n, cfm_stream_t stream);
-/* d_k = 64 with 16-bit, 16-byte-aligned q / k / v / dO rows and no mask or a key-validity mask (m_sq == 0) takes fast kernels (tiles staged as
- * they lie in memory, transposed operands read with ds_read_b64_tr_b16, next tile prefetched) -- bit-identical to the general ones, which
- * this switch forces (tests). */
+/* d_k = 64 with 16-bit, 16-byte-aligned q / k / v / dO rows takes fast kernels, under any mask kind: none, a key-validity mask (m_sq == 0) or a
+ * (B,Tq,Tk) mask (m_sq != 0, the MFULL instances); they are profiled as attn_bwd_{delta,dq,dkv}_fast* (tiles staged as they lie in memory,
+ * transposed operands read with ds_read_b64_tr_b16, next tile prefetched) -- bit-identical to the general ones, which this switch forces (tests). */
 void cfm_attention_bwd_force_general(int32_t on);
 /* Chained blocks (cfm_layer_io.next_w): run the conv-in chain as the input stage of the block's last launch (two launches per block; the default, also
  * switched off by CFM_CIN_MERGE=0 in the environment at first use) or as a launch of its own (three).  The results are bit-identical; bench.py times the
