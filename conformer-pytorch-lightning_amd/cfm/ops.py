@@ -6,7 +6,7 @@ import torch
 
 import cfm as _c
 
-__all__ = ["rescore_prep", "token_logprob", "rescore_combine", "lsm_loss", "lsm_grad", "lsm_reduce", "lstm_forward", "lstm_backward", "fbank", "fbank_stream", "fbank_stream_ragged", "resample", "resample_stream", "resample_group", "spec_augment", "stream_prep", "stream_advance", "dwconv_causal_bn_silu", "conv_cache_update", "dropout_rows", "dropout_mask", "set_deterministic", "gemm_tn", "gemm_tn_group", "layernorm_bwd", "glu_bwd", "dwconv_bn_train", "dwconv_bn_train_bwd", "dwconv_bn_train_groups", "dwconv_bn_train_bwd_groups", "col2im_relu_bwd", "conv1_wgrad", "attention_bwd", "attention_group", "attention_bwd_group",
+__all__ = ["dec_step_attn", "dec_beam_prune", "rescore_prep", "token_logprob", "rescore_combine", "lsm_loss", "lsm_grad", "lsm_reduce", "lstm_forward", "lstm_backward", "fbank", "fbank_stream", "fbank_stream_ragged", "resample", "resample_stream", "resample_group", "spec_augment", "stream_prep", "stream_advance", "dwconv_causal_bn_silu", "conv_cache_update", "dropout_rows", "dropout_mask", "set_deterministic", "gemm_tn", "gemm_tn_group", "layernorm_bwd", "glu_bwd", "dwconv_bn_train", "dwconv_bn_train_bwd", "dwconv_bn_train_groups", "dwconv_bn_train_bwd_groups", "col2im_relu_bwd", "conv1_wgrad", "attention_bwd", "attention_group", "attention_bwd_group",
            "ctc_nll_train_groups", "ctc_grad", "rnnt_nll", "rnnt_grad", "joint_act_bwd", "rnnt_nll_packed", "rnnt_align", "rnnt_align_packed", "joint_act_packed", "joint_act_packed_bwd", "ffn_split", "adam_step", "adam_clip_step", "sumsq", "scratch_stats",
            "gemm", "ffn_fused", "ffn_fused_supported", "rowchain", "rowchain_supported", "rowchain_pair_supported", "layernorm", "attention", "kv_cache_pack", "dwconv_bn_silu", "conv1_relu", "conv1_relu_mma_supported", "conv12_relu", "conv12_supported", "ctc_nll", "ctc_topk", "ctc_greedy", "ctc_greedy_state", "ctc_prefix_beam", "ctc_align", "edit_distance", "joint_act", "valid_mask", "chunk_mask",
            "attn_mask_combine", "cast", "add_rows", "scratch", "prof_enable", "prof_reset", "prof_table", "as_u8_mask"]
@@ -1844,3 +1844,78 @@ def lsm_reduce(loss, target, batch=0):
     out = torch.empty((2,), dtype=torch.float32, device=loss.device)
     _c.call("cfm_lsm_reduce", _c.ptr(loss), _c.ptr(target), loss.numel(), int(batch), _c.ptr(out))
     return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# beam search with the attention decoder (csrc/attn_search.hip)
+# ----------------------------------------------------------------------------------------------------------------------
+def dec_step_attn(q, store, H, klen=None, slot=None, step=None, kv_new=None, out=None, cap=None, group=1, stride=0):
+    """One query per (row, head) over the K | V store (include/cfm.h cfm_dec_step_attn).  q [R, D] (unit inner stride; a column view of the fused
+    q|k|v product serves), store [slots, 2 D] dense, of q's dtype.  slot int32 [R, cap']: the table form; slot=None: slot(r, j) = (r // group) *
+    stride + j.  klen int32: the key counts, entry r // (R // klen.numel()); klen=None: step[0] + 1 (step int32 [1] on the device).  kv_new
+    [R, 2 D] (table form): this step's K | V, stored to slot(r, klen - 1) and attended to.  cap: the declared capacity (default: the table's
+    columns, resp. stride).  Returns out [R, D] of q's dtype."""
+    _c.require_hip(q, store, slot, klen, step, kv_new, out)
+    q = _rows2d(q, "dec_step_attn(q)")
+    R, H = q.shape[0], int(H)
+    _layout("dec_step_attn", "store is [slots, 2 D] of q's dtype, slot int32 [R, columns], klen and step int32", store=(store, q.dtype, (None, None)),
+            slot=_opt(slot, _I32, (R, None)), klen=_opt(klen, _I32, None), step=_opt(step, _I32, 1))
+    D = store.shape[1] // 2
+    if H < 1 or D % H or q.shape[1] != D or store.shape[1] != 2 * D:
+        raise ValueError("cfm.dec_step_attn: q %s, store %s and H = %d do not fit (q [R, D], store [slots, 2 D], D %% H == 0)" % (tuple(q.shape), tuple(store.shape), H))
+    if klen is None and step is None:
+        raise ValueError("cfm.dec_step_attn: the key counts come from klen or from the device step counter; both are None")
+    if klen is not None and (klen.numel() < 1 or R % klen.numel()):
+        raise ValueError("cfm.dec_step_attn: %d key counts for %d rows" % (klen.numel(), R))
+    if kv_new is not None:
+        kv_new = _rows2d(kv_new, "dec_step_attn(kv_new)")
+        if tuple(kv_new.shape) != (R, 2 * D) or kv_new.dtype != q.dtype:
+            raise ValueError("cfm.dec_step_attn: kv_new must be [%d, %d] of q's dtype, got %s %s" % (R, 2 * D, tuple(kv_new.shape), kv_new.dtype))
+    if out is None:
+        out = torch.empty((R, D), dtype=q.dtype, device=q.device)
+    out = _rows2d(out, "dec_step_attn(out)")
+    if tuple(out.shape) != (R, D) or out.dtype != q.dtype:
+        raise ValueError("cfm.dec_step_attn: out must be [%d, %d] of q's dtype, got %s %s" % (R, D, tuple(out.shape), out.dtype))
+    d = _c.DecStepAttnDesc()
+    d.q, d.store, d.slot, d.klen, d.step, d.kv_new, d.out = _c.ptr(q), _c.ptr(store), _c.ptr(slot), _c.ptr(klen), _c.ptr(step), _c.ptr(kv_new), _c.ptr(out)
+    d.ldq, d.ld_new, d.ldo, d.slots = q.stride(0) if R > 1 else max(q.stride(0), D), 0 if kv_new is None else (kv_new.stride(0) if R > 1 else max(kv_new.stride(0), 2 * D)), \
+        out.stride(0) if R > 1 else max(out.stride(0), D), store.shape[0]
+    d.R, d.H, d.dk, d.io_dtype = R, H, D // H, _c.dt_code(q)
+    d.slot_ld = 0 if slot is None else slot.shape[1]
+    d.group, d.stride = int(group), int(stride)
+    d.cap = int(cap) if cap is not None else (d.slot_ld if slot is not None else int(stride))
+    d.klen_group = 1 if klen is None else R // klen.numel()
+    _c.call("cfm_dec_step_attn", ctypes.byref(d))
+    return out
+
+
+DEC_BEAM_STATE = (("score", _F32), ("token", _I32), ("parent", _I32), ("finished", torch.uint8), ("hlen", _I32), ("klen", _I32))
+
+
+def dec_beam_prune(topk_idx, topk_logp, state, embed, pe, eos, V):
+    """One step's pruning and bookkeeping of the attention decoder's beam search, in place on `state` (include/cfm.h cfm_dec_beam_prune).
+    topk_idx int32 / topk_logp f32 [R, k] (cfm.ctc_topk on the step's logits, viewed as rows), R = B * K.  state: a dict of device tensors --
+    score f32, token / parent / hlen / klen int32, finished uint8 [R]; tokens, slots int32 [R, Lmax]; x f32 [R, D]; step, max_len int32 [B];
+    done uint8 [B]; n_done, all_done int32 [1]; nbest_tokens int32 [B, K, Lmax], nbest_len int32 [B, K], nbest_score f32 [B, K].
+    embed f32 [V', D], pe f32 [>= Lmax, D].  Returns state."""
+    S = state
+    _want("dec_beam_prune", "topk_idx int32 and topk_logp float32 are [R, k]", topk_idx=(topk_idx, _I32, (None, None)), topk_logp=(topk_logp, _F32, tuple(topk_idx.shape)),
+          embed=(embed, _F32, (None, None)), nbest_tokens=(S["nbest_tokens"], _I32, (None, None, None)))
+    (R, k), (B, K, Lmax), D = topk_idx.shape, S["nbest_tokens"].shape, embed.shape[1]
+    if B * K != R:
+        raise ValueError("cfm.dec_beam_prune: %d rows of top-k, but the n-best buffers are for %d x %d" % (R, B, K))
+    spec = {n: (S[n], dt, (R,)) for n, dt in DEC_BEAM_STATE}
+    spec.update(tokens=(S["tokens"], _I32, (R, Lmax)), slots=(S["slots"], _I32, (R, Lmax)), x=(S["x"], _F32, (R, D)), step=(S["step"], _I32, (B,)),
+                max_len=(S["max_len"], _I32, (B,)), done=(S["done"], torch.uint8, (B,)), n_done=(S["n_done"], _I32, 1), all_done=(S["all_done"], _I32, 1),
+                nbest_len=(S["nbest_len"], _I32, (B, K)), nbest_score=(S["nbest_score"], _F32, (B, K)), pe=(pe, _F32, (None, D)))
+    _want("dec_beam_prune", "an entry of state (R = %d rows, B = %d, K = %d, Lmax = %d, D = %d)" % (R, B, K, Lmax, D), **spec)
+    if pe.shape[0] < Lmax:
+        raise ValueError("cfm.dec_beam_prune: %d positions but the position table has %d rows" % (Lmax, pe.shape[0]))
+    d = _c.DecBeamPruneDesc()
+    d.topk_idx, d.topk_logp, d.embed, d.pe = _c.ptr(topk_idx), _c.ptr(topk_logp), _c.ptr(embed), _c.ptr(pe)
+    for n in ("max_len", "score", "token", "parent", "finished", "hlen", "klen", "tokens", "slots", "x", "step", "done", "n_done", "all_done", "nbest_tokens", "nbest_len",
+              "nbest_score"):
+        setattr(d, n, _c.ptr(S[n]))
+    d.B, d.K, d.k_ld, d.Lmax, d.D, d.V, d.eos = B, K, k, Lmax, D, min(int(V), embed.shape[0]), int(eos)
+    _c.call("cfm_dec_beam_prune", ctypes.byref(d))
+    return S

@@ -17,12 +17,15 @@ Forced alignment (eval mode only, cfm_ctc_align in csrc/ctc.hip; the reference h
 token's first and last encoder frame and its log-probability along the best single alignment, and that alignment's score.  Blank is 0 as in the
 loss, and there is no dropout, for the same reason as in decoding.
 """
+import math
+
 import torch
 import torch.nn as nn
 
 import cfm
 import token_log
 from cfm import packing
+from greedy import _Search, _nbest_lists
 
 
 class CTCDecoder(nn.Module):
@@ -496,3 +499,166 @@ class AttentionRescorer:
                 rows.append((tk, f, {"left": l, "right": rt, "first_pass": sc}) if return_details else (tk, f))
             out.append(rows)
         return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------------------
+# Autoregressive beam search with the attention decoder: the incremental path (a device K/V cache)
+# ------------------------------------------------------------------------------------------------------------------------------------------------
+class _DecoderWeights:
+    """What greedy._Search asks of a head, for a search that has no predictor and no joint: the identity of the decoder's weights (with the
+    precision mode: the packs differ)."""
+
+    def __init__(self, owner, dec):
+        self.owner, self.dec = owner, dec
+
+    def weights_key(self):
+        return packing.weights_key(list(self.dec.parameters()), cfm.resolve_precision(self.owner).name)
+
+
+class AttentionBeamSearch(_Search):
+    """Decoding with the attention decoder alone: per utterance the `beam` best token strings with their scores s(y) = sum of the token
+    log-probabilities, eos included -- the quantity AttentionRescorer's left decoder assigns -- no length normalisation.  Specified in float64,
+    without a cache, in tests/attention_search_ref.py; a BiTransformerDecoder searches with its left decoder.  Eval mode only, device only.
+
+    The R = B * beam hypotheses are the rows of one step: per layer cfm.layernorm, the fused q|k|v product, cfm.dec_step_attn over the self-attention
+    store (append and attend in one launch), the out-projection with the residual, cfm.layernorm, the q product, cfm.dec_step_attn over the memory's
+    keys and values (projected once per utterance and layer before the loop), the out-projection, cfm.layernorm and both feed-forward products; then
+    after_norm, the output product, cfm.ctc_topk and cfm.dec_beam_prune.  Position j's K | V is written once, to slot j * R + (the row at step
+    j) of a [layers][max_len * R][2 D] store, and never moved: a row carries its ancestry as a table of slots, and pruning reorders only that.
+    `steps_per_replay` steps are captured in one HIP graph; the host reads one done flag per replay.  Weight changes, other shapes and another
+    precision mode drop the graph (greedy._Search).
+
+    search(encoder_out [B, T, D], encoder_out_lens (B,)) -> per utterance a list of (tokens, score), best first, sos / eos stripped; an utterance
+    without frames gives [([], 0.0)].  max_len: the most steps (default: the utterance's frames); a hypothesis cut off there is returned unfinished,
+    its score without an eos term.  return_device=True: (that list, (tokens int32 [B, beam, Lmax], lengths int32 [B, beam], scores f32 [B, beam])),
+    the triple AttentionRescorer.scores / rescore take.  Limits: 1 <= beam <= 16, beam <= V, B * beam <= 1024, max_len <= 1023, T <= 2048."""
+
+    _SNAP = ("score", "token", "parent", "finished", "hlen", "klen", "tokens", "slots", "x", "step", "done", "n_done", "all_done", "nbest_tokens", "nbest_len",
+             "nbest_score")      # what a step changes (packing.capture_step); the self-attention store is written at a position before it is read
+
+    def __init__(self, decoder, beam=10, sos=None, eos=None, max_len=None, steps_per_replay=8, use_graph=True):
+        if isinstance(decoder, BiTransformerDecoder):
+            left = decoder.left_decoder
+        elif isinstance(decoder, TransformerDecoder):
+            left = decoder
+        else:
+            raise TypeError("AttentionBeamSearch: decoder is a TransformerDecoder or a BiTransformerDecoder, got %s" % type(decoder).__name__)
+        super().__init__(None, None, 0, steps_per_replay, use_graph, head=_DecoderWeights(decoder, left))
+        self.decoder, self.left = decoder, left
+        V = left.output_layer.out_features
+        self.beam, self.max_len = int(beam), None if max_len is None else int(max_len)
+        self.sos = V - 1 if sos is None else int(sos)
+        self.eos = V - 1 if eos is None else int(eos)
+        if not 1 <= self.beam <= 16:
+            raise ValueError("AttentionBeamSearch: beam = %d outside 1..16 (the top-k launch returns at most 16 classes)" % self.beam)
+        if self.beam > V:
+            raise ValueError("AttentionBeamSearch: beam = %d above the vocabulary's %d classes" % (self.beam, V))
+        if self.max_len is not None and not 1 <= self.max_len <= 1023:
+            raise ValueError("AttentionBeamSearch: max_len = %d outside 1..1023" % self.max_len)
+        if not (0 <= self.sos < V and 0 <= self.eos < V) or self.steps_per_replay < 1:
+            raise ValueError("AttentionBeamSearch: sos and eos inside the vocabulary, steps_per_replay positive")
+        self._S = self._key = None
+        self.steps = self.replays = 0
+
+    def _state(self, B, T, Lmax, dev, prec):
+        left, K = self.left, self.beam
+        R, D, n_layers = B * K, left.output_layer.in_features, len(left.decoders)
+        z = lambda dt, *s: torch.zeros(s, dtype=dt, device=dev)
+        f32, i32, u8 = torch.float32, torch.int32, torch.uint8
+        return dict(lens=z(i32, B), max_len=z(i32, B), score=z(f32, R), token=z(i32, R), parent=z(i32, R), finished=z(u8, R), hlen=z(i32, R), klen=z(i32, R),
+                    tokens=z(i32, R, Lmax), slots=z(i32, R, Lmax), x=z(f32, R, D), step=z(i32, B), done=z(u8, B), n_done=z(i32, 1), all_done=z(i32, 1),
+                    nbest_tokens=z(i32, B, K, Lmax), nbest_len=z(i32, B, K), nbest_score=z(f32, B, K), rows=torch.full((1,), R, dtype=i32, device=dev),
+                    self_kv=z(prec.act_dtype, n_layers, Lmax * R, 2 * D), mem_kv=z(prec.act_dtype, n_layers, B * T, 2 * D))
+
+    def _begin(self, S, lens, Lmax):
+        """The live set [sos] at score 0 in the first row of every utterance (the other rows: score -inf), an utterance without frames done."""
+        K, dev = self.beam, lens.device
+        R, D = S["score"].shape[0], S["x"].shape[1]
+        S["score"].fill_(float("-inf"))
+        S["score"][::K] = 0.0
+        S["token"].fill_(self.sos)
+        S["parent"].copy_(torch.arange(R, dtype=torch.int32, device=dev))
+        for k in ("finished", "hlen", "tokens", "slots", "step", "nbest_tokens", "nbest_len"):
+            S[k].zero_()
+        S["klen"].fill_(1)
+        S["slots"][:, 0] = S["parent"]
+        S["max_len"].copy_(lens.clamp(max=Lmax) if self.max_len is None else torch.where(lens > 0, torch.full_like(lens, Lmax), torch.zeros_like(lens)))
+        done = lens <= 0
+        S["done"].copy_(done.to(torch.uint8))
+        S["n_done"].copy_(done.sum().to(torch.int32).reshape(1))
+        S["all_done"].copy_((S["n_done"] >= lens.shape[0]).to(torch.int32))
+        S["nbest_score"].fill_(float("-inf"))
+        S["nbest_score"][:, 0] = torch.where(done, 0.0, float("-inf"))
+        E = self.left.embed[0].weight.detach()
+        S["x"].copy_((E[self.sos].double() * math.sqrt(D) + self.left.position_table(Lmax + 1)[0].double()).float().expand(R, D))
+
+    def _step(self):
+        S, left, prec = self._S, self.left, self._prec
+        K, H = self.beam, left.decoders[0].self_attn.num_heads
+        x = S["x"]
+        (R, D), dev, adt = x.shape, x.device, prec.act_dtype
+        B, T = S["lens"].shape[0], S["mem_kv"].shape[1] // S["lens"].shape[0]
+        buf = lambda tag, dt, *shape: cfm.scratch("att_search_" + tag, int(torch.Size(shape).numel()), dt, dev).view(*shape)
+        xn, ctx, q = buf("xn", adt, R, D), buf("ctx", adt, R, D), buf("q", adt, R, D)
+        qkv = buf("qkv", adt, R, 3 * D)
+        for l, layer in enumerate(left.decoders):
+            pk = packing.pack_mhsa(layer.self_attn, prec, False)
+            cfm.layernorm(x, layer.norm1.weight, layer.norm1.bias, out1=xn)
+            cfm.gemm(xn, pk.qkv_w, bias=pk.qkv_b, w_lo=pk.qkv_w_lo, out=qkv)
+            cfm.dec_step_attn(qkv[:, :D], S["self_kv"][l], H, klen=S["klen"], slot=S["slots"], kv_new=qkv[:, D:], out=ctx)
+            cfm.gemm(ctx, pk.out_w, bias=pk.out_b, w_lo=pk.out_w_lo, residual=x, out=x)
+            pk = packing.pack_mhsa(layer.src_attn, prec, False)
+            cfm.layernorm(x, layer.norm2.weight, layer.norm2.bias, out1=xn)
+            cfm.gemm(xn, pk.q_w, bias=pk.q_b, w_lo=pk.q_w_lo, out=q)
+            cfm.dec_step_attn(q, S["mem_kv"][l], H, klen=S["lens"], out=ctx, group=K, stride=T)
+            cfm.gemm(ctx, pk.out_w, bias=pk.out_b, w_lo=pk.out_w_lo, residual=x, out=x)
+            pf = packing.pack_ffn(layer.feed_forward, prec)
+            cfm.layernorm(x, layer.norm3.weight, layer.norm3.bias, out1=xn)
+            hid = cfm.gemm(xn, pf.w1, bias=pf.b1, w_lo=pf.w1_lo, act=cfm.ACT_RELU, out=buf("hid", adt, R, pf.w1.shape[0]))
+            cfm.gemm(hid, pf.w2, bias=pf.b2, w_lo=pf.w2_lo, residual=x, out=x)
+        cfm.layernorm(x, left.after_norm.weight, left.after_norm.bias, out1=xn)
+        po = left._output_pack(prec)
+        logits = cfm.gemm(xn, po.w, bias=po.b, w_lo=po.w_lo, out=buf("logits", torch.float32, R, po.Vp))
+        top = (buf("topk_idx", torch.int32, 1, R, K), buf("topk_logp", torch.float32, 1, R, K), buf("lse", torch.float32, 1, R))
+        cfm.ctc_topk(logits.view(1, R, po.Vp), po.V, S["rows"], K, out=top)                 # the one top-k of the library: B = 1, T = R
+        cfm.dec_beam_prune(top[0].view(R, K), top[1].view(R, K), S, left.embed[0].weight.detach(), self._pe, self.eos, po.V)
+
+    def _run_steps(self):
+        for _ in range(self.steps_per_replay):
+            self._step()
+
+    @torch.no_grad()
+    def search(self, encoder_out, encoder_out_lens, return_device=False):
+        if self.decoder.training:
+            raise RuntimeError("AttentionBeamSearch is an eval-mode operation (the decoder's dropout would be live); call .eval()")
+        if encoder_out.dim() != 3 or encoder_out.shape[2] != self.left.output_layer.in_features:
+            raise ValueError("AttentionBeamSearch: encoder_out must be [B, T, %d], got %s" % (self.left.output_layer.in_features, tuple(encoder_out.shape)))
+        (B, T, D), K, dev = encoder_out.shape, self.beam, encoder_out.device
+        Lmax = max(T, 1) if self.max_len is None else self.max_len
+        if B < 1 or B * K > 1024:
+            raise ValueError("AttentionBeamSearch: B * beam = %d * %d rows, one step takes 1..1024" % (B, K))
+        if Lmax > 1023:
+            raise ValueError("AttentionBeamSearch: max_len defaults to the %d encoder frames, above the 1023 steps a search takes; pass max_len" % T)
+        if T > 2048:
+            raise ValueError("AttentionBeamSearch: %d encoder frames, cfm_dec_step_attn attends to at most 2048 keys" % T)
+        cfm.require_hip(encoder_out)
+        prec = cfm.resolve_precision(self.decoder)
+        self._sync_weights()
+        key = (B, T, K, Lmax, str(dev), prec.name)
+        if self._key != key:                                                            # new buffers: the graph holds their addresses
+            self._S, self._key = self._state(B, T, Lmax, dev, prec), key
+            self._drop()
+        S, self._prec = self._S, prec
+        self._pe = self.left.position_table(Lmax + 1)
+        lens = torch.as_tensor(encoder_out_lens).to(device=dev, dtype=torch.int32).reshape(B).clamp(0, T)
+        S["lens"].copy_(lens)
+        if T > 0:
+            mem = encoder_out.detach().to(torch.float32).reshape(B * T, D).contiguous()
+            for l, layer in enumerate(self.left.decoders):                                  # the memory's keys and values: once per utterance and layer
+                pk = packing.pack_mhsa(layer.src_attn, prec, False)
+                cfm.gemm(mem, pk.qkv_w[D:], bias=pk.qkv_b[D:], w_lo=None if pk.qkv_w_lo is None else pk.qkv_w_lo[D:], out=S["mem_kv"][l])
+        self._begin(S, lens, Lmax)
+        self.replays = 0 if bool(S["all_done"]) else self._replay(S, self._SNAP, lambda: bool(S["all_done"]), Lmax // self.steps_per_replay + 2)
+        out = _nbest_lists(S["nbest_tokens"], S["nbest_len"], S["nbest_score"], range(B))
+        self.steps = int(S["step"].max()) + 1 if self.replays else 0
+        return (out, (S["nbest_tokens"].clone(), S["nbest_len"].clone(), S["nbest_score"].clone())) if return_device else out

@@ -128,11 +128,13 @@ def replay_until_done(graph, run, done, limit):
 
 
 class _Search:
-    """The host bookkeeping of the four searches.  Descriptor(s) and graph hold addresses of packs and state buffers: whoever replaces either
+    """The host bookkeeping of the searches.  Descriptor(s) and graph hold addresses of packs and state buffers: whoever replaces either
     calls _drop().  A subclass has _run_steps() (the steps of one replay) and keeps its descriptor in _desc, or one per step parity in _descs."""
 
-    def __init__(self, predictor, joint, blank, steps_per_replay, use_graph, even_steps=False):
-        self.predictor, self.joint, self._head = predictor, joint, _Head(predictor, joint)
+    def __init__(self, predictor, joint, blank, steps_per_replay, use_graph, even_steps=False, head=None):
+        """head: what stands for the weights -- an object with weights_key(); default: _Head(predictor, joint).  A search without a predictor and
+        a joint (decoder.AttentionBeamSearch) passes its own, None for both, and guards train mode itself."""
+        self.predictor, self.joint, self._head = predictor, joint, _Head(predictor, joint) if head is None else head
         self.blank, self.use_graph, self._key_w, self._enc_keep = int(blank), bool(use_graph), None, None
         self.steps_per_replay = int(steps_per_replay) + (int(steps_per_replay) & 1 if even_steps else 0)       # even: the beam searches' step parity
         self._drop()

@@ -311,8 +311,9 @@ class OfflineRecognizer:
     score / score_audio recognise and then score the hypotheses against known transcripts on the device (metrics.py, cfm.edit_distance).
     attention: a decoder.TransformerDecoder / BiTransformerDecoder (or a ready decoder.AttentionRescorer) on the same encoder; recognize(beam=k,
     rescore=True), recognize_ctc(beam=k, rescore=True) and their _audio forms then re-rank each n-best list by the attention decoder
-    (first_pass_weight, reverse_weight: AttentionRescorer's) and return (tokens, final score) pairs, best first.  attention=None changes nothing and
-    adds no launch."""
+    (first_pass_weight, reverse_weight: AttentionRescorer's) and return (tokens, final score) pairs, best first.  recognize_attention /
+    recognize_attention_audio decode with the attention decoder itself (decoder.AttentionBeamSearch).  attention=None changes nothing and adds no
+    launch."""
 
     def __init__(self, encoder, predictor, joint, blank=0, n_steps=64, fbank=None, ctc=None, attention=None, first_pass_weight=0.5, reverse_weight=0.0,
                  **search_kw):
@@ -325,7 +326,7 @@ class OfflineRecognizer:
         self.fbank = fbank
         self.encoder_out = self.encoder_out_lens = self._beam = None
         self._resamplers = {}                                # sample_rate -> resample.Resampler, made on first use
-        self.rescorer = None
+        self.rescorer = self._attention = None               # _attention: decoder.AttentionBeamSearch, made on the first recognize_attention
         if attention is not None:
             import decoder
             self.rescorer = attention if isinstance(attention, decoder.AttentionRescorer) else decoder.AttentionRescorer(
@@ -429,6 +430,34 @@ class OfflineRecognizer:
     def recognize_ctc_audio(self, samples, lengths, beam=None, sample_rate=None, rescore=False):
         self._check_rescore(rescore, beam, "recognize_ctc_audio")
         return self.recognize_ctc(*self._features(samples, lengths, sample_rate), beam=beam, rescore=rescore)
+
+    @torch.no_grad()
+    def recognize_attention(self, feats, lengths, beam=10, rescore=False):
+        """The attention decoder's own hypotheses of the same ragged batch: forward_utterances once, then decoder.AttentionBeamSearch (the left
+        decoder searches) over groups of at most 1024 // beam utterances -- per utterance a list of (tokens, score), best first; an utterance with
+        no encoder frame gives [([], 0.0)].  rescore=True (a recogniser built with reverse_weight > 0, i.e. with a right decoder): the search's
+        device n-best triple goes through the rescorer, so the right decoder re-ranks the left decoder's search; (tokens, final score)."""
+        if self.rescorer is None:
+            raise RuntimeError("OfflineRecognizer.recognize_attention: the recogniser was built without an attention decoder (attention=None)")
+        if rescore and not self.rescorer.reverse_weight > 0.0:
+            raise ValueError("OfflineRecognizer.recognize_attention: rescore=True re-ranks the left decoder's search by the right decoder; build the "
+                             "recogniser with reverse_weight > 0 (a BiTransformerDecoder)")
+        import decoder
+        self.encoder_out, self.encoder_out_lens = self.encoder.forward_utterances(feats, lengths)
+        if self._attention is None or self._attention.beam != int(beam):
+            self._attention = decoder.AttentionBeamSearch(self.rescorer.decoder, beam=beam, sos=self.rescorer.sos, eos=self.rescorer.eos)
+        group, out, triples = max(1, 1024 // self._attention.beam), [], []
+        for b0 in range(0, self.encoder_out.shape[0], group):
+            nbest, triple = self._attention.search(self.encoder_out[b0:b0 + group], self.encoder_out_lens[b0:b0 + group], return_device=True)
+            out.extend(nbest)
+            triples.append(triple)
+        if not rescore:
+            return out
+        triple = triples[0] if len(triples) == 1 else tuple(torch.cat([t[k] for t in triples], 0) for k in range(3))
+        return self.rescorer.rescore(self.encoder_out, self.encoder_out_lens, triple)
+
+    def recognize_attention_audio(self, samples, lengths, beam=10, sample_rate=None, rescore=False):
+        return self.recognize_attention(*self._features(samples, lengths, sample_rate), beam=beam, rescore=rescore)
 
     @torch.no_grad()
     def align(self, feats, lengths, labels, label_lengths, return_path=False, head="ctc"):

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CFM_VERSION 307 /* 0.3.7: removed cfm_dwconv_bn_train (cfm_dwconv_bn_train_groups with one group), cfm_dwconv_bn_train_bwd and cfm_dwconv_bn_train_bwd_acc (cfm_dwconv_bn_train_bwd_groups with one group; its accumulate argument) and cfm_layernorm_bwd (cfm_layernorm_bwd_fused with the descriptor's optional fields zero). 0.3.6 (additive): cfm_route, cfm_encoder_layer_route (the route cfm_encoder_layer_forward would take, asked on the host), cfm_ffsplit_max_rows. 0.3.5: removed the attention input stage of the conv-in chain (cfm_rowchain_desc.att_*, cfm_layer_scratch.vt and its row stride) and the transposed-value output of the macaron chain's tail that fed it (three cfm_rowchain_desc fields); psum_out chains take no head. 0.3.4: removed cfm_ctc_nll_train (cfm_ctc_nll_train_groups is the training forward), cfm_ctc_grad requires beta (alpha is no longer overwritten), removed cfm_rnnt_desc.sweep / cfm_rnnt_packed_desc.sweep (the LDS recursion is the only one). 0.3.3: removed cfm_encoder_layer_train_forward / _backward (the stack entry points run a single block), cfm_ffn_train_forward / _supported, cfm_ffn_train_desc, cfm_pack_ffn_fragments, cfm_layer_train_weights.*_w1f / *_w2f, cfm_layer_train_io.B / T / attn_mask / am_sb / am_sq / side_stream and cfm_encoder_train_backward's n_scratch. 0.3.2 (additive, same number): packed RNN-T lattices (cfm_lattice, cfm_rnnt_packed_desc, cfm_rnnt_packed_nll / _grad, cfm_joint_act_packed / _bwd). 0.3.2 (additive, same number): the RNN-T loss (cfm_rnnt_desc, cfm_rnnt_nll, cfm_rnnt_grad) and the transducer joint's activation backward (cfm_joint_act_bwd). 0.3.2: cfm_rowchain_desc.cin_* (the conv-in chain as the input stage of the next launch). 0.3.1: row chains at D = 512, cfm_rowchain_desc.psum_out / psum_in (feed-forward split over workgroup pairs), cfm_conv12_relu at C = 512. 0.3.0: row groups in the train entry points (cfm_train_group, cfm_layer_train_io.n_groups), cfm_gemm_tn_group + deferred weight gradients, cfm_encoder_train_forward / _backward (the whole stack from one host call). 0.2.3: cfm_ffn_split, cfm_layer_scratch.psum (the feed-forward split over FF for few rows). 0.2.2: cfm_ctc_nll_train / cfm_ctc_grad take a beta buffer (both recursions in one launch); GEMM tile ids 9-11 (K groups). 0.2.1: fused front-end (cfm_conv12_relu); attention stage of the conv-in chain (cfm_rowchain_desc.att_*, cfm_layer_scratch.vt). 0.2.0: training entry points */
+#define CFM_VERSION 307 /* 0.3.7: removed cfm_dwconv_bn_train (cfm_dwconv_bn_train_groups with one group), cfm_dwconv_bn_train_bwd and cfm_dwconv_bn_train_bwd_acc (cfm_dwconv_bn_train_bwd_groups with one group; its accumulate argument) and cfm_layernorm_bwd (cfm_layernorm_bwd_fused with the descriptor's optional fields zero). 0.3.7 (additive, same number): the attention decoder's beam search (cfm_dec_step_attn_desc, cfm_dec_step_attn, cfm_dec_beam_prune_desc, cfm_dec_beam_prune). 0.3.6 (additive): cfm_route, cfm_encoder_layer_route (the route cfm_encoder_layer_forward would take, asked on the host), cfm_ffsplit_max_rows. 0.3.5: removed the attention input stage of the conv-in chain (cfm_rowchain_desc.att_*, cfm_layer_scratch.vt and its row stride) and the transposed-value output of the macaron chain's tail that fed it (three cfm_rowchain_desc fields); psum_out chains take no head. 0.3.4: removed cfm_ctc_nll_train (cfm_ctc_nll_train_groups is the training forward), cfm_ctc_grad requires beta (alpha is no longer overwritten), removed cfm_rnnt_desc.sweep / cfm_rnnt_packed_desc.sweep (the LDS recursion is the only one). 0.3.3: removed cfm_encoder_layer_train_forward / _backward (the stack entry points run a single block), cfm_ffn_train_forward / _supported, cfm_ffn_train_desc, cfm_pack_ffn_fragments, cfm_layer_train_weights.*_w1f / *_w2f, cfm_layer_train_io.B / T / attn_mask / am_sb / am_sq / side_stream and cfm_encoder_train_backward's n_scratch. 0.3.2 (additive, same number): packed RNN-T lattices (cfm_lattice, cfm_rnnt_packed_desc, cfm_rnnt_packed_nll / _grad, cfm_joint_act_packed / _bwd). 0.3.2 (additive, same number): the RNN-T loss (cfm_rnnt_desc, cfm_rnnt_nll, cfm_rnnt_grad) and the transducer joint's activation backward (cfm_joint_act_bwd). 0.3.2: cfm_rowchain_desc.cin_* (the conv-in chain as the input stage of the next launch). 0.3.1: row chains at D = 512, cfm_rowchain_desc.psum_out / psum_in (feed-forward split over workgroup pairs), cfm_conv12_relu at C = 512. 0.3.0: row groups in the train entry points (cfm_train_group, cfm_layer_train_io.n_groups), cfm_gemm_tn_group + deferred weight gradients, cfm_encoder_train_forward / _backward (the whole stack from one host call). 0.2.3: cfm_ffn_split, cfm_layer_scratch.psum (the feed-forward split over FF for few rows). 0.2.2: cfm_ctc_nll_train / cfm_ctc_grad take a beta buffer (both recursions in one launch); GEMM tile ids 9-11 (K groups). 0.2.1: fused front-end (cfm_conv12_relu); attention stage of the conv-in chain (cfm_rowchain_desc.att_*, cfm_layer_scratch.vt). 0.2.0: training entry points */
 
 typedef void* cfm_stream_t;
 
@@ -1681,6 +1681,86 @@ int cfm_lsm_grad(const cfm_lsm_grad_desc* d, cfm_stream_t stream);
  *   batch > 0 (the reference's default), else the number of targets >= 0 (normalize_length), at least 1: a call without one valid target
  *   gives 0 where the reference gives 0 / 0 -- the one deliberate difference. */
 int cfm_lsm_reduce(const float* loss, const int32_t* target, int32_t M, int32_t batch, float* out, cfm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Autoregressive beam search with the attention decoder (csrc/attn_search.hip; the definition is tests/attention_search_ref.py in float64, the
+ * host side decoder.AttentionBeamSearch).  R = B * K rows: utterance b owns rows b*K .. b*K + K - 1, best hypothesis first.
+ *
+ * cfm_dec_step_attn: ONE query per (row, head) against keys and values that live in a store addressed through an indirection:
+ *     s_j = (q_r,h . K[slot(r, j)]_h) / sqrt(dk),  p = softmax over j < klen(r),  out_r,h = sum_j p_j V[slot(r, j)]_h        (all in f32)
+ *   q [R, >= D] rows ldq apart, out [R, D] rows ldo apart, store [slots, 2 D] dense (row s: K | V of one position), all of io_dtype
+ *   (f32, bf16 or fp16; the fp32 precision mode keeps the store in f32).  D = H * dk.
+ *   slot(r, j): the table form reads slot[r * slot_ld + j] (int32; several rows may name the same slots: shared ancestors); with slot NULL
+ *   it is (r / group) * stride + j -- cross-attention over [owners, stride] memory rows, `group` rows per owner.  A slot is clamped into
+ *   [0, slots) before it is used, so no table content makes the kernel leave the store.
+ *   klen(r): klen[r / klen_group] (int32), or, with klen NULL, step[0] + 1 -- a device step counter, so that a captured graph needs no
+ *   host argument per step.  Clamped into [0, cap]; cap is the declared capacity (cap <= slot_ld, resp. cap <= stride).  klen = 0 writes zeros.
+ *   kv_new (optional, table form only; [R, 2 D] rows ld_new apart): this step's own K | V.  It is the key of position klen - 1: the kernel
+ *   stores it to slot(r, klen - 1) -- exactly that one store row per row r, head slice by head slice -- and attends to it from kv_new itself,
+ *   so append and attend are one launch and nothing is read back.  Nothing is stored for a row with klen = 0.
+ *   One wavefront per (row, head): scores with one key per lane into LDS, wave maximum and sum, then the context with dk / 4 lanes across a
+ *   value row and 64 / (dk / 4) keys in flight, reduced through LDS in a fixed order.  No atomics: the same input gives the same bits.
+ *   Limits (CFM_ERR_ARG): D % 8 == 0, dk % 4 == 0, dk <= 128, 1 <= cap <= 2048, ldq, ldo, ld_new multiples of 4, 16-byte aligned bases. */
+typedef struct {
+    const void* q;
+    void* store;
+    const int32_t* slot;
+    const int32_t* klen;
+    const int32_t* step;
+    const void* kv_new;
+    void* out;
+    int64_t ldq, ld_new, ldo, slots;
+    int32_t R, H, dk, cap, slot_ld, group, stride, klen_group, io_dtype;
+} cfm_dec_step_attn_desc;
+int cfm_dec_step_attn(const cfm_dec_step_attn_desc* d, cfm_stream_t stream);
+
+/* cfm_dec_beam_prune: one search step's pruning and bookkeeping, one workgroup per utterance, no host synchronisation.
+ *   topk_idx int32 / topk_logp f32 [R, k_ld]: per row its K best classes and their log-probabilities (cfm_ctc_topk on the step's f32 logits:
+ *   descending, the lower class first among equal values).  Utterance b at step i = step[b], unless done[b]:
+ *     candidates  an unfinished row offers its K classes at score[row] + logp (one f32 add); a finished row (its last token was eos)
+ *                 offers itself alone, score unchanged
+ *     order       higher score first, then the better-ranked parent, then the lower class; the best K are kept in that order (a row whose
+ *                 score is -inf -- an unused beam slot of step 0 -- never beats a real candidate)
+ *     per kept    token, score, finished, parent (a global row index), hlen (tokens before eos), klen (the next step's key count),
+ *                 tokens int32 [R, Lmax] (the strings, eos included) and slots int32 [R, Lmax] (the ancestry table of cfm_dec_step_attn's
+ *                 self-attention store) both reordered by parent IN PLACE, tokens[row][i] = the new token, slots[row][i + 1] =
+ *                 (i + 1) * R + row: position j's K | V is written once, to slot j * R + (the row at step j), and never moved
+ *     x           f32 [R, D]: the next step's decoder input rows embed[token] * sqrt(D) + pe[i + 1] (in double, rounded once)
+ *     done        when every kept hypothesis is finished or i + 1 == max_len[b] (int32 [B], 1 <= max_len[b] <= Lmax): done[b] = 1, n_done += 1,
+ *                 all_done[0] = 1 once n_done reaches B, and the n-best buffers nbest_tokens int32 [B, K, Lmax] (eos stripped; only the
+ *                 first nbest_len entries are written), nbest_len int32 [B, K], nbest_score f32 [B, K] are written -- once; a kept
+ *                 entry of score -inf has length 0
+ *   INVARIANT: the rows of a done utterance keep valid indices for every later step a captured graph still runs: parent = the row itself,
+ *   step, klen and tokens frozen, x rewritten from the frozen token and position; slots frozen too, but for the entry at the last position i,
+ *   which is set to i * R + row when the utterance becomes done (kept siblings share their parent's slot at position i; a frozen row keeps
+ *   appending its K | V at that position every later step, so the slot must be its own: no two rows write one slot).  Such a row attends
+ *   within its own table; its outputs are ignored.  Plain C++ and vector stores only.
+ *   1 <= K <= 16, K <= k_ld, K <= V, 1 <= Lmax <= 1023, B * K <= 1024; embed f32 [V, D], pe f32 [>= Lmax, D]. */
+typedef struct {
+    const int32_t* topk_idx;
+    const float* topk_logp;
+    const float* embed;
+    const float* pe;
+    const int32_t* max_len;
+    float* score;
+    int32_t* token;
+    int32_t* parent;
+    uint8_t* finished;
+    int32_t* hlen;
+    int32_t* klen;
+    int32_t* tokens;
+    int32_t* slots;
+    float* x;
+    int32_t* step;
+    uint8_t* done;
+    int32_t* n_done;
+    int32_t* all_done;
+    int32_t* nbest_tokens;
+    int32_t* nbest_len;
+    float* nbest_score;
+    int32_t B, K, k_ld, Lmax, D, V, eos;
+} cfm_dec_beam_prune_desc;
+int cfm_dec_beam_prune(const cfm_dec_beam_prune_desc* d, cfm_stream_t stream);
 
 #ifdef __cplusplus
 }
