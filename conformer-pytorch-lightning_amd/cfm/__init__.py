@@ -321,6 +321,12 @@ class DecBeamPruneDesc(ctypes.Structure):
                 [(n, c_i32) for n in ("B", "K", "k_ld", "Lmax", "D", "V", "eos")])
 
 
+class CtcPrefixDesc(ctypes.Structure):
+    _fields_ = ([(n, c_p) for n in ("x", "state", "psi", "topk_idx", "topk_logp", "token", "hlen", "finished", "step", "done", "lens", "parent", "tokens", "out_idx", "out_logp",
+                                    "cand_psi")] +
+                [(n, c_i32) for n in ("B", "K", "P", "T", "V", "Lmax", "blank", "eos")] + [("ctc_weight", c_f)])
+
+
 class FfnSplitDesc(ctypes.Structure):
     _fields_ = [("x", c_p), ("psum", c_p), ("psum_b2", c_p), ("psum_splits", c_i32), ("psum_alpha", c_f), ("ln1_g", c_p), ("ln1_b", c_p), ("ln2_g", c_p),
                 ("ln2_b", c_p), ("rows_out", c_p), ("rows2_out", c_p), ("ln_g", c_p), ("ln_b", c_p), ("w1", c_p), ("b1", c_p), ("N1", c_i32), ("act", c_i32),
@@ -355,7 +361,7 @@ for _c_name, _cls in dict(
         cfm_greedy_chunk_desc=GreedyChunkDesc, cfm_ctc_greedy_desc=CtcGreedyDesc, cfm_ctc_beam_desc=CtcBeamDesc, cfm_ctc_align_desc=CtcAlignDesc, cfm_edit_distance_desc=EditDistanceDesc, cfm_rnnt_beam_desc=RnntBeamDesc, cfm_rnnt_beam_stream_desc=RnntBeamStreamDesc, cfm_fbank_desc=FbankDesc, cfm_resample_desc=ResampleDesc,
         cfm_resample_bank=ResampleBank, cfm_resample_group_desc=ResampleGroupDesc, cfm_spec_augment_desc=SpecAugmentDesc,
         cfm_rescore_prep_desc=RescorePrepDesc, cfm_token_logprob_desc=TokenLogprobDesc, cfm_rescore_combine_desc=RescoreCombineDesc, cfm_lsm_loss_desc=LsmLossDesc, cfm_lsm_grad_desc=LsmGradDesc,
-        cfm_dec_step_attn_desc=DecStepAttnDesc, cfm_dec_beam_prune_desc=DecBeamPruneDesc,
+        cfm_dec_step_attn_desc=DecStepAttnDesc, cfm_dec_beam_prune_desc=DecBeamPruneDesc, cfm_ctc_prefix_desc=CtcPrefixDesc,
         cfm_ffn_split_desc=FfnSplitDesc, cfm_layer_scratch=LayerScratch, cfm_layer_io=LayerIO).items():
     _cls._c_name_ = _c_name
 PROTOTYPES = (
@@ -473,6 +479,9 @@ PROTOTYPES = (
     ("cfm_lsm_reduce", c_int, c_p, c_p, c_i32, c_i32, c_p, c_p),
     ("cfm_dec_step_attn", c_int, P(DecStepAttnDesc), c_p),
     ("cfm_dec_beam_prune", c_int, P(DecBeamPruneDesc), c_p),
+    ("cfm_ctc_logprob_t", c_int, c_p, c_i64, c_i32, c_i32, c_i32, c_p, c_p, c_p),
+    ("cfm_ctc_prefix_score", c_int, P(CtcPrefixDesc), c_p),
+    ("cfm_ctc_prefix_advance", c_int, P(CtcPrefixDesc), c_p),
 )
 
 _lib = None

@@ -6,7 +6,7 @@ import torch
 
 import cfm as _c
 
-__all__ = ["dec_step_attn", "dec_beam_prune", "rescore_prep", "token_logprob", "rescore_combine", "lsm_loss", "lsm_grad", "lsm_reduce", "lstm_forward", "lstm_backward", "fbank", "fbank_stream", "fbank_stream_ragged", "resample", "resample_stream", "resample_group", "spec_augment", "stream_prep", "stream_advance", "dwconv_causal_bn_silu", "conv_cache_update", "dropout_rows", "dropout_mask", "set_deterministic", "gemm_tn", "gemm_tn_group", "layernorm_bwd", "glu_bwd", "dwconv_bn_train", "dwconv_bn_train_bwd", "dwconv_bn_train_groups", "dwconv_bn_train_bwd_groups", "col2im_relu_bwd", "conv1_wgrad", "attention_bwd", "attention_group", "attention_bwd_group",
+__all__ = ["dec_step_attn", "dec_beam_prune", "ctc_logprob_t", "ctc_prefix_score", "ctc_prefix_advance", "rescore_prep", "token_logprob", "rescore_combine", "lsm_loss", "lsm_grad", "lsm_reduce", "lstm_forward", "lstm_backward", "fbank", "fbank_stream", "fbank_stream_ragged", "resample", "resample_stream", "resample_group", "spec_augment", "stream_prep", "stream_advance", "dwconv_causal_bn_silu", "conv_cache_update", "dropout_rows", "dropout_mask", "set_deterministic", "gemm_tn", "gemm_tn_group", "layernorm_bwd", "glu_bwd", "dwconv_bn_train", "dwconv_bn_train_bwd", "dwconv_bn_train_groups", "dwconv_bn_train_bwd_groups", "col2im_relu_bwd", "conv1_wgrad", "attention_bwd", "attention_group", "attention_bwd_group",
            "ctc_nll_train_groups", "ctc_grad", "rnnt_nll", "rnnt_grad", "joint_act_bwd", "rnnt_nll_packed", "rnnt_align", "rnnt_align_packed", "joint_act_packed", "joint_act_packed_bwd", "ffn_split", "adam_step", "adam_clip_step", "sumsq", "scratch_stats",
            "gemm", "ffn_fused", "ffn_fused_supported", "rowchain", "rowchain_supported", "rowchain_pair_supported", "layernorm", "attention", "kv_cache_pack", "dwconv_bn_silu", "conv1_relu", "conv1_relu_mma_supported", "conv12_relu", "conv12_supported", "ctc_nll", "ctc_topk", "ctc_greedy", "ctc_greedy_state", "ctc_prefix_beam", "ctc_align", "edit_distance", "joint_act", "valid_mask", "chunk_mask",
            "attn_mask_combine", "cast", "add_rows", "scratch", "prof_enable", "prof_reset", "prof_table", "as_u8_mask"]
@@ -1919,3 +1919,65 @@ def dec_beam_prune(topk_idx, topk_logp, state, embed, pe, eos, V):
     d.B, d.K, d.k_ld, d.Lmax, d.D, d.V, d.eos = B, K, k, Lmax, D, min(int(V), embed.shape[0]), int(eos)
     _c.call("cfm_dec_beam_prune", ctypes.byref(d))
     return S
+
+
+def ctc_logprob_t(logits, V, lens, out=None):
+    """log_softmax of the CTC head's f32 logits [B, T, ld >= V], CLASS-major: f32 [B, V, Tp], Tp = T rounded up to 4 (include/cfm.h
+    cfm_ctc_logprob_t).  lens int32 [B]; elements at t >= lens[b] are not written (out: the tensor to write into; a fresh one is zero-filled)."""
+    _c.require_hip(logits, lens, out)
+    B, T = _ctc_logits("ctc_logprob_t", logits)
+    V, Tp = int(V), (T + 3) // 4 * 4
+    if out is None:
+        out = torch.zeros((B, V, Tp), dtype=torch.float32, device=logits.device)
+    _want("ctc_logprob_t", "out is [B, V, T rounded up to 4]", out=(out, _F32, (B, V, Tp)), **_i32(B, lens=lens))
+    _c.call("cfm_ctc_logprob_t", _c.ptr(logits), logits.stride(1), B, T, V, _c.ptr(lens), _c.ptr(out))
+    return out
+
+
+def _ctc_prefix_desc(op, x, T, ctc_state, psi, state, K, ctc_weight, blank, eos):
+    """The operands cfm_ctc_prefix_score and cfm_ctc_prefix_advance share: x f32 [B, V, Tp], ctc_state f32 [2, R, Tp, 2], psi f32 [R], and of the
+    search state `state` (cfm.dec_beam_prune's dict) token, hlen, finished [R], step, done, lens [B]."""
+    S = state
+    _want(op, "x is the [B, V, Tp] of ctc_logprob_t", x=(x, _F32, (None, None, None)))
+    B, V, Tp = x.shape
+    K, T = int(K), int(T)
+    R = B * K
+    if (T + 3) // 4 * 4 != Tp:
+        raise ValueError("cfm.%s: T = %d frames, but x has Tp = %d columns per class (T rounded up to 4)" % (op, T, Tp))
+    _want(op, "ctc_state is [2, R, Tp, 2] and psi [R] with R = B * K = %d * %d" % (B, K), ctc_state=(ctc_state, _F32, (2, R, Tp, 2)), psi=(psi, _F32, (R,)),
+          token=(S["token"], _I32, (R,)), hlen=(S["hlen"], _I32, (R,)), finished=(S["finished"], torch.uint8, (R,)), step=(S["step"], _I32, (B,)),
+          done=(S["done"], torch.uint8, (B,)), lens=(S["lens"], _I32, (B,)))
+    d = _c.CtcPrefixDesc()
+    d.x, d.state, d.psi = _c.ptr(x), _c.ptr(ctc_state), _c.ptr(psi)
+    for n in ("token", "hlen", "finished", "step", "done", "lens"):
+        setattr(d, n, _c.ptr(S[n]))
+    d.B, d.K, d.T, d.V, d.blank, d.eos, d.ctc_weight = B, K, T, V, int(blank), int(eos), float(ctc_weight)
+    return d, R
+
+
+def ctc_prefix_score(x, T, ctc_state, psi, topk_idx, topk_logp, state, K, ctc_weight, blank, eos, out=None):
+    """One step's CTC prefix scores of every row's P attention candidates and the K best combined offers per row (include/cfm.h
+    cfm_ctc_prefix_score).  topk_idx int32 / topk_logp f32 [R, P].  Returns (out_idx int32, out_logp f32, cand_psi f32), each [R, K] -- the
+    first two are cfm.dec_beam_prune's top-k lists (out: such a triple to write into)."""
+    d, R = _ctc_prefix_desc("ctc_prefix_score", x, T, ctc_state, psi, state, K, ctc_weight, blank, eos)
+    _want("ctc_prefix_score", "topk_idx int32 and topk_logp float32 are [R, P]", topk_idx=(topk_idx, _I32, (R, None)), topk_logp=(topk_logp, _F32, tuple(topk_idx.shape)))
+    if out is None:
+        out = (torch.empty((R, d.K), dtype=torch.int32, device=x.device), torch.empty((R, d.K), dtype=torch.float32, device=x.device),
+               torch.empty((R, d.K), dtype=torch.float32, device=x.device))
+    _want("ctc_prefix_score", "out must be (out_idx int32, out_logp float32, cand_psi float32), each [R, K]", out_idx=(out[0], _I32, (R, d.K)), out_logp=(out[1], _F32, (R, d.K)),
+          cand_psi=(out[2], _F32, (R, d.K)))
+    d.P = topk_idx.shape[1]
+    d.topk_idx, d.topk_logp, d.out_idx, d.out_logp, d.cand_psi = _c.ptr(topk_idx), _c.ptr(topk_logp), _c.ptr(out[0]), _c.ptr(out[1]), _c.ptr(out[2])
+    _c.call("cfm_ctc_prefix_score", ctypes.byref(d))
+    return out
+
+
+def ctc_prefix_advance(x, T, ctc_state, psi, state, K, blank, eos):
+    """After cfm.dec_beam_prune: the CTC state and psi of every kept unfinished row, from its parent's, into the other half of ctc_state
+    (include/cfm.h cfm_ctc_prefix_advance).  state: the prune's dict (parent, token, tokens, hlen, finished, step, done, lens are read)."""
+    d, R = _ctc_prefix_desc("ctc_prefix_advance", x, T, ctc_state, psi, state, K, 1.0, blank, eos)
+    _want("ctc_prefix_advance", "parent is [R] and tokens [R, Lmax]", parent=(state["parent"], _I32, (R,)), tokens=(state["tokens"], _I32, (R, None)))
+    d.P = d.K
+    d.parent, d.tokens, d.Lmax = _c.ptr(state["parent"]), _c.ptr(state["tokens"]), state["tokens"].shape[1]
+    _c.call("cfm_ctc_prefix_advance", ctypes.byref(d))
+    return ctc_state, psi

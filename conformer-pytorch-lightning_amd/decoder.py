@@ -535,6 +535,7 @@ class AttentionBeamSearch(_Search):
 
     _SNAP = ("score", "token", "parent", "finished", "hlen", "klen", "tokens", "slots", "x", "step", "done", "n_done", "all_done", "nbest_tokens", "nbest_len",
              "nbest_score")      # what a step changes (packing.capture_step); the self-attention store is written at a position before it is read
+    _who = "AttentionBeamSearch"
 
     def __init__(self, decoder, beam=10, sos=None, eos=None, max_len=None, steps_per_replay=8, use_graph=True):
         if isinstance(decoder, BiTransformerDecoder):
@@ -592,6 +593,9 @@ class AttentionBeamSearch(_Search):
         E = self.left.embed[0].weight.detach()
         S["x"].copy_((E[self.sos].double() * math.sqrt(D) + self.left.position_table(Lmax + 1)[0].double()).float().expand(R, D))
 
+    def _prepare(self, S, encoder_out, T):
+        """What a subclass derives from the encoder output once per search, before _begin (JointBeamSearch: the CTC head's log-probabilities)."""
+
     def _step(self):
         S, left, prec = self._S, self.left, self._prec
         K, H = self.beam, left.decoders[0].self_attn.num_heads
@@ -619,9 +623,14 @@ class AttentionBeamSearch(_Search):
         cfm.layernorm(x, left.after_norm.weight, left.after_norm.bias, out1=xn)
         po = left._output_pack(prec)
         logits = cfm.gemm(xn, po.w, bias=po.b, w_lo=po.w_lo, out=buf("logits", torch.float32, R, po.Vp))
+        self._select(logits, po, buf)
+
+    def _select(self, logits, po, buf):
+        """The step's f32 logits [R, Vp] to the pruned beam: cfm.ctc_topk and cfm.dec_beam_prune (JointBeamSearch scores the candidates in between)."""
+        S, K, R = self._S, self.beam, logits.shape[0]
         top = (buf("topk_idx", torch.int32, 1, R, K), buf("topk_logp", torch.float32, 1, R, K), buf("lse", torch.float32, 1, R))
         cfm.ctc_topk(logits.view(1, R, po.Vp), po.V, S["rows"], K, out=top)                 # the one top-k of the library: B = 1, T = R
-        cfm.dec_beam_prune(top[0].view(R, K), top[1].view(R, K), S, left.embed[0].weight.detach(), self._pe, self.eos, po.V)
+        cfm.dec_beam_prune(top[0].view(R, K), top[1].view(R, K), S, self.left.embed[0].weight.detach(), self._pe, self.eos, po.V)
 
     def _run_steps(self):
         for _ in range(self.steps_per_replay):
@@ -630,17 +639,17 @@ class AttentionBeamSearch(_Search):
     @torch.no_grad()
     def search(self, encoder_out, encoder_out_lens, return_device=False):
         if self.decoder.training:
-            raise RuntimeError("AttentionBeamSearch is an eval-mode operation (the decoder's dropout would be live); call .eval()")
+            raise RuntimeError("%s is an eval-mode operation (the decoder's dropout would be live); call .eval()" % self._who)
         if encoder_out.dim() != 3 or encoder_out.shape[2] != self.left.output_layer.in_features:
-            raise ValueError("AttentionBeamSearch: encoder_out must be [B, T, %d], got %s" % (self.left.output_layer.in_features, tuple(encoder_out.shape)))
+            raise ValueError("%s: encoder_out must be [B, T, %d], got %s" % (self._who, self.left.output_layer.in_features, tuple(encoder_out.shape)))
         (B, T, D), K, dev = encoder_out.shape, self.beam, encoder_out.device
         Lmax = max(T, 1) if self.max_len is None else self.max_len
         if B < 1 or B * K > 1024:
-            raise ValueError("AttentionBeamSearch: B * beam = %d * %d rows, one step takes 1..1024" % (B, K))
+            raise ValueError("%s: B * beam = %d * %d rows, one step takes 1..1024" % (self._who, B, K))
         if Lmax > 1023:
-            raise ValueError("AttentionBeamSearch: max_len defaults to the %d encoder frames, above the 1023 steps a search takes; pass max_len" % T)
+            raise ValueError("%s: max_len defaults to the %d encoder frames, above the 1023 steps a search takes; pass max_len" % (self._who, T))
         if T > 2048:
-            raise ValueError("AttentionBeamSearch: %d encoder frames, cfm_dec_step_attn attends to at most 2048 keys" % T)
+            raise ValueError("%s: %d encoder frames, cfm_dec_step_attn attends to at most 2048 keys" % (self._who, T))
         cfm.require_hip(encoder_out)
         prec = cfm.resolve_precision(self.decoder)
         self._sync_weights()
@@ -657,8 +666,100 @@ class AttentionBeamSearch(_Search):
             for l, layer in enumerate(self.left.decoders):                                  # the memory's keys and values: once per utterance and layer
                 pk = packing.pack_mhsa(layer.src_attn, prec, False)
                 cfm.gemm(mem, pk.qkv_w[D:], bias=pk.qkv_b[D:], w_lo=None if pk.qkv_w_lo is None else pk.qkv_w_lo[D:], out=S["mem_kv"][l])
+        self._prepare(S, encoder_out, T)
         self._begin(S, lens, Lmax)
         self.replays = 0 if bool(S["all_done"]) else self._replay(S, self._SNAP, lambda: bool(S["all_done"]), Lmax // self.steps_per_replay + 2)
         out = _nbest_lists(S["nbest_tokens"], S["nbest_len"], S["nbest_score"], range(B))
         self.steps = int(S["step"].max()) + 1 if self.replays else 0
         return (out, (S["nbest_tokens"].clone(), S["nbest_len"].clone(), S["nbest_score"].clone())) if return_device else out
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------------------
+# Joint CTC/attention decoding: the attention beam search with the CTC head's prefix probabilities (csrc/ctc_prefix.hip)
+# ------------------------------------------------------------------------------------------------------------------------------------------------
+class _JointWeights(_DecoderWeights):
+    """Both heads' weights: a change to the CTC projection drops the graph as a change to the decoder does."""
+
+    def __init__(self, owner, dec, ctc):
+        super().__init__(owner, dec)
+        self.ctc = ctc
+
+    def weights_key(self):
+        return super().weights_key() + packing.weights_key(list(self.ctc.parameters()), cfm.resolve_precision(self.ctc).name)
+
+
+class JointBeamSearch(AttentionBeamSearch):
+    """Joint CTC/attention decoding: AttentionBeamSearch in which every candidate extension is also scored by the CTC head's prefix probability.
+    An unfinished hypothesis g offers class c at
+
+        (1 - ctc_weight) * logp_att(c) + ctc_weight * (psi(g.c) - psi(g)),      psi(h) = log P_ctc(the output starts with h),  psi(g.eos) = log P_ctc(g)
+
+    so a finished hypothesis scores (1 - ctc_weight) * (the attention decoder's s(y)) + ctc_weight * (minus the CTC loss of y).  Specified in float64
+    in tests/ctc_prefix_ref.py; include/cfm.h states the kernels.  Each row's `pre_beam` best attention classes are its candidates (beam <= pre_beam
+    <= min(16, V); default min(16, V, ceil(1.5 beam))); per row the `beam` best by the combined offer go to the prune, which is unchanged.
+
+    Once per search the CTC head's logits (CTCDecoder's packed projection, no dropout) become class-major log-probabilities (cfm.ctc_logprob_t,
+    B * V * Tp * 4 bytes); per step cfm.ctc_topk (k = pre_beam), cfm.ctc_prefix_score, cfm.dec_beam_prune and cfm.ctc_prefix_advance, which carries
+    each kept row's CTC state (2 * R * Tp * 8 bytes, double-buffered by step parity) from its parent's.  search() returns what
+    AttentionBeamSearch.search returns, the scores being the combined ones; there is no length normalisation.  eos != blank."""
+
+    _SNAP = AttentionBeamSearch._SNAP + ("ctc_state", "ctc_psi")
+    _who = "JointBeamSearch"
+
+    def __init__(self, decoder, ctc, beam=10, ctc_weight=0.3, pre_beam=None, blank=0, sos=None, eos=None, max_len=None, steps_per_replay=8, use_graph=True):
+        super().__init__(decoder, beam=beam, sos=sos, eos=eos, max_len=max_len, steps_per_replay=steps_per_replay, use_graph=use_graph)
+        if not isinstance(ctc, CTCDecoder):
+            raise TypeError("JointBeamSearch: ctc is a CTCDecoder, got %s" % type(ctc).__name__)
+        V = self.left.output_layer.out_features
+        if ctc.ctc_lo.out_features != V:
+            raise ValueError("JointBeamSearch: the CTC head has %d classes, the attention decoder %d" % (ctc.ctc_lo.out_features, V))
+        if ctc.ctc_lo.in_features != self.left.output_layer.in_features:
+            raise ValueError("JointBeamSearch: the CTC head reads %d features, the attention decoder's memory has %d" %
+                             (ctc.ctc_lo.in_features, self.left.output_layer.in_features))
+        self.ctc, self.ctc_weight, self.blank = ctc, float(ctc_weight), int(blank)
+        if not 0.0 < self.ctc_weight <= 1.0:
+            raise ValueError("JointBeamSearch: ctc_weight = %r outside (0, 1] (0 is AttentionBeamSearch)" % (ctc_weight,))
+        self.pre_beam = min(16, V, -(-3 * self.beam // 2)) if pre_beam is None else int(pre_beam)
+        if not self.beam <= self.pre_beam <= min(16, V):
+            raise ValueError("JointBeamSearch: pre_beam = %d outside beam = %d .. min(16, V) = %d" % (self.pre_beam, self.beam, min(16, V)))
+        if not 0 <= self.blank < V or self.blank == self.eos:
+            raise ValueError("JointBeamSearch: blank = %d inside the vocabulary and different from eos = %d" % (self.blank, self.eos))
+        self._head = _JointWeights(decoder, self.left, ctc)
+
+    def _state(self, B, T, Lmax, dev, prec):
+        S = super()._state(B, T, Lmax, dev, prec)
+        V, R, Tp = self.left.output_layer.out_features, B * self.beam, (T + 3) // 4 * 4
+        z = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)
+        S.update(ctc_x=z(B, V, Tp), ctc_state=z(2, R, Tp, 2), ctc_psi=z(R))
+        return S
+
+    def search(self, encoder_out, encoder_out_lens, return_device=False):
+        if self.ctc.training:
+            raise RuntimeError("JointBeamSearch is an eval-mode operation (inference only); call .eval() on the CTC head")
+        return super().search(encoder_out, encoder_out_lens, return_device)
+
+    def _prepare(self, S, encoder_out, T):
+        if T > 0:
+            pk = self.ctc._weights(cfm.resolve_precision(self.ctc))
+            cfm.ctc_logprob_t(CTCDecoder._logits(encoder_out.detach(), pk), pk.V, S["lens"], out=S["ctc_x"])
+
+    def _begin(self, S, lens, Lmax):
+        """Every row starts as the empty prefix, in half 0 (step 0): gamma_n = -inf, gamma_b the running sum of the blank column, psi = 0."""
+        super()._begin(S, lens, Lmax)
+        T = S["mem_kv"].shape[1] // lens.shape[0]
+        S["ctc_psi"].zero_()
+        if T > 0:
+            # the running sum also covers columns t >= lens[b] of ctc_x, which hold zeros or an earlier search's values, and half 1 is left as it
+            # was: the kernels read frames t < lens[b] of the half the step counter names, nothing else
+            S["ctc_state"][0, :, :, 0] = float("-inf")
+            S["ctc_state"][0, :, :T, 1] = S["ctc_x"][:, self.blank, :T].cumsum(-1).repeat_interleave(self.beam, 0)
+
+    def _select(self, logits, po, buf):
+        S, K, P, R = self._S, self.beam, self.pre_beam, logits.shape[0]
+        T = S["mem_kv"].shape[1] // S["lens"].shape[0]
+        top = (buf("pre_idx", torch.int32, 1, R, P), buf("pre_logp", torch.float32, 1, R, P), buf("lse", torch.float32, 1, R))
+        cfm.ctc_topk(logits.view(1, R, po.Vp), po.V, S["rows"], P, out=top)
+        out = (buf("topk_idx", torch.int32, R, K), buf("topk_logp", torch.float32, R, K), buf("cand_psi", torch.float32, R, K))
+        cfm.ctc_prefix_score(S["ctc_x"], T, S["ctc_state"], S["ctc_psi"], top[0].view(R, P), top[1].view(R, P), S, K, self.ctc_weight, self.blank, self.eos, out=out)
+        cfm.dec_beam_prune(out[0], out[1], S, self.left.embed[0].weight.detach(), self._pe, self.eos, po.V)
+        cfm.ctc_prefix_advance(S["ctc_x"], T, S["ctc_state"], S["ctc_psi"], S, K, self.blank, self.eos)

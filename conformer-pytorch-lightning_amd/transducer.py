@@ -312,8 +312,8 @@ class OfflineRecognizer:
     attention: a decoder.TransformerDecoder / BiTransformerDecoder (or a ready decoder.AttentionRescorer) on the same encoder; recognize(beam=k,
     rescore=True), recognize_ctc(beam=k, rescore=True) and their _audio forms then re-rank each n-best list by the attention decoder
     (first_pass_weight, reverse_weight: AttentionRescorer's) and return (tokens, final score) pairs, best first.  recognize_attention /
-    recognize_attention_audio decode with the attention decoder itself (decoder.AttentionBeamSearch).  attention=None changes nothing and adds no
-    launch."""
+    recognize_attention_audio decode with the attention decoder itself (decoder.AttentionBeamSearch); with ctc= as well, recognize_joint /
+    recognize_joint_audio decode with both heads (decoder.JointBeamSearch).  attention=None changes nothing and adds no launch."""
 
     def __init__(self, encoder, predictor, joint, blank=0, n_steps=64, fbank=None, ctc=None, attention=None, first_pass_weight=0.5, reverse_weight=0.0,
                  **search_kw):
@@ -327,6 +327,7 @@ class OfflineRecognizer:
         self.encoder_out = self.encoder_out_lens = self._beam = None
         self._resamplers = {}                                # sample_rate -> resample.Resampler, made on first use
         self.rescorer = self._attention = None               # _attention: decoder.AttentionBeamSearch, made on the first recognize_attention
+        self._joint = None                                   # decoder.JointBeamSearch, made on the first recognize_joint
         if attention is not None:
             import decoder
             self.rescorer = attention if isinstance(attention, decoder.AttentionRescorer) else decoder.AttentionRescorer(
@@ -458,6 +459,41 @@ class OfflineRecognizer:
 
     def recognize_attention_audio(self, samples, lengths, beam=10, sample_rate=None, rescore=False):
         return self.recognize_attention(*self._features(samples, lengths, sample_rate), beam=beam, rescore=rescore)
+
+    @torch.no_grad()
+    def recognize_joint(self, feats, lengths, beam=10, ctc_weight=0.3, rescore=False):
+        """Joint CTC/attention decoding of the same ragged batch: forward_utterances once, then decoder.JointBeamSearch (the left decoder's beam
+        search, every candidate also scored by the CTC head's prefix probability) over groups of at most 1024 // beam utterances -- per utterance a
+        list of (tokens, combined score), best first; an utterance with no encoder frame gives [([], 0.0)].  rescore=True: as recognize_attention,
+        the right decoder re-ranks the search's n-best triple (a recogniser built with reverse_weight > 0)."""
+        self._check_joint(rescore, "recognize_joint")
+        import decoder
+        if self._joint is None or (self._joint.beam, self._joint.ctc_weight) != (int(beam), float(ctc_weight)):
+            self._joint = decoder.JointBeamSearch(self.rescorer.decoder, self.ctc, beam=beam, ctc_weight=ctc_weight, blank=self.blank, sos=self.rescorer.sos,
+                                                  eos=self.rescorer.eos)
+        self.encoder_out, self.encoder_out_lens = self.encoder.forward_utterances(feats, lengths)
+        group, out, triples = max(1, 1024 // self._joint.beam), [], []
+        for b0 in range(0, self.encoder_out.shape[0], group):
+            nbest, triple = self._joint.search(self.encoder_out[b0:b0 + group], self.encoder_out_lens[b0:b0 + group], return_device=True)
+            out.extend(nbest)
+            triples.append(triple)
+        if not rescore:
+            return out
+        triple = triples[0] if len(triples) == 1 else tuple(torch.cat([t[k] for t in triples], 0) for k in range(3))
+        return self.rescorer.rescore(self.encoder_out, self.encoder_out_lens, triple)
+
+    def _check_joint(self, rescore, who):
+        if self.ctc is None:
+            raise RuntimeError("OfflineRecognizer.%s: the recogniser was built without a CTC head (ctc=None)" % who)
+        if self.rescorer is None:
+            raise RuntimeError("OfflineRecognizer.%s: the recogniser was built without an attention decoder (attention=None)" % who)
+        if rescore and not self.rescorer.reverse_weight > 0.0:
+            raise ValueError("OfflineRecognizer.%s: rescore=True re-ranks the left decoder's search by the right decoder; build the recogniser with "
+                             "reverse_weight > 0 (a BiTransformerDecoder)" % who)
+
+    def recognize_joint_audio(self, samples, lengths, beam=10, ctc_weight=0.3, sample_rate=None, rescore=False):
+        self._check_joint(rescore, "recognize_joint_audio")
+        return self.recognize_joint(*self._features(samples, lengths, sample_rate), beam=beam, ctc_weight=ctc_weight, rescore=rescore)
 
     @torch.no_grad()
     def align(self, feats, lengths, labels, label_lengths, return_path=False, head="ctc"):

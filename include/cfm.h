@@ -1762,6 +1762,69 @@ typedef struct {
 } cfm_dec_beam_prune_desc;
 int cfm_dec_beam_prune(const cfm_dec_beam_prune_desc* d, cfm_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Joint CTC/attention decoding: the CTC prefix scorer of the attention beam search (csrc/ctc_prefix.hip; the definition is
+ * tests/ctc_prefix_ref.py in float64, the host side decoder.JointBeamSearch).  x[t, c] = log_softmax(CTC logits of utterance b)[t, c] for
+ * t < n = lens[b] (clamped to [0, T]); (+) is logaddexp.  A hypothesis g carries gamma_n[t], gamma_b[t] -- the log-probabilities of the
+ * alignments of exactly g to frames 0..t that end in its last token / in blank -- and psi(g), the log-probability that the output starts with
+ * g.  The empty g: gamma_n = -inf, gamma_b[t] = sum_{tau <= t} x[tau, blank], psi = 0.  For a candidate c (not blank, not eos), `last` the
+ * last token of g:
+ *     phi[t]      = gamma_b[t] if c == last, else gamma_n[t] (+) gamma_b[t]
+ *     psi(g.c)    = init (+) (+)_{t=1..n-1} (phi[t-1] + x[t, c]),   init = x[0, c] if g is empty, else -inf
+ *     gamma_n'[0] = init, gamma_b'[0] = -inf,  gamma_n'[t] = (gamma_n'[t-1] (+) phi[t-1]) + x[t, c],
+ *     gamma_b'[t] = (gamma_n'[t-1] (+) gamma_b'[t-1]) + x[t, blank]
+ *   psi(g.eos) = gamma_n[n-1] (+) gamma_b[n-1], the CTC log-likelihood of g itself; psi(g.blank) = -inf, and the state of g.blank is -inf
+ *   throughout.  The increment delta = psi(g.c) - psi(g) is -inf whenever either term is -inf: no NaN is produced.
+ * Layouts: Tp = T rounded up to 4.  x f32 [B, V, Tp], CLASS-major: a candidate's column is contiguous in t.  state f32 [2][R, Tp, 2]: two
+ * halves of (gamma_n, gamma_b) pairs, R = B * K rows, utterance b owning rows b*K .. b*K + K - 1 as in cfm_dec_beam_prune; psi f32 [R].
+ * The half that holds the hypotheses a step scores is step[b] & 1 (step: the prune's per-utterance counter), so a captured graph needs no
+ * host argument per step.  No atomics, fixed reduction orders: the same input gives the same bits.  Plain C++ and vector stores only.
+ *
+ * cfm_ctc_logprob_t: once per search.  logits f32 [B*T, ld] as for cfm_ctc_topk (ld >= V, ld % 4 == 0); per frame t < lens[b] the
+ *   max-shifted f32 log-sum-exp, x[b, c, t] = (logits - max) - log(sum).  Elements at t >= lens[b], the padding t >= T included, are NOT
+ *   TOUCHED, and nothing below reads them.  1 <= T <= 2048, B <= 65535, logits and x 16-byte aligned. */
+int cfm_ctc_logprob_t(const float* logits, int64_t ld, int32_t B, int32_t T, int32_t V, const int32_t* lens, float* x, cfm_stream_t stream);
+
+/* cfm_ctc_prefix_score: once per step, before the prune, one workgroup per row.  topk_idx int32 / topk_logp f32 [R, P]: the row's P best
+ *   attention classes (cfm_ctc_topk with k = P) and their log-probabilities.  Candidate j of an unfinished row of an utterance that is not
+ *   done offers  (1 - ctc_weight) * topk_logp[j] + ctc_weight * delta(g . topk_idx[j])  (the attention term is dropped, not multiplied by
+ *   zero, at ctc_weight = 1; a NaN offer counts as -inf).  g's last token is token[r], g is empty when hlen[r] <= 0, psi(g) is psi[r].
+ *   The K best of the P offers are written in descending order, the lower class first among equal values, as out_idx int32 / out_logp f32
+ *   [R, K] -- what cfm_dec_beam_prune takes as its top-k lists -- with cand_psi f32 [R, K] = psi(g.c) of each.  Every row of a finished
+ *   hypothesis, of a done utterance or of an utterance without frames is written as (eos, -inf, -inf): the prune ignores it.
+ *   A class index read from topk_idx is clamped into [0, V) before use.  One wavefront per candidate reduces over t: the maximum, then the
+ *   shifted sum, each lane over t = 1 + lane, 65 + lane, ... and the lanes in wave_sum's order.
+ * cfm_ctc_prefix_advance: once per step, after the prune (step[b] then counts the steps taken), one lane per row.  For every kept
+ *   unfinished row r of an utterance that is not done: gamma_n', gamma_b' and psi of (parent[r], token[r]) from the parent's state in half
+ *   (step[b] + 1) & 1, written to row r of half step[b] & 1 and to psi[r]; frames t >= lens[b] are not touched.  The parent's last token is
+ *   tokens[r][hlen[r] - 2] (tokens int32 [R, Lmax], reordered by the prune; hlen[r] >= 1 is the new length, 1: the parent was empty).
+ *   parent[r] is clamped into the utterance's rows, token[r] into [0, V), hlen[r] into [1, Lmax].  Finished rows, rows of done utterances and
+ *   the half that was read stay bit-unchanged.
+ * Limits (CFM_ERR_ARG): 1 <= K <= P <= 16, P <= V, 1 <= T <= 2048, R = B * K <= 1024, eos != blank, both in [0, V), ctc_weight in (0, 1],
+ *   x and state 16-byte aligned. */
+typedef struct {
+    const float* x;
+    float* state;
+    float* psi;
+    const int32_t* topk_idx;
+    const float* topk_logp;
+    const int32_t* token;
+    const int32_t* hlen;
+    const uint8_t* finished;
+    const int32_t* step;
+    const uint8_t* done;
+    const int32_t* lens;
+    const int32_t* parent;
+    const int32_t* tokens;
+    int32_t* out_idx;
+    float* out_logp;
+    float* cand_psi;
+    int32_t B, K, P, T, V, Lmax, blank, eos;
+    float ctc_weight;
+} cfm_ctc_prefix_desc;
+int cfm_ctc_prefix_score(const cfm_ctc_prefix_desc* d, cfm_stream_t stream);
+int cfm_ctc_prefix_advance(const cfm_ctc_prefix_desc* d, cfm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
